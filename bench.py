@@ -6,15 +6,20 @@ Workload (BASELINE.json configs[1], per GPU): 1 000 000 synthetic UDP payloads o
 generator: include/kmp_synth.h, seed 1234.  A "step" is one full pass of the hot path over that
 arena (scan kernel + partial-count reduce, then the cross-GPU count sum), inputs resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (N > 1)
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
+Rank 0 prints ONE JSON line (contract in the task statement) with an extra object:
   roofline     -- HBM roofline of the scan kernel: algorithmic bytes (sum of payload lengths of
                   one launch) / average launch duration measured with HIP events on the launch
-                  stream, against 8.0 TB/s.
-  cpu_baseline -- the CPU restatement of openmp_data.c:126-178 (oracle/, "port") timed on the
-                  host cores on the same arena (rank 0, N == 1 only).
+                  stream during the timed steps, against 8.0 TB/s.
+A plain run stops there.  --full adds, after the timed steps (rank 0, N == 1 only):
+  cpu_baseline  -- the CPU restatement of openmp_data.c:126-178 (oracle/, "port") timed on the
+                   host cores on the same arena (--no-cpu-baseline leaves it out);
+  extra_configs -- the other BASELINE configs and the dense-candidate / adversarial inputs, each
+                   count-checked and timed on its own (--no-extra leaves them out).
+--dump-outputs DIR writes what the last timed step computed, the per-pattern match counts after
+the reduce over ranks, as DIR/counts.npy (float64, one entry per pattern).
 """
 import argparse
 import json
@@ -277,9 +282,12 @@ def main() -> None:
     ap.add_argument("--packets-per-gpu", type=int, default=1_000_000)
     ap.add_argument("--depth", type=int, default=0, help="chunk loads in flight per wavefront (0 = library default)")
     ap.add_argument("--blocks-per-cu", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra_configs legs (Zipf lengths, strings.txt fused, pcap fixture, "
-                    "dense-candidate and adversarial inputs) that follow the timed headline region at N = 1")
+    ap.add_argument("--full", action="store_true", help="after the headline, also time the CPU baseline and the extra_configs legs "
+                    "(N = 1); a plain run measures the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the per-pattern counts of the last timed step to DIR/counts.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra_configs legs (Zipf lengths, strings.txt fused, "
+                    "pcap fixture, dense-candidate and adversarial inputs) that follow the timed headline region at N = 1")
     ap.add_argument("--extra-passes", type=int, default=60)
     ap.add_argument("--cpu-reps", type=int, default=3)
     ap.add_argument("--force-dist", action="store_true", help="rehearsal: create the process group and run the all-reduce path "
@@ -287,6 +295,8 @@ def main() -> None:
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to rehearse "
                     "the multi-rank code path on a box with fewer GPUs than ranks)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))          # before anything touches the GPU
@@ -414,11 +424,14 @@ def main() -> None:
         planted_all = int(t.item())
     if total != planted_all:
         raise SystemExit(f"rank {rank}: reduced count {total} != planted {planted_all}")
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "counts.npy"), np.array([total], dtype=np.float64))
 
     # ---- CPU baseline + sample parity (rank 0, N == 1) -------------------------------------------
     cpu = None
     sample97 = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import oracle
         o = oracle.load()
         host = d_arena.cpu().numpy()
@@ -477,7 +490,7 @@ def main() -> None:
     # ---- the other BASELINE configs, after the timed headline region (rank 0, N == 1) -----------------
     extra = None
     extra_error = None
-    if rank == 0 and world == 1 and not args.no_extra:
+    if args.full and rank == 0 and world == 1 and not args.no_extra:
         headline = (d_arena, d_off, d_len, n, PAYLOAD_LEN)
         del d_arena, d_off, d_len
         # a failing leg (a count check included) must not cost the headline line, which has been measured and checked by now:

@@ -17,6 +17,7 @@ Outputs:
   fixture_counts.json             per fixture x mode: packets, payloads, bytes, counts[97], sha256 of payload stream
   kat_matcher.json                known-answer vectors for kmp_matcher / kmp_prefix from B
   kat_extract.json                known-answer vectors for dump_UDP_packet / dump_TCP_packet from B
+  ref_random.json                 B's answers on the seeded random inputs of tests/test_oracle.py
 """
 import hashlib
 import json
@@ -30,6 +31,9 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 
 from oracle import load_ref, read_pcap_py, tokenize_patterns_py  # noqa: E402
+
+sys.path.insert(0, os.path.dirname(HERE))
+import test_oracle  # noqa: E402  (the seeded inputs of its reference tests)
 
 REF = "/root/reference"
 FIXTURES = ["udp.pcap", "tcp.pcap", "udp_1000.pcap", "big_udp.pcap", "very_big_udp.pcap"]
@@ -207,6 +211,26 @@ def main() -> None:
     with open(os.path.join(HERE, "kat_extract.json"), "w") as f:
         json.dump(ext, f, indent=0)
     print("kat_extract:", len(ext), "vectors")
+
+    # ---- B's answers on the seeded random inputs of tests/test_oracle.py -------------------------
+    T = test_oracle
+    cases = list(T.matcher_cases())
+    frames = list(T.udp_frames())
+    host, off, ln, planted = T.bench_arena()
+    counts = [ref.count_arena(host, off, ln, p, 2)[0] for p in T.BENCH_ARENA_PATTERNS]
+    assert counts[0] == planted, (counts, planted)
+    rr = {
+        "source": "reference object code (oracle/_ref/libkmpref.so) via make_goldens.py",
+        "matcher": {"inputs_sha256": T.inputs_sha256(b for case in cases for b in case),
+                    "count": [ref.kmp_matcher(t, p) for t, p in cases], "prefix": [ref.kmp_prefix(p) for _, p in cases]},
+        "extract_udp": {"inputs_sha256": T.inputs_sha256(frames), "result": [ref.dump(f, None, "udp") for f in frames]},
+        "bench_arena": {"arena_sha256": hashlib.sha256(host.tobytes()).hexdigest(),
+                        "patterns": [p.decode() for p in T.BENCH_ARENA_PATTERNS], "count": counts},
+    }
+    with open(os.path.join(HERE, "ref_random.json"), "w") as f:
+        json.dump(rr, f, separators=(",", ":"))
+        f.write("\n")
+    print("ref_random:", len(cases), "matcher cases,", len(frames), "frames, bench arena counts", counts)
 
 
 if __name__ == "__main__":

@@ -3,16 +3,19 @@
 1. against the committed golden vectors (tests/golden/*.json: SURVEY App. B counts from the
    reference's compiled serial.c, and known-answer vectors from the reference's object code);
 2. against an independent naive definition (SURVEY App. A, second form);
-3. when oracle/_ref/libkmpref.so travelled with the repo, directly against the reference's own
-   kmp_matcher / kmp_prefix / dump_*_packet on fresh random inputs.
+3. against the reference's own kmp_matcher / kmp_prefix / dump_*_packet on seeded random inputs:
+   their stored answers (tests/golden/ref_random.json) always, the object code itself as well when
+   oracle/_ref/libkmpref.so travelled with the repo.
 """
+import hashlib
+import json
 import os
 import random
 
 import numpy as np
 import pytest
 
-from conftest import DATA
+from conftest import DATA, GOLDEN
 from oracle import read_pcap_py, tokenize_patterns_py
 
 
@@ -104,7 +107,13 @@ def test_random_against_naive(oracle):
         assert oracle.naive_count(text, pat) == want
 
 
-def test_random_against_reference_object_code(oracle, reflib):
+# ---- against the reference's own object code -------------------------------------------------------------
+# The inputs are seeded.  tests/golden/ref_random.json holds what the reference's object code answered on them
+# (tests/golden/make_goldens.py), so the oracle is held to those answers everywhere; where oracle/_ref/libkmpref.so
+# was built, the object code is also asked again and must still give the stored answers.
+
+def matcher_cases():
+    """The 3000 (text, pattern) pairs of test_random_against_reference_object_code."""
     rng = random.Random(11)
     for _ in range(3000):
         alpha = rng.choice([b"ab", b"abc", b"a\0b", bytes(range(256))])
@@ -112,12 +121,11 @@ def test_random_against_reference_object_code(oracle, reflib):
         m = rng.randrange(1, 20)
         text = bytes(rng.choice(alpha) for _ in range(n))
         pat = bytes(rng.choice([b for b in alpha if b]) for _ in range(m))
-        assert oracle.kmp_matcher(text, pat) == reflib.kmp_matcher(text, pat)
-        assert oracle.kmp_prefix(pat) == reflib.kmp_prefix(pat)
+        yield text, pat
 
 
-def test_extract_against_reference_object_code(oracle, reflib):
-    """Random frames on the UDP path, where the reference is bounds-checked (packet_dumping.h:94-128)."""
+def udp_frames():
+    """The 3000 random frames of test_extract_against_reference_object_code."""
     rng = random.Random(13)
     for _ in range(3000):
         n = rng.randrange(0, 120)
@@ -126,27 +134,78 @@ def test_extract_against_reference_object_code(oracle, reflib):
             frame[23] = 17
         if n > 14 and rng.random() < 0.7:
             frame[14] = 0x40 | rng.choice([0, 4, 5, 5, 5, 6, 15])
-        assert oracle.dump(bytes(frame), None, "udp") == reflib.dump(bytes(frame), None, "udp")
+        yield bytes(frame)
 
 
-def test_reference_driver_equals_oracle_on_benchmark_arena(oracle, reflib):
-    """bench.py's "reference" CPU baseline: the reference's own kmp_matcher, one call per payload of the benchmark
-    arena (1500-byte payloads, zero-padded 1504-byte slots), must count what the restatement counts."""
+BENCH_ARENA_PATTERNS = [b"NEEDLE_16B_PATRN", b"ab"]
+
+
+def bench_arena():
+    """bench.py's arena in small: 3000 payloads of 1500 B (zero-padded 1504-byte slots), seed 1234, the needle in ~10 %."""
     import multithreading_string_matching_amd as K
-    if not reflib.has_driver:
-        pytest.skip("oracle/_ref/libkmpref.so predates the baseline driver")
     n, L = 3000, 1500
-    needle = b"NEEDLE_16B_PATRN"
-    sp = K.SynthParams.make(seed=1234, needle=needle, plant_permille=100)
+    sp = K.SynthParams.make(seed=1234, needle=BENCH_ARENA_PATTERNS[0], plant_permille=100)
     off, ln, nbytes = K.arena_layout(None, L, n)
     host = np.zeros(nbytes, dtype=np.uint8)
     K.synth_fill_host(host, off, ln, sp, threads=2)
-    want, _ = oracle.count(host, off, ln, [needle, b"ab"], threads=2)
-    for pat, w in zip([needle, b"ab"], want):
-        for threads in (1, 3):
-            got, _ = reflib.count_arena(host, off, ln, pat, threads)
-            assert got == int(w)
-    assert int(want[0]) == K.synth_count_planted(sp, n, L)
+    return host, off, ln, K.synth_count_planted(sp, n, L)
+
+
+def inputs_sha256(items) -> str:
+    h = hashlib.sha256()
+    for b in items:
+        h.update(len(b).to_bytes(4, "little"))
+        h.update(b)
+    return h.hexdigest()
+
+
+@pytest.fixture(scope="module")
+def ref_random():
+    with open(os.path.join(GOLDEN, "ref_random.json")) as f:
+        return json.load(f)
+
+
+def test_random_against_reference_object_code(oracle, reflib, ref_random):
+    want = ref_random["matcher"]
+    cases = list(matcher_cases())
+    assert inputs_sha256(b for case in cases for b in case) == want["inputs_sha256"], "the seeded inputs changed"
+    assert len(want["count"]) == len(want["prefix"]) == len(cases)
+    for (text, pat), count, prefix in zip(cases, want["count"], want["prefix"]):
+        assert oracle.kmp_matcher(text, pat) == count, (text, pat)
+        assert oracle.kmp_prefix(pat) == prefix, pat
+        if reflib is not None:
+            assert reflib.kmp_matcher(text, pat) == count, (text, pat)
+            assert reflib.kmp_prefix(pat) == prefix, pat
+
+
+def test_extract_against_reference_object_code(oracle, reflib, ref_random):
+    """Random frames on the UDP path, where the reference is bounds-checked (packet_dumping.h:94-128)."""
+    want = ref_random["extract_udp"]
+    frames = list(udp_frames())
+    assert inputs_sha256(frames) == want["inputs_sha256"], "the seeded inputs changed"
+    assert len(want["result"]) == len(frames)
+    for frame, r in zip(frames, want["result"]):
+        r = tuple(r) if r is not None else None
+        assert oracle.dump(frame, None, "udp") == r, frame.hex()
+        if reflib is not None:
+            assert reflib.dump(frame, None, "udp") == r, frame.hex()
+
+
+def test_reference_driver_equals_oracle_on_benchmark_arena(oracle, reflib, ref_random):
+    """bench.py's "reference" CPU baseline: the reference's own kmp_matcher, one call per payload of the benchmark
+    arena (1500-byte payloads, zero-padded 1504-byte slots), must count what the restatement counts."""
+    want = ref_random["bench_arena"]
+    host, off, ln, planted = bench_arena()
+    assert hashlib.sha256(host.tobytes()).hexdigest() == want["arena_sha256"], "the synthetic arena changed"
+    assert [p.decode() for p in BENCH_ARENA_PATTERNS] == want["patterns"]
+    counts, _ = oracle.count(host, off, ln, BENCH_ARENA_PATTERNS, threads=2)
+    assert counts.tolist() == want["count"]
+    if reflib is not None and reflib.has_driver:
+        for pat, w in zip(BENCH_ARENA_PATTERNS, want["count"]):
+            for threads in (1, 3):
+                got, _ = reflib.count_arena(host, off, ln, pat, threads)
+                assert got == w
+    assert want["count"][0] == planted
 
 
 def test_openmp_equals_serial_on_random_arena(oracle):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Turn one round's rocprofv3 output under gpurun_out/prof/<tag>_kt (kernel trace + stats of bench.py) and the
+"""Turn one round's rocprofv3 output under profile_out/prof/<tag>_kt (kernel trace + stats of bench.py) and the
 PMC log of tools/pmc.sh into the files kept under profiles/ (kernel stats, per-launch trace of the scan kernel,
 roofline_traffic.json).  Usage: tools/collect_profiles.py <tag> <pmc-log> [round-prefix]"""
 import csv, glob, json, os, re, statistics, sys
@@ -7,7 +7,7 @@ import csv, glob, json, os, re, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag, pmc_log = sys.argv[1], sys.argv[2]
 pre = sys.argv[3] if len(sys.argv) > 3 else "r01"
-kt_dir = os.path.join(ROOT, "gpurun_out", "prof", f"{tag}_kt")
+kt_dir = os.path.join(ROOT, "profile_out", "prof", f"{tag}_kt")
 # gpurun merges every call's output into the same local directory: take the newest run
 newest = lambda pat: max(glob.glob(os.path.join(kt_dir, "**", pat), recursive=True), key=os.path.getmtime)
 stats = newest("*kernel_stats.csv")
