@@ -125,6 +125,25 @@ int   kmpgpu_host_unregister(const void *ptr);
  * 1 <= pat_len[i] <= 99, no 0x00 inside a pattern (fscanf("%s") + strlen cannot produce one). */
 int  kmpgpu_set_patterns(kmpgpu_ctx *ctx, const uint8_t *const *pat, const uint32_t *pat_len, uint32_t n_pat);
 
+/* Case-insensitive patterns (not in the reference; grep -i, Snort / Suricata "nocase").  flags[i] (NULL = all 0) carries
+ * KMPGPU_PAT_NOCASE for pattern i; every other bit is reserved and rejected with KMPGPU_EINVAL.  kmpgpu_set_patterns(...) is
+ * kmpgpu_set_patterns_flags(..., NULL, ...).  For a nocase pattern ASCII letters match either case (0x41..0x5A equal
+ * 0x61..0x7A); every other byte compares exactly (0x40 '@', 0x5B '[', 0x60 '`', 0x7B '{' and all of 0x80..0xFF: 0xC1 is not
+ * 0xE1); E_k, overlapping starts, 1..99 bytes and no 0x00 are as above.  Formally
+ *     count_nocase(payloads, p) == count(fold(payloads), fold(p)),  fold = lowercase ASCII A-Z only,
+ * and kmpgpu_scan_offsets reports the (packet, offset, pattern) of that formulation, pattern = the caller's index.  Flags are
+ * per pattern: one set may mix both kinds, and the same bytes may appear with both flags, each index counted on its own.
+ * Cost: the nocase patterns that hold an ASCII letter are counted over a folded copy of the arena that the context owns
+ * (same layout; the caller's arena is never written, kmpgpu_arena_download returns the original bytes), made once per
+ * arena -- on the context's stream at the start of the first pass after a load / attach / repack, inside kernel_ms, not a
+ * launch of kmpgpu_timing -- and grown like the other device buffers (kmpgpu_reserve sizes it when the patterns need it).
+ * All-nocase set: that fold (one read + one write of the arena), then exactly the passes of the folded set taken
+ * case-sensitively.  Mixed set: the fold, the case-sensitive passes and the nocase passes -- at least two reads of the
+ * arena per scan.  A nocase pattern without a letter is its case-sensitive self and costs nothing extra. */
+#define KMPGPU_PAT_NOCASE 1u
+int  kmpgpu_set_patterns_flags(kmpgpu_ctx *ctx, const uint8_t *const *pat, const uint32_t *pat_len,
+                               const uint32_t *flags /* NULL = all 0 */, uint32_t n_pat);
+
 /* Replaces array_of_payloads, serial.c:99,124-136: upload a host arena + index (H2D copy,
  * device copy owned by the context).  Contract: pkt_off[k] % 16 == 0 and
  * pkt_off[k] + max(16, round_up(pkt_len[k], 16)) <= arena_bytes for every k (checked): every

@@ -127,6 +127,7 @@ GPU_API = {
     "kmpgpu_host_register": (C.c_int, [C.c_void_p, C.c_size_t]),
     "kmpgpu_host_unregister": (C.c_int, [C.c_void_p]),
     "kmpgpu_set_patterns": (C.c_int, [C.c_void_p, C.POINTER(u8p), u32p, C.c_uint32]),
+    "kmpgpu_set_patterns_flags": (C.c_int, [C.c_void_p, C.POINTER(u8p), u32p, u32p, C.c_uint32]),
     "kmpgpu_load_arena": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]),
     "kmpgpu_load_frames_begin": (C.c_int, [C.c_void_p, u8p, C.c_uint64, u64p, u32p, C.c_uint64, C.c_int]),
     "kmpgpu_load_frames_finish": (C.c_int, [C.c_void_p, u64p]),

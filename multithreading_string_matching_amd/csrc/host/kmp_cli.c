@@ -17,6 +17,9 @@
  * Extension (the reference prints counts only, serial.c:163-166): with the environment variable
  * KMPGPU_OFFSETS_FILE=<path> every match is also written to <path> as "payload,offset,pattern"
  * lines (payload = index among the extracted payloads, pattern = index in the pattern file).
+ *
+ * KMPGPU_NOCASE=1: every pattern matches case-insensitively (ASCII letters; kmpgpu_set_patterns_flags), in the counts and in
+ * the offsets file alike; the report prints every token as written in the pattern file.
  */
 #include <errno.h>
 #include <pthread.h>
@@ -89,6 +92,20 @@ typedef struct shard_job {
     pthread_t thread;
 } shard_job;
 
+/* KMPGPU_NOCASE=1: every pattern is matched case-insensitively (ASCII letters, KMPGPU_PAT_NOCASE); the report prints the
+ * tokens as written. */
+static int set_patterns_env(kmpgpu_ctx *c, const uint8_t *const *pp, const uint32_t *len, uint32_t n)
+{
+    const char *e = getenv("KMPGPU_NOCASE");
+    if (!(e && e[0] == '1' && e[1] == 0) || n == 0) return kmpgpu_set_patterns(c, pp, len, n);
+    uint32_t *fl = (uint32_t *)malloc(n * sizeof *fl);
+    if (!fl) return KMPGPU_ENOMEM;
+    for (uint32_t i = 0; i < n; i++) fl[i] = KMPGPU_PAT_NOCASE;
+    const int rc = kmpgpu_set_patterns_flags(c, pp, len, fl, n);
+    free(fl);
+    return rc;
+}
+
 static void *shard_fail(shard_job *j, const char *what)
 {
     j->rc = 1; j->what = what;
@@ -100,7 +117,7 @@ static void *shard_load(void *arg)
 {
     shard_job *j = (shard_job *)arg;
     if (kmpgpu_init(&j->ctx, j->device)) return shard_fail(j, "kmpgpu_init");
-    if (kmpgpu_set_patterns(j->ctx, j->pp, j->pats->len, j->pats->n)) return shard_fail(j, "kmpgpu_set_patterns");
+    if (set_patterns_env(j->ctx, j->pp, j->pats->len, j->pats->n)) return shard_fail(j, "kmpgpu_set_patterns");
     if (j->frames) {
         /* only the bytes this shard's frames span are uploaded (kmpgpu_load_frames) */
         if (kmpgpu_load_frames(j->ctx, j->frames->bytes, j->frames->nbytes, j->frames->off + j->lo, j->frames->caplen + j->lo, j->cnt, j->tcp,

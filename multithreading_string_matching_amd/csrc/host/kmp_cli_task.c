@@ -18,6 +18,8 @@
  * work on the host.  (Uploading straight from the mapping was measured and dropped: pageable pages go through the
  * runtime's bounce buffers at 15 GB/s, and pinning them costs 55 ms per GB: profiles/r03_end_to_end_pinning_experiment.txt.)
  *
+ * KMPGPU_NOCASE=1: every pattern matches case-insensitively (ASCII letters; kmpgpu_set_patterns_flags), in both routes.
+ *
  * stdout is byte-compatible with the reference (openmp_task.c:190-196).  No CPU fallback: exit code 2
  * without a gfx950 device.
  */
@@ -119,11 +121,25 @@ static void *stage_batches(void *arg)
     }
 }
 
+/* KMPGPU_NOCASE=1: every pattern is matched case-insensitively (ASCII letters, KMPGPU_PAT_NOCASE); the report prints the
+ * tokens as written. */
+static int set_patterns_env(kmpgpu_ctx *c, const uint8_t *const *pp, const uint32_t *len, uint32_t n)
+{
+    const char *e = getenv("KMPGPU_NOCASE");
+    if (!(e && e[0] == '1' && e[1] == 0) || n == 0) return kmpgpu_set_patterns(c, pp, len, n);
+    uint32_t *fl = (uint32_t *)malloc(n * sizeof *fl);
+    if (!fl) return KMPGPU_ENOMEM;
+    for (uint32_t i = 0; i < n; i++) fl[i] = KMPGPU_PAT_NOCASE;
+    const int rc = kmpgpu_set_patterns_flags(c, pp, len, fl, n);
+    free(fl);
+    return rc;
+}
+
 static kmpgpu_ctx *make_context(const shared *sh, int device)
 {
     kmpgpu_ctx *c = NULL;
     if (kmpgpu_init(&c, device)) die_gpu("kmpgpu_init");
-    if (kmpgpu_set_patterns(c, sh->pp, sh->pats->len, sh->pats->n)) die_gpu("kmpgpu_set_patterns");
+    if (set_patterns_env(c, sh->pp, sh->pats->len, sh->pats->n)) die_gpu("kmpgpu_set_patterns");
     if (kmpgpu_set_option(c, KMPGPU_OPT_ACCUMULATE, 1) || kmpgpu_counts_reset(c)) die_gpu("kmpgpu_set_option");
     /* the device buffers of a batch, once: the first batch does not pay for a dozen allocations under the clock */
     if (kmpgpu_reserve(c, sh->batch_bytes + 64, sh->cap_pkts, sh->frames_mode ? sh->batch_bytes + 64 : 0, sh->frames_mode ? sh->cap_pkts : 0)) die_gpu("kmpgpu_reserve");

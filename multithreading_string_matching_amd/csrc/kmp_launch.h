@@ -81,6 +81,10 @@ hipError_t kmp_launch_validate(const uint64_t *pkt_off, const uint32_t *pkt_len,
 hipError_t kmp_launch_synth_fill(uint8_t *arena, const uint64_t *pkt_off, const uint32_t *pkt_len, uint64_t first_pkt_id,
                                  uint64_t n, const kmp_synth_params &sp, hipStream_t st);
 hipError_t kmp_launch_add_counts(unsigned long long *dst, const unsigned long long *src, uint32_t n, hipStream_t st);
+/* kmp_fold.hip: dst[0, bytes) = src[0, bytes) with ASCII A-Z lowercased (bytes a multiple of 16, both 16-byte aligned), and the end
+ * of the furthest slot of an index (atomicMax into *end, which the caller zeroes) */
+hipError_t kmp_launch_fold(const uint8_t *src, uint8_t *dst, uint64_t bytes, hipStream_t st);
+hipError_t kmp_launch_slot_end(const uint64_t *pkt_off, const uint32_t *pkt_len, uint64_t n, unsigned long long *end, hipStream_t st);
 hipError_t kmp_launch_fixed_index(uint64_t *pkt_off, uint32_t *pkt_len, uint64_t n, uint32_t len, uint64_t stride,
                                   hipStream_t st);
 

@@ -68,10 +68,7 @@ struct kmpgpu_ctx {
 
     /* patterns */
     uint32_t              n_pat = 0;
-    kmp_pattern_dev      *d_patterns = nullptr;
-    uint32_t             *d_ids = nullptr;          /* [n_pat]: long patterns (m >= 4) first, then short */
-    uint32_t              n_long = 0, n_short = 0;
-    /* fused multi-pattern pass: unique patterns of 2..20 bytes share one arena read */
+    kmp_pattern_dev      *d_patterns = nullptr;     /* [n_pat], file order; a KMPGPU_PAT_NOCASE pattern of set 1 is stored folded */
     /* fused multi-pattern pass: the eligible patterns in groups of at most KMP_MULTI_MAX_UNIQUE distinct ones, one read
      * of the arena per group */
     struct FusedGroup {
@@ -82,10 +79,25 @@ struct kmpgpu_ctx {
         uint32_t  words = 0, n_unique = 0, cshift = 0, bmask = 0, n_ones = 0, ones = 0, n_ids = 0;   /* cshift: a plain group's short patterns, a classed one's class shift */
         bool      classed = false;
     };
-    std::vector<FusedGroup> fused_groups;
-    uint32_t              n_multi_unique = 0;          /* distinct eligible patterns over all groups */
-    uint32_t             *d_rest_ids = nullptr;      /* [rest_long + rest_short] everything else, long first  */
-    uint32_t              rest_long = 0, rest_short = 0;
+    /* The passes of one set of patterns over one arena: sets[0] holds the case-sensitive patterns (and the KMPGPU_PAT_NOCASE ones
+     * without an ASCII letter, which are the same either way) and scans d_arena; sets[1] the other KMPGPU_PAT_NOCASE patterns,
+     * folded, and scans the folded copy d_fold.  Both write their patterns' counts, by pattern index, into the same buffer. */
+    struct PatternSet {
+        uint32_t              n = 0;                 /* patterns in the set                                     */
+        uint32_t             *d_ids = nullptr;       /* [n]: long patterns (m >= 4) first, then short           */
+        uint32_t              n_long = 0, n_short = 0;
+        std::vector<FusedGroup> fused_groups;
+        uint32_t              n_multi_unique = 0;    /* distinct eligible patterns over all groups              */
+        uint32_t             *d_rest_ids = nullptr;  /* [rest_long + rest_short] everything else, long first    */
+        uint32_t              rest_long = 0, rest_short = 0;
+    };
+    PatternSet            sets[2];
+
+    /* the folded copy of the arena for sets[1] (kmp_fold.hip): same offsets as d_arena, [0, end of the furthest slot) */
+    uint8_t        *d_fold = nullptr;
+    uint64_t        fold_cap = 0;
+    bool            fold_stale = true;                /* d_arena has changed since the last fold */
+    uint64_t        fold_end = 0;                     /* end of the furthest slot where known (host-side index); 0: ask the device */
 
     /* arena */
     const uint8_t  *d_arena = nullptr;
@@ -163,11 +175,11 @@ bool use_flat(const kmpgpu_ctx *c)
 /* Fused multi-pattern pass: explicit (1) or automatic (2): from 2 unique eligible patterns on -- 0.24 ms against
  * 2 x 0.23 ms as streaming passes over 1.5 GB (profiles/r02_multipattern.txt); the 1-byte patterns that ride along
  * do not count, a set of one eligible pattern plus 1-byte patterns keeps its streaming passes. */
-bool use_fused(const kmpgpu_ctx *c)
+bool use_fused(const kmpgpu_ctx *c, const kmpgpu_ctx::PatternSet &s)
 {
-    if (!c->packed || !c->bitmap_live || c->mode != 0 || c->kernel_sel == 1 || c->fused_groups.empty()) return false;
-    if (c->fused == 1) return c->n_multi_unique >= 2;
-    return c->fused == 2 && c->n_multi_unique >= 2;
+    if (!c->packed || !c->bitmap_live || c->mode != 0 || c->kernel_sel == 1 || s.fused_groups.empty()) return false;
+    if (c->fused == 1) return s.n_multi_unique >= 2;
+    return c->fused == 2 && s.n_multi_unique >= 2;
 }
 
 bool use_packed(const kmpgpu_ctx *c)
@@ -175,7 +187,7 @@ bool use_packed(const kmpgpu_ctx *c)
     return c->packed && c->bitmap_live && c->mode == 0 && (c->kernel_sel == 2 || ((c->kernel_sel == 0 || c->kernel_sel == 3) && !use_flat(c)));
 }
 
-uint32_t grid_blocks(const kmpgpu_ctx *c, bool emit = false)
+uint32_t grid_blocks(const kmpgpu_ctx *c, const kmpgpu_ctx::PatternSet &s, bool emit = false)
 {
     /* In units of 4-wavefront blocks.  An explicit KMPGPU_OPT_BLOCKS_PER_CU means CUs x that many (the shape of rounds 1-2:
      * a persistent grid, 4 per CU for the flat kernel, 6 for the packed one); automatic: the flat and the packed kernel
@@ -183,21 +195,21 @@ uint32_t grid_blocks(const kmpgpu_ctx *c, bool emit = false)
      * fits a CU (two of its 16-wavefront blocks = 8 of these units). */
     const bool streaming = use_flat(c) || use_packed(c);
     int fused_bpc = 7;
-    if (use_fused(c)) {
+    if (use_fused(c, s)) {
         /* as many wavefronts as a CU holds of the kernel the pass will take (registers and the 160 KB of LDS), counted here in 4-wavefront blocks,
          * the unit the plan is cut in.  Only the first group carries 1-byte patterns; the plan follows it. */
         uint32_t waves = 64u;
-        for (const kmpgpu_ctx::FusedGroup &g : c->fused_groups)
-            waves = std::min(waves, kmp_multi_resident_waves(kmp_multi_kind(emit, c->pad_clean, c->fused_groups.front().n_ones), g.words, g.n_unique));
+        for (const kmpgpu_ctx::FusedGroup &g : s.fused_groups)
+            waves = std::min(waves, kmp_multi_resident_waves(kmp_multi_kind(emit, c->pad_clean, s.fused_groups.front().n_ones), g.words, g.n_unique));
         /* ONE round of blocks: inside a block the wavefronts share its region out among themselves as they go (work units, enqueue_pass), so no
          * block ends long before the others and a second round has nothing to even out (with fixed ranges it had: 325 -> 317 us; with
          * units one round 303 / 146 / 154 us, two rounds 303 / 158 / 165 us on 1500-byte, Zipf and 64-byte packets, profiles/r03_fused_units_sweep2.txt) */
         fused_bpc = (int)std::max<uint32_t>(1u, waves / KMP_BLOCK_WAVES);
     }
     const int bpc = c->blocks_per_cu > 0 ? c->blocks_per_cu
-                  : use_fused(c) ? fused_bpc : !streaming ? 8 : use_flat(c) ? 4 : 6;
+                  : use_fused(c, s) ? fused_bpc : !streaming ? 8 : use_flat(c) ? 4 : 6;
     uint64_t need = (c->n_pkts + KMP_BLOCK_WAVES - 1) / KMP_BLOCK_WAVES;
-    if (c->blocks_per_cu <= 0 && use_flat(c) && !use_fused(c) && c->uni_stride) {
+    if (c->blocks_per_cu <= 0 && use_flat(c) && !use_fused(c, s) && c->uni_stride) {
         /* The flat kernel does NOT run as a persistent grid: a wavefront takes ~6 KiB (four 1500-byte packets) and the grid is
          * one block per four such ranges.  The hardware hands the blocks out in order as CUs free up, so at any moment the
          * whole chip reads one compact, moving window of the arena and nobody waits for a straggler at the end: 209-211 us per
@@ -212,7 +224,7 @@ uint32_t grid_blocks(const kmpgpu_ctx *c, bool emit = false)
         bx = std::min(bx, max_bx);
         return (uint32_t)std::max<uint64_t>(bx, 1);
     }
-    if (c->blocks_per_cu <= 0 && use_packed(c) && !use_fused(c)) {
+    if (c->blocks_per_cu <= 0 && use_packed(c) && !use_fused(c, s)) {
         /* The packed kernel likewise: ~16 KiB per wavefront and as many blocks as that takes, handed out in order by the
          * hardware (its per-range set-up -- plan entry, bitmap words -- is heavier than the flat kernel's, 6 KiB ranges cost
          * more than they gain): Zipf 64..9000 B 109 -> 105 us per 0.67 GB, 64-byte payloads 155 -> 143 us per 0.77 GB
@@ -226,7 +238,7 @@ uint32_t grid_blocks(const kmpgpu_ctx *c, bool emit = false)
         /* small captures: give every wavefront at least 8 KiB to stream instead of launching
          * thousands of nearly empty wavefronts per pattern */
         const uint64_t span = c->span_end - c->uni_off0;
-        const uint64_t per_wave = use_fused(c) ? 2048ull : 8192ull;      /* the fused pass does ~10x the work per byte */
+        const uint64_t per_wave = use_fused(c, s) ? 2048ull : 8192ull;      /* the fused pass does ~10x the work per byte */
         need = std::min<uint64_t>(need, (span + KMP_BLOCK_WAVES * per_wave - 1) / (KMP_BLOCK_WAVES * per_wave));
     }
     uint64_t cap = (uint64_t)c->cu_count * (uint64_t)bpc;
@@ -234,14 +246,22 @@ uint32_t grid_blocks(const kmpgpu_ctx *c, bool emit = false)
     return (uint32_t)std::max<uint64_t>(b, 1);
 }
 
-void free_fused_groups(kmpgpu_ctx *c)
+void free_pattern_set(kmpgpu_ctx::PatternSet &s)
 {
-    for (kmpgpu_ctx::FusedGroup &g : c->fused_groups)
+    for (kmpgpu_ctx::FusedGroup &g : s.fused_groups)
         for (uint32_t *p : {g.d_tables, g.d_ids, g.d_rows, g.d_uid_first, g.d_uid_ids})
             if (p) (void)hipFree(p);
-    c->fused_groups.clear();
-    c->n_multi_unique = 0;
+    s.fused_groups.clear();
+    s.n_multi_unique = 0;
+    if (s.d_ids) (void)hipFree(s.d_ids);
+    if (s.d_rest_ids) (void)hipFree(s.d_rest_ids);
+    s.d_ids = s.d_rest_ids = nullptr;
+    s.n = s.n_long = s.n_short = s.rest_long = s.rest_short = 0;
 }
+
+/* The set a scan reports the grid of (kmpgpu_timing.grid_blocks): the case-sensitive one, or the nocase one when it is alone. */
+const kmpgpu_ctx::PatternSet &primary_set(const kmpgpu_ctx *c) { return c->sets[0].n || !c->sets[1].n ? c->sets[0] : c->sets[1]; }
+
 
 int ensure_partials(kmpgpu_ctx *c, size_t elems)
 {
@@ -266,6 +286,7 @@ void release_arena(kmpgpu_ctx *c, bool keep_buffers = false)
     c->arena_bytes = c->n_pkts = c->payload_bytes = 0;
     c->uniform = false; c->packed = false; c->pad_clean = false; c->plan_waves = 0; c->uplan_units = 0;
     c->bitmap_live = false;                           /* the buffer itself (1/128 of an arena) is kept for the next arena */
+    c->fold_stale = true; c->fold_end = 0;            /* (so is the fold buffer) */
 }
 
 /* Host ranges pinned through kmpgpu_host_register.  One copy must not straddle two registrations (the runtime refuses it), and a
@@ -322,6 +343,8 @@ void release_frame_scratch(kmpgpu_ctx *c)
     c->fr_file_cap = c->fr_off_cap = c->fr_cl_cap = c->fr_ws_cap = c->fr_src_cap = 0;
 }
 
+int grow_fold(kmpgpu_ctx *c, uint64_t bytes);
+
 /* An arena whose slots are not back to back (gaps, shuffled order) is copied once into a packed one owned
  * by the context, so that the streaming kernels apply to it too (KMPGPU_OPT_REPACK, default on). */
 int repack_arena(kmpgpu_ctx *c)
@@ -359,6 +382,45 @@ int repack_arena(kmpgpu_ctx *c)
     c->arena_bytes = nbytes;
     c->packed = true; c->uniform = false;
     c->uni_off0 = 0; c->span_end = tot[0];
+    c->fold_stale = true;
+    (void)grow_fold(c, nbytes);                   /* (a failure is reported by the first scan that needs the fold) */
+    return KMPGPU_OK;
+}
+
+/* The fold buffer holds at least `bytes` (an arena's size): grown where the other buffers are, only while a pattern needs it. */
+int grow_fold(kmpgpu_ctx *c, uint64_t bytes)
+{
+    if (!c->sets[1].n || !bytes) return KMPGPU_OK;
+    const hipError_t e = grow_buffer(&c->d_fold, &c->fold_cap, (bytes + 15u) & ~15ull);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? KMPGPU_ENOMEM : KMPGPU_EHIP, "the fold buffer of the nocase patterns (%llu bytes) could not be allocated: %s",
+                    (unsigned long long)bytes, hipGetErrorString(e));
+    }
+    return KMPGPU_OK;
+}
+
+/* Before a pass of the nocase set: d_fold = fold(d_arena) over [0, end of the furthest slot), once per arena (enqueued on the
+ * context's stream; neither a launch of kmpgpu_timing nor one kmpgpu_profile_* records). */
+int ensure_fold(kmpgpu_ctx *c)
+{
+    if (!c->fold_stale) return KMPGPU_OK;
+    uint64_t end = c->packed ? c->span_end : c->fold_end;          /* slots back to back: the last one is the furthest */
+    if (!end) {
+        /* an index that is not in arena order (an arena scanned in place): its furthest slot, asked once */
+        HIP_TRY(hipMemsetAsync(c->d_sum + 5, 0, sizeof(unsigned long long), c->stream));
+        HIP_TRY(kmp_launch_slot_end(c->d_off, c->d_len, c->n_pkts, c->d_sum + 5, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->h_small + 15, c->d_sum + 5, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        end = c->fold_end = c->h_small[15];
+    }
+    if (end > c->arena_bytes) return fail(KMPGPU_EINVAL, "kmpgpu_scan: a slot ends behind the arena");
+    if (c->fold_cap < end) {
+        int rc = grow_fold(c, end);
+        if (rc) return rc;
+    }
+    HIP_TRY(kmp_launch_fold(c->d_arena, c->d_fold, end, c->stream));
+    c->fold_stale = false;
     return KMPGPU_OK;
 }
 
@@ -395,31 +457,26 @@ int prepare_packed(kmpgpu_ctx *c)
 /* Enqueue one full pass: scan launches (patterns grouped by "shorter than 4 bytes") + reduce. */
 struct EmitTarget { void *out = nullptr; unsigned long long *counter = nullptr; unsigned long long cap = 0; };
 
-int enqueue_pass(kmpgpu_ctx *c, uint32_t *launches, unsigned long long *d_out, const EmitTarget *emit = nullptr)
+/* Partial counts of one set's pass: a row per pattern -- or, where the fused pass runs, a row per id of its largest group (a classed group
+ * numbers its patterns by bucket class, up to 1024 ids however few patterns it has) and one per pattern that keeps a pass of its own. */
+size_t part_rows(const kmpgpu_ctx *c, const kmpgpu_ctx::PatternSet &s)
 {
-    if (!d_out) d_out = c->d_counts;
-    if (!c->d_patterns || c->n_pat == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan: no patterns set");
-    if (!c->d_off && c->n_pkts) return fail(KMPGPU_ESTATE, "kmpgpu_scan: no arena loaded");
-    uint32_t nl = 0;
-    if (c->n_pkts == 0) {
-        if (!c->accumulate) HIP_TRY(hipMemsetAsync(d_out, 0, sizeof(unsigned long long) * c->n_pat, c->stream));
-        if (launches) *launches = 0;
-        return KMPGPU_OK;
-    }
-    const uint32_t bx = grid_blocks(c, emit != nullptr);
-    /* partial counts: a row per pattern -- or, where the fused pass runs, a row per id of its largest group (a classed group numbers
-     * its patterns by bucket class, up to 1024 ids however few patterns it has) and one per pattern that keeps a pass of its own */
-    size_t part_rows = c->n_pat;
-    if (use_fused(c)) {
+    size_t rows = c->n_pat;
+    if (use_fused(c, s)) {
         size_t max_u = 0;
-        for (const kmpgpu_ctx::FusedGroup &g : c->fused_groups) max_u = std::max<size_t>(max_u, g.n_unique);
-        part_rows = std::max<size_t>(part_rows, max_u + c->rest_long + c->rest_short);
+        for (const kmpgpu_ctx::FusedGroup &g : s.fused_groups) max_u = std::max<size_t>(max_u, g.n_unique);
+        rows = std::max<size_t>(rows, max_u + s.rest_long + s.rest_short);
     }
-    int rc = ensure_partials(c, (size_t)bx * part_rows);
-    if (rc) return rc;
+    return rows;
+}
 
+/* The launches of one set over `arena` (d_arena, or the folded copy for the nocase set): scan launches (patterns grouped by "shorter
+ * than 4 bytes") + reduce, into d_out by pattern index. */
+int enqueue_set(kmpgpu_ctx *c, const kmpgpu_ctx::PatternSet &s, const uint8_t *arena, uint32_t bx, uint32_t &nl, unsigned long long *d_out,
+                const EmitTarget *emit)
+{
     kmp_scan_args a{};
-    a.arena = c->d_arena; a.pkt_off = c->d_off; a.pkt_len = c->d_len; a.n_pkts = c->n_pkts;
+    a.arena = arena; a.pkt_off = c->d_off; a.pkt_len = c->d_len; a.n_pkts = c->n_pkts;
     a.patterns = c->d_patterns; a.blocks_x = bx; a.depth = c->depth; /* 0: the launcher's own default */ a.mode = c->mode;
     a.nontemporal = c->nontemporal != 0;
     a.pad_clean = c->pad_clean;
@@ -436,12 +493,12 @@ int enqueue_pass(kmpgpu_ctx *c, uint32_t *launches, unsigned long long *d_out, c
     }
     const bool flat = use_flat(c) && ppw * c->uni_stride < (1ull << 31);
     if (flat) {
-        a.arena = c->d_arena + c->uni_off0;
+        a.arena = arena + c->uni_off0;
         a.uniform_stride = c->uni_stride; a.uniform_len = c->uni_len; a.pkts_per_wave = (uint32_t)ppw;
     }
     /* packed arenas: byte-balanced wavefront ranges (plan) + packet-start bitmap, used by the packed
      * streaming kernel (mixed lengths) and by the fused multi-pattern pass */
-    const bool fused = use_fused(c);
+    const bool fused = use_fused(c, s);
     bool packed = !flat && use_packed(c);
     bool do_fused = false;
     if (fused) {
@@ -452,7 +509,7 @@ int enqueue_pass(kmpgpu_ctx *c, uint32_t *launches, unsigned long long *d_out, c
          * is done when the second one has a third to go.  (Small units throughout cost more than they balance: a unit begins
          * with the dependent chain counter - entry - first loads, which the other wavefronts of the SIMD do not cover --
          * profiles/r03_tried_all_units_dynamic.txt.) */
-        const uint32_t bwaves = kmp_multi_block_waves(kmp_multi_kind(emit != nullptr, c->pad_clean, c->fused_groups.front().n_ones));
+        const uint32_t bwaves = kmp_multi_block_waves(kmp_multi_kind(emit != nullptr, c->pad_clean, s.fused_groups.front().n_ones));
         uint64_t fblocks = ((uint64_t)bx * KMP_BLOCK_WAVES + bwaves - 1u) / bwaves;
         const uint32_t sides = fblocks >= 2 ? 2u : 1u;
         fblocks -= fblocks % sides;
@@ -541,15 +598,15 @@ int enqueue_pass(kmpgpu_ctx *c, uint32_t *launches, unsigned long long *d_out, c
         return hipSuccess;
     };
 
-    const uint32_t *ids = c->d_ids;
-    uint32_t n_long = c->n_long, n_short = c->n_short;
+    const uint32_t *ids = s.d_ids;
+    uint32_t n_long = s.n_long, n_short = s.n_short;
     size_t part_base = 0;                         /* partial rows already used */
     if (do_fused) {
         /* one read of the arena for every group of unique patterns of 2..99 bytes (up to 256, classed groups up to 1024) */
         uint32_t max_u = 0;
-        for (const kmpgpu_ctx::FusedGroup &g : c->fused_groups) {
+        for (const kmpgpu_ctx::FusedGroup &g : s.fused_groups) {
             kmp_scan_args f = a;
-            f.arena = c->d_arena;
+            f.arena = arena;
             f.plan = c->d_uplan;
             f.fused_classed = g.classed;
             f.partials = c->d_partials;
@@ -569,7 +626,7 @@ int enqueue_pass(kmpgpu_ctx *c, uint32_t *launches, unsigned long long *d_out, c
             max_u = std::max(max_u, g.n_unique);
         }
         part_base = max_u;
-        ids = c->d_rest_ids; n_long = c->rest_long; n_short = c->rest_short;
+        ids = s.d_rest_ids; n_long = s.rest_long; n_short = s.rest_short;
     }
 
     struct Group { uint32_t first, n; bool masked; } groups[2] = {{0, n_long, false}, {n_long, n_short, true}};
@@ -594,206 +651,58 @@ int enqueue_pass(kmpgpu_ctx *c, uint32_t *launches, unsigned long long *d_out, c
             ++nl;
         }
     }
+    return KMPGPU_OK;
+}
+
+/* Enqueue one full pass: the case-sensitive set over the arena, then the nocase set over its folded copy. */
+int enqueue_pass(kmpgpu_ctx *c, uint32_t *launches, unsigned long long *d_out, const EmitTarget *emit = nullptr)
+{
+    if (!d_out) d_out = c->d_counts;
+    if (!c->d_patterns || c->n_pat == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan: no patterns set");
+    if (!c->d_off && c->n_pkts) return fail(KMPGPU_ESTATE, "kmpgpu_scan: no arena loaded");
+    uint32_t nl = 0;
+    if (c->n_pkts == 0) {
+        if (!c->accumulate) HIP_TRY(hipMemsetAsync(d_out, 0, sizeof(unsigned long long) * c->n_pat, c->stream));
+        if (launches) *launches = 0;
+        return KMPGPU_OK;
+    }
+    /* the folded copy first: a failure leaves no pass half enqueued */
+    int rc = c->sets[1].n ? ensure_fold(c) : KMPGPU_OK;
+    if (rc) return rc;
+    /* the grid depends on the set (the fused pass); the partials are sized for the larger of the two passes, which run one after the
+     * other on the stream and reuse them */
+    uint32_t bx[2] = {0, 0};
+    size_t elems = 0;
+    for (int k = 0; k < 2; k++)
+        if (c->sets[k].n) {
+            bx[k] = grid_blocks(c, c->sets[k], emit != nullptr);
+            elems = std::max(elems, (size_t)bx[k] * part_rows(c, c->sets[k]));
+        }
+    rc = ensure_partials(c, elems);
+    if (rc) return rc;
+    for (int k = 0; k < 2; k++)
+        if (c->sets[k].n && (rc = enqueue_set(c, c->sets[k], k ? c->d_fold : c->d_arena, bx[k], nl, d_out, emit))) return rc;
     if (launches) *launches = nl;
     return KMPGPU_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-const char *kmpgpu_last_error(void) { return g_err.c_str(); }
-
-int kmpgpu_device_count(void)
+/* The passes of one set (kmpgpu_ctx::PatternSet) over the patterns `members` (indices into host, file order): the long / short split
+ * of the streaming passes and the tables of the fused pass, built on the bytes as stored (folded for the nocase set, so that
+ * "HOST" and "Host" share a row). */
+int build_set(kmpgpu_ctx *c, kmpgpu_ctx::PatternSet &s, const std::vector<kmp_pattern_dev> &host, const std::vector<uint32_t> &members)
 {
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess) return fail(KMPGPU_EHIP, "hipGetDeviceCount failed: %s", hipGetErrorString(e));
-    return n;
-}
-
-int kmpgpu_init(kmpgpu_ctx **out, int device)
-{
-    if (!out) return fail(KMPGPU_EINVAL, "kmpgpu_init: ctx is NULL");
-    *out = nullptr;
-    int n = 0;
-    HIP_TRY(hipGetDeviceCount(&n));
-    if (n <= 0) return fail(KMPGPU_EHIP, "kmpgpu_init: no HIP device visible");
-    if (device < 0 || device >= n) return fail(KMPGPU_EINVAL, "kmpgpu_init: device %d out of range (0..%d)", device, n - 1);
-    HIP_TRY(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, device));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(KMPGPU_EHIP, "kmpgpu_init: device %d is %s; this library carries gfx950 code only", device, prop.gcnArchName);
-    kmpgpu_ctx *c = new (std::nothrow) kmpgpu_ctx();
-    if (!c) return fail(KMPGPU_ENOMEM, "kmpgpu_init: out of host memory");
-    c->device = device;
-    c->cu_count = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    hipError_t e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
-    if (e == hipSuccess) {
-        c->stream = c->own_stream;
-        for (auto &ev : c->ev) if (e == hipSuccess) e = hipEventCreate(&ev);
-    }
-    if (e == hipSuccess) e = hipMalloc(&c->d_err, 2 * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&c->d_sum, 6 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_small, 16 * sizeof(unsigned long long), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        kmpgpu_destroy(c);
-        return fail(KMPGPU_EHIP, "kmpgpu_init: %s", hipGetErrorString(e));
-    }
-    *out = c;
-    return KMPGPU_OK;
-}
-
-void kmpgpu_destroy(kmpgpu_ctx *c)
-{
-    if (!c) return;
-    if (c->comm) comm_forget(c->comm, c);           /* a communicator outliving one of its contexts: it keeps device + stream handle only */
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    release_arena(c);
-    release_frame_scratch(c);
-    if (c->d_bitmap) (void)hipFree(c->d_bitmap);
-    if (c->d_patterns) (void)hipFree(c->d_patterns);
-    if (c->d_ids) (void)hipFree(c->d_ids);
-    if (c->d_partials) (void)hipFree(c->d_partials);
-    if (c->d_counts) (void)hipFree(c->d_counts);
-    if (c->d_plan) (void)hipFree(c->d_plan);
-    if (c->d_uplan) (void)hipFree(c->d_uplan);
-    if (c->d_pool) (void)hipFree(c->d_pool);
-    free_fused_groups(c);
-    if (c->d_rest_ids) (void)hipFree(c->d_rest_ids);
-    if (c->d_err) (void)hipFree(c->d_err);
-    if (c->d_sum) (void)hipFree(c->d_sum);
-    if (c->h_counts) (void)hipHostFree(c->h_counts);
-    if (c->h_small) (void)hipHostFree(c->h_small);
-    for (auto ev : c->ev) if (ev) (void)hipEventDestroy(ev);
-    for (auto ev : c->prof_ev) if (ev) (void)hipEventDestroy(ev);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;
-}
-
-int kmpgpu_set_stream(kmpgpu_ctx *c, void *hip_stream)
-{
-    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_set_stream: ctx is NULL");
-    c->stream = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
-    return KMPGPU_OK;
-}
-
-int kmpgpu_set_option(kmpgpu_ctx *c, int key, int64_t value)
-{
-    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_set_option: ctx is NULL");
-    switch (key) {
-    case KMPGPU_OPT_MODE:
-        if (value != 0 && value != 1) return fail(KMPGPU_EINVAL, "mode must be 0 or 1");
-        c->mode = (int)value; return KMPGPU_OK;
-    case KMPGPU_OPT_BLOCKS_PER_CU:
-        if (value < 0 || value > 256) return fail(KMPGPU_EINVAL, "blocks per CU must be 0 (auto) or 1..256");
-        c->blocks_per_cu = (int)value; return KMPGPU_OK;
-    case KMPGPU_OPT_DEPTH:
-        if (value != 0 && (value < 2 || value > 8 || value == 7)) return fail(KMPGPU_EINVAL, "depth must be 0 (auto), 2..6 or 8");
-        c->depth = (int)value; return KMPGPU_OK;
-    case KMPGPU_OPT_FUSED:
-        if (value < 0 || value > 2) return fail(KMPGPU_EINVAL, "fused must be 0, 1 or 2");
-        c->fused = (int)value; return KMPGPU_OK;
-    case KMPGPU_OPT_REPACK:
-        c->repack = value ? 1 : 0; return KMPGPU_OK;
-    case KMPGPU_OPT_ACCUMULATE:
-        c->accumulate = value ? 1 : 0; return KMPGPU_OK;
-    case KMPGPU_OPT_KERNEL:
-        if (value < 0 || value > 3) return fail(KMPGPU_EINVAL, "kernel selection must be 0, 1, 2 or 3");
-        c->kernel_sel = (int)value; return KMPGPU_OK;
-    case KMPGPU_OPT_NONTEMPORAL:
-        c->nontemporal = value ? 1 : 0; return KMPGPU_OK;
-    case KMPGPU_OPT_FUSED_UNIT:
-        if (value != 0 && (value < 1024 || value > (1 << 20) || (value & 1023))) return fail(KMPGPU_EINVAL, "fused unit must be 0 (auto) or a multiple of 1024 up to 1 MiB");
-        c->fused_unit = (int)value; return KMPGPU_OK;
-    default:
-        return fail(KMPGPU_EINVAL, "unknown option %d", key);
-    }
-}
-
-void *kmpgpu_host_alloc(size_t bytes)
-{
-    void *p = nullptr;
-    if (hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess) {
-        fail(KMPGPU_EHIP, "hipHostMalloc(%zu) failed", bytes);
-        return nullptr;
-    }
-    return p;
-}
-
-void kmpgpu_host_free(void *p) { if (p) (void)hipHostFree(p); }
-
-int kmpgpu_host_register(const void *ptr, size_t bytes)
-{
-    if (!ptr || !bytes) return fail(KMPGPU_EINVAL, "kmpgpu_host_register: NULL / empty range");
-    if ((uintptr_t)ptr & 4095u) return fail(KMPGPU_EINVAL, "kmpgpu_host_register: the range must start on a page boundary");
-    /* portable: visible to every device's context (several shards upload from one mapping); the memory may be a PROT_READ mapping */
-    hipError_t e = hipHostRegister(const_cast<void *>(ptr), bytes, hipHostRegisterPortable | hipHostRegisterReadOnly);
-    if (e != hipSuccess) { (void)hipGetLastError(); e = hipHostRegister(const_cast<void *>(ptr), bytes, hipHostRegisterPortable); }
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(KMPGPU_EHIP, "hipHostRegister(%zu bytes) failed: %s", bytes, hipGetErrorString(e)); }
-    std::lock_guard<std::mutex> lock(g_pinned_mu);
-    g_pinned[(uintptr_t)ptr] = bytes;
-    return KMPGPU_OK;
-}
-
-int kmpgpu_host_unregister(const void *ptr)
-{
-    if (!ptr) return fail(KMPGPU_EINVAL, "kmpgpu_host_unregister: NULL");
-    { std::lock_guard<std::mutex> lock(g_pinned_mu); g_pinned.erase((uintptr_t)ptr); }
-    HIP_TRY(hipHostUnregister(const_cast<void *>(ptr)));
-    return KMPGPU_OK;
-}
-
-int kmpgpu_set_patterns(kmpgpu_ctx *c, const uint8_t *const *pat, const uint32_t *pat_len, uint32_t n_pat)
-{
-    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_set_patterns: ctx is NULL");
-    if (n_pat && (!pat || !pat_len)) return fail(KMPGPU_EINVAL, "kmpgpu_set_patterns: NULL pattern arrays");
-    HIP_TRY(hipSetDevice(c->device));
-    std::vector<kmp_pattern_dev> host(n_pat ? n_pat : 1);
-    std::vector<uint32_t> ids_long, ids_short;
-    for (uint32_t i = 0; i < n_pat; i++) {
-        const uint32_t m = pat_len[i];
-        if (m < 1 || m > KMPGPU_MAX_PATTERN_LEN) return fail(KMPGPU_EINVAL, "pattern %u: length %u not in 1..99", i, m);
-        if (!pat[i]) return fail(KMPGPU_EINVAL, "pattern %u is NULL", i);
-        if (memchr(pat[i], 0, m)) return fail(KMPGPU_EINVAL, "pattern %u contains a 0x00 byte", i);
-        kmp_pattern_dev &d = host[i];
-        memset(&d, 0, sizeof d);
-        memcpy(d.pat, pat[i], m);
-        failure_table(d.pat, m, d.fail);
-        d.m = m;
-        const uint32_t f = m < 4 ? m : 4;
-        for (uint32_t b = 0; b < f; b++) { d.first |= (uint32_t)d.pat[b] << (8 * b); d.mask |= 0xFFu << (8 * b); }
-        (m >= 4 ? ids_long : ids_short).push_back(i);
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->d_patterns) { HIP_TRY(hipFree(c->d_patterns)); c->d_patterns = nullptr; }
-    if (c->d_ids) { HIP_TRY(hipFree(c->d_ids)); c->d_ids = nullptr; }
-    if (c->d_counts) { HIP_TRY(hipFree(c->d_counts)); c->d_counts = nullptr; }
-    c->n_pat = n_pat; c->n_long = (uint32_t)ids_long.size(); c->n_short = (uint32_t)ids_short.size();
-    const size_t np = n_pat ? n_pat : 1;
-    HIP_TRY(hipMalloc(&c->d_patterns, np * sizeof(kmp_pattern_dev)));
-    HIP_TRY(hipMalloc(&c->d_ids, np * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&c->d_counts, np * sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(c->d_counts, 0, np * sizeof(unsigned long long)));
-    if (n_pat) {
-        std::vector<uint32_t> ids(ids_long);
-        ids.insert(ids.end(), ids_short.begin(), ids_short.end());
-        HIP_TRY(hipMemcpy(c->d_patterns, host.data(), n_pat * sizeof(kmp_pattern_dev), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->d_ids, ids.data(), n_pat * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    if (c->h_counts_cap < np) {
-        if (c->h_counts) (void)hipHostFree(c->h_counts);
-        c->h_counts = nullptr; c->h_counts_cap = 0;
-        HIP_TRY(hipHostMalloc((void **)&c->h_counts, np * sizeof(uint64_t), hipHostMallocDefault));
-        c->h_counts_cap = np;
-    }
+    (void)c;
+    s.n = (uint32_t)members.size();
+    if (!s.n) return KMPGPU_OK;
+    std::vector<uint32_t> ids;
+    for (const uint32_t i : members) if (host[i].m >= 4) ids.push_back(i);
+    s.n_long = (uint32_t)ids.size();
+    for (const uint32_t i : members) if (host[i].m < 4) ids.push_back(i);
+    s.n_short = s.n - s.n_long;
+    HIP_TRY(hipMalloc(&s.d_ids, ids.size() * sizeof(uint32_t)));
+    HIP_TRY(hipMemcpy(s.d_ids, ids.data(), ids.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
 
     /* ---- tables of the fused multi-pattern pass (layout: kmp_device.h) ------------------------- */
-    free_fused_groups(c);
-    if (c->d_rest_ids) { HIP_TRY(hipFree(c->d_rest_ids)); c->d_rest_ids = nullptr; }
-    c->rest_long = c->rest_short = 0;
     /* a group: its distinct patterns, the row (unique-pattern id of the kernel) of each, the patterns counted by it and their rows.
      * `classed`: more than 256 rows -- an entry has eight bits for an id, the kernel adds the first id of the bucket's class
      * (= bucket >> 7: eight classes of up to 256 patterns each, 1024 in all; kmp_device.h) */
@@ -810,16 +719,17 @@ int kmpgpu_set_patterns(kmpgpu_ctx *c, const uint8_t *const *pat, const uint32_t
     std::vector<uint32_t> first_pat;                               /* ... and the first pattern of the list that is each of them */
     std::unordered_map<std::string, uint32_t> uniq_of;
     std::vector<std::pair<uint32_t, uint32_t>> elig;               /* (pattern index, its distinct pattern) */
-    for (uint32_t i = 0; i < n_pat; i++) {
-        const uint32_t m = pat_len[i];
+    for (const uint32_t i : members) {
+        const uint8_t *const pi = host[i].pat;
+        const uint32_t m = host[i].m;
         if (m == 1) {
             size_t k = 0;
-            while (k < one_bytes.size() && one_bytes[k] != pat[i][0]) k++;
-            if (k == one_bytes.size() && k < KMP_MULTI_MAX_ONES) one_bytes.push_back(pat[i][0]);
+            while (k < one_bytes.size() && one_bytes[k] != pi[0]) k++;
+            if (k == one_bytes.size() && k < KMP_MULTI_MAX_ONES) one_bytes.push_back(pi[0]);
             if (k < one_bytes.size()) { one_ids.emplace_back(i, (uint32_t)k); continue; }
         }
         if (m < KMP_MULTI_MIN_LEN || m > KMP_MULTI_MAX_LEN) { (m >= 4 ? rest_l : rest_s).push_back(i); continue; }
-        const std::string key((const char *)pat[i], m);
+        const std::string key((const char *)pi, m);
         auto it = uniq_of.find(key);
         if (it == uniq_of.end()) {
             /* (a record names the pattern whose bytes 8 .. m-1 the kernel compares against in 16 bits: a pattern of nine bytes or
@@ -829,7 +739,7 @@ int kmpgpu_set_patterns(kmpgpu_ctx *c, const uint8_t *const *pat, const uint32_t
         }
         elig.emplace_back(i, it->second);
     }
-    if (uniq_all.size() < 2) {                    /* nothing to fuse: every pattern keeps its own pass (c->d_ids) */
+    if (uniq_all.size() < 2) {                    /* nothing to fuse: every pattern keeps its own pass (s.d_ids) */
         return KMPGPU_OK;
     }
     /* Which group a distinct pattern goes to.  Up to 256 of them: one group, rows in file order (short ones first, below).  More: the
@@ -976,8 +886,8 @@ int kmpgpu_set_patterns(kmpgpu_ctx *c, const uint8_t *const *pat, const uint32_t
         for (uint32_t u = 0; u < rows_n + n_ones; u++) uid_first[u + 1] += uid_first[u];
         { std::vector<uint32_t> fill(uid_first.begin(), uid_first.end() - 1);
           for (size_t i = 0; i < h.ids.size(); i++) uid_ids[fill[h.rows[i]]++] = h.ids[i]; }
-        c->fused_groups.emplace_back();
-        kmpgpu_ctx::FusedGroup &g = c->fused_groups.back();
+        s.fused_groups.emplace_back();
+        kmpgpu_ctx::FusedGroup &g = s.fused_groups.back();
         auto up = [&](uint32_t **d, const std::vector<uint32_t> &v) -> hipError_t {
             hipError_t e = hipMalloc(d, (v.size() ? v.size() : 1) * sizeof(uint32_t));
             if (e == hipSuccess && !v.empty()) e = hipMemcpy(*d, v.data(), v.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
@@ -989,13 +899,223 @@ int kmpgpu_set_patterns(kmpgpu_ctx *c, const uint8_t *const *pat, const uint32_t
         HIP_TRY(up(&g.d_uid_first, uid_first));
         HIP_TRY(up(&g.d_uid_ids, uid_ids));
         g.words = (uint32_t)tab.size(); g.n_unique = rows_n + n_ones; g.cshift = h.classed ? KMP_MULTI_CLS_SHIFT : cls_short[0]; g.classed = h.classed; g.bmask = bmask; g.n_ones = n_ones; g.ones = ones; g.n_ids = (uint32_t)h.ids.size();
-        c->n_multi_unique += U;
+        s.n_multi_unique += U;
     }
     std::vector<uint32_t> rest(rest_l);
     rest.insert(rest.end(), rest_s.begin(), rest_s.end());
-    HIP_TRY(hipMalloc(&c->d_rest_ids, (rest.size() ? rest.size() : 1) * sizeof(uint32_t)));
-    if (!rest.empty()) HIP_TRY(hipMemcpy(c->d_rest_ids, rest.data(), rest.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    c->rest_long = (uint32_t)rest_l.size(); c->rest_short = (uint32_t)rest_s.size();
+    HIP_TRY(hipMalloc(&s.d_rest_ids, (rest.size() ? rest.size() : 1) * sizeof(uint32_t)));
+    if (!rest.empty()) HIP_TRY(hipMemcpy(s.d_rest_ids, rest.data(), rest.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    s.rest_long = (uint32_t)rest_l.size(); s.rest_short = (uint32_t)rest_s.size();
+    return KMPGPU_OK;
+}
+
+
+}  // namespace
+
+extern "C" {
+
+const char *kmpgpu_last_error(void) { return g_err.c_str(); }
+
+int kmpgpu_device_count(void)
+{
+    int n = 0;
+    hipError_t e = hipGetDeviceCount(&n);
+    if (e != hipSuccess) return fail(KMPGPU_EHIP, "hipGetDeviceCount failed: %s", hipGetErrorString(e));
+    return n;
+}
+
+int kmpgpu_init(kmpgpu_ctx **out, int device)
+{
+    if (!out) return fail(KMPGPU_EINVAL, "kmpgpu_init: ctx is NULL");
+    *out = nullptr;
+    int n = 0;
+    HIP_TRY(hipGetDeviceCount(&n));
+    if (n <= 0) return fail(KMPGPU_EHIP, "kmpgpu_init: no HIP device visible");
+    if (device < 0 || device >= n) return fail(KMPGPU_EINVAL, "kmpgpu_init: device %d out of range (0..%d)", device, n - 1);
+    HIP_TRY(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, device));
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return fail(KMPGPU_EHIP, "kmpgpu_init: device %d is %s; this library carries gfx950 code only", device, prop.gcnArchName);
+    kmpgpu_ctx *c = new (std::nothrow) kmpgpu_ctx();
+    if (!c) return fail(KMPGPU_ENOMEM, "kmpgpu_init: out of host memory");
+    c->device = device;
+    c->cu_count = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    hipError_t e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
+    if (e == hipSuccess) {
+        c->stream = c->own_stream;
+        for (auto &ev : c->ev) if (e == hipSuccess) e = hipEventCreate(&ev);
+    }
+    if (e == hipSuccess) e = hipMalloc(&c->d_err, 2 * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(&c->d_sum, 6 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_small, 16 * sizeof(unsigned long long), hipHostMallocDefault);
+    if (e != hipSuccess) {
+        kmpgpu_destroy(c);
+        return fail(KMPGPU_EHIP, "kmpgpu_init: %s", hipGetErrorString(e));
+    }
+    *out = c;
+    return KMPGPU_OK;
+}
+
+void kmpgpu_destroy(kmpgpu_ctx *c)
+{
+    if (!c) return;
+    if (c->comm) comm_forget(c->comm, c);           /* a communicator outliving one of its contexts: it keeps device + stream handle only */
+    (void)hipSetDevice(c->device);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    release_arena(c);
+    release_frame_scratch(c);
+    if (c->d_bitmap) (void)hipFree(c->d_bitmap);
+    if (c->d_patterns) (void)hipFree(c->d_patterns);
+    if (c->d_partials) (void)hipFree(c->d_partials);
+    if (c->d_counts) (void)hipFree(c->d_counts);
+    if (c->d_plan) (void)hipFree(c->d_plan);
+    if (c->d_uplan) (void)hipFree(c->d_uplan);
+    if (c->d_pool) (void)hipFree(c->d_pool);
+    free_pattern_set(c->sets[0]);
+    free_pattern_set(c->sets[1]);
+    if (c->d_fold) (void)hipFree(c->d_fold);
+    if (c->d_err) (void)hipFree(c->d_err);
+    if (c->d_sum) (void)hipFree(c->d_sum);
+    if (c->h_counts) (void)hipHostFree(c->h_counts);
+    if (c->h_small) (void)hipHostFree(c->h_small);
+    for (auto ev : c->ev) if (ev) (void)hipEventDestroy(ev);
+    for (auto ev : c->prof_ev) if (ev) (void)hipEventDestroy(ev);
+    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
+    delete c;
+}
+
+int kmpgpu_set_stream(kmpgpu_ctx *c, void *hip_stream)
+{
+    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_set_stream: ctx is NULL");
+    c->stream = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
+    return KMPGPU_OK;
+}
+
+int kmpgpu_set_option(kmpgpu_ctx *c, int key, int64_t value)
+{
+    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_set_option: ctx is NULL");
+    switch (key) {
+    case KMPGPU_OPT_MODE:
+        if (value != 0 && value != 1) return fail(KMPGPU_EINVAL, "mode must be 0 or 1");
+        c->mode = (int)value; return KMPGPU_OK;
+    case KMPGPU_OPT_BLOCKS_PER_CU:
+        if (value < 0 || value > 256) return fail(KMPGPU_EINVAL, "blocks per CU must be 0 (auto) or 1..256");
+        c->blocks_per_cu = (int)value; return KMPGPU_OK;
+    case KMPGPU_OPT_DEPTH:
+        if (value != 0 && (value < 2 || value > 8 || value == 7)) return fail(KMPGPU_EINVAL, "depth must be 0 (auto), 2..6 or 8");
+        c->depth = (int)value; return KMPGPU_OK;
+    case KMPGPU_OPT_FUSED:
+        if (value < 0 || value > 2) return fail(KMPGPU_EINVAL, "fused must be 0, 1 or 2");
+        c->fused = (int)value; return KMPGPU_OK;
+    case KMPGPU_OPT_REPACK:
+        c->repack = value ? 1 : 0; return KMPGPU_OK;
+    case KMPGPU_OPT_ACCUMULATE:
+        c->accumulate = value ? 1 : 0; return KMPGPU_OK;
+    case KMPGPU_OPT_KERNEL:
+        if (value < 0 || value > 3) return fail(KMPGPU_EINVAL, "kernel selection must be 0, 1, 2 or 3");
+        c->kernel_sel = (int)value; return KMPGPU_OK;
+    case KMPGPU_OPT_NONTEMPORAL:
+        c->nontemporal = value ? 1 : 0; return KMPGPU_OK;
+    case KMPGPU_OPT_FUSED_UNIT:
+        if (value != 0 && (value < 1024 || value > (1 << 20) || (value & 1023))) return fail(KMPGPU_EINVAL, "fused unit must be 0 (auto) or a multiple of 1024 up to 1 MiB");
+        c->fused_unit = (int)value; return KMPGPU_OK;
+    default:
+        return fail(KMPGPU_EINVAL, "unknown option %d", key);
+    }
+}
+
+void *kmpgpu_host_alloc(size_t bytes)
+{
+    void *p = nullptr;
+    if (hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess) {
+        fail(KMPGPU_EHIP, "hipHostMalloc(%zu) failed", bytes);
+        return nullptr;
+    }
+    return p;
+}
+
+void kmpgpu_host_free(void *p) { if (p) (void)hipHostFree(p); }
+
+int kmpgpu_host_register(const void *ptr, size_t bytes)
+{
+    if (!ptr || !bytes) return fail(KMPGPU_EINVAL, "kmpgpu_host_register: NULL / empty range");
+    if ((uintptr_t)ptr & 4095u) return fail(KMPGPU_EINVAL, "kmpgpu_host_register: the range must start on a page boundary");
+    /* portable: visible to every device's context (several shards upload from one mapping); the memory may be a PROT_READ mapping */
+    hipError_t e = hipHostRegister(const_cast<void *>(ptr), bytes, hipHostRegisterPortable | hipHostRegisterReadOnly);
+    if (e != hipSuccess) { (void)hipGetLastError(); e = hipHostRegister(const_cast<void *>(ptr), bytes, hipHostRegisterPortable); }
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(KMPGPU_EHIP, "hipHostRegister(%zu bytes) failed: %s", bytes, hipGetErrorString(e)); }
+    std::lock_guard<std::mutex> lock(g_pinned_mu);
+    g_pinned[(uintptr_t)ptr] = bytes;
+    return KMPGPU_OK;
+}
+
+int kmpgpu_host_unregister(const void *ptr)
+{
+    if (!ptr) return fail(KMPGPU_EINVAL, "kmpgpu_host_unregister: NULL");
+    { std::lock_guard<std::mutex> lock(g_pinned_mu); g_pinned.erase((uintptr_t)ptr); }
+    HIP_TRY(hipHostUnregister(const_cast<void *>(ptr)));
+    return KMPGPU_OK;
+}
+
+int kmpgpu_set_patterns(kmpgpu_ctx *c, const uint8_t *const *pat, const uint32_t *pat_len, uint32_t n_pat)
+{
+    return kmpgpu_set_patterns_flags(c, pat, pat_len, nullptr, n_pat);
+}
+
+int kmpgpu_set_patterns_flags(kmpgpu_ctx *c, const uint8_t *const *pat, const uint32_t *pat_len, const uint32_t *flags, uint32_t n_pat)
+{
+    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_set_patterns: ctx is NULL");
+    if (n_pat && (!pat || !pat_len)) return fail(KMPGPU_EINVAL, "kmpgpu_set_patterns: NULL pattern arrays");
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<kmp_pattern_dev> host(n_pat ? n_pat : 1);
+    std::vector<uint32_t> members[2];              /* the patterns of sets[0] (case-sensitive) and sets[1] (nocase, with a letter) */
+    for (uint32_t i = 0; i < n_pat; i++) {
+        const uint32_t m = pat_len[i];
+        if (m < 1 || m > KMPGPU_MAX_PATTERN_LEN) return fail(KMPGPU_EINVAL, "pattern %u: length %u not in 1..99", i, m);
+        if (!pat[i]) return fail(KMPGPU_EINVAL, "pattern %u is NULL", i);
+        if (memchr(pat[i], 0, m)) return fail(KMPGPU_EINVAL, "pattern %u contains a 0x00 byte", i);
+        const uint32_t fl = flags ? flags[i] : 0u;
+        if (fl & ~KMPGPU_PAT_NOCASE) return fail(KMPGPU_EINVAL, "pattern %u: unknown flag bits 0x%x", i, fl & ~KMPGPU_PAT_NOCASE);
+        kmp_pattern_dev &d = host[i];
+        memset(&d, 0, sizeof d);
+        memcpy(d.pat, pat[i], m);
+        /* nocase: stored folded (ASCII A-Z -> a-z, kmp_fold.hip), failure table included; without a letter it is its case-sensitive self */
+        bool letter = false;
+        if (fl & KMPGPU_PAT_NOCASE)
+            for (uint32_t b = 0; b < m; b++) {
+                if (d.pat[b] >= 'A' && d.pat[b] <= 'Z') d.pat[b] += 'a' - 'A';
+                letter |= d.pat[b] >= 'a' && d.pat[b] <= 'z';
+            }
+        failure_table(d.pat, m, d.fail);
+        d.m = m;
+        const uint32_t f = m < 4 ? m : 4;
+        for (uint32_t b = 0; b < f; b++) { d.first |= (uint32_t)d.pat[b] << (8 * b); d.mask |= 0xFFu << (8 * b); }
+        members[letter ? 1 : 0].push_back(i);
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->d_patterns) { HIP_TRY(hipFree(c->d_patterns)); c->d_patterns = nullptr; }
+    if (c->d_counts) { HIP_TRY(hipFree(c->d_counts)); c->d_counts = nullptr; }
+    free_pattern_set(c->sets[0]);
+    free_pattern_set(c->sets[1]);
+    c->n_pat = n_pat;
+    const size_t np = n_pat ? n_pat : 1;
+    HIP_TRY(hipMalloc(&c->d_patterns, np * sizeof(kmp_pattern_dev)));
+    HIP_TRY(hipMalloc(&c->d_counts, np * sizeof(unsigned long long)));
+    HIP_TRY(hipMemset(c->d_counts, 0, np * sizeof(unsigned long long)));
+    if (n_pat) HIP_TRY(hipMemcpy(c->d_patterns, host.data(), n_pat * sizeof(kmp_pattern_dev), hipMemcpyHostToDevice));
+    if (c->h_counts_cap < np) {
+        if (c->h_counts) (void)hipHostFree(c->h_counts);
+        c->h_counts = nullptr; c->h_counts_cap = 0;
+        HIP_TRY(hipHostMalloc((void **)&c->h_counts, np * sizeof(uint64_t), hipHostMallocDefault));
+        c->h_counts_cap = np;
+    }
+    for (int k = 0; k < 2; k++) {
+        const int rc = build_set(c, c->sets[k], host, members[k]);
+        if (rc) return rc;
+    }
+    /* an arena is attached already: its fold buffer now (a failure is reported by the first scan that needs the buffer) */
+    if (c->n_pkts) (void)grow_fold(c, c->arena_bytes);
     return KMPGPU_OK;
 }
 
@@ -1004,7 +1124,7 @@ int kmpgpu_load_arena(kmpgpu_ctx *c, const uint8_t *arena, uint64_t arena_bytes,
 {
     if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_load_arena: ctx is NULL");
     if (n_pkts && (!arena || !pkt_off || !pkt_len)) return fail(KMPGPU_EINVAL, "kmpgpu_load_arena: NULL buffers");
-    uint64_t payload = 0;
+    uint64_t payload = 0, fold_end = 0;
     for (uint64_t k = 0; k < n_pkts; k++) {         /* the layout contract the kernels rely on */
         const uint64_t o = pkt_off[k], l16 = ((uint64_t)pkt_len[k] + 15u) & ~15ull;
         if (o & 15u) return fail(KMPGPU_EINVAL, "payload %llu: offset %llu is not 16-byte aligned", (unsigned long long)k, (unsigned long long)o);
@@ -1013,6 +1133,7 @@ int kmpgpu_load_arena(kmpgpu_ctx *c, const uint8_t *arena, uint64_t arena_bytes,
             return fail(KMPGPU_EINVAL, "payload %llu: [%llu, +%llu) padded to 16 B (at least one 16-byte slot) exceeds the arena (%llu B)", (unsigned long long)k,
                         (unsigned long long)o, (unsigned long long)pkt_len[k], (unsigned long long)arena_bytes);
         payload += pkt_len[k];
+        fold_end = std::max<uint64_t>(fold_end, o + std::max<uint64_t>(l16, 16));
     }
     bool packed = n_pkts > 0;
     for (uint64_t k = 0; packed && k + 1 < n_pkts; k++)
@@ -1058,6 +1179,8 @@ int kmpgpu_load_arena(kmpgpu_ctx *c, const uint8_t *arena, uint64_t arena_bytes,
     c->uniform = uniform; c->uni_off0 = pkt_off[0]; c->uni_stride = (uint32_t)ustride; c->uni_len = pkt_len[0];
     c->packed = packed;
     c->span_end = pkt_off[n_pkts - 1] + std::max<uint64_t>(((uint64_t)pkt_len[n_pkts - 1] + 15u) & ~15ull, 16);
+    c->fold_end = fold_end;                           /* (the last entry's slot is the furthest only when the index is in arena order) */
+    (void)grow_fold(c, arena_bytes);                  /* (a failure is reported by the first scan that needs the fold) */
     return prepare_packed(c);
 }
 
@@ -1081,6 +1204,8 @@ static int finish_device_index(kmpgpu_ctx *c, const char *who)
     c->uni_off0 = info[1]; c->uni_stride = (uint32_t)info[2]; c->uni_len = (uint32_t)info[3];
     c->packed = (err[1] & 2u) == 0;
     c->span_end = info[4];
+    c->fold_stale = true;
+    (void)grow_fold(c, c->arena_bytes);              /* (a failure is reported by the first scan that needs the fold) */
     return prepare_packed(c);
 }
 
@@ -1221,6 +1346,10 @@ int kmpgpu_reserve(kmpgpu_ctx *c, uint64_t arena_bytes, uint64_t n_pkts, uint64_
             c->bitmap_cap = words;
         }
     }
+    if (arena_bytes) {
+        const int rc = grow_fold(c, arena_bytes);    /* the nocase patterns' folded copy of a batch */
+        if (rc) return rc;
+    }
     if (frame_bytes && n_frames) {
         HIP_TRY(grow_buffer(&c->fr_file, &c->fr_file_cap, frame_bytes + 64));
         HIP_TRY(grow_buffer(&c->fr_off, &c->fr_off_cap, n_frames));
@@ -1266,6 +1395,8 @@ int kmpgpu_attach_arena(kmpgpu_ctx *c, const void *d_arena, uint64_t arena_bytes
     c->uni_off0 = info[1]; c->uni_stride = (uint32_t)info[2]; c->uni_len = (uint32_t)info[3];
     c->packed = (err[1] & 2u) == 0;
     c->span_end = info[4];
+    c->fold_stale = true;
+    (void)grow_fold(c, c->arena_bytes);              /* (a failure is reported by the first scan that needs the fold) */
     return prepare_packed(c);
 }
 
@@ -1342,7 +1473,7 @@ int kmpgpu_scan(kmpgpu_ctx *c, uint64_t *counts_out, kmpgpu_timing *t)
     HIP_TRY(hipEventElapsedTime(&d_ms, c->ev[1], c->ev[2]));
     memcpy(counts_out, c->h_counts, sizeof(uint64_t) * c->n_pat);
     c->last.kernel_ms = k_ms; c->last.d2h_ms = d_ms; c->last.launches = launches;
-    c->last.grid_blocks = c->n_pkts ? grid_blocks(c) : 0;
+    c->last.grid_blocks = c->n_pkts ? grid_blocks(c, primary_set(c)) : 0;
     if (t) *t = c->last;
     return KMPGPU_OK;
 }
@@ -1439,6 +1570,7 @@ int kmpgpu_synth_fill(kmpgpu_ctx *c, void *d_arena, const void *d_pkt_off, const
     if (sp->needle_len > KMP_SYNTH_MAX_NEEDLE || sp->span == 0 || sp->span > 256 || sp->lo + sp->span > 256)
         return fail(KMPGPU_EINVAL, "kmpgpu_synth_fill: bad generator parameters");
     HIP_TRY(hipSetDevice(c->device));
+    if (d_arena == (const void *)c->d_arena) c->fold_stale = true;
     HIP_TRY(kmp_launch_synth_fill((uint8_t *)d_arena, (const uint64_t *)d_pkt_off, (const uint32_t *)d_pkt_len, first_pkt_id,
                                   n_pkts, *sp, c->stream));
     return KMPGPU_OK;

@@ -23,6 +23,7 @@ OPT_REPACK = 7
 OPT_FUSED_UNIT = 8
 KERNEL_AUTO, KERNEL_GENERAL, KERNEL_PACKED, KERNEL_FLAT = 0, 1, 2, 3
 MODE_FILTER, MODE_AUTOMATON = 0, 1
+PAT_NOCASE = 1          # kmpgpu_set_patterns_flags: ASCII letters match either case
 
 
 def device_count() -> int:
@@ -49,13 +50,20 @@ class GpuMatcher:
     def set_stream(self, hip_stream: Optional[int]) -> None:
         gpu_check(self._g.kmpgpu_set_stream(self._ctx, C.c_void_p(hip_stream or 0)), "kmpgpu_set_stream")
 
-    def set_patterns(self, patterns: Sequence[bytes]) -> None:
-        """serial.c:148-152: patterns + failure tables (built inside the library)."""
+    def set_patterns(self, patterns: Sequence[bytes], nocase=False) -> None:
+        """serial.c:148-152: patterns + failure tables (built inside the library).  nocase: a bool for every pattern, or one
+        per pattern -- ASCII letters of such a pattern match either case (kmpgpu_set_patterns_flags)."""
         n = len(patterns)
         bufs = [np.frombuffer(p + b"\0", dtype=np.uint8) for p in patterns]
         ptrs = (u8p * max(n, 1))(*[b.ctypes.data_as(u8p) for b in bufs])
         lens = (C.c_uint32 * max(n, 1))(*[len(p) for p in patterns])
-        gpu_check(self._g.kmpgpu_set_patterns(self._ctx, ptrs, lens, n), "kmpgpu_set_patterns")
+        if isinstance(nocase, (bool, int, np.bool_)):
+            nocase = [bool(nocase)] * n
+        nocase = [bool(x) for x in nocase]
+        if len(nocase) != n:
+            raise ValueError(f"nocase: {len(nocase)} flags for {n} patterns")
+        flags = (C.c_uint32 * max(n, 1))(*[PAT_NOCASE if x else 0 for x in nocase])
+        gpu_check(self._g.kmpgpu_set_patterns_flags(self._ctx, ptrs, lens, flags, n), "kmpgpu_set_patterns_flags")
         self.patterns = list(patterns)
 
     # -- arena ------------------------------------------------------------------------------------
@@ -271,11 +279,11 @@ class GpuComm:
         self.close()
 
 
-def count_matches(patterns: Sequence[bytes], arena: HostArena, device: int = 0, **options) -> np.ndarray:
-    """One-shot helper: counts of every pattern over a host arena on one GPU."""
+def count_matches(patterns: Sequence[bytes], arena: HostArena, device: int = 0, nocase=False, **options) -> np.ndarray:
+    """One-shot helper: counts of every pattern over a host arena on one GPU (nocase: as GpuMatcher.set_patterns)."""
     with GpuMatcher(device) as m:
         for k, v in options.items():
             m.set_option({"mode": OPT_MODE, "depth": OPT_DEPTH, "blocks_per_cu": OPT_BLOCKS_PER_CU}[k], v)
-        m.set_patterns(patterns)
+        m.set_patterns(patterns, nocase=nocase)
         m.load_arena(arena)
         return m.scan()[0]

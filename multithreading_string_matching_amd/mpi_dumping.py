@@ -14,6 +14,8 @@ kmpgpu_scan_enqueue) and the only exchange is the all-reduce of the counters -- 
 (backend "nccl"); "gloo" (KMPGPU_DIST_BACKEND=gloo) rehearses the same program on a box with fewer
 GPUs than ranks.  Argument handling, messages and exit codes follow mpi_dumping.c:48-67,73-78,110-142
 (the usage lines name ./serial: the reference's own slip).
+
+KMPGPU_NOCASE=1 (as in bin/serial): every pattern is matched case-insensitively (ASCII letters; kmpgpu_set_patterns_flags).
 """
 from __future__ import annotations
 
@@ -106,7 +108,10 @@ def count_and_report(m, patterns, pcap_path, proto, rank, world, dev, out=None) 
         if not hasattr(m, "scan_enqueue"):               # a factory: the context is created here, under the flag
             m = own = m()
         if patterns:
-            m.set_patterns(patterns)
+            if os.environ.get("KMPGPU_NOCASE", "") == "1":
+                m.set_patterns(patterns, nocase=True)
+            else:
+                m.set_patterns(patterns)
         m.load_pcap_frames(pcap_path, proto, rank, world)       # this rank's frames: extraction on the GPU
     except KmpHostError as e:                            # mpi_dumping.c:110-114,135-142: message on rank 0, every rank leaves with 0
         if rank == 0:
