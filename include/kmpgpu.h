@@ -261,6 +261,31 @@ int  kmpgpu_profile_end(kmpgpu_ctx *ctx, float *ms_out, uint32_t *n);
 int  kmpgpu_scan_offsets(kmpgpu_ctx *ctx, kmpgpu_match *out, uint64_t cap, uint64_t *n_found,
                          uint64_t *counts_out);
 
+/* Which payloads hold which patterns (grep -l / grep -c per payload, an alert per packet, the filter in front of a packet
+ * export): one bit per (pattern, payload), made on the device in one pass.  With c[k][i] the count defined at the top of
+ * this file for payload k and pattern i (E_k, overlapping starts, KMPGPU_PAT_NOCASE where the pattern carries it):
+ *     hit[i][k]     = c[k][i] >= 1
+ *     pkt_counts[i] = sum over k of hit[i][k]         (payloads that hold pattern i)
+ *     any[k]        = OR over i of hit[i][k]          (payload k holds at least one pattern)
+ *     counts[i]     = sum over k of c[k][i]           (exactly what kmpgpu_scan returns)
+ * Duplicate patterns get identical rows, one per index; an empty payload never hits.
+ * Layout: W = ceil(n_pkts / 64) words per row; payload k is bit (k & 63) of word (k >> 6), LSB first; row i of hits_out
+ * starts at hits_out + i * W; the bits of index n_pkts and above are 0.  Every output may be NULL:
+ * pkt_counts_out[n_pat], any_out[W], hits_out[n_pat * W], counts_out[n_pat].
+ * Synchronous, on the context's stream; *t (may be NULL) gets kernel_ms (zeroing + scan launches + reduce), d2h_ms and
+ * launches.  Preconditions and errors as kmpgpu_scan_offsets: streaming kernels only (KMPGPU_OPT_MODE 1 or KMPGPU_OPT_KERNEL
+ * 1: KMPGPU_EINVAL), an arena kept in place with KMPGPU_OPT_REPACK = 0 is packed once, no patterns: KMPGPU_ESTATE; with
+ * n_pkts == 0 every output is 0 and nothing is launched.  The pass writes to buffers of its own: the context's counters (a
+ * running total under KMPGPU_OPT_ACCUMULATE, the result of a count reduce) stay as they are.
+ * Cost: the scan kernels of kmpgpu_scan_offsets, which set the bit of a (pattern, payload) pair with one atomic OR per
+ * distinct pair per wavefront and call instead of writing records, then one read of the bit matrix.  That matrix is device
+ * memory owned by the context, n_pat x W x 8 bytes (97 patterns x 1 M payloads: 12 MB; 4 000 x 8 M: 4 GB), grown like the
+ * other buffers, zeroed before every pass and freed by kmpgpu_destroy; when it cannot be allocated the call fails with
+ * KMPGPU_ENOMEM / KMPGPU_EHIP and the context stays usable. */
+int  kmpgpu_scan_packets(kmpgpu_ctx *ctx, uint64_t *pkt_counts_out /* [n_pat] or NULL */,
+                         uint64_t *any_out /* [W] or NULL */, uint64_t *hits_out /* [n_pat * W] or NULL */,
+                         uint64_t *counts_out /* [n_pat] or NULL */, kmpgpu_timing *t /* or NULL */);
+
 /* Fill a device arena with the synthetic payloads of kmp_synth.h (benchmark input S1/S2):
  * packet ids first_pkt_id .. first_pkt_id + n_pkts - 1 at the slots of the given device index. */
 int  kmpgpu_synth_fill(kmpgpu_ctx *ctx, void *d_arena, const void *d_pkt_off, const void *d_pkt_len,

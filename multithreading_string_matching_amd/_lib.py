@@ -147,6 +147,7 @@ GPU_API = {
     "kmpgpu_profile_begin": (C.c_int, [C.c_void_p, C.c_uint32]),
     "kmpgpu_profile_end": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), u32p]),
     "kmpgpu_scan_offsets": (C.c_int, [C.c_void_p, C.POINTER(Match), C.c_uint64, u64p, u64p]),
+    "kmpgpu_scan_packets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
     "kmpgpu_synth_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(SynthParams)]),
     "kmpgpu_fixed_index": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32]),
     "kmpgpu_arena_info": (C.c_int, [C.c_void_p, u64p, u64p]),

@@ -17,6 +17,8 @@
  * Extension (the reference prints counts only, serial.c:163-166): with the environment variable
  * KMPGPU_OFFSETS_FILE=<path> every match is also written to <path> as "payload,offset,pattern"
  * lines (payload = index among the extracted payloads, pattern = index in the pattern file).
+ * KMPGPU_PACKETS_FILE=<path>: which payloads hold which patterns (kmpgpu_scan_packets), one "payload,pattern" line per
+ * pair that holds at least one match, sorted by payload, then by pattern (indices as in the offsets file).
  *
  * KMPGPU_NOCASE=1: every pattern matches case-insensitively (ASCII letters; kmpgpu_set_patterns_flags), in the counts and in
  * the offsets file alike; the report prints every token as written in the pattern file.
@@ -322,6 +324,29 @@ int main(int argc, char *argv[])
                 shard_lo += np;
             }
             fclose(off_fp);
+        }
+        const char *pk_path = getenv("KMPGPU_PACKETS_FILE");
+        if (pk_path && pk_path[0]) {
+            FILE *pk_fp = fopen(pk_path, "w");
+            if (!pk_fp) { perror("KMPGPU_PACKETS_FILE"); exit(1); }
+            uint64_t shard_lo = 0;                                          /* payload index of the shard's first payload */
+            for (int r = 0; r < shards; r++) {
+                uint64_t np = 0;
+                kmpgpu_arena_info(ctxs[r], &np, NULL);
+                const uint64_t W = (np + 63) / 64;
+                uint64_t *any = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)(W ? W : 1));
+                uint64_t *hits = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)(W ? W : 1) * pats.n);
+                if (!any || !hits || kmpgpu_scan_packets(ctxs[r], NULL, any, hits, NULL, NULL)) die_gpu("kmpgpu_scan_packets");
+                for (uint64_t k = 0; k < np; k++) {
+                    const uint64_t bit = 1ull << (k & 63);
+                    if (!(any[k >> 6] & bit)) continue;
+                    for (uint32_t i = 0; i < pats.n; i++)
+                        if (hits[(size_t)i * W + (k >> 6)] & bit) fprintf(pk_fp, "%llu,%u\n", (unsigned long long)(shard_lo + k), i);
+                }
+                free(any); free(hits);
+                shard_lo += np;
+            }
+            fclose(pk_fp);
         }
         for (int r = 0; r < shards && want_stats; r++) {
             uint64_t e = 0;

@@ -126,18 +126,46 @@ __device__ __forceinline__ PatConst load_pat_const(const kmp_pattern_dev *gp)
 
 /* Match-offset emission (kmpgpu_scan_offsets): {packet, offset, pattern} appended to a device
  * buffer.  The lanes that found a match are compacted with a ballot: one atomic add per wavefront
- * reserves their slots, each lane's rank inside the ballot (mbcnt) is its slot. */
+ * reserves their slots, each lane's rank inside the ballot (mbcnt) is its slot.
+ * Mark mode (kmpgpu_scan_packets, marks != NULL): no record; bit `pkt` of row `pattern` of the hit matrix
+ * marks[rows][stride] is set instead.  The members behind `pattern` grow the struct by 16 bytes, so that
+ * the kernel arguments that follow it keep their alignment. */
 struct Emitter {
     uint4              *out;        /* kmpgpu_match[cap] viewed as 16-byte records */
     unsigned long long *counter;    /* matches found so far (may exceed cap)       */
     unsigned long long  cap;
     uint32_t            pattern;
+    unsigned long long *marks;      /* mark mode: the hit matrix, or NULL          */
+    uint32_t            mark_stride;/* 64-bit words per row (>= ceil(n_pkts / 64)) */
+    uint32_t            mark_rows;  /* rows (patterns)                             */
 };
+
+/* Mark mode: the (pattern, packet) pairs of the ok lanes, one atomic OR per DISTINCT pair.  A 1 KiB chunk spans a few
+ * packets at most, so the lanes of a call collapse into one or two pairs: take the first lane's pair, drop every lane
+ * that has the same one, let one lane set the bit, repeat: the wave deduplicates before it issues an atomic.  Dense
+ * text -- a match at every offset -- costs one atomic per call and packet, not one per match. */
+__device__ __forceinline__ void mark_match_as(bool ok, uint64_t pkt, uint32_t pattern, const Emitter &e)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    uint64_t b = ballot64(ok);                       /* among the lanes that are active here */
+    while (b != 0ull) {
+        const uint32_t l = (uint32_t)__builtin_ctzll(b);
+        const uint32_t pl = (uint32_t)__builtin_amdgcn_readlane((int)pattern, (int)l);
+        const uint32_t klo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)pkt, (int)l);
+        const uint32_t khi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(pkt >> 32), (int)l);
+        const uint64_t k = ((uint64_t)khi << 32) | klo;
+        b &= ~ballot64(ok && pattern == pl && pkt == k);
+        /* (the bounds hold for every counted match; checked all the same: a stray index must not write outside the matrix) */
+        if (lane == l && pl < e.mark_rows && (k >> 6) < e.mark_stride)
+            atomicOr(e.marks + (uint64_t)pl * e.mark_stride + (k >> 6), 1ull << (k & 63u));
+    }
+}
 
 template <bool EMIT>
 __device__ __forceinline__ void emit_match_as(bool ok, uint64_t pkt, uint32_t offset, uint32_t pattern, const Emitter &e)
 {
     if (!EMIT) return;
+    if (e.marks) { mark_match_as(ok, pkt, pattern, e); return; }      /* a kernel argument: wave-uniform */
     const uint64_t b = ballot64(ok);                 /* among the lanes that are active here */
     if (b == 0ull) return;
     const uint32_t leader = (uint32_t)__builtin_ctzll(b);

@@ -40,7 +40,14 @@ struct kmp_scan_args {
     void                  *emit_out;
     unsigned long long    *emit_counter;
     unsigned long long     emit_cap;
+    /* hit-matrix marking (kmpgpu_scan_packets): bit k of row i of emit_marks[mark_rows][mark_stride] is set where payload k
+     * holds pattern i.  Runs the same EMIT kernels, grid and plan as the offsets pass, writing no record */
+    unsigned long long    *emit_marks;
+    uint32_t               mark_stride, mark_rows;
 };
+
+/* the pass writes offset records or marks: the launchers take the EMIT instantiations */
+static inline bool kmp_emits(const kmp_scan_args &a) { return a.emit_out != nullptr || a.emit_marks != nullptr; }
 
 hipError_t kmp_launch_scan(const kmp_scan_args &a, hipStream_t st);
 hipError_t kmp_launch_scan_flat(const kmp_scan_args &a, hipStream_t st);
@@ -85,6 +92,10 @@ hipError_t kmp_launch_add_counts(unsigned long long *dst, const unsigned long lo
  * of the furthest slot of an index (atomicMax into *end, which the caller zeroes) */
 hipError_t kmp_launch_fold(const uint8_t *src, uint8_t *dst, uint64_t bytes, hipStream_t st);
 hipError_t kmp_launch_slot_end(const uint64_t *pkt_off, const uint32_t *pkt_len, uint64_t n, unsigned long long *end, hipStream_t st);
+/* kmp_marks.hip: per row of the hit matrix marks[n_rows][stride] (stride even, the matrix 16-byte aligned) the number of set bits,
+ * added to pkt_counts[row], and per column word the OR over all rows, ORed into any[word]; both zeroed by the caller */
+hipError_t kmp_launch_marks_reduce(const unsigned long long *marks, uint32_t n_rows, uint64_t stride, unsigned long long *pkt_counts,
+                                   unsigned long long *any, hipStream_t st);
 hipError_t kmp_launch_fixed_index(uint64_t *pkt_off, uint32_t *pkt_len, uint64_t n, uint32_t len, uint64_t stride,
                                   hipStream_t st);
 

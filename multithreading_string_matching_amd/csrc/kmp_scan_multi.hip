@@ -784,11 +784,11 @@ hipError_t kmp_launch_scan_multi(const kmp_scan_args &a, const uint32_t *tables,
 {
     if (n_unique == 0 || a.blocks_x == 0 || a.fused_blocks == 0) return hipSuccess;
     const kmp_plan_entry *plan = reinterpret_cast<const kmp_plan_entry *>(a.plan);
-    const int kind = kmp_multi_kind(a.emit_out != nullptr, a.pad_clean, n_ones);
+    const int kind = kmp_multi_kind(kmp_emits(a), a.pad_clean, n_ones);
     const uint32_t bwaves = kmp_multi_block_waves(kind);
     const bool classed = a.fused_classed;
     const size_t lds = kmp_multi_lds_bytes(table_words, n_unique, bwaves) - KMP_MULTI_STATIC_BYTES;      /* the dynamic part */
-    const Emitter em{reinterpret_cast<uint4 *>(a.emit_out), a.emit_counter, a.emit_cap, 0u};
+    const Emitter em{reinterpret_cast<uint4 *>(a.emit_out), a.emit_counter, a.emit_cap, 0u, a.emit_marks, a.mark_stride, a.mark_rows};
     /* tuning builds only (make HIPFLAGS+=-DKMP_MULTI_TUNING; tools/fused_ablation.py, profiles/r02_fused_ablation.txt): cut the
      * kernel after a stage -- 1 = level 1 alone, 2 = + hit masking, 3 = + queueing; the counts are wrong then.  The product
      * build passes the constant 0. */
@@ -810,7 +810,7 @@ hipError_t kmp_launch_scan_multi(const kmp_scan_args &a, const uint32_t *tables,
         else if (n_ones) KMP_MULTI_LAUNCH1(kmp_scan_multi_wide_kernel, NT_, CLEAN_, true);                                           \
         else if (!(CLEAN_)) KMP_MULTI_LAUNCH1(kmp_scan_multi_wide_kernel, NT_, CLEAN_, false);                                       \
         else KMP_MULTI_LAUNCH1(kmp_scan_multi_kernel, NT_, true, false); } while (0)
-    if (a.emit_out) { if (a.pad_clean) KMP_MULTI_LAUNCH(true, true, true); else KMP_MULTI_LAUNCH(true, true, false); }
+    if (kmp_emits(a)) { if (a.pad_clean) KMP_MULTI_LAUNCH(true, true, true); else KMP_MULTI_LAUNCH(true, true, false); }
     else if (a.pad_clean) { if (a.nontemporal) KMP_MULTI_LAUNCH(false, true, true); else KMP_MULTI_LAUNCH(false, false, true); }
     else                  { if (a.nontemporal) KMP_MULTI_LAUNCH(false, true, false); else KMP_MULTI_LAUNCH(false, false, false); }
 #undef KMP_MULTI_LAUNCH

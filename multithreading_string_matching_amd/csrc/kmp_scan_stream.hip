@@ -394,6 +394,9 @@ Emitter emitter_of(const kmp_scan_args &a)
     e.counter = a.emit_counter;
     e.cap = a.emit_cap;
     e.pattern = 0;
+    e.marks = a.emit_marks;
+    e.mark_stride = a.mark_stride;
+    e.mark_rows = a.mark_rows;
     return e;
 }
 
@@ -403,7 +406,7 @@ hipError_t launch_flat_t(const kmp_scan_args &a, hipStream_t st)
     dim3 grid(a.blocks_x, a.n_ids), block(KMP_BLOCK_THREADS);
     const Emitter em = emitter_of(a);
 #define KMP_FLAT_ARGS a.arena, a.n_pkts, a.uniform_stride, a.uniform_len, a.pkts_per_wave, a.patterns, a.pat_ids, a.partials, a.zero_counts, em
-    if (a.emit_out)
+    if (kmp_emits(a))
         hipLaunchKernelGGL((kmp_scan_flat_kernel<4, true, true>), grid, block, 0, st, KMP_FLAT_ARGS);
     else if (a.nontemporal)
         hipLaunchKernelGGL((kmp_scan_flat_kernel<DEPTH, true>), grid, block, 0, st, KMP_FLAT_ARGS);
@@ -422,7 +425,7 @@ hipError_t launch_packed_t(const kmp_scan_args &a, hipStream_t st)
     const kmp_plan_entry *plan = reinterpret_cast<const kmp_plan_entry *>(a.plan);
     const Emitter em = emitter_of(a);
 #define KMP_PACKED_ARGS a.arena, a.pkt_off, a.pkt_len, a.bitmap, plan, a.patterns, a.pat_ids, a.partials, a.zero_counts, em, (a.pad_clean ? 1u : 0u)
-    if (a.emit_out)
+    if (kmp_emits(a))
         hipLaunchKernelGGL((kmp_scan_packed_kernel<4, true, true>), grid, block, 0, st, KMP_PACKED_ARGS);
     else if (a.nontemporal)
         hipLaunchKernelGGL((kmp_scan_packed_kernel<DEPTH, true>), grid, block, 0, st, KMP_PACKED_ARGS);

@@ -146,6 +146,8 @@ struct kmpgpu_ctx {
     size_t              h_counts_cap = 0;
     unsigned long long *h_small = nullptr;            /* pinned, 16 words: where the loaders read small device results back (a copy to pageable
                                                          memory goes through the runtime's blocking staging path) */
+    unsigned long long *d_marks = nullptr;            /* kmpgpu_scan_packets: hit matrix [n_pat][stride], then pkt_counts[n_pat], any[stride], counts[n_pat] */
+    uint64_t            marks_cap = 0;                /* words */
 
     /* options */
     int mode = 0, blocks_per_cu = 0 /* auto */, depth = 0 /* auto */, nontemporal = 1, kernel_sel = 0, fused = 2 /* auto */, accumulate = 0, repack = 1;
@@ -455,7 +457,10 @@ int prepare_packed(kmpgpu_ctx *c)
 }
 
 /* Enqueue one full pass: scan launches (patterns grouped by "shorter than 4 bytes") + reduce. */
-struct EmitTarget { void *out = nullptr; unsigned long long *counter = nullptr; unsigned long long cap = 0; };
+struct EmitTarget {
+    void *out = nullptr; unsigned long long *counter = nullptr; unsigned long long cap = 0;
+    unsigned long long *marks = nullptr; uint32_t mark_stride = 0;       /* kmpgpu_scan_packets: the hit matrix instead of records */
+};
 
 /* Partial counts of one set's pass: a row per pattern -- or, where the fused pass runs, a row per id of its largest group (a classed group
  * numbers its patterns by bucket class, up to 1024 ids however few patterns it has) and one per pattern that keeps a pass of its own. */
@@ -480,7 +485,10 @@ int enqueue_set(kmpgpu_ctx *c, const kmpgpu_ctx::PatternSet &s, const uint8_t *a
     a.patterns = c->d_patterns; a.blocks_x = bx; a.depth = c->depth; /* 0: the launcher's own default */ a.mode = c->mode;
     a.nontemporal = c->nontemporal != 0;
     a.pad_clean = c->pad_clean;
-    if (emit) { a.emit_out = emit->out; a.emit_counter = emit->counter; a.emit_cap = emit->cap; }
+    if (emit) {
+        a.emit_out = emit->out; a.emit_counter = emit->counter; a.emit_cap = emit->cap;
+        a.emit_marks = emit->marks; a.mark_stride = emit->mark_stride; a.mark_rows = c->n_pat;
+    }
     /* uniform-stride arenas take the flat streaming kernel (contiguous packet run per wavefront) */
     const uint64_t nwaves = (uint64_t)bx * KMP_BLOCK_WAVES;
     uint64_t ppw = (c->n_pkts + nwaves - 1) / nwaves;
@@ -644,7 +652,8 @@ int enqueue_set(kmpgpu_ctx *c, const kmpgpu_ctx::PatternSet &s, const uint8_t *a
             hipEvent_t e0, e1;
             HIP_TRY(record(e0, e1));
             if (emit && !flat && !packed)
-                return fail(KMPGPU_EINVAL, "kmpgpu_scan_offsets: the arena could not be brought into the streaming kernels' layout");
+                return fail(KMPGPU_EINVAL, "%s: the arena could not be brought into the streaming kernels' layout",
+                            emit->marks ? "kmpgpu_scan_packets" : "kmpgpu_scan_offsets");
             HIP_TRY(flat ? kmp_launch_scan_flat(a, c->stream) : packed ? kmp_launch_scan_packed(a, c->stream) : kmp_launch_scan(a, c->stream));
             if (e0) { HIP_TRY(hipEventRecord(e1, c->stream)); c->prof_n++; }
             HIP_TRY(kmp_launch_reduce(a.partials, bx, a.pat_ids, n, d_out, c->stream, nullptr, c->accumulate, sliced));
@@ -969,6 +978,7 @@ void kmpgpu_destroy(kmpgpu_ctx *c)
     if (c->d_patterns) (void)hipFree(c->d_patterns);
     if (c->d_partials) (void)hipFree(c->d_partials);
     if (c->d_counts) (void)hipFree(c->d_counts);
+    if (c->d_marks) (void)hipFree(c->d_marks);
     if (c->d_plan) (void)hipFree(c->d_plan);
     if (c->d_uplan) (void)hipFree(c->d_uplan);
     if (c->d_pool) (void)hipFree(c->d_pool);
@@ -1560,6 +1570,83 @@ int kmpgpu_scan_offsets(kmpgpu_ctx *c, kmpgpu_match *out, uint64_t cap, uint64_t
     (void)hipFree(d_out);
     if (d_cnt) (void)hipFree(d_cnt);
     return rc;
+}
+
+int kmpgpu_scan_packets(kmpgpu_ctx *c, uint64_t *pkt_counts_out, uint64_t *any_out, uint64_t *hits_out, uint64_t *counts_out, kmpgpu_timing *t)
+{
+    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_scan_packets: ctx is NULL");
+    if (c->mode != 0 || c->kernel_sel == 1) return fail(KMPGPU_EINVAL, "kmpgpu_scan_packets runs on the streaming kernels only (mode 0, kernel 0, 2 or 3)");
+    if (!c->d_patterns || c->n_pat == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan_packets: no patterns set");
+    if (!c->d_off && c->n_pkts) return fail(KMPGPU_ESTATE, "kmpgpu_scan_packets: no arena loaded");
+    HIP_TRY(hipSetDevice(c->device));
+    const uint64_t W = (c->n_pkts + 63u) / 64u;
+    const size_t np = c->n_pat;
+    if (c->n_pkts == 0) {
+        /* nothing to scan: every payload count, every total is 0, and there are no bit words */
+        if (pkt_counts_out) memset(pkt_counts_out, 0, np * sizeof(uint64_t));
+        if (counts_out) memset(counts_out, 0, np * sizeof(uint64_t));
+        if (t) { *t = kmpgpu_timing{}; }
+        return KMPGPU_OK;
+    }
+    /* rows of an even number of words: the reduce reads 16 bytes per lane */
+    const uint64_t stride = (W + 1u) & ~1ull;
+    if (stride > 0xFFFFFFFEull) return fail(KMPGPU_EINVAL, "kmpgpu_scan_packets: too many payloads for the hit matrix");
+    if (!c->packed) {
+        /* an arena kept in place (KMPGPU_OPT_REPACK = 0) whose slots are not back to back: packed now, once (kmpgpu_scan_offsets) */
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        const int keep = c->repack;
+        c->repack = 1;
+        const int rr = prepare_packed(c);
+        c->repack = keep;
+        if (rr) return rr;
+    }
+    /* one device buffer, grown like the others: [marks n_pat x stride][pkt_counts n_pat][any stride][counts n_pat] */
+    const uint64_t mat = (uint64_t)np * stride;
+    const uint64_t words = mat + np + stride + np;
+    hipError_t e = grow_buffer(&c->d_marks, &c->marks_cap, words);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? KMPGPU_ENOMEM : KMPGPU_EHIP, "kmpgpu_scan_packets: the hit matrix (%llu bytes) could not be allocated: %s",
+                    (unsigned long long)(words * 8u), hipGetErrorString(e));
+    }
+    unsigned long long *d_mat = c->d_marks, *d_pc = d_mat + mat, *d_any = d_pc + np, *d_cnt = d_any + stride;
+    uint32_t launches = 0;
+    HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+    /* zeroed before every pass: the bits of an earlier (larger) arena must not leak into this one */
+    HIP_TRY(hipMemsetAsync(d_mat, 0, (size_t)words * sizeof(unsigned long long), c->stream));
+    {
+        /* the pass writes its counts to a buffer of its own and never accumulates: the context's counters stay as they are */
+        EmitTarget tg;
+        tg.out = nullptr; tg.counter = nullptr; tg.cap = 0;
+        tg.marks = d_mat; tg.mark_stride = (uint32_t)stride;
+        const int acc = c->accumulate;
+        c->accumulate = 0;
+        const int rc = enqueue_pass(c, &launches, d_cnt, &tg);
+        c->accumulate = acc;
+        if (rc) return rc;
+    }
+    HIP_TRY(kmp_launch_marks_reduce(d_mat, c->n_pat, stride, d_pc, d_any, c->stream));
+    ++launches;
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    if (pkt_counts_out) HIP_TRY(hipMemcpyAsync(pkt_counts_out, d_pc, np * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (any_out) HIP_TRY(hipMemcpyAsync(any_out, d_any, W * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, d_cnt, np * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (hits_out) {
+        if (stride == W) HIP_TRY(hipMemcpyAsync(hits_out, d_mat, (size_t)mat * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        else HIP_TRY(hipMemcpy2DAsync(hits_out, W * sizeof(uint64_t), d_mat, stride * sizeof(uint64_t), W * sizeof(uint64_t), np,
+                                      hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (t) {
+        float k_ms = 0, d_ms = 0;
+        HIP_TRY(hipEventElapsedTime(&k_ms, c->ev[0], c->ev[1]));
+        HIP_TRY(hipEventElapsedTime(&d_ms, c->ev[1], c->ev[2]));
+        *t = kmpgpu_timing{};
+        t->kernel_ms = k_ms; t->d2h_ms = d_ms; t->launches = launches;
+        t->grid_blocks = grid_blocks(c, primary_set(c), true);
+    }
+    return KMPGPU_OK;
 }
 
 int kmpgpu_synth_fill(kmpgpu_ctx *c, void *d_arena, const void *d_pkt_off, const void *d_pkt_len, uint64_t first_pkt_id,

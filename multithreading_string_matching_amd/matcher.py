@@ -190,6 +190,28 @@ class GpuMatcher:
         arr = np.frombuffer(buf, dtype=np.dtype([("packet", "<u8"), ("offset", "<u4"), ("pattern", "<u4")]), count=k).copy()
         return arr, int(found.value), counts[:n]
 
+    def scan_packets(self, hits: bool = False) -> dict:
+        """Which payloads hold which patterns (kmpgpu_scan_packets), one pass on the device:
+        ``pkt_counts`` (uint64[n_pat]) payloads that hold pattern i, ``any`` (bool[n_pkts]) payload k holds some pattern,
+        ``counts`` (uint64[n_pat]) as scan(), ``timing``; with hits=True also ``hits`` (bool[n_pat, n_pkts])."""
+        n = len(self.patterns)
+        n_pkts, _ = self.arena_info()
+        W = (n_pkts + 63) // 64
+        pkt_counts = np.zeros(max(n, 1), dtype=np.uint64)
+        counts = np.zeros(max(n, 1), dtype=np.uint64)
+        any_w = np.zeros(max(W, 1), dtype=np.uint64)
+        hit_w = np.zeros((n, W) if hits and n * W else 1, dtype=np.uint64)
+        t = Timing()
+        gpu_check(self._g.kmpgpu_scan_packets(self._ctx, pkt_counts.ctypes.data, any_w.ctypes.data,
+                                              hit_w.ctypes.data if hits else None, counts.ctypes.data, C.byref(t)),
+                  "kmpgpu_scan_packets")
+        out = {"pkt_counts": pkt_counts[:n], "counts": counts[:n], "timing": t,
+               "any": np.unpackbits(any_w[:W].view(np.uint8), bitorder="little")[:n_pkts].astype(bool)}
+        if hits:
+            bits = np.unpackbits(hit_w.reshape(n, W).view(np.uint8), axis=1, bitorder="little") if n * W else np.zeros((n, 0), np.uint8)
+            out["hits"] = bits[:, :n_pkts].astype(bool)
+        return out
+
     # -- synthetic input (bench / tests) ---------------------------------------------------------
     def synth_fill(self, d_arena, d_off, d_len, sp: SynthParams, first_pkt_id: int = 0) -> None:
         gpu_check(self._g.kmpgpu_synth_fill(self._ctx, d_arena.data_ptr(), d_off.data_ptr(), d_len.data_ptr(), first_pkt_id,
