@@ -8,9 +8,14 @@
  * calls below (INTEGRATION.md shows the patch).  Library:
  * multithreading_string_matching_amd/lib/libkmpgpu.so (hipcc, --offload-arch=gfx950).
  *
- * Semantics (bit-exact with compiled serial.c): for payload k of length L_k,
- * E_k = min(L_k, index of its first 0x00); count[i] = sum over k of the number of start offsets
- * s with s + m_i <= E_k and payload_k[s : s+m_i] == pattern_i (overlapping starts all count).
+ * Semantics: payload k of length L_k is text up to E_k, and count[i] = sum over k of the number of start offsets s with
+ * s + m_i <= E_k and payload_k[s : s+m_i] == pattern_i (overlapping starts all count; a window never leaves its payload).
+ *   E_k = min(L_k, index of its first 0x00)   the reference's rule (kmp_matcher takes strlen() of the payload, serial.c:191;
+ *                                             SURVEY.md App. A), bit-exact with compiled serial.c.  The default.
+ *   E_k = L_k                                 whole payloads, KMPGPU_OPT_WHOLE_PAYLOAD = 1: a 0x00 is a text byte like any other
+ *                                             (which matches nothing: patterns hold none).  Not the reference's behaviour.
+ * Everything that counts, reports or marks matches -- kmpgpu_scan, kmpgpu_scan_enqueue, kmpgpu_scan_offsets,
+ * kmpgpu_scan_packets, with or without KMPGPU_PAT_NOCASE -- uses the E_k of the option's value at the time of the call.
  *
  * Conventions: plain pointers and sizes only; every function returns 0 or a negative KMPGPU_E*
  * code and never exits; kmpgpu_last_error() gives the text (per thread).  One context drives one GPU;
@@ -92,6 +97,12 @@ typedef struct kmpgpu_match {
                                         of 1024 up to 1 MiB; 0 = auto, 32 KiB; larger where a region has more than ~220 of
                                         them): a wavefront that is through its own share of the region takes the pool's
                                         units one after the other */
+#define KMPGPU_OPT_WHOLE_PAYLOAD 9   /* 0 (default) = a payload is text up to its first 0x00, the reference's strlen() rule; 1 = up to
+                                        its end (E_k = L_k, "Semantics" above); any other value: KMPGPU_EINVAL.  Pass state, not
+                                        arena or pattern state: it holds from the next pass on, for every way a pass is made, and may
+                                        be switched between two scans of one context with nothing reloaded, re-attached or re-set.
+                                        Patterns stay free of 0x00 either way.  The whole-payload kernels keep 4 chunk loads in
+                                        flight (the fused pass 3, as always): KMPGPU_OPT_DEPTH is accepted and has no effect on them */
 #define KMPGPU_OPT_NONTEMPORAL 100   /* 1 (default) = arena loads carry the non-temporal hint (every
                                         byte is read once per pass; measured +10 % on MI355X), 0 =
                                         default cache policy                                   */
@@ -129,7 +140,7 @@ int  kmpgpu_set_patterns(kmpgpu_ctx *ctx, const uint8_t *const *pat, const uint3
  * KMPGPU_PAT_NOCASE for pattern i; every other bit is reserved and rejected with KMPGPU_EINVAL.  kmpgpu_set_patterns(...) is
  * kmpgpu_set_patterns_flags(..., NULL, ...).  For a nocase pattern ASCII letters match either case (0x41..0x5A equal
  * 0x61..0x7A); every other byte compares exactly (0x40 '@', 0x5B '[', 0x60 '`', 0x7B '{' and all of 0x80..0xFF: 0xC1 is not
- * 0xE1); E_k, overlapping starts, 1..99 bytes and no 0x00 are as above.  Formally
+ * 0xE1); E_k (which follows KMPGPU_OPT_WHOLE_PAYLOAD), overlapping starts, 1..99 bytes and no 0x00 are as above.  Formally
  *     count_nocase(payloads, p) == count(fold(payloads), fold(p)),  fold = lowercase ASCII A-Z only,
  * and kmpgpu_scan_offsets reports the (packet, offset, pattern) of that formulation, pattern = the caller's index.  Flags are
  * per pattern: one set may mix both kinds, and the same bytes may appear with both flags, each index counted on its own.
@@ -253,7 +264,8 @@ int  kmpgpu_device_of(kmpgpu_ctx *ctx);
 int  kmpgpu_profile_begin(kmpgpu_ctx *ctx, uint32_t max_launches);
 int  kmpgpu_profile_end(kmpgpu_ctx *ctx, float *ms_out, uint32_t *n);
 
-/* Counts plus the matches themselves: every (packet, start offset, pattern) that counts, at most
+/* Counts plus the matches themselves: every (packet, start offset, pattern) that counts (E_k follows KMPGPU_OPT_WHOLE_PAYLOAD: with
+ * whole payloads the records behind a payload's first 0x00 appear), at most
  * cap of them written to out (host memory, unspecified order); *n_found is the total number found
  * (may exceed cap).  The pass writes its counts to a buffer of its own: the context's counters (a running total under
  * KMPGPU_OPT_ACCUMULATE, the result of a count reduce) stay as they are.  An arena that is scanned in place with slots
@@ -263,7 +275,8 @@ int  kmpgpu_scan_offsets(kmpgpu_ctx *ctx, kmpgpu_match *out, uint64_t cap, uint6
 
 /* Which payloads hold which patterns (grep -l / grep -c per payload, an alert per packet, the filter in front of a packet
  * export): one bit per (pattern, payload), made on the device in one pass.  With c[k][i] the count defined at the top of
- * this file for payload k and pattern i (E_k, overlapping starts, KMPGPU_PAT_NOCASE where the pattern carries it):
+ * this file for payload k and pattern i (E_k as KMPGPU_OPT_WHOLE_PAYLOAD says, overlapping starts, KMPGPU_PAT_NOCASE where the
+ * pattern carries it):
  *     hit[i][k]     = c[k][i] >= 1
  *     pkt_counts[i] = sum over k of hit[i][k]         (payloads that hold pattern i)
  *     any[k]        = OR over i of hit[i][k]          (payload k holds at least one pattern)
@@ -300,7 +313,8 @@ int  kmpgpu_fixed_index(kmpgpu_ctx *ctx, void *d_pkt_off, void *d_pkt_len, uint6
 int  kmpgpu_arena_info(kmpgpu_ctx *ctx, uint64_t *n_pkts, uint64_t *payload_bytes);
 /* Sum over payloads of min(len, first 0x00 + 1): the bytes a strlen()-bounded scan (serial.c:191) has to
  * touch; equals payload_bytes on NUL-free input.  Reported beside the payload bytes for inputs that carry
- * NUL bytes; one extra pass over the arena, not part of kmpgpu_scan. */
+ * NUL bytes; one extra pass over the arena, not part of kmpgpu_scan.  Always the strlen figure, whatever
+ * KMPGPU_OPT_WHOLE_PAYLOAD says: a whole-payload pass looks at all payload_bytes (kmpgpu_arena_info). */
 int  kmpgpu_effective_bytes(kmpgpu_ctx *ctx, uint64_t *bytes_out);
 /* Copy the context's device arena + index back to host buffers (tests: the on-device extraction must
  * build exactly the arena the host builds).  Buffers sized from kmpgpu_arena_info / arena_bytes. */

@@ -22,6 +22,10 @@
  *
  * KMPGPU_NOCASE=1: every pattern matches case-insensitively (ASCII letters; kmpgpu_set_patterns_flags), in the counts and in
  * the offsets file alike; the report prints every token as written in the pattern file.
+ *
+ * KMPGPU_WHOLE_PAYLOAD=1: a payload is matched up to its end instead of up to its first 0x00 (KMPGPU_OPT_WHOLE_PAYLOAD; not the
+ * reference's behaviour), in the counts, the offsets file and the packets file alike; KMPGPU_STATS=1 prints which rule was used.
+ * Unset or 0: the reference's rule, output as ever.
  */
 #include <errno.h>
 #include <pthread.h>
@@ -94,10 +98,19 @@ typedef struct shard_job {
     pthread_t thread;
 } shard_job;
 
+static int whole_payload_env(void)
+{
+    const char *e = getenv("KMPGPU_WHOLE_PAYLOAD");
+    return e && e[0] == '1' && e[1] == 0;
+}
+
 /* KMPGPU_NOCASE=1: every pattern is matched case-insensitively (ASCII letters, KMPGPU_PAT_NOCASE); the report prints the
  * tokens as written. */
 static int set_patterns_env(kmpgpu_ctx *c, const uint8_t *const *pp, const uint32_t *len, uint32_t n)
 {
+    /* KMPGPU_WHOLE_PAYLOAD=1: payloads are matched to their ends, not to their first 0x00 (KMPGPU_OPT_WHOLE_PAYLOAD); every context
+     * of the run passes through here */
+    if (whole_payload_env() && kmpgpu_set_option(c, KMPGPU_OPT_WHOLE_PAYLOAD, 1)) return KMPGPU_EINVAL;
     const char *e = getenv("KMPGPU_NOCASE");
     if (!(e && e[0] == '1' && e[1] == 0) || n == 0) return kmpgpu_set_patterns(c, pp, len, n);
     uint32_t *fl = (uint32_t *)malloc(n * sizeof *fl);
@@ -373,6 +386,7 @@ int main(int argc, char *argv[])
         fprintf(stderr, "[kmpgpu] kernel %.3f ms (%.2f GB/s payload x patterns, %.3g matches/s), h2d %.3f ms\n", kernel_ms,
                 bytes / (kernel_ms * 1e6), (double)total / (kernel_ms * 1e-3), h2d_ms);
         if (want_stats) {
+            fprintf(stderr, "[kmpgpu] text rule: %s\n", whole_payload_env() ? "whole payloads (KMPGPU_WHOLE_PAYLOAD=1)" : "up to a payload's first NUL (the reference's strlen)");
             fprintf(stderr, "[kmpgpu] %llu of the %llu payload bytes lie at or before the first NUL of their payload\n",
                     (unsigned long long)eff_bytes, (unsigned long long)arena.payload_bytes);
             fprintf(stderr, "[kmpgpu] phases: capture -> host buffers %.3f s, waiting for the HIP runtime %.3f s, contexts + upload + scan %.3f s\n",

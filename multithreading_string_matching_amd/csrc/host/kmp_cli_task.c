@@ -19,6 +19,8 @@
  * runtime's bounce buffers at 15 GB/s, and pinning them costs 55 ms per GB: profiles/r03_end_to_end_pinning_experiment.txt.)
  *
  * KMPGPU_NOCASE=1: every pattern matches case-insensitively (ASCII letters; kmpgpu_set_patterns_flags), in both routes.
+ * KMPGPU_WHOLE_PAYLOAD=1: payloads are matched to their ends, not to their first 0x00 (KMPGPU_OPT_WHOLE_PAYLOAD), in both routes and
+ * in every context of a shard; KMPGPU_STATS=1 prints which rule was used.
  *
  * stdout is byte-compatible with the reference (openmp_task.c:190-196).  No CPU fallback: exit code 2
  * without a gfx950 device.
@@ -121,10 +123,19 @@ static void *stage_batches(void *arg)
     }
 }
 
+static int whole_payload_env(void)
+{
+    const char *e = getenv("KMPGPU_WHOLE_PAYLOAD");
+    return e && e[0] == '1' && e[1] == 0;
+}
+
 /* KMPGPU_NOCASE=1: every pattern is matched case-insensitively (ASCII letters, KMPGPU_PAT_NOCASE); the report prints the
  * tokens as written. */
 static int set_patterns_env(kmpgpu_ctx *c, const uint8_t *const *pp, const uint32_t *len, uint32_t n)
 {
+    /* KMPGPU_WHOLE_PAYLOAD=1: payloads are matched to their ends, not to their first 0x00 (KMPGPU_OPT_WHOLE_PAYLOAD); every context
+     * of the run passes through here */
+    if (whole_payload_env() && kmpgpu_set_option(c, KMPGPU_OPT_WHOLE_PAYLOAD, 1)) return KMPGPU_EINVAL;
     const char *e = getenv("KMPGPU_NOCASE");
     if (!(e && e[0] == '1' && e[1] == 0) || n == 0) return kmpgpu_set_patterns(c, pp, len, n);
     uint32_t *fl = (uint32_t *)malloc(n * sizeof *fl);
@@ -435,6 +446,7 @@ int main(int argc, char *argv[])
     { const char *st = getenv("KMPGPU_STATS");
       if (st && st[0] && st[0] != '0') {
           double load_s = 0, wait_s = 0, h2d = 0;
+          fprintf(stderr, "[kmpgpu] text rule: %s\n", whole_payload_env() ? "whole payloads (KMPGPU_WHOLE_PAYLOAD=1)" : "up to a payload's first NUL (the reference's strlen)");
           for (int r = 0; r < (pats.n ? n_cons : 0); r++) { load_s += cons[r].load_s; wait_s += cons[r].wait_s; h2d += cons[r].h2d_ms; }
           fprintf(stderr, "[kmpgpu] phases: producer %.3f s building batches + %.3f s waiting for a free slot; staging copies %.3f s; consumers %.3f s in the load calls "
                           "(uploads by the events: %.3f s), %.3f s waiting for a batch\n",

@@ -22,6 +22,7 @@ struct kmp_scan_args {
     int                    mode;         /* 0 filter + confirm, 1 automaton only             */
     bool                   masked;       /* every pattern of this launch is shorter than 4   */
     bool                   nontemporal;
+    bool                   whole;        /* KMPGPU_OPT_WHOLE_PAYLOAD: E_k = L_k, the whole-payload instantiations */
     /* flat kernel only: every payload has length uniform_len, payload k starts at arena + k * uniform_stride */
     uint32_t               uniform_stride;
     uint32_t               uniform_len;

@@ -153,7 +153,8 @@ __device__ __forceinline__ uint32_t first_nul_pos(uint32_t w0, uint32_t w1, uint
  * Register ring: DEPTH chunk loads per wavefront, statically assigned (the loop body is unrolled
  * DEPTH times), so each s_waitcnt only waits for the chunk it consumes plus its successor (halo).
  */
-template <int DEPTH, bool MASKED, int MODE, bool NT>
+/* WHOLE (KMPGPU_OPT_WHOLE_PAYLOAD): the text ends at L and nowhere else -- no 0x00 test, and no packet is ever left early (dead_seq). */
+template <int DEPTH, bool MASKED, int MODE, bool NT, bool WHOLE = false>
 __global__ void __launch_bounds__(KMP_BLOCK_THREADS)
 kmp_scan_kernel(const uint8_t *__restrict__ arena, const uint64_t *__restrict__ pkt_off,
                 const uint32_t *__restrict__ pkt_len, uint64_t n_pkts,
@@ -209,9 +210,12 @@ kmp_scan_kernel(const uint8_t *__restrict__ arena, const uint64_t *__restrict__ 
                 const bool     inb        = p0 < ((L + 15u) & ~15u);     /* lane holds real slot bytes */
                 const uint32_t w[5] = {v.x, v.y, v.z, v.w, wave_shl1(v.x, sgpr(vn.x))};
 
-                const uint32_t zm = zero_byte_mask(w[0]) | zero_byte_mask(w[1]) | zero_byte_mask(w[2]) | zero_byte_mask(w[3]);
-                const uint64_t bz = __ballot(inb && zm != 0u);
-                if (bz != 0ull) dead_seq = me.seq;     /* the first NUL (or the slot padding) is in this chunk */
+                uint64_t bz = 0ull;
+                if constexpr (!WHOLE) {
+                    const uint32_t zm = zero_byte_mask(w[0]) | zero_byte_mask(w[1]) | zero_byte_mask(w[2]) | zero_byte_mask(w[3]);
+                    bz = __ballot(inb && zm != 0u);
+                    if (bz != 0ull) dead_seq = me.seq;     /* the first NUL (or the slot padding) is in this chunk */
+                }
 
                 if (MODE == 1) {
                     uint32_t Eloc = L;
@@ -279,7 +283,15 @@ template <int DEPTH, bool MASKED, int MODE>
 hipError_t launch_scan_t(const kmp_scan_args &a, hipStream_t st)
 {
     dim3 grid(a.blocks_x, a.n_ids), block(KMP_BLOCK_THREADS);
-    if (a.nontemporal)
+    if (a.whole) {
+        /* whole payloads: four chunks in flight (the default), whatever KMPGPU_OPT_DEPTH says */
+        if (a.nontemporal)
+            hipLaunchKernelGGL((kmp_scan_kernel<4, MASKED, MODE, true, true>), grid, block, 0, st, a.arena, a.pkt_off, a.pkt_len,
+                               a.n_pkts, a.patterns, a.pat_ids, a.partials);
+        else
+            hipLaunchKernelGGL((kmp_scan_kernel<4, MASKED, MODE, false, true>), grid, block, 0, st, a.arena, a.pkt_off, a.pkt_len,
+                               a.n_pkts, a.patterns, a.pat_ids, a.partials);
+    } else if (a.nontemporal)
         hipLaunchKernelGGL((kmp_scan_kernel<DEPTH, MASKED, MODE, true>), grid, block, 0, st, a.arena, a.pkt_off, a.pkt_len,
                            a.n_pkts, a.patterns, a.pat_ids, a.partials);
     else

@@ -80,7 +80,10 @@ __device__ __forceinline__ void shr_by_byte_into(uint32_t &acc, uint32_t word, u
 #undef KMP_SHR_SDWA
 }
 
-template <int DEPTH, bool NT, bool CLEAN, bool EMIT, bool ONES, uint32_t WAVES, bool CLASSED>
+/* WHOLE (KMPGPU_OPT_WHOLE_PAYLOAD): a payload is text up to its end, E = L.  No 0x00 masks, no `dead` carry, no nul_limit: the hit mask
+ * goes to the queue as level 1 made it (level 2 checks every hit's room, and no pattern holds a 0x00), the 1-byte patterns count every
+ * byte inside the payload. */
+template <int DEPTH, bool NT, bool CLEAN, bool EMIT, bool ONES, uint32_t WAVES, bool CLASSED, bool WHOLE>
 __device__ __forceinline__ void
 kmp_scan_multi_body(const uint8_t *__restrict__ arena, const uint32_t *__restrict__ pkt_len,
                       const unsigned long long *__restrict__ bitmap, const kmp_plan_entry *__restrict__ plan,
@@ -425,14 +428,18 @@ kmp_scan_multi_body(const uint8_t *__restrict__ arena, const uint32_t *__restric
 
                     const uint32_t w[5] = {v.x, v.y, v.z, v.w, wave_shl1(v.x, sgpr(bn.x))};
 
-                    const uint32_t z[4] = {zero_byte_mask(w[0]), zero_byte_mask(w[1]), zero_byte_mask(w[2]), zero_byte_mask(w[3])};
-                    const uint32_t zm = z[0] | z[1] | z[2] | z[3];
-                    const uint64_t zl = ballot64(zm != 0u);
+                    uint32_t z[4] = {0u, 0u, 0u, 0u};
+                    uint64_t zl = 0ull;
                     const bool dead_in = dead;
+                    if constexpr (!WHOLE) {
+                    z[0] = zero_byte_mask(w[0]); z[1] = zero_byte_mask(w[1]); z[2] = zero_byte_mask(w[2]); z[3] = zero_byte_mask(w[3]);
+                    const uint32_t zm = z[0] | z[1] | z[2] | z[3];
+                    zl = ballot64(zm != 0u);
                     if (zl != 0ull) {
                         asm volatile("" ::: "memory");
                         dead = (st == 0ull) ? true : ((zl >> (63u - (uint32_t)__builtin_clzll(st))) != 0ull);
                     } else dead = dead && st == 0ull;
+                    }
 
                     /* rem: payload bytes left from this lane's first byte; last_lanes: the lanes behind which a packet starts */
                     int32_t rem = 0;
@@ -543,7 +550,7 @@ kmp_scan_multi_body(const uint8_t *__restrict__ arena, const uint32_t *__restric
                         int32_t nl = 15;                                             /* last start offset no 0x00 precedes */
                         /* (the 1-byte patterns over clean padding take care of a lane's own 0x00 themselves, below) */
                         constexpr bool ONES_BY_MASK = ONES && CLEAN && !EMIT;
-                        const bool seg = dead_in || (zl & ~last_lanes) != 0ull;
+                        const bool seg = !WHOLE && (dead_in || (zl & ~last_lanes) != 0ull);       /* (whole payloads: zl and z[] are constant zeros, what tests them is not compiled) */
                         /* (the hit mask is cut down where nl is worked out, inside these branches: applied behind them it became nine
                          * instructions of selects on every chunk, with nl == 15 in all lanes on nearly all of them) */
                         if (seg) {
@@ -733,21 +740,44 @@ template <int DEPTH, bool NT, bool CLEAN, bool ONES, bool CLASSED>
 __global__ void __launch_bounds__(KMP_MULTI_BLOCK_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8)))
 kmp_scan_multi_kernel(KMP_MULTI_PARAMS)
 {
-    kmp_scan_multi_body<DEPTH, NT, CLEAN, false, ONES, KMP_MULTI_BLOCK_WAVES, CLASSED>(KMP_MULTI_ARGS);
+    kmp_scan_multi_body<DEPTH, NT, CLEAN, false, ONES, KMP_MULTI_BLOCK_WAVES, CLASSED, false>(KMP_MULTI_ARGS);
 }
 
 template <int DEPTH, bool NT, bool CLEAN, bool ONES, bool CLASSED>
 __global__ void __launch_bounds__(KMP_MULTI_WIDE_WAVES * KMP_WAVE) __attribute__((amdgpu_waves_per_eu(6, 6)))
 kmp_scan_multi_wide_kernel(KMP_MULTI_PARAMS)
 {
-    kmp_scan_multi_body<DEPTH, NT, CLEAN, false, ONES, KMP_MULTI_WIDE_WAVES, CLASSED>(KMP_MULTI_ARGS);
+    kmp_scan_multi_body<DEPTH, NT, CLEAN, false, ONES, KMP_MULTI_WIDE_WAVES, CLASSED, false>(KMP_MULTI_ARGS);
 }
 
 template <int DEPTH, bool NT, bool CLEAN, bool ONES, bool CLASSED>
 __global__ void __launch_bounds__(KMP_MULTI_BLOCK_THREADS)
 kmp_scan_multi_emit_kernel(KMP_MULTI_PARAMS)
 {
-    kmp_scan_multi_body<DEPTH, NT, CLEAN, true, ONES, KMP_MULTI_BLOCK_WAVES, CLASSED>(KMP_MULTI_ARGS);
+    kmp_scan_multi_body<DEPTH, NT, CLEAN, true, ONES, KMP_MULTI_BLOCK_WAVES, CLASSED, false>(KMP_MULTI_ARGS);
+}
+
+/* The same three for whole payloads (KMPGPU_OPT_WHOLE_PAYLOAD), block sizes and register budgets as their twins: the launch geometry
+ * (kmp_multi_kind, kmp_multi_resident_waves) does not know the difference. */
+template <int DEPTH, bool NT, bool CLEAN, bool ONES, bool CLASSED>
+__global__ void __launch_bounds__(KMP_MULTI_BLOCK_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8)))
+kmp_scan_multi_whole_kernel(KMP_MULTI_PARAMS)
+{
+    kmp_scan_multi_body<DEPTH, NT, CLEAN, false, ONES, KMP_MULTI_BLOCK_WAVES, CLASSED, true>(KMP_MULTI_ARGS);
+}
+
+template <int DEPTH, bool NT, bool CLEAN, bool ONES, bool CLASSED>
+__global__ void __launch_bounds__(KMP_MULTI_WIDE_WAVES * KMP_WAVE) __attribute__((amdgpu_waves_per_eu(6, 6)))
+kmp_scan_multi_whole_wide_kernel(KMP_MULTI_PARAMS)
+{
+    kmp_scan_multi_body<DEPTH, NT, CLEAN, false, ONES, KMP_MULTI_WIDE_WAVES, CLASSED, true>(KMP_MULTI_ARGS);
+}
+
+template <int DEPTH, bool NT, bool CLEAN, bool ONES, bool CLASSED>
+__global__ void __launch_bounds__(KMP_MULTI_BLOCK_THREADS)
+kmp_scan_multi_whole_emit_kernel(KMP_MULTI_PARAMS)
+{
+    kmp_scan_multi_body<DEPTH, NT, CLEAN, true, ONES, KMP_MULTI_BLOCK_WAVES, CLASSED, true>(KMP_MULTI_ARGS);
 }
 
 }  // namespace
@@ -801,19 +831,23 @@ hipError_t kmp_launch_scan_multi(const kmp_scan_args &a, const uint32_t *tables,
 #define KMP_MULTI_LAUNCH0(KERNEL_, NT_, CLEAN_, ONES_, CLASSED_) hipLaunchKernelGGL((KERNEL_<3, NT_, CLEAN_, ONES_, CLASSED_>), dim3(a.fused_blocks), \
         dim3(bwaves * KMP_WAVE), lds, st, a.arena, a.pkt_len, a.bitmap, plan, tables, table_words, n_unique, cshift, bucket_mask, n_ones, ones, ablate, a.n_units, a.units_per_block, a.fused_sides, a.fused_pool, a.span_end, a.blocks_x, \
         a.partials, em, uid_first, uid_ids, a.patterns)
-#define KMP_MULTI_LAUNCH(EMIT_K_, NT_, CLEAN_) do {                                                                               \
+#define KMP_MULTI_LAUNCH_K(K_, KW_, KE_, EMIT_K_, NT_, CLEAN_) do {                                                             \
         if (classed) {        /* (a classed group has no 1-byte patterns riding along) */                                             \
-            if (EMIT_K_) KMP_MULTI_LAUNCH0(kmp_scan_multi_emit_kernel, NT_, CLEAN_, false, true);                                     \
-            else if (!(CLEAN_)) KMP_MULTI_LAUNCH0(kmp_scan_multi_wide_kernel, NT_, CLEAN_, false, true);                              \
-            else KMP_MULTI_LAUNCH0(kmp_scan_multi_kernel, NT_, true, false, true);                                                    \
-        } else if (EMIT_K_) { if (n_ones) KMP_MULTI_LAUNCH1(kmp_scan_multi_emit_kernel, NT_, CLEAN_, true); else KMP_MULTI_LAUNCH1(kmp_scan_multi_emit_kernel, NT_, CLEAN_, false); } \
-        else if (n_ones) KMP_MULTI_LAUNCH1(kmp_scan_multi_wide_kernel, NT_, CLEAN_, true);                                           \
-        else if (!(CLEAN_)) KMP_MULTI_LAUNCH1(kmp_scan_multi_wide_kernel, NT_, CLEAN_, false);                                       \
-        else KMP_MULTI_LAUNCH1(kmp_scan_multi_kernel, NT_, true, false); } while (0)
+            if (EMIT_K_) KMP_MULTI_LAUNCH0(KE_, NT_, CLEAN_, false, true);                                                            \
+            else if (!(CLEAN_)) KMP_MULTI_LAUNCH0(KW_, NT_, CLEAN_, false, true);                                                     \
+            else KMP_MULTI_LAUNCH0(K_, NT_, true, false, true);                                                                       \
+        } else if (EMIT_K_) { if (n_ones) KMP_MULTI_LAUNCH1(KE_, NT_, CLEAN_, true); else KMP_MULTI_LAUNCH1(KE_, NT_, CLEAN_, false); } \
+        else if (n_ones) KMP_MULTI_LAUNCH1(KW_, NT_, CLEAN_, true);                                                                  \
+        else if (!(CLEAN_)) KMP_MULTI_LAUNCH1(KW_, NT_, CLEAN_, false);                                                              \
+        else KMP_MULTI_LAUNCH1(K_, NT_, true, false); } while (0)
+#define KMP_MULTI_LAUNCH(EMIT_K_, NT_, CLEAN_) do {                                                                               \
+        if (a.whole) KMP_MULTI_LAUNCH_K(kmp_scan_multi_whole_kernel, kmp_scan_multi_whole_wide_kernel, kmp_scan_multi_whole_emit_kernel, EMIT_K_, NT_, CLEAN_); \
+        else KMP_MULTI_LAUNCH_K(kmp_scan_multi_kernel, kmp_scan_multi_wide_kernel, kmp_scan_multi_emit_kernel, EMIT_K_, NT_, CLEAN_); } while (0)
     if (kmp_emits(a)) { if (a.pad_clean) KMP_MULTI_LAUNCH(true, true, true); else KMP_MULTI_LAUNCH(true, true, false); }
     else if (a.pad_clean) { if (a.nontemporal) KMP_MULTI_LAUNCH(false, true, true); else KMP_MULTI_LAUNCH(false, false, true); }
     else                  { if (a.nontemporal) KMP_MULTI_LAUNCH(false, true, false); else KMP_MULTI_LAUNCH(false, false, false); }
 #undef KMP_MULTI_LAUNCH
+#undef KMP_MULTI_LAUNCH_K
 #undef KMP_MULTI_LAUNCH1
 #undef KMP_MULTI_LAUNCH0
     return hipGetLastError();

@@ -118,6 +118,7 @@ struct kmpgpu_ctx {
     uint64_t        uplan_units = 0, uplan_cap = 0;
     kmp_plan_shape  uplan_shape{};                    /* what d_uplan was cut for */
     int             fused_unit = 0;                   /* KMPGPU_OPT_FUSED_UNIT */
+    int             whole_payload = 0;                /* KMPGPU_OPT_WHOLE_PAYLOAD: pass state, read when a pass is enqueued */
     uint64_t        uni_off0 = 0;
     uint32_t        uni_stride = 0, uni_len = 0;
     void           *owned_arena = nullptr, *owned_off = nullptr, *owned_len = nullptr;
@@ -484,6 +485,7 @@ int enqueue_set(kmpgpu_ctx *c, const kmpgpu_ctx::PatternSet &s, const uint8_t *a
     a.arena = arena; a.pkt_off = c->d_off; a.pkt_len = c->d_len; a.n_pkts = c->n_pkts;
     a.patterns = c->d_patterns; a.blocks_x = bx; a.depth = c->depth; /* 0: the launcher's own default */ a.mode = c->mode;
     a.nontemporal = c->nontemporal != 0;
+    a.whole = c->whole_payload != 0;
     a.pad_clean = c->pad_clean;
     if (emit) {
         a.emit_out = emit->out; a.emit_counter = emit->counter; a.emit_cap = emit->cap;
@@ -1030,6 +1032,9 @@ int kmpgpu_set_option(kmpgpu_ctx *c, int key, int64_t value)
     case KMPGPU_OPT_FUSED_UNIT:
         if (value != 0 && (value < 1024 || value > (1 << 20) || (value & 1023))) return fail(KMPGPU_EINVAL, "fused unit must be 0 (auto) or a multiple of 1024 up to 1 MiB");
         c->fused_unit = (int)value; return KMPGPU_OK;
+    case KMPGPU_OPT_WHOLE_PAYLOAD:
+        if (value != 0 && value != 1) return fail(KMPGPU_EINVAL, "whole payload must be 0 (text ends at a payload's first 0x00) or 1 (at its end)");
+        c->whole_payload = (int)value; return KMPGPU_OK;
     default:
         return fail(KMPGPU_EINVAL, "unknown option %d", key);
     }

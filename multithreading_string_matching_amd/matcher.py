@@ -21,6 +21,7 @@ from .host import HostArena
 OPT_MODE, OPT_BLOCKS_PER_CU, OPT_DEPTH, OPT_FUSED, OPT_KERNEL, OPT_ACCUMULATE, OPT_NONTEMPORAL = 1, 2, 3, 4, 5, 6, 100
 OPT_REPACK = 7
 OPT_FUSED_UNIT = 8
+OPT_WHOLE_PAYLOAD = 9   # 1: a payload is text up to its end, not up to its first 0x00 (kmpgpu.h, "Semantics")
 KERNEL_AUTO, KERNEL_GENERAL, KERNEL_PACKED, KERNEL_FLAT = 0, 1, 2, 3
 MODE_FILTER, MODE_AUTOMATON = 0, 1
 PAT_NOCASE = 1          # kmpgpu_set_patterns_flags: ASCII letters match either case
@@ -301,11 +302,14 @@ class GpuComm:
         self.close()
 
 
-def count_matches(patterns: Sequence[bytes], arena: HostArena, device: int = 0, nocase=False, **options) -> np.ndarray:
-    """One-shot helper: counts of every pattern over a host arena on one GPU (nocase: as GpuMatcher.set_patterns)."""
+def count_matches(patterns: Sequence[bytes], arena: HostArena, device: int = 0, nocase=False, whole_payload=False, **options) -> np.ndarray:
+    """One-shot helper: counts of every pattern over a host arena on one GPU (nocase: as GpuMatcher.set_patterns;
+    whole_payload: payloads are text up to their ends, OPT_WHOLE_PAYLOAD, instead of up to their first 0x00)."""
     with GpuMatcher(device) as m:
         for k, v in options.items():
             m.set_option({"mode": OPT_MODE, "depth": OPT_DEPTH, "blocks_per_cu": OPT_BLOCKS_PER_CU}[k], v)
+        if whole_payload:
+            m.set_option(OPT_WHOLE_PAYLOAD, 1)
         m.set_patterns(patterns, nocase=nocase)
         m.load_arena(arena)
         return m.scan()[0]

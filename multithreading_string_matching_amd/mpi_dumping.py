@@ -16,6 +16,7 @@ GPUs than ranks.  Argument handling, messages and exit codes follow mpi_dumping.
 (the usage lines name ./serial: the reference's own slip).
 
 KMPGPU_NOCASE=1 (as in bin/serial): every pattern is matched case-insensitively (ASCII letters; kmpgpu_set_patterns_flags).
+KMPGPU_WHOLE_PAYLOAD=1 (as in bin/serial): payloads are matched to their ends, not to their first 0x00 (KMPGPU_OPT_WHOLE_PAYLOAD).
 """
 from __future__ import annotations
 
@@ -100,6 +101,7 @@ def count_and_report(m, patterns, pcap_path, proto, rank, world, dev, out=None) 
     from . import dist as kd
     from . import host
     from ._lib import KmpGpuError, KmpHostError
+    from .matcher import OPT_WHOLE_PAYLOAD
 
     out = sys.stdout if out is None else out
     flag = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -107,6 +109,8 @@ def count_and_report(m, patterns, pcap_path, proto, rank, world, dev, out=None) 
     try:
         if not hasattr(m, "scan_enqueue"):               # a factory: the context is created here, under the flag
             m = own = m()
+        if os.environ.get("KMPGPU_WHOLE_PAYLOAD", "") == "1":
+            m.set_option(OPT_WHOLE_PAYLOAD, 1)
         if patterns:
             if os.environ.get("KMPGPU_NOCASE", "") == "1":
                 m.set_patterns(patterns, nocase=True)
