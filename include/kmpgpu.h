@@ -15,7 +15,7 @@
  *   E_k = L_k                                 whole payloads, KMPGPU_OPT_WHOLE_PAYLOAD = 1: a 0x00 is a text byte like any other
  *                                             (which matches nothing: patterns hold none).  Not the reference's behaviour.
  * Everything that counts, reports or marks matches -- kmpgpu_scan, kmpgpu_scan_enqueue, kmpgpu_scan_offsets,
- * kmpgpu_scan_packets, with or without KMPGPU_PAT_NOCASE -- uses the E_k of the option's value at the time of the call.
+ * kmpgpu_scan_packets, kmpgpu_scan_rules, with or without KMPGPU_PAT_NOCASE -- uses the E_k of the option's value at the time of the call.
  *
  * Conventions: plain pointers and sizes only; every function returns 0 or a negative KMPGPU_E*
  * code and never exits; kmpgpu_last_error() gives the text (per thread).  One context drives one GPU;
@@ -298,6 +298,47 @@ int  kmpgpu_scan_offsets(kmpgpu_ctx *ctx, kmpgpu_match *out, uint64_t cap, uint6
 int  kmpgpu_scan_packets(kmpgpu_ctx *ctx, uint64_t *pkt_counts_out /* [n_pat] or NULL */,
                          uint64_t *any_out /* [W] or NULL */, uint64_t *hits_out /* [n_pat * W] or NULL */,
                          uint64_t *counts_out /* [n_pat] or NULL */, kmpgpu_timing *t /* or NULL */);
+
+/* Content rules: AND / NOT of patterns per payload, evaluated on the device behind the marking pass of kmpgpu_scan_packets (a
+ * signature is several contents that must all be in one payload, often with one that must not be: "GET" and "/admin" and not
+ * "Host: intranet"; grep -l a | xargs grep -l b | xargs grep -L c).  Only the per-rule results leave the device.
+ * A rule is a non-empty list of terms; a term is a pattern index i < n_pat, | KMPGPU_RULE_NOT for a negated term.  With
+ * hit[i][k] exactly as kmpgpu_scan_packets defines it (E_k as KMPGPU_OPT_WHOLE_PAYLOAD says, KMPGPU_PAT_NOCASE per pattern):
+ *     rule_hit[r][k]     = AND over the positive terms i of hit[i][k]  AND  AND over the negated terms i of !hit[i][k]   (k < n_pkts)
+ *     rule_pkt_counts[r] = sum over k of rule_hit[r][k]     (payloads that rule r matches)
+ *     any[k]             = OR over r of rule_hit[r][k]      (payload k matches at least one rule)
+ * So: a rule of negated terms only matches every payload that holds none of them, empty payloads included; i and !i in one rule
+ * never matches; a term may repeat; rules may share patterns and may be identical, each rule index gets its own row.
+ * Layout as kmpgpu_scan_packets: W = ceil(n_pkts / 64) words per row, payload k is bit (k & 63) of word (k >> 6), LSB first; row r
+ * of rule_hits_out starts at rule_hits_out + r * W; the bits of index n_pkts and above are 0 in every output word, also for an
+ * all-negated rule.
+ *
+ * kmpgpu_set_rules copies the rules and uploads them: rule r = terms[rule_off[r] .. rule_off[r + 1]), rule_off[n_rules + 1].  They
+ * refer to the pattern set current at the call: no patterns set: KMPGPU_ESTATE; a later kmpgpu_set_patterns /
+ * kmpgpu_set_patterns_flags drops them (the indices would mean something else).  rule_off[0] != 0, a decreasing rule_off, a rule
+ * without terms or a term whose index is >= n_pat: KMPGPU_EINVAL, and the rules set before stay in force.  n_rules == 0 clears
+ * the rules.
+ *
+ * kmpgpu_scan_rules: synchronous, on the context's stream.  The marking pass of kmpgpu_scan_packets (the same code: zeroing, scan
+ * launches), then the rules kernel over the matrix instead of the pattern-level reduce; counts_out is what kmpgpu_scan returns.
+ * Every output may be NULL: rule_pkt_counts_out[n_rules], any_out[W], rule_hits_out[n_rules * W], counts_out[n_pat].
+ * Preconditions and errors as kmpgpu_scan_packets (streaming kernels only; an arena kept in place is packed once; with
+ * n_pkts == 0 every output is 0 and nothing is launched; the context's counters stay as they are, also under
+ * KMPGPU_OPT_ACCUMULATE); no rules set: KMPGPU_ESTATE.  *t (may be NULL): kernel_ms covers zeroing, scan launches and the rules
+ * kernel, launches counts the rules kernel; under kmpgpu_profile_begin the rules kernel is recorded as the last launch.
+ * kmpgpu_scan_packets returns the same before and after a kmpgpu_scan_rules on the context.
+ * Cost: the rules kernel reads (sum of the rules' terms) x W x 8 bytes of the matrix (less where a payload word has already run
+ * empty) and writes n_rules x W x 8.  Device memory, owned by the context next to the hit matrix, grown like the other buffers,
+ * written or zeroed in full by every pass and freed by kmpgpu_destroy: with W2 = 2 * ceil(W / 2),
+ *     (n_rules x W2  +  n_rules  +  W2) x 8 bytes      (100 rules x 1 M payloads: 12.5 MB; 4 000 x 8 M: 4 GB)
+ * and 16 bytes per rule + 16 per four terms behind a rule's first two for the rules themselves.  When the rows cannot be allocated
+ * the call fails with KMPGPU_ENOMEM / KMPGPU_EHIP and the context stays usable. */
+#define KMPGPU_RULE_NOT 0x80000000u     /* term = pattern index | KMPGPU_RULE_NOT for a negated term */
+int  kmpgpu_set_rules(kmpgpu_ctx *ctx, const uint32_t *rule_off /* [n_rules + 1], rule r = terms[rule_off[r] .. rule_off[r+1]) */,
+                      const uint32_t *terms, uint32_t n_rules);
+int  kmpgpu_scan_rules(kmpgpu_ctx *ctx, uint64_t *rule_pkt_counts_out /* [n_rules] or NULL */, uint64_t *any_out /* [W] or NULL */,
+                       uint64_t *rule_hits_out /* [n_rules * W] or NULL */, uint64_t *counts_out /* [n_pat] or NULL: as kmpgpu_scan */,
+                       kmpgpu_timing *t /* or NULL */);
 
 /* Fill a device arena with the synthetic payloads of kmp_synth.h (benchmark input S1/S2):
  * packet ids first_pkt_id .. first_pkt_id + n_pkts - 1 at the slots of the given device index. */

@@ -72,6 +72,24 @@ int  kmp_patterns_load(const char *path, kmp_patterns *out);                 /* 
 int  kmp_patterns_parse(const uint8_t *text, size_t n, kmp_patterns *out);
 void kmp_patterns_free(kmp_patterns *p);
 
+/* ---- content rules --------------------------------------------------------------------------
+ * Not in the reference: the rules of kmpgpu_set_rules (include/kmpgpu.h) from a text file.  One rule per line; its terms are
+ * separated by blanks; a term is a decimal pattern index (the position in the pattern file, 0-based) with an optional leading '!'
+ * for a pattern that must NOT be in the payload.  Blank lines and lines whose first non-blank character is '#' are skipped; rule
+ * index = order of the rule lines.  off / terms are what kmpgpu_set_rules takes: rule r = terms[off[r] .. off[r + 1]), a negated
+ * term carries KMP_RULE_NOT (= KMPGPU_RULE_NOT).
+ * KMPHOST_EIO: the file cannot be opened; KMPHOST_EINVAL: a term that is not a number, an index >= n_patterns, a bare '!' --
+ * errbuf then starts with "line N: " (N counts every line of the file, from 1). */
+#define KMP_RULE_NOT      0x80000000u
+#define KMP_RULES_ERRBUF  256
+typedef struct kmp_rules {
+    uint32_t  n;          /* number of rules                               */
+    uint32_t *off;        /* [n + 1]                                       */
+    uint32_t *terms;      /* [off[n]]                                      */
+} kmp_rules;
+int  kmp_rules_parse(const char *path, uint32_t n_patterns, kmp_rules *out, char errbuf[KMP_RULES_ERRBUF]);
+void kmp_rules_free(kmp_rules *r);
+
 /* KMP failure function: replaces kmp_prefix (serial.c:217-238); prefix has room for m ints. */
 void kmp_failure_table(const uint8_t *pat, uint32_t m, int32_t *prefix);
 

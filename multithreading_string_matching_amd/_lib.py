@@ -22,6 +22,8 @@ GPU_SO = os.path.join(LIBDIR, "libkmpgpu.so")
 
 KMP_SYNTH_MAX_NEEDLE = 100
 KMP_PCAP_ERRBUF = 256
+KMP_RULES_ERRBUF = 256
+RULE_NOT = 0x80000000      # KMPGPU_RULE_NOT / KMP_RULE_NOT: the term's pattern must not be in the payload
 
 u8p = C.POINTER(C.c_uint8)
 u32p = C.POINTER(C.c_uint32)
@@ -57,6 +59,11 @@ class SynthParams(C.Structure):
 class Patterns(C.Structure):
     """kmp_patterns (include/kmphost.h)."""
     _fields_ = [("n", C.c_uint32), ("blob", u8p), ("off", u32p), ("len", u32p)]
+
+
+class Rules(C.Structure):
+    """kmp_rules (include/kmphost.h)."""
+    _fields_ = [("n", C.c_uint32), ("off", u32p), ("terms", u32p)]
 
 
 class Arena(C.Structure):
@@ -95,6 +102,8 @@ HOST_API = {
     "kmp_patterns_load": (C.c_int, [C.c_char_p, C.POINTER(Patterns)]),
     "kmp_patterns_parse": (C.c_int, [u8p, C.c_size_t, C.POINTER(Patterns)]),
     "kmp_patterns_free": (None, [C.POINTER(Patterns)]),
+    "kmp_rules_parse": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(Rules), C.c_char_p]),
+    "kmp_rules_free": (None, [C.POINTER(Rules)]),
     "kmp_failure_table": (None, [u8p, C.c_uint32, i32p]),
     "kmp_arena_from_pcap": (C.c_int, [C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Arena), C.c_char_p]),
     "kmp_arena_from_payloads": (C.c_int, [C.POINTER(u8p), u32p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(Arena)]),
@@ -148,6 +157,8 @@ GPU_API = {
     "kmpgpu_profile_end": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), u32p]),
     "kmpgpu_scan_offsets": (C.c_int, [C.c_void_p, C.POINTER(Match), C.c_uint64, u64p, u64p]),
     "kmpgpu_scan_packets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
+    "kmpgpu_set_rules": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint32]),
+    "kmpgpu_scan_rules": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
     "kmpgpu_synth_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(SynthParams)]),
     "kmpgpu_fixed_index": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32]),
     "kmpgpu_arena_info": (C.c_int, [C.c_void_p, u64p, u64p]),

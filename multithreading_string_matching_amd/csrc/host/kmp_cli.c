@@ -20,6 +20,12 @@
  * KMPGPU_PACKETS_FILE=<path>: which payloads hold which patterns (kmpgpu_scan_packets), one "payload,pattern" line per
  * pair that holds at least one match, sorted by payload, then by pattern (indices as in the offsets file).
  *
+ * KMPGPU_RULES_FILE=<rules> with KMPGPU_ALERTS_FILE=<path>: content rules over the patterns (kmpgpu_set_rules, kmpgpu_scan_rules; the
+ * file format is kmp_rules_parse's, kmphost.h: one rule per line, terms are indices into the pattern file, "!" in front of one that
+ * must not be in the payload), one "payload,rule" line per payload that a rule matches, sorted by payload, then by rule (rule =
+ * index among the rule lines).  One of the two without the other, or a rules file that does not parse: message on stderr, exit 1,
+ * before any GPU work.  Both go together with KMPGPU_NOCASE, KMPGPU_WHOLE_PAYLOAD, KMPGPU_DEVICE_EXTRACT and KMPGPU_PACKETS_FILE.
+ *
  * KMPGPU_NOCASE=1: every pattern matches case-insensitively (ASCII letters; kmpgpu_set_patterns_flags), in the counts and in
  * the offsets file alike; the report prints every token as written in the pattern file.
  *
@@ -194,6 +200,24 @@ int main(int argc, char *argv[])
         exit(1);
     }
 
+    /* the content rules, read before anything touches the GPU */
+    const char *rules_path = getenv("KMPGPU_RULES_FILE"), *alerts_path = getenv("KMPGPU_ALERTS_FILE");
+    if (rules_path && !rules_path[0]) rules_path = NULL;
+    if (alerts_path && !alerts_path[0]) alerts_path = NULL;
+    kmp_rules rules;
+    memset(&rules, 0, sizeof rules);
+    if ((rules_path != NULL) != (alerts_path != NULL)) {
+        fprintf(stderr, "KMPGPU_RULES_FILE and KMPGPU_ALERTS_FILE go together: %s is not set\n", rules_path ? "KMPGPU_ALERTS_FILE" : "KMPGPU_RULES_FILE");
+        exit(1);
+    }
+    if (rules_path) {
+        char rules_err[KMP_RULES_ERRBUF];
+        if (kmp_rules_parse(rules_path, pats.n, &rules, rules_err)) {
+            fprintf(stderr, "error reading rules file %s: %s\n", rules_path, rules_err);
+            exit(1);
+        }
+    }
+
 #if !KMP_CLI_OPENMP_FORM
     const double t_start = now_s();                                         /* serial.c:110-111: before the file read */
 #endif
@@ -361,6 +385,29 @@ int main(int argc, char *argv[])
             }
             fclose(pk_fp);
         }
+        if (alerts_path) {
+            FILE *al_fp = fopen(alerts_path, "w");
+            if (!al_fp) { perror("KMPGPU_ALERTS_FILE"); exit(1); }
+            uint64_t shard_lo = 0;                                          /* payload index of the shard's first payload */
+            for (int r = 0; r < shards && rules.n; r++) {
+                uint64_t np = 0;
+                kmpgpu_arena_info(ctxs[r], &np, NULL);
+                const uint64_t W = (np + 63) / 64;
+                uint64_t *any = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)(W ? W : 1));
+                uint64_t *hits = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)(W ? W : 1) * rules.n);
+                if (!any || !hits || kmpgpu_set_rules(ctxs[r], rules.off, rules.terms, rules.n)) die_gpu("kmpgpu_set_rules");
+                if (kmpgpu_scan_rules(ctxs[r], NULL, any, hits, NULL, NULL)) die_gpu("kmpgpu_scan_rules");
+                for (uint64_t k = 0; k < np; k++) {
+                    const uint64_t bit = 1ull << (k & 63);
+                    if (!(any[k >> 6] & bit)) continue;
+                    for (uint32_t i = 0; i < rules.n; i++)
+                        if (hits[(size_t)i * W + (k >> 6)] & bit) fprintf(al_fp, "%llu,%u\n", (unsigned long long)(shard_lo + k), i);
+                }
+                free(any); free(hits);
+                shard_lo += np;
+            }
+            fclose(al_fp);
+        }
         for (int r = 0; r < shards && want_stats; r++) {
             uint64_t e = 0;
             if (kmpgpu_effective_bytes(ctxs[r], &e)) die_gpu("kmpgpu_effective_bytes");
@@ -397,5 +444,6 @@ int main(int argc, char *argv[])
     kmp_arena_free(&arena);
     kmp_frames_free(&frames);
     kmp_patterns_free(&pats);
+    kmp_rules_free(&rules);
     return 0;
 }

@@ -423,6 +423,81 @@ void kmp_patterns_free(kmp_patterns *p)
     memset(p, 0, sizeof *p);
 }
 
+/* ============================ content rules ============================================= */
+
+static int rules_push(uint32_t **v, size_t *n, size_t *cap, uint32_t x)
+{
+    if (*n == *cap) {
+        const size_t nc = *cap ? *cap * 2 : 64;
+        uint32_t *nv = (uint32_t *)realloc(*v, nc * sizeof(uint32_t));
+        if (!nv) return KMPHOST_ENOMEM;
+        *v = nv; *cap = nc;
+    }
+    (*v)[(*n)++] = x;
+    return KMPHOST_OK;
+}
+
+int kmp_rules_parse(const char *path, uint32_t n_patterns, kmp_rules *out, char errbuf[KMP_RULES_ERRBUF])
+{
+    memset(out, 0, sizeof *out);
+    if (errbuf) errbuf[0] = 0;
+    FILE *fp = fopen(path, "rb");
+    if (!fp) {
+        if (errbuf) snprintf(errbuf, KMP_RULES_ERRBUF, "%s: %s", path, strerror(errno));
+        return KMPHOST_EIO;
+    }
+    char *line = NULL;
+    size_t line_cap = 0, n_off = 0, cap_off = 0, n_terms = 0, cap_terms = 0, lineno = 0;
+    ssize_t got;
+    int rc = rules_push(&out->off, &n_off, &cap_off, 0);
+    while (!rc && (got = getline(&line, &line_cap, fp)) >= 0) {
+        lineno++;
+        const char *p = line, *end = line + got;
+        while (p < end && is_c_space((uint8_t)*p)) p++;
+        if (p == end || *p == '#') continue;                           /* blank line, comment */
+        while (p < end && !rc) {
+            const char *tok = p;
+            uint32_t neg = 0;
+            uint64_t v = 0;
+            if (*p == '!') { neg = KMP_RULE_NOT; p++; }
+            const char *digits = p;
+            while (p < end && *p >= '0' && *p <= '9') { if (v < (1ull << 40)) v = v * 10 + (uint64_t)(*p - '0'); p++; }
+            const char *stop = p;
+            while (stop < end && !is_c_space((uint8_t)*stop)) stop++;   /* the whole token, for the message */
+            if (p == digits && neg && stop == p) {
+                if (errbuf) snprintf(errbuf, KMP_RULES_ERRBUF, "line %zu: '!' without a pattern index", lineno);
+                rc = KMPHOST_EINVAL;
+            } else if (p == digits || stop != p) {
+                if (errbuf) snprintf(errbuf, KMP_RULES_ERRBUF, "line %zu: '%.*s' is not a pattern index", lineno, (int)(stop - tok > 64 ? 64 : stop - tok), tok);
+                rc = KMPHOST_EINVAL;
+            } else if (v >= n_patterns) {
+                if (errbuf) snprintf(errbuf, KMP_RULES_ERRBUF, "line %zu: pattern index %llu, but there are %u patterns", lineno, (unsigned long long)v, n_patterns);
+                rc = KMPHOST_EINVAL;
+            } else
+                rc = rules_push(&out->terms, &n_terms, &cap_terms, (uint32_t)v | neg);
+            while (p < end && is_c_space((uint8_t)*p)) p++;
+        }
+        if (!rc && n_terms > 0xFFFFFFFFull) rc = KMPHOST_EINVAL;
+        if (!rc) rc = rules_push(&out->off, &n_off, &cap_off, (uint32_t)n_terms);
+    }
+    free(line);
+    fclose(fp);
+    if (rc) {
+        if (rc == KMPHOST_ENOMEM && errbuf) snprintf(errbuf, KMP_RULES_ERRBUF, "out of memory");
+        kmp_rules_free(out);
+        return rc;
+    }
+    out->n = (uint32_t)(n_off - 1);
+    return KMPHOST_OK;
+}
+
+void kmp_rules_free(kmp_rules *r)
+{
+    if (!r) return;
+    free(r->off); free(r->terms);
+    memset(r, 0, sizeof *r);
+}
+
 /* serial.c:217-238 */
 void kmp_failure_table(const uint8_t *pat, uint32_t m, int32_t *prefix)
 {

@@ -97,6 +97,16 @@ hipError_t kmp_launch_slot_end(const uint64_t *pkt_off, const uint32_t *pkt_len,
  * added to pkt_counts[row], and per column word the OR over all rows, ORed into any[word]; both zeroed by the caller */
 hipError_t kmp_launch_marks_reduce(const unsigned long long *marks, uint32_t n_rows, uint64_t stride, unsigned long long *pkt_counts,
                                    unsigned long long *any, hipStream_t st);
+/* kmp_rules.hip: the rules of kmpgpu_set_rules over the hit matrix marks[n_pat][stride] (stride even, 16-byte aligned) that holds n_pkts
+ * payloads.  The rules lie on the device as CSR in 16-byte units.  A term is a pattern index (< n_pat, checked by the caller) |
+ * KMPGPU_RULE_NOT (kmpgpu.h) for a negated term.  heads[r] = {first quad of rule r's further terms, the quad behind its last, its first term, its
+ * second term}, quads[q] = four further terms; a rule of one term has it twice in its head, and the last quad of a rule is filled up
+ * with repeats of that quad's first term (a repeated term changes nothing, and no load of the kernel hangs on a condition).  Every word of
+ * rule_rows[n_rules][stride] is written (the bits of index n_pkts and above as 0), a rule's set bits are added to rule_counts[r],
+ * the OR over all rules is ORed into any[stride]; the caller zeroes those two */
+hipError_t kmp_launch_rules(const unsigned long long *marks, uint64_t stride, uint64_t n_pkts, const uint4 *heads, const uint4 *quads,
+                            uint32_t n_rules, unsigned long long *rule_rows, unsigned long long *rule_counts, unsigned long long *any,
+                            hipStream_t st);
 hipError_t kmp_launch_fixed_index(uint64_t *pkt_off, uint32_t *pkt_len, uint64_t n, uint32_t len, uint64_t stride,
                                   hipStream_t st);
 

@@ -149,6 +149,11 @@ struct kmpgpu_ctx {
                                                          memory goes through the runtime's blocking staging path) */
     unsigned long long *d_marks = nullptr;            /* kmpgpu_scan_packets: hit matrix [n_pat][stride], then pkt_counts[n_pat], any[stride], counts[n_pat] */
     uint64_t            marks_cap = 0;                /* words */
+    /* kmpgpu_set_rules / kmpgpu_scan_rules: the rules as the kernel reads them (kmp_launch.h, kmp_launch_rules) and the results */
+    uint32_t            n_rules = 0;
+    uint4              *d_rule_heads = nullptr, *d_rule_quads = nullptr;
+    unsigned long long *d_rule_out = nullptr;         /* rule rows [n_rules][stride], then rule_pkt_counts[n_rules], any[stride] */
+    uint64_t            rule_out_cap = 0;             /* words */
 
     /* options */
     int mode = 0, blocks_per_cu = 0 /* auto */, depth = 0 /* auto */, nontemporal = 1, kernel_sel = 0, fused = 2 /* auto */, accumulate = 0, repack = 1;
@@ -274,6 +279,15 @@ int ensure_partials(kmpgpu_ctx *c, size_t elems)
     HIP_TRY(hipMalloc(&c->d_partials, elems * sizeof(unsigned long long)));
     c->partials_cap = elems;
     return KMPGPU_OK;
+}
+
+/* the rules go with the pattern set their indices refer to */
+void drop_rules(kmpgpu_ctx *c)
+{
+    if (c->d_rule_heads) (void)hipFree(c->d_rule_heads);
+    if (c->d_rule_quads) (void)hipFree(c->d_rule_quads);
+    c->d_rule_heads = c->d_rule_quads = nullptr;
+    c->n_rules = 0;
 }
 
 void release_arena(kmpgpu_ctx *c, bool keep_buffers = false)
@@ -981,6 +995,8 @@ void kmpgpu_destroy(kmpgpu_ctx *c)
     if (c->d_partials) (void)hipFree(c->d_partials);
     if (c->d_counts) (void)hipFree(c->d_counts);
     if (c->d_marks) (void)hipFree(c->d_marks);
+    drop_rules(c);
+    if (c->d_rule_out) (void)hipFree(c->d_rule_out);
     if (c->d_plan) (void)hipFree(c->d_plan);
     if (c->d_uplan) (void)hipFree(c->d_uplan);
     if (c->d_pool) (void)hipFree(c->d_pool);
@@ -1113,6 +1129,7 @@ int kmpgpu_set_patterns_flags(kmpgpu_ctx *c, const uint8_t *const *pat, const ui
     if (c->d_counts) { HIP_TRY(hipFree(c->d_counts)); c->d_counts = nullptr; }
     free_pattern_set(c->sets[0]);
     free_pattern_set(c->sets[1]);
+    drop_rules(c);                                 /* their indices meant the old patterns */
     c->n_pat = n_pat;
     const size_t np = n_pat ? n_pat : 1;
     HIP_TRY(hipMalloc(&c->d_patterns, np * sizeof(kmp_pattern_dev)));
@@ -1577,25 +1594,31 @@ int kmpgpu_scan_offsets(kmpgpu_ctx *c, kmpgpu_match *out, uint64_t cap, uint64_t
     return rc;
 }
 
-int kmpgpu_scan_packets(kmpgpu_ctx *c, uint64_t *pkt_counts_out, uint64_t *any_out, uint64_t *hits_out, uint64_t *counts_out, kmpgpu_timing *t)
+namespace {
+
+/* The marking pass kmpgpu_scan_packets and kmpgpu_scan_rules share: preconditions, the arena packed where it was kept in place, the
+ * context's matrix buffer grown and zeroed, and the scan launches that mark it.  Leaves c->ev[0] recorded in front of the zeroing.
+ * empty: no payloads, nothing was enqueued. */
+struct MarkPass {
+    bool empty = false;
+    uint64_t W = 0, stride = 0, mat = 0;          /* words per row as the caller sees them / on the device (even); words of the matrix */
+    unsigned long long *d_mat = nullptr, *d_pc = nullptr, *d_any = nullptr, *d_cnt = nullptr;    /* [n_pat][stride], [n_pat], [stride], [n_pat] */
+    uint32_t launches = 0;
+};
+
+int marking_pass(kmpgpu_ctx *c, const char *who, MarkPass *p)
 {
-    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_scan_packets: ctx is NULL");
-    if (c->mode != 0 || c->kernel_sel == 1) return fail(KMPGPU_EINVAL, "kmpgpu_scan_packets runs on the streaming kernels only (mode 0, kernel 0, 2 or 3)");
-    if (!c->d_patterns || c->n_pat == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan_packets: no patterns set");
-    if (!c->d_off && c->n_pkts) return fail(KMPGPU_ESTATE, "kmpgpu_scan_packets: no arena loaded");
+    if (c->mode != 0 || c->kernel_sel == 1) return fail(KMPGPU_EINVAL, "%s runs on the streaming kernels only (mode 0, kernel 0, 2 or 3)", who);
+    if (!c->d_patterns || c->n_pat == 0) return fail(KMPGPU_ESTATE, "%s: no patterns set", who);
+    if (!c->d_off && c->n_pkts) return fail(KMPGPU_ESTATE, "%s: no arena loaded", who);
     HIP_TRY(hipSetDevice(c->device));
-    const uint64_t W = (c->n_pkts + 63u) / 64u;
+    *p = MarkPass{};
+    p->W = (c->n_pkts + 63u) / 64u;
     const size_t np = c->n_pat;
-    if (c->n_pkts == 0) {
-        /* nothing to scan: every payload count, every total is 0, and there are no bit words */
-        if (pkt_counts_out) memset(pkt_counts_out, 0, np * sizeof(uint64_t));
-        if (counts_out) memset(counts_out, 0, np * sizeof(uint64_t));
-        if (t) { *t = kmpgpu_timing{}; }
-        return KMPGPU_OK;
-    }
-    /* rows of an even number of words: the reduce reads 16 bytes per lane */
-    const uint64_t stride = (W + 1u) & ~1ull;
-    if (stride > 0xFFFFFFFEull) return fail(KMPGPU_EINVAL, "kmpgpu_scan_packets: too many payloads for the hit matrix");
+    if (c->n_pkts == 0) { p->empty = true; return KMPGPU_OK; }
+    /* rows of an even number of words: the reduce and the rules kernel read 16 bytes per lane */
+    const uint64_t stride = (p->W + 1u) & ~1ull;
+    if (stride > 0xFFFFFFFEull) return fail(KMPGPU_EINVAL, "%s: too many payloads for the hit matrix", who);
     if (!c->packed) {
         /* an arena kept in place (KMPGPU_OPT_REPACK = 0) whose slots are not back to back: packed now, once (kmpgpu_scan_offsets) */
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1611,36 +1634,35 @@ int kmpgpu_scan_packets(kmpgpu_ctx *c, uint64_t *pkt_counts_out, uint64_t *any_o
     hipError_t e = grow_buffer(&c->d_marks, &c->marks_cap, words);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? KMPGPU_ENOMEM : KMPGPU_EHIP, "kmpgpu_scan_packets: the hit matrix (%llu bytes) could not be allocated: %s",
-                    (unsigned long long)(words * 8u), hipGetErrorString(e));
+        return fail(e == hipErrorOutOfMemory ? KMPGPU_ENOMEM : KMPGPU_EHIP, "%s: the hit matrix (%llu bytes) could not be allocated: %s",
+                    who, (unsigned long long)(words * 8u), hipGetErrorString(e));
     }
-    unsigned long long *d_mat = c->d_marks, *d_pc = d_mat + mat, *d_any = d_pc + np, *d_cnt = d_any + stride;
-    uint32_t launches = 0;
+    p->stride = stride; p->mat = mat;
+    p->d_mat = c->d_marks; p->d_pc = p->d_mat + mat; p->d_any = p->d_pc + np; p->d_cnt = p->d_any + stride;
     HIP_TRY(hipEventRecord(c->ev[0], c->stream));
     /* zeroed before every pass: the bits of an earlier (larger) arena must not leak into this one */
-    HIP_TRY(hipMemsetAsync(d_mat, 0, (size_t)words * sizeof(unsigned long long), c->stream));
-    {
-        /* the pass writes its counts to a buffer of its own and never accumulates: the context's counters stay as they are */
-        EmitTarget tg;
-        tg.out = nullptr; tg.counter = nullptr; tg.cap = 0;
-        tg.marks = d_mat; tg.mark_stride = (uint32_t)stride;
-        const int acc = c->accumulate;
-        c->accumulate = 0;
-        const int rc = enqueue_pass(c, &launches, d_cnt, &tg);
-        c->accumulate = acc;
-        if (rc) return rc;
-    }
-    HIP_TRY(kmp_launch_marks_reduce(d_mat, c->n_pat, stride, d_pc, d_any, c->stream));
-    ++launches;
-    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-    if (pkt_counts_out) HIP_TRY(hipMemcpyAsync(pkt_counts_out, d_pc, np * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (any_out) HIP_TRY(hipMemcpyAsync(any_out, d_any, W * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, d_cnt, np * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (hits_out) {
-        if (stride == W) HIP_TRY(hipMemcpyAsync(hits_out, d_mat, (size_t)mat * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-        else HIP_TRY(hipMemcpy2DAsync(hits_out, W * sizeof(uint64_t), d_mat, stride * sizeof(uint64_t), W * sizeof(uint64_t), np,
-                                      hipMemcpyDeviceToHost, c->stream));
-    }
+    HIP_TRY(hipMemsetAsync(p->d_mat, 0, (size_t)words * sizeof(unsigned long long), c->stream));
+    /* the pass writes its counts to a buffer of its own and never accumulates: the context's counters stay as they are */
+    EmitTarget tg;
+    tg.out = nullptr; tg.counter = nullptr; tg.cap = 0;
+    tg.marks = p->d_mat; tg.mark_stride = (uint32_t)stride;
+    const int acc = c->accumulate;
+    c->accumulate = 0;
+    const int rc = enqueue_pass(c, &p->launches, p->d_cnt, &tg);
+    c->accumulate = acc;
+    return rc;
+}
+
+/* rows of W words from a device matrix whose rows are `stride` words apart */
+hipError_t download_rows(kmpgpu_ctx *c, uint64_t *dst, const unsigned long long *src, uint64_t W, uint64_t stride, uint64_t rows)
+{
+    if (stride == W) return hipMemcpyAsync(dst, src, (size_t)(rows * W) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream);
+    return hipMemcpy2DAsync(dst, W * sizeof(uint64_t), src, stride * sizeof(uint64_t), W * sizeof(uint64_t), rows, hipMemcpyDeviceToHost, c->stream);
+}
+
+/* waits for the pass and its downloads; kernel_ms = ev[0]..ev[1], d2h_ms = ev[1]..ev[2] */
+int finish_marking(kmpgpu_ctx *c, uint32_t launches, kmpgpu_timing *t)
+{
     HIP_TRY(hipEventRecord(c->ev[2], c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (t) {
@@ -1652,6 +1674,125 @@ int kmpgpu_scan_packets(kmpgpu_ctx *c, uint64_t *pkt_counts_out, uint64_t *any_o
         t->grid_blocks = grid_blocks(c, primary_set(c), true);
     }
     return KMPGPU_OK;
+}
+
+}  // namespace
+
+int kmpgpu_scan_packets(kmpgpu_ctx *c, uint64_t *pkt_counts_out, uint64_t *any_out, uint64_t *hits_out, uint64_t *counts_out, kmpgpu_timing *t)
+{
+    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_scan_packets: ctx is NULL");
+    MarkPass p;
+    const int rc = marking_pass(c, "kmpgpu_scan_packets", &p);
+    if (rc) return rc;
+    const size_t np = c->n_pat;
+    if (p.empty) {
+        /* nothing to scan: every payload count, every total is 0, and there are no bit words */
+        if (pkt_counts_out) memset(pkt_counts_out, 0, np * sizeof(uint64_t));
+        if (counts_out) memset(counts_out, 0, np * sizeof(uint64_t));
+        if (t) { *t = kmpgpu_timing{}; }
+        return KMPGPU_OK;
+    }
+    HIP_TRY(kmp_launch_marks_reduce(p.d_mat, c->n_pat, p.stride, p.d_pc, p.d_any, c->stream));
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    if (pkt_counts_out) HIP_TRY(hipMemcpyAsync(pkt_counts_out, p.d_pc, np * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (any_out) HIP_TRY(hipMemcpyAsync(any_out, p.d_any, p.W * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, p.d_cnt, np * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (hits_out) HIP_TRY(download_rows(c, hits_out, p.d_mat, p.W, p.stride, np));
+    return finish_marking(c, p.launches + 1u, t);
+}
+
+int kmpgpu_set_rules(kmpgpu_ctx *c, const uint32_t *rule_off, const uint32_t *terms, uint32_t n_rules)
+{
+    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_set_rules: ctx is NULL");
+    if (!c->d_patterns || c->n_pat == 0) return fail(KMPGPU_ESTATE, "kmpgpu_set_rules: no patterns set");
+    HIP_TRY(hipSetDevice(c->device));
+    if (n_rules == 0) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        drop_rules(c);
+        return KMPGPU_OK;
+    }
+    if (!rule_off || !terms) return fail(KMPGPU_EINVAL, "kmpgpu_set_rules: NULL rule arrays");
+    if (rule_off[0] != 0) return fail(KMPGPU_EINVAL, "kmpgpu_set_rules: rule_off[0] is %u, not 0", rule_off[0]);
+    /* the device form (kmp_launch.h): a head per rule with its first two terms, the others in quads; positive terms first, so that
+     * a lane of the kernel whose payloads miss one of them stops early */
+    std::vector<uint4> heads(n_rules), quads;
+    std::vector<uint32_t> ord;
+    for (uint32_t r = 0; r < n_rules; r++) {
+        if (rule_off[r + 1] < rule_off[r]) return fail(KMPGPU_EINVAL, "kmpgpu_set_rules: rule_off decreases at rule %u", r);
+        if (rule_off[r + 1] == rule_off[r]) return fail(KMPGPU_EINVAL, "kmpgpu_set_rules: rule %u has no terms", r);
+        ord.clear();
+        for (int neg = 0; neg < 2; neg++)
+            for (uint32_t j = rule_off[r]; j < rule_off[r + 1]; j++) {
+                if ((terms[j] & ~KMPGPU_RULE_NOT) >= c->n_pat)
+                    return fail(KMPGPU_EINVAL, "kmpgpu_set_rules: rule %u: term %u names pattern %u of %u", r, j - rule_off[r], terms[j] & ~KMPGPU_RULE_NOT, c->n_pat);
+                if (((terms[j] & KMPGPU_RULE_NOT) != 0) == (neg != 0)) ord.push_back(terms[j]);
+            }
+        /* filled up with a term that is loaded at the same time: a repeated term changes nothing */
+        if (ord.size() < 2) ord.push_back(ord[0]);
+        while ((ord.size() - 2) % 4) ord.push_back(ord[ord.size() - (ord.size() - 2) % 4]);
+        if (quads.size() + (ord.size() - 2) / 4 > 0xFFFFFFFFull) return fail(KMPGPU_EINVAL, "kmpgpu_set_rules: too many terms");
+        heads[r] = make_uint4((uint32_t)quads.size(), (uint32_t)(quads.size() + (ord.size() - 2) / 4), ord[0], ord[1]);
+        for (size_t j = 2; j < ord.size(); j += 4) quads.push_back(make_uint4(ord[j], ord[j + 1], ord[j + 2], ord[j + 3]));
+    }
+    uint4 *d_heads = nullptr, *d_quads = nullptr;
+    hipError_t e = hipMalloc((void **)&d_heads, heads.size() * sizeof(uint4));
+    if (e == hipSuccess) e = hipMalloc((void **)&d_quads, (quads.size() ? quads.size() : 1) * sizeof(uint4));
+    if (e == hipSuccess) e = hipMemcpy(d_heads, heads.data(), heads.size() * sizeof(uint4), hipMemcpyHostToDevice);
+    if (e == hipSuccess && !quads.empty()) e = hipMemcpy(d_quads, quads.data(), quads.size() * sizeof(uint4), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        if (d_heads) (void)hipFree(d_heads);
+        if (d_quads) (void)hipFree(d_quads);
+        return fail(e == hipErrorOutOfMemory ? KMPGPU_ENOMEM : KMPGPU_EHIP, "kmpgpu_set_rules: the rules could not be uploaded: %s", hipGetErrorString(e));
+    }
+    drop_rules(c);
+    c->d_rule_heads = d_heads; c->d_rule_quads = d_quads; c->n_rules = n_rules;
+    return KMPGPU_OK;
+}
+
+int kmpgpu_scan_rules(kmpgpu_ctx *c, uint64_t *rule_pkt_counts_out, uint64_t *any_out, uint64_t *rule_hits_out, uint64_t *counts_out, kmpgpu_timing *t)
+{
+    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_scan_rules: ctx is NULL");
+    if (c->n_rules == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan_rules: no rules set");
+    MarkPass p;
+    const int rc = marking_pass(c, "kmpgpu_scan_rules", &p);
+    if (rc) return rc;
+    const size_t np = c->n_pat, nr = c->n_rules;
+    if (p.empty) {
+        /* nothing to scan: no rule matches anything (an all-negated rule has no payload to match either), and there are no bit words */
+        if (rule_pkt_counts_out) memset(rule_pkt_counts_out, 0, nr * sizeof(uint64_t));
+        if (counts_out) memset(counts_out, 0, np * sizeof(uint64_t));
+        if (t) { *t = kmpgpu_timing{}; }
+        return KMPGPU_OK;
+    }
+    /* one device buffer, grown like the others: [rule rows n_rules x stride][rule_pkt_counts n_rules][any stride] */
+    const uint64_t rows = (uint64_t)nr * p.stride;
+    const uint64_t words = rows + nr + p.stride;
+    hipError_t e = grow_buffer(&c->d_rule_out, &c->rule_out_cap, words);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        /* the marking pass is under way on the stream; the context stays usable */
+        (void)hipStreamSynchronize(c->stream);
+        return fail(e == hipErrorOutOfMemory ? KMPGPU_ENOMEM : KMPGPU_EHIP, "kmpgpu_scan_rules: the rule rows (%llu bytes) could not be allocated: %s",
+                    (unsigned long long)(words * 8u), hipGetErrorString(e));
+    }
+    unsigned long long *d_rows = c->d_rule_out, *d_rc = d_rows + rows, *d_any = d_rc + nr;
+    /* the kernel adds to the counts and ORs into any; it writes every word of the rows itself */
+    HIP_TRY(hipMemsetAsync(d_rc, 0, (size_t)(nr + p.stride) * sizeof(unsigned long long), c->stream));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (c->profiling && c->prof_n < c->prof_cap) {
+        e0 = c->prof_ev[2 * c->prof_n]; e1 = c->prof_ev[2 * c->prof_n + 1];
+        HIP_TRY(hipEventRecord(e0, c->stream));
+    }
+    HIP_TRY(kmp_launch_rules(p.d_mat, p.stride, c->n_pkts, c->d_rule_heads, c->d_rule_quads, c->n_rules, d_rows, d_rc, d_any, c->stream));
+    if (e0) { HIP_TRY(hipEventRecord(e1, c->stream)); c->prof_n++; }
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    if (rule_pkt_counts_out) HIP_TRY(hipMemcpyAsync(rule_pkt_counts_out, d_rc, nr * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (any_out) HIP_TRY(hipMemcpyAsync(any_out, d_any, p.W * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, p.d_cnt, np * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (rule_hits_out) HIP_TRY(download_rows(c, rule_hits_out, d_rows, p.W, p.stride, nr));
+    return finish_marking(c, p.launches + 1u, t);
 }
 
 int kmpgpu_synth_fill(kmpgpu_ctx *c, void *d_arena, const void *d_pkt_off, const void *d_pkt_len, uint64_t first_pkt_id,

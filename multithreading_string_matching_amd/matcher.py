@@ -41,6 +41,7 @@ class GpuMatcher:
         gpu_check(self._g.kmpgpu_init(C.byref(self._ctx), device), "kmpgpu_init")
         self.device = device
         self.patterns: List[bytes] = []
+        self.rules: list = []      # (all_of, none_of) per rule, as set_rules took them
         self._keep = None          # objects whose device memory the context borrows
         self._comm = None          # the GpuComm this matcher is a rank of: closed before the context
 
@@ -66,6 +67,21 @@ class GpuMatcher:
         flags = (C.c_uint32 * max(n, 1))(*[PAT_NOCASE if x else 0 for x in nocase])
         gpu_check(self._g.kmpgpu_set_patterns_flags(self._ctx, ptrs, lens, flags, n), "kmpgpu_set_patterns_flags")
         self.patterns = list(patterns)
+        self.rules = []            # the library drops its rules with the pattern set they referred to
+
+    def set_rules(self, rules) -> None:
+        """Content rules over the current patterns (kmpgpu_set_rules): a sequence of (all_of, none_of) pattern-index sequences;
+        a rule matches a payload that holds every pattern of all_of and none of none_of.  An empty sequence clears the rules."""
+        rules = [([int(i) for i in a], [int(i) for i in b]) for a, b in rules]
+        for a, b in rules:
+            for i in a + b:
+                if not 0 <= i < _lib.RULE_NOT:
+                    raise ValueError(f"rule term {i}: not a pattern index")
+        off = np.zeros(len(rules) + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([len(a) + len(b) for a, b in rules])
+        terms = np.array([t for a, b in rules for t in a + [i | _lib.RULE_NOT for i in b]] or [0], dtype=np.uint32)
+        gpu_check(self._g.kmpgpu_set_rules(self._ctx, off.ctypes.data_as(u32p), terms.ctypes.data_as(u32p), len(rules)), "kmpgpu_set_rules")
+        self.rules = rules
 
     # -- arena ------------------------------------------------------------------------------------
     def load_arena(self, arena, off: Optional[np.ndarray] = None, ln: Optional[np.ndarray] = None) -> None:
@@ -210,6 +226,28 @@ class GpuMatcher:
                "any": np.unpackbits(any_w[:W].view(np.uint8), bitorder="little")[:n_pkts].astype(bool)}
         if hits:
             bits = np.unpackbits(hit_w.reshape(n, W).view(np.uint8), axis=1, bitorder="little") if n * W else np.zeros((n, 0), np.uint8)
+            out["hits"] = bits[:, :n_pkts].astype(bool)
+        return out
+
+    def scan_rules(self, hits: bool = False) -> dict:
+        """Which payloads match which rules (kmpgpu_scan_rules): the marking pass of scan_packets and the rules on the device.
+        ``rule_pkt_counts`` (uint64[n_rules]) payloads that rule r matches, ``any`` (bool[n_pkts]) payload k matches some rule,
+        ``counts`` (uint64[n_pat]) as scan(), ``timing``; with hits=True also ``hits`` (bool[n_rules, n_pkts])."""
+        n, nr = len(self.patterns), len(self.rules)
+        n_pkts, _ = self.arena_info()
+        W = (n_pkts + 63) // 64
+        rule_counts = np.zeros(max(nr, 1), dtype=np.uint64)
+        counts = np.zeros(max(n, 1), dtype=np.uint64)
+        any_w = np.zeros(max(W, 1), dtype=np.uint64)
+        hit_w = np.zeros((nr, W) if hits and nr * W else 1, dtype=np.uint64)
+        t = Timing()
+        gpu_check(self._g.kmpgpu_scan_rules(self._ctx, rule_counts.ctypes.data, any_w.ctypes.data,
+                                            hit_w.ctypes.data if hits else None, counts.ctypes.data, C.byref(t)),
+                  "kmpgpu_scan_rules")
+        out = {"rule_pkt_counts": rule_counts[:nr], "counts": counts[:n], "timing": t,
+               "any": np.unpackbits(any_w[:W].view(np.uint8), bitorder="little")[:n_pkts].astype(bool)}
+        if hits:
+            bits = np.unpackbits(hit_w.reshape(nr, W).view(np.uint8), axis=1, bitorder="little") if nr * W else np.zeros((nr, 0), np.uint8)
             out["hits"] = bits[:, :n_pkts].astype(bool)
         return out
 
