@@ -340,6 +340,44 @@ int  kmpgpu_scan_rules(kmpgpu_ctx *ctx, uint64_t *rule_pkt_counts_out /* [n_rule
                        uint64_t *rule_hits_out /* [n_rules * W] or NULL */, uint64_t *counts_out /* [n_pat] or NULL: as kmpgpu_scan */,
                        kmpgpu_timing *t /* or NULL */);
 
+/* Per-pattern offset windows: WHERE in its payload a match has to start ("GET " at offset 0, a magic number in the first 8 bytes, a
+ * token only behind a 12-byte header; Snort / Suricata: offset, depth).  Pattern i gets a window [first_i, last_i] on the start offset
+ * s of a match inside its payload; the default, and the state without windows, is [0, UINT32_MAX].  A match (k, s, i) that counts under
+ * the rules at the top of this file (E_k as KMPGPU_OPT_WHOLE_PAYLOAD says, overlapping starts, KMPGPU_PAT_NOCASE per pattern) is IN
+ * WINDOW iff
+ *     first_i <= s <= last_i
+ * Snort's `offset:o; depth:d` for a pattern of m bytes is first = o, last = o + d - m; a prefix anchor is [0, 0].  A window that lies
+ * behind every payload's end never hits.  The window is on the payload's own offsets: a 0x00 in front of s takes the match away under
+ * the default E_k and does not under KMPGPU_OPT_WHOLE_PAYLOAD, exactly as without windows.
+ *
+ * Who follows the windows:
+ *     kmpgpu_scan_offsets   only in-window records are written, and *n_found is the number of in-window matches;
+ *     kmpgpu_scan_packets   hit[i][k] = payload k has at least one in-window match of pattern i; pkt_counts and any follow from that hit;
+ *     kmpgpu_scan_rules     rule_hit, rule_pkt_counts and any are defined over that hit; nothing else changes.
+ * Duplicate patterns have a window each (their rows and records then differ): this is how one byte string is used with two windows,
+ * in two rules or in one.
+ * Who does NOT: kmpgpu_scan and kmpgpu_scan_enqueue do not look at windows, and counts_out of the three calls above stays exactly
+ * what kmpgpu_scan returns -- every match, in window or not.  So with windows set pkt_counts[i] == 0 no longer implies
+ * counts[i] == 0, *n_found may be smaller than the sum of counts_out, and the context's own counters (KMPGPU_OPT_ACCUMULATE) are as
+ * untouched as before.  Windowed counts, windows relative to a payload's end and windows between two patterns (distance / within)
+ * do not exist.
+ * With no windows set, or with every window the default, every output of every call is bit-identical to what it is without this
+ * call, and the kernels run what they run without it.
+ *
+ * kmpgpu_set_windows copies first[n_pat], last[n_pat] and uploads them (8 bytes per pattern of device memory, owned by the context,
+ * uploaded on its stream, freed by kmpgpu_destroy).  The windows belong to the pattern set current at the call: no patterns set:
+ * KMPGPU_ESTATE; n_pat different from the context's pattern count, first[i] > last[i] for some i, or a NULL array: KMPGPU_EINVAL;
+ * after any error the windows set before stay in force.  n_pat == 0 clears the windows (first and last are ignored and may be
+ * NULL).  A later kmpgpu_set_patterns / kmpgpu_set_patterns_flags drops them, as it drops the rules.  Windows are pass state:
+ * they may be set, changed and cleared between two passes of one context with nothing reloaded or re-attached, and rules set
+ * earlier stay valid -- they name pattern indices, the windows change what a hit is.
+ * Cost (measured, DESIGN.md §3.13, profiles/windows.txt): nothing for kmpgpu_scan / kmpgpu_scan_enqueue, whose kernels are the
+ * code they were; a marking pass without windows takes the time it took within the run-to-run spread; with a window on every
+ * pattern the pass pays for the filter in its emitters -- with windows that drop nothing +4 % for one 16-byte pattern, +9 % for
+ * 97 tokens in the fused pass (a per-match load of the window), +25 % on text that matches at every offset -- and gets faster
+ * where the windows drop matches (97 tokens with [0, 63]: 0.71 of the time without windows). */
+int  kmpgpu_set_windows(kmpgpu_ctx *ctx, const uint32_t *first /* [n_pat] */, const uint32_t *last /* [n_pat] */, uint32_t n_pat);
+
 /* Fill a device arena with the synthetic payloads of kmp_synth.h (benchmark input S1/S2):
  * packet ids first_pkt_id .. first_pkt_id + n_pkts - 1 at the slots of the given device index. */
 int  kmpgpu_synth_fill(kmpgpu_ctx *ctx, void *d_arena, const void *d_pkt_off, const void *d_pkt_len,

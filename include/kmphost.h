@@ -90,6 +90,20 @@ typedef struct kmp_rules {
 int  kmp_rules_parse(const char *path, uint32_t n_patterns, kmp_rules *out, char errbuf[KMP_RULES_ERRBUF]);
 void kmp_rules_free(kmp_rules *r);
 
+/* ---- offset windows --------------------------------------------------------------------------
+ * Not in the reference: the windows of kmpgpu_set_windows (include/kmpgpu.h) from a text file.  One window per line,
+ *     <pattern index> <first> <last>
+ * three decimal fields separated by blanks: the pattern's position in the pattern file (0-based) and the first and the last start
+ * offset inside a payload at which a match of it is reported; '*' for <last> means no upper bound (UINT32_MAX).  Blank lines and
+ * lines whose first non-blank character is '#' are skipped; a pattern that no line names keeps the default window [0, UINT32_MAX].
+ * first_out / last_out have room for n_patterns values each and are what kmpgpu_set_windows takes; on an error their contents are
+ * unspecified.
+ * KMPHOST_EIO: the file cannot be opened; KMPHOST_EINVAL: a field that is not a number (or does not fit 32 bits), a line of fewer
+ * or more than three fields, an index >= n_patterns, first > last, a pattern named twice -- errbuf then starts with "line N: "
+ * (N counts every line of the file, from 1). */
+#define KMP_WINDOWS_ERRBUF 256
+int  kmp_windows_parse(const char *path, uint32_t n_patterns, uint32_t *first_out, uint32_t *last_out, char errbuf[KMP_WINDOWS_ERRBUF]);
+
 /* KMP failure function: replaces kmp_prefix (serial.c:217-238); prefix has room for m ints. */
 void kmp_failure_table(const uint8_t *pat, uint32_t m, int32_t *prefix);
 

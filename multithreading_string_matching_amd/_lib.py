@@ -23,6 +23,7 @@ GPU_SO = os.path.join(LIBDIR, "libkmpgpu.so")
 KMP_SYNTH_MAX_NEEDLE = 100
 KMP_PCAP_ERRBUF = 256
 KMP_RULES_ERRBUF = 256
+KMP_WINDOWS_ERRBUF = 256
 RULE_NOT = 0x80000000      # KMPGPU_RULE_NOT / KMP_RULE_NOT: the term's pattern must not be in the payload
 
 u8p = C.POINTER(C.c_uint8)
@@ -104,6 +105,7 @@ HOST_API = {
     "kmp_patterns_free": (None, [C.POINTER(Patterns)]),
     "kmp_rules_parse": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(Rules), C.c_char_p]),
     "kmp_rules_free": (None, [C.POINTER(Rules)]),
+    "kmp_windows_parse": (C.c_int, [C.c_char_p, C.c_uint32, u32p, u32p, C.c_char_p]),
     "kmp_failure_table": (None, [u8p, C.c_uint32, i32p]),
     "kmp_arena_from_pcap": (C.c_int, [C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Arena), C.c_char_p]),
     "kmp_arena_from_payloads": (C.c_int, [C.POINTER(u8p), u32p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(Arena)]),
@@ -159,6 +161,7 @@ GPU_API = {
     "kmpgpu_scan_packets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
     "kmpgpu_set_rules": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint32]),
     "kmpgpu_scan_rules": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
+    "kmpgpu_set_windows": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint32]),
     "kmpgpu_synth_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(SynthParams)]),
     "kmpgpu_fixed_index": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32]),
     "kmpgpu_arena_info": (C.c_int, [C.c_void_p, u64p, u64p]),

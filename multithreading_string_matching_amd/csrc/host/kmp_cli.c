@@ -26,6 +26,13 @@
  * index among the rule lines).  One of the two without the other, or a rules file that does not parse: message on stderr, exit 1,
  * before any GPU work.  Both go together with KMPGPU_NOCASE, KMPGPU_WHOLE_PAYLOAD, KMPGPU_DEVICE_EXTRACT and KMPGPU_PACKETS_FILE.
  *
+ * KMPGPU_WINDOWS_FILE=<windows>: per-pattern offset windows (kmpgpu_set_windows; the file format is kmp_windows_parse's, kmphost.h:
+ * "<pattern index> <first> <last>" per line, '*' for no upper bound) on every shard's context.  They take effect on the files written
+ * for KMPGPU_OFFSETS_FILE, KMPGPU_PACKETS_FILE and KMPGPU_RULES_FILE + KMPGPU_ALERTS_FILE: only the matches that start inside their
+ * pattern's window are listed, mark a payload or feed a rule.  stdout -- the counts -- is what it is without windows.  A windows
+ * file that does not parse, or one set without any of those output files (it has no effect): message on stderr, exit 1, before
+ * any GPU work.
+ *
  * KMPGPU_NOCASE=1: every pattern matches case-insensitively (ASCII letters; kmpgpu_set_patterns_flags), in the counts and in
  * the offsets file alike; the report prints every token as written in the pattern file.
  *
@@ -104,6 +111,9 @@ typedef struct shard_job {
     pthread_t thread;
 } shard_job;
 
+/* KMPGPU_WINDOWS_FILE: the windows every shard's context gets behind its patterns (NULL: none) */
+static uint32_t *g_win_first, *g_win_last;
+
 static int whole_payload_env(void)
 {
     const char *e = getenv("KMPGPU_WHOLE_PAYLOAD");
@@ -139,6 +149,7 @@ static void *shard_load(void *arg)
     shard_job *j = (shard_job *)arg;
     if (kmpgpu_init(&j->ctx, j->device)) return shard_fail(j, "kmpgpu_init");
     if (set_patterns_env(j->ctx, j->pp, j->pats->len, j->pats->n)) return shard_fail(j, "kmpgpu_set_patterns");
+    if (g_win_first && kmpgpu_set_windows(j->ctx, g_win_first, g_win_last, j->pats->n)) return shard_fail(j, "kmpgpu_set_windows");
     if (j->frames) {
         /* only the bytes this shard's frames span are uploaded (kmpgpu_load_frames) */
         if (kmpgpu_load_frames(j->ctx, j->frames->bytes, j->frames->nbytes, j->frames->off + j->lo, j->frames->caplen + j->lo, j->cnt, j->tcp,
@@ -214,6 +225,24 @@ int main(int argc, char *argv[])
         char rules_err[KMP_RULES_ERRBUF];
         if (kmp_rules_parse(rules_path, pats.n, &rules, rules_err)) {
             fprintf(stderr, "error reading rules file %s: %s\n", rules_path, rules_err);
+            exit(1);
+        }
+    }
+
+    /* the offset windows likewise */
+    const char *windows_path = getenv("KMPGPU_WINDOWS_FILE");
+    if (windows_path && windows_path[0]) {
+        const char *of = getenv("KMPGPU_OFFSETS_FILE"), *pf = getenv("KMPGPU_PACKETS_FILE");
+        if (!(of && of[0]) && !(pf && pf[0]) && !alerts_path) {
+            fprintf(stderr, "KMPGPU_WINDOWS_FILE has no effect without KMPGPU_OFFSETS_FILE, KMPGPU_PACKETS_FILE or KMPGPU_RULES_FILE + KMPGPU_ALERTS_FILE\n");
+            exit(1);
+        }
+        char windows_err[KMP_WINDOWS_ERRBUF];
+        g_win_first = (uint32_t *)malloc(sizeof(uint32_t) * (pats.n ? pats.n : 1));
+        g_win_last = (uint32_t *)malloc(sizeof(uint32_t) * (pats.n ? pats.n : 1));
+        if (!g_win_first || !g_win_last) { fprintf(stderr, "error reading windows file %s: out of memory\n", windows_path); exit(1); }
+        if (kmp_windows_parse(windows_path, pats.n, g_win_first, g_win_last, windows_err)) {
+            fprintf(stderr, "error reading windows file %s: %s\n", windows_path, windows_err);
             exit(1);
         }
     }
@@ -445,5 +474,6 @@ int main(int argc, char *argv[])
     kmp_frames_free(&frames);
     kmp_patterns_free(&pats);
     kmp_rules_free(&rules);
+    free(g_win_first); free(g_win_last);
     return 0;
 }

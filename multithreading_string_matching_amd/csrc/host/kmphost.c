@@ -498,6 +498,84 @@ void kmp_rules_free(kmp_rules *r)
     memset(r, 0, sizeof *r);
 }
 
+/* ============================ offset windows ============================================ */
+
+/* One field of a windows line at *pp: a decimal number that fits 32 bits, or (star_ok) a lone '*' = UINT32_MAX.  Leaves *pp behind
+ * the field and the blanks that follow it; on failure *tok / *tok_len name the field for the message (tok_len 0: the line ended). */
+static int windows_field(const char **pp, const char *end, int star_ok, uint32_t *out, const char **tok, int *tok_len)
+{
+    const char *p = *pp;
+    *tok = p;
+    uint64_t v = 0;
+    const char *digits = p;
+    while (p < end && *p >= '0' && *p <= '9') { if (v < (1ull << 40)) v = v * 10 + (uint64_t)(*p - '0'); p++; }
+    const char *stop = p;
+    while (stop < end && !is_c_space((uint8_t)*stop)) stop++;           /* the whole token, for the message */
+    *tok_len = (int)(stop - *tok > 64 ? 64 : stop - *tok);
+    int ok = p > digits && stop == p && v <= 0xFFFFFFFFull;
+    if (!ok && star_ok && stop == digits + 1 && *digits == '*') { v = 0xFFFFFFFFull; ok = 1; }
+    while (stop < end && is_c_space((uint8_t)*stop)) stop++;
+    *pp = stop;
+    *out = (uint32_t)v;
+    return ok;
+}
+
+int kmp_windows_parse(const char *path, uint32_t n_patterns, uint32_t *first_out, uint32_t *last_out, char errbuf[KMP_WINDOWS_ERRBUF])
+{
+    if (errbuf) errbuf[0] = 0;
+    FILE *fp = fopen(path, "rb");
+    if (!fp) {
+        if (errbuf) snprintf(errbuf, KMP_WINDOWS_ERRBUF, "%s: %s", path, strerror(errno));
+        return KMPHOST_EIO;
+    }
+    uint8_t *named = (uint8_t *)calloc(n_patterns ? n_patterns : 1, 1);
+    if (!named) { fclose(fp); if (errbuf) snprintf(errbuf, KMP_WINDOWS_ERRBUF, "out of memory"); return KMPHOST_ENOMEM; }
+    for (uint32_t i = 0; i < n_patterns; i++) { first_out[i] = 0u; last_out[i] = 0xFFFFFFFFu; }
+    char *line = NULL;
+    size_t line_cap = 0, lineno = 0;
+    ssize_t got;
+    int rc = KMPHOST_OK;
+    while (!rc && (got = getline(&line, &line_cap, fp)) >= 0) {
+        lineno++;
+        const char *p = line, *end = line + got;
+        while (p < end && is_c_space((uint8_t)*p)) p++;
+        if (p == end || *p == '#') continue;                           /* blank line, comment */
+        static const char *const what[3] = {"a pattern index", "a first offset", "a last offset or '*'"};
+        uint32_t f[3] = {0, 0, 0};
+        for (int k = 0; k < 3 && !rc; k++) {
+            const char *tok;
+            int tl;
+            if (p == end) {
+                if (errbuf) snprintf(errbuf, KMP_WINDOWS_ERRBUF, "line %zu: %d of the three fields <pattern index> <first> <last>", lineno, k);
+                rc = KMPHOST_EINVAL;
+            } else if (!windows_field(&p, end, k == 2, &f[k], &tok, &tl)) {
+                if (errbuf) snprintf(errbuf, KMP_WINDOWS_ERRBUF, "line %zu: '%.*s' is not %s", lineno, tl, tok, what[k]);
+                rc = KMPHOST_EINVAL;
+            }
+        }
+        if (rc) break;
+        if (p != end) {
+            if (errbuf) snprintf(errbuf, KMP_WINDOWS_ERRBUF, "line %zu: more than the three fields <pattern index> <first> <last>", lineno);
+            rc = KMPHOST_EINVAL;
+        } else if (f[0] >= n_patterns) {
+            if (errbuf) snprintf(errbuf, KMP_WINDOWS_ERRBUF, "line %zu: pattern index %u, but there are %u patterns", lineno, f[0], n_patterns);
+            rc = KMPHOST_EINVAL;
+        } else if (f[1] > f[2]) {
+            if (errbuf) snprintf(errbuf, KMP_WINDOWS_ERRBUF, "line %zu: first offset %u lies behind last offset %u", lineno, f[1], f[2]);
+            rc = KMPHOST_EINVAL;
+        } else if (named[f[0]]) {
+            if (errbuf) snprintf(errbuf, KMP_WINDOWS_ERRBUF, "line %zu: pattern %u has a window already", lineno, f[0]);
+            rc = KMPHOST_EINVAL;
+        } else {
+            named[f[0]] = 1; first_out[f[0]] = f[1]; last_out[f[0]] = f[2];
+        }
+    }
+    free(line);
+    free(named);
+    fclose(fp);
+    return rc;
+}
+
 /* serial.c:217-238 */
 void kmp_failure_table(const uint8_t *pat, uint32_t m, int32_t *prefix)
 {

@@ -129,7 +129,11 @@ __device__ __forceinline__ PatConst load_pat_const(const kmp_pattern_dev *gp)
  * reserves their slots, each lane's rank inside the ballot (mbcnt) is its slot.
  * Mark mode (kmpgpu_scan_packets, marks != NULL): no record; bit `pkt` of row `pattern` of the hit matrix
  * marks[rows][stride] is set instead.  The members behind `pattern` grow the struct by 16 bytes, so that
- * the kernel arguments that follow it keep their alignment. */
+ * the kernel arguments that follow it keep their alignment.
+ * Windows (kmpgpu_set_windows, windows != NULL): a match of pattern i at payload offset s is reported or marked only where
+ * windows[i].x <= s <= windows[i].y.  The flat and the packed kernel, whose pattern is one per block, read their pattern's pair into
+ * win_first / win_last ahead of the loop (a scalar load); the fused kernel, whose pattern is per lane, reads it per match.  These
+ * three members are another 16 bytes. */
 struct Emitter {
     uint4              *out;        /* kmpgpu_match[cap] viewed as 16-byte records */
     unsigned long long *counter;    /* matches found so far (may exceed cap)       */
@@ -138,7 +142,13 @@ struct Emitter {
     unsigned long long *marks;      /* mark mode: the hit matrix, or NULL          */
     uint32_t            mark_stride;/* 64-bit words per row (>= ceil(n_pkts / 64)) */
     uint32_t            mark_rows;  /* rows (patterns)                             */
+    const uint2        *windows;    /* {first, last} per pattern index, or NULL: no window differs from [0, UINT32_MAX] */
+    /* the next two, like `pattern`, are not arguments: the host passes 0 / UINT32_MAX, the flat and the packed kernel overwrite them
+     * with windows[pattern] before their loop (registers of the kernel's own copy of the struct); the fused kernel does not use them */
+    uint32_t            win_first;
+    uint32_t            win_last;
 };
+static_assert(sizeof(Emitter) % 16 == 0, "the kernel arguments behind the Emitter keep their alignment");
 
 /* Mark mode: the (pattern, packet) pairs of the ok lanes, one atomic OR per DISTINCT pair.  A 1 KiB chunk spans a few
  * packets at most, so the lanes of a call collapse into one or two pairs: take the first lane's pair, drop every lane
@@ -161,10 +171,9 @@ __device__ __forceinline__ void mark_match_as(bool ok, uint64_t pkt, uint32_t pa
     }
 }
 
-template <bool EMIT>
-__device__ __forceinline__ void emit_match_as(bool ok, uint64_t pkt, uint32_t offset, uint32_t pattern, const Emitter &e)
+/* What both emitters do with the lanes that are left: a record each, or their marks. */
+__device__ __forceinline__ void emit_filtered(bool ok, uint64_t pkt, uint32_t offset, uint32_t pattern, const Emitter &e)
 {
-    if (!EMIT) return;
     if (e.marks) { mark_match_as(ok, pkt, pattern, e); return; }      /* a kernel argument: wave-uniform */
     const uint64_t b = ballot64(ok);                 /* among the lanes that are active here */
     if (b == 0ull) return;
@@ -181,10 +190,27 @@ __device__ __forceinline__ void emit_match_as(bool ok, uint64_t pkt, uint32_t of
     }
 }
 
+/* A match of `pattern`, which may differ from lane to lane (the fused kernel: uid_ids[d]). */
+template <bool EMIT>
+__device__ __forceinline__ void emit_match_as(bool ok, uint64_t pkt, uint32_t offset, uint32_t pattern, const Emitter &e)
+{
+    if (!EMIT) return;
+    /* a kernel argument: wave-uniform.  One 8-byte load per lane that has a match, of its own pattern's window */
+    if (e.windows) {
+        uint2 win = make_uint2(0u, 0u);
+        if (ok) win = e.windows[pattern];
+        ok = ok && win.x <= offset && offset <= win.y;
+    }
+    emit_filtered(ok, pkt, offset, pattern, e);
+}
+
+/* The flat and the packed kernel: the pattern, and with it the window, is one per block (e.pattern, e.win_first, e.win_last). */
 template <bool EMIT>
 __device__ __forceinline__ void emit_match(bool ok, uint64_t pkt, uint32_t offset, const Emitter &e)
 {
-    emit_match_as<EMIT>(ok, pkt, offset, e.pattern, e);
+    if (!EMIT) return;
+    if (e.windows) ok = ok && e.win_first <= offset && offset <= e.win_last;      /* a kernel argument: wave-uniform */
+    emit_filtered(ok, pkt, offset, e.pattern, e);
 }
 
 /* Rare path, part 1: cut a lane's largest valid start index down by the strlen() rule -- no start

@@ -45,6 +45,10 @@ struct kmp_scan_args {
      * holds pattern i.  Runs the same EMIT kernels, grid and plan as the offsets pass, writing no record */
     unsigned long long    *emit_marks;
     uint32_t               mark_stride, mark_rows;
+    /* per-pattern offset windows (kmpgpu_set_windows): {first, last} by pattern index, 8 bytes each; a match is reported or marked only
+     * where first <= its offset in the payload <= last.  Set only for a pass that emits or marks, NULL where no window differs from the
+     * default [0, UINT32_MAX] */
+    const void            *emit_windows;
 };
 
 /* the pass writes offset records or marks: the launchers take the EMIT instantiations */

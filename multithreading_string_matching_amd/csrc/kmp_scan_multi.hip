@@ -620,9 +620,8 @@ kmp_scan_multi_body(const uint8_t *__restrict__ arena, const uint32_t *__restric
                                 for (int q4 = 0; q4 < 4; ++q4) {
                                     const uint64_t S = mqsad(w[q4], w[q4 + 1], ref, 0ull);
                                     if constexpr (!EMIT) {
-                                        Emitter none{};
                                         uint32_t dummy = 0u;
-                                        found = tally_group<false>(q4, S, barred, nv2, found, 0u, dummy, 0ull, none);
+                                        found = tally_group<false>(q4, S, barred, nv2, found, 0u, dummy, 0ull, em);       /* (not read: EMIT is false) */
                                     } else {
 #pragma unroll
                                         for (int a = 0; a < 4; ++a) {
@@ -818,7 +817,8 @@ hipError_t kmp_launch_scan_multi(const kmp_scan_args &a, const uint32_t *tables,
     const uint32_t bwaves = kmp_multi_block_waves(kind);
     const bool classed = a.fused_classed;
     const size_t lds = kmp_multi_lds_bytes(table_words, n_unique, bwaves) - KMP_MULTI_STATIC_BYTES;      /* the dynamic part */
-    const Emitter em{reinterpret_cast<uint4 *>(a.emit_out), a.emit_counter, a.emit_cap, 0u, a.emit_marks, a.mark_stride, a.mark_rows};
+    const Emitter em{reinterpret_cast<uint4 *>(a.emit_out), a.emit_counter, a.emit_cap, 0u, a.emit_marks, a.mark_stride, a.mark_rows,
+                     reinterpret_cast<const uint2 *>(a.emit_windows), 0u, 0xFFFFFFFFu};
     /* tuning builds only (make HIPFLAGS+=-DKMP_MULTI_TUNING; tools/fused_ablation.py, profiles/r02_fused_ablation.txt): cut the
      * kernel after a stage -- 1 = level 1 alone, 2 = + hit masking, 3 = + queueing; the counts are wrong then.  The product
      * build passes the constant 0. */

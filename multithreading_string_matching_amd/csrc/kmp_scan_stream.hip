@@ -117,7 +117,7 @@ kmp_plan_kernel(const uint64_t *__restrict__ pkt_off, const uint32_t *__restrict
 namespace {
 Emitter emitter_of(const kmp_scan_args &a)
 {
-    Emitter e;
+    Emitter e{};
     e.out = reinterpret_cast<uint4 *>(a.emit_out);
     e.counter = a.emit_counter;
     e.cap = a.emit_cap;
@@ -125,6 +125,9 @@ Emitter emitter_of(const kmp_scan_args &a)
     e.marks = a.emit_marks;
     e.mark_stride = a.mark_stride;
     e.mark_rows = a.mark_rows;
+    e.windows = reinterpret_cast<const uint2 *>(a.emit_windows);
+    e.win_first = 0u;
+    e.win_last = 0xFFFFFFFFu;
     return e;
 }
 

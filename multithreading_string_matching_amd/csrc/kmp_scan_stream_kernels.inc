@@ -61,6 +61,10 @@ KMP_FLAT_KERNEL(const uint8_t *__restrict__ arena, uint64_t n_pkts, uint32_t str
     const PatConst pc = load_pat_const(gp);
     const uint32_t m = pc.m;
     if (EMIT) em.pattern = pid;
+    if (EMIT && em.windows) {                /* this block's window, once: pid is uniform, a scalar load */
+        const uint2 win = em.windows[pid];
+        em.win_first = win.x; em.win_last = win.y;
+    }
 
     uint32_t cnt = 0u;
     {
@@ -183,6 +187,10 @@ KMP_PACKED_KERNEL(const uint8_t *__restrict__ arena, const uint64_t *__restrict_
     const PatConst pc = load_pat_const(gp);
     const uint32_t m = pc.m;
     if (EMIT) em.pattern = pid;
+    if (EMIT && em.windows) {                /* this block's window, once: pid is uniform, a scalar load */
+        const uint2 win = em.windows[pid];
+        em.win_first = win.x; em.win_last = win.y;
+    }
 
     uint32_t cnt = 0u;
     if (range) {

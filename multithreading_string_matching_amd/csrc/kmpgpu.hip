@@ -154,6 +154,9 @@ struct kmpgpu_ctx {
     uint4              *d_rule_heads = nullptr, *d_rule_quads = nullptr;
     unsigned long long *d_rule_out = nullptr;         /* rule rows [n_rules][stride], then rule_pkt_counts[n_rules], any[stride] */
     uint64_t            rule_out_cap = 0;             /* words */
+    /* kmpgpu_set_windows: {first, last} per pattern index as the emitters read it (kmp_launch.h, emit_windows); NULL: no windows set, or
+     * every one of them the default -- the emitting passes then run as they do without */
+    uint2              *d_windows = nullptr;
 
     /* options */
     int mode = 0, blocks_per_cu = 0 /* auto */, depth = 0 /* auto */, nontemporal = 1, kernel_sel = 0, fused = 2 /* auto */, accumulate = 0, repack = 1;
@@ -288,6 +291,13 @@ void drop_rules(kmpgpu_ctx *c)
     if (c->d_rule_quads) (void)hipFree(c->d_rule_quads);
     c->d_rule_heads = c->d_rule_quads = nullptr;
     c->n_rules = 0;
+}
+
+/* so do the windows */
+void drop_windows(kmpgpu_ctx *c)
+{
+    if (c->d_windows) (void)hipFree(c->d_windows);
+    c->d_windows = nullptr;
 }
 
 void release_arena(kmpgpu_ctx *c, bool keep_buffers = false)
@@ -504,6 +514,7 @@ int enqueue_set(kmpgpu_ctx *c, const kmpgpu_ctx::PatternSet &s, const uint8_t *a
     if (emit) {
         a.emit_out = emit->out; a.emit_counter = emit->counter; a.emit_cap = emit->cap;
         a.emit_marks = emit->marks; a.mark_stride = emit->mark_stride; a.mark_rows = c->n_pat;
+        a.emit_windows = c->d_windows;               /* every launch of the pass: streaming, fused, 1-byte reads, the nocase set */
     }
     /* uniform-stride arenas take the flat streaming kernel (contiguous packet run per wavefront) */
     const uint64_t nwaves = (uint64_t)bx * KMP_BLOCK_WAVES;
@@ -996,6 +1007,7 @@ void kmpgpu_destroy(kmpgpu_ctx *c)
     if (c->d_counts) (void)hipFree(c->d_counts);
     if (c->d_marks) (void)hipFree(c->d_marks);
     drop_rules(c);
+    drop_windows(c);
     if (c->d_rule_out) (void)hipFree(c->d_rule_out);
     if (c->d_plan) (void)hipFree(c->d_plan);
     if (c->d_uplan) (void)hipFree(c->d_uplan);
@@ -1130,6 +1142,7 @@ int kmpgpu_set_patterns_flags(kmpgpu_ctx *c, const uint8_t *const *pat, const ui
     free_pattern_set(c->sets[0]);
     free_pattern_set(c->sets[1]);
     drop_rules(c);                                 /* their indices meant the old patterns */
+    drop_windows(c);                               /* ... and so did the windows' */
     c->n_pat = n_pat;
     const size_t np = n_pat ? n_pat : 1;
     HIP_TRY(hipMalloc(&c->d_patterns, np * sizeof(kmp_pattern_dev)));
@@ -1748,6 +1761,42 @@ int kmpgpu_set_rules(kmpgpu_ctx *c, const uint32_t *rule_off, const uint32_t *te
     }
     drop_rules(c);
     c->d_rule_heads = d_heads; c->d_rule_quads = d_quads; c->n_rules = n_rules;
+    return KMPGPU_OK;
+}
+
+int kmpgpu_set_windows(kmpgpu_ctx *c, const uint32_t *first, const uint32_t *last, uint32_t n_pat)
+{
+    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_set_windows: ctx is NULL");
+    if (!c->d_patterns || c->n_pat == 0) return fail(KMPGPU_ESTATE, "kmpgpu_set_windows: no patterns set");
+    HIP_TRY(hipSetDevice(c->device));
+    if (n_pat == 0) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        drop_windows(c);
+        return KMPGPU_OK;
+    }
+    if (n_pat != c->n_pat) return fail(KMPGPU_EINVAL, "kmpgpu_set_windows: %u windows for %u patterns", n_pat, c->n_pat);
+    if (!first || !last) return fail(KMPGPU_EINVAL, "kmpgpu_set_windows: NULL window arrays");
+    std::vector<uint2> win(n_pat);
+    bool all_default = true;
+    for (uint32_t i = 0; i < n_pat; i++) {
+        if (first[i] > last[i]) return fail(KMPGPU_EINVAL, "kmpgpu_set_windows: pattern %u: first %u lies behind last %u", i, first[i], last[i]);
+        win[i] = make_uint2(first[i], last[i]);
+        all_default = all_default && first[i] == 0u && last[i] == 0xFFFFFFFFu;
+    }
+    /* no window differs from the default: no table, and the emitting passes run what they run without windows */
+    uint2 *d_win = nullptr;
+    if (!all_default) {
+        hipError_t e = hipMalloc((void **)&d_win, win.size() * sizeof(uint2));
+        if (e == hipSuccess) e = hipMemcpyAsync(d_win, win.data(), win.size() * sizeof(uint2), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      /* (win is a local) */
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            if (d_win) (void)hipFree(d_win);
+            return fail(e == hipErrorOutOfMemory ? KMPGPU_ENOMEM : KMPGPU_EHIP, "kmpgpu_set_windows: the windows could not be uploaded: %s", hipGetErrorString(e));
+        }
+    } else HIP_TRY(hipStreamSynchronize(c->stream));
+    drop_windows(c);
+    c->d_windows = d_win;
     return KMPGPU_OK;
 }
 

@@ -35,13 +35,16 @@ def device_count() -> int:
 
 
 class GpuMatcher:
-    def __init__(self, device: int = 0):
-        self._g = _lib.gpu_lib()
+    def __init__(self, device: int = 0, lib=None):
+        """lib: another build of libkmpgpu.so, loaded and bound by the caller (tools/windows.py times the parent commit's build next to
+        this one); every call of the matcher goes to it.  Default: the package's own library."""
+        self._g = lib if lib is not None else _lib.gpu_lib()
         self._ctx = C.c_void_p()
         gpu_check(self._g.kmpgpu_init(C.byref(self._ctx), device), "kmpgpu_init")
         self.device = device
         self.patterns: List[bytes] = []
         self.rules: list = []      # (all_of, none_of) per rule, as set_rules took them
+        self.windows: list = []    # (first, last) per pattern as set_windows took them (last None: unbounded), [] = none
         self._keep = None          # objects whose device memory the context borrows
         self._comm = None          # the GpuComm this matcher is a rank of: closed before the context
 
@@ -68,6 +71,7 @@ class GpuMatcher:
         gpu_check(self._g.kmpgpu_set_patterns_flags(self._ctx, ptrs, lens, flags, n), "kmpgpu_set_patterns_flags")
         self.patterns = list(patterns)
         self.rules = []            # the library drops its rules with the pattern set they referred to
+        self.windows = []          # ... and its windows
 
     def set_rules(self, rules) -> None:
         """Content rules over the current patterns (kmpgpu_set_rules): a sequence of (all_of, none_of) pattern-index sequences;
@@ -82,6 +86,23 @@ class GpuMatcher:
         terms = np.array([t for a, b in rules for t in a + [i | _lib.RULE_NOT for i in b]] or [0], dtype=np.uint32)
         gpu_check(self._g.kmpgpu_set_rules(self._ctx, off.ctypes.data_as(u32p), terms.ctypes.data_as(u32p), len(rules)), "kmpgpu_set_rules")
         self.rules = rules
+
+    def set_windows(self, windows) -> None:
+        """Offset windows of the current patterns (kmpgpu_set_windows): one (first, last) per pattern, last None = unbounded;
+        scan_offsets, scan_packets and scan_rules then report, mark and combine only the matches that start at first..last of
+        their payload.  scan() and every counts output are not affected.  None or an empty sequence clears the windows."""
+        windows = [(int(a), None if b is None else int(b)) for a, b in (windows or [])]
+        if not windows:
+            gpu_check(self._g.kmpgpu_set_windows(self._ctx, None, None, 0), "kmpgpu_set_windows")
+            self.windows = []
+            return
+        for a, b in windows:
+            if not 0 <= a <= 0xFFFFFFFF or not (b is None or 0 <= b <= 0xFFFFFFFF):
+                raise ValueError(f"window ({a}, {b}): offsets are 32-bit")
+        first = np.array([a for a, _ in windows], dtype=np.uint32)
+        last = np.array([0xFFFFFFFF if b is None else b for _, b in windows], dtype=np.uint32)
+        gpu_check(self._g.kmpgpu_set_windows(self._ctx, first.ctypes.data_as(u32p), last.ctypes.data_as(u32p), len(windows)), "kmpgpu_set_windows")
+        self.windows = windows
 
     # -- arena ------------------------------------------------------------------------------------
     def load_arena(self, arena, off: Optional[np.ndarray] = None, ln: Optional[np.ndarray] = None) -> None:
