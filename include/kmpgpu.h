@@ -274,7 +274,7 @@ int  kmpgpu_scan_offsets(kmpgpu_ctx *ctx, kmpgpu_match *out, uint64_t cap, uint6
                          uint64_t *counts_out);
 
 /* Which payloads hold which patterns (grep -l / grep -c per payload, an alert per packet, the filter in front of a packet
- * export): one bit per (pattern, payload), made on the device in one pass.  With c[k][i] the count defined at the top of
+ * export -- kmpgpu_load_selected takes any[] or a row and compacts those payloads on the device): one bit per (pattern, payload), made on the device in one pass.  With c[k][i] the count defined at the top of
  * this file for payload k and pattern i (E_k as KMPGPU_OPT_WHOLE_PAYLOAD says, overlapping starts, KMPGPU_PAT_NOCASE where the
  * pattern carries it):
  *     hit[i][k]     = c[k][i] >= 1
@@ -377,6 +377,40 @@ int  kmpgpu_scan_rules(kmpgpu_ctx *ctx, uint64_t *rule_pkt_counts_out /* [n_rule
  * 97 tokens in the fused pass (a per-match load of the window), +25 % on text that matches at every offset -- and gets faster
  * where the windows drop matches (97 tokens with [0, 63]: 0.71 of the time without windows). */
 int  kmpgpu_set_windows(kmpgpu_ctx *ctx, const uint32_t *first /* [n_pat] */, const uint32_t *last /* [n_pat] */, uint32_t n_pat);
+
+/* The payloads a bitmap selects, compacted on the device into a packed arena that a second context owns: the consumer of any[] and of
+ * the rows of kmpgpu_scan_packets / kmpgpu_scan_rules (the filter in front of a packet export -- only the selected bytes are downloaded
+ * --, and the cascade: a cheap first stage selects, a costly second one -- a thousand patterns, nocase sets -- scans the subset with
+ * patterns, rules and windows of its own; its hit rows and offsets refer to the compacted arena, and the bitmap's set bits map them
+ * back to the source).
+ * Selection: select is W = ceil(n_src / 64) 64-bit words laid out as kmpgpu_scan_packets lays them out (payload k is bit (k & 63) of
+ * word (k >> 6)), n_src being src's current payload count; bits of index n_src and above are ignored, whatever they hold.
+ * select_on_device == 0: host memory, borrowed for the call and uploaded; == 1: device memory on src's device (8-byte aligned),
+ * complete before the call, only read; any other value: KMPGPU_EINVAL.
+ * Result: dst owns a packed arena of exactly the selected payloads in ascending source order -- the j-th set bit below n_src is
+ * payload j --, each with its source length in a slot of max(16, round_up(len, 16)) bytes, slots back to back from offset 0.  Every
+ * byte between a payload's end and its slot's end is 0x00, whatever the source held there (a borrowed source may have dirty padding);
+ * an empty payload owns one zero slot.  The arena is in the state kmpgpu_load_frames leaves: owned by the context, padding known
+ * clean, packet-start bitmap and plans rebuilt, uniform / packed taken from a device-side pass over the new index, the nocase fold
+ * stale (made again by the first pass that needs it).  *n_selected (may be NULL) = the number of payloads.  No payload selected, or
+ * n_src == 0 (src without an arena; select may then be NULL): dst is left without an arena, as kmpgpu_load_arena(..., n_pkts = 0)
+ * leaves it -- scans return zeros --, the return value is KMPGPU_OK and dst's earlier arena is not kept.
+ * Untouched: src is not written; its arena, index and derived state stay, and every output of it is bit-identical before and after.
+ * The source is whatever src scans now -- loaded, attached (borrowed), extracted from frames, repacked, or kept in place under
+ * KMPGPU_OPT_REPACK = 0 (then not packed: the index is followed as it is).  dst's patterns, flags, rules, windows, options and
+ * counters stay too: they belong to the pattern set or the context, not to the arena.
+ * Ordering: synchronous.  Waits for dst's stream, as the loaders do, then for src's, as kmpgpu_counts_add does, and works on dst's
+ * stream.  dst's owned buffers are reused when the result fits and grown as the loaders grow them otherwise (kmpgpu_reserve sizes
+ * them); the workspace is the scratch dst keeps for kmpgpu_load_frames, so a ring of selections does not allocate per call.
+ * Errors: dst == src (selection in place does not exist), a NULL context, select NULL with n_src > 0, contexts on different devices
+ * (peer copies do not exist): KMPGPU_EINVAL; either context between kmpgpu_load_frames_begin and _finish: KMPGPU_ESTATE; after each
+ * of these dst keeps the arena it had.  After an allocation failure (KMPGPU_ENOMEM / KMPGPU_EHIP) dst is without an arena and both
+ * contexts stay usable.
+ * kmpgpu_last_timing(dst): h2d_ms / h2d_bytes of the bitmap upload (0 for a device bitmap), kernel_ms from the first selection kernel
+ * to the copy's end, launches = the kernels in that span (masked lengths, two scan kernels, index, copy: 5; 3 when nothing is selected).
+ * Cost: one read of src's lengths and offsets, one read of the selected slots and one write of them. */
+int  kmpgpu_load_selected(kmpgpu_ctx *dst, kmpgpu_ctx *src, const void *select /* uint64_t[ceil(n_src / 64)] */, int select_on_device,
+                          uint64_t *n_selected /* or NULL */);
 
 /* Fill a device arena with the synthetic payloads of kmp_synth.h (benchmark input S1/S2):
  * packet ids first_pkt_id .. first_pkt_id + n_pkts - 1 at the slots of the given device index. */

@@ -194,6 +194,12 @@ void kmp_report(FILE *fp, const kmp_patterns *pats, const uint64_t *counts, doub
 /* Write a classic little-endian pcap of Ethernet/IPv4/UDP frames around the arena's payloads
  * (test + benchmark tooling: proves arena-route == pcap-route). */
 int kmp_write_udp_pcap(const char *path, const uint8_t *arena, const uint64_t *off, const uint32_t *len, uint64_t n);
+/* The same in parts, for payloads that arrive arena by arena (the shards of a packet export): append == 0 starts the file (global
+ * header, then these n frames), append != 0 adds n frames behind what the file holds; first_record = the number of frames written
+ * before, which the record timestamps count on.  Parts written in order give byte for byte the file of one kmp_write_udp_pcap call
+ * over all payloads.  n == 0 with append == 0 leaves a valid capture without frames. */
+int kmp_write_udp_pcap_part(const char *path, int append, const uint8_t *arena, const uint64_t *off, const uint32_t *len, uint64_t n,
+                            uint64_t first_record);
 
 #ifdef __cplusplus
 }

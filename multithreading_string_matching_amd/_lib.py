@@ -123,6 +123,7 @@ HOST_API = {
     "kmp_synth_count_planted": (C.c_uint64, [u32p, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(SynthParams)]),
     "kmp_report": (None, [C.c_void_p, C.POINTER(Patterns), u64p, C.c_double]),
     "kmp_write_udp_pcap": (C.c_int, [C.c_char_p, u8p, u64p, u32p, C.c_uint64]),
+    "kmp_write_udp_pcap_part": (C.c_int, [C.c_char_p, C.c_int, u8p, u64p, u32p, C.c_uint64, C.c_uint64]),
 }
 
 # the symbols include/kmpgpu.h declares
@@ -162,6 +163,7 @@ GPU_API = {
     "kmpgpu_set_rules": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint32]),
     "kmpgpu_scan_rules": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
     "kmpgpu_set_windows": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint32]),
+    "kmpgpu_load_selected": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, u64p]),
     "kmpgpu_synth_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(SynthParams)]),
     "kmpgpu_fixed_index": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32]),
     "kmpgpu_arena_info": (C.c_int, [C.c_void_p, u64p, u64p]),

@@ -33,6 +33,14 @@
  * file that does not parse, or one set without any of those output files (it has no effect): message on stderr, exit 1, before
  * any GPU work.
  *
+ * KMPGPU_EXPORT_FILE=<out.pcap>: the payloads that hold at least one pattern (any of kmpgpu_scan_packets) -- with KMPGPU_RULES_FILE set,
+ * the payloads that at least one rule matches (any of kmpgpu_scan_rules) -- written as a capture, in payload order over all shards.
+ * Per shard the selection is compacted on the device into a second context (kmpgpu_load_selected) and only the selected bytes are
+ * downloaded.  The frames are the synthetic Ethernet/IPv4/UDP frames of kmp_write_udp_pcap around the payloads, also in tcp mode: the
+ * capture's own headers are not kept.  Windows (KMPGPU_WINDOWS_FILE) decide what a hit is here as in the packets file; with
+ * KMPGPU_RULES_FILE, KMPGPU_ALERTS_FILE may be left out when this variable is set.  A path that cannot be written: message on stderr,
+ * exit 1, before any GPU work.  stdout is what it is without the variable.
+ *
  * KMPGPU_NOCASE=1: every pattern matches case-insensitively (ASCII letters; kmpgpu_set_patterns_flags), in the counts and in
  * the offsets file alike; the report prints every token as written in the pattern file.
  *
@@ -217,7 +225,9 @@ int main(int argc, char *argv[])
     if (alerts_path && !alerts_path[0]) alerts_path = NULL;
     kmp_rules rules;
     memset(&rules, 0, sizeof rules);
-    if ((rules_path != NULL) != (alerts_path != NULL)) {
+    const char *export_path = getenv("KMPGPU_EXPORT_FILE");
+    if (export_path && !export_path[0]) export_path = NULL;
+    if ((rules_path != NULL) != (alerts_path != NULL) && !(rules_path && export_path)) {      /* (an export takes the rules' any[] without an alerts file) */
         fprintf(stderr, "KMPGPU_RULES_FILE and KMPGPU_ALERTS_FILE go together: %s is not set\n", rules_path ? "KMPGPU_ALERTS_FILE" : "KMPGPU_RULES_FILE");
         exit(1);
     }
@@ -233,8 +243,8 @@ int main(int argc, char *argv[])
     const char *windows_path = getenv("KMPGPU_WINDOWS_FILE");
     if (windows_path && windows_path[0]) {
         const char *of = getenv("KMPGPU_OFFSETS_FILE"), *pf = getenv("KMPGPU_PACKETS_FILE");
-        if (!(of && of[0]) && !(pf && pf[0]) && !alerts_path) {
-            fprintf(stderr, "KMPGPU_WINDOWS_FILE has no effect without KMPGPU_OFFSETS_FILE, KMPGPU_PACKETS_FILE or KMPGPU_RULES_FILE + KMPGPU_ALERTS_FILE\n");
+        if (!(of && of[0]) && !(pf && pf[0]) && !alerts_path && !export_path) {
+            fprintf(stderr, "KMPGPU_WINDOWS_FILE has no effect without KMPGPU_OFFSETS_FILE, KMPGPU_PACKETS_FILE, KMPGPU_EXPORT_FILE or KMPGPU_RULES_FILE + KMPGPU_ALERTS_FILE\n");
             exit(1);
         }
         char windows_err[KMP_WINDOWS_ERRBUF];
@@ -245,6 +255,12 @@ int main(int argc, char *argv[])
             fprintf(stderr, "error reading windows file %s: %s\n", windows_path, windows_err);
             exit(1);
         }
+    }
+
+    /* the export starts as a capture without frames: a path that cannot be written ends the run here */
+    if (export_path && kmp_write_udp_pcap_part(export_path, 0, NULL, NULL, NULL, 0, 0)) {
+        perror("KMPGPU_EXPORT_FILE");
+        exit(1);
     }
 
 #if !KMP_CLI_OPENMP_FORM
@@ -436,6 +452,36 @@ int main(int argc, char *argv[])
                 shard_lo += np;
             }
             fclose(al_fp);
+        }
+        if (export_path) {
+            uint64_t written = 0;                                           /* frames in the file so far */
+            for (int r = 0; r < shards; r++) {
+                uint64_t np = 0, nsel = 0, nb = 0;
+                kmpgpu_arena_info(ctxs[r], &np, NULL);
+                const uint64_t W = (np + 63) / 64;
+                uint64_t *any = (uint64_t *)calloc((size_t)(W ? W : 1), sizeof(uint64_t));
+                if (!any) die_gpu("KMPGPU_EXPORT_FILE: out of memory");
+                if (rules_path) {
+                    if (rules.n && kmpgpu_set_rules(ctxs[r], rules.off, rules.terms, rules.n)) die_gpu("kmpgpu_set_rules");
+                    if (rules.n && kmpgpu_scan_rules(ctxs[r], NULL, any, NULL, NULL, NULL)) die_gpu("kmpgpu_scan_rules");
+                } else if (kmpgpu_scan_packets(ctxs[r], NULL, any, NULL, NULL, NULL)) die_gpu("kmpgpu_scan_packets");
+                /* the shard's selection, compacted next to it on its device; only these bytes come back */
+                kmpgpu_ctx *ex = NULL;
+                if (kmpgpu_init(&ex, job[r].device)) die_gpu("kmpgpu_init");
+                if (kmpgpu_load_selected(ex, ctxs[r], any, 0, &nsel)) die_gpu("kmpgpu_load_selected");
+                free(any);
+                if (nsel) {
+                    if (kmpgpu_arena_download(ex, NULL, 0, &nb, NULL, NULL)) die_gpu("kmpgpu_arena_download");
+                    uint8_t *bytes = (uint8_t *)malloc((size_t)(nb ? nb : 1));
+                    uint64_t *off = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)nsel);
+                    uint32_t *len = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)nsel);
+                    if (!bytes || !off || !len || kmpgpu_arena_download(ex, bytes, nb, &nb, off, len)) die_gpu("kmpgpu_arena_download");
+                    if (kmp_write_udp_pcap_part(export_path, 1, bytes, off, len, nsel, written)) { perror("KMPGPU_EXPORT_FILE"); exit(1); }
+                    written += nsel;
+                    free(bytes); free(off); free(len);
+                }
+                kmpgpu_destroy(ex);
+            }
         }
         for (int r = 0; r < shards && want_stats; r++) {
             uint64_t e = 0;

@@ -1005,12 +1005,14 @@ void kmp_report(FILE *fp, const kmp_patterns *pats, const uint64_t *counts, doub
 
 /* ============================ pcap writer (tooling) ===================================== */
 
-int kmp_write_udp_pcap(const char *path, const uint8_t *arena, const uint64_t *off, const uint32_t *len, uint64_t n)
+/* append == 0: a new file, global header first; != 0: records behind what the file holds */
+int kmp_write_udp_pcap_part(const char *path, int append, const uint8_t *arena, const uint64_t *off, const uint32_t *len, uint64_t n,
+                            uint64_t first_record)
 {
-    FILE *fp = fopen(path, "wb");
+    FILE *fp = fopen(path, append ? "ab" : "wb");
     if (!fp) return KMPHOST_EIO;
     const uint32_t gh[6] = {0xA1B2C3D4u, 0x00040002u, 0, 0, 262144u, 1u};   /* v2.4, Ethernet */
-    fwrite(gh, sizeof gh, 1, fp);
+    if (!append && fwrite(gh, sizeof gh, 1, fp) != 1) { fclose(fp); return KMPHOST_EIO; }
     uint8_t hdr[42];
     memset(hdr, 0, sizeof hdr);
     for (int i = 0; i < 12; i++) hdr[i] = (uint8_t)(i + 1);
@@ -1019,8 +1021,9 @@ int kmp_write_udp_pcap(const char *path, const uint8_t *arena, const uint64_t *o
     hdr[22] = 64;                               /* TTL */
     hdr[23] = 17;                               /* UDP */
     for (uint64_t k = 0; k < n; k++) {
+        const uint64_t rec = first_record + k;
         const uint32_t L = len[k], tot = 42u + L;
-        const uint32_t rh[4] = {(uint32_t)(k / 1000000u), (uint32_t)(k % 1000000u), tot, tot};
+        const uint32_t rh[4] = {(uint32_t)(rec / 1000000u), (uint32_t)(rec % 1000000u), tot, tot};
         hdr[16] = (uint8_t)((28u + L) >> 8); hdr[17] = (uint8_t)(28u + L);
         hdr[38] = (uint8_t)((8u + L) >> 8); hdr[39] = (uint8_t)(8u + L);
         if (fwrite(rh, sizeof rh, 1, fp) != 1 || fwrite(hdr, sizeof hdr, 1, fp) != 1 ||
@@ -1030,4 +1033,9 @@ int kmp_write_udp_pcap(const char *path, const uint8_t *arena, const uint64_t *o
         }
     }
     return fclose(fp) ? KMPHOST_EIO : KMPHOST_OK;
+}
+
+int kmp_write_udp_pcap(const char *path, const uint8_t *arena, const uint64_t *off, const uint32_t *len, uint64_t n)
+{
+    return kmp_write_udp_pcap_part(path, 0, arena, off, len, n, 0);
 }

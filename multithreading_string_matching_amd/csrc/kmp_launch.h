@@ -76,6 +76,8 @@ size_t kmp_multi_lds_bytes(uint32_t table_words, uint32_t n_unique, uint32_t wav
 int kmp_multi_kind(bool emit, bool pad_clean, uint32_t n_ones);
 uint32_t kmp_multi_block_waves(int kind);
 uint32_t kmp_multi_resident_waves(int kind, uint32_t table_words, uint32_t n_unique);
+#define KMP_SCAN_ITEMS 4u                                         /* items per thread in the block scan of kmp_prep.hip */
+#define KMP_SCAN_TILE  (KMP_BLOCK_THREADS * KMP_SCAN_ITEMS)      /* items per block: the scan workspace holds one total per tile */
 size_t kmp_extract_ws_bytes(uint64_t n_frames);
 hipError_t kmp_launch_extract_phase1(const uint8_t *file, const uint64_t *frame_off, const uint32_t *caplen, uint64_t n, int tcp,
                                      uint8_t *ws, unsigned long long *totals, hipStream_t st);
@@ -113,5 +115,15 @@ hipError_t kmp_launch_rules(const unsigned long long *marks, uint64_t stride, ui
                             hipStream_t st);
 hipError_t kmp_launch_fixed_index(uint64_t *pkt_off, uint32_t *pkt_len, uint64_t n, uint32_t len, uint64_t stride,
                                   hipStream_t st);
+/* kmp_select.hip (kmpgpu_load_selected): the payloads of an index of n whose bit is set in select[ceil(n / 64)] (payload k: bit k & 63 of
+ * word k >> 6; bits at n and above are not read as payloads), compacted into a packed arena.  ws: kmp_extract_ws_bytes(n) bytes, kept
+ * from phase 1 to phase 2.  Phase 1 (3 kernels) leaves totals[0] = bytes of the packed selection, totals[1] = selected payloads n_sel.
+ * Phase 2 (2 kernels) writes pkt_off[n_sel], pkt_len[n_sel], the 16-byte records recs[n_sel] the copy reads, and arena[0, total_bytes):
+ * every slot whole, 0x00 behind its payload's end.  The source's slots are 16-byte aligned (the layout contract of kmpgpu.h). */
+hipError_t kmp_launch_select_phase1(const unsigned long long *select, const uint32_t *pkt_len, uint64_t n, uint8_t *ws,
+                                    unsigned long long *totals, hipStream_t st);
+hipError_t kmp_launch_select_phase2(const uint8_t *src_arena, const uint64_t *src_off, uint64_t n, uint8_t *ws, uint64_t n_sel,
+                                    uint64_t total_bytes, uint8_t *arena, uint64_t *pkt_off, uint32_t *pkt_len, void *recs,
+                                    bool nontemporal, hipStream_t st);
 
 #endif

@@ -22,8 +22,7 @@ namespace {
  *   kmp_scan_*_kernel       exclusive scan of {slot bytes, valid} -> slot offsets and packet indices
  *   kmp_gather_kernel       one wavefront per payload: copy it to its 16-byte aligned slot, zero the pad
  * ============================================================================================== */
-#define KMP_SCAN_ITEMS 4u                                         /* items per thread in the block scan */
-#define KMP_SCAN_TILE  (KMP_BLOCK_THREADS * KMP_SCAN_ITEMS)
+/* (KMP_SCAN_ITEMS, KMP_SCAN_TILE: kmp_launch.h) */
 
 __global__ void __launch_bounds__(KMP_BLOCK_THREADS)
 kmp_extract_kernel(const uint8_t *__restrict__ file, const uint64_t *__restrict__ frame_off,

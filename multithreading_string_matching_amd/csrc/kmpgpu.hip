@@ -1445,6 +1445,103 @@ int kmpgpu_attach_arena(kmpgpu_ctx *c, const void *d_arena, uint64_t arena_bytes
     return prepare_packed(c);
 }
 
+int kmpgpu_load_selected(kmpgpu_ctx *dst, kmpgpu_ctx *src, const void *select, int select_on_device, uint64_t *n_selected)
+{
+    if (n_selected) *n_selected = 0;
+    if (!dst || !src) return fail(KMPGPU_EINVAL, "kmpgpu_load_selected: ctx is NULL");
+    if (dst == src) return fail(KMPGPU_EINVAL, "kmpgpu_load_selected: dst and src are the same context (selection in place does not exist)");
+    if (select_on_device != 0 && select_on_device != 1) return fail(KMPGPU_EINVAL, "kmpgpu_load_selected: select_on_device is %d, not 0 or 1", select_on_device);
+    if (dst->device != src->device)
+        return fail(KMPGPU_EINVAL, "kmpgpu_load_selected: the contexts sit on devices %d and %d (selection across devices does not exist)", dst->device, src->device);
+    if (dst->fr_pending || src->fr_pending) return fail(KMPGPU_ESTATE, "kmpgpu_load_selected: %s sits between kmpgpu_load_frames_begin and _finish", dst->fr_pending ? "dst" : "src");
+    const uint64_t n = src->n_pkts;
+    if (n && !select) return fail(KMPGPU_EINVAL, "kmpgpu_load_selected: select is NULL");
+    if (n && select_on_device && ((uintptr_t)select & 7u)) return fail(KMPGPU_EINVAL, "kmpgpu_load_selected: the device bitmap is not 8-byte aligned");
+    HIP_TRY(hipSetDevice(dst->device));
+    HIP_TRY(hipStreamSynchronize(dst->stream));           /* the passes over the arena that is about to be replaced */
+    HIP_TRY(hipStreamSynchronize(src->stream));           /* whatever src's stream still does with its arena */
+    kmpgpu_ctx *c = dst;
+    c->last = kmpgpu_timing{};
+    if (n == 0) { release_arena(c, /* keep_buffers = */ true); return KMPGPU_OK; }
+
+    /* the scratch of kmpgpu_load_frames: fr_off takes the uploaded bitmap, fr_ws the scan, fr_src the copy's records */
+    const uint64_t words = (n + 63) / 64;
+    HIP_TRY(grow_buffer(&c->fr_ws, &c->fr_ws_cap, (uint64_t)kmp_extract_ws_bytes(n)));
+    if (!c->fr_tot) HIP_TRY(hipMalloc(&c->fr_tot, 2 * sizeof(unsigned long long)));
+    const unsigned long long *d_select = (const unsigned long long *)select;
+    if (!select_on_device) {
+        HIP_TRY(grow_buffer(&c->fr_off, &c->fr_off_cap, words));
+        HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+        HIP_TRY(hipMemcpyAsync(c->fr_off, select, words * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+        d_select = (const unsigned long long *)c->fr_off;
+    }
+    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+    HIP_TRY(kmp_launch_select_phase1(d_select, src->d_len, n, c->fr_ws, c->fr_tot, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_small, c->fr_tot, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));         /* (pinned: no staging) */
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    unsigned long long tot[2] = {0, 0};
+    memcpy(tot, c->h_small, sizeof tot);
+    if (!select_on_device) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+        c->last.h2d_ms = ms; c->last.h2d_bytes = words * sizeof(uint64_t);
+    }
+    const uint64_t n_pkts = tot[1], arena_bytes = tot[0] + 64;
+    /* from here on dst's earlier arena is gone, whatever happens */
+    release_arena(c, /* keep_buffers = */ true);
+    if (n_pkts == 0) {
+        HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+        HIP_TRY(hipEventSynchronize(c->ev[3]));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
+        c->last.kernel_ms = ms; c->last.launches = 3;
+        return KMPGPU_OK;
+    }
+    if (!(c->owned_arena && c->cap_arena >= arena_bytes && c->cap_pkts >= n_pkts)) {
+        if (c->owned_arena) HIP_TRY(hipFree(c->owned_arena));
+        if (c->owned_off) HIP_TRY(hipFree(c->owned_off));
+        if (c->owned_len) HIP_TRY(hipFree(c->owned_len));
+        c->owned_arena = c->owned_off = c->owned_len = nullptr; c->cap_arena = c->cap_pkts = 0;
+        const uint64_t take_b = arena_bytes + arena_bytes / 8, take_n = n_pkts + n_pkts / 8;
+        hipError_t e = hipMalloc(&c->owned_arena, take_b);
+        if (e == hipSuccess) e = hipMalloc(&c->owned_off, take_n * sizeof(uint64_t));
+        if (e == hipSuccess) e = hipMalloc(&c->owned_len, take_n * sizeof(uint32_t));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            release_arena(c);                             /* (frees what was allocated: dst is empty and usable) */
+            return fail(e == hipErrorOutOfMemory ? KMPGPU_ENOMEM : KMPGPU_EHIP, "kmpgpu_load_selected: an arena of %llu bytes / %llu payloads could not be allocated: %s",
+                        (unsigned long long)take_b, (unsigned long long)take_n, hipGetErrorString(e));
+        }
+        c->cap_arena = take_b; c->cap_pkts = take_n;
+    }
+    {
+        const hipError_t e = grow_buffer(&c->fr_src, &c->fr_src_cap, 2 * n_pkts);      /* 16 bytes per selected payload */
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(e == hipErrorOutOfMemory ? KMPGPU_ENOMEM : KMPGPU_EHIP, "kmpgpu_load_selected: the copy's records (%llu payloads) could not be allocated: %s",
+                        (unsigned long long)n_pkts, hipGetErrorString(e));
+        }
+    }
+    HIP_TRY(hipMemsetAsync((uint8_t *)c->owned_arena + tot[0], 0, 64, c->stream));
+    HIP_TRY(kmp_launch_select_phase2(src->d_arena, src->d_off, n, c->fr_ws, n_pkts, tot[0], (uint8_t *)c->owned_arena, (uint64_t *)c->owned_off,
+                                     (uint32_t *)c->owned_len, c->fr_src, c->nontemporal != 0, c->stream));
+    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    c->d_arena = (const uint8_t *)c->owned_arena;
+    c->d_off = (const uint64_t *)c->owned_off;
+    c->d_len = (const uint32_t *)c->owned_len;
+    c->arena_bytes = arena_bytes; c->n_pkts = n_pkts;
+    c->pad_known_clean = true;                            /* kmp_select_copy_kernel writes every slot whole: payload, then 0x00 up to the slot's end */
+    const int rc = finish_device_index(c, "kmpgpu_load_selected");
+    c->pad_known_clean = false;
+    if (rc) { release_arena(c, true); return rc; }
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
+    c->last.kernel_ms = ms; c->last.launches = 5;
+    if (n_selected) *n_selected = n_pkts;
+    return KMPGPU_OK;
+}
+
 int kmpgpu_scan_enqueue(kmpgpu_ctx *c, void *d_counts_out)
 {
     if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_scan_enqueue: ctx is NULL");

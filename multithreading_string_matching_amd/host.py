@@ -189,6 +189,15 @@ def write_udp_pcap(path: str, arena: np.ndarray, off: np.ndarray, ln: np.ndarray
         raise KmpHostError(f"kmp_write_udp_pcap failed: {rc}")
 
 
+def write_udp_pcap_part(path: str, append: bool, arena: np.ndarray, off: np.ndarray, ln: np.ndarray, first_record: int = 0) -> None:
+    """One part of a capture written arena by arena (kmp_write_udp_pcap_part): append=False starts the file."""
+    L = _lib.host_lib()
+    rc = L.kmp_write_udp_pcap_part(path.encode(), 1 if append else 0, _np_ptr(arena, u8p), _np_ptr(off, u64p), _np_ptr(ln, u32p), len(ln),
+                                   first_record)
+    if rc:
+        raise KmpHostError(f"kmp_write_udp_pcap_part failed: {rc}")
+
+
 def format_report(patterns: Sequence[bytes], counts: Sequence[int]) -> str:
     """stdout of the reference minus the elapsed line (serial.c:163-166)."""
     lines = ["Printing the number of appereances of each string throughout the entire pcap file:"]

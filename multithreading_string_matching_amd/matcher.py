@@ -34,6 +34,30 @@ def device_count() -> int:
     return n
 
 
+def select_words(select: np.ndarray, n_src: int) -> np.ndarray:
+    """The bitmap words kmpgpu_load_selected takes (payload k = bit k & 63 of word k >> 6) from what GpuMatcher.load_selected is
+    given on the host: bool[n_src], packed here, or uint64[ceil(n_src / 64)], passed through.  No device needed."""
+    W = (n_src + 63) // 64
+    select = np.asarray(select)
+    if select.dtype == np.bool_:
+        if select.shape != (n_src,):
+            raise ValueError(f"select: bool{list(select.shape)} for {n_src} payloads")
+        b = np.zeros(W * 64, dtype=np.uint8)
+        b[:n_src] = select
+        return np.packbits(b, bitorder="little").view(np.uint64) if W else np.zeros(0, dtype=np.uint64)
+    if select.dtype != np.uint64 or select.shape != (W,):
+        raise ValueError(f"select: {select.dtype}{list(select.shape)}; bool[{n_src}] or uint64[{W}] is needed")
+    return np.ascontiguousarray(select)
+
+
+def selected_indices(words: np.ndarray, n_src: int) -> np.ndarray:
+    """Ascending indices of the set bits below n_src of uint64 bitmap words: the map from the payloads of a selection back to
+    the source's (bits at n_src and above are ignored, as kmpgpu_load_selected ignores them)."""
+    words = np.ascontiguousarray(words, dtype=np.uint64)
+    bits = np.unpackbits(words.view(np.uint8), bitorder="little")[:n_src]
+    return np.flatnonzero(bits).astype(np.uint64)
+
+
 class GpuMatcher:
     def __init__(self, device: int = 0, lib=None):
         """lib: another build of libkmpgpu.so, loaded and bound by the caller (tools/windows.py times the parent commit's build next to
@@ -150,6 +174,40 @@ class GpuMatcher:
             return int(n.value), int(fr.n)
         finally:
             H.kmp_frames_free(C.byref(fr))
+
+    def load_selected(self, src: "GpuMatcher", select) -> np.ndarray:
+        """Make this matcher's arena the payloads of ``src`` that ``select`` picks, compacted on the device in ascending source
+        order (kmpgpu_load_selected); patterns, rules, windows and options of this matcher stay.  select: a bool[n_src] numpy
+        array (packed here), a uint64[W] numpy array of bitmap words as scan_packets lays them out (W = ceil(n_src / 64)), or
+        a torch tensor of W 64-bit words (int64 / uint64) on src's device, which is handed over as it is.  Returns the source
+        indices of the selected payloads: payload j of this matcher is payload result[j] of src (for a device bitmap the words
+        are copied to the host once for this)."""
+        n_src, _ = src.arena_info()
+        W = (n_src + 63) // 64
+        on_device = 0
+        if isinstance(select, np.ndarray):
+            words = select_words(select, n_src)
+            ptr = words.ctypes.data if W else None
+        else:                                     # a torch tensor
+            if select.dtype.itemsize != 8 or select.dtype.is_floating_point or select.numel() != W:
+                raise ValueError(f"select: a tensor of {W} 64-bit words is needed for {n_src} payloads")
+            if select.is_cuda:
+                if select.device.index != src.device or not select.is_contiguous():
+                    raise ValueError("select: the tensor must be contiguous and on the source's device")
+                import torch
+                torch.cuda.current_stream(select.device).synchronize()       # complete before the call (kmpgpu.h)
+                on_device, ptr = 1, (select.data_ptr() if W else None)
+                words = select.cpu().numpy().view(np.uint64).reshape(-1)
+            else:
+                words = np.ascontiguousarray(select.numpy()).view(np.uint64).reshape(-1)
+                ptr = words.ctypes.data if W else None
+        n = C.c_uint64()
+        gpu_check(self._g.kmpgpu_load_selected(self._ctx, src._ctx, ptr, on_device, C.byref(n)), "kmpgpu_load_selected")
+        self._keep = None
+        idx = selected_indices(words, n_src)
+        if idx.size != int(n.value):
+            raise KmpGpuError(f"kmpgpu_load_selected reports {int(n.value)} payloads, the bitmap holds {idx.size}")
+        return idx
 
     def arena_download(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         n, _ = self.arena_info()
