@@ -1,6 +1,7 @@
 /*
- * kmp_device.h -- layouts shared by the HIP kernels (kmp_scan_*.hip / kmp_prep.hip) and the C-ABI host code
- * (kmpgpu.hip).  gfx950 only.
+ * kmp_device.h -- layouts shared by the HIP kernels (kmp_scan_*.hip / kmp_prep.hip) and the host code: the C-ABI layer
+ * (kmpgpu.hip) and the builder of the fused pass's tables (kmp_tables.cpp, which includes no HIP header: neither does this file).
+ * gfx950 only.
  */
 #ifndef KMP_DEVICE_H
 #define KMP_DEVICE_H
@@ -27,7 +28,7 @@ typedef struct __attribute__((aligned(16))) kmp_pattern_dev {
 } kmp_pattern_dev;
 
 /* Tables of the fused multi-pattern kernel (kmp_scan_multi_kernel), one blob of uint32 words built on
- * the host (kmpgpu_set_patterns) and copied into LDS by every block:
+ * the host (kmpgpu_set_patterns: kmp_build_tables, kmp_tables.cpp) and copied into LDS by every block:
  *   [0, 2048)        two words per bucket KMP_MULTI_HASH(key): its first entry itself, then where its further entries start
  *                    (bits 0-15) | number of entries (bits 16-31) -- one 8-byte read decides a bucket of one pattern.
  *                    key = b0 | b1 << 8 | (b2 & 31) << 16 (bucket mask KMP_MULTI_KEYMASK): patterns that only share their

@@ -1,4 +1,5 @@
-/* kmp_launch.h -- launch entry points of kmp_scan_*.hip / kmp_prep.hip, used by the C-ABI layer (kmpgpu.hip). */
+/* kmp_launch.h -- launch entry points of kmp_scan_*.hip / kmp_prep.hip / kmp_fold.hip / kmp_marks.hip / kmp_rules.hip / kmp_select.hip, used
+ * by the C-ABI layer (kmpgpu.hip), which alone decides what is launched; the tables kmp_launch_scan_multi takes come from kmp_tables.h. */
 #ifndef KMP_LAUNCH_H
 #define KMP_LAUNCH_H
 

@@ -24,6 +24,7 @@
 #include "kmpgpu.h"
 #include "kmp_device.h"
 #include "kmp_launch.h"
+#include "kmp_tables.h"
 
 namespace {
 
@@ -45,6 +46,19 @@ int fail(int code, const char *fmt, ...)
         hipError_t e_ = (expr);                                                                             \
         if (e_ != hipSuccess) return fail(KMPGPU_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_));     \
     } while (0)
+
+/* A device allocation or upload that failed: KMPGPU_ENOMEM where the memory ran out, the runtime's error state cleared.  fmt says what
+ * was being taken; the runtime's own text follows it. */
+int alloc_fail(hipError_t e, const char *fmt, ...)
+{
+    (void)hipGetLastError();
+    char what[384];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(what, sizeof what, fmt, ap);
+    va_end(ap);
+    return fail(e == hipErrorOutOfMemory ? KMPGPU_ENOMEM : KMPGPU_EHIP, "%s: %s", what, hipGetErrorString(e));
+}
 
 /* Failure function, as kmp_prefix (serial.c:217-238). */
 void failure_table(const uint8_t *pat, uint32_t m, uint8_t *out)
@@ -107,21 +121,22 @@ struct kmpgpu_ctx {
     bool            uniform = false;                  /* every payload has the same length, slots back to back */
     bool            packed = false;                   /* slots back to back (any lengths): flat streaming with bitmap + plan */
     bool            pad_clean = false;                /* packed arena whose slot padding is all 0x00 (kmp_check_padding_kernel) */
-    bool            pad_known_clean = false;          /* set around prepare_packed by a loader that wrote the padding itself: no check pass */
     uint64_t        span_end = 0;                     /* end offset of the last slot */
     unsigned long long *d_bitmap = nullptr;           /* one bit per 16-byte slot: a payload starts here */
-    void           *d_plan = nullptr;                 /* kmp_plan_entry[plan_waves + 1] */
+    uint4          *d_plan = nullptr;                 /* kmp_plan_entry[plan_waves + 1], 16 bytes each */
     uint64_t        plan_waves = 0, plan_cap = 0;
     uint32_t       *d_pool = nullptr;                 /* fused pass: next pool unit of every region */
     uint64_t        pool_cap = 0;
-    void           *d_uplan = nullptr;                /* fused pass: kmp_plan_entry[uplan_units + 1], the work units of its blocks' regions */
+    uint4          *d_uplan = nullptr;                /* fused pass: kmp_plan_entry[uplan_units + 1], the work units of its blocks' regions */
     uint64_t        uplan_units = 0, uplan_cap = 0;
     kmp_plan_shape  uplan_shape{};                    /* what d_uplan was cut for */
     int             fused_unit = 0;                   /* KMPGPU_OPT_FUSED_UNIT */
     int             whole_payload = 0;                /* KMPGPU_OPT_WHOLE_PAYLOAD: pass state, read when a pass is enqueued */
     uint64_t        uni_off0 = 0;
     uint32_t        uni_stride = 0, uni_len = 0;
-    void           *owned_arena = nullptr, *owned_off = nullptr, *owned_len = nullptr;
+    uint8_t        *owned_arena = nullptr;
+    uint64_t       *owned_off = nullptr;
+    uint32_t       *owned_len = nullptr;
     uint64_t        cap_arena = 0, cap_pkts = 0;      /* capacities of the owned buffers (reused by the next load) */
     uint64_t        bitmap_cap = 0;                   /* words d_bitmap holds (kept from load to load: a streamed capture loads batch after batch) */
     bool            bitmap_live = false;              /* d_bitmap describes the arena that is attached now */
@@ -139,7 +154,7 @@ struct kmpgpu_ctx {
 
     /* results */
     unsigned long long *d_partials = nullptr;
-    size_t              partials_cap = 0;             /* elements */
+    uint64_t            partials_cap = 0;             /* elements */
     unsigned long long *d_counts = nullptr;
     uint32_t           *d_err = nullptr;              /* [2] validation flags */
     unsigned long long *d_sum = nullptr;              /* [6] payload bytes, offset 0, stride, length 0, end of last slot */
@@ -189,13 +204,21 @@ bool use_flat(const kmpgpu_ctx *c)
 bool use_fused(const kmpgpu_ctx *c, const kmpgpu_ctx::PatternSet &s)
 {
     if (!c->packed || !c->bitmap_live || c->mode != 0 || c->kernel_sel == 1 || s.fused_groups.empty()) return false;
-    if (c->fused == 1) return s.n_multi_unique >= 2;
-    return c->fused == 2 && s.n_multi_unique >= 2;
+    return c->fused != 0 && s.n_multi_unique >= 2;
 }
 
 bool use_packed(const kmpgpu_ctx *c)
 {
     return c->packed && c->bitmap_live && c->mode == 0 && (c->kernel_sel == 2 || ((c->kernel_sel == 0 || c->kernel_sel == 3) && !use_flat(c)));
+}
+
+/* Packets of a uniform stride after which a range starts on a 128-byte line again: wavefront ranges of a multiple of it share no cache
+ * line with their neighbours.  (Long payloads: a shared line per range is noise, a range of several payloads is not.) */
+uint64_t line_quantum(uint32_t stride)
+{
+    uint64_t g = stride, r = 128;
+    while (r) { const uint64_t t = g % r; g = r; r = t; }                         /* gcd(stride, 128) */
+    return stride >= 4096u ? 1 : 128 / g;
 }
 
 uint32_t grid_blocks(const kmpgpu_ctx *c, const kmpgpu_ctx::PatternSet &s, bool emit = false)
@@ -226,9 +249,7 @@ uint32_t grid_blocks(const kmpgpu_ctx *c, const kmpgpu_ctx::PatternSet &s, bool 
          * whole chip reads one compact, moving window of the arena and nobody waits for a straggler at the end: 209-211 us per
          * 1.5 GB (0.89 of the HBM peak) against 223-234 us with four resident blocks per CU and 366 KB per wavefront
          * (profiles/r02_flat_grid.txt).  Capped so that blocks x patterns stays below 2^22 (partial counts; a launch of 2^30 threads). */
-        uint64_t g = c->uni_stride, r = 128;
-        while (r) { const uint64_t t = g % r; g = r; r = t; }                     /* gcd(stride, 128): ranges start on 128-byte lines */
-        const uint64_t q = c->uni_stride >= 4096u ? 1 : 128 / g;                  /* (long payloads: a shared line per range is noise, a range of several is not) */
+        const uint64_t q = line_quantum(c->uni_stride);                           /* ranges start on 128-byte lines */
         const uint64_t ppw = std::max<uint64_t>(6144 / c->uni_stride / q * q, q);        /* about 6 KiB, a multiple of q packets (1504-byte slots: 4) */
         uint64_t bx = (c->n_pkts + KMP_BLOCK_WAVES * ppw - 1) / (KMP_BLOCK_WAVES * ppw);
         const uint64_t max_bx = std::max<uint64_t>((1ull << 22) / std::max<uint32_t>(c->n_pat, 1u), (uint64_t)c->cu_count * 4u);
@@ -257,6 +278,30 @@ uint32_t grid_blocks(const kmpgpu_ctx *c, const kmpgpu_ctx::PatternSet &s, bool 
     return (uint32_t)std::max<uint64_t>(b, 1);
 }
 
+/* A device buffer of at least `want` elements, kept between calls: taken anew only when it is too small -- a batch that fits the buffer of
+ * the one before costs no hipMalloc and no hipFree (either synchronises the device).  EXACT: what is asked for (a buffer whose size follows
+ * from the arena or the grid); EIGHTH: an eighth more (one that follows the batches of a streamed capture, which vary a little). */
+enum Headroom { EXACT, EIGHTH };
+
+template <typename T>
+hipError_t grow_buffer(T **p, uint64_t *cap, uint64_t want, Headroom headroom)
+{
+    if (*p && *cap >= want) return hipSuccess;
+    if (*p) { const hipError_t e = hipFree(*p); *p = nullptr; *cap = 0; if (e != hipSuccess) return e; }
+    const uint64_t take = headroom == EIGHTH ? want + want / 8 + 1 : want;
+    const hipError_t e = hipMalloc((void **)p, (size_t)take * sizeof(T));
+    if (e == hipSuccess) *cap = take;
+    return e;
+}
+
+template <typename T>
+void free_buffer(T **p, uint64_t *cap = nullptr)
+{
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    if (cap) *cap = 0;
+}
+
 void free_pattern_set(kmpgpu_ctx::PatternSet &s)
 {
     for (kmpgpu_ctx::FusedGroup &g : s.fused_groups)
@@ -264,51 +309,64 @@ void free_pattern_set(kmpgpu_ctx::PatternSet &s)
             if (p) (void)hipFree(p);
     s.fused_groups.clear();
     s.n_multi_unique = 0;
-    if (s.d_ids) (void)hipFree(s.d_ids);
-    if (s.d_rest_ids) (void)hipFree(s.d_rest_ids);
-    s.d_ids = s.d_rest_ids = nullptr;
+    free_buffer(&s.d_ids);
+    free_buffer(&s.d_rest_ids);
     s.n = s.n_long = s.n_short = s.rest_long = s.rest_short = 0;
 }
 
 /* The set a scan reports the grid of (kmpgpu_timing.grid_blocks): the case-sensitive one, or the nocase one when it is alone. */
 const kmpgpu_ctx::PatternSet &primary_set(const kmpgpu_ctx *c) { return c->sets[0].n || !c->sets[1].n ? c->sets[0] : c->sets[1]; }
 
-
-int ensure_partials(kmpgpu_ctx *c, size_t elems)
-{
-    if (elems <= c->partials_cap) return KMPGPU_OK;
-    if (c->d_partials) HIP_TRY(hipFree(c->d_partials));
-    c->d_partials = nullptr; c->partials_cap = 0;
-    HIP_TRY(hipMalloc(&c->d_partials, elems * sizeof(unsigned long long)));
-    c->partials_cap = elems;
-    return KMPGPU_OK;
-}
-
 /* the rules go with the pattern set their indices refer to */
 void drop_rules(kmpgpu_ctx *c)
 {
-    if (c->d_rule_heads) (void)hipFree(c->d_rule_heads);
-    if (c->d_rule_quads) (void)hipFree(c->d_rule_quads);
-    c->d_rule_heads = c->d_rule_quads = nullptr;
+    free_buffer(&c->d_rule_heads);
+    free_buffer(&c->d_rule_quads);
     c->n_rules = 0;
 }
 
 /* so do the windows */
-void drop_windows(kmpgpu_ctx *c)
+void drop_windows(kmpgpu_ctx *c) { free_buffer(&c->d_windows); }
+
+/* the patterns and all that is built on them */
+void release_patterns(kmpgpu_ctx *c)
 {
-    if (c->d_windows) (void)hipFree(c->d_windows);
-    c->d_windows = nullptr;
+    free_buffer(&c->d_patterns);
+    free_buffer(&c->d_counts);
+    free_pattern_set(c->sets[0]);
+    free_pattern_set(c->sets[1]);
+    drop_rules(c);                                 /* their indices meant these patterns */
+    drop_windows(c);                               /* ... and so did the windows' */
+}
+
+/* The context's own arena / offset / length buffers. */
+void free_owned_arena(kmpgpu_ctx *c)
+{
+    free_buffer(&c->owned_arena, &c->cap_arena);
+    free_buffer(&c->owned_off, &c->cap_pkts);
+    free_buffer(&c->owned_len);
+}
+
+bool owned_arena_holds(const kmpgpu_ctx *c, uint64_t bytes, uint64_t n) { return c->owned_arena && c->cap_arena >= bytes && c->cap_pkts >= n; }
+
+/* They hold `bytes` and `n` payloads: kept when they do already (streamed captures load batch after batch), otherwise taken anew, all three,
+ * exactly or with an eighth of headroom.  On failure all three are freed: the context owns nothing and stays usable. */
+hipError_t ensure_owned_arena(kmpgpu_ctx *c, uint64_t bytes, uint64_t n, Headroom headroom)
+{
+    if (owned_arena_holds(c, bytes, n)) return hipSuccess;
+    free_owned_arena(c);
+    const uint64_t take_b = bytes + (headroom == EIGHTH ? bytes / 8 : 0), take_n = n + (headroom == EIGHTH ? n / 8 : 0);
+    hipError_t e = hipMalloc(&c->owned_arena, take_b);
+    if (e == hipSuccess) e = hipMalloc(&c->owned_off, take_n * sizeof(uint64_t));
+    if (e == hipSuccess) e = hipMalloc(&c->owned_len, take_n * sizeof(uint32_t));
+    if (e != hipSuccess) { free_owned_arena(c); return e; }
+    c->cap_arena = take_b; c->cap_pkts = take_n;
+    return hipSuccess;
 }
 
 void release_arena(kmpgpu_ctx *c, bool keep_buffers = false)
 {
-    if (!keep_buffers) {
-        if (c->owned_arena) (void)hipFree(c->owned_arena);
-        if (c->owned_off) (void)hipFree(c->owned_off);
-        if (c->owned_len) (void)hipFree(c->owned_len);
-        c->owned_arena = c->owned_off = c->owned_len = nullptr;
-        c->cap_arena = c->cap_pkts = 0;
-    }
+    if (!keep_buffers) free_owned_arena(c);
     c->d_arena = nullptr; c->d_off = nullptr; c->d_len = nullptr;
     c->arena_bytes = c->n_pkts = c->payload_bytes = 0;
     c->uniform = false; c->packed = false; c->pad_clean = false; c->plan_waves = 0; c->uplan_units = 0;
@@ -350,80 +408,29 @@ hipError_t upload_split(void *dst, const uint8_t *src, uint64_t n, hipStream_t s
     return hipSuccess;
 }
 
-/* a device buffer of at least `want` elements, kept between calls: grown (with an eighth of headroom) only when it is too small */
-template <typename T>
-hipError_t grow_buffer(T **p, uint64_t *cap, uint64_t want)
-{
-    if (*p && *cap >= want) return hipSuccess;
-    if (*p) { const hipError_t e = hipFree(*p); *p = nullptr; *cap = 0; if (e != hipSuccess) return e; }
-    const uint64_t take = want + want / 8 + 1;
-    const hipError_t e = hipMalloc((void **)p, (size_t)take * sizeof(T));
-    if (e == hipSuccess) *cap = take;
-    return e;
-}
-
 void release_frame_scratch(kmpgpu_ctx *c)
 {
-    for (void *p : {(void *)c->fr_file, (void *)c->fr_ws, (void *)c->fr_off, (void *)c->fr_src, (void *)c->fr_cl, (void *)c->fr_tot})
-        if (p) (void)hipFree(p);
-    c->fr_file = c->fr_ws = nullptr; c->fr_off = c->fr_src = nullptr; c->fr_cl = nullptr; c->fr_tot = nullptr;
-    c->fr_file_cap = c->fr_off_cap = c->fr_cl_cap = c->fr_ws_cap = c->fr_src_cap = 0;
+    free_buffer(&c->fr_file, &c->fr_file_cap); free_buffer(&c->fr_ws, &c->fr_ws_cap); free_buffer(&c->fr_off, &c->fr_off_cap);
+    free_buffer(&c->fr_src, &c->fr_src_cap); free_buffer(&c->fr_cl, &c->fr_cl_cap); free_buffer(&c->fr_tot);
 }
 
-int grow_fold(kmpgpu_ctx *c, uint64_t bytes);
-
-/* An arena whose slots are not back to back (gaps, shuffled order) is copied once into a packed one owned
- * by the context, so that the streaming kernels apply to it too (KMPGPU_OPT_REPACK, default on). */
-int repack_arena(kmpgpu_ctx *c)
+/* What the passes keep from one to the next: every buffer that grow_buffer sizes for them (the frame scratch and the owned arena have
+ * their own release above). */
+void release_pass_buffers(kmpgpu_ctx *c)
 {
-    if (c->packed || !c->repack || c->n_pkts == 0) return KMPGPU_OK;
-    uint8_t *ws = nullptr, *na = nullptr;
-    uint64_t *noff = nullptr;
-    uint32_t *nlen = nullptr;
-    unsigned long long *d_tot = nullptr, tot[2] = {0, 0};
-    auto drop = [&]() { if (ws) (void)hipFree(ws); if (d_tot) (void)hipFree(d_tot); };
-#define KMP_TRY3(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { drop(); if (na) (void)hipFree(na); if (noff) (void)hipFree(noff); if (nlen) (void)hipFree(nlen); \
-        return fail(KMPGPU_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } } while (0)
-    KMP_TRY3(hipMalloc(&ws, kmp_extract_ws_bytes(c->n_pkts)));
-    KMP_TRY3(hipMalloc(&d_tot, 2 * sizeof(unsigned long long)));
-    KMP_TRY3(kmp_launch_repack_phase1(c->d_len, c->n_pkts, ws, d_tot, c->stream));
-    KMP_TRY3(hipMemcpyAsync(tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, c->stream));
-    KMP_TRY3(hipStreamSynchronize(c->stream));
-    const uint64_t nbytes = tot[0] + 64;
-    KMP_TRY3(hipMalloc(&na, nbytes));
-    KMP_TRY3(hipMalloc(&noff, c->n_pkts * sizeof(uint64_t)));
-    KMP_TRY3(hipMalloc(&nlen, c->n_pkts * sizeof(uint32_t)));
-    KMP_TRY3(hipMemsetAsync(na + tot[0], 0, 64, c->stream));
-    KMP_TRY3(hipMemcpyAsync(nlen, c->d_len, c->n_pkts * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
-    KMP_TRY3(kmp_launch_repack_phase2(c->d_arena, c->d_off, c->d_len, c->n_pkts, ws, na, noff, c->stream));
-    KMP_TRY3(hipStreamSynchronize(c->stream));
-#undef KMP_TRY3
-    drop();
-    /* the context now owns the packed copy; a borrowed or uploaded original is released */
-    if (c->owned_arena) (void)hipFree(c->owned_arena);
-    if (c->owned_off) (void)hipFree(c->owned_off);
-    if (c->owned_len) (void)hipFree(c->owned_len);
-    c->owned_arena = na; c->owned_off = noff; c->owned_len = nlen;
-    c->cap_arena = nbytes; c->cap_pkts = c->n_pkts;
-    c->d_arena = na; c->d_off = noff; c->d_len = nlen;
-    c->arena_bytes = nbytes;
-    c->packed = true; c->uniform = false;
-    c->uni_off0 = 0; c->span_end = tot[0];
-    c->fold_stale = true;
-    (void)grow_fold(c, nbytes);                   /* (a failure is reported by the first scan that needs the fold) */
-    return KMPGPU_OK;
+    free_buffer(&c->d_bitmap, &c->bitmap_cap); free_buffer(&c->d_plan, &c->plan_cap); free_buffer(&c->d_uplan, &c->uplan_cap);
+    free_buffer(&c->d_pool, &c->pool_cap); free_buffer(&c->d_partials, &c->partials_cap); free_buffer(&c->d_fold, &c->fold_cap);
+    free_buffer(&c->d_marks, &c->marks_cap); free_buffer(&c->d_rule_out, &c->rule_out_cap);
+    c->bitmap_live = false; c->plan_waves = c->uplan_units = 0; c->fold_stale = true;
 }
 
 /* The fold buffer holds at least `bytes` (an arena's size): grown where the other buffers are, only while a pattern needs it. */
 int grow_fold(kmpgpu_ctx *c, uint64_t bytes)
 {
     if (!c->sets[1].n || !bytes) return KMPGPU_OK;
-    const hipError_t e = grow_buffer(&c->d_fold, &c->fold_cap, (bytes + 15u) & ~15ull);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? KMPGPU_ENOMEM : KMPGPU_EHIP, "the fold buffer of the nocase patterns (%llu bytes) could not be allocated: %s",
-                    (unsigned long long)bytes, hipGetErrorString(e));
-    }
+    const uint64_t want = (bytes + 15u) & ~15ull;
+    const hipError_t e = grow_buffer(&c->d_fold, &c->fold_cap, want, EIGHTH);
+    if (e != hipSuccess) return alloc_fail(e, "the fold buffer of the nocase patterns (%llu bytes) could not be allocated", (unsigned long long)bytes);
     return KMPGPU_OK;
 }
 
@@ -451,26 +458,74 @@ int ensure_fold(kmpgpu_ctx *c)
     return KMPGPU_OK;
 }
 
-/* Side tables of the packed streaming kernel: start bitmap now, wavefront plan on first use. */
-int prepare_packed(kmpgpu_ctx *c)
+/* What a loader has found out about an index it has checked against the layout contract: by kmpgpu_load_arena's loop over a host index,
+ * or by kmp_validate_index_kernel over one that lies on the device (validate_index). */
+struct IndexFacts {
+    uint64_t payload_bytes = 0;
+    bool     uniform = false;                         /* every payload has the same length, slots at one stride */
+    uint64_t off0 = 0;                                /* the first payload's offset, the stride and the length of a uniform index */
+    uint32_t stride = 0, len0 = 0;
+    bool     packed = false;                          /* slots back to back */
+    uint64_t span_end = 0;                            /* end of the last slot */
+    uint64_t fold_end = 0;                            /* end of the furthest slot (the last one only when the index is in arena order); 0: not known */
+};
+
+int install_arena(kmpgpu_ctx *c, const uint8_t *arena, const uint64_t *off, const uint32_t *len, uint64_t arena_bytes, uint64_t n_pkts,
+                  const IndexFacts &f, bool wrote_padding);
+
+/* An arena whose slots are not back to back (gaps, shuffled order) is copied once into a packed one owned by the context, so that
+ * the streaming kernels apply to it too: by prepare_packed under KMPGPU_OPT_REPACK (default on), and whatever that option says by
+ * the passes that run on the streaming kernels only. */
+int repack_arena(kmpgpu_ctx *c)
 {
-    int rc = repack_arena(c);
-    if (rc) return rc;
-    if (!c->packed || c->n_pkts == 0) return KMPGPU_OK;
-    const size_t words = (size_t)(c->arena_bytes / KMP_CHUNK) + 32;      /* the group prefetch reads up to 2 * DEPTH + 1 words past the end */
-    if (c->bitmap_cap < words) {
-        if (c->d_bitmap) HIP_TRY(hipFree(c->d_bitmap));
-        c->d_bitmap = nullptr; c->bitmap_cap = 0;
-        HIP_TRY(hipMalloc(&c->d_bitmap, words * sizeof(unsigned long long)));
-        c->bitmap_cap = words;
-    }
+    uint8_t *ws = nullptr, *na = nullptr;
+    uint64_t *noff = nullptr;
+    uint32_t *nlen = nullptr;
+    unsigned long long *d_tot = nullptr, tot[2] = {0, 0};
+    auto drop = [&]() { if (ws) (void)hipFree(ws); if (d_tot) (void)hipFree(d_tot); };
+#define KMP_TRY3(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { drop(); if (na) (void)hipFree(na); if (noff) (void)hipFree(noff); if (nlen) (void)hipFree(nlen); \
+        return fail(KMPGPU_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } } while (0)
+    KMP_TRY3(hipMalloc(&ws, kmp_extract_ws_bytes(c->n_pkts)));
+    KMP_TRY3(hipMalloc(&d_tot, 2 * sizeof(unsigned long long)));
+    KMP_TRY3(kmp_launch_repack_phase1(c->d_len, c->n_pkts, ws, d_tot, c->stream));
+    KMP_TRY3(hipMemcpyAsync(tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, c->stream));
+    KMP_TRY3(hipStreamSynchronize(c->stream));
+    const uint64_t nbytes = tot[0] + 64;
+    KMP_TRY3(hipMalloc(&na, nbytes));
+    KMP_TRY3(hipMalloc(&noff, c->n_pkts * sizeof(uint64_t)));
+    KMP_TRY3(hipMalloc(&nlen, c->n_pkts * sizeof(uint32_t)));
+    KMP_TRY3(hipMemsetAsync(na + tot[0], 0, 64, c->stream));
+    KMP_TRY3(hipMemcpyAsync(nlen, c->d_len, c->n_pkts * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+    KMP_TRY3(kmp_launch_repack_phase2(c->d_arena, c->d_off, c->d_len, c->n_pkts, ws, na, noff, c->stream));
+    KMP_TRY3(hipStreamSynchronize(c->stream));
+#undef KMP_TRY3
+    drop();
+    /* the context now owns the packed copy; a borrowed or uploaded original is released */
+    free_owned_arena(c);
+    c->owned_arena = na; c->owned_off = noff; c->owned_len = nlen;
+    c->cap_arena = nbytes; c->cap_pkts = c->n_pkts;
+    IndexFacts f;
+    f.payload_bytes = c->payload_bytes;
+    f.packed = true;
+    f.span_end = f.fold_end = tot[0];
+    return install_arena(c, na, noff, nlen, nbytes, c->n_pkts, f, /* wrote_padding = */ false);
+}
+
+/* Side tables of the packed streaming kernel: start bitmap now, wavefront plan on first use.  wrote_padding: the loader wrote the
+ * slot padding of the context's own arena itself, no check pass. */
+int prepare_packed(kmpgpu_ctx *c, bool wrote_padding)
+{
+    if (c->n_pkts == 0) return KMPGPU_OK;
+    if (!c->packed) return c->repack ? repack_arena(c) : KMPGPU_OK;          /* (which installs its packed copy and so comes back here) */
+    const uint64_t words = c->arena_bytes / KMP_CHUNK + 32;              /* the group prefetch reads up to 2 * DEPTH + 1 words past the end */
+    HIP_TRY(grow_buffer(&c->d_bitmap, &c->bitmap_cap, words, EXACT));
     HIP_TRY(hipMemsetAsync(c->d_bitmap, 0, words * sizeof(unsigned long long), c->stream));
     HIP_TRY(kmp_launch_build_bitmap(c->d_off, c->n_pkts, c->d_bitmap, c->stream));
     c->bitmap_live = true;
     /* slot padding: checked once; cleared when the arena is the context's own copy, otherwise the packed
      * kernel keeps fetching offset and length of a candidate's payload from the index */
-    const bool own = c->owned_arena && c->d_arena == (const uint8_t *)c->owned_arena;
-    if (own && c->pad_known_clean) { c->pad_clean = true; return KMPGPU_OK; }
+    const bool own = c->owned_arena && c->d_arena == c->owned_arena;
+    if (own && wrote_padding) { c->pad_clean = true; return KMPGPU_OK; }
     uint32_t dirty = 0;
     HIP_TRY(hipMemsetAsync(c->d_err, 0, sizeof(uint32_t), c->stream));
     HIP_TRY(kmp_launch_check_padding(const_cast<uint8_t *>(c->d_arena), c->d_off, c->d_len, c->n_pkts, own ? 1 : 0, c->d_err, c->stream));
@@ -479,6 +534,62 @@ int prepare_packed(kmpgpu_ctx *c)
     memcpy(&dirty, c->h_small, sizeof dirty);
     c->pad_clean = own || dirty == 0;
     return KMPGPU_OK;
+}
+
+/* The one place an arena becomes the context's: the pointers (its own buffers or borrowed ones), what is known about the index, the fold
+ * buffer, and the packed kernels' side tables. */
+int install_arena(kmpgpu_ctx *c, const uint8_t *arena, const uint64_t *off, const uint32_t *len, uint64_t arena_bytes, uint64_t n_pkts,
+                  const IndexFacts &f, bool wrote_padding)
+{
+    c->d_arena = arena; c->d_off = off; c->d_len = len;
+    c->arena_bytes = arena_bytes; c->n_pkts = n_pkts; c->payload_bytes = f.payload_bytes;
+    c->uniform = f.uniform; c->uni_off0 = f.off0; c->uni_stride = f.stride; c->uni_len = f.len0;
+    c->packed = f.packed;
+    c->span_end = f.span_end;
+    c->fold_stale = true; c->fold_end = f.fold_end;
+    (void)grow_fold(c, arena_bytes);                  /* (a failure is reported by the first scan that needs the fold) */
+    return prepare_packed(c, wrote_padding);
+}
+
+/* The layout contract, uniform / packed detection and the payload sum of an index that lies on the device (kmp_validate_index_kernel),
+ * read back through the pinned words (a copy to pageable memory goes through the runtime's blocking staging path). */
+int validate_index(kmpgpu_ctx *c, const char *who, const uint64_t *d_off, const uint32_t *d_len, uint64_t n_pkts, uint64_t arena_bytes, IndexFacts *f)
+{
+    HIP_TRY(hipMemsetAsync(c->d_err, 0, 2 * sizeof(uint32_t), c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_sum, 0, 6 * sizeof(unsigned long long), c->stream));
+    HIP_TRY(kmp_launch_validate(d_off, d_len, n_pkts, arena_bytes, c->d_err, c->d_sum, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_small, c->d_sum, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_small + 8, c->d_err, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const unsigned long long *info = c->h_small;
+    uint32_t err[2];
+    memcpy(err, c->h_small + 8, sizeof err);
+    if (err[0] & 1u) return fail(KMPGPU_EINVAL, "%s: a payload offset is not 16-byte aligned", who);
+    if (err[0] & 2u) return fail(KMPGPU_EINVAL, "%s: a payload (padded to 16 B) exceeds the arena", who);
+    if (err[0] & 4u) return fail(KMPGPU_EINVAL, "%s: a payload length is not below 2^30", who);
+    *f = IndexFacts{};
+    f->payload_bytes = info[0];
+    f->uniform = ((err[1] & 1u) == 0) && info[2] >= 16 && info[2] < (1ull << 31);
+    f->off0 = info[1]; f->stride = (uint32_t)info[2]; f->len0 = (uint32_t)info[3];
+    f->packed = (err[1] & 2u) == 0;
+    f->span_end = info[4];
+    return KMPGPU_OK;
+}
+
+/* A launch that kmpgpu_profile_begin .. _end times: the next event pair, its first event recorded in front of the launch and its second
+ * one (*e1; NULL while no profile runs or it is full) behind it. */
+hipError_t profile_launch(kmpgpu_ctx *c, hipEvent_t *e1)
+{
+    *e1 = nullptr;
+    if (!c->profiling || c->prof_n >= c->prof_cap) return hipSuccess;
+    *e1 = c->prof_ev[2 * c->prof_n + 1];
+    return hipEventRecord(c->prof_ev[2 * c->prof_n], c->stream);
+}
+hipError_t profile_launched(kmpgpu_ctx *c, hipEvent_t e1)
+{
+    if (!e1) return hipSuccess;
+    c->prof_n++;
+    return hipEventRecord(e1, c->stream);
 }
 
 /* Enqueue one full pass: scan launches (patterns grouped by "shorter than 4 bytes") + reduce. */
@@ -500,10 +611,64 @@ size_t part_rows(const kmpgpu_ctx *c, const kmpgpu_ctx::PatternSet &s)
     return rows;
 }
 
+/* The work units of the fused pass over `span` bytes on a grid of bx 4-wavefront blocks, run as blocks of `bwaves` wavefronts. */
+struct FusedPlan {
+    kmp_plan_shape shape;              /* region, step, units per region, big units, pool unit: what kmp_plan_kernel cuts */
+    uint64_t fblocks = 0;              /* blocks of the launch; fblocks / sides regions */
+    uint32_t sides = 1;                /* blocks that share a region */
+    uint64_t n_units = 0;              /* regions x shape.units */
+};
+
+/* The fused pass: one region of the arena per PAIR of blocks, in work units their wavefronts take one after the other
+ * (kmp_scan_multi.hip).  Every wavefront starts with one large unit of its own, and the second half of the region
+ * lies in a pool of 32 KiB units for whoever is done first (profiles/r03_fused_units_sweep4_pair_pools.txt): the SIMDs serve their wavefronts in order of age, so the
+ * first wavefront of a block is through its share when the last one has a third to go, and the block that came to a CU first
+ * is done when the second one has a third to go.  (Small units throughout cost more than they balance: a unit begins
+ * with the dependent chain counter - entry - first loads, which the other wavefronts of the SIMD do not cover --
+ * profiles/r03_tried_all_units_dynamic.txt.)
+ * false: the plan does not fit 32 bits (positions inside a region and unit numbers are 32-bit, kmp_scan_multi.hip); the set then keeps its
+ * streaming passes. */
+bool plan_fused(uint64_t span, uint32_t bx, uint32_t bwaves, int fused_unit, FusedPlan *p)
+{
+    uint64_t fblocks = ((uint64_t)bx * KMP_BLOCK_WAVES + bwaves - 1u) / bwaves;
+    const uint32_t sides = fblocks >= 2 ? 2u : 1u;
+    fblocks -= fblocks % sides;
+    const uint64_t regions = fblocks / sides;
+    kmp_plan_shape sh{};
+    sh.region = (((span + regions - 1) / regions) + 1023ull) & ~1023ull;
+    uint64_t small = fused_unit ? (uint64_t)fused_unit : 32768ull, pool_num = 1, pool_div = 2, big = 0;
+#ifdef KMP_MULTI_TUNING
+    if (const char *e = getenv("KMP_FUSED_UNIT")) big = strtoull(e, nullptr, 0) & ~1023ull;          /* 0: from the pool's share */
+    if (const char *e = getenv("KMP_FUSED_SMALL")) small = std::max<uint64_t>(1024ull, strtoull(e, nullptr, 0) & ~1023ull);
+    if (const char *e = getenv("KMP_FUSED_TAIL_DIV")) { pool_num = 1; pool_div = std::max<uint64_t>(1ull, strtoull(e, nullptr, 0)); }
+    if (const char *e = getenv("KMP_FUSED_TAIL_NUM")) pool_num = std::min<uint64_t>(pool_div, strtoull(e, nullptr, 0));
+#endif
+    uint64_t big_units = (uint64_t)sides * bwaves;
+    /* (a small region -- a capture of a few hundred KB per block -- goes to the wavefronts whole: a unit of the pool costs a round trip
+     * to the counter in global memory, which a pass of 10 us does not have) */
+    const bool no_pool = sh.region < (1ull << 20) && !big;
+    const uint64_t own_bytes = no_pool ? sh.region : sh.region - sh.region / pool_div * pool_num;
+    sh.step = big ? big : std::max<uint64_t>(1024ull, no_pool ? ((own_bytes + big_units - 1) / big_units + 1023ull) & ~1023ull : (own_bytes / big_units) & ~1023ull);
+    if (!no_pool && big_units * sh.step > sh.region) big_units = sh.region / sh.step;
+    uint64_t rest = no_pool ? 0ull : sh.region - big_units * sh.step;         /* (without a pool the shares reach the region's end: kmp_plan_kernel cuts them there) */
+    /* (a small region: at least two units of the pool per wavefront, or the last unit is all that is left to do for a long time) */
+    if (!fused_unit) small = std::min<uint64_t>(small, std::max<uint64_t>(1024ull, (rest / (2ull * big_units ? 2ull * big_units : 1ull)) & ~1023ull));
+    /* a block holds the entries of its units in LDS, KMP_MULTI_MAX_UNITS of them: a large region has larger pool units */
+    const uint64_t room = KMP_MULTI_MAX_UNITS - 1u - big_units;                  /* (one entry stays free: "no such unit") */
+    if ((rest + small - 1) / small > room) small = (((rest + room - 1) / room) + 1023ull) & ~1023ull;
+    sh.small = (uint32_t)small;
+    const uint64_t upb = big_units + (rest + small - 1) / small;
+    const uint64_t n_units = regions * upb;
+    if (!(sh.region < 0x7FE00000ull && n_units < (1ull << 31))) return false;
+    sh.big_units = (uint32_t)big_units; sh.units = (uint32_t)upb;
+    p->shape = sh; p->fblocks = fblocks; p->sides = sides; p->n_units = n_units;
+    return true;
+}
+
 /* The launches of one set over `arena` (d_arena, or the folded copy for the nocase set): scan launches (patterns grouped by "shorter
  * than 4 bytes") + reduce, into d_out by pattern index. */
 int enqueue_set(kmpgpu_ctx *c, const kmpgpu_ctx::PatternSet &s, const uint8_t *arena, uint32_t bx, uint32_t &nl, unsigned long long *d_out,
-                const EmitTarget *emit)
+                bool accumulate, const EmitTarget *emit)
 {
     kmp_scan_args a{};
     a.arena = arena; a.pkt_off = c->d_off; a.pkt_len = c->d_len; a.n_pkts = c->n_pkts;
@@ -521,9 +686,7 @@ int enqueue_set(kmpgpu_ctx *c, const kmpgpu_ctx::PatternSet &s, const uint8_t *a
     uint64_t ppw = (c->n_pkts + nwaves - 1) / nwaves;
     if (c->uniform && c->uni_stride) {
         /* start every wavefront's range on a 128-byte line so that neighbouring ranges share no cache line */
-        uint64_t g = c->uni_stride, r = 128;
-        while (r) { const uint64_t t = g % r; g = r; r = t; }      /* gcd(stride, 128) */
-        const uint64_t q = c->uni_stride >= 4096u ? 1 : 128 / g;
+        const uint64_t q = line_quantum(c->uni_stride);
         ppw = (ppw + q - 1) / q * q;
     }
     const bool flat = use_flat(c) && ppw * c->uni_stride < (1ull << 31);
@@ -537,65 +700,19 @@ int enqueue_set(kmpgpu_ctx *c, const kmpgpu_ctx::PatternSet &s, const uint8_t *a
     bool packed = !flat && use_packed(c);
     bool do_fused = false;
     if (fused) {
-        /* The fused pass: one region of the arena per PAIR of blocks, in work units their wavefronts take one after the other
-         * (kmp_scan_multi.hip).  Every wavefront starts with one large unit of its own, and the second half of the region
-         * lies in a pool of 32 KiB units for whoever is done first (profiles/r03_fused_units_sweep4_pair_pools.txt): the SIMDs serve their wavefronts in order of age, so the
-         * first wavefront of a block is through its share when the last one has a third to go, and the block that came to a CU first
-         * is done when the second one has a third to go.  (Small units throughout cost more than they balance: a unit begins
-         * with the dependent chain counter - entry - first loads, which the other wavefronts of the SIMD do not cover --
-         * profiles/r03_tried_all_units_dynamic.txt.) */
-        const uint32_t bwaves = kmp_multi_block_waves(kmp_multi_kind(emit != nullptr, c->pad_clean, s.fused_groups.front().n_ones));
-        uint64_t fblocks = ((uint64_t)bx * KMP_BLOCK_WAVES + bwaves - 1u) / bwaves;
-        const uint32_t sides = fblocks >= 2 ? 2u : 1u;
-        fblocks -= fblocks % sides;
-        const uint64_t regions = fblocks / sides;
-        const uint64_t span = c->span_end - c->uni_off0;
-        kmp_plan_shape sh{};
-        sh.region = (((span + regions - 1) / regions) + 1023ull) & ~1023ull;
-        uint64_t small = c->fused_unit ? (uint64_t)c->fused_unit : 32768ull, pool_num = 1, pool_div = 2, big = 0;
-#ifdef KMP_MULTI_TUNING
-        if (const char *e = getenv("KMP_FUSED_UNIT")) big = strtoull(e, nullptr, 0) & ~1023ull;          /* 0: from the pool's share */
-        if (const char *e = getenv("KMP_FUSED_SMALL")) small = std::max<uint64_t>(1024ull, strtoull(e, nullptr, 0) & ~1023ull);
-        if (const char *e = getenv("KMP_FUSED_TAIL_DIV")) { pool_num = 1; pool_div = std::max<uint64_t>(1ull, strtoull(e, nullptr, 0)); }
-        if (const char *e = getenv("KMP_FUSED_TAIL_NUM")) pool_num = std::min<uint64_t>(pool_div, strtoull(e, nullptr, 0));
-#endif
-        uint64_t big_units = (uint64_t)sides * bwaves;
-        /* (a small region -- a capture of a few hundred KB per block -- goes to the wavefronts whole: a unit of the pool costs a round trip
-         * to the counter in global memory, which a pass of 10 us does not have) */
-        const bool no_pool = sh.region < (1ull << 20) && !big;
-        const uint64_t own_bytes = no_pool ? sh.region : sh.region - sh.region / pool_div * pool_num;
-        sh.step = big ? big : std::max<uint64_t>(1024ull, no_pool ? ((own_bytes + big_units - 1) / big_units + 1023ull) & ~1023ull : (own_bytes / big_units) & ~1023ull);
-        if (!no_pool && big_units * sh.step > sh.region) big_units = sh.region / sh.step;
-        uint64_t rest = no_pool ? 0ull : sh.region - big_units * sh.step;         /* (without a pool the shares reach the region's end: kmp_plan_kernel cuts them there) */
-        /* (a small region: at least two units of the pool per wavefront, or the last unit is all that is left to do for a long time) */
-        if (!c->fused_unit) small = std::min<uint64_t>(small, std::max<uint64_t>(1024ull, (rest / (2ull * big_units ? 2ull * big_units : 1ull)) & ~1023ull));
-        /* a block holds the entries of its units in LDS, KMP_MULTI_MAX_UNITS of them: a large region has larger pool units */
-        const uint64_t room = KMP_MULTI_MAX_UNITS - 1u - big_units;                  /* (one entry stays free: "no such unit") */
-        if ((rest + small - 1) / small > room) small = (((rest + room - 1) / room) + 1023ull) & ~1023ull;
-        sh.small = (uint32_t)small;
-        const uint64_t upb = big_units + (rest + small - 1) / small;
-        const uint64_t n_units = regions * upb;
-        if (sh.region < 0x7FE00000ull && n_units < (1ull << 31)) {                   /* (positions inside a region are 32-bit, kmp_scan_multi.hip) */
-            sh.big_units = (uint32_t)big_units; sh.units = (uint32_t)upb;
-            const kmp_plan_shape &o = c->uplan_shape;
-            if (c->uplan_units != n_units || o.step != sh.step || o.region != sh.region || o.units != sh.units || o.big_units != sh.big_units || o.small != sh.small) {
-                if (c->uplan_cap < n_units + 1) {
-                    if (c->d_uplan) HIP_TRY(hipFree(c->d_uplan));
-                    c->d_uplan = nullptr; c->uplan_cap = 0;
-                    HIP_TRY(hipMalloc(&c->d_uplan, (n_units + 1) * 16));
-                    c->uplan_cap = n_units + 1;
-                }
-                HIP_TRY(kmp_launch_plan(c->d_off, c->d_len, c->n_pkts, n_units, sh, c->d_uplan, c->stream));
-                c->uplan_units = n_units; c->uplan_shape = sh;
+        /* its work units (plan_fused), cut at packet starts once per shape (kmp_plan_kernel), and a pool counter per region */
+        const uint32_t bwaves =kmp_multi_block_waves(kmp_multi_kind(emit != nullptr, c->pad_clean, s.fused_groups.front().n_ones));
+        FusedPlan fp;
+        if (plan_fused(c->span_end - c->uni_off0, bx, bwaves, c->fused_unit, &fp)) {
+            const kmp_plan_shape &sh = fp.shape, &o = c->uplan_shape;
+            if (c->uplan_units != fp.n_units || o.step != sh.step || o.region != sh.region || o.units != sh.units || o.big_units != sh.big_units || o.small != sh.small) {
+                HIP_TRY(grow_buffer(&c->d_uplan, &c->uplan_cap, fp.n_units + 1, EXACT));
+                HIP_TRY(kmp_launch_plan(c->d_off, c->d_len, c->n_pkts, fp.n_units, sh, c->d_uplan, c->stream));
+                c->uplan_units = fp.n_units; c->uplan_shape = sh;
             }
-            if (c->pool_cap < regions) {
-                if (c->d_pool) HIP_TRY(hipFree(c->d_pool));
-                c->d_pool = nullptr; c->pool_cap = 0;
-                HIP_TRY(hipMalloc(&c->d_pool, regions * sizeof(uint32_t)));
-                c->pool_cap = regions;
-            }
-            a.fused_blocks = (uint32_t)fblocks; a.units_per_block = (uint32_t)upb; a.n_units = (uint32_t)n_units; a.span_end = c->span_end;
-            a.fused_sides = sides; a.fused_pool = c->d_pool;
+            HIP_TRY(grow_buffer(&c->d_pool, &c->pool_cap, fp.fblocks / fp.sides, EXACT));       /* a counter per region */
+            a.fused_blocks = (uint32_t)fp.fblocks; a.units_per_block = sh.units; a.n_units = (uint32_t)fp.n_units; a.span_end = c->span_end;
+            a.fused_sides = fp.sides; a.fused_pool = c->d_pool;
             a.bitmap = c->d_bitmap;
             do_fused = true;
         }
@@ -609,12 +726,7 @@ int enqueue_set(kmpgpu_ctx *c, const kmpgpu_ctx::PatternSet &s, const uint8_t *a
         if (bpw >= (1ull << 30)) packed = false;
         else {
             if (c->plan_waves != nwaves) {
-                if (c->plan_cap < nwaves + 1) {
-                    if (c->d_plan) HIP_TRY(hipFree(c->d_plan));
-                    c->d_plan = nullptr; c->plan_cap = 0;
-                    HIP_TRY(hipMalloc(&c->d_plan, (nwaves + 1) * 16));
-                    c->plan_cap = nwaves + 1;
-                }
+                HIP_TRY(grow_buffer(&c->d_plan, &c->plan_cap, nwaves + 1, EXACT));
                 kmp_plan_shape sh{};
                 sh.step = bpw ? bpw : 16;
                 HIP_TRY(kmp_launch_plan(c->d_off, c->d_len, c->n_pkts, nwaves, sh, c->d_plan, c->stream));
@@ -623,15 +735,6 @@ int enqueue_set(kmpgpu_ctx *c, const kmpgpu_ctx::PatternSet &s, const uint8_t *a
             a.bitmap = c->d_bitmap; a.plan = c->d_plan;
         }
     }
-
-    auto record = [&](hipEvent_t &e0, hipEvent_t &e1) -> hipError_t {
-        e0 = e1 = nullptr;
-        if (c->profiling && c->prof_n < c->prof_cap) {
-            e0 = c->prof_ev[2 * c->prof_n]; e1 = c->prof_ev[2 * c->prof_n + 1];
-            return hipEventRecord(e0, c->stream);
-        }
-        return hipSuccess;
-    };
 
     const uint32_t *ids = s.d_ids;
     uint32_t n_long = s.n_long, n_short = s.n_short;
@@ -652,11 +755,11 @@ int enqueue_set(kmpgpu_ctx *c, const kmpgpu_ctx::PatternSet &s, const uint8_t *a
                 HIP_TRY(hipMemsetAsync(c->d_pool, 0, (size_t)(a.fused_blocks / a.fused_sides) * sizeof(uint32_t), c->stream));
                 f.fused_pool = c->d_pool;
             }
-            hipEvent_t e0, e1;
-            HIP_TRY(record(e0, e1));
+            hipEvent_t e1;
+            HIP_TRY(profile_launch(c, &e1));
             HIP_TRY(kmp_launch_scan_multi(f, g.d_tables, g.words, g.n_unique, g.cshift, g.bmask, g.n_ones, g.ones, g.d_uid_first, g.d_uid_ids, c->stream));
-            if (e0) { HIP_TRY(hipEventRecord(e1, c->stream)); c->prof_n++; }
-            HIP_TRY(kmp_launch_reduce(c->d_partials, bx, g.d_ids, g.n_ids, d_out, c->stream, g.d_rows, c->accumulate));
+            HIP_TRY(profile_launched(c, e1));
+            HIP_TRY(kmp_launch_reduce(c->d_partials, bx, g.d_ids, g.n_ids, d_out, c->stream, g.d_rows, accumulate));
             ++nl;
             max_u = std::max(max_u, g.n_unique);
         }
@@ -675,30 +778,31 @@ int enqueue_set(kmpgpu_ctx *c, const kmpgpu_ctx::PatternSet &s, const uint8_t *a
             a.masked = g.masked;
             /* tens of thousands of partials per pattern are added up by several blocks, which add to the counter: it starts from 0 */
             const bool sliced = (flat || packed) && kmp_reduce_is_sliced(bx);
-            a.zero_counts = (sliced && !c->accumulate) ? d_out : nullptr;
-            hipEvent_t e0, e1;
-            HIP_TRY(record(e0, e1));
+            a.zero_counts = (sliced && !accumulate) ? d_out : nullptr;
+            hipEvent_t e1;
+            HIP_TRY(profile_launch(c, &e1));
             if (emit && !flat && !packed)
                 return fail(KMPGPU_EINVAL, "%s: the arena could not be brought into the streaming kernels' layout",
                             emit->marks ? "kmpgpu_scan_packets" : "kmpgpu_scan_offsets");
             HIP_TRY(flat ? kmp_launch_scan_flat(a, c->stream) : packed ? kmp_launch_scan_packed(a, c->stream) : kmp_launch_scan(a, c->stream));
-            if (e0) { HIP_TRY(hipEventRecord(e1, c->stream)); c->prof_n++; }
-            HIP_TRY(kmp_launch_reduce(a.partials, bx, a.pat_ids, n, d_out, c->stream, nullptr, c->accumulate, sliced));
+            HIP_TRY(profile_launched(c, e1));
+            HIP_TRY(kmp_launch_reduce(a.partials, bx, a.pat_ids, n, d_out, c->stream, nullptr, accumulate, sliced));
             ++nl;
         }
     }
     return KMPGPU_OK;
 }
 
-/* Enqueue one full pass: the case-sensitive set over the arena, then the nocase set over its folded copy. */
-int enqueue_pass(kmpgpu_ctx *c, uint32_t *launches, unsigned long long *d_out, const EmitTarget *emit = nullptr)
+/* Enqueue one full pass: the case-sensitive set over the arena, then the nocase set over its folded copy.  accumulate: the counts are
+ * added to d_out (KMPGPU_OPT_ACCUMULATE for the counting passes; a pass that emits writes to a buffer of its own and never accumulates). */
+int enqueue_pass(kmpgpu_ctx *c, uint32_t *launches, unsigned long long *d_out, bool accumulate, const EmitTarget *emit = nullptr)
 {
     if (!d_out) d_out = c->d_counts;
     if (!c->d_patterns || c->n_pat == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan: no patterns set");
     if (!c->d_off && c->n_pkts) return fail(KMPGPU_ESTATE, "kmpgpu_scan: no arena loaded");
     uint32_t nl = 0;
     if (c->n_pkts == 0) {
-        if (!c->accumulate) HIP_TRY(hipMemsetAsync(d_out, 0, sizeof(unsigned long long) * c->n_pat, c->stream));
+        if (!accumulate) HIP_TRY(hipMemsetAsync(d_out, 0, sizeof(unsigned long long) * c->n_pat, c->stream));
         if (launches) *launches = 0;
         return KMPGPU_OK;
     }
@@ -714,237 +818,47 @@ int enqueue_pass(kmpgpu_ctx *c, uint32_t *launches, unsigned long long *d_out, c
             bx[k] = grid_blocks(c, c->sets[k], emit != nullptr);
             elems = std::max(elems, (size_t)bx[k] * part_rows(c, c->sets[k]));
         }
-    rc = ensure_partials(c, elems);
-    if (rc) return rc;
+    HIP_TRY(grow_buffer(&c->d_partials, &c->partials_cap, elems, EXACT));
     for (int k = 0; k < 2; k++)
-        if (c->sets[k].n && (rc = enqueue_set(c, c->sets[k], k ? c->d_fold : c->d_arena, bx[k], nl, d_out, emit))) return rc;
+        if (c->sets[k].n && (rc = enqueue_set(c, c->sets[k], k ? c->d_fold : c->d_arena, bx[k], nl, d_out, accumulate, emit))) return rc;
     if (launches) *launches = nl;
     return KMPGPU_OK;
 }
 
-/* The passes of one set (kmpgpu_ctx::PatternSet) over the patterns `members` (indices into host, file order): the long / short split
- * of the streaming passes and the tables of the fused pass, built on the bytes as stored (folded for the nocase set, so that
- * "HOST" and "Host" share a row). */
-int build_set(kmpgpu_ctx *c, kmpgpu_ctx::PatternSet &s, const std::vector<kmp_pattern_dev> &host, const std::vector<uint32_t> &members)
+hipError_t upload_words(uint32_t **d, const std::vector<uint32_t> &v)
 {
-    (void)c;
-    s.n = (uint32_t)members.size();
-    if (!s.n) return KMPGPU_OK;
-    std::vector<uint32_t> ids;
-    for (const uint32_t i : members) if (host[i].m >= 4) ids.push_back(i);
-    s.n_long = (uint32_t)ids.size();
-    for (const uint32_t i : members) if (host[i].m < 4) ids.push_back(i);
-    s.n_short = s.n - s.n_long;
-    HIP_TRY(hipMalloc(&s.d_ids, ids.size() * sizeof(uint32_t)));
-    HIP_TRY(hipMemcpy(s.d_ids, ids.data(), ids.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-
-    /* ---- tables of the fused multi-pattern pass (layout: kmp_device.h) ------------------------- */
-    /* a group: its distinct patterns, the row (unique-pattern id of the kernel) of each, the patterns counted by it and their rows.
-     * `classed`: more than 256 rows -- an entry has eight bits for an id, the kernel adds the first id of the bucket's class
-     * (= bucket >> 7: eight classes of up to 256 patterns each, 1024 in all; kmp_device.h) */
-    constexpr uint32_t NCLS = KMP_MULTI_CLS_WORDS;
-    struct HostGroup { std::vector<std::string> uniq; std::vector<uint32_t> gidx, row; std::vector<uint32_t> ids, rows; bool classed = false;
-                       uint32_t n_cls[NCLS] = {}, overflow = 0; std::vector<uint8_t> bucket_used; };
-    std::vector<HostGroup> hg;
-    std::vector<uint32_t> rest_l, rest_s;
-    /* 1-byte patterns: up to KMP_MULTI_MAX_ONES distinct ones ride along with the first fused group (counted straight
-     * off the text registers, no filter, no queue); further ones keep one streaming pass each */
-    std::vector<uint8_t> one_bytes;
-    std::vector<std::pair<uint32_t, uint32_t>> one_ids;            /* (pattern index, slot) */
-    std::vector<std::string> uniq_all;                             /* the distinct eligible patterns, file order */
-    std::vector<uint32_t> first_pat;                               /* ... and the first pattern of the list that is each of them */
-    std::unordered_map<std::string, uint32_t> uniq_of;
-    std::vector<std::pair<uint32_t, uint32_t>> elig;               /* (pattern index, its distinct pattern) */
-    for (const uint32_t i : members) {
-        const uint8_t *const pi = host[i].pat;
-        const uint32_t m = host[i].m;
-        if (m == 1) {
-            size_t k = 0;
-            while (k < one_bytes.size() && one_bytes[k] != pi[0]) k++;
-            if (k == one_bytes.size() && k < KMP_MULTI_MAX_ONES) one_bytes.push_back(pi[0]);
-            if (k < one_bytes.size()) { one_ids.emplace_back(i, (uint32_t)k); continue; }
-        }
-        if (m < KMP_MULTI_MIN_LEN || m > KMP_MULTI_MAX_LEN) { (m >= 4 ? rest_l : rest_s).push_back(i); continue; }
-        const std::string key((const char *)pi, m);
-        auto it = uniq_of.find(key);
-        if (it == uniq_of.end()) {
-            /* (a record names the pattern whose bytes 8 .. m-1 the kernel compares against in 16 bits: a pattern of nine bytes or
-             * more that first occurs behind the 65 536th of the list keeps a pass of its own) */
-            if (m > 8 && i > 0xFFFFu) { rest_l.push_back(i); continue; }
-            it = uniq_of.emplace(key, (uint32_t)uniq_all.size()).first; uniq_all.push_back(key); first_pat.push_back(i);
-        }
-        elig.emplace_back(i, it->second);
-    }
-    if (uniq_all.size() < 2) {                    /* nothing to fuse: every pattern keeps its own pass (s.d_ids) */
-        return KMPGPU_OK;
-    }
-    /* Which group a distinct pattern goes to.  Up to 256 of them: one group, rows in file order (short ones first, below).  More: the
-     * 2-byte patterns (entered under every third byte: 32 buckets each, in all classes) and, if 1-byte patterns ride along, the first
-     * patterns of the file fill plain groups of 256; everything else goes to classed groups of up to 1024 -- first fit, a pattern
-     * whose class is full (256) or whose bucket would overflow the entry list waits for the next group. */
-    std::vector<std::pair<uint32_t, uint32_t>> place(uniq_all.size());        /* distinct pattern -> (group, index in its uniq) */
-    auto key_class = [](const std::string &p) {
-        const uint32_t w24 = (uint8_t)p[0] | ((uint32_t)(uint8_t)p[1] << 8) | ((uint32_t)(uint8_t)p[2] << 16);
-        return KMP_MULTI_HASH(w24 & KMP_MULTI_KEYMASK);
-    };
-    {
-        const bool big = uniq_all.size() > KMP_MULTI_MAX_UNIQUE;
-        std::vector<uint32_t> plain, classed;
-        for (uint32_t u = 0; u < uniq_all.size(); u++) (!big || uniq_all[u].size() == 2 ? plain : classed).push_back(u);
-        if (big && plain.empty() && !one_bytes.empty()) {                     /* the 1-byte patterns need a plain first group */
-            const size_t take = std::min<size_t>(classed.size(), KMP_MULTI_MAX_UNIQUE);
-            plain.assign(classed.begin(), classed.begin() + take);
-            classed.erase(classed.begin(), classed.begin() + take);
-        }
-        for (uint32_t u : plain) {
-            if (hg.empty() || hg.back().uniq.size() == KMP_MULTI_MAX_UNIQUE) hg.emplace_back();
-            place[u] = {(uint32_t)hg.size() - 1u, (uint32_t)hg.back().uniq.size()};
-            hg.back().uniq.push_back(uniq_all[u]); hg.back().gidx.push_back(u);
-        }
-        const size_t first_classed = hg.size();
-        for (uint32_t u : classed) {
-            const std::string &p = uniq_all[u];
-            const uint32_t b = key_class(p), cl = b >> KMP_MULTI_CLS_SHIFT;
-            size_t gi = first_classed;
-            for (; gi < hg.size(); gi++) {
-                HostGroup &h = hg[gi];
-                if (h.uniq.size() < 4u * KMP_MULTI_MAX_UNIQUE && h.n_cls[cl] < 256u && h.overflow + (h.bucket_used[b] ? 1u : 0u) <= KMP_MULTI_MAX_ENTRIES) break;
-            }
-            if (gi == hg.size()) { hg.emplace_back(); hg.back().classed = true; hg.back().bucket_used.assign(KMP_MULTI_BUCKETS, 0); }
-            HostGroup &h = hg[gi];
-            h.n_cls[cl]++;
-            if (h.bucket_used[b]) h.overflow++; else h.bucket_used[b] = 1;
-            place[u] = {(uint32_t)gi, (uint32_t)h.uniq.size()};
-            h.uniq.push_back(p); h.gidx.push_back(u);
-        }
-    }
-    bool first_group = true;
-    for (HostGroup &h : hg) {
-        const uint32_t U = (uint32_t)h.uniq.size();
-        const uint32_t n_ones = first_group ? (uint32_t)one_bytes.size() : 0u;
-        uint32_t ones = 0;
-        for (uint32_t k = 0; k < n_ones; k++) ones |= (uint32_t)one_bytes[k] << (8 * k);
-        first_group = false;
-        /* rows: class by class, short patterns (2 or 3 bytes: decided by their bucket entry alone) first in each (a plain group is one class) */
-        uint32_t cls_short[NCLS] = {}, cls_n[NCLS] = {}, rec_base[NCLS] = {}, row_base[NCLS] = {};
-        std::vector<uint32_t> cls_of(U, 0u), in_cls(U, 0u);
-        h.row.assign(U, 0u);
-        for (uint32_t u = 0; u < U; u++) {
-            cls_of[u] = h.classed ? key_class(h.uniq[u]) >> KMP_MULTI_CLS_SHIFT : 0u;
-            cls_n[cls_of[u]]++;
-            if (h.uniq[u].size() <= KMP_MULTI_SHORT_LEN) cls_short[cls_of[u]]++;
-        }
-        for (uint32_t cl = 1; cl < NCLS; cl++) {
-            row_base[cl] = row_base[cl - 1] + cls_n[cl - 1];
-            rec_base[cl] = rec_base[cl - 1] + (cls_n[cl - 1] - cls_short[cl - 1]);
-        }
-        {
-            uint32_t next_short[NCLS] = {}, next_long[NCLS];
-            for (uint32_t cl = 0; cl < NCLS; cl++) next_long[cl] = cls_short[cl];
-            for (uint32_t u = 0; u < U; u++) {
-                const uint32_t cl = cls_of[u];
-                in_cls[u] = h.uniq[u].size() <= KMP_MULTI_SHORT_LEN ? next_short[cl]++ : next_long[cl]++;
-                h.row[u] = row_base[cl] + in_cls[u];
-            }
-        }
-        const uint32_t rows_n = U;
-        const uint32_t n_long = rec_base[NCLS - 1] + (cls_n[NCLS - 1] - cls_short[NCLS - 1]);
-        std::vector<uint32_t> tab(KMP_MULTI_REC_W0 + (h.classed ? KMP_MULTI_CLS_WORDS + (size_t)n_long * KMP_MULTI_CREC_WORDS : (size_t)n_long * KMP_MULTI_REC_WORDS), 0u);
-        if (h.classed)
-            for (uint32_t cl = 0; cl < NCLS; cl++) tab[KMP_MULTI_REC_W0 + cl] = KMP_MULTI_CLS_WORD(cls_short[cl], rec_base[cl], row_base[cl]);
-        uint32_t *bucket = tab.data() + KMP_MULTI_BUCKET_W0;
-        uint32_t *entry = tab.data() + KMP_MULTI_ENTRY_W0;
-        std::vector<std::vector<uint32_t>> lists(KMP_MULTI_BUCKETS);
-        uint32_t n_two = 0;
-        for (uint32_t u = 0; u < U; u++) n_two += h.uniq[u].size() == 2 ? 1u : 0u;
-        const uint32_t bmask = n_two <= KMP_MULTI_MAX_TWO ? KMP_MULTI_KEYMASK : 0xFFFFu;        /* bucket key: three bytes, or two when 2-byte patterns abound */
-        for (uint32_t u = 0; u < U; u++) {
-            const std::string &p = h.uniq[u];
-            const uint32_t w16 = (uint8_t)p[0] | ((uint32_t)(uint8_t)p[1] << 8);
-            uint32_t *pair = tab.data() + KMP_MULTI_FILTER_W0;
-            if (p.size() >= 3) {
-                pair[2u * KMP_MULTI_PAIR(p[1], p[2])]      |= 1u << ((uint8_t)p[0] & 31u);       /* p0 may stand before p1 p2 */
-                pair[2u * KMP_MULTI_PAIR(p[0], p[1]) + 1u] |= 1u << ((uint8_t)p[2] & 31u);       /* p2 may follow p0 p1       */
-            } else {
-                for (uint32_t t = 0; t < 32u; t++) pair[2u * KMP_MULTI_PAIR(p[1], t)] |= 1u << ((uint8_t)p[0] & 31u);
-                pair[2u * KMP_MULTI_PAIR(p[0], p[1]) + 1u] = 0xFFFFFFFFu;                       /* whatever follows        */
-            }
-            for (uint32_t t = 0; t < 32u; t++) {                      /* a 2-byte pattern matches whatever follows it */
-                const uint32_t third = p.size() >= 3 ? (uint32_t)(uint8_t)p[2] : t;
-                const uint32_t w24 = w16 | (third << 16);
-                std::vector<uint32_t> &l = lists[KMP_MULTI_HASH(w24 & bmask)];
-                if (l.empty() || l.back() != u) l.push_back(u);
-                if (p.size() >= 3) break;
-            }
-            if (p.size() <= KMP_MULTI_SHORT_LEN) continue;
-            const uint32_t cl = cls_of[u];
-            if (h.classed) {
-                uint32_t *rec = tab.data() + KMP_MULTI_REC_W0 + KMP_MULTI_CLS_WORDS + (size_t)(rec_base[cl] + in_cls[u] - cls_short[cl]) * KMP_MULTI_CREC_WORDS;
-                rec[0] = (uint32_t)(uint8_t)p[3] | ((uint32_t)p.size() << 8) | (first_pat[h.gidx[u]] << 16);      /* byte 3 (the entry has bytes 0-2), the length, a pattern that has the rest */
-                for (uint32_t b = 4; b < p.size() && b < 8u; b++) rec[1] |= (uint32_t)(uint8_t)p[b] << (8 * (b & 3));
-            } else {
-                uint32_t *rec = tab.data() + KMP_MULTI_REC_W0 + (size_t)(in_cls[u] - cls_short[0]) * KMP_MULTI_REC_WORDS;
-                for (uint32_t b = 0; b < p.size() && b < 8u; b++) {
-                    rec[b >> 2] |= (uint32_t)(uint8_t)p[b] << (8 * (b & 3));
-                    if (b >= 4u) rec[2] |= 0xFFu << (8 * (b & 3));
-                }
-                rec[3] = (uint32_t)p.size() | (first_pat[h.gidx[u]] << 8);         /* the rest of it: kmp_pattern_dev[that index].pat */
-            }
-        }
-        uint32_t pos = 0;
-        for (uint32_t hh = 0; hh < KMP_MULTI_BUCKETS; hh++) {
-            for (size_t q = 0; q < lists[hh].size(); q++) {
-                const uint32_t u = lists[hh][q];
-                const std::string &p = h.uniq[u];
-                const uint32_t third = p.size() >= 3 ? (uint32_t)(uint8_t)p[2] : 0u;      /* never 0x00 inside a pattern */
-                const uint32_t ent = (uint32_t)(uint8_t)p[0] | ((uint32_t)(uint8_t)p[1] << 8) | (third << 16) | (in_cls[u] << 24);
-                if (q == 0) { bucket[2 * hh] = ent; continue; }       /* the first entry sits in the bucket itself */
-                if (pos >= KMP_MULTI_MAX_ENTRIES) return fail(KMPGPU_EINVAL, "kmpgpu_set_patterns: fused tables: entry list overflow");
-                entry[pos++] = ent;
-            }
-            const uint32_t extra = lists[hh].empty() ? 0u : (uint32_t)lists[hh].size() - 1u;
-            bucket[2 * hh + 1] = (pos - extra) | ((uint32_t)lists[hh].size() << 16);
-        }
-        /* the patterns this group counts, and the row of each */
-        for (const auto &e : elig) {
-            const auto &pl = place[e.second];
-            if (&hg[pl.first] != &h) continue;
-            h.ids.push_back(e.first);
-            h.rows.push_back(h.row[pl.second]);
-        }
-        /* the 1-byte patterns that ride along: rows behind the group's own */
-        if (n_ones)
-            for (const auto &oi : one_ids) { h.ids.push_back(oi.first); h.rows.push_back(rows_n + oi.second); }
-        /* row -> the pattern indices that share it, for the offset records (duplicates are reported one by one) and for the
-         * rest of a pattern of nine bytes or more (kmp_pattern_dev[first of them].pat) */
-        std::vector<uint32_t> uid_first(rows_n + n_ones + 1, 0u), uid_ids(h.ids.size());
-        for (uint32_t r : h.rows) uid_first[r + 1]++;
-        for (uint32_t u = 0; u < rows_n + n_ones; u++) uid_first[u + 1] += uid_first[u];
-        { std::vector<uint32_t> fill(uid_first.begin(), uid_first.end() - 1);
-          for (size_t i = 0; i < h.ids.size(); i++) uid_ids[fill[h.rows[i]]++] = h.ids[i]; }
-        s.fused_groups.emplace_back();
-        kmpgpu_ctx::FusedGroup &g = s.fused_groups.back();
-        auto up = [&](uint32_t **d, const std::vector<uint32_t> &v) -> hipError_t {
-            hipError_t e = hipMalloc(d, (v.size() ? v.size() : 1) * sizeof(uint32_t));
-            if (e == hipSuccess && !v.empty()) e = hipMemcpy(*d, v.data(), v.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-            return e;
-        };
-        HIP_TRY(up(&g.d_tables, tab));
-        HIP_TRY(up(&g.d_ids, h.ids));
-        HIP_TRY(up(&g.d_rows, h.rows));
-        HIP_TRY(up(&g.d_uid_first, uid_first));
-        HIP_TRY(up(&g.d_uid_ids, uid_ids));
-        g.words = (uint32_t)tab.size(); g.n_unique = rows_n + n_ones; g.cshift = h.classed ? KMP_MULTI_CLS_SHIFT : cls_short[0]; g.classed = h.classed; g.bmask = bmask; g.n_ones = n_ones; g.ones = ones; g.n_ids = (uint32_t)h.ids.size();
-        s.n_multi_unique += U;
-    }
-    std::vector<uint32_t> rest(rest_l);
-    rest.insert(rest.end(), rest_s.begin(), rest_s.end());
-    HIP_TRY(hipMalloc(&s.d_rest_ids, (rest.size() ? rest.size() : 1) * sizeof(uint32_t)));
-    if (!rest.empty()) HIP_TRY(hipMemcpy(s.d_rest_ids, rest.data(), rest.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    s.rest_long = (uint32_t)rest_l.size(); s.rest_short = (uint32_t)rest_s.size();
-    return KMPGPU_OK;
+    hipError_t e = hipMalloc(d, (v.size() ? v.size() : 1) * sizeof(uint32_t));
+    if (e == hipSuccess && !v.empty()) e = hipMemcpy(*d, v.data(), v.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    return e;
 }
 
+/* The passes of one set (kmpgpu_ctx::PatternSet) over the patterns `members` (indices into host, file order): the long / short split
+ * of the streaming passes and the tables of the fused pass as kmp_build_tables makes them (kmp_tables.cpp), uploaded. */
+int build_set(kmpgpu_ctx::PatternSet &s, const std::vector<kmp_pattern_dev> &host, const std::vector<uint32_t> &members)
+{
+    s.n = (uint32_t)members.size();
+    if (!s.n) return KMPGPU_OK;
+    kmp_set_tables t;
+    if (!kmp_build_tables(host.data(), members, &t)) return fail(KMPGPU_EINVAL, "kmpgpu_set_patterns: fused tables: entry list overflow");
+    s.n_long = t.n_long; s.n_short = t.n_short;
+    HIP_TRY(upload_words(&s.d_ids, t.ids));
+    for (const kmp_group_tables &h : t.groups) {
+        s.fused_groups.emplace_back();
+        kmpgpu_ctx::FusedGroup &g = s.fused_groups.back();
+        HIP_TRY(upload_words(&g.d_tables, h.tables));
+        HIP_TRY(upload_words(&g.d_ids, h.ids));
+        HIP_TRY(upload_words(&g.d_rows, h.rows));
+        HIP_TRY(upload_words(&g.d_uid_first, h.uid_first));
+        HIP_TRY(upload_words(&g.d_uid_ids, h.uid_ids));
+        g.words = (uint32_t)h.tables.size(); g.n_ids = (uint32_t)h.ids.size();
+        g.n_unique = h.n_unique; g.cshift = h.cshift; g.classed = h.classed; g.bmask = h.bmask; g.n_ones = h.n_ones; g.ones = h.ones;
+    }
+    s.n_multi_unique = t.n_multi_unique;
+    if (t.groups.empty()) return KMPGPU_OK;           /* nothing to fuse: every pattern keeps its own pass (s.d_ids) */
+    HIP_TRY(upload_words(&s.d_rest_ids, t.rest));
+    s.rest_long = t.rest_long; s.rest_short = t.rest_short;
+    return KMPGPU_OK;
+}
 
 }  // namespace
 
@@ -1001,22 +915,10 @@ void kmpgpu_destroy(kmpgpu_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     release_arena(c);
     release_frame_scratch(c);
-    if (c->d_bitmap) (void)hipFree(c->d_bitmap);
-    if (c->d_patterns) (void)hipFree(c->d_patterns);
-    if (c->d_partials) (void)hipFree(c->d_partials);
-    if (c->d_counts) (void)hipFree(c->d_counts);
-    if (c->d_marks) (void)hipFree(c->d_marks);
-    drop_rules(c);
-    drop_windows(c);
-    if (c->d_rule_out) (void)hipFree(c->d_rule_out);
-    if (c->d_plan) (void)hipFree(c->d_plan);
-    if (c->d_uplan) (void)hipFree(c->d_uplan);
-    if (c->d_pool) (void)hipFree(c->d_pool);
-    free_pattern_set(c->sets[0]);
-    free_pattern_set(c->sets[1]);
-    if (c->d_fold) (void)hipFree(c->d_fold);
-    if (c->d_err) (void)hipFree(c->d_err);
-    if (c->d_sum) (void)hipFree(c->d_sum);
+    release_pass_buffers(c);
+    release_patterns(c);
+    free_buffer(&c->d_err);                         /* (what kmpgpu_init took) */
+    free_buffer(&c->d_sum);
     if (c->h_counts) (void)hipHostFree(c->h_counts);
     if (c->h_small) (void)hipHostFree(c->h_small);
     for (auto ev : c->ev) if (ev) (void)hipEventDestroy(ev);
@@ -1137,12 +1039,7 @@ int kmpgpu_set_patterns_flags(kmpgpu_ctx *c, const uint8_t *const *pat, const ui
         members[letter ? 1 : 0].push_back(i);
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->d_patterns) { HIP_TRY(hipFree(c->d_patterns)); c->d_patterns = nullptr; }
-    if (c->d_counts) { HIP_TRY(hipFree(c->d_counts)); c->d_counts = nullptr; }
-    free_pattern_set(c->sets[0]);
-    free_pattern_set(c->sets[1]);
-    drop_rules(c);                                 /* their indices meant the old patterns */
-    drop_windows(c);                               /* ... and so did the windows' */
+    release_patterns(c);
     c->n_pat = n_pat;
     const size_t np = n_pat ? n_pat : 1;
     HIP_TRY(hipMalloc(&c->d_patterns, np * sizeof(kmp_pattern_dev)));
@@ -1156,7 +1053,7 @@ int kmpgpu_set_patterns_flags(kmpgpu_ctx *c, const uint8_t *const *pat, const ui
         c->h_counts_cap = np;
     }
     for (int k = 0; k < 2; k++) {
-        const int rc = build_set(c, c->sets[k], host, members[k]);
+        const int rc = build_set(c->sets[k], host, members[k]);
         if (rc) return rc;
     }
     /* an arena is attached already: its fold buffer now (a failure is reported by the first scan that needs the buffer) */
@@ -1169,7 +1066,7 @@ int kmpgpu_load_arena(kmpgpu_ctx *c, const uint8_t *arena, uint64_t arena_bytes,
 {
     if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_load_arena: ctx is NULL");
     if (n_pkts && (!arena || !pkt_off || !pkt_len)) return fail(KMPGPU_EINVAL, "kmpgpu_load_arena: NULL buffers");
-    uint64_t payload = 0, fold_end = 0;
+    IndexFacts f;
     for (uint64_t k = 0; k < n_pkts; k++) {         /* the layout contract the kernels rely on */
         const uint64_t o = pkt_off[k], l16 = ((uint64_t)pkt_len[k] + 15u) & ~15ull;
         if (o & 15u) return fail(KMPGPU_EINVAL, "payload %llu: offset %llu is not 16-byte aligned", (unsigned long long)k, (unsigned long long)o);
@@ -1177,36 +1074,32 @@ int kmpgpu_load_arena(kmpgpu_ctx *c, const uint8_t *arena, uint64_t arena_bytes,
         if (o > arena_bytes || std::max<uint64_t>(l16, 16) > arena_bytes - o)
             return fail(KMPGPU_EINVAL, "payload %llu: [%llu, +%llu) padded to 16 B (at least one 16-byte slot) exceeds the arena (%llu B)", (unsigned long long)k,
                         (unsigned long long)o, (unsigned long long)pkt_len[k], (unsigned long long)arena_bytes);
-        payload += pkt_len[k];
-        fold_end = std::max<uint64_t>(fold_end, o + std::max<uint64_t>(l16, 16));
+        f.payload_bytes += pkt_len[k];
+        f.span_end = o + std::max<uint64_t>(l16, 16);
+        f.fold_end = std::max<uint64_t>(f.fold_end, f.span_end);
     }
-    bool packed = n_pkts > 0;
-    for (uint64_t k = 0; packed && k + 1 < n_pkts; k++)
-        if (pkt_off[k + 1] != pkt_off[k] + std::max<uint64_t>(((uint64_t)pkt_len[k] + 15u) & ~15ull, 16)) packed = false;
-    bool uniform = n_pkts > 0;
-    uint64_t ustride = 0;
-    if (uniform) {
+    f.packed = n_pkts > 0;
+    for (uint64_t k = 0; f.packed && k + 1 < n_pkts; k++)
+        if (pkt_off[k + 1] != pkt_off[k] + std::max<uint64_t>(((uint64_t)pkt_len[k] + 15u) & ~15ull, 16)) f.packed = false;
+    f.uniform = n_pkts > 0;
+    if (f.uniform) {
         const uint64_t l16 = std::max<uint64_t>(((uint64_t)pkt_len[0] + 15u) & ~15ull, 16);
-        ustride = n_pkts > 1 ? pkt_off[1] - pkt_off[0] : l16;
-        if (n_pkts > 1 && pkt_off[1] < pkt_off[0]) uniform = false;
-        if (ustride < l16 || (ustride & 15u) || ustride >= (1ull << 31)) uniform = false;
-        for (uint64_t k = 0; uniform && k < n_pkts; k++)
-            if (pkt_len[k] != pkt_len[0] || pkt_off[k] != pkt_off[0] + k * ustride) uniform = false;
+        const uint64_t ustride = n_pkts > 1 ? pkt_off[1] - pkt_off[0] : l16;
+        if (n_pkts > 1 && pkt_off[1] < pkt_off[0]) f.uniform = false;
+        if (ustride < l16 || (ustride & 15u) || ustride >= (1ull << 31)) f.uniform = false;
+        for (uint64_t k = 0; f.uniform && k < n_pkts; k++)
+            if (pkt_len[k] != pkt_len[0] || pkt_off[k] != pkt_off[0] + k * ustride) f.uniform = false;
+        f.off0 = pkt_off[0]; f.stride = (uint32_t)ustride; f.len0 = pkt_len[0];
     }
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     /* streamed captures load batch after batch: keep the device buffers when the next batch fits */
-    const bool reuse = c->owned_arena && c->cap_arena >= arena_bytes && c->cap_pkts >= n_pkts && n_pkts > 0;
+    const bool reuse = owned_arena_holds(c, arena_bytes, n_pkts) && n_pkts > 0;
     release_arena(c, reuse);
     c->last.h2d_ms = 0; c->last.h2d_bytes = 0;
     if (n_pkts == 0) return KMPGPU_OK;
     if (arena_bytes < 16) return fail(KMPGPU_EINVAL, "arena smaller than 16 bytes");
-    if (!reuse) {
-        HIP_TRY(hipMalloc(&c->owned_arena, arena_bytes));
-        HIP_TRY(hipMalloc(&c->owned_off, n_pkts * sizeof(uint64_t)));
-        HIP_TRY(hipMalloc(&c->owned_len, n_pkts * sizeof(uint32_t)));
-        c->cap_arena = arena_bytes; c->cap_pkts = n_pkts;
-    }
+    HIP_TRY(ensure_owned_arena(c, arena_bytes, n_pkts, EXACT));
     HIP_TRY(hipEventRecord(c->ev[0], c->stream));
     HIP_TRY(upload_split(c->owned_arena, arena, arena_bytes, c->stream));
     HIP_TRY(hipMemcpyAsync(c->owned_off, pkt_off, n_pkts * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
@@ -1217,41 +1110,7 @@ int kmpgpu_load_arena(kmpgpu_ctx *c, const uint8_t *arena, uint64_t arena_bytes,
     HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
     c->last.h2d_ms = ms;
     c->last.h2d_bytes = arena_bytes + n_pkts * (sizeof(uint64_t) + sizeof(uint32_t));
-    c->d_arena = (const uint8_t *)c->owned_arena;
-    c->d_off = (const uint64_t *)c->owned_off;
-    c->d_len = (const uint32_t *)c->owned_len;
-    c->arena_bytes = arena_bytes; c->n_pkts = n_pkts; c->payload_bytes = payload;
-    c->uniform = uniform; c->uni_off0 = pkt_off[0]; c->uni_stride = (uint32_t)ustride; c->uni_len = pkt_len[0];
-    c->packed = packed;
-    c->span_end = pkt_off[n_pkts - 1] + std::max<uint64_t>(((uint64_t)pkt_len[n_pkts - 1] + 15u) & ~15ull, 16);
-    c->fold_end = fold_end;                           /* (the last entry's slot is the furthest only when the index is in arena order) */
-    (void)grow_fold(c, arena_bytes);                  /* (a failure is reported by the first scan that needs the fold) */
-    return prepare_packed(c);
-}
-
-/* Shared tail of the loaders that produce the index on the device: contract + uniform/packed
- * detection + payload sum from kmp_validate_index_kernel, then the packed kernels' side tables. */
-static int finish_device_index(kmpgpu_ctx *c, const char *who)
-{
-    HIP_TRY(hipMemsetAsync(c->d_err, 0, 2 * sizeof(uint32_t), c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_sum, 0, 6 * sizeof(unsigned long long), c->stream));
-    HIP_TRY(kmp_launch_validate(c->d_off, c->d_len, c->n_pkts, c->arena_bytes, c->d_err, c->d_sum, c->stream));
-    uint32_t err[2] = {0, 0};
-    unsigned long long info[6] = {0, 0, 0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(c->h_small, c->d_sum, sizeof info, hipMemcpyDeviceToHost, c->stream));          /* (pinned: no staging) */
-    HIP_TRY(hipMemcpyAsync(c->h_small + 8, c->d_err, sizeof err, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    memcpy(info, c->h_small, sizeof info);
-    memcpy(err, c->h_small + 8, sizeof err);
-    if (err[0]) return fail(KMPGPU_EINVAL, "%s: the payload index violates the layout contract (flags %u)", who, err[0]);
-    c->payload_bytes = info[0];
-    c->uniform = ((err[1] & 1u) == 0) && info[2] >= 16 && info[2] < (1ull << 31);
-    c->uni_off0 = info[1]; c->uni_stride = (uint32_t)info[2]; c->uni_len = (uint32_t)info[3];
-    c->packed = (err[1] & 2u) == 0;
-    c->span_end = info[4];
-    c->fold_stale = true;
-    (void)grow_fold(c, c->arena_bytes);              /* (a failure is reported by the first scan that needs the fold) */
-    return prepare_packed(c);
+    return install_arena(c, c->owned_arena, c->owned_off, c->owned_len, arena_bytes, n_pkts, f, /* wrote_padding = */ false);
 }
 
 int kmpgpu_load_frames_begin(kmpgpu_ctx *c, const uint8_t *file_bytes, uint64_t file_nbytes, const uint64_t *frame_off,
@@ -1280,10 +1139,10 @@ int kmpgpu_load_frames_begin(kmpgpu_ctx *c, const uint8_t *file_bytes, uint64_t 
     if (n_frames == 0) return KMPGPU_OK;
 
     /* scratch, grown on demand and kept (no hipMalloc / hipFree per batch: either synchronises the whole device) */
-    HIP_TRY(grow_buffer(&c->fr_file, &c->fr_file_cap, span + 64));
-    HIP_TRY(grow_buffer(&c->fr_off, &c->fr_off_cap, n_frames));
-    HIP_TRY(grow_buffer(&c->fr_cl, &c->fr_cl_cap, n_frames));
-    HIP_TRY(grow_buffer(&c->fr_ws, &c->fr_ws_cap, (uint64_t)kmp_extract_ws_bytes(n_frames)));
+    HIP_TRY(grow_buffer(&c->fr_file, &c->fr_file_cap, span + 64, EIGHTH));
+    HIP_TRY(grow_buffer(&c->fr_off, &c->fr_off_cap, n_frames, EIGHTH));
+    HIP_TRY(grow_buffer(&c->fr_cl, &c->fr_cl_cap, n_frames, EIGHTH));
+    HIP_TRY(grow_buffer(&c->fr_ws, &c->fr_ws_cap, (uint64_t)kmp_extract_ws_bytes(n_frames), EIGHTH));
     if (!c->fr_tot) HIP_TRY(hipMalloc(&c->fr_tot, 2 * sizeof(unsigned long long)));
 
     /* the device buffer holds the file's bytes [span_lo, span_hi): the kernels address it through the pointer that stands for
@@ -1327,32 +1186,18 @@ int kmpgpu_load_frames_finish(kmpgpu_ctx *c, uint64_t *n_payloads)
     const uint64_t n_pkts = tot[1], arena_bytes = tot[0] + 64;
     if (n_payloads) *n_payloads = n_pkts;
     if (n_pkts == 0) return KMPGPU_OK;
-    if (!(c->owned_arena && c->cap_arena >= arena_bytes && c->cap_pkts >= n_pkts)) {
-        if (c->owned_arena) HIP_TRY(hipFree(c->owned_arena));
-        if (c->owned_off) HIP_TRY(hipFree(c->owned_off));
-        if (c->owned_len) HIP_TRY(hipFree(c->owned_len));
-        c->owned_arena = c->owned_off = c->owned_len = nullptr; c->cap_arena = c->cap_pkts = 0;
-        const uint64_t take_b = arena_bytes + arena_bytes / 8, take_n = n_pkts + n_pkts / 8;
-        HIP_TRY(hipMalloc(&c->owned_arena, take_b));
-        HIP_TRY(hipMalloc(&c->owned_off, take_n * sizeof(uint64_t)));
-        HIP_TRY(hipMalloc(&c->owned_len, take_n * sizeof(uint32_t)));
-        c->cap_arena = take_b; c->cap_pkts = take_n;
-    }
-    HIP_TRY(grow_buffer(&c->fr_src, &c->fr_src_cap, n_pkts));
+    HIP_TRY(ensure_owned_arena(c, arena_bytes, n_pkts, EIGHTH));
+    HIP_TRY(grow_buffer(&c->fr_src, &c->fr_src_cap, n_pkts, EIGHTH));
     const uint8_t *d_file0 = c->fr_file - c->fr_span_lo;
-    HIP_TRY(hipMemsetAsync((uint8_t *)c->owned_arena + tot[0], 0, 64, c->stream));
-    HIP_TRY(kmp_launch_extract_phase2(d_file0, c->fr_off, n_frames, c->fr_ws, n_pkts, (uint8_t *)c->owned_arena, (uint64_t *)c->owned_off,
-                                      (uint32_t *)c->owned_len, c->fr_src, c->stream));
-    c->d_arena = (const uint8_t *)c->owned_arena;
-    c->d_off = (const uint64_t *)c->owned_off;
-    c->d_len = (const uint32_t *)c->owned_len;
-    c->arena_bytes = arena_bytes; c->n_pkts = n_pkts;
-    c->pad_known_clean = true;                          /* kmp_gather_kernel writes every slot whole: payload, then 0x00 up to the slot's end */
-    const int rc = finish_device_index(c, "kmpgpu_load_frames");
-    c->pad_known_clean = false;
+    HIP_TRY(hipMemsetAsync(c->owned_arena + tot[0], 0, 64, c->stream));
+    HIP_TRY(kmp_launch_extract_phase2(d_file0, c->fr_off, n_frames, c->fr_ws, n_pkts, c->owned_arena, c->owned_off, c->owned_len, c->fr_src, c->stream));
+    IndexFacts f;
+    int rc = validate_index(c, "kmpgpu_load_frames", c->owned_off, c->owned_len, n_pkts, arena_bytes, &f);
+    /* kmp_gather_kernel writes every slot whole: payload, then 0x00 up to the slot's end */
+    if (!rc) rc = install_arena(c, c->owned_arena, c->owned_off, c->owned_len, arena_bytes, n_pkts, f, /* wrote_padding = */ true);
     /* one capture uploaded whole: its bytes are not kept around (a streamed capture's batches are small and the next one
      * reuses the buffer) */
-    if (c->fr_file_cap > (1ull << 30)) { (void)hipFree(c->fr_file); c->fr_file = nullptr; c->fr_file_cap = 0; }
+    if (c->fr_file_cap > (1ull << 30)) free_buffer(&c->fr_file, &c->fr_file_cap);
     return rc;
 }
 
@@ -1369,42 +1214,27 @@ int kmpgpu_reserve(kmpgpu_ctx *c, uint64_t arena_bytes, uint64_t n_pkts, uint64_
     if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_reserve: ctx is NULL");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (arena_bytes && n_pkts && !(c->owned_arena && c->cap_arena >= arena_bytes && c->cap_pkts >= n_pkts)) {
-        if (c->d_arena == (const uint8_t *)c->owned_arena) release_arena(c, true);        /* the arena in use lives in these buffers */
-        if (c->owned_arena) HIP_TRY(hipFree(c->owned_arena));
-        if (c->owned_off) HIP_TRY(hipFree(c->owned_off));
-        if (c->owned_len) HIP_TRY(hipFree(c->owned_len));
-        c->owned_arena = c->owned_off = c->owned_len = nullptr; c->cap_arena = c->cap_pkts = 0;
-        HIP_TRY(hipMalloc(&c->owned_arena, arena_bytes));
-        HIP_TRY(hipMalloc(&c->owned_off, n_pkts * sizeof(uint64_t)));
-        HIP_TRY(hipMalloc(&c->owned_len, n_pkts * sizeof(uint32_t)));
-        c->cap_arena = arena_bytes; c->cap_pkts = n_pkts;
+    if (arena_bytes && n_pkts && !owned_arena_holds(c, arena_bytes, n_pkts)) {
+        if (c->d_arena == c->owned_arena) release_arena(c, true);        /* the arena in use lives in these buffers */
+        HIP_TRY(ensure_owned_arena(c, arena_bytes, n_pkts, EXACT));
     }
     if (arena_bytes) {
         const uint64_t words = arena_bytes / KMP_CHUNK + 32;
-        if (c->bitmap_cap < words) {
-            const bool live = c->bitmap_live;
-            if (live) return fail(KMPGPU_ESTATE, "kmpgpu_reserve: an arena larger than the reserved size is attached");
-            if (c->d_bitmap) HIP_TRY(hipFree(c->d_bitmap));
-            c->d_bitmap = nullptr; c->bitmap_cap = 0;
-            HIP_TRY(hipMalloc(&c->d_bitmap, words * sizeof(unsigned long long)));
-            c->bitmap_cap = words;
-        }
-    }
-    if (arena_bytes) {
+        if (c->bitmap_cap < words && c->bitmap_live) return fail(KMPGPU_ESTATE, "kmpgpu_reserve: an arena larger than the reserved size is attached");
+        HIP_TRY(grow_buffer(&c->d_bitmap, &c->bitmap_cap, words, EXACT));
         const int rc = grow_fold(c, arena_bytes);    /* the nocase patterns' folded copy of a batch */
         if (rc) return rc;
     }
     if (frame_bytes && n_frames) {
-        HIP_TRY(grow_buffer(&c->fr_file, &c->fr_file_cap, frame_bytes + 64));
-        HIP_TRY(grow_buffer(&c->fr_off, &c->fr_off_cap, n_frames));
-        HIP_TRY(grow_buffer(&c->fr_cl, &c->fr_cl_cap, n_frames));
-        HIP_TRY(grow_buffer(&c->fr_ws, &c->fr_ws_cap, (uint64_t)kmp_extract_ws_bytes(n_frames)));
-        HIP_TRY(grow_buffer(&c->fr_src, &c->fr_src_cap, n_frames));
+        HIP_TRY(grow_buffer(&c->fr_file, &c->fr_file_cap, frame_bytes + 64, EIGHTH));
+        HIP_TRY(grow_buffer(&c->fr_off, &c->fr_off_cap, n_frames, EIGHTH));
+        HIP_TRY(grow_buffer(&c->fr_cl, &c->fr_cl_cap, n_frames, EIGHTH));
+        HIP_TRY(grow_buffer(&c->fr_ws, &c->fr_ws_cap, (uint64_t)kmp_extract_ws_bytes(n_frames), EIGHTH));
+        HIP_TRY(grow_buffer(&c->fr_src, &c->fr_src_cap, n_frames, EIGHTH));
         if (!c->fr_tot) HIP_TRY(hipMalloc(&c->fr_tot, 2 * sizeof(unsigned long long)));
         HIP_TRY(hipMemsetAsync(c->fr_file, 0, frame_bytes + 64, c->stream));      /* first touch now: the first upload into fresh device memory runs at 3/4 of the rate */
     }
-    if (c->owned_arena && arena_bytes && c->d_arena != (const uint8_t *)c->owned_arena) HIP_TRY(hipMemsetAsync(c->owned_arena, 0, std::min<uint64_t>(arena_bytes, c->cap_arena), c->stream));
+    if (c->owned_arena && arena_bytes && c->d_arena != c->owned_arena) HIP_TRY(hipMemsetAsync(c->owned_arena, 0, std::min<uint64_t>(arena_bytes, c->cap_arena), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return KMPGPU_OK;
 }
@@ -1421,28 +1251,10 @@ int kmpgpu_attach_arena(kmpgpu_ctx *c, const void *d_arena, uint64_t arena_bytes
     release_arena(c);
     if (n_pkts == 0) return KMPGPU_OK;
     if (arena_bytes < 16) return fail(KMPGPU_EINVAL, "arena smaller than 16 bytes");
-    HIP_TRY(hipMemsetAsync(c->d_err, 0, 2 * sizeof(uint32_t), c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_sum, 0, 6 * sizeof(unsigned long long), c->stream));
-    HIP_TRY(kmp_launch_validate((const uint64_t *)d_pkt_off, (const uint32_t *)d_pkt_len, n_pkts, arena_bytes, c->d_err, c->d_sum, c->stream));
-    uint32_t err[2] = {0, 0};
-    unsigned long long info[6] = {0, 0, 0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(err, c->d_err, sizeof err, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(info, c->d_sum, sizeof info, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (err[0] & 1u) return fail(KMPGPU_EINVAL, "kmpgpu_attach_arena: a payload offset is not 16-byte aligned");
-    if (err[0] & 2u) return fail(KMPGPU_EINVAL, "kmpgpu_attach_arena: a payload (padded to 16 B) exceeds the arena");
-    if (err[0] & 4u) return fail(KMPGPU_EINVAL, "kmpgpu_attach_arena: a payload length is not below 2^30");
-    c->d_arena = (const uint8_t *)d_arena;
-    c->d_off = (const uint64_t *)d_pkt_off;
-    c->d_len = (const uint32_t *)d_pkt_len;
-    c->arena_bytes = arena_bytes; c->n_pkts = n_pkts; c->payload_bytes = info[0];
-    c->uniform = ((err[1] & 1u) == 0) && info[2] >= 16 && info[2] < (1ull << 31);
-    c->uni_off0 = info[1]; c->uni_stride = (uint32_t)info[2]; c->uni_len = (uint32_t)info[3];
-    c->packed = (err[1] & 2u) == 0;
-    c->span_end = info[4];
-    c->fold_stale = true;
-    (void)grow_fold(c, c->arena_bytes);              /* (a failure is reported by the first scan that needs the fold) */
-    return prepare_packed(c);
+    IndexFacts f;
+    const int rc = validate_index(c, "kmpgpu_attach_arena", (const uint64_t *)d_pkt_off, (const uint32_t *)d_pkt_len, n_pkts, arena_bytes, &f);
+    if (rc) return rc;                               /* (nothing is attached) */
+    return install_arena(c, (const uint8_t *)d_arena, (const uint64_t *)d_pkt_off, (const uint32_t *)d_pkt_len, arena_bytes, n_pkts, f, /* wrote_padding = */ false);
 }
 
 int kmpgpu_load_selected(kmpgpu_ctx *dst, kmpgpu_ctx *src, const void *select, int select_on_device, uint64_t *n_selected)
@@ -1466,11 +1278,11 @@ int kmpgpu_load_selected(kmpgpu_ctx *dst, kmpgpu_ctx *src, const void *select, i
 
     /* the scratch of kmpgpu_load_frames: fr_off takes the uploaded bitmap, fr_ws the scan, fr_src the copy's records */
     const uint64_t words = (n + 63) / 64;
-    HIP_TRY(grow_buffer(&c->fr_ws, &c->fr_ws_cap, (uint64_t)kmp_extract_ws_bytes(n)));
+    HIP_TRY(grow_buffer(&c->fr_ws, &c->fr_ws_cap, (uint64_t)kmp_extract_ws_bytes(n), EIGHTH));
     if (!c->fr_tot) HIP_TRY(hipMalloc(&c->fr_tot, 2 * sizeof(unsigned long long)));
     const unsigned long long *d_select = (const unsigned long long *)select;
     if (!select_on_device) {
-        HIP_TRY(grow_buffer(&c->fr_off, &c->fr_off_cap, words));
+        HIP_TRY(grow_buffer(&c->fr_off, &c->fr_off_cap, words, EIGHTH));
         HIP_TRY(hipEventRecord(c->ev[0], c->stream));
         HIP_TRY(hipMemcpyAsync(c->fr_off, select, words * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipEventRecord(c->ev[1], c->stream));
@@ -1498,42 +1310,20 @@ int kmpgpu_load_selected(kmpgpu_ctx *dst, kmpgpu_ctx *src, const void *select, i
         c->last.kernel_ms = ms; c->last.launches = 3;
         return KMPGPU_OK;
     }
-    if (!(c->owned_arena && c->cap_arena >= arena_bytes && c->cap_pkts >= n_pkts)) {
-        if (c->owned_arena) HIP_TRY(hipFree(c->owned_arena));
-        if (c->owned_off) HIP_TRY(hipFree(c->owned_off));
-        if (c->owned_len) HIP_TRY(hipFree(c->owned_len));
-        c->owned_arena = c->owned_off = c->owned_len = nullptr; c->cap_arena = c->cap_pkts = 0;
-        const uint64_t take_b = arena_bytes + arena_bytes / 8, take_n = n_pkts + n_pkts / 8;
-        hipError_t e = hipMalloc(&c->owned_arena, take_b);
-        if (e == hipSuccess) e = hipMalloc(&c->owned_off, take_n * sizeof(uint64_t));
-        if (e == hipSuccess) e = hipMalloc(&c->owned_len, take_n * sizeof(uint32_t));
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            release_arena(c);                             /* (frees what was allocated: dst is empty and usable) */
-            return fail(e == hipErrorOutOfMemory ? KMPGPU_ENOMEM : KMPGPU_EHIP, "kmpgpu_load_selected: an arena of %llu bytes / %llu payloads could not be allocated: %s",
-                        (unsigned long long)take_b, (unsigned long long)take_n, hipGetErrorString(e));
-        }
-        c->cap_arena = take_b; c->cap_pkts = take_n;
-    }
-    {
-        const hipError_t e = grow_buffer(&c->fr_src, &c->fr_src_cap, 2 * n_pkts);      /* 16 bytes per selected payload */
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(e == hipErrorOutOfMemory ? KMPGPU_ENOMEM : KMPGPU_EHIP, "kmpgpu_load_selected: the copy's records (%llu payloads) could not be allocated: %s",
-                        (unsigned long long)n_pkts, hipGetErrorString(e));
-        }
-    }
-    HIP_TRY(hipMemsetAsync((uint8_t *)c->owned_arena + tot[0], 0, 64, c->stream));
-    HIP_TRY(kmp_launch_select_phase2(src->d_arena, src->d_off, n, c->fr_ws, n_pkts, tot[0], (uint8_t *)c->owned_arena, (uint64_t *)c->owned_off,
-                                     (uint32_t *)c->owned_len, c->fr_src, c->nontemporal != 0, c->stream));
+    hipError_t e = ensure_owned_arena(c, arena_bytes, n_pkts, EIGHTH);       /* (on failure dst is empty and usable) */
+    if (e != hipSuccess)
+        return alloc_fail(e, "kmpgpu_load_selected: an arena of %llu bytes / %llu payloads could not be allocated",
+                          (unsigned long long)(arena_bytes + arena_bytes / 8), (unsigned long long)(n_pkts + n_pkts / 8));
+    e = grow_buffer(&c->fr_src, &c->fr_src_cap, 2 * n_pkts, EIGHTH);      /* 16 bytes per selected payload */
+    if (e != hipSuccess) return alloc_fail(e, "kmpgpu_load_selected: the copy's records (%llu payloads) could not be allocated", (unsigned long long)n_pkts);
+    HIP_TRY(hipMemsetAsync(c->owned_arena + tot[0], 0, 64, c->stream));
+    HIP_TRY(kmp_launch_select_phase2(src->d_arena, src->d_off, n, c->fr_ws, n_pkts, tot[0], c->owned_arena, c->owned_off, c->owned_len, c->fr_src,
+                                     c->nontemporal != 0, c->stream));
     HIP_TRY(hipEventRecord(c->ev[3], c->stream));
-    c->d_arena = (const uint8_t *)c->owned_arena;
-    c->d_off = (const uint64_t *)c->owned_off;
-    c->d_len = (const uint32_t *)c->owned_len;
-    c->arena_bytes = arena_bytes; c->n_pkts = n_pkts;
-    c->pad_known_clean = true;                            /* kmp_select_copy_kernel writes every slot whole: payload, then 0x00 up to the slot's end */
-    const int rc = finish_device_index(c, "kmpgpu_load_selected");
-    c->pad_known_clean = false;
+    IndexFacts f;
+    int rc = validate_index(c, "kmpgpu_load_selected", c->owned_off, c->owned_len, n_pkts, arena_bytes, &f);
+    /* kmp_select_copy_kernel writes every slot whole: payload, then 0x00 up to the slot's end */
+    if (!rc) rc = install_arena(c, c->owned_arena, c->owned_off, c->owned_len, arena_bytes, n_pkts, f, /* wrote_padding = */ true);
     if (rc) { release_arena(c, true); return rc; }
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
@@ -1547,7 +1337,7 @@ int kmpgpu_scan_enqueue(kmpgpu_ctx *c, void *d_counts_out)
     if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_scan_enqueue: ctx is NULL");
     if ((uintptr_t)d_counts_out & 7u) return fail(KMPGPU_EINVAL, "kmpgpu_scan_enqueue: d_counts_out is not 8-byte aligned");
     HIP_TRY(hipSetDevice(c->device));
-    return enqueue_pass(c, nullptr, (unsigned long long *)d_counts_out);
+    return enqueue_pass(c, nullptr, (unsigned long long *)d_counts_out, c->accumulate != 0);
 }
 
 void *kmpgpu_counts_device(kmpgpu_ctx *c) { return c ? (void *)c->d_counts : nullptr; }
@@ -1604,7 +1394,7 @@ int kmpgpu_scan(kmpgpu_ctx *c, uint64_t *counts_out, kmpgpu_timing *t)
     HIP_TRY(hipSetDevice(c->device));
     uint32_t launches = 0;
     HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-    int rc = enqueue_pass(c, &launches, nullptr);
+    int rc = enqueue_pass(c, &launches, nullptr, c->accumulate != 0);
     if (rc) return rc;
     HIP_TRY(hipEventRecord(c->ev[1], c->stream));
     HIP_TRY(hipMemcpyAsync(c->h_counts, c->d_counts, sizeof(uint64_t) * c->n_pat, hipMemcpyDeviceToHost, c->stream));
@@ -1660,10 +1450,7 @@ int kmpgpu_scan_offsets(kmpgpu_ctx *c, kmpgpu_match *out, uint64_t cap, uint64_t
         /* an arena kept in place (KMPGPU_OPT_REPACK = 0) whose slots are not back to back: the offsets come from the
          * streaming kernels, so it is packed now, once (the context scans its packed copy from here on) */
         HIP_TRY(hipStreamSynchronize(c->stream));
-        const int keep = c->repack;
-        c->repack = 1;
-        const int rr = prepare_packed(c);
-        c->repack = keep;
+        const int rr = repack_arena(c);
         if (rr) return rr;
     }
     void *d_out = nullptr;
@@ -1681,10 +1468,7 @@ int kmpgpu_scan_offsets(kmpgpu_ctx *c, kmpgpu_match *out, uint64_t cap, uint64_t
          * total under KMPGPU_OPT_ACCUMULATE, or the result of a count reduce) are left as they are. */
         EmitTarget t;
         t.out = d_out; t.counter = d_cnt; t.cap = cap;
-        const int acc = c->accumulate;
-        c->accumulate = 0;
-        rc = enqueue_pass(c, nullptr, d_cnt + 1, &t);
-        c->accumulate = acc;
+        rc = enqueue_pass(c, nullptr, d_cnt + 1, /* accumulate = */ false, &t);
     }
     if (!rc && (e = hipMemcpyAsync(&found, d_cnt, sizeof found, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
         rc = fail(KMPGPU_EHIP, "hipMemcpyAsync failed: %s", hipGetErrorString(e));
@@ -1732,21 +1516,14 @@ int marking_pass(kmpgpu_ctx *c, const char *who, MarkPass *p)
     if (!c->packed) {
         /* an arena kept in place (KMPGPU_OPT_REPACK = 0) whose slots are not back to back: packed now, once (kmpgpu_scan_offsets) */
         HIP_TRY(hipStreamSynchronize(c->stream));
-        const int keep = c->repack;
-        c->repack = 1;
-        const int rr = prepare_packed(c);
-        c->repack = keep;
+        const int rr = repack_arena(c);
         if (rr) return rr;
     }
     /* one device buffer, grown like the others: [marks n_pat x stride][pkt_counts n_pat][any stride][counts n_pat] */
     const uint64_t mat = (uint64_t)np * stride;
     const uint64_t words = mat + np + stride + np;
-    hipError_t e = grow_buffer(&c->d_marks, &c->marks_cap, words);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? KMPGPU_ENOMEM : KMPGPU_EHIP, "%s: the hit matrix (%llu bytes) could not be allocated: %s",
-                    who, (unsigned long long)(words * 8u), hipGetErrorString(e));
-    }
+    hipError_t e = grow_buffer(&c->d_marks, &c->marks_cap, words, EIGHTH);
+    if (e != hipSuccess) return alloc_fail(e, "%s: the hit matrix (%llu bytes) could not be allocated", who, (unsigned long long)(words * 8u));
     p->stride = stride; p->mat = mat;
     p->d_mat = c->d_marks; p->d_pc = p->d_mat + mat; p->d_any = p->d_pc + np; p->d_cnt = p->d_any + stride;
     HIP_TRY(hipEventRecord(c->ev[0], c->stream));
@@ -1756,11 +1533,7 @@ int marking_pass(kmpgpu_ctx *c, const char *who, MarkPass *p)
     EmitTarget tg;
     tg.out = nullptr; tg.counter = nullptr; tg.cap = 0;
     tg.marks = p->d_mat; tg.mark_stride = (uint32_t)stride;
-    const int acc = c->accumulate;
-    c->accumulate = 0;
-    const int rc = enqueue_pass(c, &p->launches, p->d_cnt, &tg);
-    c->accumulate = acc;
-    return rc;
+    return enqueue_pass(c, &p->launches, p->d_cnt, /* accumulate = */ false, &tg);
 }
 
 /* rows of W words from a device matrix whose rows are `stride` words apart */
@@ -1851,10 +1624,9 @@ int kmpgpu_set_rules(kmpgpu_ctx *c, const uint32_t *rule_off, const uint32_t *te
     if (e == hipSuccess && !quads.empty()) e = hipMemcpy(d_quads, quads.data(), quads.size() * sizeof(uint4), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
-        (void)hipGetLastError();
-        if (d_heads) (void)hipFree(d_heads);
-        if (d_quads) (void)hipFree(d_quads);
-        return fail(e == hipErrorOutOfMemory ? KMPGPU_ENOMEM : KMPGPU_EHIP, "kmpgpu_set_rules: the rules could not be uploaded: %s", hipGetErrorString(e));
+        free_buffer(&d_heads);
+        free_buffer(&d_quads);
+        return alloc_fail(e, "kmpgpu_set_rules: the rules could not be uploaded");
     }
     drop_rules(c);
     c->d_rule_heads = d_heads; c->d_rule_quads = d_quads; c->n_rules = n_rules;
@@ -1887,9 +1659,8 @@ int kmpgpu_set_windows(kmpgpu_ctx *c, const uint32_t *first, const uint32_t *las
         if (e == hipSuccess) e = hipMemcpyAsync(d_win, win.data(), win.size() * sizeof(uint2), hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      /* (win is a local) */
         if (e != hipSuccess) {
-            (void)hipGetLastError();
-            if (d_win) (void)hipFree(d_win);
-            return fail(e == hipErrorOutOfMemory ? KMPGPU_ENOMEM : KMPGPU_EHIP, "kmpgpu_set_windows: the windows could not be uploaded: %s", hipGetErrorString(e));
+            free_buffer(&d_win);
+            return alloc_fail(e, "kmpgpu_set_windows: the windows could not be uploaded");
         }
     } else HIP_TRY(hipStreamSynchronize(c->stream));
     drop_windows(c);
@@ -1915,24 +1686,19 @@ int kmpgpu_scan_rules(kmpgpu_ctx *c, uint64_t *rule_pkt_counts_out, uint64_t *an
     /* one device buffer, grown like the others: [rule rows n_rules x stride][rule_pkt_counts n_rules][any stride] */
     const uint64_t rows = (uint64_t)nr * p.stride;
     const uint64_t words = rows + nr + p.stride;
-    hipError_t e = grow_buffer(&c->d_rule_out, &c->rule_out_cap, words);
+    hipError_t e = grow_buffer(&c->d_rule_out, &c->rule_out_cap, words, EIGHTH);
     if (e != hipSuccess) {
-        (void)hipGetLastError();
         /* the marking pass is under way on the stream; the context stays usable */
         (void)hipStreamSynchronize(c->stream);
-        return fail(e == hipErrorOutOfMemory ? KMPGPU_ENOMEM : KMPGPU_EHIP, "kmpgpu_scan_rules: the rule rows (%llu bytes) could not be allocated: %s",
-                    (unsigned long long)(words * 8u), hipGetErrorString(e));
+        return alloc_fail(e, "kmpgpu_scan_rules: the rule rows (%llu bytes) could not be allocated", (unsigned long long)(words * 8u));
     }
     unsigned long long *d_rows = c->d_rule_out, *d_rc = d_rows + rows, *d_any = d_rc + nr;
     /* the kernel adds to the counts and ORs into any; it writes every word of the rows itself */
     HIP_TRY(hipMemsetAsync(d_rc, 0, (size_t)(nr + p.stride) * sizeof(unsigned long long), c->stream));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (c->profiling && c->prof_n < c->prof_cap) {
-        e0 = c->prof_ev[2 * c->prof_n]; e1 = c->prof_ev[2 * c->prof_n + 1];
-        HIP_TRY(hipEventRecord(e0, c->stream));
-    }
+    hipEvent_t e1;
+    HIP_TRY(profile_launch(c, &e1));
     HIP_TRY(kmp_launch_rules(p.d_mat, p.stride, c->n_pkts, c->d_rule_heads, c->d_rule_quads, c->n_rules, d_rows, d_rc, d_any, c->stream));
-    if (e0) { HIP_TRY(hipEventRecord(e1, c->stream)); c->prof_n++; }
+    HIP_TRY(profile_launched(c, e1));
     HIP_TRY(hipEventRecord(c->ev[1], c->stream));
     if (rule_pkt_counts_out) HIP_TRY(hipMemcpyAsync(rule_pkt_counts_out, d_rc, nr * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     if (any_out) HIP_TRY(hipMemcpyAsync(any_out, d_any, p.W * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));

@@ -23,6 +23,8 @@ Where every kernel's second code path starts, read off the launchers (KMP_BLOCK_
        as 64-bit values
   R10  kmpgpu_attach_arena of a borrowed, non-packed   any size                                             test_repack_at_scale (route "attach")
        arena (device-side check -> repack)
+  R11  the arena buffers and the install path that    buffers grow, are reused, are given back            test_one_context_through_every_loader
+       every loader shares (csrc/kmpgpu.hip)
 
 Checked to bite: with each of these memory-safe changes made to a scratch build, tests here failed while the rest of the GPU
 suite passed -- the carry cb, or cc, of kmp_scan_totals_kernel not applied to the tiles' prefixes (totals kept; R2: the
@@ -537,3 +539,82 @@ def test_uniform_index_with_one_odd_length(gm, oracle, route):
     finally:
         _restore(gm)
         gm.load_arena(np.zeros(0, np.uint8), np.zeros(0, np.uint64), np.zeros(0, np.uint32))
+
+
+# ------------------------------------------------------------------------------------------------
+# one context through every loader: the kept buffers grow, are reused, and carry no arena over
+# ------------------------------------------------------------------------------------------------
+def _mixed_arena(n, seed):
+    """n payloads of 0..200 bytes over the letters of the two patterns below, packed, padding 0x00."""
+    rng = np.random.default_rng(seed)
+    ln = rng.integers(0, 201, n).astype(np.uint32)
+    off = PM.packed_offsets(ln)
+    end = int(off[-1] + PM.slot_bytes(ln)[-1]) if n else 0
+    arena = np.frombuffer(b"idhtp", dtype=np.uint8)[rng.integers(0, 5, end + 64)]
+    arena = PM.clean_padding(arena, off, ln)
+    arena[end:] = 0
+    return arena, off.astype(np.uint64), ln
+
+
+def test_one_context_through_every_loader(oracle):
+    """kmpgpu_load_arena, kmpgpu_attach_arena, kmpgpu_load_frames and kmpgpu_load_selected share the context's arena buffers and
+    one way of installing an arena: sizes that grow and shrink in a fixed order, and after every step the arena's size and the
+    counts of two patterns against the oracle.  Then the uploads again on a context whose buffers kmpgpu_reserve took first."""
+    import os
+
+    from conftest import DATA
+    from multithreading_string_matching_amd.host import HostArena
+
+    pats = [b"id", b"http"]
+    pcap = os.path.join(DATA, "udp.pcap")
+    cap = HostArena.from_pcap(pcap, "udp")
+    arenas = {n: _mixed_arena(n, seed=80 + k) for k, n in enumerate((300, 3000, 100))}
+    empty = (np.zeros(0, np.uint8), np.zeros(0, np.uint64), np.zeros(0, np.uint32))
+    want = {n: oracle.count(a, off, ln, pats)[0].tolist() for n, (a, off, ln) in arenas.items()}
+    want_cap = oracle.count(cap.bytes, cap.off, cap.len, pats)[0].tolist()
+    assert min(want[300]) > 0 and min(want_cap) > 0
+    sel = np.arange(300) % 3 == 1                                       # every third payload of the 300
+    a, off, ln = arenas[300]
+    s_off, s_arena = PM.gather_slots(a, off[sel], ln[sel])
+    want_sel = oracle.count(s_arena, s_off, ln[sel], pats)[0].tolist()
+    d300 = (torch.from_numpy(a).cuda(), torch.from_numpy(off.astype(np.int64)).cuda(), torch.from_numpy(ln.astype(np.int32)).cuda())
+    torch.cuda.synchronize()
+
+    def check(m, n_pkts, payload_bytes, counts, step):
+        assert m.arena_info() == (n_pkts, payload_bytes), step
+        for kernel in (KERNEL_AUTO, KERNEL_PACKED):
+            assert _scan(m, kernel).tolist() == counts, (step, kernel)
+
+    def upload(m, n, step):
+        m.load_arena(*arenas[n])
+        check(m, n, int(arenas[n][2].sum()), want[n], step)
+
+    def frames(m, step):
+        assert m.load_pcap_frames(pcap, "udp")[0] == int(cap.len.shape[0])
+        check(m, int(cap.len.shape[0]), int(cap.len.sum()), want_cap, step)
+
+    with GpuMatcher(0) as m, GpuMatcher(0) as src, GpuMatcher(0) as r:
+        for x in (m, src, r):
+            x.set_patterns(pats)
+        src.load_arena(*arenas[300])
+        upload(m, 300, "load 300")
+        m.attach_arena(*d300)                                           # borrowed: the context's own buffers are given back
+        check(m, 300, int(ln.sum()), want[300], "attach 300")
+        upload(m, 3000, "load 3000 (the buffers grow)")
+        upload(m, 100, "load 100 (the buffers are reused)")
+        frames(m, "frames")
+        assert m.load_selected(src, sel).tolist() == np.flatnonzero(sel).tolist()
+        check(m, int(sel.sum()), int(ln[sel].sum()), want_sel, "selected")
+        m.load_arena(*empty)
+        check(m, 0, 0, [0, 0], "empty")
+        upload(m, 300, "load 300 again")
+
+        big = arenas[3000]
+        _lib.gpu_check(_lib.gpu_lib().kmpgpu_reserve(r._ctx, big[0].size, 3000, os.path.getsize(pcap), 4096), "kmpgpu_reserve")
+        assert r.arena_info() == (0, 0)
+        for n in (300, 3000, 100):
+            upload(r, n, f"reserved, load {n}")
+        frames(r, "reserved, frames")
+        r.load_arena(*empty)
+        check(r, 0, 0, [0, 0], "reserved, empty")
+        upload(r, 300, "reserved, load 300 again")

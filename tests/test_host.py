@@ -328,6 +328,22 @@ def test_host_library_under_sanitizers(tmp_path, pcap, payloads):
         assert r.returncode == 0 and "sanitizer driver ok" in r.stdout, r.stderr[-2000:]
 
 
+def test_table_builder_under_sanitizers(tmp_path):
+    """csrc/kmp_tables.cpp (the fused pass's tables, host code without a HIP header) with plain g++ under ASan + UBSan, driven by
+    tests/tables_sanitizer_driver.cpp over the smallest pattern sets that reach each of its branches."""
+    import shutil
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "multithreading_string_matching_amd", "csrc")
+    exe = str(tmp_path / "tables_driver")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I" + os.path.join(root, "include"),
+           "-I" + csrc, os.path.join(root, "tests", "tables_sanitizer_driver.cpp"), os.path.join(csrc, "kmp_tables.cpp"), "-o", exe]
+    subprocess.run(cmd, check=True, capture_output=True, timeout=300)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    assert r.returncode == 0 and "tables driver ok" in r.stdout, (r.stdout + r.stderr)[-2000:]
+
+
 # ---- command lines: what needs no GPU (serial.c:33-51,59-63,91-95) -------------------------------
 def _run(prog, *args):
     return subprocess.run([os.path.join(_lib.BINDIR, prog), *args], capture_output=True, text=True, timeout=120)
