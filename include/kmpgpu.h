@@ -15,7 +15,7 @@
  *   E_k = L_k                                 whole payloads, KMPGPU_OPT_WHOLE_PAYLOAD = 1: a 0x00 is a text byte like any other
  *                                             (which matches nothing: patterns hold none).  Not the reference's behaviour.
  * Everything that counts, reports or marks matches -- kmpgpu_scan, kmpgpu_scan_enqueue, kmpgpu_scan_offsets,
- * kmpgpu_scan_packets, kmpgpu_scan_rules, with or without KMPGPU_PAT_NOCASE -- uses the E_k of the option's value at the time of the call.
+ * kmpgpu_scan_packets, kmpgpu_scan_rules, kmpgpu_scan_relations, with or without KMPGPU_PAT_NOCASE -- uses the E_k of the option's value at the time of the call.
  *
  * Conventions: plain pointers and sizes only; every function returns 0 or a negative KMPGPU_E*
  * code and never exits; kmpgpu_last_error() gives the text (per thread).  One context drives one GPU;
@@ -315,7 +315,7 @@ int  kmpgpu_scan_packets(kmpgpu_ctx *ctx, uint64_t *pkt_counts_out /* [n_pat] or
  *
  * kmpgpu_set_rules copies the rules and uploads them: rule r = terms[rule_off[r] .. rule_off[r + 1]), rule_off[n_rules + 1].  They
  * refer to the pattern set current at the call: no patterns set: KMPGPU_ESTATE; a later kmpgpu_set_patterns /
- * kmpgpu_set_patterns_flags drops them (the indices would mean something else).  rule_off[0] != 0, a decreasing rule_off, a rule
+ * kmpgpu_set_patterns_flags drops them (the indices would mean something else), and so does every kmpgpu_set_relations.  rule_off[0] != 0, a decreasing rule_off, a rule
  * without terms or a term whose index is >= n_pat: KMPGPU_EINVAL, and the rules set before stay in force.  n_rules == 0 clears
  * the rules.
  *
@@ -359,8 +359,8 @@ int  kmpgpu_scan_rules(kmpgpu_ctx *ctx, uint64_t *rule_pkt_counts_out /* [n_rule
  * Who does NOT: kmpgpu_scan and kmpgpu_scan_enqueue do not look at windows, and counts_out of the three calls above stays exactly
  * what kmpgpu_scan returns -- every match, in window or not.  So with windows set pkt_counts[i] == 0 no longer implies
  * counts[i] == 0, *n_found may be smaller than the sum of counts_out, and the context's own counters (KMPGPU_OPT_ACCUMULATE) are as
- * untouched as before.  Windowed counts, windows relative to a payload's end and windows between two patterns (distance / within)
- * do not exist.
+ * untouched as before.  Windowed counts and windows relative to a payload's end do not exist; a window between two
+ * patterns (distance / within) is a relation, kmpgpu_set_relations below, and a match has to be in window to enter one.
  * With no windows set, or with every window the default, every output of every call is bit-identical to what it is without this
  * call, and the kernels run what they run without it.
  *
@@ -377,6 +377,59 @@ int  kmpgpu_scan_rules(kmpgpu_ctx *ctx, uint64_t *rule_pkt_counts_out /* [n_rule
  * 97 tokens in the fused pass (a per-match load of the window), +25 % on text that matches at every offset -- and gets faster
  * where the windows drop matches (97 tokens with [0, 63]: 0.71 of the time without windows). */
 int  kmpgpu_set_windows(kmpgpu_ctx *ctx, const uint32_t *first /* [n_pat] */, const uint32_t *last /* [n_pat] */, uint32_t n_pat);
+
+/* Relations between two patterns: HOW FAR the start of one lies behind the end of the other ("Host:" at most 20 bytes behind the end of
+ * "GET "; Snort / Suricata: distance, within), decided on the device behind the marking pass of kmpgpu_scan_packets.  A rule "a and b"
+ * fires on any payload that holds both patterns anywhere; relation q = {a, b, dmin, dmax} fires where two of their matches lie as asked.
+ * Write (k, s, i) for a match of pattern i at start offset s of payload k that counts under the rules at the top of this file (E_k as
+ * KMPGPU_OPT_WHOLE_PAYLOAD says, overlapping starts, KMPGPU_PAT_NOCASE per pattern) AND is in window (kmpgpu_set_windows) -- exactly
+ * the matches that set hit[i][k] of kmpgpu_scan_packets.  With m_a the length of pattern a:
+ *     rel_hit[q][k]     = there are matches (k, sa, a) and (k, sb, b) with  dmin <= (int64)sb - ((int64)sa + m_a) <= dmax
+ *     rel_pkt_counts[q] = sum over k of rel_hit[q][k]      (payloads in which relation q holds)
+ *     any[k]            = OR over q of rel_hit[q][k]
+ *     counts[i]         = exactly what kmpgpu_scan returns, as in the sibling calls (every match, in window or not)
+ * dmin == INT32_MIN: no lower bound; dmax == INT32_MAX: no upper bound.  Snort's `distance:d` is dmin = d; `within:w` behind it is
+ * dmax = d + w - m_b (b has to END inside the w bytes), without a distance d = 0.  Negative values put b in front of a or let the two
+ * overlap (sb = sa is -m_a).  a == b is allowed and taken literally: two occurrences of one pattern, or one match paired with itself
+ * where -m_a lies in [dmin, dmax].  Relations may share patterns and may be identical; each index gets its own row.
+ * Layout as kmpgpu_scan_packets: W = ceil(n_pkts / 64) words per row, payload k is bit (k & 63) of word (k >> 6), LSB first; row q of
+ * rel_hits_out starts at rel_hits_out + q * W; the bits of index n_pkts and above are 0 in every output word.
+ *
+ * Relations as rule terms: while relations are set, relation q is term index n_pat + q of kmpgpu_set_rules and may carry
+ * KMPGPU_RULE_NOT; the bound that kmpgpu_set_rules checks is n_pat + n_rel (n_pat with none set), and kmpgpu_scan_rules runs the relation
+ * kernel between its marking pass and its rules kernel -- only then.  n_pat + n_rel < 2^31.
+ * NOT A CHAIN: every relation is decided on its own.  A rule of rel(a, b) and rel(b, c) asks for some pair (a, b) and some pair (b, c);
+ * the two b need not be the same match.  Snort's chained contents (each relative to the match before) are not expressed.
+ *
+ * kmpgpu_set_relations copies rel[n_rel] and uploads it (16 bytes per relation of device memory, owned by the context, freed by
+ * kmpgpu_destroy).  The relations belong to the pattern set current at the call: no patterns set: KMPGPU_ESTATE; a later
+ * kmpgpu_set_patterns / kmpgpu_set_patterns_flags drops them, as it drops rules and windows.  a or b >= n_pat, dmin > dmax, rel == NULL
+ * with n_rel > 0, n_pat + n_rel >= 2^31: KMPGPU_EINVAL, and the relations and rules set before stay in force.  EVERY successful call
+ * drops the rules, n_rel == 0 (which clears the relations; rel may be NULL) included: the rows their terms name have changed.  So the
+ * order is patterns, relations, rules.  Windows and KMPGPU_OPT_WHOLE_PAYLOAD stay pass state: they may change between two passes with
+ * nothing set again, and the relations follow them.
+ *
+ * kmpgpu_scan_relations: synchronous, on the context's stream.  The marking pass of kmpgpu_scan_packets (the same code), then the
+ * relation kernel instead of the pattern-level reduce.  Every output may be NULL: rel_pkt_counts_out[n_rel], any_out[W],
+ * rel_hits_out[n_rel * W], counts_out[n_pat].  Preconditions and errors as kmpgpu_scan_packets (streaming kernels only; an arena kept
+ * in place is packed once; with n_pkts == 0 every output is 0 and nothing is launched; the context's counters stay as they are); no
+ * relations set: KMPGPU_ESTATE.  *t (may be NULL): kernel_ms covers zeroing, scan launches and the relation kernel, launches counts
+ * it; under kmpgpu_profile_begin it is recorded behind the scan launches (in kmpgpu_scan_rules: in front of the rules kernel).
+ * With no relations set every output of every other call is bit-identical to what it is without these two calls, with the same
+ * launches and device buffers.
+ * Cost (the figures of tools/relations.py go to profiles/relations.txt): the relations are n_rel further rows of the hit matrix, (n_rel x W2 + n_rel)
+ * x 8 bytes, zeroed with it.  The kernel reads two words of the matrix per (relation, 64 payloads) and then only the payloads that
+ * hold both patterns: one wavefront per such payload finds E_k and sweeps the text 64 start offsets at a time, with no memory that
+ * grows with the payload.  Few candidates: a pass over the matrix.  Every payload a candidate of every relation: n_rel reads of the
+ * arena, a wavefront per payload -- the dense case of §3.15. */
+typedef struct kmpgpu_relation {
+    uint32_t a, b;            /* pattern indices (file order); b is measured from the END of a                 */
+    int32_t  dmin, dmax;      /* dmin <= start of b - end of a <= dmax; INT32_MIN / INT32_MAX: unbounded side */
+} kmpgpu_relation;
+int  kmpgpu_set_relations(kmpgpu_ctx *ctx, const kmpgpu_relation *rel /* [n_rel] */, uint32_t n_rel);
+int  kmpgpu_scan_relations(kmpgpu_ctx *ctx, uint64_t *rel_pkt_counts_out /* [n_rel] or NULL */, uint64_t *any_out /* [W] or NULL */,
+                           uint64_t *rel_hits_out /* [n_rel * W] or NULL */, uint64_t *counts_out /* [n_pat] or NULL: as kmpgpu_scan */,
+                           kmpgpu_timing *t /* or NULL */);
 
 /* The payloads a bitmap selects, compacted on the device into a packed arena that a second context owns: the consumer of any[] and of
  * the rows of kmpgpu_scan_packets / kmpgpu_scan_rules (the filter in front of a packet export -- only the selected bytes are downloaded

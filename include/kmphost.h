@@ -88,7 +88,31 @@ typedef struct kmp_rules {
     uint32_t *terms;      /* [off[n]]                                      */
 } kmp_rules;
 int  kmp_rules_parse(const char *path, uint32_t n_patterns, kmp_rules *out, char errbuf[KMP_RULES_ERRBUF]);
+/* The same with relations as terms (kmpgpu_set_relations): "r<q>" / "!r<q>", q < n_relations a decimal relation index (the order of
+ * the relation lines of kmp_relations_parse), is encoded as n_patterns + q, the row kmpgpu_set_rules knows it by.  A relation index
+ * >= n_relations: KMPHOST_EINVAL, "line N: ".  n_patterns + n_relations >= 2^31 (a term's bit 31 is KMP_RULE_NOT): KMPHOST_EINVAL
+ * before the file is opened, errbuf without a line number.  kmp_rules_parse is this with n_relations = 0, where "r3" is no term at all. */
+int  kmp_rules_parse_rel(const char *path, uint32_t n_patterns, uint32_t n_relations, kmp_rules *out, char errbuf[KMP_RULES_ERRBUF]);
 void kmp_rules_free(kmp_rules *r);
+
+/* ---- relations -------------------------------------------------------------------------------
+ * Not in the reference: the relations of kmpgpu_set_relations (include/kmpgpu.h) from a text file.  One relation per line,
+ *     <a> <b> <dmin> <dmax>
+ * four fields separated by blanks: two pattern indices (positions in the pattern file, 0-based) and the bounds on
+ * (start of b) - (end of a), decimal and possibly negative; '*' for <dmin> means no lower bound (INT32_MIN), for <dmax> no upper
+ * bound (INT32_MAX).  Blank lines and lines whose first non-blank character is '#' are skipped; relation index = order of the
+ * relation lines.  rel is what kmpgpu_set_relations takes (kmp_relation has the layout of kmpgpu_relation).
+ * KMPHOST_EIO: the file cannot be opened; KMPHOST_EINVAL: a field that is not a number (or does not fit 32 bits), a line of fewer or
+ * more than four fields, an index >= n_patterns, dmin > dmax -- errbuf then starts with "line N: " (N counts every line of the
+ * file, from 1). */
+#define KMP_RELATIONS_ERRBUF 256
+typedef struct kmp_relation { uint32_t a, b; int32_t dmin, dmax; } kmp_relation;
+typedef struct kmp_relations {
+    uint32_t      n;      /* number of relations                           */
+    kmp_relation *rel;    /* [n]                                           */
+} kmp_relations;
+int  kmp_relations_parse(const char *path, uint32_t n_patterns, kmp_relations *out, char errbuf[KMP_RELATIONS_ERRBUF]);
+void kmp_relations_free(kmp_relations *r);
 
 /* ---- offset windows --------------------------------------------------------------------------
  * Not in the reference: the windows of kmpgpu_set_windows (include/kmpgpu.h) from a text file.  One window per line,

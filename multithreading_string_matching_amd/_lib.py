@@ -24,6 +24,9 @@ KMP_SYNTH_MAX_NEEDLE = 100
 KMP_PCAP_ERRBUF = 256
 KMP_RULES_ERRBUF = 256
 KMP_WINDOWS_ERRBUF = 256
+KMP_RELATIONS_ERRBUF = 256
+REL_NO_MIN = -(1 << 31)    # kmpgpu_relation.dmin == INT32_MIN: no lower bound
+REL_NO_MAX = (1 << 31) - 1  # kmpgpu_relation.dmax == INT32_MAX: no upper bound
 RULE_NOT = 0x80000000      # KMPGPU_RULE_NOT / KMP_RULE_NOT: the term's pattern must not be in the payload
 
 u8p = C.POINTER(C.c_uint8)
@@ -67,6 +70,16 @@ class Rules(C.Structure):
     _fields_ = [("n", C.c_uint32), ("off", u32p), ("terms", u32p)]
 
 
+class Relation(C.Structure):
+    """kmpgpu_relation (include/kmpgpu.h) = kmp_relation (include/kmphost.h)."""
+    _fields_ = [("a", C.c_uint32), ("b", C.c_uint32), ("dmin", C.c_int32), ("dmax", C.c_int32)]
+
+
+class Relations(C.Structure):
+    """kmp_relations (include/kmphost.h)."""
+    _fields_ = [("n", C.c_uint32), ("rel", C.POINTER(Relation))]
+
+
 class Arena(C.Structure):
     """kmp_arena (include/kmphost.h)."""
     _fields_ = [
@@ -104,7 +117,10 @@ HOST_API = {
     "kmp_patterns_parse": (C.c_int, [u8p, C.c_size_t, C.POINTER(Patterns)]),
     "kmp_patterns_free": (None, [C.POINTER(Patterns)]),
     "kmp_rules_parse": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(Rules), C.c_char_p]),
+    "kmp_rules_parse_rel": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(Rules), C.c_char_p]),
     "kmp_rules_free": (None, [C.POINTER(Rules)]),
+    "kmp_relations_parse": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(Relations), C.c_char_p]),
+    "kmp_relations_free": (None, [C.POINTER(Relations)]),
     "kmp_windows_parse": (C.c_int, [C.c_char_p, C.c_uint32, u32p, u32p, C.c_char_p]),
     "kmp_failure_table": (None, [u8p, C.c_uint32, i32p]),
     "kmp_arena_from_pcap": (C.c_int, [C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Arena), C.c_char_p]),
@@ -163,6 +179,8 @@ GPU_API = {
     "kmpgpu_set_rules": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint32]),
     "kmpgpu_scan_rules": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
     "kmpgpu_set_windows": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint32]),
+    "kmpgpu_set_relations": (C.c_int, [C.c_void_p, C.POINTER(Relation), C.c_uint32]),
+    "kmpgpu_scan_relations": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
     "kmpgpu_load_selected": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, u64p]),
     "kmpgpu_synth_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(SynthParams)]),
     "kmpgpu_fixed_index": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32]),

@@ -26,6 +26,12 @@
  * index among the rule lines).  One of the two without the other, or a rules file that does not parse: message on stderr, exit 1,
  * before any GPU work.  Both go together with KMPGPU_NOCASE, KMPGPU_WHOLE_PAYLOAD, KMPGPU_DEVICE_EXTRACT and KMPGPU_PACKETS_FILE.
  *
+ * KMPGPU_RELATIONS_FILE=<relations>, together with KMPGPU_RULES_FILE and KMPGPU_ALERTS_FILE: distance / within relations between two
+ * patterns (kmpgpu_set_relations; the file format is kmp_relations_parse's, kmphost.h: "<a> <b> <dmin> <dmax>" per line, '*' for an
+ * unbounded side), set on every shard's context before the rules, whose file may then name relation q as "r<q>" / "!r<q>"
+ * (kmp_rules_parse_rel).  A relations file that does not parse, or the variable without the other two: message on stderr, exit 1,
+ * before any GPU work.  stdout is what it is without the variable.
+ *
  * KMPGPU_WINDOWS_FILE=<windows>: per-pattern offset windows (kmpgpu_set_windows; the file format is kmp_windows_parse's, kmphost.h:
  * "<pattern index> <first> <last>" per line, '*' for no upper bound) on every shard's context.  They take effect on the files written
  * for KMPGPU_OFFSETS_FILE, KMPGPU_PACKETS_FILE and KMPGPU_RULES_FILE + KMPGPU_ALERTS_FILE: only the matches that start inside their
@@ -121,6 +127,8 @@ typedef struct shard_job {
 
 /* KMPGPU_WINDOWS_FILE: the windows every shard's context gets behind its patterns (NULL: none) */
 static uint32_t *g_win_first, *g_win_last;
+/* KMPGPU_RELATIONS_FILE: the relations every shard's context gets behind its patterns, before any rule is set (n == 0: none) */
+static kmp_relations g_relations;
 
 static int whole_payload_env(void)
 {
@@ -158,6 +166,8 @@ static void *shard_load(void *arg)
     if (kmpgpu_init(&j->ctx, j->device)) return shard_fail(j, "kmpgpu_init");
     if (set_patterns_env(j->ctx, j->pp, j->pats->len, j->pats->n)) return shard_fail(j, "kmpgpu_set_patterns");
     if (g_win_first && kmpgpu_set_windows(j->ctx, g_win_first, g_win_last, j->pats->n)) return shard_fail(j, "kmpgpu_set_windows");
+    _Static_assert(sizeof(kmp_relation) == sizeof(kmpgpu_relation), "kmp_relation has the layout of kmpgpu_relation");
+    if (g_relations.n && kmpgpu_set_relations(j->ctx, (const kmpgpu_relation *)g_relations.rel, g_relations.n)) return shard_fail(j, "kmpgpu_set_relations");
     if (j->frames) {
         /* only the bytes this shard's frames span are uploaded (kmpgpu_load_frames) */
         if (kmpgpu_load_frames(j->ctx, j->frames->bytes, j->frames->nbytes, j->frames->off + j->lo, j->frames->caplen + j->lo, j->cnt, j->tcp,
@@ -231,9 +241,22 @@ int main(int argc, char *argv[])
         fprintf(stderr, "KMPGPU_RULES_FILE and KMPGPU_ALERTS_FILE go together: %s is not set\n", rules_path ? "KMPGPU_ALERTS_FILE" : "KMPGPU_RULES_FILE");
         exit(1);
     }
+    /* the relations, which the rules may name */
+    const char *relations_path = getenv("KMPGPU_RELATIONS_FILE");
+    if (relations_path && relations_path[0]) {
+        if (!rules_path || !alerts_path) {
+            fprintf(stderr, "KMPGPU_RELATIONS_FILE goes together with KMPGPU_RULES_FILE and KMPGPU_ALERTS_FILE: %s is not set\n", rules_path ? "KMPGPU_ALERTS_FILE" : "KMPGPU_RULES_FILE");
+            exit(1);
+        }
+        char relations_err[KMP_RELATIONS_ERRBUF];
+        if (kmp_relations_parse(relations_path, pats.n, &g_relations, relations_err)) {
+            fprintf(stderr, "error reading relations file %s: %s\n", relations_path, relations_err);
+            exit(1);
+        }
+    }
     if (rules_path) {
         char rules_err[KMP_RULES_ERRBUF];
-        if (kmp_rules_parse(rules_path, pats.n, &rules, rules_err)) {
+        if (kmp_rules_parse_rel(rules_path, pats.n, g_relations.n, &rules, rules_err)) {
             fprintf(stderr, "error reading rules file %s: %s\n", rules_path, rules_err);
             exit(1);
         }
@@ -520,6 +543,7 @@ int main(int argc, char *argv[])
     kmp_frames_free(&frames);
     kmp_patterns_free(&pats);
     kmp_rules_free(&rules);
+    kmp_relations_free(&g_relations);
     free(g_win_first); free(g_win_last);
     return 0;
 }

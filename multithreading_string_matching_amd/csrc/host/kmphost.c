@@ -439,8 +439,18 @@ static int rules_push(uint32_t **v, size_t *n, size_t *cap, uint32_t x)
 
 int kmp_rules_parse(const char *path, uint32_t n_patterns, kmp_rules *out, char errbuf[KMP_RULES_ERRBUF])
 {
+    return kmp_rules_parse_rel(path, n_patterns, 0, out, errbuf);
+}
+
+int kmp_rules_parse_rel(const char *path, uint32_t n_patterns, uint32_t n_relations, kmp_rules *out, char errbuf[KMP_RULES_ERRBUF])
+{
     memset(out, 0, sizeof *out);
     if (errbuf) errbuf[0] = 0;
+    /* a term is a row below 2^31: bit 31 is KMP_RULE_NOT (kmpgpu_set_relations refuses such a set too) */
+    if ((uint64_t)n_patterns + n_relations >= (1ull << 31)) {
+        if (errbuf) snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations do not fit the 2^31 rows a term can name", n_patterns, n_relations);
+        return KMPHOST_EINVAL;
+    }
     FILE *fp = fopen(path, "rb");
     if (!fp) {
         if (errbuf) snprintf(errbuf, KMP_RULES_ERRBUF, "%s: %s", path, strerror(errno));
@@ -460,16 +470,26 @@ int kmp_rules_parse(const char *path, uint32_t n_patterns, kmp_rules *out, char 
             uint32_t neg = 0;
             uint64_t v = 0;
             if (*p == '!') { neg = KMP_RULE_NOT; p++; }
+            /* r<q>: relation q, where the caller has relations (without any the token is no term at all, as it always was) */
+            const int is_rel = n_relations && p < end && *p == 'r';
+            if (is_rel) p++;
             const char *digits = p;
             while (p < end && *p >= '0' && *p <= '9') { if (v < (1ull << 40)) v = v * 10 + (uint64_t)(*p - '0'); p++; }
             const char *stop = p;
             while (stop < end && !is_c_space((uint8_t)*stop)) stop++;   /* the whole token, for the message */
-            if (p == digits && neg && stop == p) {
+            if (p == digits && neg && stop == p && !is_rel) {
                 if (errbuf) snprintf(errbuf, KMP_RULES_ERRBUF, "line %zu: '!' without a pattern index", lineno);
                 rc = KMPHOST_EINVAL;
             } else if (p == digits || stop != p) {
-                if (errbuf) snprintf(errbuf, KMP_RULES_ERRBUF, "line %zu: '%.*s' is not a pattern index", lineno, (int)(stop - tok > 64 ? 64 : stop - tok), tok);
+                if (errbuf) snprintf(errbuf, KMP_RULES_ERRBUF, "line %zu: '%.*s' is not a pattern index%s", lineno, (int)(stop - tok > 64 ? 64 : stop - tok), tok,
+                                     n_relations ? " or r<relation index>" : "");
                 rc = KMPHOST_EINVAL;
+            } else if (is_rel) {
+                if (v >= n_relations) {
+                    if (errbuf) snprintf(errbuf, KMP_RULES_ERRBUF, "line %zu: relation index %llu, but there are %u relations", lineno, (unsigned long long)v, n_relations);
+                    rc = KMPHOST_EINVAL;
+                } else
+                    rc = rules_push(&out->terms, &n_terms, &cap_terms, (n_patterns + (uint32_t)v) | neg);
             } else if (v >= n_patterns) {
                 if (errbuf) snprintf(errbuf, KMP_RULES_ERRBUF, "line %zu: pattern index %llu, but there are %u patterns", lineno, (unsigned long long)v, n_patterns);
                 rc = KMPHOST_EINVAL;
@@ -495,6 +515,105 @@ void kmp_rules_free(kmp_rules *r)
 {
     if (!r) return;
     free(r->off); free(r->terms);
+    memset(r, 0, sizeof *r);
+}
+
+/* ============================ relations ================================================= */
+
+/* One field of a relations line at *pp: a decimal number, with a leading '-' where neg_ok, that fits lo..hi, or (star != 0) a lone '*' =
+ * star.  Leaves *pp behind the field and the blanks that follow it; on failure *tok / *tok_len name the field for the message. */
+static int relations_field(const char **pp, const char *end, int neg_ok, int64_t lo, int64_t hi, int64_t star, int64_t *out, const char **tok, int *tok_len)
+{
+    const char *p = *pp;
+    *tok = p;
+    const int neg = neg_ok && p < end && *p == '-';
+    if (neg) p++;
+    int64_t v = 0;
+    const char *digits = p;
+    while (p < end && *p >= '0' && *p <= '9') { if (v < ((int64_t)1 << 40)) v = v * 10 + (int64_t)(*p - '0'); p++; }
+    const char *stop = p;
+    while (stop < end && !is_c_space((uint8_t)*stop)) stop++;           /* the whole token, for the message */
+    *tok_len = (int)(stop - *tok > 64 ? 64 : stop - *tok);
+    if (neg) v = -v;
+    int ok = p > digits && stop == p && v >= lo && v <= hi;
+    if (!ok && star && stop == *tok + 1 && **tok == '*') { v = star; ok = 1; }
+    while (stop < end && is_c_space((uint8_t)*stop)) stop++;
+    *pp = stop;
+    *out = v;
+    return ok;
+}
+
+int kmp_relations_parse(const char *path, uint32_t n_patterns, kmp_relations *out, char errbuf[KMP_RELATIONS_ERRBUF])
+{
+    memset(out, 0, sizeof *out);
+    if (errbuf) errbuf[0] = 0;
+    FILE *fp = fopen(path, "rb");
+    if (!fp) {
+        if (errbuf) snprintf(errbuf, KMP_RELATIONS_ERRBUF, "%s: %s", path, strerror(errno));
+        return KMPHOST_EIO;
+    }
+    char *line = NULL;
+    size_t line_cap = 0, lineno = 0, n = 0, cap = 0;
+    ssize_t got;
+    int rc = KMPHOST_OK;
+    while (!rc && (got = getline(&line, &line_cap, fp)) >= 0) {
+        lineno++;
+        const char *p = line, *end = line + got;
+        while (p < end && is_c_space((uint8_t)*p)) p++;
+        if (p == end || *p == '#') continue;                           /* blank line, comment */
+        static const char *const what[4] = {"a pattern index", "a pattern index", "a lower bound or '*'", "an upper bound or '*'"};
+        int64_t f[4] = {0, 0, 0, 0};
+        for (int k = 0; k < 4 && !rc; k++) {
+            const char *tok;
+            int tl;
+            if (p == end) {
+                if (errbuf) snprintf(errbuf, KMP_RELATIONS_ERRBUF, "line %zu: %d of the four fields <a> <b> <dmin> <dmax>", lineno, k);
+                rc = KMPHOST_EINVAL;
+            } else if (!relations_field(&p, end, k >= 2, k >= 2 ? INT32_MIN : 0, k >= 2 ? INT32_MAX : 0xFFFFFFFFll,
+                                        k == 2 ? INT32_MIN : k == 3 ? INT32_MAX : 0, &f[k], &tok, &tl)) {
+                if (errbuf) snprintf(errbuf, KMP_RELATIONS_ERRBUF, "line %zu: '%.*s' is not %s", lineno, tl, tok, what[k]);
+                rc = KMPHOST_EINVAL;
+            }
+        }
+        if (rc) break;
+        if (p != end) {
+            if (errbuf) snprintf(errbuf, KMP_RELATIONS_ERRBUF, "line %zu: more than the four fields <a> <b> <dmin> <dmax>", lineno);
+            rc = KMPHOST_EINVAL;
+        } else if (f[0] >= n_patterns || f[1] >= n_patterns) {
+            if (errbuf) snprintf(errbuf, KMP_RELATIONS_ERRBUF, "line %zu: pattern index %lld, but there are %u patterns", lineno,
+                                 (long long)(f[0] >= n_patterns ? f[0] : f[1]), n_patterns);
+            rc = KMPHOST_EINVAL;
+        } else if (f[2] > f[3]) {
+            if (errbuf) snprintf(errbuf, KMP_RELATIONS_ERRBUF, "line %zu: lower bound %lld lies above upper bound %lld", lineno, (long long)f[2], (long long)f[3]);
+            rc = KMPHOST_EINVAL;
+        } else {
+            if (n == cap) {
+                const size_t nc = cap ? cap * 2 : 64;
+                kmp_relation *nv = (kmp_relation *)realloc(out->rel, nc * sizeof *nv);
+                if (!nv) { rc = KMPHOST_ENOMEM; break; }
+                out->rel = nv; cap = nc;
+            }
+            out->rel[n].a = (uint32_t)f[0]; out->rel[n].b = (uint32_t)f[1];
+            out->rel[n].dmin = (int32_t)f[2]; out->rel[n].dmax = (int32_t)f[3];
+            n++;
+        }
+    }
+    free(line);
+    fclose(fp);
+    if (!rc && n > 0x7FFFFFFFull) rc = KMPHOST_EINVAL;
+    if (rc) {
+        if (rc == KMPHOST_ENOMEM && errbuf) snprintf(errbuf, KMP_RELATIONS_ERRBUF, "out of memory");
+        kmp_relations_free(out);
+        return rc;
+    }
+    out->n = (uint32_t)n;
+    return KMPHOST_OK;
+}
+
+void kmp_relations_free(kmp_relations *r)
+{
+    if (!r) return;
+    free(r->rel);
     memset(r, 0, sizeof *r);
 }
 

@@ -1,4 +1,5 @@
-/* kmp_launch.h -- launch entry points of kmp_scan_*.hip / kmp_prep.hip / kmp_fold.hip / kmp_marks.hip / kmp_rules.hip / kmp_select.hip, used
+/* kmp_launch.h -- launch entry points of kmp_scan_*.hip / kmp_prep.hip / kmp_fold.hip / kmp_marks.hip / kmp_rules.hip / kmp_relations.hip /
+ * kmp_select.hip, used
  * by the C-ABI layer (kmpgpu.hip), which alone decides what is launched; the tables kmp_launch_scan_multi takes come from kmp_tables.h. */
 #ifndef KMP_LAUNCH_H
 #define KMP_LAUNCH_H
@@ -114,6 +115,17 @@ hipError_t kmp_launch_marks_reduce(const unsigned long long *marks, uint32_t n_r
 hipError_t kmp_launch_rules(const unsigned long long *marks, uint64_t stride, uint64_t n_pkts, const uint4 *heads, const uint4 *quads,
                             uint32_t n_rules, unsigned long long *rule_rows, unsigned long long *rule_counts, unsigned long long *any,
                             hipStream_t st);
+/* kmp_relations.hip: the relations of kmpgpu_set_relations, decided for the payloads that hold both patterns.  marks[..][stride] is the hit
+ * matrix the marking pass has just filled for n_pkts payloads (rows = pattern indices); relations[q] = {a | A << 31, b | B << 31, dmin,
+ * dmax} with a, b < 2^31 pattern indices (checked by the caller) and A / B set where that pattern's bytes are compared in `fold`, the
+ * folded copy of the arena (a pattern of the nocase set; patterns[i].pat is folded then), instead of `arena`.  windows: {first, last} per
+ * pattern index or NULL; whole: E_k = L_k.  Word j < ceil(n_pkts / 64) of rows[q][stride] is written for every q (the caller zeroes the
+ * padding word of an odd row), a relation's set bits are added to rel_counts[q] and ORed into any[]; the caller zeroes those two.  At most
+ * max_blocks blocks, grid-stride. */
+hipError_t kmp_launch_relations(const unsigned long long *marks, uint64_t stride, uint64_t n_pkts, const uint4 *relations, uint32_t n_rel,
+                                const kmp_pattern_dev *patterns, const uint8_t *arena, const uint8_t *fold, const uint64_t *pkt_off,
+                                const uint32_t *pkt_len, const void *windows, bool whole, uint32_t max_blocks, unsigned long long *rows,
+                                unsigned long long *rel_counts, unsigned long long *any, hipStream_t st);
 hipError_t kmp_launch_fixed_index(uint64_t *pkt_off, uint32_t *pkt_len, uint64_t n, uint32_t len, uint64_t stride,
                                   hipStream_t st);
 /* kmp_select.hip (kmpgpu_load_selected): the payloads of an index of n whose bit is set in select[ceil(n / 64)] (payload k: bit k & 63 of

@@ -162,7 +162,7 @@ struct kmpgpu_ctx {
     size_t              h_counts_cap = 0;
     unsigned long long *h_small = nullptr;            /* pinned, 16 words: where the loaders read small device results back (a copy to pageable
                                                          memory goes through the runtime's blocking staging path) */
-    unsigned long long *d_marks = nullptr;            /* kmpgpu_scan_packets: hit matrix [n_pat][stride], then pkt_counts[n_pat], any[stride], counts[n_pat] */
+    unsigned long long *d_marks = nullptr;            /* the marking pass: hit matrix [n_pat + n_rel][stride], then pkt_counts[n_pat], any[stride], counts[n_pat], rel_pkt_counts[n_rel] */
     uint64_t            marks_cap = 0;                /* words */
     /* kmpgpu_set_rules / kmpgpu_scan_rules: the rules as the kernel reads them (kmp_launch.h, kmp_launch_rules) and the results */
     uint32_t            n_rules = 0;
@@ -172,6 +172,12 @@ struct kmpgpu_ctx {
     /* kmpgpu_set_windows: {first, last} per pattern index as the emitters read it (kmp_launch.h, emit_windows); NULL: no windows set, or
      * every one of them the default -- the emitting passes then run as they do without */
     uint2              *d_windows = nullptr;
+    /* kmpgpu_set_relations: {a, b, dmin, dmax} per relation as the relation kernel reads it (kmp_launch.h, kmp_launch_relations); relation
+     * q is row n_pat + q of the hit matrix and term n_pat + q of a rule.  pat_fold[i]: pattern i is one of sets[1], its bytes are compared
+     * in d_fold */
+    uint32_t            n_rel = 0;
+    uint4              *d_relations = nullptr;
+    std::vector<uint8_t> pat_fold;
 
     /* options */
     int mode = 0, blocks_per_cu = 0 /* auto */, depth = 0 /* auto */, nontemporal = 1, kernel_sel = 0, fused = 2 /* auto */, accumulate = 0, repack = 1;
@@ -328,6 +334,13 @@ void drop_rules(kmpgpu_ctx *c)
 /* so do the windows */
 void drop_windows(kmpgpu_ctx *c) { free_buffer(&c->d_windows); }
 
+/* ... and the relations */
+void drop_relations(kmpgpu_ctx *c)
+{
+    free_buffer(&c->d_relations);
+    c->n_rel = 0;
+}
+
 /* the patterns and all that is built on them */
 void release_patterns(kmpgpu_ctx *c)
 {
@@ -337,6 +350,8 @@ void release_patterns(kmpgpu_ctx *c)
     free_pattern_set(c->sets[1]);
     drop_rules(c);                                 /* their indices meant these patterns */
     drop_windows(c);                               /* ... and so did the windows' */
+    drop_relations(c);                             /* ... and the relations' */
+    c->pat_fold.clear();
 }
 
 /* The context's own arena / offset / length buffers. */
@@ -1041,6 +1056,8 @@ int kmpgpu_set_patterns_flags(kmpgpu_ctx *c, const uint8_t *const *pat, const ui
     HIP_TRY(hipStreamSynchronize(c->stream));
     release_patterns(c);
     c->n_pat = n_pat;
+    c->pat_fold.assign(n_pat, 0);
+    for (uint32_t i : members[1]) c->pat_fold[i] = 1;
     const size_t np = n_pat ? n_pat : 1;
     HIP_TRY(hipMalloc(&c->d_patterns, np * sizeof(kmp_pattern_dev)));
     HIP_TRY(hipMalloc(&c->d_counts, np * sizeof(unsigned long long)));
@@ -1496,7 +1513,8 @@ namespace {
 struct MarkPass {
     bool empty = false;
     uint64_t W = 0, stride = 0, mat = 0;          /* words per row as the caller sees them / on the device (even); words of the matrix */
-    unsigned long long *d_mat = nullptr, *d_pc = nullptr, *d_any = nullptr, *d_cnt = nullptr;    /* [n_pat][stride], [n_pat], [stride], [n_pat] */
+    unsigned long long *d_mat = nullptr, *d_pc = nullptr, *d_any = nullptr, *d_cnt = nullptr;    /* [n_pat + n_rel][stride], [n_pat], [stride], [n_pat] */
+    unsigned long long *d_rel = nullptr, *d_relc = nullptr;     /* the relations' rows inside d_mat (row n_pat on), [n_rel] */
     uint32_t launches = 0;
 };
 
@@ -1519,13 +1537,15 @@ int marking_pass(kmpgpu_ctx *c, const char *who, MarkPass *p)
         const int rr = repack_arena(c);
         if (rr) return rr;
     }
-    /* one device buffer, grown like the others: [marks n_pat x stride][pkt_counts n_pat][any stride][counts n_pat] */
-    const uint64_t mat = (uint64_t)np * stride;
-    const uint64_t words = mat + np + stride + np;
+    /* one device buffer, grown like the others: [marks (n_pat + n_rel) x stride][pkt_counts n_pat][any stride][counts n_pat]
+     * [rel_pkt_counts n_rel]; the scan kernels mark rows 0 .. n_pat - 1, the relation kernel writes the rows behind them */
+    const uint64_t mat = ((uint64_t)np + c->n_rel) * stride;
+    const uint64_t words = mat + np + stride + np + c->n_rel;
     hipError_t e = grow_buffer(&c->d_marks, &c->marks_cap, words, EIGHTH);
     if (e != hipSuccess) return alloc_fail(e, "%s: the hit matrix (%llu bytes) could not be allocated", who, (unsigned long long)(words * 8u));
     p->stride = stride; p->mat = mat;
     p->d_mat = c->d_marks; p->d_pc = p->d_mat + mat; p->d_any = p->d_pc + np; p->d_cnt = p->d_any + stride;
+    p->d_rel = p->d_mat + (uint64_t)np * stride; p->d_relc = p->d_cnt + np;
     HIP_TRY(hipEventRecord(c->ev[0], c->stream));
     /* zeroed before every pass: the bits of an earlier (larger) arena must not leak into this one */
     HIP_TRY(hipMemsetAsync(p->d_mat, 0, (size_t)words * sizeof(unsigned long long), c->stream));
@@ -1541,6 +1561,19 @@ hipError_t download_rows(kmpgpu_ctx *c, uint64_t *dst, const unsigned long long 
 {
     if (stride == W) return hipMemcpyAsync(dst, src, (size_t)(rows * W) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream);
     return hipMemcpy2DAsync(dst, W * sizeof(uint64_t), src, stride * sizeof(uint64_t), W * sizeof(uint64_t), rows, hipMemcpyDeviceToHost, c->stream);
+}
+
+/* The relation kernel behind a marking pass: rows n_pat .. of the matrix, their popcounts into p.d_relc and their OR into p.d_any (all
+ * zeroed by the pass; kmpgpu_scan_rules has no other use for that any[]).  One launch, recorded by a running profile. */
+int enqueue_relations(kmpgpu_ctx *c, const MarkPass &p)
+{
+    hipEvent_t e1;
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_relations(p.d_mat, p.stride, c->n_pkts, c->d_relations, c->n_rel, c->d_patterns, c->d_arena, c->d_fold, c->d_off,
+                                 c->d_len, c->d_windows, c->whole_payload != 0, (uint32_t)c->cu_count * 8u, p.d_rel, p.d_relc, p.d_any,
+                                 c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    return KMPGPU_OK;
 }
 
 /* waits for the pass and its downloads; kernel_ms = ev[0]..ev[1], d2h_ms = ev[1]..ev[2] */
@@ -1606,8 +1639,9 @@ int kmpgpu_set_rules(kmpgpu_ctx *c, const uint32_t *rule_off, const uint32_t *te
         ord.clear();
         for (int neg = 0; neg < 2; neg++)
             for (uint32_t j = rule_off[r]; j < rule_off[r + 1]; j++) {
-                if ((terms[j] & ~KMPGPU_RULE_NOT) >= c->n_pat)
-                    return fail(KMPGPU_EINVAL, "kmpgpu_set_rules: rule %u: term %u names pattern %u of %u", r, j - rule_off[r], terms[j] & ~KMPGPU_RULE_NOT, c->n_pat);
+                if ((terms[j] & ~KMPGPU_RULE_NOT) >= c->n_pat + c->n_rel)           /* (n_pat + n_rel < 2^31: kmpgpu_set_relations) */
+                    return fail(KMPGPU_EINVAL, "kmpgpu_set_rules: rule %u: term %u names row %u of %u patterns + %u relations", r, j - rule_off[r],
+                                terms[j] & ~KMPGPU_RULE_NOT, c->n_pat, c->n_rel);
                 if (((terms[j] & KMPGPU_RULE_NOT) != 0) == (neg != 0)) ord.push_back(terms[j]);
             }
         /* filled up with a term that is loaded at the same time: a repeated term changes nothing */
@@ -1695,6 +1729,11 @@ int kmpgpu_scan_rules(kmpgpu_ctx *c, uint64_t *rule_pkt_counts_out, uint64_t *an
     unsigned long long *d_rows = c->d_rule_out, *d_rc = d_rows + rows, *d_any = d_rc + nr;
     /* the kernel adds to the counts and ORs into any; it writes every word of the rows itself */
     HIP_TRY(hipMemsetAsync(d_rc, 0, (size_t)(nr + p.stride) * sizeof(unsigned long long), c->stream));
+    /* relations set: their rows of the matrix first, the rules read them as they read the patterns' */
+    if (c->n_rel) {
+        const int rr = enqueue_relations(c, p);
+        if (rr) return rr;
+    }
     hipEvent_t e1;
     HIP_TRY(profile_launch(c, &e1));
     HIP_TRY(kmp_launch_rules(p.d_mat, p.stride, c->n_pkts, c->d_rule_heads, c->d_rule_quads, c->n_rules, d_rows, d_rc, d_any, c->stream));
@@ -1704,6 +1743,66 @@ int kmpgpu_scan_rules(kmpgpu_ctx *c, uint64_t *rule_pkt_counts_out, uint64_t *an
     if (any_out) HIP_TRY(hipMemcpyAsync(any_out, d_any, p.W * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, p.d_cnt, np * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     if (rule_hits_out) HIP_TRY(download_rows(c, rule_hits_out, d_rows, p.W, p.stride, nr));
+    return finish_marking(c, p.launches + (c->n_rel ? 2u : 1u), t);
+}
+
+int kmpgpu_set_relations(kmpgpu_ctx *c, const kmpgpu_relation *rel, uint32_t n_rel)
+{
+    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_set_relations: ctx is NULL");
+    if (!c->d_patterns || c->n_pat == 0) return fail(KMPGPU_ESTATE, "kmpgpu_set_relations: no patterns set");
+    HIP_TRY(hipSetDevice(c->device));
+    static_assert(sizeof(kmpgpu_relation) == sizeof(uint4), "a relation is a 16-byte record");
+    uint4 *d_rel = nullptr;
+    if (n_rel) {
+        if (!rel) return fail(KMPGPU_EINVAL, "kmpgpu_set_relations: rel is NULL");
+        if ((uint64_t)c->n_pat + n_rel >= (1ull << 31))
+            return fail(KMPGPU_EINVAL, "kmpgpu_set_relations: %u patterns + %u relations do not fit the 2^31 rows a rule term can name", c->n_pat, n_rel);
+        std::vector<uint4> host(n_rel);
+        for (uint32_t q = 0; q < n_rel; q++) {
+            const kmpgpu_relation &r = rel[q];
+            if (r.a >= c->n_pat || r.b >= c->n_pat)
+                return fail(KMPGPU_EINVAL, "kmpgpu_set_relations: relation %u names pattern %u of %u", q, r.a >= c->n_pat ? r.a : r.b, c->n_pat);
+            if (r.dmin > r.dmax) return fail(KMPGPU_EINVAL, "kmpgpu_set_relations: relation %u: dmin %d lies above dmax %d", q, r.dmin, r.dmax);
+            /* bit 31: the pattern's bytes are compared in the folded copy of the arena */
+            host[q] = make_uint4(r.a | ((uint32_t)c->pat_fold[r.a] << 31), r.b | ((uint32_t)c->pat_fold[r.b] << 31), (uint32_t)r.dmin, (uint32_t)r.dmax);
+        }
+        hipError_t e = hipMalloc((void **)&d_rel, host.size() * sizeof(uint4));
+        if (e == hipSuccess) e = hipMemcpyAsync(d_rel, host.data(), host.size() * sizeof(uint4), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      /* (host is a local) */
+        if (e != hipSuccess) {
+            free_buffer(&d_rel);
+            return alloc_fail(e, "kmpgpu_set_relations: the relations could not be uploaded");
+        }
+    } else HIP_TRY(hipStreamSynchronize(c->stream));
+    drop_relations(c);
+    drop_rules(c);                                 /* the rows their terms named are no longer the same, whatever was set or cleared */
+    c->d_relations = d_rel; c->n_rel = n_rel;
+    return KMPGPU_OK;
+}
+
+int kmpgpu_scan_relations(kmpgpu_ctx *c, uint64_t *rel_pkt_counts_out, uint64_t *any_out, uint64_t *rel_hits_out, uint64_t *counts_out, kmpgpu_timing *t)
+{
+    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_scan_relations: ctx is NULL");
+    if (!c->d_patterns || c->n_pat == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan_relations: no patterns set");
+    if (c->n_rel == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan_relations: no relations set");
+    MarkPass p;
+    const int rc = marking_pass(c, "kmpgpu_scan_relations", &p);
+    if (rc) return rc;
+    const size_t np = c->n_pat, nq = c->n_rel;
+    if (p.empty) {
+        /* nothing to scan: no relation holds anywhere, and there are no bit words */
+        if (rel_pkt_counts_out) memset(rel_pkt_counts_out, 0, nq * sizeof(uint64_t));
+        if (counts_out) memset(counts_out, 0, np * sizeof(uint64_t));
+        if (t) { *t = kmpgpu_timing{}; }
+        return KMPGPU_OK;
+    }
+    const int rr = enqueue_relations(c, p);
+    if (rr) return rr;
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    if (rel_pkt_counts_out) HIP_TRY(hipMemcpyAsync(rel_pkt_counts_out, p.d_relc, nq * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (any_out) HIP_TRY(hipMemcpyAsync(any_out, p.d_any, p.W * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, p.d_cnt, np * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (rel_hits_out) HIP_TRY(download_rows(c, rel_hits_out, p.d_rel, p.W, p.stride, nq));
     return finish_marking(c, p.launches + 1u, t);
 }
 

@@ -69,6 +69,7 @@ class GpuMatcher:
         self.patterns: List[bytes] = []
         self.rules: list = []      # (all_of, none_of) per rule, as set_rules took them
         self.windows: list = []    # (first, last) per pattern as set_windows took them (last None: unbounded), [] = none
+        self.relations: list = []  # (a, b, dmin, dmax) per relation as set_relations took them (None: unbounded side), [] = none
         self._keep = None          # objects whose device memory the context borrows
         self._comm = None          # the GpuComm this matcher is a rank of: closed before the context
 
@@ -96,6 +97,7 @@ class GpuMatcher:
         self.patterns = list(patterns)
         self.rules = []            # the library drops its rules with the pattern set they referred to
         self.windows = []          # ... and its windows
+        self.relations = []        # ... and its relations
 
     def set_rules(self, rules) -> None:
         """Content rules over the current patterns (kmpgpu_set_rules): a sequence of (all_of, none_of) pattern-index sequences;
@@ -104,12 +106,38 @@ class GpuMatcher:
         for a, b in rules:
             for i in a + b:
                 if not 0 <= i < _lib.RULE_NOT:
-                    raise ValueError(f"rule term {i}: not a pattern index")
+                    raise ValueError(f"rule term {i}: not a pattern index (or rel(q))")
         off = np.zeros(len(rules) + 1, dtype=np.uint32)
         off[1:] = np.cumsum([len(a) + len(b) for a, b in rules])
         terms = np.array([t for a, b in rules for t in a + [i | _lib.RULE_NOT for i in b]] or [0], dtype=np.uint32)
         gpu_check(self._g.kmpgpu_set_rules(self._ctx, off.ctypes.data_as(u32p), terms.ctypes.data_as(u32p), len(rules)), "kmpgpu_set_rules")
         self.rules = rules
+
+    def set_relations(self, relations) -> None:
+        """Distance / within relations between two of the current patterns (kmpgpu_set_relations): a sequence of (a, b, dmin, dmax),
+        relation q holding in a payload with an in-window match of a at sa and one of b at sb where dmin <= sb - (sa + len(a)) <= dmax;
+        None for dmin or dmax leaves that side unbounded.  None or an empty sequence clears the relations.  Every successful call
+        drops the rules, as the library does: set the relations first, then the rules, whose terms may be rel(q)."""
+        relations = [(int(a), int(b), None if lo is None else int(lo), None if hi is None else int(hi)) for a, b, lo, hi in (relations or [])]
+        for a, b, lo, hi in relations:
+            if not (0 <= a <= 0xFFFFFFFF and 0 <= b <= 0xFFFFFFFF):
+                raise ValueError(f"relation ({a}, {b}, {lo}, {hi}): pattern indices are 32-bit")
+            if not all(x is None or _lib.REL_NO_MIN <= x <= _lib.REL_NO_MAX for x in (lo, hi)):
+                raise ValueError(f"relation ({a}, {b}, {lo}, {hi}): bounds are 32-bit")
+        arr = (_lib.Relation * max(len(relations), 1))()
+        for r, (a, b, lo, hi) in zip(arr, relations):
+            r.a, r.b = a, b
+            r.dmin = _lib.REL_NO_MIN if lo is None else lo
+            r.dmax = _lib.REL_NO_MAX if hi is None else hi
+        gpu_check(self._g.kmpgpu_set_relations(self._ctx, arr if relations else None, len(relations)), "kmpgpu_set_relations")
+        self.relations = relations
+        self.rules = []            # the library drops its rules with the rows they referred to
+
+    def rel(self, q: int) -> int:
+        """The term of relation q in set_rules: it is row len(patterns) + q of the hit matrix."""
+        if not 0 <= q < len(self.relations):
+            raise ValueError(f"rel({q}): {len(self.relations)} relations are set")
+        return len(self.patterns) + q
 
     def set_windows(self, windows) -> None:
         """Offset windows of the current patterns (kmpgpu_set_windows): one (first, last) per pattern, last None = unbounded;
@@ -327,6 +355,28 @@ class GpuMatcher:
                "any": np.unpackbits(any_w[:W].view(np.uint8), bitorder="little")[:n_pkts].astype(bool)}
         if hits:
             bits = np.unpackbits(hit_w.reshape(nr, W).view(np.uint8), axis=1, bitorder="little") if nr * W else np.zeros((nr, 0), np.uint8)
+            out["hits"] = bits[:, :n_pkts].astype(bool)
+        return out
+
+    def scan_relations(self, hits: bool = False) -> dict:
+        """In which payloads which relations hold (kmpgpu_scan_relations): the marking pass of scan_packets and the relation kernel.
+        ``rel_pkt_counts`` (uint64[n_rel]) payloads in which relation q holds, ``any`` (bool[n_pkts]) some relation holds in payload k,
+        ``counts`` (uint64[n_pat]) as scan(), ``timing``; with hits=True also ``hits`` (bool[n_rel, n_pkts])."""
+        n, nq = len(self.patterns), len(self.relations)
+        n_pkts, _ = self.arena_info()
+        W = (n_pkts + 63) // 64
+        rel_counts = np.zeros(max(nq, 1), dtype=np.uint64)
+        counts = np.zeros(max(n, 1), dtype=np.uint64)
+        any_w = np.zeros(max(W, 1), dtype=np.uint64)
+        hit_w = np.zeros((nq, W) if hits and nq * W else 1, dtype=np.uint64)
+        t = Timing()
+        gpu_check(self._g.kmpgpu_scan_relations(self._ctx, rel_counts.ctypes.data, any_w.ctypes.data,
+                                                hit_w.ctypes.data if hits else None, counts.ctypes.data, C.byref(t)),
+                  "kmpgpu_scan_relations")
+        out = {"rel_pkt_counts": rel_counts[:nq], "counts": counts[:n], "timing": t,
+               "any": np.unpackbits(any_w[:W].view(np.uint8), bitorder="little")[:n_pkts].astype(bool)}
+        if hits:
+            bits = np.unpackbits(hit_w.reshape(nq, W).view(np.uint8), axis=1, bitorder="little") if nq * W else np.zeros((nq, 0), np.uint8)
             out["hits"] = bits[:, :n_pkts].astype(bool)
         return out
 
