@@ -17,14 +17,15 @@ from conftest import DATA
 
 pytestmark = pytest.mark.gpu
 
-# torch first: see the header comment of tests/test_gpu_parity.py
+from gpu_support import gm, reset  # noqa: E402,F401  (torch first)
+
 import torch  # noqa: E402
 
 import multithreading_string_matching_amd as K  # noqa: E402
 from multithreading_string_matching_amd import _lib  # noqa: E402
 from multithreading_string_matching_amd.matcher import (  # noqa: E402
     KERNEL_AUTO, KERNEL_FLAT, KERNEL_GENERAL, KERNEL_PACKED, MODE_AUTOMATON, MODE_FILTER, OPT_ACCUMULATE, OPT_BLOCKS_PER_CU, OPT_FUSED,
-    OPT_FUSED_UNIT, OPT_KERNEL, OPT_MODE, GpuMatcher)
+    OPT_FUSED_UNIT, OPT_KERNEL, OPT_MODE)
 
 KERNEL_FUSED = 100          # test-only alias: auto kernel selection + the fused multi-pattern pass
 # (mode, kernel) as in test_gpu_parity.VARIANTS
@@ -33,23 +34,10 @@ VARIANTS = ((MODE_FILTER, KERNEL_AUTO), (MODE_FILTER, KERNEL_FLAT), (MODE_FILTER
 IDX16 = 0xFFFF              # the largest pattern index a launch (gridDim.y) or a classed record (16 bits) holds
 
 
-@pytest.fixture(scope="module")
-def gm():
-    m = GpuMatcher(0)
-    yield m
-    m.close()
-
-
 def _select(gm, mode, kernel):
     gm.set_option(OPT_MODE, mode)
     gm.set_option(OPT_KERNEL, KERNEL_AUTO if kernel == KERNEL_FUSED else kernel)
     gm.set_option(OPT_FUSED, 1 if kernel == KERNEL_FUSED else 2 if kernel == KERNEL_AUTO else 0)
-
-
-def _restore(gm):
-    for key, value in ((OPT_MODE, MODE_FILTER), (OPT_KERNEL, KERNEL_AUTO), (OPT_FUSED, 2), (OPT_ACCUMULATE, 0), (OPT_BLOCKS_PER_CU, 0),
-                       (OPT_FUSED_UNIT, 0)):
-        gm.set_option(key, value)
 
 
 def _check_records(recs, arena, patterns, want, sample=400):
@@ -189,7 +177,7 @@ def test_many_patterns_past_the_16_bit_index(gm, oracle, tmp_path):
             assert int(recs["pattern"].max()) > IDX16
             _check_records(recs, arena, pats, want)
     finally:
-        _restore(gm)
+        reset(gm)
 
     # the command lines, with a pattern file of more than 65 536 tokens mostly cut out of the capture's payloads
     cap = K.HostArena.from_pcap(os.path.join(DATA, "udp_1000.pcap"), "udp")
@@ -304,7 +292,7 @@ def test_sliced_reduce_accumulates(gm, oracle):
             assert np.bincount(recs["pattern"].astype(np.int64), minlength=len(B_PATTERNS)).tolist() == w.tolist()
             assert gm.counts_read().tolist() == running.tolist(), fused
     finally:
-        _restore(gm)
+        reset(gm)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -406,4 +394,4 @@ def test_fused_pool_with_riders_and_classed_groups(gm, oracle):
         gm.load_arena(arena)
         del d_arena, d_off, d_len
     finally:
-        _restore(gm)
+        reset(gm)

@@ -1,13 +1,12 @@
 """Case-insensitive patterns (KMPGPU_PAT_NOCASE, kmpgpu_set_patterns_flags) on a real MI355X.
 
-The checker is the CPU oracle, unchanged, applied to host-folded inputs: for a nocase pattern p,
-count(payloads, p) == oracle.count(fold(payloads), fold(p)) with fold = lowercase ASCII A-Z only.
+The checker is the CPU oracle, unchanged, applied to host-folded inputs (oracle_counts_arena of tests/match_model.py): for a
+nocase pattern p, count(payloads, p) == oracle.count(fold(payloads), fold(p)).  Offset records come from the host model there.
 
 Run on a real MI355X:  python -m pytest tests/test_gpu_nocase.py -m gpu
 """
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,51 +15,18 @@ from conftest import DATA
 
 pytestmark = pytest.mark.gpu
 
-# torch first, as tests/test_gpu_parity.py explains: its wheel carries its own ROCm runtime libraries
-import torch  # noqa: E402,F401
+from gpu_support import VARIANTS, gm, reset, run_cli, strip_elapsed  # noqa: E402,F401  (torch first)
 
+import match_model as MM  # noqa: E402
 import multithreading_string_matching_amd as K  # noqa: E402
 from multithreading_string_matching_amd import _lib  # noqa: E402
 from multithreading_string_matching_amd.matcher import (  # noqa: E402
-    KERNEL_AUTO, KERNEL_FLAT, KERNEL_GENERAL, KERNEL_PACKED, MODE_AUTOMATON, MODE_FILTER, OPT_FUSED, OPT_KERNEL, OPT_MODE, PAT_NOCASE,
-    GpuMatcher)
+    KERNEL_AUTO, KERNEL_FLAT, KERNEL_GENERAL, KERNEL_PACKED, OPT_ACCUMULATE, OPT_FUSED, OPT_KERNEL, OPT_MODE, OPT_REPACK, PAT_NOCASE)
 
-OPT_ACCUMULATE, OPT_REPACK = 6, 7
 # letters of both cases, the bytes next to 'A'..'Z' / 'a'..'z', and their bit-7 twins (0xC1 / 0xE1 are 'A' / 'a' + 0x80)
 ALPHABET = b"aAbBcCzZ@[`{" + bytes([0xC1, 0xE1, 0xDA, 0xFA])
 FIXTURE_KEYS = ["udp.pcap:udp", "udp_1000.pcap:udp", "big_udp.pcap:udp", "very_big_udp.pcap:udp",
                 "tcp.pcap:tcp", "tcp.pcap:udp", "udp.pcap:tcp", "udp_1000.pcap:tcp"]
-
-
-def fold(a):
-    """ASCII A-Z -> a-z, every other byte as it is (numpy arrays and bytes)."""
-    if isinstance(a, (bytes, bytearray)):
-        return bytes(a).lower()                      # bytes.lower() touches ASCII A-Z only
-    a = np.array(a, dtype=np.uint8, copy=True)
-    a[(a >= 0x41) & (a <= 0x5A)] += 0x20
-    return a
-
-
-def expected(oracle, arena, off, ln, pats, nocase):
-    """Per-index counts: case-sensitive patterns on the arena, nocase ones on the folded arena with the folded pattern."""
-    if isinstance(nocase, bool):
-        nocase = [nocase] * len(pats)
-    cs, _ = oracle.count(arena, off, ln, pats)
-    fo, _ = oracle.count(fold(arena), off, ln, [fold(p) for p in pats])
-    return [int(fo[i]) if nocase[i] else int(cs[i]) for i in range(len(pats))]
-
-
-def expected_matches(payloads, pats, nocase):
-    out = []
-    for k, text in enumerate(payloads):
-        E = text.index(0) if 0 in text else len(text)
-        for i, p in enumerate(pats):
-            t, q = (fold(text), fold(p)) if nocase[i] else (text, p)
-            s = t.find(q, 0, E)
-            while s != -1:
-                out.append((k, s, i))
-                s = t.find(q, s + 1, E)
-    return sorted(out)
 
 
 def random_case(rng, p):
@@ -96,24 +62,6 @@ def patterns_from(rng, payloads, lengths):
     return pats
 
 
-@pytest.fixture(scope="module")
-def gm():
-    m = GpuMatcher(0)
-    yield m
-    m.close()
-
-
-def reset(gm):
-    gm.set_option(OPT_MODE, MODE_FILTER)
-    gm.set_option(OPT_KERNEL, KERNEL_AUTO)
-    gm.set_option(OPT_FUSED, 2)
-    gm.set_option(OPT_REPACK, 1)
-    gm.set_option(OPT_ACCUMULATE, 0)
-
-
-# (name, mode, kernel, fused)
-VARIANTS = [("auto", MODE_FILTER, KERNEL_AUTO, 2), ("flat", MODE_FILTER, KERNEL_FLAT, 0), ("packed", MODE_FILTER, KERNEL_PACKED, 0),
-            ("general", MODE_FILTER, KERNEL_GENERAL, 0), ("automaton", MODE_AUTOMATON, KERNEL_GENERAL, 0), ("fused", MODE_FILTER, KERNEL_AUTO, 1)]
 LENGTHS = [1, 2, 3, 4, 8, 9, 16, 17, 40, 99]
 
 
@@ -125,8 +73,8 @@ def test_every_kernel_family(gm, oracle, uniform, variant):
     payloads = random_payloads(rng, 600, length=1500 if uniform else None)
     pats = patterns_from(rng, payloads, LENGTHS) + [b"A", b"@", b"\xc1", b"Z"]     # 1-byte patterns ride along with the fused pass
     arena = K.HostArena.from_payloads(payloads)
-    want = expected(oracle, arena.bytes, arena.off, arena.len, pats, True)
-    want_cs = expected(oracle, arena.bytes, arena.off, arena.len, pats, False)
+    want = MM.oracle_counts_arena(oracle, arena.bytes, arena.off, arena.len, pats, True)
+    want_cs = MM.oracle_counts_arena(oracle, arena.bytes, arena.off, arena.len, pats, False)
     assert want != want_cs                           # the input tells the two apart
     reset(gm)
     gm.set_option(OPT_MODE, mode); gm.set_option(OPT_KERNEL, kernel); gm.set_option(OPT_FUSED, fused)
@@ -146,7 +94,7 @@ def test_classed_groups(gm, oracle, n_pats):
     payloads = random_payloads(rng, 800)
     pats = patterns_from(rng, payloads, [rng.randrange(3, 12) for _ in range(n_pats // 2)])[:n_pats]
     arena = K.HostArena.from_payloads(payloads)
-    want = expected(oracle, arena.bytes, arena.off, arena.len, pats, True)
+    want = MM.oracle_counts_arena(oracle, arena.bytes, arena.off, arena.len, pats, True)
     reset(gm)
     gm.set_patterns(pats, nocase=True)
     gm.load_arena(arena)
@@ -167,7 +115,7 @@ def test_mixed_flags_in_one_set(gm, oracle):
     pats = [b"Host", b"host", b"HOST", b"hOsT", b"Host", b"host", b"GET", b"get", b"user-agent", b"@[`{", b"12", b"\xc1\xda", b"H", b"t"]
     flags = [False, True, True, True, True, False, False, True, True, True, True, True, True, False]
     arena = K.HostArena.from_payloads(payloads)
-    want = expected(oracle, arena.bytes, arena.off, arena.len, pats, flags)
+    want = MM.oracle_counts_arena(oracle, arena.bytes, arena.off, arena.len, pats, flags)
     assert want[0] != want[1] and want[1] == want[2] == want[3] == want[4]
     reset(gm)
     gm.load_arena(arena)
@@ -183,7 +131,7 @@ def test_mixed_flags_in_one_set(gm, oracle):
     got_cs, t_cs = gm.scan()
     gm.set_patterns(plain, nocase=True)
     got_nc, t_nc = gm.scan()
-    assert got_nc.tolist() == got_cs.tolist() == expected(oracle, arena.bytes, arena.off, arena.len, plain, False)
+    assert got_nc.tolist() == got_cs.tolist() == MM.oracle_counts_arena(oracle, arena.bytes, arena.off, arena.len, plain, False)
     assert t_nc.launches == t_cs.launches
 
 
@@ -191,10 +139,10 @@ def test_mixed_flags_in_one_set(gm, oracle):
 def test_strings_txt_nocase_still_fuses(gm, oracle, tokens, key):
     pcap, mode = key.split(":")
     arena = K.HostArena.from_pcap(os.path.join(DATA, pcap), mode)
-    want = expected(oracle, arena.bytes, arena.off, arena.len, tokens, True)
+    want = MM.oracle_counts_arena(oracle, arena.bytes, arena.off, arena.len, tokens, True)
     reset(gm)
-    gm.load_arena(fold(arena.bytes), arena.off, arena.len)      # the host-folded formulation: folded arena, folded tokens, case-sensitive
-    gm.set_patterns([fold(t) for t in tokens])
+    gm.load_arena(MM.fold(arena.bytes), arena.off, arena.len)      # the host-folded formulation: folded arena, folded tokens, case-sensitive
+    gm.set_patterns([MM.fold(t) for t in tokens])
     got_f, t_f = gm.scan()
     gm.load_arena(arena)
     gm.set_patterns(tokens, nocase=True)
@@ -209,9 +157,9 @@ def test_offsets_mixed_set(gm, oracle, uniform):
     payloads = random_payloads(rng, 400, length=1500 if uniform else None)
     pats = [b"aB", b"ab", b"AbC", b"@[", b"\xc1a", b"zZzZ", b"b", b"A", b"Ab"] + patterns_from(rng, payloads, [5, 17])
     flags = [True, False, True, True, True, True, False, True, True] + [i % 2 == 0 for i in range(4)]
-    want = expected_matches(payloads, pats, flags)
+    want = sorted(MM.records(MM.starts(payloads, pats, nocase=flags)))
     arena = K.HostArena.from_payloads(payloads)
-    counts_want = expected(oracle, arena.bytes, arena.off, arena.len, pats, flags)
+    counts_want = MM.oracle_counts_arena(oracle, arena.bytes, arena.off, arena.len, pats, flags)
     assert len(want) == sum(counts_want)
     reset(gm)
     gm.set_patterns(pats, nocase=flags)
@@ -220,7 +168,7 @@ def test_offsets_mixed_set(gm, oracle, uniform):
         gm.set_option(OPT_KERNEL, kernel); gm.set_option(OPT_FUSED, fused)
         got, found, counts = gm.scan_offsets(len(want) + 10)
         assert found == len(want) and counts.tolist() == counts_want, (kernel, fused)
-        assert sorted((int(r["packet"]), int(r["offset"]), int(r["pattern"])) for r in got) == want, (kernel, fused)
+        assert MM.triples(got) == want, (kernel, fused)
     reset(gm)
 
 
@@ -233,15 +181,15 @@ def test_arena_untouched_and_no_stale_fold(gm, oracle):
     reset(gm)
     gm.set_patterns(pats, nocase=True)
     gm.load_arena(a)
-    assert gm.scan()[0].tolist() == expected(oracle, a.bytes, a.off, a.len, pats, True)
+    assert gm.scan()[0].tolist() == MM.oracle_counts_arena(oracle, a.bytes, a.off, a.len, pats, True)
     got, off, ln = gm.arena_download()                 # the original bytes, not the folded copy
     end = int(off[-1]) + max(16, (int(ln[-1]) + 15) // 16 * 16)
     assert np.array_equal(got[:end], np.asarray(a.bytes)[:end])
     gm.set_patterns(pats)
-    assert gm.scan()[0].tolist() == expected(oracle, a.bytes, a.off, a.len, pats, False)
+    assert gm.scan()[0].tolist() == MM.oracle_counts_arena(oracle, a.bytes, a.off, a.len, pats, False)
     gm.set_patterns(pats, nocase=True)
     gm.load_arena(b)                                   # same size: into the same device buffers
-    assert gm.scan()[0].tolist() == expected(oracle, b.bytes, b.off, b.len, pats, True)
+    assert gm.scan()[0].tolist() == MM.oracle_counts_arena(oracle, b.bytes, b.off, b.len, pats, True)
 
 
 def test_borrowed_arena_rewritten_and_reattached(gm, oracle):
@@ -264,7 +212,7 @@ def test_borrowed_arena_rewritten_and_reattached(gm, oracle):
         d_len[: a.n_pkts] = torch.from_numpy(a.len.astype(np.int32))
         torch.cuda.synchronize()
         gm.attach_arena(d_arena, d_off[: a.n_pkts], d_len[: a.n_pkts])
-        want = expected(oracle, a.bytes, a.off, a.len, pats, True)
+        want = MM.oracle_counts_arena(oracle, a.bytes, a.off, a.len, pats, True)
         for fused in (0, 1):
             gm.set_option(OPT_FUSED, fused)
             assert gm.scan()[0].tolist() == want
@@ -294,7 +242,7 @@ def test_non_packed_arena_in_place(gm, oracle):
         arena[int(off[k]):int(off[k]) + len(p)] = np.frombuffer(p, dtype=np.uint8)
     ln = np.array([len(p) for p in payloads], dtype=np.uint32)
     pats = [b"aB", b"abCab", b"b", b"CABcabCABcab", b"@a"]
-    want = expected(oracle, arena, off, ln, pats, True)
+    want = MM.oracle_counts_arena(oracle, arena, off, ln, pats, True)
     reset(gm)
     gm.set_patterns(pats, nocase=True)
     for repack in (1, 0):
@@ -307,8 +255,8 @@ def test_non_packed_arena_in_place(gm, oracle):
             gm.set_option(OPT_KERNEL, KERNEL_AUTO)
             recs, found, counts = gm.scan_offsets(sum(want) + 4)         # packs the arena on demand: folded again
             assert found == sum(want) and counts.tolist() == want
-            assert sorted((int(r["packet"]), int(r["offset"]), int(r["pattern"])) for r in recs) == \
-                expected_matches(payloads, pats, [True] * len(pats))
+            assert MM.triples(recs) == \
+                sorted(MM.records(MM.starts(payloads, pats, nocase=[True] * len(pats))))
             assert gm.scan()[0].tolist() == want
     reset(gm)
 
@@ -320,7 +268,7 @@ def test_accumulate_over_batches(gm, oracle):
     want = [0] * len(pats)
     for bt in batches:
         a = K.HostArena.from_payloads(bt)
-        want = [x + y for x, y in zip(want, expected(oracle, a.bytes, a.off, a.len, pats, True))]
+        want = [x + y for x, y in zip(want, MM.oracle_counts_arena(oracle, a.bytes, a.off, a.len, pats, True))]
     reset(gm)
     gm.set_patterns(pats, nocase=True)
     gm.set_option(OPT_ACCUMULATE, 1)
@@ -340,7 +288,7 @@ def test_device_extraction(gm, oracle, tokens, key):
     reset(gm)
     gm.set_patterns(tokens, nocase=True)
     gm.load_pcap_frames(path, mode)
-    assert gm.scan()[0].tolist() == expected(oracle, host.bytes, host.off, host.len, tokens, True)
+    assert gm.scan()[0].tolist() == MM.oracle_counts_arena(oracle, host.bytes, host.off, host.len, tokens, True)
 
 
 def test_api_flags(gm, oracle, tokens):
@@ -364,7 +312,7 @@ def test_api_flags(gm, oracle, tokens):
         assert g.kmpgpu_set_patterns_flags(gm._ctx, ptrs, lens, flags, n) == -2        # KMPGPU_EINVAL
         assert b"flag" in g.kmpgpu_last_error()
     gm.set_patterns(tokens, nocase=True)                                                # the context is still usable
-    assert gm.scan()[0].tolist() == expected(oracle, arena.bytes, arena.off, arena.len, tokens, True)
+    assert gm.scan()[0].tolist() == MM.oracle_counts_arena(oracle, arena.bytes, arena.off, arena.len, tokens, True)
     with pytest.raises(ValueError):
         gm.set_patterns(tokens, nocase=[True])
 
@@ -372,12 +320,6 @@ def test_api_flags(gm, oracle, tokens):
 # ------------------------------------------------------------------------------------------------
 # the drop-in command lines: KMPGPU_NOCASE=1
 # ------------------------------------------------------------------------------------------------
-def _strip_elapsed(out):
-    lines = out.splitlines(keepends=True)
-    assert lines and lines[-1].startswith("Elapsed time = ") and lines[-1].endswith(" seconds\n")
-    return "".join(lines[:-1])
-
-
 CLI_RUNS = [("serial", [], {}), ("openmp_data", ["2"], {}), ("openmp_task", ["2"], {"KMPGPU_DEVICE_EXTRACT": "0", "KMPGPU_BATCH_BYTES": "65536"}),
             ("openmp_task", ["1"], {"KMPGPU_DEVICE_EXTRACT": "1", "KMPGPU_BATCH_BYTES": "65536"}), ("serial", [], {"KMPGPU_DEVICE_EXTRACT": "1"})]
 
@@ -388,23 +330,19 @@ def test_cli_nocase(oracle, tokens, key, run):
     prog, extra, env_extra = run
     pcap, mode = key.split(":")
     host = K.HostArena.from_pcap(os.path.join(DATA, pcap), mode)
-    want = expected(oracle, host.bytes, host.off, host.len, tokens, True)
-    assert want != expected(oracle, host.bytes, host.off, host.len, tokens, False)
-    env = dict(os.environ, KMPGPU_NOCASE="1", **env_extra)
-    r = subprocess.run([os.path.join(_lib.BINDIR, prog), os.path.join(DATA, pcap), os.path.join(DATA, "strings.txt"), *extra, mode],
-                       capture_output=True, text=True, timeout=300, env=env)
+    want = MM.oracle_counts_arena(oracle, host.bytes, host.off, host.len, tokens, True)
+    assert want != MM.oracle_counts_arena(oracle, host.bytes, host.off, host.len, tokens, False)
+    r = run_cli(prog, pcap, extra=extra, env_extra=dict(env_extra, KMPGPU_NOCASE="1"), mode=mode, scrub=None)
     assert r.returncode == 0, r.stderr
-    assert _strip_elapsed(r.stdout) == K.format_report(tokens, want)
+    assert strip_elapsed(r.stdout) == K.format_report(tokens, want)
 
 
 def test_cli_offsets_file_nocase(oracle, tokens, tmp_path):
     host = K.HostArena.from_pcap(os.path.join(DATA, "udp_1000.pcap"), "udp")
     payloads = [host.payload(k) for k in range(host.n_pkts)]
-    want = expected_matches(payloads, tokens, [True] * len(tokens))
+    want = sorted(MM.records(MM.starts(payloads, tokens, nocase=[True] * len(tokens))))
     out = tmp_path / "offsets.csv"
-    env = dict(os.environ, KMPGPU_NOCASE="1", KMPGPU_OFFSETS_FILE=str(out))
-    r = subprocess.run([os.path.join(_lib.BINDIR, "serial"), os.path.join(DATA, "udp_1000.pcap"), os.path.join(DATA, "strings.txt"), "udp"],
-                       capture_output=True, text=True, timeout=300, env=env)
+    r = run_cli("serial", env_extra={"KMPGPU_NOCASE": "1", "KMPGPU_OFFSETS_FILE": str(out)}, scrub=None)
     assert r.returncode == 0, r.stderr
     got = sorted(tuple(int(x) for x in line.split(",")) for line in out.read_text().splitlines() if line and line[0].isdigit())
     assert got == want

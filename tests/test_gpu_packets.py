@@ -1,14 +1,12 @@
 """Which payloads hold which patterns (kmpgpu_scan_packets, GpuMatcher.scan_packets) on a real MI355X.
 
-The expectation is computed on the host, payload by payload: hit[i][k] = pattern i occurs in payload k before its first
-0x00 (E_k), a KMPGPU_PAT_NOCASE pattern on host-folded text (as tests/test_gpu_nocase.py does); the totals come from
-the CPU oracle.  Every output of the call is compared exactly: pkt_counts, any, the hit matrix and counts.
+The expectation is the hit matrix of the host model (tests/match_model.py); the totals come from the CPU oracle.  Every output of
+the call is compared exactly: pkt_counts, any, the hit matrix and counts.
 
 Run on a real MI355X:  python -m pytest tests/test_gpu_packets.py -m gpu
 """
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,47 +15,17 @@ from conftest import DATA
 
 pytestmark = pytest.mark.gpu
 
-# torch first, as tests/test_gpu_parity.py explains: its wheel carries its own ROCm runtime libraries
+from gpu_support import KERNELS, gm, load, reset, run_cli, strip_elapsed  # noqa: E402,F401  (torch first)
+
 import torch  # noqa: E402
 
+import match_model as MM  # noqa: E402
 import multithreading_string_matching_amd as K  # noqa: E402
 from multithreading_string_matching_amd import _lib  # noqa: E402
 from multithreading_string_matching_amd.matcher import (  # noqa: E402
-    KERNEL_AUTO, KERNEL_FLAT, KERNEL_GENERAL, KERNEL_PACKED, MODE_AUTOMATON, MODE_FILTER, OPT_FUSED, OPT_KERNEL, OPT_MODE, GpuMatcher)
+    KERNEL_AUTO, KERNEL_GENERAL, MODE_AUTOMATON, OPT_ACCUMULATE, OPT_FUSED, OPT_KERNEL, OPT_MODE, OPT_REPACK, GpuMatcher)
 
-OPT_ACCUMULATE, OPT_REPACK = 6, 7
 ALPHABET = b"abcdAB"
-
-
-def fold(b):
-    return bytes(b).lower()                          # ASCII A-Z only
-
-
-def text_end(t):
-    z = t.find(b"\0")
-    return len(t) if z < 0 else z
-
-
-def host_hits(payloads, pats, nocase=None):
-    """bool[n_pat, n_pkts]: pattern i occurs in payload k[0:E_k] (folded for a nocase pattern)."""
-    nocase = nocase or [False] * len(pats)
-    hits = np.zeros((len(pats), len(payloads)), dtype=bool)
-    fp = [fold(p) if nc else p for p, nc in zip(pats, nocase)]
-    for k, text in enumerate(payloads):
-        t = text[:text_end(text)]
-        tf = fold(t)
-        for i, p in enumerate(fp):
-            hits[i, k] = p in (tf if nocase[i] else t)
-    return hits
-
-
-def host_counts(oracle, payloads, pats, nocase=None):
-    nocase = nocase or [False] * len(pats)
-    cs = oracle.count_payloads(payloads, pats)
-    if not any(nocase):
-        return [int(x) for x in cs]
-    fo = oracle.count_payloads([fold(t) for t in payloads], [fold(p) for p in pats])
-    return [int(fo[i]) if nocase[i] else int(cs[i]) for i in range(len(pats))]
 
 
 def check(res, hits, counts):
@@ -70,25 +38,6 @@ def check(res, hits, counts):
     assert res["counts"].tolist() == list(counts)
     pc, c = res["pkt_counts"], res["counts"]
     assert (pc <= c).all() and ((pc == 0) == (c == 0)).all()
-
-
-@pytest.fixture(scope="module")
-def gm():
-    m = GpuMatcher(0)
-    yield m
-    m.close()
-
-
-def reset(gm):
-    gm.set_option(OPT_MODE, MODE_FILTER)
-    gm.set_option(OPT_KERNEL, KERNEL_AUTO)
-    gm.set_option(OPT_FUSED, 2)
-    gm.set_option(OPT_REPACK, 1)
-    gm.set_option(OPT_ACCUMULATE, 0)
-
-
-# (name, kernel, fused): the automatic choice (fused for multi-pattern sets) and the two streaming kernels on their own
-KERNELS = [("auto", KERNEL_AUTO, 2), ("flat", KERNEL_FLAT, 0), ("packed", KERNEL_PACKED, 0)]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -129,7 +78,7 @@ def _sub(rng, payloads, m):
     """a piece of some payload's text (so that it matches), or random bytes"""
     for _ in range(200):
         t = rng.choice(payloads)
-        t = t[:text_end(t)]
+        t = t[:MM.text_end(t)]
         if len(t) >= m:
             s = rng.randrange(len(t) - m + 1)
             return t[s:s + m]
@@ -161,21 +110,6 @@ def _pattern_set(rng, name, payloads, tokens):
     return [p.replace(b"\0", b"a") for p in pats], None
 
 
-def _load(gm, payloads, slots):
-    if slots is None:
-        gm.load_arena(K.HostArena.from_payloads(payloads))
-        return None
-    # a borrowed arena (attach_arena) keeps its dirty padding: the kernels take each payload's end from the index
-    ln = np.array([len(t) for t in payloads], dtype=np.uint32)
-    size = np.array([len(s) for s in slots], dtype=np.uint64)
-    off = np.concatenate([[0], np.cumsum(size)[:-1]]).astype(np.uint64)
-    arena = np.frombuffer(b"".join(slots) + b"\0" * 64, dtype=np.uint8).copy()
-    keep = (torch.from_numpy(arena).cuda(), torch.from_numpy(off.astype(np.int64)).cuda(), torch.from_numpy(ln.astype(np.int32)).cuda())
-    torch.cuda.synchronize()
-    gm.attach_arena(*keep)
-    return keep
-
-
 SINGLE_LENGTHS = [1, 2, 3, 4, 16, 17, 99]
 ARENAS = ["uniform", "mixed", "dirty", "nul", "empty"]
 SETS = ["singles", "riders", "tokens", "classed", "dups", "nocase"]
@@ -192,11 +126,11 @@ def test_random_arenas(gm, oracle, tokens, kind, pset):
     else:
         payloads, slots = _arena(rng, kind, plant)
         sets = [_pattern_set(rng, pset, payloads, tokens)]
-    keep = _load(gm, payloads, slots)
+    keep = load(gm, payloads, slots)
     try:
         for pats, nocase in sets:
-            hits = host_hits(payloads, pats, nocase)
-            counts = host_counts(oracle, payloads, pats, nocase)
+            hits = MM.hits(MM.starts(payloads, pats, nocase=nocase))
+            counts = MM.oracle_counts(oracle, payloads, pats, nocase)
             gm.set_patterns(pats, nocase=nocase if nocase else False)
             for name, kernel, fused in KERNELS:
                 reset(gm)
@@ -224,8 +158,8 @@ def test_random_arenas(gm, oracle, tokens, kind, pset):
 def test_pcap_fixtures(gm, oracle, tokens, pcap, mode):
     arena = K.HostArena.from_pcap(os.path.join(DATA, pcap), mode)
     payloads = [arena.payload(k) for k in range(arena.n_pkts)]
-    hits = host_hits(payloads, tokens)
-    counts = host_counts(oracle, payloads, tokens)
+    hits = MM.hits(MM.starts(payloads, tokens), len(tokens))
+    counts = MM.oracle_counts(oracle, payloads, tokens)
     reset(gm)
     gm.set_patterns(tokens)
     gm.load_arena(arena)
@@ -253,25 +187,26 @@ def test_context_state(gm, oracle):
         gm.set_patterns(pats)
         # running totals under OPT_ACCUMULATE are left alone
         gm.load_arena(K.HostArena.from_payloads(big))
-        want_big = host_counts(oracle, big, pats)
+        want_big = MM.oracle_counts(oracle, big, pats)
+        hits_small, want_small = MM.hits(MM.starts(small, pats)), MM.oracle_counts(oracle, small, pats)
         gm.set_option(OPT_ACCUMULATE, 1)
         gm.counts_reset()
         gm.scan_enqueue(); gm.scan_enqueue()
         assert gm.counts_read().tolist() == [2 * c for c in want_big]
-        check(gm.scan_packets(hits=True), host_hits(big, pats), want_big)
+        check(gm.scan_packets(hits=True), MM.hits(MM.starts(big, pats)), want_big)
         assert gm.counts_read().tolist() == [2 * c for c in want_big]
         gm.set_option(OPT_ACCUMULATE, 0)
         assert gm.scan()[0].tolist() == want_big                      # a later scan() still matches
         # a smaller arena after a larger one: no stale bits, no stale totals
         gm.load_arena(K.HostArena.from_payloads(small))
         res = gm.scan_packets(hits=True)
-        check(res, host_hits(small, pats), host_counts(oracle, small, pats))
+        check(res, hits_small, want_small)
         # mode 1 / kernel 1: EINVAL, the context stays usable
         for key, val in ((OPT_MODE, MODE_AUTOMATON), (OPT_KERNEL, KERNEL_GENERAL)):
             gm.set_option(key, val)
             assert g.kmpgpu_scan_packets(gm._ctx, None, None, None, None, None) == -2
             reset(gm)
-        check(gm.scan_packets(hits=True), host_hits(small, pats), host_counts(oracle, small, pats))
+        check(gm.scan_packets(hits=True), hits_small, want_small)
         # n_pkts == 0: zeros, nothing launched
         gm.load_arena(np.zeros(64, np.uint8), np.zeros(0, np.uint64), np.zeros(0, np.uint32))
         res = gm.scan_packets(hits=True)
@@ -306,9 +241,9 @@ def test_arena_kept_in_place(gm, oracle):
         gm.set_option(OPT_REPACK, 0)
         gm.set_patterns(pats)
         gm.load_arena(arena, off, ln)
-        want = host_counts(oracle, payloads, pats)
+        want = MM.oracle_counts(oracle, payloads, pats)
         assert gm.scan()[0].tolist() == want
-        check(gm.scan_packets(hits=True), host_hits(payloads, pats), want)
+        check(gm.scan_packets(hits=True), MM.hits(MM.starts(payloads, pats)), want)
         assert gm.scan()[0].tolist() == want
     finally:
         reset(gm)
@@ -323,7 +258,7 @@ def test_many_patterns(gm, oracle):
     payloads = _text_payloads(rng, 100, 300, b"abcd", extra=b"ef")
     pats, placed = _many_patterns(rng, payloads)
     assert len(pats) > 65536
-    hits = host_hits(payloads, pats)
+    hits = MM.hits(MM.starts(payloads, pats))
     counts = [int(x) for x in oracle.count_payloads(payloads, pats, threads=8)]
     assert hits[IDX16 + 1:].any()
     try:
@@ -353,8 +288,8 @@ def test_dense(gm, oracle, uniform):
                 t[rng.randrange(len(t))] = 0
                 payloads[k] = bytes(t)
     pats = [b"a" * m]
-    hits = np.array([[text_end(t) >= m for t in payloads]])
-    counts = [sum(max(0, text_end(t) - m + 1) for t in payloads)]
+    hits = np.array([[MM.text_end(t) >= m for t in payloads]])
+    counts = [sum(max(0, MM.text_end(t) - m + 1) for t in payloads)]
     try:
         reset(gm)
         gm.set_patterns(pats)
@@ -366,7 +301,8 @@ def test_dense(gm, oracle, uniform):
         gm.set_option(OPT_KERNEL, KERNEL_AUTO); gm.set_option(OPT_FUSED, 1)
         pats2 = pats + [b"aa"]
         gm.set_patterns(pats2)
-        check(gm.scan_packets(hits=True), host_hits(payloads, pats2), host_counts(oracle, payloads, pats2))
+        hits2 = np.array([[MM.text_end(t) >= len(p) for t in payloads] for p in pats2])
+        check(gm.scan_packets(hits=True), hits2, MM.oracle_counts(oracle, payloads, pats2))
     finally:
         reset(gm)
 
@@ -413,12 +349,6 @@ def test_full_size_1m(gm):
 # ------------------------------------------------------------------------------------------------
 # 8. the command lines: KMPGPU_PACKETS_FILE
 # ------------------------------------------------------------------------------------------------
-def _strip_elapsed(out):
-    lines = out.splitlines(keepends=True)
-    assert lines and lines[-1].startswith("Elapsed time = ") and lines[-1].endswith(" seconds\n")
-    return "".join(lines[:-1])
-
-
 CLI_RUNS = [("serial", [], {}), ("openmp_data", ["3"], {}), ("serial", [], {"KMPGPU_RCCL": "1"}),
             ("openmp_data", ["3"], {"KMPGPU_DEVICE_EXTRACT": "1"}), ("serial", [], {"KMPGPU_NOCASE": "1"})]
 
@@ -430,16 +360,14 @@ def test_cli_packets_file(oracle, tokens, fixture_counts, tmp_path, run):
     arena = K.HostArena.from_pcap(os.path.join(DATA, "big_udp.pcap"), "udp")
     payloads = [arena.payload(k) for k in range(arena.n_pkts)]
     flags = [nocase] * len(tokens)
-    hits = host_hits(payloads, tokens, flags)
+    hits = MM.hits(MM.starts(payloads, tokens, nocase=flags))
     want = sorted((int(k), int(i)) for i, k in np.argwhere(hits))
-    counts = host_counts(oracle, payloads, tokens, flags)
+    counts = MM.oracle_counts(oracle, payloads, tokens, flags)
     if not nocase:
         assert counts == fixture_counts["fixtures"]["big_udp.pcap:udp"]["counts"]
     out = tmp_path / "packets.csv"
-    env = dict(os.environ, KMPGPU_PACKETS_FILE=str(out), **env_extra)
-    r = subprocess.run([os.path.join(_lib.BINDIR, prog), os.path.join(DATA, "big_udp.pcap"), os.path.join(DATA, "strings.txt"), *extra, "udp"],
-                       capture_output=True, text=True, timeout=300, env=env)
+    r = run_cli(prog, "big_udp.pcap", extra=extra, env_extra=dict(env_extra, KMPGPU_PACKETS_FILE=str(out)), scrub=None)
     assert r.returncode == 0, r.stderr
-    assert _strip_elapsed(r.stdout) == K.format_report(tokens, counts)
+    assert strip_elapsed(r.stdout) == K.format_report(tokens, counts)
     got = [tuple(int(x) for x in line.split(",")) for line in out.read_text().splitlines()]
     assert got == want                                # sorted by payload, then by pattern, as written

@@ -17,9 +17,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
 
-# torch first: its wheel carries its own ROCm runtime libraries, and a process in which /opt/rocm's libamdhip64 (what libkmpgpu.so
-# links) is loaded BEFORE torch's ends up with torch seeing "No HIP GPUs" (seen when this file was run on its own; in the whole
-# suite tests/test_dist.py imports torch earlier).  The C-ABI library itself does not care which of the two it gets.
+from gpu_support import gm, strip_elapsed  # noqa: E402,F401  (before the package: it imports torch first, and says why)
+
 import torch  # noqa: E402,F401
 
 import multithreading_string_matching_amd as K  # noqa: E402
@@ -32,13 +31,6 @@ FIXTURE_KEYS = [
     "udp.pcap:udp", "udp_1000.pcap:udp", "big_udp.pcap:udp", "very_big_udp.pcap:udp",
     "tcp.pcap:tcp", "tcp.pcap:udp", "udp.pcap:tcp", "udp_1000.pcap:tcp",
 ]
-
-
-@pytest.fixture(scope="module")
-def gm():
-    m = GpuMatcher(0)
-    yield m
-    m.close()
 
 
 KERNEL_FUSED = 100          # test-only alias: auto kernel selection + the fused multi-pattern pass
@@ -917,18 +909,12 @@ def _run(prog, *args):
     return subprocess.run([exe, *args], capture_output=True, text=True, timeout=300)
 
 
-def _strip_elapsed(out):
-    lines = out.splitlines(keepends=True)
-    assert lines and lines[-1].startswith("Elapsed time = ") and lines[-1].endswith(" seconds\n")
-    return "".join(lines[:-1])
-
-
 @pytest.mark.parametrize("key", FIXTURE_KEYS)
 def test_cli_serial_stdout(fixture_counts, tokens, key):
     fx = fixture_counts["fixtures"][key]
     r = _run("serial", os.path.join(DATA, fx["pcap"]), os.path.join(DATA, "strings.txt"), fx["mode"])
     assert r.returncode == 0, r.stderr
-    assert _strip_elapsed(r.stdout) == K.format_report(tokens, fx["counts"])
+    assert strip_elapsed(r.stdout) == K.format_report(tokens, fx["counts"])
 
 
 def test_cli_empty_pattern_file(tmp_path):
@@ -938,13 +924,13 @@ def test_cli_empty_pattern_file(tmp_path):
     for prog, extra in (("serial", []), ("openmp_data", ["2"]), ("openmp_task", ["2"])):
         r = _run(prog, os.path.join(DATA, "udp_1000.pcap"), str(empty), *extra)
         assert r.returncode == 0, r.stderr
-        assert _strip_elapsed(r.stdout) == K.format_report([], [])
+        assert strip_elapsed(r.stdout) == K.format_report([], [])
 
 
 def test_cli_default_protocol_is_udp(fixture_counts, tokens):
     fx = fixture_counts["fixtures"]["udp_1000.pcap:udp"]
     r = _run("serial", os.path.join(DATA, "udp_1000.pcap"), os.path.join(DATA, "strings.txt"))
-    assert r.returncode == 0 and _strip_elapsed(r.stdout) == K.format_report(tokens, fx["counts"])
+    assert r.returncode == 0 and strip_elapsed(r.stdout) == K.format_report(tokens, fx["counts"])
 
 
 @pytest.mark.parametrize("shards", ["1", "2", "3", "8"])
@@ -952,9 +938,9 @@ def test_cli_openmp_data_form(fixture_counts, tokens, shards):
     fx = fixture_counts["fixtures"]["big_udp.pcap:udp"]
     r = _run("openmp_data", os.path.join(DATA, "big_udp.pcap"), os.path.join(DATA, "strings.txt"), shards, "udp")
     assert r.returncode == 0, r.stderr
-    assert _strip_elapsed(r.stdout) == K.format_report(tokens, fx["counts"])
+    assert strip_elapsed(r.stdout) == K.format_report(tokens, fx["counts"])
     r = _run("openmp_data", os.path.join(DATA, "big_udp.pcap"), os.path.join(DATA, "strings.txt"), shards)
-    assert r.returncode == 0 and _strip_elapsed(r.stdout) == K.format_report(tokens, fx["counts"])
+    assert r.returncode == 0 and strip_elapsed(r.stdout) == K.format_report(tokens, fx["counts"])
 
 
 @pytest.mark.parametrize("extract", ["0", "1"])
@@ -970,7 +956,7 @@ def test_cli_openmp_task_streaming(fixture_counts, tokens, key, shards, batch, e
     r = subprocess.run([exe, os.path.join(DATA, fx["pcap"]), os.path.join(DATA, "strings.txt"), shards, fx["mode"]],
                        capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr
-    assert _strip_elapsed(r.stdout) == K.format_report(tokens, fx["counts"])
+    assert strip_elapsed(r.stdout) == K.format_report(tokens, fx["counts"])
     assert f"streamed {fx['packets']} frames, {fx['payloads']} payloads, {fx['payload_bytes']} payload bytes in " in r.stderr, r.stderr
     nb = int(r.stderr.split(" payload bytes in ")[1].split()[0])
     volume = os.path.getsize(os.path.join(DATA, fx["pcap"])) if extract == "1" else fx["payload_bytes"]      # what a batch is measured in
@@ -1185,7 +1171,7 @@ def test_mpi_dumping_program(fixture_counts, tokens, key, nproc):
     r = _torchrun_mpi(nproc, [os.path.join(DATA, fx["pcap"]), os.path.join(DATA, "strings.txt"), fx["mode"]], 29561 + nproc)
     assert r.returncode == 0, r.stderr[-2000:]
     out = r.stdout[r.stdout.index("Printing the number"):]        # gloo announces its connections on stdout first; RCCL does not
-    assert _strip_elapsed(out) == K.format_report(tokens, fx["counts"])
+    assert strip_elapsed(out) == K.format_report(tokens, fx["counts"])
     assert r.stdout.count("Elapsed time = ") == 1 and r.stdout.count("Printing the number") == 1
 
 
@@ -1208,7 +1194,7 @@ def test_cli_device_extraction(fixture_counts, tokens):
         args = [os.path.join(_lib.BINDIR, prog), os.path.join(DATA, fx["pcap"]), os.path.join(DATA, "strings.txt")] + extra + [fx["mode"]]
         r = subprocess.run(args, capture_output=True, text=True, timeout=300, env=env)
         assert r.returncode == 0, r.stderr
-        assert _strip_elapsed(r.stdout) == K.format_report(tokens, fx["counts"])
+        assert strip_elapsed(r.stdout) == K.format_report(tokens, fx["counts"])
 
 
 def test_accumulate_option(gm, oracle):
@@ -1239,7 +1225,7 @@ def test_cli_offsets_file(tokens, fixture_counts, tmp_path, shards, extra):
                        text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr
     fx = fixture_counts["fixtures"]["big_udp.pcap:udp"]
-    assert _strip_elapsed(r.stdout) == K.format_report(tokens, fx["counts"])
+    assert strip_elapsed(r.stdout) == K.format_report(tokens, fx["counts"])
     arena = K.HostArena.from_pcap(os.path.join(DATA, "big_udp.pcap"), "udp")
     rows = [tuple(map(int, line.split(","))) for line in out.read_text().splitlines()]
     assert len(rows) == sum(fx["counts"]) and len(set(rows)) == len(rows)
@@ -1267,7 +1253,7 @@ def test_cli_pcap_route_equals_arena_route(gm, tmp_path):
     r = _run("serial", pcap, str(strings), "udp")
     assert r.returncode == 0, r.stderr
     planted = K.synth_count_planted(sp, n, 1500)
-    assert _strip_elapsed(r.stdout) == K.format_report([needle], [planted])
+    assert strip_elapsed(r.stdout) == K.format_report([needle], [planted])
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1315,17 +1301,17 @@ def test_cli_rccl_reduce(fixture_counts, tokens):
         r = subprocess.run([exe, os.path.join(DATA, "big_udp.pcap"), os.path.join(DATA, "strings.txt"), "1", "udp"], capture_output=True, text=True,
                            timeout=300, env=env)
         assert r.returncode == 0, r.stderr
-        assert _strip_elapsed(r.stdout) == K.format_report(tokens, fx["counts"])
+        assert strip_elapsed(r.stdout) == K.format_report(tokens, fx["counts"])
         assert "count reduce: RCCL all-reduce" in r.stderr
     # the streamed form: the two contexts of a shard are merged on the device (kmpgpu_counts_add), then the same reduce
     env = dict(os.environ, KMPGPU_RCCL="1", KMPGPU_BATCH_BYTES="1048576")
     r = subprocess.run([os.path.join(_lib.BINDIR, "openmp_task"), os.path.join(DATA, "big_udp.pcap"), os.path.join(DATA, "strings.txt"), "1", "udp"],
                        capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr
-    assert _strip_elapsed(r.stdout) == K.format_report(tokens, fx["counts"]) and "count reduce: RCCL all-reduce" in r.stderr
+    assert strip_elapsed(r.stdout) == K.format_report(tokens, fx["counts"]) and "count reduce: RCCL all-reduce" in r.stderr
     # more shards than devices: the shards share the GPU and are summed on the host
     r = subprocess.run([exe, os.path.join(DATA, "big_udp.pcap"), os.path.join(DATA, "strings.txt"), "3", "udp"], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and _strip_elapsed(r.stdout) == K.format_report(tokens, fx["counts"])
+    assert r.returncode == 0 and strip_elapsed(r.stdout) == K.format_report(tokens, fx["counts"])
     assert "count reduce: host sum" in r.stderr or K.device_count() >= 3
 
 
@@ -1335,7 +1321,7 @@ def test_cli_stdout_is_the_literal_golden_text():
     for prog, extra in (("serial", ["udp"]), ("openmp_data", ["2", "udp"]), ("openmp_task", ["2", "udp"])):
         r = _run(prog, os.path.join(DATA, "udp_1000.pcap"), os.path.join(DATA, "strings.txt"), *extra)
         assert r.returncode == 0, r.stderr
-        assert _strip_elapsed(r.stdout) == golden, prog
+        assert strip_elapsed(r.stdout) == golden, prog
 
 
 def test_frame_shards_upload_only_their_span(gm, fixture_counts, tokens):

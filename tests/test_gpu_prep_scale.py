@@ -47,7 +47,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-# torch first: see the header comment of tests/test_gpu_parity.py
+from gpu_support import gm, reset  # noqa: E402,F401  (torch first)
+
 import torch  # noqa: E402
 
 import prep_model as PM  # noqa: E402
@@ -66,18 +67,6 @@ VALIDATE_ITEMS = 2048 * 256  # ... of kmp_validate_index_kernel
 SLOT_END_ITEMS = 1024 * 256  # ... of kmp_slot_end_kernel
 N_BIG = 2_500_123           # ten rounds of the totals kernel, the last one partial; not a multiple of 1 024
 assert N_BIG % TILE and (N_BIG + ROUND - 1) // ROUND == 10 and PM.ROUND_ITEMS == ROUND
-
-
-@pytest.fixture(scope="module")
-def gm():
-    m = GpuMatcher(0)
-    yield m
-    m.close()
-
-
-def _restore(gm):
-    for key, value in ((OPT_MODE, MODE_FILTER), (OPT_KERNEL, KERNEL_AUTO), (OPT_FUSED, 2), (OPT_REPACK, 1)):
-        gm.set_option(key, value)
 
 
 def _scan(gm, kernel):
@@ -168,7 +157,7 @@ def test_extraction_at_threshold_edges(gm, lib, proto, n):
         if n > ROUND:
             assert len(acc) > GATHER_WAVES
     finally:
-        _restore(gm)
+        reset(gm)
 
 
 @pytest.mark.parametrize("proto", ["udp", "tcp"])
@@ -196,7 +185,7 @@ def test_extraction_sequence_shapes(gm, lib, proto, shape):
         else:
             assert len(acc) > ROUND and int(plen[acc].max()) == 0
     finally:
-        _restore(gm)
+        reset(gm)
 
 
 def test_extraction_buffers_reused(gm, lib):
@@ -210,7 +199,7 @@ def test_extraction_buffers_reused(gm, lib):
         _check_extraction(gm, lib, "tcp", PM.make_sequence("empty_rounds", N_BIG, lib.rule["tcp"][1], seed=23), two_steps=True, packed_tags=False)
         _check_extraction(gm, lib, "udp", PM.make_sequence("mixed", 3, plen, seed=24))
     finally:
-        _restore(gm)
+        reset(gm)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -262,7 +251,7 @@ def test_arena_past_4_gib(gm, lib):
             assert _scan(gm, kernel).tolist() == want_tags.tolist(), kernel
         assert gm.effective_bytes() == 1458 * len(acc)
     finally:
-        _restore(gm)
+        reset(gm)
         gm.load_arena(np.zeros(0, np.uint8), np.zeros(0, np.uint64), np.zeros(0, np.uint32))      # gives the 4.6 GB back
     assert gm.arena_info() == (0, 0)
 
@@ -299,7 +288,7 @@ def test_source_past_4_gib(gm, lib):
         assert _scan(gm, KERNEL_FUSED).tolist() == want.tolist()
         assert gm.effective_bytes() == PM.effective_bytes(arena, off, ln)
     finally:
-        _restore(gm)
+        reset(gm)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -360,7 +349,7 @@ def test_repack_at_scale(gm, oracle, n):
                 if route == "attach":
                     assert torch.equal(d_arena.cpu(), torch.from_numpy(arena)) and torch.equal(d_off.cpu(), torch.from_numpy(off.astype(np.int64)))
     finally:
-        _restore(gm)
+        reset(gm)
         gm.load_arena(np.zeros(0, np.uint8), np.zeros(0, np.uint64), np.zeros(0, np.uint32))
 
 
@@ -407,7 +396,7 @@ def test_padding_at_scale(gm, oracle, dirty_from):
             assert _scan(gm, kernel).tolist() == want.tolist(), ("borrowed", kernel)
         assert np.array_equal(d_arena.cpu().numpy(), arena)
     finally:
-        _restore(gm)
+        reset(gm)
         gm.load_arena(np.zeros(0, np.uint8), np.zeros(0, np.uint64), np.zeros(0, np.uint32))
 
 
@@ -508,7 +497,7 @@ def test_layout_check_on_the_device(gm, oracle, where):
         gm.attach_arena(d_big, d_o, d_len, arena_bytes=far + 16)
         assert _scan(gm, KERNEL_AUTO).tolist() == want.tolist()
     finally:
-        _restore(gm)
+        reset(gm)
         gm.load_arena(np.zeros(0, np.uint8), np.zeros(0, np.uint64), np.zeros(0, np.uint32))
 
 
@@ -537,7 +526,7 @@ def test_uniform_index_with_one_odd_length(gm, oracle, route):
         for kernel in (KERNEL_AUTO, KERNEL_PACKED, KERNEL_FUSED, KERNEL_GENERAL):
             assert _scan(gm, kernel).tolist() == want.tolist(), kernel
     finally:
-        _restore(gm)
+        reset(gm)
         gm.load_arena(np.zeros(0, np.uint8), np.zeros(0, np.uint64), np.zeros(0, np.uint32))
 
 

@@ -1,16 +1,13 @@
 """Distance / within relations between two patterns (kmpgpu_set_relations, kmpgpu_scan_relations, GpuMatcher.set_relations) on a
 real MI355X.
 
-The expectation is a host model, payload by payload: t = payload[:E_k] (E_k = the first 0x00, or the payload's end under
-OPT_WHOLE_PAYLOAD), folded for a nocase pattern; every start of every pattern by bytes.find, overlapping starts included, filtered by
-the pattern's window; relation (a, b, dmin, dmax) holds where some start sa of a and some start sb of b have
-dmin <= sb - (sa + len(a)) <= dmax, looked for over all pairs.  counts come from the CPU oracle.  Every comparison is exact.
+The expectation is the host model of tests/match_model.py: the starts of every pattern, the hit matrix and the relation rows over
+them.  counts come from the CPU oracle.  Every comparison is exact.
 
 Run on a real MI355X:  python -m pytest tests/test_gpu_relations.py -m gpu
 """
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
@@ -19,161 +16,28 @@ from conftest import DATA, GOLDEN
 
 pytestmark = pytest.mark.gpu
 
-# torch first, as tests/test_gpu_parity.py explains: its wheel carries its own ROCm runtime libraries
-import torch  # noqa: E402
+from gpu_support import KERNELS, attach_slots, check_relations, check_rules, gm, reset, run_cli, strip_elapsed  # noqa: E402,F401  (torch first)
 
+import match_model as MM  # noqa: E402
 import multithreading_string_matching_amd as K  # noqa: E402
+from match_model import I32_MAX, I32_MIN, U32_MAX  # noqa: E402
 from multithreading_string_matching_amd import _lib  # noqa: E402
 from multithreading_string_matching_amd.matcher import (  # noqa: E402
-    KERNEL_AUTO, KERNEL_FLAT, KERNEL_PACKED, MODE_FILTER, OPT_FUSED, OPT_KERNEL, OPT_MODE, OPT_WHOLE_PAYLOAD, GpuMatcher)
+    KERNEL_AUTO, OPT_ACCUMULATE, OPT_FUSED, OPT_KERNEL, OPT_REPACK, OPT_WHOLE_PAYLOAD, GpuMatcher)
 
-OPT_ACCUMULATE, OPT_REPACK = 6, 7
-U32_MAX = 0xFFFFFFFF
-I32_MIN, I32_MAX = -(1 << 31), (1 << 31) - 1
 ALPHABET = b"abcdAB"
 EINVAL, ESTATE = -2, -3
 
-# (name, kernel, fused), as tests/test_gpu_packets.py: the automatic choice (fused for multi-pattern sets), the two streaming kernels
-KERNELS = [("auto", KERNEL_AUTO, 2), ("flat", KERNEL_FLAT, 0), ("packed", KERNEL_PACKED, 0)]
-
-
-# ------------------------------------------------------------------------------------------------
-# the host model
-# ------------------------------------------------------------------------------------------------
-def fold(b):
-    return bytes(b).lower()                          # ASCII A-Z only
-
-
-def text_end(t, whole=False):
-    z = -1 if whole else t.find(b"\0")
-    return len(t) if z < 0 else z
-
-
-def all_starts(payloads, pats, windows=None, nocase=None, whole=False):
-    """starts[k][i]: the in-window start offsets of pattern i in payload k, ascending"""
-    nocase = nocase or [False] * len(pats)
-    win = [(a, U32_MAX if b is None else b) for a, b in windows] if windows else [(0, U32_MAX)] * len(pats)
-    fp = [fold(p) if nc else p for p, nc in zip(pats, nocase)]
-    out = []
-    for text in payloads:
-        t = text[:text_end(text, whole)]
-        tf = fold(t)
-        row = []
-        for i, p in enumerate(fp):
-            src = tf if nocase[i] else t
-            first, last = win[i]
-            ss = []
-            s = src.find(p)
-            while s >= 0:
-                if first <= s <= last:
-                    ss.append(s)
-                s = src.find(p, s + 1)
-            row.append(ss)
-        out.append(row)
-    return out
-
-
-def pair_exists(sa, sb, m_a, dmin, dmax):
-    """the definition, over all pairs"""
-    lo = I32_MIN if dmin is None else dmin
-    hi = I32_MAX if dmax is None else dmax
-    for x in sa:
-        for y in sb:
-            if lo <= y - (x + m_a) <= hi:
-                return True
-    return False
-
-
-def model(payloads, pats, relations, windows=None, nocase=None, whole=False):
-    """(hits bool[n_pat, n_pkts], rel rows bool[n_rel, n_pkts])"""
-    st = all_starts(payloads, pats, windows, nocase, whole)
-    hits = np.zeros((len(pats), len(payloads)), dtype=bool)
-    rows = np.zeros((len(relations), len(payloads)), dtype=bool)
-    for k, row in enumerate(st):
-        for i, ss in enumerate(row):
-            hits[i, k] = bool(ss)
-        memo = {}
-        for q, rel in enumerate(relations):
-            a, b, dmin, dmax = rel
-            if row[a] and row[b]:
-                if rel not in memo:
-                    memo[rel] = pair_exists(row[a], row[b], len(pats[a]), dmin, dmax)
-                rows[q, k] = memo[rel]
-    return hits, rows
-
-
-def all_counts(oracle, payloads, pats, nocase=None, whole=False):
-    """what kmpgpu_scan returns (the oracle's strlen rule; whole payloads: on the 0x00 bytes mapped to a byte that no pattern holds)"""
-    nocase = nocase or [False] * len(pats)
-    if whole:
-        assert all(b"\x01" not in p for p in pats)
-        payloads = [t.replace(b"\0", b"\x01") for t in payloads]
-    cs = oracle.count_payloads(payloads, pats)
-    if not any(nocase):
-        return [int(x) for x in cs]
-    fo = oracle.count_payloads([fold(t) for t in payloads], [fold(p) for p in pats])
-    return [int(fo[i]) if nocase[i] else int(cs[i]) for i in range(len(pats))]
-
-
-def rule_rows(hits, rel_rows, rules):
-    """rules over the rows [patterns..., relations...]"""
-    mat = np.concatenate([hits, rel_rows], axis=0)
-    rows = np.zeros((len(rules), mat.shape[1]), dtype=bool)
-    for r, (pos, neg) in enumerate(rules):
-        row = np.ones(mat.shape[1], dtype=bool)
-        for i in pos:
-            row &= mat[i]
-        for i in neg:
-            row &= ~mat[i]
-        rows[r] = row
-    return rows
-
-
-def check_relations(gm, rows, counts):
-    res = gm.scan_relations(hits=True)
-    bad = np.argwhere(res["hits"] != rows)
-    assert bad.size == 0, [(int(q), int(k), bool(rows[q, k]), gm.relations[int(q)]) for q, k in bad[:8]]
-    assert res["rel_pkt_counts"].tolist() == rows.sum(axis=1).tolist()
-    assert res["any"].tolist() == rows.any(axis=0).tolist()
-    assert res["counts"].tolist() == list(counts)
-    return res
-
-
-def check_rules(gm, hits, rel_rows, rules, counts):
-    want = rule_rows(hits, rel_rows, rules)
-    res = gm.scan_rules(hits=True)
-    bad = np.argwhere(res["hits"] != want)
-    assert bad.size == 0, [(int(r), int(k), bool(want[r, k])) for r, k in bad[:8]]
-    assert res["rule_pkt_counts"].tolist() == want.sum(axis=1).tolist()
-    assert res["any"].tolist() == want.any(axis=0).tolist()
-    assert res["counts"].tolist() == list(counts)
-    return res
-
 
 def check_kernels(gm, oracle, payloads, pats, relations, windows=None, nocase=None, whole=False, kernels=KERNELS):
-    hits, rows = model(payloads, pats, relations, windows, nocase, whole)
-    counts = all_counts(oracle, payloads, pats, nocase, whole)
+    st = MM.starts(payloads, pats, windows, nocase, whole)
+    hits, rows = MM.hits(st), MM.relation_rows(st, pats, relations)
+    counts = MM.oracle_counts(oracle, payloads, pats, nocase, whole)
     for name, kernel, fused in kernels:
         gm.set_option(OPT_KERNEL, kernel); gm.set_option(OPT_FUSED, fused)
         check_relations(gm, rows, counts)
     gm.set_option(OPT_KERNEL, KERNEL_AUTO); gm.set_option(OPT_FUSED, 2)
     return hits, rows, counts
-
-
-@pytest.fixture(scope="module")
-def gm():
-    m = GpuMatcher(0)
-    yield m
-    m.close()
-
-
-def reset(gm):
-    gm.set_option(OPT_MODE, MODE_FILTER)
-    gm.set_option(OPT_KERNEL, KERNEL_AUTO)
-    gm.set_option(OPT_FUSED, 2)
-    gm.set_option(OPT_REPACK, 1)
-    gm.set_option(OPT_ACCUMULATE, 0)
-    gm.set_option(OPT_WHOLE_PAYLOAD, 0)
 
 
 def place(L, items, fill=b"abcd", rng=None):
@@ -340,18 +204,6 @@ def test_several_occurrences(gm, oracle):
 # ------------------------------------------------------------------------------------------------
 # 4. the text's end
 # ------------------------------------------------------------------------------------------------
-def _attach(gm, payloads, slots):
-    """a borrowed arena keeps what lies in its padding (tests/test_gpu_packets.py)"""
-    ln = np.array([len(t) for t in payloads], dtype=np.uint32)
-    size = np.array([len(s) for s in slots], dtype=np.uint64)
-    off = np.concatenate([[0], np.cumsum(size)[:-1]]).astype(np.uint64)
-    arena = np.frombuffer(b"".join(slots) + b"\0" * 64, dtype=np.uint8).copy()
-    keep = (torch.from_numpy(arena).cuda(), torch.from_numpy(off.astype(np.int64)).cuda(), torch.from_numpy(ln.astype(np.int32)).cuda())
-    torch.cuda.synchronize()
-    gm.attach_arena(*keep)
-    return keep
-
-
 def test_text_end(gm, oracle):
     rng = random.Random("end")
     A, B = b"EFX", b"GHY"
@@ -376,7 +228,7 @@ def test_text_end(gm, oracle):
         reset(gm)
         gm.set_patterns([A, B])
         for attach in (False, True):
-            keep = _attach(gm, payloads, slots) if attach else gm.load_arena(K.HostArena.from_payloads(payloads))
+            keep = attach_slots(gm, payloads, slots) if attach else gm.load_arena(K.HostArena.from_payloads(payloads))
             gm.set_relations(relations)
             seen = {}
             for whole in (0, 1, 0):                   # switched between two calls with nothing reloaded
@@ -415,7 +267,7 @@ def test_nocase(gm, oracle, nocase):
         gm.load_arena(K.HostArena.from_payloads(payloads))
         gm.set_relations(relations)
         hits, rows, _ = check_kernels(gm, oracle, payloads, pats, relations, nocase=flags)
-        _, sens = model(payloads, pats, relations)
+        sens = MM.relation_rows(MM.starts(payloads, pats), pats, relations)
         assert rows[:7].any(axis=1).all() and (rows != sens).any()      # folding found pairs that the bytes as written do not hold
     finally:
         reset(gm)
@@ -445,7 +297,7 @@ def test_windows(gm, oracle):
             gm.set_windows(windows)
             hits, rows, counts = check_kernels(gm, oracle, payloads, [A, B], relations, windows=windows)
             assert (rows != base).any()
-            check_rules(gm, hits, rows, gm.rules, counts)            # the rules, set before the windows, stay valid
+            check_rules(gm, np.concatenate([hits, rows]), gm.rules, counts)            # the rules, set before the windows, stay valid
             gm.set_windows(None)                                     # cleared between two passes, nothing re-set
             assert (check_kernels(gm, oracle, payloads, [A, B], relations)[1] == base).all()
         gm.set_windows([(0, 50), (0, None)])
@@ -548,7 +400,7 @@ def test_random_differential(gm, oracle, seed, kind):
         gm.set_patterns(pats)
         if kind == "dirty":
             slots = [t + bytes(rng.choice(ALPHABET) for _ in range((-len(t)) % 16 or (16 if not t else 0))) for t in payloads]
-            keep = _attach(gm, payloads, slots)
+            keep = attach_slots(gm, payloads, slots)
         elif kind == "in_place":
             # OPT_REPACK = 0: slots with gaps, not in payload order; the marking pass packs such an arena on the call
             ln = np.array([len(t) for t in payloads], dtype=np.uint32)
@@ -595,7 +447,8 @@ def test_rules_over_relations(gm, oracle):
         assert gm.rules == []
         R = gm.rel
         # a relation that holds in some of the payloads that hold both of its patterns: as a term it narrows "a and b"
-        hits0, rows0 = model(payloads, pats, relations)
+        st0 = MM.starts(payloads, pats)
+        hits0, rows0 = MM.hits(st0), MM.relation_rows(st0, pats, relations)
         qn = next(q for q, (a, b, _, _) in enumerate(relations) if rows0[q].any() and (hits0[a] & hits0[b] & ~rows0[q]).any())
         a0, b0 = relations[qn][:2]
         rules = [([a0, b0, R(qn)], []), ([a0], [R(qn)]), ([], [R(1)]), ([R(2), R(3)], []), ([R(4)], [R(5), 0]), ([R(6), R(7), R(8), R(9), 1, 2], [R(10)]), ([R(39)], []),
@@ -606,13 +459,13 @@ def test_rules_over_relations(gm, oracle):
             hits, rows, counts = check_kernels(gm, oracle, payloads, pats, relations, windows=w)
             for _, kernel, fused in KERNELS:
                 gm.set_option(OPT_KERNEL, kernel); gm.set_option(OPT_FUSED, fused)
-                check_rules(gm, hits, rows, rules, counts)
+                check_rules(gm, np.concatenate([hits, rows]), rules, counts)
             gm.set_option(OPT_KERNEL, KERNEL_AUTO); gm.set_option(OPT_FUSED, 2)      # (as `before` was taken: the launches are compared below)
-            want = rule_rows(hits, rows, rules)
+            want = MM.rule_rows(np.concatenate([hits, rows]), rules)
             empty = np.array([len(t) == 0 for t in payloads])
             assert want[2][empty].all() and empty.any()                 # all-negated: empty payloads match
             if w is None:
-                assert (want[0] != rule_rows(hits, rows, [([a0, b0], [])])[0]).any() and want[0].any() and want[1].any()
+                assert (want[0] != MM.rule_rows(np.concatenate([hits, rows]), [([a0, b0], [])])[0]).any() and want[0].any() and want[1].any()
         gm.set_windows(None)
         # pattern-level calls return what they returned before there were relations
         gm.scan_relations()
@@ -666,14 +519,15 @@ def test_state_and_errors(gm, oracle):
         gm.set_relations(relations)
         rules = [([0, gm.rel(0)], []), ([], [gm.rel(4)])]
         gm.set_rules(rules)
-        hits, rows = model(payloads, pats, relations)
-        counts = all_counts(oracle, payloads, pats)
+        st = MM.starts(payloads, pats)
+        hits, rows = MM.hits(st), MM.relation_rows(st, pats, relations)
+        counts = MM.oracle_counts(oracle, payloads, pats)
         # every refused call leaves the relations and the rules set before in force
         for bad in ([(n, 0, 0, 0)], [(0, n, 0, 0)], [(0, 1, 0, 5), (0, U32_MAX, 0, 5)], [(0, 1, 5, 4)], [(0, 1, I32_MAX, I32_MIN)], [(0, 1, 1, 0), (0, 1, 0, 0)]):
             assert call(gm._ctx, bad) == EINVAL, bad
             assert b"kmpgpu_set_relations" in g.kmpgpu_last_error()
             check_relations(gm, rows, counts)
-            check_rules(gm, hits, rows, rules, counts)
+            check_rules(gm, np.concatenate([hits, rows]), rules, counts)
         assert g.kmpgpu_set_relations(gm._ctx, None, 3) == EINVAL
         # too many rows: n_pat + n_rel has to stay below 2^31 (the bound is checked before rel[] is read: one element is enough)
         one = (_lib.Relation * 1)()
@@ -682,11 +536,11 @@ def test_state_and_errors(gm, oracle):
             assert g.kmpgpu_set_relations(gm._ctx, one, n_rel) == EINVAL, n_rel
             assert b"kmpgpu_set_relations" in g.kmpgpu_last_error()
             check_relations(gm, rows, counts)
-            check_rules(gm, hits, rows, rules, counts)
+            check_rules(gm, np.concatenate([hits, rows]), rules, counts)
         with pytest.raises(Exception):
             gm.set_relations([(0, n, 0, 0)])
         assert gm.relations == relations and gm.rules == rules
-        check_rules(gm, hits, rows, rules, counts)
+        check_rules(gm, np.concatenate([hits, rows]), rules, counts)
         # the bound of a rule's term is n_pat + n_rel
         u32p = _lib.GPU_API["kmpgpu_set_rules"][1][1]
         off = np.array([0, 1], dtype=np.uint32)
@@ -694,7 +548,7 @@ def test_state_and_errors(gm, oracle):
             t = np.array([term], dtype=np.uint32)
             assert g.kmpgpu_set_rules(gm._ctx, off.ctypes.data_as(u32p), t.ctypes.data_as(u32p), 1) == rc, term
         gm.rules = [([n + len(relations) - 1], [])]
-        check_rules(gm, hits, rows, gm.rules, counts)
+        check_rules(gm, np.concatenate([hits, rows]), gm.rules, counts)
         # a successful kmpgpu_set_relations drops the rules: the same relations again, and a clear
         for rels in (relations, []):
             gm.set_rules(rules if rels else [([0], [])])
@@ -749,8 +603,8 @@ def test_state_and_errors(gm, oracle):
 def _fixture_relations(payloads, tokens):
     """three relations over tokens that co-occur in udp_1000.pcap, picked with the model: the pairs with the most candidates, bounded so
     that the first one holds in some of its candidates and not in others"""
-    st = all_starts(payloads, tokens)
-    hits = np.array([[bool(ss) for ss in row] for row in st]).T
+    st = MM.starts(payloads, tokens)
+    hits = MM.hits(st)
     both = (hits[:, None, :] & hits[None, :, :]).sum(axis=2)
     np.fill_diagonal(both, 0)
     pairs = [divmod(int(i), len(tokens)) for i in np.argsort(-both, axis=None)[:40]]
@@ -759,7 +613,7 @@ def _fixture_relations(payloads, tokens):
         if len(ds) >= 3:
             mid = ds[len(ds) // 2]
             rel0 = (a, b, min(mid, 0), max(mid, 0))
-            rows = model(payloads, tokens, [rel0])[1]
+            rows = MM.relation_rows(st, tokens, [rel0])
             if 0 < rows[0].sum() < both[a, b]:
                 others = [p for p in pairs if p != (a, b) and set(p) != {a, b}][:2]
                 return [rel0, (others[0][0], others[0][1], 0, 64), (others[1][0], others[1][1], None, -1)]
@@ -771,7 +625,8 @@ def capture(tokens):
     arena = K.HostArena.from_pcap(os.path.join(DATA, "udp_1000.pcap"), "udp")
     payloads = [bytes(arena.payload(k)) for k in range(arena.n_pkts)]
     relations = _fixture_relations(payloads, tokens)
-    hits, rows = model(payloads, tokens, relations)
+    st = MM.starts(payloads, tokens)
+    hits, rows = MM.hits(st), MM.relation_rows(st, tokens, relations)
     return arena, payloads, relations, hits, rows
 
 
@@ -800,19 +655,6 @@ def test_fixture_capture(gm, oracle, tokens, fixture_counts, capture):
 # ------------------------------------------------------------------------------------------------
 # 12. the command lines: KMPGPU_RELATIONS_FILE
 # ------------------------------------------------------------------------------------------------
-def _run(prog, extra, env_extra):
-    env = {k: v for k, v in os.environ.items() if not k.startswith("KMPGPU_")}
-    env.update(env_extra)
-    return subprocess.run([os.path.join(_lib.BINDIR, prog), os.path.join(DATA, "udp_1000.pcap"), os.path.join(DATA, "strings.txt"), *extra, "udp"],
-                          capture_output=True, text=True, timeout=300, env=env)
-
-
-def _strip_elapsed(out):
-    lines = out.splitlines(keepends=True)
-    assert lines and lines[-1].startswith("Elapsed time = ") and lines[-1].endswith(" seconds\n")
-    return "".join(lines[:-1])
-
-
 @pytest.mark.parametrize("prog,extra", [("serial", []), ("openmp_data", ["1"]), ("openmp_data", ["3"])])
 def test_cli_relations_file(tokens, tmp_path, capture, prog, extra):
     _, payloads, relations, hits, rows = capture
@@ -825,25 +667,25 @@ def test_cli_relations_file(tokens, tmp_path, capture, prog, extra):
     rf = tmp_path / "rules.txt"
     rf.write_text("".join(" ".join([str(i) if i < n else f"r{i - n}" for i in pos] + [f"!{i}" if i < n else f"!r{i - n}" for i in neg]) + "\n" for pos, neg in rules))
     al = tmp_path / "alerts.csv"
-    r = _run(prog, extra, {"KMPGPU_RELATIONS_FILE": str(lf), "KMPGPU_RULES_FILE": str(rf), "KMPGPU_ALERTS_FILE": str(al)})
+    r = run_cli(prog, extra=extra, env_extra={"KMPGPU_RELATIONS_FILE": str(lf), "KMPGPU_RULES_FILE": str(rf), "KMPGPU_ALERTS_FILE": str(al)})
     assert r.returncode == 0, r.stderr
     with open(os.path.join(GOLDEN, "stdout_udp_1000_udp.txt")) as f:
-        assert _strip_elapsed(r.stdout) == f.read()
+        assert strip_elapsed(r.stdout) == f.read()
     got = [tuple(int(x) for x in line.split(",")) for line in al.read_text().splitlines()]
-    want = rule_rows(hits, rows, rules)
+    want = MM.rule_rows(np.concatenate([hits, rows]), rules)
     assert got == sorted((int(k), int(r_)) for r_, k in np.argwhere(want))
     assert want[0].any() and want[1].any()
     # a relations file that does not parse, a missing one, or the variable without its partners: exit 1 before any GPU work
     bad = tmp_path / "bad.txt"
     bad.write_text("0 1 0 5\n0 1 9 3\n")
-    r = _run(prog, extra, {"KMPGPU_RELATIONS_FILE": str(bad), "KMPGPU_RULES_FILE": str(rf), "KMPGPU_ALERTS_FILE": str(al)})
+    r = run_cli(prog, extra=extra, env_extra={"KMPGPU_RELATIONS_FILE": str(bad), "KMPGPU_RULES_FILE": str(rf), "KMPGPU_ALERTS_FILE": str(al)})
     assert r.returncode == 1 and "line 2: " in r.stderr and r.stdout == ""
-    r = _run(prog, extra, {"KMPGPU_RELATIONS_FILE": str(tmp_path / "none.txt"), "KMPGPU_RULES_FILE": str(rf), "KMPGPU_ALERTS_FILE": str(al)})
+    r = run_cli(prog, extra=extra, env_extra={"KMPGPU_RELATIONS_FILE": str(tmp_path / "none.txt"), "KMPGPU_RULES_FILE": str(rf), "KMPGPU_ALERTS_FILE": str(al)})
     assert r.returncode == 1 and r.stdout == ""
-    r = _run(prog, extra, {"KMPGPU_RELATIONS_FILE": str(lf)})
+    r = run_cli(prog, extra=extra, env_extra={"KMPGPU_RELATIONS_FILE": str(lf)})
     assert r.returncode == 1 and "KMPGPU_RULES_FILE" in r.stderr and r.stdout == ""
-    r = _run(prog, extra, {"KMPGPU_RELATIONS_FILE": str(lf), "KMPGPU_RULES_FILE": str(rf)})
+    r = run_cli(prog, extra=extra, env_extra={"KMPGPU_RELATIONS_FILE": str(lf), "KMPGPU_RULES_FILE": str(rf)})
     assert r.returncode == 1 and "KMPGPU_ALERTS_FILE" in r.stderr and r.stdout == ""
     # without the relations the same rules file does not parse: r0 is no term
-    r = _run(prog, extra, {"KMPGPU_RULES_FILE": str(rf), "KMPGPU_ALERTS_FILE": str(al)})
+    r = run_cli(prog, extra=extra, env_extra={"KMPGPU_RULES_FILE": str(rf), "KMPGPU_ALERTS_FILE": str(al)})
     assert r.returncode == 1 and "line 1: " in r.stderr and r.stdout == ""

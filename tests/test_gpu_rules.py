@@ -1,9 +1,8 @@
 """Content rules (kmpgpu_set_rules, kmpgpu_scan_rules, GpuMatcher.set_rules / scan_rules) on a real MI355X.
 
-The expectation is a host model built from the payload bytes: hit[i][k] = pattern i occurs in payload k before E_k (its first
-0x00, or its end under KMPGPU_OPT_WHOLE_PAYLOAD), a KMPGPU_PAT_NOCASE pattern on folded text; the rules are applied to that
-matrix with numpy and the pattern totals are counted in Python.  Nothing of it comes from the library.  Every output of the
-call is compared exactly, through the C-ABI and as whole words, so that a bit behind n_pkts shows.
+The expectation is the host model of tests/match_model.py: the rules are applied to its hit matrix with numpy, and the pattern
+totals are the model's own counts.  Nothing of it comes from the library.  Every output of the call is compared exactly, through
+the C-ABI and as whole words, so that a bit behind n_pkts shows.
 
 The thresholds of the kernel as built (csrc/kmp_rules.hip) and the tests that cross them:
   * a group of cl = 1, 2, 4 .. 64 lanes covers a rule's row, two words per lane, cl the smallest power of two with
@@ -31,71 +30,18 @@ from conftest import DATA, GOLDEN
 
 pytestmark = pytest.mark.gpu
 
-# torch first, as tests/test_gpu_parity.py explains: its wheel carries its own ROCm runtime libraries
-import torch  # noqa: E402
+from gpu_support import KERNELS, gm, load, reset, run_cli, strip_elapsed  # noqa: E402,F401  (torch first)
 
+import match_model as MM  # noqa: E402
 import multithreading_string_matching_amd as K  # noqa: E402
+from match_model import RULE_NOT as NOT  # noqa: E402
 from multithreading_string_matching_amd import _lib  # noqa: E402
 from multithreading_string_matching_amd.matcher import (  # noqa: E402
-    KERNEL_AUTO, KERNEL_FLAT, KERNEL_GENERAL, KERNEL_PACKED, MODE_AUTOMATON, MODE_FILTER, OPT_FUSED, OPT_KERNEL, OPT_MODE,
-    OPT_WHOLE_PAYLOAD, GpuMatcher)
+    KERNEL_GENERAL, MODE_AUTOMATON, OPT_ACCUMULATE, OPT_FUSED, OPT_KERNEL, OPT_MODE, OPT_REPACK, OPT_WHOLE_PAYLOAD, GpuMatcher)
 
-OPT_ACCUMULATE, OPT_REPACK = 6, 7
 EINVAL, ESTATE = -2, -3
-NOT = 0x80000000
 ALPHABET = b"abcdAB"
 SENTINEL = 0xA5A5A5A5A5A5A5A5                          # what the output buffers hold before a call
-
-
-# ------------------------------------------------------------------------------------------------
-# the host model
-# ------------------------------------------------------------------------------------------------
-def fold(b):
-    return bytes(b).lower()                          # ASCII A-Z only
-
-
-def text_of(t, whole):
-    z = -1 if whole else t.find(b"\0")
-    return t if z < 0 else t[:z]
-
-
-def occurrences(t, p):
-    n, s = 0, t.find(p)
-    while s >= 0:
-        n, s = n + 1, t.find(p, s + 1)
-    return n
-
-
-def host_model(payloads, pats, nocase=None, whole=False):
-    """(hit bool[n_pat, n_pkts], counts[n_pat]): occurrences of pattern i in payload k[0:E_k], folded for a nocase pattern."""
-    nocase = nocase or [False] * len(pats)
-    c = np.zeros((len(pats), len(payloads)), dtype=np.int64)
-    fp = [fold(p) if nc else p for p, nc in zip(pats, nocase)]
-    for k, raw in enumerate(payloads):
-        t = text_of(raw, whole)
-        tf = fold(t)
-        for i, p in enumerate(fp):
-            c[i, k] = occurrences(tf if nocase[i] else t, p)
-    return c > 0, [int(x) for x in c.sum(axis=1)]
-
-
-def rule_model(hits, rules):
-    """bool[n_rules, n_pkts] from the (all_of, none_of) rules over the host hit matrix."""
-    out = np.ones((len(rules), hits.shape[1]), dtype=bool)
-    for r, (pos, neg) in enumerate(rules):
-        for i in pos:
-            out[r] &= hits[i]
-        for i in neg:
-            out[r] &= ~hits[i]
-    return out
-
-
-def words(bits):
-    """bool[..., n] -> uint64[..., ceil(n / 64)], LSB first, the bits behind n as 0"""
-    n = bits.shape[-1]
-    W = (n + 63) // 64
-    pad = np.zeros(bits.shape[:-1] + (W * 64 - n,), dtype=bool)
-    return np.packbits(np.concatenate([bits, pad], axis=-1), axis=-1, bitorder="little").view(np.uint64)
 
 
 def scan_raw(gm, n_rules, skip=()):
@@ -114,13 +60,13 @@ def scan_raw(gm, n_rules, skip=()):
 
 def check(gm, hits, counts, rules, skip=()):
     """one kmpgpu_scan_rules against the model: every word of every output, and nothing written behind them"""
-    want = rule_model(hits, rules)
+    want = MM.rule_rows(hits, rules)
     n_rules, n_pkts = want.shape
     W = (n_pkts + 63) // 64
     rc, got = scan_raw(gm, n_rules, skip)
     assert rc == 0, _lib.gpu_lib().kmpgpu_last_error()
-    expect = {"rule_pkt_counts": want.sum(axis=1).astype(np.uint64), "any": words(want.any(axis=0)) if n_rules else np.zeros(W, np.uint64),
-              "hits": words(want).reshape(-1), "counts": np.array(counts, dtype=np.uint64)}
+    expect = {"rule_pkt_counts": want.sum(axis=1).astype(np.uint64), "any": MM.words(want.any(axis=0)) if n_rules else np.zeros(W, np.uint64),
+              "hits": MM.words(want).reshape(-1), "counts": np.array(counts, dtype=np.uint64)}
     for name, e in expect.items():
         g = got[name]
         assert g[-1] == SENTINEL, name                                        # nothing behind the output
@@ -131,31 +77,6 @@ def check(gm, hits, counts, rules, skip=()):
         assert bad.size == 0, (name, [(int(j), hex(int(g[j])), hex(int(e[j]))) for j in bad[:6]])
     return got
 
-
-def flat_rules(rules):
-    off = np.zeros(len(rules) + 1, dtype=np.uint32)
-    off[1:] = np.cumsum([len(a) + len(b) for a, b in rules])
-    terms = np.array([t for a, b in rules for t in list(a) + [i | NOT for i in b]] or [0], dtype=np.uint32)
-    return off, terms
-
-
-@pytest.fixture(scope="module")
-def gm():
-    m = GpuMatcher(0)
-    yield m
-    m.close()
-
-
-def reset(gm):
-    gm.set_option(OPT_MODE, MODE_FILTER)
-    gm.set_option(OPT_KERNEL, KERNEL_AUTO)
-    gm.set_option(OPT_FUSED, 2)
-    gm.set_option(OPT_REPACK, 1)
-    gm.set_option(OPT_ACCUMULATE, 0)
-    gm.set_option(OPT_WHOLE_PAYLOAD, 0)
-
-
-KERNELS = [("auto", KERNEL_AUTO, 2), ("flat", KERNEL_FLAT, 0), ("packed", KERNEL_PACKED, 0)]
 
 POOL_PATS = [b"ab", b"cdA", b"B", b"abcd", b"dd", b"aBc", b"ba", b"AB", b"cab", b"dAb"]
 
@@ -182,7 +103,7 @@ def pool():
     """8193 small payloads x POOL_PATS and their host model, computed once: the edge tests take prefixes of it"""
     rng = random.Random(8193)
     payloads = small_payloads(rng, 8193, POOL_PATS)
-    per_payload = np.array([[occurrences(t, p) for t in payloads] for p in POOL_PATS], dtype=np.int64)
+    per_payload = MM.per_payload(MM.starts(payloads, POOL_PATS))
     hits = per_payload > 0
     assert all(0 < h.sum() < len(payloads) for h in hits)                     # every pattern hits some payloads and misses others
     return payloads, hits, np.cumsum(per_payload, axis=1)
@@ -223,7 +144,7 @@ def test_column_edges(gm, pool, n_pkts):
     got = check(gm, hits, counts, EDGE_RULES)
     # an all-negated rule matches every payload that holds none of its patterns, the empty ones included
     empty = np.array([len(t) == 0 for t in payloads])
-    want = rule_model(hits, EDGE_RULES)
+    want = MM.rule_rows(hits, EDGE_RULES)
     assert (want[0][empty]).all() and int(got["rule_pkt_counts"][0]) == int((~(hits[0] | hits[2] | hits[4])).sum())
     assert int(got["rule_pkt_counts"][5]) == 0                                 # i and !i never matches
     # the Python view of the same call
@@ -320,32 +241,19 @@ def _pass_arena(rng, kind):
     return payloads, slots
 
 
-def _attach(gm, payloads, slots):
-    ln = np.array([len(t) for t in payloads], dtype=np.uint32)
-    size = np.array([len(s) for s in slots], dtype=np.uint64)
-    off = np.concatenate([[0], np.cumsum(size)[:-1]]).astype(np.uint64)
-    arena = np.frombuffer(b"".join(slots) + b"\0" * 64, dtype=np.uint8).copy()
-    keep = (torch.from_numpy(arena).cuda(), torch.from_numpy(off.astype(np.int64)).cuda(), torch.from_numpy(ln.astype(np.int32)).cuda())
-    torch.cuda.synchronize()
-    gm.attach_arena(*keep)
-    return keep
-
-
 @pytest.mark.parametrize("kind", ["uniform", "mixed", "empty", "dirty"])
 def test_every_pass(gm, kind):
     rng = random.Random(f"rules-{kind}")
     payloads, slots = _pass_arena(rng, kind)
-    hits, counts = host_model(payloads, MIXED_PATS, MIXED_NOCASE)
+    st = MM.starts(payloads, MIXED_PATS, nocase=MIXED_NOCASE)
+    hits, counts = MM.hits(st), MM.counts(st)
     assert (hits.sum(axis=1) > 0).all()
     keep = None
     try:
         reset(gm)
         gm.set_patterns(MIXED_PATS, nocase=MIXED_NOCASE)
         gm.set_rules(MIXED_RULES)
-        if slots is None:
-            gm.load_arena(K.HostArena.from_payloads(payloads))
-        else:
-            keep = _attach(gm, payloads, slots)
+        keep = load(gm, payloads, slots)
         for name, kernel, fused in KERNELS:
             gm.set_option(OPT_KERNEL, kernel); gm.set_option(OPT_FUSED, fused)
             check(gm, hits, counts, MIXED_RULES)
@@ -370,7 +278,8 @@ def test_arena_kept_in_place(gm):
     arena = np.zeros(pos + 64, dtype=np.uint8)
     for k, t in enumerate(payloads):
         arena[int(off[k]):int(off[k]) + len(t)] = np.frombuffer(t, dtype=np.uint8)
-    hits, counts = host_model(payloads, MIXED_PATS, MIXED_NOCASE)
+    st = MM.starts(payloads, MIXED_PATS, nocase=MIXED_NOCASE)
+    hits, counts = MM.hits(st), MM.counts(st)
     try:
         reset(gm)
         gm.set_option(OPT_REPACK, 0)
@@ -388,8 +297,9 @@ def test_arena_kept_in_place(gm):
 def test_whole_payload_switched_between_calls(gm):
     rng = random.Random(9)
     payloads = small_payloads(rng, 900, MIXED_PATS, nul=0.6)
-    model = {w: host_model(payloads, MIXED_PATS, MIXED_NOCASE, whole=bool(w)) for w in (0, 1)}
-    assert not np.array_equal(rule_model(model[0][0], MIXED_RULES), rule_model(model[1][0], MIXED_RULES))
+    st = {w: MM.starts(payloads, MIXED_PATS, nocase=MIXED_NOCASE, whole=bool(w)) for w in (0, 1)}
+    model = {w: (MM.hits(st[w]), MM.counts(st[w])) for w in (0, 1)}
+    assert not np.array_equal(MM.rule_rows(model[0][0], MIXED_RULES), MM.rule_rows(model[1][0], MIXED_RULES))
     try:
         reset(gm)
         gm.set_patterns(MIXED_PATS, nocase=MIXED_NOCASE)
@@ -410,7 +320,7 @@ def test_state(gm, pool):
     big, big_hits, big_counts = pool_prefix(pool, 5000)
     small, small_hits, small_counts = pool_prefix(pool, 70)
     rules = EDGE_RULES
-    off, terms = flat_rules(rules)
+    off, terms = MM.flat_rules(rules)
 
     def set_raw(ctx, off, terms, n):
         return g.kmpgpu_set_rules(ctx, off.ctypes.data_as(_lib.u32p), terms.ctypes.data_as(_lib.u32p), n)
@@ -498,7 +408,8 @@ def udp1000(tokens):
     """udp_1000.pcap x the 97 tokens: payloads, host hit matrix, totals, 40 generated rules and their rows"""
     arena = K.HostArena.from_pcap(os.path.join(DATA, "udp_1000.pcap"), "udp")
     payloads = [arena.payload(k) for k in range(arena.n_pkts)]
-    hits, counts = host_model(payloads, tokens)
+    st = MM.starts(payloads, tokens)
+    hits, counts = MM.hits(st), MM.counts(st)
     rng = random.Random(1000)
     live = [i for i in range(len(tokens)) if hits[i].any()]
     rules = []
@@ -506,7 +417,7 @@ def udp1000(tokens):
         pos = [rng.choice(live) if rng.random() < 0.8 else rng.randrange(len(tokens)) for _ in range(rng.randrange(0, 4))]
         neg = [rng.choice(live) if rng.random() < 0.6 else rng.randrange(len(tokens)) for _ in range(rng.randrange(0 if pos else 1, 3))]
         rules.append((pos, neg))
-    want = rule_model(hits, rules)
+    want = MM.rule_rows(hits, rules)
     assert want.any() and not want.all()
     return arena, hits, counts, rules, want
 
@@ -536,12 +447,6 @@ def _rules_file(path, rules):
     path.write_text("\n".join(lines) + "\n")
 
 
-def _strip_elapsed(out):
-    lines = out.splitlines(keepends=True)
-    assert lines and lines[-1].startswith("Elapsed time = ") and lines[-1].endswith(" seconds\n")
-    return "".join(lines[:-1])
-
-
 CLI_RUNS = [("serial", []), ("openmp_data", ["1"]), ("openmp_data", ["3"])]
 
 
@@ -553,13 +458,12 @@ def test_cli_alerts_file(udp1000, tmp_path, run, with_packets):
     golden = open(os.path.join(GOLDEN, "stdout_udp_1000_udp.txt")).read()
     _rules_file(tmp_path / "rules.txt", rules)
     alerts, packets = tmp_path / "alerts.csv", tmp_path / "packets.csv"
-    env = dict(os.environ, KMPGPU_RULES_FILE=str(tmp_path / "rules.txt"), KMPGPU_ALERTS_FILE=str(alerts))
+    env = {"KMPGPU_RULES_FILE": str(tmp_path / "rules.txt"), "KMPGPU_ALERTS_FILE": str(alerts)}
     if with_packets:
         env["KMPGPU_PACKETS_FILE"] = str(packets)
-    r = subprocess.run([os.path.join(_lib.BINDIR, prog), os.path.join(DATA, "udp_1000.pcap"), os.path.join(DATA, "strings.txt"), *extra, "udp"],
-                       capture_output=True, text=True, timeout=300, env=env)
+    r = run_cli(prog, extra=extra, env_extra=env, scrub=None)
     assert r.returncode == 0, r.stderr
-    assert _strip_elapsed(r.stdout) == golden
+    assert strip_elapsed(r.stdout) == golden
     got = [tuple(int(x) for x in line.split(",")) for line in alerts.read_text().splitlines()]
     assert got == sorted((int(k), int(i)) for i, k in np.argwhere(want))      # sorted by payload, then by rule, as written
     if with_packets:

@@ -5,7 +5,7 @@ The expectation is a numpy model, exact in every comparison: the selected indice
 index and arena are tests/prep_model.py's packed layout (gather_slots: every payload followed by 0x00 up to its slot's end) over
 the source's payloads at those indices.  dst.arena_download() is compared over [0, end of the last slot) plus the 64 zero bytes
 behind it, with index, arena_info and n_selected; counts on dst come from the CPU oracle over the selected payloads; hit rows,
-rule rows and offsets from the host model of tests/test_gpu_windows.py.
+rule rows and offsets from the host model of tests/match_model.py.
 
 Where every kernel's second code path starts, read off the launchers of csrc/kmp_select.hip and csrc/kmp_prep.hip:
 
@@ -31,7 +31,6 @@ Run on a real MI355X:  python -m pytest tests/test_gpu_select.py -m gpu
 import ctypes as C
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
@@ -40,17 +39,17 @@ from conftest import DATA, GOLDEN
 
 pytestmark = pytest.mark.gpu
 
-# torch first, as tests/test_gpu_parity.py explains: its wheel carries its own ROCm runtime libraries
+from gpu_support import reset, run_cli, strip_elapsed  # noqa: E402  (torch first)
+
 import torch  # noqa: E402
 
+import match_model as MM  # noqa: E402
 import multithreading_string_matching_amd as K  # noqa: E402
 import prep_model as PM  # noqa: E402
 from multithreading_string_matching_amd import _lib  # noqa: E402
 from multithreading_string_matching_amd.matcher import (  # noqa: E402
-    KERNEL_AUTO, MODE_FILTER, OPT_FUSED, OPT_KERNEL, OPT_MODE, OPT_NONTEMPORAL, OPT_REPACK, OPT_WHOLE_PAYLOAD, GpuMatcher, device_count,
-    select_words, selected_indices)
-from test_gpu_windows import (  # noqa: E402
-    all_counts, check_all, check_offsets, check_packets, check_rules, make_payloads, model, random_rules, random_windows, rule_rows, sub)
+    OPT_NONTEMPORAL, OPT_REPACK, OPT_WHOLE_PAYLOAD, GpuMatcher, device_count, select_words, selected_indices)
+from test_gpu_windows import check_all, make_payloads, random_rules, random_windows, sub  # noqa: E402
 
 EINVAL, ESTATE = -2, -3
 LENGTHS = [0, 1, 15, 16, 17, 48, 1500, 9000]
@@ -76,12 +75,6 @@ def dst():
     m = GpuMatcher(0)
     yield m
     m.close()
-
-
-def reset(*ms):
-    for m in ms:
-        for key, value in ((OPT_MODE, MODE_FILTER), (OPT_KERNEL, KERNEL_AUTO), (OPT_FUSED, 2), (OPT_REPACK, 1), (OPT_WHOLE_PAYLOAD, 0), (OPT_NONTEMPORAL, 1)):
-            m.set_option(key, value)
 
 
 def density(name, n, seed=0):
@@ -404,7 +397,7 @@ def test_dst_state_nocase_rules_windows(src, dst, oracle, kind):
         src.set_patterns(pats[:2])
         dst.set_patterns(pats, nocase=nocase); dst.set_windows(windows); dst.set_rules(rules)
         dst.load_arena(K.HostArena.from_payloads(payloads[:40]))                   # an arena, a fold and plans of its own first
-        assert dst.scan()[0].tolist() == all_counts(oracle, payloads[:40], pats, nocase)
+        assert dst.scan()[0].tolist() == MM.oracle_counts(oracle, payloads[:40], pats, nocase)
         src.load_arena(K.HostArena.from_payloads(payloads))
         for name in ("random_0.9", "alternating"):
             idx = dst.load_selected(src, density(name, len(payloads), seed=2))
@@ -498,7 +491,7 @@ def test_cascade_on_a_capture(src, dst, oracle, tokens):
     97 tokens over the subset.  Rows mapped back through the returned indices are the rows of a full pass restricted to them."""
     host = K.HostArena.from_pcap(os.path.join(DATA, "udp_1000.pcap"), "udp")
     payloads = [bytes(host.payload(k)) for k in range(host.n_pkts)]
-    _, free_hits = model(payloads, tokens)
+    free_hits = MM.hits(MM.starts(payloads, tokens))
     per = free_hits.sum(axis=1)
     first = int(np.argmin(np.where((per >= 20) & (per < len(payloads)), per, 1 << 30)))       # a token in some payloads, not in all
     try:
@@ -605,37 +598,24 @@ def test_two_devices_are_refused(src):
 # ------------------------------------------------------------------------------------------------
 # 8. the command lines: KMPGPU_EXPORT_FILE
 # ------------------------------------------------------------------------------------------------
-def _run(prog, extra, env_extra):
-    env = {k: v for k, v in os.environ.items() if not k.startswith("KMPGPU_")}
-    env.update(env_extra)
-    return subprocess.run([os.path.join(_lib.BINDIR, prog), os.path.join(DATA, "udp_1000.pcap"), os.path.join(DATA, "strings.txt"), *extra, "udp"],
-                          capture_output=True, text=True, timeout=300, env=env)
-
-
-def _strip_elapsed(out):
-    lines = out.splitlines(keepends=True)
-    assert lines and lines[-1].startswith("Elapsed time = ") and lines[-1].endswith(" seconds\n")
-    return "".join(lines[:-1])
-
-
 @pytest.mark.parametrize("prog,extra", [("serial", []), ("openmp_data", ["1"]), ("openmp_data", ["2"])])
 def test_cli_export_file(tokens, tmp_path, prog, extra):
     arena = K.HostArena.from_pcap(os.path.join(DATA, "udp_1000.pcap"), "udp")
     payloads = [bytes(arena.payload(k)) for k in range(arena.n_pkts)]
-    _, free_hits = model(payloads, tokens)
+    free_hits = MM.hits(MM.starts(payloads, tokens))
     busy = [int(i) for i in np.argsort(-free_hits.sum(axis=1))[:6]]
     with open(os.path.join(GOLDEN, "stdout_udp_1000_udp.txt")) as f:
         golden = f.read()
-    plain = _run(prog, extra, {})
-    assert plain.returncode == 0 and _strip_elapsed(plain.stdout) == golden
+    plain = run_cli(prog, extra=extra, env_extra={})
+    assert plain.returncode == 0 and strip_elapsed(plain.stdout) == golden
 
     def exported(env):
         out = tmp_path / "export.pcap"
         if out.exists():
             out.unlink()
-        r = _run(prog, extra, dict(env, KMPGPU_EXPORT_FILE=str(out)))
+        r = run_cli(prog, extra=extra, env_extra=dict(env, KMPGPU_EXPORT_FILE=str(out)))
         assert r.returncode == 0, r.stderr
-        assert _strip_elapsed(r.stdout) == golden                                         # stdout as without the variable
+        assert strip_elapsed(r.stdout) == golden                                         # stdout as without the variable
         back = K.HostArena.from_pcap(str(out), "udp")
         return [bytes(back.payload(k)) for k in range(back.n_pkts)]
 
@@ -647,7 +627,7 @@ def test_cli_export_file(tokens, tmp_path, prog, extra):
     rules = [([busy[4]], [busy[5]]), ([busy[5], busy[1]], [busy[4]])]
     rf = tmp_path / "rules.txt"
     rf.write_text("".join(" ".join([str(i) for i in pos] + [f"!{i}" for i in neg]) + "\n" for pos, neg in rules))
-    rows = rule_rows(free_hits, rules)
+    rows = MM.rule_rows(free_hits, rules)
     want = [payloads[int(k)] for k in np.flatnonzero(rows.any(axis=0))]
     assert 0 < len(want) < int(free_hits.any(axis=0).sum())
     assert exported({"KMPGPU_RULES_FILE": str(rf)}) == want
@@ -659,7 +639,7 @@ def test_cli_export_file(tokens, tmp_path, prog, extra):
         text += f"{i} {windows[i][0]} {'*' if windows[i][1] is None else windows[i][1]}\n"
     wf = tmp_path / "windows.txt"
     wf.write_text(text)
-    _, hits = model(payloads, tokens, windows)
+    hits = MM.hits(MM.starts(payloads, tokens, windows))
     want = [payloads[int(k)] for k in np.flatnonzero(hits.any(axis=0))]
     assert 0 < len(want) < int(free_hits.any(axis=0).sum())
     assert exported({"KMPGPU_WINDOWS_FILE": str(wf)}) == want

@@ -1,11 +1,8 @@
 """Whole-payload scanning (KMPGPU_OPT_WHOLE_PAYLOAD = 1: E_k = L_k, a 0x00 is a text byte like any other) on a real MI355X.
 
-The checker is the CPU oracle, unchanged (it implements the reference's strlen() rule), through one identity: for a byte r that
-occurs in no pattern,
-    count_whole(payloads, p) == oracle.count(remap(payloads), p),    remap: every 0x00 -> r
--- a window equal to a NUL-free, r-free pattern holds neither byte, so the remapping neither makes nor destroys a match, and the
-remapped text has no 0x00 left to stop at.  Offsets and hit bitmaps are checked against a plain Python model (bytes.find from
-s + 1, no cut).  Every randomised test first asserts, on the CPU, that its input tells the two rules apart.
+The checker is the CPU oracle, unchanged (it implements the reference's strlen() rule), on the 0x00 bytes mapped to a byte that no
+pattern holds (oracle_counts_arena of tests/match_model.py, which says why that is the same count).  Offsets and hit bitmaps are
+checked against the host model there.  Every randomised test first asserts, on the CPU, that its input tells the two rules apart.
 
 Run on a real MI355X:  python -m pytest tests/test_gpu_whole_payload.py -m gpu
 """
@@ -22,79 +19,21 @@ from conftest import DATA, GOLDEN, ROOT
 
 pytestmark = pytest.mark.gpu
 
-# torch first, as tests/test_gpu_parity.py explains: its wheel carries its own ROCm runtime libraries
-import torch  # noqa: E402,F401
+from gpu_support import VARIANTS, gm, reset, run_cli, strip_elapsed  # noqa: E402,F401  (torch first)
 
+import torch  # noqa: E402
+
+import match_model as MM  # noqa: E402
 import multithreading_string_matching_amd as K  # noqa: E402
 from multithreading_string_matching_amd import _lib  # noqa: E402
 from multithreading_string_matching_amd.matcher import (  # noqa: E402
-    KERNEL_AUTO, KERNEL_FLAT, KERNEL_GENERAL, KERNEL_PACKED, MODE_AUTOMATON, MODE_FILTER, OPT_BLOCKS_PER_CU, OPT_DEPTH, OPT_FUSED,
-    OPT_KERNEL, OPT_MODE, GpuMatcher)
+    KERNEL_AUTO, KERNEL_FLAT, KERNEL_GENERAL, KERNEL_PACKED, OPT_ACCUMULATE, OPT_BLOCKS_PER_CU, OPT_DEPTH, OPT_FUSED, OPT_FUSED_UNIT, OPT_KERNEL,
+    OPT_MODE, OPT_REPACK, OPT_WHOLE_PAYLOAD)
 
-OPT_ACCUMULATE, OPT_REPACK, OPT_FUSED_UNIT, OPT_WHOLE = 6, 7, 8, 9
-R = 0xFF                                             # the remap byte: in no pattern of this file (asserted where it is used)
-TEXT = b"abcdeABCDE-" + bytes([0x01, 0x80, 0xC1, 0xFE])          # the text alphabet: no 0x00, no R
+TEXT = b"abcdeABCDE-" + bytes([0x01, 0x80, 0xC1, 0xFE])          # the text alphabet: no 0x00, no MM.REMAP
 FIXTURE_KEYS = ["udp.pcap:udp", "udp_1000.pcap:udp", "big_udp.pcap:udp", "very_big_udp.pcap:udp",
                 "tcp.pcap:tcp", "tcp.pcap:udp", "udp.pcap:tcp", "udp_1000.pcap:tcp"]
-# (name, mode, kernel, fused)
-VARIANTS = [("auto", MODE_FILTER, KERNEL_AUTO, 2), ("flat", MODE_FILTER, KERNEL_FLAT, 0), ("packed", MODE_FILTER, KERNEL_PACKED, 0),
-            ("general", MODE_FILTER, KERNEL_GENERAL, 0), ("automaton", MODE_AUTOMATON, KERNEL_GENERAL, 0), ("fused", MODE_FILTER, KERNEL_AUTO, 1)]
 LENGTHS = [1, 2, 3, 4, 8, 9, 16, 17, 40, 99]
-
-
-# ------------------------------------------------------------------------------------------------
-# the expected answers
-# ------------------------------------------------------------------------------------------------
-def fold(a):
-    if isinstance(a, (bytes, bytearray)):
-        return bytes(a).lower()
-    a = np.array(a, dtype=np.uint8, copy=True)
-    a[(a >= 0x41) & (a <= 0x5A)] += 0x20
-    return a
-
-
-def remap(a):
-    a = np.array(a, dtype=np.uint8, copy=True)
-    a[a == 0] = R
-    return a
-
-
-def want_whole(oracle, arena, off, ln, pats, nocase=None, threads=0):
-    assert bytes([R]) not in b"".join(pats) and b"\0" not in b"".join(pats)
-    cs = oracle.count(remap(arena), off, ln, pats, threads)[0]
-    if nocase is None:
-        return [int(x) for x in cs]
-    fo = oracle.count(remap(fold(arena)), off, ln, [fold(p) for p in pats], threads)[0]
-    return [int(fo[i]) if nocase[i] else int(cs[i]) for i in range(len(pats))]
-
-
-def want_strlen(oracle, arena, off, ln, pats, threads=0):
-    return [int(x) for x in oracle.count(arena, off, ln, pats, threads)[0]]
-
-
-def model_matches(payloads, pats, whole=True, nocase=None):
-    """(payload, offset, pattern) of every match, sorted: bytes.find from s + 1, cut at the first 0x00 only under the strlen rule"""
-    out = []
-    for k, text in enumerate(payloads):
-        E = len(text) if whole or 0 not in text else text.index(0)
-        for i, p in enumerate(pats):
-            t, q = (fold(text), fold(p)) if nocase and nocase[i] else (text, p)
-            s = t.find(q, 0, E)
-            while s != -1:
-                out.append((k, s, i))
-                s = t.find(q, s + 1, E)
-    return out if not out else sorted(out)
-
-
-def counts_of(matches, n_pat):
-    c = [0] * n_pat
-    for _, _, i in matches:
-        c[i] += 1
-    return c
-
-
-def triples(recs):
-    return sorted((int(r["packet"]), int(r["offset"]), int(r["pattern"])) for r in recs)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -161,28 +100,9 @@ def nul_payloads(rng, n, length, pats):
 
 
 @pytest.fixture(scope="module")
-def gm():
-    m = GpuMatcher(0)
-    yield m
-    m.close()
-
-
-@pytest.fixture(scope="module")
 def whole_golden():
     with open(os.path.join(GOLDEN, "whole_payload_counts.json")) as f:
         return json.load(f)["fixtures"]
-
-
-def reset(gm):
-    gm.set_option(OPT_MODE, MODE_FILTER)
-    gm.set_option(OPT_KERNEL, KERNEL_AUTO)
-    gm.set_option(OPT_FUSED, 2)
-    gm.set_option(OPT_REPACK, 1)
-    gm.set_option(OPT_ACCUMULATE, 0)
-    gm.set_option(OPT_FUSED_UNIT, 0)
-    gm.set_option(OPT_DEPTH, 0)
-    gm.set_option(OPT_BLOCKS_PER_CU, 0)
-    gm.set_option(OPT_WHOLE, 0)
 
 
 def select(gm, variant):
@@ -202,17 +122,17 @@ def test_every_kernel_family(gm, oracle, uniform, variant):
     payloads = nul_payloads(rng, 600, 1500 if uniform else None, pats)
     assert sum(1 for p in payloads if p.count(0) >= 2) > 300 and any(bytes(1024) in p for p in payloads) and any(0 not in p for p in payloads)
     arena = K.HostArena.from_payloads(payloads)
-    whole = want_whole(oracle, arena.bytes, arena.off, arena.len, pats)
-    strlen = want_strlen(oracle, arena.bytes, arena.off, arena.len, pats)
+    whole = MM.oracle_counts_arena(oracle, arena.bytes, arena.off, arena.len, pats, whole=True)
+    strlen = MM.oracle_counts_arena(oracle, arena.bytes, arena.off, arena.len, pats)
     assert whole != strlen and all(w >= s for w, s in zip(whole, strlen))
-    assert whole == counts_of(model_matches(payloads, pats), len(pats))             # the identity itself, on this input
+    assert whole == MM.counts(MM.starts(payloads, pats, whole=True))             # the identity itself, on this input
     assert sum(1 for w, s in zip(whole, strlen) if w != s) >= len(LENGTHS)
     reset(gm)
     select(gm, variant)
     gm.set_patterns(pats)
     gm.load_arena(arena)
     for opt, want in ((1, whole), (0, strlen), (1, whole)):                          # the same context, nothing reloaded in between
-        gm.set_option(OPT_WHOLE, opt)
+        gm.set_option(OPT_WHOLE_PAYLOAD, opt)
         got = gm.scan()[0].tolist()
         assert got == want, (variant[0], opt, [(pats[i], g, w) for i, (g, w) in enumerate(zip(got, want)) if g != w][:6])
     for depth in (2, 3, 5, 6, 8):                                                    # any depth is mapped to an instantiated one, never refused
@@ -245,25 +165,25 @@ def test_one_byte_zeroed_never_matches(gm, oracle, variant):
                 payloads.append(t)
         arena = K.HostArena.from_payloads(payloads)
         pats = [p, control]
-        whole = want_whole(oracle, arena.bytes, arena.off, arena.len, pats)
-        strlen = want_strlen(oracle, arena.bytes, arena.off, arena.len, pats)
+        whole = MM.oracle_counts_arena(oracle, arena.bytes, arena.off, arena.len, pats, whole=True)
+        strlen = MM.oracle_counts_arena(oracle, arena.bytes, arena.off, arena.len, pats)
         assert whole[0] == 0 and whole != strlen
         gm.set_patterns(pats)
         gm.load_arena(arena)
-        gm.set_option(OPT_WHOLE, 1)
+        gm.set_option(OPT_WHOLE_PAYLOAD, 1)
         assert gm.scan()[0].tolist() == whole, (variant[0], m)
-        gm.set_option(OPT_WHOLE, 0)
+        gm.set_option(OPT_WHOLE_PAYLOAD, 0)
         assert gm.scan()[0].tolist() == strlen, (variant[0], m)
         everything += payloads
         all_pats.append(p)
     # all lengths in one set (the fused pass with every pattern in its tables)
     arena = K.HostArena.from_payloads(everything)
     pats = all_pats + [control]
-    whole = want_whole(oracle, arena.bytes, arena.off, arena.len, pats)
-    assert whole == counts_of(model_matches(everything, pats), len(pats))
+    whole = MM.oracle_counts_arena(oracle, arena.bytes, arena.off, arena.len, pats, whole=True)
+    assert whole == MM.counts(MM.starts(everything, pats, whole=True))
     gm.set_patterns(pats)
     gm.load_arena(arena)
-    gm.set_option(OPT_WHOLE, 1)
+    gm.set_option(OPT_WHOLE_PAYLOAD, 1)
     assert gm.scan()[0].tolist() == whole, variant[0]
     reset(gm)
 
@@ -306,23 +226,23 @@ def test_payload_ends_without_padding(gm, oracle, with_empty):
     assert all(len(p) % 16 == 0 for p in payloads) and (with_empty == any(len(p) == 0 for p in payloads))
     arena = K.HostArena.from_payloads(payloads)
     assert arena.nbytes >= sum(max(16, len(p)) for p in payloads)
-    whole = want_whole(oracle, arena.bytes, arena.off, arena.len, pats)
-    strlen = want_strlen(oracle, arena.bytes, arena.off, arena.len, pats)
-    assert whole != strlen and whole == counts_of(model_matches(payloads, pats), len(pats))
+    whole = MM.oracle_counts_arena(oracle, arena.bytes, arena.off, arena.len, pats, whole=True)
+    strlen = MM.oracle_counts_arena(oracle, arena.bytes, arena.off, arena.len, pats)
+    assert whole != strlen and whole == MM.counts(MM.starts(payloads, pats, whole=True))
     # the input has what it is meant to have: matches that end at a payload's end, and windows across a boundary that would match
     joined = b"".join(payloads)
     assert sum(joined.count(p) for p in pats[:9]) > sum(whole[:9]) and any(t.endswith(p) for t in payloads for p in pats[:9] if t)
     reset(gm)
     gm.set_patterns(pats)
     gm.load_arena(arena)
-    gm.set_option(OPT_WHOLE, 1)
+    gm.set_option(OPT_WHOLE_PAYLOAD, 1)
     for v in VARIANTS:
         select(gm, v)
         assert gm.scan()[0].tolist() == whole, v[0]
     reset(gm)
-    gm.set_option(OPT_WHOLE, 1)
+    gm.set_option(OPT_WHOLE_PAYLOAD, 1)
     recs, found, counts = gm.scan_offsets(sum(whole) + 8)
-    assert found == sum(whole) and counts.tolist() == whole and triples(recs) == model_matches(payloads, pats)
+    assert found == sum(whole) and counts.tolist() == whole and MM.triples(recs) == sorted(MM.records(MM.starts(payloads, pats, whole=True)))
     reset(gm)
 
 
@@ -365,10 +285,11 @@ def test_payload_ends_with_dirty_padding(gm, oracle, gaps):
     pats = [rand_text(rng, m) for m in (2, 3, 4, 8, 9, 16, 17, 40)] + [b"b"]
     arena, off, ln, payloads, tails = _dirty_arena(rng, pats, 1200, gaps)
     assert tails > 100                                      # complete occurrences that run out of their payloads: none may count
-    whole = want_whole(oracle, arena, off, ln, pats)
-    strlen = want_strlen(oracle, arena, off, ln, pats)
-    model = model_matches(payloads, pats)
-    assert whole != strlen and whole == counts_of(model, len(pats))
+    whole = MM.oracle_counts_arena(oracle, arena, off, ln, pats, whole=True)
+    strlen = MM.oracle_counts_arena(oracle, arena, off, ln, pats)
+    st = MM.starts(payloads, pats, whole=True)
+    model = sorted(MM.records(st))
+    assert whole != strlen and whole == MM.counts(st)
     d_arena = torch.from_numpy(arena).cuda()
     d_off = torch.from_numpy(off.astype(np.int64)).cuda()
     d_len = torch.from_numpy(ln.astype(np.int32)).cuda()
@@ -382,12 +303,12 @@ def test_payload_ends_with_dirty_padding(gm, oracle, gaps):
         for v in VARIANTS:
             select(gm, v)
             for opt, want in ((1, whole), (0, strlen)):
-                gm.set_option(OPT_WHOLE, opt)
+                gm.set_option(OPT_WHOLE_PAYLOAD, opt)
                 assert gm.scan()[0].tolist() == want, (gaps, repack, v[0], opt)
         select(gm, VARIANTS[0])
-        gm.set_option(OPT_WHOLE, 1)
+        gm.set_option(OPT_WHOLE_PAYLOAD, 1)
         recs, found, counts = gm.scan_offsets(len(model) + 8)
-        assert found == len(model) and counts.tolist() == whole and triples(recs) == model, (gaps, repack)
+        assert found == len(model) and counts.tolist() == whole and MM.triples(recs) == model, (gaps, repack)
         r = gm.scan_packets(hits=True)
         assert r["counts"].tolist() == whole and int(r["hits"].sum()) == len({(k, i) for k, _, i in model}), (gaps, repack)
         assert gm.scan()[0].tolist() == whole
@@ -412,17 +333,17 @@ def test_fused_classed_groups_and_pool(gm, oracle, n_pats):
     pats = pats[:n_pats] + pats[:5] + [pats[7]]               # duplicates keep identical counts, one per index
     payloads = nul_payloads(rng, 700, None, pats[:200])
     arena = K.HostArena.from_payloads(payloads)
-    whole = want_whole(oracle, arena.bytes, arena.off, arena.len, pats, threads=8)
-    strlen = want_strlen(oracle, arena.bytes, arena.off, arena.len, pats, threads=8)
+    whole = MM.oracle_counts_arena(oracle, arena.bytes, arena.off, arena.len, pats, whole=True, threads=8)
+    strlen = MM.oracle_counts_arena(oracle, arena.bytes, arena.off, arena.len, pats, threads=8)
     assert whole != strlen and whole[:5] == whole[n_pats:n_pats + 5] and whole[7] == whole[-1]
     reset(gm)
     gm.set_patterns(pats)
     gm.load_arena(arena)
-    gm.set_option(OPT_WHOLE, 1)
+    gm.set_option(OPT_WHOLE_PAYLOAD, 1)
     for fused, unit in ((1, 0), (1, 1024), (0, 0)):
         gm.set_option(OPT_FUSED, fused); gm.set_option(OPT_FUSED_UNIT, unit)
         assert gm.scan()[0].tolist() == whole, (fused, unit)
-    gm.set_option(OPT_FUSED, 1); gm.set_option(OPT_FUSED_UNIT, 1024); gm.set_option(OPT_WHOLE, 0)
+    gm.set_option(OPT_FUSED, 1); gm.set_option(OPT_FUSED_UNIT, 1024); gm.set_option(OPT_WHOLE_PAYLOAD, 0)
     assert gm.scan()[0].tolist() == strlen
     reset(gm)
 
@@ -435,8 +356,8 @@ def test_fused_pool_on_a_large_arena(gm, oracle):
     base = nul_payloads(rng, 400, None, pats)
     payloads = [base[rng.randrange(len(base))] for _ in range(60_000)]
     arena = K.HostArena.from_payloads(payloads)
-    whole = want_whole(oracle, arena.bytes, arena.off, arena.len, pats, threads=8)
-    strlen = want_strlen(oracle, arena.bytes, arena.off, arena.len, pats, threads=8)
+    whole = MM.oracle_counts_arena(oracle, arena.bytes, arena.off, arena.len, pats, whole=True, threads=8)
+    strlen = MM.oracle_counts_arena(oracle, arena.bytes, arena.off, arena.len, pats, threads=8)
     assert whole != strlen
     reset(gm)
     gm.set_patterns(pats)
@@ -445,9 +366,9 @@ def test_fused_pool_on_a_large_arena(gm, oracle):
     gm.set_option(OPT_BLOCKS_PER_CU, 1)                       # few, large regions
     for unit in (1024, 0, 65536):
         gm.set_option(OPT_FUSED_UNIT, unit)
-        gm.set_option(OPT_WHOLE, 1)
+        gm.set_option(OPT_WHOLE_PAYLOAD, 1)
         assert gm.scan()[0].tolist() == whole, unit
-        gm.set_option(OPT_WHOLE, 0)
+        gm.set_option(OPT_WHOLE_PAYLOAD, 0)
         assert gm.scan()[0].tolist() == strlen, unit
     reset(gm)
 
@@ -462,9 +383,9 @@ def test_with_nocase_mixed_flags(gm, oracle):
     flags = [False, True, True, True, True, False, True, True, False, True, True, False, True, False]
     payloads = [p.replace(b"\x01", b"Q") for p in nul_payloads(rng, 500, None, words)]
     arena = K.HostArena.from_payloads(payloads)
-    whole = want_whole(oracle, arena.bytes, arena.off, arena.len, pats, flags)
-    assert whole == counts_of(model_matches(payloads, pats, nocase=flags), len(pats))
-    strlen = counts_of(model_matches(payloads, pats, whole=False, nocase=flags), len(pats))
+    whole = MM.oracle_counts_arena(oracle, arena.bytes, arena.off, arena.len, pats, flags, whole=True)
+    assert whole == MM.counts(MM.starts(payloads, pats, nocase=flags, whole=True))
+    strlen = MM.counts(MM.starts(payloads, pats, whole=False, nocase=flags))
     assert whole != strlen and whole[0] != whole[1] and whole[1] == whole[2] == whole[3]
     reset(gm)
     gm.load_arena(arena)
@@ -472,7 +393,7 @@ def test_with_nocase_mixed_flags(gm, oracle):
     for v in VARIANTS:
         select(gm, v)
         for opt, want in ((1, whole), (0, strlen)):
-            gm.set_option(OPT_WHOLE, opt)
+            gm.set_option(OPT_WHOLE_PAYLOAD, opt)
             assert gm.scan()[0].tolist() == want, (v[0], opt)
     reset(gm)
 
@@ -490,10 +411,11 @@ def test_offsets(gm, oracle, uniform):
     pats = cut_patterns(rng, texts, [2, 3, 5, 9, 17, 40], per=1) + [b"a", b"ab", b"E"]
     payloads = nul_payloads(rng, 400, 1500 if uniform else None, pats)
     arena = K.HostArena.from_payloads(payloads)
-    model = model_matches(payloads, pats)
-    whole = want_whole(oracle, arena.bytes, arena.off, arena.len, pats)
-    strlen = want_strlen(oracle, arena.bytes, arena.off, arena.len, pats)
-    assert whole != strlen and counts_of(model, len(pats)) == whole
+    st = MM.starts(payloads, pats, whole=True)
+    model = sorted(MM.records(st))
+    whole = MM.oracle_counts_arena(oracle, arena.bytes, arena.off, arena.len, pats, whole=True)
+    strlen = MM.oracle_counts_arena(oracle, arena.bytes, arena.off, arena.len, pats)
+    assert whole != strlen and MM.counts(st) == whole
     behind = [(k, s, i) for k, s, i in model if 0 in payloads[k][:s]]
     assert behind
     reset(gm)
@@ -505,17 +427,17 @@ def test_offsets(gm, oracle, uniform):
     before = gm.counts_read().tolist()                        # the context's running total: untouched by the offsets calls
     for kernel, fused in STREAMING:
         gm.set_option(OPT_KERNEL, kernel); gm.set_option(OPT_FUSED, fused)
-        gm.set_option(OPT_WHOLE, 1)
+        gm.set_option(OPT_WHOLE_PAYLOAD, 1)
         recs, found, counts = gm.scan_offsets(len(model) + 10)
         assert found == len(model) == sum(counts.tolist()) and counts.tolist() == whole, (kernel, fused)
-        got = triples(recs)
+        got = MM.triples(recs)
         assert got == model, (kernel, fused)
         assert set(behind) <= set(got)                        # records behind their payload's first 0x00
         recs, found, counts = gm.scan_offsets(7)              # a cap smaller than found: the full total all the same
-        assert found == len(model) and len(recs) == 7 and counts.tolist() == whole and set(triples(recs)) <= set(model)
-        gm.set_option(OPT_WHOLE, 0)
+        assert found == len(model) and len(recs) == 7 and counts.tolist() == whole and set(MM.triples(recs)) <= set(model)
+        gm.set_option(OPT_WHOLE_PAYLOAD, 0)
         recs, found, counts = gm.scan_offsets(len(model) + 10)
-        assert counts.tolist() == strlen and triples(recs) == model_matches(payloads, pats, whole=False), (kernel, fused)
+        assert counts.tolist() == strlen and MM.triples(recs) == sorted(MM.records(MM.starts(payloads, pats, whole=False))), (kernel, fused)
     assert gm.counts_read().tolist() == before
     reset(gm)
 
@@ -532,15 +454,12 @@ def test_packets(gm, oracle, uniform):
     n, P = len(payloads), len(pats)
 
     def expect(whole):
-        hits = np.zeros((P, n), dtype=bool)
-        model = model_matches(payloads, pats, whole=whole)
-        for k, _, i in model:
-            hits[i, k] = True
-        return hits, counts_of(model, P)
+        st = MM.starts(payloads, pats, whole=whole)
+        return MM.hits(st), MM.counts(st)
 
     hits_w, counts_w = expect(True)
     hits_s, counts_s = expect(False)
-    assert counts_w == want_whole(oracle, arena.bytes, arena.off, arena.len, pats) and counts_w != counts_s
+    assert counts_w == MM.oracle_counts_arena(oracle, arena.bytes, arena.off, arena.len, pats, whole=True) and counts_w != counts_s
     assert hits_w[4, 3] and not hits_s[:, 3].any() and (hits_w != hits_s).any()
     reset(gm)
     gm.set_patterns(pats)
@@ -552,7 +471,7 @@ def test_packets(gm, oracle, uniform):
     for kernel, fused in STREAMING:
         gm.set_option(OPT_KERNEL, kernel); gm.set_option(OPT_FUSED, fused)
         for opt, hits, counts in ((1, hits_w, counts_w), (0, hits_s, counts_s), (1, hits_w, counts_w)):
-            gm.set_option(OPT_WHOLE, opt)
+            gm.set_option(OPT_WHOLE_PAYLOAD, opt)
             r = gm.scan_packets(hits=True)
             assert np.array_equal(r["hits"], hits), (kernel, fused, opt)
             assert np.array_equal(r["any"], hits.any(axis=0)), (kernel, fused, opt)
@@ -573,12 +492,12 @@ def test_state_accumulate_and_bad_values(gm, oracle):
     whole, strlen = [0] * len(pats), [0] * len(pats)
     for bt in batches:
         a = K.HostArena.from_payloads(bt)
-        whole = [x + y for x, y in zip(whole, want_whole(oracle, a.bytes, a.off, a.len, pats))]
-        strlen = [x + y for x, y in zip(strlen, want_strlen(oracle, a.bytes, a.off, a.len, pats))]
+        whole = [x + y for x, y in zip(whole, MM.oracle_counts_arena(oracle, a.bytes, a.off, a.len, pats, whole=True))]
+        strlen = [x + y for x, y in zip(strlen, MM.oracle_counts_arena(oracle, a.bytes, a.off, a.len, pats))]
     assert whole != strlen
     reset(gm)
     gm.set_patterns(pats)
-    gm.set_option(OPT_WHOLE, 1)
+    gm.set_option(OPT_WHOLE_PAYLOAD, 1)
     gm.set_option(OPT_ACCUMULATE, 1)
     gm.counts_reset()
     for bt in batches:
@@ -589,25 +508,25 @@ def test_state_accumulate_and_bad_values(gm, oracle):
 
     g = _lib.gpu_lib()
     last = K.HostArena.from_payloads(batches[-1])
-    want_last = want_whole(oracle, last.bytes, last.off, last.len, pats)
+    want_last = MM.oracle_counts_arena(oracle, last.bytes, last.off, last.len, pats, whole=True)
     for bad in (2, -1, 1 << 40):
-        assert g.kmpgpu_set_option(gm._ctx, OPT_WHOLE, C.c_int64(bad)) == -2          # KMPGPU_EINVAL ...
+        assert g.kmpgpu_set_option(gm._ctx, OPT_WHOLE_PAYLOAD, C.c_int64(bad)) == -2          # KMPGPU_EINVAL ...
         assert gm.scan()[0].tolist() == want_last                                    # ... and the option is unchanged
-    gm.set_option(OPT_WHOLE, 0)
-    assert g.kmpgpu_set_option(gm._ctx, OPT_WHOLE, C.c_int64(2)) == -2
-    assert gm.scan()[0].tolist() == want_strlen(oracle, last.bytes, last.off, last.len, pats)
+    gm.set_option(OPT_WHOLE_PAYLOAD, 0)
+    assert g.kmpgpu_set_option(gm._ctx, OPT_WHOLE_PAYLOAD, C.c_int64(2)) == -2
+    assert gm.scan()[0].tolist() == MM.oracle_counts_arena(oracle, last.bytes, last.off, last.len, pats)
     # a pattern that holds a 0x00 is refused in either mode, and the set in place stays
     u8p = C.POINTER(C.c_uint8)
     buf = np.frombuffer(b"ab\0d", dtype=np.uint8)
     ptrs = (u8p * 1)(buf.ctypes.data_as(u8p))
     lens = (C.c_uint32 * 1)(4)
     for opt in (1, 0):
-        gm.set_option(OPT_WHOLE, opt)
+        gm.set_option(OPT_WHOLE_PAYLOAD, opt)
         assert g.kmpgpu_set_patterns(gm._ctx, ptrs, lens, 1) == -2
         assert b"0x00" in g.kmpgpu_last_error()
     # the one-shot helper
     assert K.matcher.count_matches(pats, last, whole_payload=True).tolist() == want_last
-    assert K.matcher.count_matches(pats, last).tolist() == want_strlen(oracle, last.bytes, last.off, last.len, pats)
+    assert K.matcher.count_matches(pats, last).tolist() == MM.oracle_counts_arena(oracle, last.bytes, last.off, last.len, pats)
     assert K.matcher.OPT_WHOLE_PAYLOAD == 9
     reset(gm)
 
@@ -625,15 +544,15 @@ def test_fixtures(gm, tokens, fixture_counts, whole_golden, key):
     gm.load_arena(K.HostArena.from_pcap(path, mode))
     for v in (VARIANTS[0], VARIANTS[2], VARIANTS[3], VARIANTS[5]):
         select(gm, v)
-        gm.set_option(OPT_WHOLE, 1)
+        gm.set_option(OPT_WHOLE_PAYLOAD, 1)
         assert gm.scan()[0].tolist() == want, (key, v[0])
-        gm.set_option(OPT_WHOLE, 0)
+        gm.set_option(OPT_WHOLE_PAYLOAD, 0)
         assert gm.scan()[0].tolist() == today, (key, v[0])
     reset(gm)
-    gm.set_option(OPT_WHOLE, 1)
+    gm.set_option(OPT_WHOLE_PAYLOAD, 1)
     gm.load_pcap_frames(path, mode)                           # extraction on the device
     assert gm.scan()[0].tolist() == want, key
-    gm.set_option(OPT_WHOLE, 0)
+    gm.set_option(OPT_WHOLE_PAYLOAD, 0)
     assert gm.scan()[0].tolist() == today, key
     reset(gm)
 
@@ -647,24 +566,9 @@ def test_golden_sums(fixture_counts, whole_golden):
 # ------------------------------------------------------------------------------------------------
 # 10. the drop-in command lines: KMPGPU_WHOLE_PAYLOAD=1
 # ------------------------------------------------------------------------------------------------
-def _strip_elapsed(out):
-    lines = out.splitlines(keepends=True)
-    assert lines and lines[-1].startswith("Elapsed time = ") and lines[-1].endswith(" seconds\n")
-    return "".join(lines[:-1])
-
-
 CLI_RUNS = [("serial", [], {}), ("openmp_data", ["2"], {}), ("openmp_task", ["2"], {"KMPGPU_DEVICE_EXTRACT": "0", "KMPGPU_BATCH_BYTES": "65536"}),
             ("openmp_task", ["1"], {"KMPGPU_DEVICE_EXTRACT": "1", "KMPGPU_BATCH_BYTES": "65536"}), ("serial", [], {"KMPGPU_DEVICE_EXTRACT": "1"}),
             ("serial", [], {"KMPGPU_RCCL": "1"})]
-
-
-def _run_cli(prog, extra, env_extra, pcap, mode):
-    env = {k: v for k, v in os.environ.items() if k != "KMPGPU_WHOLE_PAYLOAD"}
-    env.update(env_extra)
-    r = subprocess.run([os.path.join(_lib.BINDIR, prog), os.path.join(DATA, pcap), os.path.join(DATA, "strings.txt"), *extra, mode],
-                       capture_output=True, text=True, timeout=300, env=env)
-    assert r.returncode == 0, r.stderr
-    return r
 
 
 @pytest.mark.parametrize("key", ["udp_1000.pcap:udp", "very_big_udp.pcap:udp"])
@@ -674,12 +578,14 @@ def test_cli_whole_payload(tokens, fixture_counts, whole_golden, key, run):
     pcap, mode = key.split(":")
     want, today = whole_golden[key]["counts"], fixture_counts["fixtures"][key]["counts"]
     assert want != today
-    r = _run_cli(prog, extra, dict(env_extra, KMPGPU_WHOLE_PAYLOAD="1", KMPGPU_STATS="1"), pcap, mode)
-    assert _strip_elapsed(r.stdout) == K.format_report(tokens, want)
+    r = run_cli(prog, pcap, extra=extra, env_extra=dict(env_extra, KMPGPU_WHOLE_PAYLOAD="1", KMPGPU_STATS="1"), mode=mode, scrub="KMPGPU_WHOLE_PAYLOAD")
+    assert r.returncode == 0, r.stderr
+    assert strip_elapsed(r.stdout) == K.format_report(tokens, want)
     assert "text rule: whole payloads" in r.stderr
     for unset in ({}, {"KMPGPU_WHOLE_PAYLOAD": "0"}):
-        r = _run_cli(prog, extra, dict(env_extra, **unset), pcap, mode)
-        assert _strip_elapsed(r.stdout) == K.format_report(tokens, today)
+        r = run_cli(prog, pcap, extra=extra, env_extra=dict(env_extra, **unset), mode=mode, scrub="KMPGPU_WHOLE_PAYLOAD")
+        assert r.returncode == 0, r.stderr
+        assert strip_elapsed(r.stdout) == K.format_report(tokens, today)
 
 
 @pytest.mark.parametrize("prog,extra", [("serial", []), ("openmp_data", ["3"])])
@@ -687,17 +593,18 @@ def test_cli_offsets_and_packets_files(tokens, tmp_path, prog, extra):
     host = K.HostArena.from_pcap(os.path.join(DATA, "udp_1000.pcap"), "udp")
     payloads = [bytes(host.payload(k)) for k in range(host.n_pkts)]
     for whole in (True, False):
-        model = model_matches(payloads, tokens, whole=whole)
+        model = sorted(MM.records(MM.starts(payloads, tokens, whole=whole)))
         off, pk = tmp_path / f"offsets{whole}.csv", tmp_path / f"packets{whole}.csv"
         env = {"KMPGPU_OFFSETS_FILE": str(off), "KMPGPU_PACKETS_FILE": str(pk)}
         if whole:
             env["KMPGPU_WHOLE_PAYLOAD"] = "1"
-        _run_cli(prog, extra, env, "udp_1000.pcap", "udp")
+        r = run_cli(prog, extra=extra, env_extra=env, scrub="KMPGPU_WHOLE_PAYLOAD")
+        assert r.returncode == 0, r.stderr
         got = sorted(tuple(int(x) for x in line.split(",")) for line in off.read_text().splitlines() if line and line[0].isdigit())
         assert got == model, whole
         got = [tuple(int(x) for x in line.split(",")) for line in pk.read_text().splitlines() if line and line[0].isdigit()]
         assert got == sorted({(k, i) for k, _, i in model}), whole
-    assert model_matches(payloads, tokens, whole=True) != model_matches(payloads, tokens, whole=False)
+    assert sorted(MM.records(MM.starts(payloads, tokens, whole=True))) != sorted(MM.records(MM.starts(payloads, tokens, whole=False)))
 
 
 def test_mpi_dumping_whole_payload(tokens, fixture_counts, whole_golden):
@@ -711,7 +618,7 @@ def test_mpi_dumping_whole_payload(tokens, fixture_counts, whole_golden):
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
         assert r.returncode == 0, r.stderr[-2000:]
         out = r.stdout[r.stdout.index("Printing the number"):]
-        assert _strip_elapsed(out) == K.format_report(tokens, want)
+        assert strip_elapsed(out) == K.format_report(tokens, want)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -753,9 +660,9 @@ def test_full_size_1m(gm, oracle, shape):
     results = {}
     for name, kernel, fused in (("auto", KERNEL_AUTO, 0), ("flat", KERNEL_FLAT, 0), ("packed", KERNEL_PACKED, 0), ("general", KERNEL_GENERAL, 0), ("fused", KERNEL_AUTO, 1)):
         gm.set_option(OPT_KERNEL, kernel); gm.set_option(OPT_FUSED, fused)
-        gm.set_option(OPT_WHOLE, 1)
+        gm.set_option(OPT_WHOLE_PAYLOAD, 1)
         results[name] = gm.scan()[0].tolist()
-        gm.set_option(OPT_WHOLE, 0)
+        gm.set_option(OPT_WHOLE_PAYLOAD, 0)
         results[name + "/strlen"] = gm.scan()[0].tolist()
     first, first_s = results["auto"], results["auto/strlen"]
     assert all(v == (first_s if k.endswith("/strlen") else first) for k, v in results.items()), results
@@ -764,10 +671,10 @@ def test_full_size_1m(gm, oracle, shape):
     ns = 100_000
     end = int(off[ns])
     host = d_arena[:end + 64].cpu().numpy()
-    want = want_whole(oracle, host, off[:ns], ln[:ns], pats, threads=8)
-    assert want != want_strlen(oracle, host, off[:ns], ln[:ns], pats, threads=8)
+    want = MM.oracle_counts_arena(oracle, host, off[:ns], ln[:ns], pats, whole=True, threads=8)
+    assert want != MM.oracle_counts_arena(oracle, host, off[:ns], ln[:ns], pats, threads=8)
     gm.attach_arena(d_arena, d_off[:ns], d_len[:ns])
-    gm.set_option(OPT_WHOLE, 1)
+    gm.set_option(OPT_WHOLE_PAYLOAD, 1)
     for name, kernel, fused in (("auto", KERNEL_AUTO, 0), ("packed", KERNEL_PACKED, 0), ("general", KERNEL_GENERAL, 0), ("fused", KERNEL_AUTO, 1)):
         gm.set_option(OPT_KERNEL, kernel); gm.set_option(OPT_FUSED, fused)
         assert gm.scan()[0].tolist() == want, (shape, name)

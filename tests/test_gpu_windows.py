@@ -1,16 +1,13 @@
 """Per-pattern offset windows (kmpgpu_set_windows, GpuMatcher.set_windows) on a real MI355X.
 
-The expectation is a host model, payload by payload: t = payload[:E_k] (E_k = the first 0x00, or the payload's end under
-OPT_WHOLE_PAYLOAD), folded for a nocase pattern; every start of every pattern by bytes.find, overlapping starts included; the
-starts inside the pattern's window [first, last] are the records, their (pattern, payload) pairs the hit matrix, from which
-pkt_counts, any and the rule rows follow.  counts -- which the windows must not touch -- come from the CPU oracle.  Every
-comparison is exact.
+The expectation is the host model of tests/match_model.py: the starts inside the patterns' windows are the records, their (pattern,
+payload) pairs the hit matrix, from which pkt_counts, any and the rule rows follow.  counts -- which the windows must not touch --
+come from the CPU oracle.  Every comparison is exact.
 
 Run on a real MI355X:  python -m pytest tests/test_gpu_windows.py -m gpu
 """
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
@@ -19,130 +16,23 @@ from conftest import DATA, GOLDEN
 
 pytestmark = pytest.mark.gpu
 
-# torch first, as tests/test_gpu_parity.py explains: its wheel carries its own ROCm runtime libraries
-import torch  # noqa: E402
+from gpu_support import KERNELS, check_offsets, check_packets, check_rules, gm, reset, run_cli, strip_elapsed  # noqa: E402,F401  (torch first)
 
+import match_model as MM  # noqa: E402
 import multithreading_string_matching_amd as K  # noqa: E402
+from match_model import U32_MAX  # noqa: E402
 from multithreading_string_matching_amd import _lib  # noqa: E402
-from multithreading_string_matching_amd.matcher import (  # noqa: E402
-    KERNEL_AUTO, KERNEL_FLAT, KERNEL_PACKED, MODE_FILTER, OPT_FUSED, OPT_KERNEL, OPT_MODE, OPT_WHOLE_PAYLOAD, GpuMatcher)
+from multithreading_string_matching_amd.matcher import OPT_ACCUMULATE, OPT_FUSED, OPT_KERNEL, OPT_REPACK, OPT_WHOLE_PAYLOAD, GpuMatcher  # noqa: E402
 
-OPT_ACCUMULATE, OPT_REPACK = 6, 7
-U32_MAX = 0xFFFFFFFF
 ALPHABET = b"abcdAB"
 BEHIND = (5000, 6000)                                # behind the end of every payload of these tests (at most 2200 bytes)
-
-# (name, kernel, fused), as tests/test_gpu_packets.py: the automatic choice (fused for multi-pattern sets), the two streaming kernels
-KERNELS = [("auto", KERNEL_AUTO, 2), ("flat", KERNEL_FLAT, 0), ("packed", KERNEL_PACKED, 0)]
-
-
-# ------------------------------------------------------------------------------------------------
-# the host model
-# ------------------------------------------------------------------------------------------------
-def fold(b):
-    return bytes(b).lower()                          # ASCII A-Z only
-
-
-def text_end(t, whole=False):
-    z = -1 if whole else t.find(b"\0")
-    return len(t) if z < 0 else z
-
-
-def bounds(windows, n):
-    """[(first, last)] with last as a number, for n patterns; None / []: the default for every pattern"""
-    if not windows:
-        return [(0, U32_MAX)] * n
-    assert len(windows) == n
-    return [(a, U32_MAX if b is None else b) for a, b in windows]
-
-
-def model(payloads, pats, windows=None, nocase=None, whole=False):
-    """(records {(payload, offset, pattern)} in window, hits bool[n_pat, n_pkts])"""
-    nocase = nocase or [False] * len(pats)
-    win = bounds(windows, len(pats))
-    fp = [fold(p) if nc else p for p, nc in zip(pats, nocase)]
-    recs = set()
-    hits = np.zeros((len(pats), len(payloads)), dtype=bool)
-    for k, text in enumerate(payloads):
-        t = text[:text_end(text, whole)]
-        tf = fold(t)
-        for i, p in enumerate(fp):
-            src = tf if nocase[i] else t
-            first, last = win[i]
-            s = src.find(p)
-            while s >= 0:
-                if first <= s <= last:
-                    recs.add((k, s, i))
-                    hits[i, k] = True
-                s = src.find(p, s + 1)
-    return recs, hits
-
-
-def all_counts(oracle, payloads, pats, nocase=None, whole=False):
-    """what kmpgpu_scan returns: every match, windows or not (the oracle's strlen rule; whole payloads: on the 0x00 bytes mapped to
-    a byte that no pattern of these tests holds)"""
-    nocase = nocase or [False] * len(pats)
-    if whole:
-        assert all(b"\x01" not in p for p in pats)
-        payloads = [t.replace(b"\0", b"\x01") for t in payloads]
-    cs = oracle.count_payloads(payloads, pats)
-    if not any(nocase):
-        return [int(x) for x in cs]
-    fo = oracle.count_payloads([fold(t) for t in payloads], [fold(p) for p in pats])
-    return [int(fo[i]) if nocase[i] else int(cs[i]) for i in range(len(pats))]
-
-
-def rule_rows(hits, rules):
-    rows = np.zeros((len(rules), hits.shape[1]), dtype=bool)
-    for r, (pos, neg) in enumerate(rules):
-        row = np.ones(hits.shape[1], dtype=bool)
-        for i in pos:
-            row &= hits[i]
-        for i in neg:
-            row &= ~hits[i]
-        rows[r] = row
-    return rows
-
-
-def triples(recs):
-    return sorted((int(r["packet"]), int(r["offset"]), int(r["pattern"])) for r in recs)
-
-
-def check_offsets(gm, recs, counts):
-    got, found, cnt = gm.scan_offsets(max(sum(counts), 1))
-    assert found == len(recs)
-    assert cnt.tolist() == list(counts)
-    got = triples(got)
-    assert len(got) == len(set(got))                  # no record twice
-    want = sorted(recs)
-    assert got == want, ([x for x in got if x not in recs][:6], [x for x in want if x not in set(got)][:6])
-
-
-def check_packets(gm, hits, counts):
-    res = gm.scan_packets(hits=True)
-    bad = np.argwhere(res["hits"] != hits)
-    assert bad.size == 0, [(int(i), int(k), bool(hits[i, k])) for i, k in bad[:8]]
-    assert res["pkt_counts"].tolist() == hits.sum(axis=1).tolist()
-    assert res["any"].tolist() == hits.any(axis=0).tolist()
-    assert res["counts"].tolist() == list(counts)
-    return res
-
-
-def check_rules(gm, hits, rules, counts):
-    rows = rule_rows(hits, rules)
-    res = gm.scan_rules(hits=True)
-    bad = np.argwhere(res["hits"] != rows)
-    assert bad.size == 0, [(int(r), int(k), bool(rows[r, k])) for r, k in bad[:8]]
-    assert res["rule_pkt_counts"].tolist() == rows.sum(axis=1).tolist()
-    assert res["any"].tolist() == rows.any(axis=0).tolist()
-    assert res["counts"].tolist() == list(counts)
-    return res
 
 
 def check_all(gm, oracle, payloads, pats, windows, rules=None, nocase=None, whole=False, kernels=KERNELS):
     """the three calls that follow the windows, and the counts that do not, on every kernel setting"""
-    recs, hits = model(payloads, pats, windows, nocase, whole)
-    counts = all_counts(oracle, payloads, pats, nocase, whole)
+    st = MM.starts(payloads, pats, windows, nocase, whole)
+    recs, hits = MM.records(st), MM.hits(st, len(pats))
+    counts = MM.oracle_counts(oracle, payloads, pats, nocase, whole)
     for name, kernel, fused in kernels:
         gm.set_option(OPT_KERNEL, kernel); gm.set_option(OPT_FUSED, fused)
         check_offsets(gm, recs, counts)
@@ -151,22 +41,6 @@ def check_all(gm, oracle, payloads, pats, windows, rules=None, nocase=None, whol
             check_rules(gm, hits, rules, counts)
         assert gm.scan()[0].tolist() == counts, name
     return recs, hits, counts
-
-
-@pytest.fixture(scope="module")
-def gm():
-    m = GpuMatcher(0)
-    yield m
-    m.close()
-
-
-def reset(gm):
-    gm.set_option(OPT_MODE, MODE_FILTER)
-    gm.set_option(OPT_KERNEL, KERNEL_AUTO)
-    gm.set_option(OPT_FUSED, 2)
-    gm.set_option(OPT_REPACK, 1)
-    gm.set_option(OPT_ACCUMULATE, 0)
-    gm.set_option(OPT_WHOLE_PAYLOAD, 0)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -198,7 +72,7 @@ def sub(rng, payloads, m):
     """a piece of some payload's text (so that it matches)"""
     for _ in range(200):
         t = rng.choice(payloads)
-        t = t[:text_end(t)]
+        t = t[:MM.text_end(t)]
         if len(t) >= m:
             s = rng.randrange(len(t) - m + 1)
             return t[s:s + m]
@@ -336,7 +210,7 @@ def test_lengths_and_edges(gm, oracle, m, uniform):
         assert not hits[wins.index(BEHIND)].any() and not hits[nw + wins.index(BEHIND)].any()      # wholly behind every payload: never
         assert hits[0].any() and hits[wins.index((1024, 1024))].any()
         # [0, UINT32_MAX] on an index = no window on it
-        _, free = model(payloads, pats)
+        free = MM.hits(MM.starts(payloads, pats))
         assert (hits[wins.index((0, U32_MAX))] == free[0]).all() and (hits[wins.index((0, U32_MAX - 1))] == free[0]).all()
         assert (hits[0] != free[0]).any()
     finally:
@@ -413,7 +287,7 @@ def test_duplicates_with_a_window_each(gm, oracle):
         assert counts[0] == counts[2] == counts[4]
         rows = [hits[i].tolist() for i in (0, 2, 4)]
         assert rows[0] != rows[1] and rows[1] != rows[2] and rows[0] != rows[2]
-        assert rule_rows(hits, rules).sum(axis=1).min() > 0
+        assert MM.rule_rows(hits, rules).sum(axis=1).min() > 0
     finally:
         reset(gm)
 
@@ -436,7 +310,7 @@ def test_with_nocase_mixed_flags(gm, oracle):
         gm.set_windows(windows)
         gm.set_rules(rules)
         recs, hits, _ = check_all(gm, oracle, payloads, pats, windows, rules, nocase=nocase)
-        assert hits[0].sum() > model(payloads, pats, windows)[1][0].sum()           # folding found more inside the window
+        assert hits[0].sum() > MM.hits(MM.starts(payloads, pats, windows))[0].sum()           # folding found more inside the window
     finally:
         reset(gm)
 
@@ -490,7 +364,7 @@ def test_windows_are_pass_state(gm, oracle):
             recs, found, cnt = m.scan_offsets(4_000_000)
             pk = m.scan_packets(hits=True)
             ru = m.scan_rules(hits=True)
-            out.append((triples(recs), found, cnt.tolist(), pk["hits"].tobytes(), pk["pkt_counts"].tolist(), pk["any"].tobytes(), pk["counts"].tolist(),
+            out.append((MM.triples(recs), found, cnt.tolist(), pk["hits"].tobytes(), pk["pkt_counts"].tolist(), pk["any"].tobytes(), pk["counts"].tolist(),
                         ru["hits"].tobytes(), ru["rule_pkt_counts"].tolist(), ru["any"].tobytes(), ru["counts"].tolist(), m.scan()[0].tolist()))
         return out
 
@@ -536,7 +410,7 @@ def test_counters_are_untouched(gm, oracle):
         reset(gm)
         gm.set_patterns(pats)
         gm.load_arena(K.HostArena.from_payloads(payloads))
-        want = all_counts(oracle, payloads, pats)
+        want = MM.oracle_counts(oracle, payloads, pats)
         assert gm.scan()[0].tolist() == want
         gm.set_windows(windows)
         gm.set_rules([([0], [1])])
@@ -546,7 +420,8 @@ def test_counters_are_untouched(gm, oracle):
         gm.set_option(OPT_ACCUMULATE, 1)
         gm.counts_reset()
         gm.scan_enqueue(); gm.scan_enqueue()
-        recs, hits = model(payloads, pats, windows)
+        st = MM.starts(payloads, pats, windows)
+        recs, hits = MM.records(st), MM.hits(st)
         check_offsets(gm, recs, want)
         check_packets(gm, hits, want)
         check_rules(gm, hits, gm.rules, want)
@@ -585,9 +460,10 @@ def test_life_cycle_and_errors(gm, oracle):
         gm.load_arena(K.HostArena.from_payloads(payloads))
         windows = [(0, 0), (3, 900), (16, None)]
         gm.set_windows(windows)
-        recs, hits = model(payloads, pats, windows)
-        counts = all_counts(oracle, payloads, pats)
-        assert recs != model(payloads, pats)[0]
+        st, free = MM.starts(payloads, pats, windows), MM.starts(payloads, pats)
+        recs, hits = MM.records(st), MM.hits(st)
+        counts = MM.oracle_counts(oracle, payloads, pats)
+        assert recs != MM.records(free)
         # every refused call leaves the windows set before in force
         bad = [([0, 0], [1, 1], 2),                                    # n_pat differs from the context's
                ([0, 0, 0, 0], [1, 1, 1, 1], 4),
@@ -620,9 +496,8 @@ def test_life_cycle_and_errors(gm, oracle):
         check_packets(gm, hits, counts)
         gm.set_patterns(pats)
         assert gm.windows == []
-        free_recs, free_hits = model(payloads, pats)
-        check_offsets(gm, free_recs, counts)
-        check_packets(gm, free_hits, counts)
+        check_offsets(gm, MM.records(free), counts)
+        check_packets(gm, MM.hits(free), counts)
     finally:
         reset(gm)
 
@@ -630,24 +505,12 @@ def test_life_cycle_and_errors(gm, oracle):
 # ------------------------------------------------------------------------------------------------
 # 7. the command lines: KMPGPU_WINDOWS_FILE
 # ------------------------------------------------------------------------------------------------
-def _run(prog, extra, env_extra):
-    env = {k: v for k, v in os.environ.items() if not k.startswith("KMPGPU_")}
-    env.update(env_extra)
-    return subprocess.run([os.path.join(_lib.BINDIR, prog), os.path.join(DATA, "udp_1000.pcap"), os.path.join(DATA, "strings.txt"), *extra, "udp"],
-                          capture_output=True, text=True, timeout=300, env=env)
-
-
-def _strip_elapsed(out):
-    lines = out.splitlines(keepends=True)
-    assert lines and lines[-1].startswith("Elapsed time = ") and lines[-1].endswith(" seconds\n")
-    return "".join(lines[:-1])
-
-
 @pytest.mark.parametrize("prog,extra", [("serial", []), ("openmp_data", ["2"])])
 def test_cli_windows_file(tokens, tmp_path, prog, extra):
     arena = K.HostArena.from_pcap(os.path.join(DATA, "udp_1000.pcap"), "udp")
     payloads = [bytes(arena.payload(k)) for k in range(arena.n_pkts)]
-    free_recs, free_hits = model(payloads, tokens)
+    free = MM.starts(payloads, tokens)
+    free_recs, free_hits = MM.records(free), MM.hits(free)
     # a window on the patterns that hit most: anchored, a range, an open end, one behind everything
     busy = [int(i) for i in np.argsort(-free_hits.sum(axis=1))[:8]]
     kinds = [(0, 0), (0, 63), (16, None), (1, 200), BEHIND, (0, 15), (32, 1024), (0, None)]
@@ -661,26 +524,27 @@ def test_cli_windows_file(tokens, tmp_path, prog, extra):
     rules = [([busy[0]], []), ([busy[1]], [busy[2]]), ([busy[3], busy[5]], []), ([], [busy[7]])]
     rf = tmp_path / "rules.txt"
     rf.write_text("".join(" ".join([str(i) for i in pos] + [f"!{i}" for i in neg]) + "\n" for pos, neg in rules))
-    recs, hits = model(payloads, tokens, windows)
+    st = MM.starts(payloads, tokens, windows)
+    recs, hits = MM.records(st), MM.hits(st)
     assert 0 < len(recs) < len(free_recs)
     off, pk, al = tmp_path / "offsets.csv", tmp_path / "packets.csv", tmp_path / "alerts.csv"
-    r = _run(prog, extra, {"KMPGPU_WINDOWS_FILE": str(wf), "KMPGPU_OFFSETS_FILE": str(off), "KMPGPU_PACKETS_FILE": str(pk),
-                           "KMPGPU_RULES_FILE": str(rf), "KMPGPU_ALERTS_FILE": str(al)})
+    r = run_cli(prog, extra=extra, env_extra={"KMPGPU_WINDOWS_FILE": str(wf), "KMPGPU_OFFSETS_FILE": str(off), "KMPGPU_PACKETS_FILE": str(pk),
+                                              "KMPGPU_RULES_FILE": str(rf), "KMPGPU_ALERTS_FILE": str(al)})
     assert r.returncode == 0, r.stderr
     with open(os.path.join(GOLDEN, "stdout_udp_1000_udp.txt")) as f:
-        assert _strip_elapsed(r.stdout) == f.read()                                  # the counts do not follow the windows
+        assert strip_elapsed(r.stdout) == f.read()                                  # the counts do not follow the windows
     got = sorted(tuple(int(x) for x in line.split(",")) for line in off.read_text().splitlines())
     assert got == sorted(recs)
     got = [tuple(int(x) for x in line.split(",")) for line in pk.read_text().splitlines()]
     assert got == sorted((int(k), int(i)) for i, k in np.argwhere(hits))
     got = [tuple(int(x) for x in line.split(",")) for line in al.read_text().splitlines()]
-    assert got == sorted((int(k), int(r_)) for r_, k in np.argwhere(rule_rows(hits, rules)))
+    assert got == sorted((int(k), int(r_)) for r_, k in np.argwhere(MM.rule_rows(hits, rules)))
     # a windows file that does not parse, or one without an output file that it could act on: exit 1
     bad = tmp_path / "bad.txt"
     bad.write_text(f"{busy[0]} 0 0\n{busy[1]} 9 3\n")
-    r = _run(prog, extra, {"KMPGPU_WINDOWS_FILE": str(bad), "KMPGPU_PACKETS_FILE": str(pk)})
+    r = run_cli(prog, extra=extra, env_extra={"KMPGPU_WINDOWS_FILE": str(bad), "KMPGPU_PACKETS_FILE": str(pk)})
     assert r.returncode == 1 and "line 2: " in r.stderr and r.stdout == ""
-    r = _run(prog, extra, {"KMPGPU_WINDOWS_FILE": str(tmp_path / "none.txt"), "KMPGPU_PACKETS_FILE": str(pk)})
+    r = run_cli(prog, extra=extra, env_extra={"KMPGPU_WINDOWS_FILE": str(tmp_path / "none.txt"), "KMPGPU_PACKETS_FILE": str(pk)})
     assert r.returncode == 1 and r.stdout == ""
-    r = _run(prog, extra, {"KMPGPU_WINDOWS_FILE": str(wf)})
+    r = run_cli(prog, extra=extra, env_extra={"KMPGPU_WINDOWS_FILE": str(wf)})
     assert r.returncode == 1 and "no effect" in r.stderr and r.stdout == ""
