@@ -15,7 +15,7 @@
  *   E_k = L_k                                 whole payloads, KMPGPU_OPT_WHOLE_PAYLOAD = 1: a 0x00 is a text byte like any other
  *                                             (which matches nothing: patterns hold none).  Not the reference's behaviour.
  * Everything that counts, reports or marks matches -- kmpgpu_scan, kmpgpu_scan_enqueue, kmpgpu_scan_offsets,
- * kmpgpu_scan_packets, kmpgpu_scan_rules, kmpgpu_scan_relations, with or without KMPGPU_PAT_NOCASE -- uses the E_k of the option's value at the time of the call.
+ * kmpgpu_scan_packets, kmpgpu_scan_rules, kmpgpu_scan_relations, kmpgpu_scan_chains, with or without KMPGPU_PAT_NOCASE -- uses the E_k of the option's value at the time of the call.
  *
  * Conventions: plain pointers and sizes only; every function returns 0 or a negative KMPGPU_E*
  * code and never exits; kmpgpu_last_error() gives the text (per thread).  One context drives one GPU;
@@ -399,7 +399,8 @@ int  kmpgpu_set_windows(kmpgpu_ctx *ctx, const uint32_t *first /* [n_pat] */, co
  * KMPGPU_RULE_NOT; the bound that kmpgpu_set_rules checks is n_pat + n_rel (n_pat with none set), and kmpgpu_scan_rules runs the relation
  * kernel between its marking pass and its rules kernel -- only then.  n_pat + n_rel < 2^31.
  * NOT A CHAIN: every relation is decided on its own.  A rule of rel(a, b) and rel(b, c) asks for some pair (a, b) and some pair (b, c);
- * the two b need not be the same match.  Snort's chained contents (each relative to the match before) are not expressed.
+ * the two b need not be the same match.  Snort's chained contents (each relative to the match before) are a chain: kmpgpu_set_chains
+ * below.
  *
  * kmpgpu_set_relations copies rel[n_rel] and uploads it (16 bytes per relation of device memory, owned by the context, freed by
  * kmpgpu_destroy).  The relations belong to the pattern set current at the call: no patterns set: KMPGPU_ESTATE; a later
@@ -430,6 +431,62 @@ int  kmpgpu_set_relations(kmpgpu_ctx *ctx, const kmpgpu_relation *rel /* [n_rel]
 int  kmpgpu_scan_relations(kmpgpu_ctx *ctx, uint64_t *rel_pkt_counts_out /* [n_rel] or NULL */, uint64_t *any_out /* [W] or NULL */,
                            uint64_t *rel_hits_out /* [n_rel * W] or NULL */, uint64_t *counts_out /* [n_pat] or NULL: as kmpgpu_scan */,
                            kmpgpu_timing *t /* or NULL */);
+
+/* Content chains: every content measured from THE MATCH BEFORE IT (Snort / Suricata: content:"A"; content:"B"; distance:0; within:10;
+ * content:"C"; distance:5; -- C is measured from the same B that was measured from A), decided on the device behind the marking pass of
+ * kmpgpu_scan_packets.  A rule of rel(A, B) and rel(B, C) asks for less: its two B may be different matches, and on repetitive traffic
+ * (a header name twice) it fires where the signature does not.
+ * A chain is 2 .. KMPGPU_CHAIN_MAX contents p_0 .. p_{n-1}, each a pattern index; links j = 1 .. n-1 carry (dmin_j, dmax_j).  With
+ * (k, s, i) a match exactly as relations define it (it counts under the rules at the top of this file, E_k as KMPGPU_OPT_WHOLE_PAYLOAD
+ * says, overlapping starts, KMPGPU_PAT_NOCASE per pattern, AND it is in window) and m_i the length of pattern i:
+ *     chain_hit[c][k]     = there are matches (k, s_0, p_0) .. (k, s_{n-1}, p_{n-1}) with
+ *                           dmin_j <= (int64)s_j - ((int64)s_{j-1} + m_{p_{j-1}}) <= dmax_j   for every j = 1 .. n-1
+ *     chain_pkt_counts[c] = sum over k of chain_hit[c][k]
+ *     any[k]              = OR over c of chain_hit[c][k]
+ *     counts[i]           = exactly what kmpgpu_scan returns, as in the sibling calls
+ * dmin == INT32_MIN / dmax == INT32_MAX: that side is open, as for relations.  The definition is existential over all tuples, not
+ * greedy: the first B behind A may be out of reach of every C while a later one serves.  A pattern may repeat inside a chain and is
+ * taken literally: a, a, a is three occurrences, or fewer where a negative distance lets a match pair with itself.  A chain of two
+ * contents is bit-identical to the relation {p_0, p_1, dmin_1, dmax_1}.  Chains may share patterns and may be identical; each index
+ * gets its own row.  Layout as kmpgpu_scan_packets: W = ceil(n_pkts / 64) words per row, row c of chain_hits_out starts at
+ * chain_hits_out + c * W; the bits of index n_pkts and above are 0 in every output word.
+ *
+ * kmpgpu_set_chains copies and uploads the chains: chain c = links[chain_off[c] .. chain_off[c + 1]), chain_off[n_chains + 1].  Its first
+ * link names p_0 and must carry INT32_MIN / INT32_MAX: it is relative to nothing (a position constraint on p_0 is a window).  The chains
+ * belong to the pattern set current at the call: no patterns set: KMPGPU_ESTATE; a later kmpgpu_set_patterns /
+ * kmpgpu_set_patterns_flags drops them, as it drops rules, windows and relations; kmpgpu_set_relations keeps them (they name patterns,
+ * not rows).  chain_off[0] != 0, a decreasing chain_off, a chain of fewer than 2 or more than KMPGPU_CHAIN_MAX links, a pattern index
+ * >= n_pat, dmin > dmax, bounds on a first link, a NULL array with n_chains > 0, n_pat + n_rel + n_chains >= 2^31: KMPGPU_EINVAL, and the
+ * chains and rules set before stay in force.  n_chains == 0 clears the chains (the arrays may be NULL).  EVERY successful call drops the
+ * rules: the rows their terms name have changed.  So the order is patterns, relations, chains, rules.  (A kmpgpu_set_relations that
+ * would push n_pat + n_rel + n_chains to 2^31 is refused in the same way.)
+ *
+ * Chains as rule terms: while chains are set, chain c is term index n_pat + n_rel + c of kmpgpu_set_rules and may carry KMPGPU_RULE_NOT;
+ * the bound that kmpgpu_set_rules checks is n_pat + n_rel + n_chains, and kmpgpu_scan_rules runs the relation kernel where relations are
+ * set, then the chain kernel where chains are set, then the rules kernel.
+ *
+ * kmpgpu_scan_chains: synchronous, on the context's stream.  The marking pass of kmpgpu_scan_packets, then the chain kernel instead of
+ * the pattern-level reduce.  Every output may be NULL: chain_pkt_counts_out[n_chains], any_out[W], chain_hits_out[n_chains * W],
+ * counts_out[n_pat].  Preconditions and errors as kmpgpu_scan_packets (streaming kernels only; an arena kept in place is packed once;
+ * with n_pkts == 0 every output is 0 and nothing is launched; the context's counters stay as they are); no chains set: KMPGPU_ESTATE.
+ * *t (may be NULL): kernel_ms covers zeroing, scan launches and the chain kernel, launches counts it; under kmpgpu_profile_begin it is
+ * recorded behind the scan launches (in kmpgpu_scan_rules: between the relation kernel and the rules kernel).
+ * With no chains set every output of every other call is bit-identical to what it is without these two calls, with the same launches
+ * and device buffers.
+ * Cost (the figures of tools/chains.py go to profiles/chains.txt): the chains are n_chains further rows of the hit
+ * matrix, (n_chains x W2 + n_chains) x 8 bytes, zeroed with it, and KMPGPU_CHAIN_MAX x 16 bytes per chain for the chains themselves.
+ * The kernel reads n words of the matrix per (chain, 64 payloads) and then only the payloads that hold every content: one wavefront
+ * per such payload sweeps the text 64 offsets at a time with one carried position per link and no memory that grows with the payload;
+ * a link with an open side widens the sweep by about twice the payload's length. */
+#define KMPGPU_CHAIN_MAX 8
+typedef struct kmpgpu_chain_link {
+    uint32_t pattern;         /* pattern index (file order)                                                                   */
+    int32_t  dmin, dmax;      /* dmin <= start of this content - end of the one before <= dmax; first link: INT32_MIN, INT32_MAX */
+} kmpgpu_chain_link;
+int  kmpgpu_set_chains(kmpgpu_ctx *ctx, const uint32_t *chain_off /* [n_chains + 1] */, const kmpgpu_chain_link *links, uint32_t n_chains);
+int  kmpgpu_scan_chains(kmpgpu_ctx *ctx, uint64_t *chain_pkt_counts_out /* [n_chains] or NULL */, uint64_t *any_out /* [W] or NULL */,
+                        uint64_t *chain_hits_out /* [n_chains * W] or NULL */, uint64_t *counts_out /* [n_pat] or NULL: as kmpgpu_scan */,
+                        kmpgpu_timing *t /* or NULL */);
 
 /* The payloads a bitmap selects, compacted on the device into a packed arena that a second context owns: the consumer of any[] and of
  * the rows of kmpgpu_scan_packets / kmpgpu_scan_rules (the filter in front of a packet export -- only the selected bytes are downloaded

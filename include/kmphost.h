@@ -93,6 +93,12 @@ int  kmp_rules_parse(const char *path, uint32_t n_patterns, kmp_rules *out, char
  * >= n_relations: KMPHOST_EINVAL, "line N: ".  n_patterns + n_relations >= 2^31 (a term's bit 31 is KMP_RULE_NOT): KMPHOST_EINVAL
  * before the file is opened, errbuf without a line number.  kmp_rules_parse is this with n_relations = 0, where "r3" is no term at all. */
 int  kmp_rules_parse_rel(const char *path, uint32_t n_patterns, uint32_t n_relations, kmp_rules *out, char errbuf[KMP_RULES_ERRBUF]);
+/* ... and with chains as terms (kmpgpu_set_chains): "c<q>" / "!c<q>", q < n_chains a decimal chain index (the order of the chain lines of
+ * kmp_chains_parse), is encoded as n_patterns + n_relations + q.  A chain index >= n_chains: KMPHOST_EINVAL, "line N: ".
+ * n_patterns + n_relations + n_chains >= 2^31: KMPHOST_EINVAL before the file is opened.  kmp_rules_parse_rel is this with n_chains = 0,
+ * where "c3" is no term at all. */
+int  kmp_rules_parse_terms(const char *path, uint32_t n_patterns, uint32_t n_relations, uint32_t n_chains, kmp_rules *out,
+                           char errbuf[KMP_RULES_ERRBUF]);
 void kmp_rules_free(kmp_rules *r);
 
 /* ---- relations -------------------------------------------------------------------------------
@@ -113,6 +119,28 @@ typedef struct kmp_relations {
 } kmp_relations;
 int  kmp_relations_parse(const char *path, uint32_t n_patterns, kmp_relations *out, char errbuf[KMP_RELATIONS_ERRBUF]);
 void kmp_relations_free(kmp_relations *r);
+
+/* ---- chains ----------------------------------------------------------------------------------
+ * Not in the reference: the chains of kmpgpu_set_chains (include/kmpgpu.h) from a text file.  One chain per line,
+ *     <p0> <dmin> <dmax> <p1> [<dmin> <dmax> <p2> ...]
+ * 3n - 2 fields separated by blanks for a chain of n contents, 2 <= n <= KMP_CHAIN_MAX: pattern indices (positions in the pattern file,
+ * 0-based) with, between two of them, the bounds on (start of the next content) - (end of the one before), decimal and possibly
+ * negative; '*' for <dmin> means no lower bound (INT32_MIN), for <dmax> no upper bound (INT32_MAX).  Blank lines and lines whose first
+ * non-blank character is '#' are skipped; chain index = order of the chain lines.  off / links are what kmpgpu_set_chains takes
+ * (kmp_chain_link has the layout of kmpgpu_chain_link; a chain's first link carries INT32_MIN / INT32_MAX).
+ * KMPHOST_EIO: the file cannot be opened; KMPHOST_EINVAL: a field that is not a number (or does not fit 32 bits), a field count that is
+ * not 3n - 2, fewer than 2 or more than KMP_CHAIN_MAX contents, an index >= n_patterns, dmin > dmax -- errbuf then starts with
+ * "line N: " (N counts every line of the file, from 1). */
+#define KMP_CHAINS_ERRBUF 256
+#define KMP_CHAIN_MAX     8
+typedef struct kmp_chain_link { uint32_t pattern; int32_t dmin, dmax; } kmp_chain_link;
+typedef struct kmp_chains {
+    uint32_t        n;      /* number of chains                              */
+    uint32_t       *off;    /* [n + 1]                                       */
+    kmp_chain_link *links;  /* [off[n]]                                      */
+} kmp_chains;
+int  kmp_chains_parse(const char *path, uint32_t n_patterns, kmp_chains *out, char errbuf[KMP_CHAINS_ERRBUF]);
+void kmp_chains_free(kmp_chains *c);
 
 /* ---- offset windows --------------------------------------------------------------------------
  * Not in the reference: the windows of kmpgpu_set_windows (include/kmpgpu.h) from a text file.  One window per line,

@@ -25,6 +25,8 @@ KMP_PCAP_ERRBUF = 256
 KMP_RULES_ERRBUF = 256
 KMP_WINDOWS_ERRBUF = 256
 KMP_RELATIONS_ERRBUF = 256
+KMP_CHAINS_ERRBUF = 256
+CHAIN_MAX = 8              # KMPGPU_CHAIN_MAX / KMP_CHAIN_MAX: contents of one chain
 REL_NO_MIN = -(1 << 31)    # kmpgpu_relation.dmin == INT32_MIN: no lower bound
 REL_NO_MAX = (1 << 31) - 1  # kmpgpu_relation.dmax == INT32_MAX: no upper bound
 RULE_NOT = 0x80000000      # KMPGPU_RULE_NOT / KMP_RULE_NOT: the term's pattern must not be in the payload
@@ -80,6 +82,16 @@ class Relations(C.Structure):
     _fields_ = [("n", C.c_uint32), ("rel", C.POINTER(Relation))]
 
 
+class ChainLink(C.Structure):
+    """kmpgpu_chain_link (include/kmpgpu.h) = kmp_chain_link (include/kmphost.h)."""
+    _fields_ = [("pattern", C.c_uint32), ("dmin", C.c_int32), ("dmax", C.c_int32)]
+
+
+class Chains(C.Structure):
+    """kmp_chains (include/kmphost.h)."""
+    _fields_ = [("n", C.c_uint32), ("off", u32p), ("links", C.POINTER(ChainLink))]
+
+
 class Arena(C.Structure):
     """kmp_arena (include/kmphost.h)."""
     _fields_ = [
@@ -118,7 +130,10 @@ HOST_API = {
     "kmp_patterns_free": (None, [C.POINTER(Patterns)]),
     "kmp_rules_parse": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(Rules), C.c_char_p]),
     "kmp_rules_parse_rel": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(Rules), C.c_char_p]),
+    "kmp_rules_parse_terms": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Rules), C.c_char_p]),
     "kmp_rules_free": (None, [C.POINTER(Rules)]),
+    "kmp_chains_parse": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(Chains), C.c_char_p]),
+    "kmp_chains_free": (None, [C.POINTER(Chains)]),
     "kmp_relations_parse": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(Relations), C.c_char_p]),
     "kmp_relations_free": (None, [C.POINTER(Relations)]),
     "kmp_windows_parse": (C.c_int, [C.c_char_p, C.c_uint32, u32p, u32p, C.c_char_p]),
@@ -181,6 +196,8 @@ GPU_API = {
     "kmpgpu_set_windows": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint32]),
     "kmpgpu_set_relations": (C.c_int, [C.c_void_p, C.POINTER(Relation), C.c_uint32]),
     "kmpgpu_scan_relations": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
+    "kmpgpu_set_chains": (C.c_int, [C.c_void_p, u32p, C.POINTER(ChainLink), C.c_uint32]),
+    "kmpgpu_scan_chains": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
     "kmpgpu_load_selected": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, u64p]),
     "kmpgpu_synth_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(SynthParams)]),
     "kmpgpu_fixed_index": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32]),

@@ -32,6 +32,12 @@
  * (kmp_rules_parse_rel).  A relations file that does not parse, or the variable without the other two: message on stderr, exit 1,
  * before any GPU work.  stdout is what it is without the variable.
  *
+ * KMPGPU_CHAINS_FILE=<chains>, together with KMPGPU_RULES_FILE and KMPGPU_ALERTS_FILE, with or without KMPGPU_RELATIONS_FILE: content
+ * chains, each content relative to the match before it (kmpgpu_set_chains; the file format is kmp_chains_parse's, kmphost.h:
+ * "<p0> <dmin> <dmax> <p1> [<dmin> <dmax> <p2> ...]" per line), set on every shard's context behind the relations and before the rules,
+ * whose file may then name chain q as "c<q>" / "!c<q>" (kmp_rules_parse_terms).  A chains file that does not parse, or the variable
+ * without the other two: message on stderr, exit 1, before any GPU work.  stdout is what it is without the variable.
+ *
  * KMPGPU_WINDOWS_FILE=<windows>: per-pattern offset windows (kmpgpu_set_windows; the file format is kmp_windows_parse's, kmphost.h:
  * "<pattern index> <first> <last>" per line, '*' for no upper bound) on every shard's context.  They take effect on the files written
  * for KMPGPU_OFFSETS_FILE, KMPGPU_PACKETS_FILE and KMPGPU_RULES_FILE + KMPGPU_ALERTS_FILE: only the matches that start inside their
@@ -129,6 +135,8 @@ typedef struct shard_job {
 static uint32_t *g_win_first, *g_win_last;
 /* KMPGPU_RELATIONS_FILE: the relations every shard's context gets behind its patterns, before any rule is set (n == 0: none) */
 static kmp_relations g_relations;
+/* KMPGPU_CHAINS_FILE: the chains every shard's context gets behind its relations, before any rule is set (n == 0: none) */
+static kmp_chains g_chains;
 
 static int whole_payload_env(void)
 {
@@ -168,6 +176,8 @@ static void *shard_load(void *arg)
     if (g_win_first && kmpgpu_set_windows(j->ctx, g_win_first, g_win_last, j->pats->n)) return shard_fail(j, "kmpgpu_set_windows");
     _Static_assert(sizeof(kmp_relation) == sizeof(kmpgpu_relation), "kmp_relation has the layout of kmpgpu_relation");
     if (g_relations.n && kmpgpu_set_relations(j->ctx, (const kmpgpu_relation *)g_relations.rel, g_relations.n)) return shard_fail(j, "kmpgpu_set_relations");
+    _Static_assert(sizeof(kmp_chain_link) == sizeof(kmpgpu_chain_link), "kmp_chain_link has the layout of kmpgpu_chain_link");
+    if (g_chains.n && kmpgpu_set_chains(j->ctx, g_chains.off, (const kmpgpu_chain_link *)g_chains.links, g_chains.n)) return shard_fail(j, "kmpgpu_set_chains");
     if (j->frames) {
         /* only the bytes this shard's frames span are uploaded (kmpgpu_load_frames) */
         if (kmpgpu_load_frames(j->ctx, j->frames->bytes, j->frames->nbytes, j->frames->off + j->lo, j->frames->caplen + j->lo, j->cnt, j->tcp,
@@ -254,9 +264,22 @@ int main(int argc, char *argv[])
             exit(1);
         }
     }
+    /* ... and the chains */
+    const char *chains_path = getenv("KMPGPU_CHAINS_FILE");
+    if (chains_path && chains_path[0]) {
+        if (!rules_path || !alerts_path) {
+            fprintf(stderr, "KMPGPU_CHAINS_FILE goes together with KMPGPU_RULES_FILE and KMPGPU_ALERTS_FILE: %s is not set\n", rules_path ? "KMPGPU_ALERTS_FILE" : "KMPGPU_RULES_FILE");
+            exit(1);
+        }
+        char chains_err[KMP_CHAINS_ERRBUF];
+        if (kmp_chains_parse(chains_path, pats.n, &g_chains, chains_err)) {
+            fprintf(stderr, "error reading chains file %s: %s\n", chains_path, chains_err);
+            exit(1);
+        }
+    }
     if (rules_path) {
         char rules_err[KMP_RULES_ERRBUF];
-        if (kmp_rules_parse_rel(rules_path, pats.n, g_relations.n, &rules, rules_err)) {
+        if (kmp_rules_parse_terms(rules_path, pats.n, g_relations.n, g_chains.n, &rules, rules_err)) {
             fprintf(stderr, "error reading rules file %s: %s\n", rules_path, rules_err);
             exit(1);
         }
@@ -544,6 +567,7 @@ int main(int argc, char *argv[])
     kmp_patterns_free(&pats);
     kmp_rules_free(&rules);
     kmp_relations_free(&g_relations);
+    kmp_chains_free(&g_chains);
     free(g_win_first); free(g_win_last);
     return 0;
 }

@@ -444,11 +444,19 @@ int kmp_rules_parse(const char *path, uint32_t n_patterns, kmp_rules *out, char 
 
 int kmp_rules_parse_rel(const char *path, uint32_t n_patterns, uint32_t n_relations, kmp_rules *out, char errbuf[KMP_RULES_ERRBUF])
 {
+    return kmp_rules_parse_terms(path, n_patterns, n_relations, 0, out, errbuf);
+}
+
+int kmp_rules_parse_terms(const char *path, uint32_t n_patterns, uint32_t n_relations, uint32_t n_chains, kmp_rules *out, char errbuf[KMP_RULES_ERRBUF])
+{
     memset(out, 0, sizeof *out);
     if (errbuf) errbuf[0] = 0;
-    /* a term is a row below 2^31: bit 31 is KMP_RULE_NOT (kmpgpu_set_relations refuses such a set too) */
-    if ((uint64_t)n_patterns + n_relations >= (1ull << 31)) {
-        if (errbuf) snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations do not fit the 2^31 rows a term can name", n_patterns, n_relations);
+    /* a term is a row below 2^31: bit 31 is KMP_RULE_NOT (kmpgpu_set_relations and kmpgpu_set_chains refuse such a set too) */
+    if ((uint64_t)n_patterns + n_relations + n_chains >= (1ull << 31)) {
+        if (errbuf) {
+            if (n_chains) snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations + %u chains do not fit the 2^31 rows a term can name", n_patterns, n_relations, n_chains);
+            else snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations do not fit the 2^31 rows a term can name", n_patterns, n_relations);
+        }
         return KMPHOST_EINVAL;
     }
     FILE *fp = fopen(path, "rb");
@@ -472,18 +480,26 @@ int kmp_rules_parse_rel(const char *path, uint32_t n_patterns, uint32_t n_relati
             if (*p == '!') { neg = KMP_RULE_NOT; p++; }
             /* r<q>: relation q, where the caller has relations (without any the token is no term at all, as it always was) */
             const int is_rel = n_relations && p < end && *p == 'r';
-            if (is_rel) p++;
+            /* c<q>: chain q, in the same way */
+            const int is_chain = n_chains && p < end && *p == 'c';
+            if (is_rel || is_chain) p++;
             const char *digits = p;
             while (p < end && *p >= '0' && *p <= '9') { if (v < (1ull << 40)) v = v * 10 + (uint64_t)(*p - '0'); p++; }
             const char *stop = p;
             while (stop < end && !is_c_space((uint8_t)*stop)) stop++;   /* the whole token, for the message */
-            if (p == digits && neg && stop == p && !is_rel) {
+            if (p == digits && neg && stop == p && !is_rel && !is_chain) {
                 if (errbuf) snprintf(errbuf, KMP_RULES_ERRBUF, "line %zu: '!' without a pattern index", lineno);
                 rc = KMPHOST_EINVAL;
             } else if (p == digits || stop != p) {
-                if (errbuf) snprintf(errbuf, KMP_RULES_ERRBUF, "line %zu: '%.*s' is not a pattern index%s", lineno, (int)(stop - tok > 64 ? 64 : stop - tok), tok,
-                                     n_relations ? " or r<relation index>" : "");
+                if (errbuf) snprintf(errbuf, KMP_RULES_ERRBUF, "line %zu: '%.*s' is not a pattern index%s%s", lineno, (int)(stop - tok > 64 ? 64 : stop - tok), tok,
+                                     n_relations ? " or r<relation index>" : "", n_chains ? " or c<chain index>" : "");
                 rc = KMPHOST_EINVAL;
+            } else if (is_chain) {
+                if (v >= n_chains) {
+                    if (errbuf) snprintf(errbuf, KMP_RULES_ERRBUF, "line %zu: chain index %llu, but there are %u chains", lineno, (unsigned long long)v, n_chains);
+                    rc = KMPHOST_EINVAL;
+                } else
+                    rc = rules_push(&out->terms, &n_terms, &cap_terms, (n_patterns + n_relations + (uint32_t)v) | neg);
             } else if (is_rel) {
                 if (v >= n_relations) {
                     if (errbuf) snprintf(errbuf, KMP_RULES_ERRBUF, "line %zu: relation index %llu, but there are %u relations", lineno, (unsigned long long)v, n_relations);
@@ -615,6 +631,99 @@ void kmp_relations_free(kmp_relations *r)
     if (!r) return;
     free(r->rel);
     memset(r, 0, sizeof *r);
+}
+
+/* ============================ chains ==================================================== */
+
+int kmp_chains_parse(const char *path, uint32_t n_patterns, kmp_chains *out, char errbuf[KMP_CHAINS_ERRBUF])
+{
+    memset(out, 0, sizeof *out);
+    if (errbuf) errbuf[0] = 0;
+    FILE *fp = fopen(path, "rb");
+    if (!fp) {
+        if (errbuf) snprintf(errbuf, KMP_CHAINS_ERRBUF, "%s: %s", path, strerror(errno));
+        return KMPHOST_EIO;
+    }
+    char *line = NULL;
+    size_t line_cap = 0, lineno = 0, n_off = 0, cap_off = 0, n_links = 0, cap_links = 0;
+    ssize_t got;
+    int rc = rules_push(&out->off, &n_off, &cap_off, 0);
+    while (!rc && (got = getline(&line, &line_cap, fp)) >= 0) {
+        lineno++;
+        const char *p = line, *end = line + got;
+        while (p < end && is_c_space((uint8_t)*p)) p++;
+        if (p == end || *p == '#') continue;                           /* blank line, comment */
+        static const char *const what[3] = {"a pattern index", "a lower bound or '*'", "an upper bound or '*'"};
+        kmp_chain_link l[KMP_CHAIN_MAX];
+        uint32_t n = 0;                                                 /* contents so far */
+        int k = 0;                                                      /* the field that comes next: 0 an index, 1 dmin, 2 dmax */
+        int64_t lo = INT32_MIN, hi = INT32_MAX;                         /* the bounds in front of the next index (the first has none) */
+        while (p < end && !rc) {
+            const char *tok;
+            int tl;
+            int64_t v;
+            if (k == 0 && n == KMP_CHAIN_MAX) {
+                if (errbuf) snprintf(errbuf, KMP_CHAINS_ERRBUF, "line %zu: more than %d contents", lineno, KMP_CHAIN_MAX);
+                rc = KMPHOST_EINVAL;
+            } else if (!relations_field(&p, end, k != 0, k ? INT32_MIN : 0, k ? INT32_MAX : 0xFFFFFFFFll, k == 1 ? INT32_MIN : k == 2 ? INT32_MAX : 0, &v,
+                                        &tok, &tl)) {
+                if (errbuf) snprintf(errbuf, KMP_CHAINS_ERRBUF, "line %zu: '%.*s' is not %s", lineno, tl, tok, what[k]);
+                rc = KMPHOST_EINVAL;
+            } else if (k == 0) {
+                if (v >= n_patterns) {
+                    if (errbuf) snprintf(errbuf, KMP_CHAINS_ERRBUF, "line %zu: pattern index %lld, but there are %u patterns", lineno, (long long)v, n_patterns);
+                    rc = KMPHOST_EINVAL;
+                } else {
+                    l[n].pattern = (uint32_t)v; l[n].dmin = (int32_t)lo; l[n].dmax = (int32_t)hi;
+                    n++; k = 1;
+                }
+            } else if (k == 1) {
+                lo = v; k = 2;
+            } else {
+                hi = v; k = 0;
+                if (lo > hi) {
+                    if (errbuf) snprintf(errbuf, KMP_CHAINS_ERRBUF, "line %zu: lower bound %lld lies above upper bound %lld", lineno, (long long)lo, (long long)hi);
+                    rc = KMPHOST_EINVAL;
+                }
+            }
+        }
+        if (rc) break;
+        if (k != 1) {                                                   /* the line has to end behind an index */
+            if (errbuf) snprintf(errbuf, KMP_CHAINS_ERRBUF, "line %zu: the fields are <p0> <dmin> <dmax> <p1> [<dmin> <dmax> <p2> ...]: bounds without the content behind them", lineno);
+            rc = KMPHOST_EINVAL;
+        } else if (n < 2) {
+            if (errbuf) snprintf(errbuf, KMP_CHAINS_ERRBUF, "line %zu: a chain has at least 2 contents: <p0> <dmin> <dmax> <p1> ...", lineno);
+            rc = KMPHOST_EINVAL;
+        } else {
+            if (n_links + n > cap_links) {
+                const size_t nc = cap_links ? cap_links * 2 : 64;
+                kmp_chain_link *nv = (kmp_chain_link *)realloc(out->links, nc * sizeof *nv);
+                if (!nv) { rc = KMPHOST_ENOMEM; break; }
+                out->links = nv; cap_links = nc;
+            }
+            memcpy(out->links + n_links, l, n * sizeof l[0]);
+            n_links += n;
+            if (n_links > 0xFFFFFFFFull) rc = KMPHOST_EINVAL;
+            if (!rc) rc = rules_push(&out->off, &n_off, &cap_off, (uint32_t)n_links);
+        }
+    }
+    free(line);
+    fclose(fp);
+    if (!rc && n_off - 1 > 0x7FFFFFFFull) rc = KMPHOST_EINVAL;
+    if (rc) {
+        if (rc == KMPHOST_ENOMEM && errbuf) snprintf(errbuf, KMP_CHAINS_ERRBUF, "out of memory");
+        kmp_chains_free(out);
+        return rc;
+    }
+    out->n = (uint32_t)(n_off - 1);
+    return KMPHOST_OK;
+}
+
+void kmp_chains_free(kmp_chains *c)
+{
+    if (!c) return;
+    free(c->off); free(c->links);
+    memset(c, 0, sizeof *c);
 }
 
 /* ============================ offset windows ============================================ */

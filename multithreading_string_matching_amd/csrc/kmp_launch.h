@@ -1,5 +1,5 @@
 /* kmp_launch.h -- launch entry points of kmp_scan_*.hip / kmp_prep.hip / kmp_fold.hip / kmp_marks.hip / kmp_rules.hip / kmp_relations.hip /
- * kmp_select.hip, used
+ * kmp_chains.hip / kmp_select.hip, used
  * by the C-ABI layer (kmpgpu.hip), which alone decides what is launched; the tables kmp_launch_scan_multi takes come from kmp_tables.h. */
 #ifndef KMP_LAUNCH_H
 #define KMP_LAUNCH_H
@@ -126,6 +126,15 @@ hipError_t kmp_launch_relations(const unsigned long long *marks, uint64_t stride
                                 const kmp_pattern_dev *patterns, const uint8_t *arena, const uint8_t *fold, const uint64_t *pkt_off,
                                 const uint32_t *pkt_len, const void *windows, bool whole, uint32_t max_blocks, unsigned long long *rows,
                                 unsigned long long *rel_counts, unsigned long long *any, hipStream_t st);
+/* kmp_chains.hip: the chains of kmpgpu_set_chains, decided for the payloads that hold every content.  As kmp_launch_relations, but for
+ * chains[c * KMPGPU_CHAIN_MAX + i] = {p_i | F << 31, dmin_i, dmax_i, n}: link i < n of chain c (2 <= n <= KMPGPU_CHAIN_MAX, checked by the
+ * caller; the bounds of link 0 are not read, the records behind link n - 1 neither), F set where that pattern's bytes are compared in
+ * `fold`.  Word j < ceil(n_pkts / 64) of rows[c][stride] is written for every c, a chain's set bits are added to chain_counts[c] and ORed
+ * into any[]; the caller zeroes those two.  At most max_blocks blocks, grid-stride. */
+hipError_t kmp_launch_chains(const unsigned long long *marks, uint64_t stride, uint64_t n_pkts, const uint4 *chains, uint32_t n_chains,
+                             const kmp_pattern_dev *patterns, const uint8_t *arena, const uint8_t *fold, const uint64_t *pkt_off,
+                             const uint32_t *pkt_len, const void *windows, bool whole, uint32_t max_blocks, unsigned long long *rows,
+                             unsigned long long *chain_counts, unsigned long long *any, hipStream_t st);
 hipError_t kmp_launch_fixed_index(uint64_t *pkt_off, uint32_t *pkt_len, uint64_t n, uint32_t len, uint64_t stride,
                                   hipStream_t st);
 /* kmp_select.hip (kmpgpu_load_selected): the payloads of an index of n whose bit is set in select[ceil(n / 64)] (payload k: bit k & 63 of

@@ -162,7 +162,7 @@ struct kmpgpu_ctx {
     size_t              h_counts_cap = 0;
     unsigned long long *h_small = nullptr;            /* pinned, 16 words: where the loaders read small device results back (a copy to pageable
                                                          memory goes through the runtime's blocking staging path) */
-    unsigned long long *d_marks = nullptr;            /* the marking pass: hit matrix [n_pat + n_rel][stride], then pkt_counts[n_pat], any[stride], counts[n_pat], rel_pkt_counts[n_rel] */
+    unsigned long long *d_marks = nullptr;            /* the marking pass: hit matrix [n_pat + n_rel + n_chains][stride], then pkt_counts[n_pat], any[stride], counts[n_pat], rel_pkt_counts[n_rel], chain_pkt_counts[n_chains] */
     uint64_t            marks_cap = 0;                /* words */
     /* kmpgpu_set_rules / kmpgpu_scan_rules: the rules as the kernel reads them (kmp_launch.h, kmp_launch_rules) and the results */
     uint32_t            n_rules = 0;
@@ -178,6 +178,10 @@ struct kmpgpu_ctx {
     uint32_t            n_rel = 0;
     uint4              *d_relations = nullptr;
     std::vector<uint8_t> pat_fold;
+    /* kmpgpu_set_chains: KMPGPU_CHAIN_MAX link records per chain as the chain kernel reads them (kmp_launch.h, kmp_launch_chains); chain c
+     * is row n_pat + n_rel + c of the hit matrix and term n_pat + n_rel + c of a rule */
+    uint32_t            n_chains = 0;
+    uint4              *d_chains = nullptr;
 
     /* options */
     int mode = 0, blocks_per_cu = 0 /* auto */, depth = 0 /* auto */, nontemporal = 1, kernel_sel = 0, fused = 2 /* auto */, accumulate = 0, repack = 1;
@@ -341,6 +345,13 @@ void drop_relations(kmpgpu_ctx *c)
     c->n_rel = 0;
 }
 
+/* ... and the chains */
+void drop_chains(kmpgpu_ctx *c)
+{
+    free_buffer(&c->d_chains);
+    c->n_chains = 0;
+}
+
 /* the patterns and all that is built on them */
 void release_patterns(kmpgpu_ctx *c)
 {
@@ -351,6 +362,7 @@ void release_patterns(kmpgpu_ctx *c)
     drop_rules(c);                                 /* their indices meant these patterns */
     drop_windows(c);                               /* ... and so did the windows' */
     drop_relations(c);                             /* ... and the relations' */
+    drop_chains(c);                                /* ... and the chains' */
     c->pat_fold.clear();
 }
 
@@ -1513,8 +1525,9 @@ namespace {
 struct MarkPass {
     bool empty = false;
     uint64_t W = 0, stride = 0, mat = 0;          /* words per row as the caller sees them / on the device (even); words of the matrix */
-    unsigned long long *d_mat = nullptr, *d_pc = nullptr, *d_any = nullptr, *d_cnt = nullptr;    /* [n_pat + n_rel][stride], [n_pat], [stride], [n_pat] */
+    unsigned long long *d_mat = nullptr, *d_pc = nullptr, *d_any = nullptr, *d_cnt = nullptr;    /* [n_pat + n_rel + n_chains][stride], [n_pat], [stride], [n_pat] */
     unsigned long long *d_rel = nullptr, *d_relc = nullptr;     /* the relations' rows inside d_mat (row n_pat on), [n_rel] */
+    unsigned long long *d_chain = nullptr, *d_chainc = nullptr; /* the chains' rows inside d_mat (row n_pat + n_rel on), [n_chains] */
     uint32_t launches = 0;
 };
 
@@ -1537,15 +1550,17 @@ int marking_pass(kmpgpu_ctx *c, const char *who, MarkPass *p)
         const int rr = repack_arena(c);
         if (rr) return rr;
     }
-    /* one device buffer, grown like the others: [marks (n_pat + n_rel) x stride][pkt_counts n_pat][any stride][counts n_pat]
-     * [rel_pkt_counts n_rel]; the scan kernels mark rows 0 .. n_pat - 1, the relation kernel writes the rows behind them */
-    const uint64_t mat = ((uint64_t)np + c->n_rel) * stride;
-    const uint64_t words = mat + np + stride + np + c->n_rel;
+    /* one device buffer, grown like the others: [marks (n_pat + n_rel + n_chains) x stride][pkt_counts n_pat][any stride][counts n_pat]
+     * [rel_pkt_counts n_rel][chain_pkt_counts n_chains]; the scan kernels mark rows 0 .. n_pat - 1, the relation kernel and the chain
+     * kernel write the rows behind them */
+    const uint64_t mat = ((uint64_t)np + c->n_rel + c->n_chains) * stride;
+    const uint64_t words = mat + np + stride + np + c->n_rel + c->n_chains;
     hipError_t e = grow_buffer(&c->d_marks, &c->marks_cap, words, EIGHTH);
     if (e != hipSuccess) return alloc_fail(e, "%s: the hit matrix (%llu bytes) could not be allocated", who, (unsigned long long)(words * 8u));
     p->stride = stride; p->mat = mat;
     p->d_mat = c->d_marks; p->d_pc = p->d_mat + mat; p->d_any = p->d_pc + np; p->d_cnt = p->d_any + stride;
     p->d_rel = p->d_mat + (uint64_t)np * stride; p->d_relc = p->d_cnt + np;
+    p->d_chain = p->d_rel + (uint64_t)c->n_rel * stride; p->d_chainc = p->d_relc + c->n_rel;
     HIP_TRY(hipEventRecord(c->ev[0], c->stream));
     /* zeroed before every pass: the bits of an earlier (larger) arena must not leak into this one */
     HIP_TRY(hipMemsetAsync(p->d_mat, 0, (size_t)words * sizeof(unsigned long long), c->stream));
@@ -1572,6 +1587,18 @@ int enqueue_relations(kmpgpu_ctx *c, const MarkPass &p)
     HIP_TRY(kmp_launch_relations(p.d_mat, p.stride, c->n_pkts, c->d_relations, c->n_rel, c->d_patterns, c->d_arena, c->d_fold, c->d_off,
                                  c->d_len, c->d_windows, c->whole_payload != 0, (uint32_t)c->cu_count * 8u, p.d_rel, p.d_relc, p.d_any,
                                  c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    return KMPGPU_OK;
+}
+
+/* The chain kernel behind a marking pass, in the same way: rows n_pat + n_rel .. of the matrix, their popcounts into p.d_chainc. */
+int enqueue_chains(kmpgpu_ctx *c, const MarkPass &p)
+{
+    hipEvent_t e1;
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_chains(p.d_mat, p.stride, c->n_pkts, c->d_chains, c->n_chains, c->d_patterns, c->d_arena, c->d_fold, c->d_off,
+                              c->d_len, c->d_windows, c->whole_payload != 0, (uint32_t)c->cu_count * 8u, p.d_chain, p.d_chainc, p.d_any,
+                              c->stream));
     HIP_TRY(profile_launched(c, e1));
     return KMPGPU_OK;
 }
@@ -1639,9 +1666,9 @@ int kmpgpu_set_rules(kmpgpu_ctx *c, const uint32_t *rule_off, const uint32_t *te
         ord.clear();
         for (int neg = 0; neg < 2; neg++)
             for (uint32_t j = rule_off[r]; j < rule_off[r + 1]; j++) {
-                if ((terms[j] & ~KMPGPU_RULE_NOT) >= c->n_pat + c->n_rel)           /* (n_pat + n_rel < 2^31: kmpgpu_set_relations) */
-                    return fail(KMPGPU_EINVAL, "kmpgpu_set_rules: rule %u: term %u names row %u of %u patterns + %u relations", r, j - rule_off[r],
-                                terms[j] & ~KMPGPU_RULE_NOT, c->n_pat, c->n_rel);
+                if ((terms[j] & ~KMPGPU_RULE_NOT) >= c->n_pat + c->n_rel + c->n_chains)    /* (the sum < 2^31: kmpgpu_set_relations, kmpgpu_set_chains) */
+                    return fail(KMPGPU_EINVAL, "kmpgpu_set_rules: rule %u: term %u names row %u of %u patterns + %u relations + %u chains", r,
+                                j - rule_off[r], terms[j] & ~KMPGPU_RULE_NOT, c->n_pat, c->n_rel, c->n_chains);
                 if (((terms[j] & KMPGPU_RULE_NOT) != 0) == (neg != 0)) ord.push_back(terms[j]);
             }
         /* filled up with a term that is loaded at the same time: a repeated term changes nothing */
@@ -1734,6 +1761,11 @@ int kmpgpu_scan_rules(kmpgpu_ctx *c, uint64_t *rule_pkt_counts_out, uint64_t *an
         const int rr = enqueue_relations(c, p);
         if (rr) return rr;
     }
+    /* ... and so do the chains' rows behind those */
+    if (c->n_chains) {
+        const int rr = enqueue_chains(c, p);
+        if (rr) return rr;
+    }
     hipEvent_t e1;
     HIP_TRY(profile_launch(c, &e1));
     HIP_TRY(kmp_launch_rules(p.d_mat, p.stride, c->n_pkts, c->d_rule_heads, c->d_rule_quads, c->n_rules, d_rows, d_rc, d_any, c->stream));
@@ -1743,7 +1775,7 @@ int kmpgpu_scan_rules(kmpgpu_ctx *c, uint64_t *rule_pkt_counts_out, uint64_t *an
     if (any_out) HIP_TRY(hipMemcpyAsync(any_out, d_any, p.W * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, p.d_cnt, np * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     if (rule_hits_out) HIP_TRY(download_rows(c, rule_hits_out, d_rows, p.W, p.stride, nr));
-    return finish_marking(c, p.launches + (c->n_rel ? 2u : 1u), t);
+    return finish_marking(c, p.launches + 1u + (c->n_rel ? 1u : 0u) + (c->n_chains ? 1u : 0u), t);
 }
 
 int kmpgpu_set_relations(kmpgpu_ctx *c, const kmpgpu_relation *rel, uint32_t n_rel)
@@ -1755,8 +1787,9 @@ int kmpgpu_set_relations(kmpgpu_ctx *c, const kmpgpu_relation *rel, uint32_t n_r
     uint4 *d_rel = nullptr;
     if (n_rel) {
         if (!rel) return fail(KMPGPU_EINVAL, "kmpgpu_set_relations: rel is NULL");
-        if ((uint64_t)c->n_pat + n_rel >= (1ull << 31))
-            return fail(KMPGPU_EINVAL, "kmpgpu_set_relations: %u patterns + %u relations do not fit the 2^31 rows a rule term can name", c->n_pat, n_rel);
+        if ((uint64_t)c->n_pat + n_rel + c->n_chains >= (1ull << 31))
+            return fail(KMPGPU_EINVAL, "kmpgpu_set_relations: %u patterns + %u relations%s do not fit the 2^31 rows a rule term can name", c->n_pat, n_rel,
+                        c->n_chains ? " + the chains" : "");
         std::vector<uint4> host(n_rel);
         for (uint32_t q = 0; q < n_rel; q++) {
             const kmpgpu_relation &r = rel[q];
@@ -1803,6 +1836,76 @@ int kmpgpu_scan_relations(kmpgpu_ctx *c, uint64_t *rel_pkt_counts_out, uint64_t 
     if (any_out) HIP_TRY(hipMemcpyAsync(any_out, p.d_any, p.W * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, p.d_cnt, np * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     if (rel_hits_out) HIP_TRY(download_rows(c, rel_hits_out, p.d_rel, p.W, p.stride, nq));
+    return finish_marking(c, p.launches + 1u, t);
+}
+
+int kmpgpu_set_chains(kmpgpu_ctx *c, const uint32_t *chain_off, const kmpgpu_chain_link *links, uint32_t n_chains)
+{
+    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_set_chains: ctx is NULL");
+    if (!c->d_patterns || c->n_pat == 0) return fail(KMPGPU_ESTATE, "kmpgpu_set_chains: no patterns set");
+    HIP_TRY(hipSetDevice(c->device));
+    uint4 *d_chains = nullptr;
+    if (n_chains) {
+        if (!chain_off || !links) return fail(KMPGPU_EINVAL, "kmpgpu_set_chains: NULL chain arrays");
+        if ((uint64_t)c->n_pat + c->n_rel + n_chains >= (1ull << 31))
+            return fail(KMPGPU_EINVAL, "kmpgpu_set_chains: %u patterns + %u relations + %u chains do not fit the 2^31 rows a rule term can name", c->n_pat,
+                        c->n_rel, n_chains);
+        if (chain_off[0] != 0) return fail(KMPGPU_EINVAL, "kmpgpu_set_chains: chain_off[0] is %u, not 0", chain_off[0]);
+        /* the device form (kmp_launch.h): KMPGPU_CHAIN_MAX records per chain, {pattern | fold << 31, dmin, dmax, n} per link, the records behind
+         * the last link repeating it */
+        std::vector<uint4> host((size_t)n_chains * KMPGPU_CHAIN_MAX);
+        for (uint32_t q = 0; q < n_chains; q++) {
+            if (chain_off[q + 1] < chain_off[q]) return fail(KMPGPU_EINVAL, "kmpgpu_set_chains: chain_off decreases at chain %u", q);
+            const uint32_t n = chain_off[q + 1] - chain_off[q];
+            if (n < 2 || n > KMPGPU_CHAIN_MAX) return fail(KMPGPU_EINVAL, "kmpgpu_set_chains: chain %u has %u contents, not 2 .. %d", q, n, KMPGPU_CHAIN_MAX);
+            const kmpgpu_chain_link *l = links + chain_off[q];
+            if (l[0].dmin != INT32_MIN || l[0].dmax != INT32_MAX)
+                return fail(KMPGPU_EINVAL, "kmpgpu_set_chains: chain %u: its first content is relative to nothing and carries no bounds (a window places it)", q);
+            for (uint32_t i = 0; i < KMPGPU_CHAIN_MAX; i++) {
+                const kmpgpu_chain_link &k = l[i < n ? i : n - 1];
+                if (k.pattern >= c->n_pat) return fail(KMPGPU_EINVAL, "kmpgpu_set_chains: chain %u names pattern %u of %u", q, k.pattern, c->n_pat);
+                if (k.dmin > k.dmax) return fail(KMPGPU_EINVAL, "kmpgpu_set_chains: chain %u: dmin %d lies above dmax %d", q, k.dmin, k.dmax);
+                /* bit 31: the pattern's bytes are compared in the folded copy of the arena */
+                host[(size_t)q * KMPGPU_CHAIN_MAX + i] = make_uint4(k.pattern | ((uint32_t)c->pat_fold[k.pattern] << 31), (uint32_t)k.dmin, (uint32_t)k.dmax, n);
+            }
+        }
+        hipError_t e = hipMalloc((void **)&d_chains, host.size() * sizeof(uint4));
+        if (e == hipSuccess) e = hipMemcpyAsync(d_chains, host.data(), host.size() * sizeof(uint4), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      /* (host is a local) */
+        if (e != hipSuccess) {
+            free_buffer(&d_chains);
+            return alloc_fail(e, "kmpgpu_set_chains: the chains could not be uploaded");
+        }
+    } else HIP_TRY(hipStreamSynchronize(c->stream));
+    drop_chains(c);
+    drop_rules(c);                                 /* the rows their terms named are no longer the same, whatever was set or cleared */
+    c->d_chains = d_chains; c->n_chains = n_chains;
+    return KMPGPU_OK;
+}
+
+int kmpgpu_scan_chains(kmpgpu_ctx *c, uint64_t *chain_pkt_counts_out, uint64_t *any_out, uint64_t *chain_hits_out, uint64_t *counts_out, kmpgpu_timing *t)
+{
+    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_scan_chains: ctx is NULL");
+    if (!c->d_patterns || c->n_pat == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan_chains: no patterns set");
+    if (c->n_chains == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan_chains: no chains set");
+    MarkPass p;
+    const int rc = marking_pass(c, "kmpgpu_scan_chains", &p);
+    if (rc) return rc;
+    const size_t np = c->n_pat, nq = c->n_chains;
+    if (p.empty) {
+        /* nothing to scan: no chain holds anywhere, and there are no bit words */
+        if (chain_pkt_counts_out) memset(chain_pkt_counts_out, 0, nq * sizeof(uint64_t));
+        if (counts_out) memset(counts_out, 0, np * sizeof(uint64_t));
+        if (t) { *t = kmpgpu_timing{}; }
+        return KMPGPU_OK;
+    }
+    const int rr = enqueue_chains(c, p);
+    if (rr) return rr;
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    if (chain_pkt_counts_out) HIP_TRY(hipMemcpyAsync(chain_pkt_counts_out, p.d_chainc, nq * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (any_out) HIP_TRY(hipMemcpyAsync(any_out, p.d_any, p.W * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, p.d_cnt, np * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (chain_hits_out) HIP_TRY(download_rows(c, chain_hits_out, p.d_chain, p.W, p.stride, nq));
     return finish_marking(c, p.launches + 1u, t);
 }
 

@@ -70,6 +70,7 @@ class GpuMatcher:
         self.rules: list = []      # (all_of, none_of) per rule, as set_rules took them
         self.windows: list = []    # (first, last) per pattern as set_windows took them (last None: unbounded), [] = none
         self.relations: list = []  # (a, b, dmin, dmax) per relation as set_relations took them (None: unbounded side), [] = none
+        self.chains: list = []     # (p0, (p1, dmin, dmax), ...) per chain as set_chains took them (None: unbounded side), [] = none
         self._keep = None          # objects whose device memory the context borrows
         self._comm = None          # the GpuComm this matcher is a rank of: closed before the context
 
@@ -98,6 +99,7 @@ class GpuMatcher:
         self.rules = []            # the library drops its rules with the pattern set they referred to
         self.windows = []          # ... and its windows
         self.relations = []        # ... and its relations
+        self.chains = []           # ... and its chains
 
     def set_rules(self, rules) -> None:
         """Content rules over the current patterns (kmpgpu_set_rules): a sequence of (all_of, none_of) pattern-index sequences;
@@ -106,7 +108,7 @@ class GpuMatcher:
         for a, b in rules:
             for i in a + b:
                 if not 0 <= i < _lib.RULE_NOT:
-                    raise ValueError(f"rule term {i}: not a pattern index (or rel(q))")
+                    raise ValueError(f"rule term {i}: not a pattern index (or rel(q), chain(c))")
         off = np.zeros(len(rules) + 1, dtype=np.uint32)
         off[1:] = np.cumsum([len(a) + len(b) for a, b in rules])
         terms = np.array([t for a, b in rules for t in a + [i | _lib.RULE_NOT for i in b]] or [0], dtype=np.uint32)
@@ -138,6 +140,39 @@ class GpuMatcher:
         if not 0 <= q < len(self.relations):
             raise ValueError(f"rel({q}): {len(self.relations)} relations are set")
         return len(self.patterns) + q
+
+    def set_chains(self, chains) -> None:
+        """Content chains over the current patterns (kmpgpu_set_chains): a sequence of (p0, (p1, dmin, dmax), (p2, dmin, dmax), ...), 2 to 8
+        contents each; chain c holds in a payload with in-window matches s_0 .. s_{n-1} of p_0 .. p_{n-1} where every content starts
+        dmin .. dmax bytes behind the end of THE MATCH of the content before it; None for dmin or dmax leaves that side unbounded.  None
+        or an empty sequence clears the chains.  Every successful call drops the rules, as the library does: set the relations, then the
+        chains, then the rules, whose terms may be chain(c)."""
+        chains = [(int(ch[0]),) + tuple((int(p), None if lo is None else int(lo), None if hi is None else int(hi)) for p, lo, hi in ch[1:])
+                  for ch in (chains or [])]
+        for ch in chains:
+            for p, lo, hi in ((ch[0], None, None),) + ch[1:]:
+                if not 0 <= p <= 0xFFFFFFFF:
+                    raise ValueError(f"chain {ch}: pattern indices are 32-bit")
+                if not all(x is None or _lib.REL_NO_MIN <= x <= _lib.REL_NO_MAX for x in (lo, hi)):
+                    raise ValueError(f"chain {ch}: bounds are 32-bit")
+        off = np.zeros(len(chains) + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([len(ch) for ch in chains])
+        arr = (_lib.ChainLink * max(int(off[-1]), 1))()
+        flat = [link for ch in chains for link in ((ch[0], None, None),) + ch[1:]]
+        for l, (p, lo, hi) in zip(arr, flat):
+            l.pattern = p
+            l.dmin = _lib.REL_NO_MIN if lo is None else lo
+            l.dmax = _lib.REL_NO_MAX if hi is None else hi
+        gpu_check(self._g.kmpgpu_set_chains(self._ctx, off.ctypes.data_as(u32p) if chains else None, arr if chains else None, len(chains)),
+                  "kmpgpu_set_chains")
+        self.chains = chains
+        self.rules = []            # the library drops its rules with the rows they referred to
+
+    def chain(self, c: int) -> int:
+        """The term of chain c in set_rules: it is row len(patterns) + len(relations) + c of the hit matrix."""
+        if not 0 <= c < len(self.chains):
+            raise ValueError(f"chain({c}): {len(self.chains)} chains are set")
+        return len(self.patterns) + len(self.relations) + c
 
     def set_windows(self, windows) -> None:
         """Offset windows of the current patterns (kmpgpu_set_windows): one (first, last) per pattern, last None = unbounded;
@@ -374,6 +409,28 @@ class GpuMatcher:
                                                 hit_w.ctypes.data if hits else None, counts.ctypes.data, C.byref(t)),
                   "kmpgpu_scan_relations")
         out = {"rel_pkt_counts": rel_counts[:nq], "counts": counts[:n], "timing": t,
+               "any": np.unpackbits(any_w[:W].view(np.uint8), bitorder="little")[:n_pkts].astype(bool)}
+        if hits:
+            bits = np.unpackbits(hit_w.reshape(nq, W).view(np.uint8), axis=1, bitorder="little") if nq * W else np.zeros((nq, 0), np.uint8)
+            out["hits"] = bits[:, :n_pkts].astype(bool)
+        return out
+
+    def scan_chains(self, hits: bool = False) -> dict:
+        """In which payloads which chains hold (kmpgpu_scan_chains): the marking pass of scan_packets and the chain kernel.
+        ``chain_pkt_counts`` (uint64[n_chains]) payloads in which chain c holds, ``any`` (bool[n_pkts]) some chain holds in payload k,
+        ``counts`` (uint64[n_pat]) as scan(), ``timing``; with hits=True also ``hits`` (bool[n_chains, n_pkts])."""
+        n, nq = len(self.patterns), len(self.chains)
+        n_pkts, _ = self.arena_info()
+        W = (n_pkts + 63) // 64
+        chain_counts = np.zeros(max(nq, 1), dtype=np.uint64)
+        counts = np.zeros(max(n, 1), dtype=np.uint64)
+        any_w = np.zeros(max(W, 1), dtype=np.uint64)
+        hit_w = np.zeros((nq, W) if hits and nq * W else 1, dtype=np.uint64)
+        t = Timing()
+        gpu_check(self._g.kmpgpu_scan_chains(self._ctx, chain_counts.ctypes.data, any_w.ctypes.data,
+                                             hit_w.ctypes.data if hits else None, counts.ctypes.data, C.byref(t)),
+                  "kmpgpu_scan_chains")
+        out = {"chain_pkt_counts": chain_counts[:nq], "counts": counts[:n], "timing": t,
                "any": np.unpackbits(any_w[:W].view(np.uint8), bitorder="little")[:n_pkts].astype(bool)}
         if hits:
             bits = np.unpackbits(hit_w.reshape(nq, W).view(np.uint8), axis=1, bitorder="little") if nq * W else np.zeros((nq, 0), np.uint8)
