@@ -488,6 +488,64 @@ int  kmpgpu_scan_chains(kmpgpu_ctx *ctx, uint64_t *chain_pkt_counts_out /* [n_ch
                         uint64_t *chain_hits_out /* [n_chains * W] or NULL */, uint64_t *counts_out /* [n_pat] or NULL: as kmpgpu_scan */,
                         kmpgpu_timing *t /* or NULL */);
 
+/* The alert list: which payloads hit which rows, as records instead of a bit matrix (the hit rows of kmpgpu_scan_packets and the rows of
+ * kmpgpu_scan_rules / _relations / _chains are rows x W x 8 bytes that the caller downloads and walks; the answer is normally a handful of
+ * (payload, rule) pairs).  The set bits of one row family are compacted on the device into 16-byte records, in capture order.
+ * family names the rows, and row[i][k] is exactly the bit the family's own call defines -- under windows, KMPGPU_OPT_WHOLE_PAYLOAD and
+ * KMPGPU_PAT_NOCASE, and for rules with relation and chain terms:
+ *     KMPGPU_ALERT_PATTERNS   hit[i][k] of kmpgpu_scan_packets,         index = pattern i
+ *     KMPGPU_ALERT_RULES      rule_hit[r][k] of kmpgpu_scan_rules,      index = rule r
+ *     KMPGPU_ALERT_RELATIONS  rel_hit[q][k] of kmpgpu_scan_relations,   index = relation q
+ *     KMPGPU_ALERT_CHAINS     chain_hit[c][k] of kmpgpu_scan_chains,    index = chain c
+ * The list is every (packet = k, index = i) with row[i][k] set and k < n_pkts, sorted by packet ascending, then index ascending; no pair
+ * appears twice, and the bits of index n_pkts and above never give a record.  The order does not depend on the run: no atomic decides a
+ * position.
+ *     *n_found        the length of the whole list (it does not depend on max_records)
+ *     *n_packets      the distinct payloads in it (may be NULL) = the set bits of the family's any[]
+ *     pkt_counts_out  [rows of the family] or NULL: what the family's own call returns under that name (pkt_counts, rule_pkt_counts,
+ *                     rel_pkt_counts, chain_pkt_counts)
+ *     counts_out      [n_pat] or NULL: exactly what kmpgpu_scan returns
+ * Where the records live: the first min(max_records, *n_found) records of the list -- a prefix of the sorted list, not an arbitrary
+ * subset; UINT64_MAX: all of them -- are built in a device buffer the context owns, 16 bytes per record, grown like the other buffers
+ * and freed by kmpgpu_destroy.  kmpgpu_alerts_read copies records [first, first + n) of that buffer to out (host memory); n == 0 copies
+ * nothing (out may be NULL).  A range that leaves the kept prefix: KMPGPU_EINVAL, and the list stays.  No list: KMPGPU_ESTATE -- no
+ * kmpgpu_scan_alerts has ended well on the context yet, or since then an arena was loaded, attached, extracted or selected INTO the
+ * context (kmpgpu_load_arena, kmpgpu_attach_arena, kmpgpu_load_frames, kmpgpu_load_selected as dst) or patterns were set.  Every
+ * kmpgpu_scan_alerts replaces the list, a failed one leaves none.
+ * Ordering: synchronous, on the context's stream.  The marking pass of kmpgpu_scan_packets (the same code: zeroing, scan launches), then
+ * what the family needs -- the pattern-level reduce, or the relation, chain and rules kernels as kmpgpu_scan_rules orders them --, then the
+ * list kernels: count, two scan kernels (the ones kmpgpu_load_frames and kmpgpu_load_selected use, in the scratch kept for them), the
+ * totals read once on the host, fill.
+ * Preconditions and errors as the family's own call: streaming kernels only (KMPGPU_OPT_MODE 1 or KMPGPU_OPT_KERNEL 1: KMPGPU_EINVAL); an
+ * arena kept in place with KMPGPU_OPT_REPACK = 0 is packed once; no patterns, or nothing of the family set: KMPGPU_ESTATE; a context
+ * between kmpgpu_load_frames_begin and _finish: KMPGPU_ESTATE; an unknown family or n_found == NULL: KMPGPU_EINVAL; a family of more than
+ * 0xFFFFFFFE / 16 = 268 435 455 rows: KMPGPU_EINVAL (a payload's records are scanned as a 32-bit byte length).  With n_pkts == 0
+ * everything is 0, nothing is launched and an empty list exists.  When the records cannot be allocated the call fails with KMPGPU_ENOMEM /
+ * KMPGPU_EHIP and the context stays usable.
+ * What stays as it is: the context's counters (also under KMPGPU_OPT_ACCUMULATE); every output of every other call is bit-identical with
+ * and without this call having run; kmpgpu_scan_packets and kmpgpu_scan_rules return the same before and after.
+ * *t (may be NULL): kernel_ms from the zeroing to the end of the fill kernel (the host's read of the totals lies inside), d2h_ms the small
+ * outputs, launches = the launches of the family's own call + 4 (count, two scan kernels, fill; + 3 where no record is kept and the fill
+ * is not launched).  Under kmpgpu_profile_begin the list kernels are recorded last, as three entries: count, the two scan kernels
+ * together, fill (where launched); in front of them the family's kernels as its own call records them, and for KMPGPU_ALERT_PATTERNS the
+ * pattern-level reduce as one entry.
+ * Cost (the figures of tools/alerts.py go to profiles/alerts.txt): the rows are read twice (count and fill), 32 bytes
+ * per (row, 256 payloads) and only where any[] has a bit; 20 bytes per payload of scan workspace are written and read; 16 bytes per
+ * kept record are written. */
+#define KMPGPU_ALERT_PATTERNS  0   /* rows of kmpgpu_scan_packets:   index = pattern  */
+#define KMPGPU_ALERT_RULES     1   /* rows of kmpgpu_scan_rules:     index = rule     */
+#define KMPGPU_ALERT_RELATIONS 2   /* rows of kmpgpu_scan_relations: index = relation */
+#define KMPGPU_ALERT_CHAINS    3   /* rows of kmpgpu_scan_chains:    index = chain    */
+typedef struct kmpgpu_alert {
+    uint64_t packet;          /* payload index in the arena                                */
+    uint32_t index;           /* row of the family: pattern, rule, relation or chain index */
+    uint32_t reserved;        /* 0                                                         */
+} kmpgpu_alert;
+int  kmpgpu_scan_alerts(kmpgpu_ctx *ctx, int family, uint64_t max_records, uint64_t *n_found, uint64_t *n_packets /* or NULL */,
+                        uint64_t *pkt_counts_out /* [rows of the family] or NULL */, uint64_t *counts_out /* [n_pat] or NULL: as kmpgpu_scan */,
+                        kmpgpu_timing *t /* or NULL */);
+int  kmpgpu_alerts_read(kmpgpu_ctx *ctx, kmpgpu_alert *out, uint64_t first, uint64_t n);
+
 /* The payloads a bitmap selects, compacted on the device into a packed arena that a second context owns: the consumer of any[] and of
  * the rows of kmpgpu_scan_packets / kmpgpu_scan_rules (the filter in front of a packet export -- only the selected bytes are downloaded
  * --, and the cascade: a cheap first stage selects, a costly second one -- a thousand patterns, nocase sets -- scans the subset with

@@ -117,6 +117,11 @@ class Match(C.Structure):
     _fields_ = [("packet", C.c_uint64), ("offset", C.c_uint32), ("pattern", C.c_uint32)]
 
 
+class Alert(C.Structure):
+    """kmpgpu_alert (include/kmpgpu.h)."""
+    _fields_ = [("packet", C.c_uint64), ("index", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 # name -> (restype, argtypes); also the list of symbols include/kmphost.h declares
 HOST_API = {
     "kmp_pcap_open": (C.c_void_p, [C.c_char_p, C.c_char_p]),
@@ -198,6 +203,8 @@ GPU_API = {
     "kmpgpu_scan_relations": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
     "kmpgpu_set_chains": (C.c_int, [C.c_void_p, u32p, C.POINTER(ChainLink), C.c_uint32]),
     "kmpgpu_scan_chains": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
+    "kmpgpu_scan_alerts": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, u64p, u64p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
+    "kmpgpu_alerts_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "kmpgpu_load_selected": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, u64p]),
     "kmpgpu_synth_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(SynthParams)]),
     "kmpgpu_fixed_index": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32]),

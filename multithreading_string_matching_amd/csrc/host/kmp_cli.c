@@ -17,10 +17,10 @@
  * Extension (the reference prints counts only, serial.c:163-166): with the environment variable
  * KMPGPU_OFFSETS_FILE=<path> every match is also written to <path> as "payload,offset,pattern"
  * lines (payload = index among the extracted payloads, pattern = index in the pattern file).
- * KMPGPU_PACKETS_FILE=<path>: which payloads hold which patterns (kmpgpu_scan_packets), one "payload,pattern" line per
+ * KMPGPU_PACKETS_FILE=<path>: which payloads hold which patterns (kmpgpu_scan_alerts over the rows of kmpgpu_scan_packets), one "payload,pattern" line per
  * pair that holds at least one match, sorted by payload, then by pattern (indices as in the offsets file).
  *
- * KMPGPU_RULES_FILE=<rules> with KMPGPU_ALERTS_FILE=<path>: content rules over the patterns (kmpgpu_set_rules, kmpgpu_scan_rules; the
+ * KMPGPU_RULES_FILE=<rules> with KMPGPU_ALERTS_FILE=<path>: content rules over the patterns (kmpgpu_set_rules, kmpgpu_scan_alerts; the
  * file format is kmp_rules_parse's, kmphost.h: one rule per line, terms are indices into the pattern file, "!" in front of one that
  * must not be in the payload), one "payload,rule" line per payload that a rule matches, sorted by payload, then by rule (rule =
  * index among the rule lines).  One of the two without the other, or a rules file that does not parse: message on stderr, exit 1,
@@ -100,6 +100,22 @@ static void die_gpu(const char *what)
 {
     fprintf(stderr, "%s: %s\n", what, kmpgpu_last_error());
     exit(2);
+}
+
+/* One "payload,index" line per record of a context's alert list (kmpgpu_scan_alerts: built and sorted by payload, then index, on the
+ * device), the payload counted from the shard's first one.  The records come back in pieces of a fixed size; no bit matrix leaves the
+ * device. */
+#define ALERT_PIECE 65536u
+static void write_alerts(FILE *fp, kmpgpu_ctx *ctx, int family, uint64_t shard_lo)
+{
+    static kmpgpu_alert piece[ALERT_PIECE];
+    uint64_t found = 0;
+    if (kmpgpu_scan_alerts(ctx, family, UINT64_MAX, &found, NULL, NULL, NULL, NULL)) die_gpu("kmpgpu_scan_alerts");
+    for (uint64_t first = 0; first < found; first += ALERT_PIECE) {
+        const uint64_t n = found - first < ALERT_PIECE ? found - first : ALERT_PIECE;
+        if (kmpgpu_alerts_read(ctx, piece, first, n)) die_gpu("kmpgpu_alerts_read");
+        for (uint64_t i = 0; i < n; i++) fprintf(fp, "%llu,%u\n", (unsigned long long)(shard_lo + piece[i].packet), piece[i].index);
+    }
 }
 
 /* The HIP runtime takes 0.2-0.3 s to come up.  It does so on a side thread while the main thread maps, indexes
@@ -461,17 +477,7 @@ int main(int argc, char *argv[])
             for (int r = 0; r < shards; r++) {
                 uint64_t np = 0;
                 kmpgpu_arena_info(ctxs[r], &np, NULL);
-                const uint64_t W = (np + 63) / 64;
-                uint64_t *any = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)(W ? W : 1));
-                uint64_t *hits = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)(W ? W : 1) * pats.n);
-                if (!any || !hits || kmpgpu_scan_packets(ctxs[r], NULL, any, hits, NULL, NULL)) die_gpu("kmpgpu_scan_packets");
-                for (uint64_t k = 0; k < np; k++) {
-                    const uint64_t bit = 1ull << (k & 63);
-                    if (!(any[k >> 6] & bit)) continue;
-                    for (uint32_t i = 0; i < pats.n; i++)
-                        if (hits[(size_t)i * W + (k >> 6)] & bit) fprintf(pk_fp, "%llu,%u\n", (unsigned long long)(shard_lo + k), i);
-                }
-                free(any); free(hits);
+                write_alerts(pk_fp, ctxs[r], KMPGPU_ALERT_PATTERNS, shard_lo);
                 shard_lo += np;
             }
             fclose(pk_fp);
@@ -483,18 +489,8 @@ int main(int argc, char *argv[])
             for (int r = 0; r < shards && rules.n; r++) {
                 uint64_t np = 0;
                 kmpgpu_arena_info(ctxs[r], &np, NULL);
-                const uint64_t W = (np + 63) / 64;
-                uint64_t *any = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)(W ? W : 1));
-                uint64_t *hits = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)(W ? W : 1) * rules.n);
-                if (!any || !hits || kmpgpu_set_rules(ctxs[r], rules.off, rules.terms, rules.n)) die_gpu("kmpgpu_set_rules");
-                if (kmpgpu_scan_rules(ctxs[r], NULL, any, hits, NULL, NULL)) die_gpu("kmpgpu_scan_rules");
-                for (uint64_t k = 0; k < np; k++) {
-                    const uint64_t bit = 1ull << (k & 63);
-                    if (!(any[k >> 6] & bit)) continue;
-                    for (uint32_t i = 0; i < rules.n; i++)
-                        if (hits[(size_t)i * W + (k >> 6)] & bit) fprintf(al_fp, "%llu,%u\n", (unsigned long long)(shard_lo + k), i);
-                }
-                free(any); free(hits);
+                if (kmpgpu_set_rules(ctxs[r], rules.off, rules.terms, rules.n)) die_gpu("kmpgpu_set_rules");
+                write_alerts(al_fp, ctxs[r], KMPGPU_ALERT_RULES, shard_lo);
                 shard_lo += np;
             }
             fclose(al_fp);

@@ -1,5 +1,5 @@
 /* kmp_launch.h -- launch entry points of kmp_scan_*.hip / kmp_prep.hip / kmp_fold.hip / kmp_marks.hip / kmp_rules.hip / kmp_relations.hip /
- * kmp_chains.hip / kmp_select.hip, used
+ * kmp_chains.hip / kmp_select.hip / kmp_alerts.hip, used
  * by the C-ABI layer (kmpgpu.hip), which alone decides what is launched; the tables kmp_launch_scan_multi takes come from kmp_tables.h. */
 #ifndef KMP_LAUNCH_H
 #define KMP_LAUNCH_H
@@ -147,5 +147,16 @@ hipError_t kmp_launch_select_phase1(const unsigned long long *select, const uint
 hipError_t kmp_launch_select_phase2(const uint8_t *src_arena, const uint64_t *src_off, uint64_t n, uint8_t *ws, uint64_t n_sel,
                                     uint64_t total_bytes, uint8_t *arena, uint64_t *pkt_off, uint32_t *pkt_len, void *recs,
                                     bool nontemporal, hipStream_t st);
+/* kmp_alerts.hip (kmpgpu_scan_alerts): the set bits of rows[n_rows][stride] (stride even, 16-byte aligned, every word of a row readable,
+ * the bits of index n_pkts and above not looked at; 16 * n_rows <= 0xFFFFFFFE) as 16-byte records {payload (64 bits), row, 0}, sorted by
+ * payload, then row.  any[ceil(n_pkts / 64)]: the OR over the rows, complete before the count; a column word whose any word is 0 is not read.
+ * ws: kmp_extract_ws_bytes(n_pkts) bytes, kept from the count to the fill.  _count (1 kernel) leaves per payload its records' bytes, _scan
+ * (2 kernels) every payload's offset and totals[0] = 16 * records, totals[1] = payloads with a record, _fill (1 kernel) writes the records
+ * whose position in the list is below max_records to recs[min(max_records, records)]. */
+hipError_t kmp_launch_alerts_count(const unsigned long long *rows, uint64_t stride, uint32_t n_rows, uint64_t n_pkts,
+                                   const unsigned long long *any, uint8_t *ws, hipStream_t st);
+hipError_t kmp_launch_alerts_scan(uint64_t n_pkts, uint8_t *ws, unsigned long long *totals, hipStream_t st);
+hipError_t kmp_launch_alerts_fill(const unsigned long long *rows, uint64_t stride, uint32_t n_rows, uint64_t n_pkts,
+                                  const unsigned long long *any, uint8_t *ws, void *recs, uint64_t max_records, hipStream_t st);
 
 #endif

@@ -182,6 +182,11 @@ struct kmpgpu_ctx {
      * is row n_pat + n_rel + c of the hit matrix and term n_pat + n_rel + c of a rule */
     uint32_t            n_chains = 0;
     uint4              *d_chains = nullptr;
+    /* kmpgpu_scan_alerts: the kept prefix of the last pass's list, 16 bytes per record (kmp_launch.h, kmp_launch_alerts_fill); alerts_valid:
+     * a list exists -- an alerts pass has ended well and neither the arena nor the patterns have changed since */
+    uint4              *d_alerts = nullptr;
+    uint64_t            alerts_cap = 0, alerts_kept = 0;
+    bool                alerts_valid = false;
 
     /* options */
     int mode = 0, blocks_per_cu = 0 /* auto */, depth = 0 /* auto */, nontemporal = 1, kernel_sel = 0, fused = 2 /* auto */, accumulate = 0, repack = 1;
@@ -364,6 +369,7 @@ void release_patterns(kmpgpu_ctx *c)
     drop_relations(c);                             /* ... and the relations' */
     drop_chains(c);                                /* ... and the chains' */
     c->pat_fold.clear();
+    c->alerts_valid = false;                       /* the list named their rows */
 }
 
 /* The context's own arena / offset / length buffers. */
@@ -399,6 +405,7 @@ void release_arena(kmpgpu_ctx *c, bool keep_buffers = false)
     c->uniform = false; c->packed = false; c->pad_clean = false; c->plan_waves = 0; c->uplan_units = 0;
     c->bitmap_live = false;                           /* the buffer itself (1/128 of an arena) is kept for the next arena */
     c->fold_stale = true; c->fold_end = 0;            /* (so is the fold buffer) */
+    c->alerts_valid = false;                          /* the list of kmpgpu_scan_alerts named this arena's payloads */
 }
 
 /* Host ranges pinned through kmpgpu_host_register.  One copy must not straddle two registrations (the runtime refuses it), and a
@@ -447,7 +454,8 @@ void release_pass_buffers(kmpgpu_ctx *c)
 {
     free_buffer(&c->d_bitmap, &c->bitmap_cap); free_buffer(&c->d_plan, &c->plan_cap); free_buffer(&c->d_uplan, &c->uplan_cap);
     free_buffer(&c->d_pool, &c->pool_cap); free_buffer(&c->d_partials, &c->partials_cap); free_buffer(&c->d_fold, &c->fold_cap);
-    free_buffer(&c->d_marks, &c->marks_cap); free_buffer(&c->d_rule_out, &c->rule_out_cap);
+    free_buffer(&c->d_marks, &c->marks_cap); free_buffer(&c->d_rule_out, &c->rule_out_cap); free_buffer(&c->d_alerts, &c->alerts_cap);
+    c->alerts_valid = false;
     c->bitmap_live = false; c->plan_waves = c->uplan_units = 0; c->fold_stale = true;
 }
 
@@ -574,6 +582,7 @@ int install_arena(kmpgpu_ctx *c, const uint8_t *arena, const uint64_t *off, cons
     c->packed = f.packed;
     c->span_end = f.span_end;
     c->fold_stale = true; c->fold_end = f.fold_end;
+    c->alerts_valid = false;
     (void)grow_fold(c, arena_bytes);                  /* (a failure is reported by the first scan that needs the fold) */
     return prepare_packed(c, wrote_padding);
 }
@@ -1603,6 +1612,47 @@ int enqueue_chains(kmpgpu_ctx *c, const MarkPass &p)
     return KMPGPU_OK;
 }
 
+/* What kmpgpu_scan_rules runs behind its marking pass, in its order: the relation kernel and the chain kernel where those are set, then
+ * the rules kernel.  The rule rows, their popcounts and their OR lie in the context's rule buffer, grown here. */
+struct RuleStage {
+    unsigned long long *d_rows = nullptr, *d_rc = nullptr, *d_any = nullptr;     /* [n_rules][stride], [n_rules], [stride] */
+    uint32_t launches = 0;
+};
+
+int enqueue_rules(kmpgpu_ctx *c, const char *who, const MarkPass &p, RuleStage *o)
+{
+    const size_t nr = c->n_rules;
+    /* one device buffer, grown like the others: [rule rows n_rules x stride][rule_pkt_counts n_rules][any stride] */
+    const uint64_t rows = (uint64_t)nr * p.stride;
+    const uint64_t words = rows + nr + p.stride;
+    hipError_t e = grow_buffer(&c->d_rule_out, &c->rule_out_cap, words, EIGHTH);
+    if (e != hipSuccess) {
+        /* the marking pass is under way on the stream; the context stays usable */
+        (void)hipStreamSynchronize(c->stream);
+        return alloc_fail(e, "%s: the rule rows (%llu bytes) could not be allocated", who, (unsigned long long)(words * 8u));
+    }
+    unsigned long long *d_rows = c->d_rule_out, *d_rc = d_rows + rows, *d_any = d_rc + nr;
+    /* the kernel adds to the counts and ORs into any; it writes every word of the rows itself */
+    HIP_TRY(hipMemsetAsync(d_rc, 0, (size_t)(nr + p.stride) * sizeof(unsigned long long), c->stream));
+    /* relations set: their rows of the matrix first, the rules read them as they read the patterns' */
+    if (c->n_rel) {
+        const int rr = enqueue_relations(c, p);
+        if (rr) return rr;
+    }
+    /* ... and so do the chains' rows behind those */
+    if (c->n_chains) {
+        const int rr = enqueue_chains(c, p);
+        if (rr) return rr;
+    }
+    hipEvent_t e1;
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_rules(p.d_mat, p.stride, c->n_pkts, c->d_rule_heads, c->d_rule_quads, c->n_rules, d_rows, d_rc, d_any, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    o->d_rows = d_rows; o->d_rc = d_rc; o->d_any = d_any;
+    o->launches = 1u + (c->n_rel ? 1u : 0u) + (c->n_chains ? 1u : 0u);
+    return KMPGPU_OK;
+}
+
 /* waits for the pass and its downloads; kernel_ms = ev[0]..ev[1], d2h_ms = ev[1]..ev[2] */
 int finish_marking(kmpgpu_ctx *c, uint32_t launches, kmpgpu_timing *t)
 {
@@ -1744,38 +1794,16 @@ int kmpgpu_scan_rules(kmpgpu_ctx *c, uint64_t *rule_pkt_counts_out, uint64_t *an
         if (t) { *t = kmpgpu_timing{}; }
         return KMPGPU_OK;
     }
-    /* one device buffer, grown like the others: [rule rows n_rules x stride][rule_pkt_counts n_rules][any stride] */
-    const uint64_t rows = (uint64_t)nr * p.stride;
-    const uint64_t words = rows + nr + p.stride;
-    hipError_t e = grow_buffer(&c->d_rule_out, &c->rule_out_cap, words, EIGHTH);
-    if (e != hipSuccess) {
-        /* the marking pass is under way on the stream; the context stays usable */
-        (void)hipStreamSynchronize(c->stream);
-        return alloc_fail(e, "kmpgpu_scan_rules: the rule rows (%llu bytes) could not be allocated", (unsigned long long)(words * 8u));
-    }
-    unsigned long long *d_rows = c->d_rule_out, *d_rc = d_rows + rows, *d_any = d_rc + nr;
-    /* the kernel adds to the counts and ORs into any; it writes every word of the rows itself */
-    HIP_TRY(hipMemsetAsync(d_rc, 0, (size_t)(nr + p.stride) * sizeof(unsigned long long), c->stream));
-    /* relations set: their rows of the matrix first, the rules read them as they read the patterns' */
-    if (c->n_rel) {
-        const int rr = enqueue_relations(c, p);
-        if (rr) return rr;
-    }
-    /* ... and so do the chains' rows behind those */
-    if (c->n_chains) {
-        const int rr = enqueue_chains(c, p);
-        if (rr) return rr;
-    }
-    hipEvent_t e1;
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_rules(p.d_mat, p.stride, c->n_pkts, c->d_rule_heads, c->d_rule_quads, c->n_rules, d_rows, d_rc, d_any, c->stream));
-    HIP_TRY(profile_launched(c, e1));
+    RuleStage o;
+    const int rr = enqueue_rules(c, "kmpgpu_scan_rules", p, &o);
+    if (rr) return rr;
+    unsigned long long *d_rows = o.d_rows, *d_rc = o.d_rc, *d_any = o.d_any;
     HIP_TRY(hipEventRecord(c->ev[1], c->stream));
     if (rule_pkt_counts_out) HIP_TRY(hipMemcpyAsync(rule_pkt_counts_out, d_rc, nr * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     if (any_out) HIP_TRY(hipMemcpyAsync(any_out, d_any, p.W * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, p.d_cnt, np * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     if (rule_hits_out) HIP_TRY(download_rows(c, rule_hits_out, d_rows, p.W, p.stride, nr));
-    return finish_marking(c, p.launches + 1u + (c->n_rel ? 1u : 0u) + (c->n_chains ? 1u : 0u), t);
+    return finish_marking(c, p.launches + o.launches, t);
 }
 
 int kmpgpu_set_relations(kmpgpu_ctx *c, const kmpgpu_relation *rel, uint32_t n_rel)
@@ -1907,6 +1935,119 @@ int kmpgpu_scan_chains(kmpgpu_ctx *c, uint64_t *chain_pkt_counts_out, uint64_t *
     if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, p.d_cnt, np * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     if (chain_hits_out) HIP_TRY(download_rows(c, chain_hits_out, p.d_chain, p.W, p.stride, nq));
     return finish_marking(c, p.launches + 1u, t);
+}
+
+int kmpgpu_scan_alerts(kmpgpu_ctx *c, int family, uint64_t max_records, uint64_t *n_found, uint64_t *n_packets, uint64_t *pkt_counts_out,
+                       uint64_t *counts_out, kmpgpu_timing *t)
+{
+    static_assert(sizeof(kmpgpu_alert) == sizeof(uint4), "an alert is a 16-byte record");
+    if (!c || !n_found) return fail(KMPGPU_EINVAL, "kmpgpu_scan_alerts: NULL argument");
+    *n_found = 0;
+    if (n_packets) *n_packets = 0;
+    /* the rows of the family, as its own call checks them */
+    uint64_t n_rows = 0;
+    switch (family) {
+    case KMPGPU_ALERT_PATTERNS:  n_rows = c->n_pat; break;            /* (no patterns: the marking pass says so) */
+    case KMPGPU_ALERT_RULES:     n_rows = c->n_rules; break;
+    case KMPGPU_ALERT_RELATIONS: n_rows = c->n_rel; break;
+    case KMPGPU_ALERT_CHAINS:    n_rows = c->n_chains; break;
+    default: return fail(KMPGPU_EINVAL, "kmpgpu_scan_alerts: family %d is none of KMPGPU_ALERT_*", family);
+    }
+    if (family != KMPGPU_ALERT_PATTERNS && (!c->d_patterns || c->n_pat == 0)) return fail(KMPGPU_ESTATE, "kmpgpu_scan_alerts: no patterns set");
+    if (family != KMPGPU_ALERT_PATTERNS && n_rows == 0)
+        return fail(KMPGPU_ESTATE, "kmpgpu_scan_alerts: no %s set", family == KMPGPU_ALERT_RULES ? "rules" : family == KMPGPU_ALERT_RELATIONS ? "relations" : "chains");
+    if (c->fr_pending) return fail(KMPGPU_ESTATE, "kmpgpu_scan_alerts: the context sits between kmpgpu_load_frames_begin and _finish");
+    /* a payload's records are scanned as a 32-bit byte length (kmp_scan_local_kernel), 0xFFFFFFFF taken */
+    if (16ull * n_rows > 0xFFFFFFFEull) return fail(KMPGPU_EINVAL, "kmpgpu_scan_alerts: %llu rows: 16 bytes x rows do not fit 32 bits", (unsigned long long)n_rows);
+    c->alerts_valid = false;                       /* the list before this pass is gone, whatever happens */
+    MarkPass p;
+    const int rc = marking_pass(c, "kmpgpu_scan_alerts", &p);
+    if (rc) return rc;
+    n_rows = family == KMPGPU_ALERT_PATTERNS ? c->n_pat : n_rows;
+    const size_t np = c->n_pat;
+    if (p.empty) {
+        /* nothing to scan: an empty list */
+        if (pkt_counts_out) memset(pkt_counts_out, 0, (size_t)n_rows * sizeof(uint64_t));
+        if (counts_out) memset(counts_out, 0, np * sizeof(uint64_t));
+        if (t) { *t = kmpgpu_timing{}; }
+        c->alerts_kept = 0; c->alerts_valid = true;
+        return KMPGPU_OK;
+    }
+    /* the family's rows, their popcounts and their OR, by the kernels of the family's own call */
+    const unsigned long long *d_rows = nullptr, *d_pc = nullptr, *d_any = nullptr;
+    uint32_t launches = p.launches + 1u;
+    hipEvent_t e1;
+    if (family == KMPGPU_ALERT_PATTERNS) {
+        HIP_TRY(profile_launch(c, &e1));
+        HIP_TRY(kmp_launch_marks_reduce(p.d_mat, c->n_pat, p.stride, p.d_pc, p.d_any, c->stream));
+        HIP_TRY(profile_launched(c, e1));
+        d_rows = p.d_mat; d_pc = p.d_pc; d_any = p.d_any;
+    } else if (family == KMPGPU_ALERT_RULES) {
+        RuleStage o;
+        const int rr = enqueue_rules(c, "kmpgpu_scan_alerts", p, &o);
+        if (rr) return rr;
+        d_rows = o.d_rows; d_pc = o.d_rc; d_any = o.d_any;
+        launches = p.launches + o.launches;
+    } else if (family == KMPGPU_ALERT_RELATIONS) {
+        const int rr = enqueue_relations(c, p);
+        if (rr) return rr;
+        d_rows = p.d_rel; d_pc = p.d_relc; d_any = p.d_any;
+    } else {
+        const int rr = enqueue_chains(c, p);
+        if (rr) return rr;
+        d_rows = p.d_chain; d_pc = p.d_chainc; d_any = p.d_any;
+    }
+    /* the list: count, scan (in the scratch kept for kmpgpu_load_frames, as kmpgpu_load_selected uses it), the totals read once, fill */
+    hipError_t e = grow_buffer(&c->fr_ws, &c->fr_ws_cap, (uint64_t)kmp_extract_ws_bytes(c->n_pkts), EIGHTH);
+    if (e == hipSuccess && !c->fr_tot) e = hipMalloc(&c->fr_tot, 2 * sizeof(unsigned long long));
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);      /* the pass is under way on the stream; the context stays usable */
+        return alloc_fail(e, "kmpgpu_scan_alerts: the scan workspace (%llu bytes) could not be allocated", (unsigned long long)kmp_extract_ws_bytes(c->n_pkts));
+    }
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_alerts_count(d_rows, p.stride, (uint32_t)n_rows, c->n_pkts, d_any, c->fr_ws, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_alerts_scan(c->n_pkts, c->fr_ws, c->fr_tot, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(hipMemcpyAsync(c->h_small, c->fr_tot, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));         /* (pinned: no staging) */
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    unsigned long long tot[2] = {0, 0};
+    memcpy(tot, c->h_small, sizeof tot);
+    const uint64_t found = tot[0] / 16u, kept = std::min<uint64_t>(found, max_records);
+    launches += 3u;
+    if (kept) {
+        e = grow_buffer(&c->d_alerts, &c->alerts_cap, kept, EIGHTH);
+        if (e != hipSuccess) return alloc_fail(e, "kmpgpu_scan_alerts: the records (%llu bytes) could not be allocated", (unsigned long long)(kept * 16u));
+        HIP_TRY(profile_launch(c, &e1));
+        HIP_TRY(kmp_launch_alerts_fill(d_rows, p.stride, (uint32_t)n_rows, c->n_pkts, d_any, c->fr_ws, c->d_alerts, kept, c->stream));
+        HIP_TRY(profile_launched(c, e1));
+        launches += 1u;
+    }
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    if (pkt_counts_out) HIP_TRY(hipMemcpyAsync(pkt_counts_out, d_pc, (size_t)n_rows * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, p.d_cnt, np * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    const int fr = finish_marking(c, launches, t);
+    if (fr) return fr;
+    *n_found = found;
+    if (n_packets) *n_packets = tot[1];
+    c->alerts_kept = kept; c->alerts_valid = true;
+    return KMPGPU_OK;
+}
+
+int kmpgpu_alerts_read(kmpgpu_ctx *c, kmpgpu_alert *out, uint64_t first, uint64_t n)
+{
+    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_alerts_read: ctx is NULL");
+    if (!c->alerts_valid) return fail(KMPGPU_ESTATE, "kmpgpu_alerts_read: no list (no kmpgpu_scan_alerts since the arena or the patterns were set)");
+    if (first > c->alerts_kept || n > c->alerts_kept - first)
+        return fail(KMPGPU_EINVAL, "kmpgpu_alerts_read: records [%llu, +%llu) leave the %llu kept", (unsigned long long)first, (unsigned long long)n,
+                    (unsigned long long)c->alerts_kept);
+    if (n == 0) return KMPGPU_OK;
+    if (!out) return fail(KMPGPU_EINVAL, "kmpgpu_alerts_read: out is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(out, c->d_alerts + first, (size_t)n * sizeof(kmpgpu_alert), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return KMPGPU_OK;
 }
 
 int kmpgpu_synth_fill(kmpgpu_ctx *c, void *d_arena, const void *d_pkt_off, const void *d_pkt_len, uint64_t first_pkt_id,

@@ -25,6 +25,10 @@ OPT_WHOLE_PAYLOAD = 9   # 1: a payload is text up to its end, not up to its firs
 KERNEL_AUTO, KERNEL_GENERAL, KERNEL_PACKED, KERNEL_FLAT = 0, 1, 2, 3
 MODE_FILTER, MODE_AUTOMATON = 0, 1
 PAT_NOCASE = 1          # kmpgpu_set_patterns_flags: ASCII letters match either case
+ALERT_PATTERNS, ALERT_RULES, ALERT_RELATIONS, ALERT_CHAINS = 0, 1, 2, 3     # KMPGPU_ALERT_*: the row family of scan_alerts
+ALERT_FAMILIES = {"patterns": ALERT_PATTERNS, "rules": ALERT_RULES, "relations": ALERT_RELATIONS, "chains": ALERT_CHAINS}
+ALERT_DTYPE = np.dtype([("packet", "<u8"), ("index", "<u4"), ("reserved", "<u4")])     # kmpgpu_alert, 16 bytes
+ALERTS_ALL = 0xFFFFFFFFFFFFFFFF     # max_records: keep the whole list
 
 
 def device_count() -> int:
@@ -436,6 +440,36 @@ class GpuMatcher:
             bits = np.unpackbits(hit_w.reshape(nq, W).view(np.uint8), axis=1, bitorder="little") if nq * W else np.zeros((nq, 0), np.uint8)
             out["hits"] = bits[:, :n_pkts].astype(bool)
         return out
+
+    def scan_alerts(self, family: str = "rules", max_records: Optional[int] = None, read: bool = True) -> dict:
+        """Which payloads hit which rows of a family, as a list built on the device (kmpgpu_scan_alerts): family "patterns", "rules",
+        "relations" or "chains" -- the rows of scan_packets, scan_rules, scan_relations, scan_chains.  ``n_found`` the length of the
+        whole list, ``n_packets`` the distinct payloads in it, ``pkt_counts`` (uint64[rows]) what the family's own call returns under
+        its name for it, ``counts`` (uint64[n_pat]) as scan(), ``timing``, and ``alerts``: the kept prefix -- the first
+        min(max_records, n_found) records of the list sorted by packet, then index; max_records None keeps all -- as a structured
+        array (ALERT_DTYPE), or with read=False an empty one: the records stay on the device for alerts_read()."""
+        if family not in ALERT_FAMILIES:
+            raise ValueError(f"family {family!r}: one of {sorted(ALERT_FAMILIES)} is needed")
+        cap = ALERTS_ALL if max_records is None else int(max_records)
+        if not 0 <= cap <= ALERTS_ALL:
+            raise ValueError(f"max_records {max_records}: not a 64-bit count")
+        n = len(self.patterns)
+        rows = {"patterns": n, "rules": len(self.rules), "relations": len(self.relations), "chains": len(self.chains)}[family]
+        found, packets = C.c_uint64(), C.c_uint64()
+        pkt_counts = np.zeros(max(rows, 1), dtype=np.uint64)
+        counts = np.zeros(max(n, 1), dtype=np.uint64)
+        t = Timing()
+        gpu_check(self._g.kmpgpu_scan_alerts(self._ctx, ALERT_FAMILIES[family], cap, C.byref(found), C.byref(packets), pkt_counts.ctypes.data,
+                                             counts.ctypes.data, C.byref(t)), "kmpgpu_scan_alerts")
+        kept = min(int(found.value), cap)
+        return {"alerts": self.alerts_read(0, kept) if read else np.zeros(0, dtype=ALERT_DTYPE), "n_found": int(found.value),
+                "n_packets": int(packets.value), "pkt_counts": pkt_counts[:rows], "counts": counts[:n], "timing": t}
+
+    def alerts_read(self, first: int, n: int) -> np.ndarray:
+        """Records [first, first + n) of the prefix the last scan_alerts kept on the device (kmpgpu_alerts_read)."""
+        out = np.zeros(max(int(n), 1), dtype=ALERT_DTYPE)
+        gpu_check(self._g.kmpgpu_alerts_read(self._ctx, out.ctypes.data, int(first), int(n)), "kmpgpu_alerts_read")
+        return out[: int(n)]
 
     # -- synthetic input (bench / tests) ---------------------------------------------------------
     def synth_fill(self, d_arena, d_off, d_len, sp: SynthParams, first_pkt_id: int = 0) -> None:
