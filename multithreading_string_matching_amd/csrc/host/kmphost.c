@@ -536,9 +536,10 @@ void kmp_rules_free(kmp_rules *r)
 
 /* ============================ relations ================================================= */
 
-/* One field of a relations line at *pp: a decimal number, with a leading '-' where neg_ok, that fits lo..hi, or (star != 0) a lone '*' =
- * star.  Leaves *pp behind the field and the blanks that follow it; on failure *tok / *tok_len name the field for the message. */
-static int relations_field(const char **pp, const char *end, int neg_ok, int64_t lo, int64_t hi, int64_t star, int64_t *out, const char **tok, int *tok_len)
+/* One field of a relations, chains or windows line at *pp: a decimal number, with a leading '-' where neg_ok, that fits lo..hi, or
+ * (star != 0) a lone '*' = star.  Leaves *pp behind the field and the blanks that follow it; on failure *tok / *tok_len name the field for
+ * the message. */
+static int number_field(const char **pp, const char *end, int neg_ok, int64_t lo, int64_t hi, int64_t star, int64_t *out, const char **tok, int *tok_len)
 {
     const char *p = *pp;
     *tok = p;
@@ -585,8 +586,8 @@ int kmp_relations_parse(const char *path, uint32_t n_patterns, kmp_relations *ou
             if (p == end) {
                 if (errbuf) snprintf(errbuf, KMP_RELATIONS_ERRBUF, "line %zu: %d of the four fields <a> <b> <dmin> <dmax>", lineno, k);
                 rc = KMPHOST_EINVAL;
-            } else if (!relations_field(&p, end, k >= 2, k >= 2 ? INT32_MIN : 0, k >= 2 ? INT32_MAX : 0xFFFFFFFFll,
-                                        k == 2 ? INT32_MIN : k == 3 ? INT32_MAX : 0, &f[k], &tok, &tl)) {
+            } else if (!number_field(&p, end, k >= 2, k >= 2 ? INT32_MIN : 0, k >= 2 ? INT32_MAX : 0xFFFFFFFFll,
+                                     k == 2 ? INT32_MIN : k == 3 ? INT32_MAX : 0, &f[k], &tok, &tl)) {
                 if (errbuf) snprintf(errbuf, KMP_RELATIONS_ERRBUF, "line %zu: '%.*s' is not %s", lineno, tl, tok, what[k]);
                 rc = KMPHOST_EINVAL;
             }
@@ -665,8 +666,8 @@ int kmp_chains_parse(const char *path, uint32_t n_patterns, kmp_chains *out, cha
             if (k == 0 && n == KMP_CHAIN_MAX) {
                 if (errbuf) snprintf(errbuf, KMP_CHAINS_ERRBUF, "line %zu: more than %d contents", lineno, KMP_CHAIN_MAX);
                 rc = KMPHOST_EINVAL;
-            } else if (!relations_field(&p, end, k != 0, k ? INT32_MIN : 0, k ? INT32_MAX : 0xFFFFFFFFll, k == 1 ? INT32_MIN : k == 2 ? INT32_MAX : 0, &v,
-                                        &tok, &tl)) {
+            } else if (!number_field(&p, end, k != 0, k ? INT32_MIN : 0, k ? INT32_MAX : 0xFFFFFFFFll, k == 1 ? INT32_MIN : k == 2 ? INT32_MAX : 0, &v,
+                                     &tok, &tl)) {
                 if (errbuf) snprintf(errbuf, KMP_CHAINS_ERRBUF, "line %zu: '%.*s' is not %s", lineno, tl, tok, what[k]);
                 rc = KMPHOST_EINVAL;
             } else if (k == 0) {
@@ -728,26 +729,6 @@ void kmp_chains_free(kmp_chains *c)
 
 /* ============================ offset windows ============================================ */
 
-/* One field of a windows line at *pp: a decimal number that fits 32 bits, or (star_ok) a lone '*' = UINT32_MAX.  Leaves *pp behind
- * the field and the blanks that follow it; on failure *tok / *tok_len name the field for the message (tok_len 0: the line ended). */
-static int windows_field(const char **pp, const char *end, int star_ok, uint32_t *out, const char **tok, int *tok_len)
-{
-    const char *p = *pp;
-    *tok = p;
-    uint64_t v = 0;
-    const char *digits = p;
-    while (p < end && *p >= '0' && *p <= '9') { if (v < (1ull << 40)) v = v * 10 + (uint64_t)(*p - '0'); p++; }
-    const char *stop = p;
-    while (stop < end && !is_c_space((uint8_t)*stop)) stop++;           /* the whole token, for the message */
-    *tok_len = (int)(stop - *tok > 64 ? 64 : stop - *tok);
-    int ok = p > digits && stop == p && v <= 0xFFFFFFFFull;
-    if (!ok && star_ok && stop == digits + 1 && *digits == '*') { v = 0xFFFFFFFFull; ok = 1; }
-    while (stop < end && is_c_space((uint8_t)*stop)) stop++;
-    *pp = stop;
-    *out = (uint32_t)v;
-    return ok;
-}
-
 int kmp_windows_parse(const char *path, uint32_t n_patterns, uint32_t *first_out, uint32_t *last_out, char errbuf[KMP_WINDOWS_ERRBUF])
 {
     if (errbuf) errbuf[0] = 0;
@@ -773,13 +754,14 @@ int kmp_windows_parse(const char *path, uint32_t n_patterns, uint32_t *first_out
         for (int k = 0; k < 3 && !rc; k++) {
             const char *tok;
             int tl;
+            int64_t v = 0;
             if (p == end) {
                 if (errbuf) snprintf(errbuf, KMP_WINDOWS_ERRBUF, "line %zu: %d of the three fields <pattern index> <first> <last>", lineno, k);
                 rc = KMPHOST_EINVAL;
-            } else if (!windows_field(&p, end, k == 2, &f[k], &tok, &tl)) {
+            } else if (!number_field(&p, end, 0, 0, 0xFFFFFFFFll, k == 2 ? 0xFFFFFFFFll : 0, &v, &tok, &tl)) {      /* '*': UINT32_MAX */
                 if (errbuf) snprintf(errbuf, KMP_WINDOWS_ERRBUF, "line %zu: '%.*s' is not %s", lineno, tl, tok, what[k]);
                 rc = KMPHOST_EINVAL;
-            }
+            } else f[k] = (uint32_t)v;
         }
         if (rc) break;
         if (p != end) {

@@ -1,0 +1,115 @@
+/*
+ * kmp_rowtables.cpp -- the tables of the rules, windows, relations and chains as the kernels read them (kmp_rowtables.h).  Host code only.
+ */
+#include "kmp_rowtables.h"
+
+#include <stdarg.h>
+#include <stdio.h>
+
+namespace {
+
+int refuse(std::string *msg, const char *fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    *msg = buf;
+    return KMPGPU_EINVAL;
+}
+
+/* bit 31: the pattern's bytes are compared in the folded copy of the arena */
+uint32_t fold_bit(const uint8_t *pat_fold, uint32_t pattern) { return pattern | ((uint32_t)(pat_fold[pattern] != 0) << 31); }
+
+}  // namespace
+
+int kmp_pack_rules(const uint32_t *rule_off, const uint32_t *terms, uint32_t n_rules, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains,
+                   std::vector<uint32_t> *heads, std::vector<uint32_t> *quads, std::string *msg)
+{
+    heads->clear(); quads->clear();
+    if (!rule_off || !terms) return refuse(msg, "kmpgpu_set_rules: NULL rule arrays");
+    if (rule_off[0] != 0) return refuse(msg, "kmpgpu_set_rules: rule_off[0] is %u, not 0", rule_off[0]);
+    const uint64_t n_rows = (uint64_t)n_pat + n_rel + n_chains;          /* (< 2^31: kmp_pack_relations, kmp_pack_chains) */
+    std::vector<uint32_t> ord;
+    for (uint32_t r = 0; r < n_rules; r++) {
+        if (rule_off[r + 1] < rule_off[r]) return refuse(msg, "kmpgpu_set_rules: rule_off decreases at rule %u", r);
+        if (rule_off[r + 1] == rule_off[r]) return refuse(msg, "kmpgpu_set_rules: rule %u has no terms", r);
+        ord.clear();
+        for (int neg = 0; neg < 2; neg++)
+            for (uint32_t j = rule_off[r]; j < rule_off[r + 1]; j++) {
+                if ((terms[j] & ~KMPGPU_RULE_NOT) >= n_rows)
+                    return refuse(msg, "kmpgpu_set_rules: rule %u: term %u names row %u of %u patterns + %u relations + %u chains", r,
+                                  j - rule_off[r], terms[j] & ~KMPGPU_RULE_NOT, n_pat, n_rel, n_chains);
+                if (((terms[j] & KMPGPU_RULE_NOT) != 0) == (neg != 0)) ord.push_back(terms[j]);
+            }
+        /* filled up with a term that is loaded at the same time: a repeated term changes nothing */
+        if (ord.size() < 2) ord.push_back(ord[0]);
+        while ((ord.size() - 2) % 4) ord.push_back(ord[ord.size() - (ord.size() - 2) % 4]);
+        const uint64_t q0 = quads->size() / 4, q1 = q0 + (ord.size() - 2) / 4;
+        if (q1 > 0xFFFFFFFFull) return refuse(msg, "kmpgpu_set_rules: too many terms");
+        heads->insert(heads->end(), {(uint32_t)q0, (uint32_t)q1, ord[0], ord[1]});
+        quads->insert(quads->end(), ord.begin() + 2, ord.end());
+    }
+    return KMPGPU_OK;
+}
+
+int kmp_pack_windows(const uint32_t *first, const uint32_t *last, uint32_t n_windows, uint32_t n_pat, std::vector<uint32_t> *windows,
+                     std::string *msg)
+{
+    windows->clear();
+    if (n_windows != n_pat) return refuse(msg, "kmpgpu_set_windows: %u windows for %u patterns", n_windows, n_pat);
+    if (!first || !last) return refuse(msg, "kmpgpu_set_windows: NULL window arrays");
+    bool all_default = true;
+    for (uint32_t i = 0; i < n_pat; i++) {
+        if (first[i] > last[i]) return refuse(msg, "kmpgpu_set_windows: pattern %u: first %u lies behind last %u", i, first[i], last[i]);
+        windows->insert(windows->end(), {first[i], last[i]});
+        all_default = all_default && first[i] == 0u && last[i] == 0xFFFFFFFFu;
+    }
+    if (all_default) windows->clear();
+    return KMPGPU_OK;
+}
+
+int kmp_pack_relations(const kmpgpu_relation *rel, uint32_t n_rel, uint32_t n_pat, uint32_t n_chains, const uint8_t *pat_fold,
+                       std::vector<uint32_t> *relations, std::string *msg)
+{
+    relations->clear();
+    if (!rel) return refuse(msg, "kmpgpu_set_relations: rel is NULL");
+    if ((uint64_t)n_pat + n_rel + n_chains >= (1ull << 31))
+        return refuse(msg, "kmpgpu_set_relations: %u patterns + %u relations%s do not fit the 2^31 rows a rule term can name", n_pat, n_rel,
+                      n_chains ? " + the chains" : "");
+    for (uint32_t q = 0; q < n_rel; q++) {
+        const kmpgpu_relation &r = rel[q];
+        if (r.a >= n_pat || r.b >= n_pat)
+            return refuse(msg, "kmpgpu_set_relations: relation %u names pattern %u of %u", q, r.a >= n_pat ? r.a : r.b, n_pat);
+        if (r.dmin > r.dmax) return refuse(msg, "kmpgpu_set_relations: relation %u: dmin %d lies above dmax %d", q, r.dmin, r.dmax);
+        relations->insert(relations->end(), {fold_bit(pat_fold, r.a), fold_bit(pat_fold, r.b), (uint32_t)r.dmin, (uint32_t)r.dmax});
+    }
+    return KMPGPU_OK;
+}
+
+int kmp_pack_chains(const uint32_t *chain_off, const kmpgpu_chain_link *links, uint32_t n_chains, uint32_t n_pat, uint32_t n_rel,
+                    const uint8_t *pat_fold, std::vector<uint32_t> *chains, std::string *msg)
+{
+    chains->clear();
+    if (!chain_off || !links) return refuse(msg, "kmpgpu_set_chains: NULL chain arrays");
+    if ((uint64_t)n_pat + n_rel + n_chains >= (1ull << 31))
+        return refuse(msg, "kmpgpu_set_chains: %u patterns + %u relations + %u chains do not fit the 2^31 rows a rule term can name", n_pat, n_rel,
+                      n_chains);
+    if (chain_off[0] != 0) return refuse(msg, "kmpgpu_set_chains: chain_off[0] is %u, not 0", chain_off[0]);
+    for (uint32_t q = 0; q < n_chains; q++) {
+        if (chain_off[q + 1] < chain_off[q]) return refuse(msg, "kmpgpu_set_chains: chain_off decreases at chain %u", q);
+        const uint32_t n = chain_off[q + 1] - chain_off[q];
+        if (n < 2 || n > KMPGPU_CHAIN_MAX) return refuse(msg, "kmpgpu_set_chains: chain %u has %u contents, not 2 .. %d", q, n, KMPGPU_CHAIN_MAX);
+        const kmpgpu_chain_link *l = links + chain_off[q];
+        if (l[0].dmin != INT32_MIN || l[0].dmax != INT32_MAX)
+            return refuse(msg, "kmpgpu_set_chains: chain %u: its first content is relative to nothing and carries no bounds (a window places it)", q);
+        for (uint32_t i = 0; i < KMPGPU_CHAIN_MAX; i++) {
+            const kmpgpu_chain_link &k = l[i < n ? i : n - 1];
+            if (k.pattern >= n_pat) return refuse(msg, "kmpgpu_set_chains: chain %u names pattern %u of %u", q, k.pattern, n_pat);
+            if (k.dmin > k.dmax) return refuse(msg, "kmpgpu_set_chains: chain %u: dmin %d lies above dmax %d", q, k.dmin, k.dmax);
+            chains->insert(chains->end(), {fold_bit(pat_fold, k.pattern), (uint32_t)k.dmin, (uint32_t)k.dmax, n});
+        }
+    }
+    return KMPGPU_OK;
+}

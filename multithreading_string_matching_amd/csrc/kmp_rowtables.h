@@ -1,0 +1,39 @@
+/*
+ * kmp_rowtables.h -- what kmpgpu_set_rules, kmpgpu_set_windows, kmpgpu_set_relations and kmpgpu_set_chains upload, checked and packed on
+ * the host by kmp_rowtables.cpp into the form the kernels read bit for bit (kmp_launch.h: kmp_launch_rules, emit_windows,
+ * kmp_launch_relations, kmp_launch_chains).  Host code without a HIP header, as kmp_tables.h: it builds and runs without a device
+ * (tests/rowtables_sanitizer_driver.cpp).
+ *
+ * Every packer returns KMPGPU_OK with its table -- 16-byte records as four uint32_t, window records as two -- or KMPGPU_EINVAL with the
+ * whole text of kmpgpu_last_error in *msg.  It reads none of its arrays before the counts alone have passed.  n_pat, n_rel, n_chains: the
+ * rows of the context's hit matrix; pat_fold[i]: pattern i is compared in the folded copy of the arena (bit 31 of its index in a record).
+ */
+#ifndef KMP_ROWTABLES_H
+#define KMP_ROWTABLES_H
+
+#include <stdint.h>
+
+#include <string>
+#include <vector>
+
+#include "kmpgpu.h"
+
+/* heads[r] = {first quad of rule r's further terms, the quad behind its last, first term, second term}, quads[q] = four further terms: a
+ * rule's plain terms in front of its negated ones (a lane of the kernel whose payloads miss one of them stops early), a rule of one term
+ * with it twice in its head, the last quad filled up with repeats of its own first term. */
+int kmp_pack_rules(const uint32_t *rule_off, const uint32_t *terms, uint32_t n_rules, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains,
+                   std::vector<uint32_t> *heads, std::vector<uint32_t> *quads, std::string *msg);
+
+/* {first, last} per pattern; empty where every window is the default [0, UINT32_MAX]: no table, the emitting passes run as without */
+int kmp_pack_windows(const uint32_t *first, const uint32_t *last, uint32_t n_windows, uint32_t n_pat, std::vector<uint32_t> *windows,
+                     std::string *msg);
+
+/* {a | fold << 31, b | fold << 31, dmin, dmax} per relation */
+int kmp_pack_relations(const kmpgpu_relation *rel, uint32_t n_rel, uint32_t n_pat, uint32_t n_chains, const uint8_t *pat_fold,
+                       std::vector<uint32_t> *relations, std::string *msg);
+
+/* KMPGPU_CHAIN_MAX records {pattern | fold << 31, dmin, dmax, n} per chain of n contents, the records behind the last link repeating it */
+int kmp_pack_chains(const uint32_t *chain_off, const kmpgpu_chain_link *links, uint32_t n_chains, uint32_t n_pat, uint32_t n_rel,
+                    const uint8_t *pat_fold, std::vector<uint32_t> *chains, std::string *msg);
+
+#endif

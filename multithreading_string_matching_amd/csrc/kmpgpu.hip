@@ -24,6 +24,7 @@
 #include "kmpgpu.h"
 #include "kmp_device.h"
 #include "kmp_launch.h"
+#include "kmp_rowtables.h"
 #include "kmp_tables.h"
 
 namespace {
@@ -1528,15 +1529,13 @@ int kmpgpu_scan_offsets(kmpgpu_ctx *c, kmpgpu_match *out, uint64_t cap, uint64_t
 
 namespace {
 
-/* The marking pass kmpgpu_scan_packets and kmpgpu_scan_rules share: preconditions, the arena packed where it was kept in place, the
- * context's matrix buffer grown and zeroed, and the scan launches that mark it.  Leaves c->ev[0] recorded in front of the zeroing.
+/* The marking pass every row family starts with: preconditions, the arena packed where it was kept in place, the context's matrix buffer
+ * grown and zeroed, and the scan launches that mark it.  Leaves c->ev[0] recorded in front of the zeroing.
  * empty: no payloads, nothing was enqueued. */
 struct MarkPass {
     bool empty = false;
     uint64_t W = 0, stride = 0, mat = 0;          /* words per row as the caller sees them / on the device (even); words of the matrix */
-    unsigned long long *d_mat = nullptr, *d_pc = nullptr, *d_any = nullptr, *d_cnt = nullptr;    /* [n_pat + n_rel + n_chains][stride], [n_pat], [stride], [n_pat] */
-    unsigned long long *d_rel = nullptr, *d_relc = nullptr;     /* the relations' rows inside d_mat (row n_pat on), [n_rel] */
-    unsigned long long *d_chain = nullptr, *d_chainc = nullptr; /* the chains' rows inside d_mat (row n_pat + n_rel on), [n_chains] */
+    unsigned long long *d_mat = nullptr, *d_cnt = nullptr;       /* [n_pat + n_rel + n_chains][stride]; the scan's counts [n_pat] */
     uint32_t launches = 0;
 };
 
@@ -1561,15 +1560,13 @@ int marking_pass(kmpgpu_ctx *c, const char *who, MarkPass *p)
     }
     /* one device buffer, grown like the others: [marks (n_pat + n_rel + n_chains) x stride][pkt_counts n_pat][any stride][counts n_pat]
      * [rel_pkt_counts n_rel][chain_pkt_counts n_chains]; the scan kernels mark rows 0 .. n_pat - 1, the relation kernel and the chain
-     * kernel write the rows behind them */
+     * kernel write the rows behind them (family_rows) */
     const uint64_t mat = ((uint64_t)np + c->n_rel + c->n_chains) * stride;
     const uint64_t words = mat + np + stride + np + c->n_rel + c->n_chains;
     hipError_t e = grow_buffer(&c->d_marks, &c->marks_cap, words, EIGHTH);
     if (e != hipSuccess) return alloc_fail(e, "%s: the hit matrix (%llu bytes) could not be allocated", who, (unsigned long long)(words * 8u));
     p->stride = stride; p->mat = mat;
-    p->d_mat = c->d_marks; p->d_pc = p->d_mat + mat; p->d_any = p->d_pc + np; p->d_cnt = p->d_any + stride;
-    p->d_rel = p->d_mat + (uint64_t)np * stride; p->d_relc = p->d_cnt + np;
-    p->d_chain = p->d_rel + (uint64_t)c->n_rel * stride; p->d_chainc = p->d_relc + c->n_rel;
+    p->d_mat = c->d_marks; p->d_cnt = p->d_mat + mat + np + stride;
     HIP_TRY(hipEventRecord(c->ev[0], c->stream));
     /* zeroed before every pass: the bits of an earlier (larger) arena must not leak into this one */
     HIP_TRY(hipMemsetAsync(p->d_mat, 0, (size_t)words * sizeof(unsigned long long), c->stream));
@@ -1587,69 +1584,106 @@ hipError_t download_rows(kmpgpu_ctx *c, uint64_t *dst, const unsigned long long 
     return hipMemcpy2DAsync(dst, W * sizeof(uint64_t), src, stride * sizeof(uint64_t), W * sizeof(uint64_t), rows, hipMemcpyDeviceToHost, c->stream);
 }
 
-/* The relation kernel behind a marking pass: rows n_pat .. of the matrix, their popcounts into p.d_relc and their OR into p.d_any (all
- * zeroed by the pass; kmpgpu_scan_rules has no other use for that any[]).  One launch, recorded by a running profile. */
-int enqueue_relations(kmpgpu_ctx *c, const MarkPass &p)
-{
-    hipEvent_t e1;
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_relations(p.d_mat, p.stride, c->n_pkts, c->d_relations, c->n_rel, c->d_patterns, c->d_arena, c->d_fold, c->d_off,
-                                 c->d_len, c->d_windows, c->whole_payload != 0, (uint32_t)c->cu_count * 8u, p.d_rel, p.d_relc, p.d_any,
-                                 c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    return KMPGPU_OK;
-}
-
-/* The chain kernel behind a marking pass, in the same way: rows n_pat + n_rel .. of the matrix, their popcounts into p.d_chainc. */
-int enqueue_chains(kmpgpu_ctx *c, const MarkPass &p)
-{
-    hipEvent_t e1;
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_chains(p.d_mat, p.stride, c->n_pkts, c->d_chains, c->n_chains, c->d_patterns, c->d_arena, c->d_fold, c->d_off,
-                              c->d_len, c->d_windows, c->whole_payload != 0, (uint32_t)c->cu_count * 8u, p.d_chain, p.d_chainc, p.d_any,
-                              c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    return KMPGPU_OK;
-}
-
-/* What kmpgpu_scan_rules runs behind its marking pass, in its order: the relation kernel and the chain kernel where those are set, then
- * the rules kernel.  The rule rows, their popcounts and their OR lie in the context's rule buffer, grown here. */
-struct RuleStage {
-    unsigned long long *d_rows = nullptr, *d_rc = nullptr, *d_any = nullptr;     /* [n_rules][stride], [n_rules], [stride] */
-    uint32_t launches = 0;
+/* A row family (KMPGPU_ALERT_*): patterns, rules, relations or chains.  Where its results lie on the device once its kernels are
+ * enqueued behind a marking pass (enqueue_family). */
+struct FamilyRows {
+    unsigned long long *d_rows = nullptr, *d_pc = nullptr, *d_any = nullptr;     /* [n_rows][stride], payloads per row [n_rows], [stride] */
+    uint64_t n_rows = 0;
+    uint32_t launches = 0;                        /* added to the marking pass's */
 };
 
-int enqueue_rules(kmpgpu_ctx *c, const char *who, const MarkPass &p, RuleStage *o)
+uint64_t family_n_rows(const kmpgpu_ctx *c, int family)
 {
-    const size_t nr = c->n_rules;
-    /* one device buffer, grown like the others: [rule rows n_rules x stride][rule_pkt_counts n_rules][any stride] */
-    const uint64_t rows = (uint64_t)nr * p.stride;
-    const uint64_t words = rows + nr + p.stride;
-    hipError_t e = grow_buffer(&c->d_rule_out, &c->rule_out_cap, words, EIGHTH);
-    if (e != hipSuccess) {
-        /* the marking pass is under way on the stream; the context stays usable */
-        (void)hipStreamSynchronize(c->stream);
-        return alloc_fail(e, "%s: the rule rows (%llu bytes) could not be allocated", who, (unsigned long long)(words * 8u));
+    return family == KMPGPU_ALERT_PATTERNS ? c->n_pat : family == KMPGPU_ALERT_RULES ? c->n_rules : family == KMPGPU_ALERT_RELATIONS ? c->n_rel : c->n_chains;
+}
+
+/* The one place that knows where the families live: the patterns, relations and chains in the marks buffer as marking_pass lays it out
+ * (they share its any[]; one family's kernel writes it per pass), the rules in the context's rule buffer [rule rows n_rules x stride]
+ * [rule_pkt_counts n_rules][any stride]. */
+void family_rows(const kmpgpu_ctx *c, const MarkPass &p, int family, FamilyRows *f)
+{
+    *f = FamilyRows{};
+    f->n_rows = family_n_rows(c, family);
+    if (family == KMPGPU_ALERT_RULES) {
+        f->d_rows = c->d_rule_out; f->d_pc = f->d_rows + f->n_rows * p.stride; f->d_any = f->d_pc + f->n_rows;
+        return;
     }
-    unsigned long long *d_rows = c->d_rule_out, *d_rc = d_rows + rows, *d_any = d_rc + nr;
-    /* the kernel adds to the counts and ORs into any; it writes every word of the rows itself */
-    HIP_TRY(hipMemsetAsync(d_rc, 0, (size_t)(nr + p.stride) * sizeof(unsigned long long), c->stream));
-    /* relations set: their rows of the matrix first, the rules read them as they read the patterns' */
-    if (c->n_rel) {
-        const int rr = enqueue_relations(c, p);
-        if (rr) return rr;
-    }
-    /* ... and so do the chains' rows behind those */
-    if (c->n_chains) {
-        const int rr = enqueue_chains(c, p);
-        if (rr) return rr;
-    }
+    const uint64_t np = c->n_pat, first = family == KMPGPU_ALERT_PATTERNS ? 0 : family == KMPGPU_ALERT_RELATIONS ? np : np + c->n_rel;
+    f->d_rows = p.d_mat + first * p.stride;
+    f->d_pc = family == KMPGPU_ALERT_PATTERNS ? p.d_mat + p.mat : p.d_cnt + first;      /* (the counts of the rows behind the patterns': behind the scan's counts) */
+    f->d_any = p.d_mat + p.mat + np;
+}
+
+/* The relation kernel or the chain kernel behind a marking pass: the family's rows of the matrix, their popcounts and their OR into any[]
+ * (all zeroed by the pass; kmpgpu_scan_rules has no other use for that any[]).  One launch, recorded by a running profile. */
+int enqueue_pairing(kmpgpu_ctx *c, const MarkPass &p, int family)
+{
+    const bool rel = family == KMPGPU_ALERT_RELATIONS;
+    FamilyRows f;
+    family_rows(c, p, family, &f);
     hipEvent_t e1;
     HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_rules(p.d_mat, p.stride, c->n_pkts, c->d_rule_heads, c->d_rule_quads, c->n_rules, d_rows, d_rc, d_any, c->stream));
+    HIP_TRY((rel ? kmp_launch_relations : kmp_launch_chains)(p.d_mat, p.stride, c->n_pkts, rel ? c->d_relations : c->d_chains, (uint32_t)f.n_rows,
+                                                             c->d_patterns, c->d_arena, c->d_fold, c->d_off, c->d_len, c->d_windows,
+                                                             c->whole_payload != 0, (uint32_t)c->cu_count * 8u, f.d_rows, f.d_pc, f.d_any,
+                                                             c->stream));
     HIP_TRY(profile_launched(c, e1));
-    o->d_rows = d_rows; o->d_rc = d_rc; o->d_any = d_any;
-    o->launches = 1u + (c->n_rel ? 1u : 0u) + (c->n_chains ? 1u : 0u);
+    return KMPGPU_OK;
+}
+
+/* The one place that runs a family's kernels behind a marking pass, and says where they leave their results.  Patterns: the marks reduce.
+ * Relations, chains: their kernel.  Rules: the relation kernel and the chain kernel where those are set, then the rules kernel, into the
+ * context's rule buffer, grown here. */
+int enqueue_family(kmpgpu_ctx *c, const char *who, int family, const MarkPass &p, bool profile_reduce, FamilyRows *f)
+{
+    hipEvent_t e1 = nullptr;
+    if (family == KMPGPU_ALERT_PATTERNS) {
+        family_rows(c, p, family, f);
+        /* profile_reduce: kmpgpu_scan_alerts has a running profile record the marks reduce, kmpgpu_scan_packets never has */
+        if (profile_reduce) HIP_TRY(profile_launch(c, &e1));
+        HIP_TRY(kmp_launch_marks_reduce(p.d_mat, c->n_pat, p.stride, f->d_pc, f->d_any, c->stream));
+        HIP_TRY(profile_launched(c, e1));
+        f->launches = 1u;
+        return KMPGPU_OK;
+    }
+    if (family == KMPGPU_ALERT_RULES) {
+        const uint64_t nr = c->n_rules, words = nr * p.stride + nr + p.stride;
+        hipError_t e = grow_buffer(&c->d_rule_out, &c->rule_out_cap, words, EIGHTH);
+        if (e != hipSuccess) {
+            /* the marking pass is under way on the stream; the context stays usable */
+            (void)hipStreamSynchronize(c->stream);
+            return alloc_fail(e, "%s: the rule rows (%llu bytes) could not be allocated", who, (unsigned long long)(words * 8u));
+        }
+        family_rows(c, p, family, f);
+        /* the kernel adds to the counts and ORs into any; it writes every word of the rows itself */
+        HIP_TRY(hipMemsetAsync(f->d_pc, 0, (size_t)(nr + p.stride) * sizeof(unsigned long long), c->stream));
+        /* relations set: their rows of the matrix first, the rules read them as they read the patterns'; and so the chains' behind those */
+        for (int pairing : {KMPGPU_ALERT_RELATIONS, KMPGPU_ALERT_CHAINS})
+            if (family_n_rows(c, pairing)) {
+                const int rr = enqueue_pairing(c, p, pairing);
+                if (rr) return rr;
+                f->launches++;
+            }
+        HIP_TRY(profile_launch(c, &e1));
+        HIP_TRY(kmp_launch_rules(p.d_mat, p.stride, c->n_pkts, c->d_rule_heads, c->d_rule_quads, c->n_rules, f->d_rows, f->d_pc, f->d_any, c->stream));
+        HIP_TRY(profile_launched(c, e1));
+        f->launches++;
+        return KMPGPU_OK;
+    }
+    family_rows(c, p, family, f);
+    f->launches = 1u;
+    return enqueue_pairing(c, p, family);
+}
+
+/* What every family's call starts with: the marking pass, and on an empty arena (p->empty) the outputs that hold something -- every payload
+ * count, every total is 0, and there are no bit words. */
+int begin_family(kmpgpu_ctx *c, const char *who, int family, uint64_t *row_counts_out, uint64_t *counts_out, kmpgpu_timing *t, MarkPass *p)
+{
+    const int rc = marking_pass(c, who, p);
+    if (rc || !p->empty) return rc;
+    if (row_counts_out) memset(row_counts_out, 0, (size_t)family_n_rows(c, family) * sizeof(uint64_t));
+    if (counts_out) memset(counts_out, 0, (size_t)c->n_pat * sizeof(uint64_t));
+    if (t) { *t = kmpgpu_timing{}; }
     return KMPGPU_OK;
 }
 
@@ -1669,175 +1703,124 @@ int finish_marking(kmpgpu_ctx *c, uint32_t launches, kmpgpu_timing *t)
     return KMPGPU_OK;
 }
 
+/* The body of kmpgpu_scan_packets, _rules, _relations and _chains behind their own checks: marking pass, the family's kernels, downloads. */
+int scan_family(kmpgpu_ctx *c, const char *who, int family, uint64_t *row_counts_out, uint64_t *any_out, uint64_t *hits_out, uint64_t *counts_out,
+                kmpgpu_timing *t)
+{
+    MarkPass p;
+    const int rc = begin_family(c, who, family, row_counts_out, counts_out, t, &p);
+    if (rc || p.empty) return rc;
+    FamilyRows f;
+    const int rr = enqueue_family(c, who, family, p, /* profile_reduce = */ false, &f);
+    if (rr) return rr;
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    if (row_counts_out) HIP_TRY(hipMemcpyAsync(row_counts_out, f.d_pc, (size_t)f.n_rows * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (any_out) HIP_TRY(hipMemcpyAsync(any_out, f.d_any, p.W * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, p.d_cnt, (size_t)c->n_pat * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (hits_out) HIP_TRY(download_rows(c, hits_out, f.d_rows, p.W, p.stride, f.n_rows));
+    return finish_marking(c, p.launches + f.launches, t);
+}
+
+/* One table a setter swaps in: its words as a packer of kmp_rowtables.h left them (none: the table is cleared) and the context's pointer. */
+struct HostTable {
+    const std::vector<uint32_t> &words;
+    void **slot;
+};
+
+/* The one place a table of the rules, windows, relations or chains reaches the device: every table into a fresh buffer, then the stream
+ * synchronised (the words are the caller's locals, and no pass may still read an old table), then the old buffers freed and the new ones
+ * in their place.  All or nothing: on failure the context is as it was. */
+int swap_tables(kmpgpu_ctx *c, const char *what, std::initializer_list<HostTable> tables)
+{
+    std::vector<void *> fresh;
+    hipError_t e = hipSuccess;
+    for (const HostTable &tb : tables) {
+        const size_t bytes = tb.words.size() * sizeof(uint32_t);
+        fresh.push_back(nullptr);
+        if (e == hipSuccess && bytes) e = hipMalloc(&fresh.back(), bytes);
+        if (e == hipSuccess && bytes) e = hipMemcpyAsync(fresh.back(), tb.words.data(), bytes, hipMemcpyHostToDevice, c->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        for (void *d : fresh) free_buffer(&d);
+        return alloc_fail(e, "%s could not be uploaded", what);
+    }
+    size_t k = 0;
+    for (const HostTable &tb : tables) {
+        free_buffer(tb.slot);
+        *tb.slot = fresh[k++];
+    }
+    return KMPGPU_OK;
+}
+
+/* what every setter checks before it looks at its table */
+int setter_state(kmpgpu_ctx *c, const char *who)
+{
+    if (!c) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
+    if (!c->d_patterns || c->n_pat == 0) return fail(KMPGPU_ESTATE, "%s: no patterns set", who);
+    HIP_TRY(hipSetDevice(c->device));
+    return KMPGPU_OK;
+}
+
 }  // namespace
 
 int kmpgpu_scan_packets(kmpgpu_ctx *c, uint64_t *pkt_counts_out, uint64_t *any_out, uint64_t *hits_out, uint64_t *counts_out, kmpgpu_timing *t)
 {
     if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_scan_packets: ctx is NULL");
-    MarkPass p;
-    const int rc = marking_pass(c, "kmpgpu_scan_packets", &p);
-    if (rc) return rc;
-    const size_t np = c->n_pat;
-    if (p.empty) {
-        /* nothing to scan: every payload count, every total is 0, and there are no bit words */
-        if (pkt_counts_out) memset(pkt_counts_out, 0, np * sizeof(uint64_t));
-        if (counts_out) memset(counts_out, 0, np * sizeof(uint64_t));
-        if (t) { *t = kmpgpu_timing{}; }
-        return KMPGPU_OK;
-    }
-    HIP_TRY(kmp_launch_marks_reduce(p.d_mat, c->n_pat, p.stride, p.d_pc, p.d_any, c->stream));
-    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-    if (pkt_counts_out) HIP_TRY(hipMemcpyAsync(pkt_counts_out, p.d_pc, np * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (any_out) HIP_TRY(hipMemcpyAsync(any_out, p.d_any, p.W * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, p.d_cnt, np * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (hits_out) HIP_TRY(download_rows(c, hits_out, p.d_mat, p.W, p.stride, np));
-    return finish_marking(c, p.launches + 1u, t);
+    return scan_family(c, "kmpgpu_scan_packets", KMPGPU_ALERT_PATTERNS, pkt_counts_out, any_out, hits_out, counts_out, t);
 }
 
 int kmpgpu_set_rules(kmpgpu_ctx *c, const uint32_t *rule_off, const uint32_t *terms, uint32_t n_rules)
 {
-    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_set_rules: ctx is NULL");
-    if (!c->d_patterns || c->n_pat == 0) return fail(KMPGPU_ESTATE, "kmpgpu_set_rules: no patterns set");
-    HIP_TRY(hipSetDevice(c->device));
-    if (n_rules == 0) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        drop_rules(c);
-        return KMPGPU_OK;
+    const int sr = setter_state(c, "kmpgpu_set_rules");
+    if (sr) return sr;
+    std::vector<uint32_t> heads, quads;
+    std::string msg;
+    if (n_rules) {
+        const int rc = kmp_pack_rules(rule_off, terms, n_rules, c->n_pat, c->n_rel, c->n_chains, &heads, &quads, &msg);
+        if (rc) return fail(rc, "%s", msg.c_str());
+        if (quads.empty()) quads.assign(4, 0u);         /* rules of one or two terms only: one quad nobody reads, never a NULL table */
     }
-    if (!rule_off || !terms) return fail(KMPGPU_EINVAL, "kmpgpu_set_rules: NULL rule arrays");
-    if (rule_off[0] != 0) return fail(KMPGPU_EINVAL, "kmpgpu_set_rules: rule_off[0] is %u, not 0", rule_off[0]);
-    /* the device form (kmp_launch.h): a head per rule with its first two terms, the others in quads; positive terms first, so that
-     * a lane of the kernel whose payloads miss one of them stops early */
-    std::vector<uint4> heads(n_rules), quads;
-    std::vector<uint32_t> ord;
-    for (uint32_t r = 0; r < n_rules; r++) {
-        if (rule_off[r + 1] < rule_off[r]) return fail(KMPGPU_EINVAL, "kmpgpu_set_rules: rule_off decreases at rule %u", r);
-        if (rule_off[r + 1] == rule_off[r]) return fail(KMPGPU_EINVAL, "kmpgpu_set_rules: rule %u has no terms", r);
-        ord.clear();
-        for (int neg = 0; neg < 2; neg++)
-            for (uint32_t j = rule_off[r]; j < rule_off[r + 1]; j++) {
-                if ((terms[j] & ~KMPGPU_RULE_NOT) >= c->n_pat + c->n_rel + c->n_chains)    /* (the sum < 2^31: kmpgpu_set_relations, kmpgpu_set_chains) */
-                    return fail(KMPGPU_EINVAL, "kmpgpu_set_rules: rule %u: term %u names row %u of %u patterns + %u relations + %u chains", r,
-                                j - rule_off[r], terms[j] & ~KMPGPU_RULE_NOT, c->n_pat, c->n_rel, c->n_chains);
-                if (((terms[j] & KMPGPU_RULE_NOT) != 0) == (neg != 0)) ord.push_back(terms[j]);
-            }
-        /* filled up with a term that is loaded at the same time: a repeated term changes nothing */
-        if (ord.size() < 2) ord.push_back(ord[0]);
-        while ((ord.size() - 2) % 4) ord.push_back(ord[ord.size() - (ord.size() - 2) % 4]);
-        if (quads.size() + (ord.size() - 2) / 4 > 0xFFFFFFFFull) return fail(KMPGPU_EINVAL, "kmpgpu_set_rules: too many terms");
-        heads[r] = make_uint4((uint32_t)quads.size(), (uint32_t)(quads.size() + (ord.size() - 2) / 4), ord[0], ord[1]);
-        for (size_t j = 2; j < ord.size(); j += 4) quads.push_back(make_uint4(ord[j], ord[j + 1], ord[j + 2], ord[j + 3]));
-    }
-    uint4 *d_heads = nullptr, *d_quads = nullptr;
-    hipError_t e = hipMalloc((void **)&d_heads, heads.size() * sizeof(uint4));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_quads, (quads.size() ? quads.size() : 1) * sizeof(uint4));
-    if (e == hipSuccess) e = hipMemcpy(d_heads, heads.data(), heads.size() * sizeof(uint4), hipMemcpyHostToDevice);
-    if (e == hipSuccess && !quads.empty()) e = hipMemcpy(d_quads, quads.data(), quads.size() * sizeof(uint4), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        free_buffer(&d_heads);
-        free_buffer(&d_quads);
-        return alloc_fail(e, "kmpgpu_set_rules: the rules could not be uploaded");
-    }
-    drop_rules(c);
-    c->d_rule_heads = d_heads; c->d_rule_quads = d_quads; c->n_rules = n_rules;
+    const int rc = swap_tables(c, "kmpgpu_set_rules: the rules", {{heads, (void **)&c->d_rule_heads}, {quads, (void **)&c->d_rule_quads}});
+    if (rc) return rc;
+    c->n_rules = n_rules;
     return KMPGPU_OK;
 }
 
 int kmpgpu_set_windows(kmpgpu_ctx *c, const uint32_t *first, const uint32_t *last, uint32_t n_pat)
 {
-    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_set_windows: ctx is NULL");
-    if (!c->d_patterns || c->n_pat == 0) return fail(KMPGPU_ESTATE, "kmpgpu_set_windows: no patterns set");
-    HIP_TRY(hipSetDevice(c->device));
-    if (n_pat == 0) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        drop_windows(c);
-        return KMPGPU_OK;
+    const int sr = setter_state(c, "kmpgpu_set_windows");
+    if (sr) return sr;
+    std::vector<uint32_t> win;
+    std::string msg;
+    if (n_pat) {
+        const int rc = kmp_pack_windows(first, last, n_pat, c->n_pat, &win, &msg);
+        if (rc) return fail(rc, "%s", msg.c_str());
     }
-    if (n_pat != c->n_pat) return fail(KMPGPU_EINVAL, "kmpgpu_set_windows: %u windows for %u patterns", n_pat, c->n_pat);
-    if (!first || !last) return fail(KMPGPU_EINVAL, "kmpgpu_set_windows: NULL window arrays");
-    std::vector<uint2> win(n_pat);
-    bool all_default = true;
-    for (uint32_t i = 0; i < n_pat; i++) {
-        if (first[i] > last[i]) return fail(KMPGPU_EINVAL, "kmpgpu_set_windows: pattern %u: first %u lies behind last %u", i, first[i], last[i]);
-        win[i] = make_uint2(first[i], last[i]);
-        all_default = all_default && first[i] == 0u && last[i] == 0xFFFFFFFFu;
-    }
-    /* no window differs from the default: no table, and the emitting passes run what they run without windows */
-    uint2 *d_win = nullptr;
-    if (!all_default) {
-        hipError_t e = hipMalloc((void **)&d_win, win.size() * sizeof(uint2));
-        if (e == hipSuccess) e = hipMemcpyAsync(d_win, win.data(), win.size() * sizeof(uint2), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      /* (win is a local) */
-        if (e != hipSuccess) {
-            free_buffer(&d_win);
-            return alloc_fail(e, "kmpgpu_set_windows: the windows could not be uploaded");
-        }
-    } else HIP_TRY(hipStreamSynchronize(c->stream));
-    drop_windows(c);
-    c->d_windows = d_win;
-    return KMPGPU_OK;
+    return swap_tables(c, "kmpgpu_set_windows: the windows", {{win, (void **)&c->d_windows}});
 }
 
 int kmpgpu_scan_rules(kmpgpu_ctx *c, uint64_t *rule_pkt_counts_out, uint64_t *any_out, uint64_t *rule_hits_out, uint64_t *counts_out, kmpgpu_timing *t)
 {
     if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_scan_rules: ctx is NULL");
     if (c->n_rules == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan_rules: no rules set");
-    MarkPass p;
-    const int rc = marking_pass(c, "kmpgpu_scan_rules", &p);
-    if (rc) return rc;
-    const size_t np = c->n_pat, nr = c->n_rules;
-    if (p.empty) {
-        /* nothing to scan: no rule matches anything (an all-negated rule has no payload to match either), and there are no bit words */
-        if (rule_pkt_counts_out) memset(rule_pkt_counts_out, 0, nr * sizeof(uint64_t));
-        if (counts_out) memset(counts_out, 0, np * sizeof(uint64_t));
-        if (t) { *t = kmpgpu_timing{}; }
-        return KMPGPU_OK;
-    }
-    RuleStage o;
-    const int rr = enqueue_rules(c, "kmpgpu_scan_rules", p, &o);
-    if (rr) return rr;
-    unsigned long long *d_rows = o.d_rows, *d_rc = o.d_rc, *d_any = o.d_any;
-    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-    if (rule_pkt_counts_out) HIP_TRY(hipMemcpyAsync(rule_pkt_counts_out, d_rc, nr * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (any_out) HIP_TRY(hipMemcpyAsync(any_out, d_any, p.W * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, p.d_cnt, np * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (rule_hits_out) HIP_TRY(download_rows(c, rule_hits_out, d_rows, p.W, p.stride, nr));
-    return finish_marking(c, p.launches + o.launches, t);
+    return scan_family(c, "kmpgpu_scan_rules", KMPGPU_ALERT_RULES, rule_pkt_counts_out, any_out, rule_hits_out, counts_out, t);
 }
 
 int kmpgpu_set_relations(kmpgpu_ctx *c, const kmpgpu_relation *rel, uint32_t n_rel)
 {
-    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_set_relations: ctx is NULL");
-    if (!c->d_patterns || c->n_pat == 0) return fail(KMPGPU_ESTATE, "kmpgpu_set_relations: no patterns set");
-    HIP_TRY(hipSetDevice(c->device));
-    static_assert(sizeof(kmpgpu_relation) == sizeof(uint4), "a relation is a 16-byte record");
-    uint4 *d_rel = nullptr;
+    const int sr = setter_state(c, "kmpgpu_set_relations");
+    if (sr) return sr;
+    std::vector<uint32_t> host;
+    std::string msg;
     if (n_rel) {
-        if (!rel) return fail(KMPGPU_EINVAL, "kmpgpu_set_relations: rel is NULL");
-        if ((uint64_t)c->n_pat + n_rel + c->n_chains >= (1ull << 31))
-            return fail(KMPGPU_EINVAL, "kmpgpu_set_relations: %u patterns + %u relations%s do not fit the 2^31 rows a rule term can name", c->n_pat, n_rel,
-                        c->n_chains ? " + the chains" : "");
-        std::vector<uint4> host(n_rel);
-        for (uint32_t q = 0; q < n_rel; q++) {
-            const kmpgpu_relation &r = rel[q];
-            if (r.a >= c->n_pat || r.b >= c->n_pat)
-                return fail(KMPGPU_EINVAL, "kmpgpu_set_relations: relation %u names pattern %u of %u", q, r.a >= c->n_pat ? r.a : r.b, c->n_pat);
-            if (r.dmin > r.dmax) return fail(KMPGPU_EINVAL, "kmpgpu_set_relations: relation %u: dmin %d lies above dmax %d", q, r.dmin, r.dmax);
-            /* bit 31: the pattern's bytes are compared in the folded copy of the arena */
-            host[q] = make_uint4(r.a | ((uint32_t)c->pat_fold[r.a] << 31), r.b | ((uint32_t)c->pat_fold[r.b] << 31), (uint32_t)r.dmin, (uint32_t)r.dmax);
-        }
-        hipError_t e = hipMalloc((void **)&d_rel, host.size() * sizeof(uint4));
-        if (e == hipSuccess) e = hipMemcpyAsync(d_rel, host.data(), host.size() * sizeof(uint4), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      /* (host is a local) */
-        if (e != hipSuccess) {
-            free_buffer(&d_rel);
-            return alloc_fail(e, "kmpgpu_set_relations: the relations could not be uploaded");
-        }
-    } else HIP_TRY(hipStreamSynchronize(c->stream));
-    drop_relations(c);
+        const int rc = kmp_pack_relations(rel, n_rel, c->n_pat, c->n_chains, c->pat_fold.data(), &host, &msg);
+        if (rc) return fail(rc, "%s", msg.c_str());
+    }
+    const int rc = swap_tables(c, "kmpgpu_set_relations: the relations", {{host, (void **)&c->d_relations}});
+    if (rc) return rc;
     drop_rules(c);                                 /* the rows their terms named are no longer the same, whatever was set or cleared */
-    c->d_relations = d_rel; c->n_rel = n_rel;
+    c->n_rel = n_rel;
     return KMPGPU_OK;
 }
 
@@ -1846,68 +1829,23 @@ int kmpgpu_scan_relations(kmpgpu_ctx *c, uint64_t *rel_pkt_counts_out, uint64_t 
     if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_scan_relations: ctx is NULL");
     if (!c->d_patterns || c->n_pat == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan_relations: no patterns set");
     if (c->n_rel == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan_relations: no relations set");
-    MarkPass p;
-    const int rc = marking_pass(c, "kmpgpu_scan_relations", &p);
-    if (rc) return rc;
-    const size_t np = c->n_pat, nq = c->n_rel;
-    if (p.empty) {
-        /* nothing to scan: no relation holds anywhere, and there are no bit words */
-        if (rel_pkt_counts_out) memset(rel_pkt_counts_out, 0, nq * sizeof(uint64_t));
-        if (counts_out) memset(counts_out, 0, np * sizeof(uint64_t));
-        if (t) { *t = kmpgpu_timing{}; }
-        return KMPGPU_OK;
-    }
-    const int rr = enqueue_relations(c, p);
-    if (rr) return rr;
-    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-    if (rel_pkt_counts_out) HIP_TRY(hipMemcpyAsync(rel_pkt_counts_out, p.d_relc, nq * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (any_out) HIP_TRY(hipMemcpyAsync(any_out, p.d_any, p.W * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, p.d_cnt, np * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (rel_hits_out) HIP_TRY(download_rows(c, rel_hits_out, p.d_rel, p.W, p.stride, nq));
-    return finish_marking(c, p.launches + 1u, t);
+    return scan_family(c, "kmpgpu_scan_relations", KMPGPU_ALERT_RELATIONS, rel_pkt_counts_out, any_out, rel_hits_out, counts_out, t);
 }
 
 int kmpgpu_set_chains(kmpgpu_ctx *c, const uint32_t *chain_off, const kmpgpu_chain_link *links, uint32_t n_chains)
 {
-    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_set_chains: ctx is NULL");
-    if (!c->d_patterns || c->n_pat == 0) return fail(KMPGPU_ESTATE, "kmpgpu_set_chains: no patterns set");
-    HIP_TRY(hipSetDevice(c->device));
-    uint4 *d_chains = nullptr;
+    const int sr = setter_state(c, "kmpgpu_set_chains");
+    if (sr) return sr;
+    std::vector<uint32_t> host;
+    std::string msg;
     if (n_chains) {
-        if (!chain_off || !links) return fail(KMPGPU_EINVAL, "kmpgpu_set_chains: NULL chain arrays");
-        if ((uint64_t)c->n_pat + c->n_rel + n_chains >= (1ull << 31))
-            return fail(KMPGPU_EINVAL, "kmpgpu_set_chains: %u patterns + %u relations + %u chains do not fit the 2^31 rows a rule term can name", c->n_pat,
-                        c->n_rel, n_chains);
-        if (chain_off[0] != 0) return fail(KMPGPU_EINVAL, "kmpgpu_set_chains: chain_off[0] is %u, not 0", chain_off[0]);
-        /* the device form (kmp_launch.h): KMPGPU_CHAIN_MAX records per chain, {pattern | fold << 31, dmin, dmax, n} per link, the records behind
-         * the last link repeating it */
-        std::vector<uint4> host((size_t)n_chains * KMPGPU_CHAIN_MAX);
-        for (uint32_t q = 0; q < n_chains; q++) {
-            if (chain_off[q + 1] < chain_off[q]) return fail(KMPGPU_EINVAL, "kmpgpu_set_chains: chain_off decreases at chain %u", q);
-            const uint32_t n = chain_off[q + 1] - chain_off[q];
-            if (n < 2 || n > KMPGPU_CHAIN_MAX) return fail(KMPGPU_EINVAL, "kmpgpu_set_chains: chain %u has %u contents, not 2 .. %d", q, n, KMPGPU_CHAIN_MAX);
-            const kmpgpu_chain_link *l = links + chain_off[q];
-            if (l[0].dmin != INT32_MIN || l[0].dmax != INT32_MAX)
-                return fail(KMPGPU_EINVAL, "kmpgpu_set_chains: chain %u: its first content is relative to nothing and carries no bounds (a window places it)", q);
-            for (uint32_t i = 0; i < KMPGPU_CHAIN_MAX; i++) {
-                const kmpgpu_chain_link &k = l[i < n ? i : n - 1];
-                if (k.pattern >= c->n_pat) return fail(KMPGPU_EINVAL, "kmpgpu_set_chains: chain %u names pattern %u of %u", q, k.pattern, c->n_pat);
-                if (k.dmin > k.dmax) return fail(KMPGPU_EINVAL, "kmpgpu_set_chains: chain %u: dmin %d lies above dmax %d", q, k.dmin, k.dmax);
-                /* bit 31: the pattern's bytes are compared in the folded copy of the arena */
-                host[(size_t)q * KMPGPU_CHAIN_MAX + i] = make_uint4(k.pattern | ((uint32_t)c->pat_fold[k.pattern] << 31), (uint32_t)k.dmin, (uint32_t)k.dmax, n);
-            }
-        }
-        hipError_t e = hipMalloc((void **)&d_chains, host.size() * sizeof(uint4));
-        if (e == hipSuccess) e = hipMemcpyAsync(d_chains, host.data(), host.size() * sizeof(uint4), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      /* (host is a local) */
-        if (e != hipSuccess) {
-            free_buffer(&d_chains);
-            return alloc_fail(e, "kmpgpu_set_chains: the chains could not be uploaded");
-        }
-    } else HIP_TRY(hipStreamSynchronize(c->stream));
-    drop_chains(c);
+        const int rc = kmp_pack_chains(chain_off, links, n_chains, c->n_pat, c->n_rel, c->pat_fold.data(), &host, &msg);
+        if (rc) return fail(rc, "%s", msg.c_str());
+    }
+    const int rc = swap_tables(c, "kmpgpu_set_chains: the chains", {{host, (void **)&c->d_chains}});
+    if (rc) return rc;
     drop_rules(c);                                 /* the rows their terms named are no longer the same, whatever was set or cleared */
-    c->d_chains = d_chains; c->n_chains = n_chains;
+    c->n_chains = n_chains;
     return KMPGPU_OK;
 }
 
@@ -1916,25 +1854,7 @@ int kmpgpu_scan_chains(kmpgpu_ctx *c, uint64_t *chain_pkt_counts_out, uint64_t *
     if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_scan_chains: ctx is NULL");
     if (!c->d_patterns || c->n_pat == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan_chains: no patterns set");
     if (c->n_chains == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan_chains: no chains set");
-    MarkPass p;
-    const int rc = marking_pass(c, "kmpgpu_scan_chains", &p);
-    if (rc) return rc;
-    const size_t np = c->n_pat, nq = c->n_chains;
-    if (p.empty) {
-        /* nothing to scan: no chain holds anywhere, and there are no bit words */
-        if (chain_pkt_counts_out) memset(chain_pkt_counts_out, 0, nq * sizeof(uint64_t));
-        if (counts_out) memset(counts_out, 0, np * sizeof(uint64_t));
-        if (t) { *t = kmpgpu_timing{}; }
-        return KMPGPU_OK;
-    }
-    const int rr = enqueue_chains(c, p);
-    if (rr) return rr;
-    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-    if (chain_pkt_counts_out) HIP_TRY(hipMemcpyAsync(chain_pkt_counts_out, p.d_chainc, nq * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (any_out) HIP_TRY(hipMemcpyAsync(any_out, p.d_any, p.W * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, p.d_cnt, np * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (chain_hits_out) HIP_TRY(download_rows(c, chain_hits_out, p.d_chain, p.W, p.stride, nq));
-    return finish_marking(c, p.launches + 1u, t);
+    return scan_family(c, "kmpgpu_scan_chains", KMPGPU_ALERT_CHAINS, chain_pkt_counts_out, any_out, chain_hits_out, counts_out, t);
 }
 
 int kmpgpu_scan_alerts(kmpgpu_ctx *c, int family, uint64_t max_records, uint64_t *n_found, uint64_t *n_packets, uint64_t *pkt_counts_out,
@@ -1944,15 +1864,9 @@ int kmpgpu_scan_alerts(kmpgpu_ctx *c, int family, uint64_t max_records, uint64_t
     if (!c || !n_found) return fail(KMPGPU_EINVAL, "kmpgpu_scan_alerts: NULL argument");
     *n_found = 0;
     if (n_packets) *n_packets = 0;
-    /* the rows of the family, as its own call checks them */
-    uint64_t n_rows = 0;
-    switch (family) {
-    case KMPGPU_ALERT_PATTERNS:  n_rows = c->n_pat; break;            /* (no patterns: the marking pass says so) */
-    case KMPGPU_ALERT_RULES:     n_rows = c->n_rules; break;
-    case KMPGPU_ALERT_RELATIONS: n_rows = c->n_rel; break;
-    case KMPGPU_ALERT_CHAINS:    n_rows = c->n_chains; break;
-    default: return fail(KMPGPU_EINVAL, "kmpgpu_scan_alerts: family %d is none of KMPGPU_ALERT_*", family);
-    }
+    if (family < KMPGPU_ALERT_PATTERNS || family > KMPGPU_ALERT_CHAINS) return fail(KMPGPU_EINVAL, "kmpgpu_scan_alerts: family %d is none of KMPGPU_ALERT_*", family);
+    /* the rows of the family, as its own call checks them (no patterns for the patterns' own: the marking pass says so) */
+    const uint64_t n_rows = family_n_rows(c, family);
     if (family != KMPGPU_ALERT_PATTERNS && (!c->d_patterns || c->n_pat == 0)) return fail(KMPGPU_ESTATE, "kmpgpu_scan_alerts: no patterns set");
     if (family != KMPGPU_ALERT_PATTERNS && n_rows == 0)
         return fail(KMPGPU_ESTATE, "kmpgpu_scan_alerts: no %s set", family == KMPGPU_ALERT_RULES ? "rules" : family == KMPGPU_ALERT_RELATIONS ? "relations" : "chains");
@@ -1961,42 +1875,19 @@ int kmpgpu_scan_alerts(kmpgpu_ctx *c, int family, uint64_t max_records, uint64_t
     if (16ull * n_rows > 0xFFFFFFFEull) return fail(KMPGPU_EINVAL, "kmpgpu_scan_alerts: %llu rows: 16 bytes x rows do not fit 32 bits", (unsigned long long)n_rows);
     c->alerts_valid = false;                       /* the list before this pass is gone, whatever happens */
     MarkPass p;
-    const int rc = marking_pass(c, "kmpgpu_scan_alerts", &p);
+    const int rc = begin_family(c, "kmpgpu_scan_alerts", family, pkt_counts_out, counts_out, t, &p);
     if (rc) return rc;
-    n_rows = family == KMPGPU_ALERT_PATTERNS ? c->n_pat : n_rows;
-    const size_t np = c->n_pat;
     if (p.empty) {
         /* nothing to scan: an empty list */
-        if (pkt_counts_out) memset(pkt_counts_out, 0, (size_t)n_rows * sizeof(uint64_t));
-        if (counts_out) memset(counts_out, 0, np * sizeof(uint64_t));
-        if (t) { *t = kmpgpu_timing{}; }
         c->alerts_kept = 0; c->alerts_valid = true;
         return KMPGPU_OK;
     }
     /* the family's rows, their popcounts and their OR, by the kernels of the family's own call */
-    const unsigned long long *d_rows = nullptr, *d_pc = nullptr, *d_any = nullptr;
-    uint32_t launches = p.launches + 1u;
+    FamilyRows f;
+    const int rr = enqueue_family(c, "kmpgpu_scan_alerts", family, p, /* profile_reduce = */ true, &f);
+    if (rr) return rr;
+    uint32_t launches = p.launches + f.launches;
     hipEvent_t e1;
-    if (family == KMPGPU_ALERT_PATTERNS) {
-        HIP_TRY(profile_launch(c, &e1));
-        HIP_TRY(kmp_launch_marks_reduce(p.d_mat, c->n_pat, p.stride, p.d_pc, p.d_any, c->stream));
-        HIP_TRY(profile_launched(c, e1));
-        d_rows = p.d_mat; d_pc = p.d_pc; d_any = p.d_any;
-    } else if (family == KMPGPU_ALERT_RULES) {
-        RuleStage o;
-        const int rr = enqueue_rules(c, "kmpgpu_scan_alerts", p, &o);
-        if (rr) return rr;
-        d_rows = o.d_rows; d_pc = o.d_rc; d_any = o.d_any;
-        launches = p.launches + o.launches;
-    } else if (family == KMPGPU_ALERT_RELATIONS) {
-        const int rr = enqueue_relations(c, p);
-        if (rr) return rr;
-        d_rows = p.d_rel; d_pc = p.d_relc; d_any = p.d_any;
-    } else {
-        const int rr = enqueue_chains(c, p);
-        if (rr) return rr;
-        d_rows = p.d_chain; d_pc = p.d_chainc; d_any = p.d_any;
-    }
     /* the list: count, scan (in the scratch kept for kmpgpu_load_frames, as kmpgpu_load_selected uses it), the totals read once, fill */
     hipError_t e = grow_buffer(&c->fr_ws, &c->fr_ws_cap, (uint64_t)kmp_extract_ws_bytes(c->n_pkts), EIGHTH);
     if (e == hipSuccess && !c->fr_tot) e = hipMalloc(&c->fr_tot, 2 * sizeof(unsigned long long));
@@ -2005,7 +1896,7 @@ int kmpgpu_scan_alerts(kmpgpu_ctx *c, int family, uint64_t max_records, uint64_t
         return alloc_fail(e, "kmpgpu_scan_alerts: the scan workspace (%llu bytes) could not be allocated", (unsigned long long)kmp_extract_ws_bytes(c->n_pkts));
     }
     HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_alerts_count(d_rows, p.stride, (uint32_t)n_rows, c->n_pkts, d_any, c->fr_ws, c->stream));
+    HIP_TRY(kmp_launch_alerts_count(f.d_rows, p.stride, (uint32_t)f.n_rows, c->n_pkts, f.d_any, c->fr_ws, c->stream));
     HIP_TRY(profile_launched(c, e1));
     HIP_TRY(profile_launch(c, &e1));
     HIP_TRY(kmp_launch_alerts_scan(c->n_pkts, c->fr_ws, c->fr_tot, c->stream));
@@ -2020,13 +1911,13 @@ int kmpgpu_scan_alerts(kmpgpu_ctx *c, int family, uint64_t max_records, uint64_t
         e = grow_buffer(&c->d_alerts, &c->alerts_cap, kept, EIGHTH);
         if (e != hipSuccess) return alloc_fail(e, "kmpgpu_scan_alerts: the records (%llu bytes) could not be allocated", (unsigned long long)(kept * 16u));
         HIP_TRY(profile_launch(c, &e1));
-        HIP_TRY(kmp_launch_alerts_fill(d_rows, p.stride, (uint32_t)n_rows, c->n_pkts, d_any, c->fr_ws, c->d_alerts, kept, c->stream));
+        HIP_TRY(kmp_launch_alerts_fill(f.d_rows, p.stride, (uint32_t)f.n_rows, c->n_pkts, f.d_any, c->fr_ws, c->d_alerts, kept, c->stream));
         HIP_TRY(profile_launched(c, e1));
         launches += 1u;
     }
     HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-    if (pkt_counts_out) HIP_TRY(hipMemcpyAsync(pkt_counts_out, d_pc, (size_t)n_rows * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, p.d_cnt, np * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (pkt_counts_out) HIP_TRY(hipMemcpyAsync(pkt_counts_out, f.d_pc, (size_t)f.n_rows * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, p.d_cnt, (size_t)c->n_pat * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     const int fr = finish_marking(c, launches, t);
     if (fr) return fr;
     *n_found = found;

@@ -353,93 +353,49 @@ class GpuMatcher:
         arr = np.frombuffer(buf, dtype=np.dtype([("packet", "<u8"), ("offset", "<u4"), ("pattern", "<u4")]), count=k).copy()
         return arr, int(found.value), counts[:n]
 
+    def _scan_family(self, fn, rows: int, counts_key: str, hits: bool) -> dict:
+        """What scan_packets, scan_rules, scan_relations and scan_chains share: the C call ``fn`` over a family of ``rows`` rows, its
+        per-row payload counts returned under ``counts_key``."""
+        n = len(self.patterns)
+        n_pkts, _ = self.arena_info()
+        W = (n_pkts + 63) // 64
+        row_counts = np.zeros(max(rows, 1), dtype=np.uint64)
+        counts = np.zeros(max(n, 1), dtype=np.uint64)
+        any_w = np.zeros(max(W, 1), dtype=np.uint64)
+        hit_w = np.zeros((rows, W) if hits and rows * W else 1, dtype=np.uint64)
+        t = Timing()
+        gpu_check(getattr(self._g, fn)(self._ctx, row_counts.ctypes.data, any_w.ctypes.data, hit_w.ctypes.data if hits else None,
+                                       counts.ctypes.data, C.byref(t)), fn)
+        out = {counts_key: row_counts[:rows], "counts": counts[:n], "timing": t,
+               "any": np.unpackbits(any_w[:W].view(np.uint8), bitorder="little")[:n_pkts].astype(bool)}
+        if hits:
+            bits = np.unpackbits(hit_w.reshape(rows, W).view(np.uint8), axis=1, bitorder="little") if rows * W else np.zeros((rows, 0), np.uint8)
+            out["hits"] = bits[:, :n_pkts].astype(bool)
+        return out
+
     def scan_packets(self, hits: bool = False) -> dict:
         """Which payloads hold which patterns (kmpgpu_scan_packets), one pass on the device:
         ``pkt_counts`` (uint64[n_pat]) payloads that hold pattern i, ``any`` (bool[n_pkts]) payload k holds some pattern,
         ``counts`` (uint64[n_pat]) as scan(), ``timing``; with hits=True also ``hits`` (bool[n_pat, n_pkts])."""
-        n = len(self.patterns)
-        n_pkts, _ = self.arena_info()
-        W = (n_pkts + 63) // 64
-        pkt_counts = np.zeros(max(n, 1), dtype=np.uint64)
-        counts = np.zeros(max(n, 1), dtype=np.uint64)
-        any_w = np.zeros(max(W, 1), dtype=np.uint64)
-        hit_w = np.zeros((n, W) if hits and n * W else 1, dtype=np.uint64)
-        t = Timing()
-        gpu_check(self._g.kmpgpu_scan_packets(self._ctx, pkt_counts.ctypes.data, any_w.ctypes.data,
-                                              hit_w.ctypes.data if hits else None, counts.ctypes.data, C.byref(t)),
-                  "kmpgpu_scan_packets")
-        out = {"pkt_counts": pkt_counts[:n], "counts": counts[:n], "timing": t,
-               "any": np.unpackbits(any_w[:W].view(np.uint8), bitorder="little")[:n_pkts].astype(bool)}
-        if hits:
-            bits = np.unpackbits(hit_w.reshape(n, W).view(np.uint8), axis=1, bitorder="little") if n * W else np.zeros((n, 0), np.uint8)
-            out["hits"] = bits[:, :n_pkts].astype(bool)
-        return out
+        return self._scan_family("kmpgpu_scan_packets", len(self.patterns), "pkt_counts", hits)
 
     def scan_rules(self, hits: bool = False) -> dict:
         """Which payloads match which rules (kmpgpu_scan_rules): the marking pass of scan_packets and the rules on the device.
         ``rule_pkt_counts`` (uint64[n_rules]) payloads that rule r matches, ``any`` (bool[n_pkts]) payload k matches some rule,
         ``counts`` (uint64[n_pat]) as scan(), ``timing``; with hits=True also ``hits`` (bool[n_rules, n_pkts])."""
-        n, nr = len(self.patterns), len(self.rules)
-        n_pkts, _ = self.arena_info()
-        W = (n_pkts + 63) // 64
-        rule_counts = np.zeros(max(nr, 1), dtype=np.uint64)
-        counts = np.zeros(max(n, 1), dtype=np.uint64)
-        any_w = np.zeros(max(W, 1), dtype=np.uint64)
-        hit_w = np.zeros((nr, W) if hits and nr * W else 1, dtype=np.uint64)
-        t = Timing()
-        gpu_check(self._g.kmpgpu_scan_rules(self._ctx, rule_counts.ctypes.data, any_w.ctypes.data,
-                                            hit_w.ctypes.data if hits else None, counts.ctypes.data, C.byref(t)),
-                  "kmpgpu_scan_rules")
-        out = {"rule_pkt_counts": rule_counts[:nr], "counts": counts[:n], "timing": t,
-               "any": np.unpackbits(any_w[:W].view(np.uint8), bitorder="little")[:n_pkts].astype(bool)}
-        if hits:
-            bits = np.unpackbits(hit_w.reshape(nr, W).view(np.uint8), axis=1, bitorder="little") if nr * W else np.zeros((nr, 0), np.uint8)
-            out["hits"] = bits[:, :n_pkts].astype(bool)
-        return out
+        return self._scan_family("kmpgpu_scan_rules", len(self.rules), "rule_pkt_counts", hits)
 
     def scan_relations(self, hits: bool = False) -> dict:
         """In which payloads which relations hold (kmpgpu_scan_relations): the marking pass of scan_packets and the relation kernel.
         ``rel_pkt_counts`` (uint64[n_rel]) payloads in which relation q holds, ``any`` (bool[n_pkts]) some relation holds in payload k,
         ``counts`` (uint64[n_pat]) as scan(), ``timing``; with hits=True also ``hits`` (bool[n_rel, n_pkts])."""
-        n, nq = len(self.patterns), len(self.relations)
-        n_pkts, _ = self.arena_info()
-        W = (n_pkts + 63) // 64
-        rel_counts = np.zeros(max(nq, 1), dtype=np.uint64)
-        counts = np.zeros(max(n, 1), dtype=np.uint64)
-        any_w = np.zeros(max(W, 1), dtype=np.uint64)
-        hit_w = np.zeros((nq, W) if hits and nq * W else 1, dtype=np.uint64)
-        t = Timing()
-        gpu_check(self._g.kmpgpu_scan_relations(self._ctx, rel_counts.ctypes.data, any_w.ctypes.data,
-                                                hit_w.ctypes.data if hits else None, counts.ctypes.data, C.byref(t)),
-                  "kmpgpu_scan_relations")
-        out = {"rel_pkt_counts": rel_counts[:nq], "counts": counts[:n], "timing": t,
-               "any": np.unpackbits(any_w[:W].view(np.uint8), bitorder="little")[:n_pkts].astype(bool)}
-        if hits:
-            bits = np.unpackbits(hit_w.reshape(nq, W).view(np.uint8), axis=1, bitorder="little") if nq * W else np.zeros((nq, 0), np.uint8)
-            out["hits"] = bits[:, :n_pkts].astype(bool)
-        return out
+        return self._scan_family("kmpgpu_scan_relations", len(self.relations), "rel_pkt_counts", hits)
 
     def scan_chains(self, hits: bool = False) -> dict:
         """In which payloads which chains hold (kmpgpu_scan_chains): the marking pass of scan_packets and the chain kernel.
         ``chain_pkt_counts`` (uint64[n_chains]) payloads in which chain c holds, ``any`` (bool[n_pkts]) some chain holds in payload k,
         ``counts`` (uint64[n_pat]) as scan(), ``timing``; with hits=True also ``hits`` (bool[n_chains, n_pkts])."""
-        n, nq = len(self.patterns), len(self.chains)
-        n_pkts, _ = self.arena_info()
-        W = (n_pkts + 63) // 64
-        chain_counts = np.zeros(max(nq, 1), dtype=np.uint64)
-        counts = np.zeros(max(n, 1), dtype=np.uint64)
-        any_w = np.zeros(max(W, 1), dtype=np.uint64)
-        hit_w = np.zeros((nq, W) if hits and nq * W else 1, dtype=np.uint64)
-        t = Timing()
-        gpu_check(self._g.kmpgpu_scan_chains(self._ctx, chain_counts.ctypes.data, any_w.ctypes.data,
-                                             hit_w.ctypes.data if hits else None, counts.ctypes.data, C.byref(t)),
-                  "kmpgpu_scan_chains")
-        out = {"chain_pkt_counts": chain_counts[:nq], "counts": counts[:n], "timing": t,
-               "any": np.unpackbits(any_w[:W].view(np.uint8), bitorder="little")[:n_pkts].astype(bool)}
-        if hits:
-            bits = np.unpackbits(hit_w.reshape(nq, W).view(np.uint8), axis=1, bitorder="little") if nq * W else np.zeros((nq, 0), np.uint8)
-            out["hits"] = bits[:, :n_pkts].astype(bool)
-        return out
+        return self._scan_family("kmpgpu_scan_chains", len(self.chains), "chain_pkt_counts", hits)
 
     def scan_alerts(self, family: str = "rules", max_records: Optional[int] = None, read: bool = True) -> dict:
         """Which payloads hit which rows of a family, as a list built on the device (kmpgpu_scan_alerts): family "patterns", "rules",

@@ -79,6 +79,22 @@ def test_errors_carry_the_line_number(tmp_path, text, line, what):
     assert what in msg, msg
 
 
+@pytest.mark.parametrize("text, message", [
+    (b"0 -1 5\n", "line 1: '-1' is not a first offset"),          # no sign anywhere in a windows line
+    (b"0 * 5\n", "line 1: '*' is not a first offset"),            # '*' in the first two fields
+    (b"* 0 5\n", "line 1: '*' is not a pattern index"),
+    (b"12345678901234 0 0\n", "line 1: '12345678901234' is not a pattern index"),      # 14 digits, in every field
+    (b"0 12345678901234 *\n", "line 1: '12345678901234' is not a first offset"),
+    (b"0 0 12345678901234\n", "line 1: '12345678901234' is not a last offset or '*'"),
+])
+def test_field_messages_whole(tmp_path, text, message):
+    """The number-field parser is shared with the relations and chains files, whose fields take a sign and a '*' where these do not:
+    the whole message, as the parser that was the windows file's own printed it."""
+    rc, wins, msg = _parse(tmp_path, text, 5)
+    assert rc == -4 and wins is None                               # KMPHOST_EINVAL
+    assert msg == message
+
+
 def test_missing_file(tmp_path):
     L = _lib.host_lib()
     a = np.zeros(3, dtype=np.uint32)
