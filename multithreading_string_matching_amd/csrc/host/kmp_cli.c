@@ -60,15 +60,14 @@
  * reference's behaviour), in the counts, the offsets file and the packets file alike; KMPGPU_STATS=1 prints which rule was used.
  * Unset or 0: the reference's rule, output as ever.
  */
-#include <errno.h>
 #include <pthread.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
 
 #include "kmpgpu.h"
 #include "kmphost.h"
+#include "kmp_cli_common.h"
 
 #ifndef KMP_CLI_OPENMP_FORM
 #define KMP_CLI_OPENMP_FORM 0
@@ -82,40 +81,165 @@
 #define ARGS "<file.pcap> <string.txt> [tcp/udp]"
 #endif
 
-static double now_s(void)
+/* What the command line and the environment ask for: filled once by load_options, read-only from then on. */
+typedef struct cli_options {
+    const char *pcap_path;
+    int proto, shards;
+    kmp_patterns pats;
+    const uint8_t **pp;                     /* pp[i]: the bytes of pattern i */
+    int whole_payload, nocase, device_extract, want_stats;
+    const char *offsets_path, *packets_path, *rules_path, *alerts_path, *export_path;
+    /* what every shard's context gets behind its patterns, in this order and before any rule is set */
+    uint32_t *win_first, *win_last;         /* KMPGPU_WINDOWS_FILE (NULL: none) */
+    kmp_relations relations;                /* KMPGPU_RELATIONS_FILE (n == 0: none) */
+    kmp_chains chains;                      /* KMPGPU_CHAINS_FILE (n == 0: none) */
+    kmp_rules rules;                        /* KMPGPU_RULES_FILE, set before the first output that needs them */
+} cli_options;
+
+/* The capture in host memory -- as payloads, or with KMPGPU_DEVICE_EXTRACT=1 as raw frames -- and when it got there. */
+typedef struct capture {
+    kmp_arena arena;
+    kmp_frames frames;
+    double t_load0, t_loaded, t_warm;
+} capture;
+
+/* One GPU shard: a contiguous range of the payloads (or, with KMPGPU_DEVICE_EXTRACT=1, of the frames). */
+typedef struct shard_job {
+    const cli_options *opt;
+    const capture *cap;
+    int device, threaded, rc;
+    uint64_t lo, cnt;                       /* first unit and number of units of this shard */
+    kmpgpu_ctx *ctx;
+    kmpgpu_timing t;
+    uint64_t n_payloads, payload_bytes;     /* what the context holds (kmpgpu_arena_info) */
+    uint64_t payload_lo;                    /* index of the shard's first payload among all payloads */
+    uint64_t *reb;
+    const char *what;
+    char err[512];
+    pthread_t thread;
+} shard_job;
+
+/* The shards of a run and what they found. */
+typedef struct cli_run {
+    int ndev, shards, reduce_rccl, rules_set;
+    shard_job *job;
+    kmpgpu_ctx **ctxs;                      /* ctxs[r] = job[r].ctx */
+    kmpgpu_comm *comm;
+    uint64_t *own, *counts;                 /* own[r * n_patterns + i]: shard r's count of pattern i; counts[i]: the total */
+    double kernel_ms;
+    uint64_t eff_bytes;
+} cli_run;
+
+static void usage(const char *head)
 {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
+    printf("%s " PROG " " ARGS "\n", head);                                 /* "USAGE": serial.c:43, openmp_data.c:46; "USAGE:": serial.c:49, openmp_data.c:52 */
+    exit(1);
 }
 
-static int parse_proto(const char *s, int *proto)
+static void needs_rules_and_alerts(const char *var, const cli_options *opt)
 {
-    if (strcmp(s, "udp") == 0) { *proto = KMP_PROTO_UDP; return 1; }       /* serial.c:38-41 */
-    if (strcmp(s, "tcp") == 0) { *proto = KMP_PROTO_TCP; return 1; }
-    return 0;
+    if (opt->rules_path && opt->alerts_path) return;
+    fprintf(stderr, "%s goes together with KMPGPU_RULES_FILE and KMPGPU_ALERTS_FILE: %s is not set\n", var, opt->rules_path ? "KMPGPU_ALERTS_FILE" : "KMPGPU_RULES_FILE");
+    exit(1);
 }
 
-static void die_gpu(const char *what)
+/* The command line, the pattern file and every environment variable, each read once; the files that say what to look for are parsed and
+ * the export path is probed.  Whatever is wrong ends the run here with exit code 1, before anything touches the GPU. */
+static void load_options(int argc, char *argv[], cli_options *opt)
 {
-    fprintf(stderr, "%s: %s\n", what, kmpgpu_last_error());
-    exit(2);
-}
+    memset(opt, 0, sizeof *opt);
+    opt->proto = KMP_PROTO_UDP;                                             /* serial.c:31 */
+    opt->shards = 1;
+    if (argc != 3 + KMP_CLI_OPENMP_FORM && argc != 4 + KMP_CLI_OPENMP_FORM) usage("USAGE:");       /* serial.c:33, openmp_data.c:35 */
+#if KMP_CLI_OPENMP_FORM
+    opt->shards = atoi(argv[3]);                                            /* openmp_data.c:38 */
+    if (opt->shards < 1) opt->shards = 1;
+#endif
+    if (argc == 4 + KMP_CLI_OPENMP_FORM && !parse_proto(argv[argc - 1], &opt->proto)) usage("USAGE");
+    opt->pcap_path = argv[1];
 
-/* One "payload,index" line per record of a context's alert list (kmpgpu_scan_alerts: built and sorted by payload, then index, on the
- * device), the payload counted from the shard's first one.  The records come back in pieces of a fixed size; no bit matrix leaves the
- * device. */
-#define ALERT_PIECE 65536u
-static void write_alerts(FILE *fp, kmpgpu_ctx *ctx, int family, uint64_t shard_lo)
-{
-    static kmpgpu_alert piece[ALERT_PIECE];
-    uint64_t found = 0;
-    if (kmpgpu_scan_alerts(ctx, family, UINT64_MAX, &found, NULL, NULL, NULL, NULL)) die_gpu("kmpgpu_scan_alerts");
-    for (uint64_t first = 0; first < found; first += ALERT_PIECE) {
-        const uint64_t n = found - first < ALERT_PIECE ? found - first : ALERT_PIECE;
-        if (kmpgpu_alerts_read(ctx, piece, first, n)) die_gpu("kmpgpu_alerts_read");
-        for (uint64_t i = 0; i < n; i++) fprintf(fp, "%llu,%u\n", (unsigned long long)(shard_lo + piece[i].packet), piece[i].index);
+    const int rc = kmp_patterns_load(argv[2], &opt->pats);                  /* serial.c:54-87 */
+    if (rc == KMPHOST_EIO) {
+        perror("error opening file: ");                                     /* serial.c:61 */
+        exit(1);
     }
+    if (rc) {
+        fprintf(stderr, "error reading pattern file: %s\n", rc == KMPHOST_ETOKEN ? "token longer than 99 bytes" : "out of memory");
+        exit(1);
+    }
+    const uint32_t n = opt->pats.n;
+    opt->pp = (const uint8_t **)malloc(sizeof(uint8_t *) * (n ? n : 1));
+    for (uint32_t i = 0; i < n; i++) opt->pp[i] = opt->pats.blob + opt->pats.off[i];
+
+    opt->whole_payload = env_flag("KMPGPU_WHOLE_PAYLOAD");
+    opt->nocase = env_flag("KMPGPU_NOCASE");
+    opt->device_extract = env_device_extract();
+    /* KMPGPU_STATS=1: also report the bytes up to the first NUL of every payload (what strlen bounds, serial.c:191);
+     * one extra pass over the arena, so it is opt-in and the "Elapsed time" line of a plain run stays comparable */
+    opt->want_stats = env_stats();
+    opt->offsets_path = env_path("KMPGPU_OFFSETS_FILE");
+    opt->packets_path = env_path("KMPGPU_PACKETS_FILE");
+    opt->rules_path = env_path("KMPGPU_RULES_FILE");
+    opt->alerts_path = env_path("KMPGPU_ALERTS_FILE");
+    opt->export_path = env_path("KMPGPU_EXPORT_FILE");
+    const char *relations_path = env_path("KMPGPU_RELATIONS_FILE"), *chains_path = env_path("KMPGPU_CHAINS_FILE"), *windows_path = env_path("KMPGPU_WINDOWS_FILE");
+
+    /* the content rules (an export takes the rules' any[] without an alerts file) */
+    if ((opt->rules_path != NULL) != (opt->alerts_path != NULL) && !(opt->rules_path && opt->export_path)) {
+        fprintf(stderr, "KMPGPU_RULES_FILE and KMPGPU_ALERTS_FILE go together: %s is not set\n", opt->rules_path ? "KMPGPU_ALERTS_FILE" : "KMPGPU_RULES_FILE");
+        exit(1);
+    }
+    /* the relations and the chains, which the rules may name */
+    char err[256];
+    _Static_assert(sizeof err >= KMP_RELATIONS_ERRBUF && sizeof err >= KMP_CHAINS_ERRBUF && sizeof err >= KMP_RULES_ERRBUF && sizeof err >= KMP_WINDOWS_ERRBUF,
+                   "room for every parser's message");
+    if (relations_path) {
+        needs_rules_and_alerts("KMPGPU_RELATIONS_FILE", opt);
+        if (kmp_relations_parse(relations_path, n, &opt->relations, err)) {
+            fprintf(stderr, "error reading relations file %s: %s\n", relations_path, err);
+            exit(1);
+        }
+    }
+    if (chains_path) {
+        needs_rules_and_alerts("KMPGPU_CHAINS_FILE", opt);
+        if (kmp_chains_parse(chains_path, n, &opt->chains, err)) {
+            fprintf(stderr, "error reading chains file %s: %s\n", chains_path, err);
+            exit(1);
+        }
+    }
+    if (opt->rules_path && kmp_rules_parse_terms(opt->rules_path, n, opt->relations.n, opt->chains.n, &opt->rules, err)) {
+        fprintf(stderr, "error reading rules file %s: %s\n", opt->rules_path, err);
+        exit(1);
+    }
+    /* the offset windows likewise */
+    if (windows_path) {
+        if (!opt->offsets_path && !opt->packets_path && !opt->alerts_path && !opt->export_path) {
+            fprintf(stderr, "KMPGPU_WINDOWS_FILE has no effect without KMPGPU_OFFSETS_FILE, KMPGPU_PACKETS_FILE, KMPGPU_EXPORT_FILE or KMPGPU_RULES_FILE + KMPGPU_ALERTS_FILE\n");
+            exit(1);
+        }
+        opt->win_first = (uint32_t *)malloc(sizeof(uint32_t) * (n ? n : 1));
+        opt->win_last = (uint32_t *)malloc(sizeof(uint32_t) * (n ? n : 1));
+        if (!opt->win_first || !opt->win_last) { fprintf(stderr, "error reading windows file %s: out of memory\n", windows_path); exit(1); }
+        if (kmp_windows_parse(windows_path, n, opt->win_first, opt->win_last, err)) {
+            fprintf(stderr, "error reading windows file %s: %s\n", windows_path, err);
+            exit(1);
+        }
+    }
+    /* the export starts as a capture without frames: a path that cannot be written ends the run here */
+    if (opt->export_path && kmp_write_udp_pcap_part(opt->export_path, 0, NULL, NULL, NULL, 0, 0)) {
+        perror("KMPGPU_EXPORT_FILE");
+        exit(1);
+    }
+}
+
+static void free_options(cli_options *opt)
+{
+    free(opt->pp);
+    kmp_patterns_free(&opt->pats);
+    kmp_rules_free(&opt->rules);
+    kmp_relations_free(&opt->relations);
+    kmp_chains_free(&opt->chains);
+    free(opt->win_first); free(opt->win_last);
 }
 
 /* The HIP runtime takes 0.2-0.3 s to come up.  It does so on a side thread while the main thread maps, indexes
@@ -130,51 +254,32 @@ static void *warm_gpu(void *arg)
     return NULL;
 }
 
-/* One GPU shard: a contiguous range of the payloads (or, with KMPGPU_DEVICE_EXTRACT=1, of the frames). */
-typedef struct shard_job {
-    int device, tcp, threaded, rc;
-    uint64_t lo, cnt;                       /* first unit and number of units of this shard */
-    const kmp_arena *arena;
-    const kmp_frames *frames;               /* non-NULL: extraction on the device */
-    const uint8_t *const *pp;
-    const kmp_patterns *pats;
-    kmpgpu_ctx *ctx;
-    kmpgpu_timing t;
-    uint64_t n_payloads, payload_bytes;
-    uint64_t *reb, *own;
-    const char *what;
-    char err[512];
-    pthread_t thread;
-} shard_job;
-
-/* KMPGPU_WINDOWS_FILE: the windows every shard's context gets behind its patterns (NULL: none) */
-static uint32_t *g_win_first, *g_win_last;
-/* KMPGPU_RELATIONS_FILE: the relations every shard's context gets behind its patterns, before any rule is set (n == 0: none) */
-static kmp_relations g_relations;
-/* KMPGPU_CHAINS_FILE: the chains every shard's context gets behind its relations, before any rule is set (n == 0: none) */
-static kmp_chains g_chains;
-
-static int whole_payload_env(void)
+static void load_capture(const cli_options *opt, capture *cap)
 {
-    const char *e = getenv("KMPGPU_WHOLE_PAYLOAD");
-    return e && e[0] == '1' && e[1] == 0;
-}
-
-/* KMPGPU_NOCASE=1: every pattern is matched case-insensitively (ASCII letters, KMPGPU_PAT_NOCASE); the report prints the
- * tokens as written. */
-static int set_patterns_env(kmpgpu_ctx *c, const uint8_t *const *pp, const uint32_t *len, uint32_t n)
-{
-    /* KMPGPU_WHOLE_PAYLOAD=1: payloads are matched to their ends, not to their first 0x00 (KMPGPU_OPT_WHOLE_PAYLOAD); every context
-     * of the run passes through here */
-    if (whole_payload_env() && kmpgpu_set_option(c, KMPGPU_OPT_WHOLE_PAYLOAD, 1)) return KMPGPU_EINVAL;
-    const char *e = getenv("KMPGPU_NOCASE");
-    if (!(e && e[0] == '1' && e[1] == 0) || n == 0) return kmpgpu_set_patterns(c, pp, len, n);
-    uint32_t *fl = (uint32_t *)malloc(n * sizeof *fl);
-    if (!fl) return KMPGPU_ENOMEM;
-    for (uint32_t i = 0; i < n; i++) fl[i] = KMPGPU_PAT_NOCASE;
-    const int rc = kmpgpu_set_patterns_flags(c, pp, len, fl, n);
-    free(fl);
-    return rc;
+    memset(cap, 0, sizeof *cap);
+    pthread_t warm;
+    const int warming = pthread_create(&warm, NULL, warm_gpu, NULL) == 0;
+    cap->t_load0 = now_s();
+    char errbuf[KMP_PCAP_ERRBUF];
+    int rc;
+    /* One-shot buffers stay in ordinary memory: pinning 1.5 GB costs 0.22 s and unpinning 0.15 s, while the
+     * host-to-device copy runs at PCIe speed from pageable memory and even straight from the mapped file on the
+     * MI355X hosts (profiles/r01_h2d_probe.txt).  Pinned buffers pay off where they are reused (bin/openmp_task). */
+    if (opt->device_extract)
+        rc = kmp_frames_from_pcap(opt->pcap_path, NULL, NULL, &cap->frames, errbuf);
+    else
+        rc = kmp_arena_from_pcap(opt->pcap_path, opt->proto, NULL, NULL, &cap->arena, errbuf);                /* serial.c:91-141 */
+    cap->t_loaded = now_s();
+    if (warming) pthread_join(warm, NULL);                                  /* the runtime is up (or there is none: reported by main) */
+    cap->t_warm = now_s();
+    if (rc == KMPHOST_EIO || rc == KMPHOST_EFORMAT) {
+        fprintf(stderr, "error reading pcap file: %s\n", errbuf);           /* serial.c:93 */
+        exit(1);
+    }
+    if (rc) {
+        fprintf(stderr, "error building the payload arena: %s\n", errbuf[0] ? errbuf : kmpgpu_last_error());
+        exit(2);
+    }
 }
 
 static void *shard_fail(shard_job *j, const char *what)
@@ -187,21 +292,21 @@ static void *shard_fail(shard_job *j, const char *what)
 static void *shard_load(void *arg)
 {
     shard_job *j = (shard_job *)arg;
+    const cli_options *o = j->opt;
     if (kmpgpu_init(&j->ctx, j->device)) return shard_fail(j, "kmpgpu_init");
-    if (set_patterns_env(j->ctx, j->pp, j->pats->len, j->pats->n)) return shard_fail(j, "kmpgpu_set_patterns");
-    if (g_win_first && kmpgpu_set_windows(j->ctx, g_win_first, g_win_last, j->pats->n)) return shard_fail(j, "kmpgpu_set_windows");
+    if (set_patterns_env(j->ctx, o->pp, o->pats.len, o->pats.n, o->whole_payload, o->nocase)) return shard_fail(j, "kmpgpu_set_patterns");
+    if (o->win_first && kmpgpu_set_windows(j->ctx, o->win_first, o->win_last, o->pats.n)) return shard_fail(j, "kmpgpu_set_windows");
     _Static_assert(sizeof(kmp_relation) == sizeof(kmpgpu_relation), "kmp_relation has the layout of kmpgpu_relation");
-    if (g_relations.n && kmpgpu_set_relations(j->ctx, (const kmpgpu_relation *)g_relations.rel, g_relations.n)) return shard_fail(j, "kmpgpu_set_relations");
+    if (o->relations.n && kmpgpu_set_relations(j->ctx, (const kmpgpu_relation *)o->relations.rel, o->relations.n)) return shard_fail(j, "kmpgpu_set_relations");
     _Static_assert(sizeof(kmp_chain_link) == sizeof(kmpgpu_chain_link), "kmp_chain_link has the layout of kmpgpu_chain_link");
-    if (g_chains.n && kmpgpu_set_chains(j->ctx, g_chains.off, (const kmpgpu_chain_link *)g_chains.links, g_chains.n)) return shard_fail(j, "kmpgpu_set_chains");
-    if (j->frames) {
+    if (o->chains.n && kmpgpu_set_chains(j->ctx, o->chains.off, (const kmpgpu_chain_link *)o->chains.links, o->chains.n)) return shard_fail(j, "kmpgpu_set_chains");
+    if (o->device_extract) {
         /* only the bytes this shard's frames span are uploaded (kmpgpu_load_frames) */
-        if (kmpgpu_load_frames(j->ctx, j->frames->bytes, j->frames->nbytes, j->frames->off + j->lo, j->frames->caplen + j->lo, j->cnt, j->tcp,
-                               &j->n_payloads))
+        const kmp_frames *f = &j->cap->frames;
+        if (kmpgpu_load_frames(j->ctx, f->bytes, f->nbytes, f->off + j->lo, f->caplen + j->lo, j->cnt, o->proto == KMP_PROTO_TCP, &j->n_payloads))
             return shard_fail(j, "kmpgpu_load_frames");
-        kmpgpu_arena_info(j->ctx, NULL, &j->payload_bytes);
     } else {
-        const kmp_arena *a = j->arena;
+        const kmp_arena *a = &j->cap->arena;
         const uint64_t hi = j->lo + j->cnt;
         const uint64_t b0 = a->off[j->lo];
         const uint64_t b1 = (hi < a->n_pkts) ? a->off[hi] : a->nbytes;
@@ -211,359 +316,202 @@ static void *shard_load(void *arg)
         /* slots are contiguous and at least 16 bytes each, so [b0, b1) holds the whole shard */
         if (kmpgpu_load_arena(j->ctx, a->bytes + b0, b1 - b0, j->reb, a->len + j->lo, j->cnt)) return shard_fail(j, "kmpgpu_load_arena");
     }
+    kmpgpu_arena_info(j->ctx, &j->n_payloads, &j->payload_bytes);
     if (kmpgpu_last_timing(j->ctx, &j->t)) return shard_fail(j, "kmpgpu_last_timing");
     return NULL;
 }
 
+/* Shards: contiguous ranges of the units, N/P each, the remainder to shard 0 (mpi_dumping.c:149-157); shard r on device
+ * r % ndev.  Every shard is brought up by its own host thread -- context, patterns, upload (and extraction) --
+ * so that the uploads of the shards run side by side, one PCIe link each (MPI_Scatterv, mpi_dumping.c:161). */
+static void start_shards(const cli_options *opt, const capture *cap, uint64_t units, cli_run *run)
+{
+    const int shards = run->shards;
+    shard_job *job = run->job = (shard_job *)calloc((size_t)shards, sizeof *job);
+    run->ctxs = (kmpgpu_ctx **)calloc((size_t)shards, sizeof *run->ctxs);
+    uint64_t lo = 0;
+    for (int r = 0; r < shards; r++) {
+        job[r].opt = opt; job[r].cap = cap; job[r].device = r % run->ndev;
+        job[r].lo = lo; job[r].cnt = units / (uint64_t)shards + (r == 0 ? units % (uint64_t)shards : 0);
+        lo += job[r].cnt;
+    }
+    for (int r = 1; r < shards; r++) {
+        job[r].threaded = pthread_create(&job[r].thread, NULL, shard_load, &job[r]) == 0;
+        if (!job[r].threaded) shard_load(&job[r]);
+    }
+    shard_load(&job[0]);
+    for (int r = 1; r < shards; r++) if (job[r].threaded) pthread_join(job[r].thread, NULL);
+    uint64_t payload_lo = 0;
+    for (int r = 0; r < shards; r++) {
+        if (job[r].rc) { fprintf(stderr, "%s: %s\n", job[r].what, job[r].err); exit(2); }
+        run->ctxs[r] = job[r].ctx;
+        job[r].payload_lo = payload_lo;
+        payload_lo += job[r].n_payloads;
+    }
+}
+
+/* KMPGPU_OFFSETS_FILE: every match of every shard as a "payload,offset,pattern" line */
+static void write_offsets(const char *path, const cli_run *run, uint32_t n_patterns)
+{
+    FILE *fp = fopen(path, "w");
+    if (!fp) { perror("KMPGPU_OFFSETS_FILE"); exit(1); }
+    for (int r = 0; r < run->shards; r++) {
+        uint64_t total = 0, found = 0;
+        for (uint32_t i = 0; i < n_patterns; i++) total += run->own[(size_t)r * n_patterns + i];
+        kmpgpu_match *mm = (kmpgpu_match *)malloc(sizeof *mm * (size_t)(total ? total : 1));
+        if (!mm || kmpgpu_scan_offsets(run->ctxs[r], mm, total, &found, NULL)) die_gpu("kmpgpu_scan_offsets");
+        for (uint64_t i = 0; i < found && i < total; i++)
+            fprintf(fp, "%llu,%u,%u\n", (unsigned long long)(mm[i].packet + run->job[r].payload_lo), mm[i].offset, mm[i].pattern);
+        free(mm);
+    }
+    fclose(fp);
+}
+
+/* The rules on every shard's context, once: before the first output that needs them (the alerts file, behind its fopen, or the export). */
+static void set_rules_once(const cli_options *opt, cli_run *run)
+{
+    if (run->rules_set || !opt->rules.n) return;
+    for (int r = 0; r < run->shards; r++)
+        if (kmpgpu_set_rules(run->ctxs[r], opt->rules.off, opt->rules.terms, opt->rules.n)) die_gpu("kmpgpu_set_rules");
+    run->rules_set = 1;
+}
+
+/* KMPGPU_PACKETS_FILE (family KMPGPU_ALERT_PATTERNS), KMPGPU_ALERTS_FILE (KMPGPU_ALERT_RULES; a rules file without rules leaves the file
+ * empty): one "payload,index" line per record of every context's alert list of the family (kmpgpu_scan_alerts: built and sorted by
+ * payload, then index, on the device).  The records come back in pieces of a fixed size; no bit matrix leaves the device. */
+#define ALERT_PIECE 65536u
+static void write_alerts(const char *path, const cli_options *opt, cli_run *run, int family)
+{
+    static kmpgpu_alert piece[ALERT_PIECE];
+    const int by_rules = family == KMPGPU_ALERT_RULES;
+    FILE *fp = fopen(path, "w");
+    if (!fp) { perror(by_rules ? "KMPGPU_ALERTS_FILE" : "KMPGPU_PACKETS_FILE"); exit(1); }
+    if (by_rules) set_rules_once(opt, run);
+    for (int r = 0; r < (by_rules && !opt->rules.n ? 0 : run->shards); r++) {
+        uint64_t found = 0;
+        if (kmpgpu_scan_alerts(run->ctxs[r], family, UINT64_MAX, &found, NULL, NULL, NULL, NULL)) die_gpu("kmpgpu_scan_alerts");
+        for (uint64_t first = 0; first < found; first += ALERT_PIECE) {
+            const uint64_t n = found - first < ALERT_PIECE ? found - first : ALERT_PIECE;
+            if (kmpgpu_alerts_read(run->ctxs[r], piece, first, n)) die_gpu("kmpgpu_alerts_read");
+            for (uint64_t i = 0; i < n; i++) fprintf(fp, "%llu,%u\n", (unsigned long long)(run->job[r].payload_lo + piece[i].packet), piece[i].index);
+        }
+    }
+    fclose(fp);
+}
+
+/* KMPGPU_EXPORT_FILE: the payloads that a rule matches (by_rules) or that hold a pattern, appended shard by shard to the capture that
+ * load_options started.  A shard's selection is compacted next to it on its device; only these bytes come back. */
+static void write_export(const char *path, const cli_run *run, int by_rules, int have_rules)
+{
+    uint64_t written = 0;                                                   /* frames in the file so far */
+    for (int r = 0; r < run->shards; r++) {
+        uint64_t nsel = 0, nb = 0;
+        const uint64_t W = (run->job[r].n_payloads + 63) / 64;
+        uint64_t *any = (uint64_t *)calloc((size_t)(W ? W : 1), sizeof(uint64_t));
+        if (!any) die_gpu("KMPGPU_EXPORT_FILE: out of memory");
+        if (by_rules) {                                                     /* (a rules file without rules selects nothing) */
+            if (have_rules && kmpgpu_scan_rules(run->ctxs[r], NULL, any, NULL, NULL, NULL)) die_gpu("kmpgpu_scan_rules");
+        } else if (kmpgpu_scan_packets(run->ctxs[r], NULL, any, NULL, NULL, NULL)) die_gpu("kmpgpu_scan_packets");
+        kmpgpu_ctx *ex = NULL;
+        if (kmpgpu_init(&ex, run->job[r].device)) die_gpu("kmpgpu_init");
+        if (kmpgpu_load_selected(ex, run->ctxs[r], any, 0, &nsel)) die_gpu("kmpgpu_load_selected");
+        free(any);
+        if (nsel) {
+            if (kmpgpu_arena_download(ex, NULL, 0, &nb, NULL, NULL)) die_gpu("kmpgpu_arena_download");
+            uint8_t *bytes = (uint8_t *)malloc((size_t)(nb ? nb : 1));
+            uint64_t *off = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)nsel);
+            uint32_t *len = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)nsel);
+            if (!bytes || !off || !len || kmpgpu_arena_download(ex, bytes, nb, &nb, off, len)) die_gpu("kmpgpu_arena_download");
+            if (kmp_write_udp_pcap_part(path, 1, bytes, off, len, nsel, written)) { perror("KMPGPU_EXPORT_FILE"); exit(1); }
+            written += nsel;
+            free(bytes); free(off); free(len);
+        }
+        kmpgpu_destroy(ex);
+    }
+}
+
+/* stderr: what ran where and how fast; with KMPGPU_STATS=1 the text rule, the bytes it bounds and the phases */
+static void print_stats(const cli_options *opt, const capture *cap, const cli_run *run, double t_finish)
+{
+    uint64_t total = 0, h2d_bytes = 0, n_pkts = cap->arena.n_pkts, payload_bytes = cap->arena.payload_bytes;
+    double h2d_ms = 0;
+    for (uint32_t i = 0; i < opt->pats.n; i++) total += run->counts[i];
+    for (int r = 0; r < run->shards; r++) {
+        h2d_ms += run->job[r].t.h2d_ms; h2d_bytes += run->job[r].t.h2d_bytes;
+        if (opt->device_extract) { n_pkts += run->job[r].n_payloads; payload_bytes += run->job[r].payload_bytes; }      /* (the host arena is empty then) */
+    }
+    const double bytes = (double)payload_bytes * (double)opt->pats.n;
+    fprintf(stderr, "[kmpgpu] %llu frames, %llu payloads, %llu payload bytes, %u patterns, %d shard(s) on %d device(s), count reduce: %s, %llu bytes uploaded\n",
+            (unsigned long long)(opt->device_extract ? cap->frames.n : cap->arena.n_frames), (unsigned long long)n_pkts, (unsigned long long)payload_bytes,
+            opt->pats.n, run->shards, run->ndev, run->reduce_rccl ? "RCCL all-reduce" : (run->shards > 1 ? "host sum" : "none"), (unsigned long long)h2d_bytes);
+    fprintf(stderr, "[kmpgpu] kernel %.3f ms (%.2f GB/s payload x patterns, %.3g matches/s), h2d %.3f ms\n", run->kernel_ms,
+            bytes / (run->kernel_ms * 1e6), (double)total / (run->kernel_ms * 1e-3), h2d_ms);
+    if (!opt->want_stats) return;
+    print_text_rule(opt->whole_payload);
+    fprintf(stderr, "[kmpgpu] %llu of the %llu payload bytes lie at or before the first NUL of their payload\n",
+            (unsigned long long)run->eff_bytes, (unsigned long long)payload_bytes);
+    fprintf(stderr, "[kmpgpu] phases: capture -> host buffers %.3f s, waiting for the HIP runtime %.3f s, contexts + upload + scan %.3f s\n",
+            cap->t_loaded - cap->t_load0, cap->t_warm - cap->t_loaded, t_finish - cap->t_warm);
+}
+
 int main(int argc, char *argv[])
 {
-    int proto = KMP_PROTO_UDP;                                              /* serial.c:31 */
-    int shards = 1;
-#if KMP_CLI_OPENMP_FORM
-    if (argc == 4 || argc == 5) {                                           /* openmp_data.c:35 */
-        shards = atoi(argv[3]);                                             /* openmp_data.c:38 */
-        if (argc == 5 && !parse_proto(argv[4], &proto)) {
-            printf("USAGE " PROG " " ARGS "\n");                            /* openmp_data.c:46 */
-            exit(1);
-        }
-    } else {
-        printf("USAGE: " PROG " " ARGS "\n");                               /* openmp_data.c:52 */
-        exit(1);
-    }
-    if (shards < 1) shards = 1;
-#else
-    if (argc == 3 || argc == 4) {                                           /* serial.c:33 */
-        if (argc == 4 && !parse_proto(argv[3], &proto)) {
-            printf("USAGE " PROG " " ARGS "\n");                            /* serial.c:43 */
-            exit(1);
-        }
-    } else {
-        printf("USAGE: " PROG " " ARGS "\n");                               /* serial.c:49 */
-        exit(1);
-    }
-#endif
-    const char *pcap_path = argv[1], *strings_path = argv[2];
-
-    kmp_patterns pats;
-    int rc = kmp_patterns_load(strings_path, &pats);                        /* serial.c:54-87 */
-    if (rc == KMPHOST_EIO) {
-        perror("error opening file: ");                                     /* serial.c:61 */
-        exit(1);
-    }
-    if (rc) {
-        fprintf(stderr, "error reading pattern file: %s\n", rc == KMPHOST_ETOKEN ? "token longer than 99 bytes" : "out of memory");
-        exit(1);
-    }
-
-    /* the content rules, read before anything touches the GPU */
-    const char *rules_path = getenv("KMPGPU_RULES_FILE"), *alerts_path = getenv("KMPGPU_ALERTS_FILE");
-    if (rules_path && !rules_path[0]) rules_path = NULL;
-    if (alerts_path && !alerts_path[0]) alerts_path = NULL;
-    kmp_rules rules;
-    memset(&rules, 0, sizeof rules);
-    const char *export_path = getenv("KMPGPU_EXPORT_FILE");
-    if (export_path && !export_path[0]) export_path = NULL;
-    if ((rules_path != NULL) != (alerts_path != NULL) && !(rules_path && export_path)) {      /* (an export takes the rules' any[] without an alerts file) */
-        fprintf(stderr, "KMPGPU_RULES_FILE and KMPGPU_ALERTS_FILE go together: %s is not set\n", rules_path ? "KMPGPU_ALERTS_FILE" : "KMPGPU_RULES_FILE");
-        exit(1);
-    }
-    /* the relations, which the rules may name */
-    const char *relations_path = getenv("KMPGPU_RELATIONS_FILE");
-    if (relations_path && relations_path[0]) {
-        if (!rules_path || !alerts_path) {
-            fprintf(stderr, "KMPGPU_RELATIONS_FILE goes together with KMPGPU_RULES_FILE and KMPGPU_ALERTS_FILE: %s is not set\n", rules_path ? "KMPGPU_ALERTS_FILE" : "KMPGPU_RULES_FILE");
-            exit(1);
-        }
-        char relations_err[KMP_RELATIONS_ERRBUF];
-        if (kmp_relations_parse(relations_path, pats.n, &g_relations, relations_err)) {
-            fprintf(stderr, "error reading relations file %s: %s\n", relations_path, relations_err);
-            exit(1);
-        }
-    }
-    /* ... and the chains */
-    const char *chains_path = getenv("KMPGPU_CHAINS_FILE");
-    if (chains_path && chains_path[0]) {
-        if (!rules_path || !alerts_path) {
-            fprintf(stderr, "KMPGPU_CHAINS_FILE goes together with KMPGPU_RULES_FILE and KMPGPU_ALERTS_FILE: %s is not set\n", rules_path ? "KMPGPU_ALERTS_FILE" : "KMPGPU_RULES_FILE");
-            exit(1);
-        }
-        char chains_err[KMP_CHAINS_ERRBUF];
-        if (kmp_chains_parse(chains_path, pats.n, &g_chains, chains_err)) {
-            fprintf(stderr, "error reading chains file %s: %s\n", chains_path, chains_err);
-            exit(1);
-        }
-    }
-    if (rules_path) {
-        char rules_err[KMP_RULES_ERRBUF];
-        if (kmp_rules_parse_terms(rules_path, pats.n, g_relations.n, g_chains.n, &rules, rules_err)) {
-            fprintf(stderr, "error reading rules file %s: %s\n", rules_path, rules_err);
-            exit(1);
-        }
-    }
-
-    /* the offset windows likewise */
-    const char *windows_path = getenv("KMPGPU_WINDOWS_FILE");
-    if (windows_path && windows_path[0]) {
-        const char *of = getenv("KMPGPU_OFFSETS_FILE"), *pf = getenv("KMPGPU_PACKETS_FILE");
-        if (!(of && of[0]) && !(pf && pf[0]) && !alerts_path && !export_path) {
-            fprintf(stderr, "KMPGPU_WINDOWS_FILE has no effect without KMPGPU_OFFSETS_FILE, KMPGPU_PACKETS_FILE, KMPGPU_EXPORT_FILE or KMPGPU_RULES_FILE + KMPGPU_ALERTS_FILE\n");
-            exit(1);
-        }
-        char windows_err[KMP_WINDOWS_ERRBUF];
-        g_win_first = (uint32_t *)malloc(sizeof(uint32_t) * (pats.n ? pats.n : 1));
-        g_win_last = (uint32_t *)malloc(sizeof(uint32_t) * (pats.n ? pats.n : 1));
-        if (!g_win_first || !g_win_last) { fprintf(stderr, "error reading windows file %s: out of memory\n", windows_path); exit(1); }
-        if (kmp_windows_parse(windows_path, pats.n, g_win_first, g_win_last, windows_err)) {
-            fprintf(stderr, "error reading windows file %s: %s\n", windows_path, windows_err);
-            exit(1);
-        }
-    }
-
-    /* the export starts as a capture without frames: a path that cannot be written ends the run here */
-    if (export_path && kmp_write_udp_pcap_part(export_path, 0, NULL, NULL, NULL, 0, 0)) {
-        perror("KMPGPU_EXPORT_FILE");
-        exit(1);
-    }
-
+    cli_options opt;
+    capture cap;
+    cli_run run;
+    memset(&run, 0, sizeof run);
+    load_options(argc, argv, &opt);
 #if !KMP_CLI_OPENMP_FORM
     const double t_start = now_s();                                         /* serial.c:110-111: before the file read */
 #endif
-    pthread_t warm;
-    const int warming = pthread_create(&warm, NULL, warm_gpu, NULL) == 0;
-    const double t_load0 = now_s();
-    char errbuf[KMP_PCAP_ERRBUF];
-    kmp_arena arena;
-    kmp_frames frames;
-    memset(&arena, 0, sizeof arena);
-    memset(&frames, 0, sizeof frames);
-    const char *dx = getenv("KMPGPU_DEVICE_EXTRACT");
-    const int device_extract = dx && dx[0] == '1';
-    /* One-shot buffers stay in ordinary memory: pinning 1.5 GB costs 0.22 s and unpinning 0.15 s, while the
-     * host-to-device copy runs at PCIe speed from pageable memory and even straight from the mapped file on the
-     * MI355X hosts (profiles/r01_h2d_probe.txt).  Pinned buffers pay off where they are reused (bin/openmp_task). */
-    if (device_extract)
-        rc = kmp_frames_from_pcap(pcap_path, NULL, NULL, &frames, errbuf);
-    else
-        rc = kmp_arena_from_pcap(pcap_path, proto, NULL, NULL, &arena, errbuf);                              /* serial.c:91-141 */
-    const double t_loaded = now_s();
-    if (warming) pthread_join(warm, NULL);                                  /* the runtime is up (or there is none: reported below) */
-    const double t_warm = now_s();
-    if (rc == KMPHOST_EIO || rc == KMPHOST_EFORMAT) {
-        fprintf(stderr, "error reading pcap file: %s\n", errbuf);           /* serial.c:93 */
-        exit(1);
-    }
-    if (rc) {
-        fprintf(stderr, "error building the payload arena: %s\n", errbuf[0] ? errbuf : kmpgpu_last_error());
-        exit(2);
-    }
+    load_capture(&opt, &cap);
 #if KMP_CLI_OPENMP_FORM
     const double t_start = now_s();                                         /* openmp_data.c:126: after the pre-load */
 #endif
+    run.ndev = kmpgpu_device_count();
+    if (run.ndev <= 0) die_gpu("no MI355X device");
 
-    const int ndev = kmpgpu_device_count();
-    if (ndev <= 0) die_gpu("no MI355X device");
+    const uint32_t n = opt.pats.n;
+    const uint64_t units = opt.device_extract ? cap.frames.n : cap.arena.n_pkts;      /* what is split over the shards */
+    run.shards = (uint64_t)opt.shards > units ? (int)units : opt.shards;
+    run.counts = (uint64_t *)calloc(n ? n : 1, sizeof(uint64_t));
+    if (n && units) {
+        start_shards(&opt, &cap, units, &run);
+        run.own = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)run.shards * n);
+        if (!run.own) die_gpu("out of memory");
 
-    uint64_t *counts = (uint64_t *)calloc(pats.n ? pats.n : 1, sizeof(uint64_t));
-    uint64_t *part = (uint64_t *)calloc(pats.n ? pats.n : 1, sizeof(uint64_t));
-    const uint8_t **pp = (const uint8_t **)malloc(sizeof(uint8_t *) * (pats.n ? pats.n : 1));
-    for (uint32_t i = 0; i < pats.n; i++) pp[i] = pats.blob + pats.off[i];
-
-    double kernel_ms = 0, h2d_ms = 0;
-    /* KMPGPU_STATS=1: also report the bytes up to the first NUL of every payload (what strlen bounds, serial.c:191);
-     * one extra pass over the arena, so it is opt-in and the "Elapsed time" line of a plain run stays comparable */
-    const char *stats_env = getenv("KMPGPU_STATS");
-    const int want_stats = stats_env && stats_env[0] && stats_env[0] != '0';
-    uint64_t eff_bytes = 0, h2d_bytes = 0;
-    int reduce_rccl = 0;
-    kmpgpu_comm *td_comm = NULL; kmpgpu_ctx **td_ctxs = NULL; shard_job *td_job = NULL; int td_n = 0;      /* torn down after the report */
-    const uint64_t units = device_extract ? frames.n : arena.n_pkts;       /* what is split over the shards */
-    if (pats.n && units) {
-        /* Shards: contiguous ranges, N/P each, the remainder to shard 0 (mpi_dumping.c:149-157); shard r on device
-         * r % ndev.  Every shard is brought up by its own host thread -- context, patterns, upload (and extraction) --
-         * so that the uploads of the shards run side by side, one PCIe link each (MPI_Scatterv, mpi_dumping.c:161). */
-        if ((uint64_t)shards > units) shards = (int)units;
-        shard_job *job = (shard_job *)calloc((size_t)shards, sizeof *job);
-        uint64_t lo = 0;
-        for (int r = 0; r < shards; r++) {
-            const uint64_t cnt = units / (uint64_t)shards + (r == 0 ? units % (uint64_t)shards : 0);
-            job[r].device = r % ndev; job[r].lo = lo; job[r].cnt = cnt;
-            job[r].arena = &arena; job[r].frames = device_extract ? &frames : NULL; job[r].tcp = proto == KMP_PROTO_TCP;
-            job[r].pp = pp; job[r].pats = &pats;
-            lo += cnt;
-        }
-        for (int r = 1; r < shards; r++)
-            if (pthread_create(&job[r].thread, NULL, shard_load, &job[r]) != 0) { job[r].threaded = 0; shard_load(&job[r]); } else job[r].threaded = 1;
-        shard_load(&job[0]);
-        for (int r = 1; r < shards; r++) if (job[r].threaded) pthread_join(job[r].thread, NULL);
-        for (int r = 0; r < shards; r++) {
-            if (job[r].rc) { fprintf(stderr, "%s: %s\n", job[r].what, job[r].err); exit(2); }
-            h2d_ms += job[r].t.h2d_ms; h2d_bytes += job[r].t.h2d_bytes;
-            if (device_extract) { arena.n_pkts += job[r].n_payloads; arena.payload_bytes += job[r].payload_bytes; }
-        }
-        if (device_extract) arena.n_frames = frames.n;
-
-        /* The count reduce (mpi_dumping.c:202).  One shard per device: RCCL all-reduce over xGMI of the shards' device
-         * counters (kmpgpu_comm_*), then ONE download.  Shards that share a device (more shards than GPUs): host sum.
-         * KMPGPU_RCCL=0 forces the host sum, =1 asks for the communicator even with a single shard. */
-        const char *rccl_env = getenv("KMPGPU_RCCL");
-        kmpgpu_comm *comm = NULL;
-        kmpgpu_ctx **ctxs = (kmpgpu_ctx **)calloc((size_t)shards, sizeof *ctxs);
-        for (int r = 0; r < shards; r++) ctxs[r] = job[r].ctx;
-        if (shards <= ndev && (shards > 1 || (rccl_env && rccl_env[0] == '1')) && !(rccl_env && rccl_env[0] == '0')) {
-            /* no communicator is no reason to stop: the shards' own counters are summed on the host instead (below) */
-            if (kmpgpu_comm_init(&comm, ctxs, shards)) {
-                fprintf(stderr, "[kmpgpu] kmpgpu_comm_init: %s -- summing the shards' counts on the host\n", kmpgpu_last_error());
-                comm = NULL;
-            } else reduce_rccl = 1;
-        }
+        run.comm = reduce_comm(run.ctxs, run.shards, run.ndev);
         const double t_scan0 = now_s();
         /* every shard's pass is enqueued before any result is read, so the GPUs work side by side
          * (mpi_dumping.c:198-202: all ranks count, then one reduce) */
-        for (int r = 0; r < shards; r++)
-            if (kmpgpu_scan_enqueue(ctxs[r], NULL)) die_gpu("kmpgpu_scan_enqueue");
-        if (comm) {
-            /* the shards' own counts are kept before they are summed in place: the offset files need them again below, and
-             * they are what the host sums should the all-reduce fail (n_patterns x 8 bytes per shard) */
-            for (int r = 0; r < shards; r++) {
-                job[r].own = (uint64_t *)malloc(sizeof(uint64_t) * (pats.n ? pats.n : 1));
-                if (!job[r].own || kmpgpu_counts_read(ctxs[r], job[r].own)) die_gpu("kmpgpu_counts_read");
-            }
-            int bad = kmpgpu_comm_allreduce_counts(comm) != 0;
-            if (!bad) bad = kmpgpu_counts_read(ctxs[0], counts) != 0;                          /* MPI_Reduce root 0 */
-            for (int r = 1; r < shards && !bad; r++) bad = kmpgpu_sync(ctxs[r]) != 0;
-            if (bad) {
-                fprintf(stderr, "[kmpgpu] RCCL all-reduce of the counts: %s -- summing the shards' counts on the host\n", kmpgpu_last_error());
-                reduce_rccl = 0;
-                for (uint32_t i = 0; i < pats.n; i++) {
-                    counts[i] = 0;
-                    for (int r = 0; r < shards; r++) counts[i] += job[r].own[i];            /* mpi_dumping.c:202 MPI_SUM */
-                }
-            }
-        } else {
-            for (int r = 0; r < shards; r++) {
-                if (kmpgpu_counts_read(ctxs[r], part)) die_gpu("kmpgpu_counts_read");
-                for (uint32_t i = 0; i < pats.n; i++) counts[i] += part[i];     /* mpi_dumping.c:202 MPI_SUM */
-                if (getenv("KMPGPU_OFFSETS_FILE")) {
-                    job[r].own = (uint64_t *)malloc(sizeof(uint64_t) * pats.n);
-                    memcpy(job[r].own, part, sizeof(uint64_t) * pats.n);
-                }
-            }
-        }
-        kernel_ms = (now_s() - t_scan0) * 1e3;                              /* wall time of the concurrent passes + reduce (mpi_dumping.c:206 MPI_MAX) */
+        for (int r = 0; r < run.shards; r++)
+            if (kmpgpu_scan_enqueue(run.ctxs[r], NULL)) die_gpu("kmpgpu_scan_enqueue");
+        run.reduce_rccl = reduce_counts(run.ctxs, run.shards, n, run.own, run.counts, run.comm);
+        run.kernel_ms = (now_s() - t_scan0) * 1e3;                          /* wall time of the concurrent passes + reduce (mpi_dumping.c:206 MPI_MAX) */
 
-        const char *off_path = getenv("KMPGPU_OFFSETS_FILE");
-        if (off_path && off_path[0]) {
-            FILE *off_fp = fopen(off_path, "w");
-            if (!off_fp) { perror("KMPGPU_OFFSETS_FILE"); exit(1); }
-            uint64_t shard_lo = 0;                                          /* payload index of the shard's first payload */
-            for (int r = 0; r < shards; r++) {
-                uint64_t total = 0, found = 0, np = 0;
-                for (uint32_t i = 0; i < pats.n; i++) total += job[r].own[i];
-                kmpgpu_match *mm = (kmpgpu_match *)malloc(sizeof *mm * (size_t)(total ? total : 1));
-                if (!mm || kmpgpu_scan_offsets(ctxs[r], mm, total, &found, NULL)) die_gpu("kmpgpu_scan_offsets");
-                for (uint64_t i = 0; i < found && i < total; i++)
-                    fprintf(off_fp, "%llu,%u,%u\n", (unsigned long long)(mm[i].packet + shard_lo), mm[i].offset, mm[i].pattern);
-                free(mm);
-                kmpgpu_arena_info(ctxs[r], &np, NULL);
-                shard_lo += np;
-            }
-            fclose(off_fp);
+        if (opt.offsets_path) write_offsets(opt.offsets_path, &run, n);
+        if (opt.packets_path) write_alerts(opt.packets_path, &opt, &run, KMPGPU_ALERT_PATTERNS);
+        if (opt.alerts_path) write_alerts(opt.alerts_path, &opt, &run, KMPGPU_ALERT_RULES);
+        if (opt.export_path) {
+            set_rules_once(&opt, &run);
+            write_export(opt.export_path, &run, opt.rules_path != NULL, opt.rules.n != 0);
         }
-        const char *pk_path = getenv("KMPGPU_PACKETS_FILE");
-        if (pk_path && pk_path[0]) {
-            FILE *pk_fp = fopen(pk_path, "w");
-            if (!pk_fp) { perror("KMPGPU_PACKETS_FILE"); exit(1); }
-            uint64_t shard_lo = 0;                                          /* payload index of the shard's first payload */
-            for (int r = 0; r < shards; r++) {
-                uint64_t np = 0;
-                kmpgpu_arena_info(ctxs[r], &np, NULL);
-                write_alerts(pk_fp, ctxs[r], KMPGPU_ALERT_PATTERNS, shard_lo);
-                shard_lo += np;
-            }
-            fclose(pk_fp);
-        }
-        if (alerts_path) {
-            FILE *al_fp = fopen(alerts_path, "w");
-            if (!al_fp) { perror("KMPGPU_ALERTS_FILE"); exit(1); }
-            uint64_t shard_lo = 0;                                          /* payload index of the shard's first payload */
-            for (int r = 0; r < shards && rules.n; r++) {
-                uint64_t np = 0;
-                kmpgpu_arena_info(ctxs[r], &np, NULL);
-                if (kmpgpu_set_rules(ctxs[r], rules.off, rules.terms, rules.n)) die_gpu("kmpgpu_set_rules");
-                write_alerts(al_fp, ctxs[r], KMPGPU_ALERT_RULES, shard_lo);
-                shard_lo += np;
-            }
-            fclose(al_fp);
-        }
-        if (export_path) {
-            uint64_t written = 0;                                           /* frames in the file so far */
-            for (int r = 0; r < shards; r++) {
-                uint64_t np = 0, nsel = 0, nb = 0;
-                kmpgpu_arena_info(ctxs[r], &np, NULL);
-                const uint64_t W = (np + 63) / 64;
-                uint64_t *any = (uint64_t *)calloc((size_t)(W ? W : 1), sizeof(uint64_t));
-                if (!any) die_gpu("KMPGPU_EXPORT_FILE: out of memory");
-                if (rules_path) {
-                    if (rules.n && kmpgpu_set_rules(ctxs[r], rules.off, rules.terms, rules.n)) die_gpu("kmpgpu_set_rules");
-                    if (rules.n && kmpgpu_scan_rules(ctxs[r], NULL, any, NULL, NULL, NULL)) die_gpu("kmpgpu_scan_rules");
-                } else if (kmpgpu_scan_packets(ctxs[r], NULL, any, NULL, NULL, NULL)) die_gpu("kmpgpu_scan_packets");
-                /* the shard's selection, compacted next to it on its device; only these bytes come back */
-                kmpgpu_ctx *ex = NULL;
-                if (kmpgpu_init(&ex, job[r].device)) die_gpu("kmpgpu_init");
-                if (kmpgpu_load_selected(ex, ctxs[r], any, 0, &nsel)) die_gpu("kmpgpu_load_selected");
-                free(any);
-                if (nsel) {
-                    if (kmpgpu_arena_download(ex, NULL, 0, &nb, NULL, NULL)) die_gpu("kmpgpu_arena_download");
-                    uint8_t *bytes = (uint8_t *)malloc((size_t)(nb ? nb : 1));
-                    uint64_t *off = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)nsel);
-                    uint32_t *len = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)nsel);
-                    if (!bytes || !off || !len || kmpgpu_arena_download(ex, bytes, nb, &nb, off, len)) die_gpu("kmpgpu_arena_download");
-                    if (kmp_write_udp_pcap_part(export_path, 1, bytes, off, len, nsel, written)) { perror("KMPGPU_EXPORT_FILE"); exit(1); }
-                    written += nsel;
-                    free(bytes); free(off); free(len);
-                }
-                kmpgpu_destroy(ex);
-            }
-        }
-        for (int r = 0; r < shards && want_stats; r++) {
+        for (int r = 0; r < run.shards && opt.want_stats; r++) {
             uint64_t e = 0;
-            if (kmpgpu_effective_bytes(ctxs[r], &e)) die_gpu("kmpgpu_effective_bytes");
-            eff_bytes += e;
+            if (kmpgpu_effective_bytes(run.ctxs[r], &e)) die_gpu("kmpgpu_effective_bytes");
+            run.eff_bytes += e;
         }
-        /* (teardown after the report: serial.c:159-160 takes the time before it frees anything, :178-180) */
-        td_comm = comm; td_ctxs = ctxs; td_job = job; td_n = shards;
     }
     const double t_finish = now_s();                                        /* serial.c:159-160 */
 
-    kmp_report(stdout, &pats, counts, t_finish - t_start);                  /* serial.c:163-169 */
-    if (td_comm) kmpgpu_comm_destroy(td_comm);
-    for (int r = 0; r < td_n; r++) { kmpgpu_destroy(td_ctxs[r]); free(td_job[r].own); free(td_job[r].reb); }
-    free(td_ctxs); free(td_job);
-
-    if (kernel_ms > 0) {
-        uint64_t total = 0;
-        for (uint32_t i = 0; i < pats.n; i++) total += counts[i];
-        const double bytes = (double)arena.payload_bytes * (double)pats.n;
-        fprintf(stderr, "[kmpgpu] %llu frames, %llu payloads, %llu payload bytes, %u patterns, %d shard(s) on %d device(s), count reduce: %s, %llu bytes uploaded\n",
-                (unsigned long long)arena.n_frames, (unsigned long long)arena.n_pkts, (unsigned long long)arena.payload_bytes,
-                pats.n, shards, ndev, reduce_rccl ? "RCCL all-reduce" : (shards > 1 ? "host sum" : "none"), (unsigned long long)h2d_bytes);
-        fprintf(stderr, "[kmpgpu] kernel %.3f ms (%.2f GB/s payload x patterns, %.3g matches/s), h2d %.3f ms\n", kernel_ms,
-                bytes / (kernel_ms * 1e6), (double)total / (kernel_ms * 1e-3), h2d_ms);
-        if (want_stats) {
-            fprintf(stderr, "[kmpgpu] text rule: %s\n", whole_payload_env() ? "whole payloads (KMPGPU_WHOLE_PAYLOAD=1)" : "up to a payload's first NUL (the reference's strlen)");
-            fprintf(stderr, "[kmpgpu] %llu of the %llu payload bytes lie at or before the first NUL of their payload\n",
-                    (unsigned long long)eff_bytes, (unsigned long long)arena.payload_bytes);
-            fprintf(stderr, "[kmpgpu] phases: capture -> host buffers %.3f s, waiting for the HIP runtime %.3f s, contexts + upload + scan %.3f s\n",
-                    t_loaded - t_load0, t_warm - t_loaded, t_finish - t_warm);
-        }
-    }
-    free(counts); free(part); free(pp);
-    kmp_arena_free(&arena);
-    kmp_frames_free(&frames);
-    kmp_patterns_free(&pats);
-    kmp_rules_free(&rules);
-    kmp_relations_free(&g_relations);
-    kmp_chains_free(&g_chains);
-    free(g_win_first); free(g_win_last);
+    kmp_report(stdout, &opt.pats, run.counts, t_finish - t_start);         /* serial.c:163-169 */
+    /* teardown after the report: serial.c:159-160 takes the time before it frees anything, :178-180 */
+    if (run.comm) kmpgpu_comm_destroy(run.comm);
+    for (int r = 0; r < run.shards && run.job; r++) { kmpgpu_destroy(run.ctxs[r]); free(run.job[r].reb); }
+    if (run.kernel_ms > 0) print_stats(&opt, &cap, &run, t_finish);
+    free(run.ctxs); free(run.job); free(run.own); free(run.counts);
+    kmp_arena_free(&cap.arena);
+    kmp_frames_free(&cap.frames);
+    free_options(&opt);
     return 0;
 }

@@ -29,11 +29,10 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
 
 #include "kmpgpu.h"
 #include "kmphost.h"
-
+#include "kmp_cli_common.h"
 
 typedef struct slot {
     uint8_t  *arena;                 /* pinned: the payload arena of a batch / the raw bytes of a frame batch */
@@ -69,6 +68,7 @@ typedef struct shared {
     int             serial_uploads;  /* raw frames: an upload is enqueued only when the one before it on that device is through (default) */
     pthread_mutex_t up_mu[KMP_MAX_DEVICES];
     kmpgpu_ctx     *up_last[KMP_MAX_DEVICES];
+    int             whole_payload, nocase;    /* KMPGPU_WHOLE_PAYLOAD=1, KMPGPU_NOCASE=1: how every context matches (set_patterns_env) */
 } shared;
 
 typedef struct consumer {
@@ -80,19 +80,6 @@ typedef struct consumer {
     uint64_t  batches, payloads, bytes;
     double    load_s, wait_s;        /* time inside the load calls / waiting for a filled slot */
 } consumer;
-
-static double now_s(void)
-{
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
-}
-
-static void die_gpu(const char *what)
-{
-    fprintf(stderr, "%s: %s\n", what, kmpgpu_last_error());
-    exit(2);
-}
 
 /* KMPGPU_DEVICE_EXTRACT=1, second stage: the raw bytes of a walked batch go from the mapped capture into the slot's pinned buffer
  * (kmp_copy_bytes: several threads), the frame offsets are rebased to that buffer, and the batch is handed to the consumers. */
@@ -123,34 +110,11 @@ static void *stage_batches(void *arg)
     }
 }
 
-static int whole_payload_env(void)
-{
-    const char *e = getenv("KMPGPU_WHOLE_PAYLOAD");
-    return e && e[0] == '1' && e[1] == 0;
-}
-
-/* KMPGPU_NOCASE=1: every pattern is matched case-insensitively (ASCII letters, KMPGPU_PAT_NOCASE); the report prints the
- * tokens as written. */
-static int set_patterns_env(kmpgpu_ctx *c, const uint8_t *const *pp, const uint32_t *len, uint32_t n)
-{
-    /* KMPGPU_WHOLE_PAYLOAD=1: payloads are matched to their ends, not to their first 0x00 (KMPGPU_OPT_WHOLE_PAYLOAD); every context
-     * of the run passes through here */
-    if (whole_payload_env() && kmpgpu_set_option(c, KMPGPU_OPT_WHOLE_PAYLOAD, 1)) return KMPGPU_EINVAL;
-    const char *e = getenv("KMPGPU_NOCASE");
-    if (!(e && e[0] == '1' && e[1] == 0) || n == 0) return kmpgpu_set_patterns(c, pp, len, n);
-    uint32_t *fl = (uint32_t *)malloc(n * sizeof *fl);
-    if (!fl) return KMPGPU_ENOMEM;
-    for (uint32_t i = 0; i < n; i++) fl[i] = KMPGPU_PAT_NOCASE;
-    const int rc = kmpgpu_set_patterns_flags(c, pp, len, fl, n);
-    free(fl);
-    return rc;
-}
-
 static kmpgpu_ctx *make_context(const shared *sh, int device)
 {
     kmpgpu_ctx *c = NULL;
     if (kmpgpu_init(&c, device)) die_gpu("kmpgpu_init");
-    if (set_patterns_env(c, sh->pp, sh->pats->len, sh->pats->n)) die_gpu("kmpgpu_set_patterns");
+    if (set_patterns_env(c, sh->pp, sh->pats->len, sh->pats->n, sh->whole_payload, sh->nocase)) die_gpu("kmpgpu_set_patterns");
     if (kmpgpu_set_option(c, KMPGPU_OPT_ACCUMULATE, 1) || kmpgpu_counts_reset(c)) die_gpu("kmpgpu_set_option");
     /* the device buffers of a batch, once: the first batch does not pay for a dozen allocations under the clock */
     if (kmpgpu_reserve(c, sh->batch_bytes + 64, sh->cap_pkts, sh->frames_mode ? sh->batch_bytes + 64 : 0, sh->frames_mode ? sh->cap_pkts : 0)) die_gpu("kmpgpu_reserve");
@@ -266,13 +230,9 @@ int main(int argc, char *argv[])
     int shards = 1;
     if (argc == 4 || argc == 5) {                                            /* openmp_task.c:35 */
         shards = atoi(argv[3]);                                              /* openmp_task.c:38 */
-        if (argc == 5) {
-            if (strcmp(argv[4], "udp") == 0) proto = KMP_PROTO_UDP;
-            else if (strcmp(argv[4], "tcp") == 0) proto = KMP_PROTO_TCP;
-            else {
-                printf("USAGE ./openmp_task <file.pcap> <string.txt> thread_number [tcp/udp]\n");   /* openmp_task.c:46 */
-                exit(1);
-            }
+        if (argc == 5 && !parse_proto(argv[4], &proto)) {
+            printf("USAGE ./openmp_task <file.pcap> <string.txt> thread_number [tcp/udp]\n");       /* openmp_task.c:46 */
+            exit(1);
         }
     } else {
         printf("USAGE: ./openmp_task <file.pcap> <string.txt> [tcp/udp]\n");                       /* openmp_task.c:52 (sic) */
@@ -296,15 +256,14 @@ int main(int argc, char *argv[])
     uint64_t batch_bytes = 64ull << 20;
     const char *env = getenv("KMPGPU_BATCH_BYTES");
     if (env && atoll(env) >= (1 << 16)) batch_bytes = (uint64_t)atoll(env);                 /* 64 KiB and up: a frame (<= 64 KiB captured) always fits */
-    const char *dx = getenv("KMPGPU_DEVICE_EXTRACT");
-    const int frames_mode = dx && dx[0] == '1';
+    const int frames_mode = env_device_extract();
     /* a frame record takes 16 bytes of header and up; a payload slot 16 bytes and up, 64 on average or more in practice */
     const uint64_t cap_pkts = frames_mode ? batch_bytes / 32 : batch_bytes / 64;
 
     /* consumer threads (contexts) per GPU shard: two by default; KMPGPU_STREAM_CONTEXTS = 1..8 */
     int per_shard = 2;
     { const char *e = getenv("KMPGPU_STREAM_CONTEXTS"); if (e && atoi(e) >= 1 && atoi(e) <= 8) per_shard = atoi(e); }
-    { const char *dx0 = getenv("KMPGPU_DEVICE_EXTRACT"); if (dx0 && dx0[0] == '1') per_shard = 1; }       /* raw frames: one thread per shard drives two contexts */
+    if (frames_mode) per_shard = 1;                                                                  /* raw frames: one thread per shard drives two contexts */
     shared sh;
     memset(&sh, 0, sizeof sh);
     pthread_mutex_init(&sh.mu, NULL);
@@ -313,6 +272,7 @@ int main(int argc, char *argv[])
     sh.n_slots = (frames_mode ? 5 : 3 + per_shard) * shards;
     sh.slots = (slot *)calloc((size_t)sh.n_slots, sizeof(slot));
     sh.pats = &pats; sh.ndev = ndev;
+    sh.whole_payload = env_flag("KMPGPU_WHOLE_PAYLOAD"); sh.nocase = env_flag("KMPGPU_NOCASE");
     sh.frames_mode = frames_mode; sh.tcp = proto == KMP_PROTO_TCP;
     sh.batch_bytes = batch_bytes; sh.cap_pkts = cap_pkts; sh.per_shard = per_shard;
     { const char *e = getenv("KMPGPU_SERIAL_UPLOADS"); sh.serial_uploads = e ? atoi(e) != 0 : 1; }
@@ -409,30 +369,12 @@ int main(int argc, char *argv[])
             if (kmpgpu_sync(cons[per_shard * r].total)) die_gpu("kmpgpu_sync");
             tot[r] = cons[per_shard * r].total;
         }
-        /* The sum over the shards (mpi_dumping.c:202): one shard per device -> RCCL all-reduce of the device counters and
-         * one download; shards that share a device -> host sum.  KMPGPU_RCCL=0 / 1 as in bin/openmp_data. */
-        const char *rccl_env = getenv("KMPGPU_RCCL");
-        kmpgpu_comm *comm = NULL;
-        /* every shard's own totals first: what the host sums when there is no communicator or the all-reduce fails */
-        uint64_t *part = (uint64_t *)calloc((size_t)shards * pats.n, sizeof(uint64_t));
-        for (int r = 0; r < shards; r++)
-            if (kmpgpu_counts_read(tot[r], part + (size_t)r * pats.n)) die_gpu("kmpgpu_counts_read");
-        if (shards <= ndev && (shards > 1 || (rccl_env && rccl_env[0] == '1')) && !(rccl_env && rccl_env[0] == '0')) {
-            int bad = kmpgpu_comm_init(&comm, tot, shards) != 0;
-            if (!bad) bad = kmpgpu_comm_allreduce_counts(comm) != 0;
-            if (!bad) bad = kmpgpu_counts_read(tot[0], counts) != 0;
-            for (int r = 1; r < shards && !bad; r++) bad = kmpgpu_sync(tot[r]) != 0;
-            if (bad) fprintf(stderr, "[kmpgpu] RCCL count reduce: %s -- summing the shards' counts on the host\n", kmpgpu_last_error());
-            else reduce_rccl = 1;
-            if (comm) kmpgpu_comm_destroy(comm);
-        }
-        if (!reduce_rccl) {
-            for (uint32_t i = 0; i < pats.n; i++) {
-                counts[i] = 0;
-                for (int r = 0; r < shards; r++) counts[i] += part[(size_t)r * pats.n + i];          /* mpi_dumping.c:202 MPI_SUM */
-            }
-        }
-        free(part);
+        /* the sum over the shards (mpi_dumping.c:202), as in bin/openmp_data */
+        uint64_t *own = (uint64_t *)calloc((size_t)shards * pats.n, sizeof(uint64_t));
+        kmpgpu_comm *comm = reduce_comm(tot, shards, ndev);
+        reduce_rccl = reduce_counts(tot, shards, pats.n, own, counts, comm);
+        if (comm) kmpgpu_comm_destroy(comm);
+        free(own);
         free(tot);
     }
     const double t_finish = now_s();                                                                /* openmp_task.c:188 */
@@ -443,15 +385,14 @@ int main(int argc, char *argv[])
             (unsigned long long)(batch_bytes >> 20), frames_mode ? "raw frames, extraction on the GPU" : "payloads extracted on the host", shards, reduce_rccl ? "RCCL all-reduce" : (shards > 1 ? "host sum" : "none"), t_finish - t_start,
             (double)bytes / (t_finish - t_start) / 1e9);
 
-    { const char *st = getenv("KMPGPU_STATS");
-      if (st && st[0] && st[0] != '0') {
-          double load_s = 0, wait_s = 0, h2d = 0;
-          fprintf(stderr, "[kmpgpu] text rule: %s\n", whole_payload_env() ? "whole payloads (KMPGPU_WHOLE_PAYLOAD=1)" : "up to a payload's first NUL (the reference's strlen)");
-          for (int r = 0; r < (pats.n ? n_cons : 0); r++) { load_s += cons[r].load_s; wait_s += cons[r].wait_s; h2d += cons[r].h2d_ms; }
-          fprintf(stderr, "[kmpgpu] phases: producer %.3f s building batches + %.3f s waiting for a free slot; staging copies %.3f s; consumers %.3f s in the load calls "
-                          "(uploads by the events: %.3f s), %.3f s waiting for a batch\n",
-                  prod_walk_s, prod_wait_s, sh.copy_s, load_s, h2d * 1e-3, wait_s);
-      } }
+    if (env_stats()) {
+        double load_s = 0, wait_s = 0, h2d = 0;
+        print_text_rule(sh.whole_payload);
+        for (int r = 0; r < (pats.n ? n_cons : 0); r++) { load_s += cons[r].load_s; wait_s += cons[r].wait_s; h2d += cons[r].h2d_ms; }
+        fprintf(stderr, "[kmpgpu] phases: producer %.3f s building batches + %.3f s waiting for a free slot; staging copies %.3f s; consumers %.3f s in the load calls "
+                        "(uploads by the events: %.3f s), %.3f s waiting for a batch\n",
+                prod_walk_s, prod_wait_s, sh.copy_s, load_s, h2d * 1e-3, wait_s);
+    }
     /* teardown, after the clock has stopped (openmp_task.c:188 takes the time before it frees anything) */
     if (pats.n) for (int r = 0; r < n_cons; r++) { kmpgpu_destroy(cons[r].total); if (cons[r].extra) kmpgpu_destroy(cons[r].extra); }
     kmp_batch_close(rd);

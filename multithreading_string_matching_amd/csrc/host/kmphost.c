@@ -12,6 +12,7 @@
 #endif
 #include <fcntl.h>
 #include <pthread.h>
+#include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
 #include <sys/mman.h>
@@ -423,118 +424,59 @@ void kmp_patterns_free(kmp_patterns *p)
     memset(p, 0, sizeof *p);
 }
 
-/* ============================ content rules ============================================= */
+/* ============================ text files, line by line ================================== */
 
-static int rules_push(uint32_t **v, size_t *n, size_t *cap, uint32_t x)
+/* What the rules, relations, chains and windows files share: one entry per line, blank lines and lines whose first non-blank character
+ * is '#' skipped.  text_lines opens path and hands every other line to fn -- p at its first non-blank character, end behind its last
+ * one (the newline included), lineno counting every line of the file from 1 -- until fn returns something other than KMPHOST_OK,
+ * which text_lines then returns.  The message of a file that cannot be opened (KMPHOST_EIO) and the one that goes with
+ * KMPHOST_ENOMEM are written here. */
+#define KMP_LINE_ERRBUF 256
+_Static_assert(KMP_RULES_ERRBUF == KMP_LINE_ERRBUF && KMP_RELATIONS_ERRBUF == KMP_LINE_ERRBUF && KMP_CHAINS_ERRBUF == KMP_LINE_ERRBUF &&
+               KMP_WINDOWS_ERRBUF == KMP_LINE_ERRBUF, "the four formats' error buffers have one size");
+typedef int (*line_fn)(void *ctx, const char *p, const char *end, size_t lineno, char *errbuf);
+
+static int out_of_memory(char *errbuf)
 {
-    if (*n == *cap) {
-        const size_t nc = *cap ? *cap * 2 : 64;
-        uint32_t *nv = (uint32_t *)realloc(*v, nc * sizeof(uint32_t));
-        if (!nv) return KMPHOST_ENOMEM;
-        *v = nv; *cap = nc;
-    }
-    (*v)[(*n)++] = x;
-    return KMPHOST_OK;
+    if (errbuf) snprintf(errbuf, KMP_LINE_ERRBUF, "out of memory");
+    return KMPHOST_ENOMEM;
 }
 
-int kmp_rules_parse(const char *path, uint32_t n_patterns, kmp_rules *out, char errbuf[KMP_RULES_ERRBUF])
+static int text_lines(const char *path, line_fn fn, void *ctx, char *errbuf)
 {
-    return kmp_rules_parse_rel(path, n_patterns, 0, out, errbuf);
-}
-
-int kmp_rules_parse_rel(const char *path, uint32_t n_patterns, uint32_t n_relations, kmp_rules *out, char errbuf[KMP_RULES_ERRBUF])
-{
-    return kmp_rules_parse_terms(path, n_patterns, n_relations, 0, out, errbuf);
-}
-
-int kmp_rules_parse_terms(const char *path, uint32_t n_patterns, uint32_t n_relations, uint32_t n_chains, kmp_rules *out, char errbuf[KMP_RULES_ERRBUF])
-{
-    memset(out, 0, sizeof *out);
-    if (errbuf) errbuf[0] = 0;
-    /* a term is a row below 2^31: bit 31 is KMP_RULE_NOT (kmpgpu_set_relations and kmpgpu_set_chains refuse such a set too) */
-    if ((uint64_t)n_patterns + n_relations + n_chains >= (1ull << 31)) {
-        if (errbuf) {
-            if (n_chains) snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations + %u chains do not fit the 2^31 rows a term can name", n_patterns, n_relations, n_chains);
-            else snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations do not fit the 2^31 rows a term can name", n_patterns, n_relations);
-        }
-        return KMPHOST_EINVAL;
-    }
     FILE *fp = fopen(path, "rb");
     if (!fp) {
-        if (errbuf) snprintf(errbuf, KMP_RULES_ERRBUF, "%s: %s", path, strerror(errno));
+        if (errbuf) snprintf(errbuf, KMP_LINE_ERRBUF, "%s: %s", path, strerror(errno));
         return KMPHOST_EIO;
     }
     char *line = NULL;
-    size_t line_cap = 0, n_off = 0, cap_off = 0, n_terms = 0, cap_terms = 0, lineno = 0;
+    size_t line_cap = 0, lineno = 0;
     ssize_t got;
-    int rc = rules_push(&out->off, &n_off, &cap_off, 0);
+    int rc = KMPHOST_OK;
     while (!rc && (got = getline(&line, &line_cap, fp)) >= 0) {
         lineno++;
         const char *p = line, *end = line + got;
         while (p < end && is_c_space((uint8_t)*p)) p++;
         if (p == end || *p == '#') continue;                           /* blank line, comment */
-        while (p < end && !rc) {
-            const char *tok = p;
-            uint32_t neg = 0;
-            uint64_t v = 0;
-            if (*p == '!') { neg = KMP_RULE_NOT; p++; }
-            /* r<q>: relation q, where the caller has relations (without any the token is no term at all, as it always was) */
-            const int is_rel = n_relations && p < end && *p == 'r';
-            /* c<q>: chain q, in the same way */
-            const int is_chain = n_chains && p < end && *p == 'c';
-            if (is_rel || is_chain) p++;
-            const char *digits = p;
-            while (p < end && *p >= '0' && *p <= '9') { if (v < (1ull << 40)) v = v * 10 + (uint64_t)(*p - '0'); p++; }
-            const char *stop = p;
-            while (stop < end && !is_c_space((uint8_t)*stop)) stop++;   /* the whole token, for the message */
-            if (p == digits && neg && stop == p && !is_rel && !is_chain) {
-                if (errbuf) snprintf(errbuf, KMP_RULES_ERRBUF, "line %zu: '!' without a pattern index", lineno);
-                rc = KMPHOST_EINVAL;
-            } else if (p == digits || stop != p) {
-                if (errbuf) snprintf(errbuf, KMP_RULES_ERRBUF, "line %zu: '%.*s' is not a pattern index%s%s", lineno, (int)(stop - tok > 64 ? 64 : stop - tok), tok,
-                                     n_relations ? " or r<relation index>" : "", n_chains ? " or c<chain index>" : "");
-                rc = KMPHOST_EINVAL;
-            } else if (is_chain) {
-                if (v >= n_chains) {
-                    if (errbuf) snprintf(errbuf, KMP_RULES_ERRBUF, "line %zu: chain index %llu, but there are %u chains", lineno, (unsigned long long)v, n_chains);
-                    rc = KMPHOST_EINVAL;
-                } else
-                    rc = rules_push(&out->terms, &n_terms, &cap_terms, (n_patterns + n_relations + (uint32_t)v) | neg);
-            } else if (is_rel) {
-                if (v >= n_relations) {
-                    if (errbuf) snprintf(errbuf, KMP_RULES_ERRBUF, "line %zu: relation index %llu, but there are %u relations", lineno, (unsigned long long)v, n_relations);
-                    rc = KMPHOST_EINVAL;
-                } else
-                    rc = rules_push(&out->terms, &n_terms, &cap_terms, (n_patterns + (uint32_t)v) | neg);
-            } else if (v >= n_patterns) {
-                if (errbuf) snprintf(errbuf, KMP_RULES_ERRBUF, "line %zu: pattern index %llu, but there are %u patterns", lineno, (unsigned long long)v, n_patterns);
-                rc = KMPHOST_EINVAL;
-            } else
-                rc = rules_push(&out->terms, &n_terms, &cap_terms, (uint32_t)v | neg);
-            while (p < end && is_c_space((uint8_t)*p)) p++;
-        }
-        if (!rc && n_terms > 0xFFFFFFFFull) rc = KMPHOST_EINVAL;
-        if (!rc) rc = rules_push(&out->off, &n_off, &cap_off, (uint32_t)n_terms);
+        rc = fn(ctx, p, end, lineno, errbuf);
     }
     free(line);
     fclose(fp);
-    if (rc) {
-        if (rc == KMPHOST_ENOMEM && errbuf) snprintf(errbuf, KMP_RULES_ERRBUF, "out of memory");
-        kmp_rules_free(out);
-        return rc;
-    }
-    out->n = (uint32_t)(n_off - 1);
-    return KMPHOST_OK;
+    return rc == KMPHOST_ENOMEM ? out_of_memory(errbuf) : rc;
 }
 
-void kmp_rules_free(kmp_rules *r)
+/* "line N: " and the message into errbuf; KMPHOST_EINVAL */
+__attribute__((format(printf, 3, 4))) static int line_error(char *errbuf, size_t lineno, const char *fmt, ...)
 {
-    if (!r) return;
-    free(r->off); free(r->terms);
-    memset(r, 0, sizeof *r);
+    if (errbuf) {
+        const int k = snprintf(errbuf, KMP_LINE_ERRBUF, "line %zu: ", lineno);
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(errbuf + k, (size_t)(KMP_LINE_ERRBUF - k), fmt, ap);
+        va_end(ap);
+    }
+    return KMPHOST_EINVAL;
 }
-
-/* ============================ relations ================================================= */
 
 /* One field of a relations, chains or windows line at *pp: a decimal number, with a leading '-' where neg_ok, that fits lo..hi, or
  * (star != 0) a lone '*' = star.  Leaves *pp behind the field and the blanks that follow it; on failure *tok / *tok_len name the field for
@@ -560,70 +502,150 @@ static int number_field(const char **pp, const char *end, int neg_ok, int64_t lo
     return ok;
 }
 
+static int rules_push(uint32_t **v, size_t *n, size_t *cap, uint32_t x)
+{
+    if (*n == *cap) {
+        const size_t nc = *cap ? *cap * 2 : 64;
+        uint32_t *nv = (uint32_t *)realloc(*v, nc * sizeof(uint32_t));
+        if (!nv) return KMPHOST_ENOMEM;
+        *v = nv; *cap = nc;
+    }
+    (*v)[(*n)++] = x;
+    return KMPHOST_OK;
+}
+
+/* ============================ content rules ============================================= */
+
+typedef struct rules_ctx {
+    uint32_t n_patterns, n_relations, n_chains;
+    kmp_rules *out;
+    size_t n_off, cap_off, n_terms, cap_terms;
+} rules_ctx;
+
+static int rules_line(void *ctx, const char *p, const char *end, size_t lineno, char *errbuf)
+{
+    rules_ctx *c = (rules_ctx *)ctx;
+    while (p < end) {
+        const char *tok = p;
+        uint32_t neg = 0, row;
+        uint64_t v = 0;
+        if (*p == '!') { neg = KMP_RULE_NOT; p++; }
+        /* r<q>: relation q, where the caller has relations (without any the token is no term at all, as it always was) */
+        const int is_rel = c->n_relations && p < end && *p == 'r';
+        /* c<q>: chain q, in the same way */
+        const int is_chain = c->n_chains && p < end && *p == 'c';
+        if (is_rel || is_chain) p++;
+        const char *digits = p;
+        while (p < end && *p >= '0' && *p <= '9') { if (v < (1ull << 40)) v = v * 10 + (uint64_t)(*p - '0'); p++; }
+        const char *stop = p;
+        while (stop < end && !is_c_space((uint8_t)*stop)) stop++;   /* the whole token, for the message */
+        if (p == digits && neg && stop == p && !is_rel && !is_chain) return line_error(errbuf, lineno, "'!' without a pattern index");
+        if (p == digits || stop != p)
+            return line_error(errbuf, lineno, "'%.*s' is not a pattern index%s%s", (int)(stop - tok > 64 ? 64 : stop - tok), tok,
+                              c->n_relations ? " or r<relation index>" : "", c->n_chains ? " or c<chain index>" : "");
+        if (is_chain) {
+            if (v >= c->n_chains) return line_error(errbuf, lineno, "chain index %llu, but there are %u chains", (unsigned long long)v, c->n_chains);
+            row = c->n_patterns + c->n_relations + (uint32_t)v;
+        } else if (is_rel) {
+            if (v >= c->n_relations) return line_error(errbuf, lineno, "relation index %llu, but there are %u relations", (unsigned long long)v, c->n_relations);
+            row = c->n_patterns + (uint32_t)v;
+        } else {
+            if (v >= c->n_patterns) return line_error(errbuf, lineno, "pattern index %llu, but there are %u patterns", (unsigned long long)v, c->n_patterns);
+            row = (uint32_t)v;
+        }
+        if (rules_push(&c->out->terms, &c->n_terms, &c->cap_terms, row | neg)) return KMPHOST_ENOMEM;
+        while (p < end && is_c_space((uint8_t)*p)) p++;
+    }
+    if (c->n_terms > 0xFFFFFFFFull) return KMPHOST_EINVAL;
+    return rules_push(&c->out->off, &c->n_off, &c->cap_off, (uint32_t)c->n_terms);
+}
+
+int kmp_rules_parse(const char *path, uint32_t n_patterns, kmp_rules *out, char errbuf[KMP_RULES_ERRBUF])
+{
+    return kmp_rules_parse_rel(path, n_patterns, 0, out, errbuf);
+}
+
+int kmp_rules_parse_rel(const char *path, uint32_t n_patterns, uint32_t n_relations, kmp_rules *out, char errbuf[KMP_RULES_ERRBUF])
+{
+    return kmp_rules_parse_terms(path, n_patterns, n_relations, 0, out, errbuf);
+}
+
+int kmp_rules_parse_terms(const char *path, uint32_t n_patterns, uint32_t n_relations, uint32_t n_chains, kmp_rules *out, char errbuf[KMP_RULES_ERRBUF])
+{
+    memset(out, 0, sizeof *out);
+    if (errbuf) errbuf[0] = 0;
+    /* a term is a row below 2^31: bit 31 is KMP_RULE_NOT (kmpgpu_set_relations and kmpgpu_set_chains refuse such a set too) */
+    if ((uint64_t)n_patterns + n_relations + n_chains >= (1ull << 31)) {
+        if (errbuf) {
+            if (n_chains) snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations + %u chains do not fit the 2^31 rows a term can name", n_patterns, n_relations, n_chains);
+            else snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations do not fit the 2^31 rows a term can name", n_patterns, n_relations);
+        }
+        return KMPHOST_EINVAL;
+    }
+    rules_ctx c = {n_patterns, n_relations, n_chains, out, 0, 0, 0, 0};
+    int rc = rules_push(&out->off, &c.n_off, &c.cap_off, 0) ? out_of_memory(errbuf) : text_lines(path, rules_line, &c, errbuf);
+    if (rc) {
+        kmp_rules_free(out);
+        return rc;
+    }
+    out->n = (uint32_t)(c.n_off - 1);
+    return KMPHOST_OK;
+}
+
+void kmp_rules_free(kmp_rules *r)
+{
+    if (!r) return;
+    free(r->off); free(r->terms);
+    memset(r, 0, sizeof *r);
+}
+
+/* ============================ relations ================================================= */
+
+typedef struct relations_ctx {
+    uint32_t n_patterns;
+    kmp_relations *out;
+    size_t n, cap;
+} relations_ctx;
+
+static int relations_line(void *ctx, const char *p, const char *end, size_t lineno, char *errbuf)
+{
+    relations_ctx *c = (relations_ctx *)ctx;
+    static const char *const what[4] = {"a pattern index", "a pattern index", "a lower bound or '*'", "an upper bound or '*'"};
+    int64_t f[4] = {0, 0, 0, 0};
+    for (int k = 0; k < 4; k++) {
+        const char *tok;
+        int tl;
+        if (p == end) return line_error(errbuf, lineno, "%d of the four fields <a> <b> <dmin> <dmax>", k);
+        if (!number_field(&p, end, k >= 2, k >= 2 ? INT32_MIN : 0, k >= 2 ? INT32_MAX : 0xFFFFFFFFll, k == 2 ? INT32_MIN : k == 3 ? INT32_MAX : 0, &f[k], &tok, &tl))
+            return line_error(errbuf, lineno, "'%.*s' is not %s", tl, tok, what[k]);
+    }
+    if (p != end) return line_error(errbuf, lineno, "more than the four fields <a> <b> <dmin> <dmax>");
+    if (f[0] >= c->n_patterns || f[1] >= c->n_patterns)
+        return line_error(errbuf, lineno, "pattern index %lld, but there are %u patterns", (long long)(f[0] >= c->n_patterns ? f[0] : f[1]), c->n_patterns);
+    if (f[2] > f[3]) return line_error(errbuf, lineno, "lower bound %lld lies above upper bound %lld", (long long)f[2], (long long)f[3]);
+    if (c->n == c->cap) {
+        const size_t nc = c->cap ? c->cap * 2 : 64;
+        kmp_relation *nv = (kmp_relation *)realloc(c->out->rel, nc * sizeof *nv);
+        if (!nv) return KMPHOST_ENOMEM;
+        c->out->rel = nv; c->cap = nc;
+    }
+    const kmp_relation r = {(uint32_t)f[0], (uint32_t)f[1], (int32_t)f[2], (int32_t)f[3]};
+    c->out->rel[c->n++] = r;
+    return KMPHOST_OK;
+}
+
 int kmp_relations_parse(const char *path, uint32_t n_patterns, kmp_relations *out, char errbuf[KMP_RELATIONS_ERRBUF])
 {
     memset(out, 0, sizeof *out);
     if (errbuf) errbuf[0] = 0;
-    FILE *fp = fopen(path, "rb");
-    if (!fp) {
-        if (errbuf) snprintf(errbuf, KMP_RELATIONS_ERRBUF, "%s: %s", path, strerror(errno));
-        return KMPHOST_EIO;
-    }
-    char *line = NULL;
-    size_t line_cap = 0, lineno = 0, n = 0, cap = 0;
-    ssize_t got;
-    int rc = KMPHOST_OK;
-    while (!rc && (got = getline(&line, &line_cap, fp)) >= 0) {
-        lineno++;
-        const char *p = line, *end = line + got;
-        while (p < end && is_c_space((uint8_t)*p)) p++;
-        if (p == end || *p == '#') continue;                           /* blank line, comment */
-        static const char *const what[4] = {"a pattern index", "a pattern index", "a lower bound or '*'", "an upper bound or '*'"};
-        int64_t f[4] = {0, 0, 0, 0};
-        for (int k = 0; k < 4 && !rc; k++) {
-            const char *tok;
-            int tl;
-            if (p == end) {
-                if (errbuf) snprintf(errbuf, KMP_RELATIONS_ERRBUF, "line %zu: %d of the four fields <a> <b> <dmin> <dmax>", lineno, k);
-                rc = KMPHOST_EINVAL;
-            } else if (!number_field(&p, end, k >= 2, k >= 2 ? INT32_MIN : 0, k >= 2 ? INT32_MAX : 0xFFFFFFFFll,
-                                     k == 2 ? INT32_MIN : k == 3 ? INT32_MAX : 0, &f[k], &tok, &tl)) {
-                if (errbuf) snprintf(errbuf, KMP_RELATIONS_ERRBUF, "line %zu: '%.*s' is not %s", lineno, tl, tok, what[k]);
-                rc = KMPHOST_EINVAL;
-            }
-        }
-        if (rc) break;
-        if (p != end) {
-            if (errbuf) snprintf(errbuf, KMP_RELATIONS_ERRBUF, "line %zu: more than the four fields <a> <b> <dmin> <dmax>", lineno);
-            rc = KMPHOST_EINVAL;
-        } else if (f[0] >= n_patterns || f[1] >= n_patterns) {
-            if (errbuf) snprintf(errbuf, KMP_RELATIONS_ERRBUF, "line %zu: pattern index %lld, but there are %u patterns", lineno,
-                                 (long long)(f[0] >= n_patterns ? f[0] : f[1]), n_patterns);
-            rc = KMPHOST_EINVAL;
-        } else if (f[2] > f[3]) {
-            if (errbuf) snprintf(errbuf, KMP_RELATIONS_ERRBUF, "line %zu: lower bound %lld lies above upper bound %lld", lineno, (long long)f[2], (long long)f[3]);
-            rc = KMPHOST_EINVAL;
-        } else {
-            if (n == cap) {
-                const size_t nc = cap ? cap * 2 : 64;
-                kmp_relation *nv = (kmp_relation *)realloc(out->rel, nc * sizeof *nv);
-                if (!nv) { rc = KMPHOST_ENOMEM; break; }
-                out->rel = nv; cap = nc;
-            }
-            out->rel[n].a = (uint32_t)f[0]; out->rel[n].b = (uint32_t)f[1];
-            out->rel[n].dmin = (int32_t)f[2]; out->rel[n].dmax = (int32_t)f[3];
-            n++;
-        }
-    }
-    free(line);
-    fclose(fp);
-    if (!rc && n > 0x7FFFFFFFull) rc = KMPHOST_EINVAL;
+    relations_ctx c = {n_patterns, out, 0, 0};
+    int rc = text_lines(path, relations_line, &c, errbuf);
+    if (!rc && c.n > 0x7FFFFFFFull) rc = KMPHOST_EINVAL;
     if (rc) {
-        if (rc == KMPHOST_ENOMEM && errbuf) snprintf(errbuf, KMP_RELATIONS_ERRBUF, "out of memory");
         kmp_relations_free(out);
         return rc;
     }
-    out->n = (uint32_t)n;
+    out->n = (uint32_t)c.n;
     return KMPHOST_OK;
 }
 
@@ -636,87 +658,65 @@ void kmp_relations_free(kmp_relations *r)
 
 /* ============================ chains ==================================================== */
 
+typedef struct chains_ctx {
+    uint32_t n_patterns;
+    kmp_chains *out;
+    size_t n_off, cap_off, n_links, cap_links;
+} chains_ctx;
+
+static int chains_line(void *ctx, const char *p, const char *end, size_t lineno, char *errbuf)
+{
+    chains_ctx *c = (chains_ctx *)ctx;
+    static const char *const what[3] = {"a pattern index", "a lower bound or '*'", "an upper bound or '*'"};
+    kmp_chain_link l[KMP_CHAIN_MAX];
+    uint32_t n = 0;                                                 /* contents so far */
+    int k = 0;                                                      /* the field that comes next: 0 an index, 1 dmin, 2 dmax */
+    int64_t lo = INT32_MIN, hi = INT32_MAX;                         /* the bounds in front of the next index (the first has none) */
+    while (p < end) {
+        const char *tok;
+        int tl;
+        int64_t v;
+        if (k == 0 && n == KMP_CHAIN_MAX) return line_error(errbuf, lineno, "more than %d contents", KMP_CHAIN_MAX);
+        if (!number_field(&p, end, k != 0, k ? INT32_MIN : 0, k ? INT32_MAX : 0xFFFFFFFFll, k == 1 ? INT32_MIN : k == 2 ? INT32_MAX : 0, &v, &tok, &tl))
+            return line_error(errbuf, lineno, "'%.*s' is not %s", tl, tok, what[k]);
+        if (k == 0) {
+            if (v >= c->n_patterns) return line_error(errbuf, lineno, "pattern index %lld, but there are %u patterns", (long long)v, c->n_patterns);
+            l[n].pattern = (uint32_t)v; l[n].dmin = (int32_t)lo; l[n].dmax = (int32_t)hi;
+            n++; k = 1;
+        } else if (k == 1) {
+            lo = v; k = 2;
+        } else {
+            hi = v; k = 0;
+            if (lo > hi) return line_error(errbuf, lineno, "lower bound %lld lies above upper bound %lld", (long long)lo, (long long)hi);
+        }
+    }
+    if (k != 1)                                                     /* the line has to end behind an index */
+        return line_error(errbuf, lineno, "the fields are <p0> <dmin> <dmax> <p1> [<dmin> <dmax> <p2> ...]: bounds without the content behind them");
+    if (n < 2) return line_error(errbuf, lineno, "a chain has at least 2 contents: <p0> <dmin> <dmax> <p1> ...");
+    if (c->n_links + n > c->cap_links) {
+        const size_t nc = c->cap_links ? c->cap_links * 2 : 64;
+        kmp_chain_link *nv = (kmp_chain_link *)realloc(c->out->links, nc * sizeof *nv);
+        if (!nv) return KMPHOST_ENOMEM;
+        c->out->links = nv; c->cap_links = nc;
+    }
+    memcpy(c->out->links + c->n_links, l, n * sizeof l[0]);
+    c->n_links += n;
+    if (c->n_links > 0xFFFFFFFFull) return KMPHOST_EINVAL;
+    return rules_push(&c->out->off, &c->n_off, &c->cap_off, (uint32_t)c->n_links);
+}
+
 int kmp_chains_parse(const char *path, uint32_t n_patterns, kmp_chains *out, char errbuf[KMP_CHAINS_ERRBUF])
 {
     memset(out, 0, sizeof *out);
     if (errbuf) errbuf[0] = 0;
-    FILE *fp = fopen(path, "rb");
-    if (!fp) {
-        if (errbuf) snprintf(errbuf, KMP_CHAINS_ERRBUF, "%s: %s", path, strerror(errno));
-        return KMPHOST_EIO;
-    }
-    char *line = NULL;
-    size_t line_cap = 0, lineno = 0, n_off = 0, cap_off = 0, n_links = 0, cap_links = 0;
-    ssize_t got;
-    int rc = rules_push(&out->off, &n_off, &cap_off, 0);
-    while (!rc && (got = getline(&line, &line_cap, fp)) >= 0) {
-        lineno++;
-        const char *p = line, *end = line + got;
-        while (p < end && is_c_space((uint8_t)*p)) p++;
-        if (p == end || *p == '#') continue;                           /* blank line, comment */
-        static const char *const what[3] = {"a pattern index", "a lower bound or '*'", "an upper bound or '*'"};
-        kmp_chain_link l[KMP_CHAIN_MAX];
-        uint32_t n = 0;                                                 /* contents so far */
-        int k = 0;                                                      /* the field that comes next: 0 an index, 1 dmin, 2 dmax */
-        int64_t lo = INT32_MIN, hi = INT32_MAX;                         /* the bounds in front of the next index (the first has none) */
-        while (p < end && !rc) {
-            const char *tok;
-            int tl;
-            int64_t v;
-            if (k == 0 && n == KMP_CHAIN_MAX) {
-                if (errbuf) snprintf(errbuf, KMP_CHAINS_ERRBUF, "line %zu: more than %d contents", lineno, KMP_CHAIN_MAX);
-                rc = KMPHOST_EINVAL;
-            } else if (!number_field(&p, end, k != 0, k ? INT32_MIN : 0, k ? INT32_MAX : 0xFFFFFFFFll, k == 1 ? INT32_MIN : k == 2 ? INT32_MAX : 0, &v,
-                                     &tok, &tl)) {
-                if (errbuf) snprintf(errbuf, KMP_CHAINS_ERRBUF, "line %zu: '%.*s' is not %s", lineno, tl, tok, what[k]);
-                rc = KMPHOST_EINVAL;
-            } else if (k == 0) {
-                if (v >= n_patterns) {
-                    if (errbuf) snprintf(errbuf, KMP_CHAINS_ERRBUF, "line %zu: pattern index %lld, but there are %u patterns", lineno, (long long)v, n_patterns);
-                    rc = KMPHOST_EINVAL;
-                } else {
-                    l[n].pattern = (uint32_t)v; l[n].dmin = (int32_t)lo; l[n].dmax = (int32_t)hi;
-                    n++; k = 1;
-                }
-            } else if (k == 1) {
-                lo = v; k = 2;
-            } else {
-                hi = v; k = 0;
-                if (lo > hi) {
-                    if (errbuf) snprintf(errbuf, KMP_CHAINS_ERRBUF, "line %zu: lower bound %lld lies above upper bound %lld", lineno, (long long)lo, (long long)hi);
-                    rc = KMPHOST_EINVAL;
-                }
-            }
-        }
-        if (rc) break;
-        if (k != 1) {                                                   /* the line has to end behind an index */
-            if (errbuf) snprintf(errbuf, KMP_CHAINS_ERRBUF, "line %zu: the fields are <p0> <dmin> <dmax> <p1> [<dmin> <dmax> <p2> ...]: bounds without the content behind them", lineno);
-            rc = KMPHOST_EINVAL;
-        } else if (n < 2) {
-            if (errbuf) snprintf(errbuf, KMP_CHAINS_ERRBUF, "line %zu: a chain has at least 2 contents: <p0> <dmin> <dmax> <p1> ...", lineno);
-            rc = KMPHOST_EINVAL;
-        } else {
-            if (n_links + n > cap_links) {
-                const size_t nc = cap_links ? cap_links * 2 : 64;
-                kmp_chain_link *nv = (kmp_chain_link *)realloc(out->links, nc * sizeof *nv);
-                if (!nv) { rc = KMPHOST_ENOMEM; break; }
-                out->links = nv; cap_links = nc;
-            }
-            memcpy(out->links + n_links, l, n * sizeof l[0]);
-            n_links += n;
-            if (n_links > 0xFFFFFFFFull) rc = KMPHOST_EINVAL;
-            if (!rc) rc = rules_push(&out->off, &n_off, &cap_off, (uint32_t)n_links);
-        }
-    }
-    free(line);
-    fclose(fp);
-    if (!rc && n_off - 1 > 0x7FFFFFFFull) rc = KMPHOST_EINVAL;
+    chains_ctx c = {n_patterns, out, 0, 0, 0, 0};
+    int rc = rules_push(&out->off, &c.n_off, &c.cap_off, 0) ? out_of_memory(errbuf) : text_lines(path, chains_line, &c, errbuf);
+    if (!rc && c.n_off - 1 > 0x7FFFFFFFull) rc = KMPHOST_EINVAL;
     if (rc) {
-        if (rc == KMPHOST_ENOMEM && errbuf) snprintf(errbuf, KMP_CHAINS_ERRBUF, "out of memory");
         kmp_chains_free(out);
         return rc;
     }
-    out->n = (uint32_t)(n_off - 1);
+    out->n = (uint32_t)(c.n_off - 1);
     return KMPHOST_OK;
 }
 
@@ -729,60 +729,41 @@ void kmp_chains_free(kmp_chains *c)
 
 /* ============================ offset windows ============================================ */
 
+typedef struct windows_ctx {
+    uint32_t n_patterns, *first, *last;
+    uint8_t *named;                                                 /* [n_patterns]: the pattern has a line already */
+} windows_ctx;
+
+static int windows_line(void *ctx, const char *p, const char *end, size_t lineno, char *errbuf)
+{
+    windows_ctx *c = (windows_ctx *)ctx;
+    static const char *const what[3] = {"a pattern index", "a first offset", "a last offset or '*'"};
+    uint32_t f[3] = {0, 0, 0};
+    for (int k = 0; k < 3; k++) {
+        const char *tok;
+        int tl;
+        int64_t v = 0;
+        if (p == end) return line_error(errbuf, lineno, "%d of the three fields <pattern index> <first> <last>", k);
+        if (!number_field(&p, end, 0, 0, 0xFFFFFFFFll, k == 2 ? 0xFFFFFFFFll : 0, &v, &tok, &tl))      /* '*': UINT32_MAX */
+            return line_error(errbuf, lineno, "'%.*s' is not %s", tl, tok, what[k]);
+        f[k] = (uint32_t)v;
+    }
+    if (p != end) return line_error(errbuf, lineno, "more than the three fields <pattern index> <first> <last>");
+    if (f[0] >= c->n_patterns) return line_error(errbuf, lineno, "pattern index %u, but there are %u patterns", f[0], c->n_patterns);
+    if (f[1] > f[2]) return line_error(errbuf, lineno, "first offset %u lies behind last offset %u", f[1], f[2]);
+    if (c->named[f[0]]) return line_error(errbuf, lineno, "pattern %u has a window already", f[0]);
+    c->named[f[0]] = 1; c->first[f[0]] = f[1]; c->last[f[0]] = f[2];
+    return KMPHOST_OK;
+}
+
 int kmp_windows_parse(const char *path, uint32_t n_patterns, uint32_t *first_out, uint32_t *last_out, char errbuf[KMP_WINDOWS_ERRBUF])
 {
     if (errbuf) errbuf[0] = 0;
-    FILE *fp = fopen(path, "rb");
-    if (!fp) {
-        if (errbuf) snprintf(errbuf, KMP_WINDOWS_ERRBUF, "%s: %s", path, strerror(errno));
-        return KMPHOST_EIO;
-    }
-    uint8_t *named = (uint8_t *)calloc(n_patterns ? n_patterns : 1, 1);
-    if (!named) { fclose(fp); if (errbuf) snprintf(errbuf, KMP_WINDOWS_ERRBUF, "out of memory"); return KMPHOST_ENOMEM; }
+    windows_ctx c = {n_patterns, first_out, last_out, (uint8_t *)calloc(n_patterns ? n_patterns : 1, 1)};
+    if (!c.named) return out_of_memory(errbuf);
     for (uint32_t i = 0; i < n_patterns; i++) { first_out[i] = 0u; last_out[i] = 0xFFFFFFFFu; }
-    char *line = NULL;
-    size_t line_cap = 0, lineno = 0;
-    ssize_t got;
-    int rc = KMPHOST_OK;
-    while (!rc && (got = getline(&line, &line_cap, fp)) >= 0) {
-        lineno++;
-        const char *p = line, *end = line + got;
-        while (p < end && is_c_space((uint8_t)*p)) p++;
-        if (p == end || *p == '#') continue;                           /* blank line, comment */
-        static const char *const what[3] = {"a pattern index", "a first offset", "a last offset or '*'"};
-        uint32_t f[3] = {0, 0, 0};
-        for (int k = 0; k < 3 && !rc; k++) {
-            const char *tok;
-            int tl;
-            int64_t v = 0;
-            if (p == end) {
-                if (errbuf) snprintf(errbuf, KMP_WINDOWS_ERRBUF, "line %zu: %d of the three fields <pattern index> <first> <last>", lineno, k);
-                rc = KMPHOST_EINVAL;
-            } else if (!number_field(&p, end, 0, 0, 0xFFFFFFFFll, k == 2 ? 0xFFFFFFFFll : 0, &v, &tok, &tl)) {      /* '*': UINT32_MAX */
-                if (errbuf) snprintf(errbuf, KMP_WINDOWS_ERRBUF, "line %zu: '%.*s' is not %s", lineno, tl, tok, what[k]);
-                rc = KMPHOST_EINVAL;
-            } else f[k] = (uint32_t)v;
-        }
-        if (rc) break;
-        if (p != end) {
-            if (errbuf) snprintf(errbuf, KMP_WINDOWS_ERRBUF, "line %zu: more than the three fields <pattern index> <first> <last>", lineno);
-            rc = KMPHOST_EINVAL;
-        } else if (f[0] >= n_patterns) {
-            if (errbuf) snprintf(errbuf, KMP_WINDOWS_ERRBUF, "line %zu: pattern index %u, but there are %u patterns", lineno, f[0], n_patterns);
-            rc = KMPHOST_EINVAL;
-        } else if (f[1] > f[2]) {
-            if (errbuf) snprintf(errbuf, KMP_WINDOWS_ERRBUF, "line %zu: first offset %u lies behind last offset %u", lineno, f[1], f[2]);
-            rc = KMPHOST_EINVAL;
-        } else if (named[f[0]]) {
-            if (errbuf) snprintf(errbuf, KMP_WINDOWS_ERRBUF, "line %zu: pattern %u has a window already", lineno, f[0]);
-            rc = KMPHOST_EINVAL;
-        } else {
-            named[f[0]] = 1; first_out[f[0]] = f[1]; last_out[f[0]] = f[2];
-        }
-    }
-    free(line);
-    free(named);
-    fclose(fp);
+    const int rc = text_lines(path, windows_line, &c, errbuf);
+    free(c.named);
     return rc;
 }
 
