@@ -103,6 +103,9 @@ typedef struct kmpgpu_match {
                                         be switched between two scans of one context with nothing reloaded, re-attached or re-set.
                                         Patterns stay free of 0x00 either way.  The whole-payload kernels keep 4 chunk loads in
                                         flight (the fused pass 3, as always): KMPGPU_OPT_DEPTH is accepted and has no effect on them */
+#define KMPGPU_OPT_KEEP_META    10   /* 0 (default) = kmpgpu_load_frames / _begin builds the arena alone, exactly as without this option;
+                                        1 = one further kernel keeps the per-payload header metadata of every accepted frame
+                                        (kmpgpu_pkt_meta, below); any other value: KMPGPU_EINVAL.  Read when a load is begun */
 #define KMPGPU_OPT_NONTEMPORAL 100   /* 1 (default) = arena loads carry the non-temporal hint (every
                                         byte is read once per pass; measured +10 % on MI355X), 0 =
                                         default cache policy                                   */
@@ -487,6 +490,86 @@ int  kmpgpu_set_chains(kmpgpu_ctx *ctx, const uint32_t *chain_off /* [n_chains +
 int  kmpgpu_scan_chains(kmpgpu_ctx *ctx, uint64_t *chain_pkt_counts_out /* [n_chains] or NULL */, uint64_t *any_out /* [W] or NULL */,
                         uint64_t *chain_hits_out /* [n_chains * W] or NULL */, uint64_t *counts_out /* [n_pat] or NULL: as kmpgpu_scan */,
                         kmpgpu_timing *t /* or NULL */);
+
+/* Header predicates: the rule HEADER of a signature -- "alert udp 10.0.0.0/8 any -> any 53", with dsize -- as a fifth kind of row
+ * of the hit matrix, beside patterns, relations and chains.  A predicate is decided from 16 bytes of per-payload metadata and the payload's
+ * length in the index, not from the text.
+ *
+ * Metadata.  kmpgpu_pkt_meta is what the extractors saw on their way to the payload, in payload order, one record per payload.  With p the
+ * frame: src_ip = p[26]<<24 | p[27]<<16 | p[28]<<8 | p[29], dst_ip likewise from p[30..33] (host-order integers); with
+ * T = 14 + ((p[14] & 0x0F) << 2): src_port = p[T]<<8 | p[T+1], dst_port = p[T+2]<<8 | p[T+3]; proto = p[23]; reserved 0.  The byte
+ * positions are the extractors' own: no EtherType or IP-version test, the IHL from the low nibble of byte 14 -- the metadata follows the
+ * reference's quirks (in tcp mode its extractor does not test the protocol byte: proto says what a payload really is).  For every frame
+ * either extractor accepts these bytes lie inside caplen; a rejected frame has no payload and no metadata.
+ * Where it comes from: kmpgpu_load_frames / _begin under KMPGPU_OPT_KEEP_META = 1 (one further kernel behind the index scatter; with 0 the
+ * load is what it is without the option and leaves no metadata), kmpgpu_set_meta for an arena that came through kmpgpu_load_arena /
+ * kmpgpu_attach_arena, and kmpgpu_load_selected, which hands dst the metadata of the selected payloads, in order, whenever src has some
+ * (one further kernel: launches 6, or 4 when nothing is selected; without metadata on src 5 / 3 as before).
+ * Lifetime: metadata belongs to the arena.  Every loader that puts a new arena into the context drops it (kmpgpu_load_arena,
+ * kmpgpu_attach_arena, kmpgpu_load_frames without the option, kmpgpu_load_selected as dst from a src without metadata); it survives the
+ * on-device repack (which keeps payload order), kmpgpu_set_patterns and every option.
+ * kmpgpu_set_meta copies meta[n_pkts] (on_device == 0: host memory; == 1: device memory on the context's device, 4-byte aligned; any other
+ * value: KMPGPU_EINVAL) into a buffer the context owns.  n_pkts must equal the context's payload count: otherwise KMPGPU_EINVAL; no
+ * arena: KMPGPU_ESTATE; n_pkts == 0 with a NULL pointer clears the metadata.  After an error the metadata that was there stays.
+ * kmpgpu_meta_download copies the records to out[cap] and leaves their number in *n (either may be NULL); cap below the payload count
+ * with out given: KMPGPU_EINVAL; no metadata: KMPGPU_ESTATE.
+ *
+ * Predicates.  With M = meta[k] and L_k the payload's length in the index (Snort's dsize; whatever KMPGPU_OPT_WHOLE_PAYLOAD says):
+ *     dir(s, d, sp, dp) = (s & src_mask) == (src_ip & src_mask) && (d & dst_mask) == (dst_ip & dst_mask)
+ *                         && sport_lo <= sp <= sport_hi && dport_lo <= dp <= dport_hi
+ *     hdr_hit[q][k]     = ((flags & KMPGPU_HDR_ANY_PROTO) || M.proto == proto) && len_lo <= L_k <= len_hi
+ *                         && (dir(M.src_ip, M.dst_ip, M.src_port, M.dst_port)
+ *                             || ((flags & KMPGPU_HDR_BIDIR) && dir(M.dst_ip, M.src_ip, M.dst_port, M.src_port)))
+ *     hdr_pkt_counts[q] = sum over k of hdr_hit[q][k]
+ *     any[k]            = OR over q of hdr_hit[q][k]
+ *     counts[i]         = exactly what kmpgpu_scan returns, as in the sibling calls
+ * Masks are taken literally: /0 is mask 0, a non-contiguous mask is allowed.  An empty payload has metadata and can hit.  Layout as
+ * kmpgpu_scan_packets: W = ceil(n_pkts / 64) words per row, row q of hdr_hits_out starts at hdr_hits_out + q * W; the bits of index
+ * n_pkts and above are 0 in every output word.
+ *
+ * kmpgpu_set_headers copies and uploads the predicates.  They belong to the pattern set current at the call: no patterns set:
+ * KMPGPU_ESTATE; a later kmpgpu_set_patterns / kmpgpu_set_patterns_flags drops them with everything else; kmpgpu_set_relations and
+ * kmpgpu_set_chains keep them (and drop the rules, as they always do).  sport_lo > sport_hi, dport_lo > dport_hi, len_lo > len_hi, an
+ * unknown flag bit, reserved != 0, a NULL array with n_hdr > 0, n_pat + n_rel + n_chains + n_hdr >= 2^31: KMPGPU_EINVAL, and the
+ * predicates and rules set before stay in force.  n_hdr == 0 clears them (the array may be NULL).  EVERY successful call drops the rules:
+ * the rows their terms name have changed.  So the order is patterns, relations, chains, headers, rules.
+ *
+ * Headers as rule terms: predicate q is row n_pat + n_rel + n_chains + q of the hit matrix and term index n_pat + n_rel + n_chains + q of
+ * kmpgpu_set_rules, with or without KMPGPU_RULE_NOT; kmpgpu_scan_rules and kmpgpu_scan_alerts(KMPGPU_ALERT_RULES) run the header kernel
+ * behind the chain kernel and in front of the rules kernel whenever predicates are set (one launch; under kmpgpu_profile_begin it is
+ * recorded in that place).  kmpgpu_scan_alerts has no family of its own for them: the rules family is how header hits reach the list.
+ *
+ * kmpgpu_scan_headers: synchronous, on the context's stream.  The marking pass of kmpgpu_scan_packets, then the header kernel instead of
+ * the pattern-level reduce.  Every output may be NULL: hdr_pkt_counts_out[n_hdr], any_out[W], hdr_hits_out[n_hdr * W], counts_out[n_pat].
+ * Preconditions and errors as kmpgpu_scan_packets; no predicates set: KMPGPU_ESTATE.  Predicates set but no metadata on the context:
+ * KMPGPU_ESTATE ("no packet metadata") from kmpgpu_scan_headers, kmpgpu_scan_rules and kmpgpu_scan_alerts(KMPGPU_ALERT_RULES) alike, with
+ * nothing launched; the context stays usable.
+ * With no predicates set and KMPGPU_OPT_KEEP_META at 0 every output of every other call is bit-identical to what it is without these
+ * calls, with the same launches and device buffers.
+ * Cost (the figures of tools/headers.py go to profiles/headers.txt): n_hdr further rows of the hit matrix,
+ * (n_hdr x W2 + n_hdr) x 8 bytes, zeroed with it, 48 bytes per predicate, 16 bytes of metadata per payload.  The kernel reads 20 bytes
+ * per payload once, whatever n_hdr is, and writes every row in 16-byte pieces. */
+typedef struct kmpgpu_pkt_meta {   /* 16 bytes; kmp_pkt_meta in kmphost.h has the same layout */
+    uint32_t src_ip, dst_ip;       /* host-order integers */
+    uint16_t src_port, dst_port;
+    uint8_t  proto;                /* frame byte 23 */
+    uint8_t  reserved[3];          /* 0 */
+} kmpgpu_pkt_meta;
+#define KMPGPU_HDR_ANY_PROTO 1u
+#define KMPGPU_HDR_BIDIR     2u
+typedef struct kmpgpu_header {
+    uint32_t src_ip, src_mask, dst_ip, dst_mask;
+    uint16_t sport_lo, sport_hi, dport_lo, dport_hi;
+    uint32_t len_lo, len_hi;       /* on L_k, the payload's length in the index (Snort's dsize) */
+    uint8_t  proto, flags;         /* flags: KMPGPU_HDR_* */
+    uint16_t reserved;             /* 0 */
+} kmpgpu_header;
+int  kmpgpu_set_meta(kmpgpu_ctx *ctx, const void *meta /* kmpgpu_pkt_meta[n_pkts] */, uint64_t n_pkts, int on_device);
+int  kmpgpu_meta_download(kmpgpu_ctx *ctx, kmpgpu_pkt_meta *out /* [cap] or NULL */, uint64_t cap, uint64_t *n /* or NULL */);
+int  kmpgpu_set_headers(kmpgpu_ctx *ctx, const kmpgpu_header *h /* [n_hdr] */, uint32_t n_hdr);
+int  kmpgpu_scan_headers(kmpgpu_ctx *ctx, uint64_t *hdr_pkt_counts_out /* [n_hdr] or NULL */, uint64_t *any_out /* [W] or NULL */,
+                         uint64_t *hdr_hits_out /* [n_hdr * W] or NULL */, uint64_t *counts_out /* [n_pat] or NULL: as kmpgpu_scan */,
+                         kmpgpu_timing *t /* or NULL */);
 
 /* The alert list: which payloads hit which rows, as records instead of a bit matrix (the hit rows of kmpgpu_scan_packets and the rows of
  * kmpgpu_scan_rules / _relations / _chains are rows x W x 8 bytes that the caller downloads and walks; the answer is normally a handful of

@@ -59,6 +59,20 @@ void kmp_pcap_close(kmp_pcap *p);
 int kmp_extract_udp(const uint8_t *frame, uint32_t capture_len, uint32_t *payload_off, uint32_t *payload_len);
 int kmp_extract_tcp(const uint8_t *frame, uint32_t capture_len, uint32_t *payload_off, uint32_t *payload_len);
 
+/* The header fields the extractors walk past on their way to the payload (kmpgpu_pkt_meta of include/kmpgpu.h has this layout): with p the
+ * frame, src_ip = p[26]<<24 | p[27]<<16 | p[28]<<8 | p[29] and dst_ip from p[30..33] (host-order integers), the ports from
+ * T = 14 + ((p[14] & 0x0F) << 2) as p[T]<<8 | p[T+1] and p[T+2]<<8 | p[T+3], proto = p[23].  The byte positions are the extractors' own,
+ * quirks included: no EtherType or IP-version test, and in tcp mode nothing has tested p[23].  kmp_extract_meta returns 1 / 0 exactly
+ * where kmp_extract_udp (proto == KMP_PROTO_UDP) / kmp_extract_tcp (KMP_PROTO_TCP) do; for an accepted frame every byte read lies
+ * inside capture_len, for a rejected one *out is not written. */
+typedef struct kmp_pkt_meta {
+    uint32_t src_ip, dst_ip;
+    uint16_t src_port, dst_port;
+    uint8_t  proto;
+    uint8_t  reserved[3];     /* 0 */
+} kmp_pkt_meta;
+int kmp_extract_meta(const uint8_t *frame, uint32_t capture_len, int proto, kmp_pkt_meta *out);
+
 /* ---- pattern list -------------------------------------------------------------------------
  * Replaces the fscanf("%s") loader of serial.c:54-87 / openmp_data.c:57-90: whitespace-separated
  * tokens in file order, duplicates kept. */
@@ -99,6 +113,12 @@ int  kmp_rules_parse_rel(const char *path, uint32_t n_patterns, uint32_t n_relat
  * where "c3" is no term at all. */
 int  kmp_rules_parse_terms(const char *path, uint32_t n_patterns, uint32_t n_relations, uint32_t n_chains, kmp_rules *out,
                            char errbuf[KMP_RULES_ERRBUF]);
+/* ... and with header predicates as terms (kmpgpu_set_headers): "h<q>" / "!h<q>", q < n_headers a decimal predicate index (the order of the
+ * lines of kmp_headers_parse), is encoded as n_patterns + n_relations + n_chains + q.  A predicate index >= n_headers: KMPHOST_EINVAL,
+ * "line N: ".  n_patterns + n_relations + n_chains + n_headers >= 2^31: KMPHOST_EINVAL before the file is opened.  kmp_rules_parse_terms
+ * is this with n_headers = 0, where "h3" is no term at all. */
+int  kmp_rules_parse_hdr(const char *path, uint32_t n_patterns, uint32_t n_relations, uint32_t n_chains, uint32_t n_headers, kmp_rules *out,
+                         char errbuf[KMP_RULES_ERRBUF]);
 void kmp_rules_free(kmp_rules *r);
 
 /* ---- relations -------------------------------------------------------------------------------
@@ -142,6 +162,33 @@ typedef struct kmp_chains {
 int  kmp_chains_parse(const char *path, uint32_t n_patterns, kmp_chains *out, char errbuf[KMP_CHAINS_ERRBUF]);
 void kmp_chains_free(kmp_chains *c);
 
+/* ---- header predicates -----------------------------------------------------------------------
+ * Not in the reference: the predicates of kmpgpu_set_headers (include/kmpgpu.h) from a text file.  One predicate per line,
+ *     <proto> <src> <sport> <dir> <dst> <dport> [<len>]
+ * six or seven fields separated by blanks.  <proto>: udp (17), tcp (6), ip or any (KMP_HDR_ANY_PROTO), or decimal 0..255.  <src>, <dst>:
+ * any (mask 0), a.b.c.d (mask /32) or a.b.c.d/n with n = 0..32.  <sport>, <dport> (0..65535) and <len> (0..4294967295, on the payload's
+ * length; absent: any): any, n, lo:hi, lo: or :hi.  <dir>: -> or <> (KMP_HDR_BIDIR: the predicate also holds with source and destination
+ * swapped).  Blank lines and lines whose first non-blank character is '#' are skipped; predicate index = order of the lines.  hdr is
+ * what kmpgpu_set_headers takes (kmp_header has the layout of kmpgpu_header).
+ * KMPHOST_EIO: the file cannot be opened; KMPHOST_EINVAL: fewer than six or more than seven fields, a field of none of its forms, a
+ * number out of its range, lo > hi -- errbuf then starts with "line N: " (N counts every line of the file, from 1). */
+#define KMP_HEADERS_ERRBUF 256
+#define KMP_HDR_ANY_PROTO  1u
+#define KMP_HDR_BIDIR      2u
+typedef struct kmp_header {
+    uint32_t src_ip, src_mask, dst_ip, dst_mask;
+    uint16_t sport_lo, sport_hi, dport_lo, dport_hi;
+    uint32_t len_lo, len_hi;
+    uint8_t  proto, flags;
+    uint16_t reserved;        /* 0 */
+} kmp_header;
+typedef struct kmp_headers {
+    uint32_t    n;      /* number of predicates                          */
+    kmp_header *hdr;    /* [n]                                           */
+} kmp_headers;
+int  kmp_headers_parse(const char *path, kmp_headers *out, char errbuf[KMP_HEADERS_ERRBUF]);
+void kmp_headers_free(kmp_headers *h);
+
 /* ---- offset windows --------------------------------------------------------------------------
  * Not in the reference: the windows of kmpgpu_set_windows (include/kmpgpu.h) from a text file.  One window per line,
  *     <pattern index> <first> <last>
@@ -180,6 +227,10 @@ typedef struct kmp_arena {
  * caplen (openmp_data.c:116,131; equals serial.c's header->len whenever caplen == len). */
 int  kmp_arena_from_pcap(const char *path, int proto, kmp_alloc_fn alloc_fn, kmp_free_fn free_fn,
                          kmp_arena *out, char errbuf[KMP_PCAP_ERRBUF]);
+/* The identical arena, and beside it the accepted frames' header fields in payload order (kmp_extract_meta): *meta_out holds
+ * out->n_pkts records, comes from malloc() and is released with free().  kmp_arena's layout is the same either way. */
+int  kmp_arena_from_pcap_meta(const char *path, int proto, kmp_alloc_fn alloc_fn, kmp_free_fn free_fn,
+                              kmp_arena *out, char errbuf[KMP_PCAP_ERRBUF], kmp_pkt_meta **meta_out);
 /* Build an arena from caller-supplied payloads (tests, synthetic inputs). */
 int  kmp_arena_from_payloads(const uint8_t *const *payloads, const uint32_t *lens, uint64_t n,
                              kmp_alloc_fn alloc_fn, kmp_free_fn free_fn, kmp_arena *out);

@@ -26,6 +26,9 @@ KMP_RULES_ERRBUF = 256
 KMP_WINDOWS_ERRBUF = 256
 KMP_RELATIONS_ERRBUF = 256
 KMP_CHAINS_ERRBUF = 256
+KMP_HEADERS_ERRBUF = 256
+HDR_ANY_PROTO, HDR_BIDIR = 1, 2   # KMPGPU_HDR_* / KMP_HDR_*: flags of a header predicate
+HDR_TILE = 128             # KMP_HDR_TILE (csrc/kmp_launch.h): predicates the header kernel stages at a time
 CHAIN_MAX = 8              # KMPGPU_CHAIN_MAX / KMP_CHAIN_MAX: contents of one chain
 REL_NO_MIN = -(1 << 31)    # kmpgpu_relation.dmin == INT32_MIN: no lower bound
 REL_NO_MAX = (1 << 31) - 1  # kmpgpu_relation.dmax == INT32_MAX: no upper bound
@@ -92,6 +95,24 @@ class Chains(C.Structure):
     _fields_ = [("n", C.c_uint32), ("off", u32p), ("links", C.POINTER(ChainLink))]
 
 
+class PktMeta(C.Structure):
+    """kmpgpu_pkt_meta (include/kmpgpu.h) = kmp_pkt_meta (include/kmphost.h)."""
+    _fields_ = [("src_ip", C.c_uint32), ("dst_ip", C.c_uint32), ("src_port", C.c_uint16), ("dst_port", C.c_uint16),
+                ("proto", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
+class Header(C.Structure):
+    """kmpgpu_header (include/kmpgpu.h) = kmp_header (include/kmphost.h)."""
+    _fields_ = [("src_ip", C.c_uint32), ("src_mask", C.c_uint32), ("dst_ip", C.c_uint32), ("dst_mask", C.c_uint32),
+                ("sport_lo", C.c_uint16), ("sport_hi", C.c_uint16), ("dport_lo", C.c_uint16), ("dport_hi", C.c_uint16),
+                ("len_lo", C.c_uint32), ("len_hi", C.c_uint32), ("proto", C.c_uint8), ("flags", C.c_uint8), ("reserved", C.c_uint16)]
+
+
+class Headers(C.Structure):
+    """kmp_headers (include/kmphost.h)."""
+    _fields_ = [("n", C.c_uint32), ("hdr", C.POINTER(Header))]
+
+
 class Arena(C.Structure):
     """kmp_arena (include/kmphost.h)."""
     _fields_ = [
@@ -130,13 +151,17 @@ HOST_API = {
     "kmp_pcap_close": (None, [C.c_void_p]),
     "kmp_extract_udp": (C.c_int, [u8p, C.c_uint32, u32p, u32p]),
     "kmp_extract_tcp": (C.c_int, [u8p, C.c_uint32, u32p, u32p]),
+    "kmp_extract_meta": (C.c_int, [u8p, C.c_uint32, C.c_int, C.POINTER(PktMeta)]),
     "kmp_patterns_load": (C.c_int, [C.c_char_p, C.POINTER(Patterns)]),
     "kmp_patterns_parse": (C.c_int, [u8p, C.c_size_t, C.POINTER(Patterns)]),
     "kmp_patterns_free": (None, [C.POINTER(Patterns)]),
     "kmp_rules_parse": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(Rules), C.c_char_p]),
     "kmp_rules_parse_rel": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(Rules), C.c_char_p]),
     "kmp_rules_parse_terms": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Rules), C.c_char_p]),
+    "kmp_rules_parse_hdr": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Rules), C.c_char_p]),
     "kmp_rules_free": (None, [C.POINTER(Rules)]),
+    "kmp_headers_parse": (C.c_int, [C.c_char_p, C.POINTER(Headers), C.c_char_p]),
+    "kmp_headers_free": (None, [C.POINTER(Headers)]),
     "kmp_chains_parse": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(Chains), C.c_char_p]),
     "kmp_chains_free": (None, [C.POINTER(Chains)]),
     "kmp_relations_parse": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(Relations), C.c_char_p]),
@@ -144,6 +169,7 @@ HOST_API = {
     "kmp_windows_parse": (C.c_int, [C.c_char_p, C.c_uint32, u32p, u32p, C.c_char_p]),
     "kmp_failure_table": (None, [u8p, C.c_uint32, i32p]),
     "kmp_arena_from_pcap": (C.c_int, [C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Arena), C.c_char_p]),
+    "kmp_arena_from_pcap_meta": (C.c_int, [C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Arena), C.c_char_p, C.POINTER(C.POINTER(PktMeta))]),
     "kmp_arena_from_payloads": (C.c_int, [C.POINTER(u8p), u32p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(Arena)]),
     "kmp_arena_layout": (C.c_uint64, [u32p, C.c_uint32, C.c_uint64, C.c_uint32, u64p, u32p]),
     "kmp_arena_free": (None, [C.POINTER(Arena)]),
@@ -203,6 +229,10 @@ GPU_API = {
     "kmpgpu_scan_relations": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
     "kmpgpu_set_chains": (C.c_int, [C.c_void_p, u32p, C.POINTER(ChainLink), C.c_uint32]),
     "kmpgpu_scan_chains": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
+    "kmpgpu_set_meta": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]),
+    "kmpgpu_meta_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, u64p]),
+    "kmpgpu_set_headers": (C.c_int, [C.c_void_p, C.POINTER(Header), C.c_uint32]),
+    "kmpgpu_scan_headers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
     "kmpgpu_scan_alerts": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, u64p, u64p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
     "kmpgpu_alerts_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "kmpgpu_load_selected": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, u64p]),

@@ -38,6 +38,14 @@
  * whose file may then name chain q as "c<q>" / "!c<q>" (kmp_rules_parse_terms).  A chains file that does not parse, or the variable
  * without the other two: message on stderr, exit 1, before any GPU work.  stdout is what it is without the variable.
  *
+ * KMPGPU_HEADERS_FILE=<headers>, together with KMPGPU_RULES_FILE and KMPGPU_ALERTS_FILE, with or without the relations and chains files:
+ * header predicates on addresses, ports, protocol and payload length (kmpgpu_set_headers; the file format is kmp_headers_parse's, kmphost.h:
+ * "<proto> <src> <sport> <dir> <dst> <dport> [<len>]" per line), set on every shard's context behind the chains and before the rules, whose
+ * file may then name predicate q as "h<q>" / "!h<q>" (kmp_rules_parse_hdr).  The payloads' header fields come from the host extraction
+ * (kmp_arena_from_pcap_meta, kmpgpu_set_meta of the shard's slice) or, with KMPGPU_DEVICE_EXTRACT=1, from the device's
+ * (KMPGPU_OPT_KEEP_META); both routes write the same files.  A headers file that does not parse, or the variable without the other two:
+ * message on stderr, exit 1, before any GPU work.  stdout is what it is without the variable.
+ *
  * KMPGPU_WINDOWS_FILE=<windows>: per-pattern offset windows (kmpgpu_set_windows; the file format is kmp_windows_parse's, kmphost.h:
  * "<pattern index> <first> <last>" per line, '*' for no upper bound) on every shard's context.  They take effect on the files written
  * for KMPGPU_OFFSETS_FILE, KMPGPU_PACKETS_FILE and KMPGPU_RULES_FILE + KMPGPU_ALERTS_FILE: only the matches that start inside their
@@ -93,6 +101,7 @@ typedef struct cli_options {
     uint32_t *win_first, *win_last;         /* KMPGPU_WINDOWS_FILE (NULL: none) */
     kmp_relations relations;                /* KMPGPU_RELATIONS_FILE (n == 0: none) */
     kmp_chains chains;                      /* KMPGPU_CHAINS_FILE (n == 0: none) */
+    kmp_headers headers;                    /* KMPGPU_HEADERS_FILE (n == 0: none) */
     kmp_rules rules;                        /* KMPGPU_RULES_FILE, set before the first output that needs them */
 } cli_options;
 
@@ -100,6 +109,7 @@ typedef struct cli_options {
 typedef struct capture {
     kmp_arena arena;
     kmp_frames frames;
+    kmp_pkt_meta *meta;                     /* beside the arena where header predicates are set: its payloads' header fields */
     double t_load0, t_loaded, t_warm;
 } capture;
 
@@ -182,16 +192,16 @@ static void load_options(int argc, char *argv[], cli_options *opt)
     opt->rules_path = env_path("KMPGPU_RULES_FILE");
     opt->alerts_path = env_path("KMPGPU_ALERTS_FILE");
     opt->export_path = env_path("KMPGPU_EXPORT_FILE");
-    const char *relations_path = env_path("KMPGPU_RELATIONS_FILE"), *chains_path = env_path("KMPGPU_CHAINS_FILE"), *windows_path = env_path("KMPGPU_WINDOWS_FILE");
+    const char *relations_path = env_path("KMPGPU_RELATIONS_FILE"), *chains_path = env_path("KMPGPU_CHAINS_FILE"), *headers_path = env_path("KMPGPU_HEADERS_FILE"), *windows_path = env_path("KMPGPU_WINDOWS_FILE");
 
     /* the content rules (an export takes the rules' any[] without an alerts file) */
     if ((opt->rules_path != NULL) != (opt->alerts_path != NULL) && !(opt->rules_path && opt->export_path)) {
         fprintf(stderr, "KMPGPU_RULES_FILE and KMPGPU_ALERTS_FILE go together: %s is not set\n", opt->rules_path ? "KMPGPU_ALERTS_FILE" : "KMPGPU_RULES_FILE");
         exit(1);
     }
-    /* the relations and the chains, which the rules may name */
+    /* the relations, the chains and the header predicates, which the rules may name */
     char err[256];
-    _Static_assert(sizeof err >= KMP_RELATIONS_ERRBUF && sizeof err >= KMP_CHAINS_ERRBUF && sizeof err >= KMP_RULES_ERRBUF && sizeof err >= KMP_WINDOWS_ERRBUF,
+    _Static_assert(sizeof err >= KMP_RELATIONS_ERRBUF && sizeof err >= KMP_CHAINS_ERRBUF && sizeof err >= KMP_RULES_ERRBUF && sizeof err >= KMP_WINDOWS_ERRBUF && sizeof err >= KMP_HEADERS_ERRBUF,
                    "room for every parser's message");
     if (relations_path) {
         needs_rules_and_alerts("KMPGPU_RELATIONS_FILE", opt);
@@ -207,7 +217,14 @@ static void load_options(int argc, char *argv[], cli_options *opt)
             exit(1);
         }
     }
-    if (opt->rules_path && kmp_rules_parse_terms(opt->rules_path, n, opt->relations.n, opt->chains.n, &opt->rules, err)) {
+    if (headers_path) {
+        needs_rules_and_alerts("KMPGPU_HEADERS_FILE", opt);
+        if (kmp_headers_parse(headers_path, &opt->headers, err)) {
+            fprintf(stderr, "error reading headers file %s: %s\n", headers_path, err);
+            exit(1);
+        }
+    }
+    if (opt->rules_path && kmp_rules_parse_hdr(opt->rules_path, n, opt->relations.n, opt->chains.n, opt->headers.n, &opt->rules, err)) {
         fprintf(stderr, "error reading rules file %s: %s\n", opt->rules_path, err);
         exit(1);
     }
@@ -239,6 +256,7 @@ static void free_options(cli_options *opt)
     kmp_rules_free(&opt->rules);
     kmp_relations_free(&opt->relations);
     kmp_chains_free(&opt->chains);
+    kmp_headers_free(&opt->headers);
     free(opt->win_first); free(opt->win_last);
 }
 
@@ -267,6 +285,8 @@ static void load_capture(const cli_options *opt, capture *cap)
      * MI355X hosts (profiles/r01_h2d_probe.txt).  Pinned buffers pay off where they are reused (bin/openmp_task). */
     if (opt->device_extract)
         rc = kmp_frames_from_pcap(opt->pcap_path, NULL, NULL, &cap->frames, errbuf);
+    else if (opt->headers.n)                                                /* the same arena, and the header fields the predicates read */
+        rc = kmp_arena_from_pcap_meta(opt->pcap_path, opt->proto, NULL, NULL, &cap->arena, errbuf, &cap->meta);
     else
         rc = kmp_arena_from_pcap(opt->pcap_path, opt->proto, NULL, NULL, &cap->arena, errbuf);                /* serial.c:91-141 */
     cap->t_loaded = now_s();
@@ -300,6 +320,9 @@ static void *shard_load(void *arg)
     if (o->relations.n && kmpgpu_set_relations(j->ctx, (const kmpgpu_relation *)o->relations.rel, o->relations.n)) return shard_fail(j, "kmpgpu_set_relations");
     _Static_assert(sizeof(kmp_chain_link) == sizeof(kmpgpu_chain_link), "kmp_chain_link has the layout of kmpgpu_chain_link");
     if (o->chains.n && kmpgpu_set_chains(j->ctx, o->chains.off, (const kmpgpu_chain_link *)o->chains.links, o->chains.n)) return shard_fail(j, "kmpgpu_set_chains");
+    _Static_assert(sizeof(kmp_header) == sizeof(kmpgpu_header) && sizeof(kmp_pkt_meta) == sizeof(kmpgpu_pkt_meta), "kmp_header, kmp_pkt_meta have the layouts of kmpgpu.h");
+    if (o->headers.n && kmpgpu_set_headers(j->ctx, (const kmpgpu_header *)o->headers.hdr, o->headers.n)) return shard_fail(j, "kmpgpu_set_headers");
+    if (o->headers.n && o->device_extract && kmpgpu_set_option(j->ctx, KMPGPU_OPT_KEEP_META, 1)) return shard_fail(j, "kmpgpu_set_option");
     if (o->device_extract) {
         /* only the bytes this shard's frames span are uploaded (kmpgpu_load_frames) */
         const kmp_frames *f = &j->cap->frames;
@@ -315,6 +338,7 @@ static void *shard_load(void *arg)
         for (uint64_t k = 0; k < j->cnt; k++) j->reb[k] = a->off[j->lo + k] - b0;
         /* slots are contiguous and at least 16 bytes each, so [b0, b1) holds the whole shard */
         if (kmpgpu_load_arena(j->ctx, a->bytes + b0, b1 - b0, j->reb, a->len + j->lo, j->cnt)) return shard_fail(j, "kmpgpu_load_arena");
+        if (j->cap->meta && kmpgpu_set_meta(j->ctx, j->cap->meta + j->lo, j->cnt, 0)) return shard_fail(j, "kmpgpu_set_meta");
     }
     kmpgpu_arena_info(j->ctx, &j->n_payloads, &j->payload_bytes);
     if (kmpgpu_last_timing(j->ctx, &j->t)) return shard_fail(j, "kmpgpu_last_timing");
@@ -512,6 +536,7 @@ int main(int argc, char *argv[])
     free(run.ctxs); free(run.job); free(run.own); free(run.counts);
     kmp_arena_free(&cap.arena);
     kmp_frames_free(&cap.frames);
+    free(cap.meta);
     free_options(&opt);
     return 0;
 }

@@ -340,6 +340,22 @@ int kmp_extract_tcp(const uint8_t *f, uint32_t cl, uint32_t *poff, uint32_t *ple
     return 1;
 }
 
+/* The header fields both extractors walk past, for a frame the one of `proto` accepts: every byte read lies inside the captured
+ * bytes then (udp: cl >= 34 and cl - 14 - ihl >= 8; tcp: ihl >= 20 and cl >= 14 + ihl + 20). */
+int kmp_extract_meta(const uint8_t *f, uint32_t cl, int proto, kmp_pkt_meta *out)
+{
+    uint32_t o, l;
+    if (!((proto == KMP_PROTO_TCP) ? kmp_extract_tcp(f, cl, &o, &l) : kmp_extract_udp(f, cl, &o, &l))) return 0;
+    const uint32_t at = 14u + ((uint32_t)(f[14] & 0x0Fu) << 2);
+    memset(out, 0, sizeof *out);
+    out->src_ip = (uint32_t)f[26] << 24 | (uint32_t)f[27] << 16 | (uint32_t)f[28] << 8 | f[29];
+    out->dst_ip = (uint32_t)f[30] << 24 | (uint32_t)f[31] << 16 | (uint32_t)f[32] << 8 | f[33];
+    out->src_port = (uint16_t)((uint32_t)f[at] << 8 | f[at + 1u]);
+    out->dst_port = (uint16_t)((uint32_t)f[at + 2u] << 8 | f[at + 3u]);
+    out->proto = f[23];
+    return 1;
+}
+
 /* ============================ pattern list ============================================== */
 
 static int is_c_space(uint8_t b) { return b == ' ' || (b >= '\t' && b <= '\r'); }
@@ -426,14 +442,14 @@ void kmp_patterns_free(kmp_patterns *p)
 
 /* ============================ text files, line by line ================================== */
 
-/* What the rules, relations, chains and windows files share: one entry per line, blank lines and lines whose first non-blank character
+/* What the rules, relations, chains, windows and headers files share: one entry per line, blank lines and lines whose first non-blank character
  * is '#' skipped.  text_lines opens path and hands every other line to fn -- p at its first non-blank character, end behind its last
  * one (the newline included), lineno counting every line of the file from 1 -- until fn returns something other than KMPHOST_OK,
  * which text_lines then returns.  The message of a file that cannot be opened (KMPHOST_EIO) and the one that goes with
  * KMPHOST_ENOMEM are written here. */
 #define KMP_LINE_ERRBUF 256
 _Static_assert(KMP_RULES_ERRBUF == KMP_LINE_ERRBUF && KMP_RELATIONS_ERRBUF == KMP_LINE_ERRBUF && KMP_CHAINS_ERRBUF == KMP_LINE_ERRBUF &&
-               KMP_WINDOWS_ERRBUF == KMP_LINE_ERRBUF, "the four formats' error buffers have one size");
+               KMP_WINDOWS_ERRBUF == KMP_LINE_ERRBUF && KMP_HEADERS_ERRBUF == KMP_LINE_ERRBUF, "the five formats' error buffers have one size");
 typedef int (*line_fn)(void *ctx, const char *p, const char *end, size_t lineno, char *errbuf);
 
 static int out_of_memory(char *errbuf)
@@ -520,6 +536,7 @@ typedef struct rules_ctx {
     uint32_t n_patterns, n_relations, n_chains;
     kmp_rules *out;
     size_t n_off, cap_off, n_terms, cap_terms;
+    uint32_t n_headers;
 } rules_ctx;
 
 static int rules_line(void *ctx, const char *p, const char *end, size_t lineno, char *errbuf)
@@ -534,16 +551,22 @@ static int rules_line(void *ctx, const char *p, const char *end, size_t lineno, 
         const int is_rel = c->n_relations && p < end && *p == 'r';
         /* c<q>: chain q, in the same way */
         const int is_chain = c->n_chains && p < end && *p == 'c';
-        if (is_rel || is_chain) p++;
+        /* h<q>: header predicate q, in the same way */
+        const int is_hdr = c->n_headers && p < end && *p == 'h';
+        if (is_rel || is_chain || is_hdr) p++;
         const char *digits = p;
         while (p < end && *p >= '0' && *p <= '9') { if (v < (1ull << 40)) v = v * 10 + (uint64_t)(*p - '0'); p++; }
         const char *stop = p;
         while (stop < end && !is_c_space((uint8_t)*stop)) stop++;   /* the whole token, for the message */
-        if (p == digits && neg && stop == p && !is_rel && !is_chain) return line_error(errbuf, lineno, "'!' without a pattern index");
+        if (p == digits && neg && stop == p && !is_rel && !is_chain && !is_hdr) return line_error(errbuf, lineno, "'!' without a pattern index");
         if (p == digits || stop != p)
-            return line_error(errbuf, lineno, "'%.*s' is not a pattern index%s%s", (int)(stop - tok > 64 ? 64 : stop - tok), tok,
-                              c->n_relations ? " or r<relation index>" : "", c->n_chains ? " or c<chain index>" : "");
-        if (is_chain) {
+            return line_error(errbuf, lineno, "'%.*s' is not a pattern index%s%s%s", (int)(stop - tok > 64 ? 64 : stop - tok), tok,
+                              c->n_relations ? " or r<relation index>" : "", c->n_chains ? " or c<chain index>" : "",
+                              c->n_headers ? " or h<header index>" : "");
+        if (is_hdr) {
+            if (v >= c->n_headers) return line_error(errbuf, lineno, "header index %llu, but there are %u header predicates", (unsigned long long)v, c->n_headers);
+            row = c->n_patterns + c->n_relations + c->n_chains + (uint32_t)v;
+        } else if (is_chain) {
             if (v >= c->n_chains) return line_error(errbuf, lineno, "chain index %llu, but there are %u chains", (unsigned long long)v, c->n_chains);
             row = c->n_patterns + c->n_relations + (uint32_t)v;
         } else if (is_rel) {
@@ -572,17 +595,24 @@ int kmp_rules_parse_rel(const char *path, uint32_t n_patterns, uint32_t n_relati
 
 int kmp_rules_parse_terms(const char *path, uint32_t n_patterns, uint32_t n_relations, uint32_t n_chains, kmp_rules *out, char errbuf[KMP_RULES_ERRBUF])
 {
+    return kmp_rules_parse_hdr(path, n_patterns, n_relations, n_chains, 0, out, errbuf);
+}
+
+int kmp_rules_parse_hdr(const char *path, uint32_t n_patterns, uint32_t n_relations, uint32_t n_chains, uint32_t n_headers, kmp_rules *out,
+                        char errbuf[KMP_RULES_ERRBUF])
+{
     memset(out, 0, sizeof *out);
     if (errbuf) errbuf[0] = 0;
-    /* a term is a row below 2^31: bit 31 is KMP_RULE_NOT (kmpgpu_set_relations and kmpgpu_set_chains refuse such a set too) */
-    if ((uint64_t)n_patterns + n_relations + n_chains >= (1ull << 31)) {
+    /* a term is a row below 2^31: bit 31 is KMP_RULE_NOT (kmpgpu_set_relations, kmpgpu_set_chains and kmpgpu_set_headers refuse such a set too) */
+    if ((uint64_t)n_patterns + n_relations + n_chains + n_headers >= (1ull << 31)) {
         if (errbuf) {
-            if (n_chains) snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations + %u chains do not fit the 2^31 rows a term can name", n_patterns, n_relations, n_chains);
+            if (n_headers) snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations + %u chains + %u header predicates do not fit the 2^31 rows a term can name", n_patterns, n_relations, n_chains, n_headers);
+            else if (n_chains) snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations + %u chains do not fit the 2^31 rows a term can name", n_patterns, n_relations, n_chains);
             else snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations do not fit the 2^31 rows a term can name", n_patterns, n_relations);
         }
         return KMPHOST_EINVAL;
     }
-    rules_ctx c = {n_patterns, n_relations, n_chains, out, 0, 0, 0, 0};
+    rules_ctx c = {n_patterns, n_relations, n_chains, out, 0, 0, 0, 0, n_headers};
     int rc = rules_push(&out->off, &c.n_off, &c.cap_off, 0) ? out_of_memory(errbuf) : text_lines(path, rules_line, &c, errbuf);
     if (rc) {
         kmp_rules_free(out);
@@ -767,6 +797,149 @@ int kmp_windows_parse(const char *path, uint32_t n_patterns, uint32_t *first_out
     return rc;
 }
 
+/* ============================ header predicates ========================================= */
+
+typedef struct headers_ctx {
+    kmp_headers *out;
+    size_t n, cap;
+} headers_ctx;
+
+/* the next blank-separated field of a line: 0 at its end */
+static int next_field(const char **pp, const char *end, const char **tok, int *len)
+{
+    const char *p = *pp;
+    while (p < end && is_c_space((uint8_t)*p)) p++;
+    if (p == end) { *pp = p; return 0; }
+    *tok = p;
+    while (p < end && !is_c_space((uint8_t)*p)) p++;
+    *len = (int)(p - *tok);
+    *pp = p;
+    return 1;
+}
+
+static int field_is(const char *tok, int len, const char *word) { return (int)strlen(word) == len && memcmp(tok, word, (size_t)len) == 0; }
+
+/* decimal digits only, at least one, value <= max */
+static int plain_number(const char *p, const char *end, uint64_t max, uint64_t *out)
+{
+    if (p == end) return 0;
+    uint64_t v = 0;
+    for (; p < end; p++) {
+        if (*p < '0' || *p > '9') return 0;
+        v = v * 10 + (uint64_t)(*p - '0');
+        if (v > max) return 0;
+    }
+    *out = v;
+    return 1;
+}
+
+/* any | n | lo:hi | lo: | :hi over 0..max; 1: a range, 0: not one, -1: lo above hi */
+static int range_field(const char *tok, int len, uint64_t max, uint64_t *lo, uint64_t *hi)
+{
+    *lo = 0; *hi = max;
+    if (field_is(tok, len, "any")) return 1;
+    const char *end = tok + len, *colon = (const char *)memchr(tok, ':', (size_t)len);
+    if (!colon) {
+        if (!plain_number(tok, end, max, lo)) return 0;
+        *hi = *lo;
+        return 1;
+    }
+    if (len == 1) return 0;                                             /* a lone ':' */
+    if (colon > tok && !plain_number(tok, colon, max, lo)) return 0;
+    if (colon + 1 < end && !plain_number(colon + 1, end, max, hi)) return 0;
+    return *lo > *hi ? -1 : 1;
+}
+
+/* any | a.b.c.d | a.b.c.d/n */
+static int address_field(const char *tok, int len, uint32_t *ip, uint32_t *mask)
+{
+    *ip = 0; *mask = 0;
+    if (field_is(tok, len, "any")) return 1;
+    const char *end = tok + len, *slash = (const char *)memchr(tok, '/', (size_t)len), *p = tok;
+    const char *addr_end = slash ? slash : end;
+    uint32_t a = 0;
+    for (int k = 0; k < 4; k++) {
+        const char *dot = k < 3 ? (const char *)memchr(p, '.', (size_t)(addr_end - p)) : addr_end;
+        uint64_t v;
+        if (!dot || !plain_number(p, dot, 255, &v)) return 0;
+        a = a << 8 | (uint32_t)v;
+        p = dot + 1;
+    }
+    uint64_t bits = 32;
+    if (slash && !plain_number(slash + 1, end, 32, &bits)) return 0;
+    *ip = a;
+    *mask = bits ? 0xFFFFFFFFu << (32 - bits) : 0u;
+    return 1;
+}
+
+static int headers_line(void *ctx, const char *p, const char *end, size_t lineno, char *errbuf)
+{
+    headers_ctx *c = (headers_ctx *)ctx;
+    static const char *const form = "<proto> <src> <sport> <dir> <dst> <dport> [<len>]";
+    const char *tok[8];
+    int len[8], nf = 0;
+    while (nf < 8 && next_field(&p, end, &tok[nf], &len[nf])) nf++;
+    if (nf < 6) return line_error(errbuf, lineno, "%d of the six or seven fields %s", nf, form);
+    if (nf > 7) return line_error(errbuf, lineno, "more than the seven fields %s", form);
+#define FIELD(k) (len[k] > 64 ? 64 : len[k]), tok[k]
+    kmp_header h;
+    memset(&h, 0, sizeof h);
+    uint64_t lo, hi;
+    if (field_is(tok[0], len[0], "udp")) h.proto = 17;
+    else if (field_is(tok[0], len[0], "tcp")) h.proto = 6;
+    else if (field_is(tok[0], len[0], "ip") || field_is(tok[0], len[0], "any")) h.flags |= KMP_HDR_ANY_PROTO;
+    else if (plain_number(tok[0], tok[0] + len[0], 255, &lo)) h.proto = (uint8_t)lo;
+    else return line_error(errbuf, lineno, "'%.*s' is not a protocol (udp, tcp, ip, any or 0..255)", FIELD(0));
+    if (!address_field(tok[1], len[1], &h.src_ip, &h.src_mask)) return line_error(errbuf, lineno, "'%.*s' is not an address (any, a.b.c.d or a.b.c.d/0..32)", FIELD(1));
+    if (!address_field(tok[4], len[4], &h.dst_ip, &h.dst_mask)) return line_error(errbuf, lineno, "'%.*s' is not an address (any, a.b.c.d or a.b.c.d/0..32)", FIELD(4));
+    if (field_is(tok[3], len[3], "<>")) h.flags |= KMP_HDR_BIDIR;
+    else if (!field_is(tok[3], len[3], "->")) return line_error(errbuf, lineno, "'%.*s' is not a direction (-> or <>)", FIELD(3));
+    for (int k = 2; k <= 5; k += 3) {
+        const int r = range_field(tok[k], len[k], 65535, &lo, &hi);
+        if (r == 0) return line_error(errbuf, lineno, "'%.*s' is not a port range (any, n, lo:hi, lo: or :hi within 0..65535)", FIELD(k));
+        if (r < 0) return line_error(errbuf, lineno, "'%.*s': port %llu lies above %llu", FIELD(k), (unsigned long long)lo, (unsigned long long)hi);
+        if (k == 2) { h.sport_lo = (uint16_t)lo; h.sport_hi = (uint16_t)hi; } else { h.dport_lo = (uint16_t)lo; h.dport_hi = (uint16_t)hi; }
+    }
+    h.len_lo = 0; h.len_hi = UINT32_MAX;
+    if (nf == 7) {
+        const int r = range_field(tok[6], len[6], UINT32_MAX, &lo, &hi);
+        if (r == 0) return line_error(errbuf, lineno, "'%.*s' is not a length range (any, n, lo:hi, lo: or :hi within 0..4294967295)", FIELD(6));
+        if (r < 0) return line_error(errbuf, lineno, "'%.*s': length %llu lies above %llu", FIELD(6), (unsigned long long)lo, (unsigned long long)hi);
+        h.len_lo = (uint32_t)lo; h.len_hi = (uint32_t)hi;
+    }
+#undef FIELD
+    if (c->n == c->cap) {
+        const size_t nc = c->cap ? c->cap * 2 : 64;
+        kmp_header *nv = (kmp_header *)realloc(c->out->hdr, nc * sizeof *nv);
+        if (!nv) return KMPHOST_ENOMEM;
+        c->out->hdr = nv; c->cap = nc;
+    }
+    c->out->hdr[c->n++] = h;
+    return KMPHOST_OK;
+}
+
+int kmp_headers_parse(const char *path, kmp_headers *out, char errbuf[KMP_HEADERS_ERRBUF])
+{
+    memset(out, 0, sizeof *out);
+    if (errbuf) errbuf[0] = 0;
+    headers_ctx c = {out, 0, 0};
+    int rc = text_lines(path, headers_line, &c, errbuf);
+    if (!rc && c.n > 0x7FFFFFFFull) rc = KMPHOST_EINVAL;
+    if (rc) {
+        kmp_headers_free(out);
+        return rc;
+    }
+    out->n = (uint32_t)c.n;
+    return KMPHOST_OK;
+}
+
+void kmp_headers_free(kmp_headers *h)
+{
+    if (!h) return;
+    free(h->hdr);
+    memset(h, 0, sizeof *h);
+}
+
 /* serial.c:217-238 */
 void kmp_failure_table(const uint8_t *pat, uint32_t m, int32_t *prefix)
 {
@@ -876,7 +1049,15 @@ static int index_file(const kmp_view *v, kmp_index *ix, char errbuf[KMP_PCAP_ERR
 int kmp_arena_from_pcap(const char *path, int proto, kmp_alloc_fn alloc_fn, kmp_free_fn free_fn,
                         kmp_arena *out, char errbuf[KMP_PCAP_ERRBUF])
 {
+    return kmp_arena_from_pcap_meta(path, proto, alloc_fn, free_fn, out, errbuf, NULL);
+}
+
+/* ... and with meta_out the accepted frames' header fields beside the index (kmp_extract_meta), from malloc */
+int kmp_arena_from_pcap_meta(const char *path, int proto, kmp_alloc_fn alloc_fn, kmp_free_fn free_fn,
+                             kmp_arena *out, char errbuf[KMP_PCAP_ERRBUF], kmp_pkt_meta **meta_out)
+{
     memset(out, 0, sizeof *out);
+    if (meta_out) *meta_out = NULL;
     kmp_view v;
     kmp_index ix;
     int rc = view_open(path, &v, errbuf);
@@ -907,11 +1088,17 @@ int kmp_arena_from_pcap(const char *path, int proto, kmp_alloc_fn alloc_fn, kmp_
             n++;
         }
         rc = arena_alloc(out, pos + KMP_ARENA_SLACK, n, alloc_fn, free_fn, 0);
+        if (!rc && meta_out) {
+            *meta_out = (kmp_pkt_meta *)malloc(sizeof(kmp_pkt_meta) * (size_t)(n ? n : 1));
+            if (!*meta_out) { kmp_arena_free(out); rc = KMPHOST_ENOMEM; }
+        }
         if (!rc) {
             uint64_t k = 0;
             for (int64_t f = 0; f < nf; f++) {
                 if (pl[f] == UINT32_MAX) continue;
-                out->off[k] = dst[f]; out->len[k] = pl[f]; k++;
+                out->off[k] = dst[f]; out->len[k] = pl[f];
+                if (meta_out) (void)kmp_extract_meta(v.base + ix.off[f], ix.caplen[f], proto, *meta_out + k);
+                k++;
             }
             /* payload copies (serial.c:125-127) + zeroed slot padding, one stream per thread */
 #pragma omp parallel for num_threads(nt) schedule(static)

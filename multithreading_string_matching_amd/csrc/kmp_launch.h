@@ -1,5 +1,5 @@
 /* kmp_launch.h -- launch entry points of kmp_scan_*.hip / kmp_prep.hip / kmp_fold.hip / kmp_marks.hip / kmp_rules.hip / kmp_relations.hip /
- * kmp_chains.hip / kmp_select.hip / kmp_alerts.hip, used
+ * kmp_chains.hip / kmp_headers.hip / kmp_select.hip / kmp_alerts.hip, used
  * by the C-ABI layer (kmpgpu.hip), which alone decides what is launched; the tables kmp_launch_scan_multi takes come from kmp_tables.h. */
 #ifndef KMP_LAUNCH_H
 #define KMP_LAUNCH_H
@@ -135,6 +135,19 @@ hipError_t kmp_launch_chains(const unsigned long long *marks, uint64_t stride, u
                              const kmp_pattern_dev *patterns, const uint8_t *arena, const uint8_t *fold, const uint64_t *pkt_off,
                              const uint32_t *pkt_len, const void *windows, bool whole, uint32_t max_blocks, unsigned long long *rows,
                              unsigned long long *chain_counts, unsigned long long *any, hipStream_t st);
+/* kmp_headers.hip: the header predicates of kmpgpu_set_headers, decided from meta[n_pkts] (16-byte kmpgpu_pkt_meta records, 16-byte
+ * aligned) and pkt_len[n_pkts] alone.  preds[q * 3 ..]: the 48-byte record of predicate q as kmp_pack_headers leaves it (kmp_rowtables.h),
+ * taken KMP_HDR_TILE at a time.  Every word of rows[q][stride] (stride even, 16-byte aligned) is written for every q, the bits of index
+ * n_pkts and above as 0; a predicate's set bits are added to hdr_counts[q] and ORed into any[]; the caller zeroes those two. */
+#define KMP_HDR_TILE 128u
+hipError_t kmp_launch_headers(const void *meta, const uint32_t *pkt_len, uint64_t n_pkts, uint64_t stride, const uint4 *preds,
+                              uint32_t n_hdr, unsigned long long *rows, unsigned long long *hdr_counts, unsigned long long *any,
+                              hipStream_t st);
+/* ... and the metadata itself.  _extract: behind kmp_launch_extract_phase2, with its arguments and its workspace: meta[k] of every accepted
+ * frame, k as kmp_scatter_index_kernel numbers the payloads.  _select: behind kmp_launch_select_phase2, with the workspace of the selection
+ * over src's n payloads: meta[j] = src_meta[k] for the j-th selected payload k.  One kernel each. */
+hipError_t kmp_launch_meta_extract(const uint8_t *file, const uint64_t *frame_off, uint64_t n, const uint8_t *ws, void *meta, hipStream_t st);
+hipError_t kmp_launch_meta_select(const void *src_meta, uint64_t n, const uint8_t *ws, void *meta, hipStream_t st);
 hipError_t kmp_launch_fixed_index(uint64_t *pkt_off, uint32_t *pkt_len, uint64_t n, uint32_t len, uint64_t stride,
                                   hipStream_t st);
 /* kmp_select.hip (kmpgpu_load_selected): the payloads of an index of n whose bit is set in select[ceil(n / 64)] (payload k: bit k & 63 of

@@ -1,5 +1,5 @@
 /*
- * kmp_rowtables.cpp -- the tables of the rules, windows, relations and chains as the kernels read them (kmp_rowtables.h).  Host code only.
+ * kmp_rowtables.cpp -- the tables of the rules, windows, relations, chains and header predicates as the kernels read them (kmp_rowtables.h).  Host code only.
  */
 #include "kmp_rowtables.h"
 
@@ -27,10 +27,16 @@ uint32_t fold_bit(const uint8_t *pat_fold, uint32_t pattern) { return pattern | 
 int kmp_pack_rules(const uint32_t *rule_off, const uint32_t *terms, uint32_t n_rules, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains,
                    std::vector<uint32_t> *heads, std::vector<uint32_t> *quads, std::string *msg)
 {
+    return kmp_pack_rules(rule_off, terms, n_rules, n_pat, n_rel, n_chains, 0u, heads, quads, msg);
+}
+
+int kmp_pack_rules(const uint32_t *rule_off, const uint32_t *terms, uint32_t n_rules, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains,
+                   uint32_t n_hdr, std::vector<uint32_t> *heads, std::vector<uint32_t> *quads, std::string *msg)
+{
     heads->clear(); quads->clear();
     if (!rule_off || !terms) return refuse(msg, "kmpgpu_set_rules: NULL rule arrays");
     if (rule_off[0] != 0) return refuse(msg, "kmpgpu_set_rules: rule_off[0] is %u, not 0", rule_off[0]);
-    const uint64_t n_rows = (uint64_t)n_pat + n_rel + n_chains;          /* (< 2^31: kmp_pack_relations, kmp_pack_chains) */
+    const uint64_t n_rows = (uint64_t)n_pat + n_rel + n_chains + n_hdr;  /* (< 2^31: kmp_pack_relations, kmp_pack_chains, kmp_pack_headers) */
     std::vector<uint32_t> ord;
     for (uint32_t r = 0; r < n_rules; r++) {
         if (rule_off[r + 1] < rule_off[r]) return refuse(msg, "kmpgpu_set_rules: rule_off decreases at rule %u", r);
@@ -38,6 +44,9 @@ int kmp_pack_rules(const uint32_t *rule_off, const uint32_t *terms, uint32_t n_r
         ord.clear();
         for (int neg = 0; neg < 2; neg++)
             for (uint32_t j = rule_off[r]; j < rule_off[r + 1]; j++) {
+                if ((terms[j] & ~KMPGPU_RULE_NOT) >= n_rows && n_hdr)
+                    return refuse(msg, "kmpgpu_set_rules: rule %u: term %u names row %u of %u patterns + %u relations + %u chains + %u header predicates",
+                                  r, j - rule_off[r], terms[j] & ~KMPGPU_RULE_NOT, n_pat, n_rel, n_chains, n_hdr);
                 if ((terms[j] & ~KMPGPU_RULE_NOT) >= n_rows)
                     return refuse(msg, "kmpgpu_set_rules: rule %u: term %u names row %u of %u patterns + %u relations + %u chains", r,
                                   j - rule_off[r], terms[j] & ~KMPGPU_RULE_NOT, n_pat, n_rel, n_chains);
@@ -73,11 +82,17 @@ int kmp_pack_windows(const uint32_t *first, const uint32_t *last, uint32_t n_win
 int kmp_pack_relations(const kmpgpu_relation *rel, uint32_t n_rel, uint32_t n_pat, uint32_t n_chains, const uint8_t *pat_fold,
                        std::vector<uint32_t> *relations, std::string *msg)
 {
+    return kmp_pack_relations(rel, n_rel, n_pat, n_chains, 0u, pat_fold, relations, msg);
+}
+
+int kmp_pack_relations(const kmpgpu_relation *rel, uint32_t n_rel, uint32_t n_pat, uint32_t n_chains, uint32_t n_hdr, const uint8_t *pat_fold,
+                       std::vector<uint32_t> *relations, std::string *msg)
+{
     relations->clear();
     if (!rel) return refuse(msg, "kmpgpu_set_relations: rel is NULL");
-    if ((uint64_t)n_pat + n_rel + n_chains >= (1ull << 31))
-        return refuse(msg, "kmpgpu_set_relations: %u patterns + %u relations%s do not fit the 2^31 rows a rule term can name", n_pat, n_rel,
-                      n_chains ? " + the chains" : "");
+    if ((uint64_t)n_pat + n_rel + n_chains + n_hdr >= (1ull << 31))
+        return refuse(msg, "kmpgpu_set_relations: %u patterns + %u relations%s%s do not fit the 2^31 rows a rule term can name", n_pat, n_rel,
+                      n_chains ? " + the chains" : "", n_hdr ? " + the header predicates" : "");
     for (uint32_t q = 0; q < n_rel; q++) {
         const kmpgpu_relation &r = rel[q];
         if (r.a >= n_pat || r.b >= n_pat)
@@ -91,11 +106,17 @@ int kmp_pack_relations(const kmpgpu_relation *rel, uint32_t n_rel, uint32_t n_pa
 int kmp_pack_chains(const uint32_t *chain_off, const kmpgpu_chain_link *links, uint32_t n_chains, uint32_t n_pat, uint32_t n_rel,
                     const uint8_t *pat_fold, std::vector<uint32_t> *chains, std::string *msg)
 {
+    return kmp_pack_chains(chain_off, links, n_chains, n_pat, n_rel, 0u, pat_fold, chains, msg);
+}
+
+int kmp_pack_chains(const uint32_t *chain_off, const kmpgpu_chain_link *links, uint32_t n_chains, uint32_t n_pat, uint32_t n_rel,
+                    uint32_t n_hdr, const uint8_t *pat_fold, std::vector<uint32_t> *chains, std::string *msg)
+{
     chains->clear();
     if (!chain_off || !links) return refuse(msg, "kmpgpu_set_chains: NULL chain arrays");
-    if ((uint64_t)n_pat + n_rel + n_chains >= (1ull << 31))
-        return refuse(msg, "kmpgpu_set_chains: %u patterns + %u relations + %u chains do not fit the 2^31 rows a rule term can name", n_pat, n_rel,
-                      n_chains);
+    if ((uint64_t)n_pat + n_rel + n_chains + n_hdr >= (1ull << 31))
+        return refuse(msg, "kmpgpu_set_chains: %u patterns + %u relations + %u chains%s do not fit the 2^31 rows a rule term can name", n_pat, n_rel,
+                      n_chains, n_hdr ? " + the header predicates" : "");
     if (chain_off[0] != 0) return refuse(msg, "kmpgpu_set_chains: chain_off[0] is %u, not 0", chain_off[0]);
     for (uint32_t q = 0; q < n_chains; q++) {
         if (chain_off[q + 1] < chain_off[q]) return refuse(msg, "kmpgpu_set_chains: chain_off decreases at chain %u", q);
@@ -110,6 +131,29 @@ int kmp_pack_chains(const uint32_t *chain_off, const kmpgpu_chain_link *links, u
             if (k.dmin > k.dmax) return refuse(msg, "kmpgpu_set_chains: chain %u: dmin %d lies above dmax %d", q, k.dmin, k.dmax);
             chains->insert(chains->end(), {fold_bit(pat_fold, k.pattern), (uint32_t)k.dmin, (uint32_t)k.dmax, n});
         }
+    }
+    return KMPGPU_OK;
+}
+
+int kmp_pack_headers(const kmpgpu_header *h, uint32_t n_hdr, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains, std::vector<uint32_t> *headers,
+                     std::string *msg)
+{
+    headers->clear();
+    if (!h) return refuse(msg, "kmpgpu_set_headers: h is NULL");
+    if ((uint64_t)n_pat + n_rel + n_chains + n_hdr >= (1ull << 31))
+        return refuse(msg, "kmpgpu_set_headers: %u patterns + %u relations + %u chains + %u header predicates do not fit the 2^31 rows a rule term can name",
+                      n_pat, n_rel, n_chains, n_hdr);
+    for (uint32_t q = 0; q < n_hdr; q++) {
+        const kmpgpu_header &p = h[q];
+        if (p.sport_lo > p.sport_hi) return refuse(msg, "kmpgpu_set_headers: predicate %u: source port %u lies above %u", q, p.sport_lo, p.sport_hi);
+        if (p.dport_lo > p.dport_hi) return refuse(msg, "kmpgpu_set_headers: predicate %u: destination port %u lies above %u", q, p.dport_lo, p.dport_hi);
+        if (p.len_lo > p.len_hi) return refuse(msg, "kmpgpu_set_headers: predicate %u: length %u lies above %u", q, p.len_lo, p.len_hi);
+        if (p.flags & ~(KMPGPU_HDR_ANY_PROTO | KMPGPU_HDR_BIDIR))
+            return refuse(msg, "kmpgpu_set_headers: predicate %u: unknown flag bits 0x%x", q, p.flags & ~(KMPGPU_HDR_ANY_PROTO | KMPGPU_HDR_BIDIR));
+        if (p.reserved != 0) return refuse(msg, "kmpgpu_set_headers: predicate %u: reserved is %u, not 0", q, p.reserved);
+        headers->insert(headers->end(), {p.src_ip & p.src_mask, p.src_mask, p.dst_ip & p.dst_mask, p.dst_mask,
+                                         (uint32_t)p.sport_lo | (uint32_t)p.sport_hi << 16, (uint32_t)p.dport_lo | (uint32_t)p.dport_hi << 16, p.len_lo, p.len_hi,
+                                         (uint32_t)p.proto | (uint32_t)p.flags << 8, 0u, 0u, 0u});
     }
     return KMPGPU_OK;
 }

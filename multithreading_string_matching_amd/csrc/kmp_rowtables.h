@@ -1,12 +1,12 @@
 /*
- * kmp_rowtables.h -- what kmpgpu_set_rules, kmpgpu_set_windows, kmpgpu_set_relations and kmpgpu_set_chains upload, checked and packed on
+ * kmp_rowtables.h -- what kmpgpu_set_rules, kmpgpu_set_windows, kmpgpu_set_relations, kmpgpu_set_chains and kmpgpu_set_headers upload, checked and packed on
  * the host by kmp_rowtables.cpp into the form the kernels read bit for bit (kmp_launch.h: kmp_launch_rules, emit_windows,
- * kmp_launch_relations, kmp_launch_chains).  Host code without a HIP header, as kmp_tables.h: it builds and runs without a device
+ * kmp_launch_relations, kmp_launch_chains, kmp_launch_headers).  Host code without a HIP header, as kmp_tables.h: it builds and runs without a device
  * (tests/rowtables_sanitizer_driver.cpp).
  *
  * Every packer returns KMPGPU_OK with its table -- 16-byte records as four uint32_t, window records as two -- or KMPGPU_EINVAL with the
- * whole text of kmpgpu_last_error in *msg.  It reads none of its arrays before the counts alone have passed.  n_pat, n_rel, n_chains: the
- * rows of the context's hit matrix; pat_fold[i]: pattern i is compared in the folded copy of the arena (bit 31 of its index in a record).
+ * whole text of kmpgpu_last_error in *msg.  It reads none of its arrays before the counts alone have passed.  n_pat, n_rel, n_chains, n_hdr:
+ * the rows of the context's hit matrix (the entries without n_hdr are the ones with n_hdr = 0); pat_fold[i]: pattern i is compared in the folded copy of the arena (bit 31 of its index in a record).
  */
 #ifndef KMP_ROWTABLES_H
 #define KMP_ROWTABLES_H
@@ -35,5 +35,19 @@ int kmp_pack_relations(const kmpgpu_relation *rel, uint32_t n_rel, uint32_t n_pa
 /* KMPGPU_CHAIN_MAX records {pattern | fold << 31, dmin, dmax, n} per chain of n contents, the records behind the last link repeating it */
 int kmp_pack_chains(const uint32_t *chain_off, const kmpgpu_chain_link *links, uint32_t n_chains, uint32_t n_pat, uint32_t n_rel,
                     const uint8_t *pat_fold, std::vector<uint32_t> *chains, std::string *msg);
+
+/* The same with the header predicates' rows behind the chains': a rule's terms name rows below n_pat + n_rel + n_chains + n_hdr, and the
+ * 2^31 bound of the relations and chains counts them in. */
+int kmp_pack_rules(const uint32_t *rule_off, const uint32_t *terms, uint32_t n_rules, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains,
+                   uint32_t n_hdr, std::vector<uint32_t> *heads, std::vector<uint32_t> *quads, std::string *msg);
+int kmp_pack_relations(const kmpgpu_relation *rel, uint32_t n_rel, uint32_t n_pat, uint32_t n_chains, uint32_t n_hdr, const uint8_t *pat_fold,
+                       std::vector<uint32_t> *relations, std::string *msg);
+int kmp_pack_chains(const uint32_t *chain_off, const kmpgpu_chain_link *links, uint32_t n_chains, uint32_t n_pat, uint32_t n_rel,
+                    uint32_t n_hdr, const uint8_t *pat_fold, std::vector<uint32_t> *chains, std::string *msg);
+
+/* Three 16-byte records per predicate: {src_ip & src_mask, src_mask, dst_ip & dst_mask, dst_mask}, {sport_lo | sport_hi << 16,
+ * dport_lo | dport_hi << 16, len_lo, len_hi}, {proto | flags << 8, 0, 0, 0} */
+int kmp_pack_headers(const kmpgpu_header *h, uint32_t n_hdr, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains, std::vector<uint32_t> *headers,
+                     std::string *msg);
 
 #endif

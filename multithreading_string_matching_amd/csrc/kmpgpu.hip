@@ -163,7 +163,7 @@ struct kmpgpu_ctx {
     size_t              h_counts_cap = 0;
     unsigned long long *h_small = nullptr;            /* pinned, 16 words: where the loaders read small device results back (a copy to pageable
                                                          memory goes through the runtime's blocking staging path) */
-    unsigned long long *d_marks = nullptr;            /* the marking pass: hit matrix [n_pat + n_rel + n_chains][stride], then pkt_counts[n_pat], any[stride], counts[n_pat], rel_pkt_counts[n_rel], chain_pkt_counts[n_chains] */
+    unsigned long long *d_marks = nullptr;            /* the marking pass: hit matrix [n_pat + n_rel + n_chains + n_hdr][stride], then pkt_counts[n_pat], any[stride], counts[n_pat], rel_pkt_counts[n_rel], chain_pkt_counts[n_chains], hdr_pkt_counts[n_hdr] */
     uint64_t            marks_cap = 0;                /* words */
     /* kmpgpu_set_rules / kmpgpu_scan_rules: the rules as the kernel reads them (kmp_launch.h, kmp_launch_rules) and the results */
     uint32_t            n_rules = 0;
@@ -183,6 +183,17 @@ struct kmpgpu_ctx {
      * is row n_pat + n_rel + c of the hit matrix and term n_pat + n_rel + c of a rule */
     uint32_t            n_chains = 0;
     uint4              *d_chains = nullptr;
+    /* kmpgpu_set_headers: three 16-byte records per predicate as the header kernel reads them (kmp_launch.h, kmp_launch_headers); predicate q
+     * is row n_pat + n_rel + n_chains + q of the hit matrix and term n_pat + n_rel + n_chains + q of a rule */
+    uint32_t            n_hdr = 0;
+    uint4              *d_headers = nullptr;
+    /* the per-payload metadata the predicates are decided from (kmpgpu_pkt_meta, 16 bytes each), in payload order.  It belongs to the arena:
+     * has_meta falls with it (release_arena), the buffer is kept for the next one */
+    uint4              *d_meta = nullptr;
+    uint64_t            meta_cap = 0;
+    bool                has_meta = false;
+    int                 keep_meta = 0;                /* KMPGPU_OPT_KEEP_META, read when a load of frames is begun */
+    bool                fr_meta = false;              /* ... and what the load under way was begun with */
     /* kmpgpu_scan_alerts: the kept prefix of the last pass's list, 16 bytes per record (kmp_launch.h, kmp_launch_alerts_fill); alerts_valid:
      * a list exists -- an alerts pass has ended well and neither the arena nor the patterns have changed since */
     uint4              *d_alerts = nullptr;
@@ -358,6 +369,13 @@ void drop_chains(kmpgpu_ctx *c)
     c->n_chains = 0;
 }
 
+/* ... and the header predicates */
+void drop_headers(kmpgpu_ctx *c)
+{
+    free_buffer(&c->d_headers);
+    c->n_hdr = 0;
+}
+
 /* the patterns and all that is built on them */
 void release_patterns(kmpgpu_ctx *c)
 {
@@ -369,6 +387,7 @@ void release_patterns(kmpgpu_ctx *c)
     drop_windows(c);                               /* ... and so did the windows' */
     drop_relations(c);                             /* ... and the relations' */
     drop_chains(c);                                /* ... and the chains' */
+    drop_headers(c);                               /* ... and the header predicates sit behind all of them */
     c->pat_fold.clear();
     c->alerts_valid = false;                       /* the list named their rows */
 }
@@ -407,6 +426,7 @@ void release_arena(kmpgpu_ctx *c, bool keep_buffers = false)
     c->bitmap_live = false;                           /* the buffer itself (1/128 of an arena) is kept for the next arena */
     c->fold_stale = true; c->fold_end = 0;            /* (so is the fold buffer) */
     c->alerts_valid = false;                          /* the list of kmpgpu_scan_alerts named this arena's payloads */
+    c->has_meta = false;                              /* the metadata described its payloads (the buffer is kept too) */
 }
 
 /* Host ranges pinned through kmpgpu_host_register.  One copy must not straddle two registrations (the runtime refuses it), and a
@@ -456,6 +476,7 @@ void release_pass_buffers(kmpgpu_ctx *c)
     free_buffer(&c->d_bitmap, &c->bitmap_cap); free_buffer(&c->d_plan, &c->plan_cap); free_buffer(&c->d_uplan, &c->uplan_cap);
     free_buffer(&c->d_pool, &c->pool_cap); free_buffer(&c->d_partials, &c->partials_cap); free_buffer(&c->d_fold, &c->fold_cap);
     free_buffer(&c->d_marks, &c->marks_cap); free_buffer(&c->d_rule_out, &c->rule_out_cap); free_buffer(&c->d_alerts, &c->alerts_cap);
+    free_buffer(&c->d_meta, &c->meta_cap); c->has_meta = false;
     c->alerts_valid = false;
     c->bitmap_live = false; c->plan_waves = c->uplan_units = 0; c->fold_stale = true;
 }
@@ -1002,6 +1023,9 @@ int kmpgpu_set_option(kmpgpu_ctx *c, int key, int64_t value)
     case KMPGPU_OPT_WHOLE_PAYLOAD:
         if (value != 0 && value != 1) return fail(KMPGPU_EINVAL, "whole payload must be 0 (text ends at a payload's first 0x00) or 1 (at its end)");
         c->whole_payload = (int)value; return KMPGPU_OK;
+    case KMPGPU_OPT_KEEP_META:
+        if (value != 0 && value != 1) return fail(KMPGPU_EINVAL, "keep meta must be 0 (kmpgpu_load_frames builds the arena alone) or 1 (and keeps the payloads' header metadata)");
+        c->keep_meta = (int)value; return KMPGPU_OK;
     default:
         return fail(KMPGPU_EINVAL, "unknown option %d", key);
     }
@@ -1175,6 +1199,7 @@ int kmpgpu_load_frames_begin(kmpgpu_ctx *c, const uint8_t *file_bytes, uint64_t 
     release_arena(c, /* keep_buffers = */ true);        /* batch after batch: device buffers are reused when the next batch fits */
     c->last.h2d_ms = 0; c->last.h2d_bytes = 0;
     c->fr_pending = true; c->fr_n = n_frames; c->fr_tcp = tcp; c->fr_span = span; c->fr_span_lo = span_lo;
+    c->fr_meta = c->keep_meta != 0;
     if (n_frames == 0) return KMPGPU_OK;
 
     /* scratch, grown on demand and kept (no hipMalloc / hipFree per batch: either synchronises the whole device) */
@@ -1227,13 +1252,17 @@ int kmpgpu_load_frames_finish(kmpgpu_ctx *c, uint64_t *n_payloads)
     if (n_pkts == 0) return KMPGPU_OK;
     HIP_TRY(ensure_owned_arena(c, arena_bytes, n_pkts, EIGHTH));
     HIP_TRY(grow_buffer(&c->fr_src, &c->fr_src_cap, n_pkts, EIGHTH));
+    if (c->fr_meta) HIP_TRY(grow_buffer(&c->d_meta, &c->meta_cap, n_pkts, EIGHTH));
     const uint8_t *d_file0 = c->fr_file - c->fr_span_lo;
     HIP_TRY(hipMemsetAsync(c->owned_arena + tot[0], 0, 64, c->stream));
     HIP_TRY(kmp_launch_extract_phase2(d_file0, c->fr_off, n_frames, c->fr_ws, n_pkts, c->owned_arena, c->owned_off, c->owned_len, c->fr_src, c->stream));
+    /* KMPGPU_OPT_KEEP_META: the accepted frames' header fields, by the numbering the scatter has just used */
+    if (c->fr_meta) HIP_TRY(kmp_launch_meta_extract(d_file0, c->fr_off, n_frames, c->fr_ws, c->d_meta, c->stream));
     IndexFacts f;
     int rc = validate_index(c, "kmpgpu_load_frames", c->owned_off, c->owned_len, n_pkts, arena_bytes, &f);
     /* kmp_gather_kernel writes every slot whole: payload, then 0x00 up to the slot's end */
     if (!rc) rc = install_arena(c, c->owned_arena, c->owned_off, c->owned_len, arena_bytes, n_pkts, f, /* wrote_padding = */ true);
+    if (!rc) c->has_meta = c->fr_meta;
     /* one capture uploaded whole: its bytes are not kept around (a streamed capture's batches are small and the next one
      * reuses the buffer) */
     if (c->fr_file_cap > (1ull << 30)) free_buffer(&c->fr_file, &c->fr_file_cap);
@@ -1342,11 +1371,12 @@ int kmpgpu_load_selected(kmpgpu_ctx *dst, kmpgpu_ctx *src, const void *select, i
     /* from here on dst's earlier arena is gone, whatever happens */
     release_arena(c, /* keep_buffers = */ true);
     if (n_pkts == 0) {
+        if (src->has_meta) HIP_TRY(kmp_launch_meta_select(src->d_meta, n, c->fr_ws, c->d_meta, c->stream));       /* (finds no record to move) */
         HIP_TRY(hipEventRecord(c->ev[3], c->stream));
         HIP_TRY(hipEventSynchronize(c->ev[3]));
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
-        c->last.kernel_ms = ms; c->last.launches = 3;
+        c->last.kernel_ms = ms; c->last.launches = src->has_meta ? 4 : 3;
         return KMPGPU_OK;
     }
     hipError_t e = ensure_owned_arena(c, arena_bytes, n_pkts, EIGHTH);       /* (on failure dst is empty and usable) */
@@ -1355,9 +1385,15 @@ int kmpgpu_load_selected(kmpgpu_ctx *dst, kmpgpu_ctx *src, const void *select, i
                           (unsigned long long)(arena_bytes + arena_bytes / 8), (unsigned long long)(n_pkts + n_pkts / 8));
     e = grow_buffer(&c->fr_src, &c->fr_src_cap, 2 * n_pkts, EIGHTH);      /* 16 bytes per selected payload */
     if (e != hipSuccess) return alloc_fail(e, "kmpgpu_load_selected: the copy's records (%llu payloads) could not be allocated", (unsigned long long)n_pkts);
+    if (src->has_meta) {
+        e = grow_buffer(&c->d_meta, &c->meta_cap, n_pkts, EIGHTH);
+        if (e != hipSuccess) return alloc_fail(e, "kmpgpu_load_selected: the metadata (%llu payloads) could not be allocated", (unsigned long long)n_pkts);
+    }
     HIP_TRY(hipMemsetAsync(c->owned_arena + tot[0], 0, 64, c->stream));
     HIP_TRY(kmp_launch_select_phase2(src->d_arena, src->d_off, n, c->fr_ws, n_pkts, tot[0], c->owned_arena, c->owned_off, c->owned_len, c->fr_src,
                                      c->nontemporal != 0, c->stream));
+    /* src has metadata: the selected payloads' records go with them, in their new order */
+    if (src->has_meta) HIP_TRY(kmp_launch_meta_select(src->d_meta, n, c->fr_ws, c->d_meta, c->stream));
     HIP_TRY(hipEventRecord(c->ev[3], c->stream));
     IndexFacts f;
     int rc = validate_index(c, "kmpgpu_load_selected", c->owned_off, c->owned_len, n_pkts, arena_bytes, &f);
@@ -1366,7 +1402,8 @@ int kmpgpu_load_selected(kmpgpu_ctx *dst, kmpgpu_ctx *src, const void *select, i
     if (rc) { release_arena(c, true); return rc; }
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
-    c->last.kernel_ms = ms; c->last.launches = 5;
+    c->last.kernel_ms = ms; c->last.launches = src->has_meta ? 6 : 5;
+    c->has_meta = src->has_meta;
     if (n_selected) *n_selected = n_pkts;
     return KMPGPU_OK;
 }
@@ -1535,7 +1572,7 @@ namespace {
 struct MarkPass {
     bool empty = false;
     uint64_t W = 0, stride = 0, mat = 0;          /* words per row as the caller sees them / on the device (even); words of the matrix */
-    unsigned long long *d_mat = nullptr, *d_cnt = nullptr;       /* [n_pat + n_rel + n_chains][stride]; the scan's counts [n_pat] */
+    unsigned long long *d_mat = nullptr, *d_cnt = nullptr;       /* [n_pat + n_rel + n_chains + n_hdr][stride]; the scan's counts [n_pat] */
     uint32_t launches = 0;
 };
 
@@ -1558,11 +1595,11 @@ int marking_pass(kmpgpu_ctx *c, const char *who, MarkPass *p)
         const int rr = repack_arena(c);
         if (rr) return rr;
     }
-    /* one device buffer, grown like the others: [marks (n_pat + n_rel + n_chains) x stride][pkt_counts n_pat][any stride][counts n_pat]
-     * [rel_pkt_counts n_rel][chain_pkt_counts n_chains]; the scan kernels mark rows 0 .. n_pat - 1, the relation kernel and the chain
-     * kernel write the rows behind them (family_rows) */
-    const uint64_t mat = ((uint64_t)np + c->n_rel + c->n_chains) * stride;
-    const uint64_t words = mat + np + stride + np + c->n_rel + c->n_chains;
+    /* one device buffer, grown like the others: [marks (n_pat + n_rel + n_chains + n_hdr) x stride][pkt_counts n_pat][any stride][counts n_pat]
+     * [rel_pkt_counts n_rel][chain_pkt_counts n_chains][hdr_pkt_counts n_hdr]; the scan kernels mark rows 0 .. n_pat - 1, the relation
+     * kernel, the chain kernel and the header kernel write the rows behind them (family_rows) */
+    const uint64_t mat = ((uint64_t)np + c->n_rel + c->n_chains + c->n_hdr) * stride;
+    const uint64_t words = mat + np + stride + np + c->n_rel + c->n_chains + c->n_hdr;
     hipError_t e = grow_buffer(&c->d_marks, &c->marks_cap, words, EIGHTH);
     if (e != hipSuccess) return alloc_fail(e, "%s: the hit matrix (%llu bytes) could not be allocated", who, (unsigned long long)(words * 8u));
     p->stride = stride; p->mat = mat;
@@ -1584,7 +1621,10 @@ hipError_t download_rows(kmpgpu_ctx *c, uint64_t *dst, const unsigned long long 
     return hipMemcpy2DAsync(dst, W * sizeof(uint64_t), src, stride * sizeof(uint64_t), W * sizeof(uint64_t), rows, hipMemcpyDeviceToHost, c->stream);
 }
 
-/* A row family (KMPGPU_ALERT_*): patterns, rules, relations or chains.  Where its results lie on the device once its kernels are
+/* the header predicates' rows: a family of kmpgpu_scan_headers and of the rules' terms, none of kmpgpu_scan_alerts (kmpgpu.h) */
+constexpr int FAMILY_HEADERS = KMPGPU_ALERT_CHAINS + 1;
+
+/* A row family (KMPGPU_ALERT_*, FAMILY_HEADERS): patterns, rules, relations, chains or header predicates.  Where its results lie on the device once its kernels are
  * enqueued behind a marking pass (enqueue_family). */
 struct FamilyRows {
     unsigned long long *d_rows = nullptr, *d_pc = nullptr, *d_any = nullptr;     /* [n_rows][stride], payloads per row [n_rows], [stride] */
@@ -1594,10 +1634,11 @@ struct FamilyRows {
 
 uint64_t family_n_rows(const kmpgpu_ctx *c, int family)
 {
-    return family == KMPGPU_ALERT_PATTERNS ? c->n_pat : family == KMPGPU_ALERT_RULES ? c->n_rules : family == KMPGPU_ALERT_RELATIONS ? c->n_rel : c->n_chains;
+    return family == KMPGPU_ALERT_PATTERNS ? c->n_pat : family == KMPGPU_ALERT_RULES ? c->n_rules : family == KMPGPU_ALERT_RELATIONS ? c->n_rel
+         : family == KMPGPU_ALERT_CHAINS ? c->n_chains : c->n_hdr;
 }
 
-/* The one place that knows where the families live: the patterns, relations and chains in the marks buffer as marking_pass lays it out
+/* The one place that knows where the families live: the patterns, relations, chains and header predicates in the marks buffer as marking_pass lays it out
  * (they share its any[]; one family's kernel writes it per pass), the rules in the context's rule buffer [rule rows n_rules x stride]
  * [rule_pkt_counts n_rules][any stride]. */
 void family_rows(const kmpgpu_ctx *c, const MarkPass &p, int family, FamilyRows *f)
@@ -1608,7 +1649,8 @@ void family_rows(const kmpgpu_ctx *c, const MarkPass &p, int family, FamilyRows 
         f->d_rows = c->d_rule_out; f->d_pc = f->d_rows + f->n_rows * p.stride; f->d_any = f->d_pc + f->n_rows;
         return;
     }
-    const uint64_t np = c->n_pat, first = family == KMPGPU_ALERT_PATTERNS ? 0 : family == KMPGPU_ALERT_RELATIONS ? np : np + c->n_rel;
+    const uint64_t np = c->n_pat, first = family == KMPGPU_ALERT_PATTERNS ? 0 : family == KMPGPU_ALERT_RELATIONS ? np
+                                        : family == KMPGPU_ALERT_CHAINS ? np + c->n_rel : np + c->n_rel + c->n_chains;
     f->d_rows = p.d_mat + first * p.stride;
     f->d_pc = family == KMPGPU_ALERT_PATTERNS ? p.d_mat + p.mat : p.d_cnt + first;      /* (the counts of the rows behind the patterns': behind the scan's counts) */
     f->d_any = p.d_mat + p.mat + np;
@@ -1631,9 +1673,21 @@ int enqueue_pairing(kmpgpu_ctx *c, const MarkPass &p, int family)
     return KMPGPU_OK;
 }
 
+/* The header kernel behind a marking pass, in the same way: the predicates' rows from the metadata and the index's lengths alone. */
+int enqueue_headers(kmpgpu_ctx *c, const MarkPass &p)
+{
+    FamilyRows f;
+    family_rows(c, p, FAMILY_HEADERS, &f);
+    hipEvent_t e1;
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_headers(c->d_meta, c->d_len, c->n_pkts, p.stride, c->d_headers, (uint32_t)f.n_rows, f.d_rows, f.d_pc, f.d_any, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    return KMPGPU_OK;
+}
+
 /* The one place that runs a family's kernels behind a marking pass, and says where they leave their results.  Patterns: the marks reduce.
- * Relations, chains: their kernel.  Rules: the relation kernel and the chain kernel where those are set, then the rules kernel, into the
- * context's rule buffer, grown here. */
+ * Relations, chains, header predicates: their kernel.  Rules: the relation kernel, the chain kernel and the header kernel where those are
+ * set, then the rules kernel, into the context's rule buffer, grown here. */
 int enqueue_family(kmpgpu_ctx *c, const char *who, int family, const MarkPass &p, bool profile_reduce, FamilyRows *f)
 {
     hipEvent_t e1 = nullptr;
@@ -1664,6 +1718,11 @@ int enqueue_family(kmpgpu_ctx *c, const char *who, int family, const MarkPass &p
                 if (rr) return rr;
                 f->launches++;
             }
+        if (c->n_hdr) {
+            const int rr = enqueue_headers(c, p);
+            if (rr) return rr;
+            f->launches++;
+        }
         HIP_TRY(profile_launch(c, &e1));
         HIP_TRY(kmp_launch_rules(p.d_mat, p.stride, c->n_pkts, c->d_rule_heads, c->d_rule_quads, c->n_rules, f->d_rows, f->d_pc, f->d_any, c->stream));
         HIP_TRY(profile_launched(c, e1));
@@ -1672,13 +1731,16 @@ int enqueue_family(kmpgpu_ctx *c, const char *who, int family, const MarkPass &p
     }
     family_rows(c, p, family, f);
     f->launches = 1u;
-    return enqueue_pairing(c, p, family);
+    return family == FAMILY_HEADERS ? enqueue_headers(c, p) : enqueue_pairing(c, p, family);
 }
 
 /* What every family's call starts with: the marking pass, and on an empty arena (p->empty) the outputs that hold something -- every payload
  * count, every total is 0, and there are no bit words. */
 int begin_family(kmpgpu_ctx *c, const char *who, int family, uint64_t *row_counts_out, uint64_t *counts_out, kmpgpu_timing *t, MarkPass *p)
 {
+    /* header predicates are decided from the metadata: none on the context is found out before anything is launched */
+    if ((family == FAMILY_HEADERS || (family == KMPGPU_ALERT_RULES && c->n_hdr)) && c->n_pkts && !c->has_meta)
+        return fail(KMPGPU_ESTATE, "%s: no packet metadata (KMPGPU_OPT_KEEP_META, kmpgpu_set_meta)", who);
     const int rc = marking_pass(c, who, p);
     if (rc || !p->empty) return rc;
     if (row_counts_out) memset(row_counts_out, 0, (size_t)family_n_rows(c, family) * sizeof(uint64_t));
@@ -1703,7 +1765,7 @@ int finish_marking(kmpgpu_ctx *c, uint32_t launches, kmpgpu_timing *t)
     return KMPGPU_OK;
 }
 
-/* The body of kmpgpu_scan_packets, _rules, _relations and _chains behind their own checks: marking pass, the family's kernels, downloads. */
+/* The body of kmpgpu_scan_packets, _rules, _relations, _chains and _headers behind their own checks: marking pass, the family's kernels, downloads. */
 int scan_family(kmpgpu_ctx *c, const char *who, int family, uint64_t *row_counts_out, uint64_t *any_out, uint64_t *hits_out, uint64_t *counts_out,
                 kmpgpu_timing *t)
 {
@@ -1777,7 +1839,7 @@ int kmpgpu_set_rules(kmpgpu_ctx *c, const uint32_t *rule_off, const uint32_t *te
     std::vector<uint32_t> heads, quads;
     std::string msg;
     if (n_rules) {
-        const int rc = kmp_pack_rules(rule_off, terms, n_rules, c->n_pat, c->n_rel, c->n_chains, &heads, &quads, &msg);
+        const int rc = kmp_pack_rules(rule_off, terms, n_rules, c->n_pat, c->n_rel, c->n_chains, c->n_hdr, &heads, &quads, &msg);
         if (rc) return fail(rc, "%s", msg.c_str());
         if (quads.empty()) quads.assign(4, 0u);         /* rules of one or two terms only: one quad nobody reads, never a NULL table */
     }
@@ -1814,7 +1876,7 @@ int kmpgpu_set_relations(kmpgpu_ctx *c, const kmpgpu_relation *rel, uint32_t n_r
     std::vector<uint32_t> host;
     std::string msg;
     if (n_rel) {
-        const int rc = kmp_pack_relations(rel, n_rel, c->n_pat, c->n_chains, c->pat_fold.data(), &host, &msg);
+        const int rc = kmp_pack_relations(rel, n_rel, c->n_pat, c->n_chains, c->n_hdr, c->pat_fold.data(), &host, &msg);
         if (rc) return fail(rc, "%s", msg.c_str());
     }
     const int rc = swap_tables(c, "kmpgpu_set_relations: the relations", {{host, (void **)&c->d_relations}});
@@ -1839,7 +1901,7 @@ int kmpgpu_set_chains(kmpgpu_ctx *c, const uint32_t *chain_off, const kmpgpu_cha
     std::vector<uint32_t> host;
     std::string msg;
     if (n_chains) {
-        const int rc = kmp_pack_chains(chain_off, links, n_chains, c->n_pat, c->n_rel, c->pat_fold.data(), &host, &msg);
+        const int rc = kmp_pack_chains(chain_off, links, n_chains, c->n_pat, c->n_rel, c->n_hdr, c->pat_fold.data(), &host, &msg);
         if (rc) return fail(rc, "%s", msg.c_str());
     }
     const int rc = swap_tables(c, "kmpgpu_set_chains: the chains", {{host, (void **)&c->d_chains}});
@@ -1855,6 +1917,77 @@ int kmpgpu_scan_chains(kmpgpu_ctx *c, uint64_t *chain_pkt_counts_out, uint64_t *
     if (!c->d_patterns || c->n_pat == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan_chains: no patterns set");
     if (c->n_chains == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan_chains: no chains set");
     return scan_family(c, "kmpgpu_scan_chains", KMPGPU_ALERT_CHAINS, chain_pkt_counts_out, any_out, chain_hits_out, counts_out, t);
+}
+
+int kmpgpu_set_headers(kmpgpu_ctx *c, const kmpgpu_header *h, uint32_t n_hdr)
+{
+    static_assert(sizeof(kmpgpu_header) == 36, "kmpgpu_header is the 36-byte record of kmpgpu.h");
+    const int sr = setter_state(c, "kmpgpu_set_headers");
+    if (sr) return sr;
+    std::vector<uint32_t> host;
+    std::string msg;
+    if (n_hdr) {
+        const int rc = kmp_pack_headers(h, n_hdr, c->n_pat, c->n_rel, c->n_chains, &host, &msg);
+        if (rc) return fail(rc, "%s", msg.c_str());
+    }
+    const int rc = swap_tables(c, "kmpgpu_set_headers: the header predicates", {{host, (void **)&c->d_headers}});
+    if (rc) return rc;
+    drop_rules(c);                                 /* the rows their terms named are no longer the same, whatever was set or cleared */
+    c->n_hdr = n_hdr;
+    return KMPGPU_OK;
+}
+
+int kmpgpu_scan_headers(kmpgpu_ctx *c, uint64_t *hdr_pkt_counts_out, uint64_t *any_out, uint64_t *hdr_hits_out, uint64_t *counts_out, kmpgpu_timing *t)
+{
+    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_scan_headers: ctx is NULL");
+    if (!c->d_patterns || c->n_pat == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan_headers: no patterns set");
+    if (c->n_hdr == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan_headers: no header predicates set");
+    return scan_family(c, "kmpgpu_scan_headers", FAMILY_HEADERS, hdr_pkt_counts_out, any_out, hdr_hits_out, counts_out, t);
+}
+
+int kmpgpu_set_meta(kmpgpu_ctx *c, const void *meta, uint64_t n_pkts, int on_device)
+{
+    static_assert(sizeof(kmpgpu_pkt_meta) == 16, "kmpgpu_pkt_meta is the 16-byte record of kmpgpu.h");
+    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_set_meta: ctx is NULL");
+    if (on_device != 0 && on_device != 1) return fail(KMPGPU_EINVAL, "kmpgpu_set_meta: on_device is %d, not 0 or 1", on_device);
+    if (c->fr_pending) return fail(KMPGPU_ESTATE, "kmpgpu_set_meta: the context sits between kmpgpu_load_frames_begin and _finish");
+    if (n_pkts == 0 && !meta) { c->has_meta = false; return KMPGPU_OK; }
+    if (!c->d_off || c->n_pkts == 0) return fail(KMPGPU_ESTATE, "kmpgpu_set_meta: no arena loaded");
+    if (n_pkts != c->n_pkts)
+        return fail(KMPGPU_EINVAL, "kmpgpu_set_meta: %llu records for the arena's %llu payloads", (unsigned long long)n_pkts, (unsigned long long)c->n_pkts);
+    if (!meta) return fail(KMPGPU_EINVAL, "kmpgpu_set_meta: meta is NULL");
+    if (on_device && ((uintptr_t)meta & 3u)) return fail(KMPGPU_EINVAL, "kmpgpu_set_meta: the device records are not 4-byte aligned");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));      /* a pass may still read the records that are about to be replaced */
+    /* into a fresh buffer where the one at hand is too small: after a failure the metadata that was there stays */
+    uint4 *d = c->d_meta;
+    if (c->meta_cap < n_pkts) {
+        const hipError_t e = hipMalloc((void **)&d, (size_t)n_pkts * sizeof(uint4));
+        if (e != hipSuccess) return alloc_fail(e, "kmpgpu_set_meta: the metadata (%llu bytes) could not be allocated", (unsigned long long)(n_pkts * 16u));
+    }
+    hipError_t e = hipMemcpyAsync(d, meta, (size_t)n_pkts * sizeof(uint4), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        if (d != c->d_meta) (void)hipFree(d); else c->has_meta = false;       /* (copied over in place: what was there is gone) */
+        return alloc_fail(e, "kmpgpu_set_meta: the metadata could not be copied");
+    }
+    if (d != c->d_meta) { free_buffer(&c->d_meta, &c->meta_cap); c->d_meta = d; c->meta_cap = n_pkts; }
+    c->has_meta = true;
+    return KMPGPU_OK;
+}
+
+int kmpgpu_meta_download(kmpgpu_ctx *c, kmpgpu_pkt_meta *out, uint64_t cap, uint64_t *n)
+{
+    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_meta_download: ctx is NULL");
+    if (n) *n = 0;
+    if (!c->has_meta) return fail(KMPGPU_ESTATE, "kmpgpu_meta_download: no packet metadata (KMPGPU_OPT_KEEP_META, kmpgpu_set_meta)");
+    if (n) *n = c->n_pkts;
+    if (!out || c->n_pkts == 0) return KMPGPU_OK;
+    if (cap < c->n_pkts) return fail(KMPGPU_EINVAL, "kmpgpu_meta_download: room for %llu of %llu records", (unsigned long long)cap, (unsigned long long)c->n_pkts);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(out, c->d_meta, (size_t)c->n_pkts * sizeof(uint4), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return KMPGPU_OK;
 }
 
 int kmpgpu_scan_alerts(kmpgpu_ctx *c, int family, uint64_t max_records, uint64_t *n_found, uint64_t *n_packets, uint64_t *pkt_counts_out,

@@ -15,6 +15,12 @@ from . import _lib
 from ._lib import Arena, KmpHostError, Patterns, SynthParams, u8p, u32p, u64p
 
 PROTO = {"udp": 0, "tcp": 1}
+# kmp_pkt_meta / kmpgpu_pkt_meta, 16 bytes: what GpuMatcher.set_meta takes and .meta() returns
+META_DTYPE = np.dtype([("src_ip", "<u4"), ("dst_ip", "<u4"), ("src_port", "<u2"), ("dst_port", "<u2"), ("proto", "u1"), ("reserved", "u1", (3,))])
+# kmp_header / kmpgpu_header, 36 bytes: one header predicate
+HEADER_DTYPE = np.dtype([("src_ip", "<u4"), ("src_mask", "<u4"), ("dst_ip", "<u4"), ("dst_mask", "<u4"), ("sport_lo", "<u2"), ("sport_hi", "<u2"),
+                         ("dport_lo", "<u2"), ("dport_hi", "<u2"), ("len_lo", "<u4"), ("len_hi", "<u4"), ("proto", "u1"), ("flags", "u1"),
+                         ("reserved", "<u2")])
 
 
 def _np_ptr(a: np.ndarray, t):
@@ -95,15 +101,41 @@ def extract(frame: bytes, capture_len: Optional[int] = None, proto: str = "udp")
     return (off.value, ln.value) if ok else None
 
 
+def extract_meta(frame: bytes, capture_len: Optional[int] = None, proto: str = "udp") -> Optional[np.ndarray]:
+    """The header fields of a frame the extractor of `proto` accepts, as a META_DTYPE scalar, or None (kmp_extract_meta)."""
+    L = _lib.host_lib()
+    buf = np.frombuffer(frame + b"\0" * 64, dtype=np.uint8).copy()
+    m = _lib.PktMeta()
+    cl = len(frame) if capture_len is None else capture_len
+    if not L.kmp_extract_meta(_np_ptr(buf, u8p), cl, PROTO[proto], C.byref(m)):
+        return None
+    return np.frombuffer(bytes(m), dtype=META_DTYPE)[0]
+
+
+def parse_headers(path: str) -> np.ndarray:
+    """The predicates of a headers file as a HEADER_DTYPE array (kmp_headers_parse); KmpHostError carries the parser's message."""
+    L = _lib.host_lib()
+    h = _lib.Headers()
+    err = C.create_string_buffer(_lib.KMP_HEADERS_ERRBUF)
+    rc = L.kmp_headers_parse(path.encode(), C.byref(h), err)
+    if rc:
+        raise KmpHostError(f"{err.value.decode(errors='replace')} ({rc})")
+    try:
+        return np.frombuffer(C.string_at(h.hdr, h.n * C.sizeof(_lib.Header)), dtype=HEADER_DTYPE).copy() if h.n else np.zeros(0, HEADER_DTYPE)
+    finally:
+        L.kmp_headers_free(C.byref(h))
+
+
 # ---------------------------------------------------------------------------------------------
 # arena  (replaces char **array_of_payloads, serial.c:99,124-136)
 # ---------------------------------------------------------------------------------------------
 class HostArena:
     """One contiguous payload arena + {offset, length} index, 16-byte aligned slots."""
 
-    def __init__(self, arena: Arena, owner: bool = True):
+    def __init__(self, arena: Arena, owner: bool = True, meta: Optional[np.ndarray] = None):
         self._a = arena
         self._owner = owner
+        self.meta = meta           # META_DTYPE[n_pkts] where the arena was built with_meta, else None
         n = int(arena.n_pkts)
         self.n_pkts = n
         self.n_frames = int(arena.n_frames)
@@ -114,8 +146,9 @@ class HostArena:
         self.len = np.ctypeslib.as_array(arena.len, shape=(max(n, 1),))[:n]
 
     @classmethod
-    def from_pcap(cls, path: str, proto: str = "udp", pinned: bool = False) -> "HostArena":
-        """serial.c:115-141: read every record, extract, store (invalid frames skipped)."""
+    def from_pcap(cls, path: str, proto: str = "udp", pinned: bool = False, with_meta: bool = False) -> "HostArena":
+        """serial.c:115-141: read every record, extract, store (invalid frames skipped).  with_meta: the identical arena, and in
+        ``.meta`` the accepted frames' header fields in payload order (kmp_arena_from_pcap_meta), as GpuMatcher.set_meta takes them."""
         L = _lib.host_lib()
         a = Arena()
         err = C.create_string_buffer(_lib.KMP_PCAP_ERRBUF)
@@ -124,10 +157,18 @@ class HostArena:
             g = _lib.gpu_lib()
             alloc = C.cast(g.kmpgpu_host_alloc, C.c_void_p)
             free = C.cast(g.kmpgpu_host_free, C.c_void_p)
-        rc = L.kmp_arena_from_pcap(path.encode(), PROTO[proto], alloc, free, C.byref(a), err)
+        mp = C.POINTER(_lib.PktMeta)()
+        if with_meta:
+            rc = L.kmp_arena_from_pcap_meta(path.encode(), PROTO[proto], alloc, free, C.byref(a), err, C.byref(mp))
+        else:
+            rc = L.kmp_arena_from_pcap(path.encode(), PROTO[proto], alloc, free, C.byref(a), err)
         if rc:
             raise KmpHostError(f"error reading pcap file: {err.value.decode(errors='replace')} ({rc})")
-        return cls(a)
+        meta = None
+        if with_meta:
+            meta = np.frombuffer(C.string_at(mp, int(a.n_pkts) * 16), dtype=META_DTYPE).copy() if a.n_pkts else np.zeros(0, META_DTYPE)
+            C.CDLL(None).free(C.cast(mp, C.c_void_p))       # (malloc'ed by the library, kmphost.h)
+        return cls(a, meta=meta)
 
     @classmethod
     def from_payloads(cls, payloads: Sequence[bytes]) -> "HostArena":

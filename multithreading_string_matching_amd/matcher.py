@@ -16,12 +16,13 @@ import numpy as np
 
 from . import _lib
 from ._lib import KmpGpuError, Match, SynthParams, Timing, gpu_check, u8p, u32p, u64p
-from .host import HostArena
+from .host import HEADER_DTYPE, META_DTYPE, HostArena
 
 OPT_MODE, OPT_BLOCKS_PER_CU, OPT_DEPTH, OPT_FUSED, OPT_KERNEL, OPT_ACCUMULATE, OPT_NONTEMPORAL = 1, 2, 3, 4, 5, 6, 100
 OPT_REPACK = 7
 OPT_FUSED_UNIT = 8
 OPT_WHOLE_PAYLOAD = 9   # 1: a payload is text up to its end, not up to its first 0x00 (kmpgpu.h, "Semantics")
+OPT_KEEP_META = 10      # 1: load_pcap_frames keeps the payloads' header metadata (kmpgpu_pkt_meta) beside the index
 KERNEL_AUTO, KERNEL_GENERAL, KERNEL_PACKED, KERNEL_FLAT = 0, 1, 2, 3
 MODE_FILTER, MODE_AUTOMATON = 0, 1
 PAT_NOCASE = 1          # kmpgpu_set_patterns_flags: ASCII letters match either case
@@ -75,6 +76,7 @@ class GpuMatcher:
         self.windows: list = []    # (first, last) per pattern as set_windows took them (last None: unbounded), [] = none
         self.relations: list = []  # (a, b, dmin, dmax) per relation as set_relations took them (None: unbounded side), [] = none
         self.chains: list = []     # (p0, (p1, dmin, dmax), ...) per chain as set_chains took them (None: unbounded side), [] = none
+        self.headers = np.zeros(0, dtype=HEADER_DTYPE)     # the predicates as set_headers took them
         self._keep = None          # objects whose device memory the context borrows
         self._comm = None          # the GpuComm this matcher is a rank of: closed before the context
 
@@ -104,6 +106,7 @@ class GpuMatcher:
         self.windows = []          # ... and its windows
         self.relations = []        # ... and its relations
         self.chains = []           # ... and its chains
+        self.headers = np.zeros(0, dtype=HEADER_DTYPE)     # ... and its header predicates
 
     def set_rules(self, rules) -> None:
         """Content rules over the current patterns (kmpgpu_set_rules): a sequence of (all_of, none_of) pattern-index sequences;
@@ -112,7 +115,7 @@ class GpuMatcher:
         for a, b in rules:
             for i in a + b:
                 if not 0 <= i < _lib.RULE_NOT:
-                    raise ValueError(f"rule term {i}: not a pattern index (or rel(q), chain(c))")
+                    raise ValueError(f"rule term {i}: not a pattern index (or rel(q), chain(c), hdr(q))")
         off = np.zeros(len(rules) + 1, dtype=np.uint32)
         off[1:] = np.cumsum([len(a) + len(b) for a, b in rules])
         terms = np.array([t for a, b in rules for t in a + [i | _lib.RULE_NOT for i in b]] or [0], dtype=np.uint32)
@@ -178,6 +181,62 @@ class GpuMatcher:
             raise ValueError(f"chain({c}): {len(self.chains)} chains are set")
         return len(self.patterns) + len(self.relations) + c
 
+    def set_headers(self, headers) -> None:
+        """Header predicates (kmpgpu_set_headers): a HEADER_DTYPE array, or a sequence of dicts with any of its fields -- src_ip,
+        src_mask, dst_ip, dst_mask, sport_lo, sport_hi, dport_lo, dport_hi, len_lo, len_hi, proto, flags (_lib.HDR_ANY_PROTO,
+        _lib.HDR_BIDIR) --, a field left out being "any": mask 0, ports 0..65535, lengths 0..UINT32_MAX; a dict without proto gets
+        HDR_ANY_PROTO.  Predicate q holds for a payload by its metadata (set_meta, OPT_KEEP_META) and its length alone.  None or an
+        empty sequence clears them.  Every successful call drops the rules, as the library does: relations, chains, headers, then
+        the rules, whose terms may be hdr(q)."""
+        if isinstance(headers, np.ndarray) and headers.dtype == HEADER_DTYPE:
+            arr = np.ascontiguousarray(headers)
+        else:
+            arr = np.zeros(len(headers or []), dtype=HEADER_DTYPE)
+            for r, h in zip(arr, headers or []):
+                r["sport_hi"] = r["dport_hi"] = 0xFFFF
+                r["len_hi"] = 0xFFFFFFFF
+                if "proto" not in h:
+                    r["flags"] = _lib.HDR_ANY_PROTO
+                for k, v in h.items():
+                    r[k] = (int(r[k]) | int(v)) if k == "flags" else int(v)
+        gpu_check(self._g.kmpgpu_set_headers(self._ctx, C.cast(arr.ctypes.data, C.POINTER(_lib.Header)) if arr.size else None, int(arr.size)),
+                  "kmpgpu_set_headers")
+        self.headers = arr.copy()
+        self.rules = []            # the library drops its rules with the rows they referred to
+
+    def hdr(self, q: int) -> int:
+        """The term of header predicate q in set_rules: it is row len(patterns) + len(relations) + len(chains) + q of the hit matrix."""
+        if not 0 <= q < len(self.headers):
+            raise ValueError(f"hdr({q}): {len(self.headers)} header predicates are set")
+        return len(self.patterns) + len(self.relations) + len(self.chains) + q
+
+    def set_meta(self, meta) -> None:
+        """The per-payload header metadata of the arena at hand (kmpgpu_set_meta): a META_DTYPE array with one record per payload
+        (HostArena.from_pcap(..., with_meta=True).meta), or a contiguous torch tensor of 16 bytes per payload on this matcher's
+        device, copied on the device.  None clears the metadata."""
+        if meta is None:
+            gpu_check(self._g.kmpgpu_set_meta(self._ctx, None, 0, 0), "kmpgpu_set_meta")
+        elif isinstance(meta, np.ndarray):
+            if meta.dtype != META_DTYPE:
+                raise ValueError(f"meta: {meta.dtype}; META_DTYPE is needed")
+            m = np.ascontiguousarray(meta)
+            gpu_check(self._g.kmpgpu_set_meta(self._ctx, m.ctypes.data if m.size else None, int(m.size), 0), "kmpgpu_set_meta")
+        else:                                     # a torch tensor
+            nbytes = meta.numel() * meta.element_size()
+            if not meta.is_cuda or meta.device.index != self.device or not meta.is_contiguous() or nbytes % 16:
+                raise ValueError("meta: a contiguous tensor of 16 bytes per payload on the matcher's device is needed")
+            import torch
+            torch.cuda.current_stream(meta.device).synchronize()
+            gpu_check(self._g.kmpgpu_set_meta(self._ctx, meta.data_ptr() if nbytes else None, nbytes // 16, 1), "kmpgpu_set_meta")
+
+    def meta(self) -> np.ndarray:
+        """The metadata the context holds, META_DTYPE[n_pkts] (kmpgpu_meta_download); KmpGpuError where it has none."""
+        n = C.c_uint64()
+        gpu_check(self._g.kmpgpu_meta_download(self._ctx, None, 0, C.byref(n)), "kmpgpu_meta_download")
+        out = np.zeros(max(int(n.value), 1), dtype=META_DTYPE)
+        gpu_check(self._g.kmpgpu_meta_download(self._ctx, out.ctypes.data, out.size, C.byref(n)), "kmpgpu_meta_download")
+        return out[: int(n.value)]
+
     def set_windows(self, windows) -> None:
         """Offset windows of the current patterns (kmpgpu_set_windows): one (first, last) per pattern, last None = unbounded;
         scan_offsets, scan_packets and scan_rules then report, mark and combine only the matches that start at first..last of
@@ -198,8 +257,9 @@ class GpuMatcher:
     # -- arena ------------------------------------------------------------------------------------
     def load_arena(self, arena, off: Optional[np.ndarray] = None, ln: Optional[np.ndarray] = None) -> None:
         """Upload a host arena (HostArena, or numpy bytes + off + len)."""
+        meta = None
         if isinstance(arena, HostArena):
-            a, off, ln = arena.bytes, arena.off, arena.len
+            a, off, ln, meta = arena.bytes, arena.off, arena.len, arena.meta
         else:
             a = np.ascontiguousarray(arena, dtype=np.uint8)
         off = np.ascontiguousarray(off, dtype=np.uint64)
@@ -209,6 +269,8 @@ class GpuMatcher:
                                             off.ctypes.data if n else None, ln.ctypes.data if n else None, n),
                   "kmpgpu_load_arena")
         self._keep = None
+        if meta is not None and n:                # an arena built with_meta brings its metadata along
+            self.set_meta(meta)
 
     def attach_arena(self, d_arena, d_off, d_len, arena_bytes: Optional[int] = None) -> None:
         """Borrow a device-resident arena: torch uint8 / int64 / int32 CUDA tensors.  arena_bytes: what the library is
@@ -354,7 +416,7 @@ class GpuMatcher:
         return arr, int(found.value), counts[:n]
 
     def _scan_family(self, fn, rows: int, counts_key: str, hits: bool) -> dict:
-        """What scan_packets, scan_rules, scan_relations and scan_chains share: the C call ``fn`` over a family of ``rows`` rows, its
+        """What scan_packets, scan_rules, scan_relations, scan_chains and scan_headers share: the C call ``fn`` over a family of ``rows`` rows, its
         per-row payload counts returned under ``counts_key``."""
         n = len(self.patterns)
         n_pkts, _ = self.arena_info()
@@ -396,6 +458,12 @@ class GpuMatcher:
         ``chain_pkt_counts`` (uint64[n_chains]) payloads in which chain c holds, ``any`` (bool[n_pkts]) some chain holds in payload k,
         ``counts`` (uint64[n_pat]) as scan(), ``timing``; with hits=True also ``hits`` (bool[n_chains, n_pkts])."""
         return self._scan_family("kmpgpu_scan_chains", len(self.chains), "chain_pkt_counts", hits)
+
+    def scan_headers(self, hits: bool = False) -> dict:
+        """For which payloads which header predicates hold (kmpgpu_scan_headers): the marking pass of scan_packets and the header kernel.
+        ``hdr_pkt_counts`` (uint64[n_hdr]) payloads for which predicate q holds, ``any`` (bool[n_pkts]) some predicate holds for payload k,
+        ``counts`` (uint64[n_pat]) as scan(), ``timing``; with hits=True also ``hits`` (bool[n_hdr, n_pkts])."""
+        return self._scan_family("kmpgpu_scan_headers", len(self.headers), "hdr_pkt_counts", hits)
 
     def scan_alerts(self, family: str = "rules", max_records: Optional[int] = None, read: bool = True) -> dict:
         """Which payloads hit which rows of a family, as a list built on the device (kmpgpu_scan_alerts): family "patterns", "rules",
