@@ -106,6 +106,10 @@ typedef struct kmpgpu_match {
 #define KMPGPU_OPT_KEEP_META    10   /* 0 (default) = kmpgpu_load_frames / _begin builds the arena alone, exactly as without this option;
                                         1 = one further kernel keeps the per-payload header metadata of every accepted frame
                                         (kmpgpu_pkt_meta, below); any other value: KMPGPU_EINVAL.  Read when a load is begun */
+#define KMPGPU_OPT_FLOW_SLOTS   11   /* slots of the hash table kmpgpu_flows_build groups the payloads in: 0 (default) = auto, the smallest
+                                        power of two >= 2 x n_pkts; any other value must be a power of two > n_pkts, or kmpgpu_flows_build
+                                        returns KMPGPU_EINVAL (negative: kmpgpu_set_option does).  A tuning knob like KMPGPU_OPT_DEPTH: no
+                                        output depends on it */
 #define KMPGPU_OPT_NONTEMPORAL 100   /* 1 (default) = arena loads carry the non-temporal hint (every
                                         byte is read once per pass; measured +10 % on MI355X), 0 =
                                         default cache policy                                   */
@@ -662,6 +666,82 @@ int  kmpgpu_alerts_read(kmpgpu_ctx *ctx, kmpgpu_alert *out, uint64_t first, uint
  * Cost: one read of src's lengths and offsets, one read of the selected slots and one write of them. */
 int  kmpgpu_load_selected(kmpgpu_ctx *dst, kmpgpu_ctx *src, const void *select /* uint64_t[ceil(n_src / 64)] */, int select_on_device,
                           uint64_t *n_selected /* or NULL */);
+
+/* Flows: the payloads of the arena grouped by the 5-tuple of their metadata (kmpgpu_pkt_meta, above), on the device -- which payloads
+ * belong to one connection, what each connection carried, and the hit rows of every family folded from payload space into flow space.
+ * Definitions.  With M = meta[k], the two endpoints of payload k are the 48-bit integers e_src = src_ip << 16 | src_port and
+ * e_dst = dst_ip << 16 | dst_port.
+ *     key(k) = (M.proto, min(e_src, e_dst), max(e_src, e_dst))      the default: both directions of a conversation are one flow
+ *     key(k) = (M.proto, e_src, e_dst)                              under KMPGPU_FLOW_DIRECTED
+ * `reserved` is not part of the key.  A:1 -> B:2 and A:2 -> B:1 are different flows either way.  The protocol byte is part of the key (the
+ * UDP frames the tcp extractor accepts do not merge with TCP ones).  Two payloads are in one flow iff their keys are equal.  Flows are
+ * numbered 0 .. n_flows - 1 in the order of their first payload; flow_of[k] is payload k's flow.  Neither the numbering nor any output
+ * depends on the run: no atomic decides an id.
+ * kmpgpu_flows_build groups the arena's payloads (*n_flows, may be NULL) and keeps flow_of[n_pkts] and the records kmpgpu_flow[n_flows] on
+ * the device; kmpgpu_flows_read copies records [first, first + n) to out, kmpgpu_flow_ids_read flow_of[first .. first + n).  n == 0
+ * copies nothing (out may be NULL).  A record: first_packet / last_packet are the flow's lowest and highest payload index, n_packets its
+ * payloads, payload_bytes the sum of their L_k (the index's lengths, whatever KMPGPU_OPT_WHOLE_PAYLOAD says), first = meta[first_packet] as
+ * it is (its direction is the flow's).
+ *
+ * kmpgpu_scan_flows: a flow-space hit matrix beside the payload-space one.  Wf = ceil(n_flows / 64); the layout is that of
+ * kmpgpu_scan_packets with flows in place of payloads (flow f is bit (f & 63) of word (f >> 6)); bits at n_flows and above are 0 in every
+ * word.  family is one of KMPGPU_ALERT_*.
+ *   KMPGPU_FLOW_SCOPE_PACKET (any family): flow_hit[r][f] = OR over the payloads k of flow f of row[r][k], where row is exactly the bit
+ *     the family's own call defines (windows, nocase, whole payloads; for rules the relation, chain and header terms): the flow holds a
+ *     payload that the row matches.
+ *   KMPGPU_FLOW_SCOPE_FLOW (KMPGPU_ALERT_RULES only; any other family: KMPGPU_EINVAL): every term row -- patterns, relations, chains, header
+ *     predicates, as the rule terms index them -- is folded first, then the rule is evaluated per flow:
+ *       flow_rule_hit[r][f] = AND over positive terms t of (OR_k row[t][k]) AND AND over negated terms t of !(OR_k row[t][k])
+ *     the cross-packet signature: one content in one payload, another in another payload of the same connection.  An all-negated rule
+ *     matches every flow that holds none of its terms.
+ *   flow_counts[r] = the flows in row r, any[f] = OR over the rows, counts = what kmpgpu_scan returns.  Every output may be NULL.
+ * Ordering: synchronous, on the context's stream.  The marking pass and the family's kernels as the family's own call runs them (for
+ * SCOPE_FLOW: as kmpgpu_scan_rules), then the fold kernel, then for SCOPE_PACKET the reduce of kmpgpu_scan_packets over the folded matrix,
+ * for SCOPE_FLOW the rules kernel of kmpgpu_scan_rules over the folded term rows with n_flows in place of n_pkts.  *t: as the family's own
+ * call, launches = its launches + 2 (fold; reduce or rules).  Under kmpgpu_profile_begin those two are recorded last, behind the family's
+ * kernels as kmpgpu_scan_alerts records them.
+ *
+ * kmpgpu_flows_select expands a flow bitmap (uint64_t[Wf]; on_device == 0: host memory, == 1: device memory, 8-byte aligned, complete
+ * before the call; bits of index n_flows and above are ignored) to the payload bitmap pkt[k] = flow_bits[flow_of[k]], W = ceil(n_pkts / 64)
+ * words, to pkt_bits_out (host, may be NULL) and into a device buffer the context owns (*d_pkt_bits, may be NULL), which stays valid until
+ * the next kmpgpu_flows_select on the context or until the flows are dropped.  It is what kmpgpu_load_selected(dst, ctx, ptr, 1, ..)
+ * takes: any[] of kmpgpu_scan_flows goes in, the whole connections that fired come out as an arena, with their metadata.  One kernel: a
+ * lane per payload, a ballot per word, 8-byte stores.
+ *
+ * State.  Flows belong to the arena and its metadata: whatever replaces or releases the arena (kmpgpu_load_arena, kmpgpu_attach_arena,
+ * kmpgpu_load_frames, kmpgpu_load_selected as dst) and kmpgpu_set_meta drop them (the buffers stay for the next build).  They survive
+ * the on-device repack, kmpgpu_set_patterns, the setters of the row families and every option.
+ * Errors.  kmpgpu_flows_build: no metadata: KMPGPU_ESTATE ("no packet metadata"); between kmpgpu_load_frames_begin and _finish:
+ * KMPGPU_ESTATE; an unknown flag bit: KMPGPU_EINVAL; n_pkts > 2^32 - 2: KMPGPU_EINVAL (ids are 32 bits); KMPGPU_OPT_FLOW_SLOTS neither 0 nor
+ * a power of two > n_pkts: KMPGPU_EINVAL.  With n_pkts == 0 it leaves 0 flows and launches nothing.  The read calls, kmpgpu_scan_flows and
+ * kmpgpu_flows_select without built flows: KMPGPU_ESTATE; a read range that leaves [0, n_flows) ([0, n_pkts) for the ids): KMPGPU_EINVAL.
+ * kmpgpu_scan_flows otherwise has the preconditions and errors of the family's own call.  An allocation failure (KMPGPU_ENOMEM /
+ * KMPGPU_EHIP) leaves the context usable and without flows.
+ * Every other call is bit-identical, with the same launches and buffers, before and after any of these calls.
+ * kmpgpu_flows_build: five kernels and two of the scan kernels kmpgpu_load_selected uses (insert, firsts, scan x 2, number, assign; the
+ * total read once on the host in between), in the scratch the context keeps for those; *t (may be NULL): kernel_ms over all of them,
+ * launches = 6.
+ * Memory, all owned by the context, grown like the other buffers and freed by kmpgpu_destroy: the table and first[],
+ * 4 bytes per slot each (slots: KMPGPU_OPT_FLOW_SLOTS); slot_of / flow_of, one array of 4 bytes per payload; the records, 48 bytes per
+ * flow; the folded matrix, (rows x Sf + rows + Sf) x 8 bytes with Sf = 2 ceil(Wf / 2) (SCOPE_FLOW: rows = terms + rules); the select
+ * buffer, (W + Wf) x 8 bytes. */
+#define KMPGPU_FLOW_DIRECTED 1u
+typedef struct kmpgpu_flow {          /* 48 bytes */
+    uint64_t first_packet, last_packet;   /* payload indices */
+    uint64_t n_packets;
+    uint64_t payload_bytes;               /* sum of L_k */
+    kmpgpu_pkt_meta first;                /* meta[first_packet] */
+} kmpgpu_flow;
+int  kmpgpu_flows_build(kmpgpu_ctx *ctx, uint32_t flags, uint64_t *n_flows /* or NULL */, kmpgpu_timing *t /* or NULL */);
+int  kmpgpu_flows_read(kmpgpu_ctx *ctx, kmpgpu_flow *out, uint64_t first, uint64_t n);
+int  kmpgpu_flow_ids_read(kmpgpu_ctx *ctx, uint32_t *out /* flow_of[first .. first + n) */, uint64_t first, uint64_t n);
+#define KMPGPU_FLOW_SCOPE_PACKET 0u
+#define KMPGPU_FLOW_SCOPE_FLOW   1u
+int  kmpgpu_scan_flows(kmpgpu_ctx *ctx, int family /* KMPGPU_ALERT_* */, uint32_t scope, uint64_t *flow_counts_out /* [rows] or NULL */,
+                       uint64_t *any_out /* [Wf] or NULL */, uint64_t *flow_hits_out /* [rows * Wf] or NULL */,
+                       uint64_t *counts_out /* [n_pat] or NULL: as kmpgpu_scan */, kmpgpu_timing *t /* or NULL */);
+int  kmpgpu_flows_select(kmpgpu_ctx *ctx, const void *flow_bits /* uint64_t[Wf] */, int on_device, uint64_t *pkt_bits_out /* host [W] or NULL */,
+                         const void **d_pkt_bits /* or NULL */);
 
 /* Fill a device arena with the synthetic payloads of kmp_synth.h (benchmark input S1/S2):
  * packet ids first_pkt_id .. first_pkt_id + n_pkts - 1 at the slots of the given device index. */

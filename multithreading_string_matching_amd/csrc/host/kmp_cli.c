@@ -61,6 +61,16 @@
  * KMPGPU_RULES_FILE, KMPGPU_ALERTS_FILE may be left out when this variable is set.  A path that cannot be written: message on stderr,
  * exit 1, before any GPU work.  stdout is what it is without the variable.
  *
+ * KMPGPU_FLOWS_FILE=<path>: the payloads grouped by the 5-tuple of their header fields on the device (kmpgpu_flows_build), one line per flow,
+ * "flow,proto,src,sport,dst,dport,first_payload,last_payload,payloads,bytes": flows are numbered in the order of their first payload,
+ * the addresses are dotted quads and, with the ports, those of the flow's first payload.  KMPGPU_FLOWS_DIRECTED=1: the two directions of
+ * a conversation are two flows.  KMPGPU_FLOW_ALERTS_FILE=<path>, together with KMPGPU_RULES_FILE (KMPGPU_ALERTS_FILE may be left out):
+ * the rules evaluated per flow (kmpgpu_scan_flows, KMPGPU_FLOW_SCOPE_FLOW: a rule's contents may lie in different payloads of the
+ * connection), one "flow,rule" line per flow a rule matches, sorted by flow, then by rule.  The header fields come the way they do for
+ * KMPGPU_HEADERS_FILE, and both routes write the same files.  Refused with a message on stderr and exit 1, before any GPU work: more
+ * than one shard (a flow would be cut at a shard's edge), KMPGPU_FLOW_ALERTS_FILE without a rules file, a path that cannot be written.
+ * stdout is what it is without the variables.
+ *
  * KMPGPU_NOCASE=1: every pattern matches case-insensitively (ASCII letters; kmpgpu_set_patterns_flags), in the counts and in
  * the offsets file alike; the report prints every token as written in the pattern file.
  *
@@ -96,7 +106,9 @@ typedef struct cli_options {
     kmp_patterns pats;
     const uint8_t **pp;                     /* pp[i]: the bytes of pattern i */
     int whole_payload, nocase, device_extract, want_stats;
-    const char *offsets_path, *packets_path, *rules_path, *alerts_path, *export_path;
+    const char *offsets_path, *packets_path, *rules_path, *alerts_path, *export_path, *flows_path, *flow_alerts_path;
+    int flows_directed;                     /* KMPGPU_FLOWS_DIRECTED */
+    int want_meta;                          /* header predicates or flows: the payloads' header fields go to the device */
     /* what every shard's context gets behind its patterns, in this order and before any rule is set */
     uint32_t *win_first, *win_last;         /* KMPGPU_WINDOWS_FILE (NULL: none) */
     kmp_relations relations;                /* KMPGPU_RELATIONS_FILE (n == 0: none) */
@@ -146,6 +158,15 @@ static void usage(const char *head)
     exit(1);
 }
 
+/* an output file that cannot be written ends the run before any GPU work; one that can starts empty */
+static void probe_writable(const char *var, const char *path)
+{
+    if (!path) return;
+    FILE *fp = fopen(path, "w");
+    if (!fp) { perror(var); exit(1); }
+    fclose(fp);
+}
+
 static void needs_rules_and_alerts(const char *var, const cli_options *opt)
 {
     if (opt->rules_path && opt->alerts_path) return;
@@ -192,10 +213,13 @@ static void load_options(int argc, char *argv[], cli_options *opt)
     opt->rules_path = env_path("KMPGPU_RULES_FILE");
     opt->alerts_path = env_path("KMPGPU_ALERTS_FILE");
     opt->export_path = env_path("KMPGPU_EXPORT_FILE");
+    opt->flows_path = env_path("KMPGPU_FLOWS_FILE");
+    opt->flow_alerts_path = env_path("KMPGPU_FLOW_ALERTS_FILE");
+    opt->flows_directed = env_flag("KMPGPU_FLOWS_DIRECTED");
     const char *relations_path = env_path("KMPGPU_RELATIONS_FILE"), *chains_path = env_path("KMPGPU_CHAINS_FILE"), *headers_path = env_path("KMPGPU_HEADERS_FILE"), *windows_path = env_path("KMPGPU_WINDOWS_FILE");
 
     /* the content rules (an export takes the rules' any[] without an alerts file) */
-    if ((opt->rules_path != NULL) != (opt->alerts_path != NULL) && !(opt->rules_path && opt->export_path)) {
+    if ((opt->rules_path != NULL) != (opt->alerts_path != NULL) && !(opt->rules_path && (opt->export_path || opt->flow_alerts_path))) {
         fprintf(stderr, "KMPGPU_RULES_FILE and KMPGPU_ALERTS_FILE go together: %s is not set\n", opt->rules_path ? "KMPGPU_ALERTS_FILE" : "KMPGPU_RULES_FILE");
         exit(1);
     }
@@ -242,6 +266,20 @@ static void load_options(int argc, char *argv[], cli_options *opt)
             exit(1);
         }
     }
+    /* flows: one shard, rules for the flow alerts, and both files started empty */
+    if (opt->flows_path || opt->flow_alerts_path) {
+        if (opt->shards > 1) {
+            fprintf(stderr, "KMPGPU_FLOWS_FILE and KMPGPU_FLOW_ALERTS_FILE need one shard, thread_number is %d: a flow would be cut at a shard's edge\n", opt->shards);
+            exit(1);
+        }
+        if (opt->flow_alerts_path && !opt->rules_path) {
+            fprintf(stderr, "KMPGPU_FLOW_ALERTS_FILE goes together with KMPGPU_RULES_FILE: it is not set\n");
+            exit(1);
+        }
+        probe_writable("KMPGPU_FLOWS_FILE", opt->flows_path);
+        probe_writable("KMPGPU_FLOW_ALERTS_FILE", opt->flow_alerts_path);
+    }
+    opt->want_meta = opt->headers.n || opt->flows_path || opt->flow_alerts_path;
     /* the export starts as a capture without frames: a path that cannot be written ends the run here */
     if (opt->export_path && kmp_write_udp_pcap_part(opt->export_path, 0, NULL, NULL, NULL, 0, 0)) {
         perror("KMPGPU_EXPORT_FILE");
@@ -285,7 +323,7 @@ static void load_capture(const cli_options *opt, capture *cap)
      * MI355X hosts (profiles/r01_h2d_probe.txt).  Pinned buffers pay off where they are reused (bin/openmp_task). */
     if (opt->device_extract)
         rc = kmp_frames_from_pcap(opt->pcap_path, NULL, NULL, &cap->frames, errbuf);
-    else if (opt->headers.n)                                                /* the same arena, and the header fields the predicates read */
+    else if (opt->want_meta)                                                /* the same arena, and the header fields the predicates and the flows read */
         rc = kmp_arena_from_pcap_meta(opt->pcap_path, opt->proto, NULL, NULL, &cap->arena, errbuf, &cap->meta);
     else
         rc = kmp_arena_from_pcap(opt->pcap_path, opt->proto, NULL, NULL, &cap->arena, errbuf);                /* serial.c:91-141 */
@@ -322,7 +360,7 @@ static void *shard_load(void *arg)
     if (o->chains.n && kmpgpu_set_chains(j->ctx, o->chains.off, (const kmpgpu_chain_link *)o->chains.links, o->chains.n)) return shard_fail(j, "kmpgpu_set_chains");
     _Static_assert(sizeof(kmp_header) == sizeof(kmpgpu_header) && sizeof(kmp_pkt_meta) == sizeof(kmpgpu_pkt_meta), "kmp_header, kmp_pkt_meta have the layouts of kmpgpu.h");
     if (o->headers.n && kmpgpu_set_headers(j->ctx, (const kmpgpu_header *)o->headers.hdr, o->headers.n)) return shard_fail(j, "kmpgpu_set_headers");
-    if (o->headers.n && o->device_extract && kmpgpu_set_option(j->ctx, KMPGPU_OPT_KEEP_META, 1)) return shard_fail(j, "kmpgpu_set_option");
+    if (o->want_meta && o->device_extract && kmpgpu_set_option(j->ctx, KMPGPU_OPT_KEEP_META, 1)) return shard_fail(j, "kmpgpu_set_option");
     if (o->device_extract) {
         /* only the bytes this shard's frames span are uploaded (kmpgpu_load_frames) */
         const kmp_frames *f = &j->cap->frames;
@@ -423,6 +461,50 @@ static void write_alerts(const char *path, const cli_options *opt, cli_run *run,
     fclose(fp);
 }
 
+/* KMPGPU_FLOWS_FILE, KMPGPU_FLOW_ALERTS_FILE: the one shard's payloads grouped on the device, the records read back in pieces; then the
+ * rules per flow, whose rows come back as a bit matrix of rules x flows (a rules file without rules leaves the file empty). */
+#define FLOW_PIECE 16384u
+static void write_flows(const cli_options *opt, cli_run *run)
+{
+    static kmpgpu_flow piece[FLOW_PIECE];
+    kmpgpu_ctx *ctx = run->ctxs[0];
+    uint64_t n_flows = 0;
+    if (kmpgpu_flows_build(ctx, opt->flows_directed ? KMPGPU_FLOW_DIRECTED : 0u, &n_flows, NULL)) die_gpu("kmpgpu_flows_build");
+    if (opt->flows_path) {
+        FILE *fp = fopen(opt->flows_path, "w");
+        if (!fp) { perror("KMPGPU_FLOWS_FILE"); exit(1); }
+        for (uint64_t first = 0; first < n_flows; first += FLOW_PIECE) {
+            const uint64_t n = n_flows - first < FLOW_PIECE ? n_flows - first : FLOW_PIECE;
+            if (kmpgpu_flows_read(ctx, piece, first, n)) die_gpu("kmpgpu_flows_read");
+            for (uint64_t i = 0; i < n; i++) {
+                const kmpgpu_flow *f = &piece[i];
+                const uint32_t s = f->first.src_ip, d = f->first.dst_ip;
+                fprintf(fp, "%llu,%u,%u.%u.%u.%u,%u,%u.%u.%u.%u,%u,%llu,%llu,%llu,%llu\n", (unsigned long long)(first + i), f->first.proto, s >> 24, s >> 16 & 255u,
+                        s >> 8 & 255u, s & 255u, f->first.src_port, d >> 24, d >> 16 & 255u, d >> 8 & 255u, d & 255u, f->first.dst_port,
+                        (unsigned long long)f->first_packet, (unsigned long long)f->last_packet, (unsigned long long)f->n_packets,
+                        (unsigned long long)f->payload_bytes);
+            }
+        }
+        fclose(fp);
+    }
+    if (opt->flow_alerts_path) {
+        FILE *fp = fopen(opt->flow_alerts_path, "w");
+        if (!fp) { perror("KMPGPU_FLOW_ALERTS_FILE"); exit(1); }
+        set_rules_once(opt, run);
+        const uint64_t Wf = (n_flows + 63) / 64, nr = opt->rules.n;
+        if (nr && n_flows) {
+            uint64_t *hits = (uint64_t *)calloc((size_t)(nr * Wf), sizeof(uint64_t));
+            if (!hits) die_gpu("KMPGPU_FLOW_ALERTS_FILE: out of memory");
+            if (kmpgpu_scan_flows(ctx, KMPGPU_ALERT_RULES, KMPGPU_FLOW_SCOPE_FLOW, NULL, NULL, hits, NULL, NULL)) die_gpu("kmpgpu_scan_flows");
+            for (uint64_t f = 0; f < n_flows; f++)
+                for (uint64_t r = 0; r < nr; r++)
+                    if (hits[r * Wf + (f >> 6)] >> (f & 63) & 1u) fprintf(fp, "%llu,%llu\n", (unsigned long long)f, (unsigned long long)r);
+            free(hits);
+        }
+        fclose(fp);
+    }
+}
+
 /* KMPGPU_EXPORT_FILE: the payloads that a rule matches (by_rules) or that hold a pattern, appended shard by shard to the capture that
  * load_options started.  A shard's selection is compacted next to it on its device; only these bytes come back. */
 static void write_export(const char *path, const cli_run *run, int by_rules, int have_rules)
@@ -520,6 +602,7 @@ int main(int argc, char *argv[])
             set_rules_once(&opt, &run);
             write_export(opt.export_path, &run, opt.rules_path != NULL, opt.rules.n != 0);
         }
+        if (opt.flows_path || opt.flow_alerts_path) write_flows(&opt, &run);
         for (int r = 0; r < run.shards && opt.want_stats; r++) {
             uint64_t e = 0;
             if (kmpgpu_effective_bytes(run.ctxs[r], &e)) die_gpu("kmpgpu_effective_bytes");

@@ -1,5 +1,5 @@
 /* kmp_launch.h -- launch entry points of kmp_scan_*.hip / kmp_prep.hip / kmp_fold.hip / kmp_marks.hip / kmp_rules.hip / kmp_relations.hip /
- * kmp_chains.hip / kmp_headers.hip / kmp_select.hip / kmp_alerts.hip, used
+ * kmp_chains.hip / kmp_headers.hip / kmp_select.hip / kmp_alerts.hip / kmp_flows.hip, used
  * by the C-ABI layer (kmpgpu.hip), which alone decides what is launched; the tables kmp_launch_scan_multi takes come from kmp_tables.h. */
 #ifndef KMP_LAUNCH_H
 #define KMP_LAUNCH_H
@@ -171,5 +171,33 @@ hipError_t kmp_launch_alerts_count(const unsigned long long *rows, uint64_t stri
 hipError_t kmp_launch_alerts_scan(uint64_t n_pkts, uint8_t *ws, unsigned long long *totals, hipStream_t st);
 hipError_t kmp_launch_alerts_fill(const unsigned long long *rows, uint64_t stride, uint32_t n_rows, uint64_t n_pkts,
                                   const unsigned long long *any, uint8_t *ws, void *recs, uint64_t max_records, hipStream_t st);
+
+/* kmp_flows.hip (kmpgpu_flows_build, kmpgpu_scan_flows, kmpgpu_flows_select): the n_pkts <= 2^32 - 2 payloads of meta[] (16-byte
+ * kmpgpu_pkt_meta records, 16-byte aligned) grouped by their flow key (kmp_flow_key.h).  In the order they are launched:
+ * _insert: table[slots] (a power of two > n_pkts, at most 2^32; all 0 before the launch) takes every key, first[slots] (all 0xFFFFFFFF
+ *   before) the lowest payload index of every taken slot, slot_of[n_pkts] every payload's slot.
+ * _firsts, _scan (2 kernels): in ws, kmp_extract_ws_bytes(n_pkts) bytes kept up to _number: which payloads are their flow's first, their
+ *   rank among those, totals[1] = n_flows.
+ * _number: table[slot] = the id of the slot's flow; recs[n_flows] (48-byte kmpgpu_flow records, 16-byte aligned): first_packet, first, and
+ *   0 in the three fields _assign adds up.
+ * _assign: slot_flow[n_pkts] holds slot_of on entry and flow_of on return; n_packets, payload_bytes (of pkt_len[]), last_packet of recs.
+ * _fold: out[r][f >> 6] |= 1 << (f & 63) for every set bit k < n_pkts of rows[r][stride], f = flow_of[k] < n_flows; r < n_rows,
+ *   out[n_rows][stride_f] zeroed by the caller, 64 stride_f >= n_flows.  any[ceil(n_pkts / 64)] or NULL: a column word whose any word is 0 is
+ *   not read.
+ * _expand: bit k of pkt_bits[ceil(n_pkts / 64)] = bit flow_of[k] of flow_bits[ceil(n_flows / 64)]; every word is written, the bits of index
+ *   n_pkts and above as 0. */
+hipError_t kmp_launch_flows_insert(const void *meta, uint64_t n_pkts, bool directed, uint32_t *table, uint64_t slots, uint32_t *first,
+                                   uint32_t *slot_of, hipStream_t st);
+hipError_t kmp_launch_flows_firsts(const uint32_t *first, const uint32_t *slot_of, uint64_t n_pkts, uint8_t *ws, hipStream_t st);
+hipError_t kmp_launch_flows_scan(uint64_t n_pkts, uint8_t *ws, unsigned long long *totals, hipStream_t st);
+hipError_t kmp_launch_flows_number(const void *meta, uint64_t n_pkts, uint8_t *ws, const uint32_t *slot_of, uint32_t *table, void *recs,
+                                   hipStream_t st);
+hipError_t kmp_launch_flows_assign(const uint32_t *table, uint32_t *slot_flow, const uint32_t *pkt_len, uint64_t n_pkts, void *recs,
+                                   hipStream_t st);
+hipError_t kmp_launch_flows_fold(const unsigned long long *rows, uint64_t stride, uint32_t n_rows, uint64_t n_pkts,
+                                 const unsigned long long *any, const uint32_t *flow_of, uint64_t n_flows, unsigned long long *out,
+                                 uint64_t stride_f, hipStream_t st);
+hipError_t kmp_launch_flows_expand(const unsigned long long *flow_bits, const uint32_t *flow_of, uint64_t n_pkts, unsigned long long *pkt_bits,
+                                   hipStream_t st);
 
 #endif

@@ -23,6 +23,7 @@
 
 #include "kmpgpu.h"
 #include "kmp_device.h"
+#include "kmp_flow_key.h"
 #include "kmp_launch.h"
 #include "kmp_rowtables.h"
 #include "kmp_tables.h"
@@ -199,6 +200,18 @@ struct kmpgpu_ctx {
     uint4              *d_alerts = nullptr;
     uint64_t            alerts_cap = 0, alerts_kept = 0;
     bool                alerts_valid = false;
+    /* kmpgpu_flows_build: the hash table [flow_slots] and the lowest payload of every slot's flow [flow_slots], slot_of / flow_of [n_pkts]
+     * (one array), the records [n_flows]; kmpgpu_scan_flows: the folded matrix; kmpgpu_flows_select: the payload bitmap and the uploaded
+     * flow bitmap behind it.  flows_valid: flows are built, and neither the arena nor its metadata have changed since (drop_flows) */
+    uint32_t           *d_flow_table = nullptr, *d_flow_first = nullptr, *d_flow_of = nullptr;
+    uint64_t            flow_table_cap = 0, flow_first_cap = 0, flow_of_cap = 0;
+    kmpgpu_flow        *d_flow_recs = nullptr;
+    uint64_t            flow_recs_cap = 0;
+    unsigned long long *d_flow_fold = nullptr, *d_flow_sel = nullptr;
+    uint64_t            flow_fold_cap = 0, flow_sel_cap = 0;          /* words */
+    uint64_t            n_flows = 0;
+    bool                flows_valid = false;
+    int64_t             flow_slots = 0;               /* KMPGPU_OPT_FLOW_SLOTS */
 
     /* options */
     int mode = 0, blocks_per_cu = 0 /* auto */, depth = 0 /* auto */, nontemporal = 1, kernel_sel = 0, fused = 2 /* auto */, accumulate = 0, repack = 1;
@@ -376,6 +389,13 @@ void drop_headers(kmpgpu_ctx *c)
     c->n_hdr = 0;
 }
 
+/* the flows go with the arena and its metadata; their buffers are kept for the next build */
+void drop_flows(kmpgpu_ctx *c)
+{
+    c->flows_valid = false;
+    c->n_flows = 0;
+}
+
 /* the patterns and all that is built on them */
 void release_patterns(kmpgpu_ctx *c)
 {
@@ -427,6 +447,7 @@ void release_arena(kmpgpu_ctx *c, bool keep_buffers = false)
     c->fold_stale = true; c->fold_end = 0;            /* (so is the fold buffer) */
     c->alerts_valid = false;                          /* the list of kmpgpu_scan_alerts named this arena's payloads */
     c->has_meta = false;                              /* the metadata described its payloads (the buffer is kept too) */
+    drop_flows(c);                                    /* ... and the flows grouped them */
 }
 
 /* Host ranges pinned through kmpgpu_host_register.  One copy must not straddle two registrations (the runtime refuses it), and a
@@ -477,6 +498,9 @@ void release_pass_buffers(kmpgpu_ctx *c)
     free_buffer(&c->d_pool, &c->pool_cap); free_buffer(&c->d_partials, &c->partials_cap); free_buffer(&c->d_fold, &c->fold_cap);
     free_buffer(&c->d_marks, &c->marks_cap); free_buffer(&c->d_rule_out, &c->rule_out_cap); free_buffer(&c->d_alerts, &c->alerts_cap);
     free_buffer(&c->d_meta, &c->meta_cap); c->has_meta = false;
+    free_buffer(&c->d_flow_table, &c->flow_table_cap); free_buffer(&c->d_flow_first, &c->flow_first_cap); free_buffer(&c->d_flow_of, &c->flow_of_cap);
+    free_buffer(&c->d_flow_recs, &c->flow_recs_cap); free_buffer(&c->d_flow_fold, &c->flow_fold_cap); free_buffer(&c->d_flow_sel, &c->flow_sel_cap);
+    drop_flows(c);
     c->alerts_valid = false;
     c->bitmap_live = false; c->plan_waves = c->uplan_units = 0; c->fold_stale = true;
 }
@@ -1026,6 +1050,9 @@ int kmpgpu_set_option(kmpgpu_ctx *c, int key, int64_t value)
     case KMPGPU_OPT_KEEP_META:
         if (value != 0 && value != 1) return fail(KMPGPU_EINVAL, "keep meta must be 0 (kmpgpu_load_frames builds the arena alone) or 1 (and keeps the payloads' header metadata)");
         c->keep_meta = (int)value; return KMPGPU_OK;
+    case KMPGPU_OPT_FLOW_SLOTS:
+        if (value < 0) return fail(KMPGPU_EINVAL, "flow slots must be 0 (auto) or a power of two above the payload count");
+        c->flow_slots = value; return KMPGPU_OK;
     default:
         return fail(KMPGPU_EINVAL, "unknown option %d", key);
     }
@@ -1951,7 +1978,7 @@ int kmpgpu_set_meta(kmpgpu_ctx *c, const void *meta, uint64_t n_pkts, int on_dev
     if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_set_meta: ctx is NULL");
     if (on_device != 0 && on_device != 1) return fail(KMPGPU_EINVAL, "kmpgpu_set_meta: on_device is %d, not 0 or 1", on_device);
     if (c->fr_pending) return fail(KMPGPU_ESTATE, "kmpgpu_set_meta: the context sits between kmpgpu_load_frames_begin and _finish");
-    if (n_pkts == 0 && !meta) { c->has_meta = false; return KMPGPU_OK; }
+    if (n_pkts == 0 && !meta) { c->has_meta = false; drop_flows(c); return KMPGPU_OK; }
     if (!c->d_off || c->n_pkts == 0) return fail(KMPGPU_ESTATE, "kmpgpu_set_meta: no arena loaded");
     if (n_pkts != c->n_pkts)
         return fail(KMPGPU_EINVAL, "kmpgpu_set_meta: %llu records for the arena's %llu payloads", (unsigned long long)n_pkts, (unsigned long long)c->n_pkts);
@@ -1968,11 +1995,12 @@ int kmpgpu_set_meta(kmpgpu_ctx *c, const void *meta, uint64_t n_pkts, int on_dev
     hipError_t e = hipMemcpyAsync(d, meta, (size_t)n_pkts * sizeof(uint4), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
-        if (d != c->d_meta) (void)hipFree(d); else c->has_meta = false;       /* (copied over in place: what was there is gone) */
+        if (d != c->d_meta) (void)hipFree(d); else { c->has_meta = false; drop_flows(c); }       /* (copied over in place: what was there is gone) */
         return alloc_fail(e, "kmpgpu_set_meta: the metadata could not be copied");
     }
     if (d != c->d_meta) { free_buffer(&c->d_meta, &c->meta_cap); c->d_meta = d; c->meta_cap = n_pkts; }
     c->has_meta = true;
+    drop_flows(c);                                 /* they grouped the payloads by the records before these */
     return KMPGPU_OK;
 }
 
@@ -2071,6 +2099,182 @@ int kmpgpu_alerts_read(kmpgpu_ctx *c, kmpgpu_alert *out, uint64_t first, uint64_
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipMemcpyAsync(out, c->d_alerts + first, (size_t)n * sizeof(kmpgpu_alert), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return KMPGPU_OK;
+}
+
+int kmpgpu_flows_build(kmpgpu_ctx *c, uint32_t flags, uint64_t *n_flows, kmpgpu_timing *t)
+{
+    static_assert(sizeof(kmpgpu_flow) == 48, "kmpgpu_flow is the 48-byte record of kmpgpu.h");
+    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_flows_build: ctx is NULL");
+    if (n_flows) *n_flows = 0;
+    if (flags & ~KMPGPU_FLOW_DIRECTED) return fail(KMPGPU_EINVAL, "kmpgpu_flows_build: flags 0x%x hold a bit that is none of KMPGPU_FLOW_*", flags);
+    if (c->fr_pending) return fail(KMPGPU_ESTATE, "kmpgpu_flows_build: the context sits between kmpgpu_load_frames_begin and _finish");
+    const uint64_t n = c->n_pkts;
+    if (n && !c->has_meta) return fail(KMPGPU_ESTATE, "kmpgpu_flows_build: no packet metadata (KMPGPU_OPT_KEEP_META, kmpgpu_set_meta)");
+    if (n > 0xFFFFFFFEull) return fail(KMPGPU_EINVAL, "kmpgpu_flows_build: %llu payloads: flow ids are 32 bits wide", (unsigned long long)n);
+    const uint64_t slots = c->flow_slots ? (uint64_t)c->flow_slots : kmp_flow_auto_slots(n);
+    if ((slots & (slots - 1)) || slots <= n || slots > (1ull << 32))
+        return fail(KMPGPU_EINVAL, "kmpgpu_flows_build: KMPGPU_OPT_FLOW_SLOTS is %llu, no power of two above the %llu payloads (at most 2^32)",
+                    (unsigned long long)slots, (unsigned long long)n);
+    drop_flows(c);                                 /* the flows before this build are gone, whatever happens */
+    if (t) *t = kmpgpu_timing{};
+    if (n == 0) { c->flows_valid = true; return KMPGPU_OK; }
+    HIP_TRY(hipSetDevice(c->device));
+    hipError_t e = grow_buffer(&c->d_flow_table, &c->flow_table_cap, slots, EXACT);
+    if (e == hipSuccess) e = grow_buffer(&c->d_flow_first, &c->flow_first_cap, slots, EXACT);
+    if (e == hipSuccess) e = grow_buffer(&c->d_flow_of, &c->flow_of_cap, n, EIGHTH);
+    if (e == hipSuccess) e = grow_buffer(&c->fr_ws, &c->fr_ws_cap, (uint64_t)kmp_extract_ws_bytes(n), EIGHTH);
+    if (e == hipSuccess && !c->fr_tot) e = hipMalloc(&c->fr_tot, 2 * sizeof(unsigned long long));
+    if (e != hipSuccess)
+        return alloc_fail(e, "kmpgpu_flows_build: the table (%llu slots) and the ids (%llu payloads) could not be allocated", (unsigned long long)slots,
+                          (unsigned long long)n);
+    hipEvent_t e1;
+    HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_flow_table, 0, (size_t)slots * sizeof(uint32_t), c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_flow_first, 0xFF, (size_t)slots * sizeof(uint32_t), c->stream));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_flows_insert(c->d_meta, n, (flags & KMPGPU_FLOW_DIRECTED) != 0, c->d_flow_table, slots, c->d_flow_first, c->d_flow_of, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_flows_firsts(c->d_flow_first, c->d_flow_of, n, c->fr_ws, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_flows_scan(n, c->fr_ws, c->fr_tot, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(hipMemcpyAsync(c->h_small, c->fr_tot, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));         /* (pinned: no staging) */
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    unsigned long long tot[2] = {0, 0};
+    memcpy(tot, c->h_small, sizeof tot);
+    const uint64_t nf = tot[1];
+    if (nf == 0 || nf > n) return fail(KMPGPU_EHIP, "kmpgpu_flows_build: %llu flows for %llu payloads", (unsigned long long)nf, (unsigned long long)n);
+    e = grow_buffer(&c->d_flow_recs, &c->flow_recs_cap, nf, EIGHTH);
+    if (e != hipSuccess) return alloc_fail(e, "kmpgpu_flows_build: the records (%llu flows) could not be allocated", (unsigned long long)nf);
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_flows_number(c->d_meta, n, c->fr_ws, c->d_flow_of, c->d_flow_table, c->d_flow_recs, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_flows_assign(c->d_flow_table, c->d_flow_of, c->d_len, n, c->d_flow_recs, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (t) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+        t->kernel_ms = ms; t->launches = 6;
+    }
+    c->n_flows = nf; c->flows_valid = true;
+    if (n_flows) *n_flows = nf;
+    return KMPGPU_OK;
+}
+
+namespace {
+
+/* what kmpgpu_flows_read and kmpgpu_flow_ids_read share: elements [first, first + n) of `total`, `size` bytes each, from src to out */
+int flows_read_range(kmpgpu_ctx *c, const char *who, void *out, const void *src, size_t size, uint64_t first, uint64_t n, uint64_t total)
+{
+    if (!c) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
+    if (!c->flows_valid) return fail(KMPGPU_ESTATE, "%s: no flows (no kmpgpu_flows_build since the arena or its metadata were set)", who);
+    if (first > total || n > total - first)
+        return fail(KMPGPU_EINVAL, "%s: elements [%llu, +%llu) leave the %llu there are", who, (unsigned long long)first, (unsigned long long)n,
+                    (unsigned long long)total);
+    if (n == 0) return KMPGPU_OK;
+    if (!out) return fail(KMPGPU_EINVAL, "%s: out is NULL", who);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(out, (const uint8_t *)src + first * size, (size_t)n * size, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return KMPGPU_OK;
+}
+
+}  // namespace
+
+int kmpgpu_flows_read(kmpgpu_ctx *c, kmpgpu_flow *out, uint64_t first, uint64_t n)
+{
+    return flows_read_range(c, "kmpgpu_flows_read", out, c ? c->d_flow_recs : nullptr, sizeof(kmpgpu_flow), first, n, c ? c->n_flows : 0);
+}
+
+int kmpgpu_flow_ids_read(kmpgpu_ctx *c, uint32_t *out, uint64_t first, uint64_t n)
+{
+    return flows_read_range(c, "kmpgpu_flow_ids_read", out, c ? c->d_flow_of : nullptr, sizeof(uint32_t), first, n, c && c->flows_valid ? c->n_pkts : 0);
+}
+
+int kmpgpu_scan_flows(kmpgpu_ctx *c, int family, uint32_t scope, uint64_t *flow_counts_out, uint64_t *any_out, uint64_t *flow_hits_out,
+                      uint64_t *counts_out, kmpgpu_timing *t)
+{
+    const char *who = "kmpgpu_scan_flows";
+    if (!c) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
+    if (family < KMPGPU_ALERT_PATTERNS || family > KMPGPU_ALERT_CHAINS) return fail(KMPGPU_EINVAL, "%s: family %d is none of KMPGPU_ALERT_*", who, family);
+    if (scope != KMPGPU_FLOW_SCOPE_PACKET && scope != KMPGPU_FLOW_SCOPE_FLOW) return fail(KMPGPU_EINVAL, "%s: scope %u is none of KMPGPU_FLOW_SCOPE_*", who, scope);
+    const bool per_flow = scope == KMPGPU_FLOW_SCOPE_FLOW;
+    if (per_flow && family != KMPGPU_ALERT_RULES) return fail(KMPGPU_EINVAL, "%s: KMPGPU_FLOW_SCOPE_FLOW evaluates rules, family %d has none", who, family);
+    if (!c->flows_valid) return fail(KMPGPU_ESTATE, "%s: no flows (no kmpgpu_flows_build since the arena or its metadata were set)", who);
+    /* the rows of the family, as its own call checks them (no patterns for the patterns' own: the marking pass says so) */
+    const uint64_t n_rows = family_n_rows(c, family);
+    if (family != KMPGPU_ALERT_PATTERNS && (!c->d_patterns || c->n_pat == 0)) return fail(KMPGPU_ESTATE, "%s: no patterns set", who);
+    if (family != KMPGPU_ALERT_PATTERNS && n_rows == 0)
+        return fail(KMPGPU_ESTATE, "%s: no %s set", who, family == KMPGPU_ALERT_RULES ? "rules" : family == KMPGPU_ALERT_RELATIONS ? "relations" : "chains");
+    if (c->fr_pending) return fail(KMPGPU_ESTATE, "%s: the context sits between kmpgpu_load_frames_begin and _finish", who);
+    MarkPass p;
+    const int rc = begin_family(c, who, family, flow_counts_out, counts_out, t, &p);
+    if (rc || p.empty) return rc;
+    FamilyRows f;
+    const int rr = enqueue_family(c, who, family, p, /* profile_reduce = */ true, &f);
+    if (rr) return rr;
+    /* the folded matrix, rows of an even number of words as the reduce and the rules kernel read them: SCOPE_PACKET [family's rows x Sf]
+     * [flow_counts rows][any Sf]; SCOPE_FLOW [term rows x Sf][rule rows x Sf][flow_counts rules][any Sf] */
+    const uint64_t Wf = (c->n_flows + 63u) / 64u, Sf = (Wf + 1u) & ~1ull;
+    const uint64_t n_terms = (uint64_t)c->n_pat + c->n_rel + c->n_chains + c->n_hdr;
+    const uint64_t fold_rows = per_flow ? n_terms : n_rows, out_rows = per_flow ? n_terms + n_rows : n_rows;
+    const uint64_t words = out_rows * Sf + n_rows + Sf;
+    const hipError_t e = grow_buffer(&c->d_flow_fold, &c->flow_fold_cap, words, EIGHTH);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);      /* the pass is under way on the stream; the context stays usable */
+        return alloc_fail(e, "%s: the folded matrix (%llu bytes) could not be allocated", who, (unsigned long long)(words * 8u));
+    }
+    unsigned long long *d_rows = c->d_flow_fold + (per_flow ? n_terms * Sf : 0), *d_fc = c->d_flow_fold + out_rows * Sf, *d_any = d_fc + n_rows;
+    HIP_TRY(hipMemsetAsync(c->d_flow_fold, 0, (size_t)words * sizeof(unsigned long long), c->stream));
+    hipEvent_t e1;
+    HIP_TRY(profile_launch(c, &e1));
+    /* SCOPE_FLOW folds the whole hit matrix, and no any[] covers all of its rows */
+    HIP_TRY(kmp_launch_flows_fold(per_flow ? p.d_mat : f.d_rows, p.stride, (uint32_t)fold_rows, c->n_pkts, per_flow ? nullptr : f.d_any, c->d_flow_of,
+                                  c->n_flows, c->d_flow_fold, Sf, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(profile_launch(c, &e1));
+    if (per_flow)
+        HIP_TRY(kmp_launch_rules(c->d_flow_fold, Sf, c->n_flows, c->d_rule_heads, c->d_rule_quads, c->n_rules, d_rows, d_fc, d_any, c->stream));
+    else
+        HIP_TRY(kmp_launch_marks_reduce(d_rows, (uint32_t)n_rows, Sf, d_fc, d_any, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    if (flow_counts_out) HIP_TRY(hipMemcpyAsync(flow_counts_out, d_fc, (size_t)n_rows * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (any_out) HIP_TRY(hipMemcpyAsync(any_out, d_any, Wf * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, p.d_cnt, (size_t)c->n_pat * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (flow_hits_out) HIP_TRY(download_rows(c, flow_hits_out, d_rows, Wf, Sf, n_rows));
+    return finish_marking(c, p.launches + f.launches + 2u, t);
+}
+
+int kmpgpu_flows_select(kmpgpu_ctx *c, const void *flow_bits, int on_device, uint64_t *pkt_bits_out, const void **d_pkt_bits)
+{
+    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_flows_select: ctx is NULL");
+    if (d_pkt_bits) *d_pkt_bits = nullptr;
+    if (on_device != 0 && on_device != 1) return fail(KMPGPU_EINVAL, "kmpgpu_flows_select: on_device is %d, not 0 or 1", on_device);
+    if (!c->flows_valid) return fail(KMPGPU_ESTATE, "kmpgpu_flows_select: no flows (no kmpgpu_flows_build since the arena or its metadata were set)");
+    if (c->n_pkts == 0) return KMPGPU_OK;
+    if (!flow_bits) return fail(KMPGPU_EINVAL, "kmpgpu_flows_select: flow_bits is NULL");
+    if (on_device && ((uintptr_t)flow_bits & 7u)) return fail(KMPGPU_EINVAL, "kmpgpu_flows_select: the device bitmap is not 8-byte aligned");
+    HIP_TRY(hipSetDevice(c->device));
+    const uint64_t W = (c->n_pkts + 63u) / 64u, Wf = (c->n_flows + 63u) / 64u;
+    HIP_TRY(hipStreamSynchronize(c->stream));      /* the bitmap of the select before this one may still be read */
+    const hipError_t e = grow_buffer(&c->d_flow_sel, &c->flow_sel_cap, W + Wf, EIGHTH);
+    if (e != hipSuccess) return alloc_fail(e, "kmpgpu_flows_select: the bitmaps (%llu bytes) could not be allocated", (unsigned long long)((W + Wf) * 8u));
+    const unsigned long long *d_bits = (const unsigned long long *)flow_bits;
+    if (!on_device) {
+        HIP_TRY(hipMemcpyAsync(c->d_flow_sel + W, flow_bits, Wf * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+        d_bits = c->d_flow_sel + W;
+    }
+    HIP_TRY(kmp_launch_flows_expand(d_bits, c->d_flow_of, c->n_pkts, c->d_flow_sel, c->stream));
+    if (pkt_bits_out) HIP_TRY(hipMemcpyAsync(pkt_bits_out, c->d_flow_sel, W * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (d_pkt_bits) *d_pkt_bits = c->d_flow_sel;
     return KMPGPU_OK;
 }
 

@@ -23,6 +23,7 @@ OPT_REPACK = 7
 OPT_FUSED_UNIT = 8
 OPT_WHOLE_PAYLOAD = 9   # 1: a payload is text up to its end, not up to its first 0x00 (kmpgpu.h, "Semantics")
 OPT_KEEP_META = 10      # 1: load_pcap_frames keeps the payloads' header metadata (kmpgpu_pkt_meta) beside the index
+OPT_FLOW_SLOTS = 11     # slots of the hash table of build_flows: 0 = auto, or a power of two above the payload count
 KERNEL_AUTO, KERNEL_GENERAL, KERNEL_PACKED, KERNEL_FLAT = 0, 1, 2, 3
 MODE_FILTER, MODE_AUTOMATON = 0, 1
 PAT_NOCASE = 1          # kmpgpu_set_patterns_flags: ASCII letters match either case
@@ -30,6 +31,10 @@ ALERT_PATTERNS, ALERT_RULES, ALERT_RELATIONS, ALERT_CHAINS = 0, 1, 2, 3     # KM
 ALERT_FAMILIES = {"patterns": ALERT_PATTERNS, "rules": ALERT_RULES, "relations": ALERT_RELATIONS, "chains": ALERT_CHAINS}
 ALERT_DTYPE = np.dtype([("packet", "<u8"), ("index", "<u4"), ("reserved", "<u4")])     # kmpgpu_alert, 16 bytes
 ALERTS_ALL = 0xFFFFFFFFFFFFFFFF     # max_records: keep the whole list
+FLOW_DIRECTED = 1       # KMPGPU_FLOW_DIRECTED: the two directions of a conversation are two flows
+FLOW_SCOPES = {"packet": 0, "flow": 1}     # KMPGPU_FLOW_SCOPE_*
+FLOW_DTYPE = np.dtype([("first_packet", "<u8"), ("last_packet", "<u8"), ("n_packets", "<u8"), ("payload_bytes", "<u8"),
+                       ("first", META_DTYPE)])     # kmpgpu_flow, 48 bytes
 
 
 def device_count() -> int:
@@ -494,6 +499,95 @@ class GpuMatcher:
         out = np.zeros(max(int(n), 1), dtype=ALERT_DTYPE)
         gpu_check(self._g.kmpgpu_alerts_read(self._ctx, out.ctypes.data, int(first), int(n)), "kmpgpu_alerts_read")
         return out[: int(n)]
+
+    # -- flows ------------------------------------------------------------------------------------
+    def build_flows(self, directed: bool = False) -> int:
+        """Group the arena's payloads by the 5-tuple of their metadata, on the device (kmpgpu_flows_build): both directions of a
+        conversation are one flow unless ``directed``.  Returns the number of flows; they are numbered in the order of their first
+        payload and stay until the arena or its metadata change."""
+        n = C.c_uint64()
+        gpu_check(self._g.kmpgpu_flows_build(self._ctx, FLOW_DIRECTED if directed else 0, C.byref(n), None), "kmpgpu_flows_build")
+        self._n_flows = int(n.value)
+        return self._n_flows
+
+    def flows(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """Records [first, first + n) of the flows (kmpgpu_flows_read) as a FLOW_DTYPE array; n None: all from ``first`` on."""
+        n = self._flow_count() - int(first) if n is None else int(n)
+        out = np.zeros(max(n, 1), dtype=FLOW_DTYPE)
+        gpu_check(self._g.kmpgpu_flows_read(self._ctx, out.ctypes.data, int(first), max(n, 0)), "kmpgpu_flows_read")
+        return out[: max(n, 0)]
+
+    def flow_ids(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """flow_of[first .. first + n) (kmpgpu_flow_ids_read), uint32; n None: all from ``first`` on."""
+        n = self.arena_info()[0] - int(first) if n is None else int(n)
+        out = np.zeros(max(n, 1), dtype=np.uint32)
+        gpu_check(self._g.kmpgpu_flow_ids_read(self._ctx, out.ctypes.data, int(first), max(n, 0)), "kmpgpu_flow_ids_read")
+        return out[: max(n, 0)]
+
+    def _flow_count(self) -> int:
+        """The flows the context holds; KmpGpuError where it has none (the library is asked: it knows when they were dropped)."""
+        gpu_check(self._g.kmpgpu_flows_read(self._ctx, None, 0, 0), "kmpgpu_flows_read")
+        return getattr(self, "_n_flows", 0)
+
+    def scan_flows(self, family: str = "rules", scope: str = "packet", hits: bool = False) -> dict:
+        """The rows of a family in flow space (kmpgpu_scan_flows).  scope "packet": flow f is in row r where one of its payloads is in
+        row r of the family's own call; scope "flow" (rules only): every term row is folded first and the rule evaluated per flow -- its
+        contents may lie in different payloads of the connection.  ``flow_counts`` (uint64[rows]) flows in row r, ``any``
+        (bool[n_flows]), ``counts`` (uint64[n_pat]) as scan(), ``timing``; with hits=True also ``hits`` (bool[rows, n_flows])."""
+        if family not in ALERT_FAMILIES:
+            raise ValueError(f"family {family!r}: one of {sorted(ALERT_FAMILIES)} is needed")
+        if scope not in FLOW_SCOPES:
+            raise ValueError(f"scope {scope!r}: one of {sorted(FLOW_SCOPES)} is needed")
+        n = len(self.patterns)
+        rows = {"patterns": n, "rules": len(self.rules), "relations": len(self.relations), "chains": len(self.chains)}[family]
+        n_flows = getattr(self, "_n_flows", 0)
+        Wf = (n_flows + 63) // 64
+        row_counts = np.zeros(max(rows, 1), dtype=np.uint64)
+        counts = np.zeros(max(n, 1), dtype=np.uint64)
+        any_w = np.zeros(max(Wf, 1), dtype=np.uint64)
+        hit_w = np.zeros((rows, Wf) if hits and rows * Wf else 1, dtype=np.uint64)
+        t = Timing()
+        gpu_check(self._g.kmpgpu_scan_flows(self._ctx, ALERT_FAMILIES[family], FLOW_SCOPES[scope], row_counts.ctypes.data, any_w.ctypes.data,
+                                            hit_w.ctypes.data if hits else None, counts.ctypes.data, C.byref(t)), "kmpgpu_scan_flows")
+        out = {"flow_counts": row_counts[:rows], "counts": counts[:n], "timing": t,
+               "any": np.unpackbits(any_w[:Wf].view(np.uint8), bitorder="little")[:n_flows].astype(bool)}
+        if hits:
+            bits = np.unpackbits(hit_w.reshape(rows, Wf).view(np.uint8), axis=1, bitorder="little") if rows * Wf else np.zeros((rows, 0), np.uint8)
+            out["hits"] = bits[:, :n_flows].astype(bool)
+        return out
+
+    def select_flows(self, bits, device: bool = False):
+        """The payloads of the chosen flows as a payload bitmap (kmpgpu_flows_select): bits is bool[n_flows] or uint64[ceil(n_flows / 64)]
+        on the host, or a torch tensor of that many 64-bit words on this matcher's device.  Returns uint64[ceil(n_pkts / 64)] words as
+        load_selected takes them; with device=True a torch int64 tensor of them on the device instead, copied from the context's buffer."""
+        n_flows = self._flow_count()
+        n_pkts, _ = self.arena_info()
+        W, Wf = (n_pkts + 63) // 64, (n_flows + 63) // 64
+        on_device = 0
+        if isinstance(bits, np.ndarray):
+            words = select_words(bits, n_flows)
+            ptr = words.ctypes.data if Wf else None
+        else:                                     # a torch tensor
+            if bits.dtype.itemsize != 8 or bits.dtype.is_floating_point or bits.numel() != Wf or not bits.is_cuda \
+                    or bits.device.index != self.device or not bits.is_contiguous():
+                raise ValueError(f"bits: a contiguous tensor of {Wf} 64-bit words on the matcher's device is needed for {n_flows} flows")
+            import torch
+            torch.cuda.current_stream(bits.device).synchronize()             # complete before the call (kmpgpu.h)
+            on_device, ptr = 1, (bits.data_ptr() if Wf else None)
+        out = np.zeros(max(W, 1), dtype=np.uint64)
+        d_ptr = C.c_void_p()
+        gpu_check(self._g.kmpgpu_flows_select(self._ctx, ptr, on_device, None if device else out.ctypes.data, C.byref(d_ptr)),
+                  "kmpgpu_flows_select")
+        if not device:
+            return out[:W]
+        import torch
+        if not W:
+            return torch.zeros(0, dtype=torch.int64, device=f"cuda:{self.device}")
+
+        class _Words:                             # the context's buffer, as torch reads foreign device memory
+            __cuda_array_interface__ = {"shape": (W,), "typestr": "<i8", "data": (int(d_ptr.value), False), "version": 2}
+        # the buffer holds until the next select_flows: a copy of the caller's own outlives it
+        return torch.as_tensor(_Words(), device=f"cuda:{self.device}").clone()
 
     # -- synthetic input (bench / tests) ---------------------------------------------------------
     def synth_fill(self, d_arena, d_off, d_len, sp: SynthParams, first_pkt_id: int = 0) -> None:
