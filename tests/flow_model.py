@@ -3,6 +3,9 @@ include/kmpgpu.h ("Flows"): with M = meta[k], e_src = src_ip << 16 | src_port an
     key(k) = (proto, min(e_src, e_dst), max(e_src, e_dst))      by default
     key(k) = (proto, e_src, e_dst)                              directed
 two payloads are one flow iff their keys are equal, flows are numbered in the order of their first payload.
+
+flow_of / records are that definition, record by record.  flow_of_np / records_np give the same arrays from numpy's sort of the key
+columns, for the captures of hundreds of thousands of payloads that tests/test_gpu_rows_scale.py builds.
 """
 import numpy as np
 
@@ -44,6 +47,58 @@ def records(meta, lens, directed=False):
         r["last_packet"] = k
         r["n_packets"] += 1
         r["payload_bytes"] += int(lens[k])
+    return recs
+
+
+def key_columns(meta, directed=False):
+    """uint64[n, 3]: the key's columns (proto, e_src, e_dst), the endpoints swapped into ascending order unless directed"""
+    es = meta["src_ip"].astype(np.uint64) << np.uint64(16) | meta["src_port"].astype(np.uint64)
+    ed = meta["dst_ip"].astype(np.uint64) << np.uint64(16) | meta["dst_port"].astype(np.uint64)
+    if not directed:
+        es, ed = np.minimum(es, ed), np.maximum(es, ed)
+    return np.stack([meta["proto"].astype(np.uint64), es, ed], axis=1)
+
+
+def _first_and_flow(meta, directed):
+    """(first payload of every flow, ascending; uint32[n_pkts] flow of every payload): the distinct rows of the key columns, renumbered by
+    the index at which each appears first"""
+    if len(meta) == 0:
+        return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.uint32)
+    _, first, inv = np.unique(key_columns(meta, directed), axis=0, return_index=True, return_inverse=True)
+    order = np.argsort(first, kind="stable")          # the distinct keys in the order of their first payload
+    rank = np.empty(len(first), dtype=np.uint32)
+    rank[order] = np.arange(len(first), dtype=np.uint32)
+    return first[order].astype(np.int64), rank[np.asarray(inv).reshape(-1)]
+
+
+def flow_of_np(meta, directed=False):
+    """flow_of without the Python loop: for hundreds of thousands of payloads.  tests/test_flow_model.py holds it to flow_of."""
+    return _first_and_flow(meta, directed)[1]
+
+
+def records_np(meta, lens, directed=False):
+    """records without the Python loop, byte for byte the same"""
+    return flows_np(meta, lens, directed)[1]
+
+
+def flows_np(meta, lens, directed=False):
+    """(flow_of_np, records_np) from one sort of the keys"""
+    first, fo = _first_and_flow(meta, directed)
+    return fo, _records_np(meta, lens, first, fo)
+
+
+def _records_np(meta, lens, first, fo):
+    recs = np.zeros(len(first), dtype=FLOW_DTYPE)
+    if len(first) == 0:
+        return recs
+    k = np.arange(len(fo), dtype=np.uint64)
+    recs["first_packet"] = first
+    recs["first"] = meta[first]
+    recs["n_packets"] = np.bincount(fo, minlength=len(first))
+    bytes_, last = np.zeros(len(first), dtype=np.uint64), np.zeros(len(first), dtype=np.uint64)
+    np.add.at(bytes_, fo, np.asarray(lens).astype(np.uint64))
+    np.maximum.at(last, fo, k)
+    recs["payload_bytes"], recs["last_packet"] = bytes_, last
     return recs
 
 

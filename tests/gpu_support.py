@@ -1,8 +1,10 @@
 """What the GPU test modules share: the context fixture, the options' defaults, the kernel selections, borrowed arenas with dirty
-padding, the command lines, and the exact comparisons of a pass's outputs with tests/match_model.py's answers.
+padding, the frame library of tests/prep_model.py and its loader, the command lines, and the exact comparisons of a pass's outputs
+with the answers of tests/match_model.py and tests/flow_model.py.
 
 Import from this module before the package, for the reason given below.
 """
+import ctypes as C
 import os
 import subprocess
 
@@ -17,8 +19,9 @@ from conftest import DATA
 import torch  # noqa: E402
 
 import match_model as MM  # noqa: E402
+import prep_model as PM  # noqa: E402
 from multithreading_string_matching_amd import _lib  # noqa: E402
-from multithreading_string_matching_amd.host import HostArena  # noqa: E402
+from multithreading_string_matching_amd.host import META_DTYPE, HostArena  # noqa: E402
 from multithreading_string_matching_amd.matcher import (  # noqa: E402
     KERNEL_AUTO, KERNEL_FLAT, KERNEL_GENERAL, KERNEL_PACKED, MODE_AUTOMATON, MODE_FILTER, OPT_ACCUMULATE, OPT_BLOCKS_PER_CU, OPT_DEPTH,
     OPT_FUSED, OPT_FUSED_UNIT, OPT_KERNEL, OPT_MODE, OPT_NONTEMPORAL, OPT_REPACK, OPT_WHOLE_PAYLOAD, GpuMatcher)
@@ -71,6 +74,84 @@ def load(gm, payloads, slots=None):
         gm.load_arena(HostArena.from_payloads(payloads))
         return None
     return attach_slots(gm, payloads, slots)
+
+
+# ------------------------------------------------------------------------------------------------
+# frames: the library of tests/prep_model.py, and kmpgpu_load_frames over an index into it
+# ------------------------------------------------------------------------------------------------
+class FrameLib:
+    """The frame library with the oracle's verdict on every frame under both rules."""
+
+    def __init__(self, oracle):
+        self.frames = PM.frame_library()
+        self.blob, self.boff, self.cap = PM.library_blob(self.frames)
+        self.K = len(self.frames)
+        self.tags = [PM.tag(t) for t in range(self.K)]
+        self.rule = {}
+        for proto in ("udp", "tcp"):
+            poff, plen = PM.library_rule(self.frames, proto, oracle.dump)
+            self.rule[proto] = (poff, plen, PM.library_payloads(self.frames, poff, plen))
+
+
+@pytest.fixture(scope="module")
+def lib(oracle):
+    return FrameLib(oracle)
+
+
+def load_frames(gm, file_bytes, frame_off, caplen, proto, two_steps=False):
+    G = _lib.gpu_lib()
+    frame_off = np.ascontiguousarray(frame_off, dtype=np.uint64)
+    caplen = np.ascontiguousarray(caplen, dtype=np.uint32)
+    n = C.c_uint64(12345)
+    args = (gm._ctx, file_bytes.ctypes.data_as(_lib.u8p), file_bytes.size, frame_off.ctypes.data_as(_lib.u64p), caplen.ctypes.data_as(_lib.u32p),
+            len(frame_off), 1 if proto == "tcp" else 0)
+    if two_steps:
+        _lib.gpu_check(G.kmpgpu_load_frames_begin(*args), "kmpgpu_load_frames_begin")
+        _lib.gpu_check(G.kmpgpu_load_frames_uploaded(gm._ctx), "kmpgpu_load_frames_uploaded")
+        _lib.gpu_check(G.kmpgpu_load_frames_finish(gm._ctx, C.byref(n)), "kmpgpu_load_frames_finish")
+    else:
+        _lib.gpu_check(G.kmpgpu_load_frames(*args, C.byref(n)), "kmpgpu_load_frames")
+    gm._keep = None
+    return int(n.value)
+
+
+# ------------------------------------------------------------------------------------------------
+# flows
+# ------------------------------------------------------------------------------------------------
+FLOW_A, FLOW_B = 0x0A000001, 0xC0A80101
+ONES = 0xFFFFFFFFFFFFFFFF
+
+
+def meta_of_flows(flow, seed=1):
+    """one record per payload for the flow numbers given: flow f talks from FLOW_A + f, port 1000 + f % 7, and every third payload of a
+    flow is the answer (source and destination swapped)"""
+    flow = np.asarray(flow, dtype=np.int64)
+    rng = np.random.default_rng(seed)
+    back = rng.integers(0, 3, len(flow)) == 0
+    meta = np.zeros(len(flow), dtype=META_DTYPE)
+    src, dst, sp, dp = FLOW_A + flow, np.full(len(flow), FLOW_B), 1000 + flow % 7, np.full(len(flow), 53)
+    meta["src_ip"], meta["dst_ip"] = np.where(back, dst, src), np.where(back, src, dst)
+    meta["src_port"], meta["dst_port"] = np.where(back, dp, sp), np.where(back, sp, dp)
+    meta["proto"] = 17
+    return meta
+
+
+def check_fold(m, family, scope, want, counts=None):
+    res = m.scan_flows(family, scope, hits=True)
+    bad = np.argwhere(res["hits"] != want)
+    assert bad.size == 0, [(int(r), int(f), bool(want[r, f])) for r, f in bad[:8]]
+    assert res["flow_counts"].tolist() == want.sum(axis=1).tolist()
+    assert res["any"].tolist() == want.any(axis=0).tolist()
+    if counts is not None:
+        assert res["counts"].tolist() == list(counts)
+    # the raw words: the bits at n_flows and above are 0 in every word
+    Wf = (want.shape[1] + 63) // 64
+    hit_w, any_w = np.full((want.shape[0], Wf), ONES, dtype=np.uint64), np.full(Wf, ONES, dtype=np.uint64)
+    fam = {"patterns": 0, "rules": 1, "relations": 2, "chains": 3}[family]
+    _lib.gpu_check(m._g.kmpgpu_scan_flows(m._ctx, fam, 1 if scope == "flow" else 0, None, any_w.ctypes.data, hit_w.ctypes.data, None, None),
+                   "kmpgpu_scan_flows")
+    assert np.array_equal(hit_w, MM.words(want)) and np.array_equal(any_w, MM.words(want.any(axis=0)))
+    return res
 
 
 # ------------------------------------------------------------------------------------------------

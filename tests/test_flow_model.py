@@ -108,3 +108,63 @@ def test_fixture_flows(pcap, mode):
     assert int(FM.records(meta, lens)["n_packets"].max()) == largest
     if (pcap, mode) == ("udp_1000.pcap", "tcp"):
         assert sorted(set(meta["proto"].tolist())) == [6, 17]         # the protocol byte keeps them apart
+
+
+# ------------------------------------------------------------------------------------------------
+# the vectorised model (flow_of_np, records_np) against the dict model, byte for byte
+# ------------------------------------------------------------------------------------------------
+def _same_as_the_dict_model(meta, lens):
+    for directed in (False, True):
+        fo = FM.flow_of_np(meta, directed)
+        assert fo.dtype == np.uint32 and np.array_equal(fo, FM.flow_of(meta, directed))
+        recs = FM.records_np(meta, lens, directed)
+        assert recs.dtype == FM.FLOW_DTYPE and recs.tobytes() == FM.records(meta, lens, directed).tobytes()
+
+
+def test_vectorised_model_on_the_hand_written_cases():
+    base = (A, B, 1000, 80, 6)
+    cases = [
+        [(A, B, 1000, 80, 6), (B, A, 80, 1000, 6), (A, B, 1000, 80, 6), (C, A, 5, 6, 17)],
+        [base, (C, B, 1000, 80, 6), (A, C, 1000, 80, 6), (A, B, 1001, 80, 6), (A, B, 1000, 81, 6), (A, B, 1000, 80, 17), base],
+        [(A, B, 1, 2, 17), (A, B, 2, 1, 17), (B, A, 2, 1, 17), (B, A, 1, 2, 17)],
+        [(A, A, 1, 2, 17), (A, A, 2, 1, 17)],
+        [(C, A, 9, 9, 17), (A, B, 1, 2, 17), (C, A, 9, 9, 17), (B, C, 3, 4, 6), (A, B, 1, 2, 17)],
+        [(0, 0, 0, 0, 0), (0xFFFFFFFF, 0xFFFFFFFF, 65535, 65535, 255), (0, 0xFFFFFFFF, 0, 65535, 0), (0xFFFFFFFF, 0, 65535, 0, 0)],
+        [base],
+        [],
+    ]
+    for recs in cases:
+        meta = _meta(*recs)
+        _same_as_the_dict_model(meta, [10 * (k + 1) for k in range(len(recs))])
+    # `reserved` is no part of the key, and travels with the first payload's record
+    meta = _meta(base, base, (B, A, 80, 1000, 6))
+    meta["reserved"][0] = (7, 0, 0)
+    meta["reserved"][2] = (0, 0, 9)
+    _same_as_the_dict_model(meta, [1, 2, 3])
+    assert FM.flow_of_np(meta).tolist() == [0, 0, 0] and FM.records_np(meta, [1, 2, 3])["first"].tobytes() == meta[:1].tobytes()
+    assert FM.flow_of_np(meta[:0]).shape == (0,) and FM.records_np(meta[:0], []).shape == (0,)
+
+
+@pytest.mark.parametrize("pcap,mode", sorted(FIXTURES))
+def test_vectorised_model_on_the_fixtures(pcap, mode):
+    n, directed, bidir, _ = FIXTURES[(pcap, mode)]
+    pay, meta = HM.capture(HM.pcap_frames(os.path.join(DATA, pcap)), mode)
+    _same_as_the_dict_model(meta, [len(t) for t in pay])
+    assert len(FM.records_np(meta, [len(t) for t in pay], True)) == directed and int(FM.flow_of_np(meta).max()) + 1 == bidir
+
+
+@pytest.mark.parametrize("seed,n,n_keys", [(1, 5000, 40), (2, 3000, 700), (3, 4001, 4001)])
+def test_vectorised_model_on_random_records(seed, n, n_keys):
+    """a few thousand records over few keys, so that most payloads join a flow that exists, in both directions; the fields are drawn
+    from small domains, so that keys differ in one field only and the swap of an undirected key meets another flow's key"""
+    rng = np.random.default_rng(seed)
+    pool = HM.meta_array([(int(rng.choice([A, B, C, 0, 0xFFFFFFFF])), int(rng.choice([A, B, C, 0xFFFFFFFF])), int(rng.choice([0, 1, 80, 65535])),
+                           int(rng.choice([0, 1, 80, 65535])) if n_keys < 1000 else int(rng.integers(1 << 16)), int(rng.choice([6, 17, 255]))) for _ in range(n_keys)])
+    meta = pool[rng.integers(0, n_keys, n)]
+    back = rng.random(n) < 0.4                         # the answer: source and destination swapped
+    meta["src_ip"][back], meta["dst_ip"][back] = meta["dst_ip"][back], meta["src_ip"][back]
+    meta["src_port"][back], meta["dst_port"][back] = meta["dst_port"][back], meta["src_port"][back]
+    meta["reserved"] = rng.integers(0, 256, (n, 3))
+    lens = rng.integers(0, 70000, n)
+    _same_as_the_dict_model(meta, lens)
+    assert len(FM.records_np(meta, lens, True)) > len(FM.records_np(meta, lens)) > 1

@@ -10,7 +10,8 @@ import pytest
 
 from conftest import DATA
 
-from gpu_support import KERNELS, attach_slots, gm, load, reset, run_cli, strip_elapsed, torch  # noqa: F401  (gm: the context fixture)
+from gpu_support import (FLOW_A as A, FLOW_B as B, KERNELS, ONES, attach_slots, check_fold as _check_fold, gm, load,  # noqa: F401  (gm: the context fixture)
+                         meta_of_flows as _meta_of_flows, reset, run_cli, strip_elapsed, torch)
 
 import chain_model as CM
 import flow_model as FM
@@ -18,7 +19,7 @@ import header_model as HM
 import match_model as MM
 from multithreading_string_matching_amd import _lib
 from multithreading_string_matching_amd._lib import KmpGpuError
-from multithreading_string_matching_amd.host import META_DTYPE, HostArena
+from multithreading_string_matching_amd.host import HostArena
 from multithreading_string_matching_amd.matcher import (FLOW_DTYPE, OPT_FLOW_SLOTS, OPT_FUSED, OPT_KEEP_META, OPT_KERNEL, OPT_REPACK,
                                                         OPT_WHOLE_PAYLOAD, GpuMatcher)
 from test_flow_model import FIXTURES
@@ -27,8 +28,6 @@ pytestmark = pytest.mark.gpu
 
 EINVAL, ESTATE = -2, -3
 TILE = 256 * 4                # KMP_SCAN_TILE
-ONES = 0xFFFFFFFFFFFFFFFF
-A, B = 0x0A000001, 0xC0A80101
 SIZES = [1, 63, 64, 65, 127, 128, 129, 255, 256, 257, TILE - 1, TILE, TILE + 1, 2 * TILE + 1]
 SHAPE_PATS = [b"GET", b"zz"]
 H = HM.header
@@ -36,20 +35,6 @@ H = HM.header
 
 def raises(code, text):
     return pytest.raises(KmpGpuError, match=rf"\({code}\).*{text}")
-
-
-def _meta_of_flows(flow, seed=1):
-    """one record per payload for the flow numbers given: flow f talks from A + f, port 1000 + f % 7, and every third payload of a flow
-    is the answer (source and destination swapped)"""
-    flow = np.asarray(flow, dtype=np.int64)
-    rng = np.random.default_rng(seed)
-    back = rng.integers(0, 3, len(flow)) == 0
-    meta = np.zeros(len(flow), dtype=META_DTYPE)
-    src, dst, sp, dp = A + flow, np.full(len(flow), B), 1000 + flow % 7, np.full(len(flow), 53)
-    meta["src_ip"], meta["dst_ip"] = np.where(back, dst, src), np.where(back, src, dst)
-    meta["src_port"], meta["dst_port"] = np.where(back, dp, sp), np.where(back, sp, dp)
-    meta["proto"] = 17
-    return meta
 
 
 def _check_build(m, meta, lens, directed=False, n_flows=None):
@@ -61,24 +46,6 @@ def _check_build(m, meta, lens, directed=False, n_flows=None):
     r = m.flows()
     assert r.dtype == FLOW_DTYPE and r.tobytes() == recs.tobytes(), [i for i in range(len(recs)) if r[i] != recs[i]][:4]
     return fo, recs
-
-
-def _check_fold(m, family, scope, want, counts=None):
-    res = m.scan_flows(family, scope, hits=True)
-    bad = np.argwhere(res["hits"] != want)
-    assert bad.size == 0, [(int(r), int(f), bool(want[r, f])) for r, f in bad[:8]]
-    assert res["flow_counts"].tolist() == want.sum(axis=1).tolist()
-    assert res["any"].tolist() == want.any(axis=0).tolist()
-    if counts is not None:
-        assert res["counts"].tolist() == list(counts)
-    # the raw words: the bits at n_flows and above are 0 in every word
-    Wf = (want.shape[1] + 63) // 64
-    hit_w, any_w = np.full((want.shape[0], Wf), ONES, dtype=np.uint64), np.full(Wf, ONES, dtype=np.uint64)
-    fam = {"patterns": 0, "rules": 1, "relations": 2, "chains": 3}[family]
-    _lib.gpu_check(m._g.kmpgpu_scan_flows(m._ctx, fam, 1 if scope == "flow" else 0, None, any_w.ctypes.data, hit_w.ctypes.data, None, None),
-                   "kmpgpu_scan_flows")
-    assert np.array_equal(hit_w, MM.words(want)) and np.array_equal(any_w, MM.words(want.any(axis=0)))
-    return res
 
 
 # ------------------------------------------------------------------------------------------------

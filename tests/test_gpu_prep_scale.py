@@ -40,14 +40,12 @@ cases are large enough for the bad entry as well.
 
 Run on a real MI355X:  python -m pytest tests -m gpu
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
-from gpu_support import gm, reset  # noqa: E402,F401  (torch first)
+from gpu_support import gm, lib, load_frames as _load_frames, reset  # noqa: E402,F401  (torch first; gm, lib: fixtures)
 
 import torch  # noqa: E402
 
@@ -74,42 +72,6 @@ def _scan(gm, kernel):
     gm.set_option(OPT_KERNEL, KERNEL_AUTO if kernel == KERNEL_FUSED else kernel)
     gm.set_option(OPT_FUSED, 1 if kernel == KERNEL_FUSED else 2 if kernel == KERNEL_AUTO else 0)
     return gm.scan()[0]
-
-
-class Lib:
-    """The frame library with the oracle's verdict on every frame under both rules."""
-
-    def __init__(self, oracle):
-        self.frames = PM.frame_library()
-        self.blob, self.boff, self.cap = PM.library_blob(self.frames)
-        self.K = len(self.frames)
-        self.tags = [PM.tag(t) for t in range(self.K)]
-        self.rule = {}
-        for proto in ("udp", "tcp"):
-            poff, plen = PM.library_rule(self.frames, proto, oracle.dump)
-            self.rule[proto] = (poff, plen, PM.library_payloads(self.frames, poff, plen))
-
-
-@pytest.fixture(scope="module")
-def lib(oracle):
-    return Lib(oracle)
-
-
-def _load_frames(gm, file_bytes, frame_off, caplen, proto, two_steps=False):
-    G = _lib.gpu_lib()
-    frame_off = np.ascontiguousarray(frame_off, dtype=np.uint64)
-    caplen = np.ascontiguousarray(caplen, dtype=np.uint32)
-    n = C.c_uint64(12345)
-    args = (gm._ctx, file_bytes.ctypes.data_as(_lib.u8p), file_bytes.size, frame_off.ctypes.data_as(_lib.u64p), caplen.ctypes.data_as(_lib.u32p),
-            len(frame_off), 1 if proto == "tcp" else 0)
-    if two_steps:
-        _lib.gpu_check(G.kmpgpu_load_frames_begin(*args), "kmpgpu_load_frames_begin")
-        _lib.gpu_check(G.kmpgpu_load_frames_uploaded(gm._ctx), "kmpgpu_load_frames_uploaded")
-        _lib.gpu_check(G.kmpgpu_load_frames_finish(gm._ctx, C.byref(n)), "kmpgpu_load_frames_finish")
-    else:
-        _lib.gpu_check(G.kmpgpu_load_frames(*args, C.byref(n)), "kmpgpu_load_frames")
-    gm._keep = None
-    return int(n.value)
 
 
 def _first_diff(a, b):
