@@ -743,6 +743,73 @@ int  kmpgpu_scan_flows(kmpgpu_ctx *ctx, int family /* KMPGPU_ALERT_* */, uint32_
 int  kmpgpu_flows_select(kmpgpu_ctx *ctx, const void *flow_bits /* uint64_t[Wf] */, int on_device, uint64_t *pkt_bits_out /* host [W] or NULL */,
                          const void **d_pkt_bits /* or NULL */);
 
+/* Flow seams: contents split across two payloads of a flow.  A per-payload matcher is walked past by cutting a content in two ("GET /adm"
+ * ends one TCP segment, "in HTTP/1.1" starts the next): "/admin" hits in neither payload, and no flow-scope rule that names it fires.  The
+ * overlap construction closes that gap without reassembly: for every payload that has a predecessor in its flow and direction, a SEAM -- a
+ * small payload made of the predecessor's last `reach` bytes followed by this payload's first `reach` bytes -- goes into a packed arena
+ * that a second context owns, and everything the library has scans the seams.  A pattern of up to reach + 1 bytes that straddles the
+ * boundary lies inside the seam.
+ * Definitions.  src holds built flows (kmpgpu_flows_build); e_src, e_dst, flow_of and kmpgpu_flow.first as defined there.
+ *     dir(k)  = 0 where payload k's (e_src, e_dst) equal those of its flow's first payload (kmpgpu_flow.first), else 1.  Under
+ *               KMPGPU_FLOW_DIRECTED it is always 0, and a flow whose two endpoints are equal has dir 0 throughout.
+ *     pred(k) = the largest j < k with flow_of[j] == flow_of[k] and dir(j) == dir(k): a TCP stream is per direction, so an undirected flow
+ *               has two chains.  A payload without a predecessor has no seam.
+ * Seams are numbered in ascending order of `next`.  With prev = pred(next), tail_len = min(reach, L_prev), head_len = min(reach, L_next)
+ * (the index's lengths, whatever KMPGPU_OPT_WHOLE_PAYLOAD says), seam j is the raw bytes
+ *     payload_prev[L_prev - tail_len : L_prev] ++ payload_next[0 : head_len]
+ * There is one seam per payload with a predecessor, also when it comes to 0 bytes (an empty payload owning one zero slot), so
+ * n_seams == n_pkts - (number of distinct (flow, dir)).  The order is capture order, not sequence numbers, and no atomic decides it: the
+ * arena and every record are byte-identical from run to run.  reach is 1 .. KMPGPU_MAX_PATTERN_LEN - 1 = 98.
+ *
+ * kmpgpu_load_seams.  dst ends up in the state kmpgpu_load_selected leaves it in: an owned packed arena of the n_seams seams, slots of
+ * max(16, round_up(len, 16)) bytes back to back from offset 0, 0x00 behind every seam's end, padding known clean, packet-start bitmap and
+ * plans rebuilt, the nocase fold stale.  dst gets metadata, meta[j] = src.meta[next_j] (header predicates of dst's rules see the segment
+ * the seam leads into), and keeps the records kmpgpu_seam[n_seams] and seam_flow[j] = src.flow_of[next_j] in device buffers it owns;
+ * kmpgpu_seams_read copies records [first, first + n) to out, ranges and errors as kmpgpu_flows_read.  Whatever replaces or releases dst's
+ * arena (kmpgpu_load_arena, kmpgpu_attach_arena, kmpgpu_load_frames, kmpgpu_load_selected and kmpgpu_load_seams as dst) drops the seam
+ * state; the buffers stay for the next build.  *n_seams (may be NULL) = the number of seams.  n_pkts == 0, or no seam at all (every flow
+ * direction a single payload): dst is left without an arena, the call returns KMPGPU_OK with *n_seams = 0, and an empty seam list exists.
+ * Untouched: src is not written, and every output of it is bit-identical before and after.  The source is whatever src scans now (loaded,
+ * attached, extracted, repacked or kept in place).  Of its arena no byte outside the slots of prev and next is read: the gather loads
+ * aligned 16-byte units that hold a byte of a tail or a head, so a borrowed arena owes nothing behind its last slot.
+ * A SEAM IS A PAYLOAD OF ITS OWN.  dst scans it under dst's own patterns, flags, windows (offsets count from the seam's first byte) and E
+ * rule.  Under the default strlen rule a 0x00 in the seam ends the seam's text; a 0x00 in prev more than `reach` bytes in front of prev's
+ * end is not seen, so the seam rows may hold a match that lies in prev's bytes behind prev's first 0x00 -- bytes src's own scan never
+ * reaches.  Under KMPGPU_OPT_WHOLE_PAYLOAD on both contexts the seam rows hold nothing that the concatenated stream does not hold.
+ * Ordering: synchronous.  Waits for dst's stream and for src's, as kmpgpu_load_selected does, and works on dst's stream; the scratch is
+ * the one dst keeps for kmpgpu_load_frames plus a sort buffer of its own (24 bytes per source payload and rocPRIM's temporary storage).
+ * Errors: dst == src, a NULL context, reach outside 1 .. 98, contexts on different devices: KMPGPU_EINVAL; src without built flows:
+ * KMPGPU_ESTATE ("no flows"); either context between kmpgpu_load_frames_begin and _finish: KMPGPU_ESTATE; after each of these dst keeps its
+ * arena.  After an allocation failure (KMPGPU_ENOMEM / KMPGPU_EHIP) dst is without an arena and both contexts stay usable.
+ * kmpgpu_last_timing(dst): kernel_ms from the keys kernel to the gather's end (the host's read of the totals lies inside), launches = 7
+ * (keys, the sort counted as one, pred, two scan kernels, index, gather; 5 where there is no seam).  Under kmpgpu_profile_begin on dst the
+ * entries are keys, sort, pred + the two scan kernels, index, gather.
+ *
+ * kmpgpu_scan_flows_seams(src, seams, ...) is kmpgpu_scan_flows(src, KMPGPU_ALERT_RULES, KMPGPU_FLOW_SCOPE_FLOW, ...) with one step added:
+ * before the rules kernel, the pattern rows of a marking pass over `seams` (the pass of kmpgpu_scan_packets(seams), on seams' stream, which
+ * the call waits for as kmpgpu_counts_add does) are folded into the same folded matrix through seam_flow, by the fold kernel a second time:
+ *     term[i][f] = OR over the payloads k of flow f of hit_src[i][k]  |  OR over the seams j of flow f of hit_seams[i][j]      (i < n_pat)
+ * Relation, chain and header terms stay src's own, and counts_out stays what kmpgpu_scan(src) returns: cross-boundary matches are not
+ * counted.  One boundary per seam: a content that spans three payloads is not found.  Outputs and layout as kmpgpu_scan_flows.
+ * Preconditions: `seams` holds a seam list built from src's CURRENT flows (every kmpgpu_flows_build and everything that drops the flows
+ * starts a new generation; a list of another generation or another context: KMPGPU_ESTATE), both contexts sit on one device (otherwise
+ * KMPGPU_EINVAL) and hold the same pattern bytes and flags (otherwise KMPGPU_ESTATE); everything else as kmpgpu_scan_flows on src and as
+ * kmpgpu_scan_packets on seams.  *t: as kmpgpu_scan_flows, launches = what kmpgpu_scan_flows reports + what kmpgpu_scan_packets(seams)
+ * reports + 1 (the second fold).  With an empty seam list the call returns exactly what kmpgpu_scan_flows(SCOPE_FLOW) returns, launches
+ * included.
+ * Every existing call keeps its outputs, launches and buffers, with or without these calls having run.
+ * Cost (the figures of tools/seams.py go to profiles/seams.txt): 24 bytes per source payload sorted, one read of the two
+ * slots' ends per seam, 2 x reach bytes written per seam; the scan of the seams is a scan of n_seams small payloads. */
+typedef struct kmpgpu_seam {        /* 24 bytes */
+    uint64_t prev, next;            /* payload indices in src: the seam joins the end of prev to the start of next */
+    uint32_t tail_len, head_len;    /* min(reach, L_prev), min(reach, L_next); the seam payload is tail_len + head_len bytes */
+} kmpgpu_seam;
+int  kmpgpu_load_seams(kmpgpu_ctx *dst, kmpgpu_ctx *src, uint32_t reach, uint64_t *n_seams /* or NULL */);
+int  kmpgpu_seams_read(kmpgpu_ctx *dst, kmpgpu_seam *out, uint64_t first, uint64_t n);
+int  kmpgpu_scan_flows_seams(kmpgpu_ctx *src, kmpgpu_ctx *seams, uint64_t *flow_counts_out /* [n_rules] or NULL */,
+                             uint64_t *any_out /* [Wf] or NULL */, uint64_t *flow_hits_out /* [n_rules * Wf] or NULL */,
+                             uint64_t *counts_out /* [n_pat] or NULL: as kmpgpu_scan(src) */, kmpgpu_timing *t /* or NULL */);
+
 /* Fill a device arena with the synthetic payloads of kmp_synth.h (benchmark input S1/S2):
  * packet ids first_pkt_id .. first_pkt_id + n_pkts - 1 at the slots of the given device index. */
 int  kmpgpu_synth_fill(kmpgpu_ctx *ctx, void *d_arena, const void *d_pkt_off, const void *d_pkt_len,

@@ -71,6 +71,13 @@
  * than one shard (a flow would be cut at a shard's edge), KMPGPU_FLOW_ALERTS_FILE without a rules file, a path that cannot be written.
  * stdout is what it is without the variables.
  *
+ * KMPGPU_FLOW_SEAMS=<reach>, together with KMPGPU_FLOW_ALERTS_FILE: contents split across two consecutive payloads of a flow direction
+ * count as present in the flow.  A second context on the shard's device gets the seams of the capture (kmpgpu_load_seams: per payload
+ * with a predecessor in its flow and direction, the predecessor's last <reach> bytes and the payload's first <reach> bytes) and the same
+ * patterns under the same text rule and case rule, and the flow alerts come from kmpgpu_scan_flows_seams.  The windows of
+ * KMPGPU_WINDOWS_FILE count from a payload's start and stay with the payloads: the seams are scanned without windows.  Refused with a
+ * message on stderr and exit 1, before any GPU work: the variable without KMPGPU_FLOW_ALERTS_FILE, a reach that is no number in 1..98.
+ *
  * KMPGPU_NOCASE=1: every pattern matches case-insensitively (ASCII letters; kmpgpu_set_patterns_flags), in the counts and in
  * the offsets file alike; the report prints every token as written in the pattern file.
  *
@@ -108,6 +115,7 @@ typedef struct cli_options {
     int whole_payload, nocase, device_extract, want_stats;
     const char *offsets_path, *packets_path, *rules_path, *alerts_path, *export_path, *flows_path, *flow_alerts_path;
     int flows_directed;                     /* KMPGPU_FLOWS_DIRECTED */
+    uint32_t flow_seams;                    /* KMPGPU_FLOW_SEAMS: the reach, 0 without the variable */
     int want_meta;                          /* header predicates or flows: the payloads' header fields go to the device */
     /* what every shard's context gets behind its patterns, in this order and before any rule is set */
     uint32_t *win_first, *win_last;         /* KMPGPU_WINDOWS_FILE (NULL: none) */
@@ -278,6 +286,21 @@ static void load_options(int argc, char *argv[], cli_options *opt)
         }
         probe_writable("KMPGPU_FLOWS_FILE", opt->flows_path);
         probe_writable("KMPGPU_FLOW_ALERTS_FILE", opt->flow_alerts_path);
+    }
+    /* seams: they change what the flow alerts file holds and nothing else */
+    const char *seams_env = env_path("KMPGPU_FLOW_SEAMS");
+    if (seams_env) {
+        if (!opt->flow_alerts_path) {
+            fprintf(stderr, "KMPGPU_FLOW_SEAMS goes together with KMPGPU_FLOW_ALERTS_FILE: it is not set\n");
+            exit(1);
+        }
+        char *end = NULL;
+        const long reach = strtol(seams_env, &end, 10);
+        if (end == seams_env || *end || reach < 1 || reach > KMPGPU_MAX_PATTERN_LEN - 1) {
+            fprintf(stderr, "KMPGPU_FLOW_SEAMS is \"%s\": a reach of 1..%d bytes is needed\n", seams_env, KMPGPU_MAX_PATTERN_LEN - 1);
+            exit(1);
+        }
+        opt->flow_seams = (uint32_t)reach;
     }
     opt->want_meta = opt->headers.n || opt->flows_path || opt->flow_alerts_path;
     /* the export starts as a capture without frames: a path that cannot be written ends the run here */
@@ -495,7 +518,15 @@ static void write_flows(const cli_options *opt, cli_run *run)
         if (nr && n_flows) {
             uint64_t *hits = (uint64_t *)calloc((size_t)(nr * Wf), sizeof(uint64_t));
             if (!hits) die_gpu("KMPGPU_FLOW_ALERTS_FILE: out of memory");
-            if (kmpgpu_scan_flows(ctx, KMPGPU_ALERT_RULES, KMPGPU_FLOW_SCOPE_FLOW, NULL, NULL, hits, NULL, NULL)) die_gpu("kmpgpu_scan_flows");
+            if (opt->flow_seams) {
+                /* KMPGPU_FLOW_SEAMS: the seams in a context of their own, next to the shard, under the same patterns */
+                kmpgpu_ctx *sm = NULL;
+                if (kmpgpu_init(&sm, run->job[0].device)) die_gpu("kmpgpu_init");
+                if (set_patterns_env(sm, opt->pp, opt->pats.len, opt->pats.n, opt->whole_payload, opt->nocase)) die_gpu("kmpgpu_set_patterns");
+                if (kmpgpu_load_seams(sm, ctx, opt->flow_seams, NULL)) die_gpu("kmpgpu_load_seams");
+                if (kmpgpu_scan_flows_seams(ctx, sm, NULL, NULL, hits, NULL, NULL)) die_gpu("kmpgpu_scan_flows_seams");
+                kmpgpu_destroy(sm);
+            } else if (kmpgpu_scan_flows(ctx, KMPGPU_ALERT_RULES, KMPGPU_FLOW_SCOPE_FLOW, NULL, NULL, hits, NULL, NULL)) die_gpu("kmpgpu_scan_flows");
             for (uint64_t f = 0; f < n_flows; f++)
                 for (uint64_t r = 0; r < nr; r++)
                     if (hits[r * Wf + (f >> 6)] >> (f & 63) & 1u) fprintf(fp, "%llu,%llu\n", (unsigned long long)f, (unsigned long long)r);

@@ -1,5 +1,5 @@
 /* kmp_launch.h -- launch entry points of kmp_scan_*.hip / kmp_prep.hip / kmp_fold.hip / kmp_marks.hip / kmp_rules.hip / kmp_relations.hip /
- * kmp_chains.hip / kmp_headers.hip / kmp_select.hip / kmp_alerts.hip / kmp_flows.hip, used
+ * kmp_chains.hip / kmp_headers.hip / kmp_select.hip / kmp_alerts.hip / kmp_flows.hip / kmp_seams.hip, used
  * by the C-ABI layer (kmpgpu.hip), which alone decides what is launched; the tables kmp_launch_scan_multi takes come from kmp_tables.h. */
 #ifndef KMP_LAUNCH_H
 #define KMP_LAUNCH_H
@@ -199,5 +199,27 @@ hipError_t kmp_launch_flows_fold(const unsigned long long *rows, uint64_t stride
                                  uint64_t stride_f, hipStream_t st);
 hipError_t kmp_launch_flows_expand(const unsigned long long *flow_bits, const uint32_t *flow_of, uint64_t n_pkts, unsigned long long *pkt_bits,
                                    hipStream_t st);
+
+/* kmp_seams.hip (kmpgpu_load_seams): the seams of an index of n <= 2^32 - 2 payloads whose flows are built -- meta[n], flow_of[n],
+ * flow_recs[n_flows] as kmp_flows.hip leaves them --, gathered into a packed arena.  In the order they are launched:
+ * _keys: (flow_of[k] << 1 | dir(k), k) for every payload, into sort_buf (kmp_seam_sort_bytes(n, n_flows) bytes, 256-byte aligned, kept up to
+ *   _phase1; 0: rocPRIM refused the size query).
+ * _sort: rocprim::radix_sort_pairs over the key's live bits, stable, inside sort_buf.
+ * _phase1 (3 kernels): pred[] and the seam lengths in ws (kmp_extract_ws_bytes(n) bytes, kept up to _index), their scan; totals[0] = bytes of
+ *   the packed seams, totals[1] = n_seams.
+ * _index: pkt_off[n_seams], pkt_len[n_seams], the kmpgpu_seam records seams[n_seams], seam_flow[n_seams], meta[n_seams] (16-byte aligned),
+ *   and recs[2 n_seams] (16 bytes each), which the gather reads.
+ * _gather: arena[0, total_bytes): every slot whole, 0x00 behind its seam's end.  Of src_arena only aligned 16-byte units that hold a byte of a
+ *   tail or a head are read (the source's slots are 16-byte aligned: the layout contract of kmpgpu.h). */
+size_t kmp_seam_sort_bytes(uint64_t n, uint64_t n_flows);
+hipError_t kmp_launch_seam_keys(const void *meta, const uint32_t *flow_of, const void *flow_recs, uint64_t n, uint8_t *sort_buf, hipStream_t st);
+hipError_t kmp_launch_seam_sort(uint64_t n, uint64_t n_flows, uint8_t *sort_buf, size_t sort_bytes, hipStream_t st);
+hipError_t kmp_launch_seam_phase1(const uint32_t *pkt_len, uint64_t n, uint32_t reach, const uint8_t *sort_buf, uint8_t *ws,
+                                  unsigned long long *totals, hipStream_t st);
+hipError_t kmp_launch_seam_index(const uint64_t *src_off, const uint32_t *src_len, const void *src_meta, const uint32_t *flow_of, uint64_t n,
+                                 uint32_t reach, uint8_t *ws, uint64_t *pkt_off, uint32_t *pkt_len, void *seams, uint32_t *seam_flow, void *meta,
+                                 void *recs, hipStream_t st);
+hipError_t kmp_launch_seam_gather(const uint8_t *src_arena, const uint64_t *pkt_off, const void *recs, uint64_t n_seams, uint64_t total_bytes,
+                                  uint8_t *arena, bool nontemporal, hipStream_t st);
 
 #endif

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <map>
 #include <cstdarg>
 #include <cstdio>
@@ -31,6 +32,8 @@
 namespace {
 
 thread_local std::string g_err;
+
+std::atomic<uint64_t> g_ctx_ids{0};               /* kmpgpu_ctx::id */
 
 int fail(int code, const char *fmt, ...)
 {
@@ -212,6 +215,19 @@ struct kmpgpu_ctx {
     uint64_t            n_flows = 0;
     bool                flows_valid = false;
     int64_t             flow_slots = 0;               /* KMPGPU_OPT_FLOW_SLOTS */
+    /* which build of the flows the context holds: kmpgpu_flows_build and drop_flows start a new generation, and id tells one context from
+     * every other the process has made (a seam list names the context and the generation it was built from) */
+    uint64_t            id = 0, flows_gen = 0;
+    /* kmpgpu_load_seams, in dst: the kmpgpu_seam records and seam_flow [n_seams], the sort's buffers (kmp_seam_sort_bytes).  seams_valid: a
+     * list exists, and the arena is the one it describes (drop_seams); seam_src / seam_gen: the flows it was built from */
+    kmpgpu_seam        *d_seams = nullptr;
+    uint32_t           *d_seam_flow = nullptr;
+    uint8_t            *d_seam_sort = nullptr;
+    uint64_t            seams_cap = 0, seam_flow_cap = 0, seam_sort_cap = 0;
+    uint64_t            n_seams = 0, seam_src = 0, seam_gen = 0;
+    bool                seams_valid = false;
+    /* the patterns as they were set, one record {length, flags, bytes} each: what kmpgpu_scan_flows_seams compares between two contexts */
+    std::vector<uint8_t> pat_sig;
 
     /* options */
     int mode = 0, blocks_per_cu = 0 /* auto */, depth = 0 /* auto */, nontemporal = 1, kernel_sel = 0, fused = 2 /* auto */, accumulate = 0, repack = 1;
@@ -394,6 +410,14 @@ void drop_flows(kmpgpu_ctx *c)
 {
     c->flows_valid = false;
     c->n_flows = 0;
+    c->flows_gen++;                                /* a seam list built from them is none of the next build's */
+}
+
+/* the seam list goes with the arena it describes; its buffers are kept for the next build */
+void drop_seams(kmpgpu_ctx *c)
+{
+    c->seams_valid = false;
+    c->n_seams = 0;
 }
 
 /* the patterns and all that is built on them */
@@ -409,6 +433,7 @@ void release_patterns(kmpgpu_ctx *c)
     drop_chains(c);                                /* ... and the chains' */
     drop_headers(c);                               /* ... and the header predicates sit behind all of them */
     c->pat_fold.clear();
+    c->pat_sig.clear();
     c->alerts_valid = false;                       /* the list named their rows */
 }
 
@@ -448,6 +473,7 @@ void release_arena(kmpgpu_ctx *c, bool keep_buffers = false)
     c->alerts_valid = false;                          /* the list of kmpgpu_scan_alerts named this arena's payloads */
     c->has_meta = false;                              /* the metadata described its payloads (the buffer is kept too) */
     drop_flows(c);                                    /* ... and the flows grouped them */
+    drop_seams(c);                                    /* ... and the seam list said which of src's payloads they join */
 }
 
 /* Host ranges pinned through kmpgpu_host_register.  One copy must not straddle two registrations (the runtime refuses it), and a
@@ -501,6 +527,8 @@ void release_pass_buffers(kmpgpu_ctx *c)
     free_buffer(&c->d_flow_table, &c->flow_table_cap); free_buffer(&c->d_flow_first, &c->flow_first_cap); free_buffer(&c->d_flow_of, &c->flow_of_cap);
     free_buffer(&c->d_flow_recs, &c->flow_recs_cap); free_buffer(&c->d_flow_fold, &c->flow_fold_cap); free_buffer(&c->d_flow_sel, &c->flow_sel_cap);
     drop_flows(c);
+    free_buffer(&c->d_seams, &c->seams_cap); free_buffer(&c->d_seam_flow, &c->seam_flow_cap); free_buffer(&c->d_seam_sort, &c->seam_sort_cap);
+    drop_seams(c);
     c->alerts_valid = false;
     c->bitmap_live = false; c->plan_waves = c->uplan_units = 0; c->fold_stale = true;
 }
@@ -972,6 +1000,7 @@ int kmpgpu_init(kmpgpu_ctx **out, int device)
     kmpgpu_ctx *c = new (std::nothrow) kmpgpu_ctx();
     if (!c) return fail(KMPGPU_ENOMEM, "kmpgpu_init: out of host memory");
     c->device = device;
+    c->id = ++g_ctx_ids;
     c->cu_count = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     hipError_t e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
     if (e == hipSuccess) {
@@ -1129,6 +1158,11 @@ int kmpgpu_set_patterns_flags(kmpgpu_ctx *c, const uint8_t *const *pat, const ui
     HIP_TRY(hipStreamSynchronize(c->stream));
     release_patterns(c);
     c->n_pat = n_pat;
+    for (uint32_t i = 0; i < n_pat; i++) {
+        c->pat_sig.push_back((uint8_t)pat_len[i]);
+        c->pat_sig.push_back((uint8_t)(flags ? flags[i] : 0u));
+        c->pat_sig.insert(c->pat_sig.end(), pat[i], pat[i] + pat_len[i]);
+    }
     c->pat_fold.assign(n_pat, 0);
     for (uint32_t i : members[1]) c->pat_fold[i] = 1;
     const size_t np = n_pat ? n_pat : 1;
@@ -1432,6 +1466,111 @@ int kmpgpu_load_selected(kmpgpu_ctx *dst, kmpgpu_ctx *src, const void *select, i
     c->last.kernel_ms = ms; c->last.launches = src->has_meta ? 6 : 5;
     c->has_meta = src->has_meta;
     if (n_selected) *n_selected = n_pkts;
+    return KMPGPU_OK;
+}
+
+int kmpgpu_load_seams(kmpgpu_ctx *dst, kmpgpu_ctx *src, uint32_t reach, uint64_t *n_seams)
+{
+    const char *who = "kmpgpu_load_seams";
+    if (n_seams) *n_seams = 0;
+    if (!dst || !src) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
+    if (dst == src) return fail(KMPGPU_EINVAL, "%s: dst and src are the same context (a context holds one arena)", who);
+    if (reach < 1u || reach > KMPGPU_MAX_PATTERN_LEN - 1u)
+        return fail(KMPGPU_EINVAL, "%s: reach %u is not in 1..%u", who, reach, KMPGPU_MAX_PATTERN_LEN - 1u);
+    if (dst->device != src->device)
+        return fail(KMPGPU_EINVAL, "%s: the contexts sit on devices %d and %d (seams across devices do not exist)", who, dst->device, src->device);
+    if (dst->fr_pending || src->fr_pending) return fail(KMPGPU_ESTATE, "%s: %s sits between kmpgpu_load_frames_begin and _finish", who, dst->fr_pending ? "dst" : "src");
+    if (!src->flows_valid) return fail(KMPGPU_ESTATE, "%s: no flows (no kmpgpu_flows_build since the arena or its metadata were set)", who);
+    HIP_TRY(hipSetDevice(dst->device));
+    HIP_TRY(hipStreamSynchronize(dst->stream));           /* the passes over the arena that is about to be replaced */
+    HIP_TRY(hipStreamSynchronize(src->stream));           /* whatever src's stream still does with its arena */
+    kmpgpu_ctx *c = dst;
+    c->last = kmpgpu_timing{};
+    const uint64_t n = src->n_pkts;
+    /* from here on dst's earlier arena is gone, whatever happens */
+    release_arena(c, /* keep_buffers = */ true);
+    auto listed = [&](uint64_t ns) {
+        c->n_seams = ns; c->seam_src = src->id; c->seam_gen = src->flows_gen; c->seams_valid = true;
+        if (n_seams) *n_seams = ns;
+        return KMPGPU_OK;
+    };
+    if (n == 0) return listed(0);
+
+    /* the scratch of kmpgpu_load_frames (fr_ws the scan, fr_src the gather's records) and the sort's own buffer */
+    const uint64_t sort_bytes = kmp_seam_sort_bytes(n, src->n_flows);
+    if (!sort_bytes) return fail(KMPGPU_EHIP, "%s: the sort of %llu payloads could not be sized", who, (unsigned long long)n);
+    hipError_t e = grow_buffer(&c->fr_ws, &c->fr_ws_cap, (uint64_t)kmp_extract_ws_bytes(n), EIGHTH);
+    if (e == hipSuccess && !c->fr_tot) e = hipMalloc(&c->fr_tot, 2 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = grow_buffer(&c->d_seam_sort, &c->seam_sort_cap, sort_bytes, EIGHTH);
+    if (e != hipSuccess) return alloc_fail(e, "%s: the sort's buffers (%llu bytes) could not be allocated", who, (unsigned long long)sort_bytes);
+    hipEvent_t e1;
+    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_seam_keys(src->d_meta, src->d_flow_of, src->d_flow_recs, n, c->d_seam_sort, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_seam_sort(n, src->n_flows, c->d_seam_sort, (size_t)c->seam_sort_cap, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_seam_phase1(src->d_len, n, reach, c->d_seam_sort, c->fr_ws, c->fr_tot, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(hipMemcpyAsync(c->h_small, c->fr_tot, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));         /* (pinned: no staging) */
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    unsigned long long tot[2] = {0, 0};
+    memcpy(tot, c->h_small, sizeof tot);
+    const uint64_t ns = tot[1], arena_bytes = tot[0] + 64;
+    if (ns == 0) {
+        HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+        HIP_TRY(hipEventSynchronize(c->ev[3]));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
+        c->last.kernel_ms = ms; c->last.launches = 5;
+        return listed(0);
+    }
+    e = ensure_owned_arena(c, arena_bytes, ns, EIGHTH);                      /* (on failure dst is empty and usable) */
+    if (e != hipSuccess)
+        return alloc_fail(e, "%s: an arena of %llu bytes / %llu seams could not be allocated", who, (unsigned long long)(arena_bytes + arena_bytes / 8),
+                          (unsigned long long)(ns + ns / 8));
+    e = grow_buffer(&c->fr_src, &c->fr_src_cap, 4 * ns, EIGHTH);             /* 32 bytes per seam */
+    if (e == hipSuccess) e = grow_buffer(&c->d_meta, &c->meta_cap, ns, EIGHTH);
+    if (e == hipSuccess) e = grow_buffer(&c->d_seams, &c->seams_cap, ns, EIGHTH);
+    if (e == hipSuccess) e = grow_buffer(&c->d_seam_flow, &c->seam_flow_cap, ns, EIGHTH);
+    if (e != hipSuccess) return alloc_fail(e, "%s: the records of %llu seams could not be allocated", who, (unsigned long long)ns);
+    HIP_TRY(hipMemsetAsync(c->owned_arena + tot[0], 0, 64, c->stream));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_seam_index(src->d_off, src->d_len, src->d_meta, src->d_flow_of, n, reach, c->fr_ws, c->owned_off, c->owned_len, c->d_seams,
+                                  c->d_seam_flow, c->d_meta, c->fr_src, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_seam_gather(src->d_arena, c->owned_off, c->fr_src, ns, tot[0], c->owned_arena, c->nontemporal != 0, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    IndexFacts f;
+    int rc = validate_index(c, who, c->owned_off, c->owned_len, ns, arena_bytes, &f);
+    /* kmp_seam_gather_kernel writes every slot whole: seam, then 0x00 up to the slot's end */
+    if (!rc) rc = install_arena(c, c->owned_arena, c->owned_off, c->owned_len, arena_bytes, ns, f, /* wrote_padding = */ true);
+    if (rc) { release_arena(c, true); return rc; }
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
+    c->last.kernel_ms = ms; c->last.launches = 7;
+    c->has_meta = true;
+    return listed(ns);
+}
+
+int kmpgpu_seams_read(kmpgpu_ctx *c, kmpgpu_seam *out, uint64_t first, uint64_t n)
+{
+    static_assert(sizeof(kmpgpu_seam) == 24, "kmpgpu_seam is the 24-byte record of kmpgpu.h");
+    const char *who = "kmpgpu_seams_read";
+    if (!c) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
+    if (!c->seams_valid) return fail(KMPGPU_ESTATE, "%s: no seams (no kmpgpu_load_seams since the arena was set)", who);
+    if (first > c->n_seams || n > c->n_seams - first)
+        return fail(KMPGPU_EINVAL, "%s: elements [%llu, +%llu) leave the %llu there are", who, (unsigned long long)first, (unsigned long long)n,
+                    (unsigned long long)c->n_seams);
+    if (n == 0) return KMPGPU_OK;
+    if (!out) return fail(KMPGPU_EINVAL, "%s: out is NULL", who);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(out, c->d_seams + first, (size_t)n * sizeof(kmpgpu_seam), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return KMPGPU_OK;
 }
 
@@ -2197,10 +2336,11 @@ int kmpgpu_flow_ids_read(kmpgpu_ctx *c, uint32_t *out, uint64_t first, uint64_t 
     return flows_read_range(c, "kmpgpu_flow_ids_read", out, c ? c->d_flow_of : nullptr, sizeof(uint32_t), first, n, c && c->flows_valid ? c->n_pkts : 0);
 }
 
-int kmpgpu_scan_flows(kmpgpu_ctx *c, int family, uint32_t scope, uint64_t *flow_counts_out, uint64_t *any_out, uint64_t *flow_hits_out,
-                      uint64_t *counts_out, kmpgpu_timing *t)
+/* The body of kmpgpu_scan_flows, and of kmpgpu_scan_flows_seams where sm is given: the context whose seam list (checked by the caller)
+ * adds its pattern rows to the folded term rows. */
+static int scan_flows_body(kmpgpu_ctx *c, const char *who, kmpgpu_ctx *sm, int family, uint32_t scope, uint64_t *flow_counts_out, uint64_t *any_out,
+                           uint64_t *flow_hits_out, uint64_t *counts_out, kmpgpu_timing *t)
 {
-    const char *who = "kmpgpu_scan_flows";
     if (!c) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
     if (family < KMPGPU_ALERT_PATTERNS || family > KMPGPU_ALERT_CHAINS) return fail(KMPGPU_EINVAL, "%s: family %d is none of KMPGPU_ALERT_*", who, family);
     if (scope != KMPGPU_FLOW_SCOPE_PACKET && scope != KMPGPU_FLOW_SCOPE_FLOW) return fail(KMPGPU_EINVAL, "%s: scope %u is none of KMPGPU_FLOW_SCOPE_*", who, scope);
@@ -2213,6 +2353,21 @@ int kmpgpu_scan_flows(kmpgpu_ctx *c, int family, uint32_t scope, uint64_t *flow_
     if (family != KMPGPU_ALERT_PATTERNS && n_rows == 0)
         return fail(KMPGPU_ESTATE, "%s: no %s set", who, family == KMPGPU_ALERT_RULES ? "rules" : family == KMPGPU_ALERT_RELATIONS ? "relations" : "chains");
     if (c->fr_pending) return fail(KMPGPU_ESTATE, "%s: the context sits between kmpgpu_load_frames_begin and _finish", who);
+    /* the seams first, on their own context's stream: the pass of kmpgpu_scan_packets, which runs beside src's where the streams differ.
+     * Its any[] lets the fold skip the words no pattern has a bit in.  An empty list (a context without an arena) adds nothing */
+    MarkPass ps;
+    FamilyRows fs;
+    bool seams = false;
+    if (sm && c->n_pkts) {
+        const int rs = begin_family(sm, who, KMPGPU_ALERT_PATTERNS, nullptr, nullptr, nullptr, &ps);
+        if (rs) return rs;
+        seams = !ps.empty;
+        if (seams) {
+            const int re = enqueue_family(sm, who, KMPGPU_ALERT_PATTERNS, ps, /* profile_reduce = */ false, &fs);
+            if (re) return re;
+            HIP_TRY(hipSetDevice(c->device));
+        }
+    }
     MarkPass p;
     const int rc = begin_family(c, who, family, flow_counts_out, counts_out, t, &p);
     if (rc || p.empty) return rc;
@@ -2238,6 +2393,13 @@ int kmpgpu_scan_flows(kmpgpu_ctx *c, int family, uint32_t scope, uint64_t *flow_
     HIP_TRY(kmp_launch_flows_fold(per_flow ? p.d_mat : f.d_rows, p.stride, (uint32_t)fold_rows, c->n_pkts, per_flow ? nullptr : f.d_any, c->d_flow_of,
                                   c->n_flows, c->d_flow_fold, Sf, c->stream));
     HIP_TRY(profile_launched(c, e1));
+    if (seams) {
+        /* the same kernel a second time: its output is an atomic OR into the matrix zeroed above */
+        HIP_TRY(hipStreamSynchronize(sm->stream));                  /* the seams' pass has landed in its matrix */
+        HIP_TRY(profile_launch(c, &e1));
+        HIP_TRY(kmp_launch_flows_fold(ps.d_mat, ps.stride, c->n_pat, sm->n_pkts, fs.d_any, sm->d_seam_flow, c->n_flows, c->d_flow_fold, Sf, c->stream));
+        HIP_TRY(profile_launched(c, e1));
+    }
     HIP_TRY(profile_launch(c, &e1));
     if (per_flow)
         HIP_TRY(kmp_launch_rules(c->d_flow_fold, Sf, c->n_flows, c->d_rule_heads, c->d_rule_quads, c->n_rules, d_rows, d_fc, d_any, c->stream));
@@ -2249,7 +2411,29 @@ int kmpgpu_scan_flows(kmpgpu_ctx *c, int family, uint32_t scope, uint64_t *flow_
     if (any_out) HIP_TRY(hipMemcpyAsync(any_out, d_any, Wf * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, p.d_cnt, (size_t)c->n_pat * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     if (flow_hits_out) HIP_TRY(download_rows(c, flow_hits_out, d_rows, Wf, Sf, n_rows));
-    return finish_marking(c, p.launches + f.launches + 2u, t);
+    return finish_marking(c, p.launches + f.launches + 2u + (seams ? ps.launches + fs.launches + 1u : 0u), t);
+}
+
+int kmpgpu_scan_flows(kmpgpu_ctx *c, int family, uint32_t scope, uint64_t *flow_counts_out, uint64_t *any_out, uint64_t *flow_hits_out,
+                      uint64_t *counts_out, kmpgpu_timing *t)
+{
+    return scan_flows_body(c, "kmpgpu_scan_flows", nullptr, family, scope, flow_counts_out, any_out, flow_hits_out, counts_out, t);
+}
+
+int kmpgpu_scan_flows_seams(kmpgpu_ctx *c, kmpgpu_ctx *sm, uint64_t *flow_counts_out, uint64_t *any_out, uint64_t *flow_hits_out, uint64_t *counts_out,
+                            kmpgpu_timing *t)
+{
+    const char *who = "kmpgpu_scan_flows_seams";
+    if (!c || !sm) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
+    if (c == sm) return fail(KMPGPU_EINVAL, "%s: src and seams are the same context", who);
+    if (c->device != sm->device) return fail(KMPGPU_EINVAL, "%s: the contexts sit on devices %d and %d", who, c->device, sm->device);
+    if (!c->flows_valid) return fail(KMPGPU_ESTATE, "%s: no flows (no kmpgpu_flows_build since the arena or its metadata were set)", who);
+    if (sm->fr_pending) return fail(KMPGPU_ESTATE, "%s: seams sits between kmpgpu_load_frames_begin and _finish", who);
+    if (!sm->seams_valid) return fail(KMPGPU_ESTATE, "%s: no seams (no kmpgpu_load_seams since the arena was set)", who);
+    if (sm->seam_src != c->id || sm->seam_gen != c->flows_gen)
+        return fail(KMPGPU_ESTATE, "%s: the seam list was not built from src's current flows", who);
+    if (c->n_pat != sm->n_pat || c->pat_sig != sm->pat_sig) return fail(KMPGPU_ESTATE, "%s: the contexts do not hold the same patterns", who);
+    return scan_flows_body(c, who, sm, KMPGPU_ALERT_RULES, KMPGPU_FLOW_SCOPE_FLOW, flow_counts_out, any_out, flow_hits_out, counts_out, t);
 }
 
 int kmpgpu_flows_select(kmpgpu_ctx *c, const void *flow_bits, int on_device, uint64_t *pkt_bits_out, const void **d_pkt_bits)

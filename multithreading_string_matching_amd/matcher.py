@@ -35,6 +35,7 @@ FLOW_DIRECTED = 1       # KMPGPU_FLOW_DIRECTED: the two directions of a conversa
 FLOW_SCOPES = {"packet": 0, "flow": 1}     # KMPGPU_FLOW_SCOPE_*
 FLOW_DTYPE = np.dtype([("first_packet", "<u8"), ("last_packet", "<u8"), ("n_packets", "<u8"), ("payload_bytes", "<u8"),
                        ("first", META_DTYPE)])     # kmpgpu_flow, 48 bytes
+SEAM_DTYPE = np.dtype([("prev", "<u8"), ("next", "<u8"), ("tail_len", "<u4"), ("head_len", "<u4")])      # kmpgpu_seam, 24 bytes
 
 
 def device_count() -> int:
@@ -538,8 +539,15 @@ class GpuMatcher:
             raise ValueError(f"family {family!r}: one of {sorted(ALERT_FAMILIES)} is needed")
         if scope not in FLOW_SCOPES:
             raise ValueError(f"scope {scope!r}: one of {sorted(FLOW_SCOPES)} is needed")
+        rows = {"patterns": len(self.patterns), "rules": len(self.rules), "relations": len(self.relations), "chains": len(self.chains)}[family]
+
+        def call(row_counts, any_w, hit_w, counts, t):
+            return self._g.kmpgpu_scan_flows(self._ctx, ALERT_FAMILIES[family], FLOW_SCOPES[scope], row_counts, any_w, hit_w, counts, t)
+        return self._scan_flow_rows(call, "kmpgpu_scan_flows", rows, hits)
+
+    def _scan_flow_rows(self, call, name: str, rows: int, hits: bool) -> dict:
+        """What scan_flows and scan_flow_seams share: the output buffers of a flow-space call and their unpacking."""
         n = len(self.patterns)
-        rows = {"patterns": n, "rules": len(self.rules), "relations": len(self.relations), "chains": len(self.chains)}[family]
         n_flows = getattr(self, "_n_flows", 0)
         Wf = (n_flows + 63) // 64
         row_counts = np.zeros(max(rows, 1), dtype=np.uint64)
@@ -547,14 +555,41 @@ class GpuMatcher:
         any_w = np.zeros(max(Wf, 1), dtype=np.uint64)
         hit_w = np.zeros((rows, Wf) if hits and rows * Wf else 1, dtype=np.uint64)
         t = Timing()
-        gpu_check(self._g.kmpgpu_scan_flows(self._ctx, ALERT_FAMILIES[family], FLOW_SCOPES[scope], row_counts.ctypes.data, any_w.ctypes.data,
-                                            hit_w.ctypes.data if hits else None, counts.ctypes.data, C.byref(t)), "kmpgpu_scan_flows")
+        gpu_check(call(row_counts.ctypes.data, any_w.ctypes.data, hit_w.ctypes.data if hits else None, counts.ctypes.data, C.byref(t)), name)
         out = {"flow_counts": row_counts[:rows], "counts": counts[:n], "timing": t,
                "any": np.unpackbits(any_w[:Wf].view(np.uint8), bitorder="little")[:n_flows].astype(bool)}
         if hits:
             bits = np.unpackbits(hit_w.reshape(rows, Wf).view(np.uint8), axis=1, bitorder="little") if rows * Wf else np.zeros((rows, 0), np.uint8)
             out["hits"] = bits[:, :n_flows].astype(bool)
         return out
+
+    # -- flow seams --------------------------------------------------------------------------------
+    def load_seams(self, src: "GpuMatcher", reach: int = 98) -> int:
+        """Make this matcher's arena the seams of ``src``, whose flows are built (kmpgpu_load_seams): for every payload with a predecessor
+        in its flow and direction, the predecessor's last ``reach`` bytes followed by the payload's first ``reach`` bytes, as a payload of
+        its own.  A pattern of up to reach + 1 bytes that straddles the boundary lies inside the seam.  Patterns, rules, windows and options
+        of this matcher stay.  Returns the number of seams."""
+        n = C.c_uint64()
+        gpu_check(self._g.kmpgpu_load_seams(self._ctx, src._ctx, int(reach), C.byref(n)), "kmpgpu_load_seams")
+        self._keep = None
+        self._n_seams = int(n.value)
+        return self._n_seams
+
+    def seams(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """Records [first, first + n) of the seam list (kmpgpu_seams_read) as a SEAM_DTYPE array; n None: all from ``first`` on."""
+        gpu_check(self._g.kmpgpu_seams_read(self._ctx, None, 0, 0), "kmpgpu_seams_read")        # (the library knows when the list was dropped)
+        n = getattr(self, "_n_seams", 0) - int(first) if n is None else int(n)
+        out = np.zeros(max(n, 1), dtype=SEAM_DTYPE)
+        gpu_check(self._g.kmpgpu_seams_read(self._ctx, out.ctypes.data, int(first), max(n, 0)), "kmpgpu_seams_read")
+        return out[: max(n, 0)]
+
+    def scan_flow_seams(self, seams: "GpuMatcher", hits: bool = False) -> dict:
+        """scan_flows("rules", "flow") with the pattern rows of ``seams`` -- a matcher that holds this one's patterns and the seam list
+        load_seams built from this one's current flows -- folded into the term rows (kmpgpu_scan_flows_seams): a content split across two
+        consecutive payloads of a flow direction counts as present in the flow.  The result is shaped like scan_flows'."""
+        def call(row_counts, any_w, hit_w, counts, t):
+            return self._g.kmpgpu_scan_flows_seams(self._ctx, seams._ctx, row_counts, any_w, hit_w, counts, t)
+        return self._scan_flow_rows(call, "kmpgpu_scan_flows_seams", len(self.rules), hits)
 
     def select_flows(self, bits, device: bool = False):
         """The payloads of the chosen flows as a payload bitmap (kmpgpu_flows_select): bits is bool[n_flows] or uint64[ceil(n_flows / 64)]
