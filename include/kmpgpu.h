@@ -536,7 +536,7 @@ int  kmpgpu_scan_chains(kmpgpu_ctx *ctx, uint64_t *chain_pkt_counts_out /* [n_ch
  * kmpgpu_set_chains keep them (and drop the rules, as they always do).  sport_lo > sport_hi, dport_lo > dport_hi, len_lo > len_hi, an
  * unknown flag bit, reserved != 0, a NULL array with n_hdr > 0, n_pat + n_rel + n_chains + n_hdr >= 2^31: KMPGPU_EINVAL, and the
  * predicates and rules set before stay in force.  n_hdr == 0 clears them (the array may be NULL).  EVERY successful call drops the rules:
- * the rows their terms name have changed.  So the order is patterns, relations, chains, headers, rules.
+ * the rows their terms name have changed.  So the order is patterns, relations, chains, headers, (byte tests,) rules.
  *
  * Headers as rule terms: predicate q is row n_pat + n_rel + n_chains + q of the hit matrix and term index n_pat + n_rel + n_chains + q of
  * kmpgpu_set_rules, with or without KMPGPU_RULE_NOT; kmpgpu_scan_rules and kmpgpu_scan_alerts(KMPGPU_ALERT_RULES) run the header kernel
@@ -574,6 +574,67 @@ int  kmpgpu_set_headers(kmpgpu_ctx *ctx, const kmpgpu_header *h /* [n_hdr] */, u
 int  kmpgpu_scan_headers(kmpgpu_ctx *ctx, uint64_t *hdr_pkt_counts_out /* [n_hdr] or NULL */, uint64_t *any_out /* [W] or NULL */,
                          uint64_t *hdr_hits_out /* [n_hdr * W] or NULL */, uint64_t *counts_out /* [n_pat] or NULL: as kmpgpu_scan */,
                          kmpgpu_timing *t /* or NULL */);
+
+/* Byte tests: what signatures for binary protocols are built from -- read 1 to 4 bytes at a position, take them as an unsigned integer,
+ * mask, compare (Snort: byte_test) -- as a sixth kind of row of the hit matrix, behind the header predicates'.  "Is the QR bit of a DNS
+ * message set": 2 bytes at 2, mask 0x8000, NE, 0.  A pattern cannot say that: the field is a range or a bit, not a byte string.
+ *
+ * With E_k the payload's text end as everywhere else (min(L_k, first 0x00) under the default rule, L_k under KMPGPU_OPT_WHOLE_PAYLOAD):
+ *     field(k, pos)     = the integer formed from bytes pos .. pos + nbytes - 1 of payload k, big-endian (network order) unless
+ *                         KMPGPU_BT_LITTLE; defined only for 0 <= pos and pos + nbytes <= E_k: no byte at or behind E_k is ever part
+ *                         of a field
+ *     holds(f)          = ((f & mask) op value), unsigned 32-bit
+ *     absolute test:      bt_hit[q][k] = field(k, offset) is defined && holds(field(k, offset))
+ *     relative test:      bt_hit[q][k] = there is a match (k, s, anchor) such that field(k, s + m_anchor + offset) is defined and holds
+ *     bt_pkt_counts[q]  = sum over k of bt_hit[q][k]
+ *     any[k]            = OR over q of bt_hit[q][k]
+ *     counts[i]         = exactly what kmpgpu_scan returns, as in the sibling calls
+ * A match is what the marking pass marks, as the relations define it: in its window, nocase per pattern, overlapping starts; the test is
+ * existential over ALL matches of the anchor, not only the first.  offset of a relative test has any sign: a negative one reaches into
+ * the match or in front of it.  Out of reach is FALSE, not undecided: a field that cannot lie inside the text makes the test false, so a
+ * negated term of a rule fires on a payload that is too short.  The field's bytes always come from the original arena, never from the
+ * folded copy, also where the anchor is a nocase pattern compared in the fold.
+ * No further operators: Snort's isdataat:N is {nbytes 1, KMPGPU_BT_GE, value 0} at offset N (a byte exists there), the bit test "&" is
+ * {mask = bits, KMPGPU_BT_NE, value 0}.  Duplicate tests are allowed, each gets its row.  Layout as kmpgpu_scan_packets:
+ * W = ceil(n_pkts / 64) words per row, LSB first, row q of bt_hits_out at bt_hits_out + q * W, the bits of index n_pkts and above 0.
+ *
+ * kmpgpu_set_bytetests copies and uploads the tests.  They belong to the pattern set current at the call: no patterns set: KMPGPU_ESTATE;
+ * a later kmpgpu_set_patterns / kmpgpu_set_patterns_flags drops them with everything else; kmpgpu_set_relations, kmpgpu_set_chains and
+ * kmpgpu_set_headers keep them (they name patterns, not rows) and count n_bt in their 2^31 bound.  nbytes outside 1..4, an unknown op or
+ * flag bit, reserved != 0, anchor >= n_pat of a relative test, anchor != 0 or offset < 0 of an absolute one, a NULL array with n_bt > 0,
+ * n_pat + n_rel + n_chains + n_hdr + n_bt >= 2^31: KMPGPU_EINVAL, and everything set before stays in force.  n_bt == 0 clears them (the
+ * array may be NULL).  EVERY successful call drops the rules.  So the order is patterns, relations, chains, headers, byte tests, rules.
+ * Windows and KMPGPU_OPT_WHOLE_PAYLOAD stay pass state: the tests follow what is set when a pass runs.
+ *
+ * Byte tests as rule terms: test q is row n_pat + n_rel + n_chains + n_hdr + q of the hit matrix and term index
+ * n_pat + n_rel + n_chains + n_hdr + q of kmpgpu_set_rules, with or without KMPGPU_RULE_NOT; kmpgpu_scan_rules and
+ * kmpgpu_scan_alerts(KMPGPU_ALERT_RULES) run the byte-test kernels (one for the absolute tests, one for the relative ones, each only
+ * where there are some) behind the header kernel and in front of the rules kernel.  kmpgpu_scan_flows folds their rows under
+ * KMPGPU_FLOW_SCOPE_FLOW as it folds every term row.  There is no KMPGPU_ALERT_* family for them: as with the header predicates the rules
+ * family is how their hits reach the alert list and the flows.  A test sees one payload: none across a flow seam (kmpgpu_load_seams).
+ *
+ * kmpgpu_scan_bytetests: synchronous, on the context's stream.  The marking pass of kmpgpu_scan_packets, then the byte-test kernels
+ * instead of the pattern-level reduce.  Every output may be NULL: bt_pkt_counts_out[n_bt], any_out[W], bt_hits_out[n_bt * W],
+ * counts_out[n_pat].  Preconditions and errors as kmpgpu_scan_packets; no byte tests set: KMPGPU_ESTATE.
+ * With no byte tests set every output of every other call is bit-identical to what it is without these calls, with the same launches and
+ * device buffers.
+ * Cost (the figures of tools/bytetests.py go to profiles/bytetests.txt): n_bt further rows of the hit matrix,
+ * (n_bt x W2 + n_bt) x 8 bytes, zeroed with it, 32 bytes per test.  The absolute kernel reads 12 bytes of index per payload, under the
+ * strlen rule the first min(L_k, H) bytes (H = the largest offset + nbytes) up to the first 0x00, and 4 or 8 bytes per (payload, test);
+ * the relative kernel reads only the payloads that hold the anchor. */
+#define KMPGPU_BT_RELATIVE 1u     /* measured from the END of a match of pattern `anchor` */
+#define KMPGPU_BT_LITTLE   2u     /* little-endian; default big-endian (network order) */
+enum { KMPGPU_BT_EQ, KMPGPU_BT_NE, KMPGPU_BT_LT, KMPGPU_BT_GT, KMPGPU_BT_LE, KMPGPU_BT_GE };
+typedef struct kmpgpu_bytetest {
+    uint32_t anchor;               /* pattern index; read only with KMPGPU_BT_RELATIVE, else must be 0 */
+    int32_t  offset;               /* absolute: from the payload's first byte, >= 0; relative: from the anchor match's end, any sign */
+    uint32_t mask, value;          /* ((field & mask) op value), unsigned 32-bit */
+    uint8_t  nbytes, op, flags, reserved;   /* nbytes 1..4 */
+} kmpgpu_bytetest;
+int  kmpgpu_set_bytetests(kmpgpu_ctx *ctx, const kmpgpu_bytetest *bt /* [n_bt] */, uint32_t n_bt);
+int  kmpgpu_scan_bytetests(kmpgpu_ctx *ctx, uint64_t *bt_pkt_counts_out /* [n_bt] or NULL */, uint64_t *any_out /* [W] or NULL */,
+                           uint64_t *bt_hits_out /* [n_bt * W] or NULL */, uint64_t *counts_out /* [n_pat] or NULL: as kmpgpu_scan */,
+                           kmpgpu_timing *t /* or NULL */);
 
 /* The alert list: which payloads hit which rows, as records instead of a bit matrix (the hit rows of kmpgpu_scan_packets and the rows of
  * kmpgpu_scan_rules / _relations / _chains are rows x W x 8 bytes that the caller downloads and walks; the answer is normally a handful of
@@ -687,10 +748,10 @@ int  kmpgpu_load_selected(kmpgpu_ctx *dst, kmpgpu_ctx *src, const void *select /
  * kmpgpu_scan_packets with flows in place of payloads (flow f is bit (f & 63) of word (f >> 6)); bits at n_flows and above are 0 in every
  * word.  family is one of KMPGPU_ALERT_*.
  *   KMPGPU_FLOW_SCOPE_PACKET (any family): flow_hit[r][f] = OR over the payloads k of flow f of row[r][k], where row is exactly the bit
- *     the family's own call defines (windows, nocase, whole payloads; for rules the relation, chain and header terms): the flow holds a
+ *     the family's own call defines (windows, nocase, whole payloads; for rules the relation, chain, header and byte-test terms): the flow holds a
  *     payload that the row matches.
  *   KMPGPU_FLOW_SCOPE_FLOW (KMPGPU_ALERT_RULES only; any other family: KMPGPU_EINVAL): every term row -- patterns, relations, chains, header
- *     predicates, as the rule terms index them -- is folded first, then the rule is evaluated per flow:
+ *     predicates, byte tests, as the rule terms index them -- is folded first, then the rule is evaluated per flow:
  *       flow_rule_hit[r][f] = AND over positive terms t of (OR_k row[t][k]) AND AND over negated terms t of !(OR_k row[t][k])
  *     the cross-packet signature: one content in one payload, another in another payload of the same connection.  An all-negated rule
  *     matches every flow that holds none of its terms.
@@ -789,7 +850,7 @@ int  kmpgpu_flows_select(kmpgpu_ctx *ctx, const void *flow_bits /* uint64_t[Wf] 
  * before the rules kernel, the pattern rows of a marking pass over `seams` (the pass of kmpgpu_scan_packets(seams), on seams' stream, which
  * the call waits for as kmpgpu_counts_add does) are folded into the same folded matrix through seam_flow, by the fold kernel a second time:
  *     term[i][f] = OR over the payloads k of flow f of hit_src[i][k]  |  OR over the seams j of flow f of hit_seams[i][j]      (i < n_pat)
- * Relation, chain and header terms stay src's own, and counts_out stays what kmpgpu_scan(src) returns: cross-boundary matches are not
+ * Relation, chain, header and byte-test terms stay src's own, and counts_out stays what kmpgpu_scan(src) returns: cross-boundary matches are not
  * counted.  One boundary per seam: a content that spans three payloads is not found.  Outputs and layout as kmpgpu_scan_flows.
  * Preconditions: `seams` holds a seam list built from src's CURRENT flows (every kmpgpu_flows_build and everything that drops the flows
  * starts a new generation; a list of another generation or another context: KMPGPU_ESTATE), both contexts sit on one device (otherwise

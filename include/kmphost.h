@@ -119,6 +119,12 @@ int  kmp_rules_parse_terms(const char *path, uint32_t n_patterns, uint32_t n_rel
  * is this with n_headers = 0, where "h3" is no term at all. */
 int  kmp_rules_parse_hdr(const char *path, uint32_t n_patterns, uint32_t n_relations, uint32_t n_chains, uint32_t n_headers, kmp_rules *out,
                          char errbuf[KMP_RULES_ERRBUF]);
+/* ... and with byte tests as terms (kmpgpu_set_bytetests): "b<q>" / "!b<q>", q < n_bytetests a decimal test index (the order of the lines of
+ * kmp_bytetests_parse), is encoded as n_patterns + n_relations + n_chains + n_headers + q.  A test index >= n_bytetests: KMPHOST_EINVAL,
+ * "line N: ".  n_patterns + n_relations + n_chains + n_headers + n_bytetests >= 2^31: KMPHOST_EINVAL before the file is opened.
+ * kmp_rules_parse_hdr is this with n_bytetests = 0, where "b3" is no term at all and every message is what it was. */
+int  kmp_rules_parse_bt(const char *path, uint32_t n_patterns, uint32_t n_relations, uint32_t n_chains, uint32_t n_headers, uint32_t n_bytetests,
+                        kmp_rules *out, char errbuf[KMP_RULES_ERRBUF]);
 void kmp_rules_free(kmp_rules *r);
 
 /* ---- relations -------------------------------------------------------------------------------
@@ -188,6 +194,36 @@ typedef struct kmp_headers {
 } kmp_headers;
 int  kmp_headers_parse(const char *path, kmp_headers *out, char errbuf[KMP_HEADERS_ERRBUF]);
 void kmp_headers_free(kmp_headers *h);
+
+/* ---- byte tests ------------------------------------------------------------------------------
+ * Not in the reference: the tests of kmpgpu_set_bytetests (include/kmpgpu.h) from a text file.  One test per line,
+ *     <nbytes> <op> <value> <offset> [after <pattern index>] [little] [mask <m>]
+ * fields separated by blanks: read <nbytes> (1..4) bytes at <offset>, take them as a big-endian integer (little: little-endian), AND
+ * them with <m> (absent: all bits) and compare with <value> by <op>, one of = != < > <= >= &.  "&" is the bit test: it sets
+ * mask = <value> and asks for a result other than 0 (KMP_BT_NE against 0), and refuses a mask clause.  after <i> makes the test relative:
+ * <offset>, then of any sign, counts from the end of a match of pattern i (a position in the pattern file, 0-based); without it <offset>
+ * counts from the payload's first byte and is not negative.  Numbers are decimal or 0x hex; the three clauses come in any order, each at
+ * most once.  Blank lines and lines whose first non-blank character is '#' are skipped; test index = order of the lines.  bt is what
+ * kmpgpu_set_bytetests takes (kmp_bytetest has the layout of kmpgpu_bytetest).
+ * KMPHOST_EIO: the file cannot be opened; KMPHOST_EINVAL: fewer than four fields, a field of none of its forms, a number out of its
+ * range, an index >= n_patterns, an unknown or repeated clause, a negative offset without after -- errbuf then starts with "line N: "
+ * (N counts every line of the file, from 1). */
+#define KMP_BYTETESTS_ERRBUF 256
+#define KMP_BT_RELATIVE    1u
+#define KMP_BT_LITTLE      2u
+enum { KMP_BT_EQ, KMP_BT_NE, KMP_BT_LT, KMP_BT_GT, KMP_BT_LE, KMP_BT_GE };
+typedef struct kmp_bytetest {
+    uint32_t anchor;
+    int32_t  offset;
+    uint32_t mask, value;
+    uint8_t  nbytes, op, flags, reserved;   /* reserved: 0 */
+} kmp_bytetest;
+typedef struct kmp_bytetests {
+    uint32_t      n;      /* number of tests                               */
+    kmp_bytetest *bt;     /* [n]                                           */
+} kmp_bytetests;
+int  kmp_bytetests_parse(const char *path, uint32_t n_patterns, kmp_bytetests *out, char errbuf[KMP_BYTETESTS_ERRBUF]);
+void kmp_bytetests_free(kmp_bytetests *b);
 
 /* ---- offset windows --------------------------------------------------------------------------
  * Not in the reference: the windows of kmpgpu_set_windows (include/kmpgpu.h) from a text file.  One window per line,

@@ -46,6 +46,13 @@
  * (KMPGPU_OPT_KEEP_META); both routes write the same files.  A headers file that does not parse, or the variable without the other two:
  * message on stderr, exit 1, before any GPU work.  stdout is what it is without the variable.
  *
+ * KMPGPU_BYTETESTS_FILE=<byte tests>, together with KMPGPU_RULES_FILE and KMPGPU_ALERTS_FILE and / or KMPGPU_FLOW_ALERTS_FILE, with or without
+ * the relations, chains and headers files: numeric fields of the payload as rule terms (kmpgpu_set_bytetests; the file format is
+ * kmp_bytetests_parse's, kmphost.h: "<nbytes> <op> <value> <offset> [after <pattern index>] [little] [mask <m>]" per line), set on every
+ * shard's context behind the header predicates and before the rules, whose file may then name test q as "b<q>" / "!b<q>"
+ * (kmp_rules_parse_bt).  A byte tests file that does not parse, or the variable without the rules and an alerts file: message on stderr,
+ * exit 1, before any GPU work.  stdout is what it is without the variable.
+ *
  * KMPGPU_WINDOWS_FILE=<windows>: per-pattern offset windows (kmpgpu_set_windows; the file format is kmp_windows_parse's, kmphost.h:
  * "<pattern index> <first> <last>" per line, '*' for no upper bound) on every shard's context.  They take effect on the files written
  * for KMPGPU_OFFSETS_FILE, KMPGPU_PACKETS_FILE and KMPGPU_RULES_FILE + KMPGPU_ALERTS_FILE: only the matches that start inside their
@@ -122,6 +129,7 @@ typedef struct cli_options {
     kmp_relations relations;                /* KMPGPU_RELATIONS_FILE (n == 0: none) */
     kmp_chains chains;                      /* KMPGPU_CHAINS_FILE (n == 0: none) */
     kmp_headers headers;                    /* KMPGPU_HEADERS_FILE (n == 0: none) */
+    kmp_bytetests bytetests;                /* KMPGPU_BYTETESTS_FILE (n == 0: none) */
     kmp_rules rules;                        /* KMPGPU_RULES_FILE, set before the first output that needs them */
 } cli_options;
 
@@ -224,16 +232,16 @@ static void load_options(int argc, char *argv[], cli_options *opt)
     opt->flows_path = env_path("KMPGPU_FLOWS_FILE");
     opt->flow_alerts_path = env_path("KMPGPU_FLOW_ALERTS_FILE");
     opt->flows_directed = env_flag("KMPGPU_FLOWS_DIRECTED");
-    const char *relations_path = env_path("KMPGPU_RELATIONS_FILE"), *chains_path = env_path("KMPGPU_CHAINS_FILE"), *headers_path = env_path("KMPGPU_HEADERS_FILE"), *windows_path = env_path("KMPGPU_WINDOWS_FILE");
+    const char *relations_path = env_path("KMPGPU_RELATIONS_FILE"), *chains_path = env_path("KMPGPU_CHAINS_FILE"), *headers_path = env_path("KMPGPU_HEADERS_FILE"), *bytetests_path = env_path("KMPGPU_BYTETESTS_FILE"), *windows_path = env_path("KMPGPU_WINDOWS_FILE");
 
     /* the content rules (an export takes the rules' any[] without an alerts file) */
     if ((opt->rules_path != NULL) != (opt->alerts_path != NULL) && !(opt->rules_path && (opt->export_path || opt->flow_alerts_path))) {
         fprintf(stderr, "KMPGPU_RULES_FILE and KMPGPU_ALERTS_FILE go together: %s is not set\n", opt->rules_path ? "KMPGPU_ALERTS_FILE" : "KMPGPU_RULES_FILE");
         exit(1);
     }
-    /* the relations, the chains and the header predicates, which the rules may name */
+    /* the relations, the chains, the header predicates and the byte tests, which the rules may name */
     char err[256];
-    _Static_assert(sizeof err >= KMP_RELATIONS_ERRBUF && sizeof err >= KMP_CHAINS_ERRBUF && sizeof err >= KMP_RULES_ERRBUF && sizeof err >= KMP_WINDOWS_ERRBUF && sizeof err >= KMP_HEADERS_ERRBUF,
+    _Static_assert(sizeof err >= KMP_RELATIONS_ERRBUF && sizeof err >= KMP_CHAINS_ERRBUF && sizeof err >= KMP_RULES_ERRBUF && sizeof err >= KMP_WINDOWS_ERRBUF && sizeof err >= KMP_HEADERS_ERRBUF && sizeof err >= KMP_BYTETESTS_ERRBUF,
                    "room for every parser's message");
     if (relations_path) {
         needs_rules_and_alerts("KMPGPU_RELATIONS_FILE", opt);
@@ -256,7 +264,19 @@ static void load_options(int argc, char *argv[], cli_options *opt)
             exit(1);
         }
     }
-    if (opt->rules_path && kmp_rules_parse_hdr(opt->rules_path, n, opt->relations.n, opt->chains.n, opt->headers.n, &opt->rules, err)) {
+    if (bytetests_path) {
+        /* a term of the rules, for the alerts per payload or per flow (or both) */
+        if (!opt->rules_path || (!opt->alerts_path && !opt->flow_alerts_path)) {
+            fprintf(stderr, "KMPGPU_BYTETESTS_FILE goes together with KMPGPU_RULES_FILE and KMPGPU_ALERTS_FILE or KMPGPU_FLOW_ALERTS_FILE: %s is not set\n",
+                    opt->rules_path ? "neither of the two" : "KMPGPU_RULES_FILE");
+            exit(1);
+        }
+        if (kmp_bytetests_parse(bytetests_path, n, &opt->bytetests, err)) {
+            fprintf(stderr, "error reading byte tests file %s: %s\n", bytetests_path, err);
+            exit(1);
+        }
+    }
+    if (opt->rules_path && kmp_rules_parse_bt(opt->rules_path, n, opt->relations.n, opt->chains.n, opt->headers.n, opt->bytetests.n, &opt->rules, err)) {
         fprintf(stderr, "error reading rules file %s: %s\n", opt->rules_path, err);
         exit(1);
     }
@@ -318,6 +338,7 @@ static void free_options(cli_options *opt)
     kmp_relations_free(&opt->relations);
     kmp_chains_free(&opt->chains);
     kmp_headers_free(&opt->headers);
+    kmp_bytetests_free(&opt->bytetests);
     free(opt->win_first); free(opt->win_last);
 }
 
@@ -383,6 +404,8 @@ static void *shard_load(void *arg)
     if (o->chains.n && kmpgpu_set_chains(j->ctx, o->chains.off, (const kmpgpu_chain_link *)o->chains.links, o->chains.n)) return shard_fail(j, "kmpgpu_set_chains");
     _Static_assert(sizeof(kmp_header) == sizeof(kmpgpu_header) && sizeof(kmp_pkt_meta) == sizeof(kmpgpu_pkt_meta), "kmp_header, kmp_pkt_meta have the layouts of kmpgpu.h");
     if (o->headers.n && kmpgpu_set_headers(j->ctx, (const kmpgpu_header *)o->headers.hdr, o->headers.n)) return shard_fail(j, "kmpgpu_set_headers");
+    _Static_assert(sizeof(kmp_bytetest) == sizeof(kmpgpu_bytetest), "kmp_bytetest has the layout of kmpgpu_bytetest");
+    if (o->bytetests.n && kmpgpu_set_bytetests(j->ctx, (const kmpgpu_bytetest *)o->bytetests.bt, o->bytetests.n)) return shard_fail(j, "kmpgpu_set_bytetests");
     if (o->want_meta && o->device_extract && kmpgpu_set_option(j->ctx, KMPGPU_OPT_KEEP_META, 1)) return shard_fail(j, "kmpgpu_set_option");
     if (o->device_extract) {
         /* only the bytes this shard's frames span are uploaded (kmpgpu_load_frames) */

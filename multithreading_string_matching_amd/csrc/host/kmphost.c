@@ -442,14 +442,15 @@ void kmp_patterns_free(kmp_patterns *p)
 
 /* ============================ text files, line by line ================================== */
 
-/* What the rules, relations, chains, windows and headers files share: one entry per line, blank lines and lines whose first non-blank character
+/* What the rules, relations, chains, windows, headers and byte tests files share: one entry per line, blank lines and lines whose first non-blank character
  * is '#' skipped.  text_lines opens path and hands every other line to fn -- p at its first non-blank character, end behind its last
  * one (the newline included), lineno counting every line of the file from 1 -- until fn returns something other than KMPHOST_OK,
  * which text_lines then returns.  The message of a file that cannot be opened (KMPHOST_EIO) and the one that goes with
  * KMPHOST_ENOMEM are written here. */
 #define KMP_LINE_ERRBUF 256
 _Static_assert(KMP_RULES_ERRBUF == KMP_LINE_ERRBUF && KMP_RELATIONS_ERRBUF == KMP_LINE_ERRBUF && KMP_CHAINS_ERRBUF == KMP_LINE_ERRBUF &&
-               KMP_WINDOWS_ERRBUF == KMP_LINE_ERRBUF && KMP_HEADERS_ERRBUF == KMP_LINE_ERRBUF, "the five formats' error buffers have one size");
+               KMP_WINDOWS_ERRBUF == KMP_LINE_ERRBUF && KMP_HEADERS_ERRBUF == KMP_LINE_ERRBUF && KMP_BYTETESTS_ERRBUF == KMP_LINE_ERRBUF,
+               "the six formats' error buffers have one size");
 typedef int (*line_fn)(void *ctx, const char *p, const char *end, size_t lineno, char *errbuf);
 
 static int out_of_memory(char *errbuf)
@@ -536,7 +537,7 @@ typedef struct rules_ctx {
     uint32_t n_patterns, n_relations, n_chains;
     kmp_rules *out;
     size_t n_off, cap_off, n_terms, cap_terms;
-    uint32_t n_headers;
+    uint32_t n_headers, n_bytetests;
 } rules_ctx;
 
 static int rules_line(void *ctx, const char *p, const char *end, size_t lineno, char *errbuf)
@@ -553,17 +554,22 @@ static int rules_line(void *ctx, const char *p, const char *end, size_t lineno, 
         const int is_chain = c->n_chains && p < end && *p == 'c';
         /* h<q>: header predicate q, in the same way */
         const int is_hdr = c->n_headers && p < end && *p == 'h';
-        if (is_rel || is_chain || is_hdr) p++;
+        /* b<q>: byte test q, in the same way */
+        const int is_bt = c->n_bytetests && p < end && *p == 'b';
+        if (is_rel || is_chain || is_hdr || is_bt) p++;
         const char *digits = p;
         while (p < end && *p >= '0' && *p <= '9') { if (v < (1ull << 40)) v = v * 10 + (uint64_t)(*p - '0'); p++; }
         const char *stop = p;
         while (stop < end && !is_c_space((uint8_t)*stop)) stop++;   /* the whole token, for the message */
-        if (p == digits && neg && stop == p && !is_rel && !is_chain && !is_hdr) return line_error(errbuf, lineno, "'!' without a pattern index");
+        if (p == digits && neg && stop == p && !is_rel && !is_chain && !is_hdr && !is_bt) return line_error(errbuf, lineno, "'!' without a pattern index");
         if (p == digits || stop != p)
-            return line_error(errbuf, lineno, "'%.*s' is not a pattern index%s%s%s", (int)(stop - tok > 64 ? 64 : stop - tok), tok,
+            return line_error(errbuf, lineno, "'%.*s' is not a pattern index%s%s%s%s", (int)(stop - tok > 64 ? 64 : stop - tok), tok,
                               c->n_relations ? " or r<relation index>" : "", c->n_chains ? " or c<chain index>" : "",
-                              c->n_headers ? " or h<header index>" : "");
-        if (is_hdr) {
+                              c->n_headers ? " or h<header index>" : "", c->n_bytetests ? " or b<byte test index>" : "");
+        if (is_bt) {
+            if (v >= c->n_bytetests) return line_error(errbuf, lineno, "byte test index %llu, but there are %u byte tests", (unsigned long long)v, c->n_bytetests);
+            row = c->n_patterns + c->n_relations + c->n_chains + c->n_headers + (uint32_t)v;
+        } else if (is_hdr) {
             if (v >= c->n_headers) return line_error(errbuf, lineno, "header index %llu, but there are %u header predicates", (unsigned long long)v, c->n_headers);
             row = c->n_patterns + c->n_relations + c->n_chains + (uint32_t)v;
         } else if (is_chain) {
@@ -601,18 +607,25 @@ int kmp_rules_parse_terms(const char *path, uint32_t n_patterns, uint32_t n_rela
 int kmp_rules_parse_hdr(const char *path, uint32_t n_patterns, uint32_t n_relations, uint32_t n_chains, uint32_t n_headers, kmp_rules *out,
                         char errbuf[KMP_RULES_ERRBUF])
 {
+    return kmp_rules_parse_bt(path, n_patterns, n_relations, n_chains, n_headers, 0, out, errbuf);
+}
+
+int kmp_rules_parse_bt(const char *path, uint32_t n_patterns, uint32_t n_relations, uint32_t n_chains, uint32_t n_headers, uint32_t n_bytetests,
+                       kmp_rules *out, char errbuf[KMP_RULES_ERRBUF])
+{
     memset(out, 0, sizeof *out);
     if (errbuf) errbuf[0] = 0;
-    /* a term is a row below 2^31: bit 31 is KMP_RULE_NOT (kmpgpu_set_relations, kmpgpu_set_chains and kmpgpu_set_headers refuse such a set too) */
-    if ((uint64_t)n_patterns + n_relations + n_chains + n_headers >= (1ull << 31)) {
+    /* a term is a row below 2^31: bit 31 is KMP_RULE_NOT (kmpgpu_set_relations, _chains, _headers and _bytetests refuse such a set too) */
+    if ((uint64_t)n_patterns + n_relations + n_chains + n_headers + n_bytetests >= (1ull << 31)) {
         if (errbuf) {
-            if (n_headers) snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations + %u chains + %u header predicates do not fit the 2^31 rows a term can name", n_patterns, n_relations, n_chains, n_headers);
+            if (n_bytetests) snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations + %u chains + %u header predicates + %u byte tests do not fit the 2^31 rows a term can name", n_patterns, n_relations, n_chains, n_headers, n_bytetests);
+            else if (n_headers) snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations + %u chains + %u header predicates do not fit the 2^31 rows a term can name", n_patterns, n_relations, n_chains, n_headers);
             else if (n_chains) snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations + %u chains do not fit the 2^31 rows a term can name", n_patterns, n_relations, n_chains);
             else snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations do not fit the 2^31 rows a term can name", n_patterns, n_relations);
         }
         return KMPHOST_EINVAL;
     }
-    rules_ctx c = {n_patterns, n_relations, n_chains, out, 0, 0, 0, 0, n_headers};
+    rules_ctx c = {n_patterns, n_relations, n_chains, out, 0, 0, 0, 0, n_headers, n_bytetests};
     int rc = rules_push(&out->off, &c.n_off, &c.cap_off, 0) ? out_of_memory(errbuf) : text_lines(path, rules_line, &c, errbuf);
     if (rc) {
         kmp_rules_free(out);
@@ -938,6 +951,117 @@ void kmp_headers_free(kmp_headers *h)
     if (!h) return;
     free(h->hdr);
     memset(h, 0, sizeof *h);
+}
+
+/* ============================ byte tests ================================================ */
+
+typedef struct bytetests_ctx {
+    uint32_t n_patterns;
+    kmp_bytetests *out;
+    size_t n, cap;
+} bytetests_ctx;
+
+/* a whole field as a number: decimal or 0x hex, with a leading '-' where neg_ok; |value| <= 2^32 - 1 */
+static int bt_number(const char *p, const char *end, int neg_ok, int64_t *out)
+{
+    const int neg = neg_ok && p < end && *p == '-';
+    if (neg) p++;
+    const int hex = end - p > 2 && p[0] == '0' && (p[1] == 'x' || p[1] == 'X');
+    if (hex) p += 2;
+    if (p == end) return 0;
+    int64_t v = 0;
+    for (; p < end; p++) {
+        int d;
+        if (*p >= '0' && *p <= '9') d = *p - '0';
+        else if (hex && *p >= 'a' && *p <= 'f') d = *p - 'a' + 10;
+        else if (hex && *p >= 'A' && *p <= 'F') d = *p - 'A' + 10;
+        else return 0;
+        v = v * (hex ? 16 : 10) + d;
+        if (v > 0xFFFFFFFFll) return 0;
+    }
+    *out = neg ? -v : v;
+    return 1;
+}
+
+static int bytetests_line(void *ctx, const char *p, const char *end, size_t lineno, char *errbuf)
+{
+    bytetests_ctx *c = (bytetests_ctx *)ctx;
+    static const char *const form = "<nbytes> <op> <value> <offset> [after <pattern index>] [little] [mask <m>]";
+    static const char *const ops[7] = {"=", "!=", "<", ">", "<=", ">=", "&"};      /* KMP_BT_EQ .. KMP_BT_GE, then the bit test */
+    const char *tok[10];
+    int len[10], nf = 0;
+    while (nf < 10 && next_field(&p, end, &tok[nf], &len[nf])) nf++;
+    if (nf < 4) return line_error(errbuf, lineno, "%d of the four fields that begin %s", nf, form);
+    if (nf > 9) return line_error(errbuf, lineno, "more fields than %s has", form);
+#define FIELD(k) (len[k] > 64 ? 64 : len[k]), tok[k]
+    kmp_bytetest b;
+    memset(&b, 0, sizeof b);
+    b.mask = 0xFFFFFFFFu;
+    int64_t v;
+    if (!bt_number(tok[0], tok[0] + len[0], 0, &v) || v < 1 || v > 4) return line_error(errbuf, lineno, "'%.*s' is not a byte count (1..4)", FIELD(0));
+    b.nbytes = (uint8_t)v;
+    int op = 0;
+    while (op < 7 && !field_is(tok[1], len[1], ops[op])) op++;
+    if (op == 7) return line_error(errbuf, lineno, "'%.*s' is not an operator (= != < > <= >= &)", FIELD(1));
+    if (!bt_number(tok[2], tok[2] + len[2], 0, &v)) return line_error(errbuf, lineno, "'%.*s' is not a value (0..4294967295, decimal or 0x hex)", FIELD(2));
+    b.value = (uint32_t)v;
+    int64_t offset;
+    if (!bt_number(tok[3], tok[3] + len[3], 1, &offset) || offset < INT32_MIN || offset > INT32_MAX)
+        return line_error(errbuf, lineno, "'%.*s' is not an offset (-2147483648..2147483647, decimal or 0x hex)", FIELD(3));
+    b.offset = (int32_t)offset;
+    int has_after = 0, has_little = 0, has_mask = 0;
+    for (int k = 4; k < nf; k++) {
+        if (field_is(tok[k], len[k], "little")) {
+            if (has_little) return line_error(errbuf, lineno, "'little' twice");
+            has_little = 1; b.flags |= KMP_BT_LITTLE;
+        } else if (field_is(tok[k], len[k], "after")) {
+            if (has_after) return line_error(errbuf, lineno, "'after' twice");
+            if (++k == nf) return line_error(errbuf, lineno, "'after' without a pattern index");
+            if (!bt_number(tok[k], tok[k] + len[k], 0, &v)) return line_error(errbuf, lineno, "'%.*s' is not a pattern index", FIELD(k));
+            if (v >= c->n_patterns) return line_error(errbuf, lineno, "pattern index %lld, but there are %u patterns", (long long)v, c->n_patterns);
+            has_after = 1; b.flags |= KMP_BT_RELATIVE; b.anchor = (uint32_t)v;
+        } else if (field_is(tok[k], len[k], "mask")) {
+            if (has_mask) return line_error(errbuf, lineno, "'mask' twice");
+            if (op == 6) return line_error(errbuf, lineno, "'&' takes its mask from <value>: it has no mask clause");
+            if (++k == nf) return line_error(errbuf, lineno, "'mask' without a mask");
+            if (!bt_number(tok[k], tok[k] + len[k], 0, &v)) return line_error(errbuf, lineno, "'%.*s' is not a mask (0..4294967295, decimal or 0x hex)", FIELD(k));
+            has_mask = 1; b.mask = (uint32_t)v;
+        } else
+            return line_error(errbuf, lineno, "'%.*s' is none of after <pattern index>, little, mask <m>", FIELD(k));
+    }
+#undef FIELD
+    if (!has_after && b.offset < 0) return line_error(errbuf, lineno, "offset %d lies in front of the payload: only a test after a pattern reaches back", b.offset);
+    if (op == 6) { b.mask = b.value; b.value = 0; b.op = KMP_BT_NE; } else b.op = (uint8_t)op;
+    if (c->n == c->cap) {
+        const size_t nc = c->cap ? c->cap * 2 : 64;
+        kmp_bytetest *nv = (kmp_bytetest *)realloc(c->out->bt, nc * sizeof *nv);
+        if (!nv) return KMPHOST_ENOMEM;
+        c->out->bt = nv; c->cap = nc;
+    }
+    c->out->bt[c->n++] = b;
+    return KMPHOST_OK;
+}
+
+int kmp_bytetests_parse(const char *path, uint32_t n_patterns, kmp_bytetests *out, char errbuf[KMP_BYTETESTS_ERRBUF])
+{
+    memset(out, 0, sizeof *out);
+    if (errbuf) errbuf[0] = 0;
+    bytetests_ctx c = {n_patterns, out, 0, 0};
+    int rc = text_lines(path, bytetests_line, &c, errbuf);
+    if (!rc && c.n > 0x7FFFFFFFull) rc = KMPHOST_EINVAL;
+    if (rc) {
+        kmp_bytetests_free(out);
+        return rc;
+    }
+    out->n = (uint32_t)c.n;
+    return KMPHOST_OK;
+}
+
+void kmp_bytetests_free(kmp_bytetests *b)
+{
+    if (!b) return;
+    free(b->bt);
+    memset(b, 0, sizeof *b);
 }
 
 /* serial.c:217-238 */

@@ -1,5 +1,5 @@
 /* kmp_launch.h -- launch entry points of kmp_scan_*.hip / kmp_prep.hip / kmp_fold.hip / kmp_marks.hip / kmp_rules.hip / kmp_relations.hip /
- * kmp_chains.hip / kmp_headers.hip / kmp_select.hip / kmp_alerts.hip / kmp_flows.hip / kmp_seams.hip, used
+ * kmp_chains.hip / kmp_headers.hip / kmp_bytetests.hip / kmp_select.hip / kmp_alerts.hip / kmp_flows.hip / kmp_seams.hip, used
  * by the C-ABI layer (kmpgpu.hip), which alone decides what is launched; the tables kmp_launch_scan_multi takes come from kmp_tables.h. */
 #ifndef KMP_LAUNCH_H
 #define KMP_LAUNCH_H
@@ -143,6 +143,19 @@ hipError_t kmp_launch_chains(const unsigned long long *marks, uint64_t stride, u
 hipError_t kmp_launch_headers(const void *meta, const uint32_t *pkt_len, uint64_t n_pkts, uint64_t stride, const uint4 *preds,
                               uint32_t n_hdr, unsigned long long *rows, unsigned long long *hdr_counts, unsigned long long *any,
                               hipStream_t st);
+/* kmp_bytetests.hip: the byte tests of kmpgpu_set_bytetests.  tests[q * 2 ..]: the 32-byte record of test q as kmp_pack_bytetests leaves
+ * it (kmp_rowtables.h), rel_idx[n_relative]: the indices of the relative tests, ascending.  One kernel per call.  relative = false: the
+ * absolute tests (none: no launch), taken KMP_BT_TILE records at a time, from arena / pkt_off / pkt_len alone; H: the largest offset +
+ * nbytes among them; every word of their rows[q][stride] (stride even, 16-byte aligned) is written, the bits of index n_pkts and above as
+ * 0.  relative = true: the relative tests (none: no launch), as kmp_launch_relations: candidates from marks[anchor][stride], word
+ * j < ceil(n_pkts / 64) of their rows written, at most max_blocks blocks, grid-stride.  Either kernel writes its own rows only, adds a
+ * test's set bits to bt_counts[q] and ORs them into any[]; the caller zeroes those two.  Field bytes come from `arena`, never from `fold`. */
+#define KMP_BT_TILE 128u
+hipError_t kmp_launch_bytetests(bool relative, const unsigned long long *marks, uint64_t stride, uint64_t n_pkts, const uint4 *tests,
+                                uint32_t n_bt, const uint32_t *rel_idx, uint32_t n_relative, uint32_t H, const kmp_pattern_dev *patterns,
+                                const uint8_t *arena, const uint8_t *fold, const uint64_t *pkt_off, const uint32_t *pkt_len,
+                                const void *windows, bool whole, uint32_t max_blocks, unsigned long long *rows,
+                                unsigned long long *bt_counts, unsigned long long *any, hipStream_t st);
 /* ... and the metadata itself.  _extract: behind kmp_launch_extract_phase2, with its arguments and its workspace: meta[k] of every accepted
  * frame, k as kmp_scatter_index_kernel numbers the payloads.  _select: behind kmp_launch_select_phase2, with the workspace of the selection
  * over src's n payloads: meta[j] = src_meta[k] for the j-th selected payload k.  One kernel each. */

@@ -1,5 +1,5 @@
 /*
- * kmp_rowtables.cpp -- the tables of the rules, windows, relations, chains and header predicates as the kernels read them (kmp_rowtables.h).  Host code only.
+ * kmp_rowtables.cpp -- the tables of the rules, windows, relations, chains, header predicates and byte tests as the kernels read them (kmp_rowtables.h).  Host code only.
  */
 #include "kmp_rowtables.h"
 
@@ -33,10 +33,16 @@ int kmp_pack_rules(const uint32_t *rule_off, const uint32_t *terms, uint32_t n_r
 int kmp_pack_rules(const uint32_t *rule_off, const uint32_t *terms, uint32_t n_rules, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains,
                    uint32_t n_hdr, std::vector<uint32_t> *heads, std::vector<uint32_t> *quads, std::string *msg)
 {
+    return kmp_pack_rules(rule_off, terms, n_rules, n_pat, n_rel, n_chains, n_hdr, 0u, heads, quads, msg);
+}
+
+int kmp_pack_rules(const uint32_t *rule_off, const uint32_t *terms, uint32_t n_rules, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains,
+                   uint32_t n_hdr, uint32_t n_bt, std::vector<uint32_t> *heads, std::vector<uint32_t> *quads, std::string *msg)
+{
     heads->clear(); quads->clear();
     if (!rule_off || !terms) return refuse(msg, "kmpgpu_set_rules: NULL rule arrays");
     if (rule_off[0] != 0) return refuse(msg, "kmpgpu_set_rules: rule_off[0] is %u, not 0", rule_off[0]);
-    const uint64_t n_rows = (uint64_t)n_pat + n_rel + n_chains + n_hdr;  /* (< 2^31: kmp_pack_relations, kmp_pack_chains, kmp_pack_headers) */
+    const uint64_t n_rows = (uint64_t)n_pat + n_rel + n_chains + n_hdr + n_bt;  /* (< 2^31: kmp_pack_relations, kmp_pack_chains, kmp_pack_headers, kmp_pack_bytetests) */
     std::vector<uint32_t> ord;
     for (uint32_t r = 0; r < n_rules; r++) {
         if (rule_off[r + 1] < rule_off[r]) return refuse(msg, "kmpgpu_set_rules: rule_off decreases at rule %u", r);
@@ -44,6 +50,9 @@ int kmp_pack_rules(const uint32_t *rule_off, const uint32_t *terms, uint32_t n_r
         ord.clear();
         for (int neg = 0; neg < 2; neg++)
             for (uint32_t j = rule_off[r]; j < rule_off[r + 1]; j++) {
+                if ((terms[j] & ~KMPGPU_RULE_NOT) >= n_rows && n_bt)
+                    return refuse(msg, "kmpgpu_set_rules: rule %u: term %u names row %u of %u patterns + %u relations + %u chains + %u header predicates + %u byte tests",
+                                  r, j - rule_off[r], terms[j] & ~KMPGPU_RULE_NOT, n_pat, n_rel, n_chains, n_hdr, n_bt);
                 if ((terms[j] & ~KMPGPU_RULE_NOT) >= n_rows && n_hdr)
                     return refuse(msg, "kmpgpu_set_rules: rule %u: term %u names row %u of %u patterns + %u relations + %u chains + %u header predicates",
                                   r, j - rule_off[r], terms[j] & ~KMPGPU_RULE_NOT, n_pat, n_rel, n_chains, n_hdr);
@@ -88,11 +97,17 @@ int kmp_pack_relations(const kmpgpu_relation *rel, uint32_t n_rel, uint32_t n_pa
 int kmp_pack_relations(const kmpgpu_relation *rel, uint32_t n_rel, uint32_t n_pat, uint32_t n_chains, uint32_t n_hdr, const uint8_t *pat_fold,
                        std::vector<uint32_t> *relations, std::string *msg)
 {
+    return kmp_pack_relations(rel, n_rel, n_pat, n_chains, n_hdr, 0u, pat_fold, relations, msg);
+}
+
+int kmp_pack_relations(const kmpgpu_relation *rel, uint32_t n_rel, uint32_t n_pat, uint32_t n_chains, uint32_t n_hdr, uint32_t n_bt,
+                       const uint8_t *pat_fold, std::vector<uint32_t> *relations, std::string *msg)
+{
     relations->clear();
     if (!rel) return refuse(msg, "kmpgpu_set_relations: rel is NULL");
-    if ((uint64_t)n_pat + n_rel + n_chains + n_hdr >= (1ull << 31))
-        return refuse(msg, "kmpgpu_set_relations: %u patterns + %u relations%s%s do not fit the 2^31 rows a rule term can name", n_pat, n_rel,
-                      n_chains ? " + the chains" : "", n_hdr ? " + the header predicates" : "");
+    if ((uint64_t)n_pat + n_rel + n_chains + n_hdr + n_bt >= (1ull << 31))
+        return refuse(msg, "kmpgpu_set_relations: %u patterns + %u relations%s%s%s do not fit the 2^31 rows a rule term can name", n_pat, n_rel,
+                      n_chains ? " + the chains" : "", n_hdr ? " + the header predicates" : "", n_bt ? " + the byte tests" : "");
     for (uint32_t q = 0; q < n_rel; q++) {
         const kmpgpu_relation &r = rel[q];
         if (r.a >= n_pat || r.b >= n_pat)
@@ -112,11 +127,17 @@ int kmp_pack_chains(const uint32_t *chain_off, const kmpgpu_chain_link *links, u
 int kmp_pack_chains(const uint32_t *chain_off, const kmpgpu_chain_link *links, uint32_t n_chains, uint32_t n_pat, uint32_t n_rel,
                     uint32_t n_hdr, const uint8_t *pat_fold, std::vector<uint32_t> *chains, std::string *msg)
 {
+    return kmp_pack_chains(chain_off, links, n_chains, n_pat, n_rel, n_hdr, 0u, pat_fold, chains, msg);
+}
+
+int kmp_pack_chains(const uint32_t *chain_off, const kmpgpu_chain_link *links, uint32_t n_chains, uint32_t n_pat, uint32_t n_rel,
+                    uint32_t n_hdr, uint32_t n_bt, const uint8_t *pat_fold, std::vector<uint32_t> *chains, std::string *msg)
+{
     chains->clear();
     if (!chain_off || !links) return refuse(msg, "kmpgpu_set_chains: NULL chain arrays");
-    if ((uint64_t)n_pat + n_rel + n_chains + n_hdr >= (1ull << 31))
-        return refuse(msg, "kmpgpu_set_chains: %u patterns + %u relations + %u chains%s do not fit the 2^31 rows a rule term can name", n_pat, n_rel,
-                      n_chains, n_hdr ? " + the header predicates" : "");
+    if ((uint64_t)n_pat + n_rel + n_chains + n_hdr + n_bt >= (1ull << 31))
+        return refuse(msg, "kmpgpu_set_chains: %u patterns + %u relations + %u chains%s%s do not fit the 2^31 rows a rule term can name", n_pat, n_rel,
+                      n_chains, n_hdr ? " + the header predicates" : "", n_bt ? " + the byte tests" : "");
     if (chain_off[0] != 0) return refuse(msg, "kmpgpu_set_chains: chain_off[0] is %u, not 0", chain_off[0]);
     for (uint32_t q = 0; q < n_chains; q++) {
         if (chain_off[q + 1] < chain_off[q]) return refuse(msg, "kmpgpu_set_chains: chain_off decreases at chain %u", q);
@@ -138,11 +159,17 @@ int kmp_pack_chains(const uint32_t *chain_off, const kmpgpu_chain_link *links, u
 int kmp_pack_headers(const kmpgpu_header *h, uint32_t n_hdr, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains, std::vector<uint32_t> *headers,
                      std::string *msg)
 {
+    return kmp_pack_headers(h, n_hdr, n_pat, n_rel, n_chains, 0u, headers, msg);
+}
+
+int kmp_pack_headers(const kmpgpu_header *h, uint32_t n_hdr, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains, uint32_t n_bt,
+                     std::vector<uint32_t> *headers, std::string *msg)
+{
     headers->clear();
     if (!h) return refuse(msg, "kmpgpu_set_headers: h is NULL");
-    if ((uint64_t)n_pat + n_rel + n_chains + n_hdr >= (1ull << 31))
-        return refuse(msg, "kmpgpu_set_headers: %u patterns + %u relations + %u chains + %u header predicates do not fit the 2^31 rows a rule term can name",
-                      n_pat, n_rel, n_chains, n_hdr);
+    if ((uint64_t)n_pat + n_rel + n_chains + n_hdr + n_bt >= (1ull << 31))
+        return refuse(msg, "kmpgpu_set_headers: %u patterns + %u relations + %u chains + %u header predicates%s do not fit the 2^31 rows a rule term can name",
+                      n_pat, n_rel, n_chains, n_hdr, n_bt ? " + the byte tests" : "");
     for (uint32_t q = 0; q < n_hdr; q++) {
         const kmpgpu_header &p = h[q];
         if (p.sport_lo > p.sport_hi) return refuse(msg, "kmpgpu_set_headers: predicate %u: source port %u lies above %u", q, p.sport_lo, p.sport_hi);
@@ -155,5 +182,43 @@ int kmp_pack_headers(const kmpgpu_header *h, uint32_t n_hdr, uint32_t n_pat, uin
                                          (uint32_t)p.sport_lo | (uint32_t)p.sport_hi << 16, (uint32_t)p.dport_lo | (uint32_t)p.dport_hi << 16, p.len_lo, p.len_hi,
                                          (uint32_t)p.proto | (uint32_t)p.flags << 8, 0u, 0u, 0u});
     }
+    return KMPGPU_OK;
+}
+
+int kmp_pack_bytetests(const kmpgpu_bytetest *bt, uint32_t n_bt, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains, uint32_t n_hdr,
+                       const uint8_t *pat_fold, std::vector<uint32_t> *tests, uint32_t *n_relative, uint32_t *reach, std::string *msg)
+{
+    tests->clear();
+    *n_relative = 0u; *reach = 0u;
+    if (!bt) return refuse(msg, "kmpgpu_set_bytetests: bt is NULL");
+    if ((uint64_t)n_pat + n_rel + n_chains + n_hdr + n_bt >= (1ull << 31))
+        return refuse(msg, "kmpgpu_set_bytetests: %u patterns + %u relations + %u chains + %u header predicates + %u byte tests do not fit the 2^31 rows a rule term can name",
+                      n_pat, n_rel, n_chains, n_hdr, n_bt);
+    std::vector<uint32_t> recs, relative;             /* a refusal leaves *tests empty */
+    uint32_t far = 0u;
+    for (uint32_t q = 0; q < n_bt; q++) {
+        const kmpgpu_bytetest &b = bt[q];
+        if (b.nbytes < 1 || b.nbytes > 4) return refuse(msg, "kmpgpu_set_bytetests: test %u reads %u bytes, not 1 .. 4", q, b.nbytes);
+        if (b.op > KMPGPU_BT_GE) return refuse(msg, "kmpgpu_set_bytetests: test %u: unknown operator %u", q, b.op);
+        if (b.flags & ~(KMPGPU_BT_RELATIVE | KMPGPU_BT_LITTLE))
+            return refuse(msg, "kmpgpu_set_bytetests: test %u: unknown flag bits 0x%x", q, b.flags & ~(KMPGPU_BT_RELATIVE | KMPGPU_BT_LITTLE));
+        if (b.reserved != 0) return refuse(msg, "kmpgpu_set_bytetests: test %u: reserved is %u, not 0", q, b.reserved);
+        uint32_t anchor = 0u;
+        if (b.flags & KMPGPU_BT_RELATIVE) {
+            if (b.anchor >= n_pat) return refuse(msg, "kmpgpu_set_bytetests: test %u names pattern %u of %u", q, b.anchor, n_pat);
+            anchor = fold_bit(pat_fold, b.anchor);
+            relative.push_back(q);
+        } else {
+            if (b.anchor != 0) return refuse(msg, "kmpgpu_set_bytetests: test %u is absolute and names anchor %u, not 0", q, b.anchor);
+            if (b.offset < 0) return refuse(msg, "kmpgpu_set_bytetests: test %u is absolute and its offset %d lies in front of the payload", q, b.offset);
+            if ((uint32_t)b.offset + b.nbytes > far) far = (uint32_t)b.offset + b.nbytes;
+        }
+        recs.insert(recs.end(), {anchor, (uint32_t)b.offset, b.mask, b.value,
+                                     (uint32_t)b.nbytes | (uint32_t)b.op << 8 | (uint32_t)b.flags << 16, 0u, 0u, 0u});
+    }
+    *n_relative = (uint32_t)relative.size();
+    *reach = far;
+    tests->swap(recs);
+    tests->insert(tests->end(), relative.begin(), relative.end());
     return KMPGPU_OK;
 }

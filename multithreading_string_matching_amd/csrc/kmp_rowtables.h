@@ -1,7 +1,7 @@
 /*
- * kmp_rowtables.h -- what kmpgpu_set_rules, kmpgpu_set_windows, kmpgpu_set_relations, kmpgpu_set_chains and kmpgpu_set_headers upload, checked and packed on
+ * kmp_rowtables.h -- what kmpgpu_set_rules, kmpgpu_set_windows, kmpgpu_set_relations, kmpgpu_set_chains, kmpgpu_set_headers and kmpgpu_set_bytetests upload, checked and packed on
  * the host by kmp_rowtables.cpp into the form the kernels read bit for bit (kmp_launch.h: kmp_launch_rules, emit_windows,
- * kmp_launch_relations, kmp_launch_chains, kmp_launch_headers).  Host code without a HIP header, as kmp_tables.h: it builds and runs without a device
+ * kmp_launch_relations, kmp_launch_chains, kmp_launch_headers, kmp_launch_bytetests).  Host code without a HIP header, as kmp_tables.h: it builds and runs without a device
  * (tests/rowtables_sanitizer_driver.cpp).
  *
  * Every packer returns KMPGPU_OK with its table -- 16-byte records as four uint32_t, window records as two -- or KMPGPU_EINVAL with the
@@ -49,5 +49,22 @@ int kmp_pack_chains(const uint32_t *chain_off, const kmpgpu_chain_link *links, u
  * dport_lo | dport_hi << 16, len_lo, len_hi}, {proto | flags << 8, 0, 0, 0} */
 int kmp_pack_headers(const kmpgpu_header *h, uint32_t n_hdr, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains, std::vector<uint32_t> *headers,
                      std::string *msg);
+
+/* The same once more with the byte tests' rows behind the header predicates': terms name rows below n_pat + n_rel + n_chains + n_hdr + n_bt,
+ * and every 2^31 bound counts n_bt in.  With n_bt = 0 every message is what the entries above give. */
+int kmp_pack_rules(const uint32_t *rule_off, const uint32_t *terms, uint32_t n_rules, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains,
+                   uint32_t n_hdr, uint32_t n_bt, std::vector<uint32_t> *heads, std::vector<uint32_t> *quads, std::string *msg);
+int kmp_pack_relations(const kmpgpu_relation *rel, uint32_t n_rel, uint32_t n_pat, uint32_t n_chains, uint32_t n_hdr, uint32_t n_bt,
+                       const uint8_t *pat_fold, std::vector<uint32_t> *relations, std::string *msg);
+int kmp_pack_chains(const uint32_t *chain_off, const kmpgpu_chain_link *links, uint32_t n_chains, uint32_t n_pat, uint32_t n_rel,
+                    uint32_t n_hdr, uint32_t n_bt, const uint8_t *pat_fold, std::vector<uint32_t> *chains, std::string *msg);
+int kmp_pack_headers(const kmpgpu_header *h, uint32_t n_hdr, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains, uint32_t n_bt,
+                     std::vector<uint32_t> *headers, std::string *msg);
+
+/* Two 16-byte records per test: {anchor | fold << 31 (0 for an absolute test), offset, mask, value}, {nbytes | op << 8 | flags << 16, 0, 0, 0};
+ * behind the 8 n_bt words of the records the *n_relative indices of the relative tests, ascending (the relative kernel's work list).
+ * *reach: the largest offset + nbytes of the absolute tests, 0 without one (H of kmp_launch_bytetests). */
+int kmp_pack_bytetests(const kmpgpu_bytetest *bt, uint32_t n_bt, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains, uint32_t n_hdr,
+                       const uint8_t *pat_fold, std::vector<uint32_t> *tests, uint32_t *n_relative, uint32_t *reach, std::string *msg);
 
 #endif

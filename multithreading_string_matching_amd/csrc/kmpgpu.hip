@@ -167,7 +167,7 @@ struct kmpgpu_ctx {
     size_t              h_counts_cap = 0;
     unsigned long long *h_small = nullptr;            /* pinned, 16 words: where the loaders read small device results back (a copy to pageable
                                                          memory goes through the runtime's blocking staging path) */
-    unsigned long long *d_marks = nullptr;            /* the marking pass: hit matrix [n_pat + n_rel + n_chains + n_hdr][stride], then pkt_counts[n_pat], any[stride], counts[n_pat], rel_pkt_counts[n_rel], chain_pkt_counts[n_chains], hdr_pkt_counts[n_hdr] */
+    unsigned long long *d_marks = nullptr;            /* the marking pass: hit matrix [n_pat + n_rel + n_chains + n_hdr + n_bt][stride], then pkt_counts[n_pat], any[stride], counts[n_pat], rel_pkt_counts[n_rel], chain_pkt_counts[n_chains], hdr_pkt_counts[n_hdr], bt_pkt_counts[n_bt] */
     uint64_t            marks_cap = 0;                /* words */
     /* kmpgpu_set_rules / kmpgpu_scan_rules: the rules as the kernel reads them (kmp_launch.h, kmp_launch_rules) and the results */
     uint32_t            n_rules = 0;
@@ -191,6 +191,11 @@ struct kmpgpu_ctx {
      * is row n_pat + n_rel + n_chains + q of the hit matrix and term n_pat + n_rel + n_chains + q of a rule */
     uint32_t            n_hdr = 0;
     uint4              *d_headers = nullptr;
+    /* kmpgpu_set_bytetests: two 16-byte records per test as the byte-test kernels read them, then the indices of the n_bt_rel relative tests
+     * (kmp_launch.h, kmp_launch_bytetests); bt_reach: the largest offset + nbytes of the absolute ones.  Test q is row
+     * n_pat + n_rel + n_chains + n_hdr + q of the hit matrix and term n_pat + n_rel + n_chains + n_hdr + q of a rule */
+    uint32_t            n_bt = 0, n_bt_rel = 0, bt_reach = 0;
+    uint4              *d_bytetests = nullptr;
     /* the per-payload metadata the predicates are decided from (kmpgpu_pkt_meta, 16 bytes each), in payload order.  It belongs to the arena:
      * has_meta falls with it (release_arena), the buffer is kept for the next one */
     uint4              *d_meta = nullptr;
@@ -405,6 +410,13 @@ void drop_headers(kmpgpu_ctx *c)
     c->n_hdr = 0;
 }
 
+/* ... and the byte tests */
+void drop_bytetests(kmpgpu_ctx *c)
+{
+    free_buffer(&c->d_bytetests);
+    c->n_bt = c->n_bt_rel = c->bt_reach = 0;
+}
+
 /* the flows go with the arena and its metadata; their buffers are kept for the next build */
 void drop_flows(kmpgpu_ctx *c)
 {
@@ -432,6 +444,7 @@ void release_patterns(kmpgpu_ctx *c)
     drop_relations(c);                             /* ... and the relations' */
     drop_chains(c);                                /* ... and the chains' */
     drop_headers(c);                               /* ... and the header predicates sit behind all of them */
+    drop_bytetests(c);                             /* ... and the byte tests' anchors meant these patterns */
     c->pat_fold.clear();
     c->pat_sig.clear();
     c->alerts_valid = false;                       /* the list named their rows */
@@ -1738,7 +1751,7 @@ namespace {
 struct MarkPass {
     bool empty = false;
     uint64_t W = 0, stride = 0, mat = 0;          /* words per row as the caller sees them / on the device (even); words of the matrix */
-    unsigned long long *d_mat = nullptr, *d_cnt = nullptr;       /* [n_pat + n_rel + n_chains + n_hdr][stride]; the scan's counts [n_pat] */
+    unsigned long long *d_mat = nullptr, *d_cnt = nullptr;       /* [n_pat + n_rel + n_chains + n_hdr + n_bt][stride]; the scan's counts [n_pat] */
     uint32_t launches = 0;
 };
 
@@ -1761,11 +1774,12 @@ int marking_pass(kmpgpu_ctx *c, const char *who, MarkPass *p)
         const int rr = repack_arena(c);
         if (rr) return rr;
     }
-    /* one device buffer, grown like the others: [marks (n_pat + n_rel + n_chains + n_hdr) x stride][pkt_counts n_pat][any stride][counts n_pat]
-     * [rel_pkt_counts n_rel][chain_pkt_counts n_chains][hdr_pkt_counts n_hdr]; the scan kernels mark rows 0 .. n_pat - 1, the relation
-     * kernel, the chain kernel and the header kernel write the rows behind them (family_rows) */
-    const uint64_t mat = ((uint64_t)np + c->n_rel + c->n_chains + c->n_hdr) * stride;
-    const uint64_t words = mat + np + stride + np + c->n_rel + c->n_chains + c->n_hdr;
+    /* one device buffer, grown like the others: [marks (n_pat + n_rel + n_chains + n_hdr + n_bt) x stride][pkt_counts n_pat][any stride]
+     * [counts n_pat][rel_pkt_counts n_rel][chain_pkt_counts n_chains][hdr_pkt_counts n_hdr][bt_pkt_counts n_bt]; the scan kernels mark rows
+     * 0 .. n_pat - 1, the relation kernel, the chain kernel, the header kernel and the byte-test kernels write the rows behind them
+     * (family_rows) */
+    const uint64_t mat = ((uint64_t)np + c->n_rel + c->n_chains + c->n_hdr + c->n_bt) * stride;
+    const uint64_t words = mat + np + stride + np + c->n_rel + c->n_chains + c->n_hdr + c->n_bt;
     hipError_t e = grow_buffer(&c->d_marks, &c->marks_cap, words, EIGHTH);
     if (e != hipSuccess) return alloc_fail(e, "%s: the hit matrix (%llu bytes) could not be allocated", who, (unsigned long long)(words * 8u));
     p->stride = stride; p->mat = mat;
@@ -1789,8 +1803,10 @@ hipError_t download_rows(kmpgpu_ctx *c, uint64_t *dst, const unsigned long long 
 
 /* the header predicates' rows: a family of kmpgpu_scan_headers and of the rules' terms, none of kmpgpu_scan_alerts (kmpgpu.h) */
 constexpr int FAMILY_HEADERS = KMPGPU_ALERT_CHAINS + 1;
+/* ... and the byte tests': a family of kmpgpu_scan_bytetests and of the rules' terms */
+constexpr int FAMILY_BYTETESTS = KMPGPU_ALERT_CHAINS + 2;
 
-/* A row family (KMPGPU_ALERT_*, FAMILY_HEADERS): patterns, rules, relations, chains or header predicates.  Where its results lie on the device once its kernels are
+/* A row family (KMPGPU_ALERT_*, FAMILY_HEADERS, FAMILY_BYTETESTS): patterns, rules, relations, chains, header predicates or byte tests.  Where its results lie on the device once its kernels are
  * enqueued behind a marking pass (enqueue_family). */
 struct FamilyRows {
     unsigned long long *d_rows = nullptr, *d_pc = nullptr, *d_any = nullptr;     /* [n_rows][stride], payloads per row [n_rows], [stride] */
@@ -1801,10 +1817,10 @@ struct FamilyRows {
 uint64_t family_n_rows(const kmpgpu_ctx *c, int family)
 {
     return family == KMPGPU_ALERT_PATTERNS ? c->n_pat : family == KMPGPU_ALERT_RULES ? c->n_rules : family == KMPGPU_ALERT_RELATIONS ? c->n_rel
-         : family == KMPGPU_ALERT_CHAINS ? c->n_chains : c->n_hdr;
+         : family == KMPGPU_ALERT_CHAINS ? c->n_chains : family == FAMILY_HEADERS ? c->n_hdr : c->n_bt;
 }
 
-/* The one place that knows where the families live: the patterns, relations, chains and header predicates in the marks buffer as marking_pass lays it out
+/* The one place that knows where the families live: the patterns, relations, chains, header predicates and byte tests in the marks buffer as marking_pass lays it out
  * (they share its any[]; one family's kernel writes it per pass), the rules in the context's rule buffer [rule rows n_rules x stride]
  * [rule_pkt_counts n_rules][any stride]. */
 void family_rows(const kmpgpu_ctx *c, const MarkPass &p, int family, FamilyRows *f)
@@ -1816,7 +1832,8 @@ void family_rows(const kmpgpu_ctx *c, const MarkPass &p, int family, FamilyRows 
         return;
     }
     const uint64_t np = c->n_pat, first = family == KMPGPU_ALERT_PATTERNS ? 0 : family == KMPGPU_ALERT_RELATIONS ? np
-                                        : family == KMPGPU_ALERT_CHAINS ? np + c->n_rel : np + c->n_rel + c->n_chains;
+                                        : family == KMPGPU_ALERT_CHAINS ? np + c->n_rel : family == FAMILY_HEADERS ? np + c->n_rel + c->n_chains
+                                        : np + c->n_rel + c->n_chains + c->n_hdr;
     f->d_rows = p.d_mat + first * p.stride;
     f->d_pc = family == KMPGPU_ALERT_PATTERNS ? p.d_mat + p.mat : p.d_cnt + first;      /* (the counts of the rows behind the patterns': behind the scan's counts) */
     f->d_any = p.d_mat + p.mat + np;
@@ -1851,9 +1868,29 @@ int enqueue_headers(kmpgpu_ctx *c, const MarkPass &p)
     return KMPGPU_OK;
 }
 
+/* The byte-test kernels behind a marking pass, in the same way: one for the absolute tests, one for the relative ones, each only where there
+ * are some.  *launches: how many that were. */
+int enqueue_bytetests(kmpgpu_ctx *c, const MarkPass &p, uint32_t *launches)
+{
+    FamilyRows f;
+    family_rows(c, p, FAMILY_BYTETESTS, &f);
+    const uint32_t *rel_idx = reinterpret_cast<const uint32_t *>(c->d_bytetests) + (size_t)c->n_bt * 8u;
+    for (int relative = 0; relative < 2; relative++) {
+        if (relative ? c->n_bt_rel == 0 : c->n_bt_rel == c->n_bt) continue;
+        hipEvent_t e1;
+        HIP_TRY(profile_launch(c, &e1));
+        HIP_TRY(kmp_launch_bytetests(relative != 0, p.d_mat, p.stride, c->n_pkts, c->d_bytetests, c->n_bt, rel_idx, c->n_bt_rel, c->bt_reach,
+                                     c->d_patterns, c->d_arena, c->d_fold, c->d_off, c->d_len, c->d_windows, c->whole_payload != 0,
+                                     (uint32_t)c->cu_count * 8u, f.d_rows, f.d_pc, f.d_any, c->stream));
+        HIP_TRY(profile_launched(c, e1));
+        ++*launches;
+    }
+    return KMPGPU_OK;
+}
+
 /* The one place that runs a family's kernels behind a marking pass, and says where they leave their results.  Patterns: the marks reduce.
- * Relations, chains, header predicates: their kernel.  Rules: the relation kernel, the chain kernel and the header kernel where those are
- * set, then the rules kernel, into the context's rule buffer, grown here. */
+ * Relations, chains, header predicates, byte tests: their kernels.  Rules: the relation kernel, the chain kernel, the header kernel and the
+ * byte-test kernels where those are set, then the rules kernel, into the context's rule buffer, grown here. */
 int enqueue_family(kmpgpu_ctx *c, const char *who, int family, const MarkPass &p, bool profile_reduce, FamilyRows *f)
 {
     hipEvent_t e1 = nullptr;
@@ -1889,6 +1926,10 @@ int enqueue_family(kmpgpu_ctx *c, const char *who, int family, const MarkPass &p
             if (rr) return rr;
             f->launches++;
         }
+        if (c->n_bt) {
+            const int rr = enqueue_bytetests(c, p, &f->launches);
+            if (rr) return rr;
+        }
         HIP_TRY(profile_launch(c, &e1));
         HIP_TRY(kmp_launch_rules(p.d_mat, p.stride, c->n_pkts, c->d_rule_heads, c->d_rule_quads, c->n_rules, f->d_rows, f->d_pc, f->d_any, c->stream));
         HIP_TRY(profile_launched(c, e1));
@@ -1896,6 +1937,7 @@ int enqueue_family(kmpgpu_ctx *c, const char *who, int family, const MarkPass &p
         return KMPGPU_OK;
     }
     family_rows(c, p, family, f);
+    if (family == FAMILY_BYTETESTS) return enqueue_bytetests(c, p, &f->launches);
     f->launches = 1u;
     return family == FAMILY_HEADERS ? enqueue_headers(c, p) : enqueue_pairing(c, p, family);
 }
@@ -1931,7 +1973,7 @@ int finish_marking(kmpgpu_ctx *c, uint32_t launches, kmpgpu_timing *t)
     return KMPGPU_OK;
 }
 
-/* The body of kmpgpu_scan_packets, _rules, _relations, _chains and _headers behind their own checks: marking pass, the family's kernels, downloads. */
+/* The body of kmpgpu_scan_packets, _rules, _relations, _chains, _headers and _bytetests behind their own checks: marking pass, the family's kernels, downloads. */
 int scan_family(kmpgpu_ctx *c, const char *who, int family, uint64_t *row_counts_out, uint64_t *any_out, uint64_t *hits_out, uint64_t *counts_out,
                 kmpgpu_timing *t)
 {
@@ -2005,7 +2047,7 @@ int kmpgpu_set_rules(kmpgpu_ctx *c, const uint32_t *rule_off, const uint32_t *te
     std::vector<uint32_t> heads, quads;
     std::string msg;
     if (n_rules) {
-        const int rc = kmp_pack_rules(rule_off, terms, n_rules, c->n_pat, c->n_rel, c->n_chains, c->n_hdr, &heads, &quads, &msg);
+        const int rc = kmp_pack_rules(rule_off, terms, n_rules, c->n_pat, c->n_rel, c->n_chains, c->n_hdr, c->n_bt, &heads, &quads, &msg);
         if (rc) return fail(rc, "%s", msg.c_str());
         if (quads.empty()) quads.assign(4, 0u);         /* rules of one or two terms only: one quad nobody reads, never a NULL table */
     }
@@ -2042,7 +2084,7 @@ int kmpgpu_set_relations(kmpgpu_ctx *c, const kmpgpu_relation *rel, uint32_t n_r
     std::vector<uint32_t> host;
     std::string msg;
     if (n_rel) {
-        const int rc = kmp_pack_relations(rel, n_rel, c->n_pat, c->n_chains, c->n_hdr, c->pat_fold.data(), &host, &msg);
+        const int rc = kmp_pack_relations(rel, n_rel, c->n_pat, c->n_chains, c->n_hdr, c->n_bt, c->pat_fold.data(), &host, &msg);
         if (rc) return fail(rc, "%s", msg.c_str());
     }
     const int rc = swap_tables(c, "kmpgpu_set_relations: the relations", {{host, (void **)&c->d_relations}});
@@ -2067,7 +2109,7 @@ int kmpgpu_set_chains(kmpgpu_ctx *c, const uint32_t *chain_off, const kmpgpu_cha
     std::vector<uint32_t> host;
     std::string msg;
     if (n_chains) {
-        const int rc = kmp_pack_chains(chain_off, links, n_chains, c->n_pat, c->n_rel, c->n_hdr, c->pat_fold.data(), &host, &msg);
+        const int rc = kmp_pack_chains(chain_off, links, n_chains, c->n_pat, c->n_rel, c->n_hdr, c->n_bt, c->pat_fold.data(), &host, &msg);
         if (rc) return fail(rc, "%s", msg.c_str());
     }
     const int rc = swap_tables(c, "kmpgpu_set_chains: the chains", {{host, (void **)&c->d_chains}});
@@ -2093,7 +2135,7 @@ int kmpgpu_set_headers(kmpgpu_ctx *c, const kmpgpu_header *h, uint32_t n_hdr)
     std::vector<uint32_t> host;
     std::string msg;
     if (n_hdr) {
-        const int rc = kmp_pack_headers(h, n_hdr, c->n_pat, c->n_rel, c->n_chains, &host, &msg);
+        const int rc = kmp_pack_headers(h, n_hdr, c->n_pat, c->n_rel, c->n_chains, c->n_bt, &host, &msg);
         if (rc) return fail(rc, "%s", msg.c_str());
     }
     const int rc = swap_tables(c, "kmpgpu_set_headers: the header predicates", {{host, (void **)&c->d_headers}});
@@ -2109,6 +2151,33 @@ int kmpgpu_scan_headers(kmpgpu_ctx *c, uint64_t *hdr_pkt_counts_out, uint64_t *a
     if (!c->d_patterns || c->n_pat == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan_headers: no patterns set");
     if (c->n_hdr == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan_headers: no header predicates set");
     return scan_family(c, "kmpgpu_scan_headers", FAMILY_HEADERS, hdr_pkt_counts_out, any_out, hdr_hits_out, counts_out, t);
+}
+
+int kmpgpu_set_bytetests(kmpgpu_ctx *c, const kmpgpu_bytetest *bt, uint32_t n_bt)
+{
+    static_assert(sizeof(kmpgpu_bytetest) == 20, "kmpgpu_bytetest is the 20-byte record of kmpgpu.h");
+    const int sr = setter_state(c, "kmpgpu_set_bytetests");
+    if (sr) return sr;
+    std::vector<uint32_t> host;
+    std::string msg;
+    uint32_t n_relative = 0, reach = 0;
+    if (n_bt) {
+        const int rc = kmp_pack_bytetests(bt, n_bt, c->n_pat, c->n_rel, c->n_chains, c->n_hdr, c->pat_fold.data(), &host, &n_relative, &reach, &msg);
+        if (rc) return fail(rc, "%s", msg.c_str());
+    }
+    const int rc = swap_tables(c, "kmpgpu_set_bytetests: the byte tests", {{host, (void **)&c->d_bytetests}});
+    if (rc) return rc;
+    drop_rules(c);                                 /* the rows their terms named are no longer the same, whatever was set or cleared */
+    c->n_bt = n_bt; c->n_bt_rel = n_relative; c->bt_reach = reach;
+    return KMPGPU_OK;
+}
+
+int kmpgpu_scan_bytetests(kmpgpu_ctx *c, uint64_t *bt_pkt_counts_out, uint64_t *any_out, uint64_t *bt_hits_out, uint64_t *counts_out, kmpgpu_timing *t)
+{
+    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_scan_bytetests: ctx is NULL");
+    if (!c->d_patterns || c->n_pat == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan_bytetests: no patterns set");
+    if (c->n_bt == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan_bytetests: no byte tests set");
+    return scan_family(c, "kmpgpu_scan_bytetests", FAMILY_BYTETESTS, bt_pkt_counts_out, any_out, bt_hits_out, counts_out, t);
 }
 
 int kmpgpu_set_meta(kmpgpu_ctx *c, const void *meta, uint64_t n_pkts, int on_device)
@@ -2377,7 +2446,7 @@ static int scan_flows_body(kmpgpu_ctx *c, const char *who, kmpgpu_ctx *sm, int f
     /* the folded matrix, rows of an even number of words as the reduce and the rules kernel read them: SCOPE_PACKET [family's rows x Sf]
      * [flow_counts rows][any Sf]; SCOPE_FLOW [term rows x Sf][rule rows x Sf][flow_counts rules][any Sf] */
     const uint64_t Wf = (c->n_flows + 63u) / 64u, Sf = (Wf + 1u) & ~1ull;
-    const uint64_t n_terms = (uint64_t)c->n_pat + c->n_rel + c->n_chains + c->n_hdr;
+    const uint64_t n_terms = (uint64_t)c->n_pat + c->n_rel + c->n_chains + c->n_hdr + c->n_bt;
     const uint64_t fold_rows = per_flow ? n_terms : n_rows, out_rows = per_flow ? n_terms + n_rows : n_rows;
     const uint64_t words = out_rows * Sf + n_rows + Sf;
     const hipError_t e = grow_buffer(&c->d_flow_fold, &c->flow_fold_cap, words, EIGHTH);

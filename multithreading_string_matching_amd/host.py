@@ -18,6 +18,9 @@ PROTO = {"udp": 0, "tcp": 1}
 # kmp_pkt_meta / kmpgpu_pkt_meta, 16 bytes: what GpuMatcher.set_meta takes and .meta() returns
 META_DTYPE = np.dtype([("src_ip", "<u4"), ("dst_ip", "<u4"), ("src_port", "<u2"), ("dst_port", "<u2"), ("proto", "u1"), ("reserved", "u1", (3,))])
 # kmp_header / kmpgpu_header, 36 bytes: one header predicate
+# kmp_bytetest / kmpgpu_bytetest, 20 bytes: one byte test
+BYTETEST_DTYPE = np.dtype([("anchor", "<u4"), ("offset", "<i4"), ("mask", "<u4"), ("value", "<u4"), ("nbytes", "u1"), ("op", "u1"), ("flags", "u1"),
+                           ("reserved", "u1")])
 HEADER_DTYPE = np.dtype([("src_ip", "<u4"), ("src_mask", "<u4"), ("dst_ip", "<u4"), ("dst_mask", "<u4"), ("sport_lo", "<u2"), ("sport_hi", "<u2"),
                          ("dport_lo", "<u2"), ("dport_hi", "<u2"), ("len_lo", "<u4"), ("len_hi", "<u4"), ("proto", "u1"), ("flags", "u1"),
                          ("reserved", "<u2")])
@@ -124,6 +127,20 @@ def parse_headers(path: str) -> np.ndarray:
         return np.frombuffer(C.string_at(h.hdr, h.n * C.sizeof(_lib.Header)), dtype=HEADER_DTYPE).copy() if h.n else np.zeros(0, HEADER_DTYPE)
     finally:
         L.kmp_headers_free(C.byref(h))
+
+
+def parse_bytetests(path: str, n_patterns: int) -> np.ndarray:
+    """The tests of a byte tests file as a BYTETEST_DTYPE array (kmp_bytetests_parse); KmpHostError carries the parser's message."""
+    L = _lib.host_lib()
+    b = _lib.ByteTests()
+    err = C.create_string_buffer(_lib.KMP_BYTETESTS_ERRBUF)
+    rc = L.kmp_bytetests_parse(path.encode(), n_patterns, C.byref(b), err)
+    if rc:
+        raise KmpHostError(f"{err.value.decode(errors='replace')} ({rc})")
+    try:
+        return np.frombuffer(C.string_at(b.bt, b.n * C.sizeof(_lib.ByteTest)), dtype=BYTETEST_DTYPE).copy() if b.n else np.zeros(0, BYTETEST_DTYPE)
+    finally:
+        L.kmp_bytetests_free(C.byref(b))
 
 
 # ---------------------------------------------------------------------------------------------

@@ -16,7 +16,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import KmpGpuError, Match, SynthParams, Timing, gpu_check, u8p, u32p, u64p
-from .host import HEADER_DTYPE, META_DTYPE, HostArena
+from .host import BYTETEST_DTYPE, HEADER_DTYPE, META_DTYPE, HostArena
 
 OPT_MODE, OPT_BLOCKS_PER_CU, OPT_DEPTH, OPT_FUSED, OPT_KERNEL, OPT_ACCUMULATE, OPT_NONTEMPORAL = 1, 2, 3, 4, 5, 6, 100
 OPT_REPACK = 7
@@ -83,6 +83,7 @@ class GpuMatcher:
         self.relations: list = []  # (a, b, dmin, dmax) per relation as set_relations took them (None: unbounded side), [] = none
         self.chains: list = []     # (p0, (p1, dmin, dmax), ...) per chain as set_chains took them (None: unbounded side), [] = none
         self.headers = np.zeros(0, dtype=HEADER_DTYPE)     # the predicates as set_headers took them
+        self.bytetests = np.zeros(0, dtype=BYTETEST_DTYPE)  # the byte tests as set_bytetests took them
         self._keep = None          # objects whose device memory the context borrows
         self._comm = None          # the GpuComm this matcher is a rank of: closed before the context
 
@@ -113,6 +114,7 @@ class GpuMatcher:
         self.relations = []        # ... and its relations
         self.chains = []           # ... and its chains
         self.headers = np.zeros(0, dtype=HEADER_DTYPE)     # ... and its header predicates
+        self.bytetests = np.zeros(0, dtype=BYTETEST_DTYPE)  # ... and its byte tests
 
     def set_rules(self, rules) -> None:
         """Content rules over the current patterns (kmpgpu_set_rules): a sequence of (all_of, none_of) pattern-index sequences;
@@ -121,7 +123,7 @@ class GpuMatcher:
         for a, b in rules:
             for i in a + b:
                 if not 0 <= i < _lib.RULE_NOT:
-                    raise ValueError(f"rule term {i}: not a pattern index (or rel(q), chain(c), hdr(q))")
+                    raise ValueError(f"rule term {i}: not a pattern index (or rel(q), chain(c), hdr(q), btest(q))")
         off = np.zeros(len(rules) + 1, dtype=np.uint32)
         off[1:] = np.cumsum([len(a) + len(b) for a, b in rules])
         terms = np.array([t for a, b in rules for t in a + [i | _lib.RULE_NOT for i in b]] or [0], dtype=np.uint32)
@@ -215,6 +217,34 @@ class GpuMatcher:
         if not 0 <= q < len(self.headers):
             raise ValueError(f"hdr({q}): {len(self.headers)} header predicates are set")
         return len(self.patterns) + len(self.relations) + len(self.chains) + q
+
+    def set_bytetests(self, tests) -> None:
+        """Byte tests (kmpgpu_set_bytetests): a BYTETEST_DTYPE array, or a sequence of dicts with nbytes (1..4), op (_lib.BT_EQ .. BT_GE),
+        value and offset, and any of mask (left out: all bits), anchor (a pattern index: the test is relative, its offset counts from the
+        end of a match of that pattern; _lib.BT_RELATIVE is set for it) and flags (_lib.BT_LITTLE; default big-endian).  Test q holds for
+        a payload where ((field & mask) op value) for the unsigned integer the nbytes bytes at the position form, all of them in front
+        of the payload's text end.  None or an empty sequence clears them.  Every successful call drops the rules, as the library does:
+        relations, chains, headers, byte tests, then the rules, whose terms may be btest(q)."""
+        if isinstance(tests, np.ndarray) and tests.dtype == BYTETEST_DTYPE:
+            arr = np.ascontiguousarray(tests)
+        else:
+            arr = np.zeros(len(tests or []), dtype=BYTETEST_DTYPE)
+            for r, b in zip(arr, tests or []):
+                r["mask"] = 0xFFFFFFFF
+                if "anchor" in b:
+                    r["flags"] = _lib.BT_RELATIVE
+                for k, v in b.items():
+                    r[k] = (int(r[k]) | int(v)) if k == "flags" else int(v)
+        gpu_check(self._g.kmpgpu_set_bytetests(self._ctx, C.cast(arr.ctypes.data, C.POINTER(_lib.ByteTest)) if arr.size else None, int(arr.size)),
+                  "kmpgpu_set_bytetests")
+        self.bytetests = arr.copy()
+        self.rules = []            # the library drops its rules with the rows they referred to
+
+    def btest(self, q: int) -> int:
+        """The term of byte test q in set_rules: it is row len(patterns) + len(relations) + len(chains) + len(headers) + q of the hit matrix."""
+        if not 0 <= q < len(self.bytetests):
+            raise ValueError(f"btest({q}): {len(self.bytetests)} byte tests are set")
+        return len(self.patterns) + len(self.relations) + len(self.chains) + len(self.headers) + q
 
     def set_meta(self, meta) -> None:
         """The per-payload header metadata of the arena at hand (kmpgpu_set_meta): a META_DTYPE array with one record per payload
@@ -422,7 +452,7 @@ class GpuMatcher:
         return arr, int(found.value), counts[:n]
 
     def _scan_family(self, fn, rows: int, counts_key: str, hits: bool) -> dict:
-        """What scan_packets, scan_rules, scan_relations, scan_chains and scan_headers share: the C call ``fn`` over a family of ``rows`` rows, its
+        """What scan_packets, scan_rules, scan_relations, scan_chains, scan_headers and scan_bytetests share: the C call ``fn`` over a family of ``rows`` rows, its
         per-row payload counts returned under ``counts_key``."""
         n = len(self.patterns)
         n_pkts, _ = self.arena_info()
@@ -470,6 +500,12 @@ class GpuMatcher:
         ``hdr_pkt_counts`` (uint64[n_hdr]) payloads for which predicate q holds, ``any`` (bool[n_pkts]) some predicate holds for payload k,
         ``counts`` (uint64[n_pat]) as scan(), ``timing``; with hits=True also ``hits`` (bool[n_hdr, n_pkts])."""
         return self._scan_family("kmpgpu_scan_headers", len(self.headers), "hdr_pkt_counts", hits)
+
+    def scan_bytetests(self, hits: bool = False) -> dict:
+        """For which payloads which byte tests hold (kmpgpu_scan_bytetests): the marking pass of scan_packets and the byte-test kernels.
+        ``bt_pkt_counts`` (uint64[n_bt]) payloads for which test q holds, ``any`` (bool[n_pkts]) some test holds for payload k,
+        ``counts`` (uint64[n_pat]) as scan(), ``timing``; with hits=True also ``hits`` (bool[n_bt, n_pkts])."""
+        return self._scan_family("kmpgpu_scan_bytetests", len(self.bytetests), "bt_pkt_counts", hits)
 
     def scan_alerts(self, family: str = "rules", max_records: Optional[int] = None, read: bool = True) -> dict:
         """Which payloads hit which rows of a family, as a list built on the device (kmpgpu_scan_alerts): family "patterns", "rules",
