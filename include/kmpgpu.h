@@ -636,6 +636,77 @@ int  kmpgpu_scan_bytetests(kmpgpu_ctx *ctx, uint64_t *bt_pkt_counts_out /* [n_bt
                            uint64_t *bt_hits_out /* [n_bt * W] or NULL */, uint64_t *counts_out /* [n_pat] or NULL: as kmpgpu_scan */,
                            kmpgpu_timing *t /* or NULL */);
 
+/* Regex rows: expressions of byte classes and repeats (the linear part of a PCRE content), decided per payload, as a seventh kind of row of the
+ * hit matrix, behind the byte tests'.  "User-Agent: followed by at least 40 non-newline bytes", "a run of 8 or more digits", "= with optional
+ * blanks around it", "a line that is only hex digits": what no fixed byte string, relation, chain or byte test says.
+ *
+ * The dialect.  An expression is a byte string of at least one element, with an optional leading ^ and an optional trailing $.
+ *   Elements, each one byte class:
+ *     a literal byte    any byte other than 0x00 and the metacharacters \ . [ ] ( ) { } * + ? | ^ $; the bytes 0x80 .. 0xFF are literals
+ *     an escape         \xHH, \n \r \t \f \v, \0 not followed by a digit, and \ followed by an ASCII punctuation byte, which is that byte
+ *     a class escape    \d \D \w \W \s \S in Python's ASCII meaning on bytes: \s is {9 .. 13, 32}, \w is [A-Za-z0-9_]
+ *     the dot           every byte but 0x0A; with KMPGPU_RX_DOTALL every byte
+ *     a bracket class   [...] and [^...] of single bytes, escapes as above, ranges a-z whose endpoints are single bytes, and class escapes;
+ *                       ] and \ inside a class are written escaped; - is a literal when it is first, last or escaped; an empty class is
+ *                       refused
+ *   Quantifiers, each behind one element: ? * + {n} {n,} {n,m} with n <= m and m >= 1.
+ *   Refused with KMPGPU_EINVAL, the message naming the expression's index and the byte position ("expression Q: position P: ..."), everything
+ *   set before staying in force: ( ) | (reserved for later), a quantifier on nothing or on a quantifier (a**, a+?), {,m}, ^ anywhere but
+ *   first, $ anywhere but last, a raw 0x00, an unknown letter escape, a bad range, an unterminated class or brace, zero elements, more
+ *   than KMPGPU_RX_MAX_POSITIONS positions.
+ *   Positions: C{n,m} is n mandatory positions and m - n optional ones, C{n,} n - 1 mandatory ones and one mandatory repeatable one (for
+ *   n = 0 it is C*), C* one optional repeatable position, C+ one repeatable one, C? one optional one, a bare element one mandatory one.
+ *   KMPGPU_RX_NOCASE: the listed set of a literal or class is closed under ASCII case BEFORE a [^...] negates it: [^a] does not match A.
+ *
+ * The meaning.  With E_k the payload's text end as everywhere else (its first 0x00 under the default rule, L_k under
+ * KMPGPU_OPT_WHOLE_PAYLOAD):
+ *     rx_hit[q][k]     = (no gate || hit[gate_q][k])
+ *                        && there are 0 <= s <= e <= E_k with payload_k[s:e] in L(expr_q),
+ *                           s == 0 where the expression starts with ^, e == E_k where it ends with $
+ *     rx_pkt_counts[q] = sum over k of rx_hit[q][k]
+ *     any[k]           = OR over q of rx_hit[q][k]
+ *     counts[i]        = exactly what kmpgpu_scan returns
+ * $ is the text end alone (Python's \Z, not Python's $, which also matches in front of a final newline).  An expression that matches the
+ * empty string (x*) hits every payload, the empty one included.  Under KMPGPU_OPT_WHOLE_PAYLOAD a 0x00 is a text byte that ., \x00, \D,
+ * [^a] and the like match; under the default rule no byte at or behind E_k is seen.  hit[gate][k] is the bit of kmpgpu_scan_packets: in
+ * the pattern's window, nocase per pattern.  The gate (KMPGPU_RX_GATED, gate[q] a pattern index) is a cost device with a defined meaning --
+ * the expression is looked at only in payloads that hold pattern gate[q], Snort's fast pattern -- and no position: the expression is not
+ * relative to the match.  The yardstick is Python's re on bytes: re.compile(expr with a trailing $ rewritten to \Z, re.I / re.S per
+ * flag).search(payload[:E_k]) is not None, and-ed with the gate's row (tests/regex_model.py).
+ *
+ * kmpgpu_set_regexes compiles, copies and uploads the expressions.  They belong to the pattern set current at the call: no patterns set:
+ * KMPGPU_ESTATE; a later kmpgpu_set_patterns / kmpgpu_set_patterns_flags drops them with everything else; kmpgpu_set_relations, _chains,
+ * _headers and _bytetests keep them and count n_rx in their 2^31 bound.  An expression outside the dialect, an unknown flag bit,
+ * gate[q] >= n_pat with KMPGPU_RX_GATED, gate[q] != 0 without it, a NULL array with n_rx > 0 (flags NULL: all 0, gate NULL: none gated),
+ * n_pat + n_rel + n_chains + n_hdr + n_bt + n_rx >= 2^31: KMPGPU_EINVAL, and everything set before stays in force.  n_rx == 0 clears them.
+ * EVERY successful call drops the rules.  So the order is patterns, relations, chains, headers, byte tests, regexes, rules.  Windows and
+ * KMPGPU_OPT_WHOLE_PAYLOAD stay pass state: the expressions follow what is set when a pass runs.
+ *
+ * Expressions as rule terms: expression q is row n_pat + n_rel + n_chains + n_hdr + n_bt + q of the hit matrix and term index
+ * n_pat + n_rel + n_chains + n_hdr + n_bt + q of kmpgpu_set_rules, with or without KMPGPU_RULE_NOT; kmpgpu_scan_rules,
+ * kmpgpu_scan_alerts(KMPGPU_ALERT_RULES) and kmpgpu_scan_flows run the regex kernel (one launch) behind the byte-test kernels and in front
+ * of the rules kernel.  KMPGPU_FLOW_SCOPE_FLOW folds their rows as it folds every term row; under kmpgpu_scan_flows_seams they stay src's
+ * own: no expression is matched across a flow seam.  There is no KMPGPU_ALERT_* family for them: the rules are the route to the alert list,
+ * the flows, kmpgpu_load_selected and the export.
+ *
+ * kmpgpu_scan_regexes: synchronous, on the context's stream.  The marking pass of kmpgpu_scan_packets, then the regex kernel instead of the
+ * pattern-level reduce.  Every output may be NULL: rx_pkt_counts_out[n_rx], any_out[W], rx_hits_out[n_rx * W] (layout as
+ * kmpgpu_scan_packets), counts_out[n_pat].  Preconditions and errors as kmpgpu_scan_packets; no expressions set: KMPGPU_ESTATE.
+ * With no expressions set every output, launch and device buffer of every other call is what it is without these calls.
+ * Cost: an expression is a position automaton of at most 63 positions stepped with a handful of 64-bit operations per
+ * text byte; its cost is deterministic, its state one 64-bit word, and no memory grows with the payload.  n_rx further rows of the hit
+ * matrix, (n_rx x W2 + n_rx) x 8 bytes, and 2080 bytes of table per expression.  The kernel reads every payload's text once per 8
+ * expressions, up to the byte at which every expression of the eight is decided. */
+#define KMPGPU_RX_NOCASE 1u       /* ASCII case-insensitive */
+#define KMPGPU_RX_DOTALL 2u       /* . matches 0x0A too */
+#define KMPGPU_RX_GATED  4u       /* only in payloads that hold pattern gate[q] */
+#define KMPGPU_RX_MAX_POSITIONS 63
+int  kmpgpu_set_regexes(kmpgpu_ctx *ctx, const uint8_t *const *expr /* [n_rx] */, const uint32_t *expr_len /* [n_rx] */,
+                        const uint32_t *flags /* [n_rx]; NULL = all 0 */, const uint32_t *gate /* [n_rx]; NULL = none gated */, uint32_t n_rx);
+int  kmpgpu_scan_regexes(kmpgpu_ctx *ctx, uint64_t *rx_pkt_counts_out /* [n_rx] or NULL */, uint64_t *any_out /* [W] or NULL */,
+                         uint64_t *rx_hits_out /* [n_rx * W] or NULL */, uint64_t *counts_out /* [n_pat] or NULL: as kmpgpu_scan */,
+                         kmpgpu_timing *t /* or NULL */);
+
 /* The alert list: which payloads hit which rows, as records instead of a bit matrix (the hit rows of kmpgpu_scan_packets and the rows of
  * kmpgpu_scan_rules / _relations / _chains are rows x W x 8 bytes that the caller downloads and walks; the answer is normally a handful of
  * (payload, rule) pairs).  The set bits of one row family are compacted on the device into 16-byte records, in capture order.

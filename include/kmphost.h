@@ -125,6 +125,12 @@ int  kmp_rules_parse_hdr(const char *path, uint32_t n_patterns, uint32_t n_relat
  * kmp_rules_parse_hdr is this with n_bytetests = 0, where "b3" is no term at all and every message is what it was. */
 int  kmp_rules_parse_bt(const char *path, uint32_t n_patterns, uint32_t n_relations, uint32_t n_chains, uint32_t n_headers, uint32_t n_bytetests,
                         kmp_rules *out, char errbuf[KMP_RULES_ERRBUF]);
+/* ... and with expressions as terms (kmpgpu_set_regexes): "x<q>" / "!x<q>", q < n_regexes a decimal expression index (the order of the lines
+ * of kmp_regexes_parse), is encoded as n_patterns + n_relations + n_chains + n_headers + n_bytetests + q.  An expression index >= n_regexes:
+ * KMPHOST_EINVAL, "line N: ".  n_patterns + n_relations + n_chains + n_headers + n_bytetests + n_regexes >= 2^31: KMPHOST_EINVAL before the
+ * file is opened.  kmp_rules_parse_bt is this with n_regexes = 0, where "x3" is no term at all and every message is what it was. */
+int  kmp_rules_parse_rx(const char *path, uint32_t n_patterns, uint32_t n_relations, uint32_t n_chains, uint32_t n_headers, uint32_t n_bytetests,
+                        uint32_t n_regexes, kmp_rules *out, char errbuf[KMP_RULES_ERRBUF]);
 void kmp_rules_free(kmp_rules *r);
 
 /* ---- relations -------------------------------------------------------------------------------
@@ -224,6 +230,33 @@ typedef struct kmp_bytetests {
 } kmp_bytetests;
 int  kmp_bytetests_parse(const char *path, uint32_t n_patterns, kmp_bytetests *out, char errbuf[KMP_BYTETESTS_ERRBUF]);
 void kmp_bytetests_free(kmp_bytetests *b);
+
+/* ---- expressions -----------------------------------------------------------------------------
+ * Not in the reference: the expressions of kmpgpu_set_regexes (include/kmpgpu.h, where the dialect is) from a text file.  One per line,
+ *     /EXPR/[i][s] [with <pattern index>]
+ * EXPR runs from behind the first '/' to the last '/' of the line and is taken byte for byte (a '/' inside it needs no escape); i makes it
+ * case-insensitive (KMP_RX_NOCASE), s lets the dot match a newline (KMP_RX_DOTALL); with <i> gates it on pattern i (a position in the
+ * pattern file, 0-based; KMP_RX_GATED): it is looked at only in payloads that hold that pattern.  Blank lines and lines whose first
+ * non-blank character is '#' are skipped; expression index = order of the lines.  expr, len, flags and gate are what kmpgpu_set_regexes
+ * takes; the dialect itself is checked there, not here.
+ * KMPHOST_EIO: the file cannot be opened; KMPHOST_EINVAL: a line that does not start with '/', no closing '/', an empty expression, an
+ * unknown or repeated flag, anything but with <pattern index> behind the flags, an index >= n_patterns -- errbuf then starts with
+ * "line N: " (N counts every line of the file, from 1). */
+#define KMP_REGEXES_ERRBUF 256
+#define KMP_RX_NOCASE 1u
+#define KMP_RX_DOTALL 2u
+#define KMP_RX_GATED  4u
+typedef struct kmp_regexes {
+    uint32_t        n;       /* number of expressions                                  */
+    const uint8_t **expr;    /* [n]: expression q, len[q] bytes, inside `bytes`         */
+    uint32_t       *len;     /* [n]                                                    */
+    uint32_t       *flags;   /* [n]: KMP_RX_*                                          */
+    uint32_t       *gate;    /* [n]: the gate pattern with KMP_RX_GATED, else 0        */
+    uint8_t        *bytes;   /* the expressions back to back                           */
+    uint32_t       *off;     /* [n + 1]: where each starts in `bytes`                  */
+} kmp_regexes;
+int  kmp_regexes_parse(const char *path, uint32_t n_patterns, kmp_regexes *out, char errbuf[KMP_REGEXES_ERRBUF]);
+void kmp_regexes_free(kmp_regexes *r);
 
 /* ---- offset windows --------------------------------------------------------------------------
  * Not in the reference: the windows of kmpgpu_set_windows (include/kmpgpu.h) from a text file.  One window per line,

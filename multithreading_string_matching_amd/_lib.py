@@ -30,9 +30,13 @@ KMP_HEADERS_ERRBUF = 256
 HDR_ANY_PROTO, HDR_BIDIR = 1, 2   # KMPGPU_HDR_* / KMP_HDR_*: flags of a header predicate
 HDR_TILE = 128             # KMP_HDR_TILE (csrc/kmp_launch.h): predicates the header kernel stages at a time
 KMP_BYTETESTS_ERRBUF = 256
+KMP_REGEXES_ERRBUF = 256
 BT_RELATIVE, BT_LITTLE = 1, 2     # KMPGPU_BT_* / KMP_BT_*: flags of a byte test
 BT_EQ, BT_NE, BT_LT, BT_GT, BT_LE, BT_GE = range(6)    # ... and its operators
 BT_TILE = 128              # KMP_BT_TILE (csrc/kmp_launch.h): tests the absolute byte-test kernel stages at a time
+RX_NOCASE, RX_DOTALL, RX_GATED = 1, 2, 4   # KMPGPU_RX_*: flags of an expression (kmpgpu_set_regexes)
+RX_MAX_POSITIONS = 63      # KMPGPU_RX_MAX_POSITIONS
+RX_TILE = 8                # KMP_RX_TILE (csrc/kmp_regex.h): expressions the regex kernel stages at a time
 CHAIN_MAX = 8              # KMPGPU_CHAIN_MAX / KMP_CHAIN_MAX: contents of one chain
 REL_NO_MIN = -(1 << 31)    # kmpgpu_relation.dmin == INT32_MIN: no lower bound
 REL_NO_MAX = (1 << 31) - 1  # kmpgpu_relation.dmax == INT32_MAX: no upper bound
@@ -128,6 +132,12 @@ class ByteTests(C.Structure):
     _fields_ = [("n", C.c_uint32), ("bt", C.POINTER(ByteTest))]
 
 
+class Regexes(C.Structure):
+    """kmp_regexes (include/kmphost.h)."""
+    _fields_ = [("n", C.c_uint32), ("expr", C.POINTER(C.POINTER(C.c_uint8))), ("len", C.POINTER(C.c_uint32)), ("flags", C.POINTER(C.c_uint32)),
+                ("gate", C.POINTER(C.c_uint32)), ("bytes", C.POINTER(C.c_uint8)), ("off", C.POINTER(C.c_uint32))]
+
+
 class Arena(C.Structure):
     """kmp_arena (include/kmphost.h)."""
     _fields_ = [
@@ -180,6 +190,9 @@ HOST_API = {
     "kmp_rules_parse_bt": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Rules), C.c_char_p]),
     "kmp_bytetests_parse": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(ByteTests), C.c_char_p]),
     "kmp_bytetests_free": (None, [C.POINTER(ByteTests)]),
+    "kmp_rules_parse_rx": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Rules), C.c_char_p]),
+    "kmp_regexes_parse": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(Regexes), C.c_char_p]),
+    "kmp_regexes_free": (None, [C.POINTER(Regexes)]),
     "kmp_chains_parse": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(Chains), C.c_char_p]),
     "kmp_chains_free": (None, [C.POINTER(Chains)]),
     "kmp_relations_parse": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(Relations), C.c_char_p]),
@@ -253,6 +266,8 @@ GPU_API = {
     "kmpgpu_scan_headers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
     "kmpgpu_set_bytetests": (C.c_int, [C.c_void_p, C.POINTER(ByteTest), C.c_uint32]),
     "kmpgpu_scan_bytetests": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
+    "kmpgpu_set_regexes": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), u32p, u32p, u32p, C.c_uint32]),
+    "kmpgpu_scan_regexes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
     "kmpgpu_scan_alerts": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, u64p, u64p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
     "kmpgpu_alerts_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "kmpgpu_load_selected": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, u64p]),

@@ -53,6 +53,14 @@
  * (kmp_rules_parse_bt).  A byte tests file that does not parse, or the variable without the rules and an alerts file: message on stderr,
  * exit 1, before any GPU work.  stdout is what it is without the variable.
  *
+ * KMPGPU_REGEX_FILE=<expressions>, together with KMPGPU_RULES_FILE and KMPGPU_ALERTS_FILE and / or KMPGPU_FLOW_ALERTS_FILE, with or without the
+ * relations, chains, headers and byte tests files: expressions of byte classes and repeats as rule terms (kmpgpu_set_regexes; the file format
+ * is kmp_regexes_parse's, kmphost.h: "/EXPR/[i][s] [with <pattern index>]" per line, the dialect kmpgpu.h's), set on every shard's context
+ * behind the byte tests and before the rules, whose file may then name expression q as "x<q>" / "!x<q>" (kmp_rules_parse_rx).  An
+ * expressions file that does not parse, or the variable without the rules and an alerts file: message on stderr, exit 1, before any GPU
+ * work; an expression outside the dialect is refused by kmpgpu_set_regexes when the shard is set up.  stdout is what it is without the
+ * variable.
+ *
  * KMPGPU_WINDOWS_FILE=<windows>: per-pattern offset windows (kmpgpu_set_windows; the file format is kmp_windows_parse's, kmphost.h:
  * "<pattern index> <first> <last>" per line, '*' for no upper bound) on every shard's context.  They take effect on the files written
  * for KMPGPU_OFFSETS_FILE, KMPGPU_PACKETS_FILE and KMPGPU_RULES_FILE + KMPGPU_ALERTS_FILE: only the matches that start inside their
@@ -130,6 +138,7 @@ typedef struct cli_options {
     kmp_chains chains;                      /* KMPGPU_CHAINS_FILE (n == 0: none) */
     kmp_headers headers;                    /* KMPGPU_HEADERS_FILE (n == 0: none) */
     kmp_bytetests bytetests;                /* KMPGPU_BYTETESTS_FILE (n == 0: none) */
+    kmp_regexes regexes;                    /* KMPGPU_REGEX_FILE (n == 0: none) */
     kmp_rules rules;                        /* KMPGPU_RULES_FILE, set before the first output that needs them */
 } cli_options;
 
@@ -232,16 +241,16 @@ static void load_options(int argc, char *argv[], cli_options *opt)
     opt->flows_path = env_path("KMPGPU_FLOWS_FILE");
     opt->flow_alerts_path = env_path("KMPGPU_FLOW_ALERTS_FILE");
     opt->flows_directed = env_flag("KMPGPU_FLOWS_DIRECTED");
-    const char *relations_path = env_path("KMPGPU_RELATIONS_FILE"), *chains_path = env_path("KMPGPU_CHAINS_FILE"), *headers_path = env_path("KMPGPU_HEADERS_FILE"), *bytetests_path = env_path("KMPGPU_BYTETESTS_FILE"), *windows_path = env_path("KMPGPU_WINDOWS_FILE");
+    const char *relations_path = env_path("KMPGPU_RELATIONS_FILE"), *chains_path = env_path("KMPGPU_CHAINS_FILE"), *headers_path = env_path("KMPGPU_HEADERS_FILE"), *bytetests_path = env_path("KMPGPU_BYTETESTS_FILE"), *regex_path = env_path("KMPGPU_REGEX_FILE"), *windows_path = env_path("KMPGPU_WINDOWS_FILE");
 
     /* the content rules (an export takes the rules' any[] without an alerts file) */
     if ((opt->rules_path != NULL) != (opt->alerts_path != NULL) && !(opt->rules_path && (opt->export_path || opt->flow_alerts_path))) {
         fprintf(stderr, "KMPGPU_RULES_FILE and KMPGPU_ALERTS_FILE go together: %s is not set\n", opt->rules_path ? "KMPGPU_ALERTS_FILE" : "KMPGPU_RULES_FILE");
         exit(1);
     }
-    /* the relations, the chains, the header predicates and the byte tests, which the rules may name */
+    /* the relations, the chains, the header predicates, the byte tests and the expressions, which the rules may name */
     char err[256];
-    _Static_assert(sizeof err >= KMP_RELATIONS_ERRBUF && sizeof err >= KMP_CHAINS_ERRBUF && sizeof err >= KMP_RULES_ERRBUF && sizeof err >= KMP_WINDOWS_ERRBUF && sizeof err >= KMP_HEADERS_ERRBUF && sizeof err >= KMP_BYTETESTS_ERRBUF,
+    _Static_assert(sizeof err >= KMP_RELATIONS_ERRBUF && sizeof err >= KMP_CHAINS_ERRBUF && sizeof err >= KMP_RULES_ERRBUF && sizeof err >= KMP_WINDOWS_ERRBUF && sizeof err >= KMP_HEADERS_ERRBUF && sizeof err >= KMP_BYTETESTS_ERRBUF && sizeof err >= KMP_REGEXES_ERRBUF,
                    "room for every parser's message");
     if (relations_path) {
         needs_rules_and_alerts("KMPGPU_RELATIONS_FILE", opt);
@@ -276,7 +285,19 @@ static void load_options(int argc, char *argv[], cli_options *opt)
             exit(1);
         }
     }
-    if (opt->rules_path && kmp_rules_parse_bt(opt->rules_path, n, opt->relations.n, opt->chains.n, opt->headers.n, opt->bytetests.n, &opt->rules, err)) {
+    if (regex_path) {
+        /* a term of the rules, for the alerts per payload or per flow (or both) */
+        if (!opt->rules_path || (!opt->alerts_path && !opt->flow_alerts_path)) {
+            fprintf(stderr, "KMPGPU_REGEX_FILE goes together with KMPGPU_RULES_FILE and KMPGPU_ALERTS_FILE or KMPGPU_FLOW_ALERTS_FILE: %s is not set\n",
+                    opt->rules_path ? "neither of the two" : "KMPGPU_RULES_FILE");
+            exit(1);
+        }
+        if (kmp_regexes_parse(regex_path, n, &opt->regexes, err)) {
+            fprintf(stderr, "error reading expressions file %s: %s\n", regex_path, err);
+            exit(1);
+        }
+    }
+    if (opt->rules_path && kmp_rules_parse_rx(opt->rules_path, n, opt->relations.n, opt->chains.n, opt->headers.n, opt->bytetests.n, opt->regexes.n, &opt->rules, err)) {
         fprintf(stderr, "error reading rules file %s: %s\n", opt->rules_path, err);
         exit(1);
     }
@@ -339,6 +360,7 @@ static void free_options(cli_options *opt)
     kmp_chains_free(&opt->chains);
     kmp_headers_free(&opt->headers);
     kmp_bytetests_free(&opt->bytetests);
+    kmp_regexes_free(&opt->regexes);
     free(opt->win_first); free(opt->win_last);
 }
 
@@ -406,6 +428,7 @@ static void *shard_load(void *arg)
     if (o->headers.n && kmpgpu_set_headers(j->ctx, (const kmpgpu_header *)o->headers.hdr, o->headers.n)) return shard_fail(j, "kmpgpu_set_headers");
     _Static_assert(sizeof(kmp_bytetest) == sizeof(kmpgpu_bytetest), "kmp_bytetest has the layout of kmpgpu_bytetest");
     if (o->bytetests.n && kmpgpu_set_bytetests(j->ctx, (const kmpgpu_bytetest *)o->bytetests.bt, o->bytetests.n)) return shard_fail(j, "kmpgpu_set_bytetests");
+    if (o->regexes.n && kmpgpu_set_regexes(j->ctx, o->regexes.expr, o->regexes.len, o->regexes.flags, o->regexes.gate, o->regexes.n)) return shard_fail(j, "kmpgpu_set_regexes");
     if (o->want_meta && o->device_extract && kmpgpu_set_option(j->ctx, KMPGPU_OPT_KEEP_META, 1)) return shard_fail(j, "kmpgpu_set_option");
     if (o->device_extract) {
         /* only the bytes this shard's frames span are uploaded (kmpgpu_load_frames) */

@@ -442,15 +442,15 @@ void kmp_patterns_free(kmp_patterns *p)
 
 /* ============================ text files, line by line ================================== */
 
-/* What the rules, relations, chains, windows, headers and byte tests files share: one entry per line, blank lines and lines whose first non-blank character
+/* What the rules, relations, chains, windows, headers, byte tests and expression files share: one entry per line, blank lines and lines whose first non-blank character
  * is '#' skipped.  text_lines opens path and hands every other line to fn -- p at its first non-blank character, end behind its last
  * one (the newline included), lineno counting every line of the file from 1 -- until fn returns something other than KMPHOST_OK,
  * which text_lines then returns.  The message of a file that cannot be opened (KMPHOST_EIO) and the one that goes with
  * KMPHOST_ENOMEM are written here. */
 #define KMP_LINE_ERRBUF 256
 _Static_assert(KMP_RULES_ERRBUF == KMP_LINE_ERRBUF && KMP_RELATIONS_ERRBUF == KMP_LINE_ERRBUF && KMP_CHAINS_ERRBUF == KMP_LINE_ERRBUF &&
-               KMP_WINDOWS_ERRBUF == KMP_LINE_ERRBUF && KMP_HEADERS_ERRBUF == KMP_LINE_ERRBUF && KMP_BYTETESTS_ERRBUF == KMP_LINE_ERRBUF,
-               "the six formats' error buffers have one size");
+               KMP_WINDOWS_ERRBUF == KMP_LINE_ERRBUF && KMP_HEADERS_ERRBUF == KMP_LINE_ERRBUF && KMP_BYTETESTS_ERRBUF == KMP_LINE_ERRBUF &&
+               KMP_REGEXES_ERRBUF == KMP_LINE_ERRBUF, "the seven formats' error buffers have one size");
 typedef int (*line_fn)(void *ctx, const char *p, const char *end, size_t lineno, char *errbuf);
 
 static int out_of_memory(char *errbuf)
@@ -537,7 +537,7 @@ typedef struct rules_ctx {
     uint32_t n_patterns, n_relations, n_chains;
     kmp_rules *out;
     size_t n_off, cap_off, n_terms, cap_terms;
-    uint32_t n_headers, n_bytetests;
+    uint32_t n_headers, n_bytetests, n_regexes;
 } rules_ctx;
 
 static int rules_line(void *ctx, const char *p, const char *end, size_t lineno, char *errbuf)
@@ -556,17 +556,23 @@ static int rules_line(void *ctx, const char *p, const char *end, size_t lineno, 
         const int is_hdr = c->n_headers && p < end && *p == 'h';
         /* b<q>: byte test q, in the same way */
         const int is_bt = c->n_bytetests && p < end && *p == 'b';
-        if (is_rel || is_chain || is_hdr || is_bt) p++;
+        /* x<q>: expression q, in the same way */
+        const int is_rx = c->n_regexes && p < end && *p == 'x';
+        if (is_rel || is_chain || is_hdr || is_bt || is_rx) p++;
         const char *digits = p;
         while (p < end && *p >= '0' && *p <= '9') { if (v < (1ull << 40)) v = v * 10 + (uint64_t)(*p - '0'); p++; }
         const char *stop = p;
         while (stop < end && !is_c_space((uint8_t)*stop)) stop++;   /* the whole token, for the message */
-        if (p == digits && neg && stop == p && !is_rel && !is_chain && !is_hdr && !is_bt) return line_error(errbuf, lineno, "'!' without a pattern index");
+        if (p == digits && neg && stop == p && !is_rel && !is_chain && !is_hdr && !is_bt && !is_rx) return line_error(errbuf, lineno, "'!' without a pattern index");
         if (p == digits || stop != p)
-            return line_error(errbuf, lineno, "'%.*s' is not a pattern index%s%s%s%s", (int)(stop - tok > 64 ? 64 : stop - tok), tok,
+            return line_error(errbuf, lineno, "'%.*s' is not a pattern index%s%s%s%s%s", (int)(stop - tok > 64 ? 64 : stop - tok), tok,
                               c->n_relations ? " or r<relation index>" : "", c->n_chains ? " or c<chain index>" : "",
-                              c->n_headers ? " or h<header index>" : "", c->n_bytetests ? " or b<byte test index>" : "");
-        if (is_bt) {
+                              c->n_headers ? " or h<header index>" : "", c->n_bytetests ? " or b<byte test index>" : "",
+                              c->n_regexes ? " or x<expression index>" : "");
+        if (is_rx) {
+            if (v >= c->n_regexes) return line_error(errbuf, lineno, "expression index %llu, but there are %u expressions", (unsigned long long)v, c->n_regexes);
+            row = c->n_patterns + c->n_relations + c->n_chains + c->n_headers + c->n_bytetests + (uint32_t)v;
+        } else if (is_bt) {
             if (v >= c->n_bytetests) return line_error(errbuf, lineno, "byte test index %llu, but there are %u byte tests", (unsigned long long)v, c->n_bytetests);
             row = c->n_patterns + c->n_relations + c->n_chains + c->n_headers + (uint32_t)v;
         } else if (is_hdr) {
@@ -613,19 +619,26 @@ int kmp_rules_parse_hdr(const char *path, uint32_t n_patterns, uint32_t n_relati
 int kmp_rules_parse_bt(const char *path, uint32_t n_patterns, uint32_t n_relations, uint32_t n_chains, uint32_t n_headers, uint32_t n_bytetests,
                        kmp_rules *out, char errbuf[KMP_RULES_ERRBUF])
 {
+    return kmp_rules_parse_rx(path, n_patterns, n_relations, n_chains, n_headers, n_bytetests, 0, out, errbuf);
+}
+
+int kmp_rules_parse_rx(const char *path, uint32_t n_patterns, uint32_t n_relations, uint32_t n_chains, uint32_t n_headers, uint32_t n_bytetests,
+                       uint32_t n_regexes, kmp_rules *out, char errbuf[KMP_RULES_ERRBUF])
+{
     memset(out, 0, sizeof *out);
     if (errbuf) errbuf[0] = 0;
-    /* a term is a row below 2^31: bit 31 is KMP_RULE_NOT (kmpgpu_set_relations, _chains, _headers and _bytetests refuse such a set too) */
-    if ((uint64_t)n_patterns + n_relations + n_chains + n_headers + n_bytetests >= (1ull << 31)) {
+    /* a term is a row below 2^31: bit 31 is KMP_RULE_NOT (kmpgpu_set_relations, _chains, _headers, _bytetests and _regexes refuse such a set too) */
+    if ((uint64_t)n_patterns + n_relations + n_chains + n_headers + n_bytetests + n_regexes >= (1ull << 31)) {
         if (errbuf) {
-            if (n_bytetests) snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations + %u chains + %u header predicates + %u byte tests do not fit the 2^31 rows a term can name", n_patterns, n_relations, n_chains, n_headers, n_bytetests);
+            if (n_regexes) snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations + %u chains + %u header predicates + %u byte tests + %u expressions do not fit the 2^31 rows a term can name", n_patterns, n_relations, n_chains, n_headers, n_bytetests, n_regexes);
+            else if (n_bytetests) snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations + %u chains + %u header predicates + %u byte tests do not fit the 2^31 rows a term can name", n_patterns, n_relations, n_chains, n_headers, n_bytetests);
             else if (n_headers) snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations + %u chains + %u header predicates do not fit the 2^31 rows a term can name", n_patterns, n_relations, n_chains, n_headers);
             else if (n_chains) snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations + %u chains do not fit the 2^31 rows a term can name", n_patterns, n_relations, n_chains);
             else snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations do not fit the 2^31 rows a term can name", n_patterns, n_relations);
         }
         return KMPHOST_EINVAL;
     }
-    rules_ctx c = {n_patterns, n_relations, n_chains, out, 0, 0, 0, 0, n_headers, n_bytetests};
+    rules_ctx c = {n_patterns, n_relations, n_chains, out, 0, 0, 0, 0, n_headers, n_bytetests, n_regexes};
     int rc = rules_push(&out->off, &c.n_off, &c.cap_off, 0) ? out_of_memory(errbuf) : text_lines(path, rules_line, &c, errbuf);
     if (rc) {
         kmp_rules_free(out);
@@ -1062,6 +1075,111 @@ void kmp_bytetests_free(kmp_bytetests *b)
     if (!b) return;
     free(b->bt);
     memset(b, 0, sizeof *b);
+}
+
+/* ============================ expressions =============================================== */
+
+typedef struct regexes_ctx {
+    uint32_t n_patterns;
+    kmp_regexes *out;
+    size_t n, cap, bytes, cap_bytes;
+} regexes_ctx;
+
+static int regexes_line(void *ctx, const char *p, const char *end, size_t lineno, char *errbuf)
+{
+    regexes_ctx *c = (regexes_ctx *)ctx;
+    static const char *const form = "/EXPR/[i][s] [with <pattern index>]";
+    while (end > p && is_c_space((uint8_t)end[-1])) end--;                /* (the newline, and blanks in front of it) */
+    if (*p != '/') return line_error(errbuf, lineno, "an expression line is %s: it starts with '/'", form);
+    const char *close = end;
+    while (close > p + 1 && close[-1] != '/') close--;                    /* EXPR runs to the last '/' of the line */
+    if (close == p + 1) return line_error(errbuf, lineno, "no closing '/': an expression line is %s", form);
+    const char *expr = p + 1, *expr_end = close - 1;
+    if (expr == expr_end) return line_error(errbuf, lineno, "an empty expression");
+    uint32_t flags = 0, gate = 0;
+    const char *q = close;
+    for (; q < end && !is_c_space((uint8_t)*q); q++) {
+        const uint32_t f = *q == 'i' ? KMP_RX_NOCASE : *q == 's' ? KMP_RX_DOTALL : 0u;
+        if (!f) return line_error(errbuf, lineno, "'%c' is not a flag (i: nocase, s: dotall)", *q);
+        if (flags & f) return line_error(errbuf, lineno, "flag '%c' twice", *q);
+        flags |= f;
+    }
+    const char *tok;
+    int len;
+    if (next_field(&q, end, &tok, &len)) {
+        if (!field_is(tok, len, "with")) return line_error(errbuf, lineno, "'%.*s' is not 'with <pattern index>'", len > 64 ? 64 : len, tok);
+        if (!next_field(&q, end, &tok, &len)) return line_error(errbuf, lineno, "'with' without a pattern index");
+        uint64_t v = 0;
+        int k = 0;
+        for (; k < len && tok[k] >= '0' && tok[k] <= '9'; k++) if (v < (1ull << 40)) v = v * 10 + (uint64_t)(tok[k] - '0');
+        if (k == 0 || k != len) return line_error(errbuf, lineno, "'%.*s' is not a pattern index", len > 64 ? 64 : len, tok);
+        if (v >= c->n_patterns) return line_error(errbuf, lineno, "pattern index %llu, but there are %u patterns", (unsigned long long)v, c->n_patterns);
+        flags |= KMP_RX_GATED; gate = (uint32_t)v;
+        if (next_field(&q, end, &tok, &len)) return line_error(errbuf, lineno, "'%.*s' behind the pattern index", len > 64 ? 64 : len, tok);
+    }
+    if (c->n == c->cap) {
+        const size_t nc = c->cap ? c->cap * 2 : 64;
+        uint32_t *no = (uint32_t *)realloc(c->out->off, (nc + 1) * sizeof *no);
+        if (!no) return KMPHOST_ENOMEM;
+        c->out->off = no;
+        uint32_t *nf = (uint32_t *)realloc(c->out->flags, nc * sizeof *nf);
+        if (!nf) return KMPHOST_ENOMEM;
+        c->out->flags = nf;
+        uint32_t *ng = (uint32_t *)realloc(c->out->gate, nc * sizeof *ng);
+        if (!ng) return KMPHOST_ENOMEM;
+        c->out->gate = ng;
+        c->cap = nc;
+    }
+    const size_t m = (size_t)(expr_end - expr);
+    if (c->bytes + m > 0x7FFFFFFFull) return line_error(errbuf, lineno, "more than 2^31 bytes of expressions");
+    if (c->bytes + m > c->cap_bytes) {
+        size_t nb = c->cap_bytes ? c->cap_bytes * 2 : 4096;
+        while (nb < c->bytes + m) nb *= 2;
+        uint8_t *nv = (uint8_t *)realloc(c->out->bytes, nb);
+        if (!nv) return KMPHOST_ENOMEM;
+        c->out->bytes = nv; c->cap_bytes = nb;
+    }
+    memcpy(c->out->bytes + c->bytes, expr, m);
+    c->out->off[c->n] = (uint32_t)c->bytes;
+    c->bytes += m;
+    c->out->off[c->n + 1] = (uint32_t)c->bytes;
+    c->out->flags[c->n] = flags;
+    c->out->gate[c->n] = gate;
+    c->n++;
+    return KMPHOST_OK;
+}
+
+int kmp_regexes_parse(const char *path, uint32_t n_patterns, kmp_regexes *out, char errbuf[KMP_REGEXES_ERRBUF])
+{
+    memset(out, 0, sizeof *out);
+    if (errbuf) errbuf[0] = 0;
+    regexes_ctx c = {n_patterns, out, 0, 0, 0, 0};
+    int rc = text_lines(path, regexes_line, &c, errbuf);
+    if (!rc && c.n > 0x7FFFFFFFull) rc = KMPHOST_EINVAL;
+    if (!rc && c.n) {
+        /* what kmpgpu_set_regexes takes: a pointer and a length per expression */
+        out->expr = (const uint8_t **)malloc(c.n * sizeof *out->expr);
+        out->len = (uint32_t *)malloc(c.n * sizeof *out->len);
+        if (!out->expr || !out->len) rc = out_of_memory(errbuf);
+        else
+            for (size_t q = 0; q < c.n; q++) {
+                out->expr[q] = out->bytes + out->off[q];
+                out->len[q] = out->off[q + 1] - out->off[q];
+            }
+    }
+    if (rc) {
+        kmp_regexes_free(out);
+        return rc;
+    }
+    out->n = (uint32_t)c.n;
+    return KMPHOST_OK;
+}
+
+void kmp_regexes_free(kmp_regexes *r)
+{
+    if (!r) return;
+    free(r->bytes); free(r->off); free(r->expr); free(r->len); free(r->flags); free(r->gate);
+    memset(r, 0, sizeof *r);
 }
 
 /* serial.c:217-238 */

@@ -1,5 +1,5 @@
 /* kmp_launch.h -- launch entry points of kmp_scan_*.hip / kmp_prep.hip / kmp_fold.hip / kmp_marks.hip / kmp_rules.hip / kmp_relations.hip /
- * kmp_chains.hip / kmp_headers.hip / kmp_bytetests.hip / kmp_select.hip / kmp_alerts.hip / kmp_flows.hip / kmp_seams.hip, used
+ * kmp_chains.hip / kmp_headers.hip / kmp_bytetests.hip / kmp_regex.hip / kmp_select.hip / kmp_alerts.hip / kmp_flows.hip / kmp_seams.hip, used
  * by the C-ABI layer (kmpgpu.hip), which alone decides what is launched; the tables kmp_launch_scan_multi takes come from kmp_tables.h. */
 #ifndef KMP_LAUNCH_H
 #define KMP_LAUNCH_H
@@ -156,6 +156,14 @@ hipError_t kmp_launch_bytetests(bool relative, const unsigned long long *marks, 
                                 const uint8_t *arena, const uint8_t *fold, const uint64_t *pkt_off, const uint32_t *pkt_len,
                                 const void *windows, bool whole, uint32_t max_blocks, unsigned long long *rows,
                                 unsigned long long *bt_counts, unsigned long long *any, hipStream_t st);
+/* kmp_regex.hip: the expressions of kmpgpu_set_regexes.  tables: the tiles of KMP_RX_TILE expressions as kmp_pack_regexes leaves them
+ * (kmp_regex.h, kmp_rowtables.h).  One kernel per call, from arena / pkt_off / pkt_len and, for the gated expressions, the gate patterns'
+ * rows of marks[][stride] alone; text ends at the first 0x00, or at pkt_len with whole.  Every word of rows[q][stride] (stride even, 16-byte
+ * aligned) is written, the bits of index n_pkts and above as 0; an expression's set bits are added to rx_counts[q] and ORed into any[]; the
+ * caller zeroes those two.  No other family's row is written. */
+hipError_t kmp_launch_regexes(const unsigned long long *marks, uint64_t stride, uint64_t n_pkts, const uint4 *tables, uint32_t n_rx,
+                              const uint8_t *arena, const uint64_t *pkt_off, const uint32_t *pkt_len, bool whole,
+                              unsigned long long *rows, unsigned long long *rx_counts, unsigned long long *any, hipStream_t st);
 /* ... and the metadata itself.  _extract: behind kmp_launch_extract_phase2, with its arguments and its workspace: meta[k] of every accepted
  * frame, k as kmp_scatter_index_kernel numbers the payloads.  _select: behind kmp_launch_select_phase2, with the workspace of the selection
  * over src's n payloads: meta[j] = src_meta[k] for the j-th selected payload k.  One kernel each. */

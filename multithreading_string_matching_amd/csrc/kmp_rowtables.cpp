@@ -1,5 +1,5 @@
 /*
- * kmp_rowtables.cpp -- the tables of the rules, windows, relations, chains, header predicates and byte tests as the kernels read them (kmp_rowtables.h).  Host code only.
+ * kmp_rowtables.cpp -- the tables of the rules, windows, relations, chains, header predicates and byte tests as the kernels read them (kmp_rowtables.h; the expressions' packer, kmp_pack_regexes, sits with their compiler in kmp_regex.cpp).  Host code only.
  */
 #include "kmp_rowtables.h"
 
@@ -39,10 +39,16 @@ int kmp_pack_rules(const uint32_t *rule_off, const uint32_t *terms, uint32_t n_r
 int kmp_pack_rules(const uint32_t *rule_off, const uint32_t *terms, uint32_t n_rules, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains,
                    uint32_t n_hdr, uint32_t n_bt, std::vector<uint32_t> *heads, std::vector<uint32_t> *quads, std::string *msg)
 {
+    return kmp_pack_rules(rule_off, terms, n_rules, n_pat, n_rel, n_chains, n_hdr, n_bt, 0u, heads, quads, msg);
+}
+
+int kmp_pack_rules(const uint32_t *rule_off, const uint32_t *terms, uint32_t n_rules, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains,
+                   uint32_t n_hdr, uint32_t n_bt, uint32_t n_rx, std::vector<uint32_t> *heads, std::vector<uint32_t> *quads, std::string *msg)
+{
     heads->clear(); quads->clear();
     if (!rule_off || !terms) return refuse(msg, "kmpgpu_set_rules: NULL rule arrays");
     if (rule_off[0] != 0) return refuse(msg, "kmpgpu_set_rules: rule_off[0] is %u, not 0", rule_off[0]);
-    const uint64_t n_rows = (uint64_t)n_pat + n_rel + n_chains + n_hdr + n_bt;  /* (< 2^31: kmp_pack_relations, kmp_pack_chains, kmp_pack_headers, kmp_pack_bytetests) */
+    const uint64_t n_rows = (uint64_t)n_pat + n_rel + n_chains + n_hdr + n_bt + n_rx;  /* (< 2^31: kmp_pack_relations, _chains, _headers, _bytetests, _regexes) */
     std::vector<uint32_t> ord;
     for (uint32_t r = 0; r < n_rules; r++) {
         if (rule_off[r + 1] < rule_off[r]) return refuse(msg, "kmpgpu_set_rules: rule_off decreases at rule %u", r);
@@ -50,6 +56,9 @@ int kmp_pack_rules(const uint32_t *rule_off, const uint32_t *terms, uint32_t n_r
         ord.clear();
         for (int neg = 0; neg < 2; neg++)
             for (uint32_t j = rule_off[r]; j < rule_off[r + 1]; j++) {
+                if ((terms[j] & ~KMPGPU_RULE_NOT) >= n_rows && n_rx)
+                    return refuse(msg, "kmpgpu_set_rules: rule %u: term %u names row %u of %u patterns + %u relations + %u chains + %u header predicates + %u byte tests + %u expressions",
+                                  r, j - rule_off[r], terms[j] & ~KMPGPU_RULE_NOT, n_pat, n_rel, n_chains, n_hdr, n_bt, n_rx);
                 if ((terms[j] & ~KMPGPU_RULE_NOT) >= n_rows && n_bt)
                     return refuse(msg, "kmpgpu_set_rules: rule %u: term %u names row %u of %u patterns + %u relations + %u chains + %u header predicates + %u byte tests",
                                   r, j - rule_off[r], terms[j] & ~KMPGPU_RULE_NOT, n_pat, n_rel, n_chains, n_hdr, n_bt);
@@ -103,11 +112,18 @@ int kmp_pack_relations(const kmpgpu_relation *rel, uint32_t n_rel, uint32_t n_pa
 int kmp_pack_relations(const kmpgpu_relation *rel, uint32_t n_rel, uint32_t n_pat, uint32_t n_chains, uint32_t n_hdr, uint32_t n_bt,
                        const uint8_t *pat_fold, std::vector<uint32_t> *relations, std::string *msg)
 {
+    return kmp_pack_relations(rel, n_rel, n_pat, n_chains, n_hdr, n_bt, 0u, pat_fold, relations, msg);
+}
+
+int kmp_pack_relations(const kmpgpu_relation *rel, uint32_t n_rel, uint32_t n_pat, uint32_t n_chains, uint32_t n_hdr, uint32_t n_bt,
+                       uint32_t n_rx, const uint8_t *pat_fold, std::vector<uint32_t> *relations, std::string *msg)
+{
     relations->clear();
     if (!rel) return refuse(msg, "kmpgpu_set_relations: rel is NULL");
-    if ((uint64_t)n_pat + n_rel + n_chains + n_hdr + n_bt >= (1ull << 31))
-        return refuse(msg, "kmpgpu_set_relations: %u patterns + %u relations%s%s%s do not fit the 2^31 rows a rule term can name", n_pat, n_rel,
-                      n_chains ? " + the chains" : "", n_hdr ? " + the header predicates" : "", n_bt ? " + the byte tests" : "");
+    if ((uint64_t)n_pat + n_rel + n_chains + n_hdr + n_bt + n_rx >= (1ull << 31))
+        return refuse(msg, "kmpgpu_set_relations: %u patterns + %u relations%s%s%s%s do not fit the 2^31 rows a rule term can name", n_pat, n_rel,
+                      n_chains ? " + the chains" : "", n_hdr ? " + the header predicates" : "", n_bt ? " + the byte tests" : "",
+                      n_rx ? " + the expressions" : "");
     for (uint32_t q = 0; q < n_rel; q++) {
         const kmpgpu_relation &r = rel[q];
         if (r.a >= n_pat || r.b >= n_pat)
@@ -133,11 +149,17 @@ int kmp_pack_chains(const uint32_t *chain_off, const kmpgpu_chain_link *links, u
 int kmp_pack_chains(const uint32_t *chain_off, const kmpgpu_chain_link *links, uint32_t n_chains, uint32_t n_pat, uint32_t n_rel,
                     uint32_t n_hdr, uint32_t n_bt, const uint8_t *pat_fold, std::vector<uint32_t> *chains, std::string *msg)
 {
+    return kmp_pack_chains(chain_off, links, n_chains, n_pat, n_rel, n_hdr, n_bt, 0u, pat_fold, chains, msg);
+}
+
+int kmp_pack_chains(const uint32_t *chain_off, const kmpgpu_chain_link *links, uint32_t n_chains, uint32_t n_pat, uint32_t n_rel,
+                    uint32_t n_hdr, uint32_t n_bt, uint32_t n_rx, const uint8_t *pat_fold, std::vector<uint32_t> *chains, std::string *msg)
+{
     chains->clear();
     if (!chain_off || !links) return refuse(msg, "kmpgpu_set_chains: NULL chain arrays");
-    if ((uint64_t)n_pat + n_rel + n_chains + n_hdr + n_bt >= (1ull << 31))
-        return refuse(msg, "kmpgpu_set_chains: %u patterns + %u relations + %u chains%s%s do not fit the 2^31 rows a rule term can name", n_pat, n_rel,
-                      n_chains, n_hdr ? " + the header predicates" : "", n_bt ? " + the byte tests" : "");
+    if ((uint64_t)n_pat + n_rel + n_chains + n_hdr + n_bt + n_rx >= (1ull << 31))
+        return refuse(msg, "kmpgpu_set_chains: %u patterns + %u relations + %u chains%s%s%s do not fit the 2^31 rows a rule term can name", n_pat, n_rel,
+                      n_chains, n_hdr ? " + the header predicates" : "", n_bt ? " + the byte tests" : "", n_rx ? " + the expressions" : "");
     if (chain_off[0] != 0) return refuse(msg, "kmpgpu_set_chains: chain_off[0] is %u, not 0", chain_off[0]);
     for (uint32_t q = 0; q < n_chains; q++) {
         if (chain_off[q + 1] < chain_off[q]) return refuse(msg, "kmpgpu_set_chains: chain_off decreases at chain %u", q);
@@ -165,11 +187,17 @@ int kmp_pack_headers(const kmpgpu_header *h, uint32_t n_hdr, uint32_t n_pat, uin
 int kmp_pack_headers(const kmpgpu_header *h, uint32_t n_hdr, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains, uint32_t n_bt,
                      std::vector<uint32_t> *headers, std::string *msg)
 {
+    return kmp_pack_headers(h, n_hdr, n_pat, n_rel, n_chains, n_bt, 0u, headers, msg);
+}
+
+int kmp_pack_headers(const kmpgpu_header *h, uint32_t n_hdr, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains, uint32_t n_bt, uint32_t n_rx,
+                     std::vector<uint32_t> *headers, std::string *msg)
+{
     headers->clear();
     if (!h) return refuse(msg, "kmpgpu_set_headers: h is NULL");
-    if ((uint64_t)n_pat + n_rel + n_chains + n_hdr + n_bt >= (1ull << 31))
-        return refuse(msg, "kmpgpu_set_headers: %u patterns + %u relations + %u chains + %u header predicates%s do not fit the 2^31 rows a rule term can name",
-                      n_pat, n_rel, n_chains, n_hdr, n_bt ? " + the byte tests" : "");
+    if ((uint64_t)n_pat + n_rel + n_chains + n_hdr + n_bt + n_rx >= (1ull << 31))
+        return refuse(msg, "kmpgpu_set_headers: %u patterns + %u relations + %u chains + %u header predicates%s%s do not fit the 2^31 rows a rule term can name",
+                      n_pat, n_rel, n_chains, n_hdr, n_bt ? " + the byte tests" : "", n_rx ? " + the expressions" : "");
     for (uint32_t q = 0; q < n_hdr; q++) {
         const kmpgpu_header &p = h[q];
         if (p.sport_lo > p.sport_hi) return refuse(msg, "kmpgpu_set_headers: predicate %u: source port %u lies above %u", q, p.sport_lo, p.sport_hi);
@@ -188,12 +216,19 @@ int kmp_pack_headers(const kmpgpu_header *h, uint32_t n_hdr, uint32_t n_pat, uin
 int kmp_pack_bytetests(const kmpgpu_bytetest *bt, uint32_t n_bt, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains, uint32_t n_hdr,
                        const uint8_t *pat_fold, std::vector<uint32_t> *tests, uint32_t *n_relative, uint32_t *reach, std::string *msg)
 {
+    return kmp_pack_bytetests(bt, n_bt, n_pat, n_rel, n_chains, n_hdr, 0u, pat_fold, tests, n_relative, reach, msg);
+}
+
+int kmp_pack_bytetests(const kmpgpu_bytetest *bt, uint32_t n_bt, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains, uint32_t n_hdr,
+                       uint32_t n_rx, const uint8_t *pat_fold, std::vector<uint32_t> *tests, uint32_t *n_relative, uint32_t *reach,
+                       std::string *msg)
+{
     tests->clear();
     *n_relative = 0u; *reach = 0u;
     if (!bt) return refuse(msg, "kmpgpu_set_bytetests: bt is NULL");
-    if ((uint64_t)n_pat + n_rel + n_chains + n_hdr + n_bt >= (1ull << 31))
-        return refuse(msg, "kmpgpu_set_bytetests: %u patterns + %u relations + %u chains + %u header predicates + %u byte tests do not fit the 2^31 rows a rule term can name",
-                      n_pat, n_rel, n_chains, n_hdr, n_bt);
+    if ((uint64_t)n_pat + n_rel + n_chains + n_hdr + n_bt + n_rx >= (1ull << 31))
+        return refuse(msg, "kmpgpu_set_bytetests: %u patterns + %u relations + %u chains + %u header predicates + %u byte tests%s do not fit the 2^31 rows a rule term can name",
+                      n_pat, n_rel, n_chains, n_hdr, n_bt, n_rx ? " + the expressions" : "");
     std::vector<uint32_t> recs, relative;             /* a refusal leaves *tests empty */
     uint32_t far = 0u;
     for (uint32_t q = 0; q < n_bt; q++) {

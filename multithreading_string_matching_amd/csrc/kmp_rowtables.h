@@ -1,7 +1,7 @@
 /*
- * kmp_rowtables.h -- what kmpgpu_set_rules, kmpgpu_set_windows, kmpgpu_set_relations, kmpgpu_set_chains, kmpgpu_set_headers and kmpgpu_set_bytetests upload, checked and packed on
+ * kmp_rowtables.h -- what kmpgpu_set_rules, kmpgpu_set_windows, kmpgpu_set_relations, kmpgpu_set_chains, kmpgpu_set_headers, kmpgpu_set_bytetests and kmpgpu_set_regexes upload, checked and packed on
  * the host by kmp_rowtables.cpp into the form the kernels read bit for bit (kmp_launch.h: kmp_launch_rules, emit_windows,
- * kmp_launch_relations, kmp_launch_chains, kmp_launch_headers, kmp_launch_bytetests).  Host code without a HIP header, as kmp_tables.h: it builds and runs without a device
+ * kmp_launch_relations, kmp_launch_chains, kmp_launch_headers, kmp_launch_bytetests, kmp_launch_regexes).  Host code without a HIP header, as kmp_tables.h: it builds and runs without a device
  * (tests/rowtables_sanitizer_driver.cpp).
  *
  * Every packer returns KMPGPU_OK with its table -- 16-byte records as four uint32_t, window records as two -- or KMPGPU_EINVAL with the
@@ -66,5 +66,28 @@ int kmp_pack_headers(const kmpgpu_header *h, uint32_t n_hdr, uint32_t n_pat, uin
  * *reach: the largest offset + nbytes of the absolute tests, 0 without one (H of kmp_launch_bytetests). */
 int kmp_pack_bytetests(const kmpgpu_bytetest *bt, uint32_t n_bt, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains, uint32_t n_hdr,
                        const uint8_t *pat_fold, std::vector<uint32_t> *tests, uint32_t *n_relative, uint32_t *reach, std::string *msg);
+
+/* The same once more with the expressions' rows behind the byte tests' (kmpgpu_set_regexes): terms name rows below
+ * n_pat + n_rel + n_chains + n_hdr + n_bt + n_rx, and every 2^31 bound counts n_rx in.  With n_rx = 0 every message is what the entries
+ * above give. */
+int kmp_pack_rules(const uint32_t *rule_off, const uint32_t *terms, uint32_t n_rules, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains,
+                   uint32_t n_hdr, uint32_t n_bt, uint32_t n_rx, std::vector<uint32_t> *heads, std::vector<uint32_t> *quads, std::string *msg);
+int kmp_pack_relations(const kmpgpu_relation *rel, uint32_t n_rel, uint32_t n_pat, uint32_t n_chains, uint32_t n_hdr, uint32_t n_bt,
+                       uint32_t n_rx, const uint8_t *pat_fold, std::vector<uint32_t> *relations, std::string *msg);
+int kmp_pack_chains(const uint32_t *chain_off, const kmpgpu_chain_link *links, uint32_t n_chains, uint32_t n_pat, uint32_t n_rel,
+                    uint32_t n_hdr, uint32_t n_bt, uint32_t n_rx, const uint8_t *pat_fold, std::vector<uint32_t> *chains, std::string *msg);
+int kmp_pack_headers(const kmpgpu_header *h, uint32_t n_hdr, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains, uint32_t n_bt, uint32_t n_rx,
+                     std::vector<uint32_t> *headers, std::string *msg);
+int kmp_pack_bytetests(const kmpgpu_bytetest *bt, uint32_t n_bt, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains, uint32_t n_hdr,
+                       uint32_t n_rx, const uint8_t *pat_fold, std::vector<uint32_t> *tests, uint32_t *n_relative, uint32_t *reach,
+                       std::string *msg);
+
+/* (defined in kmp_regex.cpp, beside the compiler it calls: kmp_rowtables.cpp links without it)  The expressions compiled (kmp_regex.h:
+ * kmp_regex_compile) and laid out in tiles of KMP_RX_TILE as kmp_regex.h describes the device table;
+ * ceil(n_rx / KMP_RX_TILE) * KMP_RX_TILE_WORDS words.  flags NULL: all 0; gate NULL: none gated.  An unknown flag bit, a gate >= n_pat of
+ * a gated expression, a gate != 0 of one that is not, an expression outside the dialect ("expression Q: position P: ..."): KMPGPU_EINVAL. */
+int kmp_pack_regexes(const uint8_t *const *expr, const uint32_t *expr_len, const uint32_t *flags, const uint32_t *gate, uint32_t n_rx,
+                     uint32_t n_pat, uint32_t n_rel, uint32_t n_chains, uint32_t n_hdr, uint32_t n_bt, std::vector<uint32_t> *tables,
+                     std::string *msg);
 
 #endif

@@ -167,7 +167,7 @@ struct kmpgpu_ctx {
     size_t              h_counts_cap = 0;
     unsigned long long *h_small = nullptr;            /* pinned, 16 words: where the loaders read small device results back (a copy to pageable
                                                          memory goes through the runtime's blocking staging path) */
-    unsigned long long *d_marks = nullptr;            /* the marking pass: hit matrix [n_pat + n_rel + n_chains + n_hdr + n_bt][stride], then pkt_counts[n_pat], any[stride], counts[n_pat], rel_pkt_counts[n_rel], chain_pkt_counts[n_chains], hdr_pkt_counts[n_hdr], bt_pkt_counts[n_bt] */
+    unsigned long long *d_marks = nullptr;            /* the marking pass: hit matrix [n_pat + n_rel + n_chains + n_hdr + n_bt + n_rx][stride], then pkt_counts[n_pat], any[stride], counts[n_pat], rel_pkt_counts[n_rel], chain_pkt_counts[n_chains], hdr_pkt_counts[n_hdr], bt_pkt_counts[n_bt], rx_pkt_counts[n_rx] */
     uint64_t            marks_cap = 0;                /* words */
     /* kmpgpu_set_rules / kmpgpu_scan_rules: the rules as the kernel reads them (kmp_launch.h, kmp_launch_rules) and the results */
     uint32_t            n_rules = 0;
@@ -196,6 +196,10 @@ struct kmpgpu_ctx {
      * n_pat + n_rel + n_chains + n_hdr + q of the hit matrix and term n_pat + n_rel + n_chains + n_hdr + q of a rule */
     uint32_t            n_bt = 0, n_bt_rel = 0, bt_reach = 0;
     uint4              *d_bytetests = nullptr;
+    /* kmpgpu_set_regexes: the expressions' tables in tiles of KMP_RX_TILE as the regex kernel reads them (kmp_regex.h, kmp_launch_regexes).
+     * Expression q is row n_pat + n_rel + n_chains + n_hdr + n_bt + q of the hit matrix and that term of a rule */
+    uint32_t            n_rx = 0;
+    uint4              *d_regexes = nullptr;
     /* the per-payload metadata the predicates are decided from (kmpgpu_pkt_meta, 16 bytes each), in payload order.  It belongs to the arena:
      * has_meta falls with it (release_arena), the buffer is kept for the next one */
     uint4              *d_meta = nullptr;
@@ -417,6 +421,13 @@ void drop_bytetests(kmpgpu_ctx *c)
     c->n_bt = c->n_bt_rel = c->bt_reach = 0;
 }
 
+/* ... and the expressions */
+void drop_regexes(kmpgpu_ctx *c)
+{
+    free_buffer(&c->d_regexes);
+    c->n_rx = 0;
+}
+
 /* the flows go with the arena and its metadata; their buffers are kept for the next build */
 void drop_flows(kmpgpu_ctx *c)
 {
@@ -445,6 +456,7 @@ void release_patterns(kmpgpu_ctx *c)
     drop_chains(c);                                /* ... and the chains' */
     drop_headers(c);                               /* ... and the header predicates sit behind all of them */
     drop_bytetests(c);                             /* ... and the byte tests' anchors meant these patterns */
+    drop_regexes(c);                               /* ... and so did the expressions' gates */
     c->pat_fold.clear();
     c->pat_sig.clear();
     c->alerts_valid = false;                       /* the list named their rows */
@@ -1751,7 +1763,7 @@ namespace {
 struct MarkPass {
     bool empty = false;
     uint64_t W = 0, stride = 0, mat = 0;          /* words per row as the caller sees them / on the device (even); words of the matrix */
-    unsigned long long *d_mat = nullptr, *d_cnt = nullptr;       /* [n_pat + n_rel + n_chains + n_hdr + n_bt][stride]; the scan's counts [n_pat] */
+    unsigned long long *d_mat = nullptr, *d_cnt = nullptr;       /* [n_pat + n_rel + n_chains + n_hdr + n_bt + n_rx][stride]; the scan's counts [n_pat] */
     uint32_t launches = 0;
 };
 
@@ -1774,12 +1786,12 @@ int marking_pass(kmpgpu_ctx *c, const char *who, MarkPass *p)
         const int rr = repack_arena(c);
         if (rr) return rr;
     }
-    /* one device buffer, grown like the others: [marks (n_pat + n_rel + n_chains + n_hdr + n_bt) x stride][pkt_counts n_pat][any stride]
-     * [counts n_pat][rel_pkt_counts n_rel][chain_pkt_counts n_chains][hdr_pkt_counts n_hdr][bt_pkt_counts n_bt]; the scan kernels mark rows
-     * 0 .. n_pat - 1, the relation kernel, the chain kernel, the header kernel and the byte-test kernels write the rows behind them
-     * (family_rows) */
-    const uint64_t mat = ((uint64_t)np + c->n_rel + c->n_chains + c->n_hdr + c->n_bt) * stride;
-    const uint64_t words = mat + np + stride + np + c->n_rel + c->n_chains + c->n_hdr + c->n_bt;
+    /* one device buffer, grown like the others: [marks (n_pat + n_rel + n_chains + n_hdr + n_bt + n_rx) x stride][pkt_counts n_pat][any stride]
+     * [counts n_pat][rel_pkt_counts n_rel][chain_pkt_counts n_chains][hdr_pkt_counts n_hdr][bt_pkt_counts n_bt][rx_pkt_counts n_rx]; the scan
+     * kernels mark rows 0 .. n_pat - 1, the relation kernel, the chain kernel, the header kernel, the byte-test kernels and the regex kernel
+     * write the rows behind them (family_rows) */
+    const uint64_t mat = ((uint64_t)np + c->n_rel + c->n_chains + c->n_hdr + c->n_bt + c->n_rx) * stride;
+    const uint64_t words = mat + np + stride + np + c->n_rel + c->n_chains + c->n_hdr + c->n_bt + c->n_rx;
     hipError_t e = grow_buffer(&c->d_marks, &c->marks_cap, words, EIGHTH);
     if (e != hipSuccess) return alloc_fail(e, "%s: the hit matrix (%llu bytes) could not be allocated", who, (unsigned long long)(words * 8u));
     p->stride = stride; p->mat = mat;
@@ -1805,8 +1817,10 @@ hipError_t download_rows(kmpgpu_ctx *c, uint64_t *dst, const unsigned long long 
 constexpr int FAMILY_HEADERS = KMPGPU_ALERT_CHAINS + 1;
 /* ... and the byte tests': a family of kmpgpu_scan_bytetests and of the rules' terms */
 constexpr int FAMILY_BYTETESTS = KMPGPU_ALERT_CHAINS + 2;
+/* ... and the expressions': a family of kmpgpu_scan_regexes and of the rules' terms */
+constexpr int FAMILY_REGEXES = KMPGPU_ALERT_CHAINS + 3;
 
-/* A row family (KMPGPU_ALERT_*, FAMILY_HEADERS, FAMILY_BYTETESTS): patterns, rules, relations, chains, header predicates or byte tests.  Where its results lie on the device once its kernels are
+/* A row family (KMPGPU_ALERT_*, FAMILY_HEADERS, FAMILY_BYTETESTS, FAMILY_REGEXES): patterns, rules, relations, chains, header predicates, byte tests or expressions.  Where its results lie on the device once its kernels are
  * enqueued behind a marking pass (enqueue_family). */
 struct FamilyRows {
     unsigned long long *d_rows = nullptr, *d_pc = nullptr, *d_any = nullptr;     /* [n_rows][stride], payloads per row [n_rows], [stride] */
@@ -1817,10 +1831,10 @@ struct FamilyRows {
 uint64_t family_n_rows(const kmpgpu_ctx *c, int family)
 {
     return family == KMPGPU_ALERT_PATTERNS ? c->n_pat : family == KMPGPU_ALERT_RULES ? c->n_rules : family == KMPGPU_ALERT_RELATIONS ? c->n_rel
-         : family == KMPGPU_ALERT_CHAINS ? c->n_chains : family == FAMILY_HEADERS ? c->n_hdr : c->n_bt;
+         : family == KMPGPU_ALERT_CHAINS ? c->n_chains : family == FAMILY_HEADERS ? c->n_hdr : family == FAMILY_BYTETESTS ? c->n_bt : c->n_rx;
 }
 
-/* The one place that knows where the families live: the patterns, relations, chains, header predicates and byte tests in the marks buffer as marking_pass lays it out
+/* The one place that knows where the families live: the patterns, relations, chains, header predicates, byte tests and expressions in the marks buffer as marking_pass lays it out
  * (they share its any[]; one family's kernel writes it per pass), the rules in the context's rule buffer [rule rows n_rules x stride]
  * [rule_pkt_counts n_rules][any stride]. */
 void family_rows(const kmpgpu_ctx *c, const MarkPass &p, int family, FamilyRows *f)
@@ -1833,7 +1847,8 @@ void family_rows(const kmpgpu_ctx *c, const MarkPass &p, int family, FamilyRows 
     }
     const uint64_t np = c->n_pat, first = family == KMPGPU_ALERT_PATTERNS ? 0 : family == KMPGPU_ALERT_RELATIONS ? np
                                         : family == KMPGPU_ALERT_CHAINS ? np + c->n_rel : family == FAMILY_HEADERS ? np + c->n_rel + c->n_chains
-                                        : np + c->n_rel + c->n_chains + c->n_hdr;
+                                        : family == FAMILY_BYTETESTS ? np + c->n_rel + c->n_chains + c->n_hdr
+                                        : np + c->n_rel + c->n_chains + c->n_hdr + c->n_bt;
     f->d_rows = p.d_mat + first * p.stride;
     f->d_pc = family == KMPGPU_ALERT_PATTERNS ? p.d_mat + p.mat : p.d_cnt + first;      /* (the counts of the rows behind the patterns': behind the scan's counts) */
     f->d_any = p.d_mat + p.mat + np;
@@ -1888,9 +1903,23 @@ int enqueue_bytetests(kmpgpu_ctx *c, const MarkPass &p, uint32_t *launches)
     return KMPGPU_OK;
 }
 
+/* The regex kernel behind a marking pass, in the same way: one launch */
+int enqueue_regexes(kmpgpu_ctx *c, const MarkPass &p)
+{
+    FamilyRows f;
+    family_rows(c, p, FAMILY_REGEXES, &f);
+    hipEvent_t e1;
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_regexes(p.d_mat, p.stride, c->n_pkts, c->d_regexes, c->n_rx, c->d_arena, c->d_off, c->d_len, c->whole_payload != 0,
+                               f.d_rows, f.d_pc, f.d_any, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    return KMPGPU_OK;
+}
+
 /* The one place that runs a family's kernels behind a marking pass, and says where they leave their results.  Patterns: the marks reduce.
- * Relations, chains, header predicates, byte tests: their kernels.  Rules: the relation kernel, the chain kernel, the header kernel and the
- * byte-test kernels where those are set, then the rules kernel, into the context's rule buffer, grown here. */
+ * Relations, chains, header predicates, byte tests, expressions: their kernels.  Rules: the relation kernel, the chain kernel, the header
+ * kernel, the byte-test kernels and the regex kernel where those are set, then the rules kernel, into the context's rule buffer, grown
+ * here. */
 int enqueue_family(kmpgpu_ctx *c, const char *who, int family, const MarkPass &p, bool profile_reduce, FamilyRows *f)
 {
     hipEvent_t e1 = nullptr;
@@ -1930,6 +1959,11 @@ int enqueue_family(kmpgpu_ctx *c, const char *who, int family, const MarkPass &p
             const int rr = enqueue_bytetests(c, p, &f->launches);
             if (rr) return rr;
         }
+        if (c->n_rx) {
+            const int rr = enqueue_regexes(c, p);
+            if (rr) return rr;
+            f->launches++;
+        }
         HIP_TRY(profile_launch(c, &e1));
         HIP_TRY(kmp_launch_rules(p.d_mat, p.stride, c->n_pkts, c->d_rule_heads, c->d_rule_quads, c->n_rules, f->d_rows, f->d_pc, f->d_any, c->stream));
         HIP_TRY(profile_launched(c, e1));
@@ -1939,6 +1973,7 @@ int enqueue_family(kmpgpu_ctx *c, const char *who, int family, const MarkPass &p
     family_rows(c, p, family, f);
     if (family == FAMILY_BYTETESTS) return enqueue_bytetests(c, p, &f->launches);
     f->launches = 1u;
+    if (family == FAMILY_REGEXES) return enqueue_regexes(c, p);
     return family == FAMILY_HEADERS ? enqueue_headers(c, p) : enqueue_pairing(c, p, family);
 }
 
@@ -1973,7 +2008,7 @@ int finish_marking(kmpgpu_ctx *c, uint32_t launches, kmpgpu_timing *t)
     return KMPGPU_OK;
 }
 
-/* The body of kmpgpu_scan_packets, _rules, _relations, _chains, _headers and _bytetests behind their own checks: marking pass, the family's kernels, downloads. */
+/* The body of kmpgpu_scan_packets, _rules, _relations, _chains, _headers, _bytetests and _regexes behind their own checks: marking pass, the family's kernels, downloads. */
 int scan_family(kmpgpu_ctx *c, const char *who, int family, uint64_t *row_counts_out, uint64_t *any_out, uint64_t *hits_out, uint64_t *counts_out,
                 kmpgpu_timing *t)
 {
@@ -2047,7 +2082,7 @@ int kmpgpu_set_rules(kmpgpu_ctx *c, const uint32_t *rule_off, const uint32_t *te
     std::vector<uint32_t> heads, quads;
     std::string msg;
     if (n_rules) {
-        const int rc = kmp_pack_rules(rule_off, terms, n_rules, c->n_pat, c->n_rel, c->n_chains, c->n_hdr, c->n_bt, &heads, &quads, &msg);
+        const int rc = kmp_pack_rules(rule_off, terms, n_rules, c->n_pat, c->n_rel, c->n_chains, c->n_hdr, c->n_bt, c->n_rx, &heads, &quads, &msg);
         if (rc) return fail(rc, "%s", msg.c_str());
         if (quads.empty()) quads.assign(4, 0u);         /* rules of one or two terms only: one quad nobody reads, never a NULL table */
     }
@@ -2084,7 +2119,7 @@ int kmpgpu_set_relations(kmpgpu_ctx *c, const kmpgpu_relation *rel, uint32_t n_r
     std::vector<uint32_t> host;
     std::string msg;
     if (n_rel) {
-        const int rc = kmp_pack_relations(rel, n_rel, c->n_pat, c->n_chains, c->n_hdr, c->n_bt, c->pat_fold.data(), &host, &msg);
+        const int rc = kmp_pack_relations(rel, n_rel, c->n_pat, c->n_chains, c->n_hdr, c->n_bt, c->n_rx, c->pat_fold.data(), &host, &msg);
         if (rc) return fail(rc, "%s", msg.c_str());
     }
     const int rc = swap_tables(c, "kmpgpu_set_relations: the relations", {{host, (void **)&c->d_relations}});
@@ -2109,7 +2144,7 @@ int kmpgpu_set_chains(kmpgpu_ctx *c, const uint32_t *chain_off, const kmpgpu_cha
     std::vector<uint32_t> host;
     std::string msg;
     if (n_chains) {
-        const int rc = kmp_pack_chains(chain_off, links, n_chains, c->n_pat, c->n_rel, c->n_hdr, c->n_bt, c->pat_fold.data(), &host, &msg);
+        const int rc = kmp_pack_chains(chain_off, links, n_chains, c->n_pat, c->n_rel, c->n_hdr, c->n_bt, c->n_rx, c->pat_fold.data(), &host, &msg);
         if (rc) return fail(rc, "%s", msg.c_str());
     }
     const int rc = swap_tables(c, "kmpgpu_set_chains: the chains", {{host, (void **)&c->d_chains}});
@@ -2135,7 +2170,7 @@ int kmpgpu_set_headers(kmpgpu_ctx *c, const kmpgpu_header *h, uint32_t n_hdr)
     std::vector<uint32_t> host;
     std::string msg;
     if (n_hdr) {
-        const int rc = kmp_pack_headers(h, n_hdr, c->n_pat, c->n_rel, c->n_chains, c->n_bt, &host, &msg);
+        const int rc = kmp_pack_headers(h, n_hdr, c->n_pat, c->n_rel, c->n_chains, c->n_bt, c->n_rx, &host, &msg);
         if (rc) return fail(rc, "%s", msg.c_str());
     }
     const int rc = swap_tables(c, "kmpgpu_set_headers: the header predicates", {{host, (void **)&c->d_headers}});
@@ -2162,7 +2197,7 @@ int kmpgpu_set_bytetests(kmpgpu_ctx *c, const kmpgpu_bytetest *bt, uint32_t n_bt
     std::string msg;
     uint32_t n_relative = 0, reach = 0;
     if (n_bt) {
-        const int rc = kmp_pack_bytetests(bt, n_bt, c->n_pat, c->n_rel, c->n_chains, c->n_hdr, c->pat_fold.data(), &host, &n_relative, &reach, &msg);
+        const int rc = kmp_pack_bytetests(bt, n_bt, c->n_pat, c->n_rel, c->n_chains, c->n_hdr, c->n_rx, c->pat_fold.data(), &host, &n_relative, &reach, &msg);
         if (rc) return fail(rc, "%s", msg.c_str());
     }
     const int rc = swap_tables(c, "kmpgpu_set_bytetests: the byte tests", {{host, (void **)&c->d_bytetests}});
@@ -2178,6 +2213,31 @@ int kmpgpu_scan_bytetests(kmpgpu_ctx *c, uint64_t *bt_pkt_counts_out, uint64_t *
     if (!c->d_patterns || c->n_pat == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan_bytetests: no patterns set");
     if (c->n_bt == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan_bytetests: no byte tests set");
     return scan_family(c, "kmpgpu_scan_bytetests", FAMILY_BYTETESTS, bt_pkt_counts_out, any_out, bt_hits_out, counts_out, t);
+}
+
+int kmpgpu_set_regexes(kmpgpu_ctx *c, const uint8_t *const *expr, const uint32_t *expr_len, const uint32_t *flags, const uint32_t *gate, uint32_t n_rx)
+{
+    const int sr = setter_state(c, "kmpgpu_set_regexes");
+    if (sr) return sr;
+    std::vector<uint32_t> host;
+    std::string msg;
+    if (n_rx) {
+        const int rc = kmp_pack_regexes(expr, expr_len, flags, gate, n_rx, c->n_pat, c->n_rel, c->n_chains, c->n_hdr, c->n_bt, &host, &msg);
+        if (rc) return fail(rc, "%s", msg.c_str());
+    }
+    const int rc = swap_tables(c, "kmpgpu_set_regexes: the expressions", {{host, (void **)&c->d_regexes}});
+    if (rc) return rc;
+    drop_rules(c);                                 /* the rows their terms named are no longer the same, whatever was set or cleared */
+    c->n_rx = n_rx;
+    return KMPGPU_OK;
+}
+
+int kmpgpu_scan_regexes(kmpgpu_ctx *c, uint64_t *rx_pkt_counts_out, uint64_t *any_out, uint64_t *rx_hits_out, uint64_t *counts_out, kmpgpu_timing *t)
+{
+    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_scan_regexes: ctx is NULL");
+    if (!c->d_patterns || c->n_pat == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan_regexes: no patterns set");
+    if (c->n_rx == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan_regexes: no expressions set");
+    return scan_family(c, "kmpgpu_scan_regexes", FAMILY_REGEXES, rx_pkt_counts_out, any_out, rx_hits_out, counts_out, t);
 }
 
 int kmpgpu_set_meta(kmpgpu_ctx *c, const void *meta, uint64_t n_pkts, int on_device)
@@ -2446,7 +2506,7 @@ static int scan_flows_body(kmpgpu_ctx *c, const char *who, kmpgpu_ctx *sm, int f
     /* the folded matrix, rows of an even number of words as the reduce and the rules kernel read them: SCOPE_PACKET [family's rows x Sf]
      * [flow_counts rows][any Sf]; SCOPE_FLOW [term rows x Sf][rule rows x Sf][flow_counts rules][any Sf] */
     const uint64_t Wf = (c->n_flows + 63u) / 64u, Sf = (Wf + 1u) & ~1ull;
-    const uint64_t n_terms = (uint64_t)c->n_pat + c->n_rel + c->n_chains + c->n_hdr + c->n_bt;
+    const uint64_t n_terms = (uint64_t)c->n_pat + c->n_rel + c->n_chains + c->n_hdr + c->n_bt + c->n_rx;
     const uint64_t fold_rows = per_flow ? n_terms : n_rows, out_rows = per_flow ? n_terms + n_rows : n_rows;
     const uint64_t words = out_rows * Sf + n_rows + Sf;
     const hipError_t e = grow_buffer(&c->d_flow_fold, &c->flow_fold_cap, words, EIGHTH);

@@ -143,6 +143,31 @@ def parse_bytetests(path: str, n_patterns: int) -> np.ndarray:
         L.kmp_bytetests_free(C.byref(b))
 
 
+def parse_regexes(path: str, n_patterns: int) -> list:
+    """The expressions of an expressions file as GpuMatcher.set_regexes takes them (kmp_regexes_parse): (bytes, dict) per line, the dict
+    with nocase, dotall and gate where the line has them; KmpHostError carries the parser's message."""
+    L = _lib.host_lib()
+    r = _lib.Regexes()
+    err = C.create_string_buffer(_lib.KMP_REGEXES_ERRBUF)
+    rc = L.kmp_regexes_parse(path.encode(), n_patterns, C.byref(r), err)
+    if rc:
+        raise KmpHostError(f"{err.value.decode(errors='replace')} ({rc})")
+    try:
+        out = []
+        for q in range(r.n):
+            opt = {}
+            if r.flags[q] & _lib.RX_NOCASE:
+                opt["nocase"] = True
+            if r.flags[q] & _lib.RX_DOTALL:
+                opt["dotall"] = True
+            if r.flags[q] & _lib.RX_GATED:
+                opt["gate"] = int(r.gate[q])
+            out.append((C.string_at(r.expr[q], r.len[q]), opt))
+        return out
+    finally:
+        L.kmp_regexes_free(C.byref(r))
+
+
 # ---------------------------------------------------------------------------------------------
 # arena  (replaces char **array_of_payloads, serial.c:99,124-136)
 # ---------------------------------------------------------------------------------------------

@@ -84,6 +84,7 @@ class GpuMatcher:
         self.chains: list = []     # (p0, (p1, dmin, dmax), ...) per chain as set_chains took them (None: unbounded side), [] = none
         self.headers = np.zeros(0, dtype=HEADER_DTYPE)     # the predicates as set_headers took them
         self.bytetests = np.zeros(0, dtype=BYTETEST_DTYPE)  # the byte tests as set_bytetests took them
+        self.regexes: list = []    # (expr, flags, gate) per expression as set_regexes took them, [] = none
         self._keep = None          # objects whose device memory the context borrows
         self._comm = None          # the GpuComm this matcher is a rank of: closed before the context
 
@@ -115,6 +116,7 @@ class GpuMatcher:
         self.chains = []           # ... and its chains
         self.headers = np.zeros(0, dtype=HEADER_DTYPE)     # ... and its header predicates
         self.bytetests = np.zeros(0, dtype=BYTETEST_DTYPE)  # ... and its byte tests
+        self.regexes = []          # ... and its expressions
 
     def set_rules(self, rules) -> None:
         """Content rules over the current patterns (kmpgpu_set_rules): a sequence of (all_of, none_of) pattern-index sequences;
@@ -123,7 +125,7 @@ class GpuMatcher:
         for a, b in rules:
             for i in a + b:
                 if not 0 <= i < _lib.RULE_NOT:
-                    raise ValueError(f"rule term {i}: not a pattern index (or rel(q), chain(c), hdr(q), btest(q))")
+                    raise ValueError(f"rule term {i}: not a pattern index (or rel(q), chain(c), hdr(q), btest(q), regex(q))")
         off = np.zeros(len(rules) + 1, dtype=np.uint32)
         off[1:] = np.cumsum([len(a) + len(b) for a, b in rules])
         terms = np.array([t for a, b in rules for t in a + [i | _lib.RULE_NOT for i in b]] or [0], dtype=np.uint32)
@@ -245,6 +247,40 @@ class GpuMatcher:
         if not 0 <= q < len(self.bytetests):
             raise ValueError(f"btest({q}): {len(self.bytetests)} byte tests are set")
         return len(self.patterns) + len(self.relations) + len(self.chains) + len(self.headers) + q
+
+    def set_regexes(self, exprs) -> None:
+        """Expressions of byte classes and repeats (kmpgpu_set_regexes; the dialect is in include/kmpgpu.h): a sequence whose entries are
+        ``bytes``, or ``(bytes, dict)`` with any of nocase (ASCII case-insensitive), dotall (. matches 0x0A too) and gate (a pattern index:
+        the expression is looked at only in payloads that hold that pattern).  Expression q hits a payload where some part of its text,
+        up to the text end, is in the expression's language (^: from the first byte, $: up to the text end).  None or an empty sequence
+        clears them.  Every successful call drops the rules, as the library does: relations, chains, headers, byte tests, regexes, then
+        the rules, whose terms may be regex(q)."""
+        took = []
+        for e in exprs or []:
+            expr, opt = (e, {}) if isinstance(e, (bytes, bytearray)) else e
+            unknown = set(opt) - {"nocase", "dotall", "gate"}
+            if unknown:
+                raise ValueError(f"set_regexes: unknown option(s) {sorted(unknown)}")
+            gate = opt.get("gate")
+            flags = (_lib.RX_NOCASE if opt.get("nocase") else 0) | (_lib.RX_DOTALL if opt.get("dotall") else 0) | (0 if gate is None else _lib.RX_GATED)
+            took.append((bytes(expr), flags, 0 if gate is None else int(gate)))
+        n = len(took)
+        bufs = [C.create_string_buffer(e, len(e)) for e, _, _ in took]      # (an expression may hold any byte, escaped or not)
+        ptrs = (C.c_char_p * max(n, 1))(*[C.cast(b, C.c_char_p) for b in bufs])
+        lens = np.array([len(e) for e, _, _ in took] or [0], dtype=np.uint32)
+        flags = np.array([f for _, f, _ in took] or [0], dtype=np.uint32)
+        gates = np.array([g for _, _, g in took] or [0], dtype=np.uint32)
+        gpu_check(self._g.kmpgpu_set_regexes(self._ctx, ptrs if n else None, lens.ctypes.data_as(u32p) if n else None,
+                                             flags.ctypes.data_as(u32p), gates.ctypes.data_as(u32p), n), "kmpgpu_set_regexes")
+        self.regexes = took
+        self.rules = []            # the library drops its rules with the rows they referred to
+
+    def regex(self, q: int) -> int:
+        """The term of expression q in set_rules: it is row len(patterns) + len(relations) + len(chains) + len(headers) + len(bytetests) + q
+        of the hit matrix."""
+        if not 0 <= q < len(self.regexes):
+            raise ValueError(f"regex({q}): {len(self.regexes)} expressions are set")
+        return len(self.patterns) + len(self.relations) + len(self.chains) + len(self.headers) + len(self.bytetests) + q
 
     def set_meta(self, meta) -> None:
         """The per-payload header metadata of the arena at hand (kmpgpu_set_meta): a META_DTYPE array with one record per payload
@@ -452,7 +488,7 @@ class GpuMatcher:
         return arr, int(found.value), counts[:n]
 
     def _scan_family(self, fn, rows: int, counts_key: str, hits: bool) -> dict:
-        """What scan_packets, scan_rules, scan_relations, scan_chains, scan_headers and scan_bytetests share: the C call ``fn`` over a family of ``rows`` rows, its
+        """What scan_packets, scan_rules, scan_relations, scan_chains, scan_headers, scan_bytetests and scan_regexes share: the C call ``fn`` over a family of ``rows`` rows, its
         per-row payload counts returned under ``counts_key``."""
         n = len(self.patterns)
         n_pkts, _ = self.arena_info()
@@ -506,6 +542,12 @@ class GpuMatcher:
         ``bt_pkt_counts`` (uint64[n_bt]) payloads for which test q holds, ``any`` (bool[n_pkts]) some test holds for payload k,
         ``counts`` (uint64[n_pat]) as scan(), ``timing``; with hits=True also ``hits`` (bool[n_bt, n_pkts])."""
         return self._scan_family("kmpgpu_scan_bytetests", len(self.bytetests), "bt_pkt_counts", hits)
+
+    def scan_regexes(self, hits: bool = False) -> dict:
+        """Which payloads which expressions hit (kmpgpu_scan_regexes): the marking pass of scan_packets and the regex kernel.
+        ``rx_pkt_counts`` (uint64[n_rx]) payloads that expression q hits, ``any`` (bool[n_pkts]) some expression hits payload k,
+        ``counts`` (uint64[n_pat]) as scan(), ``timing``; with hits=True also ``hits`` (bool[n_rx, n_pkts])."""
+        return self._scan_family("kmpgpu_scan_regexes", len(self.regexes), "rx_pkt_counts", hits)
 
     def scan_alerts(self, family: str = "rules", max_records: Optional[int] = None, read: bool = True) -> dict:
         """Which payloads hit which rows of a family, as a list built on the device (kmpgpu_scan_alerts): family "patterns", "rules",
