@@ -20,7 +20,7 @@ import seam_model as SM
 from multithreading_string_matching_amd import _lib
 from multithreading_string_matching_amd._lib import KmpGpuError
 from multithreading_string_matching_amd.host import HostArena
-from multithreading_string_matching_amd.matcher import OPT_KERNEL, OPT_REPACK, OPT_WHOLE_PAYLOAD, SEAM_DTYPE, GpuMatcher
+from multithreading_string_matching_amd.matcher import OPT_KERNEL, OPT_NONTEMPORAL, OPT_REPACK, OPT_WHOLE_PAYLOAD, SEAM_DTYPE, GpuMatcher
 
 pytestmark = pytest.mark.gpu
 
@@ -96,10 +96,21 @@ def _put(src, pay, meta, form):
 @pytest.mark.parametrize("directed", [False, True])
 @pytest.mark.parametrize("reach", [1, 15, 16, 98])
 def test_arena_against_the_model(gm, sm, reach, directed, form):
+    _arena_against_the_model(gm, sm, reach, directed, form)
+
+
+def test_default_cache_policy(gm, sm):
+    """OPT_NONTEMPORAL = 0 on the context that receives the seams: the other instantiation of the gather kernel"""
+    _arena_against_the_model(gm, sm, 98, False, "loaded", seam_options=((OPT_NONTEMPORAL, 0),))
+
+
+def _arena_against_the_model(gm, sm, reach, directed, form, seam_options=()):
     pay, meta = _capture(reach, seed=reach + 7 * directed)
     lens = [len(t) for t in pay]
     reset(gm, sm)
     try:
+        for key, value in seam_options:
+            sm.set_option(key, value)
         gm.set_patterns([b"x"])
         keep = _put(gm, pay, meta, form)
         gm.build_flows(directed)
