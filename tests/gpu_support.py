@@ -1,5 +1,5 @@
 """What the GPU test modules share: the context fixture, the options' defaults, the kernel selections, borrowed arenas with dirty
-padding, the frame library of tests/prep_model.py and its loader, the command lines, and the exact comparisons of a pass's outputs
+padding and arenas placed around offset 2^32 of one large buffer, the frame library of tests/prep_model.py and its loader, the command lines, and the exact comparisons of a pass's outputs
 with the answers of tests/match_model.py and tests/flow_model.py.
 
 Import from this module before the package, for the reason given below.
@@ -74,6 +74,107 @@ def load(gm, payloads, slots=None):
         gm.load_arena(HostArena.from_payloads(payloads))
         return None
     return attach_slots(gm, payloads, slots)
+
+
+# ------------------------------------------------------------------------------------------------
+# placed arenas: a small borrowed arena at a chosen place of one buffer of a little over 4 GiB, so that its payloads lie in front of,
+# across and behind offset 2^32 (tests/test_gpu_high_offsets.py says what that is for)
+# ------------------------------------------------------------------------------------------------
+B32 = 1 << 32
+PLACED_LOW = 4 << 20                                   # base 0: the arena lies inside [0, PLACED_LOW)
+PLACED_FROM, PLACED_TO = B32 - (4 << 20), B32 + (8 << 20)      # every other base: inside [PLACED_FROM, PLACED_TO), the buffer's end
+PLACEMENTS = ("low", "split", "edge", "behind")
+SPLIT_FRONT = 48                                       # bytes of the straddling payload in front of 2^32 under `split`
+
+
+def make_big_buffer():
+    return torch.zeros(PLACED_TO, dtype=torch.uint8, device="cuda")
+
+
+@pytest.fixture(scope="module")
+def big_buffer():
+    """one zeroed device buffer from offset 0 to 2^32 + 8 MiB per module that asks for it; the library's fold buffer of a nocase set adds
+    up to 4 GiB beside it"""
+    buf = make_big_buffer()
+    yield buf
+    del buf
+    torch.cuda.empty_cache()
+
+
+def zero_slots(payloads):
+    """every payload followed by 0x00 up to the end of its 16-byte slot, 16 bytes for an empty payload"""
+    return [t + b"\0" * ((-len(t)) % 16 or (0 if t else 16)) for t in payloads]
+
+
+def slot_offsets(slots):
+    """(offset of every slot from the arena's first byte as int64, end of the last slot)"""
+    size = np.array([len(s) for s in slots], dtype=np.int64)
+    assert (size % 16 == 0).all() and (size >= 16).all()
+    end = np.cumsum(size)
+    return end - size, int(end[-1])
+
+
+def placed_base(placement, payloads, slots=None, k=None):
+    """The arena's first byte for a placement, from the payload list.  low: 0.  split: payload k has SPLIT_FRONT bytes in front of 2^32 and
+    the rest behind; k is no multiple of 64 and more than 64 payloads follow it, so the wavefront of a per-payload kernel that holds it
+    has lanes on both sides.  edge: payload k starts at 2^32, the slot in front of it ends there.  behind: 2^32 + 4096 + 48 -- every
+    offset is above 2^32 and the first payload is on no 128-byte line."""
+    off, end = slot_offsets(zero_slots(payloads) if slots is None else slots)
+    if placement == "low":
+        base = 0
+    elif placement == "split":
+        assert k % 64 and len(payloads) - 1 - k > 64 and len(payloads[k]) > SPLIT_FRONT + 64
+        base = B32 - int(off[k]) - SPLIT_FRONT
+    elif placement == "edge":
+        assert 0 < k < len(payloads) and payloads[k] and payloads[k - 1]
+        base = B32 - int(off[k])
+    else:
+        assert placement == "behind"
+        base = B32 + 4096 + 48
+        assert base % 128
+    assert base % 16 == 0
+    assert base + end <= PLACED_LOW if placement == "low" else PLACED_FROM <= base and base + end + 64 <= PLACED_TO
+    if placement in ("split", "edge"):
+        assert base < B32 < base + end
+    return base
+
+
+def attach_placed(gm, payloads, slots, base, buf, off=None):
+    """attach_slots at absolute offsets inside buf (the big_buffer fixture): the slots are written to buf[base : base + end), everything
+    else of the two windows a placement may use is zeroed first -- a case never sees the one before it --, and the arena is attached with
+    the offsets off + base and arena_bytes = base + end, the end of the last slot.  off: the slots' offsets from base where they are not
+    back to back (every slot inside one of the two windows).  Returns the tensors to keep alive."""
+    slots = zero_slots(payloads) if slots is None else slots
+    assert base % 16 == 0 and all(s.startswith(t) for t, s in zip(payloads, slots))
+    if off is None:
+        off, end = slot_offsets(slots)
+        spans = [(base, b"".join(slots))]
+    else:
+        off = np.asarray(off, dtype=np.int64)
+        assert (off % 16 == 0).all()
+        end = max(int(o) + len(s) for o, s in zip(off, slots))
+        spans = [(base + int(o), s) for o, s in zip(off, slots)]
+    for lo, data in spans:
+        assert (0 <= lo and lo + len(data) <= PLACED_LOW) or (PLACED_FROM <= lo and lo + len(data) + 64 <= PLACED_TO), (lo, len(data))
+    assert buf.numel() == PLACED_TO
+    buf[:PLACED_LOW].zero_()
+    buf[PLACED_FROM:].zero_()
+    if len(spans) == 1:
+        lo, data = spans[0]
+        buf[lo:lo + len(data)] = torch.from_numpy(np.frombuffer(data, dtype=np.uint8).copy()).cuda()
+    else:                                              # scattered slots: one image per window, copied whole
+        for w0, w1 in ((0, PLACED_LOW), (PLACED_FROM, PLACED_TO)):
+            mine = [(lo, d) for lo, d in spans if w0 <= lo < w1]
+            if mine:
+                img = np.zeros(max(lo + len(d) for lo, d in mine) - w0, dtype=np.uint8)
+                for lo, d in mine:
+                    img[lo - w0:lo - w0 + len(d)] = np.frombuffer(d, dtype=np.uint8)
+                buf[w0:w0 + len(img)] = torch.from_numpy(img).cuda()
+    ln = np.array([len(t) for t in payloads], dtype=np.int32)
+    keep = (buf, torch.from_numpy(off + base).cuda(), torch.from_numpy(ln).cuda())
+    torch.cuda.synchronize()
+    gm.attach_arena(*keep, arena_bytes=base + end)
+    return keep
 
 
 # ------------------------------------------------------------------------------------------------

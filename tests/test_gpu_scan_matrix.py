@@ -33,9 +33,20 @@ of a payload, across 16-byte lane boundaries, at a payload's last byte, and cut 
 padding behind it holds the rest, so a kernel that reads past L_k counts too many.  Every third payload has 0x00 bytes: the first one
 directly before, inside or directly behind a planted occurrence, further ones behind it.
 
+Placed rows: test_row_placed runs every row again with its arena attached inside one borrowed buffer of a little over 4 GiB
+(gpu_support.attach_placed) at the placements `split`, `edge` and `behind` of gpu_support.placed_base -- 2^32 inside payload SPLIT_K, 48
+bytes of it in front; a slot that ends at 2^32 with EDGE_K starting there; every offset above 2^32 -- with the same expectations and
+under both grids.  The *_dirty kinds keep their text-filled padding, the others get zero padding, which the padding check over the high
+arena has to find clean for the row's kernel to run: test_trace_names_every_row_behind holds the traced kernels to the rows' names once
+more.  Inputs._plant_for_placements puts occurrences around byte 48 of SPLIT_K, at the head of EDGE_K and at the end of EDGE_K - 1;
+Inputs.placement_facts asserts on the CPU that every pattern set has a match across 2^32 under `split` and matches on either side of it
+under `edge`.  tests/test_gpu_high_offsets.py has the reasons, the kernels behind the marking pass and the record of what these cases
+catch.
+
 Run on a real MI355X:  python -m pytest tests/test_gpu_scan_matrix.py -m gpu
 Measured there: the 98 rows and the trace test, 99 passed in 16 s (the trace test 8.3 s, the slowest row 1.2 s: a classed set's 140 000
-offset records, sorted and compared on the host).
+offset records, sorted and compared on the host).  With the 294 placed rows and the second trace: 394 passed in 32 s (each trace 8.1 s,
+the slowest row 1.1 s, the slowest placed row 0.54 s).
 
 Checked to bite: three memory-safe changes made to a scratch build (never committed), one per file, each inside `if constexpr` so that
 one instantiation alone is changed.  With all three in one library these rows failed, every other row passed, and the rest of the GPU
@@ -63,7 +74,8 @@ from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
-from gpu_support import check_offsets, check_packets, gm, load, reset  # noqa: E402,F401  (torch first)
+from gpu_support import (PLACEMENTS, SPLIT_FRONT, attach_placed, big_buffer, check_offsets, check_packets, gm, load, make_big_buffer,  # noqa: E402,F401
+                         placed_base, reset)  # (torch first; big_buffer, gm: fixtures; make_big_buffer: for tests/scan_matrix_child.py)
 
 import match_model as MM  # noqa: E402
 import scan_matrix as SM  # noqa: E402
@@ -74,6 +86,11 @@ UNIFORM_N, UNIFORM_LEN = 320, 2309
 MIXED_N = 1060
 LONG_LENGTHS = (4, 5, 8, 9, 16, 17, 40, 99)
 GRIDS = (0, 1)                                          # KMPGPU_OPT_BLOCKS_PER_CU: the default grid, and one block per CU
+# The payloads the placements of gpu_support.placed_base are hung on, in both payload sets: SPLIT_K straddles 2^32 under `split`
+# (no multiple of 64, more than 64 payloads behind it), EDGE_K starts at 2^32 under `edge`.  Neither they nor EDGE_K - 1 hold a 0x00
+# (k % 3 != 0), so both text-end rules see their plants.
+SPLIT_K, EDGE_K = 101, 110
+STRADDLER = 4                                           # of LONG_LENGTHS: in the sets "long" and "riders"; it holds "ab", of "short" and "classed"
 
 
 def _text(nrng, n):
@@ -141,6 +158,7 @@ class Inputs:
         self.payloads, self.slots = {}, {}
         for name, lens in (("uniform", [UNIFORM_LEN] * UNIFORM_N), ("mixed", [_mixed_length(rng, k) for k in range(MIXED_N)])):
             built = [_payload(rng, nrng, k, L, self.long) for k, L in enumerate(lens)]
+            self._plant_for_placements(built)
             self.payloads[name] = [t for t, _ in built]
             slots = []
             for t, cont in built:
@@ -163,6 +181,45 @@ class Inputs:
                      "riders": [b"-", L[1], b"E", L[3], L[4], b"\x80", b"cab", b"Ad"],
                      "classed": [b"ab", b"Bd"] + cut + [L[2], L[5], L[6]]}
         self._counts, self._starts, self._facts = {}, {}, set()
+
+    def _plant_for_placements(self, built):
+        """SPLIT_K: long[5] up to byte 44 and long[STRADDLER] from byte 45 on, whose bytes 2 and 3 -- "ab" -- are the payload's bytes 47 and
+        48: under `split` that occurrence and that "ab" hold the last byte in front of 2^32 and the first one behind it.  (Two occurrences
+        cannot both hold byte 47: the second one ends directly in front of the first.)  EDGE_K starts with long[STRADDLER] and EDGE_K - 1 ends
+        with it: under `edge` a match from byte 2^32 on and one up to byte 2^32 - 1, the last byte of a payload that fills its slot or not."""
+        Y, X = self.long[STRADDLER], self.long[5]
+        assert Y[2:4] == b"ab" and Y.endswith(b"-")
+
+        def put(k, at, p):
+            t, cont = built[k]
+            at = at if at >= 0 else len(t) + at
+            assert 0 <= at and at + len(p) <= len(t) and 0 not in t
+            built[k] = (t[:at] + p + t[at + len(p):], cont)
+        put(SPLIT_K, SPLIT_FRONT - 3 - len(X), X)
+        put(SPLIT_K, SPLIT_FRONT - 3, Y)
+        put(EDGE_K, 0, Y)
+        put(EDGE_K - 1, -len(Y), Y)
+        if (EDGE_K - 1) % 4 == 2:                       # (its padding would go on with the occurrence cut by its end)
+            built[EDGE_K - 1] = (built[EDGE_K - 1][0], b"")
+
+    def placement_facts(self, row, placement):
+        """Under `split` the row's pattern set has a match that contains byte 2^32 and the byte in front of it; under `edge` one that
+        starts in the first lane behind 2^32 and one that ends in the last lane in front of it -- for the long patterns a match from a
+        payload's byte 0 at 2^32 on, and one that ends with the payload in front of it."""
+        whole = bool(row["options"].get("WHOLE_PAYLOAD", 0))
+        pats, _ = self.patterns(row)
+        st = self.starts(row, whole)
+        payloads = self.payloads[self.base(row["arena"])]
+
+        def spans(k):
+            return [(s, s + len(pats[i])) for i, ss in enumerate(st[k]) for s in ss]
+        if placement == "split":
+            assert any(s < SPLIT_FRONT < e for s, e in spans(SPLIT_K)), row["name"]
+        elif placement == "edge":
+            L = len(payloads[EDGE_K - 1])
+            assert any(s < 16 for s, _ in spans(EDGE_K)) and any(e > L - 16 for _, e in spans(EDGE_K - 1)), row["name"]
+            if row["patterns"] in ("long", "riders"):
+                assert any(s == 0 for s, _ in spans(EDGE_K)) and any(e == L for _, e in spans(EDGE_K - 1)), row["name"]
 
     @staticmethod
     def base(arena):
@@ -228,9 +285,14 @@ def inputs(oracle):
     return Inputs(oracle)
 
 
-def run_case(gm, row, inputs):
+def run_case(gm, row, inputs, placement="low", buf=None):
+    """placement "low": the arena as the row names it, the library's own copy or a borrowed one.  Every other placement of
+    gpu_support.PLACEMENTS: a borrowed arena inside buf (gpu_support.big_buffer) at absolute offsets around 2^32 -- the *_dirty kinds with
+    their text-filled padding, the others with zero padding, which kmp_check_padding_kernel over the high arena has to find clean for the
+    row's kernel to be the one that runs."""
     whole = bool(row["options"].get("WHOLE_PAYLOAD", 0))
     inputs.assert_facts(row)
+    inputs.placement_facts(row, placement)
     pats, nocase = inputs.patterns(row)
     counts = inputs.counts(row, whole)
     base = inputs.base(row["arena"])
@@ -238,7 +300,12 @@ def run_case(gm, row, inputs):
     try:
         for key, value in row["options"].items():
             gm.set_option(SM.OPTIONS[key], value)
-        keep = load(gm, inputs.payloads[base], inputs.slots[base] if inputs.borrowed(row["arena"]) else None)
+        slots = inputs.slots[base] if inputs.borrowed(row["arena"]) else None
+        if placement == "low":
+            keep = load(gm, inputs.payloads[base], slots)
+        else:
+            at = placed_base(placement, inputs.payloads[base], slots, {"split": SPLIT_K, "edge": EDGE_K}.get(placement))
+            keep = attach_placed(gm, inputs.payloads[base], slots, at, buf)
         gm.set_patterns(pats, nocase=nocase if nocase else False)
         for bpc in GRIDS:
             gm.set_option(OPT_BLOCKS_PER_CU, bpc)
@@ -273,11 +340,22 @@ def test_trace_names_every_row(tmp_path):
     """The same cases in a fresh process (tests/scan_matrix_child.py) under a kernel trace: the scan kernels that ran are the rows' names,
     every one of them, and none the table calls unreachable.  With tests/test_scan_matrix_host.py: every instantiation the launchers
     can pick ran inside a case that compares its results."""
+    _trace_names_every_row(tmp_path, "low")
+
+
+def test_trace_names_every_row_behind(tmp_path):
+    """The same with every arena placed behind 2^32 (the child makes a buffer of its own; this module's is not made yet): a placed row
+    runs the instantiation it names, not another one that happens to count the same -- the padding check over the high arena decides as
+    it does for the library's own copy."""
+    _trace_names_every_row(tmp_path, "behind")
+
+
+def _trace_names_every_row(tmp_path, placement):
     prof = shutil.which("rocprofv3") or ("/opt/rocm/bin/rocprofv3" if os.path.exists("/opt/rocm/bin/rocprofv3") else None)
     if prof is None:
         pytest.skip("rocprofv3 not installed")
     out = str(tmp_path / "trace")
-    r = subprocess.run([prof, "--kernel-trace", "--output-format", "csv", "-d", out, "--", sys.executable, os.path.join(ROOT, "tests", "scan_matrix_child.py")],
+    r = subprocess.run([prof, "--kernel-trace", "--output-format", "csv", "-d", out, "--", sys.executable, os.path.join(ROOT, "tests", "scan_matrix_child.py"), placement],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     files = glob.glob(os.path.join(out, "**", "*kernel_trace.csv"), recursive=True)
@@ -292,3 +370,11 @@ def test_trace_names_every_row(tmp_path):
     rows = {row["name"] for row in SM.ROWS}
     assert not traced & set(SM.UNREACHABLE), sorted(traced & set(SM.UNREACHABLE))
     assert traced == rows, ("rows whose kernel never ran: %s" % sorted(rows - traced), "kernels no row names: %s" % sorted(traced - rows))
+
+
+# behind the trace tests: the buffer of this module is made when the first placed row asks for it, after the child processes have had
+# theirs
+@pytest.mark.parametrize("placement", PLACEMENTS[1:])
+@pytest.mark.parametrize("row", SM.ROWS, ids=[r["name"] for r in SM.ROWS])
+def test_row_placed(gm, inputs, big_buffer, row, placement):
+    run_case(gm, row, inputs, placement, big_buffer)
