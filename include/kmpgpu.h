@@ -799,6 +799,66 @@ int  kmpgpu_alerts_read(kmpgpu_ctx *ctx, kmpgpu_alert *out, uint64_t first, uint
 int  kmpgpu_load_selected(kmpgpu_ctx *dst, kmpgpu_ctx *src, const void *select /* uint64_t[ceil(n_src / 64)] */, int select_on_device,
                           uint64_t *n_selected /* or NULL */);
 
+/* The payloads of an arena percent-decoded on the device into a packed arena that a second context owns: the normalised buffer the same
+ * patterns, rules, byte tests and expressions run over, so that `GET /%61dmin`, `%2e%2e%2f` and `%3Cscript` meet the rules that name
+ * `/admin`, `../` and `<script`.  Every other call looks at the payload bytes as they were captured.
+ * Definition (transform == KMPGPU_DECODE_PERCENT, the only one; any other value: KMPGPU_EINVAL).  Let payload k of src be the bytes
+ * p[0..L), L = pkt_len[k]: the whole payload -- the transform does not look at KMPGPU_OPT_WHOLE_PAYLOAD and does not stop at 0x00.
+ *   hex(b): b is one of 0-9 a-f A-F.   esc(i): i + 2 < L and p[i] == '%' and hex(p[i+1]) and hex(p[i+2]).
+ * A hex digit is never '%', so escapes cannot overlap, and every position is decided on its own: there is no left-to-right state.
+ * The decoded payload is, for i ascending: the byte 16 * val(p[i+1]) + val(p[i+2]) where esc(i); nothing where esc(i-1) or esc(i-2);
+ * otherwise p[i] -- under KMPGPU_DECODE_PLUS 0x20 where p[i] == '+' (a '+' that a %2B decodes to stays '+').  So `%%41` gives `%A`,
+ * `%2%41` gives `%2A`, and a trailing `%4` or `%` stays.  This is what Python's urllib.parse.unquote_to_bytes computes (with PLUS: after
+ * '+' was replaced by ' ').  A %00 yields a 0x00 byte: under dst's default text rule that byte ends the payload's text, which is what a
+ * server that takes the decoded bytes as a C string would see; KMPGPU_OPT_WHOLE_PAYLOAD on dst scans behind it.  A byte at or behind L
+ * never takes part -- slot padding, whatever a borrowed arena holds there, the next payload: `%4` at a payload's end followed by `1` in
+ * dirty padding is not an escape.  changed(k): payload k has at least one escape or, under PLUS, at least one '+' -- the same as "the
+ * decoded bytes differ from the original".
+ * Result without KMPGPU_DECODE_ONLY_CHANGED: dst owns a packed arena of n_src payloads in source order, payload k the decoding of src's
+ * payload k, each in a slot of max(16, round_up(len, 16)) bytes, slots back to back from offset 0.  Every byte between a payload's end
+ * and its slot's end is 0x00, whatever the source held there; an empty payload owns one zero slot.  dst's hit rows, any[], alert
+ * records and flow ids are in src's numbering.
+ * Result with KMPGPU_DECODE_ONLY_CHANGED: dst holds only the payloads with changed(k), compacted in ascending order -- the j-th set bit
+ * of the changed bitmap is dst's payload j.  This is the cheap route: scan src raw, scan only the changed payloads decoded, and map back
+ * with the bitmap, as the cascade of kmpgpu_load_selected does.  No payload changed, or n_src == 0 (src without an arena): dst is left
+ * without an arena, as kmpgpu_load_arena(..., n_pkts = 0) leaves it -- scans return zeros --, the return value is KMPGPU_OK and dst's
+ * earlier arena is not kept.
+ * Outputs: changed_out (host, may be NULL) takes W = ceil(n_src / 64) words laid out as kmpgpu_scan_packets lays them out (payload k is
+ * bit (k & 63) of word (k >> 6)); bits of index n_src and above are 0.  *d_changed (may be NULL) = the same words in a device buffer
+ * dst owns, valid until dst's next loader call (NULL where n_src == 0 or the call failed); it is what
+ * kmpgpu_load_selected(third, src, ptr, 1, ..) takes, as the d_pkt_bits of kmpgpu_flows_select is.  *stats (may be NULL): n_payloads =
+ * the payloads dst holds, n_changed = the set bits of the bitmap, bytes_in = the source bytes of the payloads dst holds, bytes_out =
+ * their decoded bytes.
+ * State: the metadata goes with the payloads, as in kmpgpu_load_selected, whenever src has some (with ONLY_CHANGED the changed
+ * payloads' records in their new order, otherwise a device copy of all of them), so header predicates, kmpgpu_flows_build and
+ * flow-scope rules work in dst.  The arena is in the state kmpgpu_load_frames leaves: owned by the context, padding known clean,
+ * packet-start bitmap and plans rebuilt, uniform / packed taken from a device-side pass over the new index, the nocase fold stale (made
+ * again by the first pass that needs it); flows and seams of dst are dropped.
+ * Untouched: src is not written; its arena, index and derived state stay, and every output of it is bit-identical before and after.
+ * The source is whatever src scans now -- loaded, attached (borrowed), extracted from frames, selected, decoded, repacked, or kept in
+ * place under KMPGPU_OPT_REPACK = 0 (then not packed: the index is followed as it is).  A decoded arena can be decoded again: `%252e`
+ * takes two calls, through a third context or back and forth between two.  dst's patterns, flags, rules, windows, options and counters
+ * stay: they belong to the pattern set or the context, not to the arena.
+ * Ordering: synchronous.  Waits for dst's stream, as the loaders do, then for src's, and works on dst's stream.  dst's owned buffers
+ * are reused when the result fits and grown as the loaders grow them otherwise (an eighth of headroom; kmpgpu_reserve sizes them); the
+ * workspace is the scratch dst keeps for kmpgpu_load_frames, and the bitmap's buffer is kept too, so a ring of calls does not allocate
+ * per call.
+ * Errors: dst == src (decoding in place does not exist), a NULL context, contexts on different devices, an unknown transform, an
+ * unknown flag bit: KMPGPU_EINVAL; either context between kmpgpu_load_frames_begin and _finish: KMPGPU_ESTATE; after each of these dst
+ * keeps the arena it had.  After an allocation failure (KMPGPU_ENOMEM / KMPGPU_EHIP) dst is without an arena and both contexts stay
+ * usable.
+ * kmpgpu_last_timing(dst): kernel_ms from the first decode kernel to the write's end, launches = the kernels in that span (decoded
+ * lengths, two scan kernels, index, write: 5; 3 where dst ends up without a payload); the metadata's copy or kernel follows the span.
+ * kmpgpu_profile_begin .. _end time the span in four pairs: lengths, scan, index, write.
+ * Cost: two reads of src's payload bytes (lengths, write) and one write of the decoded ones. */
+#define KMPGPU_DECODE_PERCENT      1      /* transform */
+#define KMPGPU_DECODE_PLUS         1u     /* flags: '+' decodes to 0x20 */
+#define KMPGPU_DECODE_ONLY_CHANGED 2u     /* dst holds the changed payloads only */
+typedef struct kmpgpu_decode_stats { uint64_t n_payloads, n_changed, bytes_in, bytes_out; } kmpgpu_decode_stats;
+int  kmpgpu_load_decoded(kmpgpu_ctx *dst, kmpgpu_ctx *src, int transform, uint32_t flags,
+                         uint64_t *changed_out /* host [ceil(n_src / 64)] or NULL */, const void **d_changed /* or NULL */,
+                         kmpgpu_decode_stats *stats /* or NULL */);
+
 /* Flows: the payloads of the arena grouped by the 5-tuple of their metadata (kmpgpu_pkt_meta, above), on the device -- which payloads
  * belong to one connection, what each connection carried, and the hit rows of every family folded from payload space into flow space.
  * Definitions.  With M = meta[k], the two endpoints of payload k are the 48-bit integers e_src = src_ip << 16 | src_port and

@@ -19,4 +19,12 @@ from .host import (  # noqa: F401
     synth_fill_host,
     write_udp_pcap,
 )
-from .matcher import GpuComm, GpuMatcher, count_matches, device_count  # noqa: F401
+from .matcher import (  # noqa: F401
+    DECODE_ONLY_CHANGED,
+    DECODE_PERCENT,
+    DECODE_PLUS,
+    GpuComm,
+    GpuMatcher,
+    count_matches,
+    device_count,
+)

@@ -158,6 +158,11 @@ class Timing(C.Structure):
                 ("launches", C.c_uint32), ("grid_blocks", C.c_uint32), ("h2d_bytes", C.c_uint64)]
 
 
+class DecodeStats(C.Structure):
+    """kmpgpu_decode_stats (include/kmpgpu.h)."""
+    _fields_ = [("n_payloads", C.c_uint64), ("n_changed", C.c_uint64), ("bytes_in", C.c_uint64), ("bytes_out", C.c_uint64)]
+
+
 class Match(C.Structure):
     """kmpgpu_match (include/kmpgpu.h)."""
     _fields_ = [("packet", C.c_uint64), ("offset", C.c_uint32), ("pattern", C.c_uint32)]
@@ -271,6 +276,7 @@ GPU_API = {
     "kmpgpu_scan_alerts": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, u64p, u64p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
     "kmpgpu_alerts_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "kmpgpu_load_selected": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, u64p]),
+    "kmpgpu_load_decoded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(DecodeStats)]),
     "kmpgpu_flows_build": (C.c_int, [C.c_void_p, C.c_uint32, u64p, C.POINTER(Timing)]),
     "kmpgpu_flows_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "kmpgpu_flow_ids_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),

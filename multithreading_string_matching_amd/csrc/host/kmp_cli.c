@@ -93,6 +93,15 @@
  * KMPGPU_WINDOWS_FILE count from a payload's start and stay with the payloads: the seams are scanned without windows.  Refused with a
  * message on stderr and exit 1, before any GPU work: the variable without KMPGPU_FLOW_ALERTS_FILE, a reach that is no number in 1..98.
  *
+ * KMPGPU_DECODE=percent or KMPGPU_DECODE=percent+plus, together with at least one of KMPGPU_PACKETS_FILE, KMPGPU_ALERTS_FILE and
+ * KMPGPU_FLOW_ALERTS_FILE: these row outputs are decided on the percent-decoded payloads (kmpgpu_load_decoded; with +plus a '+' decodes
+ * to a space as well), so that `GET /%61dmin` meets the rule that names `/admin`.  Per shard a second context on the shard's device gets
+ * the decoding of the shard's arena, every payload, so the payload numbers are the capture's, and the same patterns and flags, windows,
+ * relations, chains, header predicates, byte tests, expressions, rules and text rule as the shard's (upload_tables).  stdout -- the
+ * counts over the payloads as captured -- and KMPGPU_FLOWS_FILE are what they are without the variable.  Refused with a message on
+ * stderr and exit 1, before any GPU work: any other value; the variable together with KMPGPU_OFFSETS_FILE (offsets in decoded payloads
+ * are not mapped back), KMPGPU_EXPORT_FILE or KMPGPU_FLOW_SEAMS; the variable with none of the three row outputs.
+ *
  * KMPGPU_NOCASE=1: every pattern matches case-insensitively (ASCII letters; kmpgpu_set_patterns_flags), in the counts and in
  * the offsets file alike; the report prints every token as written in the pattern file.
  *
@@ -108,6 +117,7 @@
 #include "kmpgpu.h"
 #include "kmphost.h"
 #include "kmp_cli_common.h"
+#include "kmp_cli_decode.h"
 
 #ifndef KMP_CLI_OPENMP_FORM
 #define KMP_CLI_OPENMP_FORM 0
@@ -131,6 +141,7 @@ typedef struct cli_options {
     const char *offsets_path, *packets_path, *rules_path, *alerts_path, *export_path, *flows_path, *flow_alerts_path;
     int flows_directed;                     /* KMPGPU_FLOWS_DIRECTED */
     uint32_t flow_seams;                    /* KMPGPU_FLOW_SEAMS: the reach, 0 without the variable */
+    int decode;                             /* KMPGPU_DECODE: KMP_CLI_DECODE_* */
     int want_meta;                          /* header predicates or flows: the payloads' header fields go to the device */
     /* what every shard's context gets behind its patterns, in this order and before any rule is set */
     uint32_t *win_first, *win_last;         /* KMPGPU_WINDOWS_FILE (NULL: none) */
@@ -171,6 +182,7 @@ typedef struct cli_run {
     int ndev, shards, reduce_rccl, rules_set;
     shard_job *job;
     kmpgpu_ctx **ctxs;                      /* ctxs[r] = job[r].ctx */
+    kmpgpu_ctx **rows;                      /* rows[r]: the context the row outputs of shard r come from -- ctxs[r], or with KMPGPU_DECODE its decoding */
     kmpgpu_comm *comm;
     uint64_t *own, *counts;                 /* own[r * n_patterns + i]: shard r's count of pattern i; counts[i]: the total */
     double kernel_ms;
@@ -343,6 +355,30 @@ static void load_options(int argc, char *argv[], cli_options *opt)
         }
         opt->flow_seams = (uint32_t)reach;
     }
+    /* the decoded buffer: it changes what the row outputs hold and nothing else */
+    const char *decode_env = env_path("KMPGPU_DECODE");
+    if (decode_env) {
+        if (!kmp_cli_parse_decode(decode_env, &opt->decode)) {
+            fprintf(stderr, "KMPGPU_DECODE is \"%s\": percent or percent+plus is needed\n", decode_env);
+            exit(1);
+        }
+        if (opt->offsets_path) {
+            fprintf(stderr, "KMPGPU_DECODE does not go together with KMPGPU_OFFSETS_FILE: offsets in decoded payloads are not mapped back to the capture's\n");
+            exit(1);
+        }
+        if (opt->export_path) {
+            fprintf(stderr, "KMPGPU_DECODE does not go together with KMPGPU_EXPORT_FILE: the export selects and writes the payloads as captured\n");
+            exit(1);
+        }
+        if (opt->flow_seams) {
+            fprintf(stderr, "KMPGPU_DECODE does not go together with KMPGPU_FLOW_SEAMS: decoded seams do not exist\n");
+            exit(1);
+        }
+        if (!opt->packets_path && !opt->alerts_path && !opt->flow_alerts_path) {
+            fprintf(stderr, "KMPGPU_DECODE has no effect without KMPGPU_PACKETS_FILE, KMPGPU_ALERTS_FILE or KMPGPU_FLOW_ALERTS_FILE\n");
+            exit(1);
+        }
+    }
     opt->want_meta = opt->headers.n || opt->flows_path || opt->flow_alerts_path;
     /* the export starts as a capture without frames: a path that cannot be written ends the run here */
     if (opt->export_path && kmp_write_udp_pcap_part(opt->export_path, 0, NULL, NULL, NULL, 0, 0)) {
@@ -413,22 +449,32 @@ static void *shard_fail(shard_job *j, const char *what)
     return NULL;
 }
 
+/* What a context of the run scans with, in this order and before any rule is set: the patterns with the environment's text rule and
+ * case rule, the windows, relations, chains, header predicates, byte tests and expressions.  Every shard's context and, with
+ * KMPGPU_DECODE, its decoding pass through here.  Returns NULL, or the name of the call that failed. */
+static const char *upload_tables(kmpgpu_ctx *ctx, const cli_options *o)
+{
+    if (set_patterns_env(ctx, o->pp, o->pats.len, o->pats.n, o->whole_payload, o->nocase)) return "kmpgpu_set_patterns";
+    if (o->win_first && kmpgpu_set_windows(ctx, o->win_first, o->win_last, o->pats.n)) return "kmpgpu_set_windows";
+    _Static_assert(sizeof(kmp_relation) == sizeof(kmpgpu_relation), "kmp_relation has the layout of kmpgpu_relation");
+    if (o->relations.n && kmpgpu_set_relations(ctx, (const kmpgpu_relation *)o->relations.rel, o->relations.n)) return "kmpgpu_set_relations";
+    _Static_assert(sizeof(kmp_chain_link) == sizeof(kmpgpu_chain_link), "kmp_chain_link has the layout of kmpgpu_chain_link");
+    if (o->chains.n && kmpgpu_set_chains(ctx, o->chains.off, (const kmpgpu_chain_link *)o->chains.links, o->chains.n)) return "kmpgpu_set_chains";
+    _Static_assert(sizeof(kmp_header) == sizeof(kmpgpu_header) && sizeof(kmp_pkt_meta) == sizeof(kmpgpu_pkt_meta), "kmp_header, kmp_pkt_meta have the layouts of kmpgpu.h");
+    if (o->headers.n && kmpgpu_set_headers(ctx, (const kmpgpu_header *)o->headers.hdr, o->headers.n)) return "kmpgpu_set_headers";
+    _Static_assert(sizeof(kmp_bytetest) == sizeof(kmpgpu_bytetest), "kmp_bytetest has the layout of kmpgpu_bytetest");
+    if (o->bytetests.n && kmpgpu_set_bytetests(ctx, (const kmpgpu_bytetest *)o->bytetests.bt, o->bytetests.n)) return "kmpgpu_set_bytetests";
+    if (o->regexes.n && kmpgpu_set_regexes(ctx, o->regexes.expr, o->regexes.len, o->regexes.flags, o->regexes.gate, o->regexes.n)) return "kmpgpu_set_regexes";
+    return NULL;
+}
+
 static void *shard_load(void *arg)
 {
     shard_job *j = (shard_job *)arg;
     const cli_options *o = j->opt;
     if (kmpgpu_init(&j->ctx, j->device)) return shard_fail(j, "kmpgpu_init");
-    if (set_patterns_env(j->ctx, o->pp, o->pats.len, o->pats.n, o->whole_payload, o->nocase)) return shard_fail(j, "kmpgpu_set_patterns");
-    if (o->win_first && kmpgpu_set_windows(j->ctx, o->win_first, o->win_last, o->pats.n)) return shard_fail(j, "kmpgpu_set_windows");
-    _Static_assert(sizeof(kmp_relation) == sizeof(kmpgpu_relation), "kmp_relation has the layout of kmpgpu_relation");
-    if (o->relations.n && kmpgpu_set_relations(j->ctx, (const kmpgpu_relation *)o->relations.rel, o->relations.n)) return shard_fail(j, "kmpgpu_set_relations");
-    _Static_assert(sizeof(kmp_chain_link) == sizeof(kmpgpu_chain_link), "kmp_chain_link has the layout of kmpgpu_chain_link");
-    if (o->chains.n && kmpgpu_set_chains(j->ctx, o->chains.off, (const kmpgpu_chain_link *)o->chains.links, o->chains.n)) return shard_fail(j, "kmpgpu_set_chains");
-    _Static_assert(sizeof(kmp_header) == sizeof(kmpgpu_header) && sizeof(kmp_pkt_meta) == sizeof(kmpgpu_pkt_meta), "kmp_header, kmp_pkt_meta have the layouts of kmpgpu.h");
-    if (o->headers.n && kmpgpu_set_headers(j->ctx, (const kmpgpu_header *)o->headers.hdr, o->headers.n)) return shard_fail(j, "kmpgpu_set_headers");
-    _Static_assert(sizeof(kmp_bytetest) == sizeof(kmpgpu_bytetest), "kmp_bytetest has the layout of kmpgpu_bytetest");
-    if (o->bytetests.n && kmpgpu_set_bytetests(j->ctx, (const kmpgpu_bytetest *)o->bytetests.bt, o->bytetests.n)) return shard_fail(j, "kmpgpu_set_bytetests");
-    if (o->regexes.n && kmpgpu_set_regexes(j->ctx, o->regexes.expr, o->regexes.len, o->regexes.flags, o->regexes.gate, o->regexes.n)) return shard_fail(j, "kmpgpu_set_regexes");
+    const char *failed = upload_tables(j->ctx, o);
+    if (failed) return shard_fail(j, failed);
     if (o->want_meta && o->device_extract && kmpgpu_set_option(j->ctx, KMPGPU_OPT_KEEP_META, 1)) return shard_fail(j, "kmpgpu_set_option");
     if (o->device_extract) {
         /* only the bytes this shard's frames span are uploaded (kmpgpu_load_frames) */
@@ -460,6 +506,7 @@ static void start_shards(const cli_options *opt, const capture *cap, uint64_t un
     const int shards = run->shards;
     shard_job *job = run->job = (shard_job *)calloc((size_t)shards, sizeof *job);
     run->ctxs = (kmpgpu_ctx **)calloc((size_t)shards, sizeof *run->ctxs);
+    run->rows = (kmpgpu_ctx **)calloc((size_t)shards, sizeof *run->rows);
     uint64_t lo = 0;
     for (int r = 0; r < shards; r++) {
         job[r].opt = opt; job[r].cap = cap; job[r].device = r % run->ndev;
@@ -475,7 +522,7 @@ static void start_shards(const cli_options *opt, const capture *cap, uint64_t un
     uint64_t payload_lo = 0;
     for (int r = 0; r < shards; r++) {
         if (job[r].rc) { fprintf(stderr, "%s: %s\n", job[r].what, job[r].err); exit(2); }
-        run->ctxs[r] = job[r].ctx;
+        run->ctxs[r] = run->rows[r] = job[r].ctx;
         job[r].payload_lo = payload_lo;
         payload_lo += job[r].n_payloads;
     }
@@ -498,12 +545,27 @@ static void write_offsets(const char *path, const cli_run *run, uint32_t n_patte
     fclose(fp);
 }
 
-/* The rules on every shard's context, once: before the first output that needs them (the alerts file, behind its fopen, or the export). */
+/* KMPGPU_DECODE: next to every shard a context with the same tables that holds the shard's payloads percent-decoded, every one of them,
+ * so that payload numbers stay the capture's; the row outputs come from it. */
+static void decode_shards(const cli_options *opt, cli_run *run)
+{
+    const uint32_t flags = opt->decode == KMP_CLI_DECODE_PLUS ? KMPGPU_DECODE_PLUS : 0u;
+    for (int r = 0; r < run->shards; r++) {
+        kmpgpu_ctx *d = NULL;
+        if (kmpgpu_init(&d, run->job[r].device)) die_gpu("kmpgpu_init");
+        const char *failed = upload_tables(d, opt);
+        if (failed) die_gpu(failed);
+        if (kmpgpu_load_decoded(d, run->ctxs[r], KMPGPU_DECODE_PERCENT, flags, NULL, NULL, NULL)) die_gpu("kmpgpu_load_decoded");
+        run->rows[r] = d;
+    }
+}
+
+/* The rules on every context the row outputs come from, once: before the first output that needs them (the alerts file, behind its fopen, or the export). */
 static void set_rules_once(const cli_options *opt, cli_run *run)
 {
     if (run->rules_set || !opt->rules.n) return;
     for (int r = 0; r < run->shards; r++)
-        if (kmpgpu_set_rules(run->ctxs[r], opt->rules.off, opt->rules.terms, opt->rules.n)) die_gpu("kmpgpu_set_rules");
+        if (kmpgpu_set_rules(run->rows[r], opt->rules.off, opt->rules.terms, opt->rules.n)) die_gpu("kmpgpu_set_rules");
     run->rules_set = 1;
 }
 
@@ -520,10 +582,10 @@ static void write_alerts(const char *path, const cli_options *opt, cli_run *run,
     if (by_rules) set_rules_once(opt, run);
     for (int r = 0; r < (by_rules && !opt->rules.n ? 0 : run->shards); r++) {
         uint64_t found = 0;
-        if (kmpgpu_scan_alerts(run->ctxs[r], family, UINT64_MAX, &found, NULL, NULL, NULL, NULL)) die_gpu("kmpgpu_scan_alerts");
+        if (kmpgpu_scan_alerts(run->rows[r], family, UINT64_MAX, &found, NULL, NULL, NULL, NULL)) die_gpu("kmpgpu_scan_alerts");
         for (uint64_t first = 0; first < found; first += ALERT_PIECE) {
             const uint64_t n = found - first < ALERT_PIECE ? found - first : ALERT_PIECE;
-            if (kmpgpu_alerts_read(run->ctxs[r], piece, first, n)) die_gpu("kmpgpu_alerts_read");
+            if (kmpgpu_alerts_read(run->rows[r], piece, first, n)) die_gpu("kmpgpu_alerts_read");
             for (uint64_t i = 0; i < n; i++) fprintf(fp, "%llu,%u\n", (unsigned long long)(run->job[r].payload_lo + piece[i].packet), piece[i].index);
         }
     }
@@ -538,7 +600,10 @@ static void write_flows(const cli_options *opt, cli_run *run)
     static kmpgpu_flow piece[FLOW_PIECE];
     kmpgpu_ctx *ctx = run->ctxs[0];
     uint64_t n_flows = 0;
-    if (kmpgpu_flows_build(ctx, opt->flows_directed ? KMPGPU_FLOW_DIRECTED : 0u, &n_flows, NULL)) die_gpu("kmpgpu_flows_build");
+    /* the flows file from the payloads as captured (its byte counts are theirs); the flow alerts from the context the rows come from,
+     * which groups the same metadata into the same flows */
+    if ((opt->flows_path || run->rows[0] == ctx) && kmpgpu_flows_build(ctx, opt->flows_directed ? KMPGPU_FLOW_DIRECTED : 0u, &n_flows, NULL))
+        die_gpu("kmpgpu_flows_build");
     if (opt->flows_path) {
         FILE *fp = fopen(opt->flows_path, "w");
         if (!fp) { perror("KMPGPU_FLOWS_FILE"); exit(1); }
@@ -559,6 +624,10 @@ static void write_flows(const cli_options *opt, cli_run *run)
     if (opt->flow_alerts_path) {
         FILE *fp = fopen(opt->flow_alerts_path, "w");
         if (!fp) { perror("KMPGPU_FLOW_ALERTS_FILE"); exit(1); }
+        if (run->rows[0] != ctx) {
+            ctx = run->rows[0];
+            if (kmpgpu_flows_build(ctx, opt->flows_directed ? KMPGPU_FLOW_DIRECTED : 0u, &n_flows, NULL)) die_gpu("kmpgpu_flows_build");
+        }
         set_rules_once(opt, run);
         const uint64_t Wf = (n_flows + 63) / 64, nr = opt->rules.n;
         if (nr && n_flows) {
@@ -672,6 +741,7 @@ int main(int argc, char *argv[])
         run.reduce_rccl = reduce_counts(run.ctxs, run.shards, n, run.own, run.counts, run.comm);
         run.kernel_ms = (now_s() - t_scan0) * 1e3;                          /* wall time of the concurrent passes + reduce (mpi_dumping.c:206 MPI_MAX) */
 
+        if (opt.decode) decode_shards(&opt, &run);
         if (opt.offsets_path) write_offsets(opt.offsets_path, &run, n);
         if (opt.packets_path) write_alerts(opt.packets_path, &opt, &run, KMPGPU_ALERT_PATTERNS);
         if (opt.alerts_path) write_alerts(opt.alerts_path, &opt, &run, KMPGPU_ALERT_RULES);
@@ -691,9 +761,12 @@ int main(int argc, char *argv[])
     kmp_report(stdout, &opt.pats, run.counts, t_finish - t_start);         /* serial.c:163-169 */
     /* teardown after the report: serial.c:159-160 takes the time before it frees anything, :178-180 */
     if (run.comm) kmpgpu_comm_destroy(run.comm);
-    for (int r = 0; r < run.shards && run.job; r++) { kmpgpu_destroy(run.ctxs[r]); free(run.job[r].reb); }
+    for (int r = 0; r < run.shards && run.job; r++) {
+        if (run.rows[r] != run.ctxs[r]) kmpgpu_destroy(run.rows[r]);
+        kmpgpu_destroy(run.ctxs[r]); free(run.job[r].reb);
+    }
     if (run.kernel_ms > 0) print_stats(&opt, &cap, &run, t_finish);
-    free(run.ctxs); free(run.job); free(run.own); free(run.counts);
+    free(run.ctxs); free(run.rows); free(run.job); free(run.own); free(run.counts);
     kmp_arena_free(&cap.arena);
     kmp_frames_free(&cap.frames);
     free(cap.meta);

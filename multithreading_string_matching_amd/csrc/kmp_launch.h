@@ -1,5 +1,5 @@
 /* kmp_launch.h -- launch entry points of kmp_scan_*.hip / kmp_prep.hip / kmp_fold.hip / kmp_marks.hip / kmp_rules.hip / kmp_relations.hip /
- * kmp_chains.hip / kmp_headers.hip / kmp_bytetests.hip / kmp_regex.hip / kmp_select.hip / kmp_alerts.hip / kmp_flows.hip / kmp_seams.hip, used
+ * kmp_chains.hip / kmp_headers.hip / kmp_bytetests.hip / kmp_regex.hip / kmp_select.hip / kmp_decode.hip / kmp_alerts.hip / kmp_flows.hip / kmp_seams.hip, used
  * by the C-ABI layer (kmpgpu.hip), which alone decides what is launched; the tables kmp_launch_scan_multi takes come from kmp_tables.h. */
 #ifndef KMP_LAUNCH_H
 #define KMP_LAUNCH_H
@@ -181,6 +181,20 @@ hipError_t kmp_launch_select_phase1(const unsigned long long *select, const uint
 hipError_t kmp_launch_select_phase2(const uint8_t *src_arena, const uint64_t *src_off, uint64_t n, uint8_t *ws, uint64_t n_sel,
                                     uint64_t total_bytes, uint8_t *arena, uint64_t *pkt_off, uint32_t *pkt_len, void *recs,
                                     bool nontemporal, hipStream_t st);
+/* kmp_decode.hip (kmpgpu_load_decoded): the n payloads of an index percent-decoded (the definition: kmpgpu.h) into a packed arena.  ws:
+ * kmp_extract_ws_bytes(n) bytes, kept from _lengths to _index.  _lengths (1 kernel) leaves per payload its decoded length, or 0xFFFFFFFF
+ * for an unchanged one with only_changed, writes every word of changed[ceil(n / 64)] (bits at n and above 0) and adds to stats[3] =
+ * {source bytes of the payloads kept, changed payloads, decoded bytes}, which the caller zeroes.  _scan (2 kernels) leaves totals[0] =
+ * bytes of the packed result, totals[1] = its payloads n_dst.  _index (1 kernel) writes pkt_off[n_dst], pkt_len[n_dst] and the 16-byte
+ * records recs[n_dst]; _write (1 kernel) arena[0, total_bytes): every slot whole, 0x00 behind its payload's end.  bytes_in: stats[0].
+ * The source's slots are 16-byte aligned (the layout contract of kmpgpu.h); nothing at or behind a payload's end takes part. */
+hipError_t kmp_launch_decode_lengths(const uint8_t *src_arena, const uint64_t *src_off, const uint32_t *src_len, uint64_t n, bool plus,
+                                     bool only_changed, uint8_t *ws, unsigned long long *changed, unsigned long long *stats, hipStream_t st);
+hipError_t kmp_launch_decode_scan(uint64_t n, uint8_t *ws, unsigned long long *totals, hipStream_t st);
+hipError_t kmp_launch_decode_index(const uint64_t *src_off, const uint32_t *src_len, uint64_t n, uint8_t *ws, uint64_t n_dst, uint64_t *pkt_off,
+                                   uint32_t *pkt_len, void *recs, hipStream_t st);
+hipError_t kmp_launch_decode_write(const uint8_t *src_arena, const uint64_t *pkt_off, const void *recs, uint64_t n_dst, uint64_t bytes_in,
+                                   uint64_t total_bytes, bool plus, uint8_t *arena, bool nontemporal, hipStream_t st);
 /* kmp_alerts.hip (kmpgpu_scan_alerts): the set bits of rows[n_rows][stride] (stride even, 16-byte aligned, every word of a row readable,
  * the bits of index n_pkts and above not looked at; 16 * n_rows <= 0xFFFFFFFE) as 16-byte records {payload (64 bits), row, 0}, sorted by
  * payload, then row.  any[ceil(n_pkts / 64)]: the OR over the rows, complete before the count; a column word whose any word is 0 is not read.

@@ -223,6 +223,9 @@ struct kmpgpu_ctx {
     uint64_t            flow_fold_cap = 0, flow_sel_cap = 0;          /* words */
     uint64_t            n_flows = 0;
     bool                flows_valid = false;
+    /* kmpgpu_load_decoded as dst: the changed bitmap [ceil(n_src / 64)] and, behind it, the four words its kernels count in */
+    unsigned long long *d_dec_changed = nullptr;
+    uint64_t            dec_changed_cap = 0;          /* words */
     int64_t             flow_slots = 0;               /* KMPGPU_OPT_FLOW_SLOTS */
     /* which build of the flows the context holds: kmpgpu_flows_build and drop_flows start a new generation, and id tells one context from
      * every other the process has made (a seam list names the context and the generation it was built from) */
@@ -551,6 +554,7 @@ void release_pass_buffers(kmpgpu_ctx *c)
     free_buffer(&c->d_meta, &c->meta_cap); c->has_meta = false;
     free_buffer(&c->d_flow_table, &c->flow_table_cap); free_buffer(&c->d_flow_first, &c->flow_first_cap); free_buffer(&c->d_flow_of, &c->flow_of_cap);
     free_buffer(&c->d_flow_recs, &c->flow_recs_cap); free_buffer(&c->d_flow_fold, &c->flow_fold_cap); free_buffer(&c->d_flow_sel, &c->flow_sel_cap);
+    free_buffer(&c->d_dec_changed, &c->dec_changed_cap);
     drop_flows(c);
     free_buffer(&c->d_seams, &c->seams_cap); free_buffer(&c->d_seam_flow, &c->seam_flow_cap); free_buffer(&c->d_seam_sort, &c->seam_sort_cap);
     drop_seams(c);
@@ -1492,6 +1496,97 @@ int kmpgpu_load_selected(kmpgpu_ctx *dst, kmpgpu_ctx *src, const void *select, i
     c->has_meta = src->has_meta;
     if (n_selected) *n_selected = n_pkts;
     return KMPGPU_OK;
+}
+
+int kmpgpu_load_decoded(kmpgpu_ctx *dst, kmpgpu_ctx *src, int transform, uint32_t flags, uint64_t *changed_out, const void **d_changed,
+                        kmpgpu_decode_stats *stats)
+{
+    const char *who = "kmpgpu_load_decoded";
+    if (d_changed) *d_changed = nullptr;
+    if (stats) *stats = kmpgpu_decode_stats{};
+    if (!dst || !src) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
+    if (dst == src) return fail(KMPGPU_EINVAL, "%s: dst and src are the same context (decoding in place does not exist)", who);
+    if (transform != KMPGPU_DECODE_PERCENT) return fail(KMPGPU_EINVAL, "%s: transform %d is not KMPGPU_DECODE_PERCENT", who, transform);
+    if (flags & ~(KMPGPU_DECODE_PLUS | KMPGPU_DECODE_ONLY_CHANGED)) return fail(KMPGPU_EINVAL, "%s: unknown flag bits 0x%x", who, flags);
+    if (dst->device != src->device)
+        return fail(KMPGPU_EINVAL, "%s: the contexts sit on devices %d and %d (decoding across devices does not exist)", who, dst->device, src->device);
+    if (dst->fr_pending || src->fr_pending) return fail(KMPGPU_ESTATE, "%s: %s sits between kmpgpu_load_frames_begin and _finish", who, dst->fr_pending ? "dst" : "src");
+    const bool plus = (flags & KMPGPU_DECODE_PLUS) != 0, only_changed = (flags & KMPGPU_DECODE_ONLY_CHANGED) != 0;
+    HIP_TRY(hipSetDevice(dst->device));
+    HIP_TRY(hipStreamSynchronize(dst->stream));           /* the passes over the arena that is about to be replaced */
+    HIP_TRY(hipStreamSynchronize(src->stream));           /* whatever src's stream still does with its arena */
+    kmpgpu_ctx *c = dst;
+    c->last = kmpgpu_timing{};
+    const uint64_t n = src->n_pkts;
+    if (n == 0) { release_arena(c, /* keep_buffers = */ true); return KMPGPU_OK; }
+
+    /* the scratch of kmpgpu_load_frames (fr_ws the scan, fr_src the write's records) and the bitmap's own buffer */
+    const uint64_t words = (n + 63) / 64;
+    HIP_TRY(grow_buffer(&c->fr_ws, &c->fr_ws_cap, (uint64_t)kmp_extract_ws_bytes(n), EIGHTH));
+    if (!c->fr_tot) HIP_TRY(hipMalloc(&c->fr_tot, 2 * sizeof(unsigned long long)));
+    HIP_TRY(grow_buffer(&c->d_dec_changed, &c->dec_changed_cap, words + 4, EIGHTH));
+    unsigned long long *d_stats = c->d_dec_changed + words;
+    HIP_TRY(hipMemsetAsync(d_stats, 0, 4 * sizeof(unsigned long long), c->stream));
+    hipEvent_t e1;
+    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_decode_lengths(src->d_arena, src->d_off, src->d_len, n, plus, only_changed, c->fr_ws, c->d_dec_changed, d_stats, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_decode_scan(n, c->fr_ws, c->fr_tot, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(hipMemcpyAsync(c->h_small, c->fr_tot, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));         /* (pinned: no staging) */
+    HIP_TRY(hipMemcpyAsync(c->h_small + 2, d_stats, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    if (changed_out) HIP_TRY(hipMemcpyAsync(changed_out, c->d_dec_changed, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    unsigned long long tot[6] = {0, 0, 0, 0, 0, 0};       /* packed bytes, payloads; source bytes, changed payloads, decoded bytes */
+    memcpy(tot, c->h_small, sizeof tot);
+    const uint64_t n_pkts = tot[1], arena_bytes = tot[0] + 64;
+    auto done = [&](uint32_t launches) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
+        c->last.kernel_ms = ms; c->last.launches = launches;
+        if (d_changed) *d_changed = c->d_dec_changed;
+        if (stats) { stats->n_payloads = n_pkts; stats->n_changed = tot[3]; stats->bytes_in = tot[2]; stats->bytes_out = tot[4]; }
+        return (int)KMPGPU_OK;
+    };
+    /* from here on dst's earlier arena is gone, whatever happens */
+    release_arena(c, /* keep_buffers = */ true);
+    if (n_pkts == 0) {
+        HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+        HIP_TRY(hipEventSynchronize(c->ev[3]));
+        return done(3);
+    }
+    hipError_t e = ensure_owned_arena(c, arena_bytes, n_pkts, EIGHTH);       /* (on failure dst is empty and usable) */
+    if (e != hipSuccess)
+        return alloc_fail(e, "%s: an arena of %llu bytes / %llu payloads could not be allocated", who,
+                          (unsigned long long)(arena_bytes + arena_bytes / 8), (unsigned long long)(n_pkts + n_pkts / 8));
+    e = grow_buffer(&c->fr_src, &c->fr_src_cap, 2 * n_pkts, EIGHTH);      /* 16 bytes per payload of dst */
+    if (e != hipSuccess) return alloc_fail(e, "%s: the write's records (%llu payloads) could not be allocated", who, (unsigned long long)n_pkts);
+    if (src->has_meta) {
+        e = grow_buffer(&c->d_meta, &c->meta_cap, n_pkts, EIGHTH);
+        if (e != hipSuccess) return alloc_fail(e, "%s: the metadata (%llu payloads) could not be allocated", who, (unsigned long long)n_pkts);
+    }
+    HIP_TRY(hipMemsetAsync(c->owned_arena + tot[0], 0, 64, c->stream));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_decode_index(src->d_off, src->d_len, n, c->fr_ws, n_pkts, c->owned_off, c->owned_len, c->fr_src, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_decode_write(src->d_arena, c->owned_off, c->fr_src, n_pkts, tot[2], tot[0], plus, c->owned_arena, c->nontemporal != 0, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    /* src has metadata: the records go with the payloads -- in their new order, or all of them as they are */
+    if (src->has_meta) {
+        if (only_changed) HIP_TRY(kmp_launch_meta_select(src->d_meta, n, c->fr_ws, c->d_meta, c->stream));
+        else HIP_TRY(hipMemcpyAsync(c->d_meta, src->d_meta, n * sizeof(uint4), hipMemcpyDeviceToDevice, c->stream));
+    }
+    IndexFacts f;
+    int rc = validate_index(c, who, c->owned_off, c->owned_len, n_pkts, arena_bytes, &f);
+    /* kmp_decode_write_kernel writes every slot whole: payload, then 0x00 up to the slot's end */
+    if (!rc) rc = install_arena(c, c->owned_arena, c->owned_off, c->owned_len, arena_bytes, n_pkts, f, /* wrote_padding = */ true);
+    if (rc) { release_arena(c, true); return rc; }
+    c->has_meta = src->has_meta;
+    return done(5);
 }
 
 int kmpgpu_load_seams(kmpgpu_ctx *dst, kmpgpu_ctx *src, uint32_t reach, uint64_t *n_seams)

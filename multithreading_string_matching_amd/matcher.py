@@ -35,6 +35,8 @@ FLOW_DIRECTED = 1       # KMPGPU_FLOW_DIRECTED: the two directions of a conversa
 FLOW_SCOPES = {"packet": 0, "flow": 1}     # KMPGPU_FLOW_SCOPE_*
 FLOW_DTYPE = np.dtype([("first_packet", "<u8"), ("last_packet", "<u8"), ("n_packets", "<u8"), ("payload_bytes", "<u8"),
                        ("first", META_DTYPE)])     # kmpgpu_flow, 48 bytes
+DECODE_PERCENT = 1      # KMPGPU_DECODE_PERCENT: the transform of load_decoded
+DECODE_PLUS, DECODE_ONLY_CHANGED = 1, 2     # KMPGPU_DECODE_*: its flags
 SEAM_DTYPE = np.dtype([("prev", "<u8"), ("next", "<u8"), ("tail_len", "<u4"), ("head_len", "<u4")])      # kmpgpu_seam, 24 bytes
 
 
@@ -409,6 +411,31 @@ class GpuMatcher:
         if idx.size != int(n.value):
             raise KmpGpuError(f"kmpgpu_load_selected reports {int(n.value)} payloads, the bitmap holds {idx.size}")
         return idx
+
+    def load_decoded(self, src: "GpuMatcher", plus: bool = False, only_changed: bool = False) -> dict:
+        """Make this matcher's arena the payloads of ``src`` percent-decoded on the device (kmpgpu_load_decoded; the definition:
+        kmpgpu.h -- what urllib.parse.unquote_to_bytes computes, with ``plus`` after '+' was replaced by ' '); patterns, rules,
+        windows and options of this matcher stay.  only_changed: this matcher holds only the payloads the decoding changes,
+        compacted in ascending source order.  Returns {"changed": bool[n_src], "index": int64[n_dst], "stats": {...}}: payload j
+        of this matcher is the decoding of payload index[j] of src."""
+        n_src, _ = src.arena_info()
+        W = (n_src + 63) // 64
+        words = np.zeros(max(W, 1), dtype=np.uint64)
+        st = _lib.DecodeStats()
+        flags = (DECODE_PLUS if plus else 0) | (DECODE_ONLY_CHANGED if only_changed else 0)
+        gpu_check(self._g.kmpgpu_load_decoded(self._ctx, src._ctx, DECODE_PERCENT, flags, words.ctypes.data, None, C.byref(st)),
+                  "kmpgpu_load_decoded")
+        self._keep = None
+        bits = np.unpackbits(words[:W].view(np.uint8), bitorder="little")
+        if bits[n_src:].any():
+            raise KmpGpuError(f"kmpgpu_load_decoded set a bit at or above {n_src} in the changed bitmap")
+        changed = bits[:n_src].astype(bool)
+        index = np.flatnonzero(changed).astype(np.int64) if only_changed else np.arange(n_src, dtype=np.int64)
+        stats = {f: int(getattr(st, f)) for f, _ in _lib.DecodeStats._fields_}
+        if stats["n_changed"] != int(changed.sum()) or stats["n_payloads"] != index.size or self.arena_info()[0] != index.size:
+            raise KmpGpuError(f"kmpgpu_load_decoded reports {stats['n_payloads']} payloads and {stats['n_changed']} changed ones, the "
+                              f"bitmap holds {int(changed.sum())} of {n_src}")
+        return {"changed": changed, "index": index, "stats": stats}
 
     def arena_download(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         n, _ = self.arena_info()
