@@ -1002,6 +1002,69 @@ int  kmpgpu_scan_flows_seams(kmpgpu_ctx *src, kmpgpu_ctx *seams, uint64_t *flow_
                              uint64_t *any_out /* [Wf] or NULL */, uint64_t *flow_hits_out /* [n_rules * Wf] or NULL */,
                              uint64_t *counts_out /* [n_pat] or NULL: as kmpgpu_scan(src) */, kmpgpu_timing *t /* or NULL */);
 
+/* Flow streams: the payloads of every direction of every flow reassembled.  A signature is written against the byte stream of one direction
+ * of a connection, and the matcher sees segments: a content cut into three segments, or a stream of one-byte segments, walks past every
+ * content rule, and a seam (above) holds one boundary and pattern rows only.  kmpgpu_load_streams concatenates the payloads of every
+ * (flow, direction) of src, in capture order, into ONE payload each of a packed arena that a second context owns.  A stream is then an
+ * ordinary payload of an ordinary context: patterns, counts, offsets, windows, relations, chains, byte tests, regex rows, rules, alerts,
+ * kmpgpu_load_decoded and kmpgpu_load_selected run over it as over any other.
+ * Definitions.  src holds built flows (kmpgpu_flows_build); flow_of and dir(k) exactly as the seams section defines them.  A STREAM is one
+ * distinct (flow_of, dir) of src; streams are numbered in ascending order of flow << 1 | dir, so n_streams == n_pkts - n_seams.  Its members
+ * are the payloads of that flow and direction in capture order (a stable sort; not sequence numbers), and no atomic decides anything: the
+ * arena and every record are byte-identical from run to run.  With L_k the index's lengths, whatever KMPGPU_OPT_WHOLE_PAYLOAD says, stream s
+ * is the raw bytes
+ *     payload_k0[0 : L_k0] ++ payload_k1[0 : L_k1] ++ ...          over its members k0 < k1 < ...,
+ * cut to its first `depth` bytes, depth in 1 .. KMPGPU_STREAM_DEPTH_MAX = 2^30 (which keeps every offset inside a stream below 2^31, as the
+ * relation and chain arithmetic and pkt_len need).  A member that starts at or behind the cut contributes nothing but still has its map
+ * entry.  A stream of 0 bytes exists and owns one zero slot.
+ *
+ * kmpgpu_load_streams.  dst ends up in the state kmpgpu_load_selected leaves it in: an owned packed arena of the n_streams streams, slots of
+ * max(16, round_up(len, 16)) bytes back to back from offset 0, 0x00 behind every stream's end, padding known clean, packet-start bitmap and
+ * plans rebuilt, the nocase fold stale.  dst gets metadata, meta[s] = src.meta[first_packet_s], and keeps the records kmpgpu_stream[n_streams]
+ * and the map kmpgpu_stream_pos[n_pkts of src] in device buffers it owns; kmpgpu_streams_read / kmpgpu_stream_map_read copy elements
+ * [first, first + n) to out, ranges and errors as kmpgpu_flows_read ("no streams": KMPGPU_ESTATE).  Whatever replaces or releases dst's
+ * arena drops the stream state; the buffers stay for the next build.  *n_streams (may be NULL) = the number of streams.  n_pkts == 0: dst
+ * is left without an arena, the call returns KMPGPU_OK with *n_streams = 0, and empty records exist.
+ * Untouched: src is not written, and every output of it is bit-identical before and after.  The source is whatever src scans now (loaded,
+ * attached, extracted, repacked or kept in place).  Of its arena no byte outside a member's slot is read: the gather loads aligned 16-byte
+ * units that hold a byte of a member, so a borrowed arena owes nothing behind its last slot.
+ * A STREAM IS A PAYLOAD OF ITS OWN.  dst scans it under dst's own patterns, flags, windows and E rule.  Under the default strlen rule its
+ * text ends at the stream's first 0x00, wherever in the connection that lies.  Windows count from the stream's first byte: on a stream they
+ * mean "offset in the connection's direction".  With KMPGPU_OPT_WHOLE_PAYLOAD on both contexts the stream holds every match src holds
+ * inside the cut, plus the ones that cross member boundaries.
+ * THE FLOW IDENTITY.  After kmpgpu_load_streams(dst, src, ...), kmpgpu_flows_build(dst, flags) with the flag src's flows were built with
+ * gives flow_of_dst[s] == stream[s].flow for every s and the same n_flows: flows are numbered by their first payload, dst's order is
+ * (flow, dir), and every flow has a dir-0 stream whose metadata is the flow's `first`.  So kmpgpu_scan_flows(dst, KMPGPU_ALERT_RULES,
+ * KMPGPU_FLOW_SCOPE_FLOW, ...) is the reassembled flow-scope verdict in src's flow numbering; there is no further fold call.
+ * Ordering: synchronous.  Waits for dst's stream and for src's, as kmpgpu_load_seams does, and works on dst's stream; the scratch is the
+ * one dst keeps for kmpgpu_load_frames (grown to 40 bytes per source payload for the scans, 24 for the gather's piece records) and the
+ * sort buffer of kmpgpu_load_seams.  The host reads device totals twice: {member bytes, n_streams}, which size the records, then the packed
+ * arena's bytes, which follow from the cut lengths.
+ * Errors: dst == src, a NULL context, depth outside 1 .. 2^30, contexts on different devices: KMPGPU_EINVAL; src without built flows:
+ * KMPGPU_ESTATE ("no flows"); either context between kmpgpu_load_frames_begin and _finish: KMPGPU_ESTATE; after each of these dst keeps its
+ * arena.  After an allocation failure (KMPGPU_ENOMEM / KMPGPU_EHIP) dst is without an arena and both contexts stay usable.
+ * kmpgpu_last_timing(dst): kernel_ms from the keys kernel to the gather's end (the host's two reads lie inside), launches = 10 (keys, the
+ * sort counted as one, stream scan, stream totals, heads, records, the two slot scan kernels, index, gather).  Under kmpgpu_profile_begin on
+ * dst the entries are keys, sort, stream scan + totals, heads + records + the two slot scan kernels, index, gather.
+ * Every existing call keeps its outputs, launches and buffers, with or without these calls having run.
+ * Not done: capture order, not sequence numbers; a retransmitted segment appears twice; no TCP state, no timeouts; one cut
+ * per stream; streams are per context, not across shards or GPUs. */
+#define KMPGPU_STREAM_DEPTH_MAX (1u << 30)
+typedef struct kmpgpu_stream {        /* 48 bytes */
+    uint64_t first_packet, last_packet;   /* src payload indices of the stream's first and last member */
+    uint64_t n_packets;                   /* members */
+    uint64_t bytes;                       /* sum of the members' L_k, before the depth cut */
+    uint32_t flow, dir;                   /* src.flow_of[first_packet], dir() as kmpgpu_load_seams defines it */
+    uint32_t len, reserved;               /* min(bytes, depth): the stream payload's length in dst; 0 */
+} kmpgpu_stream;
+typedef struct kmpgpu_stream_pos {    /* 16 bytes, one per SOURCE payload */
+    uint32_t stream, reserved;            /* the stream payload k belongs to; 0 */
+    uint64_t pos;                         /* sum of L_j over the members j < k of that stream: where k's first byte lies, before the cut */
+} kmpgpu_stream_pos;
+int  kmpgpu_load_streams(kmpgpu_ctx *dst, kmpgpu_ctx *src, uint32_t depth, uint64_t *n_streams /* or NULL */);
+int  kmpgpu_streams_read(kmpgpu_ctx *dst, kmpgpu_stream *out, uint64_t first, uint64_t n);
+int  kmpgpu_stream_map_read(kmpgpu_ctx *dst, kmpgpu_stream_pos *out, uint64_t first, uint64_t n);
+
 /* Fill a device arena with the synthetic payloads of kmp_synth.h (benchmark input S1/S2):
  * packet ids first_pkt_id .. first_pkt_id + n_pkts - 1 at the slots of the given device index. */
 int  kmpgpu_synth_fill(kmpgpu_ctx *ctx, void *d_arena, const void *d_pkt_off, const void *d_pkt_len,

@@ -102,6 +102,19 @@
  * stderr and exit 1, before any GPU work: any other value; the variable together with KMPGPU_OFFSETS_FILE (offsets in decoded payloads
  * are not mapped back), KMPGPU_EXPORT_FILE or KMPGPU_FLOW_SEAMS; the variable with none of the three row outputs.
  *
+ * KMPGPU_FLOW_STREAMS=<depth>, together with KMPGPU_FLOW_ALERTS_FILE: the flow alerts are decided on the reassembled streams.  A second
+ * context on the shard's device gets the same tables as the shard's (upload_tables; the windows too: on a stream they mean "offset in the
+ * connection's direction") and the payloads of every flow direction concatenated in capture order and cut to <depth> bytes
+ * (kmpgpu_load_streams), its flows are built with the same flag (kmpgpu_flows_build: the flow numbers are the capture's), and the file
+ * holds its kmpgpu_scan_flows(KMPGPU_ALERT_RULES, KMPGPU_FLOW_SCOPE_FLOW): a content however it was cut into segments, chains, byte
+ * tests and expressions across segments.  <depth> is a decimal number in 1..1073741824, or one with k or m behind it (64k, 1m).
+ * KMPGPU_STREAMS_FILE=<path>, together with KMPGPU_FLOW_STREAMS: one line per stream,
+ * "stream,flow,dir,first_payload,last_payload,payloads,bytes,kept".  Refused with a message on stderr and exit 1, before any GPU work:
+ * KMPGPU_FLOW_STREAMS without KMPGPU_FLOW_ALERTS_FILE, a value that is no depth, more than one shard, the variable together with
+ * KMPGPU_FLOW_SEAMS (streams hold everything seams hold, up to the cut) or with KMPGPU_DECODE (decoded streams are not wired here; at the
+ * library, kmpgpu_load_decoded over the stream context does it), KMPGPU_STREAMS_FILE without KMPGPU_FLOW_STREAMS or on a path that cannot
+ * be written.  stdout is what it is without the variables.
+ *
  * KMPGPU_NOCASE=1: every pattern matches case-insensitively (ASCII letters; kmpgpu_set_patterns_flags), in the counts and in
  * the offsets file alike; the report prints every token as written in the pattern file.
  *
@@ -118,6 +131,7 @@
 #include "kmphost.h"
 #include "kmp_cli_common.h"
 #include "kmp_cli_decode.h"
+#include "kmp_cli_streams.h"
 
 #ifndef KMP_CLI_OPENMP_FORM
 #define KMP_CLI_OPENMP_FORM 0
@@ -142,6 +156,8 @@ typedef struct cli_options {
     int flows_directed;                     /* KMPGPU_FLOWS_DIRECTED */
     uint32_t flow_seams;                    /* KMPGPU_FLOW_SEAMS: the reach, 0 without the variable */
     int decode;                             /* KMPGPU_DECODE: KMP_CLI_DECODE_* */
+    uint32_t flow_streams;                  /* KMPGPU_FLOW_STREAMS: the depth, 0 without the variable */
+    const char *streams_path;               /* KMPGPU_STREAMS_FILE */
     int want_meta;                          /* header predicates or flows: the payloads' header fields go to the device */
     /* what every shard's context gets behind its patterns, in this order and before any rule is set */
     uint32_t *win_first, *win_last;         /* KMPGPU_WINDOWS_FILE (NULL: none) */
@@ -379,6 +395,34 @@ static void load_options(int argc, char *argv[], cli_options *opt)
             exit(1);
         }
     }
+    /* streams: they change what the flow alerts file holds, and write a file of their own */
+    const char *streams_env = env_path("KMPGPU_FLOW_STREAMS");
+    opt->streams_path = env_path("KMPGPU_STREAMS_FILE");
+    if (streams_env) {
+        if (!opt->flow_alerts_path) {
+            fprintf(stderr, "KMPGPU_FLOW_STREAMS goes together with KMPGPU_FLOW_ALERTS_FILE: it is not set\n");
+            exit(1);
+        }
+        if (!kmp_cli_parse_depth(streams_env, &opt->flow_streams)) {
+            fprintf(stderr, "KMPGPU_FLOW_STREAMS is \"%s\": a depth of 1..%u bytes is needed\n", streams_env, KMP_CLI_STREAM_DEPTH_MAX);
+            exit(1);
+        }
+        if (opt->flow_seams) {
+            fprintf(stderr, "KMPGPU_FLOW_STREAMS does not go together with KMPGPU_FLOW_SEAMS: streams hold everything seams hold, up to the cut\n");
+            exit(1);
+        }
+        if (opt->decode) {
+            fprintf(stderr, "KMPGPU_FLOW_STREAMS does not go together with KMPGPU_DECODE: decoded streams are not wired in this program\n");
+            exit(1);
+        }
+    }
+    if (opt->streams_path) {
+        if (!opt->flow_streams) {
+            fprintf(stderr, "KMPGPU_STREAMS_FILE goes together with KMPGPU_FLOW_STREAMS: it is not set\n");
+            exit(1);
+        }
+        probe_writable("KMPGPU_STREAMS_FILE", opt->streams_path);
+    }
     opt->want_meta = opt->headers.n || opt->flows_path || opt->flow_alerts_path;
     /* the export starts as a capture without frames: a path that cannot be written ends the run here */
     if (opt->export_path && kmp_write_udp_pcap_part(opt->export_path, 0, NULL, NULL, NULL, 0, 0)) {
@@ -592,6 +636,41 @@ static void write_alerts(const char *path, const cli_options *opt, cli_run *run,
     fclose(fp);
 }
 
+/* KMPGPU_FLOW_STREAMS: next to the shard, whose flows are built, a context with the same tables and rules that holds the shard's flow
+ * directions reassembled and groups them into the same n_flows flows; KMPGPU_STREAMS_FILE: its stream records, read back in pieces. */
+#define STREAM_PIECE 16384u
+static kmpgpu_ctx *stream_context(const cli_options *opt, kmpgpu_ctx *src, uint64_t n_flows)
+{
+    static kmpgpu_stream piece[STREAM_PIECE];
+    kmpgpu_ctx *st = NULL;
+    uint64_t n_streams = 0, nf = 0;
+    if (kmpgpu_init(&st, kmpgpu_device_of(src))) die_gpu("kmpgpu_init");
+    const char *failed = upload_tables(st, opt);
+    if (failed) die_gpu(failed);
+    if (kmpgpu_load_streams(st, src, opt->flow_streams, &n_streams)) die_gpu("kmpgpu_load_streams");
+    if (kmpgpu_flows_build(st, opt->flows_directed ? KMPGPU_FLOW_DIRECTED : 0u, &nf, NULL)) die_gpu("kmpgpu_flows_build");
+    if (nf != n_flows) {
+        fprintf(stderr, "KMPGPU_FLOW_STREAMS: the streams group into %llu flows, the capture into %llu\n", (unsigned long long)nf, (unsigned long long)n_flows);
+        exit(1);
+    }
+    if (opt->rules.n && kmpgpu_set_rules(st, opt->rules.off, opt->rules.terms, opt->rules.n)) die_gpu("kmpgpu_set_rules");
+    if (opt->streams_path) {
+        FILE *fp = fopen(opt->streams_path, "w");
+        if (!fp) { perror("KMPGPU_STREAMS_FILE"); exit(1); }
+        for (uint64_t first = 0; first < n_streams; first += STREAM_PIECE) {
+            const uint64_t n = n_streams - first < STREAM_PIECE ? n_streams - first : STREAM_PIECE;
+            if (kmpgpu_streams_read(st, piece, first, n)) die_gpu("kmpgpu_streams_read");
+            for (uint64_t i = 0; i < n; i++) {
+                const kmpgpu_stream *s = &piece[i];
+                fprintf(fp, "%llu,%u,%u,%llu,%llu,%llu,%llu,%u\n", (unsigned long long)(first + i), s->flow, s->dir, (unsigned long long)s->first_packet,
+                        (unsigned long long)s->last_packet, (unsigned long long)s->n_packets, (unsigned long long)s->bytes, s->len);
+            }
+        }
+        fclose(fp);
+    }
+    return st;
+}
+
 /* KMPGPU_FLOWS_FILE, KMPGPU_FLOW_ALERTS_FILE: the one shard's payloads grouped on the device, the records read back in pieces; then the
  * rules per flow, whose rows come back as a bit matrix of rules x flows (a rules file without rules leaves the file empty). */
 #define FLOW_PIECE 16384u
@@ -630,10 +709,14 @@ static void write_flows(const cli_options *opt, cli_run *run)
         }
         set_rules_once(opt, run);
         const uint64_t Wf = (n_flows + 63) / 64, nr = opt->rules.n;
+        kmpgpu_ctx *st = opt->flow_streams ? stream_context(opt, ctx, n_flows) : NULL;
         if (nr && n_flows) {
             uint64_t *hits = (uint64_t *)calloc((size_t)(nr * Wf), sizeof(uint64_t));
             if (!hits) die_gpu("KMPGPU_FLOW_ALERTS_FILE: out of memory");
-            if (opt->flow_seams) {
+            if (st) {
+                /* KMPGPU_FLOW_STREAMS: the rules per flow over the reassembled streams, whose flows are the capture's */
+                if (kmpgpu_scan_flows(st, KMPGPU_ALERT_RULES, KMPGPU_FLOW_SCOPE_FLOW, NULL, NULL, hits, NULL, NULL)) die_gpu("kmpgpu_scan_flows");
+            } else if (opt->flow_seams) {
                 /* KMPGPU_FLOW_SEAMS: the seams in a context of their own, next to the shard, under the same patterns */
                 kmpgpu_ctx *sm = NULL;
                 if (kmpgpu_init(&sm, run->job[0].device)) die_gpu("kmpgpu_init");
@@ -647,6 +730,7 @@ static void write_flows(const cli_options *opt, cli_run *run)
                     if (hits[r * Wf + (f >> 6)] >> (f & 63) & 1u) fprintf(fp, "%llu,%llu\n", (unsigned long long)f, (unsigned long long)r);
             free(hits);
         }
+        if (st) kmpgpu_destroy(st);
         fclose(fp);
     }
 }

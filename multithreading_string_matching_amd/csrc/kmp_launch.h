@@ -1,5 +1,5 @@
 /* kmp_launch.h -- launch entry points of kmp_scan_*.hip / kmp_prep.hip / kmp_fold.hip / kmp_marks.hip / kmp_rules.hip / kmp_relations.hip /
- * kmp_chains.hip / kmp_headers.hip / kmp_bytetests.hip / kmp_regex.hip / kmp_select.hip / kmp_decode.hip / kmp_alerts.hip / kmp_flows.hip / kmp_seams.hip, used
+ * kmp_chains.hip / kmp_headers.hip / kmp_bytetests.hip / kmp_regex.hip / kmp_select.hip / kmp_decode.hip / kmp_alerts.hip / kmp_flows.hip / kmp_seams.hip / kmp_streams.hip, used
  * by the C-ABI layer (kmpgpu.hip), which alone decides what is launched; the tables kmp_launch_scan_multi takes come from kmp_tables.h. */
 #ifndef KMP_LAUNCH_H
 #define KMP_LAUNCH_H
@@ -256,5 +256,27 @@ hipError_t kmp_launch_seam_index(const uint64_t *src_off, const uint32_t *src_le
                                  void *recs, hipStream_t st);
 hipError_t kmp_launch_seam_gather(const uint8_t *src_arena, const uint64_t *pkt_off, const void *recs, uint64_t n_seams, uint64_t total_bytes,
                                   uint8_t *arena, bool nontemporal, hipStream_t st);
+
+/* kmp_streams.hip (kmpgpu_load_streams): the payloads of every (flow, direction) of such an index concatenated in capture order, cut to
+ * `depth` bytes, into a packed arena.  After kmp_launch_seam_keys and kmp_launch_seam_sort, whose sort_buf is kept up to _index, in the
+ * order they are launched:
+ * _phase1 (2 kernels): over the sorted positions, the heads and the exclusive sum of the members' lengths, in ws (kmp_stream_ws_bytes(n)
+ *   bytes, kept up to _index); totals[0] = bytes of all members, totals[1] = n_streams.
+ * _records (4 kernels): where every stream starts in the sorted order, the kmpgpu_stream records recs[n_streams], meta[n_streams] (16-byte
+ *   aligned), and the scan of the slot sizes through kmp_launch_repack_phase1; totals[0] = bytes of the packed streams.
+ * _index: pkt_off[n_streams], pkt_len[n_streams], the kmpgpu_stream_pos entries map[n] by source payload, and pieces (24 n bytes, 16-byte
+ *   aligned): per sorted position 16 bytes {source address, bytes in front of the cut, 0}, then the 8-byte destination addresses, ascending.
+ * _gather: arena[0, total_bytes): every slot whole, 0x00 behind its stream's end.  Of src_arena only aligned 16-byte units that hold a byte
+ *   of a member are read (the source's slots are 16-byte aligned: the layout contract of kmpgpu.h). */
+size_t kmp_stream_ws_bytes(uint64_t n);
+hipError_t kmp_launch_stream_phase1(const uint32_t *pkt_len, uint64_t n, const uint8_t *sort_buf, uint8_t *ws, unsigned long long *totals,
+                                    hipStream_t st);
+hipError_t kmp_launch_stream_records(const void *src_meta, uint64_t n, uint64_t total, uint64_t n_streams, uint32_t depth,
+                                     const uint8_t *sort_buf, uint8_t *ws, void *recs, void *meta, unsigned long long *totals, hipStream_t st);
+hipError_t kmp_launch_stream_index(const uint64_t *src_off, const uint32_t *src_len, uint64_t n, uint64_t total, uint64_t n_streams,
+                                   const uint8_t *sort_buf, uint8_t *ws, uint64_t *pkt_off, uint32_t *pkt_len, void *map, void *pieces,
+                                   hipStream_t st);
+hipError_t kmp_launch_stream_gather(const uint8_t *src_arena, const void *pieces, uint64_t n, uint64_t total_bytes, uint8_t *arena,
+                                    bool nontemporal, hipStream_t st);
 
 #endif

@@ -238,6 +238,13 @@ struct kmpgpu_ctx {
     uint64_t            seams_cap = 0, seam_flow_cap = 0, seam_sort_cap = 0;
     uint64_t            n_seams = 0, seam_src = 0, seam_gen = 0;
     bool                seams_valid = false;
+    /* kmpgpu_load_streams, in dst: the kmpgpu_stream records [n_streams] and the kmpgpu_stream_pos entries [n_stream_map], one per payload
+     * of the source.  streams_valid: they exist, and the arena is the one they describe (drop_streams) */
+    kmpgpu_stream      *d_streams = nullptr;
+    kmpgpu_stream_pos  *d_stream_map = nullptr;
+    uint64_t            streams_cap = 0, stream_map_cap = 0;
+    uint64_t            n_streams = 0, n_stream_map = 0;
+    bool                streams_valid = false;
     /* the patterns as they were set, one record {length, flags, bytes} each: what kmpgpu_scan_flows_seams compares between two contexts */
     std::vector<uint8_t> pat_sig;
 
@@ -446,6 +453,13 @@ void drop_seams(kmpgpu_ctx *c)
     c->n_seams = 0;
 }
 
+/* the stream records and the map go with the arena they describe; their buffers are kept for the next build */
+void drop_streams(kmpgpu_ctx *c)
+{
+    c->streams_valid = false;
+    c->n_streams = c->n_stream_map = 0;
+}
+
 /* the patterns and all that is built on them */
 void release_patterns(kmpgpu_ctx *c)
 {
@@ -502,6 +516,7 @@ void release_arena(kmpgpu_ctx *c, bool keep_buffers = false)
     c->has_meta = false;                              /* the metadata described its payloads (the buffer is kept too) */
     drop_flows(c);                                    /* ... and the flows grouped them */
     drop_seams(c);                                    /* ... and the seam list said which of src's payloads they join */
+    drop_streams(c);                                  /* ... and the stream records which of them each stream is made of */
 }
 
 /* Host ranges pinned through kmpgpu_host_register.  One copy must not straddle two registrations (the runtime refuses it), and a
@@ -558,6 +573,8 @@ void release_pass_buffers(kmpgpu_ctx *c)
     drop_flows(c);
     free_buffer(&c->d_seams, &c->seams_cap); free_buffer(&c->d_seam_flow, &c->seam_flow_cap); free_buffer(&c->d_seam_sort, &c->seam_sort_cap);
     drop_seams(c);
+    free_buffer(&c->d_streams, &c->streams_cap); free_buffer(&c->d_stream_map, &c->stream_map_cap);
+    drop_streams(c);
     c->alerts_valid = false;
     c->bitmap_live = false; c->plan_waves = c->uplan_units = 0; c->fold_stale = true;
 }
@@ -1692,6 +1709,124 @@ int kmpgpu_seams_read(kmpgpu_ctx *c, kmpgpu_seam *out, uint64_t first, uint64_t 
     HIP_TRY(hipMemcpyAsync(out, c->d_seams + first, (size_t)n * sizeof(kmpgpu_seam), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return KMPGPU_OK;
+}
+
+int kmpgpu_load_streams(kmpgpu_ctx *dst, kmpgpu_ctx *src, uint32_t depth, uint64_t *n_streams)
+{
+    const char *who = "kmpgpu_load_streams";
+    if (n_streams) *n_streams = 0;
+    if (!dst || !src) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
+    if (dst == src) return fail(KMPGPU_EINVAL, "%s: dst and src are the same context (a context holds one arena)", who);
+    if (depth < 1u || depth > KMPGPU_STREAM_DEPTH_MAX)
+        return fail(KMPGPU_EINVAL, "%s: depth %u is not in 1..%u", who, depth, KMPGPU_STREAM_DEPTH_MAX);
+    if (dst->device != src->device)
+        return fail(KMPGPU_EINVAL, "%s: the contexts sit on devices %d and %d (streams across devices do not exist)", who, dst->device, src->device);
+    if (dst->fr_pending || src->fr_pending) return fail(KMPGPU_ESTATE, "%s: %s sits between kmpgpu_load_frames_begin and _finish", who, dst->fr_pending ? "dst" : "src");
+    if (!src->flows_valid) return fail(KMPGPU_ESTATE, "%s: no flows (no kmpgpu_flows_build since the arena or its metadata were set)", who);
+    HIP_TRY(hipSetDevice(dst->device));
+    HIP_TRY(hipStreamSynchronize(dst->stream));           /* the passes over the arena that is about to be replaced */
+    HIP_TRY(hipStreamSynchronize(src->stream));           /* whatever src's stream still does with its arena */
+    kmpgpu_ctx *c = dst;
+    c->last = kmpgpu_timing{};
+    const uint64_t n = src->n_pkts;
+    /* from here on dst's earlier arena is gone, whatever happens */
+    release_arena(c, /* keep_buffers = */ true);
+    if (n == 0) { c->streams_valid = true; return KMPGPU_OK; }       /* (no stream, no map entry) */
+
+    /* the scratch of kmpgpu_load_frames (fr_ws the scans, fr_src the gather's pieces) and the sort buffer of kmpgpu_load_seams */
+    const uint64_t sort_bytes = kmp_seam_sort_bytes(n, src->n_flows);
+    if (!sort_bytes) return fail(KMPGPU_EHIP, "%s: the sort of %llu payloads could not be sized", who, (unsigned long long)n);
+    hipError_t e = grow_buffer(&c->fr_ws, &c->fr_ws_cap, (uint64_t)kmp_stream_ws_bytes(n), EIGHTH);
+    if (e == hipSuccess && !c->fr_tot) e = hipMalloc(&c->fr_tot, 2 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = grow_buffer(&c->d_seam_sort, &c->seam_sort_cap, sort_bytes, EIGHTH);
+    if (e == hipSuccess) e = grow_buffer(&c->fr_src, &c->fr_src_cap, 3 * n, EIGHTH);              /* 24 bytes per source payload */
+    if (e == hipSuccess) e = grow_buffer(&c->d_stream_map, &c->stream_map_cap, n, EIGHTH);
+    if (e != hipSuccess) return alloc_fail(e, "%s: the sort's and the scans' buffers (%llu payloads) could not be allocated", who, (unsigned long long)n);
+    hipEvent_t e1;
+    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_seam_keys(src->d_meta, src->d_flow_of, src->d_flow_recs, n, c->d_seam_sort, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_seam_sort(n, src->n_flows, c->d_seam_sort, (size_t)c->seam_sort_cap, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_stream_phase1(src->d_len, n, c->d_seam_sort, c->fr_ws, c->fr_tot, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(hipMemcpyAsync(c->h_small, c->fr_tot, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));         /* (pinned: no staging) */
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    unsigned long long tot[2] = {0, 0};
+    memcpy(tot, c->h_small, sizeof tot);
+    const uint64_t total = tot[0], ns = tot[1];                              /* bytes of all members; streams, at least one */
+    e = grow_buffer(&c->d_streams, &c->streams_cap, ns, EIGHTH);
+    if (e == hipSuccess) e = grow_buffer(&c->d_meta, &c->meta_cap, ns, EIGHTH);
+    if (e != hipSuccess) return alloc_fail(e, "%s: the records of %llu streams could not be allocated", who, (unsigned long long)ns);
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_stream_records(src->d_meta, n, total, ns, depth, c->d_seam_sort, c->fr_ws, c->d_streams, c->d_meta, c->fr_tot, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    /* the second read: the arena's size follows from the cut lengths, which follow from the first read's n_streams */
+    HIP_TRY(hipMemcpyAsync(c->h_small, c->fr_tot, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    memcpy(tot, c->h_small, sizeof tot);
+    const uint64_t arena_bytes = tot[0] + 64;
+    e = ensure_owned_arena(c, arena_bytes, ns, EIGHTH);                      /* (on failure dst is empty and usable) */
+    if (e != hipSuccess)
+        return alloc_fail(e, "%s: an arena of %llu bytes / %llu streams could not be allocated", who, (unsigned long long)(arena_bytes + arena_bytes / 8),
+                          (unsigned long long)(ns + ns / 8));
+    HIP_TRY(hipMemsetAsync(c->owned_arena + tot[0], 0, 64, c->stream));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_stream_index(src->d_off, src->d_len, n, total, ns, c->d_seam_sort, c->fr_ws, c->owned_off, c->owned_len, c->d_stream_map,
+                                    c->fr_src, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_stream_gather(src->d_arena, c->fr_src, n, tot[0], c->owned_arena, c->nontemporal != 0, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    IndexFacts f;
+    int rc = validate_index(c, who, c->owned_off, c->owned_len, ns, arena_bytes, &f);
+    /* kmp_stream_gather_kernel writes every slot whole: stream, then 0x00 up to the slot's end */
+    if (!rc) rc = install_arena(c, c->owned_arena, c->owned_off, c->owned_len, arena_bytes, ns, f, /* wrote_padding = */ true);
+    if (rc) { release_arena(c, true); return rc; }
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
+    c->last.kernel_ms = ms; c->last.launches = 10;
+    c->has_meta = true;
+    c->n_streams = ns; c->n_stream_map = n; c->streams_valid = true;
+    if (n_streams) *n_streams = ns;
+    return KMPGPU_OK;
+}
+
+namespace {
+
+/* what kmpgpu_streams_read and kmpgpu_stream_map_read share: flows_read_range for the stream state */
+int streams_read_range(kmpgpu_ctx *c, const char *who, void *out, const void *src, size_t size, uint64_t first, uint64_t n, uint64_t total)
+{
+    if (!c) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
+    if (!c->streams_valid) return fail(KMPGPU_ESTATE, "%s: no streams (no kmpgpu_load_streams since the arena was set)", who);
+    if (first > total || n > total - first)
+        return fail(KMPGPU_EINVAL, "%s: elements [%llu, +%llu) leave the %llu there are", who, (unsigned long long)first, (unsigned long long)n,
+                    (unsigned long long)total);
+    if (n == 0) return KMPGPU_OK;
+    if (!out) return fail(KMPGPU_EINVAL, "%s: out is NULL", who);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(out, (const uint8_t *)src + first * size, (size_t)n * size, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return KMPGPU_OK;
+}
+
+}  // namespace
+
+int kmpgpu_streams_read(kmpgpu_ctx *c, kmpgpu_stream *out, uint64_t first, uint64_t n)
+{
+    static_assert(sizeof(kmpgpu_stream) == 48, "kmpgpu_stream is the 48-byte record of kmpgpu.h");
+    return streams_read_range(c, "kmpgpu_streams_read", out, c ? c->d_streams : nullptr, sizeof(kmpgpu_stream), first, n, c ? c->n_streams : 0);
+}
+
+int kmpgpu_stream_map_read(kmpgpu_ctx *c, kmpgpu_stream_pos *out, uint64_t first, uint64_t n)
+{
+    static_assert(sizeof(kmpgpu_stream_pos) == 16, "kmpgpu_stream_pos is the 16-byte record of kmpgpu.h");
+    return streams_read_range(c, "kmpgpu_stream_map_read", out, c ? c->d_stream_map : nullptr, sizeof(kmpgpu_stream_pos), first, n,
+                              c ? c->n_stream_map : 0);
 }
 
 int kmpgpu_scan_enqueue(kmpgpu_ctx *c, void *d_counts_out)

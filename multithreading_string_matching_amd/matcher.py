@@ -38,6 +38,10 @@ FLOW_DTYPE = np.dtype([("first_packet", "<u8"), ("last_packet", "<u8"), ("n_pack
 DECODE_PERCENT = 1      # KMPGPU_DECODE_PERCENT: the transform of load_decoded
 DECODE_PLUS, DECODE_ONLY_CHANGED = 1, 2     # KMPGPU_DECODE_*: its flags
 SEAM_DTYPE = np.dtype([("prev", "<u8"), ("next", "<u8"), ("tail_len", "<u4"), ("head_len", "<u4")])      # kmpgpu_seam, 24 bytes
+STREAM_DEPTH_MAX = 1 << 30     # KMPGPU_STREAM_DEPTH_MAX
+STREAM_DTYPE = np.dtype([("first_packet", "<u8"), ("last_packet", "<u8"), ("n_packets", "<u8"), ("bytes", "<u8"), ("flow", "<u4"),
+                         ("dir", "<u4"), ("len", "<u4"), ("reserved", "<u4")])      # kmpgpu_stream, 48 bytes
+STREAM_POS_DTYPE = np.dtype([("stream", "<u4"), ("reserved", "<u4"), ("pos", "<u8")])      # kmpgpu_stream_pos, 16 bytes
 
 
 def device_count() -> int:
@@ -69,6 +73,40 @@ def selected_indices(words: np.ndarray, n_src: int) -> np.ndarray:
     words = np.ascontiguousarray(words, dtype=np.uint64)
     bits = np.unpackbits(words.view(np.uint8), bitorder="little")[:n_src]
     return np.flatnonzero(bits).astype(np.uint64)
+
+
+def stream_locate(stream_map: np.ndarray, stream, offset) -> Tuple[np.ndarray, np.ndarray]:
+    """Where the bytes at ``offset`` of the stream payloads ``stream`` come from: (payload, offset_in_payload) in the source of
+    load_streams, from its stream_map() (STREAM_POS_DTYPE, one entry per source payload).  Vectorised over equally shaped arrays, so the
+    scan_offsets records of a stream context map back to the capture's payloads.  The member is the last one of the stream that starts
+    at or before the offset -- of several that start there (empty members in front of it), the one that has the byte.  Offsets are inside
+    the stream's len: a byte behind the cut does not occur.  No device needed."""
+    stream_map = np.asarray(stream_map)
+    if stream_map.dtype != STREAM_POS_DTYPE:
+        raise ValueError(f"stream_map: {stream_map.dtype}; STREAM_POS_DTYPE is needed")
+    stream = np.asarray(stream, dtype=np.uint64)
+    offset = np.asarray(offset, dtype=np.uint64)
+    if stream.shape != offset.shape:
+        raise ValueError(f"stream{list(stream.shape)} and offset{list(offset.shape)} differ in shape")
+    if len(stream_map) == 0:
+        if stream.size:
+            raise ValueError("stream_locate: stream_map is empty")
+        return np.zeros(stream.shape, np.uint64), np.zeros(stream.shape, np.uint64)
+    # members in (stream, capture order): pos ascends inside a stream.  Streams are dense (each has a member), so with every stream's
+    # positions moved behind those of the stream before it, one ascending key serves one searchsorted for all offsets
+    order = np.argsort(stream_map["stream"], kind="stable")
+    s_sorted = stream_map["stream"][order].astype(np.int64)
+    p_sorted = stream_map["pos"][order]
+    n_streams = int(s_sorted[-1]) + 1
+    if stream.size and int(stream.max()) >= n_streams:
+        raise ValueError(f"stream_locate: stream {int(stream.max())} of {n_streams}")
+    last_pos = np.zeros(n_streams, dtype=np.uint64)
+    last_pos[s_sorted] = p_sorted                                            # (ascending: the last write is the stream's last member)
+    base = np.concatenate(([0], np.cumsum(last_pos + np.uint64(1))[:-1])).astype(np.uint64)
+    key = base[s_sorted] + p_sorted
+    st = stream.ravel().astype(np.int64)
+    j = np.searchsorted(key, base[st] + np.minimum(offset.ravel(), last_pos[st]), side="right") - 1
+    return order[j].astype(np.uint64).reshape(stream.shape), (offset.ravel() - p_sorted[j]).reshape(stream.shape)
 
 
 class GpuMatcher:
@@ -695,6 +733,36 @@ class GpuMatcher:
         def call(row_counts, any_w, hit_w, counts, t):
             return self._g.kmpgpu_scan_flows_seams(self._ctx, seams._ctx, row_counts, any_w, hit_w, counts, t)
         return self._scan_flow_rows(call, "kmpgpu_scan_flows_seams", len(self.rules), hits)
+
+    # -- flow streams ------------------------------------------------------------------------------
+    def load_streams(self, src: "GpuMatcher", depth: int = 1 << 20) -> int:
+        """Make this matcher's arena the reassembled streams of ``src``, whose flows are built (kmpgpu_load_streams): the payloads of
+        every (flow, direction) concatenated in capture order and cut to ``depth`` bytes, as one payload each, numbered by
+        flow << 1 | dir.  Every scan of this matcher then sees a content however it was cut into segments; build_flows() here, with the
+        flag ``src``'s flows were built with, reproduces ``src``'s flow numbering.  Patterns, rules, windows and options of this matcher
+        stay.  Returns the number of streams."""
+        n = C.c_uint64()
+        gpu_check(self._g.kmpgpu_load_streams(self._ctx, src._ctx, int(depth), C.byref(n)), "kmpgpu_load_streams")
+        self._keep = None
+        self._n_streams = int(n.value)
+        self._n_stream_map = src.arena_info()[0]
+        return self._n_streams
+
+    def _stream_read(self, fn, name: str, total: str, dtype, first: int, n: Optional[int]) -> np.ndarray:
+        gpu_check(fn(self._ctx, None, 0, 0), name)                           # (the library knows when the records were dropped)
+        n = getattr(self, total, 0) - int(first) if n is None else int(n)
+        out = np.zeros(max(n, 1), dtype=dtype)
+        gpu_check(fn(self._ctx, out.ctypes.data, int(first), max(n, 0)), name)
+        return out[: max(n, 0)]
+
+    def streams(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """Records [first, first + n) of the streams (kmpgpu_streams_read) as a STREAM_DTYPE array; n None: all from ``first`` on."""
+        return self._stream_read(self._g.kmpgpu_streams_read, "kmpgpu_streams_read", "_n_streams", STREAM_DTYPE, first, n)
+
+    def stream_map(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """Entries [first, first + n) of the map (kmpgpu_stream_map_read), one per payload of the source, as a STREAM_POS_DTYPE array;
+        n None: all from ``first`` on.  stream_locate() maps offsets in streams back through it."""
+        return self._stream_read(self._g.kmpgpu_stream_map_read, "kmpgpu_stream_map_read", "_n_stream_map", STREAM_POS_DTYPE, first, n)
 
     def select_flows(self, bits, device: bool = False):
         """The payloads of the chosen flows as a payload bitmap (kmpgpu_flows_select): bits is bool[n_flows] or uint64[ceil(n_flows / 64)]
