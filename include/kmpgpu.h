@@ -164,7 +164,7 @@ int  kmpgpu_set_patterns_flags(kmpgpu_ctx *ctx, const uint8_t *const *pat, const
 
 /* Replaces array_of_payloads, serial.c:99,124-136: upload a host arena + index (H2D copy,
  * device copy owned by the context).  Contract: pkt_off[k] % 16 == 0 and
- * pkt_off[k] + max(16, round_up(pkt_len[k], 16)) <= arena_bytes for every k (checked): every
+ * pkt_off[k] + max(16, round_up(pkt_len[k], 16)) <= arena_bytes and pkt_len[k] <= 2^30 for every k (checked): every
  * payload, also an empty one, owns at least one readable 16-byte slot.  The bytes between a payload's
  * end and the end of its slot may hold anything; when they are 0x00 (as kmp_arena builds them -- checked
  * at load time, and cleared in the copy kmpgpu_load_arena makes) the streaming kernels take a payload's

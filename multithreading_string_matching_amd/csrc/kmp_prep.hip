@@ -215,7 +215,7 @@ kmp_reduce_kernel(const unsigned long long *__restrict__ partials, uint32_t bloc
 }
 
 /* Layout contract of kmpgpu.h for a device-resident index: err[0] |= 1 misaligned, |= 2 out of
- * bounds, |= 4 length >= 2^30; err[1] & 1: the arena is NOT uniform-stride, err[1] & 2: slots are NOT
+ * bounds, |= 4 length > 2^30; err[1] & 1: the arena is NOT uniform-stride, err[1] & 2: slots are NOT
  * packed back to back; info[0] += sum(len),
  * info[1..4] = offset of payload 0, stride (offset 1 - offset 0), length of payload 0, end of the last slot. */
 __global__ void __launch_bounds__(KMP_BLOCK_THREADS)
@@ -234,7 +234,7 @@ kmp_validate_index_kernel(const uint64_t *__restrict__ pkt_off, const uint32_t *
         const uint64_t o = pkt_off[k];
         const uint64_t l = pkt_len[k];
         if (o & 15ull) e |= 1u;
-        if (l >= (1ull << 30)) e |= 4u;
+        if (l > (1ull << 30)) e |= 4u;                       /* (2^30 itself: a stream cut at KMPGPU_STREAM_DEPTH_MAX) */
         const uint64_t l16 = (l + 15ull) & ~15ull;
         if (o > arena_bytes || (l16 < 16ull ? 16ull : l16) > arena_bytes - o) e |= 2u;   /* every payload owns >= 16 readable bytes */
         if (l != len0 || o != off0 + k * stride) nonuni |= 1u;

@@ -722,7 +722,7 @@ int validate_index(kmpgpu_ctx *c, const char *who, const uint64_t *d_off, const 
     memcpy(err, c->h_small + 8, sizeof err);
     if (err[0] & 1u) return fail(KMPGPU_EINVAL, "%s: a payload offset is not 16-byte aligned", who);
     if (err[0] & 2u) return fail(KMPGPU_EINVAL, "%s: a payload (padded to 16 B) exceeds the arena", who);
-    if (err[0] & 4u) return fail(KMPGPU_EINVAL, "%s: a payload length is not below 2^30", who);
+    if (err[0] & 4u) return fail(KMPGPU_EINVAL, "%s: a payload length is above 2^30", who);
     *f = IndexFacts{};
     f->payload_bytes = info[0];
     f->uniform = ((err[1] & 1u) == 0) && info[2] >= 16 && info[2] < (1ull << 31);
@@ -1240,7 +1240,7 @@ int kmpgpu_load_arena(kmpgpu_ctx *c, const uint8_t *arena, uint64_t arena_bytes,
     for (uint64_t k = 0; k < n_pkts; k++) {         /* the layout contract the kernels rely on */
         const uint64_t o = pkt_off[k], l16 = ((uint64_t)pkt_len[k] + 15u) & ~15ull;
         if (o & 15u) return fail(KMPGPU_EINVAL, "payload %llu: offset %llu is not 16-byte aligned", (unsigned long long)k, (unsigned long long)o);
-        if (pkt_len[k] >= (1u << 30)) return fail(KMPGPU_EINVAL, "payload %llu: length %u is not below 2^30", (unsigned long long)k, pkt_len[k]);
+        if (pkt_len[k] > (1u << 30)) return fail(KMPGPU_EINVAL, "payload %llu: length %u is above 2^30", (unsigned long long)k, pkt_len[k]);
         if (o > arena_bytes || std::max<uint64_t>(l16, 16) > arena_bytes - o)
             return fail(KMPGPU_EINVAL, "payload %llu: [%llu, +%llu) padded to 16 B (at least one 16-byte slot) exceeds the arena (%llu B)", (unsigned long long)k,
                         (unsigned long long)o, (unsigned long long)pkt_len[k], (unsigned long long)arena_bytes);

@@ -64,7 +64,17 @@ def _first_and_flow(meta, directed):
     the index at which each appears first"""
     if len(meta) == 0:
         return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.uint32)
-    _, first, inv = np.unique(key_columns(meta, directed), axis=0, return_index=True, return_inverse=True)
+    # what np.unique(cols, axis=0, return_index=True, return_inverse=True) gives, by three stable sorts of one column each instead of one
+    # sort of whole rows (seconds instead of half a minute for millions of payloads): inside a key the payloads stay in capture order,
+    # so the first one of a group is the key's first payload
+    cols = key_columns(meta, directed)
+    by_key = np.lexsort((cols[:, 2], cols[:, 1], cols[:, 0]))
+    s = cols[by_key]
+    new = np.ones(len(s), dtype=bool)
+    new[1:] = (s[1:] != s[:-1]).any(axis=1)
+    first = by_key[new]
+    inv = np.empty(len(s), dtype=np.int64)
+    inv[by_key] = np.cumsum(new) - 1
     order = np.argsort(first, kind="stable")          # the distinct keys in the order of their first payload
     rank = np.empty(len(first), dtype=np.uint32)
     rank[order] = np.arange(len(first), dtype=np.uint32)

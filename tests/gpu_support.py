@@ -1,5 +1,6 @@
 """What the GPU test modules share: the context fixture, the options' defaults, the kernel selections, borrowed arenas with dirty
-padding and arenas placed around offset 2^32 of one large buffer, the frame library of tests/prep_model.py and its loader, the command lines, and the exact comparisons of a pass's outputs
+padding and arenas placed around offset 2^32 of one large buffer, periodic arenas of any size laid out on the device and what a second
+arena built from one has to hold, the frame library of tests/prep_model.py and its loader, the command lines, and the exact comparisons of a pass's outputs
 with the answers of tests/match_model.py and tests/flow_model.py.
 
 Import from this module before the package, for the reason given below.
@@ -175,6 +176,148 @@ def attach_placed(gm, payloads, slots, base, buf, off=None):
     torch.cuda.synchronize()
     gm.attach_arena(*keep, arena_bytes=base + end)
     return keep
+
+
+# ------------------------------------------------------------------------------------------------
+# periodic arenas: payload k = period entry k % P, laid out on the device, and what a second arena built from one has to hold
+# (tests/test_gpu_high_destinations.py; tests/test_high_destinations_model.py holds all of this to the plain models on the CPU)
+# ------------------------------------------------------------------------------------------------
+PERIOD = 257
+EMPTY_ARENA = (np.zeros(0, np.uint8), np.zeros(0, np.uint64), np.zeros(0, np.uint32))
+
+
+def tagged(body, e):
+    """body with prep_model.tag(e) over its first 8 bytes; a body shorter than the tag stays as it is"""
+    return PM.tag(e) + body[8:] if len(body) >= 8 else body
+
+
+def period_image(payloads):
+    """(bytes uint8, off int64[P], len int64[P]) of the packed image of one period: slots of max(16, round_up(len, 16)) bytes back to
+    back from 0, 0x00 behind every payload's end"""
+    ln = np.array([len(t) for t in payloads], dtype=np.int64)
+    slot = PM.slot_bytes(ln).astype(np.int64)
+    off = np.cumsum(slot) - slot
+    img = np.zeros(int(slot.sum()), dtype=np.uint8)
+    for o, t in zip(off.tolist(), payloads):
+        img[o:o + len(t)] = np.frombuffer(t, dtype=np.uint8)
+    return img, off, ln
+
+
+def periodic_end(image, n):
+    """the end of the last slot of the first n payloads of the periodic arena over `image`"""
+    img, off, _ = image
+    reps, rest = divmod(n, len(off))
+    return reps * len(img) + (int(off[rest]) if rest else 0)
+
+
+def periodic_source(payloads, n, device="cuda"):
+    """The packed arena with clean padding of n payloads, payload k = payloads[k % P], made by torch on `device`: the period's image
+    copied into every row of the arena seen as [n // P, image bytes] (what repeat() gives, written in place), then the image's head for
+    the n % P payloads that are left and 64 bytes of 0x00; offsets and lengths by arithmetic over arange(n).  Nothing of the arena's size
+    exists on the host.  Returns (arena uint8, off int64[n], len int32[n]); the first m payloads are a periodic arena as well, which
+    ends at periodic_end(image, m)."""
+    P = len(payloads)
+    img, poff, pln = period_image(payloads)
+    reps, rest = divmod(n, P)
+    pb, end = len(img), periodic_end((img, poff, pln), n)
+    d_img = torch.from_numpy(img).to(device)
+    arena = torch.zeros(end + 64, dtype=torch.uint8, device=device)
+    if reps:
+        arena[:reps * pb].view(reps, pb).copy_(d_img.expand(reps, pb))
+    arena[reps * pb:end] = d_img[:end - reps * pb]
+    k = torch.arange(n, dtype=torch.int64, device=device)
+    e = k % P
+    off = (k // P) * pb + torch.from_numpy(poff).to(device)[e]
+    ln = torch.from_numpy(pln.astype(np.int32)).to(device)[e]
+    return arena, off, ln
+
+
+class PeriodicSource:
+    """One context whose borrowed arena is a periodic_source; use(m) attaches its first m payloads (the slots are back to back and the
+    padding is clean, so the library takes the arena in place), release() gives the device memory back."""
+
+    def __init__(self, patterns=(b"<K",)):
+        self.m = GpuMatcher(0)
+        self.m.set_patterns(list(patterns))
+        self.keep = None
+
+    def build(self, payloads, n):
+        self.release()
+        self.payloads, self.image, self.n = payloads, period_image(payloads), n
+        self.keep = periodic_source(payloads, n)
+        torch.cuda.synchronize()
+        return self.use(n)
+
+    def use(self, n):
+        arena, off, ln = self.keep
+        assert n <= self.n
+        self.m.attach_arena(arena, off[:n], ln[:n], arena_bytes=periodic_end(self.image, n))
+        return self.m
+
+    def release(self):
+        if self.keep is not None:
+            self.m.load_arena(*EMPTY_ARENA)
+            self.keep = None
+            torch.cuda.empty_cache()
+
+    def close(self):
+        self.release()
+        self.m.close()
+
+
+def periodic_dst(image, index, n, period=PERIOD):
+    """What a second arena has to hold that takes, of every period of a periodic source of n payloads, the entries `index` (ascending) as
+    the packed image `image` = (bytes, off, len): `per` and `reps` -- the arena is `reps` times `per` --, `head`, the bytes of the last,
+    incomplete period, `end`, and in full `off` uint64, `len` uint32 and `index` int64 (payload j of dst is payload index[j] of the
+    source), all by index arithmetic."""
+    img, poff, pln = image
+    poff, pln, index = np.asarray(poff, dtype=np.int64), np.asarray(pln, dtype=np.int64), np.asarray(index, dtype=np.int64)
+    assert len(poff) == len(pln) == len(index) and (np.diff(index) > 0).all() and (len(index) == 0 or index[-1] < period)
+    reps, rest = divmod(n, period)
+    pb = len(img)
+    head = int((index < rest).sum())                                       # payloads of the incomplete period that dst holds
+    hb = pb if head == len(pln) else int(poff[head])
+    r = np.arange(reps, dtype=np.int64)[:, None]
+    return {"per": img, "reps": reps, "head": img[:hb], "end": reps * pb + hb,
+            "off": np.concatenate([(r * pb + poff[None, :]).ravel(), reps * pb + poff[:head]]).astype(np.uint64),
+            "len": np.concatenate([np.tile(pln, reps), pln[:head]]).astype(np.uint32),
+            "index": np.concatenate([(r * period + index[None, :]).ravel(), reps * period + index[:head]])}
+
+
+def periodic_bytes(want):
+    """the arena periodic_dst describes, in full (small inputs only)"""
+    return np.concatenate([np.tile(want["per"], want["reps"]), want["head"]])
+
+
+def check_periodic_bytes(a, want, rows=128):
+    """A downloaded arena against periodic_dst's image, every byte: one reshape to [reps, period bytes] compared with the period's image
+    `rows` rows at a time, the incomplete period's bytes, and the 64 bytes of 0x00 behind the end."""
+    per, reps, end = want["per"], want["reps"], want["end"]
+    pb = len(per)
+    assert len(a) == end + 64, (len(a), end + 64)
+    body = a[:reps * pb].reshape(reps, pb)
+    for lo in range(0, reps, rows):
+        blk = body[lo:lo + rows]
+        if not (blk == per).all():
+            r, c = (int(x) for x in np.argwhere(blk != per)[0])
+            j = int(np.searchsorted(want["off"], (lo + r) * pb + c, side="right")) - 1
+            raise AssertionError(f"{int((blk != per).sum())} bytes of periods {lo} .. {lo + len(blk) - 1} differ, the first at {(lo + r) * pb + c} = "
+                                 f"period {lo + r} + {c}, payload {j} + {(lo + r) * pb + c - int(want['off'][j])}: {int(blk[r, c])}, not {int(per[c])}")
+    bad = np.flatnonzero(a[reps * pb:end] != want["head"])
+    assert bad.size == 0, (bad.size, reps * pb + int(bad[0]))
+    assert not a[end:].any()
+
+
+def tag_counts(payloads, times, n_tags=PERIOD):
+    """counts[t] of prep_model.tag(t), t < n_tags, over an arena that holds payloads[j] times[j] times: a scan finds what stands in
+    front of a payload's first 0x00"""
+    want = np.zeros(n_tags, dtype=np.int64)
+    for p, x in zip(payloads, times):
+        if x:
+            for m in PM._TAG.finditer(p.split(b"\0")[0]):
+                if int(m.group(1)) < n_tags:
+                    want[int(m.group(1))] += int(x)
+    return want
 
 
 # ------------------------------------------------------------------------------------------------

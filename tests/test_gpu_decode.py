@@ -9,6 +9,7 @@ Where the kernels of csrc/kmp_decode.hip take another path:
   runs of 64 payloads and a rest                                                                      test_densities[64 bytes]
   nothing behind a payload's end decodes: dirty padding, the next slot, the arena's end                test_sources_*
   source offsets across and behind 2^32                                                               test_high_offsets
+  destination offsets as 64-bit values, > 4 GiB                           tests/test_gpu_high_destinations.py::test_decoded_past_2_32
 Past the grid caps: tests/test_gpu_decode_scale.py.
 
 No test provokes a fault: every negative case is one the library refuses on the host before it launches anything.

@@ -435,8 +435,8 @@ def test_layout_check_on_the_device(gm, oracle, where):
     o = off.copy(); o[where] = far                               # its slot [far, far + 16) ends one byte behind the arena
     cases.append(("exceeds the arena", o, ln, far + 15))
     o = off.copy(); o[where] = far
-    l = ln.copy(); l[where] = 1 << 30
-    cases.append(("not below 2^30", o, l, far + (1 << 30) + 64))
+    l = ln.copy(); l[where] = (1 << 30) + 1                       # 2^30 itself is the longest payload (a stream cut at KMPGPU_STREAM_DEPTH_MAX)
+    cases.append(("above 2^30", o, l, far + (1 << 30) + 64))
     try:
         gm.set_patterns(pats)
         for msg, o, l, told in cases:

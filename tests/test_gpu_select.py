@@ -23,6 +23,7 @@ Where every kernel's second code path starts, read off the launchers of csrc/kmp
   S7   kmp_select_copy_kernel, a run of more than        a lane's second step: runs of > 4 KiB                every test with payloads of 100 bytes and more
        4 * 64 units
   S8   source offsets as 64-bit values                   > 4 GiB                                              test_source_past_4_gib
+  S9   destination offsets as 64-bit values              > 4 GiB                                              tests/test_gpu_high_destinations.py::test_selected_past_2_32
 
 No test provokes a fault: every negative case is one the library refuses on the host before it launches anything.
 

@@ -10,6 +10,8 @@ The caps, read off csrc/kmp_streams.hip:
   the gather: at most 2 048 blocks of 4 wavefronts, each wavefront one contiguous span of whole rounds of 64 units (1 KiB): up to
       8 192 x 1 KiB = 8 MiB every wavefront has one round; the arena of test_one_long_stream is above 9 MiB, so wavefronts carry their
       place in the piece array from one round into the next.
+  destination offsets as 64-bit values, > 4 GiB, and the high words of kmpgpu_stream.bytes and kmpgpu_stream_pos.pos:
+      tests/test_gpu_high_destinations.py::test_streams_past_2_32 and test_stream_longer_than_2_32 (a stream of exactly 2^30 bytes).
 
 Run on a real MI355X:  python -m pytest tests/test_gpu_streams_scale.py -m gpu
 """
