@@ -1047,8 +1047,8 @@ int  kmpgpu_scan_flows_seams(kmpgpu_ctx *src, kmpgpu_ctx *seams, uint64_t *flow_
  * sort counted as one, stream scan, stream totals, heads, records, the two slot scan kernels, index, gather).  Under kmpgpu_profile_begin on
  * dst the entries are keys, sort, stream scan + totals, heads + records + the two slot scan kernels, index, gather.
  * Every existing call keeps its outputs, launches and buffers, with or without these calls having run.
- * Not done: capture order, not sequence numbers; a retransmitted segment appears twice; no TCP state, no timeouts; one cut
- * per stream; streams are per context, not across shards or GPUs. */
+ * Not done here: capture order, not sequence numbers; a retransmitted segment appears twice (kmpgpu_load_streams_ordered below does both).
+ * Not done: no TCP state, no timeouts; one cut per stream; streams are per context, not across shards or GPUs. */
 #define KMPGPU_STREAM_DEPTH_MAX (1u << 30)
 typedef struct kmpgpu_stream {        /* 48 bytes */
     uint64_t first_packet, last_packet;   /* src payload indices of the stream's first and last member */
@@ -1064,6 +1064,58 @@ typedef struct kmpgpu_stream_pos {    /* 16 bytes, one per SOURCE payload */
 int  kmpgpu_load_streams(kmpgpu_ctx *dst, kmpgpu_ctx *src, uint32_t depth, uint64_t *n_streams /* or NULL */);
 int  kmpgpu_streams_read(kmpgpu_ctx *dst, kmpgpu_stream *out, uint64_t first, uint64_t n);
 int  kmpgpu_stream_map_read(kmpgpu_ctx *dst, kmpgpu_stream_pos *out, uint64_t first, uint64_t n);
+
+/* Flow streams by TCP sequence number.  kmpgpu_load_streams keeps capture order: one reordered segment leaves "GET /admin" not contiguous, a
+ * retransmitted segment makes a content count twice and moves every later offset, window, chain distance and byte test.
+ * kmpgpu_load_streams_ordered(dst, src, depth, seq, on_device, n_streams) is its sibling with one 32-bit TCP sequence number per source
+ * payload: seq is uint32_t[n_pkts of src], in host memory (on_device == 0) or in device memory on the contexts' device (on_device == 1,
+ * complete before the call), borrowed for the call.  It builds the streams of TCP flows in sequence order, with bytes already delivered
+ * dropped and holes closed.  Streams, their numbering (flow << 1 | dir), dir(k), the slot layout, depth, the metadata (meta[s] =
+ * src.meta[first_packet_s], first_packet the first member IN CAPTURE ORDER), the flow identity, the state dst is left in, what is untouched
+ * and the ordering are exactly those of kmpgpu_load_streams.
+ * Definitions.  A stream is a TCP stream iff src.meta[first_packet_s].proto == 6.  Every other stream is built exactly as
+ * kmpgpu_load_streams builds it: capture order, skip = 0, take = L_k.  For a TCP stream with members k0 < k1 < ... in capture order:
+ *     rel(k)  = (int32_t)(uint32_t)(seq[k] - seq[k0])      two's complement: serial-number arithmetic around the first captured member
+ *     off(k)  = rel(k) - min over the members j of rel(j)  in [0, 2^32): the member's offset in the stream's sequence space
+ *     order   = ascending (off(k), k)                      equal sequence numbers stay in capture order
+ *     byte x  = payload_k[x - off(k)] of the FIRST k in that order with off(k) <= x < off(k) + L_k
+ *     stream  = the bytes of all covered x in ascending x, holes closed (nothing is written for an uncovered x), cut to its first `depth`
+ *               bytes
+ * Per member, with M(k) the maximum of off(j) + L_j over the members before k in the order (0 for the first): skip(k) = min(L_k,
+ * max(0, M(k) - off(k))), take(k) = L_k - skip(k), pos(k) = the sum of take over the members before it, before the cut.  The kept bytes
+ * of a member are always a suffix of it, because every earlier member starts at or before it.  A member other than the first with
+ * off(k) > M(k) opens a gap of off(k) - M(k) bytes.  First in sequence order wins: that is the only overlap policy.
+ * No TCP flags are read: a SYN's phantom byte is a 1-byte gap, a reused 5-tuple interleaves its connections by sequence number.  A stream
+ * whose members span 2^31 or more of sequence space is computed by the arithmetic above, and nothing more is promised for it.
+ * Records.  kmpgpu_stream is unchanged: bytes is the sum of take, n_packets all members, first_packet / last_packet in capture order.
+ * kmpgpu_stream_pos is unchanged: pos is the position of the member's first kept byte.  New: kmpgpu_stream_seg[n_pkts of src], one per
+ * source payload, and kmpgpu_stream_order[n_streams]; kmpgpu_stream_segs_read / kmpgpu_stream_orders_read copy elements [first, first + n)
+ * to out, ranges and errors as kmpgpu_streams_read, and return KMPGPU_ESTATE after a plain kmpgpu_load_streams ("no sequence order").
+ * No atomic decides a value: two builds are byte-identical.
+ * Scratch: that of kmpgpu_load_streams, a workspace of its own for the second sort and the scans (40 bytes per source payload plus
+ * rocPRIM's temporary storage), and, with on_device == 0, a device copy of seq; all kept by dst for the next build.
+ * Errors: those of kmpgpu_load_streams, plus seq == NULL with n_pkts > 0, on_device outside {0, 1}, n_pkts > 2^30 (which keeps the
+ * composite sort keys inside 64 bits): KMPGPU_EINVAL; src without metadata: KMPGPU_ESTATE.  After each of these dst keeps its arena.
+ * kmpgpu_last_timing(dst): kernel_ms from the keys kernel to the gather's end (the upload of a host seq lies before it, the host's two
+ * reads inside), launches = 16 (keys, the sort, stream scan, stream totals, heads, second keys, the second sort, maximum scan, maximum
+ * totals, take scan, take totals, records, the two slot scan kernels, index, gather).  Under kmpgpu_profile_begin on dst the entries are
+ * keys, sort, stream scan + totals, heads + second keys + second sort, the four scan kernels, records + the two slot scan kernels, index,
+ * gather.
+ * Not done: no TCP state or flags, no timeouts; one cut per stream; per context; kmpgpu_load_frames keeps no sequence
+ * numbers (kmphost's kmp_arena_from_pcap_seq does); no overlap policy but first-in-sequence-order. */
+typedef struct kmpgpu_stream_seg {    /* 16 bytes, one per SOURCE payload */
+    uint32_t skip, take;                  /* bytes of k already delivered by earlier members; L_k - skip, before the cut */
+    uint32_t seq_off, reserved;           /* off(k); 0 for a member of a stream that is not TCP.  0 */
+} kmpgpu_stream_seg;
+typedef struct kmpgpu_stream_order {  /* 32 bytes, one per stream */
+    uint32_t seq_base, n_gaps;            /* the sequence number of offset 0 (the lowest of the stream); members that open a gap */
+    uint64_t gap_bytes, dup_bytes;        /* sum of the gaps; sum of skip */
+    uint32_t tcp, reserved;               /* 1: built in sequence order; 0: capture order, and every other field 0.  0 */
+} kmpgpu_stream_order;
+int  kmpgpu_load_streams_ordered(kmpgpu_ctx *dst, kmpgpu_ctx *src, uint32_t depth, const uint32_t *seq, int on_device,
+                                 uint64_t *n_streams /* or NULL */);
+int  kmpgpu_stream_segs_read(kmpgpu_ctx *dst, kmpgpu_stream_seg *out, uint64_t first, uint64_t n);
+int  kmpgpu_stream_orders_read(kmpgpu_ctx *dst, kmpgpu_stream_order *out, uint64_t first, uint64_t n);
 
 /* Fill a device arena with the synthetic payloads of kmp_synth.h (benchmark input S1/S2):
  * packet ids first_pkt_id .. first_pkt_id + n_pkts - 1 at the slots of the given device index. */

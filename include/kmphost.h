@@ -72,6 +72,10 @@ typedef struct kmp_pkt_meta {
     uint8_t  reserved[3];     /* 0 */
 } kmp_pkt_meta;
 int kmp_extract_meta(const uint8_t *frame, uint32_t capture_len, int proto, kmp_pkt_meta *out);
+/* The TCP sequence number (kmpgpu_load_streams_ordered takes one per payload): the big-endian 32 bits at T + 4.  Returns 1 / 0 exactly
+ * where the extractor of `proto` does; for an accepted frame those bytes lie inside capture_len (for a UDP frame they are its length and
+ * checksum, and no stream of UDP payloads looks at them), for a rejected one *seq is not written. */
+int kmp_extract_tcp_seq(const uint8_t *frame, uint32_t capture_len, int proto, uint32_t *seq);
 
 /* ---- pattern list -------------------------------------------------------------------------
  * Replaces the fscanf("%s") loader of serial.c:54-87 / openmp_data.c:57-90: whitespace-separated
@@ -300,6 +304,10 @@ int  kmp_arena_from_pcap(const char *path, int proto, kmp_alloc_fn alloc_fn, kmp
  * out->n_pkts records, comes from malloc() and is released with free().  kmp_arena's layout is the same either way. */
 int  kmp_arena_from_pcap_meta(const char *path, int proto, kmp_alloc_fn alloc_fn, kmp_free_fn free_fn,
                               kmp_arena *out, char errbuf[KMP_PCAP_ERRBUF], kmp_pkt_meta **meta_out);
+/* ... and beside both the accepted frames' sequence numbers in payload order (kmp_extract_tcp_seq): *seq_out holds out->n_pkts words,
+ * comes from malloc() and is released with free().  meta_out and seq_out may each be NULL. */
+int  kmp_arena_from_pcap_seq(const char *path, int proto, kmp_alloc_fn alloc_fn, kmp_free_fn free_fn,
+                             kmp_arena *out, char errbuf[KMP_PCAP_ERRBUF], kmp_pkt_meta **meta_out, uint32_t **seq_out);
 /* Build an arena from caller-supplied payloads (tests, synthetic inputs). */
 int  kmp_arena_from_payloads(const uint8_t *const *payloads, const uint32_t *lens, uint64_t n,
                              kmp_alloc_fn alloc_fn, kmp_free_fn free_fn, kmp_arena *out);

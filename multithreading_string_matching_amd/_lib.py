@@ -182,6 +182,7 @@ HOST_API = {
     "kmp_extract_udp": (C.c_int, [u8p, C.c_uint32, u32p, u32p]),
     "kmp_extract_tcp": (C.c_int, [u8p, C.c_uint32, u32p, u32p]),
     "kmp_extract_meta": (C.c_int, [u8p, C.c_uint32, C.c_int, C.POINTER(PktMeta)]),
+    "kmp_extract_tcp_seq": (C.c_int, [u8p, C.c_uint32, C.c_int, u32p]),
     "kmp_patterns_load": (C.c_int, [C.c_char_p, C.POINTER(Patterns)]),
     "kmp_patterns_parse": (C.c_int, [u8p, C.c_size_t, C.POINTER(Patterns)]),
     "kmp_patterns_free": (None, [C.POINTER(Patterns)]),
@@ -206,6 +207,8 @@ HOST_API = {
     "kmp_failure_table": (None, [u8p, C.c_uint32, i32p]),
     "kmp_arena_from_pcap": (C.c_int, [C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Arena), C.c_char_p]),
     "kmp_arena_from_pcap_meta": (C.c_int, [C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Arena), C.c_char_p, C.POINTER(C.POINTER(PktMeta))]),
+    "kmp_arena_from_pcap_seq": (C.c_int, [C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Arena), C.c_char_p, C.POINTER(C.POINTER(PktMeta)),
+                                          C.POINTER(u32p)]),
     "kmp_arena_from_payloads": (C.c_int, [C.POINTER(u8p), u32p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(Arena)]),
     "kmp_arena_layout": (C.c_uint64, [u32p, C.c_uint32, C.c_uint64, C.c_uint32, u64p, u32p]),
     "kmp_arena_free": (None, [C.POINTER(Arena)]),
@@ -288,6 +291,9 @@ GPU_API = {
     "kmpgpu_load_streams": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, u64p]),
     "kmpgpu_streams_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "kmpgpu_stream_map_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "kmpgpu_load_streams_ordered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, u64p]),
+    "kmpgpu_stream_segs_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "kmpgpu_stream_orders_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "kmpgpu_synth_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(SynthParams)]),
     "kmpgpu_fixed_index": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32]),
     "kmpgpu_arena_info": (C.c_int, [C.c_void_p, u64p, u64p]),

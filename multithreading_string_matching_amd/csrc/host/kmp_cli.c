@@ -114,6 +114,11 @@
  * KMPGPU_FLOW_SEAMS (streams hold everything seams hold, up to the cut) or with KMPGPU_DECODE (decoded streams are not wired here; at the
  * library, kmpgpu_load_decoded over the stream context does it), KMPGPU_STREAMS_FILE without KMPGPU_FLOW_STREAMS or on a path that cannot
  * be written.  stdout is what it is without the variables.
+ * KMPGPU_FLOW_STREAMS_ORDER=seq|capture (default capture), together with KMPGPU_FLOW_STREAMS: under seq the capture is read with its TCP
+ * sequence numbers (kmp_arena_from_pcap_seq) and the streams of TCP flows are built in sequence order, retransmitted bytes dropped and
+ * holes closed (kmpgpu_load_streams_ordered); KMPGPU_STREAMS_FILE then has the columns "tcp,gaps,gap_bytes,dup_bytes" behind the others,
+ * and "bytes" counts the bytes kept.  Under capture every output is byte for byte what it is without the variable.  Refused: any other
+ * value, the variable without KMPGPU_FLOW_STREAMS, and with KMPGPU_DEVICE_EXTRACT=1 (the device extractor keeps no sequence numbers).
  *
  * KMPGPU_NOCASE=1: every pattern matches case-insensitively (ASCII letters; kmpgpu_set_patterns_flags), in the counts and in
  * the offsets file alike; the report prints every token as written in the pattern file.
@@ -132,6 +137,7 @@
 #include "kmp_cli_common.h"
 #include "kmp_cli_decode.h"
 #include "kmp_cli_streams.h"
+#include "kmp_cli_streams_order.h"
 
 #ifndef KMP_CLI_OPENMP_FORM
 #define KMP_CLI_OPENMP_FORM 0
@@ -158,6 +164,7 @@ typedef struct cli_options {
     int decode;                             /* KMPGPU_DECODE: KMP_CLI_DECODE_* */
     uint32_t flow_streams;                  /* KMPGPU_FLOW_STREAMS: the depth, 0 without the variable */
     const char *streams_path;               /* KMPGPU_STREAMS_FILE */
+    int streams_order;                      /* KMPGPU_FLOW_STREAMS_ORDER: KMP_CLI_STREAMS_ORDER_* */
     int want_meta;                          /* header predicates or flows: the payloads' header fields go to the device */
     /* what every shard's context gets behind its patterns, in this order and before any rule is set */
     uint32_t *win_first, *win_last;         /* KMPGPU_WINDOWS_FILE (NULL: none) */
@@ -174,6 +181,7 @@ typedef struct capture {
     kmp_arena arena;
     kmp_frames frames;
     kmp_pkt_meta *meta;                     /* beside the arena where header predicates are set: its payloads' header fields */
+    uint32_t *seq;                          /* ... and under KMPGPU_FLOW_STREAMS_ORDER=seq their TCP sequence numbers */
     double t_load0, t_loaded, t_warm;
 } capture;
 
@@ -423,6 +431,21 @@ static void load_options(int argc, char *argv[], cli_options *opt)
         }
         probe_writable("KMPGPU_STREAMS_FILE", opt->streams_path);
     }
+    const char *order_env = env_path("KMPGPU_FLOW_STREAMS_ORDER");
+    if (order_env) {
+        if (!kmp_cli_parse_streams_order(order_env, &opt->streams_order)) {
+            fprintf(stderr, "KMPGPU_FLOW_STREAMS_ORDER is \"%s\": seq or capture is needed\n", order_env);
+            exit(1);
+        }
+        if (!opt->flow_streams) {
+            fprintf(stderr, "KMPGPU_FLOW_STREAMS_ORDER goes together with KMPGPU_FLOW_STREAMS: it is not set\n");
+            exit(1);
+        }
+        if (opt->streams_order == KMP_CLI_STREAMS_ORDER_SEQ && opt->device_extract) {
+            fprintf(stderr, "KMPGPU_FLOW_STREAMS_ORDER=seq does not go together with KMPGPU_DEVICE_EXTRACT=1: the device extractor keeps no sequence numbers\n");
+            exit(1);
+        }
+    }
     opt->want_meta = opt->headers.n || opt->flows_path || opt->flow_alerts_path;
     /* the export starts as a capture without frames: a path that cannot be written ends the run here */
     if (opt->export_path && kmp_write_udp_pcap_part(opt->export_path, 0, NULL, NULL, NULL, 0, 0)) {
@@ -469,6 +492,8 @@ static void load_capture(const cli_options *opt, capture *cap)
      * MI355X hosts (profiles/r01_h2d_probe.txt).  Pinned buffers pay off where they are reused (bin/openmp_task). */
     if (opt->device_extract)
         rc = kmp_frames_from_pcap(opt->pcap_path, NULL, NULL, &cap->frames, errbuf);
+    else if (opt->streams_order == KMP_CLI_STREAMS_ORDER_SEQ)               /* (streams go with flow alerts: the header fields are wanted too) */
+        rc = kmp_arena_from_pcap_seq(opt->pcap_path, opt->proto, NULL, NULL, &cap->arena, errbuf, &cap->meta, &cap->seq);
     else if (opt->want_meta)                                                /* the same arena, and the header fields the predicates and the flows read */
         rc = kmp_arena_from_pcap_meta(opt->pcap_path, opt->proto, NULL, NULL, &cap->arena, errbuf, &cap->meta);
     else
@@ -639,15 +664,20 @@ static void write_alerts(const char *path, const cli_options *opt, cli_run *run,
 /* KMPGPU_FLOW_STREAMS: next to the shard, whose flows are built, a context with the same tables and rules that holds the shard's flow
  * directions reassembled and groups them into the same n_flows flows; KMPGPU_STREAMS_FILE: its stream records, read back in pieces. */
 #define STREAM_PIECE 16384u
-static kmpgpu_ctx *stream_context(const cli_options *opt, kmpgpu_ctx *src, uint64_t n_flows)
+static kmpgpu_ctx *stream_context(const cli_options *opt, kmpgpu_ctx *src, const uint32_t *seq, uint64_t n_flows)
 {
     static kmpgpu_stream piece[STREAM_PIECE];
+    static kmpgpu_stream_order order_piece[STREAM_PIECE];
+    const int by_seq = opt->streams_order == KMP_CLI_STREAMS_ORDER_SEQ;
     kmpgpu_ctx *st = NULL;
     uint64_t n_streams = 0, nf = 0;
     if (kmpgpu_init(&st, kmpgpu_device_of(src))) die_gpu("kmpgpu_init");
     const char *failed = upload_tables(st, opt);
     if (failed) die_gpu(failed);
-    if (kmpgpu_load_streams(st, src, opt->flow_streams, &n_streams)) die_gpu("kmpgpu_load_streams");
+    if (by_seq) {
+        /* KMPGPU_FLOW_STREAMS_ORDER=seq: one shard holds every payload, so the capture's sequence numbers are the shard's */
+        if (kmpgpu_load_streams_ordered(st, src, opt->flow_streams, seq, 0, &n_streams)) die_gpu("kmpgpu_load_streams_ordered");
+    } else if (kmpgpu_load_streams(st, src, opt->flow_streams, &n_streams)) die_gpu("kmpgpu_load_streams");
     if (kmpgpu_flows_build(st, opt->flows_directed ? KMPGPU_FLOW_DIRECTED : 0u, &nf, NULL)) die_gpu("kmpgpu_flows_build");
     if (nf != n_flows) {
         fprintf(stderr, "KMPGPU_FLOW_STREAMS: the streams group into %llu flows, the capture into %llu\n", (unsigned long long)nf, (unsigned long long)n_flows);
@@ -660,10 +690,15 @@ static kmpgpu_ctx *stream_context(const cli_options *opt, kmpgpu_ctx *src, uint6
         for (uint64_t first = 0; first < n_streams; first += STREAM_PIECE) {
             const uint64_t n = n_streams - first < STREAM_PIECE ? n_streams - first : STREAM_PIECE;
             if (kmpgpu_streams_read(st, piece, first, n)) die_gpu("kmpgpu_streams_read");
+            if (by_seq && kmpgpu_stream_orders_read(st, order_piece, first, n)) die_gpu("kmpgpu_stream_orders_read");
             for (uint64_t i = 0; i < n; i++) {
                 const kmpgpu_stream *s = &piece[i];
-                fprintf(fp, "%llu,%u,%u,%llu,%llu,%llu,%llu,%u\n", (unsigned long long)(first + i), s->flow, s->dir, (unsigned long long)s->first_packet,
+                fprintf(fp, "%llu,%u,%u,%llu,%llu,%llu,%llu,%u", (unsigned long long)(first + i), s->flow, s->dir, (unsigned long long)s->first_packet,
                         (unsigned long long)s->last_packet, (unsigned long long)s->n_packets, (unsigned long long)s->bytes, s->len);
+                if (by_seq)
+                    fprintf(fp, ",%u,%u,%llu,%llu", order_piece[i].tcp, order_piece[i].n_gaps, (unsigned long long)order_piece[i].gap_bytes,
+                            (unsigned long long)order_piece[i].dup_bytes);
+                fputc('\n', fp);
             }
         }
         fclose(fp);
@@ -709,7 +744,7 @@ static void write_flows(const cli_options *opt, cli_run *run)
         }
         set_rules_once(opt, run);
         const uint64_t Wf = (n_flows + 63) / 64, nr = opt->rules.n;
-        kmpgpu_ctx *st = opt->flow_streams ? stream_context(opt, ctx, n_flows) : NULL;
+        kmpgpu_ctx *st = opt->flow_streams ? stream_context(opt, ctx, run->job[0].cap->seq, n_flows) : NULL;
         if (nr && n_flows) {
             uint64_t *hits = (uint64_t *)calloc((size_t)(nr * Wf), sizeof(uint64_t));
             if (!hits) die_gpu("KMPGPU_FLOW_ALERTS_FILE: out of memory");
@@ -854,6 +889,7 @@ int main(int argc, char *argv[])
     kmp_arena_free(&cap.arena);
     kmp_frames_free(&cap.frames);
     free(cap.meta);
+    free(cap.seq);
     free_options(&opt);
     return 0;
 }

@@ -356,6 +356,17 @@ int kmp_extract_meta(const uint8_t *f, uint32_t cl, int proto, kmp_pkt_meta *out
     return 1;
 }
 
+/* The TCP sequence number's place, for a frame the extractor of `proto` accepts: T + 4 .. T + 7 lie inside the captured bytes then
+ * (udp: cl - 14 - ihl >= 8; tcp: cl >= 14 + ihl + 20).  For a UDP frame the bytes there are its length and checksum. */
+int kmp_extract_tcp_seq(const uint8_t *f, uint32_t cl, int proto, uint32_t *seq)
+{
+    uint32_t o, l;
+    if (!((proto == KMP_PROTO_TCP) ? kmp_extract_tcp(f, cl, &o, &l) : kmp_extract_udp(f, cl, &o, &l))) return 0;
+    const uint32_t at = 14u + ((uint32_t)(f[14] & 0x0Fu) << 2) + 4u;
+    *seq = (uint32_t)f[at] << 24 | (uint32_t)f[at + 1u] << 16 | (uint32_t)f[at + 2u] << 8 | f[at + 3u];
+    return 1;
+}
+
 /* ============================ pattern list ============================================== */
 
 static int is_c_space(uint8_t b) { return b == ' ' || (b >= '\t' && b <= '\r'); }
@@ -1298,8 +1309,16 @@ int kmp_arena_from_pcap(const char *path, int proto, kmp_alloc_fn alloc_fn, kmp_
 int kmp_arena_from_pcap_meta(const char *path, int proto, kmp_alloc_fn alloc_fn, kmp_free_fn free_fn,
                              kmp_arena *out, char errbuf[KMP_PCAP_ERRBUF], kmp_pkt_meta **meta_out)
 {
+    return kmp_arena_from_pcap_seq(path, proto, alloc_fn, free_fn, out, errbuf, meta_out, NULL);
+}
+
+/* ... and with seq_out their sequence numbers (kmp_extract_tcp_seq), from malloc as well */
+int kmp_arena_from_pcap_seq(const char *path, int proto, kmp_alloc_fn alloc_fn, kmp_free_fn free_fn,
+                            kmp_arena *out, char errbuf[KMP_PCAP_ERRBUF], kmp_pkt_meta **meta_out, uint32_t **seq_out)
+{
     memset(out, 0, sizeof *out);
     if (meta_out) *meta_out = NULL;
+    if (seq_out) *seq_out = NULL;
     kmp_view v;
     kmp_index ix;
     int rc = view_open(path, &v, errbuf);
@@ -1334,12 +1353,20 @@ int kmp_arena_from_pcap_meta(const char *path, int proto, kmp_alloc_fn alloc_fn,
             *meta_out = (kmp_pkt_meta *)malloc(sizeof(kmp_pkt_meta) * (size_t)(n ? n : 1));
             if (!*meta_out) { kmp_arena_free(out); rc = KMPHOST_ENOMEM; }
         }
+        if (!rc && seq_out) {
+            *seq_out = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)(n ? n : 1));
+            if (!*seq_out) {
+                kmp_arena_free(out); rc = KMPHOST_ENOMEM;
+                if (meta_out) { free(*meta_out); *meta_out = NULL; }
+            }
+        }
         if (!rc) {
             uint64_t k = 0;
             for (int64_t f = 0; f < nf; f++) {
                 if (pl[f] == UINT32_MAX) continue;
                 out->off[k] = dst[f]; out->len[k] = pl[f];
                 if (meta_out) (void)kmp_extract_meta(v.base + ix.off[f], ix.caplen[f], proto, *meta_out + k);
+                if (seq_out) (void)kmp_extract_tcp_seq(v.base + ix.off[f], ix.caplen[f], proto, *seq_out + k);
                 k++;
             }
             /* payload copies (serial.c:125-127) + zeroed slot padding, one stream per thread */

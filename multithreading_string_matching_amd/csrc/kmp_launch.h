@@ -1,5 +1,5 @@
 /* kmp_launch.h -- launch entry points of kmp_scan_*.hip / kmp_prep.hip / kmp_fold.hip / kmp_marks.hip / kmp_rules.hip / kmp_relations.hip /
- * kmp_chains.hip / kmp_headers.hip / kmp_bytetests.hip / kmp_regex.hip / kmp_select.hip / kmp_decode.hip / kmp_alerts.hip / kmp_flows.hip / kmp_seams.hip / kmp_streams.hip, used
+ * kmp_chains.hip / kmp_headers.hip / kmp_bytetests.hip / kmp_regex.hip / kmp_select.hip / kmp_decode.hip / kmp_alerts.hip / kmp_flows.hip / kmp_seams.hip / kmp_streams.hip / kmp_streams_seq.hip, used
  * by the C-ABI layer (kmpgpu.hip), which alone decides what is launched; the tables kmp_launch_scan_multi takes come from kmp_tables.h. */
 #ifndef KMP_LAUNCH_H
 #define KMP_LAUNCH_H
@@ -278,5 +278,30 @@ hipError_t kmp_launch_stream_index(const uint64_t *src_off, const uint32_t *src_
                                    hipStream_t st);
 hipError_t kmp_launch_stream_gather(const uint8_t *src_arena, const void *pieces, uint64_t n, uint64_t total_bytes, uint8_t *arena,
                                     bool nontemporal, hipStream_t st);
+
+/* kmp_streams_seq.hip (kmpgpu_load_streams_ordered): those streams with the members of every TCP stream in sequence order, bytes already
+ * delivered dropped and holes closed; seq[n] is one sequence number per payload, n <= 2^30.  After kmp_launch_seam_keys,
+ * kmp_launch_seam_sort and kmp_launch_stream_phase1, whose sort_buf and ws are kept up to _index, and with ws2
+ * (kmp_stream_seq_ws_bytes(n, n_flows) bytes, 256-byte aligned, kept up to _index; 0: rocPRIM refused the size query), in the order they
+ * are launched:
+ * _order (2 kernels and the second sort): head_pos[], key2 = key << 32 | sequence offset, (key2, val) sorted stably over the bits in use.
+ * _scans (4 kernels): the running maximum of the members' ends and its tile totals, then skip[] and the sums of take and of gaps.
+ * _records (3 kernels): recs[n_streams] (kmpgpu_stream), orders[n_streams] (kmpgpu_stream_order), meta[n_streams], and the scan of the slot
+ *   sizes through kmp_launch_repack_phase1; total = the bytes of all members (of _phase1); totals[0] = bytes of the packed streams.
+ * _index: pkt_off[n_streams], pkt_len[n_streams], map[n] (kmpgpu_stream_pos) and segs[n] (kmpgpu_stream_seg) by source payload, and pieces
+ *   (24 n bytes, 16-byte aligned): per ordered position {source address, take in front of the cut, skip}, then the destination addresses.
+ * _gather: arena[0, total_bytes) as kmp_launch_stream_gather writes it; of src_arena only aligned 16-byte units that hold a KEPT byte. */
+size_t kmp_stream_seq_ws_bytes(uint64_t n, uint64_t n_flows);
+hipError_t kmp_launch_stream_seq_order(const void *src_meta, const uint32_t *seq, uint64_t n, uint64_t n_streams, uint64_t n_flows,
+                                       const uint8_t *sort_buf, uint8_t *ws, uint8_t *ws2, size_t ws2_bytes, hipStream_t st);
+hipError_t kmp_launch_stream_seq_scans(const uint32_t *pkt_len, uint64_t n, const uint8_t *sort_buf, uint8_t *ws, uint8_t *ws2, hipStream_t st);
+hipError_t kmp_launch_stream_seq_records(const void *src_meta, const uint32_t *seq, uint64_t n, uint64_t total, uint64_t n_streams,
+                                         uint32_t depth, const uint8_t *sort_buf, uint8_t *ws, uint8_t *ws2, void *recs, void *orders,
+                                         void *meta, unsigned long long *totals, hipStream_t st);
+hipError_t kmp_launch_stream_seq_index(const uint64_t *src_off, const uint32_t *src_len, uint64_t n, uint64_t n_streams, const uint8_t *sort_buf,
+                                       uint8_t *ws, uint8_t *ws2, uint64_t *pkt_off, uint32_t *pkt_len, void *map, void *segs, void *pieces,
+                                       hipStream_t st);
+hipError_t kmp_launch_stream_seq_gather(const uint8_t *src_arena, const void *pieces, uint64_t n, uint64_t total_bytes, uint8_t *arena,
+                                        bool nontemporal, hipStream_t st);
 
 #endif

@@ -245,6 +245,15 @@ struct kmpgpu_ctx {
     uint64_t            streams_cap = 0, stream_map_cap = 0;
     uint64_t            n_streams = 0, n_stream_map = 0;
     bool                streams_valid = false;
+    /* kmpgpu_load_streams_ordered, in dst: the kmpgpu_stream_seg entries [n_stream_map] and the kmpgpu_stream_order records [n_streams], the
+     * workspace of the second sort and its scans (kmp_stream_seq_ws_bytes) and the device copy of a host seq.  stream_order_valid: the
+     * streams were built in sequence order (dropped with them) */
+    kmpgpu_stream_seg   *d_stream_segs = nullptr;
+    kmpgpu_stream_order *d_stream_orders = nullptr;
+    uint8_t             *d_stream_seq_ws = nullptr;
+    uint32_t            *d_stream_seq = nullptr;
+    uint64_t            stream_segs_cap = 0, stream_orders_cap = 0, stream_seq_ws_cap = 0, stream_seq_cap = 0;
+    bool                stream_order_valid = false;
     /* the patterns as they were set, one record {length, flags, bytes} each: what kmpgpu_scan_flows_seams compares between two contexts */
     std::vector<uint8_t> pat_sig;
 
@@ -456,7 +465,7 @@ void drop_seams(kmpgpu_ctx *c)
 /* the stream records and the map go with the arena they describe; their buffers are kept for the next build */
 void drop_streams(kmpgpu_ctx *c)
 {
-    c->streams_valid = false;
+    c->streams_valid = c->stream_order_valid = false;
     c->n_streams = c->n_stream_map = 0;
 }
 
@@ -574,6 +583,8 @@ void release_pass_buffers(kmpgpu_ctx *c)
     free_buffer(&c->d_seams, &c->seams_cap); free_buffer(&c->d_seam_flow, &c->seam_flow_cap); free_buffer(&c->d_seam_sort, &c->seam_sort_cap);
     drop_seams(c);
     free_buffer(&c->d_streams, &c->streams_cap); free_buffer(&c->d_stream_map, &c->stream_map_cap);
+    free_buffer(&c->d_stream_segs, &c->stream_segs_cap); free_buffer(&c->d_stream_orders, &c->stream_orders_cap);
+    free_buffer(&c->d_stream_seq_ws, &c->stream_seq_ws_cap); free_buffer(&c->d_stream_seq, &c->stream_seq_cap);
     drop_streams(c);
     c->alerts_valid = false;
     c->bitmap_live = false; c->plan_waves = c->uplan_units = 0; c->fold_stale = true;
@@ -1827,6 +1838,130 @@ int kmpgpu_stream_map_read(kmpgpu_ctx *c, kmpgpu_stream_pos *out, uint64_t first
     static_assert(sizeof(kmpgpu_stream_pos) == 16, "kmpgpu_stream_pos is the 16-byte record of kmpgpu.h");
     return streams_read_range(c, "kmpgpu_stream_map_read", out, c ? c->d_stream_map : nullptr, sizeof(kmpgpu_stream_pos), first, n,
                               c ? c->n_stream_map : 0);
+}
+
+int kmpgpu_load_streams_ordered(kmpgpu_ctx *dst, kmpgpu_ctx *src, uint32_t depth, const uint32_t *seq, int on_device, uint64_t *n_streams)
+{
+    const char *who = "kmpgpu_load_streams_ordered";
+    if (n_streams) *n_streams = 0;
+    if (!dst || !src) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
+    if (dst == src) return fail(KMPGPU_EINVAL, "%s: dst and src are the same context (a context holds one arena)", who);
+    if (depth < 1u || depth > KMPGPU_STREAM_DEPTH_MAX)
+        return fail(KMPGPU_EINVAL, "%s: depth %u is not in 1..%u", who, depth, KMPGPU_STREAM_DEPTH_MAX);
+    if (on_device != 0 && on_device != 1) return fail(KMPGPU_EINVAL, "%s: on_device %d is neither 0 nor 1", who, on_device);
+    if (dst->device != src->device)
+        return fail(KMPGPU_EINVAL, "%s: the contexts sit on devices %d and %d (streams across devices do not exist)", who, dst->device, src->device);
+    if (dst->fr_pending || src->fr_pending) return fail(KMPGPU_ESTATE, "%s: %s sits between kmpgpu_load_frames_begin and _finish", who, dst->fr_pending ? "dst" : "src");
+    const uint64_t n = src->n_pkts;
+    if (n > (1ull << 30)) return fail(KMPGPU_EINVAL, "%s: %llu payloads are more than 2^30 (the composite sort keys)", who, (unsigned long long)n);
+    if (!seq && n > 0) return fail(KMPGPU_EINVAL, "%s: seq is NULL", who);
+    if (n > 0 && !src->has_meta) return fail(KMPGPU_ESTATE, "%s: src has no metadata (which stream is TCP is read from it)", who);
+    if (!src->flows_valid) return fail(KMPGPU_ESTATE, "%s: no flows (no kmpgpu_flows_build since the arena or its metadata were set)", who);
+    HIP_TRY(hipSetDevice(dst->device));
+    HIP_TRY(hipStreamSynchronize(dst->stream));           /* the passes over the arena that is about to be replaced */
+    HIP_TRY(hipStreamSynchronize(src->stream));           /* whatever src's stream still does with its arena */
+    kmpgpu_ctx *c = dst;
+    c->last = kmpgpu_timing{};
+    /* from here on dst's earlier arena is gone, whatever happens */
+    release_arena(c, /* keep_buffers = */ true);
+    if (n == 0) { c->streams_valid = c->stream_order_valid = true; return KMPGPU_OK; }       /* (no stream, no map entry) */
+
+    /* the scratch of kmpgpu_load_streams, and this call's own: the second sort's and the scans' workspace, the copy of a host seq */
+    const uint64_t sort_bytes = kmp_seam_sort_bytes(n, src->n_flows), seq_bytes = kmp_stream_seq_ws_bytes(n, src->n_flows);
+    if (!sort_bytes || !seq_bytes) return fail(KMPGPU_EHIP, "%s: the sorts of %llu payloads could not be sized", who, (unsigned long long)n);
+    hipError_t e = grow_buffer(&c->fr_ws, &c->fr_ws_cap, (uint64_t)kmp_stream_ws_bytes(n), EIGHTH);
+    if (e == hipSuccess && !c->fr_tot) e = hipMalloc(&c->fr_tot, 2 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = grow_buffer(&c->d_seam_sort, &c->seam_sort_cap, sort_bytes, EIGHTH);
+    if (e == hipSuccess) e = grow_buffer(&c->d_stream_seq_ws, &c->stream_seq_ws_cap, seq_bytes, EIGHTH);
+    if (e == hipSuccess) e = grow_buffer(&c->fr_src, &c->fr_src_cap, 3 * n, EIGHTH);              /* 24 bytes per source payload */
+    if (e == hipSuccess) e = grow_buffer(&c->d_stream_map, &c->stream_map_cap, n, EIGHTH);
+    if (e == hipSuccess) e = grow_buffer(&c->d_stream_segs, &c->stream_segs_cap, n, EIGHTH);
+    if (e == hipSuccess && !on_device) e = grow_buffer(&c->d_stream_seq, &c->stream_seq_cap, n, EIGHTH);
+    if (e != hipSuccess) return alloc_fail(e, "%s: the sorts' and the scans' buffers (%llu payloads) could not be allocated", who, (unsigned long long)n);
+    const uint32_t *d_seq = seq;
+    if (!on_device) {
+        HIP_TRY(upload_split(c->d_stream_seq, reinterpret_cast<const uint8_t *>(seq), n * sizeof(uint32_t), c->stream));
+        d_seq = c->d_stream_seq;
+    }
+    hipEvent_t e1;
+    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_seam_keys(src->d_meta, src->d_flow_of, src->d_flow_recs, n, c->d_seam_sort, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_seam_sort(n, src->n_flows, c->d_seam_sort, (size_t)c->seam_sort_cap, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_stream_phase1(src->d_len, n, c->d_seam_sort, c->fr_ws, c->fr_tot, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(hipMemcpyAsync(c->h_small, c->fr_tot, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));         /* (pinned: no staging) */
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    unsigned long long tot[2] = {0, 0};
+    memcpy(tot, c->h_small, sizeof tot);
+    const uint64_t total = tot[0], ns = tot[1];                              /* bytes of all members; streams, at least one */
+    e = grow_buffer(&c->d_streams, &c->streams_cap, ns, EIGHTH);
+    if (e == hipSuccess) e = grow_buffer(&c->d_stream_orders, &c->stream_orders_cap, ns, EIGHTH);
+    if (e == hipSuccess) e = grow_buffer(&c->d_meta, &c->meta_cap, ns, EIGHTH);
+    if (e != hipSuccess) return alloc_fail(e, "%s: the records of %llu streams could not be allocated", who, (unsigned long long)ns);
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_stream_seq_order(src->d_meta, d_seq, n, ns, src->n_flows, c->d_seam_sort, c->fr_ws, c->d_stream_seq_ws,
+                                        (size_t)c->stream_seq_ws_cap, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_stream_seq_scans(src->d_len, n, c->d_seam_sort, c->fr_ws, c->d_stream_seq_ws, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_stream_seq_records(src->d_meta, d_seq, n, total, ns, depth, c->d_seam_sort, c->fr_ws, c->d_stream_seq_ws, c->d_streams,
+                                          c->d_stream_orders, c->d_meta, c->fr_tot, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    /* the second read: the arena's size follows from the cut lengths, which follow from the first read's n_streams */
+    HIP_TRY(hipMemcpyAsync(c->h_small, c->fr_tot, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    memcpy(tot, c->h_small, sizeof tot);
+    const uint64_t arena_bytes = tot[0] + 64;
+    e = ensure_owned_arena(c, arena_bytes, ns, EIGHTH);                      /* (on failure dst is empty and usable) */
+    if (e != hipSuccess)
+        return alloc_fail(e, "%s: an arena of %llu bytes / %llu streams could not be allocated", who, (unsigned long long)(arena_bytes + arena_bytes / 8),
+                          (unsigned long long)(ns + ns / 8));
+    HIP_TRY(hipMemsetAsync(c->owned_arena + tot[0], 0, 64, c->stream));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_stream_seq_index(src->d_off, src->d_len, n, ns, c->d_seam_sort, c->fr_ws, c->d_stream_seq_ws, c->owned_off, c->owned_len,
+                                        c->d_stream_map, c->d_stream_segs, c->fr_src, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_stream_seq_gather(src->d_arena, c->fr_src, n, tot[0], c->owned_arena, c->nontemporal != 0, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    IndexFacts f;
+    int rc = validate_index(c, who, c->owned_off, c->owned_len, ns, arena_bytes, &f);
+    /* kmp_sseq_gather_kernel writes every slot whole: stream, then 0x00 up to the slot's end */
+    if (!rc) rc = install_arena(c, c->owned_arena, c->owned_off, c->owned_len, arena_bytes, ns, f, /* wrote_padding = */ true);
+    if (rc) { release_arena(c, true); return rc; }
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
+    c->last.kernel_ms = ms; c->last.launches = 16;
+    c->has_meta = true;
+    c->n_streams = ns; c->n_stream_map = n; c->streams_valid = c->stream_order_valid = true;
+    if (n_streams) *n_streams = ns;
+    return KMPGPU_OK;
+}
+
+int kmpgpu_stream_segs_read(kmpgpu_ctx *c, kmpgpu_stream_seg *out, uint64_t first, uint64_t n)
+{
+    static_assert(sizeof(kmpgpu_stream_seg) == 16, "kmpgpu_stream_seg is the 16-byte record of kmpgpu.h");
+    const char *who = "kmpgpu_stream_segs_read";
+    if (c && c->streams_valid && !c->stream_order_valid)
+        return fail(KMPGPU_ESTATE, "%s: no sequence order (the streams were built by kmpgpu_load_streams)", who);
+    return streams_read_range(c, who, out, c ? c->d_stream_segs : nullptr, sizeof(kmpgpu_stream_seg), first, n, c ? c->n_stream_map : 0);
+}
+
+int kmpgpu_stream_orders_read(kmpgpu_ctx *c, kmpgpu_stream_order *out, uint64_t first, uint64_t n)
+{
+    static_assert(sizeof(kmpgpu_stream_order) == 32, "kmpgpu_stream_order is the 32-byte record of kmpgpu.h");
+    const char *who = "kmpgpu_stream_orders_read";
+    if (c && c->streams_valid && !c->stream_order_valid)
+        return fail(KMPGPU_ESTATE, "%s: no sequence order (the streams were built by kmpgpu_load_streams)", who);
+    return streams_read_range(c, who, out, c ? c->d_stream_orders : nullptr, sizeof(kmpgpu_stream_order), first, n, c ? c->n_streams : 0);
 }
 
 int kmpgpu_scan_enqueue(kmpgpu_ctx *c, void *d_counts_out)

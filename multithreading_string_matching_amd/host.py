@@ -174,10 +174,11 @@ def parse_regexes(path: str, n_patterns: int) -> list:
 class HostArena:
     """One contiguous payload arena + {offset, length} index, 16-byte aligned slots."""
 
-    def __init__(self, arena: Arena, owner: bool = True, meta: Optional[np.ndarray] = None):
+    def __init__(self, arena: Arena, owner: bool = True, meta: Optional[np.ndarray] = None, seq: Optional[np.ndarray] = None):
         self._a = arena
         self._owner = owner
         self.meta = meta           # META_DTYPE[n_pkts] where the arena was built with_meta, else None
+        self.seq = seq             # uint32[n_pkts] where the arena was built with_seq, else None
         n = int(arena.n_pkts)
         self.n_pkts = n
         self.n_frames = int(arena.n_frames)
@@ -188,9 +189,10 @@ class HostArena:
         self.len = np.ctypeslib.as_array(arena.len, shape=(max(n, 1),))[:n]
 
     @classmethod
-    def from_pcap(cls, path: str, proto: str = "udp", pinned: bool = False, with_meta: bool = False) -> "HostArena":
+    def from_pcap(cls, path: str, proto: str = "udp", pinned: bool = False, with_meta: bool = False, with_seq: bool = False) -> "HostArena":
         """serial.c:115-141: read every record, extract, store (invalid frames skipped).  with_meta: the identical arena, and in
-        ``.meta`` the accepted frames' header fields in payload order (kmp_arena_from_pcap_meta), as GpuMatcher.set_meta takes them."""
+        ``.meta`` the accepted frames' header fields in payload order (kmp_arena_from_pcap_meta), as GpuMatcher.set_meta takes them.
+        with_seq: in ``.seq`` their TCP sequence numbers (kmp_arena_from_pcap_seq), as GpuMatcher.load_streams(seq=...) takes them."""
         L = _lib.host_lib()
         a = Arena()
         err = C.create_string_buffer(_lib.KMP_PCAP_ERRBUF)
@@ -200,7 +202,11 @@ class HostArena:
             alloc = C.cast(g.kmpgpu_host_alloc, C.c_void_p)
             free = C.cast(g.kmpgpu_host_free, C.c_void_p)
         mp = C.POINTER(_lib.PktMeta)()
-        if with_meta:
+        sp = _lib.u32p()
+        if with_seq:
+            rc = L.kmp_arena_from_pcap_seq(path.encode(), PROTO[proto], alloc, free, C.byref(a), err, C.byref(mp) if with_meta else None,
+                                           C.byref(sp))
+        elif with_meta:
             rc = L.kmp_arena_from_pcap_meta(path.encode(), PROTO[proto], alloc, free, C.byref(a), err, C.byref(mp))
         else:
             rc = L.kmp_arena_from_pcap(path.encode(), PROTO[proto], alloc, free, C.byref(a), err)
@@ -210,7 +216,11 @@ class HostArena:
         if with_meta:
             meta = np.frombuffer(C.string_at(mp, int(a.n_pkts) * 16), dtype=META_DTYPE).copy() if a.n_pkts else np.zeros(0, META_DTYPE)
             C.CDLL(None).free(C.cast(mp, C.c_void_p))       # (malloc'ed by the library, kmphost.h)
-        return cls(a, meta=meta)
+        seq = None
+        if with_seq:
+            seq = np.frombuffer(C.string_at(sp, int(a.n_pkts) * 4), dtype=np.uint32).copy() if a.n_pkts else np.zeros(0, np.uint32)
+            C.CDLL(None).free(C.cast(sp, C.c_void_p))
+        return cls(a, meta=meta, seq=seq)
 
     @classmethod
     def from_payloads(cls, payloads: Sequence[bytes]) -> "HostArena":

@@ -42,6 +42,9 @@ STREAM_DEPTH_MAX = 1 << 30     # KMPGPU_STREAM_DEPTH_MAX
 STREAM_DTYPE = np.dtype([("first_packet", "<u8"), ("last_packet", "<u8"), ("n_packets", "<u8"), ("bytes", "<u8"), ("flow", "<u4"),
                          ("dir", "<u4"), ("len", "<u4"), ("reserved", "<u4")])      # kmpgpu_stream, 48 bytes
 STREAM_POS_DTYPE = np.dtype([("stream", "<u4"), ("reserved", "<u4"), ("pos", "<u8")])      # kmpgpu_stream_pos, 16 bytes
+STREAM_SEG_DTYPE = np.dtype([("skip", "<u4"), ("take", "<u4"), ("seq_off", "<u4"), ("reserved", "<u4")])      # kmpgpu_stream_seg, 16 bytes
+STREAM_ORDER_DTYPE = np.dtype([("seq_base", "<u4"), ("n_gaps", "<u4"), ("gap_bytes", "<u8"), ("dup_bytes", "<u8"), ("tcp", "<u4"),
+                               ("reserved", "<u4")])      # kmpgpu_stream_order, 32 bytes
 
 
 def device_count() -> int:
@@ -107,6 +110,40 @@ def stream_locate(stream_map: np.ndarray, stream, offset) -> Tuple[np.ndarray, n
     st = stream.ravel().astype(np.int64)
     j = np.searchsorted(key, base[st] + np.minimum(offset.ravel(), last_pos[st]), side="right") - 1
     return order[j].astype(np.uint64).reshape(stream.shape), (offset.ravel() - p_sorted[j]).reshape(stream.shape)
+
+
+def stream_locate_ordered(stream_map: np.ndarray, segs: np.ndarray, stream, offset) -> Tuple[np.ndarray, np.ndarray]:
+    """stream_locate for streams built with load_streams(seq=...): (payload, offset_in_payload) of the bytes at ``offset`` of the stream
+    payloads ``stream``, from stream_map() and stream_segs().  Member k holds the stream's bytes [pos, pos + take), which are its own
+    bytes from ``skip`` on; a member of which nothing was kept holds none.  An offset at or behind the stream's last kept byte is a
+    ValueError.  No device needed."""
+    stream_map, segs = np.asarray(stream_map), np.asarray(segs)
+    if stream_map.dtype != STREAM_POS_DTYPE or segs.dtype != STREAM_SEG_DTYPE or stream_map.shape != segs.shape:
+        raise ValueError("stream_locate_ordered: STREAM_POS_DTYPE and STREAM_SEG_DTYPE arrays of one length are needed")
+    stream = np.asarray(stream, dtype=np.uint64)
+    offset = np.asarray(offset, dtype=np.uint64)
+    if stream.shape != offset.shape:
+        raise ValueError(f"stream{list(stream.shape)} and offset{list(offset.shape)} differ in shape")
+    if stream.size == 0:
+        return np.zeros(stream.shape, np.uint64), np.zeros(stream.shape, np.uint64)
+    kept = np.flatnonzero(segs["take"] > 0)
+    # pos < 2^32 * 2^30 and stream < 2^31 do not fit one 64-bit key in general; offsets inside a stream are below 2^31 (the depth), and a
+    # member that starts behind that holds no byte anyone asks for
+    kept = kept[stream_map["pos"][kept] < np.uint64(1 << 31)]
+    key = stream_map["stream"][kept].astype(np.uint64) << np.uint64(31) | stream_map["pos"][kept]
+    order = np.argsort(key, kind="stable")
+    key, kept = key[order], kept[order]
+    if offset.size and int(offset.max()) >= 1 << 31:
+        raise ValueError("stream_locate_ordered: an offset of 2^31 or more")
+    j = np.searchsorted(key, stream.ravel() << np.uint64(31) | offset.ravel(), side="right") - 1
+    k = kept[np.maximum(j, 0)] if kept.size else np.zeros(j.shape, np.int64)
+    inside = (j >= 0) & (kept.size > 0)
+    if kept.size:
+        within = offset.ravel() - stream_map["pos"][k]
+        inside &= (stream_map["stream"][k] == stream.ravel()) & (within < segs["take"][k])
+    if not inside.all():
+        raise ValueError("stream_locate_ordered: an offset behind its stream's last kept byte")
+    return k.astype(np.uint64).reshape(stream.shape), (within + segs["skip"][k]).astype(np.uint64).reshape(stream.shape)
 
 
 class GpuMatcher:
@@ -735,14 +772,41 @@ class GpuMatcher:
         return self._scan_flow_rows(call, "kmpgpu_scan_flows_seams", len(self.rules), hits)
 
     # -- flow streams ------------------------------------------------------------------------------
-    def load_streams(self, src: "GpuMatcher", depth: int = 1 << 20) -> int:
+    def load_streams(self, src: "GpuMatcher", depth: int = 1 << 20, seq=None) -> int:
         """Make this matcher's arena the reassembled streams of ``src``, whose flows are built (kmpgpu_load_streams): the payloads of
         every (flow, direction) concatenated in capture order and cut to ``depth`` bytes, as one payload each, numbered by
         flow << 1 | dir.  Every scan of this matcher then sees a content however it was cut into segments; build_flows() here, with the
         flag ``src``'s flows were built with, reproduces ``src``'s flow numbering.  Patterns, rules, windows and options of this matcher
-        stay.  Returns the number of streams."""
+        stay.  Returns the number of streams.
+
+        seq: one 32-bit TCP sequence number per payload of ``src`` -- a numpy array, or a contiguous torch tensor of 32-bit integers on
+        ``src``'s device, handed over as it is -- builds the TCP streams in sequence order instead (kmpgpu_load_streams_ordered):
+        retransmitted bytes dropped, holes closed; stream_segs() and stream_orders() then say what was kept."""
         n = C.c_uint64()
-        gpu_check(self._g.kmpgpu_load_streams(self._ctx, src._ctx, int(depth), C.byref(n)), "kmpgpu_load_streams")
+        if seq is None:
+            gpu_check(self._g.kmpgpu_load_streams(self._ctx, src._ctx, int(depth), C.byref(n)), "kmpgpu_load_streams")
+        else:
+            n_src, _ = src.arena_info()
+            on_device = 0
+            if isinstance(seq, np.ndarray) or not hasattr(seq, "is_cuda"):
+                words = np.ascontiguousarray(np.asarray(seq).astype(np.uint32, copy=False)).reshape(-1)
+                if words.size != n_src:
+                    raise ValueError(f"seq: {words.size} sequence numbers for {n_src} payloads")
+                ptr = words.ctypes.data if n_src else None
+            else:                                 # a torch tensor
+                if seq.dtype.itemsize != 4 or seq.dtype.is_floating_point or seq.numel() != n_src:
+                    raise ValueError(f"seq: a tensor of {n_src} 32-bit integers is needed")
+                if seq.is_cuda:
+                    if seq.device.index != src.device or not seq.is_contiguous():
+                        raise ValueError("seq: the tensor must be contiguous and on the source's device")
+                    import torch
+                    torch.cuda.current_stream(seq.device).synchronize()      # complete before the call (kmpgpu.h)
+                    on_device, ptr = 1, (seq.data_ptr() if n_src else None)
+                else:
+                    words = np.ascontiguousarray(seq.numpy()).view(np.uint32).reshape(-1)
+                    ptr = words.ctypes.data if n_src else None
+            gpu_check(self._g.kmpgpu_load_streams_ordered(self._ctx, src._ctx, int(depth), ptr, on_device, C.byref(n)),
+                      "kmpgpu_load_streams_ordered")
         self._keep = None
         self._n_streams = int(n.value)
         self._n_stream_map = src.arena_info()[0]
@@ -763,6 +827,16 @@ class GpuMatcher:
         """Entries [first, first + n) of the map (kmpgpu_stream_map_read), one per payload of the source, as a STREAM_POS_DTYPE array;
         n None: all from ``first`` on.  stream_locate() maps offsets in streams back through it."""
         return self._stream_read(self._g.kmpgpu_stream_map_read, "kmpgpu_stream_map_read", "_n_stream_map", STREAM_POS_DTYPE, first, n)
+
+    def stream_segs(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """Entries [first, first + n) of what load_streams(seq=...) kept of every payload of the source (kmpgpu_stream_segs_read) as a
+        STREAM_SEG_DTYPE array; n None: all from ``first`` on.  stream_locate_ordered() maps offsets in streams back through it."""
+        return self._stream_read(self._g.kmpgpu_stream_segs_read, "kmpgpu_stream_segs_read", "_n_stream_map", STREAM_SEG_DTYPE, first, n)
+
+    def stream_orders(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """Records [first, first + n) of the streams' sequence order (kmpgpu_stream_orders_read) as a STREAM_ORDER_DTYPE array: the
+        lowest sequence number, gaps and dropped bytes; n None: all from ``first`` on."""
+        return self._stream_read(self._g.kmpgpu_stream_orders_read, "kmpgpu_stream_orders_read", "_n_streams", STREAM_ORDER_DTYPE, first, n)
 
     def select_flows(self, bits, device: bool = False):
         """The payloads of the chosen flows as a payload bitmap (kmpgpu_flows_select): bits is bool[n_flows] or uint64[ceil(n_flows / 64)]
