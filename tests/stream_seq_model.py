@@ -88,6 +88,50 @@ def build(pay, meta, seq, depth, directed=False, fo=None):
     return streams, recs, pos, segs, orders, origin
 
 
+def build_np(lens, meta, seq, depth, directed=False):
+    """(recs, pos, segs, orders) of build without the Python loops and without the bytes, for hundreds of thousands of payloads: the
+    members sorted by (stream, off, k) with one lexsort, then the running maximum of off + L inside every stream, the kernels' formulation
+    (kept_by_maximum below).  Every stream's ends are moved behind those of the stream before it (stream << 33: an end is below 2^33), so
+    one maximum.accumulate serves all streams.  tests/test_streams_seq_high_model.py holds it to build."""
+    assert 1 <= depth <= TM.DEPTH_MAX
+    lens, seq = np.asarray(lens, dtype=np.int64), np.asarray(seq).astype(np.uint32).astype(np.int64)
+    recs, pos = TM.records_np(meta, lens, depth, directed)              # first, last, n_packets, flow, dir; pos["stream"]
+    n, S = len(lens), len(recs)
+    segs, orders = np.zeros(n, dtype=SEG_DTYPE), np.zeros(S, dtype=ORDER_DTYPE)
+    if n == 0:
+        return recs, pos, segs, orders
+    st = pos["stream"].astype(np.int64)
+    first = recs["first_packet"].astype(np.int64)
+    tcp = np.asarray(meta["proto"])[first] == 6
+    r = (seq - seq[first][st]) & 0xFFFFFFFF
+    r = np.where(tcp[st], np.where(r >= 1 << 31, r - (1 << 32), r), 0)
+    low = np.full(S, 1 << 40, dtype=np.int64)
+    np.minimum.at(low, st, r)
+    off = r - low[st]
+    k = np.lexsort((np.arange(n), off, st))
+    ks, ko, kL = st[k], off[k], lens[k]
+    head = np.ones(n, dtype=bool)
+    head[1:] = ks[1:] != ks[:-1]
+    hp = np.flatnonzero(head)
+    ep = np.concatenate([hp[1:], [n]])
+    incl = np.maximum.accumulate(ks << 33 | np.where(tcp[ks], ko + kL, 0))         # (a stream that is not TCP covers nothing)
+    M = np.where(head, 0, np.concatenate([[0], incl[:-1]]) & ((1 << 33) - 1))       # exclusive, 0 at every stream's first member
+    skip = np.clip(M - ko, 0, kL)
+    take = kL - skip
+    gap = ~head & (ko > M) & tcp[ks]
+    excl = np.cumsum(take) - take
+    kept = np.add.reduceat(take, hp)
+    segs["skip"][k], segs["take"][k], segs["seq_off"][k] = skip, take, ko
+    pos["pos"][k] = excl - excl[hp][ks]
+    recs["bytes"], recs["len"] = kept, np.minimum(kept, depth)
+    orders["tcp"] = tcp
+    orders["n_gaps"] = np.add.reduceat(gap.astype(np.int64), hp)
+    orders["gap_bytes"] = np.where(tcp, (incl[ep - 1] & ((1 << 33) - 1)) - kept, 0)
+    orders["dup_bytes"] = np.add.reduceat(kL, hp) - kept
+    orders["seq_base"] = np.where(tcp, (seq[first] + low) & 0xFFFFFFFF, 0)
+    return recs, pos, segs, orders
+
+
 def kept_by_maximum(lens, offs):
     """[(skip, take)] of members given in (off, k) order by the running maximum, the kernels' formulation: skip = min(L, max(0, M - off))"""
     out, M = [], 0
