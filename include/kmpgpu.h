@@ -696,11 +696,27 @@ int  kmpgpu_scan_bytetests(kmpgpu_ctx *ctx, uint64_t *bt_pkt_counts_out /* [n_bt
  * Cost: an expression is a position automaton of at most 63 positions stepped with a handful of 64-bit operations per
  * text byte; its cost is deterministic, its state one 64-bit word, and no memory grows with the payload.  n_rx further rows of the hit
  * matrix, (n_rx x W2 + n_rx) x 8 bytes, and 2080 bytes of table per expression.  The kernel reads every payload's text once per 8
- * expressions, up to the byte at which every expression of the eight is decided. */
+ * expressions, up to the byte at which every expression of the eight is decided.
+ *
+ * KMPGPU_RX_GROUPS, per expression: the dialect above plus groups and alternation.  ( ... ) and (?: ... ) are groups and
+ * mean the same, nothing is captured; | alternates inside a group and at top level; ? * + {n} {n,} {n,m} may stand behind a group, and
+ * groups nest, at most 32 deep.  Positions are counted after unrolling: G{n,m} is n copies of G and m - n optional ones, G{n,} n - 1
+ * copies and one G+, G* an optional G+.  Refused, in the form above: every other (? form, an empty group or alternative ((a|), (), a||b,
+ * |a), a top-level | beside a leading ^ or a trailing $ (write ^(a|b)$: Python reads ^a|b$ as (^a)|(b$)), ^ or $ inside a group, a
+ * quantifier on a quantifier ((a)+? too), an unterminated group, a ) without its opening, more than KMPGPU_RX_MAX_POSITIONS positions, and
+ * an expression whose automaton needs more than KMPGPU_RX_MAX_EDGES edge rules ("position 0: needs R edge rules, more than 8").  ("position 0: internal: ..." is the compiler's self-check of that
+ * derivation; no expression reaches it, kmp_regex.cpp says why.)  The
+ * meaning, $, the text end, the gate and the flags are the ones above; an expression with the flag and without ( ) | gives the rows it
+ * gives without it.  Without the flag ( ) | stay refused, and bit 8u stays unknown.  A flagged expression costs 2224 bytes of a second
+ * table beside its slot of the first.  Launch order wherever the regex kernel runs: the linear kernel if any expression lacks the flag,
+ * then the grouped kernel (kmp_regex_groups.hip) if any carries it, both on the context's stream and both recorded by a running profile
+ * in front of the rules kernel; a set without a flagged expression launches what it launched. */
 #define KMPGPU_RX_NOCASE 1u       /* ASCII case-insensitive */
 #define KMPGPU_RX_DOTALL 2u       /* . matches 0x0A too */
 #define KMPGPU_RX_GATED  4u       /* only in payloads that hold pattern gate[q] */
+#define KMPGPU_RX_GROUPS 16u      /* groups and alternation: the dialect's additions above (bit 8u stays unknown) */
 #define KMPGPU_RX_MAX_POSITIONS 63
+#define KMPGPU_RX_MAX_EDGES 8     /* edge rules of an expression under KMPGPU_RX_GROUPS */
 int  kmpgpu_set_regexes(kmpgpu_ctx *ctx, const uint8_t *const *expr /* [n_rx] */, const uint32_t *expr_len /* [n_rx] */,
                         const uint32_t *flags /* [n_rx]; NULL = all 0 */, const uint32_t *gate /* [n_rx]; NULL = none gated */, uint32_t n_rx);
 int  kmpgpu_scan_regexes(kmpgpu_ctx *ctx, uint64_t *rx_pkt_counts_out /* [n_rx] or NULL */, uint64_t *any_out /* [W] or NULL */,

@@ -239,7 +239,8 @@ void kmp_bytetests_free(kmp_bytetests *b);
  * Not in the reference: the expressions of kmpgpu_set_regexes (include/kmpgpu.h, where the dialect is) from a text file.  One per line,
  *     /EXPR/[i][s] [with <pattern index>]
  * EXPR runs from behind the first '/' to the last '/' of the line and is taken byte for byte (a '/' inside it needs no escape); i makes it
- * case-insensitive (KMP_RX_NOCASE), s lets the dot match a newline (KMP_RX_DOTALL); with <i> gates it on pattern i (a position in the
+ * case-insensitive (KMP_RX_NOCASE), s lets the dot match a newline (KMP_RX_DOTALL), a third letter e ("extended", KMP_RX_GROUPS) makes
+ * ( ), (?: ) and | groups and alternation: /(GET|POST) \//ie with 3; with <i> gates it on pattern i (a position in the
  * pattern file, 0-based; KMP_RX_GATED): it is looked at only in payloads that hold that pattern.  Blank lines and lines whose first
  * non-blank character is '#' are skipped; expression index = order of the lines.  expr, len, flags and gate are what kmpgpu_set_regexes
  * takes; the dialect itself is checked there, not here.
@@ -250,6 +251,7 @@ void kmp_bytetests_free(kmp_bytetests *b);
 #define KMP_RX_NOCASE 1u
 #define KMP_RX_DOTALL 2u
 #define KMP_RX_GATED  4u
+#define KMP_RX_GROUPS 16u     /* flag letter e ("extended"): groups and alternation (KMPGPU_RX_GROUPS), /(GET|POST) \//ie with 3 */
 typedef struct kmp_regexes {
     uint32_t        n;       /* number of expressions                                  */
     const uint8_t **expr;    /* [n]: expression q, len[q] bytes, inside `bytes`         */

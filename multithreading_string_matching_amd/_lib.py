@@ -35,7 +35,10 @@ BT_RELATIVE, BT_LITTLE = 1, 2     # KMPGPU_BT_* / KMP_BT_*: flags of a byte test
 BT_EQ, BT_NE, BT_LT, BT_GT, BT_LE, BT_GE = range(6)    # ... and its operators
 BT_TILE = 128              # KMP_BT_TILE (csrc/kmp_launch.h): tests the absolute byte-test kernel stages at a time
 RX_NOCASE, RX_DOTALL, RX_GATED = 1, 2, 4   # KMPGPU_RX_*: flags of an expression (kmpgpu_set_regexes)
+RX_GROUPS = 16             # KMPGPU_RX_GROUPS: groups and alternation
 RX_MAX_POSITIONS = 63      # KMPGPU_RX_MAX_POSITIONS
+RX_MAX_EDGES = 8           # KMPGPU_RX_MAX_EDGES: edge rules of an expression under RX_GROUPS
+RXG_TILE = 4               # KMP_RXG_TILE (csrc/kmp_regex.h): expressions the grouped regex kernel stages at a time
 RX_TILE = 8                # KMP_RX_TILE (csrc/kmp_regex.h): expressions the regex kernel stages at a time
 CHAIN_MAX = 8              # KMPGPU_CHAIN_MAX / KMP_CHAIN_MAX: contents of one chain
 REL_NO_MIN = -(1 << 31)    # kmpgpu_relation.dmin == INT32_MIN: no lower bound

@@ -1110,7 +1110,7 @@ static int regexes_line(void *ctx, const char *p, const char *end, size_t lineno
     uint32_t flags = 0, gate = 0;
     const char *q = close;
     for (; q < end && !is_c_space((uint8_t)*q); q++) {
-        const uint32_t f = *q == 'i' ? KMP_RX_NOCASE : *q == 's' ? KMP_RX_DOTALL : 0u;
+        const uint32_t f = *q == 'i' ? KMP_RX_NOCASE : *q == 's' ? KMP_RX_DOTALL : *q == 'e' ? KMP_RX_GROUPS : 0u;
         if (!f) return line_error(errbuf, lineno, "'%c' is not a flag (i: nocase, s: dotall)", *q);
         if (flags & f) return line_error(errbuf, lineno, "flag '%c' twice", *q);
         flags |= f;

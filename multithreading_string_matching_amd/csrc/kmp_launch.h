@@ -164,6 +164,12 @@ hipError_t kmp_launch_bytetests(bool relative, const unsigned long long *marks, 
 hipError_t kmp_launch_regexes(const unsigned long long *marks, uint64_t stride, uint64_t n_pkts, const uint4 *tables, uint32_t n_rx,
                               const uint8_t *arena, const uint64_t *pkt_off, const uint32_t *pkt_len, bool whole,
                               unsigned long long *rows, unsigned long long *rx_counts, unsigned long long *any, hipStream_t st);
+/* kmp_regex_groups.hip: the expressions under KMPGPU_RX_GROUPS, behind kmp_launch_regexes with its arguments.  tables: the tiles of
+ * KMP_RXG_TILE expressions as kmp_pack_regex_groups leaves them, n_groups of them; each writes every word of the row rows[q][stride] its
+ * record names, adds to rx_counts[q] and ORs into any[].  No other row is written. */
+hipError_t kmp_launch_regex_groups(const unsigned long long *marks, uint64_t stride, uint64_t n_pkts, const uint4 *tables, uint32_t n_groups,
+                                   const uint8_t *arena, const uint64_t *pkt_off, const uint32_t *pkt_len, bool whole,
+                                   unsigned long long *rows, unsigned long long *rx_counts, unsigned long long *any, hipStream_t st);
 /* ... and the metadata itself.  _extract: behind kmp_launch_extract_phase2, with its arguments and its workspace: meta[k] of every accepted
  * frame, k as kmp_scatter_index_kernel numbers the payloads.  _select: behind kmp_launch_select_phase2, with the workspace of the selection
  * over src's n payloads: meta[j] = src_meta[k] for the j-th selected payload k.  One kernel each. */

@@ -85,9 +85,19 @@ int kmp_pack_bytetests(const kmpgpu_bytetest *bt, uint32_t n_bt, uint32_t n_pat,
 /* (defined in kmp_regex.cpp, beside the compiler it calls: kmp_rowtables.cpp links without it)  The expressions compiled (kmp_regex.h:
  * kmp_regex_compile) and laid out in tiles of KMP_RX_TILE as kmp_regex.h describes the device table;
  * ceil(n_rx / KMP_RX_TILE) * KMP_RX_TILE_WORDS words.  flags NULL: all 0; gate NULL: none gated.  An unknown flag bit, a gate >= n_pat of
- * a gated expression, a gate != 0 of one that is not, an expression outside the dialect ("expression Q: position P: ..."): KMPGPU_EINVAL. */
+ * a gated expression, a gate != 0 of one that is not, an expression outside the dialect ("expression Q: position P: ..."): KMPGPU_EINVAL.
+ * An expression under KMPGPU_RX_GROUPS is checked here too (kmp_regex_compile_groups), so this one call refuses a bad set; its slot holds a
+ * placeholder -- one position that no byte takes, gated on the expression's own row n_pat + n_rel + n_chains + n_hdr + n_bt + q, which the
+ * marking pass has zeroed: no lane is active for it and the linear kernel stores zeros there.  A set without the flag packs as it did. */
 int kmp_pack_regexes(const uint8_t *const *expr, const uint32_t *expr_len, const uint32_t *flags, const uint32_t *gate, uint32_t n_rx,
                      uint32_t n_pat, uint32_t n_rel, uint32_t n_chains, uint32_t n_hdr, uint32_t n_bt, std::vector<uint32_t> *tables,
                      std::string *msg);
+
+/* (kmp_regex.cpp too)  The second device table: the expressions under KMPGPU_RX_GROUPS alone, in their order, in tiles of KMP_RXG_TILE as
+ * kmp_regex.h describes them, each record carrying its expression's index q; ceil(*n_groups / KMP_RXG_TILE) * KMP_RXG_TILE_WORDS words,
+ * none where no expression carries the flag.  The same checks and messages as kmp_pack_regexes. */
+int kmp_pack_regex_groups(const uint8_t *const *expr, const uint32_t *expr_len, const uint32_t *flags, const uint32_t *gate, uint32_t n_rx,
+                          uint32_t n_pat, uint32_t n_rel, uint32_t n_chains, uint32_t n_hdr, uint32_t n_bt, std::vector<uint32_t> *tables,
+                          uint32_t *n_groups, std::string *msg);
 
 #endif

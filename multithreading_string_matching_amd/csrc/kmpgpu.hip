@@ -200,6 +200,9 @@ struct kmpgpu_ctx {
      * Expression q is row n_pat + n_rel + n_chains + n_hdr + n_bt + q of the hit matrix and that term of a rule */
     uint32_t            n_rx = 0;
     uint4              *d_regexes = nullptr;
+    /* ... and of those the ones under KMPGPU_RX_GROUPS once more, in tiles of KMP_RXG_TILE for their own kernel (kmp_launch_regex_groups) */
+    uint32_t            n_rx_groups = 0;
+    uint4              *d_regex_groups = nullptr;
     /* the per-payload metadata the predicates are decided from (kmpgpu_pkt_meta, 16 bytes each), in payload order.  It belongs to the arena:
      * has_meta falls with it (release_arena), the buffer is kept for the next one */
     uint4              *d_meta = nullptr;
@@ -444,7 +447,8 @@ void drop_bytetests(kmpgpu_ctx *c)
 void drop_regexes(kmpgpu_ctx *c)
 {
     free_buffer(&c->d_regexes);
-    c->n_rx = 0;
+    free_buffer(&c->d_regex_groups);
+    c->n_rx = c->n_rx_groups = 0;
 }
 
 /* the flows go with the arena and its metadata; their buffers are kept for the next build */
@@ -2268,16 +2272,27 @@ int enqueue_bytetests(kmpgpu_ctx *c, const MarkPass &p, uint32_t *launches)
     return KMPGPU_OK;
 }
 
-/* The regex kernel behind a marking pass, in the same way: one launch */
-int enqueue_regexes(kmpgpu_ctx *c, const MarkPass &p)
+/* The regex kernels behind a marking pass, in the same way: the linear one where an expression lacks KMPGPU_RX_GROUPS, then the grouped
+ * one where an expression carries it.  *launches: how many that were. */
+int enqueue_regexes(kmpgpu_ctx *c, const MarkPass &p, uint32_t *launches)
 {
     FamilyRows f;
     family_rows(c, p, FAMILY_REGEXES, &f);
     hipEvent_t e1;
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_regexes(p.d_mat, p.stride, c->n_pkts, c->d_regexes, c->n_rx, c->d_arena, c->d_off, c->d_len, c->whole_payload != 0,
-                               f.d_rows, f.d_pc, f.d_any, c->stream));
-    HIP_TRY(profile_launched(c, e1));
+    if (c->n_rx_groups < c->n_rx) {
+        HIP_TRY(profile_launch(c, &e1));
+        HIP_TRY(kmp_launch_regexes(p.d_mat, p.stride, c->n_pkts, c->d_regexes, c->n_rx, c->d_arena, c->d_off, c->d_len, c->whole_payload != 0,
+                                   f.d_rows, f.d_pc, f.d_any, c->stream));
+        HIP_TRY(profile_launched(c, e1));
+        ++*launches;
+    }
+    if (c->n_rx_groups) {
+        HIP_TRY(profile_launch(c, &e1));
+        HIP_TRY(kmp_launch_regex_groups(p.d_mat, p.stride, c->n_pkts, c->d_regex_groups, c->n_rx_groups, c->d_arena, c->d_off, c->d_len,
+                                        c->whole_payload != 0, f.d_rows, f.d_pc, f.d_any, c->stream));
+        HIP_TRY(profile_launched(c, e1));
+        ++*launches;
+    }
     return KMPGPU_OK;
 }
 
@@ -2325,9 +2340,8 @@ int enqueue_family(kmpgpu_ctx *c, const char *who, int family, const MarkPass &p
             if (rr) return rr;
         }
         if (c->n_rx) {
-            const int rr = enqueue_regexes(c, p);
+            const int rr = enqueue_regexes(c, p, &f->launches);
             if (rr) return rr;
-            f->launches++;
         }
         HIP_TRY(profile_launch(c, &e1));
         HIP_TRY(kmp_launch_rules(p.d_mat, p.stride, c->n_pkts, c->d_rule_heads, c->d_rule_quads, c->n_rules, f->d_rows, f->d_pc, f->d_any, c->stream));
@@ -2337,8 +2351,8 @@ int enqueue_family(kmpgpu_ctx *c, const char *who, int family, const MarkPass &p
     }
     family_rows(c, p, family, f);
     if (family == FAMILY_BYTETESTS) return enqueue_bytetests(c, p, &f->launches);
+    if (family == FAMILY_REGEXES) return enqueue_regexes(c, p, &f->launches);
     f->launches = 1u;
-    if (family == FAMILY_REGEXES) return enqueue_regexes(c, p);
     return family == FAMILY_HEADERS ? enqueue_headers(c, p) : enqueue_pairing(c, p, family);
 }
 
@@ -2584,16 +2598,20 @@ int kmpgpu_set_regexes(kmpgpu_ctx *c, const uint8_t *const *expr, const uint32_t
 {
     const int sr = setter_state(c, "kmpgpu_set_regexes");
     if (sr) return sr;
-    std::vector<uint32_t> host;
+    std::vector<uint32_t> host, host_groups;
     std::string msg;
+    uint32_t n_groups = 0;
     if (n_rx) {
-        const int rc = kmp_pack_regexes(expr, expr_len, flags, gate, n_rx, c->n_pat, c->n_rel, c->n_chains, c->n_hdr, c->n_bt, &host, &msg);
+        int rc = kmp_pack_regexes(expr, expr_len, flags, gate, n_rx, c->n_pat, c->n_rel, c->n_chains, c->n_hdr, c->n_bt, &host, &msg);
+        if (!rc) rc = kmp_pack_regex_groups(expr, expr_len, flags, gate, n_rx, c->n_pat, c->n_rel, c->n_chains, c->n_hdr, c->n_bt, &host_groups, &n_groups, &msg);
         if (rc) return fail(rc, "%s", msg.c_str());
     }
-    const int rc = swap_tables(c, "kmpgpu_set_regexes: the expressions", {{host, (void **)&c->d_regexes}});
+    /* both tables or neither */
+    const int rc = swap_tables(c, "kmpgpu_set_regexes: the expressions", {{host, (void **)&c->d_regexes}, {host_groups, (void **)&c->d_regex_groups}});
     if (rc) return rc;
     drop_rules(c);                                 /* the rows their terms named are no longer the same, whatever was set or cleared */
     c->n_rx = n_rx;
+    c->n_rx_groups = n_groups;
     return KMPGPU_OK;
 }
 

@@ -160,6 +160,8 @@ def parse_regexes(path: str, n_patterns: int) -> list:
                 opt["nocase"] = True
             if r.flags[q] & _lib.RX_DOTALL:
                 opt["dotall"] = True
+            if r.flags[q] & _lib.RX_GROUPS:
+                opt["groups"] = True
             if r.flags[q] & _lib.RX_GATED:
                 opt["gate"] = int(r.gate[q])
             out.append((C.string_at(r.expr[q], r.len[q]), opt))

@@ -327,7 +327,7 @@ class GpuMatcher:
 
     def set_regexes(self, exprs) -> None:
         """Expressions of byte classes and repeats (kmpgpu_set_regexes; the dialect is in include/kmpgpu.h): a sequence whose entries are
-        ``bytes``, or ``(bytes, dict)`` with any of nocase (ASCII case-insensitive), dotall (. matches 0x0A too) and gate (a pattern index:
+        ``bytes``, or ``(bytes, dict)`` with any of nocase (ASCII case-insensitive), dotall (. matches 0x0A too), groups (( ) (?: ) and | are part of the dialect) and gate (a pattern index:
         the expression is looked at only in payloads that hold that pattern).  Expression q hits a payload where some part of its text,
         up to the text end, is in the expression's language (^: from the first byte, $: up to the text end).  None or an empty sequence
         clears them.  Every successful call drops the rules, as the library does: relations, chains, headers, byte tests, regexes, then
@@ -335,11 +335,12 @@ class GpuMatcher:
         took = []
         for e in exprs or []:
             expr, opt = (e, {}) if isinstance(e, (bytes, bytearray)) else e
-            unknown = set(opt) - {"nocase", "dotall", "gate"}
+            unknown = set(opt) - {"nocase", "dotall", "gate", "groups"}
             if unknown:
                 raise ValueError(f"set_regexes: unknown option(s) {sorted(unknown)}")
             gate = opt.get("gate")
-            flags = (_lib.RX_NOCASE if opt.get("nocase") else 0) | (_lib.RX_DOTALL if opt.get("dotall") else 0) | (0 if gate is None else _lib.RX_GATED)
+            flags = ((_lib.RX_NOCASE if opt.get("nocase") else 0) | (_lib.RX_DOTALL if opt.get("dotall") else 0)
+                     | (0 if gate is None else _lib.RX_GATED) | (_lib.RX_GROUPS if opt.get("groups") else 0))
             took.append((bytes(expr), flags, 0 if gate is None else int(gate)))
         n = len(took)
         bufs = [C.create_string_buffer(e, len(e)) for e, _, _ in took]      # (an expression may hold any byte, escaped or not)

@@ -13,7 +13,11 @@ alike; medians of --reps rounds after a warm-up, with the smallest, the quartile
                         a run of 20 optional positions, and one behind a gate (the bench needle) that every tenth and that every
                         payload holds.  Beside each the share of the payloads it hits (a lane stops walking once every expression of
                         its tile without $ has accepted) and the time per (expression, text byte) as if every byte were walked.  The rows
-                        of the first 4 096 payloads are checked against Python's re."""
+                        of the first 4 096 payloads are checked against Python's re.
+  (3) the grouped kernel  the same for expressions under KMPGPU_RX_GROUPS (kmp_regex_groups.hip), in the same run: one
+                        flagged expression without a rule (the one of (2) that walks every byte, so the two kernels' figures stand side
+                        by side), /(GET|POST|HEAD|PUT) \\//, one at KMPGPU_RX_MAX_EDGES rules, a full tile of KMP_RXG_TILE, 100 flagged
+                        ones, and a mixed set, where the linear and the grouped launch are reported apart."""
 import argparse
 import ctypes as C
 import os
@@ -84,6 +88,23 @@ def gen_exprs(n, seed=7):
             e += rng.choice([b"", b"", b"?", b"+", b"*", b"{2}", b"{1,3}", b"{2,}"])
         out.append(e)
     return out
+
+
+def gen_grouped(n, seed=11):
+    """flagged expressions over text of a..z: a group of two or three alternatives of two or three elements each (no optional element
+    at an alternative's end: a few edge rules, far from KMPGPU_RX_MAX_EDGES), sometimes optional or repeated, and a generated tail"""
+    rng = random.Random(seed)
+
+    def alt():
+        e = b""
+        for _ in range(rng.randrange(2, 4)):
+            lo = rng.randrange(0x61, 0x78)
+            e += rng.choice([bytes([lo]), b"[%c-%c]" % (lo, lo + rng.randrange(1, 4)), b"\\w", b"."]) + rng.choice([b"", b"", b"+", b"{2}"])
+        return e
+
+    tails = gen_exprs(n, seed)
+    return [(b"(" + b"|".join(alt() for _ in range(rng.randrange(2, 4))) + b")" + rng.choice([b"", b"", b"?", b"+"]) + tails[i], {"groups": True})
+            for i in range(n)]
 
 
 def check_rows(m, exprs, head, gate_head, n):
@@ -181,12 +202,12 @@ def main():
         # ---- (2) the kernel
         head, gate_head = head_of_arena()
 
-        def measure(label, exprs):
+        def measure(label, exprs, part="(2)"):
             c.set_regexes(exprs)
             share = check_rows(c, exprs, head, gate_head, n)
             tt, kk = kernel_alone(c, stream, args.reps)
             k_med = statistics.median(kk)
-            say(f"(2) {label}: {share * 100:.1f} % of the payloads per expression; kmpgpu_scan_regexes {spread(tt)}; regex kernel alone {spread(kk)}; "
+            say(f"{part} {label}: {share * 100:.1f} % of the payloads per expression; kmpgpu_scan_regexes {spread(tt)}; regex kernel alone {spread(kk)}; "
                 f"{k_med * 1e9 / len(exprs) / n / L:.3f} ps per (expression, text byte) of {len(exprs)} x {n} x {L}")
 
         for whole in (0, 1):
@@ -199,6 +220,28 @@ def main():
         gated = [(b"qz[a-m]{2,}x$", {"gate": 0})]
         measure("one expression that walks every byte, /qz[a-m]{2,}x$/, ungated", [gated[0][0]])
         measure("the same behind a gate that every tenth payload holds", gated)
+        # ---- (3) the grouped kernel: with every expression flagged it is the only regex launch, the last one of the profile
+        flag = {"groups": True}
+        measure("grouped kernel, one flagged expression without a rule, /qz[a-m]{2,}x$/ (the linear kernel's figure: four lines up)", [(gated[0][0], flag)], "(3)")
+        measure("grouped kernel, /(GET|POST|HEAD|PUT) \\// (1 rule)", [(b"(GET|POST|HEAD|PUT) /", flag)], "(3)")
+        measure(f"grouped kernel, /(ab|cd){{2,4}}e(f|gh)/ ({_lib.RX_MAX_EDGES} rules)", [(b"(ab|cd){2,4}e(f|gh)", flag)], "(3)")
+        measure(f"grouped kernel, a full tile of {_lib.RXG_TILE} generated flagged expressions", gen_grouped(_lib.RXG_TILE), "(3)")
+        measure("grouped kernel, 100 generated flagged expressions", gen_grouped(100), "(3)")
+        # a mixed set: the linear launch, then the grouped one
+        n_lin, n_grp = _lib.RX_TILE, _lib.RXG_TILE
+        mixed = gen_exprs(n_lin) + gen_grouped(n_grp)
+        c.set_regexes(mixed)
+        check_rows(c, mixed, head, gate_head, n)
+        lin_k, grp_k = [], []
+        for rnd in range(3 + args.reps):
+            c.profile_begin(64)
+            c.scan_regexes()
+            prof = c.profile_end(64)
+            if rnd >= 3:
+                lin_k.append(float(prof[-2])); grp_k.append(float(prof[-1]))
+        say(f"(3) mixed set, {n_lin} unflagged + {n_grp} flagged: linear kernel {spread(lin_k)}, "
+            f"{statistics.median(lin_k) * 1e9 / n_lin / n / L:.3f} ps per (expression, text byte); grouped kernel {spread(grp_k)}, "
+            f"{statistics.median(grp_k) * 1e9 / n_grp / n / L:.3f} ps per (expression, text byte)")
         b.synth_fill(d_arena, d_off, d_len, K.SynthParams.make(seed=1234, needle=needle, plant_permille=1000))
         b.sync()
         c.attach_arena(d_arena, d_off, d_len)
