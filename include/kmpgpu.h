@@ -1133,6 +1133,65 @@ int  kmpgpu_load_streams_ordered(kmpgpu_ctx *dst, kmpgpu_ctx *src, uint32_t dept
 int  kmpgpu_stream_segs_read(kmpgpu_ctx *dst, kmpgpu_stream_seg *out, uint64_t first, uint64_t n);
 int  kmpgpu_stream_orders_read(kmpgpu_ctx *dst, kmpgpu_stream_order *out, uint64_t first, uint64_t n);
 
+/* ---- flow bits: rule state carried along a flow's payloads (the `flowbits` of signature languages) --------------------------------------
+ * kmpgpu_set_flowbits gives rules of kmpgpu_set_rules tests and actions on n_bits state bits per flow; kmpgpu_scan_flowbits evaluates
+ * them over the built flows (kmpgpu_flows_build, directed or not, exactly as built) in capture order.
+ *
+ * Definition.  An op is (rule, bit, op): KMPGPU_FB_ISSET / KMPGPU_FB_ISNOTSET are tests, KMPGPU_FB_SET / _UNSET / _TOGGLE actions,
+ * KMPGPU_FB_NOALERT marks the rule (bit ignored).  base[r][k] is the bit kmpgpu_scan_rules defines.  For every flow f with the payloads
+ * k_1 < k_2 < ... and a 32-bit state S that starts at 0, payload after payload:
+ *   1. B = S, the state BEFORE k_j;
+ *   2. fired[r][k_j] = base[r][k_j] AND every test of rule r holds on B -- all rules of a payload see the same B;
+ *   3. S = B changed by the actions of the fired rules, rules in ascending index, a rule's actions in the order they were given;
+ *   4. alert[r][k] = fired[r][k] AND rule r has no KMPGPU_FB_NOALERT.
+ * So a bit a rule sets is seen by testers from the NEXT payload of the flow on, never in the same payload: the one deliberate difference
+ * from engines that order setters before checkers inside a packet, and what makes the state a scan.  `isnotset X; set X` fires exactly once
+ * per flow; two flows never share state; under KMPGPU_FLOW_DIRECTED the two directions of a conversation are two flows and two states.
+ *
+ * How it is parallel.  For one bit a payload's effect is a function {0,1} -> {0,1}, two bits (F(0), F(1)); a rule may test the very bit it
+ * changes, which is F depending on its argument.  Functions compose associatively, so the states before every payload are a scan of
+ * compositions in flow order, restarted at every flow's first payload.  Across different bits there is an edge Y -> X where some rule tests
+ * Y and acts on X, Y != X; this graph must be acyclic (KMPGPU_EINVAL otherwise, the bits of a cycle named in the message), level(X) is the
+ * longest path into X, and the bits are decided level by level, the lower levels' states known.
+ *
+ * kmpgpu_set_flowbits(ctx, ops, n_ops, n_bits): n_ops == 0 clears (ops and n_bits are not looked at).  KMPGPU_ESTATE without rules.
+ * KMPGPU_EINVAL, with the ops set before still in force: n_bits outside 1..KMPGPU_FLOWBITS_MAX, ops NULL, a rule >= n_rules, a bit >= n_bits
+ * (not for NOALERT), an unknown op, a nonzero reserved field, the same (rule, bit) tested both ways, a cycle.  Whatever drops the rules
+ * (kmpgpu_set_patterns, every setter that drops them) and every successful kmpgpu_set_rules drops the ops, whose rule indices meant those
+ * rules; kmpgpu_flows_build keeps them.
+ *
+ * kmpgpu_scan_flowbits: every output may be NULL.  rule_pkt_counts_out[r] = set bits of alert row r, any_out[W] the OR of the alert rows,
+ * rule_hits_out[n_rules * W] the alert rows (a NOALERT rule's row is 0 and adds nothing), state_out[n_bits * W]: bit k of row X = bit X of
+ * the state before payload k, flow_state_out[n_flows]: S after the flow's last payload, counts_out as kmpgpu_scan.  W = ceil(n_pkts / 64),
+ * bits at n_pkts and above are 0.  KMPGPU_ESTATE: no patterns, no arena, no rules, "no flow bits", "no flows" (none built since the arena
+ * or its metadata were set), between kmpgpu_load_frames_begin and _finish; the header predicates' "no packet metadata".  With n_pkts == 0
+ * every count is 0 and nothing is launched.  Results do not depend on the run: no atomic decides a value, and no block waits on another.
+ *
+ * Launches.  The pass of kmpgpu_scan_rules, unchanged.  Once per build of the flows (cached by flow generation): a stable rocPRIM radix
+ * sort of (flow_of[k], k) over the flow ids' significant bits, and one kernel for the inverse order and the head flags.  Per level four
+ * steps: build (a lane per payload: 8 bytes (f0 mask, f1 mask), stored at the payload's sorted position; a flow's first payload stores the
+ * constant function (F(0), F(0)), which is the restart), the scan -- tiles of KMP_SCAN_TILE reduced to one aggregate each, the aggregates
+ * scanned by the same kernels, recursively, then every tile scanned from its carry-in (one kernel where n_pkts <= KMP_SCAN_TILE) --, which
+ * scatters the state before every payload and writes flow_state at every flow's last, and the rows kernel (one ballot per bit of the level).
+ * Last the final pass: alert[r] = base[r] AND the tests, word-wise, with counts and any[].  t->launches counts all of them.
+ * Memory, kept by the context: 13 bytes per payload for the order, rocPRIM's temporary storage, 12 bytes per payload and 8 per tile for
+ * the scan, 4 per flow, the before rows [n_bits][stride] and the alert rows [n_rules][stride] (stride = 2 ceil(W / 2) words).  An allocation
+ * failure is KMPGPU_ENOMEM and leaves the context usable.
+ * Not done: no KMPGPU_ALERT_* family, so kmpgpu_scan_alerts / kmpgpu_scan_flows know nothing of flow bits; no seams or streams. */
+#define KMPGPU_FLOWBITS_MAX 32
+#define KMPGPU_FB_ISSET    0
+#define KMPGPU_FB_ISNOTSET 1
+#define KMPGPU_FB_SET      2
+#define KMPGPU_FB_UNSET    3
+#define KMPGPU_FB_TOGGLE   4
+#define KMPGPU_FB_NOALERT  5
+typedef struct kmpgpu_flowbit_op { uint32_t rule, bit, op, reserved; } kmpgpu_flowbit_op;
+int  kmpgpu_set_flowbits(kmpgpu_ctx *ctx, const kmpgpu_flowbit_op *ops, uint32_t n_ops, uint32_t n_bits);
+int  kmpgpu_scan_flowbits(kmpgpu_ctx *ctx, uint64_t *rule_pkt_counts_out /* [n_rules] or NULL */, uint64_t *any_out /* [W] or NULL */,
+                          uint64_t *rule_hits_out /* [n_rules * W] or NULL */, uint64_t *state_out /* [n_bits * W] or NULL */,
+                          uint32_t *flow_state_out /* [n_flows] or NULL */, uint64_t *counts_out /* [n_pat] or NULL */,
+                          kmpgpu_timing *t /* or NULL */);
+
 /* Fill a device arena with the synthetic payloads of kmp_synth.h (benchmark input S1/S2):
  * packet ids first_pkt_id .. first_pkt_id + n_pkts - 1 at the slots of the given device index. */
 int  kmpgpu_synth_fill(kmpgpu_ctx *ctx, void *d_arena, const void *d_pkt_off, const void *d_pkt_len,

@@ -264,6 +264,31 @@ typedef struct kmp_regexes {
 int  kmp_regexes_parse(const char *path, uint32_t n_patterns, kmp_regexes *out, char errbuf[KMP_REGEXES_ERRBUF]);
 void kmp_regexes_free(kmp_regexes *r);
 
+/* ---- flow bits -------------------------------------------------------------------------------
+ * Not in the reference: the ops of kmpgpu_set_flowbits (include/kmpgpu.h, where they are defined) from a text file.  One line
+ *     <rule> <word> [<word> ...]
+ * gives rule <rule> (a decimal position in the rules file, 0-based) the words' tests and actions in their order: set:<name>
+ * unset:<name> toggle:<name> isset:<name> isnotset:<name> and noalert.  A name is 1..31 characters of [A-Za-z0-9_.-]; names are numbered
+ * by first appearance, at most KMP_FLOWBITS_MAX of them.  A rule may have several lines.  Blank lines and lines whose first non-blank
+ * character is '#' are skipped.  ops is what kmpgpu_set_flowbits takes (kmp_flowbit_op has the layout of kmpgpu_flowbit_op), n_bits the
+ * number of names (1 where only noalert was used); names[b] is bit b's.
+ * KMPHOST_EIO: the file cannot be opened; KMPHOST_EINVAL: a rule that is no number below n_rules, a line without a word, an unknown word,
+ * a name of none of its forms, a 33rd name, a (rule, name) tested both ways -- errbuf then starts with "line N: " (N counts every line of
+ * the file, from 1) --, and, found when the file has been read, names that form a cycle (a rule tests one and acts on the next):
+ * errbuf names them in the cycle's order. */
+#define KMP_FLOWBITS_ERRBUF 256
+#define KMP_FLOWBITS_MAX    32
+#define KMP_FLOWBIT_NAME    32     /* bytes of a name with its 0x00 */
+enum { KMP_FB_ISSET, KMP_FB_ISNOTSET, KMP_FB_SET, KMP_FB_UNSET, KMP_FB_TOGGLE, KMP_FB_NOALERT };
+typedef struct kmp_flowbit_op { uint32_t rule, bit, op, reserved; } kmp_flowbit_op;
+typedef struct kmp_flowbits {
+    uint32_t        n, n_bits;      /* number of ops; of names                       */
+    kmp_flowbit_op *ops;            /* [n]                                           */
+    char            names[KMP_FLOWBITS_MAX][KMP_FLOWBIT_NAME];
+} kmp_flowbits;
+int  kmp_flowbits_parse(const char *path, uint32_t n_rules, kmp_flowbits *out, char errbuf[KMP_FLOWBITS_ERRBUF]);
+void kmp_flowbits_free(kmp_flowbits *f);
+
 /* ---- offset windows --------------------------------------------------------------------------
  * Not in the reference: the windows of kmpgpu_set_windows (include/kmpgpu.h) from a text file.  One window per line,
  *     <pattern index> <first> <last>

@@ -166,6 +166,20 @@ class DecodeStats(C.Structure):
     _fields_ = [("n_payloads", C.c_uint64), ("n_changed", C.c_uint64), ("bytes_in", C.c_uint64), ("bytes_out", C.c_uint64)]
 
 
+class FlowbitOp(C.Structure):
+    """kmpgpu_flowbit_op (include/kmpgpu.h)."""
+    _fields_ = [("rule", C.c_uint32), ("bit", C.c_uint32), ("op", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Flowbits(C.Structure):
+    """kmp_flowbits (include/kmphost.h)."""
+    _fields_ = [("n", C.c_uint32), ("n_bits", C.c_uint32), ("ops", C.POINTER(FlowbitOp)), ("names", (C.c_char * 32) * 32)]
+
+
+FLOWBITS_MAX = 32          # KMPGPU_FLOWBITS_MAX
+FLOWBIT_OPS = {"isset": 0, "isnotset": 1, "set": 2, "unset": 3, "toggle": 4, "noalert": 5}     # KMPGPU_FB_*
+
+
 class Match(C.Structure):
     """kmpgpu_match (include/kmpgpu.h)."""
     _fields_ = [("packet", C.c_uint64), ("offset", C.c_uint32), ("pattern", C.c_uint32)]
@@ -196,6 +210,8 @@ HOST_API = {
     "kmp_rules_free": (None, [C.POINTER(Rules)]),
     "kmp_headers_parse": (C.c_int, [C.c_char_p, C.POINTER(Headers), C.c_char_p]),
     "kmp_headers_free": (None, [C.POINTER(Headers)]),
+    "kmp_flowbits_parse": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(Flowbits), C.c_char_p]),
+    "kmp_flowbits_free": (None, [C.POINTER(Flowbits)]),
     "kmp_rules_parse_bt": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Rules), C.c_char_p]),
     "kmp_bytetests_parse": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(ByteTests), C.c_char_p]),
     "kmp_bytetests_free": (None, [C.POINTER(ByteTests)]),
@@ -287,6 +303,8 @@ GPU_API = {
     "kmpgpu_flows_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "kmpgpu_flow_ids_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "kmpgpu_scan_flows": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
+    "kmpgpu_set_flowbits": (C.c_int, [C.c_void_p, C.POINTER(FlowbitOp), C.c_uint32, C.c_uint32]),
+    "kmpgpu_scan_flowbits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
     "kmpgpu_flows_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "kmpgpu_load_seams": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, u64p]),
     "kmpgpu_seams_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),

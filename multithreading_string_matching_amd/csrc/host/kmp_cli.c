@@ -120,6 +120,14 @@
  * and "bytes" counts the bytes kept.  Under capture every output is byte for byte what it is without the variable.  Refused: any other
  * value, the variable without KMPGPU_FLOW_STREAMS, and with KMPGPU_DEVICE_EXTRACT=1 (the device extractor keeps no sequence numbers).
  *
+ * KMPGPU_FLOWBITS_FILE=<flow bits>, together with KMPGPU_RULES_FILE and KMPGPU_ALERTS_FILE: rule state carried along every flow's payloads
+ * (kmpgpu_set_flowbits, kmpgpu_scan_flowbits; the file format is kmp_flowbits_parse's, kmphost.h: "<rule> set:<name> isset:<name> ...
+ * noalert").  The payloads are grouped into flows (KMPGPU_FLOWS_DIRECTED=1: per direction) and the alerts file then holds the ALERT rows:
+ * a rule's line for a payload where the rule matches it AND its tests hold on the state its flow's earlier payloads left; "payload,rule"
+ * sorted as ever.  Message on stderr and exit 1, before any GPU work: the variable without the other two, more than one shard, the variable
+ * together with KMPGPU_FLOW_ALERTS_FILE, KMPGPU_FLOW_SEAMS, KMPGPU_FLOW_STREAMS, KMPGPU_DECODE or KMPGPU_EXPORT_FILE (left for later), a
+ * file that does not parse or whose bits form a cycle.  stdout is what it is without the variable.
+ *
  * KMPGPU_NOCASE=1: every pattern matches case-insensitively (ASCII letters; kmpgpu_set_patterns_flags), in the counts and in
  * the offsets file alike; the report prints every token as written in the pattern file.
  *
@@ -174,6 +182,8 @@ typedef struct cli_options {
     kmp_bytetests bytetests;                /* KMPGPU_BYTETESTS_FILE (n == 0: none) */
     kmp_regexes regexes;                    /* KMPGPU_REGEX_FILE (n == 0: none) */
     kmp_rules rules;                        /* KMPGPU_RULES_FILE, set before the first output that needs them */
+    const char *flowbits_path;              /* KMPGPU_FLOWBITS_FILE */
+    kmp_flowbits flowbits;                  /* ... and its ops, set behind the rules (n == 0: none) */
 } cli_options;
 
 /* The capture in host memory -- as payloads, or with KMPGPU_DEVICE_EXTRACT=1 as raw frames -- and when it got there. */
@@ -337,6 +347,29 @@ static void load_options(int argc, char *argv[], cli_options *opt)
         fprintf(stderr, "error reading rules file %s: %s\n", opt->rules_path, err);
         exit(1);
     }
+    /* flow bits: they change what the alerts file holds and nothing else; one shard, whose payloads are grouped into flows */
+    opt->flowbits_path = env_path("KMPGPU_FLOWBITS_FILE");
+    if (opt->flowbits_path) {
+        static const char *const not_with[][2] = {
+            {"KMPGPU_FLOW_ALERTS_FILE", "the rules per flow know no flow bits"}, {"KMPGPU_FLOW_SEAMS", "seams carry no state"},
+            {"KMPGPU_FLOW_STREAMS", "streams carry no state"}, {"KMPGPU_DECODE", "decoded payloads are grouped into no flows in this program"},
+            {"KMPGPU_EXPORT_FILE", "the export selects by the rules without their flow bits"}};
+        needs_rules_and_alerts("KMPGPU_FLOWBITS_FILE", opt);
+        if (opt->shards > 1) {
+            fprintf(stderr, "KMPGPU_FLOWBITS_FILE needs one shard, thread_number is %d: a flow would be cut at a shard's edge\n", opt->shards);
+            exit(1);
+        }
+        for (size_t i = 0; i < sizeof not_with / sizeof not_with[0]; i++)
+            if (env_path(not_with[i][0])) {
+                fprintf(stderr, "KMPGPU_FLOWBITS_FILE does not go together with %s: %s\n", not_with[i][0], not_with[i][1]);
+                exit(1);
+            }
+        _Static_assert(sizeof err >= KMP_FLOWBITS_ERRBUF, "room for the flow bits parser's message");
+        if (kmp_flowbits_parse(opt->flowbits_path, opt->rules.n, &opt->flowbits, err)) {
+            fprintf(stderr, "error reading flow bits file %s: %s\n", opt->flowbits_path, err);
+            exit(1);
+        }
+    }
     /* the offset windows likewise */
     if (windows_path) {
         if (!opt->offsets_path && !opt->packets_path && !opt->alerts_path && !opt->export_path) {
@@ -446,7 +479,7 @@ static void load_options(int argc, char *argv[], cli_options *opt)
             exit(1);
         }
     }
-    opt->want_meta = opt->headers.n || opt->flows_path || opt->flow_alerts_path;
+    opt->want_meta = opt->headers.n || opt->flows_path || opt->flow_alerts_path || opt->flowbits.n;
     /* the export starts as a capture without frames: a path that cannot be written ends the run here */
     if (opt->export_path && kmp_write_udp_pcap_part(opt->export_path, 0, NULL, NULL, NULL, 0, 0)) {
         perror("KMPGPU_EXPORT_FILE");
@@ -464,6 +497,7 @@ static void free_options(cli_options *opt)
     kmp_headers_free(&opt->headers);
     kmp_bytetests_free(&opt->bytetests);
     kmp_regexes_free(&opt->regexes);
+    kmp_flowbits_free(&opt->flowbits);
     free(opt->win_first); free(opt->win_last);
 }
 
@@ -638,6 +672,24 @@ static void set_rules_once(const cli_options *opt, cli_run *run)
     run->rules_set = 1;
 }
 
+/* KMPGPU_FLOWBITS_FILE: the alerts file holds the alert rows of kmpgpu_scan_flowbits instead -- the one shard's payloads grouped into
+ * flows, the ops set behind the rules, and one "payload,rule" line per set bit of the rows, by payload, then rule. */
+static void write_flowbit_alerts(FILE *fp, const cli_options *opt, cli_run *run)
+{
+    _Static_assert(sizeof(kmp_flowbit_op) == sizeof(kmpgpu_flowbit_op), "kmp_flowbit_op has the layout of kmpgpu_flowbit_op");
+    kmpgpu_ctx *ctx = run->rows[0];
+    const uint64_t n = run->job[0].n_payloads, W = (n + 63) / 64, nr = opt->rules.n;
+    if (kmpgpu_flows_build(ctx, opt->flows_directed ? KMPGPU_FLOW_DIRECTED : 0u, NULL, NULL)) die_gpu("kmpgpu_flows_build");
+    if (kmpgpu_set_flowbits(ctx, (const kmpgpu_flowbit_op *)opt->flowbits.ops, opt->flowbits.n, opt->flowbits.n_bits)) die_gpu("kmpgpu_set_flowbits");
+    uint64_t *hits = (uint64_t *)calloc((size_t)(nr * W + 1), sizeof(uint64_t));
+    if (!hits) die_gpu("KMPGPU_FLOWBITS_FILE: out of memory");
+    if (kmpgpu_scan_flowbits(ctx, NULL, NULL, hits, NULL, NULL, NULL, NULL)) die_gpu("kmpgpu_scan_flowbits");
+    for (uint64_t k = 0; k < n; k++)
+        for (uint64_t r = 0; r < nr; r++)
+            if (hits[r * W + (k >> 6)] >> (k & 63) & 1u) fprintf(fp, "%llu,%llu\n", (unsigned long long)k, (unsigned long long)r);
+    free(hits);
+}
+
 /* KMPGPU_PACKETS_FILE (family KMPGPU_ALERT_PATTERNS), KMPGPU_ALERTS_FILE (KMPGPU_ALERT_RULES; a rules file without rules leaves the file
  * empty): one "payload,index" line per record of every context's alert list of the family (kmpgpu_scan_alerts: built and sorted by
  * payload, then index, on the device).  The records come back in pieces of a fixed size; no bit matrix leaves the device. */
@@ -649,6 +701,11 @@ static void write_alerts(const char *path, const cli_options *opt, cli_run *run,
     FILE *fp = fopen(path, "w");
     if (!fp) { perror(by_rules ? "KMPGPU_ALERTS_FILE" : "KMPGPU_PACKETS_FILE"); exit(1); }
     if (by_rules) set_rules_once(opt, run);
+    if (by_rules && opt->flowbits.n) {
+        write_flowbit_alerts(fp, opt, run);
+        fclose(fp);
+        return;
+    }
     for (int r = 0; r < (by_rules && !opt->rules.n ? 0 : run->shards); r++) {
         uint64_t found = 0;
         if (kmpgpu_scan_alerts(run->rows[r], family, UINT64_MAX, &found, NULL, NULL, NULL, NULL)) die_gpu("kmpgpu_scan_alerts");

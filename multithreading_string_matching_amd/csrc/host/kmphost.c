@@ -977,6 +977,134 @@ void kmp_headers_free(kmp_headers *h)
     memset(h, 0, sizeof *h);
 }
 
+/* ============================ flow bits ================================================= */
+
+_Static_assert(KMP_FLOWBITS_ERRBUF == KMP_LINE_ERRBUF, "the flow bits' error buffer has the size of the others");
+
+typedef struct flowbits_ctx {
+    uint32_t n_rules;
+    kmp_flowbits *out;
+    size_t n, cap;
+} flowbits_ctx;
+
+static int flowbit_name_char(char ch)
+{
+    return (ch >= 'A' && ch <= 'Z') || (ch >= 'a' && ch <= 'z') || (ch >= '0' && ch <= '9') || ch == '_' || ch == '.' || ch == '-';
+}
+
+static int flowbits_line(void *ctx, const char *p, const char *end, size_t lineno, char *errbuf)
+{
+    static const char *const words[] = {"isset", "isnotset", "set", "unset", "toggle"};       /* KMP_FB_ISSET .. KMP_FB_TOGGLE */
+    flowbits_ctx *c = (flowbits_ctx *)ctx;
+    kmp_flowbits *o = c->out;
+    const char *tok;
+    int len, n_words = 0;
+    uint64_t rule;
+#define FIELD (len > 64 ? 64 : len), tok
+    next_field(&p, end, &tok, &len);                                    /* (the line is not blank) */
+    if (!plain_number(tok, tok + len, 0xFFFFFFFFull, &rule)) return line_error(errbuf, lineno, "'%.*s' is not a rule index", FIELD);
+    if (rule >= c->n_rules) return line_error(errbuf, lineno, "rule %llu of %u", (unsigned long long)rule, c->n_rules);
+    while (next_field(&p, end, &tok, &len)) {
+        n_words++;
+        kmp_flowbit_op op = {(uint32_t)rule, 0u, KMP_FB_NOALERT, 0u};
+        if (!field_is(tok, len, "noalert")) {
+            const char *colon = (const char *)memchr(tok, ':', (size_t)len);
+            uint32_t w = 0;
+            while (colon && w < 5u && !field_is(tok, (int)(colon - tok), words[w])) w++;
+            if (!colon || w == 5u)
+                return line_error(errbuf, lineno, "'%.*s' is none of set:<name> unset:<name> toggle:<name> isset:<name> isnotset:<name> noalert", FIELD);
+            const char *name = colon + 1;
+            const int nl = (int)(tok + len - name);
+            int ok = nl >= 1 && nl < KMP_FLOWBIT_NAME;
+            for (int i = 0; ok && i < nl; i++) ok = flowbit_name_char(name[i]);
+            if (!ok) return line_error(errbuf, lineno, "'%.*s': a name is 1..%d characters of [A-Za-z0-9_.-]", FIELD, KMP_FLOWBIT_NAME - 1);
+            uint32_t b = 0;
+            while (b < o->n_bits && !field_is(name, nl, o->names[b])) b++;
+            if (b == o->n_bits) {
+                if (b == KMP_FLOWBITS_MAX) return line_error(errbuf, lineno, "'%.*s' is name %d: at most %d flow bits", FIELD, KMP_FLOWBITS_MAX + 1, KMP_FLOWBITS_MAX);
+                memcpy(o->names[b], name, (size_t)nl);
+                o->names[b][nl] = 0;
+                o->n_bits++;
+            }
+            op.bit = b; op.op = w;
+            for (size_t j = 0; j < c->n && w <= KMP_FB_ISNOTSET; j++)
+                if (o->ops[j].rule == op.rule && o->ops[j].bit == b && o->ops[j].op == (w ^ 1u))
+                    return line_error(errbuf, lineno, "rule %u tests %s both set and clear", op.rule, o->names[b]);
+        }
+        if (c->n == c->cap) {
+            const size_t nc = c->cap ? c->cap * 2 : 64;
+            kmp_flowbit_op *nv = (kmp_flowbit_op *)realloc(o->ops, nc * sizeof *nv);
+            if (!nv) return KMPHOST_ENOMEM;
+            o->ops = nv; c->cap = nc;
+        }
+        o->ops[c->n++] = op;
+    }
+#undef FIELD
+    if (!n_words) return line_error(errbuf, lineno, "rule %llu has no word", (unsigned long long)rule);
+    return KMPHOST_OK;
+}
+
+/* A cycle among the names -- an edge Y -> X where a rule tests Y and acts on X != Y -- into errbuf as "a -> b -> a"; 0 without one.
+ * Depth first from every name, the path kept: an edge back into the path closes a cycle. */
+static int flowbits_cycle(const kmp_flowbits *f, char *errbuf)
+{
+    uint32_t succ[KMP_FLOWBITS_MAX] = {0}, done = 0;
+    for (uint32_t i = 0; i < f->n; i++)
+        for (uint32_t j = 0; j < f->n; j++)
+            if (f->ops[i].rule == f->ops[j].rule && f->ops[i].op <= KMP_FB_ISNOTSET && f->ops[j].op >= KMP_FB_SET && f->ops[j].op <= KMP_FB_TOGGLE &&
+                f->ops[i].bit != f->ops[j].bit)
+                succ[f->ops[i].bit] |= 1u << f->ops[j].bit;
+    for (uint32_t s = 0; s < f->n_bits; s++) {
+        uint32_t stack[KMP_FLOWBITS_MAX], next[KMP_FLOWBITS_MAX], depth = 1, on = 1u << s;
+        if (done >> s & 1u) continue;
+        stack[0] = s; next[0] = 0;
+        while (depth) {
+            const uint32_t v = stack[depth - 1];
+            uint32_t x = next[depth - 1];
+            while (x < f->n_bits && (!(succ[v] >> x & 1u) || (done >> x & 1u))) x++;
+            next[depth - 1] = x + 1u;
+            if (x >= f->n_bits) { done |= 1u << v; on &= ~(1u << v); depth--; continue; }
+            if (on >> x & 1u) {
+                if (errbuf) {
+                    uint32_t i = 0;
+                    size_t k = (size_t)snprintf(errbuf, KMP_LINE_ERRBUF, "the flow bits ");
+                    while (stack[i] != x) i++;
+                    for (; i < depth && k < KMP_LINE_ERRBUF; i++) k += (size_t)snprintf(errbuf + k, KMP_LINE_ERRBUF - k, "%s -> ", f->names[stack[i]]);
+                    if (k < KMP_LINE_ERRBUF) k += (size_t)snprintf(errbuf + k, KMP_LINE_ERRBUF - k, "%s form a cycle", f->names[x]);
+                }
+                return 1;
+            }
+            stack[depth] = x; next[depth] = 0; on |= 1u << x; depth++;
+        }
+    }
+    return 0;
+}
+
+int kmp_flowbits_parse(const char *path, uint32_t n_rules, kmp_flowbits *out, char errbuf[KMP_FLOWBITS_ERRBUF])
+{
+    _Static_assert(sizeof(kmp_flowbit_op) == 16, "kmp_flowbit_op has the layout of kmpgpu_flowbit_op");
+    memset(out, 0, sizeof *out);
+    if (errbuf) errbuf[0] = 0;
+    flowbits_ctx c = {n_rules, out, 0, 0};
+    int rc = text_lines(path, flowbits_line, &c, errbuf);
+    if (!rc && c.n > 0x7FFFFFFFull) rc = KMPHOST_EINVAL;
+    out->n = rc ? 0u : (uint32_t)c.n;
+    if (!rc && flowbits_cycle(out, errbuf)) rc = KMPHOST_EINVAL;
+    if (rc) {
+        kmp_flowbits_free(out);
+        return rc;
+    }
+    if (out->n_bits == 0) out->n_bits = 1;                              /* noalert alone: one bit nobody names */
+    return KMPHOST_OK;
+}
+
+void kmp_flowbits_free(kmp_flowbits *f)
+{
+    if (!f) return;
+    free(f->ops);
+    memset(f, 0, sizeof *f);
+}
+
 /* ============================ byte tests ================================================ */
 
 typedef struct bytetests_ctx {

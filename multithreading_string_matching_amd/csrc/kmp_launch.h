@@ -1,5 +1,5 @@
 /* kmp_launch.h -- launch entry points of kmp_scan_*.hip / kmp_prep.hip / kmp_fold.hip / kmp_marks.hip / kmp_rules.hip / kmp_relations.hip /
- * kmp_chains.hip / kmp_headers.hip / kmp_bytetests.hip / kmp_regex.hip / kmp_select.hip / kmp_decode.hip / kmp_alerts.hip / kmp_flows.hip / kmp_seams.hip / kmp_streams.hip / kmp_streams_seq.hip, used
+ * kmp_chains.hip / kmp_headers.hip / kmp_bytetests.hip / kmp_regex.hip / kmp_select.hip / kmp_decode.hip / kmp_alerts.hip / kmp_flows.hip / kmp_seams.hip / kmp_streams.hip / kmp_streams_seq.hip / kmp_flowbits.hip, used
  * by the C-ABI layer (kmpgpu.hip), which alone decides what is launched; the tables kmp_launch_scan_multi takes come from kmp_tables.h. */
 #ifndef KMP_LAUNCH_H
 #define KMP_LAUNCH_H
@@ -309,5 +309,31 @@ hipError_t kmp_launch_stream_seq_index(const uint64_t *src_off, const uint32_t *
                                        hipStream_t st);
 hipError_t kmp_launch_stream_seq_gather(const uint8_t *src_arena, const void *pieces, uint64_t n, uint64_t total_bytes, uint8_t *arena,
                                         bool nontemporal, hipStream_t st);
+
+/* kmp_flowbits.hip (kmpgpu_scan_flowbits): the flow bits over n <= 2^32 - 2 payloads whose flows are built (flow_of[n] < n_flows) and whose
+ * rule rows rule_rows[n_rules][stride] (stride even, 64 stride >= n, the bits of index n and above 0) kmp_launch_rules has written.
+ * _order (the sort and 1 kernel; once per build of the flows): order_buf (kmp_flowbits_order_bytes(n, n_flows) bytes, 256-byte aligned, kept
+ *   as long as the flows; 0: rocPRIM refused the size query) takes the payloads sorted stably by flow, the inverse and the head flags.
+ * Per level of kmp_pack_flowbits (kmp_rowtables.h), with acting[2 n_act] the level's 32-byte records:
+ * _build (1 kernel): the level's elements at their sorted positions in ws (kmp_flowbits_ws_bytes(n) bytes, 16-byte aligned), from the rule
+ *   rows and before32[n], which holds the lower levels' bits.
+ * _scan (1 kernel up to KMP_SCAN_TILE payloads, else 3 per level of aggregates above the payloads' + 1; *launches is added to):
+ *   before32[k] |= the level's bits before payload k, flow_state[f] |= the level's bits after flow f's last payload.  The caller zeroes
+ *   both before the first level.
+ * _rows (1 kernel): word j < ceil(n / 64) of before_rows[b][stride] for every bit b of level_mask; the caller zeroes the rows.
+ * _final (1 kernel): every word of alert_rows[n_rules][stride] from the rule rows, the before rows and tests[n_rules] (16-byte records); a
+ *   rule's set bits are added to counts[r] and ORed into any[stride]; the caller zeroes those two. */
+size_t kmp_flowbits_order_bytes(uint64_t n, uint64_t n_flows);
+hipError_t kmp_launch_flowbits_order(const uint32_t *flow_of, uint64_t n, uint64_t n_flows, uint8_t *order_buf, size_t order_bytes, hipStream_t st);
+size_t kmp_flowbits_ws_bytes(uint64_t n);
+hipError_t kmp_launch_flowbits_build(const unsigned long long *rule_rows, uint64_t stride, uint64_t n, const uint4 *acting, uint32_t n_act,
+                                     const uint32_t *before32, const uint8_t *order_buf, uint8_t *ws, hipStream_t st);
+hipError_t kmp_launch_flowbits_scan(uint64_t n, const uint32_t *flow_of, const uint8_t *order_buf, uint8_t *ws, uint32_t *before32,
+                                    uint32_t *flow_state, uint32_t *launches, hipStream_t st);
+hipError_t kmp_launch_flowbits_rows(const uint32_t *before32, uint64_t n, uint32_t level_mask, uint64_t stride, unsigned long long *before_rows,
+                                    hipStream_t st);
+hipError_t kmp_launch_flowbits_final(const unsigned long long *rule_rows, const unsigned long long *before_rows, uint64_t stride,
+                                     const uint4 *tests, uint32_t n_rules, unsigned long long *alert_rows, unsigned long long *counts,
+                                     unsigned long long *any, hipStream_t st);
 
 #endif

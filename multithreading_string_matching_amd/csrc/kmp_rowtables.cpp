@@ -257,3 +257,97 @@ int kmp_pack_bytetests(const kmpgpu_bytetest *bt, uint32_t n_bt, uint32_t n_pat,
     tests->insert(tests->end(), relative.begin(), relative.end());
     return KMPGPU_OK;
 }
+
+int kmp_pack_flowbits(const kmpgpu_flowbit_op *ops, uint32_t n_ops, uint32_t n_bits, uint32_t n_rules, kmp_flowbit_tables *out,
+                      std::string *msg)
+{
+    *out = kmp_flowbit_tables{};
+    if (n_bits < 1u || n_bits > KMPGPU_FLOWBITS_MAX)
+        return refuse(msg, "kmpgpu_set_flowbits: n_bits is %u, outside 1..%u", n_bits, (unsigned)KMPGPU_FLOWBITS_MAX);
+    if (!ops) return refuse(msg, "kmpgpu_set_flowbits: ops is NULL");
+    for (uint32_t j = 0; j < n_ops; j++) {
+        const kmpgpu_flowbit_op &o = ops[j];
+        if (o.rule >= n_rules) return refuse(msg, "kmpgpu_set_flowbits: op %u names rule %u of %u", j, o.rule, n_rules);
+        if (o.op > KMPGPU_FB_NOALERT) return refuse(msg, "kmpgpu_set_flowbits: op %u: %u is none of KMPGPU_FB_*", j, o.op);
+        if (o.reserved) return refuse(msg, "kmpgpu_set_flowbits: op %u: the reserved field is %u, not 0", j, o.reserved);
+        if (o.op != KMPGPU_FB_NOALERT && o.bit >= n_bits) return refuse(msg, "kmpgpu_set_flowbits: op %u names bit %u of %u", j, o.bit, n_bits);
+    }
+    /* per rule: what it tests, what it acts on */
+    std::vector<uint32_t> isset(n_rules, 0u), isnotset(n_rules, 0u), acts(n_rules, 0u), noalert(n_rules, 0u);
+    for (uint32_t j = 0; j < n_ops; j++) {
+        const kmpgpu_flowbit_op &o = ops[j];
+        const uint32_t b = o.op == KMPGPU_FB_NOALERT ? 0u : 1u << o.bit;
+        if (o.op == KMPGPU_FB_ISSET) isset[o.rule] |= b;
+        else if (o.op == KMPGPU_FB_ISNOTSET) isnotset[o.rule] |= b;
+        else if (o.op == KMPGPU_FB_NOALERT) noalert[o.rule] = 1u;
+        else acts[o.rule] |= b;
+        if (isset[o.rule] & isnotset[o.rule])
+            return refuse(msg, "kmpgpu_set_flowbits: op %u: rule %u tests bit %u both set and clear", j, o.rule, o.bit);
+    }
+    /* succ[Y]: the bits X != Y that a rule testing Y acts on */
+    uint32_t succ[KMPGPU_FLOWBITS_MAX] = {0};
+    for (uint32_t r = 0; r < n_rules; r++)
+        for (uint32_t y = 0; y < n_bits; y++)
+            if ((isset[r] | isnotset[r]) >> y & 1u) succ[y] |= acts[r] & ~(1u << y);
+    /* longest paths by relaxation: without a cycle no level passes n_bits - 1 */
+    out->level_of.assign(n_bits, 0u);
+    bool moved = true;
+    for (uint32_t round = 0; moved && round <= n_bits; round++) {
+        moved = false;
+        for (uint32_t y = 0; y < n_bits; y++)
+            for (uint32_t x = 0; x < n_bits; x++)
+                if ((succ[y] >> x & 1u) && out->level_of[x] < out->level_of[y] + 1u) { out->level_of[x] = out->level_of[y] + 1u; moved = true; }
+    }
+    if (moved) {
+        /* depth first from every bit, the path kept: an edge back into the path closes a cycle, named from the lowest start that finds one */
+        std::string path;
+        uint32_t done = 0;
+        for (uint32_t s = 0; s < n_bits && path.empty(); s++) {
+            uint32_t stack[KMPGPU_FLOWBITS_MAX], next[KMPGPU_FLOWBITS_MAX], depth = 0, on = 0;
+            if (done >> s & 1u) continue;
+            stack[0] = s; next[0] = 0; on = 1u << s; depth = 1;
+            while (depth && path.empty()) {
+                const uint32_t v = stack[depth - 1];
+                uint32_t x = next[depth - 1];
+                while (x < n_bits && (!(succ[v] >> x & 1u) || (done >> x & 1u))) x++;
+                next[depth - 1] = x + 1u;
+                if (x >= n_bits) { done |= 1u << v; on &= ~(1u << v); depth--; continue; }
+                if (on >> x & 1u) {
+                    uint32_t i = 0;
+                    while (stack[i] != x) i++;
+                    for (; i < depth; i++) path += std::to_string(stack[i]) + " -> ";
+                    path += std::to_string(x);
+                } else { stack[depth] = x; next[depth] = 0; on |= 1u << x; depth++; }
+            }
+        }
+        *out = kmp_flowbit_tables{};
+        return refuse(msg, "kmpgpu_set_flowbits: the flow bits %s form a cycle (a rule tests one and acts on the next)", path.c_str());
+    }
+    out->n_bits = n_bits;
+    for (uint32_t b = 0; b < n_bits; b++) out->n_levels = out->level_of[b] + 1u > out->n_levels ? out->level_of[b] + 1u : out->n_levels;
+    out->level_mask.assign(out->n_levels, 0u);
+    for (uint32_t b = 0; b < n_bits; b++) out->level_mask[out->level_of[b]] |= 1u << b;
+    uint32_t lower = 0;
+    for (uint32_t l = 0; l < out->n_levels; l++) {
+        const uint32_t lm = out->level_mask[l];
+        out->level_first.push_back((uint32_t)(out->acting.size() / 8u));
+        for (uint32_t r = 0; r < n_rules; r++) {
+            if (!(acts[r] & lm)) continue;
+            uint32_t a0 = 0u, a1 = ~0u;
+            for (uint32_t j = 0; j < n_ops; j++) {
+                const kmpgpu_flowbit_op &o = ops[j];
+                if (o.rule != r || o.op < KMPGPU_FB_SET || o.op > KMPGPU_FB_TOGGLE || !(lm >> o.bit & 1u)) continue;
+                const uint32_t b = 1u << o.bit;
+                if (o.op == KMPGPU_FB_SET) { a0 |= b; a1 |= b; }
+                else if (o.op == KMPGPU_FB_UNSET) { a0 &= ~b; a1 &= ~b; }
+                else { a0 ^= b; a1 ^= b; }
+            }
+            const uint32_t self = ((isset[r] & lm) ? 1u : 0u) | ((isnotset[r] & lm) ? 2u : 0u);
+            out->acting.insert(out->acting.end(), {r, isset[r] & lower, isnotset[r] & lower, self, a0, a1, 0u, 0u});
+        }
+        lower |= lm;
+    }
+    out->level_first.push_back((uint32_t)(out->acting.size() / 8u));
+    for (uint32_t r = 0; r < n_rules; r++) out->tests.insert(out->tests.end(), {isset[r], isnotset[r], noalert[r], 0u});
+    return KMPGPU_OK;
+}

@@ -1,5 +1,5 @@
 /*
- * kmp_rowtables.h -- what kmpgpu_set_rules, kmpgpu_set_windows, kmpgpu_set_relations, kmpgpu_set_chains, kmpgpu_set_headers, kmpgpu_set_bytetests and kmpgpu_set_regexes upload, checked and packed on
+ * kmp_rowtables.h -- what kmpgpu_set_rules, kmpgpu_set_windows, kmpgpu_set_relations, kmpgpu_set_chains, kmpgpu_set_headers, kmpgpu_set_bytetests, kmpgpu_set_regexes and kmpgpu_set_flowbits upload, checked and packed on
  * the host by kmp_rowtables.cpp into the form the kernels read bit for bit (kmp_launch.h: kmp_launch_rules, emit_windows,
  * kmp_launch_relations, kmp_launch_chains, kmp_launch_headers, kmp_launch_bytetests, kmp_launch_regexes).  Host code without a HIP header, as kmp_tables.h: it builds and runs without a device
  * (tests/rowtables_sanitizer_driver.cpp).
@@ -99,5 +99,22 @@ int kmp_pack_regexes(const uint8_t *const *expr, const uint32_t *expr_len, const
 int kmp_pack_regex_groups(const uint8_t *const *expr, const uint32_t *expr_len, const uint32_t *flags, const uint32_t *gate, uint32_t n_rx,
                           uint32_t n_pat, uint32_t n_rel, uint32_t n_chains, uint32_t n_hdr, uint32_t n_bt, std::vector<uint32_t> *tables,
                           uint32_t *n_groups, std::string *msg);
+
+/* kmpgpu_set_flowbits: the ops checked, the bits' levels, and the two tables the kernels of kmp_flowbits.hip read (kmp_launch.h).
+ * level_of[n_bits]: the longest path into the bit in the graph with an edge Y -> X where a rule tests Y and acts on X != Y (a self-loop is
+ * no edge); level_mask[n_levels]: the bits of a level; level_first[n_levels + 1]: the level's records in `acting`.
+ * acting: 8 words per (level, rule that acts on a bit of the level), the rules of a level in ascending index: {rule, the bits of lower
+ * levels it tests set, those it tests clear, self, a0, a1, 0, 0}.  self: bit 0 -- it tests a bit of this level set (by the graph that is the
+ * one bit of the level it acts on), bit 1 -- clear.  (a0, a1): its actions on the level's bits, in the order given, composed into one
+ * function per bit -- bit X of a0 is what they make of X = 0, of a1 of X = 1; identity (0, 1) for every other bit.
+ * tests: 4 words per rule: {bits tested set, bits tested clear, 1 for a NOALERT rule, 0}.
+ * Refusals (KMPGPU_EINVAL, the text of kmpgpu_last_error in *msg): n_bits outside 1..KMPGPU_FLOWBITS_MAX, ops NULL, a rule >= n_rules, a
+ * bit >= n_bits (not looked at for NOALERT), an unknown op, a nonzero reserved field, a (rule, bit) tested both ways, a cycle. */
+struct kmp_flowbit_tables {
+    uint32_t n_bits = 0, n_levels = 0;
+    std::vector<uint32_t> level_of, level_mask, level_first, acting, tests;
+};
+int kmp_pack_flowbits(const kmpgpu_flowbit_op *ops, uint32_t n_ops, uint32_t n_bits, uint32_t n_rules, kmp_flowbit_tables *out,
+                      std::string *msg);
 
 #endif

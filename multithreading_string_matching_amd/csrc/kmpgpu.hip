@@ -257,6 +257,17 @@ struct kmpgpu_ctx {
     uint32_t            *d_stream_seq = nullptr;
     uint64_t            stream_segs_cap = 0, stream_orders_cap = 0, stream_seq_ws_cap = 0, stream_seq_cap = 0;
     bool                stream_order_valid = false;
+    /* kmpgpu_set_flowbits: the two tables of kmp_pack_flowbits on the device and, on the host, which bits and which records of d_fb_acting
+     * (two 16-byte units each) make up every level.  kmpgpu_scan_flowbits: the order of the payloads by flow (kmp_flowbits_order_bytes),
+     * valid for the flows of generation fb_order_gen; the scan's workspace with before32[n_pkts] and flow_state[n_flows] behind it; the
+     * before rows [n_bits][stride], the alert rows [n_rules][stride], rule_pkt_counts[n_rules], any[stride] */
+    uint32_t            n_fb_bits = 0;
+    std::vector<uint32_t> fb_level_mask, fb_level_first;
+    uint4              *d_fb_acting = nullptr, *d_fb_tests = nullptr;
+    uint8_t            *d_fb_order = nullptr, *d_fb_ws = nullptr;
+    unsigned long long *d_fb_out = nullptr;
+    uint64_t            fb_order_cap = 0, fb_ws_cap = 0, fb_out_cap = 0, fb_order_gen = 0;
+    bool                fb_order_valid = false;
     /* the patterns as they were set, one record {length, flags, bytes} each: what kmpgpu_scan_flows_seams compares between two contexts */
     std::vector<uint8_t> pat_sig;
 
@@ -404,12 +415,23 @@ void free_pattern_set(kmpgpu_ctx::PatternSet &s)
 /* The set a scan reports the grid of (kmpgpu_timing.grid_blocks): the case-sensitive one, or the nocase one when it is alone. */
 const kmpgpu_ctx::PatternSet &primary_set(const kmpgpu_ctx *c) { return c->sets[0].n || !c->sets[1].n ? c->sets[0] : c->sets[1]; }
 
+/* the flow-bit ops go with the rules their indices refer to */
+void drop_flowbits(kmpgpu_ctx *c)
+{
+    free_buffer(&c->d_fb_acting);
+    free_buffer(&c->d_fb_tests);
+    c->fb_level_mask.clear();
+    c->fb_level_first.clear();
+    c->n_fb_bits = 0;
+}
+
 /* the rules go with the pattern set their indices refer to */
 void drop_rules(kmpgpu_ctx *c)
 {
     free_buffer(&c->d_rule_heads);
     free_buffer(&c->d_rule_quads);
     c->n_rules = 0;
+    drop_flowbits(c);
 }
 
 /* so do the windows */
@@ -590,6 +612,8 @@ void release_pass_buffers(kmpgpu_ctx *c)
     free_buffer(&c->d_stream_segs, &c->stream_segs_cap); free_buffer(&c->d_stream_orders, &c->stream_orders_cap);
     free_buffer(&c->d_stream_seq_ws, &c->stream_seq_ws_cap); free_buffer(&c->d_stream_seq, &c->stream_seq_cap);
     drop_streams(c);
+    free_buffer(&c->d_fb_order, &c->fb_order_cap); free_buffer(&c->d_fb_ws, &c->fb_ws_cap); free_buffer(&c->d_fb_out, &c->fb_out_cap);
+    c->fb_order_valid = false;
     c->alerts_valid = false;
     c->bitmap_live = false; c->plan_waves = c->uplan_units = 0; c->fold_stale = true;
 }
@@ -2468,6 +2492,7 @@ int kmpgpu_set_rules(kmpgpu_ctx *c, const uint32_t *rule_off, const uint32_t *te
     const int rc = swap_tables(c, "kmpgpu_set_rules: the rules", {{heads, (void **)&c->d_rule_heads}, {quads, (void **)&c->d_rule_quads}});
     if (rc) return rc;
     c->n_rules = n_rules;
+    drop_flowbits(c);                              /* their rule indices meant the rules before */
     return KMPGPU_OK;
 }
 
@@ -2946,6 +2971,97 @@ int kmpgpu_scan_flows_seams(kmpgpu_ctx *c, kmpgpu_ctx *sm, uint64_t *flow_counts
         return fail(KMPGPU_ESTATE, "%s: the seam list was not built from src's current flows", who);
     if (c->n_pat != sm->n_pat || c->pat_sig != sm->pat_sig) return fail(KMPGPU_ESTATE, "%s: the contexts do not hold the same patterns", who);
     return scan_flows_body(c, who, sm, KMPGPU_ALERT_RULES, KMPGPU_FLOW_SCOPE_FLOW, flow_counts_out, any_out, flow_hits_out, counts_out, t);
+}
+
+int kmpgpu_set_flowbits(kmpgpu_ctx *c, const kmpgpu_flowbit_op *ops, uint32_t n_ops, uint32_t n_bits)
+{
+    const int sr = setter_state(c, "kmpgpu_set_flowbits");
+    if (sr) return sr;
+    if (c->n_rules == 0) return fail(KMPGPU_ESTATE, "kmpgpu_set_flowbits: no rules set");
+    kmp_flowbit_tables tb;
+    std::string msg;
+    if (n_ops) {
+        const int rc = kmp_pack_flowbits(ops, n_ops, n_bits, c->n_rules, &tb, &msg);
+        if (rc) return fail(rc, "%s", msg.c_str());
+        if (tb.acting.empty()) tb.acting.assign(8, 0u);          /* tests only: one record nobody reads, never a NULL table */
+    }
+    const int rc = swap_tables(c, "kmpgpu_set_flowbits: the ops", {{tb.acting, (void **)&c->d_fb_acting}, {tb.tests, (void **)&c->d_fb_tests}});
+    if (rc) return rc;
+    c->n_fb_bits = tb.n_bits;
+    c->fb_level_mask = tb.level_mask;
+    c->fb_level_first = tb.level_first;
+    return KMPGPU_OK;
+}
+
+int kmpgpu_scan_flowbits(kmpgpu_ctx *c, uint64_t *rule_pkt_counts_out, uint64_t *any_out, uint64_t *rule_hits_out, uint64_t *state_out,
+                         uint32_t *flow_state_out, uint64_t *counts_out, kmpgpu_timing *t)
+{
+    const char *who = "kmpgpu_scan_flowbits";
+    if (!c) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
+    if (c->n_rules == 0) return fail(KMPGPU_ESTATE, "%s: no rules set", who);
+    if (c->n_fb_bits == 0) return fail(KMPGPU_ESTATE, "%s: no flow bits (kmpgpu_set_flowbits)", who);
+    if (!c->flows_valid) return fail(KMPGPU_ESTATE, "%s: no flows (no kmpgpu_flows_build since the arena or its metadata were set)", who);
+    if (c->fr_pending) return fail(KMPGPU_ESTATE, "%s: the context sits between kmpgpu_load_frames_begin and _finish", who);
+    MarkPass p;
+    const int rc = begin_family(c, who, KMPGPU_ALERT_RULES, rule_pkt_counts_out, counts_out, t, &p);
+    if (rc || p.empty) return rc;
+    FamilyRows f;
+    const int rr = enqueue_family(c, who, KMPGPU_ALERT_RULES, p, /* profile_reduce = */ false, &f);
+    if (rr) return rr;
+    uint32_t launches = p.launches + f.launches;
+    const uint64_t n = c->n_pkts, nf = c->n_flows, nb = c->n_fb_bits, nr = c->n_rules;
+    /* the order is the flows': built once per generation */
+    const bool ordered = c->fb_order_valid && c->fb_order_gen == c->flows_gen;
+    const uint64_t order_bytes = ordered ? c->fb_order_cap : (uint64_t)kmp_flowbits_order_bytes(n, nf);
+    const uint64_t scan_bytes = (uint64_t)kmp_flowbits_ws_bytes(n), ws_bytes = scan_bytes + 4u * (n + nf);
+    const uint64_t out_words = (nb + nr) * p.stride + nr + p.stride;
+    hipError_t e = order_bytes ? hipSuccess : hipErrorInvalidValue;               /* (0: rocPRIM refused the size query) */
+    if (e == hipSuccess && !ordered) { c->fb_order_valid = false; e = grow_buffer(&c->d_fb_order, &c->fb_order_cap, order_bytes, EIGHTH); }
+    if (e == hipSuccess) e = grow_buffer(&c->d_fb_ws, &c->fb_ws_cap, ws_bytes, EIGHTH);
+    if (e == hipSuccess) e = grow_buffer(&c->d_fb_out, &c->fb_out_cap, out_words, EIGHTH);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);      /* the pass is under way on the stream; the context stays usable */
+        return alloc_fail(e, "%s: the order, the scan workspace and the rows (%llu bytes) could not be allocated", who,
+                          (unsigned long long)(order_bytes + ws_bytes + out_words * 8u));
+    }
+    uint32_t *d_before32 = reinterpret_cast<uint32_t *>(c->d_fb_ws + scan_bytes), *d_flow_state = d_before32 + n;
+    unsigned long long *d_before = c->d_fb_out, *d_alert = d_before + nb * p.stride, *d_pc = d_alert + nr * p.stride, *d_any = d_pc + nr;
+    HIP_TRY(hipMemsetAsync(d_before32, 0, (size_t)(4u * (n + nf)), c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_fb_out, 0, (size_t)out_words * sizeof(unsigned long long), c->stream));
+    hipEvent_t e1;
+    if (!ordered) {
+        HIP_TRY(profile_launch(c, &e1));
+        HIP_TRY(kmp_launch_flowbits_order(c->d_flow_of, n, nf, c->d_fb_order, (size_t)c->fb_order_cap, c->stream));
+        HIP_TRY(profile_launched(c, e1));
+        c->fb_order_valid = true; c->fb_order_gen = c->flows_gen;
+        launches += 2u;
+    }
+    for (size_t l = 0; l < c->fb_level_mask.size(); l++) {
+        const uint32_t first = c->fb_level_first[l], n_act = c->fb_level_first[l + 1] - first;
+        if (n_act == 0) continue;                   /* bits that are tested only: 0 for ever */
+        HIP_TRY(profile_launch(c, &e1));
+        HIP_TRY(kmp_launch_flowbits_build(f.d_rows, p.stride, n, c->d_fb_acting + 2u * (size_t)first, n_act, d_before32, c->d_fb_order, c->d_fb_ws, c->stream));
+        HIP_TRY(profile_launched(c, e1));
+        HIP_TRY(profile_launch(c, &e1));
+        HIP_TRY(kmp_launch_flowbits_scan(n, c->d_flow_of, c->d_fb_order, c->d_fb_ws, d_before32, d_flow_state, &launches, c->stream));
+        HIP_TRY(profile_launched(c, e1));
+        HIP_TRY(profile_launch(c, &e1));
+        HIP_TRY(kmp_launch_flowbits_rows(d_before32, n, c->fb_level_mask[l], p.stride, d_before, c->stream));
+        HIP_TRY(profile_launched(c, e1));
+        launches += 2u;
+    }
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_flowbits_final(f.d_rows, d_before, p.stride, c->d_fb_tests, c->n_rules, d_alert, d_pc, d_any, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    launches++;
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    if (rule_pkt_counts_out) HIP_TRY(hipMemcpyAsync(rule_pkt_counts_out, d_pc, (size_t)nr * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (any_out) HIP_TRY(hipMemcpyAsync(any_out, d_any, p.W * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, p.d_cnt, (size_t)c->n_pat * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (rule_hits_out) HIP_TRY(download_rows(c, rule_hits_out, d_alert, p.W, p.stride, nr));
+    if (state_out) HIP_TRY(download_rows(c, state_out, d_before, p.W, p.stride, nb));
+    if (flow_state_out) HIP_TRY(hipMemcpyAsync(flow_state_out, d_flow_state, (size_t)nf * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    return finish_marking(c, launches, t);
 }
 
 int kmpgpu_flows_select(kmpgpu_ctx *c, const void *flow_bits, int on_device, uint64_t *pkt_bits_out, const void **d_pkt_bits)

@@ -208,6 +208,28 @@ class GpuMatcher:
         terms = np.array([t for a, b in rules for t in a + [i | _lib.RULE_NOT for i in b]] or [0], dtype=np.uint32)
         gpu_check(self._g.kmpgpu_set_rules(self._ctx, off.ctypes.data_as(u32p), terms.ctypes.data_as(u32p), len(rules)), "kmpgpu_set_rules")
         self.rules = rules
+        self.flowbits, self.n_flowbits = [], 0      # the library drops the flow-bit ops with the rules they referred to
+
+    def set_flowbits(self, ops, n_bits: Optional[int] = None) -> None:
+        """Flow-bit tests and actions of the current rules (kmpgpu_set_flowbits): a sequence of (rule, "set" | "unset" | "toggle" |
+        "isset" | "isnotset", bit) and (rule, "noalert").  A rule fires for a payload where scan_rules has it AND its tests hold on the
+        state of the payload's flow BEFORE that payload; the fired rules' actions, in rule order, make the state the flow's next payload
+        sees.  ``n_bits`` None: the highest bit named + 1.  None or an empty sequence clears the ops."""
+        rows = []
+        for op in (ops or []):
+            if len(op) not in (2, 3) or op[1] not in _lib.FLOWBIT_OPS or (len(op) == 2) != (op[1] == "noalert"):
+                raise ValueError(f"flow-bit op {op!r}: (rule, {sorted(_lib.FLOWBIT_OPS)}, bit) or (rule, 'noalert') is needed")
+            rule, bit = int(op[0]), int(op[2]) if len(op) == 3 else 0
+            if not (0 <= rule <= 0xFFFFFFFF and 0 <= bit <= 0xFFFFFFFF):
+                raise ValueError(f"flow-bit op {op!r}: rule and bit are 32-bit")
+            rows.append((rule, bit, _lib.FLOWBIT_OPS[op[1]]))
+        if n_bits is None:
+            n_bits = max([b + 1 for _, b, o in rows if o != _lib.FLOWBIT_OPS["noalert"]] or [1])
+        arr = (_lib.FlowbitOp * max(len(rows), 1))()
+        for a, (rule, bit, op) in zip(arr, rows):
+            a.rule, a.bit, a.op, a.reserved = rule, bit, op, 0
+        gpu_check(self._g.kmpgpu_set_flowbits(self._ctx, arr if rows else None, len(rows), int(n_bits) if rows else 0), "kmpgpu_set_flowbits")
+        self.flowbits, self.n_flowbits = rows, int(n_bits) if rows else 0
 
     def set_relations(self, relations) -> None:
         """Distance / within relations between two of the current patterns (kmpgpu_set_relations): a sequence of (a, b, dmin, dmax),
@@ -621,6 +643,36 @@ class GpuMatcher:
         ``rule_pkt_counts`` (uint64[n_rules]) payloads that rule r matches, ``any`` (bool[n_pkts]) payload k matches some rule,
         ``counts`` (uint64[n_pat]) as scan(), ``timing``; with hits=True also ``hits`` (bool[n_rules, n_pkts])."""
         return self._scan_family("kmpgpu_scan_rules", len(self.rules), "rule_pkt_counts", hits)
+
+    def scan_flowbits(self, hits: bool = False, state: bool = False) -> dict:
+        """The rules with their flow-bit ops over the built flows (kmpgpu_scan_flowbits): a dict as scan_rules returns -- its rows are the
+        ALERT rows: fired, and no "noalert" on the rule --, plus ``flow_state`` (uint32[n_flows]) the state after every flow's last
+        payload and, with state=True, ``state`` (bool[n_bits, n_pkts]): bit X before payload k."""
+        n, rows, nb = len(self.patterns), len(self.rules), getattr(self, "n_flowbits", 0)
+        n_pkts, _ = self.arena_info()
+        n_flows = getattr(self, "_n_flows", 0)
+        W = (n_pkts + 63) // 64
+        row_counts = np.zeros(max(rows, 1), dtype=np.uint64)
+        counts = np.zeros(max(n, 1), dtype=np.uint64)
+        any_w = np.zeros(max(W, 1), dtype=np.uint64)
+        hit_w = np.zeros((rows, W) if hits and rows * W else 1, dtype=np.uint64)
+        st_w = np.zeros((nb, W) if state and nb * W else 1, dtype=np.uint64)
+        flow_state = np.zeros(max(n_flows, 1), dtype=np.uint32)
+        t = Timing()
+        gpu_check(self._g.kmpgpu_scan_flowbits(self._ctx, row_counts.ctypes.data, any_w.ctypes.data, hit_w.ctypes.data if hits else None,
+                                               st_w.ctypes.data if state else None, flow_state.ctypes.data, counts.ctypes.data, C.byref(t)),
+                  "kmpgpu_scan_flowbits")
+
+        def unpack(words, r):
+            bits = np.unpackbits(words.reshape(r, W).view(np.uint8), axis=1, bitorder="little") if r * W else np.zeros((r, 0), np.uint8)
+            return bits[:, :n_pkts].astype(bool)
+        out = {"rule_pkt_counts": row_counts[:rows], "counts": counts[:n], "timing": t, "flow_state": flow_state[:n_flows],
+               "any": np.unpackbits(any_w[:W].view(np.uint8), bitorder="little")[:n_pkts].astype(bool)}
+        if hits:
+            out["hits"] = unpack(hit_w, rows)
+        if state:
+            out["state"] = unpack(st_w, nb)
+        return out
 
     def scan_relations(self, hits: bool = False) -> dict:
         """In which payloads which relations hold (kmpgpu_scan_relations): the marking pass of scan_packets and the relation kernel.
