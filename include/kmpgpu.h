@@ -1192,6 +1192,71 @@ int  kmpgpu_scan_flowbits(kmpgpu_ctx *ctx, uint64_t *rule_pkt_counts_out /* [n_r
                           uint32_t *flow_state_out /* [n_flows] or NULL */, uint64_t *counts_out /* [n_pat] or NULL */,
                           kmpgpu_timing *t /* or NULL */);
 
+/* ---- rate thresholds: a rule fires on the Nth hit per tracker in a time window (`detection_filter`, `threshold` of signature languages) --
+ * kmpgpu_set_thresholds gives rules of kmpgpu_set_rules conditions on how often they have hit per source, destination, flow or altogether;
+ * kmpgpu_scan_thresholds evaluates them with one timestamp per payload from the caller.
+ *
+ * Definition.  ts[k] is an unsigned 64-bit time in a unit the library does not know; a threshold's `window` is in the same unit.  Time
+ * never runs backwards for the engine: T[k] = max(ts[0 .. k]) in capture order.  A threshold q is (rule r, track, type, count, window);
+ * base[r][k] is the bit kmpgpu_scan_rules defines.  tracker(q, k) is 0 under KMPGPU_THR_BY_RULE (one tracker), meta[k].src_ip under
+ * KMPGPU_THR_BY_SRC, meta[k].dst_ip under KMPGPU_THR_BY_DST, flow_of[k] of the built flows under KMPGPU_THR_BY_FLOW (it follows
+ * KMPGPU_FLOW_DIRECTED exactly as built).
+ *   n[q][k]     = #{ j <= k : tracker(q, j) == tracker(q, k), base[r][j] == 1, T[k] - T[j] < window }
+ *   pass[q][k]  = n >= count (KMPGPU_THR_AT_LEAST) | n <= count (KMPGPU_THR_AT_MOST) | n == count (KMPGPU_THR_EXACTLY)
+ *   alert[r][k] = base[r][k] AND pass[q][k] for every threshold q on rule r          (a rule without thresholds: alert = base)
+ * window == KMPGPU_THR_NO_WINDOW means every j <= k of the tracker.  j <= k is capture order: of two payloads with equal T only the
+ * earlier one counts for the other, and a payload counts itself when it hits.
+ * THESE ARE SLIDING WINDOWS OVER THE RULE'S BASE HITS: not the tumbling windows of Snort's implementation, and they do not count issued
+ * alerts.  This is the one deliberate difference, the counterpart of flow bits' "seen from the next payload on", and what makes the count
+ * a prefix sum plus a search.  KMPGPU_THR_AT_MOST c therefore reads: the first c hits of a burst, armed again once the window holds fewer
+ * than c.
+ *
+ * kmpgpu_set_thresholds(ctx, thr, n_thr): n_thr == 0 clears (thr is not looked at).  KMPGPU_ESTATE without rules.  KMPGPU_EINVAL, with the
+ * thresholds set before still in force: thr NULL, a rule >= n_rules, an unknown track or type, count == 0, window == 0.  Whatever drops the
+ * rules and every successful kmpgpu_set_rules drops the thresholds; kmpgpu_flows_build keeps them.
+ *
+ * kmpgpu_scan_thresholds: every output may be NULL.  rule_pkt_counts_out[r] = set bits of alert row r, any_out[W] the OR of the alert rows,
+ * rule_hits_out[n_rules * W] the alert rows, window_counts_out[n_thr * n_pkts]: n[q][k] for EVERY k, also where base[r][k] is 0 (the
+ * payload itself then adds nothing), counts_out as kmpgpu_scan.  W = ceil(n_pkts / 64), bits at n_pkts and above are 0.  ts_on_device is 0
+ * or 1; 1: device memory on the context's device, 8-byte aligned.  KMPGPU_ESTATE: no patterns, no arena (no load call has reached the
+ * context yet; an arena of zero payloads is one), no rules, "no thresholds", "no
+ * packet metadata" (only when a BY_SRC or BY_DST threshold is set, or the rules hold header predicates), "no flows" (only when a BY_FLOW
+ * threshold is set), between kmpgpu_load_frames_begin and _finish.  KMPGPU_EINVAL: ts NULL with n_pkts > 0, another ts_on_device, device
+ * timestamps that are not 8-byte aligned.  With
+ * n_pkts == 0 every count is 0 and nothing is launched.  Results do not depend on the run: no atomic decides a value, and no block waits on
+ * another.
+ *
+ * Launches.  The pass of kmpgpu_scan_rules, unchanged.  The timestamps are copied into the context's buffer and max-scanned in place
+ * (64-bit; tiles of KMP_SCAN_TILE reduced to one aggregate each, the aggregates scanned by the same kernels, recursively, then every tile
+ * from its carry-in); skipped when every window is KMPGPU_THR_NO_WINDOW.  Per track in use an order: BY_FLOW the order of
+ * kmpgpu_scan_flowbits and its cache per build of the flows; BY_SRC / BY_DST one kernel for the keys and a stable rocPRIM radix sort of
+ * (address, k) over 32 bits with the inverse order and head flags, cached until the arena or its metadata change; BY_RULE the identity, no
+ * sort and no buffer.  Per sorted track one kernel that puts T into the track's order.  Per threshold: gather the rule's bits into sorted
+ * order, a 32-bit prefix sum (the same three-kernel scan), and the pass kernel -- a lane per payload, a binary search over (key, T) for the
+ * window's first position, the comparison, one ballot per 64 payloads.  Last the final pass: alert[r] = base[r] AND its pass rows.
+ * t->launches counts all of them.
+ * Memory, kept by the context: 13 bytes per payload and rocPRIM's temporary storage per sorted track, 8 bytes per payload for T and 8 per
+ * sorted track, 4 for the prefix sum, 8 per tile, the pass rows [n_thr][stride] and the alert rows [n_rules][stride] (stride =
+ * 2 ceil(W / 2) words), 4 n_thr n_pkts bytes when window_counts_out is asked for.  An allocation failure is KMPGPU_ENOMEM and leaves the
+ * context usable.
+ * Not done: thresholds over flow-bit alerts; tracking by address pair; tumbling windows and counts of issued alerts; timestamps through
+ * kmpgpu_load_frames, kmpgpu_load_selected or streams (the caller keeps them); no KMPGPU_ALERT_* family, so kmpgpu_scan_alerts /
+ * kmpgpu_scan_flows know nothing of thresholds. */
+#define KMPGPU_THR_BY_RULE  0
+#define KMPGPU_THR_BY_SRC   1
+#define KMPGPU_THR_BY_DST   2
+#define KMPGPU_THR_BY_FLOW  3
+#define KMPGPU_THR_AT_LEAST 0
+#define KMPGPU_THR_AT_MOST  1
+#define KMPGPU_THR_EXACTLY  2
+#define KMPGPU_THR_NO_WINDOW (~0ull)
+typedef struct kmpgpu_threshold { uint32_t rule, track, type, count; uint64_t window; } kmpgpu_threshold;   /* 24 bytes */
+int  kmpgpu_set_thresholds(kmpgpu_ctx *ctx, const kmpgpu_threshold *thr, uint32_t n_thr);
+int  kmpgpu_scan_thresholds(kmpgpu_ctx *ctx, const uint64_t *ts, int ts_on_device, uint64_t *rule_pkt_counts_out /* [n_rules] or NULL */,
+                            uint64_t *any_out /* [W] or NULL */, uint64_t *rule_hits_out /* [n_rules * W] or NULL */,
+                            uint32_t *window_counts_out /* [n_thr * n_pkts] or NULL */, uint64_t *counts_out /* [n_pat] or NULL */,
+                            kmpgpu_timing *t /* or NULL */);
+
 /* Fill a device arena with the synthetic payloads of kmp_synth.h (benchmark input S1/S2):
  * packet ids first_pkt_id .. first_pkt_id + n_pkts - 1 at the slots of the given device index. */
 int  kmpgpu_synth_fill(kmpgpu_ctx *ctx, void *d_arena, const void *d_pkt_off, const void *d_pkt_len,

@@ -289,6 +289,28 @@ typedef struct kmp_flowbits {
 int  kmp_flowbits_parse(const char *path, uint32_t n_rules, kmp_flowbits *out, char errbuf[KMP_FLOWBITS_ERRBUF]);
 void kmp_flowbits_free(kmp_flowbits *f);
 
+/* ---- rate thresholds -------------------------------------------------------------------------
+ * Not in the reference: the thresholds of kmpgpu_set_thresholds (include/kmpgpu.h, where they are defined) from a text file.  One line
+ *     <rule> by_rule|by_src|by_dst|by_flow at_least|at_most|exactly <count> <seconds|all>
+ * gives rule <rule> (a decimal position in the rules file, 0-based) one threshold; a rule may have several lines.  <count> is 1..2^32 - 1.
+ * <seconds> is decimal with at most 6 fraction digits (60, 0.5) and is converted exactly to microseconds, the unit of
+ * kmp_arena_from_pcap_ts; `all` is KMP_THR_NO_WINDOW.  Blank lines and lines whose first non-blank character is '#' are skipped.  thr is
+ * what kmpgpu_set_thresholds takes (kmp_threshold has the layout of kmpgpu_threshold).
+ * KMPHOST_EIO: the file cannot be opened; KMPHOST_EINVAL: a rule that is no number below n_rules, a missing field, an unknown track or
+ * type, a count that is no number in its range, a window that is neither `all` nor such seconds, that is 0, or that is more than
+ * 2^64 - 2 microseconds, a field behind the window -- errbuf names the line (a position in the file, from 1). */
+#define KMP_THRESHOLDS_ERRBUF 256
+#define KMP_THR_NO_WINDOW     (~0ull)
+enum { KMP_THR_BY_RULE, KMP_THR_BY_SRC, KMP_THR_BY_DST, KMP_THR_BY_FLOW };
+enum { KMP_THR_AT_LEAST, KMP_THR_AT_MOST, KMP_THR_EXACTLY };
+typedef struct kmp_threshold { uint32_t rule, track, type, count; uint64_t window; } kmp_threshold;
+typedef struct kmp_thresholds {
+    uint32_t       n;               /* number of thresholds                          */
+    kmp_threshold *thr;             /* [n]                                           */
+} kmp_thresholds;
+int  kmp_thresholds_parse(const char *path, uint32_t n_rules, kmp_thresholds *out, char errbuf[KMP_THRESHOLDS_ERRBUF]);
+void kmp_thresholds_free(kmp_thresholds *t);
+
 /* ---- offset windows --------------------------------------------------------------------------
  * Not in the reference: the windows of kmpgpu_set_windows (include/kmpgpu.h) from a text file.  One window per line,
  *     <pattern index> <first> <last>
@@ -335,6 +357,15 @@ int  kmp_arena_from_pcap_meta(const char *path, int proto, kmp_alloc_fn alloc_fn
  * comes from malloc() and is released with free().  meta_out and seq_out may each be NULL. */
 int  kmp_arena_from_pcap_seq(const char *path, int proto, kmp_alloc_fn alloc_fn, kmp_free_fn free_fn,
                              kmp_arena *out, char errbuf[KMP_PCAP_ERRBUF], kmp_pkt_meta **meta_out, uint32_t **seq_out);
+/* The arena and the metadata of kmp_arena_from_pcap_meta, and beside them the accepted frames' capture times in payload order, in
+ * microseconds, as kmpgpu_scan_thresholds takes them: *ts_out holds out->n_pkts words, comes from malloc() and is released with free().
+ * Classic pcap: ts_sec * 1e6 + ts_frac; under the nanosecond magic 0xA1B23C4D ts_sec * 1e6 + ts_frac / 1000.  pcapng: the block's 64-bit
+ * timestamp taken as microseconds (if_tsresol is not parsed; a Simple Packet Block has none: 0).  meta_out and ts_out may each be NULL.
+ * kmp_arena_from_pcap_seq_ts: the same with seq_out as kmp_arena_from_pcap_seq gives it; every out array may be NULL. */
+int  kmp_arena_from_pcap_ts(const char *path, int proto, kmp_alloc_fn alloc_fn, kmp_free_fn free_fn,
+                            kmp_arena *out, char errbuf[KMP_PCAP_ERRBUF], kmp_pkt_meta **meta_out, uint64_t **ts_out);
+int  kmp_arena_from_pcap_seq_ts(const char *path, int proto, kmp_alloc_fn alloc_fn, kmp_free_fn free_fn,
+                                kmp_arena *out, char errbuf[KMP_PCAP_ERRBUF], kmp_pkt_meta **meta_out, uint32_t **seq_out, uint64_t **ts_out);
 /* Build an arena from caller-supplied payloads (tests, synthetic inputs). */
 int  kmp_arena_from_payloads(const uint8_t *const *payloads, const uint32_t *lens, uint64_t n,
                              kmp_alloc_fn alloc_fn, kmp_free_fn free_fn, kmp_arena *out);

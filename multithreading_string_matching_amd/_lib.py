@@ -180,6 +180,21 @@ FLOWBITS_MAX = 32          # KMPGPU_FLOWBITS_MAX
 FLOWBIT_OPS = {"isset": 0, "isnotset": 1, "set": 2, "unset": 3, "toggle": 4, "noalert": 5}     # KMPGPU_FB_*
 
 
+class Threshold(C.Structure):
+    """kmpgpu_threshold (include/kmpgpu.h)."""
+    _fields_ = [("rule", C.c_uint32), ("track", C.c_uint32), ("type", C.c_uint32), ("count", C.c_uint32), ("window", C.c_uint64)]
+
+
+class Thresholds(C.Structure):
+    """kmp_thresholds (include/kmphost.h)."""
+    _fields_ = [("n", C.c_uint32), ("thr", C.POINTER(Threshold))]
+
+
+THR_TRACKS = {"by_rule": 0, "by_src": 1, "by_dst": 2, "by_flow": 3}           # KMPGPU_THR_BY_*
+THR_TYPES = {"at_least": 0, "at_most": 1, "exactly": 2}                       # KMPGPU_THR_AT_LEAST, _AT_MOST, _EXACTLY
+THR_NO_WINDOW = 0xFFFFFFFFFFFFFFFF                                            # KMPGPU_THR_NO_WINDOW
+
+
 class Match(C.Structure):
     """kmpgpu_match (include/kmpgpu.h)."""
     _fields_ = [("packet", C.c_uint64), ("offset", C.c_uint32), ("pattern", C.c_uint32)]
@@ -212,6 +227,8 @@ HOST_API = {
     "kmp_headers_free": (None, [C.POINTER(Headers)]),
     "kmp_flowbits_parse": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(Flowbits), C.c_char_p]),
     "kmp_flowbits_free": (None, [C.POINTER(Flowbits)]),
+    "kmp_thresholds_parse": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(Thresholds), C.c_char_p]),
+    "kmp_thresholds_free": (None, [C.POINTER(Thresholds)]),
     "kmp_rules_parse_bt": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Rules), C.c_char_p]),
     "kmp_bytetests_parse": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(ByteTests), C.c_char_p]),
     "kmp_bytetests_free": (None, [C.POINTER(ByteTests)]),
@@ -240,6 +257,10 @@ HOST_API = {
     "kmp_copy_bytes": (None, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "kmp_batch_close": (None, [C.c_void_p]),
     "kmp_synth_fill_host": (None, [u8p, u64p, u32p, C.c_uint64, C.c_uint64, C.POINTER(SynthParams), C.c_int]),
+    "kmp_arena_from_pcap_ts": (C.c_int, [C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Arena), C.c_char_p, C.POINTER(C.POINTER(PktMeta)),
+                                         C.POINTER(u64p)]),
+    "kmp_arena_from_pcap_seq_ts": (C.c_int, [C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Arena), C.c_char_p, C.POINTER(C.POINTER(PktMeta)),
+                                             C.POINTER(u32p), C.POINTER(u64p)]),
     "kmp_synth_count_planted": (C.c_uint64, [u32p, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(SynthParams)]),
     "kmp_report": (None, [C.c_void_p, C.POINTER(Patterns), u64p, C.c_double]),
     "kmp_write_udp_pcap": (C.c_int, [C.c_char_p, u8p, u64p, u32p, C.c_uint64]),
@@ -305,6 +326,9 @@ GPU_API = {
     "kmpgpu_scan_flows": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
     "kmpgpu_set_flowbits": (C.c_int, [C.c_void_p, C.POINTER(FlowbitOp), C.c_uint32, C.c_uint32]),
     "kmpgpu_scan_flowbits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
+    "kmpgpu_set_thresholds": (C.c_int, [C.c_void_p, C.POINTER(Threshold), C.c_uint32]),
+    "kmpgpu_scan_thresholds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.POINTER(Timing)]),
     "kmpgpu_flows_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "kmpgpu_load_seams": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, u64p]),
     "kmpgpu_seams_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),

@@ -128,6 +128,15 @@
  * together with KMPGPU_FLOW_ALERTS_FILE, KMPGPU_FLOW_SEAMS, KMPGPU_FLOW_STREAMS, KMPGPU_DECODE or KMPGPU_EXPORT_FILE (left for later), a
  * file that does not parse or whose bits form a cycle.  stdout is what it is without the variable.
  *
+ * KMPGPU_THRESHOLDS_FILE=<thresholds>, together with KMPGPU_RULES_FILE and KMPGPU_ALERTS_FILE: a rule fires on the Nth hit per tracker in a
+ * time window (kmpgpu_set_thresholds, kmpgpu_scan_thresholds; the file format is kmp_thresholds_parse's, kmphost.h: "<rule> by_src
+ * at_least 5 60").  The timestamps are the capture's, in microseconds (kmp_arena_from_pcap_ts); the alerts file then holds the ALERT rows:
+ * a rule's line for a payload where the rule matches it AND every threshold of the rule passes; "payload,rule" sorted as ever.  The
+ * payloads are grouped into flows (KMPGPU_FLOWS_DIRECTED=1: per direction) only when a by_flow line is present.  Message on stderr and
+ * exit 1, before any GPU work: the variable without the other two, more than one shard, the variable together with KMPGPU_FLOWBITS_FILE,
+ * KMPGPU_FLOW_ALERTS_FILE, KMPGPU_FLOW_SEAMS, KMPGPU_FLOW_STREAMS, KMPGPU_DECODE or KMPGPU_EXPORT_FILE, with KMPGPU_DEVICE_EXTRACT=1 (the
+ * device extractor keeps no timestamps), a file that does not parse.  stdout is what it is without the variable.
+ *
  * KMPGPU_NOCASE=1: every pattern matches case-insensitively (ASCII letters; kmpgpu_set_patterns_flags), in the counts and in
  * the offsets file alike; the report prints every token as written in the pattern file.
  *
@@ -184,6 +193,9 @@ typedef struct cli_options {
     kmp_rules rules;                        /* KMPGPU_RULES_FILE, set before the first output that needs them */
     const char *flowbits_path;              /* KMPGPU_FLOWBITS_FILE */
     kmp_flowbits flowbits;                  /* ... and its ops, set behind the rules (n == 0: none) */
+    const char *thresholds_path;            /* KMPGPU_THRESHOLDS_FILE */
+    kmp_thresholds thresholds;              /* ... and its thresholds, set behind the rules (n == 0: none) */
+    int thresholds_by_flow, thresholds_by_addr;       /* some line is by_flow; by_src or by_dst */
 } cli_options;
 
 /* The capture in host memory -- as payloads, or with KMPGPU_DEVICE_EXTRACT=1 as raw frames -- and when it got there. */
@@ -192,6 +204,7 @@ typedef struct capture {
     kmp_frames frames;
     kmp_pkt_meta *meta;                     /* beside the arena where header predicates are set: its payloads' header fields */
     uint32_t *seq;                          /* ... and under KMPGPU_FLOW_STREAMS_ORDER=seq their TCP sequence numbers */
+    uint64_t *ts;                           /* ... and under KMPGPU_THRESHOLDS_FILE their capture times in microseconds */
     double t_load0, t_loaded, t_warm;
 } capture;
 
@@ -370,6 +383,37 @@ static void load_options(int argc, char *argv[], cli_options *opt)
             exit(1);
         }
     }
+    /* rate thresholds: they too change what the alerts file holds and nothing else; one shard, whose timestamps come from the capture */
+    opt->thresholds_path = env_path("KMPGPU_THRESHOLDS_FILE");
+    if (opt->thresholds_path) {
+        static const char *const not_with[][2] = {
+            {"KMPGPU_FLOWBITS_FILE", "thresholds over flow-bit alerts are not defined"}, {"KMPGPU_FLOW_ALERTS_FILE", "the rules per flow know no thresholds"},
+            {"KMPGPU_FLOW_SEAMS", "seams have no time"}, {"KMPGPU_FLOW_STREAMS", "streams have no time"},
+            {"KMPGPU_DECODE", "decoded payloads keep no timestamps in this program"}, {"KMPGPU_EXPORT_FILE", "the export selects by the rules without their thresholds"}};
+        needs_rules_and_alerts("KMPGPU_THRESHOLDS_FILE", opt);
+        if (opt->shards > 1) {
+            fprintf(stderr, "KMPGPU_THRESHOLDS_FILE needs one shard, thread_number is %d: a tracker's window would be cut at a shard's edge\n", opt->shards);
+            exit(1);
+        }
+        for (size_t i = 0; i < sizeof not_with / sizeof not_with[0]; i++)
+            if (env_path(not_with[i][0])) {
+                fprintf(stderr, "KMPGPU_THRESHOLDS_FILE does not go together with %s: %s\n", not_with[i][0], not_with[i][1]);
+                exit(1);
+            }
+        if (opt->device_extract) {
+            fprintf(stderr, "KMPGPU_THRESHOLDS_FILE does not go together with KMPGPU_DEVICE_EXTRACT=1: the device extractor keeps no timestamps\n");
+            exit(1);
+        }
+        _Static_assert(sizeof err >= KMP_THRESHOLDS_ERRBUF, "room for the thresholds parser's message");
+        if (kmp_thresholds_parse(opt->thresholds_path, opt->rules.n, &opt->thresholds, err)) {
+            fprintf(stderr, "error reading thresholds file %s: %s\n", opt->thresholds_path, err);
+            exit(1);
+        }
+        for (uint32_t q = 0; q < opt->thresholds.n; q++) {
+            if (opt->thresholds.thr[q].track == KMP_THR_BY_FLOW) opt->thresholds_by_flow = 1;
+            if (opt->thresholds.thr[q].track == KMP_THR_BY_SRC || opt->thresholds.thr[q].track == KMP_THR_BY_DST) opt->thresholds_by_addr = 1;
+        }
+    }
     /* the offset windows likewise */
     if (windows_path) {
         if (!opt->offsets_path && !opt->packets_path && !opt->alerts_path && !opt->export_path) {
@@ -479,7 +523,7 @@ static void load_options(int argc, char *argv[], cli_options *opt)
             exit(1);
         }
     }
-    opt->want_meta = opt->headers.n || opt->flows_path || opt->flow_alerts_path || opt->flowbits.n;
+    opt->want_meta = opt->headers.n || opt->flows_path || opt->flow_alerts_path || opt->flowbits.n || opt->thresholds_by_flow || opt->thresholds_by_addr;
     /* the export starts as a capture without frames: a path that cannot be written ends the run here */
     if (opt->export_path && kmp_write_udp_pcap_part(opt->export_path, 0, NULL, NULL, NULL, 0, 0)) {
         perror("KMPGPU_EXPORT_FILE");
@@ -498,6 +542,7 @@ static void free_options(cli_options *opt)
     kmp_bytetests_free(&opt->bytetests);
     kmp_regexes_free(&opt->regexes);
     kmp_flowbits_free(&opt->flowbits);
+    kmp_thresholds_free(&opt->thresholds);
     free(opt->win_first); free(opt->win_last);
 }
 
@@ -528,6 +573,8 @@ static void load_capture(const cli_options *opt, capture *cap)
         rc = kmp_frames_from_pcap(opt->pcap_path, NULL, NULL, &cap->frames, errbuf);
     else if (opt->streams_order == KMP_CLI_STREAMS_ORDER_SEQ)               /* (streams go with flow alerts: the header fields are wanted too) */
         rc = kmp_arena_from_pcap_seq(opt->pcap_path, opt->proto, NULL, NULL, &cap->arena, errbuf, &cap->meta, &cap->seq);
+    else if (opt->thresholds.n)                                             /* the same arena, and every payload's capture time */
+        rc = kmp_arena_from_pcap_ts(opt->pcap_path, opt->proto, NULL, NULL, &cap->arena, errbuf, opt->want_meta ? &cap->meta : NULL, &cap->ts);
     else if (opt->want_meta)                                                /* the same arena, and the header fields the predicates and the flows read */
         rc = kmp_arena_from_pcap_meta(opt->pcap_path, opt->proto, NULL, NULL, &cap->arena, errbuf, &cap->meta);
     else
@@ -690,6 +737,24 @@ static void write_flowbit_alerts(FILE *fp, const cli_options *opt, cli_run *run)
     free(hits);
 }
 
+/* KMPGPU_THRESHOLDS_FILE: the alerts file holds the alert rows of kmpgpu_scan_thresholds instead -- the thresholds set behind the rules,
+ * the capture's timestamps, flows only where a by_flow line asks for them, and one "payload,rule" line per set bit, by payload, then rule. */
+static void write_threshold_alerts(FILE *fp, const cli_options *opt, cli_run *run)
+{
+    _Static_assert(sizeof(kmp_threshold) == sizeof(kmpgpu_threshold), "kmp_threshold has the layout of kmpgpu_threshold");
+    kmpgpu_ctx *ctx = run->rows[0];
+    const uint64_t n = run->job[0].n_payloads, W = (n + 63) / 64, nr = opt->rules.n;
+    if (opt->thresholds_by_flow && kmpgpu_flows_build(ctx, opt->flows_directed ? KMPGPU_FLOW_DIRECTED : 0u, NULL, NULL)) die_gpu("kmpgpu_flows_build");
+    if (kmpgpu_set_thresholds(ctx, (const kmpgpu_threshold *)opt->thresholds.thr, opt->thresholds.n)) die_gpu("kmpgpu_set_thresholds");
+    uint64_t *hits = (uint64_t *)calloc((size_t)(nr * W + 1), sizeof(uint64_t));
+    if (!hits) die_gpu("KMPGPU_THRESHOLDS_FILE: out of memory");
+    if (kmpgpu_scan_thresholds(ctx, run->job[0].cap->ts, 0, NULL, NULL, hits, NULL, NULL, NULL)) die_gpu("kmpgpu_scan_thresholds");
+    for (uint64_t k = 0; k < n; k++)
+        for (uint64_t r = 0; r < nr; r++)
+            if (hits[r * W + (k >> 6)] >> (k & 63) & 1u) fprintf(fp, "%llu,%llu\n", (unsigned long long)k, (unsigned long long)r);
+    free(hits);
+}
+
 /* KMPGPU_PACKETS_FILE (family KMPGPU_ALERT_PATTERNS), KMPGPU_ALERTS_FILE (KMPGPU_ALERT_RULES; a rules file without rules leaves the file
  * empty): one "payload,index" line per record of every context's alert list of the family (kmpgpu_scan_alerts: built and sorted by
  * payload, then index, on the device).  The records come back in pieces of a fixed size; no bit matrix leaves the device. */
@@ -703,6 +768,11 @@ static void write_alerts(const char *path, const cli_options *opt, cli_run *run,
     if (by_rules) set_rules_once(opt, run);
     if (by_rules && opt->flowbits.n) {
         write_flowbit_alerts(fp, opt, run);
+        fclose(fp);
+        return;
+    }
+    if (by_rules && opt->thresholds.n) {
+        write_threshold_alerts(fp, opt, run);
         fclose(fp);
         return;
     }
@@ -947,6 +1017,7 @@ int main(int argc, char *argv[])
     kmp_frames_free(&cap.frames);
     free(cap.meta);
     free(cap.seq);
+    free(cap.ts);
     free_options(&opt);
     return 0;
 }

@@ -165,6 +165,7 @@ typedef struct kmp_walk {
     int      swap;          /* file byte order differs from the host's */
     int      ng;            /* pcapng (libpcap's pcap_open_offline reads both formats) */
     uint32_t linktype, snaplen;
+    const uint8_t *blk;     /* pcapng: the block walk_next returned a packet from, its lengths checked (kmp_arena_from_pcap_ts reads its time) */
 } kmp_walk;
 
 /* The checks pcap_open_offline makes on the file header (message texts as libpcap words them). */
@@ -268,6 +269,7 @@ static int walk_next(kmp_walk *w, uint32_t *caplen, uint32_t *len, const uint8_t
         const uint32_t body = total - 12u;
         if (w->sz - w->pos - 8u < (uint64_t)body + 4u) return -1;      /* body + trailing length */
         const int r = pcapng_packet(w, type, body, h + 8, caplen, len, data);
+        w->blk = h;
         w->pos += total;
         if (r != 0) return r;
     }
@@ -1105,6 +1107,110 @@ void kmp_flowbits_free(kmp_flowbits *f)
     memset(f, 0, sizeof *f);
 }
 
+/* ============================ rate thresholds =========================================== */
+
+_Static_assert(KMP_THRESHOLDS_ERRBUF == KMP_LINE_ERRBUF, "the thresholds' error buffer has the size of the others");
+
+typedef struct thresholds_ctx {
+    uint32_t n_rules;
+    kmp_thresholds *out;
+    size_t n, cap;
+} thresholds_ctx;
+
+/* "<digits>[.<1 to 6 digits>]" as microseconds, exactly: 0 for a field that is no such number, 2 for one above max */
+static int seconds_to_us(const char *p, const char *end, uint64_t max, uint64_t *out)
+{
+    const char *dot = (const char *)memchr(p, '.', (size_t)(end - p));
+    const char *ie = dot ? dot : end;
+    uint64_t whole = 0, frac = 0;
+    if (p == ie) return 0;
+    for (const char *q = p; q < ie; q++) {
+        if (*q < '0' || *q > '9') return 0;
+        if (whole > (max - (uint64_t)(*q - '0')) / 10u) return 2;
+        whole = whole * 10u + (uint64_t)(*q - '0');
+    }
+    if (dot) {
+        const int nd = (int)(end - dot - 1);
+        if (nd < 1 || nd > 6) return 0;
+        for (const char *q = dot + 1; q < end; q++) {
+            if (*q < '0' || *q > '9') return 0;
+            frac = frac * 10u + (uint64_t)(*q - '0');
+        }
+        for (int i = nd; i < 6; i++) frac *= 10u;
+    }
+    if (whole > (max - frac) / 1000000u) return 2;
+    *out = whole * 1000000u + frac;
+    return 1;
+}
+
+static int thresholds_line(void *ctx, const char *p, const char *end, size_t lineno, char *errbuf)
+{
+    static const char *const tracks[] = {"by_rule", "by_src", "by_dst", "by_flow"};          /* KMP_THR_BY_RULE .. KMP_THR_BY_FLOW */
+    static const char *const types[] = {"at_least", "at_most", "exactly"};                   /* KMP_THR_AT_LEAST .. KMP_THR_EXACTLY */
+    thresholds_ctx *c = (thresholds_ctx *)ctx;
+    const char *tok;
+    int len;
+    uint64_t rule, count, window = KMP_THR_NO_WINDOW;
+    uint32_t track = 0, type = 0;
+#define FIELD (len > 64 ? 64 : len), tok
+    next_field(&p, end, &tok, &len);                                    /* (the line is not blank) */
+    if (!plain_number(tok, tok + len, 0xFFFFFFFFull, &rule)) return line_error(errbuf, lineno, "'%.*s' is not a rule index", FIELD);
+    if (rule >= c->n_rules) return line_error(errbuf, lineno, "rule %llu of %u", (unsigned long long)rule, c->n_rules);
+    if (!next_field(&p, end, &tok, &len)) return line_error(errbuf, lineno, "rule %llu has no track (by_rule, by_src, by_dst, by_flow)", (unsigned long long)rule);
+    while (track < 4u && !field_is(tok, len, tracks[track])) track++;
+    if (track == 4u) return line_error(errbuf, lineno, "'%.*s' is none of by_rule by_src by_dst by_flow", FIELD);
+    if (!next_field(&p, end, &tok, &len)) return line_error(errbuf, lineno, "rule %llu has no type (at_least, at_most, exactly)", (unsigned long long)rule);
+    while (type < 3u && !field_is(tok, len, types[type])) type++;
+    if (type == 3u) return line_error(errbuf, lineno, "'%.*s' is none of at_least at_most exactly", FIELD);
+    if (!next_field(&p, end, &tok, &len)) return line_error(errbuf, lineno, "rule %llu has no count", (unsigned long long)rule);
+    if (!plain_number(tok, tok + len, 0xFFFFFFFFull, &count) || count == 0)
+        return line_error(errbuf, lineno, "'%.*s' is not a count in 1..4294967295", FIELD);
+    if (!next_field(&p, end, &tok, &len)) return line_error(errbuf, lineno, "rule %llu has no window (seconds, or all)", (unsigned long long)rule);
+    if (!field_is(tok, len, "all")) {
+        const int ok = seconds_to_us(tok, tok + len, KMP_THR_NO_WINDOW - 1u, &window);
+        if (ok == 0) return line_error(errbuf, lineno, "'%.*s' is neither all nor seconds with at most 6 fraction digits", FIELD);
+        if (ok == 2) return line_error(errbuf, lineno, "'%.*s' seconds are more than 2^64 - 2 microseconds", FIELD);
+        if (window == 0) return line_error(errbuf, lineno, "'%.*s': a window of 0 holds no payload", FIELD);
+    }
+    if (next_field(&p, end, &tok, &len)) return line_error(errbuf, lineno, "'%.*s' follows the window", FIELD);
+#undef FIELD
+    if (c->n == c->cap) {
+        const size_t nc = c->cap ? c->cap * 2 : 64;
+        kmp_threshold *nv = (kmp_threshold *)realloc(c->out->thr, nc * sizeof *nv);
+        if (!nv) return out_of_memory(errbuf);
+        c->out->thr = nv; c->cap = nc;
+    }
+    const kmp_threshold t = {(uint32_t)rule, track, type, (uint32_t)count, window};
+    c->out->thr[c->n++] = t;
+    return KMPHOST_OK;
+}
+
+int kmp_thresholds_parse(const char *path, uint32_t n_rules, kmp_thresholds *out, char errbuf[KMP_THRESHOLDS_ERRBUF])
+{
+    _Static_assert(sizeof(kmp_threshold) == 24, "kmp_threshold has the layout of kmpgpu_threshold");
+    memset(out, 0, sizeof *out);
+    if (errbuf) errbuf[0] = 0;
+    thresholds_ctx c = {n_rules, out, 0, 0};
+    int rc = text_lines(path, thresholds_line, &c, errbuf);
+    if (!rc && c.n > 0x7FFFFFFFull) {
+        rc = KMPHOST_EINVAL;
+        if (errbuf) snprintf(errbuf, KMP_LINE_ERRBUF, "%zu thresholds are more than 2147483647", c.n);
+    }
+    if (rc) {
+        kmp_thresholds_free(out);
+        return rc;
+    }
+    out->n = (uint32_t)c.n;
+    return KMPHOST_OK;
+}
+
+void kmp_thresholds_free(kmp_thresholds *t)
+{
+    if (!t) return;
+    free(t->thr);
+    memset(t, 0, sizeof *t);
+}
+
 /* ============================ byte tests ================================================ */
 
 typedef struct bytetests_ctx {
@@ -1517,6 +1623,73 @@ int kmp_arena_from_pcap_seq(const char *path, int proto, kmp_alloc_fn alloc_fn, 
     free(ix.off); free(ix.caplen);
     view_close(&v);
     return rc;
+}
+
+/* The timestamp of the packet walk_next has just returned, in microseconds: a classic record's ts_sec and ts_frac lie in the 16 bytes in
+ * front of its data, which walk_next has found inside the file; a pcapng packet comes from the block w->blk, whose leading length
+ * walk_next has checked against the file and whose body pcapng_packet has found to hold the 20 bytes in front of the data -- the trailing
+ * length word is file data nobody has checked and is not looked at.  An (Enhanced) Packet Block holds the two halves of its 64-bit
+ * timestamp behind the interface id -- taken as microseconds, if_tsresol is not parsed.  A Simple Packet Block has no time: 0. */
+static uint64_t walk_ts_us(const kmp_walk *w, const uint8_t *data, int nano)
+{
+    if (!w->ng) {
+        const uint32_t sec = w->swap ? bswap32(rd32(data - 16)) : rd32(data - 16), frac = w->swap ? bswap32(rd32(data - 12)) : rd32(data - 12);
+        return (uint64_t)sec * 1000000u + (nano ? frac / 1000u : frac);
+    }
+    const uint8_t *h = w->blk;
+    const uint32_t type = w->swap ? bswap32(rd32(h)) : rd32(h);
+    if (type != 6u && type != 2u) return 0;
+    const uint32_t hi = w->swap ? bswap32(rd32(h + 12)) : rd32(h + 12), lo = w->swap ? bswap32(rd32(h + 16)) : rd32(h + 16);
+    return (uint64_t)hi << 32 | lo;
+}
+
+/* ... and with ts_out the accepted frames' capture times in microseconds, from malloc: the arena first, then one more walk over the records */
+int kmp_arena_from_pcap_ts(const char *path, int proto, kmp_alloc_fn alloc_fn, kmp_free_fn free_fn,
+                           kmp_arena *out, char errbuf[KMP_PCAP_ERRBUF], kmp_pkt_meta **meta_out, uint64_t **ts_out)
+{
+    return kmp_arena_from_pcap_seq_ts(path, proto, alloc_fn, free_fn, out, errbuf, meta_out, NULL, ts_out);
+}
+
+int kmp_arena_from_pcap_seq_ts(const char *path, int proto, kmp_alloc_fn alloc_fn, kmp_free_fn free_fn,
+                               kmp_arena *out, char errbuf[KMP_PCAP_ERRBUF], kmp_pkt_meta **meta_out, uint32_t **seq_out, uint64_t **ts_out)
+{
+    if (ts_out) *ts_out = NULL;
+    int rc = kmp_arena_from_pcap_seq(path, proto, alloc_fn, free_fn, out, errbuf, meta_out, seq_out);
+    if (rc || !ts_out) return rc;
+    uint64_t *ts = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)(out->n_pkts ? out->n_pkts : 1));
+    kmp_view v;
+    if (ts) rc = view_open(path, &v, errbuf);
+    else { rc = KMPHOST_ENOMEM; if (errbuf) snprintf(errbuf, KMP_PCAP_ERRBUF, "out of memory"); }
+    if (!rc) {
+        kmp_walk w;
+        rc = walk_init(&w, v.base, v.size, errbuf);
+        if (!rc) {
+            const uint32_t magic = rd32(v.base);
+            const int nano = !w.ng && (magic == 0xA1B23C4Du || bswap32(magic) == 0xA1B23C4Du);
+            uint32_t cl, ln, o, l;
+            const uint8_t *data;
+            uint64_t k = 0;
+            while (walk_next(&w, &cl, &ln, &data) >= 0) {
+                if (!((proto == KMP_PROTO_TCP) ? kmp_extract_tcp(data, cl, &o, &l) : kmp_extract_udp(data, cl, &o, &l))) continue;
+                if (k < out->n_pkts) ts[k] = walk_ts_us(&w, data, nano);
+                k++;
+            }
+            if (k != out->n_pkts) {                     /* (the file changed between the two walks) */
+                rc = KMPHOST_EIO;
+                if (errbuf) snprintf(errbuf, KMP_PCAP_ERRBUF, "%s changed while it was read", path);
+            }
+        }
+        view_close(&v);
+    }
+    if (rc) {
+        free(ts);
+        kmp_arena_free(out);
+        if (meta_out) { free(*meta_out); *meta_out = NULL; }
+        if (seq_out) { free(*seq_out); *seq_out = NULL; }
+        return rc;
+    }
+    *ts_out = ts;
+    return KMPHOST_OK;
 }
 
 /* ============================ raw frames (on-device extraction) ========================= */

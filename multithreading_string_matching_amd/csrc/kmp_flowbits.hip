@@ -307,6 +307,12 @@ hipError_t kmp_launch_flowbits_order(const uint32_t *flow_of, uint64_t n, uint64
     return hipGetLastError();
 }
 
+kmp_order_view kmp_flowbits_order_view(const uint8_t *order_buf, uint64_t n)
+{
+    const FbOrder o = fb_order(const_cast<uint8_t *>(order_buf), n);
+    return kmp_order_view{o.order, o.inv, o.keys, o.head};
+}
+
 size_t kmp_flowbits_ws_bytes(uint64_t n)
 {
     uint64_t elems = fb_pad(n);

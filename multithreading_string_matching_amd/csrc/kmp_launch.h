@@ -1,5 +1,5 @@
 /* kmp_launch.h -- launch entry points of kmp_scan_*.hip / kmp_prep.hip / kmp_fold.hip / kmp_marks.hip / kmp_rules.hip / kmp_relations.hip /
- * kmp_chains.hip / kmp_headers.hip / kmp_bytetests.hip / kmp_regex.hip / kmp_select.hip / kmp_decode.hip / kmp_alerts.hip / kmp_flows.hip / kmp_seams.hip / kmp_streams.hip / kmp_streams_seq.hip / kmp_flowbits.hip, used
+ * kmp_chains.hip / kmp_headers.hip / kmp_bytetests.hip / kmp_regex.hip / kmp_select.hip / kmp_decode.hip / kmp_alerts.hip / kmp_flows.hip / kmp_seams.hip / kmp_streams.hip / kmp_streams_seq.hip / kmp_flowbits.hip / kmp_thresholds.hip, used
  * by the C-ABI layer (kmpgpu.hip), which alone decides what is launched; the tables kmp_launch_scan_multi takes come from kmp_tables.h. */
 #ifndef KMP_LAUNCH_H
 #define KMP_LAUNCH_H
@@ -335,5 +335,43 @@ hipError_t kmp_launch_flowbits_rows(const uint32_t *before32, uint64_t n, uint32
 hipError_t kmp_launch_flowbits_final(const unsigned long long *rule_rows, const unsigned long long *before_rows, uint64_t stride,
                                      const uint4 *tests, uint32_t n_rules, unsigned long long *alert_rows, unsigned long long *counts,
                                      unsigned long long *any, hipStream_t st);
+
+/* The order buffer of kmp_launch_flowbits_order as its readers see it: order[n], inv[n] (inv[order[i]] = i), the sorted keys[n] and
+ * head[n + 1] (1 where the key changes at sorted position i; head[n] = 1). */
+struct kmp_order_view {
+    const uint32_t *order, *inv, *keys;
+    const uint8_t  *head;
+};
+kmp_order_view kmp_flowbits_order_view(const uint8_t *order_buf, uint64_t n);
+
+/* kmp_thresholds.hip (kmpgpu_scan_thresholds): the rate thresholds over n <= 2^32 - 2 payloads whose rule rows kmp_launch_rules has written
+ * (stride even, 64 stride >= n).  Arrays a scan runs over hold kmp_thresholds_pad(n) items (whole 16-byte loads) and are 16-byte aligned;
+ * agg (kmp_thresholds_agg_bytes(n) bytes) takes the tile aggregates of either scan.  *launches is added to.
+ * _time (1 kernel up to KMP_SCAN_TILE payloads, else 3 per level of aggregates + 1): T[n], the caller's timestamps, becomes their running
+ *   maximum, in place.
+ * _keys (1 kernel): keys[k] = the source (dst: the destination) address of meta[k]: the input of kmp_launch_flowbits_order with
+ *   n_flows = 2^32, which sorts by all 32 bits.
+ * _tsort (1 kernel): Ts[i] = T[order[i]] of an order buffer.
+ * Per threshold, with order_buf NULL for KMPGPU_THR_BY_RULE (the identity, one tracker):
+ * _count (1 kernel + the scan's): C[i] = the number of set bits of rule_row at the sorted positions 0 .. i.
+ * _pass (1 kernel): word j < ceil(n / 64) of pass_row: bit k = the threshold's comparison on n[q][k] (a payload without a base hit: 0 unless
+ *   window_counts is given); window_counts[n] (or NULL) takes n[q][k] for every k.  Ts: T in the track's order (T itself for BY_RULE);
+ *   not read where window is KMPGPU_THR_NO_WINDOW.  The caller zeroes the row.
+ * _final (1 kernel): every word of alert_rows[n_rules][stride] = the rule row AND the pass rows [n_thr][stride] the table
+ *   (kmp_pack_thresholds, kmp_rowtables.h) names for the rule; a rule's set bits are added to counts[r] and ORed into any[stride]; the caller
+ *   zeroes those two. */
+uint64_t kmp_thresholds_pad(uint64_t n);
+size_t kmp_thresholds_agg_bytes(uint64_t n);
+hipError_t kmp_launch_thresholds_time(unsigned long long *T, uint64_t n, uint8_t *agg, uint32_t *launches, hipStream_t st);
+hipError_t kmp_launch_thresholds_keys(const uint4 *meta, uint64_t n, bool dst, uint32_t *keys, hipStream_t st);
+hipError_t kmp_launch_thresholds_tsort(const unsigned long long *T, const uint8_t *order_buf, uint64_t n, unsigned long long *Ts, hipStream_t st);
+hipError_t kmp_launch_thresholds_count(const unsigned long long *rule_row, uint64_t n, const uint8_t *order_buf, uint32_t *C, uint8_t *agg,
+                                       uint32_t *launches, hipStream_t st);
+hipError_t kmp_launch_thresholds_pass(const unsigned long long *rule_row, uint64_t n, const uint8_t *order_buf, const unsigned long long *Ts,
+                                      const uint32_t *C, uint32_t type, uint32_t count, unsigned long long window,
+                                      unsigned long long *pass_row, uint32_t *window_counts, hipStream_t st);
+hipError_t kmp_launch_thresholds_final(const unsigned long long *rule_rows, const unsigned long long *pass_rows, uint64_t stride,
+                                       const uint32_t *table, uint32_t n_rules, unsigned long long *alert_rows, unsigned long long *counts,
+                                       unsigned long long *any, hipStream_t st);
 
 #endif

@@ -351,3 +351,33 @@ int kmp_pack_flowbits(const kmpgpu_flowbit_op *ops, uint32_t n_ops, uint32_t n_b
     for (uint32_t r = 0; r < n_rules; r++) out->tests.insert(out->tests.end(), {isset[r], isnotset[r], noalert[r], 0u});
     return KMPGPU_OK;
 }
+
+int kmp_pack_thresholds(const kmpgpu_threshold *thr, uint32_t n_thr, uint32_t n_rules, kmp_threshold_tables *out, std::string *msg)
+{
+    *out = kmp_threshold_tables{};
+    if (!thr) return refuse(msg, "kmpgpu_set_thresholds: thr is NULL");
+    for (uint32_t q = 0; q < n_thr; q++) {
+        const kmpgpu_threshold &t = thr[q];
+        if (t.rule >= n_rules) return refuse(msg, "kmpgpu_set_thresholds: threshold %u names rule %u of %u", q, t.rule, n_rules);
+        if (t.track > KMPGPU_THR_BY_FLOW) return refuse(msg, "kmpgpu_set_thresholds: threshold %u: track %u is none of KMPGPU_THR_BY_*", q, t.track);
+        if (t.type > KMPGPU_THR_EXACTLY) return refuse(msg, "kmpgpu_set_thresholds: threshold %u: type %u is none of KMPGPU_THR_AT_LEAST, _AT_MOST, _EXACTLY", q, t.type);
+        if (t.count == 0) return refuse(msg, "kmpgpu_set_thresholds: threshold %u: count is 0", q);
+        if (t.window == 0) return refuse(msg, "kmpgpu_set_thresholds: threshold %u: window is 0 (no payload lies inside it)", q);
+    }
+    for (uint32_t q = 0; q < n_thr; q++) {
+        out->by_track[thr[q].track].push_back(q);
+        if (thr[q].window != KMPGPU_THR_NO_WINDOW) out->windowed = true;
+    }
+    /* {first, number} per rule, then the rules' thresholds rule by rule, each rule's in the order given */
+    out->final_table.assign(2u * (size_t)n_rules, 0u);
+    for (uint32_t q = 0; q < n_thr; q++) out->final_table[2u * (size_t)thr[q].rule + 1u]++;
+    uint32_t first = 0;
+    for (uint32_t r = 0; r < n_rules; r++) { out->final_table[2u * (size_t)r] = first; first += out->final_table[2u * (size_t)r + 1u]; }
+    std::vector<uint32_t> fill(n_rules, 0u);
+    out->final_table.resize(2u * (size_t)n_rules + n_thr, 0u);
+    for (uint32_t q = 0; q < n_thr; q++) {
+        const uint32_t r = thr[q].rule;
+        out->final_table[2u * (size_t)n_rules + out->final_table[2u * (size_t)r] + fill[r]++] = q;
+    }
+    return KMPGPU_OK;
+}

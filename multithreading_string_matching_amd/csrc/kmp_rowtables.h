@@ -1,5 +1,5 @@
 /*
- * kmp_rowtables.h -- what kmpgpu_set_rules, kmpgpu_set_windows, kmpgpu_set_relations, kmpgpu_set_chains, kmpgpu_set_headers, kmpgpu_set_bytetests, kmpgpu_set_regexes and kmpgpu_set_flowbits upload, checked and packed on
+ * kmp_rowtables.h -- what kmpgpu_set_rules, kmpgpu_set_windows, kmpgpu_set_relations, kmpgpu_set_chains, kmpgpu_set_headers, kmpgpu_set_bytetests, kmpgpu_set_regexes, kmpgpu_set_flowbits and kmpgpu_set_thresholds upload, checked and packed on
  * the host by kmp_rowtables.cpp into the form the kernels read bit for bit (kmp_launch.h: kmp_launch_rules, emit_windows,
  * kmp_launch_relations, kmp_launch_chains, kmp_launch_headers, kmp_launch_bytetests, kmp_launch_regexes).  Host code without a HIP header, as kmp_tables.h: it builds and runs without a device
  * (tests/rowtables_sanitizer_driver.cpp).
@@ -116,5 +116,18 @@ struct kmp_flowbit_tables {
 };
 int kmp_pack_flowbits(const kmpgpu_flowbit_op *ops, uint32_t n_ops, uint32_t n_bits, uint32_t n_rules, kmp_flowbit_tables *out,
                       std::string *msg);
+
+/* kmpgpu_set_thresholds: the thresholds checked and grouped.  by_track[KMPGPU_THR_BY_*]: the indices q of the track's thresholds in
+ * ascending order -- what the C-ABI layer walks: one order per track in use, then the track's thresholds; windowed: some window is not
+ * KMPGPU_THR_NO_WINDOW (the timestamps are needed).  final_table, what kmp_thresholds.hip's final kernel reads: two words per rule {first,
+ * number} into the list behind them [n_thr], which holds the indices q (the pass rows) of every rule's thresholds, rule by rule, each
+ * rule's in the order given.
+ * Refusals (KMPGPU_EINVAL, the text of kmpgpu_last_error in *msg): thr NULL, a rule >= n_rules, an unknown track or type, count == 0,
+ * window == 0. */
+struct kmp_threshold_tables {
+    std::vector<uint32_t> by_track[4], final_table;
+    bool windowed = false;
+};
+int kmp_pack_thresholds(const kmpgpu_threshold *thr, uint32_t n_thr, uint32_t n_rules, kmp_threshold_tables *out, std::string *msg);
 
 #endif

@@ -268,6 +268,21 @@ struct kmpgpu_ctx {
     unsigned long long *d_fb_out = nullptr;
     uint64_t            fb_order_cap = 0, fb_ws_cap = 0, fb_out_cap = 0, fb_order_gen = 0;
     bool                fb_order_valid = false;
+    /* kmpgpu_set_thresholds: the thresholds as given, grouped by track (kmp_pack_thresholds), and the final kernel's table on the device.
+     * kmpgpu_scan_thresholds: the orders of the payloads by source and by destination address (the layout of d_fb_order), valid for the
+     * metadata of generation thr_order_gen[]; the workspace (T, the aggregates, T in every sorted track's order, the prefix sum); the pass
+     * rows [n_thr][stride], the alert rows [n_rules][stride], rule_pkt_counts[n_rules], any[stride]; the window counts where asked for.
+     * meta_gen: which arena and metadata the context holds (drop_flows counts it up unless it is kmpgpu_flows_build that calls) */
+    std::vector<kmpgpu_threshold> thr;
+    std::vector<uint32_t> thr_by_track[4];
+    bool                thr_windowed = false;
+    uint32_t           *d_thr_table = nullptr;
+    uint8_t            *d_thr_order[2] = {nullptr, nullptr}, *d_thr_ws = nullptr;
+    unsigned long long *d_thr_out = nullptr;
+    uint32_t           *d_thr_wc = nullptr;
+    uint64_t            thr_order_cap[2] = {0, 0}, thr_ws_cap = 0, thr_out_cap = 0, thr_wc_cap = 0, thr_order_gen[2] = {0, 0}, meta_gen = 0;
+    bool                thr_order_valid[2] = {false, false};
+    bool                arena_seen = false;           /* some load has reached the context (release_arena); read by kmpgpu_scan_thresholds alone */
     /* the patterns as they were set, one record {length, flags, bytes} each: what kmpgpu_scan_flows_seams compares between two contexts */
     std::vector<uint8_t> pat_sig;
 
@@ -425,6 +440,15 @@ void drop_flowbits(kmpgpu_ctx *c)
     c->n_fb_bits = 0;
 }
 
+/* ... and so do the thresholds */
+void drop_thresholds(kmpgpu_ctx *c)
+{
+    free_buffer(&c->d_thr_table);
+    c->thr.clear();
+    for (auto &v : c->thr_by_track) v.clear();
+    c->thr_windowed = false;
+}
+
 /* the rules go with the pattern set their indices refer to */
 void drop_rules(kmpgpu_ctx *c)
 {
@@ -432,6 +456,7 @@ void drop_rules(kmpgpu_ctx *c)
     free_buffer(&c->d_rule_quads);
     c->n_rules = 0;
     drop_flowbits(c);
+    drop_thresholds(c);
 }
 
 /* so do the windows */
@@ -474,11 +499,12 @@ void drop_regexes(kmpgpu_ctx *c)
 }
 
 /* the flows go with the arena and its metadata; their buffers are kept for the next build */
-void drop_flows(kmpgpu_ctx *c)
+void drop_flows(kmpgpu_ctx *c, bool rebuild = false)
 {
     c->flows_valid = false;
     c->n_flows = 0;
     c->flows_gen++;                                /* a seam list built from them is none of the next build's */
+    if (!rebuild) c->meta_gen++;                   /* the arena or its metadata change: the thresholds' address orders are none of the next one's */
 }
 
 /* the seam list goes with the arena it describes; its buffers are kept for the next build */
@@ -542,6 +568,7 @@ hipError_t ensure_owned_arena(kmpgpu_ctx *c, uint64_t bytes, uint64_t n, Headroo
 void release_arena(kmpgpu_ctx *c, bool keep_buffers = false)
 {
     if (!keep_buffers) free_owned_arena(c);
+    c->arena_seen = true;                             /* (every load comes through here first) */
     c->d_arena = nullptr; c->d_off = nullptr; c->d_len = nullptr;
     c->arena_bytes = c->n_pkts = c->payload_bytes = 0;
     c->uniform = false; c->packed = false; c->pad_clean = false; c->plan_waves = 0; c->uplan_units = 0;
@@ -614,6 +641,9 @@ void release_pass_buffers(kmpgpu_ctx *c)
     drop_streams(c);
     free_buffer(&c->d_fb_order, &c->fb_order_cap); free_buffer(&c->d_fb_ws, &c->fb_ws_cap); free_buffer(&c->d_fb_out, &c->fb_out_cap);
     c->fb_order_valid = false;
+    free_buffer(&c->d_thr_order[0], &c->thr_order_cap[0]); free_buffer(&c->d_thr_order[1], &c->thr_order_cap[1]);
+    free_buffer(&c->d_thr_ws, &c->thr_ws_cap); free_buffer(&c->d_thr_out, &c->thr_out_cap); free_buffer(&c->d_thr_wc, &c->thr_wc_cap);
+    c->thr_order_valid[0] = c->thr_order_valid[1] = false;
     c->alerts_valid = false;
     c->bitmap_live = false; c->plan_waves = c->uplan_units = 0; c->fold_stale = true;
 }
@@ -2493,6 +2523,7 @@ int kmpgpu_set_rules(kmpgpu_ctx *c, const uint32_t *rule_off, const uint32_t *te
     if (rc) return rc;
     c->n_rules = n_rules;
     drop_flowbits(c);                              /* their rule indices meant the rules before */
+    drop_thresholds(c);
     return KMPGPU_OK;
 }
 
@@ -2792,7 +2823,7 @@ int kmpgpu_flows_build(kmpgpu_ctx *c, uint32_t flags, uint64_t *n_flows, kmpgpu_
     if ((slots & (slots - 1)) || slots <= n || slots > (1ull << 32))
         return fail(KMPGPU_EINVAL, "kmpgpu_flows_build: KMPGPU_OPT_FLOW_SLOTS is %llu, no power of two above the %llu payloads (at most 2^32)",
                     (unsigned long long)slots, (unsigned long long)n);
-    drop_flows(c);                                 /* the flows before this build are gone, whatever happens */
+    drop_flows(c, /* rebuild = */ true);           /* the flows before this build are gone, whatever happens */
     if (t) *t = kmpgpu_timing{};
     if (n == 0) { c->flows_valid = true; return KMPGPU_OK; }
     HIP_TRY(hipSetDevice(c->device));
@@ -3061,6 +3092,141 @@ int kmpgpu_scan_flowbits(kmpgpu_ctx *c, uint64_t *rule_pkt_counts_out, uint64_t 
     if (rule_hits_out) HIP_TRY(download_rows(c, rule_hits_out, d_alert, p.W, p.stride, nr));
     if (state_out) HIP_TRY(download_rows(c, state_out, d_before, p.W, p.stride, nb));
     if (flow_state_out) HIP_TRY(hipMemcpyAsync(flow_state_out, d_flow_state, (size_t)nf * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    return finish_marking(c, launches, t);
+}
+
+int kmpgpu_set_thresholds(kmpgpu_ctx *c, const kmpgpu_threshold *thr, uint32_t n_thr)
+{
+    static_assert(sizeof(kmpgpu_threshold) == 24, "kmpgpu_threshold is the 24-byte record of kmpgpu.h");
+    const int sr = setter_state(c, "kmpgpu_set_thresholds");
+    if (sr) return sr;
+    if (c->n_rules == 0) return fail(KMPGPU_ESTATE, "kmpgpu_set_thresholds: no rules set");
+    kmp_threshold_tables tb;
+    std::string msg;
+    if (n_thr) {
+        const int rc = kmp_pack_thresholds(thr, n_thr, c->n_rules, &tb, &msg);
+        if (rc) return fail(rc, "%s", msg.c_str());
+    }
+    const int rc = swap_tables(c, "kmpgpu_set_thresholds: the thresholds", {{tb.final_table, (void **)&c->d_thr_table}});
+    if (rc) return rc;
+    c->thr.assign(thr, thr + n_thr);
+    for (int x = 0; x < 4; x++) c->thr_by_track[x] = tb.by_track[x];
+    c->thr_windowed = tb.windowed;
+    return KMPGPU_OK;
+}
+
+int kmpgpu_scan_thresholds(kmpgpu_ctx *c, const uint64_t *ts, int ts_on_device, uint64_t *rule_pkt_counts_out, uint64_t *any_out,
+                           uint64_t *rule_hits_out, uint32_t *window_counts_out, uint64_t *counts_out, kmpgpu_timing *t)
+{
+    const char *who = "kmpgpu_scan_thresholds";
+    if (!c) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
+    if (ts_on_device != 0 && ts_on_device != 1) return fail(KMPGPU_EINVAL, "%s: ts_on_device is %d, not 0 or 1", who, ts_on_device);
+    if (c->n_rules == 0) return fail(KMPGPU_ESTATE, "%s: no rules set", who);
+    if (c->thr.empty()) return fail(KMPGPU_ESTATE, "%s: no thresholds (kmpgpu_set_thresholds)", who);
+    if (!c->arena_seen) return fail(KMPGPU_ESTATE, "%s: no arena loaded", who);
+    if (c->fr_pending) return fail(KMPGPU_ESTATE, "%s: the context sits between kmpgpu_load_frames_begin and _finish", who);
+    const bool by_addr[2] = {!c->thr_by_track[KMPGPU_THR_BY_SRC].empty(), !c->thr_by_track[KMPGPU_THR_BY_DST].empty()};
+    const bool by_flow = !c->thr_by_track[KMPGPU_THR_BY_FLOW].empty();
+    if ((by_addr[0] || by_addr[1]) && c->n_pkts && !c->has_meta)
+        return fail(KMPGPU_ESTATE, "%s: no packet metadata (KMPGPU_OPT_KEEP_META, kmpgpu_set_meta)", who);
+    if (by_flow && !c->flows_valid) return fail(KMPGPU_ESTATE, "%s: no flows (no kmpgpu_flows_build since the arena or its metadata were set)", who);
+    if (!ts && c->n_pkts) return fail(KMPGPU_EINVAL, "%s: ts is NULL", who);
+    if (ts_on_device && ((uintptr_t)ts & 7u)) return fail(KMPGPU_EINVAL, "%s: the device timestamps are not 8-byte aligned", who);
+    MarkPass p;
+    const int rc = begin_family(c, who, KMPGPU_ALERT_RULES, rule_pkt_counts_out, counts_out, t, &p);
+    if (rc || p.empty) return rc;
+    FamilyRows f;
+    const int rr = enqueue_family(c, who, KMPGPU_ALERT_RULES, p, /* profile_reduce = */ false, &f);
+    if (rr) return rr;
+    uint32_t launches = p.launches + f.launches;
+    const uint64_t n = c->n_pkts, nr = c->n_rules, nq = c->thr.size(), P = kmp_thresholds_pad(n);
+    /* the orders in use: [0] by source, [1] by destination (this call's own, per generation of the metadata), [2] the flows' (kmpgpu_scan_flowbits') */
+    const bool ordered[3] = {c->thr_order_valid[0] && c->thr_order_gen[0] == c->meta_gen, c->thr_order_valid[1] && c->thr_order_gen[1] == c->meta_gen,
+                             c->fb_order_valid && c->fb_order_gen == c->flows_gen};
+    const bool used[3] = {by_addr[0], by_addr[1], by_flow};
+    uint8_t **order_buf[3] = {&c->d_thr_order[0], &c->d_thr_order[1], &c->d_fb_order};
+    uint64_t *order_cap[3] = {&c->thr_order_cap[0], &c->thr_order_cap[1], &c->fb_order_cap};
+    /* the workspace: T, the aggregates, T in the order of every sorted track in use, the prefix sum (before it: the addresses to sort) */
+    const uint64_t agg_bytes = (uint64_t)kmp_thresholds_agg_bytes(n);
+    uint64_t ws_bytes = 8u * P + agg_bytes + 4u * P, out_words = (nq + nr) * p.stride + nr + p.stride;
+    for (int x = 0; x < 3; x++) if (used[x] && c->thr_windowed) ws_bytes += 8u * P;
+    hipError_t e = hipSuccess;
+    for (int x = 0; x < 3 && e == hipSuccess; x++) {
+        if (!used[x] || ordered[x]) continue;
+        const uint64_t bytes = (uint64_t)kmp_flowbits_order_bytes(n, x == 2 ? c->n_flows : 1ull << 32);
+        if (!bytes) { e = hipErrorInvalidValue; break; }                          /* (rocPRIM refused the size query) */
+        if (x == 2) c->fb_order_valid = false; else c->thr_order_valid[x] = false;
+        e = grow_buffer(order_buf[x], order_cap[x], bytes, EIGHTH);
+    }
+    if (e == hipSuccess) e = grow_buffer(&c->d_thr_ws, &c->thr_ws_cap, ws_bytes, EIGHTH);
+    if (e == hipSuccess) e = grow_buffer(&c->d_thr_out, &c->thr_out_cap, out_words, EIGHTH);
+    if (e == hipSuccess && window_counts_out) e = grow_buffer(&c->d_thr_wc, &c->thr_wc_cap, nq * n, EIGHTH);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);      /* the pass is under way on the stream; the context stays usable */
+        return alloc_fail(e, "%s: the orders, the scans' workspace (%llu bytes) and the rows (%llu bytes) could not be allocated", who,
+                          (unsigned long long)ws_bytes, (unsigned long long)(out_words * 8u));
+    }
+    unsigned long long *d_T = reinterpret_cast<unsigned long long *>(c->d_thr_ws), *d_Ts[3] = {nullptr, nullptr, nullptr};
+    uint8_t *d_agg = c->d_thr_ws + 8u * P, *at = d_agg + agg_bytes;
+    for (int x = 0; x < 3; x++) if (used[x] && c->thr_windowed) { d_Ts[x] = reinterpret_cast<unsigned long long *>(at); at += 8u * P; }
+    uint32_t *d_C = reinterpret_cast<uint32_t *>(at);
+    unsigned long long *d_pass = c->d_thr_out, *d_alert = d_pass + nq * p.stride, *d_pc = d_alert + nr * p.stride, *d_any = d_pc + nr;
+    HIP_TRY(hipMemsetAsync(c->d_thr_out, 0, (size_t)out_words * sizeof(unsigned long long), c->stream));
+    hipEvent_t e1;
+    if (c->thr_windowed) {
+        if (ts_on_device) HIP_TRY(hipMemcpyAsync(d_T, ts, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
+        else HIP_TRY(upload_split(d_T, reinterpret_cast<const uint8_t *>(ts), n * sizeof(uint64_t), c->stream));
+        HIP_TRY(profile_launch(c, &e1));
+        HIP_TRY(kmp_launch_thresholds_time(d_T, n, d_agg, &launches, c->stream));
+        HIP_TRY(profile_launched(c, e1));
+    }
+    for (int x = 0; x < 3; x++) {
+        if (!used[x]) continue;
+        if (!ordered[x]) {
+            HIP_TRY(profile_launch(c, &e1));
+            if (x < 2) {
+                HIP_TRY(kmp_launch_thresholds_keys(c->d_meta, n, x == 1, d_C, c->stream));
+                launches++;
+            }
+            HIP_TRY(kmp_launch_flowbits_order(x == 2 ? c->d_flow_of : d_C, n, x == 2 ? c->n_flows : 1ull << 32, *order_buf[x], (size_t)*order_cap[x], c->stream));
+            HIP_TRY(profile_launched(c, e1));
+            if (x == 2) { c->fb_order_valid = true; c->fb_order_gen = c->flows_gen; }
+            else { c->thr_order_valid[x] = true; c->thr_order_gen[x] = c->meta_gen; }
+            launches += 2u;
+        }
+        if (d_Ts[x]) {
+            HIP_TRY(profile_launch(c, &e1));
+            HIP_TRY(kmp_launch_thresholds_tsort(d_T, *order_buf[x], n, d_Ts[x], c->stream));
+            HIP_TRY(profile_launched(c, e1));
+            launches++;
+        }
+    }
+    for (int track = 0; track < 4; track++) {
+        const uint8_t *ob = track == KMPGPU_THR_BY_RULE ? nullptr : *order_buf[track - 1];
+        const unsigned long long *Ts = track == KMPGPU_THR_BY_RULE ? (c->thr_windowed ? d_T : nullptr) : d_Ts[track - 1];
+        for (const uint32_t q : c->thr_by_track[track]) {
+            const kmpgpu_threshold &th = c->thr[q];
+            const unsigned long long *row = f.d_rows + (uint64_t)th.rule * p.stride;
+            HIP_TRY(profile_launch(c, &e1));
+            HIP_TRY(kmp_launch_thresholds_count(row, n, ob, d_C, d_agg, &launches, c->stream));
+            HIP_TRY(profile_launched(c, e1));
+            HIP_TRY(profile_launch(c, &e1));
+            HIP_TRY(kmp_launch_thresholds_pass(row, n, ob, Ts, d_C, th.type, th.count, th.window, d_pass + (uint64_t)q * p.stride,
+                                               window_counts_out ? c->d_thr_wc + (uint64_t)q * n : nullptr, c->stream));
+            HIP_TRY(profile_launched(c, e1));
+            launches++;
+        }
+    }
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_thresholds_final(f.d_rows, d_pass, p.stride, c->d_thr_table, c->n_rules, d_alert, d_pc, d_any, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    launches++;
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    if (rule_pkt_counts_out) HIP_TRY(hipMemcpyAsync(rule_pkt_counts_out, d_pc, (size_t)nr * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (any_out) HIP_TRY(hipMemcpyAsync(any_out, d_any, p.W * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, p.d_cnt, (size_t)c->n_pat * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (rule_hits_out) HIP_TRY(download_rows(c, rule_hits_out, d_alert, p.W, p.stride, nr));
+    if (window_counts_out) HIP_TRY(hipMemcpyAsync(window_counts_out, c->d_thr_wc, (size_t)(nq * n) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     return finish_marking(c, launches, t);
 }
 

@@ -176,11 +176,13 @@ def parse_regexes(path: str, n_patterns: int) -> list:
 class HostArena:
     """One contiguous payload arena + {offset, length} index, 16-byte aligned slots."""
 
-    def __init__(self, arena: Arena, owner: bool = True, meta: Optional[np.ndarray] = None, seq: Optional[np.ndarray] = None):
+    def __init__(self, arena: Arena, owner: bool = True, meta: Optional[np.ndarray] = None, seq: Optional[np.ndarray] = None,
+                 ts: Optional[np.ndarray] = None):
         self._a = arena
         self._owner = owner
         self.meta = meta           # META_DTYPE[n_pkts] where the arena was built with_meta, else None
         self.seq = seq             # uint32[n_pkts] where the arena was built with_seq, else None
+        self.ts = ts               # uint64[n_pkts], microseconds, where the arena was built with_ts, else None
         n = int(arena.n_pkts)
         self.n_pkts = n
         self.n_frames = int(arena.n_frames)
@@ -191,10 +193,12 @@ class HostArena:
         self.len = np.ctypeslib.as_array(arena.len, shape=(max(n, 1),))[:n]
 
     @classmethod
-    def from_pcap(cls, path: str, proto: str = "udp", pinned: bool = False, with_meta: bool = False, with_seq: bool = False) -> "HostArena":
+    def from_pcap(cls, path: str, proto: str = "udp", pinned: bool = False, with_meta: bool = False, with_seq: bool = False,
+                  with_ts: bool = False) -> "HostArena":
         """serial.c:115-141: read every record, extract, store (invalid frames skipped).  with_meta: the identical arena, and in
         ``.meta`` the accepted frames' header fields in payload order (kmp_arena_from_pcap_meta), as GpuMatcher.set_meta takes them.
-        with_seq: in ``.seq`` their TCP sequence numbers (kmp_arena_from_pcap_seq), as GpuMatcher.load_streams(seq=...) takes them."""
+        with_seq: in ``.seq`` their TCP sequence numbers (kmp_arena_from_pcap_seq), as GpuMatcher.load_streams(seq=...) takes them.
+        with_ts: in ``.ts`` their capture times in microseconds (kmp_arena_from_pcap_ts), as GpuMatcher.scan_thresholds takes them."""
         L = _lib.host_lib()
         a = Arena()
         err = C.create_string_buffer(_lib.KMP_PCAP_ERRBUF)
@@ -204,8 +208,11 @@ class HostArena:
             alloc = C.cast(g.kmpgpu_host_alloc, C.c_void_p)
             free = C.cast(g.kmpgpu_host_free, C.c_void_p)
         mp = C.POINTER(_lib.PktMeta)()
-        sp = _lib.u32p()
-        if with_seq:
+        sp, tp = _lib.u32p(), _lib.u64p()
+        if with_ts:
+            rc = L.kmp_arena_from_pcap_seq_ts(path.encode(), PROTO[proto], alloc, free, C.byref(a), err, C.byref(mp) if with_meta else None,
+                                              C.byref(sp) if with_seq else None, C.byref(tp))
+        elif with_seq:
             rc = L.kmp_arena_from_pcap_seq(path.encode(), PROTO[proto], alloc, free, C.byref(a), err, C.byref(mp) if with_meta else None,
                                            C.byref(sp))
         elif with_meta:
@@ -222,7 +229,11 @@ class HostArena:
         if with_seq:
             seq = np.frombuffer(C.string_at(sp, int(a.n_pkts) * 4), dtype=np.uint32).copy() if a.n_pkts else np.zeros(0, np.uint32)
             C.CDLL(None).free(C.cast(sp, C.c_void_p))
-        return cls(a, meta=meta, seq=seq)
+        ts = None
+        if with_ts:
+            ts = np.frombuffer(C.string_at(tp, int(a.n_pkts) * 8), dtype=np.uint64).copy() if a.n_pkts else np.zeros(0, np.uint64)
+            C.CDLL(None).free(C.cast(tp, C.c_void_p))
+        return cls(a, meta=meta, seq=seq, ts=ts)
 
     @classmethod
     def from_payloads(cls, payloads: Sequence[bytes]) -> "HostArena":

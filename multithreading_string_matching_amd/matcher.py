@@ -154,6 +154,7 @@ class GpuMatcher:
         self._ctx = C.c_void_p()
         gpu_check(self._g.kmpgpu_init(C.byref(self._ctx), device), "kmpgpu_init")
         self.device = device
+        self.thresholds = []                        # what set_thresholds set: scan_thresholds sizes window_counts by it
         self.patterns: List[bytes] = []
         self.rules: list = []      # (all_of, none_of) per rule, as set_rules took them
         self.windows: list = []    # (first, last) per pattern as set_windows took them (last None: unbounded), [] = none
@@ -209,6 +210,7 @@ class GpuMatcher:
         gpu_check(self._g.kmpgpu_set_rules(self._ctx, off.ctypes.data_as(u32p), terms.ctypes.data_as(u32p), len(rules)), "kmpgpu_set_rules")
         self.rules = rules
         self.flowbits, self.n_flowbits = [], 0      # the library drops the flow-bit ops with the rules they referred to
+        self.thresholds = []                        # ... and the thresholds
 
     def set_flowbits(self, ops, n_bits: Optional[int] = None) -> None:
         """Flow-bit tests and actions of the current rules (kmpgpu_set_flowbits): a sequence of (rule, "set" | "unset" | "toggle" |
@@ -230,6 +232,26 @@ class GpuMatcher:
             a.rule, a.bit, a.op, a.reserved = rule, bit, op, 0
         gpu_check(self._g.kmpgpu_set_flowbits(self._ctx, arr if rows else None, len(rows), int(n_bits) if rows else 0), "kmpgpu_set_flowbits")
         self.flowbits, self.n_flowbits = rows, int(n_bits) if rows else 0
+
+    def set_thresholds(self, thresholds) -> None:
+        """Rate thresholds of the current rules (kmpgpu_set_thresholds): a sequence of (rule, "by_rule" | "by_src" | "by_dst" | "by_flow",
+        "at_least" | "at_most" | "exactly", count, window); window is in the unit of the timestamps scan_thresholds is given, None:
+        no window (every earlier payload of the tracker counts).  A rule fires for a payload where scan_rules has it AND, for each of its
+        thresholds, the number of its hits in the payload's tracker inside the window -- the payload's own included -- compares as
+        asked.  Sliding windows over the rule's hits, not over issued alerts.  None or an empty sequence clears the thresholds."""
+        rows = []
+        for th in (thresholds or []):
+            if len(th) != 5 or th[1] not in _lib.THR_TRACKS or th[2] not in _lib.THR_TYPES:
+                raise ValueError(f"threshold {th!r}: (rule, {sorted(_lib.THR_TRACKS)}, {sorted(_lib.THR_TYPES)}, count, window) is needed")
+            rule, count, window = int(th[0]), int(th[3]), _lib.THR_NO_WINDOW if th[4] is None else int(th[4])
+            if not (0 <= rule <= 0xFFFFFFFF and 0 <= count <= 0xFFFFFFFF and 0 <= window <= _lib.THR_NO_WINDOW):
+                raise ValueError(f"threshold {th!r}: rule and count are 32-bit, window is 64-bit")
+            rows.append((rule, _lib.THR_TRACKS[th[1]], _lib.THR_TYPES[th[2]], count, window))
+        arr = (_lib.Threshold * max(len(rows), 1))()
+        for a, (rule, track, typ, count, window) in zip(arr, rows):
+            a.rule, a.track, a.type, a.count, a.window = rule, track, typ, count, window
+        gpu_check(self._g.kmpgpu_set_thresholds(self._ctx, arr if rows else None, len(rows)), "kmpgpu_set_thresholds")
+        self.thresholds = rows
 
     def set_relations(self, relations) -> None:
         """Distance / within relations between two of the current patterns (kmpgpu_set_relations): a sequence of (a, b, dmin, dmax),
@@ -672,6 +694,53 @@ class GpuMatcher:
             out["hits"] = unpack(hit_w, rows)
         if state:
             out["state"] = unpack(st_w, nb)
+        return out
+
+    def scan_thresholds(self, ts, hits: bool = True, window_counts: bool = False) -> dict:
+        """The rules with their rate thresholds (kmpgpu_scan_thresholds).  ts: one unsigned 64-bit timestamp per payload, in the unit of
+        the thresholds' windows -- a numpy array, or a contiguous torch tensor of 64-bit integers on the matcher's device, handed over as
+        it is.  A dict as scan_rules returns -- its rows are the ALERT rows --; with window_counts=True also ``window_counts``
+        (uint32[n_thr, n_pkts]): the hits in payload k's tracker inside the window that ends at k, for every k."""
+        n, rows, nq = len(self.patterns), len(self.rules), len(self.thresholds)
+        n_pkts, _ = self.arena_info()
+        on_device, keep = 0, None
+        if isinstance(ts, np.ndarray) or not hasattr(ts, "is_cuda"):
+            keep = np.asarray(ts)
+            if keep.dtype.kind not in "ui" or (keep.dtype.kind == "i" and keep.size and int(keep.min()) < 0):
+                raise ValueError(f"ts: non-negative integers are needed, not {keep.dtype}" + (" with negative values" if keep.dtype.kind == "i" else ""))
+            keep = np.ascontiguousarray(keep.astype(np.uint64, copy=False)).reshape(-1)
+            if keep.size != n_pkts:
+                raise ValueError(f"ts: {keep.size} timestamps for {n_pkts} payloads")
+            ptr = keep.ctypes.data if n_pkts else None
+        else:                                     # a torch tensor
+            if ts.dtype.itemsize != 8 or ts.dtype.is_floating_point or ts.numel() != n_pkts:
+                raise ValueError(f"ts: a tensor of {n_pkts} 64-bit integers is needed")
+            if ts.is_cuda:
+                if ts.device.index != self.device or not ts.is_contiguous():
+                    raise ValueError("ts: the tensor must be contiguous and on the matcher's device")
+                import torch
+                torch.cuda.current_stream(ts.device).synchronize()           # complete before the call (kmpgpu.h)
+                on_device, ptr = 1, (ts.data_ptr() if n_pkts else None)
+            else:
+                keep = np.ascontiguousarray(ts.numpy()).view(np.uint64).reshape(-1)
+                ptr = keep.ctypes.data if n_pkts else None
+        W = (n_pkts + 63) // 64
+        row_counts = np.zeros(max(rows, 1), dtype=np.uint64)
+        counts = np.zeros(max(n, 1), dtype=np.uint64)
+        any_w = np.zeros(max(W, 1), dtype=np.uint64)
+        hit_w = np.zeros((rows, W) if hits and rows * W else 1, dtype=np.uint64)
+        wc = np.zeros((nq, n_pkts) if window_counts and nq * n_pkts else 1, dtype=np.uint32)
+        t = Timing()
+        gpu_check(self._g.kmpgpu_scan_thresholds(self._ctx, ptr, on_device, row_counts.ctypes.data, any_w.ctypes.data,
+                                                 hit_w.ctypes.data if hits else None, wc.ctypes.data if window_counts else None,
+                                                 counts.ctypes.data, C.byref(t)), "kmpgpu_scan_thresholds")
+        out = {"rule_pkt_counts": row_counts[:rows], "counts": counts[:n], "timing": t,
+               "any": np.unpackbits(any_w[:W].view(np.uint8), bitorder="little")[:n_pkts].astype(bool)}
+        if hits:
+            bits = np.unpackbits(hit_w.reshape(rows, W).view(np.uint8), axis=1, bitorder="little") if rows * W else np.zeros((rows, 0), np.uint8)
+            out["hits"] = bits[:, :n_pkts].astype(bool)
+        if window_counts:
+            out["window_counts"] = wc.reshape(nq, n_pkts) if nq * n_pkts else np.zeros((nq, n_pkts), np.uint32)
         return out
 
     def scan_relations(self, hits: bool = False) -> dict:
