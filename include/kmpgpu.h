@@ -875,6 +875,93 @@ int  kmpgpu_load_decoded(kmpgpu_ctx *dst, kmpgpu_ctx *src, int transform, uint32
                          uint64_t *changed_out /* host [ceil(n_src / 64)] or NULL */, const void **d_changed /* or NULL */,
                          kmpgpu_decode_stats *stats /* or NULL */);
 
+/* HTTP field buffers: the method, the URI, the status, the headers or the body of the HTTP message at the start of every payload, as a
+ * packed arena that a second context owns -- the sticky buffers of signature languages (http_method, http_raw_uri, http_stat_code,
+ * http_header, http_client_body).  That context scans it with everything the library has, in src's payload numbering, so a rule that
+ * names `/admin` meets the request line only, not a Referer: header or a body.  kmpgpu_load_decoded over the RAW_URI context gives the
+ * normalised URI.  Every other call looks at a payload as one undivided byte string.
+ * Definition.  Let payload k be the bytes p[0..L), L = pkt_len[k]: the whole payload -- the locate does not look at
+ * KMPGPU_OPT_WHOLE_PAYLOAD and does not stop at 0x00.  No byte at or behind L takes part: slot padding of a borrowed arena, the next slot
+ * and the arena's end are all excluded.  Every term is "the smallest index with a local property"; there is no left-to-right state.
+ *   Start line end.  e = the smallest i with p[i] == '\n', or L if there is none.  e' = e - 1 if e >= 1 and p[e-1] == '\r', otherwise
+ *     e' = e.  The start line is p[0..e').
+ *   Tokens.  s1 = the smallest i < e' with p[i] == ' '.  s2 = the smallest i with s1 < i < e' and p[i] == ' ', or e' if there is none.
+ *   kind.  RESPONSE if e' >= 5 and p[0..5) == "HTTP/".  Otherwise REQUEST if s1 exists, 1 <= s1 <= 15, every byte of p[0..s1) is in
+ *     A..Z, and s1 + 1 < e'.  Otherwise NONE, and every field is absent.  (The bound 15 is deliberate: a payload is ruled out from its
+ *     first 16-byte unit alone.)
+ *   METHOD (REQUEST): p[0..s1).
+ *   RAW_URI (REQUEST): p[s1+1..s2).  It may be empty.
+ *   STATUS (RESPONSE, present iff s1 exists and s1 + 1 < e'): p[s1+1..s2).
+ *   HEADERS (both kinds, present iff e < L).  bl = the smallest i >= e with p[i] == '\n' and one of: i + 1 < L and p[i+1] == '\n'; or
+ *     i + 2 < L and p[i+1] == '\r' and p[i+2] == '\n'.  HEADERS is p[e+1..h1) with h1 = bl + 1, or h1 = L where there is no bl (the
+ *     segment cut the headers).  bl == e gives empty headers, which are still present.
+ *   BODY (present iff bl exists): p[b0..L), b0 = bl + 2 or bl + 3 according to which form matched.  It may be empty.
+ * A present field of length 0 and an absent field both become an empty payload of dst (one zero slot); the present bitmap tells them
+ * apart.  Limits: one message per payload, the one at its start; no chunked or compressed bodies, no header folding, no
+ * per-header buffers; methods are 1 to 15 upper-case letters; a rule cannot mix buffers inside one context -- the caller combines rows
+ * of contexts that share src's numbering.
+ *
+ * kmpgpu_http_locate decides all of this for every payload of ctx's arena in one kernel and keeps one kmpgpu_http_span per payload on
+ * the device.  Offsets count from the payload's first byte; an absent field has offset and length 0; a NONE payload's record is all
+ * zero.  tok_off / tok_len are RAW_URI for a request and STATUS for a response (KMPGPU_HTTP_HAS_TOKEN: it is present), METHOD is
+ * p[0..method_len).  *stats (may be NULL): the requests, the responses, the messages (not NONE) with a blank line, and bytes_scanned, the
+ * payload bytes the kernel looked at: min(L, 16) for a payload that its first 16 bytes rule out, otherwise min(L, 1024 (t + 1)) where
+ * step t = i / 1024 ends the search -- i = bl; or i = e where the start line makes the payload NONE after all; or i = L - 1.  The spans belong to the arena: every call that changes it drops them (the calls that drop the flows),
+ * a scan does not; with valid spans the call launches nothing and hands out the stats again.  kmpgpu_http_spans_read copies records
+ * [first, first + n) to the host (KMPGPU_ESTATE without valid spans, KMPGPU_EINVAL for a range that leaves them).  Both are synchronous
+ * on ctx's stream; KMPGPU_ESTATE between kmpgpu_load_frames_begin and _finish.  kmpgpu_last_timing: kernel_ms of the locate, launches
+ * = 1 (0 where the spans were valid); kmpgpu_profile_begin .. _end time it as one pair.
+ *
+ * kmpgpu_load_fields makes dst's arena the field `field` of every payload of src.  It runs the locate on src first where src's spans
+ * are stale (that cache is all of src that is written: its arena, index and derived state stay, and every output of it is bit-identical
+ * before and after); a ring of calls for several fields pays it once.
+ * Result without KMPGPU_FIELDS_ONLY_PRESENT: dst owns a packed arena of n_src payloads in source order, payload k the field of src's
+ * payload k (empty where absent), each in a slot of max(16, round_up(len, 16)) bytes, slots back to back from offset 0, every byte
+ * between a payload's end and its slot's end 0x00.  With it: only the payloads whose field is present, compacted in ascending order --
+ * the j-th set bit of the present bitmap is dst's payload j.  No payload held, or n_src == 0: dst is left without an arena, the return
+ * value is KMPGPU_OK and dst's earlier arena is not kept.
+ * Outputs, state, ordering and buffers are those of kmpgpu_load_decoded, word for word: present_out / *d_present as changed_out /
+ * *d_changed (the device words are what kmpgpu_load_selected(third, src, ptr, 1, ..) takes; they share the buffer of *d_changed, valid
+ * until dst's next loader call); *stats: n_payloads = the payloads dst holds, n_present = the set bits, bytes_in = the source bytes of
+ * the payloads dst holds, bytes_out = their field bytes.  The metadata goes with the payloads (a device copy, or the present payloads'
+ * records in their new order), so header predicates, kmpgpu_flows_build and flow-scope rules work in dst and give src's flow ids.  The
+ * arena is in the state kmpgpu_load_frames leaves: owned, padding clean, bitmap and plans rebuilt, the fold stale, flows, seams and
+ * spans of dst dropped.  Synchronous on dst's stream after waiting for src's; the workspace is the scratch dst keeps for
+ * kmpgpu_load_frames, so a ring of calls does not allocate per call.  The source is whatever src scans now: loaded, attached with dirty
+ * padding, extracted, selected, decoded, streams, or kept in place under KMPGPU_OPT_REPACK = 0.
+ * Errors, all refused before any launch: dst == src, a NULL context, contexts on different devices, an unknown field, an unknown flag
+ * bit: KMPGPU_EINVAL; either context between kmpgpu_load_frames_begin and _finish: KMPGPU_ESTATE; after each of these dst keeps the
+ * arena it had.  After an allocation failure dst is without an arena and both contexts stay usable.
+ * kmpgpu_last_timing(dst): kernel_ms from the first kernel to the gather's end, launches = the kernels in that span (field lengths, two
+ * scan kernels, index, gather: 5; 3 where dst ends up without a payload; one more where the locate ran).  kmpgpu_profile_begin .. _end
+ * time the span as the locate's pair (where it ran), then four pairs: lengths, scan, index, gather.
+ * Cost: the locate reads the first 16 bytes of every payload and of the messages what lies in front of their blank
+ * line in steps of 1 KiB; the load reads the spans twice and the field bytes once and writes them once. */
+#define KMPGPU_HTTP_NONE      0      /* kmpgpu_http_span.kind */
+#define KMPGPU_HTTP_REQUEST   1
+#define KMPGPU_HTTP_RESPONSE  2
+#define KMPGPU_HTTP_HAS_LF    1u     /* kmpgpu_http_span.flags: e < L (HEADERS present) */
+#define KMPGPU_HTTP_HAS_BLANK 2u     /* bl exists (BODY present) */
+#define KMPGPU_HTTP_HAS_TOKEN 4u     /* tok_off / tok_len are a present field: RAW_URI of a request, STATUS of a response */
+typedef struct kmpgpu_http_span {
+    uint8_t  kind, flags;
+    uint16_t method_len;
+    uint32_t tok_off, tok_len, hdr_off, hdr_len, body_off, body_len, reserved;
+} kmpgpu_http_span;
+typedef struct kmpgpu_http_stats { uint64_t n_requests, n_responses, n_blank, bytes_scanned; } kmpgpu_http_stats;
+int  kmpgpu_http_locate(kmpgpu_ctx *ctx, kmpgpu_http_stats *stats /* or NULL */);
+int  kmpgpu_http_spans_read(kmpgpu_ctx *ctx, kmpgpu_http_span *out, uint64_t first, uint64_t n);
+#define KMPGPU_FIELD_METHOD   1
+#define KMPGPU_FIELD_RAW_URI  2
+#define KMPGPU_FIELD_STATUS   3
+#define KMPGPU_FIELD_HEADERS  4
+#define KMPGPU_FIELD_BODY     5
+#define KMPGPU_FIELDS_ONLY_PRESENT 1u     /* flags: dst holds only the payloads whose field is present */
+typedef struct kmpgpu_fields_stats { uint64_t n_payloads, n_present, bytes_in, bytes_out; } kmpgpu_fields_stats;
+int  kmpgpu_load_fields(kmpgpu_ctx *dst, kmpgpu_ctx *src, int field, uint32_t flags,
+                        uint64_t *present_out /* host [ceil(n_src / 64)] or NULL */, const void **d_present /* or NULL */,
+                        kmpgpu_fields_stats *stats /* or NULL */);
+
 /* Flows: the payloads of the arena grouped by the 5-tuple of their metadata (kmpgpu_pkt_meta, above), on the device -- which payloads
  * belong to one connection, what each connection carried, and the hit rows of every family folded from payload space into flow space.
  * Definitions.  With M = meta[k], the two endpoints of payload k are the 48-bit integers e_src = src_ip << 16 | src_port and

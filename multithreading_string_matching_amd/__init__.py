@@ -23,6 +23,12 @@ from .matcher import (  # noqa: F401
     DECODE_ONLY_CHANGED,
     DECODE_PERCENT,
     DECODE_PLUS,
+    FIELD_BODY,
+    FIELD_HEADERS,
+    FIELD_METHOD,
+    FIELD_RAW_URI,
+    FIELD_STATUS,
+    FIELDS_ONLY_PRESENT,
     GpuComm,
     GpuMatcher,
     count_matches,

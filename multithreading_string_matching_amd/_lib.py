@@ -166,6 +166,16 @@ class DecodeStats(C.Structure):
     _fields_ = [("n_payloads", C.c_uint64), ("n_changed", C.c_uint64), ("bytes_in", C.c_uint64), ("bytes_out", C.c_uint64)]
 
 
+class HttpStats(C.Structure):
+    """kmpgpu_http_stats (include/kmpgpu.h)."""
+    _fields_ = [("n_requests", C.c_uint64), ("n_responses", C.c_uint64), ("n_blank", C.c_uint64), ("bytes_scanned", C.c_uint64)]
+
+
+class FieldsStats(C.Structure):
+    """kmpgpu_fields_stats (include/kmpgpu.h)."""
+    _fields_ = [("n_payloads", C.c_uint64), ("n_present", C.c_uint64), ("bytes_in", C.c_uint64), ("bytes_out", C.c_uint64)]
+
+
 class FlowbitOp(C.Structure):
     """kmpgpu_flowbit_op (include/kmpgpu.h)."""
     _fields_ = [("rule", C.c_uint32), ("bit", C.c_uint32), ("op", C.c_uint32), ("reserved", C.c_uint32)]
@@ -320,6 +330,9 @@ GPU_API = {
     "kmpgpu_alerts_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "kmpgpu_load_selected": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, u64p]),
     "kmpgpu_load_decoded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(DecodeStats)]),
+    "kmpgpu_http_locate": (C.c_int, [C.c_void_p, C.POINTER(HttpStats)]),
+    "kmpgpu_http_spans_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "kmpgpu_load_fields": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(FieldsStats)]),
     "kmpgpu_flows_build": (C.c_int, [C.c_void_p, C.c_uint32, u64p, C.POINTER(Timing)]),
     "kmpgpu_flows_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "kmpgpu_flow_ids_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),

@@ -102,6 +102,16 @@
  * stderr and exit 1, before any GPU work: any other value; the variable together with KMPGPU_OFFSETS_FILE (offsets in decoded payloads
  * are not mapped back), KMPGPU_EXPORT_FILE or KMPGPU_FLOW_SEAMS; the variable with none of the three row outputs.
  *
+ * KMPGPU_HTTP_FIELD=method|raw_uri|uri|status|headers|body, together with at least one of KMPGPU_PACKETS_FILE, KMPGPU_ALERTS_FILE and
+ * KMPGPU_FLOW_ALERTS_FILE: these row outputs are decided on that field of the HTTP message at the start of every payload
+ * (kmpgpu_load_fields; the definition: kmpgpu.h), so that a rule that names `/admin` meets the request line and not a Referer: header or a
+ * body.  Per shard a second context on the shard's device gets the same tables as the shard's (upload_tables) and the field buffer of the
+ * shard's arena, every payload (an absent field is an empty payload), so the payload numbers are the capture's; `uri` is raw_uri
+ * percent-decoded (kmpgpu_load_decoded) through a third context.  stdout and KMPGPU_FLOWS_FILE are what they are without the variable.
+ * Refused with a message on stderr and exit 1, before any GPU work: any other value; the variable together with KMPGPU_DECODE,
+ * KMPGPU_OFFSETS_FILE, KMPGPU_EXPORT_FILE, KMPGPU_FLOW_SEAMS, KMPGPU_FLOW_STREAMS, KMPGPU_FLOWBITS_FILE or KMPGPU_THRESHOLDS_FILE; the
+ * variable with none of the three row outputs.
+ *
  * KMPGPU_FLOW_STREAMS=<depth>, together with KMPGPU_FLOW_ALERTS_FILE: the flow alerts are decided on the reassembled streams.  A second
  * context on the shard's device gets the same tables as the shard's (upload_tables; the windows too: on a stream they mean "offset in the
  * connection's direction") and the payloads of every flow direction concatenated in capture order and cut to <depth> bytes
@@ -153,6 +163,7 @@
 #include "kmphost.h"
 #include "kmp_cli_common.h"
 #include "kmp_cli_decode.h"
+#include "kmp_cli_fields.h"
 #include "kmp_cli_streams.h"
 #include "kmp_cli_streams_order.h"
 
@@ -179,6 +190,7 @@ typedef struct cli_options {
     int flows_directed;                     /* KMPGPU_FLOWS_DIRECTED */
     uint32_t flow_seams;                    /* KMPGPU_FLOW_SEAMS: the reach, 0 without the variable */
     int decode;                             /* KMPGPU_DECODE: KMP_CLI_DECODE_* */
+    int http_field;                         /* KMPGPU_HTTP_FIELD: KMP_CLI_FIELD_* */
     uint32_t flow_streams;                  /* KMPGPU_FLOW_STREAMS: the depth, 0 without the variable */
     const char *streams_path;               /* KMPGPU_STREAMS_FILE */
     int streams_order;                      /* KMPGPU_FLOW_STREAMS_ORDER: KMP_CLI_STREAMS_ORDER_* */
@@ -229,7 +241,7 @@ typedef struct cli_run {
     int ndev, shards, reduce_rccl, rules_set;
     shard_job *job;
     kmpgpu_ctx **ctxs;                      /* ctxs[r] = job[r].ctx */
-    kmpgpu_ctx **rows;                      /* rows[r]: the context the row outputs of shard r come from -- ctxs[r], or with KMPGPU_DECODE its decoding */
+    kmpgpu_ctx **rows;                      /* rows[r]: the context the row outputs of shard r come from -- ctxs[r], or with KMPGPU_DECODE its decoding, or with KMPGPU_HTTP_FIELD its field buffer */
     kmpgpu_comm *comm;
     uint64_t *own, *counts;                 /* own[r * n_patterns + i]: shard r's count of pattern i; counts[i]: the total */
     double kernel_ms;
@@ -523,6 +535,31 @@ static void load_options(int argc, char *argv[], cli_options *opt)
             exit(1);
         }
     }
+    /* the field buffer: it changes what the row outputs hold and nothing else */
+    const char *field_env = env_path("KMPGPU_HTTP_FIELD");
+    if (field_env) {
+        static const char *const not_with[][2] = {
+            {"KMPGPU_DECODE", "uri is the percent-decoded field, every other field is taken as captured"},
+            {"KMPGPU_OFFSETS_FILE", "offsets in a field are not mapped back to the capture's"},
+            {"KMPGPU_EXPORT_FILE", "the export selects and writes the payloads as captured"},
+            {"KMPGPU_FLOW_SEAMS", "seams of fields do not exist"},
+            {"KMPGPU_FLOW_STREAMS", "fields of streams are not wired in this program"},
+            {"KMPGPU_FLOWBITS_FILE", "flow bits over a field buffer are not wired in this program"},
+            {"KMPGPU_THRESHOLDS_FILE", "a field buffer keeps no timestamps in this program"}};
+        if (!kmp_cli_parse_field(field_env, &opt->http_field)) {
+            fprintf(stderr, "KMPGPU_HTTP_FIELD is \"%s\": method, raw_uri, uri, status, headers or body is needed\n", field_env);
+            exit(1);
+        }
+        for (size_t i = 0; i < sizeof not_with / sizeof not_with[0]; i++)
+            if (env_path(not_with[i][0])) {
+                fprintf(stderr, "KMPGPU_HTTP_FIELD does not go together with %s: %s\n", not_with[i][0], not_with[i][1]);
+                exit(1);
+            }
+        if (!opt->packets_path && !opt->alerts_path && !opt->flow_alerts_path) {
+            fprintf(stderr, "KMPGPU_HTTP_FIELD has no effect without KMPGPU_PACKETS_FILE, KMPGPU_ALERTS_FILE or KMPGPU_FLOW_ALERTS_FILE\n");
+            exit(1);
+        }
+    }
     opt->want_meta = opt->headers.n || opt->flows_path || opt->flow_alerts_path || opt->flowbits.n || opt->thresholds_by_flow || opt->thresholds_by_addr;
     /* the export starts as a capture without frames: a path that cannot be written ends the run here */
     if (opt->export_path && kmp_write_udp_pcap_part(opt->export_path, 0, NULL, NULL, NULL, 0, 0)) {
@@ -706,6 +743,30 @@ static void decode_shards(const cli_options *opt, cli_run *run)
         const char *failed = upload_tables(d, opt);
         if (failed) die_gpu(failed);
         if (kmpgpu_load_decoded(d, run->ctxs[r], KMPGPU_DECODE_PERCENT, flags, NULL, NULL, NULL)) die_gpu("kmpgpu_load_decoded");
+        run->rows[r] = d;
+    }
+}
+
+/* KMPGPU_HTTP_FIELD: next to every shard a context with the same tables that holds that field of every payload of the shard (an absent
+ * field: an empty payload), so that payload numbers stay the capture's; the row outputs come from it.  uri: the raw URI goes through a
+ * context of its own, which needs no tables, and its percent-decoding is what is scanned. */
+static void field_shards(const cli_options *opt, cli_run *run)
+{
+    _Static_assert(KMP_CLI_FIELD_METHOD == KMPGPU_FIELD_METHOD && KMP_CLI_FIELD_RAW_URI == KMPGPU_FIELD_RAW_URI && KMP_CLI_FIELD_STATUS == KMPGPU_FIELD_STATUS &&
+                   KMP_CLI_FIELD_HEADERS == KMPGPU_FIELD_HEADERS && KMP_CLI_FIELD_BODY == KMPGPU_FIELD_BODY, "KMP_CLI_FIELD_* are the values of KMPGPU_FIELD_*");
+    const int uri = opt->http_field == KMP_CLI_FIELD_URI;
+    const int field = uri ? KMPGPU_FIELD_RAW_URI : opt->http_field;      /* (KMP_CLI_FIELD_* are the values of KMPGPU_FIELD_*) */
+    for (int r = 0; r < run->shards; r++) {
+        kmpgpu_ctx *d = NULL, *raw = NULL;
+        if (kmpgpu_init(&d, run->job[r].device)) die_gpu("kmpgpu_init");
+        const char *failed = upload_tables(d, opt);
+        if (failed) die_gpu(failed);
+        if (uri) {
+            if (kmpgpu_init(&raw, run->job[r].device)) die_gpu("kmpgpu_init");
+            if (kmpgpu_load_fields(raw, run->ctxs[r], field, 0u, NULL, NULL, NULL)) die_gpu("kmpgpu_load_fields");
+            if (kmpgpu_load_decoded(d, raw, KMPGPU_DECODE_PERCENT, 0u, NULL, NULL, NULL)) die_gpu("kmpgpu_load_decoded");
+            kmpgpu_destroy(raw);
+        } else if (kmpgpu_load_fields(d, run->ctxs[r], field, 0u, NULL, NULL, NULL)) die_gpu("kmpgpu_load_fields");
         run->rows[r] = d;
     }
 }
@@ -988,6 +1049,7 @@ int main(int argc, char *argv[])
         run.kernel_ms = (now_s() - t_scan0) * 1e3;                          /* wall time of the concurrent passes + reduce (mpi_dumping.c:206 MPI_MAX) */
 
         if (opt.decode) decode_shards(&opt, &run);
+        if (opt.http_field) field_shards(&opt, &run);
         if (opt.offsets_path) write_offsets(opt.offsets_path, &run, n);
         if (opt.packets_path) write_alerts(opt.packets_path, &opt, &run, KMPGPU_ALERT_PATTERNS);
         if (opt.alerts_path) write_alerts(opt.alerts_path, &opt, &run, KMPGPU_ALERT_RULES);

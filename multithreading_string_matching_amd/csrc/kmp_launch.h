@@ -1,5 +1,5 @@
 /* kmp_launch.h -- launch entry points of kmp_scan_*.hip / kmp_prep.hip / kmp_fold.hip / kmp_marks.hip / kmp_rules.hip / kmp_relations.hip /
- * kmp_chains.hip / kmp_headers.hip / kmp_bytetests.hip / kmp_regex.hip / kmp_select.hip / kmp_decode.hip / kmp_alerts.hip / kmp_flows.hip / kmp_seams.hip / kmp_streams.hip / kmp_streams_seq.hip / kmp_flowbits.hip / kmp_thresholds.hip, used
+ * kmp_chains.hip / kmp_headers.hip / kmp_bytetests.hip / kmp_regex.hip / kmp_select.hip / kmp_decode.hip / kmp_fields.hip / kmp_alerts.hip / kmp_flows.hip / kmp_seams.hip / kmp_streams.hip / kmp_streams_seq.hip / kmp_flowbits.hip / kmp_thresholds.hip, used
  * by the C-ABI layer (kmpgpu.hip), which alone decides what is launched; the tables kmp_launch_scan_multi takes come from kmp_tables.h. */
 #ifndef KMP_LAUNCH_H
 #define KMP_LAUNCH_H
@@ -201,6 +201,24 @@ hipError_t kmp_launch_decode_index(const uint64_t *src_off, const uint32_t *src_
                                    uint32_t *pkt_len, void *recs, hipStream_t st);
 hipError_t kmp_launch_decode_write(const uint8_t *src_arena, const uint64_t *pkt_off, const void *recs, uint64_t n_dst, uint64_t bytes_in,
                                    uint64_t total_bytes, bool plus, uint8_t *arena, bool nontemporal, hipStream_t st);
+/* kmp_fields.hip (kmpgpu_http_locate, kmpgpu_load_fields): the HTTP field buffers (the definition: kmpgpu.h).  _http_locate (1 kernel)
+ * writes spans[n] (kmpgpu_http_span, 32 bytes each, 16-byte aligned) and adds to stats[4] = {requests, responses, messages with a blank
+ * line, bytes scanned}, which the caller zeroes.  ws: kmp_extract_ws_bytes(n) bytes, kept from _lengths to _index.  _lengths (1 kernel)
+ * leaves per payload the length of `field` (KMPGPU_FIELD_*), or 0xFFFFFFFF for an absent one with only_present, writes every word of
+ * present[ceil(n / 64)] (bits at n and above 0) and adds to stats[3] = {source bytes of the payloads kept, payloads with the field, field
+ * bytes}, which the caller zeroes.  _scan (2 kernels) leaves totals[0] = bytes of the packed result, totals[1] = its payloads n_dst.  _index
+ * (1 kernel) writes pkt_off[n_dst], pkt_len[n_dst] and the 16-byte records recs[n_dst]; _gather (1 kernel) arena[0, total_bytes): every slot
+ * whole, 0x00 behind its payload's end.  The source's slots are 16-byte aligned (the layout contract of kmpgpu.h); of src_arena only
+ * aligned 16-byte units that hold a byte of a payload are read, and nothing at or behind a payload's end takes part. */
+hipError_t kmp_launch_http_locate(const uint8_t *src_arena, const uint64_t *src_off, const uint32_t *src_len, uint64_t n, void *spans,
+                                  unsigned long long *stats, hipStream_t st);
+hipError_t kmp_launch_fields_lengths(const void *spans, const uint32_t *src_len, uint64_t n, int field, bool only_present, uint8_t *ws,
+                                     unsigned long long *present, unsigned long long *stats, hipStream_t st);
+hipError_t kmp_launch_fields_scan(uint64_t n, uint8_t *ws, unsigned long long *totals, hipStream_t st);
+hipError_t kmp_launch_fields_index(const void *spans, const uint64_t *src_off, uint64_t n, int field, uint8_t *ws, uint64_t n_dst,
+                                   uint64_t *pkt_off, uint32_t *pkt_len, void *recs, hipStream_t st);
+hipError_t kmp_launch_fields_gather(const uint8_t *src_arena, const uint64_t *pkt_off, const void *recs, uint64_t n_dst, uint64_t total_bytes,
+                                    uint8_t *arena, bool nontemporal, hipStream_t st);
 /* kmp_alerts.hip (kmpgpu_scan_alerts): the set bits of rows[n_rows][stride] (stride even, 16-byte aligned, every word of a row readable,
  * the bits of index n_pkts and above not looked at; 16 * n_rows <= 0xFFFFFFFE) as 16-byte records {payload (64 bits), row, 0}, sorted by
  * payload, then row.  any[ceil(n_pkts / 64)]: the OR over the rows, complete before the count; a column word whose any word is 0 is not read.

@@ -34,10 +34,11 @@
 #include "kmpgpu.h"
 #include "kmp_device.h"
 #include "kmp_launch.h"
+#include "kmp_piece_dev.h"
 
 namespace {
 
-typedef uint32_t sseq_u32x4 __attribute__((ext_vector_type(4)));
+typedef kmp_piece::u32x4 sseq_u32x4;
 
 constexpr uint32_t SSEQ_UNROLL = 1;               /* as kmp_streams.hip: one unit per lane in flight, parallelism from wavefronts */
 constexpr uint32_t SSEQ_INDEX_BLOCKS = 1024;      /* grid cap of the per-payload and per-stream kernels: rounds past 262 144 elements */
@@ -374,58 +375,10 @@ kmp_sseq_index_kernel(const uint64_t *__restrict__ key2, const uint32_t *__restr
     }
 }
 
-template <bool NT>
-__device__ __forceinline__ sseq_u32x4 load_unit(const uint8_t *p)
-{
-    const sseq_u32x4 *q = reinterpret_cast<const sseq_u32x4 *>(p);
-    return NT ? __builtin_nontemporal_load(q) : *q;
-}
-template <bool NT>
-__device__ __forceinline__ void store_unit(uint8_t *p, sseq_u32x4 v)
-{
-    sseq_u32x4 *q = reinterpret_cast<sseq_u32x4 *>(p);
-    if (NT) __builtin_nontemporal_store(v, q); else *q = v;
-}
-
-/* 0xFF in the bytes below x of dword d of a unit (byte positions 4 d .. 4 d + 3), 0 <= x <= 16 */
-__device__ __forceinline__ uint32_t below_mask(uint32_t x, uint32_t d)
-{
-    const uint32_t b = 4u * d;
-    return (x >= b + 4u) ? 0xFFFFFFFFu : (x <= b) ? 0u : ((1u << (8u * (x - b))) - 1u);
-}
-
-/* fetch_piece of kmp_streams.hip (which keeps its own: that file's code object does not change): the 16 bytes [start, start + 16) of a
- * member, in coordinates relative to `base` (16-byte aligned), of which [lo, hi) are wanted (0 <= lo <= hi); start >= -15.  Bytes outside
- * [lo, hi) come out 0x00.  Only the aligned units that hold a byte of [lo, hi) are loaded: with lo = skip the bytes in front of the kept
- * suffix are neither written nor, where they fill a unit of their own, read. */
-template <bool NT>
-__device__ __forceinline__ sseq_u32x4 fetch_piece(const uint8_t *base, int32_t start, int32_t lo, int32_t hi)
-{
-    const int32_t a0 = start & ~15;                                  /* (arithmetic: -16 for a negative start) */
-    const uint32_t s = (uint32_t)(start - a0);
-    const int32_t klo = min(max(lo - start, 0), 16), khi = min(max(hi - start, 0), 16);
-    sseq_u32x4 r = (sseq_u32x4)(0u);
-    if (klo >= khi) return r;
-    sseq_u32x4 u0 = (sseq_u32x4)(0u), u1 = (sseq_u32x4)(0u);
-    if (start + klo < a0 + 16) u0 = load_unit<NT>(base + a0);
-    if (start + khi > a0 + 16) u1 = load_unit<NT>(base + a0 + 16);
-    uint32_t w[9] = {u0.x, u0.y, u0.z, u0.w, u1.x, u1.y, u1.z, u1.w, 0u};
-    /* by whole dwords, then by bytes */
-    if (s & 8u) {
-#pragma unroll
-        for (uint32_t i = 0; i < 7u; ++i) w[i] = w[i + 2u];
-    }
-    if (s & 4u) {
-#pragma unroll
-        for (uint32_t i = 0; i < 6u; ++i) w[i] = w[i + 1u];
-    }
-    uint32_t o[4];
-#pragma unroll
-    for (uint32_t d = 0; d < 4u; ++d)
-        o[d] = __builtin_amdgcn_alignbyte(w[d + 1u], w[d], s & 3u) & below_mask((uint32_t)khi, d) & ~below_mask((uint32_t)klo, d);
-    r.x = o[0]; r.y = o[1]; r.z = o[2]; r.w = o[3];
-    return r;
-}
+/* load_unit / store_unit / fetch_piece: kmp_piece_dev.h, which the gathers of the derived arenas share */
+using kmp_piece::fetch_piece;
+using kmp_piece::load_unit;
+using kmp_piece::store_unit;
 
 /* The last piece q >= p with piece_dst[q] <= d, given piece_dst[p] <= d: galloping, then halving.  0-byte pieces at or before d -- members
  * behind the cut, and here fully covered retransmissions in the middle of a stream -- are passed over by the search, not walked. */

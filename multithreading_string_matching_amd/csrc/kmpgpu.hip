@@ -229,6 +229,12 @@ struct kmpgpu_ctx {
     /* kmpgpu_load_decoded as dst: the changed bitmap [ceil(n_src / 64)] and, behind it, the four words its kernels count in */
     unsigned long long *d_dec_changed = nullptr;
     uint64_t            dec_changed_cap = 0;          /* words */
+    /* kmpgpu_http_locate: one kmpgpu_http_span (two 16-byte units) per payload, the four words the kernel counts in behind them, and those
+     * words on the host.  spans_valid: they describe the arena that is attached now (drop_spans) */
+    uint4              *d_spans = nullptr;
+    uint64_t            spans_cap = 0;                /* 16-byte units */
+    uint64_t            http_stats[4] = {0, 0, 0, 0};
+    bool                spans_valid = false;
     int64_t             flow_slots = 0;               /* KMPGPU_OPT_FLOW_SLOTS */
     /* which build of the flows the context holds: kmpgpu_flows_build and drop_flows start a new generation, and id tells one context from
      * every other the process has made (a seam list names the context and the generation it was built from) */
@@ -507,6 +513,9 @@ void drop_flows(kmpgpu_ctx *c, bool rebuild = false)
     if (!rebuild) c->meta_gen++;                   /* the arena or its metadata change: the thresholds' address orders are none of the next one's */
 }
 
+/* the HTTP spans go with the arena whose payloads they describe; their buffer is kept for the next locate */
+void drop_spans(kmpgpu_ctx *c) { c->spans_valid = false; }
+
 /* the seam list goes with the arena it describes; its buffers are kept for the next build */
 void drop_seams(kmpgpu_ctx *c)
 {
@@ -578,6 +587,7 @@ void release_arena(kmpgpu_ctx *c, bool keep_buffers = false)
     c->has_meta = false;                              /* the metadata described its payloads (the buffer is kept too) */
     drop_flows(c);                                    /* ... and the flows grouped them */
     drop_seams(c);                                    /* ... and the seam list said which of src's payloads they join */
+    drop_spans(c);                                    /* ... and the HTTP spans where their fields lie */
     drop_streams(c);                                  /* ... and the stream records which of them each stream is made of */
 }
 
@@ -632,6 +642,7 @@ void release_pass_buffers(kmpgpu_ctx *c)
     free_buffer(&c->d_flow_table, &c->flow_table_cap); free_buffer(&c->d_flow_first, &c->flow_first_cap); free_buffer(&c->d_flow_of, &c->flow_of_cap);
     free_buffer(&c->d_flow_recs, &c->flow_recs_cap); free_buffer(&c->d_flow_fold, &c->flow_fold_cap); free_buffer(&c->d_flow_sel, &c->flow_sel_cap);
     free_buffer(&c->d_dec_changed, &c->dec_changed_cap);
+    free_buffer(&c->d_spans, &c->spans_cap); drop_spans(c);
     drop_flows(c);
     free_buffer(&c->d_seams, &c->seams_cap); free_buffer(&c->d_seam_flow, &c->seam_flow_cap); free_buffer(&c->d_seam_sort, &c->seam_sort_cap);
     drop_seams(c);
@@ -1669,6 +1680,171 @@ int kmpgpu_load_decoded(kmpgpu_ctx *dst, kmpgpu_ctx *src, int transform, uint32_
     IndexFacts f;
     int rc = validate_index(c, who, c->owned_off, c->owned_len, n_pkts, arena_bytes, &f);
     /* kmp_decode_write_kernel writes every slot whole: payload, then 0x00 up to the slot's end */
+    if (!rc) rc = install_arena(c, c->owned_arena, c->owned_off, c->owned_len, arena_bytes, n_pkts, f, /* wrote_padding = */ true);
+    if (rc) { release_arena(c, true); return rc; }
+    c->has_meta = src->has_meta;
+    return done(5);
+}
+
+/* The spans of src's arena, made on the stream of `on` (src itself, or the dst of kmpgpu_load_fields, which has waited for src's stream)
+ * where they are stale; *launched: the kernel ran.  The caller synchronises the stream before it reads src->http_stats. */
+static int locate_spans(kmpgpu_ctx *src, kmpgpu_ctx *on, const char *who, bool *launched)
+{
+    *launched = false;
+    if (src->spans_valid) return KMPGPU_OK;
+    const uint64_t n = src->n_pkts;
+    memset(src->http_stats, 0, sizeof src->http_stats);
+    if (n == 0) { src->spans_valid = true; return KMPGPU_OK; }
+    const hipError_t e = grow_buffer(&src->d_spans, &src->spans_cap, 2 * n + 2, EIGHTH);       /* 32 bytes per payload, 4 words of totals */
+    if (e != hipSuccess) return alloc_fail(e, "%s: the spans (%llu payloads) could not be allocated", who, (unsigned long long)n);
+    unsigned long long *d_stats = reinterpret_cast<unsigned long long *>(src->d_spans + 2 * n);
+    HIP_TRY(hipMemsetAsync(d_stats, 0, 4 * sizeof(unsigned long long), on->stream));
+    hipEvent_t e1;
+    HIP_TRY(profile_launch(on, &e1));
+    HIP_TRY(kmp_launch_http_locate(src->d_arena, src->d_off, src->d_len, n, src->d_spans, d_stats, on->stream));
+    HIP_TRY(profile_launched(on, e1));
+    HIP_TRY(hipMemcpyAsync(on->h_small + 8, d_stats, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, on->stream));         /* (pinned: no staging) */
+    *launched = true;
+    return KMPGPU_OK;
+}
+/* ... and after that synchronisation */
+static void located_spans(kmpgpu_ctx *src, kmpgpu_ctx *on)
+{
+    memcpy(src->http_stats, on->h_small + 8, sizeof src->http_stats);
+    src->spans_valid = true;
+}
+
+int kmpgpu_http_locate(kmpgpu_ctx *c, kmpgpu_http_stats *stats)
+{
+    const char *who = "kmpgpu_http_locate";
+    if (stats) *stats = kmpgpu_http_stats{};
+    if (!c) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
+    if (c->fr_pending) return fail(KMPGPU_ESTATE, "%s: the context sits between kmpgpu_load_frames_begin and _finish", who);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->last = kmpgpu_timing{};
+    bool launched = false;
+    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+    const int rc = locate_spans(c, c, who, &launched);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    HIP_TRY(hipEventSynchronize(c->ev[3]));
+    if (launched) {
+        located_spans(c, c);
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
+        c->last.kernel_ms = ms; c->last.launches = 1;
+    }
+    if (stats) { stats->n_requests = c->http_stats[0]; stats->n_responses = c->http_stats[1]; stats->n_blank = c->http_stats[2]; stats->bytes_scanned = c->http_stats[3]; }
+    return KMPGPU_OK;
+}
+
+int kmpgpu_http_spans_read(kmpgpu_ctx *c, kmpgpu_http_span *out, uint64_t first, uint64_t n)
+{
+    const char *who = "kmpgpu_http_spans_read";
+    static_assert(sizeof(kmpgpu_http_span) == 32, "kmpgpu_http_span is two 16-byte units");
+    if (!c) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
+    if (!c->spans_valid) return fail(KMPGPU_ESTATE, "%s: no spans (no kmpgpu_http_locate since the arena was set)", who);
+    if (first > c->n_pkts || n > c->n_pkts - first)
+        return fail(KMPGPU_EINVAL, "%s: records [%llu, +%llu) leave the %llu there are", who, (unsigned long long)first, (unsigned long long)n,
+                    (unsigned long long)c->n_pkts);
+    if (n == 0) return KMPGPU_OK;
+    if (!out) return fail(KMPGPU_EINVAL, "%s: out is NULL", who);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(out, c->d_spans + 2 * first, (size_t)n * sizeof(kmpgpu_http_span), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return KMPGPU_OK;
+}
+
+int kmpgpu_load_fields(kmpgpu_ctx *dst, kmpgpu_ctx *src, int field, uint32_t flags, uint64_t *present_out, const void **d_present,
+                       kmpgpu_fields_stats *stats)
+{
+    const char *who = "kmpgpu_load_fields";
+    if (d_present) *d_present = nullptr;
+    if (stats) *stats = kmpgpu_fields_stats{};
+    if (!dst || !src) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
+    if (dst == src) return fail(KMPGPU_EINVAL, "%s: dst and src are the same context (a context holds one arena)", who);
+    if (field < KMPGPU_FIELD_METHOD || field > KMPGPU_FIELD_BODY) return fail(KMPGPU_EINVAL, "%s: field %d is none of KMPGPU_FIELD_*", who, field);
+    if (flags & ~KMPGPU_FIELDS_ONLY_PRESENT) return fail(KMPGPU_EINVAL, "%s: unknown flag bits 0x%x", who, flags);
+    if (dst->device != src->device)
+        return fail(KMPGPU_EINVAL, "%s: the contexts sit on devices %d and %d (field buffers across devices do not exist)", who, dst->device, src->device);
+    if (dst->fr_pending || src->fr_pending) return fail(KMPGPU_ESTATE, "%s: %s sits between kmpgpu_load_frames_begin and _finish", who, dst->fr_pending ? "dst" : "src");
+    const bool only_present = (flags & KMPGPU_FIELDS_ONLY_PRESENT) != 0;
+    HIP_TRY(hipSetDevice(dst->device));
+    HIP_TRY(hipStreamSynchronize(dst->stream));           /* the passes over the arena that is about to be replaced */
+    HIP_TRY(hipStreamSynchronize(src->stream));           /* whatever src's stream still does with its arena */
+    kmpgpu_ctx *c = dst;
+    c->last = kmpgpu_timing{};
+    const uint64_t n = src->n_pkts;
+    if (n == 0) { release_arena(c, /* keep_buffers = */ true); return KMPGPU_OK; }
+
+    /* the scratch of kmpgpu_load_frames (fr_ws the scan, fr_src the gather's records) and the bitmap's buffer of kmpgpu_load_decoded */
+    const uint64_t words = (n + 63) / 64;
+    HIP_TRY(grow_buffer(&c->fr_ws, &c->fr_ws_cap, (uint64_t)kmp_extract_ws_bytes(n), EIGHTH));
+    if (!c->fr_tot) HIP_TRY(hipMalloc(&c->fr_tot, 2 * sizeof(unsigned long long)));
+    HIP_TRY(grow_buffer(&c->d_dec_changed, &c->dec_changed_cap, words + 4, EIGHTH));
+    unsigned long long *d_stats = c->d_dec_changed + words;
+    HIP_TRY(hipMemsetAsync(d_stats, 0, 4 * sizeof(unsigned long long), c->stream));
+    hipEvent_t e1;
+    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+    bool located = false;
+    int rc = locate_spans(src, c, who, &located);         /* (one more launch, where the spans are stale) */
+    if (rc) return rc;
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_fields_lengths(src->d_spans, src->d_len, n, field, only_present, c->fr_ws, c->d_dec_changed, d_stats, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_fields_scan(n, c->fr_ws, c->fr_tot, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(hipMemcpyAsync(c->h_small, c->fr_tot, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));         /* (pinned: no staging) */
+    HIP_TRY(hipMemcpyAsync(c->h_small + 2, d_stats, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    if (present_out) HIP_TRY(hipMemcpyAsync(present_out, c->d_dec_changed, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (located) located_spans(src, c);
+    unsigned long long tot[6] = {0, 0, 0, 0, 0, 0};       /* packed bytes, payloads; source bytes, payloads with the field, field bytes */
+    memcpy(tot, c->h_small, sizeof tot);
+    const uint64_t n_pkts = tot[1], arena_bytes = tot[0] + 64;
+    auto done = [&](uint32_t launches) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
+        c->last.kernel_ms = ms; c->last.launches = launches + (located ? 1u : 0u);
+        if (d_present) *d_present = c->d_dec_changed;
+        if (stats) { stats->n_payloads = n_pkts; stats->n_present = tot[3]; stats->bytes_in = tot[2]; stats->bytes_out = tot[4]; }
+        return (int)KMPGPU_OK;
+    };
+    /* from here on dst's earlier arena is gone, whatever happens */
+    release_arena(c, /* keep_buffers = */ true);
+    if (n_pkts == 0) {
+        HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+        HIP_TRY(hipEventSynchronize(c->ev[3]));
+        return done(3);
+    }
+    hipError_t e = ensure_owned_arena(c, arena_bytes, n_pkts, EIGHTH);       /* (on failure dst is empty and usable) */
+    if (e != hipSuccess)
+        return alloc_fail(e, "%s: an arena of %llu bytes / %llu payloads could not be allocated", who,
+                          (unsigned long long)(arena_bytes + arena_bytes / 8), (unsigned long long)(n_pkts + n_pkts / 8));
+    e = grow_buffer(&c->fr_src, &c->fr_src_cap, 2 * n_pkts, EIGHTH);      /* 16 bytes per payload of dst */
+    if (e != hipSuccess) return alloc_fail(e, "%s: the gather's records (%llu payloads) could not be allocated", who, (unsigned long long)n_pkts);
+    if (src->has_meta) {
+        e = grow_buffer(&c->d_meta, &c->meta_cap, n_pkts, EIGHTH);
+        if (e != hipSuccess) return alloc_fail(e, "%s: the metadata (%llu payloads) could not be allocated", who, (unsigned long long)n_pkts);
+    }
+    HIP_TRY(hipMemsetAsync(c->owned_arena + tot[0], 0, 64, c->stream));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_fields_index(src->d_spans, src->d_off, n, field, c->fr_ws, n_pkts, c->owned_off, c->owned_len, c->fr_src, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(profile_launch(c, &e1));
+    HIP_TRY(kmp_launch_fields_gather(src->d_arena, c->owned_off, c->fr_src, n_pkts, tot[0], c->owned_arena, c->nontemporal != 0, c->stream));
+    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    /* src has metadata: the records go with the payloads -- in their new order, or all of them as they are */
+    if (src->has_meta) {
+        if (only_present) HIP_TRY(kmp_launch_meta_select(src->d_meta, n, c->fr_ws, c->d_meta, c->stream));
+        else HIP_TRY(hipMemcpyAsync(c->d_meta, src->d_meta, n * sizeof(uint4), hipMemcpyDeviceToDevice, c->stream));
+    }
+    IndexFacts f;
+    rc = validate_index(c, who, c->owned_off, c->owned_len, n_pkts, arena_bytes, &f);
+    /* kmp_fields_gather_kernel writes every slot whole: payload, then 0x00 up to the slot's end */
     if (!rc) rc = install_arena(c, c->owned_arena, c->owned_off, c->owned_len, arena_bytes, n_pkts, f, /* wrote_padding = */ true);
     if (rc) { release_arena(c, true); return rc; }
     c->has_meta = src->has_meta;

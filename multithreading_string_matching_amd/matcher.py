@@ -37,6 +37,13 @@ FLOW_DTYPE = np.dtype([("first_packet", "<u8"), ("last_packet", "<u8"), ("n_pack
                        ("first", META_DTYPE)])     # kmpgpu_flow, 48 bytes
 DECODE_PERCENT = 1      # KMPGPU_DECODE_PERCENT: the transform of load_decoded
 DECODE_PLUS, DECODE_ONLY_CHANGED = 1, 2     # KMPGPU_DECODE_*: its flags
+FIELD_METHOD, FIELD_RAW_URI, FIELD_STATUS, FIELD_HEADERS, FIELD_BODY = 1, 2, 3, 4, 5       # KMPGPU_FIELD_*: the field of load_fields
+FIELDS_ONLY_PRESENT = 1                     # KMPGPU_FIELDS_ONLY_PRESENT: its flag
+FIELD_NAMES = {"method": FIELD_METHOD, "raw_uri": FIELD_RAW_URI, "status": FIELD_STATUS, "headers": FIELD_HEADERS, "body": FIELD_BODY}
+# kmpgpu_http_span (include/kmpgpu.h)
+HTTP_SPAN_DTYPE = np.dtype([("kind", np.uint8), ("flags", np.uint8), ("method_len", np.uint16), ("tok_off", np.uint32), ("tok_len", np.uint32),
+                            ("hdr_off", np.uint32), ("hdr_len", np.uint32), ("body_off", np.uint32), ("body_len", np.uint32),
+                            ("reserved", np.uint32)])
 SEAM_DTYPE = np.dtype([("prev", "<u8"), ("next", "<u8"), ("tail_len", "<u4"), ("head_len", "<u4")])      # kmpgpu_seam, 24 bytes
 STREAM_DEPTH_MAX = 1 << 30     # KMPGPU_STREAM_DEPTH_MAX
 STREAM_DTYPE = np.dtype([("first_packet", "<u8"), ("last_packet", "<u8"), ("n_packets", "<u8"), ("bytes", "<u8"), ("flow", "<u4"),
@@ -556,6 +563,49 @@ class GpuMatcher:
             raise KmpGpuError(f"kmpgpu_load_decoded reports {stats['n_payloads']} payloads and {stats['n_changed']} changed ones, the "
                               f"bitmap holds {int(changed.sum())} of {n_src}")
         return {"changed": changed, "index": index, "stats": stats}
+
+    def http_locate(self) -> dict:
+        """Locate the HTTP message at the start of every payload of this matcher's arena (kmpgpu_http_locate; the definition:
+        kmpgpu.h).  The spans stay on the device until the arena changes; with valid spans nothing is launched.  Returns the
+        stats: {"n_requests", "n_responses", "n_blank", "bytes_scanned"}."""
+        st = _lib.HttpStats()
+        gpu_check(self._g.kmpgpu_http_locate(self._ctx, C.byref(st)), "kmpgpu_http_locate")
+        return {f: int(getattr(st, f)) for f, _ in _lib.HttpStats._fields_}
+
+    def http_spans(self) -> np.ndarray:
+        """The kmpgpu_http_span records of the last http_locate() / load_fields() over this matcher's arena, one per payload, as
+        a structured array (HTTP_SPAN_DTYPE)."""
+        n, _ = self.arena_info()
+        out = np.zeros(max(n, 1), dtype=HTTP_SPAN_DTYPE)
+        gpu_check(self._g.kmpgpu_http_spans_read(self._ctx, out.ctypes.data, 0, n), "kmpgpu_http_spans_read")
+        return out[:n]
+
+    def load_fields(self, src: "GpuMatcher", field: str = "raw_uri", only_present: bool = False) -> dict:
+        """Make this matcher's arena one HTTP field of every payload of ``src`` (kmpgpu_load_fields; the definition: kmpgpu.h);
+        patterns, rules, windows and options of this matcher stay.  field: "method", "raw_uri", "status", "headers" or "body".
+        only_present: this matcher holds only the payloads that have the field, compacted in ascending source order.  Returns
+        {"present": bool[n_src], "index": int64[n_dst], "stats": {...}}: payload j of this matcher is the field of payload
+        index[j] of src."""
+        if field not in FIELD_NAMES:
+            raise ValueError(f"field: {field!r} is none of {', '.join(FIELD_NAMES)}")
+        n_src, _ = src.arena_info()
+        W = (n_src + 63) // 64
+        words = np.zeros(max(W, 1), dtype=np.uint64)
+        st = _lib.FieldsStats()
+        flags = FIELDS_ONLY_PRESENT if only_present else 0
+        gpu_check(self._g.kmpgpu_load_fields(self._ctx, src._ctx, FIELD_NAMES[field], flags, words.ctypes.data, None, C.byref(st)),
+                  "kmpgpu_load_fields")
+        self._keep = None
+        bits = np.unpackbits(words[:W].view(np.uint8), bitorder="little")
+        if bits[n_src:].any():
+            raise KmpGpuError(f"kmpgpu_load_fields set a bit at or above {n_src} in the present bitmap")
+        present = bits[:n_src].astype(bool)
+        index = np.flatnonzero(present).astype(np.int64) if only_present else np.arange(n_src, dtype=np.int64)
+        stats = {f: int(getattr(st, f)) for f, _ in _lib.FieldsStats._fields_}
+        if stats["n_present"] != int(present.sum()) or stats["n_payloads"] != index.size or self.arena_info()[0] != index.size:
+            raise KmpGpuError(f"kmpgpu_load_fields reports {stats['n_payloads']} payloads and {stats['n_present']} present ones, the "
+                              f"bitmap holds {int(present.sum())} of {n_src}")
+        return {"present": present, "index": index, "stats": stats}
 
     def arena_download(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         n, _ = self.arena_info()
