@@ -875,6 +875,53 @@ int  kmpgpu_load_decoded(kmpgpu_ctx *dst, kmpgpu_ctx *src, int transform, uint32
                          uint64_t *changed_out /* host [ceil(n_src / 64)] or NULL */, const void **d_changed /* or NULL */,
                          kmpgpu_decode_stats *stats /* or NULL */);
 
+/* The base64 runs of an arena's payloads decoded on the device into a packed arena that a second context owns, so that
+ * `Authorization: Basic YWRtaW46YWRtaW4=`, a JWT in a cookie, `powershell -enc ...` or a base64 blob in a body meet the rules that
+ * name what the base64 holds (`admin:admin`).  A sibling of kmpgpu_load_decoded: a call of its own, not a value of `transform`.
+ * Definition.  Let payload k of src be the bytes p[0..L), L = pkt_len[k]: the whole payload -- the call does not look at
+ * KMPGPU_OPT_WHOLE_PAYLOAD and does not stop at 0x00.  No byte at or behind L takes part: slot padding, a borrowed arena's dirty
+ * padding, the next slot.
+ *   alpha(b): b is one of A-Z a-z 0-9 + /; under KMPGPU_B64_URLSAFE the last two are - and _ instead, and + and / are then not
+ *     alphabet.  val(b) is 0..63 in that order.
+ *   Run: a maximal interval [s, e) of alphabet bytes inside the payload: s == 0 or !alpha(p[s-1]), and e == L or !alpha(p[e]).  Its
+ *     length is m = e - s.
+ *   Decoded run: a run with m >= min_run, 4 <= min_run <= 255.
+ *   A decoded run yields floor(3m / 4) bytes: the alphabet byte at run offset r = i - s yields nothing where r % 4 == 0, otherwise the
+ *     byte ((val(p[i-1]) << 2 * (r % 4)) | (val(p[i]) >> (6 - 2 * (r % 4)))) & 0xFF.  Leftover bits at the run's end are dropped,
+ *     whatever they are: 6 bits for m % 4 == 1, then 4 and 2.
+ *   Padding: directly behind a decoded run with m % 4 == 2 the first up to two '=' yield nothing, with m % 4 == 3 the first one; they
+ *     must lie inside the payload.
+ *   Every other byte is copied: alphabet bytes of shorter runs, other '=', everything else.
+ *   changed(k): payload k holds at least one decoded run -- the same as "the output differs from the payload", because a decoded run
+ *     always shrinks.
+ * This is Python's base64 module run by run: re.sub over ([alphabet]{min_run,})(={0,2}), the run (less its last character where
+ * m % 4 == 1) padded to a multiple of 4 and given to b64decode / urlsafe_b64decode, the '=' that the padding rule does not consume put
+ * back.  A decoded 0x00 ends the payload's text under dst's default text rule, as %00 does.
+ * min_run is the caller's guard against decoding ordinary words: every run of that many letters and digits IS base64 by this
+ * definition.  `Authorization: Basic YWRtaW46YWRtaW4=\r\n` at min_run = 14 becomes `Authorization: Basic admin:admin\r\n`; at
+ * min_run = 8 the word `Authorization` (13 letters) is itself a decoded run and comes out as 9 bytes of noise.  That is the definition
+ * and not a defect: the raw context still holds the word, and the caller combines rows of contexts that share src's numbering, as for
+ * the percent-decoded buffer.  Choose min_run above the longest word the rules on dst must still see and at or below the shortest
+ * encoded value they look for (16 covers a 12-byte secret).
+ * Result, outputs (changed_out, *d_changed, *stats), state, ordering, buffers, KMPGPU_B64_ONLY_CHANGED and the empty cases (no payload
+ * changed, n_src == 0: dst left without an arena, KMPGPU_OK) are those of kmpgpu_load_decoded, word for word: slots of
+ * max(16, round_up(len, 16)) bytes back to back from offset 0, every slot's tail 0x00 whatever the source held, an empty result payload
+ * owning one zero slot; the metadata goes along; dst's rows are in src's numbering, or numbered through the changed bitmap; *d_changed
+ * is what kmpgpu_load_selected takes.  The source is whatever src scans now, a decoded, field, stream or base64 arena included: a
+ * twice-encoded value takes two calls.
+ * Errors: a NULL context, dst == src, min_run outside 4..255, an unknown flag bit, contexts on different devices: KMPGPU_EINVAL;
+ * either context between kmpgpu_load_frames_begin and _finish: KMPGPU_ESTATE.  After each of these dst keeps the arena it had, *stats
+ * is zero and *d_changed NULL.  Allocation failures: as kmpgpu_load_decoded.
+ * kmpgpu_last_timing(dst): kernel_ms from the lengths kernel to the write's end, launches = the kernels in that span (base64 lengths,
+ * two scan kernels, index, write: 5; 3 where dst ends up without a payload); the metadata's copy or kernel follows the span.
+ * kmpgpu_profile_begin .. _end time the span in four pairs: lengths, scan, index, write.
+ * Cost: two reads of src's payload bytes (lengths, write) and one write of the decoded ones. */
+#define KMPGPU_B64_URLSAFE      1u     /* flags: the alphabet ends in - _ instead of + / */
+#define KMPGPU_B64_ONLY_CHANGED 2u     /* dst holds the changed payloads only */
+int  kmpgpu_load_base64(kmpgpu_ctx *dst, kmpgpu_ctx *src, uint32_t min_run, uint32_t flags,
+                        uint64_t *changed_out /* host [ceil(n_src / 64)] or NULL */, const void **d_changed /* or NULL */,
+                        kmpgpu_decode_stats *stats /* or NULL */);
+
 /* HTTP field buffers: the method, the URI, the status, the headers or the body of the HTTP message at the start of every payload, as a
  * packed arena that a second context owns -- the sticky buffers of signature languages (http_method, http_raw_uri, http_stat_code,
  * http_header, http_client_body).  That context scans it with everything the library has, in src's payload numbering, so a rule that

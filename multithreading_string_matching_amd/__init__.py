@@ -20,6 +20,8 @@ from .host import (  # noqa: F401
     write_udp_pcap,
 )
 from .matcher import (  # noqa: F401
+    B64_ONLY_CHANGED,
+    B64_URLSAFE,
     DECODE_ONLY_CHANGED,
     DECODE_PERCENT,
     DECODE_PLUS,

@@ -330,6 +330,7 @@ GPU_API = {
     "kmpgpu_alerts_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "kmpgpu_load_selected": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, u64p]),
     "kmpgpu_load_decoded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(DecodeStats)]),
+    "kmpgpu_load_base64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(DecodeStats)]),
     "kmpgpu_http_locate": (C.c_int, [C.c_void_p, C.POINTER(HttpStats)]),
     "kmpgpu_http_spans_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "kmpgpu_load_fields": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(FieldsStats)]),

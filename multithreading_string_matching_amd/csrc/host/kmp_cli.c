@@ -112,6 +112,15 @@
  * KMPGPU_OFFSETS_FILE, KMPGPU_EXPORT_FILE, KMPGPU_FLOW_SEAMS, KMPGPU_FLOW_STREAMS, KMPGPU_FLOWBITS_FILE or KMPGPU_THRESHOLDS_FILE; the
  * variable with none of the three row outputs.
  *
+ * KMPGPU_BASE64=<min_run>[,url], together with at least one of KMPGPU_PACKETS_FILE, KMPGPU_ALERTS_FILE and KMPGPU_FLOW_ALERTS_FILE: these
+ * row outputs are decided on the payloads with their base64 runs of <min_run> (4..255) alphabet bytes and more decoded
+ * (kmpgpu_load_base64; the definition: kmpgpu.h; ,url: the alphabet that ends in - _), so that `Authorization: Basic YWRtaW46YWRtaW4=`
+ * meets the rule that names `admin:admin`.  Per shard a second context on the shard's device gets the same tables as the shard's
+ * (upload_tables) and the decoding of the shard's arena, every payload, so the payload numbers are the capture's.  stdout and
+ * KMPGPU_FLOWS_FILE are what they are without the variable.  Refused with a message on stderr and exit 1, before any GPU work: any other
+ * value; the variable together with KMPGPU_DECODE, KMPGPU_HTTP_FIELD, KMPGPU_OFFSETS_FILE, KMPGPU_EXPORT_FILE, KMPGPU_FLOW_SEAMS,
+ * KMPGPU_FLOW_STREAMS, KMPGPU_FLOWBITS_FILE or KMPGPU_THRESHOLDS_FILE; the variable with none of the three row outputs.
+ *
  * KMPGPU_FLOW_STREAMS=<depth>, together with KMPGPU_FLOW_ALERTS_FILE: the flow alerts are decided on the reassembled streams.  A second
  * context on the shard's device gets the same tables as the shard's (upload_tables; the windows too: on a stream they mean "offset in the
  * connection's direction") and the payloads of every flow direction concatenated in capture order and cut to <depth> bytes
@@ -163,6 +172,7 @@
 #include "kmphost.h"
 #include "kmp_cli_common.h"
 #include "kmp_cli_decode.h"
+#include "kmp_cli_base64.h"
 #include "kmp_cli_fields.h"
 #include "kmp_cli_streams.h"
 #include "kmp_cli_streams_order.h"
@@ -191,6 +201,8 @@ typedef struct cli_options {
     uint32_t flow_seams;                    /* KMPGPU_FLOW_SEAMS: the reach, 0 without the variable */
     int decode;                             /* KMPGPU_DECODE: KMP_CLI_DECODE_* */
     int http_field;                         /* KMPGPU_HTTP_FIELD: KMP_CLI_FIELD_* */
+    unsigned base64_min_run;                /* KMPGPU_BASE64: min_run, 0 = not set */
+    int base64_url;                         /* ... ,url */
     uint32_t flow_streams;                  /* KMPGPU_FLOW_STREAMS: the depth, 0 without the variable */
     const char *streams_path;               /* KMPGPU_STREAMS_FILE */
     int streams_order;                      /* KMPGPU_FLOW_STREAMS_ORDER: KMP_CLI_STREAMS_ORDER_* */
@@ -241,7 +253,7 @@ typedef struct cli_run {
     int ndev, shards, reduce_rccl, rules_set;
     shard_job *job;
     kmpgpu_ctx **ctxs;                      /* ctxs[r] = job[r].ctx */
-    kmpgpu_ctx **rows;                      /* rows[r]: the context the row outputs of shard r come from -- ctxs[r], or with KMPGPU_DECODE its decoding, or with KMPGPU_HTTP_FIELD its field buffer */
+    kmpgpu_ctx **rows;                      /* rows[r]: the context the row outputs of shard r come from -- ctxs[r], or with KMPGPU_DECODE its decoding, with KMPGPU_HTTP_FIELD its field buffer, with KMPGPU_BASE64 its base64 decoding */
     kmpgpu_comm *comm;
     uint64_t *own, *counts;                 /* own[r * n_patterns + i]: shard r's count of pattern i; counts[i]: the total */
     double kernel_ms;
@@ -560,6 +572,33 @@ static void load_options(int argc, char *argv[], cli_options *opt)
             exit(1);
         }
     }
+    /* the base64-decoded buffer: it changes what the row outputs hold and nothing else */
+    const char *base64_env = env_path("KMPGPU_BASE64");
+    if (base64_env) {
+        static const char *const not_with[][2] = {
+            {"KMPGPU_DECODE", "one decoding per run; at the library, kmpgpu_load_decoded over the base64 context does both"},
+            {"KMPGPU_HTTP_FIELD", "base64 in a field buffer is not wired in this program"},
+            {"KMPGPU_OFFSETS_FILE", "offsets in decoded payloads are not mapped back to the capture's"},
+            {"KMPGPU_EXPORT_FILE", "the export selects and writes the payloads as captured"},
+            {"KMPGPU_FLOW_SEAMS", "decoded seams do not exist"},
+            {"KMPGPU_FLOW_STREAMS", "base64 in streams is not wired in this program"},
+            {"KMPGPU_FLOWBITS_FILE", "flow bits over base64-decoded payloads are not wired in this program"},
+            {"KMPGPU_THRESHOLDS_FILE", "base64-decoded payloads keep no timestamps in this program"}};
+        if (!kmp_cli_parse_base64(base64_env, &opt->base64_min_run, &opt->base64_url)) {
+            fprintf(stderr, "KMPGPU_BASE64 is \"%s\": <min_run> or <min_run>,url with a min_run of %u..%u is needed\n", base64_env, KMP_CLI_BASE64_MIN_RUN_LO,
+                    KMP_CLI_BASE64_MIN_RUN_HI);
+            exit(1);
+        }
+        for (size_t i = 0; i < sizeof not_with / sizeof not_with[0]; i++)
+            if (env_path(not_with[i][0])) {
+                fprintf(stderr, "KMPGPU_BASE64 does not go together with %s: %s\n", not_with[i][0], not_with[i][1]);
+                exit(1);
+            }
+        if (!opt->packets_path && !opt->alerts_path && !opt->flow_alerts_path) {
+            fprintf(stderr, "KMPGPU_BASE64 has no effect without KMPGPU_PACKETS_FILE, KMPGPU_ALERTS_FILE or KMPGPU_FLOW_ALERTS_FILE\n");
+            exit(1);
+        }
+    }
     opt->want_meta = opt->headers.n || opt->flows_path || opt->flow_alerts_path || opt->flowbits.n || opt->thresholds_by_flow || opt->thresholds_by_addr;
     /* the export starts as a capture without frames: a path that cannot be written ends the run here */
     if (opt->export_path && kmp_write_udp_pcap_part(opt->export_path, 0, NULL, NULL, NULL, 0, 0)) {
@@ -743,6 +782,20 @@ static void decode_shards(const cli_options *opt, cli_run *run)
         const char *failed = upload_tables(d, opt);
         if (failed) die_gpu(failed);
         if (kmpgpu_load_decoded(d, run->ctxs[r], KMPGPU_DECODE_PERCENT, flags, NULL, NULL, NULL)) die_gpu("kmpgpu_load_decoded");
+        run->rows[r] = d;
+    }
+}
+
+/* KMPGPU_BASE64: as decode_shards, the shard's payloads with their base64 runs decoded. */
+static void base64_shards(const cli_options *opt, cli_run *run)
+{
+    const uint32_t flags = opt->base64_url ? KMPGPU_B64_URLSAFE : 0u;
+    for (int r = 0; r < run->shards; r++) {
+        kmpgpu_ctx *d = NULL;
+        if (kmpgpu_init(&d, run->job[r].device)) die_gpu("kmpgpu_init");
+        const char *failed = upload_tables(d, opt);
+        if (failed) die_gpu(failed);
+        if (kmpgpu_load_base64(d, run->ctxs[r], opt->base64_min_run, flags, NULL, NULL, NULL)) die_gpu("kmpgpu_load_base64");
         run->rows[r] = d;
     }
 }
@@ -1049,6 +1102,7 @@ int main(int argc, char *argv[])
         run.kernel_ms = (now_s() - t_scan0) * 1e3;                          /* wall time of the concurrent passes + reduce (mpi_dumping.c:206 MPI_MAX) */
 
         if (opt.decode) decode_shards(&opt, &run);
+        if (opt.base64_min_run) base64_shards(&opt, &run);
         if (opt.http_field) field_shards(&opt, &run);
         if (opt.offsets_path) write_offsets(opt.offsets_path, &run, n);
         if (opt.packets_path) write_alerts(opt.packets_path, &opt, &run, KMPGPU_ALERT_PATTERNS);

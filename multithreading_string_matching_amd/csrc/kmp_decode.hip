@@ -34,10 +34,12 @@
 
 #include "kmp_device.h"
 #include "kmp_launch.h"
+#include "kmp_unit_dev.h"
 
 namespace {
 
-typedef uint32_t dec_u32x4 __attribute__((ext_vector_type(4)));
+using namespace kmp_unit;     /* kmp_unit_dev.h: the units of a run dealt to the lanes, byte classes, scans, the LDS stage's sync */
+typedef u32x4 dec_u32x4;
 
 constexpr uint32_t KMP_DECODE_UNROLL = 4;             /* 16-byte units a lane has in flight */
 constexpr uint32_t KMP_DECODE_LENGTHS_BLOCKS = 1024;  /* grid cap of the lengths kernel: rounds past 4 096 groups of 64 payloads */
@@ -65,12 +67,7 @@ DecodeWs decode_ws(uint8_t *ws, uint64_t n)
     return w;
 }
 
-/* ---- byte classes of a dword, 0x80 in every byte of the class, and those four bits gathered into bits 0..3 ---- */
-__device__ __forceinline__ uint32_t eq_bytes(uint32_t w, uint32_t c4)
-{
-    const uint32_t x = w ^ c4;
-    return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);
-}
+/* ---- byte classes of a dword, 0x80 in every byte of the class (eq_bytes, bits4, eq16: kmp_unit_dev.h) ---- */
 __device__ __forceinline__ uint32_t hex_bytes(uint32_t w)
 {
     const uint32_t lo7 = w & 0x7F7F7F7Fu;
@@ -79,43 +76,11 @@ __device__ __forceinline__ uint32_t hex_bytes(uint32_t w)
     const uint32_t let = (l + 0x1F1F1F1Fu) & ~(l + 0x19191919u);            /* 0x61 <= b | 0x20 <= 0x66 */
     return (dig | let) & ~w & 0x80808080u;
 }
-__device__ __forceinline__ uint32_t bits4(uint32_t t) { return ((t >> 7) * 0x10204080u) >> 28; }
-__device__ __forceinline__ uint32_t eq16(dec_u32x4 v, uint32_t c4)
-{
-    return bits4(eq_bytes(v.x, c4)) | bits4(eq_bytes(v.y, c4)) << 4 | bits4(eq_bytes(v.z, c4)) << 8 | bits4(eq_bytes(v.w, c4)) << 12;
-}
 __device__ __forceinline__ uint32_t hex16(dec_u32x4 v)
 {
     return bits4(hex_bytes(v.x)) | bits4(hex_bytes(v.y)) << 4 | bits4(hex_bytes(v.z)) << 8 | bits4(hex_bytes(v.w)) << 12;
 }
 constexpr uint32_t PCT4 = 0x25252525u, PLUS4 = 0x2B2B2B2Bu;
-
-/* the positions of a unit that lie inside a payload of which `left` bytes remain at the unit's start */
-__device__ __forceinline__ uint32_t valid_bits(uint32_t left) { return left >= 16u ? 0xFFFFu : (1u << left) - 1u; }
-
-/* Inclusive sum over the wavefront (all 64 lanes active): four shifts inside the rows of 16, then the rows' totals handed on. */
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x)
-{
-    int v = (int)x;
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false);          /* row_shr:1 */
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, false);          /* row_shr:2 */
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, false);          /* row_shr:4 */
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, false);          /* row_shr:8 */
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);          /* row_bcast:15 into rows 1 and 3 */
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);          /* row_bcast:31 into rows 2 and 3 */
-    return (uint32_t)v;
-}
-/* ... of 64-bit values, once per run: the unit counts of 64 payloads of up to 2^30 bytes do not fit 32 bits */
-__device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t v, uint32_t lane)
-{
-#pragma unroll
-    for (uint32_t d = 1; d < KMP_WAVE; d <<= 1) {
-        const uint64_t t = __shfl_up((unsigned long long)v, d);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-__device__ __forceinline__ uint64_t bcast64(uint64_t v, uint32_t from) { return (uint64_t)__shfl((unsigned long long)v, (int)from); }
 
 /* '%' and hex masks of a unit (bits 0..15, '%' | hex << 16), and what the four bytes on either side add (same packing: the unit
  * before, of which bits 12..15 count, and the one behind, of which bits 0..3 do) -> emitted positions and escape starts */
@@ -131,49 +96,6 @@ __device__ __forceinline__ UnitMasks unit_masks(uint32_t own, uint32_t prevm, ui
     m.emit = valid & ~(C >> 4) & 0xFFFFu;
     return m;
 }
-
-template <bool NT>
-__device__ __forceinline__ dec_u32x4 load_unit(const uint8_t *p)
-{
-    const dec_u32x4 *q = reinterpret_cast<const dec_u32x4 *>(p);
-    return NT ? __builtin_nontemporal_load(q) : *q;
-}
-template <bool NT>
-__device__ __forceinline__ void store_unit(uint8_t *p, dec_u32x4 v)
-{
-    dec_u32x4 *q = reinterpret_cast<dec_u32x4 *>(p);
-    if (NT) __builtin_nontemporal_store(v, q); else *q = v;
-}
-
-/* the bytes [keep, 16) of a unit cleared; keep >= 16 leaves it whole */
-__device__ __forceinline__ dec_u32x4 keep_bytes(dec_u32x4 v, uint32_t keep)
-{
-    uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (uint32_t d = 0; d < 4u; ++d) {
-        const uint32_t lo = 4u * d;
-        w[d] &= (keep >= lo + 4u) ? 0xFFFFFFFFu : (keep <= lo) ? 0u : ((1u << (8u * (keep - lo))) - 1u);
-    }
-    dec_u32x4 r; r.x = w[0]; r.y = w[1]; r.z = w[2]; r.w = w[3];
-    return r;
-}
-
-/* the wavefront's own LDS: its DS instructions execute in order, the barriers keep the compiler from moving them */
-__device__ __forceinline__ void lds_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-/* One unit of a step, as both kernels see it. */
-struct Unit {
-    dec_u32x4 v;            /* the 16 bytes, 0 for a lane without a unit */
-    uint32_t  p;            /* payload of the run */
-    uint32_t  rel, len;     /* the unit's offset in its payload, the payload's length */
-    uint32_t  first;        /* lane of this step that holds the payload's first unit, 0 where that unit lies in an earlier step */
-    bool      act, started; /* the lane has a unit; its payload began in an earlier step */
-};
 
 /* Masks of a unit with its neighbours' through the lane shift; lane 0 from hp, the last dword of the step before (its lane 63 held the
  * unit before), lane 63 from the unit behind its own, which it loads where its own ends in a '%'.  next_x: the four bytes
@@ -198,35 +120,6 @@ __device__ __forceinline__ UnitMasks step_masks(const Unit &un, uint32_t hp, con
     if (un.rel + 16u >= un.len) nextm = 0u;                     /* ... and so does the lane behind */
     *next_x = nx;
     return unit_masks(own, prevm, nextm, valid);
-}
-
-/* The run's tables and the search.  s_ub: units of the run before payload i. */
-__device__ __forceinline__ uint32_t find_payload(const uint64_t *s_ub, uint64_t g)
-{
-    uint32_t p = 0u;                                            /* the last payload of the run that starts at or before unit g */
-#pragma unroll
-    for (uint32_t step = KMP_WAVE / 2u; step; step >>= 1)
-        if (s_ub[p + step] <= g) p += step;
-    return p;
-}
-
-template <bool NT>
-__device__ __forceinline__ void load_step(Unit &un, const uint8_t *src, const uint64_t *s_ub, const uint64_t *s_src, const uint32_t *s_len,
-                                          uint64_t gs, uint64_t total_units, uint32_t lane)
-{
-    const uint64_t g = gs + lane;
-    un.act = g < total_units;
-    un.v = (dec_u32x4)(0u);
-    un.p = 0u; un.rel = 0u; un.len = 0u; un.first = 0u; un.started = false;
-    if (un.act) {
-        un.p = find_payload(s_ub, g);
-        const uint64_t ub = s_ub[un.p];
-        un.rel = (uint32_t)(g - ub) * 16u;
-        un.len = s_len[un.p];
-        un.started = ub < gs;
-        un.first = un.started ? 0u : (uint32_t)(ub - gs);
-        un.v = load_unit<NT>(src + s_src[un.p] + un.rel);
-    }
 }
 
 __global__ void __launch_bounds__(KMP_BLOCK_THREADS)

@@ -201,6 +201,14 @@ hipError_t kmp_launch_decode_index(const uint64_t *src_off, const uint32_t *src_
                                    uint32_t *pkt_len, void *recs, hipStream_t st);
 hipError_t kmp_launch_decode_write(const uint8_t *src_arena, const uint64_t *pkt_off, const void *recs, uint64_t n_dst, uint64_t bytes_in,
                                    uint64_t total_bytes, bool plus, uint8_t *arena, bool nontemporal, hipStream_t st);
+/* kmp_base64.hip (kmpgpu_load_base64): the base64 runs of min_run (4..255) alphabet bytes and more decoded (the definition: kmpgpu.h).
+ * The phases, ws, changed, stats and recs are those of kmp_decode.hip: _lengths (1 kernel) and _write (1 kernel) here, and between
+ * them kmp_launch_decode_scan and kmp_launch_decode_index, whose workspace layout and records these two share. */
+hipError_t kmp_launch_base64_lengths(const uint8_t *src_arena, const uint64_t *src_off, const uint32_t *src_len, uint64_t n, uint32_t min_run,
+                                     bool urlsafe, bool only_changed, uint8_t *ws, unsigned long long *changed, unsigned long long *stats,
+                                     hipStream_t st);
+hipError_t kmp_launch_base64_write(const uint8_t *src_arena, const uint64_t *pkt_off, const void *recs, uint64_t n_dst, uint64_t bytes_in,
+                                   uint64_t total_bytes, uint32_t min_run, bool urlsafe, uint8_t *arena, bool nontemporal, hipStream_t st);
 /* kmp_fields.hip (kmpgpu_http_locate, kmpgpu_load_fields): the HTTP field buffers (the definition: kmpgpu.h).  _http_locate (1 kernel)
  * writes spans[n] (kmpgpu_http_span, 32 bytes each, 16-byte aligned) and adds to stats[4] = {requests, responses, messages with a blank
  * line, bytes scanned}, which the caller zeroes.  ws: kmp_extract_ws_bytes(n) bytes, kept from _lengths to _index.  _lengths (1 kernel)

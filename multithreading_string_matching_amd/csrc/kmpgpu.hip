@@ -1595,20 +1595,31 @@ int kmpgpu_load_selected(kmpgpu_ctx *dst, kmpgpu_ctx *src, const void *select, i
     return KMPGPU_OK;
 }
 
-int kmpgpu_load_decoded(kmpgpu_ctx *dst, kmpgpu_ctx *src, int transform, uint32_t flags, uint64_t *changed_out, const void **d_changed,
-                        kmpgpu_decode_stats *stats)
+/* What kmpgpu_load_decoded and kmpgpu_load_base64 differ in: the lengths and the write kernel, and what those take. */
+struct Recoding {
+    const char *who;
+    bool base64;            /* kmp_base64.hip, else kmp_decode.hip */
+    bool plus;              /* KMPGPU_DECODE_PLUS */
+    uint32_t min_run;       /* base64 */
+    bool urlsafe;           /* KMPGPU_B64_URLSAFE */
+    bool only_changed;
+};
+
+/* The checks the two calls share, behind the ones on their own arguments. */
+static int recoding_refused(const kmpgpu_ctx *dst, const kmpgpu_ctx *src, const char *who)
 {
-    const char *who = "kmpgpu_load_decoded";
-    if (d_changed) *d_changed = nullptr;
-    if (stats) *stats = kmpgpu_decode_stats{};
-    if (!dst || !src) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
-    if (dst == src) return fail(KMPGPU_EINVAL, "%s: dst and src are the same context (decoding in place does not exist)", who);
-    if (transform != KMPGPU_DECODE_PERCENT) return fail(KMPGPU_EINVAL, "%s: transform %d is not KMPGPU_DECODE_PERCENT", who, transform);
-    if (flags & ~(KMPGPU_DECODE_PLUS | KMPGPU_DECODE_ONLY_CHANGED)) return fail(KMPGPU_EINVAL, "%s: unknown flag bits 0x%x", who, flags);
     if (dst->device != src->device)
         return fail(KMPGPU_EINVAL, "%s: the contexts sit on devices %d and %d (decoding across devices does not exist)", who, dst->device, src->device);
     if (dst->fr_pending || src->fr_pending) return fail(KMPGPU_ESTATE, "%s: %s sits between kmpgpu_load_frames_begin and _finish", who, dst->fr_pending ? "dst" : "src");
-    const bool plus = (flags & KMPGPU_DECODE_PLUS) != 0, only_changed = (flags & KMPGPU_DECODE_ONLY_CHANGED) != 0;
+    return KMPGPU_OK;
+}
+
+/* The span both calls share: lengths, scan, index, write, through the one arena-install path. */
+static int load_recoded(kmpgpu_ctx *dst, kmpgpu_ctx *src, const Recoding &how, uint64_t *changed_out, const void **d_changed,
+                        kmpgpu_decode_stats *stats)
+{
+    const char *who = how.who;
+    const bool only_changed = how.only_changed;
     HIP_TRY(hipSetDevice(dst->device));
     HIP_TRY(hipStreamSynchronize(dst->stream));           /* the passes over the arena that is about to be replaced */
     HIP_TRY(hipStreamSynchronize(src->stream));           /* whatever src's stream still does with its arena */
@@ -1627,7 +1638,11 @@ int kmpgpu_load_decoded(kmpgpu_ctx *dst, kmpgpu_ctx *src, int transform, uint32_
     hipEvent_t e1;
     HIP_TRY(hipEventRecord(c->ev[2], c->stream));
     HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_decode_lengths(src->d_arena, src->d_off, src->d_len, n, plus, only_changed, c->fr_ws, c->d_dec_changed, d_stats, c->stream));
+    if (how.base64)
+        HIP_TRY(kmp_launch_base64_lengths(src->d_arena, src->d_off, src->d_len, n, how.min_run, how.urlsafe, only_changed, c->fr_ws, c->d_dec_changed,
+                                          d_stats, c->stream));
+    else
+        HIP_TRY(kmp_launch_decode_lengths(src->d_arena, src->d_off, src->d_len, n, how.plus, only_changed, c->fr_ws, c->d_dec_changed, d_stats, c->stream));
     HIP_TRY(profile_launched(c, e1));
     HIP_TRY(profile_launch(c, &e1));
     HIP_TRY(kmp_launch_decode_scan(n, c->fr_ws, c->fr_tot, c->stream));
@@ -1669,7 +1684,11 @@ int kmpgpu_load_decoded(kmpgpu_ctx *dst, kmpgpu_ctx *src, int transform, uint32_
     HIP_TRY(kmp_launch_decode_index(src->d_off, src->d_len, n, c->fr_ws, n_pkts, c->owned_off, c->owned_len, c->fr_src, c->stream));
     HIP_TRY(profile_launched(c, e1));
     HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_decode_write(src->d_arena, c->owned_off, c->fr_src, n_pkts, tot[2], tot[0], plus, c->owned_arena, c->nontemporal != 0, c->stream));
+    if (how.base64)
+        HIP_TRY(kmp_launch_base64_write(src->d_arena, c->owned_off, c->fr_src, n_pkts, tot[2], tot[0], how.min_run, how.urlsafe, c->owned_arena,
+                                        c->nontemporal != 0, c->stream));
+    else
+        HIP_TRY(kmp_launch_decode_write(src->d_arena, c->owned_off, c->fr_src, n_pkts, tot[2], tot[0], how.plus, c->owned_arena, c->nontemporal != 0, c->stream));
     HIP_TRY(profile_launched(c, e1));
     HIP_TRY(hipEventRecord(c->ev[3], c->stream));
     /* src has metadata: the records go with the payloads -- in their new order, or all of them as they are */
@@ -1679,11 +1698,41 @@ int kmpgpu_load_decoded(kmpgpu_ctx *dst, kmpgpu_ctx *src, int transform, uint32_
     }
     IndexFacts f;
     int rc = validate_index(c, who, c->owned_off, c->owned_len, n_pkts, arena_bytes, &f);
-    /* kmp_decode_write_kernel writes every slot whole: payload, then 0x00 up to the slot's end */
+    /* kmp_decode_write_kernel and kmp_base64_write_kernel write every slot whole: payload, then 0x00 up to the slot's end */
     if (!rc) rc = install_arena(c, c->owned_arena, c->owned_off, c->owned_len, arena_bytes, n_pkts, f, /* wrote_padding = */ true);
     if (rc) { release_arena(c, true); return rc; }
     c->has_meta = src->has_meta;
     return done(5);
+}
+
+int kmpgpu_load_decoded(kmpgpu_ctx *dst, kmpgpu_ctx *src, int transform, uint32_t flags, uint64_t *changed_out, const void **d_changed,
+                        kmpgpu_decode_stats *stats)
+{
+    const char *who = "kmpgpu_load_decoded";
+    if (d_changed) *d_changed = nullptr;
+    if (stats) *stats = kmpgpu_decode_stats{};
+    if (!dst || !src) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
+    if (dst == src) return fail(KMPGPU_EINVAL, "%s: dst and src are the same context (decoding in place does not exist)", who);
+    if (transform != KMPGPU_DECODE_PERCENT) return fail(KMPGPU_EINVAL, "%s: transform %d is not KMPGPU_DECODE_PERCENT", who, transform);
+    if (flags & ~(KMPGPU_DECODE_PLUS | KMPGPU_DECODE_ONLY_CHANGED)) return fail(KMPGPU_EINVAL, "%s: unknown flag bits 0x%x", who, flags);
+    if (const int rc = recoding_refused(dst, src, who)) return rc;
+    const Recoding how = {who, false, (flags & KMPGPU_DECODE_PLUS) != 0, 0u, false, (flags & KMPGPU_DECODE_ONLY_CHANGED) != 0};
+    return load_recoded(dst, src, how, changed_out, d_changed, stats);
+}
+
+int kmpgpu_load_base64(kmpgpu_ctx *dst, kmpgpu_ctx *src, uint32_t min_run, uint32_t flags, uint64_t *changed_out, const void **d_changed,
+                       kmpgpu_decode_stats *stats)
+{
+    const char *who = "kmpgpu_load_base64";
+    if (d_changed) *d_changed = nullptr;
+    if (stats) *stats = kmpgpu_decode_stats{};
+    if (!dst || !src) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
+    if (dst == src) return fail(KMPGPU_EINVAL, "%s: dst and src are the same context (decoding in place does not exist)", who);
+    if (min_run < 4u || min_run > 255u) return fail(KMPGPU_EINVAL, "%s: min_run %u is outside 4..255", who, min_run);
+    if (flags & ~(KMPGPU_B64_URLSAFE | KMPGPU_B64_ONLY_CHANGED)) return fail(KMPGPU_EINVAL, "%s: unknown flag bits 0x%x", who, flags);
+    if (const int rc = recoding_refused(dst, src, who)) return rc;
+    const Recoding how = {who, true, false, min_run, (flags & KMPGPU_B64_URLSAFE) != 0, (flags & KMPGPU_B64_ONLY_CHANGED) != 0};
+    return load_recoded(dst, src, how, changed_out, d_changed, stats);
 }
 
 /* The spans of src's arena, made on the stream of `on` (src itself, or the dst of kmpgpu_load_fields, which has waited for src's stream)

@@ -37,6 +37,7 @@ FLOW_DTYPE = np.dtype([("first_packet", "<u8"), ("last_packet", "<u8"), ("n_pack
                        ("first", META_DTYPE)])     # kmpgpu_flow, 48 bytes
 DECODE_PERCENT = 1      # KMPGPU_DECODE_PERCENT: the transform of load_decoded
 DECODE_PLUS, DECODE_ONLY_CHANGED = 1, 2     # KMPGPU_DECODE_*: its flags
+B64_URLSAFE, B64_ONLY_CHANGED = 1, 2        # KMPGPU_B64_*: the flags of load_base64
 FIELD_METHOD, FIELD_RAW_URI, FIELD_STATUS, FIELD_HEADERS, FIELD_BODY = 1, 2, 3, 4, 5       # KMPGPU_FIELD_*: the field of load_fields
 FIELDS_ONLY_PRESENT = 1                     # KMPGPU_FIELDS_ONLY_PRESENT: its flag
 FIELD_NAMES = {"method": FIELD_METHOD, "raw_uri": FIELD_RAW_URI, "status": FIELD_STATUS, "headers": FIELD_HEADERS, "body": FIELD_BODY}
@@ -545,22 +546,34 @@ class GpuMatcher:
         windows and options of this matcher stay.  only_changed: this matcher holds only the payloads the decoding changes,
         compacted in ascending source order.  Returns {"changed": bool[n_src], "index": int64[n_dst], "stats": {...}}: payload j
         of this matcher is the decoding of payload index[j] of src."""
+        flags = (DECODE_PLUS if plus else 0) | (DECODE_ONLY_CHANGED if only_changed else 0)
+        return self._load_recoded(src, "kmpgpu_load_decoded", only_changed,
+                                  lambda words, st: self._g.kmpgpu_load_decoded(self._ctx, src._ctx, DECODE_PERCENT, flags, words, None, st))
+
+    def load_base64(self, src: "GpuMatcher", min_run: int = 16, urlsafe: bool = False, only_changed: bool = False) -> dict:
+        """Make this matcher's arena the payloads of ``src`` with their base64 runs of ``min_run`` (4..255) alphabet bytes and more
+        decoded on the device (kmpgpu_load_base64; the definition: kmpgpu.h -- base64.b64decode run by run, urlsafe_b64decode with
+        ``urlsafe``); patterns, rules, windows and options of this matcher stay.  only_changed: this matcher holds only the payloads
+        with a decoded run, compacted in ascending source order.  Returns what load_decoded returns."""
+        flags = (B64_URLSAFE if urlsafe else 0) | (B64_ONLY_CHANGED if only_changed else 0)
+        return self._load_recoded(src, "kmpgpu_load_base64", only_changed,
+                                  lambda words, st: self._g.kmpgpu_load_base64(self._ctx, src._ctx, int(min_run), flags, words, None, st))
+
+    def _load_recoded(self, src: "GpuMatcher", what: str, only_changed: bool, call) -> dict:
         n_src, _ = src.arena_info()
         W = (n_src + 63) // 64
         words = np.zeros(max(W, 1), dtype=np.uint64)
         st = _lib.DecodeStats()
-        flags = (DECODE_PLUS if plus else 0) | (DECODE_ONLY_CHANGED if only_changed else 0)
-        gpu_check(self._g.kmpgpu_load_decoded(self._ctx, src._ctx, DECODE_PERCENT, flags, words.ctypes.data, None, C.byref(st)),
-                  "kmpgpu_load_decoded")
+        gpu_check(call(words.ctypes.data, C.byref(st)), what)
         self._keep = None
         bits = np.unpackbits(words[:W].view(np.uint8), bitorder="little")
         if bits[n_src:].any():
-            raise KmpGpuError(f"kmpgpu_load_decoded set a bit at or above {n_src} in the changed bitmap")
+            raise KmpGpuError(f"{what} set a bit at or above {n_src} in the changed bitmap")
         changed = bits[:n_src].astype(bool)
         index = np.flatnonzero(changed).astype(np.int64) if only_changed else np.arange(n_src, dtype=np.int64)
         stats = {f: int(getattr(st, f)) for f, _ in _lib.DecodeStats._fields_}
         if stats["n_changed"] != int(changed.sum()) or stats["n_payloads"] != index.size or self.arena_info()[0] != index.size:
-            raise KmpGpuError(f"kmpgpu_load_decoded reports {stats['n_payloads']} payloads and {stats['n_changed']} changed ones, the "
+            raise KmpGpuError(f"{what} reports {stats['n_payloads']} payloads and {stats['n_changed']} changed ones, the "
                               f"bitmap holds {int(changed.sum())} of {n_src}")
         return {"changed": changed, "index": index, "stats": stats}
 
