@@ -5,7 +5,7 @@
  * The matrix is row-major (row i, word j holds payloads 64 j .. 64 j + 63), the list is payload-major: a transposing compaction.
  *
  *   kmp_alerts_count_kernel   cnt[k] = set bits of column k, written as the "length" 16 cnt[k] (0xFFFFFFFF where cnt[k] == 0: "rejected")
- *   kmp_scan_local_kernel, kmp_scan_totals_kernel   of kmp_prep.hip, through kmp_launch_repack_phase1: the byte offset of every payload's
+ *   kmp_scan_local_kernel, kmp_scan_totals_kernel   of kmp_prep.hip, through kmp_launch_compact_scan: the byte offset of every payload's
  *                             first 16-byte record, totals = {16 x records, payloads with a record}
  *   kmp_alerts_fill_kernel    the same walk; every payload's records at its offset, ascending rows
  *
@@ -33,21 +33,6 @@ typedef uint32_t alert_u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr uint32_t KMP_ALERTS_WORDS = 4;          /* column words a wavefront owns: 32 bytes of every row */
 constexpr uint32_t KMP_ALERTS_BLOCKS = 1024;      /* grid cap of both kernels: rounds past 1024 x 4 x 4 x 64 = 1 048 576 payloads */
-
-/* The scan workspace of kmp_prep.hip (kmp_extract_ws_bytes), as kmp_select.hip uses it: the counts-as-lengths take plen's place. */
-struct AlertsWs {
-    uint64_t *loc_off, *blk_bytes;
-    uint32_t *cnt_len;
-};
-AlertsWs alerts_ws(uint8_t *ws, uint64_t n)
-{
-    const uint64_t nblk = (n + KMP_SCAN_TILE - 1) / KMP_SCAN_TILE;
-    AlertsWs w;
-    w.loc_off = reinterpret_cast<uint64_t *>(ws);
-    w.blk_bytes = w.loc_off + n;
-    w.cnt_len = reinterpret_cast<uint32_t *>(w.blk_bytes + nblk) + n;
-    return w;
-}
 
 __device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, uint32_t s)
 {
@@ -163,13 +148,8 @@ hipError_t kmp_launch_alerts_count(const unsigned long long *rows, uint64_t stri
     if (n_pkts == 0) return hipSuccess;
     if ((stride & 1u) || stride * 64u < n_pkts || (uint64_t)n_rows * 16u > 0xFFFFFFFEull) return hipErrorInvalidValue;
     hipLaunchKernelGGL(kmp_alerts_count_kernel, dim3(alerts_blocks(n_pkts)), dim3(KMP_BLOCK_THREADS), 0, st, rows, stride, n_rows, n_pkts, any,
-                       alerts_ws(ws, n_pkts).cnt_len);
+                       kmp_compact_ws(ws, n_pkts).len);
     return hipGetLastError();
-}
-
-hipError_t kmp_launch_alerts_scan(uint64_t n_pkts, uint8_t *ws, unsigned long long *totals, hipStream_t st)
-{
-    return kmp_launch_repack_phase1(alerts_ws(ws, n_pkts).cnt_len, n_pkts, ws, totals, st);      /* kmp_scan_local_kernel + kmp_scan_totals_kernel */
 }
 
 hipError_t kmp_launch_alerts_fill(const unsigned long long *rows, uint64_t stride, uint32_t n_rows, uint64_t n_pkts,
@@ -177,7 +157,7 @@ hipError_t kmp_launch_alerts_fill(const unsigned long long *rows, uint64_t strid
 {
     if (n_pkts == 0 || max_records == 0) return hipSuccess;
     if ((stride & 1u) || stride * 64u < n_pkts) return hipErrorInvalidValue;
-    const AlertsWs w = alerts_ws(ws, n_pkts);
+    const kmp_compact_view w = kmp_compact_ws(ws, n_pkts);
     hipLaunchKernelGGL(kmp_alerts_fill_kernel, dim3(alerts_blocks(n_pkts)), dim3(KMP_BLOCK_THREADS), 0, st, rows, stride, n_rows, n_pkts, any,
                        w.loc_off, w.blk_bytes, reinterpret_cast<alert_u32x4 *>(recs), max_records);
     return hipGetLastError();

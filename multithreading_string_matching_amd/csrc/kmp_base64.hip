@@ -3,14 +3,13 @@
  *
  *   kmp_base64_lengths_kernel   dec_len[k] = decoded length of payload k, or 0xFFFFFFFF ("not in dst") for an unchanged payload under
  *                               KMPGPU_B64_ONLY_CHANGED; the changed bitmap, one plain store per word; bytes in / out and n_changed
- *   kmp_scan_local_kernel, kmp_scan_totals_kernel   of kmp_prep.hip, through kmp_launch_decode_scan (kmp_launch_repack_phase1)
+ *   kmp_scan_local_kernel, kmp_scan_totals_kernel   of kmp_prep.hip, through kmp_launch_compact_scan
  *   kmp_decode_index_kernel     of kmp_decode.hip, through kmp_launch_decode_index: its records {source offset, source length,
  *                               decoded length} are the ones the write here needs
  *   kmp_base64_write_kernel     the bytes
  *
- * The shape is that of kmp_decode.hip: both kernels that read payload bytes deal the 16-byte units of a RUN of consecutive payloads to
- * the lanes in order, a step is 64 units, four steps are in flight per lane, and the write compacts through the wavefront's own LDS
- * stage or, where a step holds no decoded run and its output position is a multiple of 16, stores the units as they are.
+ * The shape is the compacting skeleton's (lengths_body, write_body: kmp_compact_dev.h), as in kmp_decode.hip; what is this
+ * file's own is the policy Base64Decode.
  *
  * What a unit cannot decide alone (kmpgpu.h: a run is MAXIMAL, and only a run of min_run bytes and more is decoded):
  *   pre   the length of the alphabet run that ends directly before the unit's first byte, 0 at a payload's first unit.  A unit that is
@@ -28,32 +27,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <algorithm>
-
 #include "kmp_device.h"
 #include "kmp_launch.h"
-#include "kmp_unit_dev.h"
+#include "kmp_compact_dev.h"
 
 namespace {
 
-using namespace kmp_unit;     /* kmp_unit_dev.h: the units of a run dealt to the lanes, byte classes, scans, the LDS stage's sync */
-typedef u32x4 b64_u32x4;
+using namespace kmp_unit;     /* kmp_compact_dev.h: lengths_body, write_body; kmp_unit_dev.h: the unit, byte classes */
 
-constexpr uint32_t KMP_B64_UNROLL = 4;              /* 16-byte units a lane has in flight */
-constexpr uint32_t KMP_B64_LENGTHS_BLOCKS = 1024;   /* grid cap of the lengths kernel: rounds past 4 096 groups of 64 payloads */
-constexpr uint32_t KMP_B64_WRITE_BLOCKS = 1024;     /* grid cap of the write kernel: rounds past 4 096 runs */
-constexpr uint32_t KMP_B64_RUN_BYTES = 16384;       /* source bytes a run of the write should come to */
 constexpr uint32_t KMP_B64_LOOKAHEAD = 16;          /* units behind a step that can decide a run: 16 * 16 >= 255 - 1 */
-/* The stage of a step, as in kmp_decode.hip (base64 never yields more bytes than it reads): < 3 072. */
-constexpr uint32_t KMP_B64_STAGE = 3072;
-
-/* The scan workspace of kmp_prep.hip (kmp_extract_ws_bytes), laid out as kmp_decode.hip lays it out: kmp_launch_decode_scan and
- * kmp_launch_decode_index read the decoded lengths where this puts them. */
-uint32_t *b64_dec_len(uint8_t *ws, uint64_t n)
-{
-    const uint64_t nblk = (n + KMP_SCAN_TILE - 1) / KMP_SCAN_TILE;
-    return reinterpret_cast<uint32_t *>(reinterpret_cast<uint64_t *>(ws) + n + nblk) + n;
-}
 
 __device__ __forceinline__ uint32_t alpha_bytes(uint32_t w, uint32_t c62, uint32_t c63)
 {
@@ -63,7 +45,7 @@ __device__ __forceinline__ uint32_t alpha_bytes(uint32_t w, uint32_t c62, uint32
     const uint32_t let = (l + 0x1F1F1F1Fu) & ~(l + 0x05050505u);            /* 0x61 <= b | 0x20 <= 0x7A */
     return ((dig | let) & ~w & 0x80808080u) | eq_bytes(w, c62) | eq_bytes(w, c63);
 }
-__device__ __forceinline__ uint32_t alpha16(b64_u32x4 v, uint32_t c62, uint32_t c63)
+__device__ __forceinline__ uint32_t alpha16(u32x4 v, uint32_t c62, uint32_t c63)
 {
     return bits4(alpha_bytes(v.x, c62, c63)) | bits4(alpha_bytes(v.y, c62, c63)) << 4 | bits4(alpha_bytes(v.z, c62, c63)) << 8 |
            bits4(alpha_bytes(v.w, c62, c63)) << 12;
@@ -80,9 +62,10 @@ __device__ __forceinline__ uint32_t b64_val(uint32_t b, uint32_t c62, uint32_t c
 /* What the step before hands to lane 0: the alphabet run that ends at its last byte, the '=' lane 0 may drop, its last dword. */
 struct StepCarry { uint32_t pre, pad, tail_w; };
 
-/* What a unit comes to: emitted positions, the positions inside decoded runs, those of run offset 0 mod 4, the run offset of the
- * byte before the unit, and the dword before the unit (its last byte is p[i-1] of position 0). */
-struct UnitVerdict { uint32_t emit, dec, zero4, r_before, prev_w; };
+/* What a unit comes to, the Step of kmp_compact_dev.h: the positions inside the payload, the emitted ones, those inside decoded runs, those
+ * of run offset 0 mod 4, the run offset of the byte before the unit (byte() counts it on), the dword before the unit (its last byte is
+ * p[i-1] of position 0), and whether the unit holds a byte of a decoded run. */
+struct UnitVerdict { uint32_t valid, emit, dec, zero4, r_before, prev_w; bool changed; };
 
 /* Keeps the runs of k and more set bits of x (x: 16 bits; k, p = 4 or 8 the largest of the two <= k, sh = k - p are wave-uniform). */
 __device__ __forceinline__ uint32_t runs_of(uint32_t x, uint32_t p, uint32_t sh)
@@ -127,7 +110,7 @@ __device__ __forceinline__ UnitVerdict step_verdict(const Unit &q, const uint8_t
              * payload bytes move in 16-byte loads only.  The units are the ones other lanes hold in the next step's registers; they
              * are read again here so that the steps stay at fixed places and their loads are issued ahead.  off < len63 keeps the
              * load inside the payload's slot: the last unit's slot padding comes with it and is masked off by valid_bits below. */
-            const b64_u32x4 w = *(const volatile __attribute__((address_space(1))) b64_u32x4 *)(uintptr_t)(a63 + 16ull * (1u + lane));
+            const u32x4 w = *(const volatile __attribute__((address_space(1))) u32x4 *)(uintptr_t)(a63 + 16ull * (1u + lane));
             la = alpha16(w, c62, c63) & valid_bits(len63 - off);
             la_on = la == 0xFFFFu && off + 16u < len63;
         }
@@ -183,6 +166,8 @@ __device__ __forceinline__ UnitVerdict step_verdict(const Unit &q, const uint8_t
     cy.tail_w = (uint32_t)__builtin_amdgcn_readlane((int)q.v.w, 63);
 
     UnitVerdict r;
+    r.valid = valid;
+    r.changed = D != 0u;
     r.dec = D;
     r.zero4 = zero4;
     r.emit = valid & ~(D & zero4) & ~cons & 0xFFFFu;
@@ -191,70 +176,34 @@ __device__ __forceinline__ UnitVerdict step_verdict(const Unit &q, const uint8_t
     return r;
 }
 
+/* The transform as lengths_body and write_body take it (kmp_compact_dev.h).  Every step needs its neighbours (a run is maximal), so
+ * there is no cheap way past step_verdict; a step that decodes nothing and drops no '=' is still stored as it is. */
+struct Base64Decode {
+    uint32_t min_run, c62, c63;
+    StepCarry cy;
+    typedef UnitVerdict Step;
+
+    __device__ __forceinline__ void reset() { cy.pre = 0u; cy.pad = 0u; cy.tail_w = 0u; }
+    __device__ __forceinline__ Step step(const Unit &q, const uint8_t *addr, uint32_t lane) { return step_verdict(q, addr, lane, min_run, c62, c63, cy); }
+    __device__ __forceinline__ uint32_t byte(Step &m, const Unit &q, uint32_t i) const
+    {
+        const uint32_t ro = (m.zero4 >> i) & 1u ? 0u : (m.r_before + 1u) & 3u;        /* run offset mod 4 of position i */
+        m.r_before = ro;
+        if (!((m.emit >> i) & 1u)) return 0u;
+        const uint32_t w[5] = {m.prev_w, q.v.x, q.v.y, q.v.z, q.v.w};
+        const uint32_t b = (w[(i + 4u) >> 2] >> (8u * (i & 3u))) & 0xFFu;
+        if (!((m.dec >> i) & 1u)) return b;
+        const uint32_t a = (w[(i + 3u) >> 2] >> (8u * ((i + 3u) & 3u))) & 0xFFu;
+        return ((b64_val(a, c62, c63) << (2u * ro)) | (b64_val(b, c62, c63) >> (6u - 2u * ro))) & 0xFFu;
+    }
+};
+
 __global__ void __launch_bounds__(KMP_BLOCK_THREADS)
 kmp_base64_lengths_kernel(const uint8_t *__restrict__ src, const uint64_t *__restrict__ src_off, const uint32_t *__restrict__ src_len,
                           uint64_t n, uint32_t min_run, uint32_t c62, uint32_t c63, uint32_t only_changed, uint32_t *__restrict__ dec_len,
                           unsigned long long *__restrict__ changed, unsigned long long *__restrict__ stats)
 {
-    __shared__ uint64_t s_ub[KMP_BLOCK_WAVES][KMP_WAVE];
-    __shared__ uint64_t s_src[KMP_BLOCK_WAVES][KMP_WAVE];
-    __shared__ uint32_t s_len[KMP_BLOCK_WAVES][KMP_WAVE];
-    __shared__ uint32_t s_dec[KMP_BLOCK_WAVES][KMP_WAVE];       /* decoded bytes of payload i so far */
-    __shared__ uint32_t s_chg[KMP_BLOCK_WAVES][KMP_WAVE];
-    const uint32_t lane = threadIdx.x & (KMP_WAVE - 1u), wid = threadIdx.x >> 6;
-    const uint64_t n_groups = (n + KMP_WAVE - 1u) / KMP_WAVE;
-    unsigned long long acc_in = 0ull, acc_out = 0ull, acc_chg = 0ull;
-    for (uint64_t r = (uint64_t)blockIdx.x * KMP_BLOCK_WAVES + wid; r < n_groups; r += (uint64_t)gridDim.x * KMP_BLOCK_WAVES) {
-        const uint64_t k = r * KMP_WAVE + lane;
-        const bool in = k < n;
-        const uint32_t len = in ? src_len[k] : 0u;
-        const uint64_t so = in ? src_off[k] : 0ull;
-        const uint64_t units = ((uint64_t)len + 15u) >> 4;
-        const uint64_t incl = wave_incl_scan64(units, lane);
-        const uint64_t total_units = bcast64(incl, KMP_WAVE - 1u);
-        __builtin_amdgcn_wave_barrier();
-        s_ub[wid][lane] = incl - units; s_src[wid][lane] = so; s_len[wid][lane] = len; s_dec[wid][lane] = 0u; s_chg[wid][lane] = 0u;
-        lds_wave_sync();
-        StepCarry cy = {0u, 0u, 0u};
-        for (uint64_t g0 = 0; g0 < total_units; g0 += (uint64_t)KMP_B64_UNROLL * KMP_WAVE) {
-            Unit un[KMP_B64_UNROLL];
-#pragma unroll
-            for (uint32_t u = 0; u < KMP_B64_UNROLL; ++u)
-                load_step<false>(un[u], src, s_ub[wid], s_src[wid], s_len[wid], g0 + (uint64_t)u * KMP_WAVE, total_units, lane);
-#pragma unroll
-            for (uint32_t u = 0; u < KMP_B64_UNROLL; ++u) {
-                const uint64_t gs = g0 + (uint64_t)u * KMP_WAVE;
-                if (gs >= total_units) break;
-                const Unit &q = un[u];
-                const UnitVerdict m = step_verdict(q, src + s_src[wid][q.p] + q.rel, lane, min_run, c62, c63, cy);
-                const uint32_t cnt = __popc(m.emit);
-                /* the step's bytes of each payload, added by the lane that holds the payload's last unit of the step */
-                const uint32_t s_incl = wave_incl_scan(cnt);
-                const uint32_t base = __shfl(s_incl - cnt, (int)q.first);
-                if (q.act) {
-                    if (m.dec) s_chg[wid][q.p] = 1u;
-                    if (lane == KMP_WAVE - 1u || gs + lane + 1u >= total_units || q.rel + 16u >= q.len) s_dec[wid][q.p] += s_incl - base;
-                }
-                lds_wave_sync();
-            }
-        }
-        lds_wave_sync();
-        const uint32_t dec = s_dec[wid][lane];
-        const bool chg = in && s_chg[wid][lane] != 0u;
-        const bool held = in && (chg || !only_changed);
-        const unsigned long long word = __ballot(chg);
-        if (in) dec_len[k] = held ? dec : 0xFFFFFFFFu;
-        if (lane == 0u) changed[r] = word;                      /* one word per wavefront: bits at n and above are 0 */
-        acc_in += held ? len : 0u; acc_out += held ? dec : 0u; acc_chg += chg ? 1u : 0u;
-        __builtin_amdgcn_wave_barrier();
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { acc_in += __shfl_xor(acc_in, o); acc_out += __shfl_xor(acc_out, o); acc_chg += __shfl_xor(acc_chg, o); }
-    if (lane == 0u) {
-        if (acc_in) atomicAdd(stats + 0, acc_in);
-        if (acc_chg) atomicAdd(stats + 1, acc_chg);
-        if (acc_out) atomicAdd(stats + 2, acc_out);
-    }
+    lengths_body(src, src_off, src_len, n, only_changed, dec_len, changed, stats, Base64Decode{min_run, c62, c63, {0u, 0u, 0u}});
 }
 
 template <bool NT>
@@ -262,104 +211,7 @@ __global__ void __launch_bounds__(KMP_BLOCK_THREADS)
 kmp_base64_write_kernel(const uint8_t *__restrict__ src, const uint64_t *__restrict__ new_off, const uint4 *__restrict__ recs, uint64_t n,
                         uint64_t total, uint32_t run, uint32_t min_run, uint32_t c62, uint32_t c63, uint8_t *__restrict__ dst)
 {
-    __shared__ uint64_t s_ub[KMP_BLOCK_WAVES][KMP_WAVE];
-    __shared__ uint64_t s_src[KMP_BLOCK_WAVES][KMP_WAVE];
-    __shared__ uint64_t s_off[KMP_BLOCK_WAVES][KMP_WAVE];       /* new offset of payload i of the run */
-    __shared__ uint32_t s_len[KMP_BLOCK_WAVES][KMP_WAVE];
-    __shared__ b64_u32x4 s_stage[KMP_BLOCK_WAVES][KMP_B64_STAGE / 16u];
-    const uint32_t lane = threadIdx.x & (KMP_WAVE - 1u), wid = threadIdx.x >> 6;
-    b64_u32x4 *stage = s_stage[wid];
-    uint8_t *stage_b = reinterpret_cast<uint8_t *>(stage);
-    for (uint32_t q = lane; q < KMP_B64_STAGE / 16u; q += KMP_WAVE) stage[q] = (b64_u32x4)(0u);
-    const uint64_t n_runs = (n + run - 1u) / run;
-    for (uint64_t r = (uint64_t)blockIdx.x * KMP_BLOCK_WAVES + wid; r < n_runs; r += (uint64_t)gridDim.x * KMP_BLOCK_WAVES) {
-        const uint64_t j = r * run + lane;
-        const bool in = lane < run && j < n;
-        uint64_t off = 0ull, so = 0ull;
-        uint32_t len = 0u;
-        if (in) {
-            const uint4 rec = recs[j];
-            off = new_off[j];
-            so = ((uint64_t)rec.y << 32) | rec.x;
-            len = rec.z;
-            if (rec.w == 0u && off + 16u <= total) store_unit<NT>(dst + off, (b64_u32x4)(0u));      /* an empty payload's zero slot */
-        }
-        const uint64_t units = ((uint64_t)len + 15u) >> 4;
-        const uint64_t incl = wave_incl_scan64(units, lane);
-        const uint64_t total_units = bcast64(incl, KMP_WAVE - 1u);
-        __builtin_amdgcn_wave_barrier();
-        s_ub[wid][lane] = incl - units; s_src[wid][lane] = so; s_off[wid][lane] = off; s_len[wid][lane] = len;
-        lds_wave_sync();
-        StepCarry cy = {0u, 0u, 0u};
-        uint32_t carry = 0u;                                    /* decoded bytes of the payload that runs on into the step, before it */
-        for (uint64_t g0 = 0; g0 < total_units; g0 += (uint64_t)KMP_B64_UNROLL * KMP_WAVE) {
-            Unit un[KMP_B64_UNROLL];
-#pragma unroll
-            for (uint32_t u = 0; u < KMP_B64_UNROLL; ++u)
-                load_step<NT>(un[u], src, s_ub[wid], s_src[wid], s_len[wid], g0 + (uint64_t)u * KMP_WAVE, total_units, lane);
-#pragma unroll
-            for (uint32_t u = 0; u < KMP_B64_UNROLL; ++u) {
-                const uint64_t gs = g0 + (uint64_t)u * KMP_WAVE;
-                if (gs >= total_units) break;
-                const Unit &q = un[u];
-                const uint32_t last_lane = (uint32_t)min((uint64_t)(KMP_WAVE - 1u), total_units - 1u - gs);
-                const bool ends = q.rel + 16u >= q.len;         /* the payload's last unit */
-                const uint64_t doff = s_off[wid][q.p];
-                const UnitVerdict m = step_verdict(q, src + s_src[wid][q.p] + q.rel, lane, min_run, c62, c63, cy);
-                const uint32_t valid = q.act ? valid_bits(q.len - q.rel) : 0u;
-                uint32_t next_carry;
-                if (!__any(m.dec | (m.emit ^ valid)) && (carry & 15u) == 0u) {
-                    /* no byte of a decoded run (a run's last bytes may all yield one), no '=' dropped, and 16-byte aligned: the units
-                     * go out as they are, tails cleared */
-                    const uint32_t before = q.started ? carry + 16u * lane : q.rel;
-                    const uint64_t d = doff + before;
-                    if (q.act && d + 16u <= total) store_unit<NT>(dst + d, keep_bytes(q.v, q.len - q.rel));
-                    next_carry = ends ? 0u : before + 16u;
-                } else {
-                    const uint32_t cnt = __popc(m.emit);
-                    const uint32_t s_incl = wave_incl_scan(cnt);
-                    const uint32_t base = __shfl(s_incl - cnt, (int)q.first);
-                    const uint32_t before = s_incl - cnt - base + (q.started ? carry : 0u);
-                    const uint64_t out = doff + before;
-                    const uint64_t a0 = bcast64(out, 0u) & ~15ull;                  /* the stage's place in dst */
-                    uint32_t pos = q.act ? (uint32_t)(out - a0) : 0u;
-                    const uint32_t w[5] = {m.prev_w, q.v.x, q.v.y, q.v.z, q.v.w};
-                    uint32_t ro = m.r_before;                                       /* run offset mod 4 of the byte before */
-#pragma unroll
-                    for (uint32_t i = 0; i < 16u; ++i) {
-                        ro = (m.zero4 >> i) & 1u ? 0u : (ro + 1u) & 3u;
-                        if ((m.emit >> i) & 1u) {
-                            uint32_t b = (w[(i + 4u) >> 2] >> (8u * (i & 3u))) & 0xFFu;
-                            if ((m.dec >> i) & 1u) {
-                                const uint32_t a = (w[(i + 3u) >> 2] >> (8u * ((i + 3u) & 3u))) & 0xFFu;
-                                b = ((b64_val(a, c62, c63) << (2u * ro)) | (b64_val(b, c62, c63) >> (6u - 2u * ro))) & 0xFFu;
-                            }
-                            if (pos < KMP_B64_STAGE) stage_b[pos] = (uint8_t)b;
-                            ++pos;
-                        }
-                    }
-                    const uint32_t end_l = ends ? (pos + 15u) & ~15u : pos;          /* a payload's end completes its slot with the stage's 0x00 */
-                    const uint32_t end = min((uint32_t)__shfl(end_l, (int)last_lane), KMP_B64_STAGE);
-                    const uint32_t n_full = end >> 4;
-                    lds_wave_sync();
-                    for (uint32_t t = lane; t < n_full; t += KMP_WAVE) {
-                        const uint64_t d = a0 + 16ull * t;
-                        if (d + 16u <= total) store_unit<NT>(dst + d, stage[t]);
-                    }
-                    const bool rest = (end & 15u) != 0u && n_full < KMP_B64_STAGE / 16u;
-                    const b64_u32x4 part = rest ? stage[n_full] : (b64_u32x4)(0u);
-                    lds_wave_sync();
-                    for (uint32_t t = lane; t < (end + 15u) >> 4; t += KMP_WAVE) stage[t] = (b64_u32x4)(0u);
-                    lds_wave_sync();
-                    if (rest && lane == 0u) stage[0] = part;                         /* the next step begins inside this unit */
-                    lds_wave_sync();
-                    next_carry = ends ? 0u : before + cnt;
-                }
-                carry = __builtin_amdgcn_readfirstlane(__shfl(next_carry, (int)last_lane));
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
+    write_body<NT>(src, new_off, recs, n, total, run, dst, Base64Decode{min_run, c62, c63, {0u, 0u, 0u}});
 }
 
 }  // namespace
@@ -370,11 +222,9 @@ hipError_t kmp_launch_base64_lengths(const uint8_t *src_arena, const uint64_t *s
                                      hipStream_t st)
 {
     if (n == 0) return hipSuccess;
-    const uint64_t groups = (n + KMP_WAVE - 1) / KMP_WAVE;
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>((groups + KMP_BLOCK_WAVES - 1) / KMP_BLOCK_WAVES, KMP_B64_LENGTHS_BLOCKS);
     const uint32_t c62 = urlsafe ? 0x2D2D2D2Du : 0x2B2B2B2Bu, c63 = urlsafe ? 0x5F5F5F5Fu : 0x2F2F2F2Fu;
-    hipLaunchKernelGGL(kmp_base64_lengths_kernel, dim3(blocks), dim3(KMP_BLOCK_THREADS), 0, st, src_arena, src_off, src_len, n, min_run, c62, c63,
-                       only_changed ? 1u : 0u, b64_dec_len(ws, n), changed, stats);
+    hipLaunchKernelGGL(kmp_base64_lengths_kernel, dim3(kmp_group_blocks(n)), dim3(KMP_BLOCK_THREADS), 0, st, src_arena, src_off, src_len, n, min_run,
+                       c62, c63, only_changed ? 1u : 0u, kmp_compact_ws(ws, n).len, changed, stats);
     return hipGetLastError();
 }
 
@@ -382,18 +232,9 @@ hipError_t kmp_launch_base64_write(const uint8_t *src_arena, const uint64_t *pkt
                                    uint64_t total_bytes, uint32_t min_run, bool urlsafe, uint8_t *arena, bool nontemporal, hipStream_t st)
 {
     if (n_dst == 0) return hipSuccess;
-    /* payloads per run: what brings an average run to KMP_B64_RUN_BYTES of source, a power of two up to 64 */
-    const uint64_t avg = std::max<uint64_t>(std::max(bytes_in, total_bytes) / n_dst, 16);
-    uint32_t run = KMP_WAVE;
-    while (run > 1u && (uint64_t)run * avg > KMP_B64_RUN_BYTES) run >>= 1;
-    const uint64_t n_runs = (n_dst + run - 1) / run;
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_runs + KMP_BLOCK_WAVES - 1) / KMP_BLOCK_WAVES, KMP_B64_WRITE_BLOCKS);
+    const kmp_run_shape rs = kmp_run_shape_of(n_dst, bytes_in > total_bytes ? bytes_in : total_bytes);       /* a run's SOURCE bytes count as well */
     const uint32_t c62 = urlsafe ? 0x2D2D2D2Du : 0x2B2B2B2Bu, c63 = urlsafe ? 0x5F5F5F5Fu : 0x2F2F2F2Fu;
-    if (nontemporal)
-        hipLaunchKernelGGL(kmp_base64_write_kernel<true>, dim3(blocks), dim3(KMP_BLOCK_THREADS), 0, st, src_arena, pkt_off, (const uint4 *)recs,
-                           n_dst, total_bytes, run, min_run, c62, c63, arena);
-    else
-        hipLaunchKernelGGL(kmp_base64_write_kernel<false>, dim3(blocks), dim3(KMP_BLOCK_THREADS), 0, st, src_arena, pkt_off, (const uint4 *)recs,
-                           n_dst, total_bytes, run, min_run, c62, c63, arena);
+    hipLaunchKernelGGL(nontemporal ? kmp_base64_write_kernel<true> : kmp_base64_write_kernel<false>, dim3(rs.blocks), dim3(KMP_BLOCK_THREADS), 0, st,
+                       src_arena, pkt_off, (const uint4 *)recs, n_dst, total_bytes, rs.run, min_run, c62, c63, arena);
     return hipGetLastError();
 }

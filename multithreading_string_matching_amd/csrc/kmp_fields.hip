@@ -5,8 +5,7 @@
  *   kmp_http_locate_kernel      one 32-byte kmpgpu_http_span per payload; requests, responses, blank lines and the bytes looked at
  *   kmp_fields_lengths_kernel   from the spans: field_len[k] of the asked field, or 0xFFFFFFFF ("not in dst") for an absent one under
  *                               KMPGPU_FIELDS_ONLY_PRESENT; the present bitmap, one plain store per word; the stats
- *   kmp_scan_local_kernel, kmp_scan_totals_kernel   of kmp_prep.hip, through kmp_launch_repack_phase1: slot offsets and payload numbers
- *                               of dst's payloads, totals = {packed bytes, payloads}
+ *   kmp_scan_local_kernel, kmp_scan_totals_kernel   of kmp_prep.hip, through kmp_launch_compact_scan
  *   kmp_fields_index_kernel     the new index, and per payload of dst the 16-byte record {source byte address of the field, length}
  *   kmp_fields_gather_kernel    the bytes
  *
@@ -20,10 +19,11 @@
  * two bytes.  A byte at or behind the payload's end has no bit in any mask.  A payload is left at the step that holds its blank line
  * (one step for a typical request), or the end of its start line where that line makes it no message after all.
  *
- * The gather is kmp_seam_gather_kernel with one piece per payload: a wavefront takes a run of up to 64 payloads of dst, deals the run's
- * 16-byte units to the lanes in order and builds each from the one or two ALIGNED source units that hold its bytes (fetch_piece,
- * kmp_piece_dev.h), cleared behind the field's end in registers.  An aligned unit that holds a byte of a payload lies inside that
- * payload's slot, so no load leaves the slot; a field that starts on a multiple of 16 (METHOD always does) is one load per unit.
+ * The lengths kernel's tail, the index and the gather's shape are the compacting skeleton's (group_tail, index_body, gather_runs:
+ * kmp_compact_dev.h).  The gather's own part is kmp_seam_gather_kernel's with one piece per payload: a destination unit is
+ * built from the one or two ALIGNED source units that hold its bytes (fetch_piece, kmp_piece_dev.h), cleared behind the field's end in
+ * registers.  An aligned unit that holds a byte of a payload lies inside that payload's slot, so no load leaves the slot; a field that
+ * starts on a multiple of 16 (METHOD always does) is one load per unit.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,67 +34,31 @@
 #include "kmp_device.h"
 #include "kmp_launch.h"
 #include "kmp_piece_dev.h"
+#include "kmp_compact_dev.h"
 
 namespace {
 
+using namespace kmp_unit;     /* kmp_compact_dev.h: group_tail, index_body, gather_runs; kmp_unit_dev.h: the unit, byte classes */
 using kmp_piece::fetch_piece;
-using kmp_piece::load_unit;
-using kmp_piece::store_unit;
-typedef kmp_piece::u32x4 fld_u32x4;
 
 constexpr uint32_t FLD_NONE = 0xFFFFFFFFu;
 constexpr uint32_t FLD_STEP = 1024u;             /* bytes of a payload the locate takes per step: 64 lanes x 16 */
 /* grid cap of the locate: rounds past 8 192 groups of 64 payloads.  8 wavefronts per SIMD: a wavefront has one step of 1 KiB in flight and
  * waits for it before it knows where to go on, so it is the number of wavefronts that hides the latency */
 constexpr uint32_t FLD_LOCATE_BLOCKS = 2048;
-constexpr uint32_t FLD_LENGTHS_BLOCKS = 1024;    /* grid cap of the lengths kernel: rounds past 4 096 groups of 64 payloads */
-constexpr uint32_t FLD_INDEX_BLOCKS = 1024;      /* grid cap of the index kernel: rounds past 262 144 payloads */
-constexpr uint32_t FLD_GATHER_BLOCKS = 1024;     /* grid cap of the gather: rounds past 4 096 runs */
-constexpr uint32_t FLD_RUN_BYTES = 16384;        /* bytes a run of the gather should come to */
-constexpr uint32_t FLD_UNROLL = 2;               /* destination units a lane of the gather has in flight (up to two loads each) */
 
-/* The scan workspace of kmp_prep.hip (kmp_extract_ws_bytes), as kmp_decode.hip uses it: the field lengths take plen's place. */
-struct FieldsWs {
-    uint64_t *loc_off, *blk_bytes;
-    uint32_t *fld_len, *loc_idx, *blk_cnt;
-};
-FieldsWs fields_ws(uint8_t *ws, uint64_t n)
-{
-    const uint64_t nblk = (n + KMP_SCAN_TILE - 1) / KMP_SCAN_TILE;
-    FieldsWs w;
-    w.loc_off = reinterpret_cast<uint64_t *>(ws);
-    w.blk_bytes = w.loc_off + n;
-    w.fld_len = reinterpret_cast<uint32_t *>(w.blk_bytes + nblk) + n;
-    w.loc_idx = w.fld_len + n;
-    w.blk_cnt = w.loc_idx + n;
-    return w;
-}
-
-/* ---- byte classes of a dword, 0x80 in every byte of the class, and those four bits gathered into bits 0..3 ---- */
-__device__ __forceinline__ uint32_t eq_bytes(uint32_t w, uint32_t c4)
-{
-    const uint32_t x = w ^ c4;
-    return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);
-}
+/* ---- byte classes of a dword, 0x80 in every byte of the class (eq_bytes, bits4, eq16: kmp_unit_dev.h) ---- */
 __device__ __forceinline__ uint32_t upper_bytes(uint32_t w)
 {
     const uint32_t lo7 = w & 0x7F7F7F7Fu;
     return (lo7 + 0x3F3F3F3Fu) & ~(lo7 + 0x25252525u) & ~w & 0x80808080u;        /* 0x41 <= b <= 0x5A */
 }
-__device__ __forceinline__ uint32_t bits4(uint32_t t) { return ((t >> 7) * 0x10204080u) >> 28; }
-__device__ __forceinline__ uint32_t eq16(fld_u32x4 v, uint32_t c4)
-{
-    return bits4(eq_bytes(v.x, c4)) | bits4(eq_bytes(v.y, c4)) << 4 | bits4(eq_bytes(v.z, c4)) << 8 | bits4(eq_bytes(v.w, c4)) << 12;
-}
-__device__ __forceinline__ uint32_t upper16(fld_u32x4 v)
+__device__ __forceinline__ uint32_t upper16(u32x4 v)
 {
     return bits4(upper_bytes(v.x)) | bits4(upper_bytes(v.y)) << 4 | bits4(upper_bytes(v.z)) << 8 | bits4(upper_bytes(v.w)) << 12;
 }
 constexpr uint32_t LF4 = 0x0A0A0A0Au, CR4 = 0x0D0D0D0Du, SP4 = 0x20202020u;
 constexpr uint32_t HTTP4 = 0x50545448u;          /* "HTTP", little-endian */
-
-/* the positions of a unit that lie inside a payload of which `left` bytes remain at the unit's start */
-__device__ __forceinline__ uint32_t valid_bits(uint64_t left) { return left >= 16u ? 0xFFFFu : (1u << (uint32_t)left) - 1u; }
 
 /* The smallest position of a step (lane l holds the positions 16 l .. 16 l + 15 as the bits of m16) that has its bit set; the same
  * value in every lane.  All 64 lanes take part. */
@@ -125,7 +89,7 @@ kmp_http_locate_kernel(const uint8_t *__restrict__ src, const uint64_t *__restri
         const bool in = k < n;
         const uint32_t L = in ? src_len[k] : 0u;
         const uint64_t so = in ? src_off[k] : 0ull;
-        fld_u32x4 v0 = (fld_u32x4)(0u);
+        u32x4 v0 = (u32x4)(0u);
         if (L) v0 = load_unit<false>(src + so);
         const uint32_t valid0 = valid_bits(L);
         const bool resp = L >= 5u && v0.x == HTTP4 && (v0.y & 0xFFu) == 0x2Fu;
@@ -152,9 +116,9 @@ kmp_http_locate_kernel(const uint8_t *__restrict__ src, const uint64_t *__restri
             for (uint64_t sb = 0; sb < Lq; sb += FLD_STEP) {
                 const uint64_t pos = sb + 16u * lane;
                 const bool act = pos < Lq;
-                fld_u32x4 v = (fld_u32x4)(0u);
+                u32x4 v = (u32x4)(0u);
                 if (act) v = load_unit<false>(p + pos);
-                const uint32_t valid = act ? valid_bits((uint64_t)Lq - pos) : 0u;
+                const uint32_t valid = act ? valid_bits((uint32_t)min((uint64_t)Lq - pos, (uint64_t)16u)) : 0u;
                 const uint32_t lf = eq16(v, LF4) & valid, cr = eq16(v, CR4) & valid;
                 scanned = (uint32_t)min((uint64_t)Lq, sb + FLD_STEP);
                 if (e == FLD_NONE) {
@@ -188,8 +152,8 @@ kmp_http_locate_kernel(const uint8_t *__restrict__ src, const uint64_t *__restri
                 if (lane == KMP_WAVE - 1u) {
                     nlf = 0u; ncr = 0u;
                     if ((lf & 0xC000u) && pos + 16u < Lq) {
-                        const fld_u32x4 nv = load_unit<false>(p + pos + 16u);
-                        const uint32_t nvalid = valid_bits((uint64_t)Lq - pos - 16u);
+                        const u32x4 nv = load_unit<false>(p + pos + 16u);
+                        const uint32_t nvalid = valid_bits((uint32_t)min((uint64_t)Lq - pos - 16u, (uint64_t)16u));
                         nlf = eq16(nv, LF4) & nvalid; ncr = eq16(nv, CR4) & nvalid;
                     }
                 }
@@ -267,26 +231,16 @@ kmp_fields_lengths_kernel(const uint4 *__restrict__ spans, const uint32_t *__res
 {
     const uint32_t lane = threadIdx.x & (KMP_WAVE - 1u), wid = threadIdx.x >> 6;
     const uint64_t n_groups = (n + KMP_WAVE - 1u) / KMP_WAVE;
-    unsigned long long acc_in = 0ull, acc_out = 0ull, acc_pres = 0ull;
+    GroupSums acc = {0ull, 0ull, 0ull};
     for (uint64_t r = (uint64_t)blockIdx.x * KMP_BLOCK_WAVES + wid; r < n_groups; r += (uint64_t)gridDim.x * KMP_BLOCK_WAVES) {
         const uint64_t k = r * KMP_WAVE + lane;
         const bool in = k < n;
         uint32_t off = 0u, len = 0u;
         bool pres = false;
         if (in) pres = field_of(spans[2u * k], spans[2u * k + 1u], field, &off, &len);
-        const bool held = in && (pres || !only_present);
-        const unsigned long long word = __ballot(pres);
-        if (in) fld_len[k] = held ? len : 0xFFFFFFFFu;
-        if (lane == 0u) present[r] = word;                      /* one word per wavefront: bits at n and above are 0 */
-        acc_in += held ? src_len[k] : 0u; acc_out += held ? len : 0u; acc_pres += pres ? 1u : 0u;
+        group_tail(acc, in, k, r, lane, pres, only_present != 0u, in ? src_len[k] : 0u, len, fld_len, present);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { acc_in += __shfl_xor(acc_in, o); acc_out += __shfl_xor(acc_out, o); acc_pres += __shfl_xor(acc_pres, o); }
-    if (lane == 0u) {
-        if (acc_in) atomicAdd(stats + 0, acc_in);
-        if (acc_pres) atomicAdd(stats + 1, acc_pres);
-        if (acc_out) atomicAdd(stats + 2, acc_out);
-    }
+    group_sums_flush(acc, lane, stats);
 }
 
 /* Payload k of the source is payload j of dst: its slot in the new arena, the field's length, and where the field's bytes lie. */
@@ -296,18 +250,12 @@ kmp_fields_index_kernel(const uint4 *__restrict__ spans, const uint64_t *__restr
                         const uint32_t *__restrict__ blk_cnt, uint64_t n, uint64_t *__restrict__ pkt_off, uint32_t *__restrict__ pkt_len,
                         uint4 *__restrict__ recs)
 {
-    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t l = fld_len[k];
-        if (l == 0xFFFFFFFFu) continue;
-        const uint64_t blk = k / KMP_SCAN_TILE;
-        const uint64_t j = (uint64_t)blk_cnt[blk] + loc_idx[k];
+    index_body(fld_len, loc_off, loc_idx, blk_bytes, blk_cnt, n, pkt_off, pkt_len, recs, [&](uint64_t k, uint32_t l) {
         uint32_t off, len;
         field_of(spans[2u * k], spans[2u * k + 1u], field, &off, &len);
         const uint64_t fs = src_off[k] + off;
-        pkt_off[j] = blk_bytes[blk] + loc_off[k];
-        pkt_len[j] = l;
-        recs[j] = make_uint4((uint32_t)fs, (uint32_t)(fs >> 32), l, 0u);
-    }
+        return make_uint4((uint32_t)fs, (uint32_t)(fs >> 32), l, 0u);
+    });
 }
 
 template <bool NT>
@@ -315,59 +263,24 @@ __global__ void __launch_bounds__(KMP_BLOCK_THREADS)
 kmp_fields_gather_kernel(const uint8_t *__restrict__ src, const uint64_t *__restrict__ new_off, const uint4 *__restrict__ recs, uint64_t n,
                          uint64_t total, uint32_t run, uint8_t *__restrict__ dst)
 {
-    __shared__ uint64_t s_off[KMP_BLOCK_WAVES][KMP_WAVE];          /* new offset of payload i of the run; ~0 behind the run's end */
-    __shared__ uint64_t s_src[KMP_BLOCK_WAVES][KMP_WAVE];          /* where its field starts in src */
+    __shared__ uint64_t s_src[KMP_BLOCK_WAVES][KMP_WAVE];          /* where payload i's field starts in src */
     __shared__ uint32_t s_len[KMP_BLOCK_WAVES][KMP_WAVE];
     const uint32_t lane = threadIdx.x & (KMP_WAVE - 1u), wid = threadIdx.x >> 6;
-    const uint64_t n_runs = (n + run - 1u) / run;
-    for (uint64_t r = (uint64_t)blockIdx.x * KMP_BLOCK_WAVES + wid; r < n_runs; r += (uint64_t)gridDim.x * KMP_BLOCK_WAVES) {
-        const uint64_t j0 = r * run, j = j0 + lane;
-        uint64_t off = ~0ull, fs = 0ull;
-        uint32_t len = 0u;
-        if (lane < run && j < n) {
-            const uint4 a = recs[j];
-            off = new_off[j];
-            fs = ((uint64_t)a.y << 32) | a.x; len = a.z;
-        }
-        /* the wavefront's own LDS: its DS instructions execute in order, the barriers keep the compiler from moving them */
-        __builtin_amdgcn_wave_barrier();
-        s_off[wid][lane] = off; s_src[wid][lane] = fs; s_len[wid][lane] = len;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const uint64_t base = new_off[j0];
-        const uint64_t end = (j0 + run < n) ? new_off[j0 + run] : total;
-        for (uint64_t d0 = base + (uint64_t)lane * 16u; d0 - lane * 16u < end; d0 += (uint64_t)FLD_UNROLL * KMP_WAVE * 16u) {
-            fld_u32x4 v[FLD_UNROLL];
-#pragma unroll
-            for (uint32_t u = 0; u < FLD_UNROLL; ++u) {
-                const uint64_t d = d0 + (uint64_t)u * KMP_WAVE * 16u;
-                v[u] = (fld_u32x4)(0u);
-                if (d < end) {
-                    uint32_t p = 0u;                                 /* the last payload of the run that starts at or before d */
-#pragma unroll
-                    for (uint32_t step = KMP_WAVE / 2u; step; step >>= 1)
-                        if (s_off[wid][p + step] <= d) p += step;
-                    const uint64_t rel64 = d - s_off[wid][p];
-                    const uint32_t F = s_len[wid][p];
-                    if (rel64 < (uint64_t)F) {                       /* (an empty payload's slot: zeros) */
-                        const uint64_t f0 = s_src[wid][p];
-                        const int32_t fa = (int32_t)(f0 & 15u);      /* the field in the coordinates of the aligned unit it starts in */
-                        /* the unit's place in the field, from the aligned unit at or before it so that the offsets stay small */
-                        const uint64_t ua = (f0 - (uint32_t)fa) + rel64;            /* 16-byte aligned: the first source unit that holds a byte of it */
-                        const uint64_t left = (uint64_t)F - rel64;
-                        v[u] = fetch_piece<NT>(src + ua, fa, fa, fa + (int32_t)min(left, (uint64_t)16u));
-                    }
-                }
-            }
-#pragma unroll
-            for (uint32_t u = 0; u < FLD_UNROLL; ++u) {
-                const uint64_t d = d0 + (uint64_t)u * KMP_WAVE * 16u;
-                if (d < end) store_unit<NT>(dst + d, v[u]);
-            }
-        }
-        __builtin_amdgcn_wave_barrier();                             /* the next run's table goes over this one */
-    }
+    gather_runs<NT, 2>(new_off, n, total, run, dst,
+        [&](uint64_t j, bool in) { return in ? recs[j] : make_uint4(0u, 0u, 0u, 0u); },
+        [&](uint4 a) {
+            s_src[wid][lane] = ((uint64_t)a.y << 32) | a.x; s_len[wid][lane] = a.z;
+        },
+        [&](uint32_t p, uint64_t rel64, uint32_t &) {
+            const uint32_t F = s_len[wid][p];
+            if (rel64 >= (uint64_t)F) return (u32x4)(0u);            /* (an empty payload's slot: zeros) */
+            const uint64_t f0 = s_src[wid][p];
+            const int32_t fa = (int32_t)(f0 & 15u);                  /* the field in the coordinates of the aligned unit it starts in */
+            /* the unit's place in the field, from the aligned unit at or before it so that the offsets stay small */
+            const uint64_t ua = (f0 - (uint32_t)fa) + rel64;         /* 16-byte aligned: the first source unit that holds a byte of it */
+            const uint64_t left = (uint64_t)F - rel64;
+            return fetch_piece<NT>(src + ua, fa, fa, fa + (int32_t)min(left, (uint64_t)16u));
+        });
 }
 
 }  // namespace
@@ -388,28 +301,18 @@ hipError_t kmp_launch_fields_lengths(const void *spans, const uint32_t *src_len,
                                      unsigned long long *present, unsigned long long *stats, hipStream_t st)
 {
     if (n == 0) return hipSuccess;
-    const FieldsWs w = fields_ws(ws, n);
-    const uint64_t groups = (n + KMP_WAVE - 1) / KMP_WAVE;
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>((groups + KMP_BLOCK_WAVES - 1) / KMP_BLOCK_WAVES, FLD_LENGTHS_BLOCKS);
-    hipLaunchKernelGGL(kmp_fields_lengths_kernel, dim3(blocks), dim3(KMP_BLOCK_THREADS), 0, st, reinterpret_cast<const uint4 *>(spans), src_len, n,
-                       (uint32_t)field, only_present ? 1u : 0u, w.fld_len, present, stats);
+    hipLaunchKernelGGL(kmp_fields_lengths_kernel, dim3(kmp_group_blocks(n)), dim3(KMP_BLOCK_THREADS), 0, st, reinterpret_cast<const uint4 *>(spans), src_len, n,
+                       (uint32_t)field, only_present ? 1u : 0u, kmp_compact_ws(ws, n).len, present, stats);
     return hipGetLastError();
-}
-
-hipError_t kmp_launch_fields_scan(uint64_t n, uint8_t *ws, unsigned long long *totals, hipStream_t st)
-{
-    if (n == 0) return hipSuccess;
-    return kmp_launch_repack_phase1(fields_ws(ws, n).fld_len, n, ws, totals, st);       /* kmp_scan_local_kernel + kmp_scan_totals_kernel */
 }
 
 hipError_t kmp_launch_fields_index(const void *spans, const uint64_t *src_off, uint64_t n, int field, uint8_t *ws, uint64_t n_dst,
                                    uint64_t *pkt_off, uint32_t *pkt_len, void *recs, hipStream_t st)
 {
     if (n == 0 || n_dst == 0) return hipSuccess;
-    const FieldsWs w = fields_ws(ws, n);
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + KMP_BLOCK_THREADS - 1) / KMP_BLOCK_THREADS, FLD_INDEX_BLOCKS);
-    hipLaunchKernelGGL(kmp_fields_index_kernel, dim3(blocks), dim3(KMP_BLOCK_THREADS), 0, st, reinterpret_cast<const uint4 *>(spans), src_off,
-                       (uint32_t)field, w.fld_len, w.loc_off, w.loc_idx, w.blk_bytes, w.blk_cnt, n, pkt_off, pkt_len, reinterpret_cast<uint4 *>(recs));
+    const kmp_compact_view w = kmp_compact_ws(ws, n);
+    hipLaunchKernelGGL(kmp_fields_index_kernel, dim3(kmp_item_blocks(n)), dim3(KMP_BLOCK_THREADS), 0, st, reinterpret_cast<const uint4 *>(spans), src_off,
+                       (uint32_t)field, w.len, w.loc_off, w.loc_idx, w.blk_bytes, w.blk_cnt, n, pkt_off, pkt_len, reinterpret_cast<uint4 *>(recs));
     return hipGetLastError();
 }
 
@@ -417,17 +320,8 @@ hipError_t kmp_launch_fields_gather(const uint8_t *src_arena, const uint64_t *pk
                                     uint8_t *arena, bool nontemporal, hipStream_t st)
 {
     if (n_dst == 0) return hipSuccess;
-    /* payloads per run: what brings an average run to FLD_RUN_BYTES, a power of two up to 64 */
-    const uint64_t avg = std::max<uint64_t>(total_bytes / n_dst, 16);
-    uint32_t run = KMP_WAVE;
-    while (run > 1u && (uint64_t)run * avg > FLD_RUN_BYTES) run >>= 1;
-    const uint64_t n_runs = (n_dst + run - 1) / run;
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_runs + KMP_BLOCK_WAVES - 1) / KMP_BLOCK_WAVES, FLD_GATHER_BLOCKS);
-    if (nontemporal)
-        hipLaunchKernelGGL(kmp_fields_gather_kernel<true>, dim3(blocks), dim3(KMP_BLOCK_THREADS), 0, st, src_arena, pkt_off, (const uint4 *)recs,
-                           n_dst, total_bytes, run, arena);
-    else
-        hipLaunchKernelGGL(kmp_fields_gather_kernel<false>, dim3(blocks), dim3(KMP_BLOCK_THREADS), 0, st, src_arena, pkt_off, (const uint4 *)recs,
-                           n_dst, total_bytes, run, arena);
+    const kmp_run_shape rs = kmp_run_shape_of(n_dst, total_bytes);
+    hipLaunchKernelGGL(nontemporal ? kmp_fields_gather_kernel<true> : kmp_fields_gather_kernel<false>, dim3(rs.blocks), dim3(KMP_BLOCK_THREADS), 0, st,
+                       src_arena, pkt_off, (const uint4 *)recs, n_dst, total_bytes, rs.run, arena);
     return hipGetLastError();
 }

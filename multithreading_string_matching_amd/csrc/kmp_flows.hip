@@ -6,7 +6,7 @@
  *                             first[slot] = the lowest payload index of the slot's flow
  *   kmp_flows_firsts_kernel   is_first[k] = (first[slot_of[k]] == k), written as the "length" the scan kernels of kmp_prep.hip take (16 for
  *                             a first payload, 0xFFFFFFFF "rejected" otherwise), as kmp_alerts.hip writes its counts
- *   kmp_scan_local_kernel, kmp_scan_totals_kernel   of kmp_prep.hip, through kmp_launch_repack_phase1: a first payload's rank among the
+ *   kmp_scan_local_kernel, kmp_scan_totals_kernel   of kmp_prep.hip, through kmp_launch_compact_scan: a first payload's rank among the
  *                             first payloads = its flow's id, totals[1] = n_flows
  *   kmp_flows_number_kernel   a first payload writes its flow's id over its slot of the table and opens the flow's record
  *   kmp_flows_assign_kernel   flow_of[k] = table[slot_of[k]] (in place, over slot_of); n_packets, payload_bytes, last_packet of the records
@@ -63,20 +63,6 @@ __device__ __forceinline__ uint64_t wave_or64(uint64_t v)
 #pragma unroll
     for (uint32_t s = 32u; s; s >>= 1) v |= shfl_xor64(v, s);
     return v;
-}
-
-/* The scan workspace of kmp_prep.hip (kmp_extract_ws_bytes), as kmp_alerts.hip uses it: is_first takes plen's place. */
-struct FlowWs {
-    uint32_t *first_len, *loc_idx, *blk_cnt;
-};
-FlowWs flow_ws(uint8_t *ws, uint64_t n)
-{
-    const uint64_t nblk = (n + KMP_SCAN_TILE - 1) / KMP_SCAN_TILE;
-    FlowWs w;
-    w.first_len = reinterpret_cast<uint32_t *>(reinterpret_cast<uint64_t *>(ws) + n + nblk) + n;
-    w.loc_idx = w.first_len + n;
-    w.blk_cnt = w.loc_idx + n;
-    return w;
 }
 
 __global__ void __launch_bounds__(FLOW_THREADS)
@@ -266,13 +252,8 @@ hipError_t kmp_launch_flows_firsts(const uint32_t *first, const uint32_t *slot_o
     uint32_t blocks;
     if (n_pkts == 0) return hipSuccess;
     if (!flow_grid(n_pkts, &blocks)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(kmp_flows_firsts_kernel, dim3(blocks), dim3(FLOW_THREADS), 0, st, first, slot_of, n_pkts, flow_ws(ws, n_pkts).first_len);
+    hipLaunchKernelGGL(kmp_flows_firsts_kernel, dim3(blocks), dim3(FLOW_THREADS), 0, st, first, slot_of, n_pkts, kmp_compact_ws(ws, n_pkts).len);
     return hipGetLastError();
-}
-
-hipError_t kmp_launch_flows_scan(uint64_t n_pkts, uint8_t *ws, unsigned long long *totals, hipStream_t st)
-{
-    return kmp_launch_repack_phase1(flow_ws(ws, n_pkts).first_len, n_pkts, ws, totals, st);      /* kmp_scan_local_kernel + kmp_scan_totals_kernel */
 }
 
 hipError_t kmp_launch_flows_number(const void *meta, uint64_t n_pkts, uint8_t *ws, const uint32_t *slot_of, uint32_t *table, void *recs,
@@ -281,9 +262,9 @@ hipError_t kmp_launch_flows_number(const void *meta, uint64_t n_pkts, uint8_t *w
     uint32_t blocks;
     if (n_pkts == 0) return hipSuccess;
     if (!flow_grid(n_pkts, &blocks)) return hipErrorInvalidValue;
-    const FlowWs w = flow_ws(ws, n_pkts);
+    const kmp_compact_view w = kmp_compact_ws(ws, n_pkts);
     hipLaunchKernelGGL(kmp_flows_number_kernel, dim3(blocks), dim3(FLOW_THREADS), 0, st, reinterpret_cast<const uint4 *>(meta), n_pkts,
-                       w.first_len, w.loc_idx, w.blk_cnt, slot_of, table, reinterpret_cast<uint4 *>(recs));
+                       w.len, w.loc_idx, w.blk_cnt, slot_of, table, reinterpret_cast<uint4 *>(recs));
     return hipGetLastError();
 }
 

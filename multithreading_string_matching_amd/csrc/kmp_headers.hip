@@ -113,21 +113,8 @@ kmp_headers_kernel(const uint4 *__restrict__ meta, const uint32_t *__restrict__ 
     if (lane == 0u && any_acc != 0ull) atomicOr(any + j, any_acc);       /* (a set bit: j < W) */
 }
 
-/* The scan workspace of kmp_prep.hip (kmp_extract_ws_bytes): loc_off[n], blk_bytes[nblk], then the 32-bit arrays poff[n], plen[n],
- * loc_idx[n], blk_cnt[nblk].  plen[i] == 0xFFFFFFFF: frame (or payload) i was rejected (not selected); otherwise it is payload
+/* The scan workspace (kmp_compact_ws, kmp_launch.h) after its scan.  len[i] == 0xFFFFFFFF: frame (or payload) i was rejected (not selected); otherwise it is payload
  * blk_cnt[i / KMP_SCAN_TILE] + loc_idx[i] of the new arena, as kmp_scatter_index_kernel and kmp_select_index_kernel number them. */
-struct MetaWs {
-    const uint32_t *plen, *loc_idx, *blk_cnt;
-};
-MetaWs meta_ws(const uint8_t *ws, uint64_t n)
-{
-    const uint64_t nblk = (n + KMP_SCAN_TILE - 1) / KMP_SCAN_TILE;
-    MetaWs w;
-    w.plen = reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint64_t *>(ws) + n + nblk) + n;
-    w.loc_idx = w.plen + n;
-    w.blk_cnt = w.loc_idx + n;
-    return w;
-}
 
 /* KMPGPU_OPT_KEEP_META: the record of every accepted frame, from the byte positions the extractors walk (kmpgpu.h).  For a frame
  * kmp_extract_kernel accepts they all lie inside its captured bytes: udp cl >= 34 and cl - 14 - ihl >= 8, tcp ihl >= 20 and
@@ -180,9 +167,9 @@ hipError_t kmp_launch_headers(const void *meta, const uint32_t *pkt_len, uint64_
 hipError_t kmp_launch_meta_extract(const uint8_t *file, const uint64_t *frame_off, uint64_t n, const uint8_t *ws, void *meta, hipStream_t st)
 {
     if (n == 0) return hipSuccess;
-    const MetaWs w = meta_ws(ws, n);
+    const kmp_compact_view w = kmp_compact_ws(const_cast<uint8_t *>(ws), n);
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + KMP_BLOCK_THREADS - 1) / KMP_BLOCK_THREADS, 4096);
-    hipLaunchKernelGGL(kmp_meta_extract_kernel, dim3(blocks), dim3(KMP_BLOCK_THREADS), 0, st, file, frame_off, w.plen, w.loc_idx, w.blk_cnt, n,
+    hipLaunchKernelGGL(kmp_meta_extract_kernel, dim3(blocks), dim3(KMP_BLOCK_THREADS), 0, st, file, frame_off, w.len, w.loc_idx, w.blk_cnt, n,
                        reinterpret_cast<uint4 *>(meta));
     return hipGetLastError();
 }
@@ -190,9 +177,9 @@ hipError_t kmp_launch_meta_extract(const uint8_t *file, const uint64_t *frame_of
 hipError_t kmp_launch_meta_select(const void *src_meta, uint64_t n, const uint8_t *ws, void *meta, hipStream_t st)
 {
     if (n == 0) return hipSuccess;
-    const MetaWs w = meta_ws(ws, n);
+    const kmp_compact_view w = kmp_compact_ws(const_cast<uint8_t *>(ws), n);
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + KMP_BLOCK_THREADS - 1) / KMP_BLOCK_THREADS, 1024);
-    hipLaunchKernelGGL(kmp_meta_select_kernel, dim3(blocks), dim3(KMP_BLOCK_THREADS), 0, st, reinterpret_cast<const uint4 *>(src_meta), w.plen,
+    hipLaunchKernelGGL(kmp_meta_select_kernel, dim3(blocks), dim3(KMP_BLOCK_THREADS), 0, st, reinterpret_cast<const uint4 *>(src_meta), w.len,
                        w.loc_idx, w.blk_cnt, n, reinterpret_cast<uint4 *>(meta));
     return hipGetLastError();
 }

@@ -1,5 +1,5 @@
 /* kmp_launch.h -- launch entry points of kmp_scan_*.hip / kmp_prep.hip / kmp_fold.hip / kmp_marks.hip / kmp_rules.hip / kmp_relations.hip /
- * kmp_chains.hip / kmp_headers.hip / kmp_bytetests.hip / kmp_regex.hip / kmp_select.hip / kmp_decode.hip / kmp_fields.hip / kmp_alerts.hip / kmp_flows.hip / kmp_seams.hip / kmp_streams.hip / kmp_streams_seq.hip / kmp_flowbits.hip / kmp_thresholds.hip, used
+ * kmp_chains.hip / kmp_headers.hip / kmp_bytetests.hip / kmp_regex.hip / kmp_select.hip / kmp_decode.hip / kmp_base64.hip / kmp_fields.hip / kmp_alerts.hip / kmp_flows.hip / kmp_seams.hip / kmp_streams.hip / kmp_streams_seq.hip / kmp_flowbits.hip / kmp_thresholds.hip, used
  * by the C-ABI layer (kmpgpu.hip), which alone decides what is launched; the tables kmp_launch_scan_multi takes come from kmp_tables.h. */
 #ifndef KMP_LAUNCH_H
 #define KMP_LAUNCH_H
@@ -81,6 +81,50 @@ uint32_t kmp_multi_resident_waves(int kind, uint32_t table_words, uint32_t n_uni
 #define KMP_SCAN_ITEMS 4u                                         /* items per thread in the block scan of kmp_prep.hip */
 #define KMP_SCAN_TILE  (KMP_BLOCK_THREADS * KMP_SCAN_ITEMS)      /* items per block: the scan workspace holds one total per tile */
 size_t kmp_extract_ws_bytes(uint64_t n_frames);
+/* The scan workspace, kmp_extract_ws_bytes(n) bytes, and the one place that spells its layout: loc_off[n], blk_bytes[nblk], then the 32-bit
+ * arrays aux[n], len[n], loc_idx[n], blk_cnt[nblk], with nblk tiles of KMP_SCAN_TILE items.  len[i] is the length of item i in the
+ * destination, or 0xFFFFFFFF ("not in dst"); the scan (kmp_launch_compact_scan) leaves item i at byte blk_bytes[i / KMP_SCAN_TILE] +
+ * loc_off[i] of a packed arena, as payload blk_cnt[i / KMP_SCAN_TILE] + loc_idx[i].  aux is the caller's and the scan does not touch it:
+ * the extractor's payload offsets, the seams' pred[]. */
+struct kmp_compact_view {
+    uint64_t *loc_off, *blk_bytes;
+    uint32_t *aux, *len, *loc_idx, *blk_cnt;
+    uint32_t  nblk;
+};
+static inline kmp_compact_view kmp_compact_ws(uint8_t *ws, uint64_t n)
+{
+    kmp_compact_view w;
+    w.nblk = (uint32_t)((n + KMP_SCAN_TILE - 1) / KMP_SCAN_TILE);
+    w.loc_off = reinterpret_cast<uint64_t *>(ws);
+    w.blk_bytes = w.loc_off + n;
+    w.aux = reinterpret_cast<uint32_t *>(w.blk_bytes + w.nblk);
+    w.len = w.aux + n;
+    w.loc_idx = w.len + n;
+    w.blk_cnt = w.loc_idx + n;
+    return w;
+}
+/* kmp_scan_local_kernel + kmp_scan_totals_kernel over the len[] of such a workspace: totals[0] = bytes of the packed result, totals[1] =
+ * its items.  What every compacting builder runs between its lengths and its index kernel. */
+hipError_t kmp_launch_compact_scan(uint64_t n, uint8_t *ws, unsigned long long *totals, hipStream_t st);
+
+/* The grids of the compacting builders ("The compacting skeleton"), all capped at KMP_GRID_CAP blocks and grid-stride beyond:
+ * a thread per item, a wavefront per group of 64 items, and a wavefront per RUN of consecutive destination payloads.  A run is a power
+ * of two up to 64 payloads that brings `bytes / n_dst`, the average payload, to KMP_RUN_BYTES. */
+#define KMP_GRID_CAP  1024u
+#define KMP_RUN_BYTES 16384u
+static inline uint32_t kmp_grid_cap(uint64_t blocks) { return (uint32_t)(blocks < KMP_GRID_CAP ? blocks : KMP_GRID_CAP); }
+static inline uint32_t kmp_item_blocks(uint64_t n) { return kmp_grid_cap((n + KMP_BLOCK_THREADS - 1) / KMP_BLOCK_THREADS); }
+static inline uint32_t kmp_group_blocks(uint64_t n) { return kmp_grid_cap(((n + KMP_WAVE - 1) / KMP_WAVE + KMP_BLOCK_WAVES - 1) / KMP_BLOCK_WAVES); }
+struct kmp_run_shape { uint32_t run, blocks; };
+static inline kmp_run_shape kmp_run_shape_of(uint64_t n_dst, uint64_t bytes)
+{
+    const uint64_t avg = bytes / n_dst > 16 ? bytes / n_dst : 16;
+    kmp_run_shape s;
+    s.run = KMP_WAVE;
+    while (s.run > 1u && (uint64_t)s.run * avg > KMP_RUN_BYTES) s.run >>= 1;
+    s.blocks = kmp_grid_cap(((n_dst + s.run - 1) / s.run + KMP_BLOCK_WAVES - 1) / KMP_BLOCK_WAVES);
+    return s;
+}
 hipError_t kmp_launch_extract_phase1(const uint8_t *file, const uint64_t *frame_off, const uint32_t *caplen, uint64_t n, int tcp,
                                      uint8_t *ws, unsigned long long *totals, hipStream_t st);
 hipError_t kmp_launch_extract_phase2(const uint8_t *file, const uint64_t *frame_off, uint64_t n, uint8_t *ws, uint64_t n_pkts,
@@ -178,32 +222,32 @@ hipError_t kmp_launch_meta_select(const void *src_meta, uint64_t n, const uint8_
 hipError_t kmp_launch_fixed_index(uint64_t *pkt_off, uint32_t *pkt_len, uint64_t n, uint32_t len, uint64_t stride,
                                   hipStream_t st);
 /* kmp_select.hip (kmpgpu_load_selected): the payloads of an index of n whose bit is set in select[ceil(n / 64)] (payload k: bit k & 63 of
- * word k >> 6; bits at n and above are not read as payloads), compacted into a packed arena.  ws: kmp_extract_ws_bytes(n) bytes, kept
- * from phase 1 to phase 2.  Phase 1 (3 kernels) leaves totals[0] = bytes of the packed selection, totals[1] = selected payloads n_sel.
- * Phase 2 (2 kernels) writes pkt_off[n_sel], pkt_len[n_sel], the 16-byte records recs[n_sel] the copy reads, and arena[0, total_bytes):
- * every slot whole, 0x00 behind its payload's end.  The source's slots are 16-byte aligned (the layout contract of kmpgpu.h). */
+ * word k >> 6; bits at n and above are not read as payloads), compacted into a packed arena.  The compacting builders -- this one,
+ * kmp_decode.hip, kmp_base64.hip, kmp_fields.hip, kmp_seams.hip -- have these in common: ws is the scan workspace above, kept from the
+ * lengths to the index; between those two runs kmp_launch_compact_scan, which leaves totals[0] = total_bytes and totals[1] = n_dst;
+ * the index writes pkt_off[n_dst], pkt_len[n_dst] and the 16-byte records recs[n_dst] the last kernel reads; that one writes
+ * arena[0, total_bytes), every slot whole and 0x00 behind its payload's end; the source's slots are 16-byte aligned (the layout
+ * contract of kmpgpu.h), of src_arena only aligned 16-byte units that hold a byte of a payload are read, and nothing at or behind a
+ * payload's end takes part.  Here: phase 1 (3 kernels) is the lengths and the scan, phase 2 (2 kernels) the index and the copy. */
 hipError_t kmp_launch_select_phase1(const unsigned long long *select, const uint32_t *pkt_len, uint64_t n, uint8_t *ws,
                                     unsigned long long *totals, hipStream_t st);
 hipError_t kmp_launch_select_phase2(const uint8_t *src_arena, const uint64_t *src_off, uint64_t n, uint8_t *ws, uint64_t n_sel,
                                     uint64_t total_bytes, uint8_t *arena, uint64_t *pkt_off, uint32_t *pkt_len, void *recs,
                                     bool nontemporal, hipStream_t st);
-/* kmp_decode.hip (kmpgpu_load_decoded): the n payloads of an index percent-decoded (the definition: kmpgpu.h) into a packed arena.  ws:
- * kmp_extract_ws_bytes(n) bytes, kept from _lengths to _index.  _lengths (1 kernel) leaves per payload its decoded length, or 0xFFFFFFFF
- * for an unchanged one with only_changed, writes every word of changed[ceil(n / 64)] (bits at n and above 0) and adds to stats[3] =
- * {source bytes of the payloads kept, changed payloads, decoded bytes}, which the caller zeroes.  _scan (2 kernels) leaves totals[0] =
- * bytes of the packed result, totals[1] = its payloads n_dst.  _index (1 kernel) writes pkt_off[n_dst], pkt_len[n_dst] and the 16-byte
- * records recs[n_dst]; _write (1 kernel) arena[0, total_bytes): every slot whole, 0x00 behind its payload's end.  bytes_in: stats[0].
- * The source's slots are 16-byte aligned (the layout contract of kmpgpu.h); nothing at or behind a payload's end takes part. */
+/* kmp_decode.hip (kmpgpu_load_decoded): the n payloads of an index percent-decoded (the definition: kmpgpu.h) into a packed arena, ws
+ * as kmp_select.hip's.  _lengths (1 kernel) leaves per payload its decoded length, or 0xFFFFFFFF for an unchanged one with only_changed,
+ * writes every word of changed[ceil(n / 64)] (bits at n and above 0) and adds to stats[3] = {source bytes of the payloads kept, changed
+ * payloads, decoded bytes}, which the caller zeroes.  Then kmp_launch_compact_scan (2 kernels), _index (1 kernel) and _write (1 kernel).
+ * bytes_in: stats[0]. */
 hipError_t kmp_launch_decode_lengths(const uint8_t *src_arena, const uint64_t *src_off, const uint32_t *src_len, uint64_t n, bool plus,
                                      bool only_changed, uint8_t *ws, unsigned long long *changed, unsigned long long *stats, hipStream_t st);
-hipError_t kmp_launch_decode_scan(uint64_t n, uint8_t *ws, unsigned long long *totals, hipStream_t st);
 hipError_t kmp_launch_decode_index(const uint64_t *src_off, const uint32_t *src_len, uint64_t n, uint8_t *ws, uint64_t n_dst, uint64_t *pkt_off,
                                    uint32_t *pkt_len, void *recs, hipStream_t st);
 hipError_t kmp_launch_decode_write(const uint8_t *src_arena, const uint64_t *pkt_off, const void *recs, uint64_t n_dst, uint64_t bytes_in,
                                    uint64_t total_bytes, bool plus, uint8_t *arena, bool nontemporal, hipStream_t st);
 /* kmp_base64.hip (kmpgpu_load_base64): the base64 runs of min_run (4..255) alphabet bytes and more decoded (the definition: kmpgpu.h).
  * The phases, ws, changed, stats and recs are those of kmp_decode.hip: _lengths (1 kernel) and _write (1 kernel) here, and between
- * them kmp_launch_decode_scan and kmp_launch_decode_index, whose workspace layout and records these two share. */
+ * them kmp_launch_compact_scan and kmp_launch_decode_index, whose records these two share. */
 hipError_t kmp_launch_base64_lengths(const uint8_t *src_arena, const uint64_t *src_off, const uint32_t *src_len, uint64_t n, uint32_t min_run,
                                      bool urlsafe, bool only_changed, uint8_t *ws, unsigned long long *changed, unsigned long long *stats,
                                      hipStream_t st);
@@ -211,18 +255,14 @@ hipError_t kmp_launch_base64_write(const uint8_t *src_arena, const uint64_t *pkt
                                    uint64_t total_bytes, uint32_t min_run, bool urlsafe, uint8_t *arena, bool nontemporal, hipStream_t st);
 /* kmp_fields.hip (kmpgpu_http_locate, kmpgpu_load_fields): the HTTP field buffers (the definition: kmpgpu.h).  _http_locate (1 kernel)
  * writes spans[n] (kmpgpu_http_span, 32 bytes each, 16-byte aligned) and adds to stats[4] = {requests, responses, messages with a blank
- * line, bytes scanned}, which the caller zeroes.  ws: kmp_extract_ws_bytes(n) bytes, kept from _lengths to _index.  _lengths (1 kernel)
- * leaves per payload the length of `field` (KMPGPU_FIELD_*), or 0xFFFFFFFF for an absent one with only_present, writes every word of
- * present[ceil(n / 64)] (bits at n and above 0) and adds to stats[3] = {source bytes of the payloads kept, payloads with the field, field
- * bytes}, which the caller zeroes.  _scan (2 kernels) leaves totals[0] = bytes of the packed result, totals[1] = its payloads n_dst.  _index
- * (1 kernel) writes pkt_off[n_dst], pkt_len[n_dst] and the 16-byte records recs[n_dst]; _gather (1 kernel) arena[0, total_bytes): every slot
- * whole, 0x00 behind its payload's end.  The source's slots are 16-byte aligned (the layout contract of kmpgpu.h); of src_arena only
- * aligned 16-byte units that hold a byte of a payload are read, and nothing at or behind a payload's end takes part. */
+ * line, bytes scanned}, which the caller zeroes.  The rest as kmp_select.hip's: _lengths (1 kernel) leaves per payload the length of
+ * `field` (KMPGPU_FIELD_*), or 0xFFFFFFFF for an absent one with only_present, writes every word of present[ceil(n / 64)] (bits at n and
+ * above 0) and adds to stats[3] = {source bytes of the payloads kept, payloads with the field, field bytes}, which the caller zeroes.
+ * Then kmp_launch_compact_scan (2 kernels), _index (1 kernel) and _gather (1 kernel). */
 hipError_t kmp_launch_http_locate(const uint8_t *src_arena, const uint64_t *src_off, const uint32_t *src_len, uint64_t n, void *spans,
                                   unsigned long long *stats, hipStream_t st);
 hipError_t kmp_launch_fields_lengths(const void *spans, const uint32_t *src_len, uint64_t n, int field, bool only_present, uint8_t *ws,
                                      unsigned long long *present, unsigned long long *stats, hipStream_t st);
-hipError_t kmp_launch_fields_scan(uint64_t n, uint8_t *ws, unsigned long long *totals, hipStream_t st);
 hipError_t kmp_launch_fields_index(const void *spans, const uint64_t *src_off, uint64_t n, int field, uint8_t *ws, uint64_t n_dst,
                                    uint64_t *pkt_off, uint32_t *pkt_len, void *recs, hipStream_t st);
 hipError_t kmp_launch_fields_gather(const uint8_t *src_arena, const uint64_t *pkt_off, const void *recs, uint64_t n_dst, uint64_t total_bytes,
@@ -230,12 +270,11 @@ hipError_t kmp_launch_fields_gather(const uint8_t *src_arena, const uint64_t *pk
 /* kmp_alerts.hip (kmpgpu_scan_alerts): the set bits of rows[n_rows][stride] (stride even, 16-byte aligned, every word of a row readable,
  * the bits of index n_pkts and above not looked at; 16 * n_rows <= 0xFFFFFFFE) as 16-byte records {payload (64 bits), row, 0}, sorted by
  * payload, then row.  any[ceil(n_pkts / 64)]: the OR over the rows, complete before the count; a column word whose any word is 0 is not read.
- * ws: kmp_extract_ws_bytes(n_pkts) bytes, kept from the count to the fill.  _count (1 kernel) leaves per payload its records' bytes, _scan
+ * ws: kmp_extract_ws_bytes(n_pkts) bytes, kept from the count to the fill.  _count (1 kernel) leaves per payload its records' bytes, kmp_launch_compact_scan
  * (2 kernels) every payload's offset and totals[0] = 16 * records, totals[1] = payloads with a record, _fill (1 kernel) writes the records
  * whose position in the list is below max_records to recs[min(max_records, records)]. */
 hipError_t kmp_launch_alerts_count(const unsigned long long *rows, uint64_t stride, uint32_t n_rows, uint64_t n_pkts,
                                    const unsigned long long *any, uint8_t *ws, hipStream_t st);
-hipError_t kmp_launch_alerts_scan(uint64_t n_pkts, uint8_t *ws, unsigned long long *totals, hipStream_t st);
 hipError_t kmp_launch_alerts_fill(const unsigned long long *rows, uint64_t stride, uint32_t n_rows, uint64_t n_pkts,
                                   const unsigned long long *any, uint8_t *ws, void *recs, uint64_t max_records, hipStream_t st);
 
@@ -243,7 +282,7 @@ hipError_t kmp_launch_alerts_fill(const unsigned long long *rows, uint64_t strid
  * kmpgpu_pkt_meta records, 16-byte aligned) grouped by their flow key (kmp_flow_key.h).  In the order they are launched:
  * _insert: table[slots] (a power of two > n_pkts, at most 2^32; all 0 before the launch) takes every key, first[slots] (all 0xFFFFFFFF
  *   before) the lowest payload index of every taken slot, slot_of[n_pkts] every payload's slot.
- * _firsts, _scan (2 kernels): in ws, kmp_extract_ws_bytes(n_pkts) bytes kept up to _number: which payloads are their flow's first, their
+ * _firsts, kmp_launch_compact_scan (2 kernels): in ws, kmp_extract_ws_bytes(n_pkts) bytes kept up to _number: which payloads are their flow's first, their
  *   rank among those, totals[1] = n_flows.
  * _number: table[slot] = the id of the slot's flow; recs[n_flows] (48-byte kmpgpu_flow records, 16-byte aligned): first_packet, first, and
  *   0 in the three fields _assign adds up.
@@ -256,7 +295,6 @@ hipError_t kmp_launch_alerts_fill(const unsigned long long *rows, uint64_t strid
 hipError_t kmp_launch_flows_insert(const void *meta, uint64_t n_pkts, bool directed, uint32_t *table, uint64_t slots, uint32_t *first,
                                    uint32_t *slot_of, hipStream_t st);
 hipError_t kmp_launch_flows_firsts(const uint32_t *first, const uint32_t *slot_of, uint64_t n_pkts, uint8_t *ws, hipStream_t st);
-hipError_t kmp_launch_flows_scan(uint64_t n_pkts, uint8_t *ws, unsigned long long *totals, hipStream_t st);
 hipError_t kmp_launch_flows_number(const void *meta, uint64_t n_pkts, uint8_t *ws, const uint32_t *slot_of, uint32_t *table, void *recs,
                                    hipStream_t st);
 hipError_t kmp_launch_flows_assign(const uint32_t *table, uint32_t *slot_flow, const uint32_t *pkt_len, uint64_t n_pkts, void *recs,

@@ -1,6 +1,6 @@
 /*
  * kmp_piece_dev.h -- device helpers of the gathers that build a derived arena from byte ranges of a source arena (kmp_seams.hip, kmp_streams.hip, kmp_streams_seq.hip,
- * kmp_fields.hip): 16-byte units loaded and stored whole, and the 16 bytes of a range that starts at any byte.  gfx950.
+ * kmp_fields.hip): the 16 bytes of a range that starts at any byte, from aligned 16-byte units.  gfx950.
  */
 #ifndef KMP_PIECE_DEV_H
 #define KMP_PIECE_DEV_H
@@ -8,29 +8,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kmp_unit_dev.h"
+
 namespace kmp_piece {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-template <bool NT>
-__device__ __forceinline__ u32x4 load_unit(const uint8_t *p)
-{
-    const u32x4 *q = reinterpret_cast<const u32x4 *>(p);
-    return NT ? __builtin_nontemporal_load(q) : *q;
-}
-template <bool NT>
-__device__ __forceinline__ void store_unit(uint8_t *p, u32x4 v)
-{
-    u32x4 *q = reinterpret_cast<u32x4 *>(p);
-    if (NT) __builtin_nontemporal_store(v, q); else *q = v;
-}
-
-/* 0xFF in the bytes [lo, hi) of dword d of a unit (byte positions 4 d .. 4 d + 3), 0 <= lo, hi <= 16 */
-__device__ __forceinline__ uint32_t below_mask(uint32_t x, uint32_t d)
-{
-    const uint32_t b = 4u * d;
-    return (x >= b + 4u) ? 0xFFFFFFFFu : (x <= b) ? 0u : ((1u << (8u * (x - b))) - 1u);
-}
+using kmp_unit::u32x4;          /* the unit, its loads and stores and the one byte mask: kmp_unit_dev.h */
+using kmp_unit::load_unit;
+using kmp_unit::store_unit;
+using kmp_unit::below_mask;
 
 /* The 16 bytes [start, start + 16) of a piece, in coordinates relative to `base` (16-byte aligned), of which [lo, hi) exist (0 <= lo <= hi);
  * start >= -15.  Bytes outside [lo, hi) come out 0x00.  Only the aligned units that hold a byte of [lo, hi) are loaded. */

@@ -304,30 +304,20 @@ hipError_t kmp_launch_extract_phase1(const uint8_t *file, const uint64_t *frame_
                                      uint8_t *ws, unsigned long long *totals, hipStream_t st)
 {
     if (n == 0) return hipSuccess;
-    const uint64_t nblk = (n + KMP_SCAN_TILE - 1) / KMP_SCAN_TILE;
-    uint64_t *loc_off = reinterpret_cast<uint64_t *>(ws);
-    uint64_t *blk_bytes = loc_off + n;
-    uint32_t *poff = reinterpret_cast<uint32_t *>(blk_bytes + nblk);
-    uint32_t *plen = poff + n, *loc_idx = plen + n, *blk_cnt = loc_idx + n;
+    const kmp_compact_view w = kmp_compact_ws(ws, n);       /* aux: the payloads' offsets in their frames */
     uint32_t blocks = (uint32_t)std::min<uint64_t>((n + KMP_BLOCK_THREADS - 1) / KMP_BLOCK_THREADS, 4096);
-    hipLaunchKernelGGL(kmp_extract_kernel, dim3(blocks), dim3(KMP_BLOCK_THREADS), 0, st, file, frame_off, caplen, n, tcp, poff, plen);
-    hipLaunchKernelGGL(kmp_scan_local_kernel, dim3((uint32_t)nblk), dim3(KMP_BLOCK_THREADS), 0, st, plen, n, loc_off, loc_idx, blk_bytes, blk_cnt);
-    hipLaunchKernelGGL(kmp_scan_totals_kernel, dim3(1), dim3(KMP_BLOCK_THREADS), 0, st, blk_bytes, blk_cnt, (uint32_t)nblk, totals);
-    return hipGetLastError();
+    hipLaunchKernelGGL(kmp_extract_kernel, dim3(blocks), dim3(KMP_BLOCK_THREADS), 0, st, file, frame_off, caplen, n, tcp, w.aux, w.len);
+    return kmp_launch_compact_scan(n, ws, totals, st);
 }
 
 hipError_t kmp_launch_extract_phase2(const uint8_t *file, const uint64_t *frame_off, uint64_t n, uint8_t *ws, uint64_t n_pkts,
                                      uint8_t *arena, uint64_t *pkt_off, uint32_t *pkt_len, uint64_t *src_off, hipStream_t st)
 {
     if (n == 0 || n_pkts == 0) return hipSuccess;
-    const uint64_t nblk = (n + KMP_SCAN_TILE - 1) / KMP_SCAN_TILE;
-    uint64_t *loc_off = reinterpret_cast<uint64_t *>(ws);
-    uint64_t *blk_bytes = loc_off + n;
-    uint32_t *poff = reinterpret_cast<uint32_t *>(blk_bytes + nblk);
-    uint32_t *plen = poff + n, *loc_idx = plen + n, *blk_cnt = loc_idx + n;
+    const kmp_compact_view w = kmp_compact_ws(ws, n);
     uint32_t blocks = (uint32_t)std::min<uint64_t>((n + KMP_BLOCK_THREADS - 1) / KMP_BLOCK_THREADS, 4096);
-    hipLaunchKernelGGL(kmp_scatter_index_kernel, dim3(blocks), dim3(KMP_BLOCK_THREADS), 0, st, frame_off, poff, plen, loc_off, loc_idx,
-                       blk_bytes, blk_cnt, n, pkt_off, pkt_len, src_off);
+    hipLaunchKernelGGL(kmp_scatter_index_kernel, dim3(blocks), dim3(KMP_BLOCK_THREADS), 0, st, frame_off, w.aux, w.len, w.loc_off, w.loc_idx,
+                       w.blk_bytes, w.blk_cnt, n, pkt_off, pkt_len, src_off);
     uint32_t gblocks = (uint32_t)std::min<uint64_t>((n_pkts + KMP_BLOCK_WAVES - 1) / KMP_BLOCK_WAVES, 8192);
     hipLaunchKernelGGL(kmp_gather_kernel, dim3(gblocks), dim3(KMP_BLOCK_THREADS), 0, st, file, src_off, pkt_off, pkt_len, n_pkts, arena);
     return hipGetLastError();
@@ -339,13 +329,17 @@ hipError_t kmp_launch_extract_phase2(const uint8_t *file, const uint64_t *frame_
 hipError_t kmp_launch_repack_phase1(const uint32_t *pkt_len, uint64_t n, uint8_t *ws, unsigned long long *totals, hipStream_t st)
 {
     if (n == 0) return hipSuccess;
-    const uint64_t nblk = (n + KMP_SCAN_TILE - 1) / KMP_SCAN_TILE;
-    uint64_t *loc_off = reinterpret_cast<uint64_t *>(ws);
-    uint64_t *blk_bytes = loc_off + n;
-    uint32_t *loc_idx = reinterpret_cast<uint32_t *>(blk_bytes + nblk) + 2 * n, *blk_cnt = loc_idx + n;
-    hipLaunchKernelGGL(kmp_scan_local_kernel, dim3((uint32_t)nblk), dim3(KMP_BLOCK_THREADS), 0, st, pkt_len, n, loc_off, loc_idx, blk_bytes, blk_cnt);
-    hipLaunchKernelGGL(kmp_scan_totals_kernel, dim3(1), dim3(KMP_BLOCK_THREADS), 0, st, blk_bytes, blk_cnt, (uint32_t)nblk, totals);
+    const kmp_compact_view w = kmp_compact_ws(ws, n);       /* the lengths are the caller's array: len[] is not used */
+    hipLaunchKernelGGL(kmp_scan_local_kernel, dim3(w.nblk), dim3(KMP_BLOCK_THREADS), 0, st, pkt_len, n, w.loc_off, w.loc_idx, w.blk_bytes, w.blk_cnt);
+    hipLaunchKernelGGL(kmp_scan_totals_kernel, dim3(1), dim3(KMP_BLOCK_THREADS), 0, st, w.blk_bytes, w.blk_cnt, w.nblk, totals);
     return hipGetLastError();
+}
+
+/* ... of the lengths a builder has left in the workspace itself (kmp_launch.h) */
+hipError_t kmp_launch_compact_scan(uint64_t n, uint8_t *ws, unsigned long long *totals, hipStream_t st)
+{
+    if (n == 0) return hipSuccess;
+    return kmp_launch_repack_phase1(kmp_compact_ws(ws, n).len, n, ws, totals, st);
 }
 
 hipError_t kmp_launch_repack_phase2(const uint8_t *old_arena, const uint64_t *old_off, const uint32_t *pkt_len, uint64_t n, uint8_t *ws,

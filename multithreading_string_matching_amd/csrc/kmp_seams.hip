@@ -9,15 +9,14 @@
  *   kmp_seam_pred_kernel      at sorted position i: k = val[i] has the predecessor val[i - 1] where the two keys are equal.  pred[k], and
  *                             seam_len[k] = min(reach, L_pred) + min(reach, L_k), or 0xFFFFFFFF ("rejected", as kmp_extract_kernel writes
  *                             it) without a predecessor
- *   kmp_scan_local_kernel, kmp_scan_totals_kernel   of kmp_prep.hip, through kmp_launch_repack_phase1: slot offsets and seam numbers in
+ *   kmp_scan_local_kernel, kmp_scan_totals_kernel   of kmp_prep.hip, through kmp_launch_compact_scan: slot offsets and seam numbers in
  *                             ascending order of `next`, totals = {packed bytes, seams}
  *   kmp_seam_index_kernel     the new index, the kmpgpu_seam records, seam_flow, the metadata, and per seam the 32-byte record the gather
  *                             reads: where its tail and its head lie in the source and how long they are
  *   kmp_seam_gather_kernel    the bytes
  *
- * The gather.  The destination is packed and written as kmp_select_copy_kernel writes its own: a wavefront takes a RUN of up to 64
- * consecutive seams, whose new offsets are the prefix sums of their unit counts, keeps the run's table in its 2 KiB of LDS, and deals the
- * run's 16-byte units to the lanes in order -- contiguous stores whatever the seam boundaries.  What differs is the source: a destination
+ * The gather.  Its shape -- a wavefront per RUN of up to 64 consecutive seams, the run's 16-byte units dealt to the lanes in order -- is the
+ * compacting skeleton's (gather_runs: kmp_compact_dev.h).  What is this file's own is the source: a destination
  * unit is made of up to two pieces, neither of them 16-byte aligned relative to it.  The tail starts at off_prev + L_prev - tail_len, any
  * byte address, and the head, which starts on its slot's first byte, lands at byte tail_len of the seam.  A piece is fetched with ALIGNED
  * 16-byte loads of the source units that hold bytes it needs -- one or two --, brought into place with a byte funnel shift
@@ -38,36 +37,14 @@
 #include "kmp_device.h"
 #include "kmp_launch.h"
 #include "kmp_piece_dev.h"
+#include "kmp_compact_dev.h"
 
 namespace {
 
-typedef kmp_piece::u32x4 seam_u32x4;
+using namespace kmp_unit;     /* kmp_compact_dev.h: gather_runs; kmp_unit_dev.h: the unit */
+using kmp_piece::fetch_piece;
 
 constexpr uint32_t SEAM_NONE = 0xFFFFFFFFu;
-constexpr uint32_t SEAM_UNROLL = 2;              /* destination units a lane has in flight (up to four loads each) */
-constexpr uint32_t SEAM_INDEX_BLOCKS = 1024;     /* grid cap of the per-payload kernels: rounds past 262 144 payloads */
-constexpr uint32_t SEAM_GATHER_BLOCKS = 1024;    /* grid cap of the gather (16 wavefronts per CU): rounds past 4 096 runs */
-constexpr uint32_t SEAM_RUN_BYTES = 16384;       /* bytes a run should come to */
-
-/* The scan workspace of kmp_prep.hip (kmp_extract_ws_bytes): loc_off[n], blk_bytes[nblk], then the 32-bit arrays poff[n], plen[n],
- * loc_idx[n], blk_cnt[nblk].  The seam lengths take plen's place, as the masked lengths of kmp_select.hip do, and pred[] takes poff's,
- * which the scan does not use. */
-struct SeamWs {
-    uint64_t *loc_off, *blk_bytes;
-    uint32_t *pred, *seam_len, *loc_idx, *blk_cnt;
-};
-SeamWs seam_ws(uint8_t *ws, uint64_t n)
-{
-    const uint64_t nblk = (n + KMP_SCAN_TILE - 1) / KMP_SCAN_TILE;
-    SeamWs w;
-    w.loc_off = reinterpret_cast<uint64_t *>(ws);
-    w.blk_bytes = w.loc_off + n;
-    w.pred = reinterpret_cast<uint32_t *>(w.blk_bytes + nblk);
-    w.seam_len = w.pred + n;
-    w.loc_idx = w.seam_len + n;
-    w.blk_cnt = w.loc_idx + n;
-    return w;
-}
 
 /* The sort's buffers in the one allocation the context keeps for them: keys in / out, values in / out, rocPRIM's temporary storage. */
 struct SeamSort {
@@ -161,75 +138,37 @@ kmp_seam_index_kernel(const uint64_t *__restrict__ src_off, const uint32_t *__re
     }
 }
 
-/* load_unit / store_unit / fetch_piece: kmp_piece_dev.h, which the gathers of the derived arenas share */
-using kmp_piece::fetch_piece;
-using kmp_piece::load_unit;
-using kmp_piece::store_unit;
+struct SeamRec { uint4 a, b; };          /* the 32-byte record of a seam: {tail address, tail_len, head_len}, {head address} */
 
 template <bool NT>
 __global__ void __launch_bounds__(KMP_BLOCK_THREADS)
 kmp_seam_gather_kernel(const uint8_t *__restrict__ src, const uint64_t *__restrict__ new_off, const uint4 *__restrict__ recs, uint64_t n,
                        uint64_t total, uint32_t run, uint8_t *__restrict__ dst)
 {
-    __shared__ uint64_t s_off[KMP_BLOCK_WAVES][KMP_WAVE];          /* new offset of seam i of the run; ~0 behind the run's end */
     __shared__ uint64_t s_tail[KMP_BLOCK_WAVES][KMP_WAVE], s_head[KMP_BLOCK_WAVES][KMP_WAVE];      /* where the two pieces start in src */
     __shared__ uint32_t s_tl[KMP_BLOCK_WAVES][KMP_WAVE], s_hl[KMP_BLOCK_WAVES][KMP_WAVE];          /* tail_len, head_len */
     const uint32_t lane = threadIdx.x & (KMP_WAVE - 1u), wid = threadIdx.x >> 6;
-    const uint64_t n_runs = (n + run - 1u) / run;
-    for (uint64_t r = (uint64_t)blockIdx.x * KMP_BLOCK_WAVES + wid; r < n_runs; r += (uint64_t)gridDim.x * KMP_BLOCK_WAVES) {
-        const uint64_t j0 = r * run, j = j0 + lane;
-        uint64_t off = ~0ull, ts = 0ull, hs = 0ull;
-        uint32_t tl = 0u, hl = 0u;
-        if (lane < run && j < n) {
-            const uint4 a = recs[2u * j], b = recs[2u * j + 1u];
-            off = new_off[j];
-            ts = ((uint64_t)a.y << 32) | a.x; tl = a.z; hl = a.w;
-            hs = ((uint64_t)b.y << 32) | b.x;
-        }
-        /* the wavefront's own LDS: its DS instructions execute in order, the barriers keep the compiler from moving them */
-        __builtin_amdgcn_wave_barrier();
-        s_off[wid][lane] = off; s_tail[wid][lane] = ts; s_head[wid][lane] = hs; s_tl[wid][lane] = tl; s_hl[wid][lane] = hl;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const uint64_t base = new_off[j0];
-        const uint64_t end = (j0 + run < n) ? new_off[j0 + run] : total;
-        for (uint64_t d0 = base + (uint64_t)lane * 16u; d0 - lane * 16u < end; d0 += (uint64_t)SEAM_UNROLL * KMP_WAVE * 16u) {
-            seam_u32x4 v[SEAM_UNROLL];
-#pragma unroll
-            for (uint32_t u = 0; u < SEAM_UNROLL; ++u) {
-                const uint64_t d = d0 + (uint64_t)u * KMP_WAVE * 16u;
-                v[u] = (seam_u32x4)(0u);
-                if (d < end) {
-                    uint32_t p = 0u;                                 /* the last seam of the run that starts at or before d */
-#pragma unroll
-                    for (uint32_t step = KMP_WAVE / 2u; step; step >>= 1)
-                        if (s_off[wid][p + step] <= d) p += step;
-                    const uint64_t rel64 = d - s_off[wid][p];
-                    const uint32_t T = s_tl[wid][p], H = s_hl[wid][p];
-                    if (rel64 < (uint64_t)T + H) {                   /* (an empty seam's slot, or nothing: zeros) */
-                        const int32_t rel = (int32_t)rel64;          /* below 2 x 98 */
-                        const uint64_t t0 = s_tail[wid][p];
-                        const int32_t ta = (int32_t)(t0 & 15u);      /* the tail in the coordinates of the aligned unit it starts in */
-                        const seam_u32x4 vt = fetch_piece<NT>(src + (t0 - (uint32_t)ta), ta + rel, ta, ta + (int32_t)T);
-                        const seam_u32x4 vh = fetch_piece<NT>(src + s_head[wid][p], rel - (int32_t)T, 0, (int32_t)H);
-                        v[u] = vt | vh;
-                    }
-                }
-            }
-#pragma unroll
-            for (uint32_t u = 0; u < SEAM_UNROLL; ++u) {
-                const uint64_t d = d0 + (uint64_t)u * KMP_WAVE * 16u;
-                if (d < end) store_unit<NT>(dst + d, v[u]);
-            }
-        }
-        __builtin_amdgcn_wave_barrier();                             /* the next run's table goes over this one */
-    }
-}
-
-uint32_t per_payload_blocks(uint64_t n)
-{
-    return (uint32_t)std::min<uint64_t>((n + KMP_BLOCK_THREADS - 1) / KMP_BLOCK_THREADS, SEAM_INDEX_BLOCKS);
+    gather_runs<NT, 2>(new_off, n, total, run, dst,
+        [&](uint64_t j, bool in) {
+            SeamRec r = {make_uint4(0u, 0u, 0u, 0u), make_uint4(0u, 0u, 0u, 0u)};
+            if (in) { r.a = recs[2u * j]; r.b = recs[2u * j + 1u]; }
+            return r;
+        },
+        [&](const SeamRec &r) {
+            const uint4 a = r.a, b = r.b;
+            s_tail[wid][lane] = ((uint64_t)a.y << 32) | a.x; s_tl[wid][lane] = a.z; s_hl[wid][lane] = a.w;
+            s_head[wid][lane] = ((uint64_t)b.y << 32) | b.x;
+        },
+        [&](uint32_t p, uint64_t rel64, uint32_t &) {
+            const uint32_t T = s_tl[wid][p], H = s_hl[wid][p];
+            if (rel64 >= (uint64_t)T + H) return (u32x4)(0u);        /* (an empty seam's slot, or nothing: zeros) */
+            const int32_t rel = (int32_t)rel64;                      /* below 2 x 98 */
+            const uint64_t t0 = s_tail[wid][p];
+            const int32_t ta = (int32_t)(t0 & 15u);                  /* the tail in the coordinates of the aligned unit it starts in */
+            const u32x4 vt = fetch_piece<NT>(src + (t0 - (uint32_t)ta), ta + rel, ta, ta + (int32_t)T);
+            const u32x4 vh = fetch_piece<NT>(src + s_head[wid][p], rel - (int32_t)T, 0, (int32_t)H);
+            return vt | vh;
+        });
 }
 
 }  // namespace
@@ -248,7 +187,7 @@ hipError_t kmp_launch_seam_keys(const void *meta, const uint32_t *flow_of, const
     static_assert(sizeof(kmpgpu_flow) == 48 && sizeof(kmpgpu_pkt_meta) == 16, "kmpgpu_flow.first is the third 16 bytes of a 48-byte record");
     if (n == 0) return hipSuccess;
     const SeamSort s = seam_sort(sort_buf, n);
-    hipLaunchKernelGGL(kmp_seam_keys_kernel, dim3(per_payload_blocks(n)), dim3(KMP_BLOCK_THREADS), 0, st, reinterpret_cast<const uint4 *>(meta),
+    hipLaunchKernelGGL(kmp_seam_keys_kernel, dim3(kmp_item_blocks(n)), dim3(KMP_BLOCK_THREADS), 0, st, reinterpret_cast<const uint4 *>(meta),
                        flow_of, reinterpret_cast<const uint4 *>(flow_recs), n, s.key_in, s.val_in);
     return hipGetLastError();
 }
@@ -268,12 +207,12 @@ hipError_t kmp_launch_seam_phase1(const uint32_t *pkt_len, uint64_t n, uint32_t 
 {
     if (n == 0) return hipSuccess;
     const SeamSort s = seam_sort(const_cast<uint8_t *>(sort_buf), n);
-    const SeamWs w = seam_ws(ws, n);
-    hipLaunchKernelGGL(kmp_seam_pred_kernel, dim3(per_payload_blocks(n)), dim3(KMP_BLOCK_THREADS), 0, st, s.key_out, s.val_out, pkt_len, n, reach,
-                       w.pred, w.seam_len);
+    const kmp_compact_view w = kmp_compact_ws(ws, n);       /* aux: pred[] */
+    hipLaunchKernelGGL(kmp_seam_pred_kernel, dim3(kmp_item_blocks(n)), dim3(KMP_BLOCK_THREADS), 0, st, s.key_out, s.val_out, pkt_len, n, reach,
+                       w.aux, w.len);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    return kmp_launch_repack_phase1(w.seam_len, n, ws, totals, st);          /* kmp_scan_local_kernel + kmp_scan_totals_kernel */
+    return kmp_launch_compact_scan(n, ws, totals, st);
 }
 
 hipError_t kmp_launch_seam_index(const uint64_t *src_off, const uint32_t *src_len, const void *src_meta, const uint32_t *flow_of, uint64_t n,
@@ -282,9 +221,9 @@ hipError_t kmp_launch_seam_index(const uint64_t *src_off, const uint32_t *src_le
 {
     static_assert(sizeof(kmpgpu_seam) == 24, "kmpgpu_seam is three 64-bit words");
     if (n == 0) return hipSuccess;
-    const SeamWs w = seam_ws(ws, n);
-    hipLaunchKernelGGL(kmp_seam_index_kernel, dim3(per_payload_blocks(n)), dim3(KMP_BLOCK_THREADS), 0, st, src_off, src_len,
-                       reinterpret_cast<const uint4 *>(src_meta), flow_of, w.pred, w.seam_len, w.loc_off, w.loc_idx, w.blk_bytes, w.blk_cnt, n,
+    const kmp_compact_view w = kmp_compact_ws(ws, n);       /* aux: pred[] */
+    hipLaunchKernelGGL(kmp_seam_index_kernel, dim3(kmp_item_blocks(n)), dim3(KMP_BLOCK_THREADS), 0, st, src_off, src_len,
+                       reinterpret_cast<const uint4 *>(src_meta), flow_of, w.aux, w.len, w.loc_off, w.loc_idx, w.blk_bytes, w.blk_cnt, n,
                        reach, pkt_off, pkt_len, reinterpret_cast<uint64_t *>(seams), seam_flow, reinterpret_cast<uint4 *>(meta),
                        reinterpret_cast<uint4 *>(recs));
     return hipGetLastError();
@@ -294,17 +233,8 @@ hipError_t kmp_launch_seam_gather(const uint8_t *src_arena, const uint64_t *pkt_
                                   uint8_t *arena, bool nontemporal, hipStream_t st)
 {
     if (n_seams == 0) return hipSuccess;
-    /* seams per run: what brings an average run to SEAM_RUN_BYTES, a power of two up to 64 */
-    const uint64_t avg = std::max<uint64_t>(total_bytes / n_seams, 16);
-    uint32_t run = KMP_WAVE;
-    while (run > 1u && (uint64_t)run * avg > SEAM_RUN_BYTES) run >>= 1;
-    const uint64_t n_runs = (n_seams + run - 1) / run;
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_runs + KMP_BLOCK_WAVES - 1) / KMP_BLOCK_WAVES, SEAM_GATHER_BLOCKS);
-    if (nontemporal)
-        hipLaunchKernelGGL(kmp_seam_gather_kernel<true>, dim3(blocks), dim3(KMP_BLOCK_THREADS), 0, st, src_arena, pkt_off, (const uint4 *)recs,
-                           n_seams, total_bytes, run, arena);
-    else
-        hipLaunchKernelGGL(kmp_seam_gather_kernel<false>, dim3(blocks), dim3(KMP_BLOCK_THREADS), 0, st, src_arena, pkt_off, (const uint4 *)recs,
-                           n_seams, total_bytes, run, arena);
+    const kmp_run_shape rs = kmp_run_shape_of(n_seams, total_bytes);
+    hipLaunchKernelGGL(nontemporal ? kmp_seam_gather_kernel<true> : kmp_seam_gather_kernel<false>, dim3(rs.blocks), dim3(KMP_BLOCK_THREADS), 0, st,
+                       src_arena, pkt_off, (const uint4 *)recs, n_seams, total_bytes, rs.run, arena);
     return hipGetLastError();
 }

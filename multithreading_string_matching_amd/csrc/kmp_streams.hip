@@ -38,7 +38,7 @@
 
 namespace {
 
-typedef kmp_piece::u32x4 stream_u32x4;
+using kmp_piece::u32x4;
 
 /* A lane's units are looked up one after the other (piece_dst -> piece record -> source units: three dependent loads each), so what
  * is in flight is one unit per lane: parallelism comes from wavefronts, 8 per SIMD (40 VGPRs allow them), not from units per lane. */
@@ -239,12 +239,12 @@ kmp_stream_gather_kernel(const uint8_t *__restrict__ src, const uint4 *__restric
     const uint64_t u_end = min(units, (w + 1u) * span);
     uint32_t p_wave = 0u;                                            /* a piece at or before the one of the round's first unit */
     for (uint64_t u0 = w * span; u0 < u_end; u0 += STREAM_CHUNK_UNITS) {
-        stream_u32x4 v[STREAM_UNROLL];
+        u32x4 v[STREAM_UNROLL];
         uint32_t p_first = p_wave;
 #pragma unroll
         for (uint32_t r = 0; r < STREAM_UNROLL; ++r) {
             const uint64_t u = u0 + (uint64_t)r * KMP_WAVE + lane;
-            v[r] = (stream_u32x4)(0u);
+            v[r] = (u32x4)(0u);
             if (u < u_end) {
                 const uint64_t d = u * 16u;
                 /* piece_dst[0] == 0 <= d.  Pieces that start at d and hold no byte are passed over: the last one at d is the one with bytes */

@@ -38,7 +38,7 @@
 
 namespace {
 
-typedef kmp_piece::u32x4 sseq_u32x4;
+using kmp_piece::u32x4;
 
 constexpr uint32_t SSEQ_UNROLL = 1;               /* as kmp_streams.hip: one unit per lane in flight, parallelism from wavefronts */
 constexpr uint32_t SSEQ_INDEX_BLOCKS = 1024;      /* grid cap of the per-payload and per-stream kernels: rounds past 262 144 elements */
@@ -402,12 +402,12 @@ kmp_sseq_gather_kernel(const uint8_t *__restrict__ src, const uint4 *__restrict_
     const uint64_t u_end = min(units, (w + 1u) * span);
     uint32_t p_wave = 0u;                                            /* a piece at or before the one of the round's first unit */
     for (uint64_t u0 = w * span; u0 < u_end; u0 += SSEQ_CHUNK_UNITS) {
-        sseq_u32x4 v[SSEQ_UNROLL];
+        u32x4 v[SSEQ_UNROLL];
         uint32_t p_first = p_wave;
 #pragma unroll
         for (uint32_t r = 0; r < SSEQ_UNROLL; ++r) {
             const uint64_t u = u0 + (uint64_t)r * KMP_WAVE + lane;
-            v[r] = (sseq_u32x4)(0u);
+            v[r] = (u32x4)(0u);
             if (u < u_end) {
                 const uint64_t d = u * 16u;
                 /* piece_dst[0] == 0 <= d */

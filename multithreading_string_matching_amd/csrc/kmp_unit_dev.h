@@ -1,8 +1,8 @@
 /*
- * kmp_unit_dev.h -- what the kernels of kmp_decode.hip and kmp_base64.hip share: both deal the 16-byte units of a RUN of consecutive
- * payloads to the lanes in order (lane i puts payload i of the run into the wavefront's LDS, a lane finds the payload of its unit with
- * a branch-free binary search over the run's unit prefix sums), classify bytes by SWAR compares on dwords, sum per payload with a DPP
- * scan over the wavefront, and stage compacted output through the wavefront's own LDS.  Device code only; gfx950.
+ * kmp_unit_dev.h -- the 16-byte unit every arena builder moves payload bytes in, and what the builders share around it: its loads and
+ * stores, the one byte mask (below_mask, keep_bytes), byte classes by SWAR compares on dwords, the wavefront's scans, the sync of a wavefront's own
+ * LDS, and the units of a RUN of consecutive payloads dealt to the lanes in order (Unit, find_payload, load_step).  The skeleton built
+ * on these is kmp_compact_dev.h.  Device code only; gfx950.
  */
 #ifndef KMP_UNIT_DEV_H
 #define KMP_UNIT_DEV_H
@@ -68,16 +68,17 @@ static __device__ __forceinline__ void store_unit(uint8_t *p, u32x4 v)
     if (NT) __builtin_nontemporal_store(v, q); else *q = v;
 }
 
+/* The one byte mask: 0xFF in the bytes below position x of dword d of a unit (byte positions 4 d .. 4 d + 3), 0 <= x; x >= 16: all */
+static __device__ __forceinline__ uint32_t below_mask(uint32_t x, uint32_t d)
+{
+    const uint32_t b = 4u * d;
+    return (x >= b + 4u) ? 0xFFFFFFFFu : (x <= b) ? 0u : ((1u << (8u * (x - b))) - 1u);
+}
 /* the bytes [keep, 16) of a unit cleared; keep >= 16 leaves it whole */
 static __device__ __forceinline__ u32x4 keep_bytes(u32x4 v, uint32_t keep)
 {
-    uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (uint32_t d = 0; d < 4u; ++d) {
-        const uint32_t lo = 4u * d;
-        w[d] &= (keep >= lo + 4u) ? 0xFFFFFFFFu : (keep <= lo) ? 0u : ((1u << (8u * (keep - lo))) - 1u);
-    }
-    u32x4 r; r.x = w[0]; r.y = w[1]; r.z = w[2]; r.w = w[3];
+    u32x4 r;
+    r.x = v.x & below_mask(keep, 0u); r.y = v.y & below_mask(keep, 1u); r.z = v.z & below_mask(keep, 2u); r.w = v.w & below_mask(keep, 3u);
     return r;
 }
 

@@ -1645,7 +1645,7 @@ static int load_recoded(kmpgpu_ctx *dst, kmpgpu_ctx *src, const Recoding &how, u
         HIP_TRY(kmp_launch_decode_lengths(src->d_arena, src->d_off, src->d_len, n, how.plus, only_changed, c->fr_ws, c->d_dec_changed, d_stats, c->stream));
     HIP_TRY(profile_launched(c, e1));
     HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_decode_scan(n, c->fr_ws, c->fr_tot, c->stream));
+    HIP_TRY(kmp_launch_compact_scan(n, c->fr_ws, c->fr_tot, c->stream));
     HIP_TRY(profile_launched(c, e1));
     HIP_TRY(hipMemcpyAsync(c->h_small, c->fr_tot, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));         /* (pinned: no staging) */
     HIP_TRY(hipMemcpyAsync(c->h_small + 2, d_stats, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
@@ -1843,7 +1843,7 @@ int kmpgpu_load_fields(kmpgpu_ctx *dst, kmpgpu_ctx *src, int field, uint32_t fla
     HIP_TRY(kmp_launch_fields_lengths(src->d_spans, src->d_len, n, field, only_present, c->fr_ws, c->d_dec_changed, d_stats, c->stream));
     HIP_TRY(profile_launched(c, e1));
     HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_fields_scan(n, c->fr_ws, c->fr_tot, c->stream));
+    HIP_TRY(kmp_launch_compact_scan(n, c->fr_ws, c->fr_tot, c->stream));
     HIP_TRY(profile_launched(c, e1));
     HIP_TRY(hipMemcpyAsync(c->h_small, c->fr_tot, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));         /* (pinned: no staging) */
     HIP_TRY(hipMemcpyAsync(c->h_small + 2, d_stats, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
@@ -2992,7 +2992,7 @@ int kmpgpu_scan_alerts(kmpgpu_ctx *c, int family, uint64_t max_records, uint64_t
     HIP_TRY(kmp_launch_alerts_count(f.d_rows, p.stride, (uint32_t)f.n_rows, c->n_pkts, f.d_any, c->fr_ws, c->stream));
     HIP_TRY(profile_launched(c, e1));
     HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_alerts_scan(c->n_pkts, c->fr_ws, c->fr_tot, c->stream));
+    HIP_TRY(kmp_launch_compact_scan(c->n_pkts, c->fr_ws, c->fr_tot, c->stream));
     HIP_TRY(profile_launched(c, e1));
     HIP_TRY(hipMemcpyAsync(c->h_small, c->fr_tot, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));         /* (pinned: no staging) */
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -3071,7 +3071,7 @@ int kmpgpu_flows_build(kmpgpu_ctx *c, uint32_t flags, uint64_t *n_flows, kmpgpu_
     HIP_TRY(kmp_launch_flows_firsts(c->d_flow_first, c->d_flow_of, n, c->fr_ws, c->stream));
     HIP_TRY(profile_launched(c, e1));
     HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_flows_scan(n, c->fr_ws, c->fr_tot, c->stream));
+    HIP_TRY(kmp_launch_compact_scan(n, c->fr_ws, c->fr_tot, c->stream));
     HIP_TRY(profile_launched(c, e1));
     HIP_TRY(hipMemcpyAsync(c->h_small, c->fr_tot, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));         /* (pinned: no staging) */
     HIP_TRY(hipStreamSynchronize(c->stream));

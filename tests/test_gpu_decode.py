@@ -6,6 +6,7 @@ Where the kernels of csrc/kmp_decode.hip take another path:
   an escape straddling two 16-byte units (two lanes) or two steps of 64 units (lane 63 / lane 0)      test_boundaries
   an escape that ends at the payload's end, an incomplete one at L - 2 and L - 1                       test_boundaries
   a step without an escape at a 16-byte aligned output position (the straight copy) / any other one    test_densities
+  a step with a '%' in it and no escape: the neighbours are asked, and the step is still copied        test_densities[lone_percent]
   runs of 64 payloads and a rest                                                                      test_densities[64 bytes]
   nothing behind a payload's end decodes: dirty padding, the next slot, the arena's end                test_sources_*
   source offsets across and behind 2^32                                                               test_high_offsets
@@ -151,7 +152,10 @@ def test_boundaries(src, dst, boundaries, plus, only_changed):
 # 6. densities
 # ------------------------------------------------------------------------------------------------
 def density_payloads(kind):
-    rng = np.random.default_rng({"hostile": 1, "all_escaped": 2, "no_percent": 3, "64_bytes": 4}[kind])
+    rng = np.random.default_rng({"hostile": 1, "all_escaped": 2, "no_percent": 3, "64_bytes": 4, "lone_percent": 5}[kind])
+    if kind == "lone_percent":
+        # one run of 60 payloads of up to 80 bytes: a '%' in every unit, never two hex digits behind it, no '+'
+        return [bytes(0x25 if j % 7 == 0 else 0x67 + (i + j) % 16 for j in range(int(L))) for i, L in enumerate(rng.integers(0, 81, 60))]
     if kind == "hostile":
         return [DM.random_payload(rng, int(L)) for L in rng.integers(0, 3001, 200)]
     if kind == "all_escaped":
@@ -163,7 +167,7 @@ def density_payloads(kind):
     return out
 
 
-@pytest.mark.parametrize("kind", ["hostile", "all_escaped", "no_percent", "64_bytes"])
+@pytest.mark.parametrize("kind", ["hostile", "all_escaped", "no_percent", "64_bytes", "lone_percent"])
 def test_densities(src, dst, third, kind):
     payloads = density_payloads(kind)
     try:
@@ -173,6 +177,8 @@ def test_densities(src, dst, third, kind):
             want = decode_and_check(dst, src, payloads, plus, only_changed)
             if kind == "all_escaped":
                 assert want["stats"]["bytes_in"] == 3 * want["stats"]["bytes_out"]
+            if kind == "lone_percent":
+                assert want["stats"]["n_changed"] == 0
         if kind == "no_percent":
             # nothing to decode: byte for byte what kmpgpu_load_selected with all bits set makes of the source
             dst.load_decoded(src)

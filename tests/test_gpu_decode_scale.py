@@ -1,9 +1,9 @@
 """kmpgpu_load_decoded past every grid cap of csrc/kmp_decode.hip, on a real MI355X.
 
-  kmp_decode_lengths_kernel   KMP_DECODE_LENGTHS_BLOCKS 1 024 blocks * 4 wavefronts * 64 payloads: a second round past 262 144 payloads
-  kmp_decode_index_kernel     KMP_DECODE_INDEX_BLOCKS 1 024 * 256 threads: past 262 144 payloads
+  kmp_decode_lengths_kernel   KMP_GRID_CAP 1 024 blocks * 4 wavefronts * 64 payloads: a second round past 262 144 payloads
+  kmp_decode_index_kernel     KMP_GRID_CAP 1 024 * 256 threads: past 262 144 payloads
   kmp_scan_totals_kernel      one round of 256 block totals (kmp_prep.hip)
-  kmp_decode_write_kernel     KMP_DECODE_WRITE_BLOCKS 1 024 * 4 runs: past 4 096 runs -- runs of 64 payloads of 16..48 bytes (262 144
+  kmp_decode_write_kernel     KMP_GRID_CAP 1 024 * 4 runs: past 4 096 runs -- runs of 64 payloads of 16..48 bytes (262 144
                               payloads), runs of 4 payloads of ~3 000 bytes (16 384 payloads)
 
 The arenas are periodic: 257 distinct payloads with escapes, repeated.  tests/decode_model.py decodes the 257 once; what dst has to

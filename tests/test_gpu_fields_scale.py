@@ -2,10 +2,10 @@
 
   kmp_http_locate_kernel      FLD_LOCATE_BLOCKS 2 048 blocks * 4 wavefronts * 64 payloads: a second round past 524 288 payloads; payloads of
                               ~3 000 bytes take three steps of 1 KiB each
-  kmp_fields_lengths_kernel   FLD_LENGTHS_BLOCKS 1 024 * 4 * 64: past 262 144 payloads
-  kmp_fields_index_kernel     FLD_INDEX_BLOCKS 1 024 * 256 threads: past 262 144 payloads
+  kmp_fields_lengths_kernel   KMP_GRID_CAP 1 024 * 4 * 64: past 262 144 payloads
+  kmp_fields_index_kernel     KMP_GRID_CAP 1 024 * 256 threads: past 262 144 payloads
   kmp_scan_totals_kernel      one round of 256 block totals (kmp_prep.hip)
-  kmp_fields_gather_kernel    FLD_GATHER_BLOCKS 1 024 * 4 runs: past 4 096 runs -- runs of 64 fields of 0..40 bytes (262 144 payloads), runs
+  kmp_fields_gather_kernel    KMP_GRID_CAP 1 024 * 4 runs: past 4 096 runs -- runs of 64 fields of 0..40 bytes (262 144 payloads), runs
                               of 4 fields of ~2 600 bytes (16 384 payloads of dst)
 
 The arenas are periodic (gpu_support.PeriodicSource): 257 distinct payloads, repeated, laid out on the device.  tests/http_model.py

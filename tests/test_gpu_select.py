@@ -13,13 +13,13 @@ Where every kernel's second code path starts, read off the launchers of csrc/kmp
   S1   kmp_select_lengths_kernel, a second bitmap word   > 64 payloads                                        test_sizes_and_densities[65 ...]
   S2   kmp_scan_local_kernel, a second tile              > 1 024 payloads (256 threads * 4 items)             test_sizes_and_densities[1025], test_at_scale
   S3   kmp_scan_totals_kernel, carries                   > 262 144 payloads (256 tiles per round)             test_at_scale (300 001)
-  S4   kmp_select_lengths_kernel and                     > 262 144 payloads (KMP_SELECT_INDEX_BLOCKS 1 024    test_at_scale
+  S4   kmp_select_lengths_kernel and                     > 262 144 payloads (KMP_GRID_CAP 1 024    test_at_scale
        kmp_select_index_kernel: grid-stride                * 256 threads)
-  S5   kmp_select_copy_kernel, r += waves                > 4 096 runs (KMP_SELECT_COPY_BLOCKS 1 024 * 4       test_at_scale[all, random_0.9, words, alternating]:
+  S5   kmp_select_copy_kernel, r += waves                > 4 096 runs (KMP_GRID_CAP 1 024 * 4       test_at_scale[all, random_0.9, words, alternating]:
                                                            waves); a run is 64 payloads at these sizes           > 262 144 selected payloads
   S6   kmp_select_copy_kernel, run length                64 payloads per run while the average slot is        test_sizes_and_densities (1 500- and 9 000-byte
                                                            <= 256 bytes, halved down to 1 from there on         payloads among 16-byte ones), test_dst_state_* (uniform
-                                                           (KMP_SELECT_RUN_BYTES 16 384)                        1 500: runs of 8), test_long_payloads (runs of 1)
+                                                           (KMP_RUN_BYTES 16 384)                        1 500: runs of 8), test_long_payloads (runs of 1)
   S7   kmp_select_copy_kernel, a run of more than        a lane's second step: runs of > 4 KiB                every test with payloads of 100 bytes and more
        4 * 64 units
   S8   source offsets as 64-bit values                   > 4 GiB                                              test_source_past_4_gib
