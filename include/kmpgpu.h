@@ -1009,6 +1009,70 @@ int  kmpgpu_load_fields(kmpgpu_ctx *dst, kmpgpu_ctx *src, int field, uint32_t fl
                         uint64_t *present_out /* host [ceil(n_src / 64)] or NULL */, const void **d_present /* or NULL */,
                         kmpgpu_fields_stats *stats /* or NULL */);
 
+/* DNS query-name buffers: the name of the first question of the DNS message in every payload, in dotted form, as a packed arena that a
+ * second context owns -- the dns.query / dns_query buffer of signature languages.  On the wire `www.youtube.com` is
+ * \x03www\x07youtube\x03com\x00, so no pattern over the payload itself can name a host; in dst a pattern `youtube.com` can.
+ * Definition.  Let payload k be the bytes p[0..L), L = pkt_len[k]: the whole payload, whatever KMPGPU_OPT_WHOLE_PAYLOAD says.  No byte at
+ * or behind L takes part: slot padding of a borrowed arena may be dirty.  b = 2 under KMPGPU_DNS_TCP_PREFIX (DNS over TCP: a 2-byte
+ * length in front, which is not checked against L), otherwise b = 0.  Let m[i] = p[b + i] and M = L - b.
+ * The payload is NONE, with every field absent and an all-zero record, unless all of these hold:
+ *   M >= 17.
+ *   QDCOUNT = be16(m[4..6)) >= 1.
+ *   The walk succeeds.  It starts at i_0 = 12.  At step t, c = m[i_t] needs i_t < M.  c == 0 ends the name at i_end = i_t.  1 <= c <= 63
+ *     needs i_t + 1 + c <= M and gives i_{t+1} = i_t + 1 + c.  c >= 64 makes the payload NONE: a compression pointer or a reserved label
+ *     type (a pointer in the first question can only point into the header).
+ *   i_end + 1 - 12 <= 255: the wire length of a name, so at most 127 labels.
+ *   i_end + 5 <= M: QTYPE and QCLASS lie inside the payload.
+ * Fields of a payload that is not NONE:
+ *   kind is QUERY where bit 15 of the flags word be16(m[2..4)) is clear, otherwise RESPONSE.
+ *   QNAME is the bytes m[13..i_end) with every m[i_t], t >= 1, replaced by '.'.  It is always present, and its length is
+ *     max(0, i_end - 13).  The root name is present and empty.
+ *   Bytes are taken as they are: no escaping of a '.' or a control byte inside a label, and no case folding -- nocase patterns are the
+ *     route against 0x20 mixing.
+ * Limits: the first question's name only; no compression pointers; no names of answers, authorities or RDATA; no
+ * detection by port; one message per payload; no IDNA decoding.
+ *
+ * kmpgpu_dns_locate decides all of this for every payload of ctx's arena in one kernel and keeps one kmpgpu_dns_span per payload on the
+ * device.  Offsets count from p[0]: name_off = b + 13, q_end = b + i_end + 5; id, qtype, qclass and the four counts are host-order values
+ * of the big-endian wire fields, n_labels the labels walked; a NONE payload's record is all zero.  flags: 0 or KMPGPU_DNS_TCP_PREFIX.
+ * *stats (may be NULL): the queries, the responses, the root names among both, and the bytes of all names.  The spans belong to the
+ * arena: exactly the calls that drop the HTTP spans drop them, a scan does not.  They are valid for the prefix flag they were made with:
+ * with valid spans of the same flag the call launches nothing and hands out the stats again, with the other flag it runs again.
+ * kmpgpu_dns_spans_read copies records [first, first + n) to the host (KMPGPU_ESTATE without valid spans, KMPGPU_EINVAL for a range that
+ * leaves them).  Both are synchronous on ctx's stream; KMPGPU_ESTATE between kmpgpu_load_frames_begin and _finish, KMPGPU_EINVAL for an
+ * unknown flag bit.  kmpgpu_last_timing: kernel_ms of the locate, launches = 1 (0 where the spans were valid); kmpgpu_profile_begin ..
+ * _end time it as one pair.
+ *
+ * kmpgpu_load_dns makes dst's arena the field `field` (KMPGPU_DNS_QNAME) of every payload of src, running the locate on src first where
+ * src's spans are stale or of the other prefix flag.  flags: KMPGPU_DNS_ONLY_PRESENT (dst holds only the payloads that are messages) and
+ * KMPGPU_DNS_TCP_PREFIX.  The result layout, present_out / *d_present, *stats, the metadata carried along, the state dst's arena is left
+ * in, dst without an arena and KMPGPU_OK where no payload is held or n_src == 0, the workspace and the ordering are those of
+ * kmpgpu_load_fields, word for word; src keeps everything but its span cache, and every output of it is bit-identical before and after.
+ * Errors, all refused before any launch: dst == src, a NULL context, contexts on different devices, an unknown field, an unknown flag
+ * bit: KMPGPU_EINVAL; either context between kmpgpu_load_frames_begin and _finish: KMPGPU_ESTATE; after each of these dst keeps the
+ * arena it had.  kmpgpu_last_timing(dst) and kmpgpu_profile_begin .. _end: as kmpgpu_load_fields (lengths, two scan kernels, index,
+ * gather: 5 launches; 3 where dst ends up without a payload; one more where the locate ran).
+ * Cost: the locate reads the first 16 bytes of every payload and of the messages the units that hold a length byte
+ * of the name; the load reads the spans twice, the separator masks and the name bytes once, and writes the names once. */
+#define KMPGPU_DNS_NONE      0      /* kmpgpu_dns_span.kind */
+#define KMPGPU_DNS_QUERY     1
+#define KMPGPU_DNS_RESPONSE  2
+typedef struct kmpgpu_dns_span {
+    uint8_t  kind, n_labels;
+    uint16_t flags;                    /* the flags word */
+    uint16_t id, qtype, qclass, qdcount, ancount, nscount, arcount, reserved;
+    uint32_t name_off, name_len, q_end;
+} kmpgpu_dns_span;
+typedef struct kmpgpu_dns_stats { uint64_t n_queries, n_responses, n_root, name_bytes; } kmpgpu_dns_stats;
+#define KMPGPU_DNS_QNAME        1      /* field */
+#define KMPGPU_DNS_ONLY_PRESENT 1u     /* flags of kmpgpu_load_dns: dst holds only the payloads that are DNS messages */
+#define KMPGPU_DNS_TCP_PREFIX   2u     /* flags of both: a 2-byte length stands in front of the message */
+int  kmpgpu_dns_locate(kmpgpu_ctx *ctx, uint32_t flags, kmpgpu_dns_stats *stats /* or NULL */);
+int  kmpgpu_dns_spans_read(kmpgpu_ctx *ctx, kmpgpu_dns_span *out, uint64_t first, uint64_t n);
+int  kmpgpu_load_dns(kmpgpu_ctx *dst, kmpgpu_ctx *src, int field, uint32_t flags,
+                     uint64_t *present_out /* host [ceil(n_src / 64)] or NULL */, const void **d_present /* or NULL */,
+                     kmpgpu_fields_stats *stats /* or NULL */);
+
 /* Flows: the payloads of the arena grouped by the 5-tuple of their metadata (kmpgpu_pkt_meta, above), on the device -- which payloads
  * belong to one connection, what each connection carried, and the hit rows of every family folded from payload space into flow space.
  * Definitions.  With M = meta[k], the two endpoints of payload k are the 48-bit integers e_src = src_ip << 16 | src_port and

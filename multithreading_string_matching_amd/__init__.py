@@ -25,6 +25,9 @@ from .matcher import (  # noqa: F401
     DECODE_ONLY_CHANGED,
     DECODE_PERCENT,
     DECODE_PLUS,
+    DNS_ONLY_PRESENT,
+    DNS_QNAME,
+    DNS_TCP_PREFIX,
     FIELD_BODY,
     FIELD_HEADERS,
     FIELD_METHOD,

@@ -171,6 +171,18 @@ class HttpStats(C.Structure):
     _fields_ = [("n_requests", C.c_uint64), ("n_responses", C.c_uint64), ("n_blank", C.c_uint64), ("bytes_scanned", C.c_uint64)]
 
 
+class DnsStats(C.Structure):
+    """kmpgpu_dns_stats (include/kmpgpu.h)."""
+    _fields_ = [("n_queries", C.c_uint64), ("n_responses", C.c_uint64), ("n_root", C.c_uint64), ("name_bytes", C.c_uint64)]
+
+
+class DnsSpan(C.Structure):
+    """kmpgpu_dns_span (include/kmpgpu.h), 32 bytes."""
+    _fields_ = [("kind", C.c_uint8), ("n_labels", C.c_uint8), ("flags", C.c_uint16), ("id", C.c_uint16), ("qtype", C.c_uint16),
+                ("qclass", C.c_uint16), ("qdcount", C.c_uint16), ("ancount", C.c_uint16), ("nscount", C.c_uint16), ("arcount", C.c_uint16),
+                ("reserved", C.c_uint16), ("name_off", C.c_uint32), ("name_len", C.c_uint32), ("q_end", C.c_uint32)]
+
+
 class FieldsStats(C.Structure):
     """kmpgpu_fields_stats (include/kmpgpu.h)."""
     _fields_ = [("n_payloads", C.c_uint64), ("n_present", C.c_uint64), ("bytes_in", C.c_uint64), ("bytes_out", C.c_uint64)]
@@ -334,6 +346,9 @@ GPU_API = {
     "kmpgpu_http_locate": (C.c_int, [C.c_void_p, C.POINTER(HttpStats)]),
     "kmpgpu_http_spans_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "kmpgpu_load_fields": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(FieldsStats)]),
+    "kmpgpu_dns_locate": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(DnsStats)]),
+    "kmpgpu_dns_spans_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "kmpgpu_load_dns": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(FieldsStats)]),
     "kmpgpu_flows_build": (C.c_int, [C.c_void_p, C.c_uint32, u64p, C.POINTER(Timing)]),
     "kmpgpu_flows_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "kmpgpu_flow_ids_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),

@@ -121,6 +121,15 @@
  * value; the variable together with KMPGPU_DECODE, KMPGPU_HTTP_FIELD, KMPGPU_OFFSETS_FILE, KMPGPU_EXPORT_FILE, KMPGPU_FLOW_SEAMS,
  * KMPGPU_FLOW_STREAMS, KMPGPU_FLOWBITS_FILE or KMPGPU_THRESHOLDS_FILE; the variable with none of the three row outputs.
  *
+ * KMPGPU_DNS_FIELD=qname[,tcp], together with at least one of KMPGPU_PACKETS_FILE, KMPGPU_ALERTS_FILE and KMPGPU_FLOW_ALERTS_FILE: these row
+ * outputs are decided on the dotted name of the first question of the DNS message in every payload (kmpgpu_load_dns; the definition:
+ * kmpgpu.h; ,tcp: a 2-byte length stands in front of every message), so that a rule that names `doubleclick.net` meets the queried name.
+ * Per shard a second context on the shard's device gets the same tables as the shard's (upload_tables) and the name buffer of the shard's
+ * arena, every payload (no message: an empty payload), so the payload numbers are the capture's.  stdout and KMPGPU_FLOWS_FILE are what
+ * they are without the variable.  Refused with a message on stderr and exit 1, before any GPU work: any other value; the variable together
+ * with KMPGPU_DECODE, KMPGPU_HTTP_FIELD, KMPGPU_BASE64, KMPGPU_OFFSETS_FILE, KMPGPU_EXPORT_FILE, KMPGPU_FLOW_SEAMS, KMPGPU_FLOW_STREAMS,
+ * KMPGPU_FLOWBITS_FILE or KMPGPU_THRESHOLDS_FILE; the variable with none of the three row outputs.
+ *
  * KMPGPU_FLOW_STREAMS=<depth>, together with KMPGPU_FLOW_ALERTS_FILE: the flow alerts are decided on the reassembled streams.  A second
  * context on the shard's device gets the same tables as the shard's (upload_tables; the windows too: on a stream they mean "offset in the
  * connection's direction") and the payloads of every flow direction concatenated in capture order and cut to <depth> bytes
@@ -174,6 +183,7 @@
 #include "kmp_cli_decode.h"
 #include "kmp_cli_base64.h"
 #include "kmp_cli_fields.h"
+#include "kmp_cli_dns.h"
 #include "kmp_cli_streams.h"
 #include "kmp_cli_streams_order.h"
 
@@ -201,6 +211,7 @@ typedef struct cli_options {
     uint32_t flow_seams;                    /* KMPGPU_FLOW_SEAMS: the reach, 0 without the variable */
     int decode;                             /* KMPGPU_DECODE: KMP_CLI_DECODE_* */
     int http_field;                         /* KMPGPU_HTTP_FIELD: KMP_CLI_FIELD_* */
+    int dns_field, dns_tcp;                 /* KMPGPU_DNS_FIELD: KMP_CLI_DNS_*, and ",tcp" */
     unsigned base64_min_run;                /* KMPGPU_BASE64: min_run, 0 = not set */
     int base64_url;                         /* ... ,url */
     uint32_t flow_streams;                  /* KMPGPU_FLOW_STREAMS: the depth, 0 without the variable */
@@ -253,7 +264,7 @@ typedef struct cli_run {
     int ndev, shards, reduce_rccl, rules_set;
     shard_job *job;
     kmpgpu_ctx **ctxs;                      /* ctxs[r] = job[r].ctx */
-    kmpgpu_ctx **rows;                      /* rows[r]: the context the row outputs of shard r come from -- ctxs[r], or with KMPGPU_DECODE its decoding, with KMPGPU_HTTP_FIELD its field buffer, with KMPGPU_BASE64 its base64 decoding */
+    kmpgpu_ctx **rows;                      /* rows[r]: the context the row outputs of shard r come from -- ctxs[r], or with KMPGPU_DECODE its decoding, with KMPGPU_HTTP_FIELD its field buffer, with KMPGPU_BASE64 its base64 decoding, with KMPGPU_DNS_FIELD its name buffer */
     kmpgpu_comm *comm;
     uint64_t *own, *counts;                 /* own[r * n_patterns + i]: shard r's count of pattern i; counts[i]: the total */
     double kernel_ms;
@@ -599,6 +610,33 @@ static void load_options(int argc, char *argv[], cli_options *opt)
             exit(1);
         }
     }
+    /* the DNS name buffer: it changes what the row outputs hold and nothing else */
+    const char *dns_env = env_path("KMPGPU_DNS_FIELD");
+    if (dns_env) {
+        static const char *const not_with[][2] = {
+            {"KMPGPU_DECODE", "a name is taken as it is on the wire; at the library, kmpgpu_load_decoded over the name context decodes it"},
+            {"KMPGPU_HTTP_FIELD", "one buffer per run"},
+            {"KMPGPU_BASE64", "base64 in a name buffer is not wired in this program"},
+            {"KMPGPU_OFFSETS_FILE", "offsets in a name are not mapped back to the capture's"},
+            {"KMPGPU_EXPORT_FILE", "the export selects and writes the payloads as captured"},
+            {"KMPGPU_FLOW_SEAMS", "seams of names do not exist"},
+            {"KMPGPU_FLOW_STREAMS", "names of streams are not wired in this program"},
+            {"KMPGPU_FLOWBITS_FILE", "flow bits over a name buffer are not wired in this program"},
+            {"KMPGPU_THRESHOLDS_FILE", "a name buffer keeps no timestamps in this program"}};
+        if (!kmp_cli_parse_dns(dns_env, &opt->dns_field, &opt->dns_tcp)) {
+            fprintf(stderr, "KMPGPU_DNS_FIELD is \"%s\": qname or qname,tcp is needed\n", dns_env);
+            exit(1);
+        }
+        for (size_t i = 0; i < sizeof not_with / sizeof not_with[0]; i++)
+            if (env_path(not_with[i][0])) {
+                fprintf(stderr, "KMPGPU_DNS_FIELD does not go together with %s: %s\n", not_with[i][0], not_with[i][1]);
+                exit(1);
+            }
+        if (!opt->packets_path && !opt->alerts_path && !opt->flow_alerts_path) {
+            fprintf(stderr, "KMPGPU_DNS_FIELD has no effect without KMPGPU_PACKETS_FILE, KMPGPU_ALERTS_FILE or KMPGPU_FLOW_ALERTS_FILE\n");
+            exit(1);
+        }
+    }
     opt->want_meta = opt->headers.n || opt->flows_path || opt->flow_alerts_path || opt->flowbits.n || opt->thresholds_by_flow || opt->thresholds_by_addr;
     /* the export starts as a capture without frames: a path that cannot be written ends the run here */
     if (opt->export_path && kmp_write_udp_pcap_part(opt->export_path, 0, NULL, NULL, NULL, 0, 0)) {
@@ -820,6 +858,21 @@ static void field_shards(const cli_options *opt, cli_run *run)
             if (kmpgpu_load_decoded(d, raw, KMPGPU_DECODE_PERCENT, 0u, NULL, NULL, NULL)) die_gpu("kmpgpu_load_decoded");
             kmpgpu_destroy(raw);
         } else if (kmpgpu_load_fields(d, run->ctxs[r], field, 0u, NULL, NULL, NULL)) die_gpu("kmpgpu_load_fields");
+        run->rows[r] = d;
+    }
+}
+
+/* KMPGPU_DNS_FIELD: as field_shards, the dotted name of the first question of every payload of the shard (no message: an empty payload). */
+static void dns_shards(const cli_options *opt, cli_run *run)
+{
+    _Static_assert(KMP_CLI_DNS_QNAME == KMPGPU_DNS_QNAME, "KMP_CLI_DNS_QNAME is the value of KMPGPU_DNS_QNAME");
+    const uint32_t flags = opt->dns_tcp ? KMPGPU_DNS_TCP_PREFIX : 0u;
+    for (int r = 0; r < run->shards; r++) {
+        kmpgpu_ctx *d = NULL;
+        if (kmpgpu_init(&d, run->job[r].device)) die_gpu("kmpgpu_init");
+        const char *failed = upload_tables(d, opt);
+        if (failed) die_gpu(failed);
+        if (kmpgpu_load_dns(d, run->ctxs[r], opt->dns_field, flags, NULL, NULL, NULL)) die_gpu("kmpgpu_load_dns");
         run->rows[r] = d;
     }
 }
@@ -1104,6 +1157,7 @@ int main(int argc, char *argv[])
         if (opt.decode) decode_shards(&opt, &run);
         if (opt.base64_min_run) base64_shards(&opt, &run);
         if (opt.http_field) field_shards(&opt, &run);
+        if (opt.dns_field) dns_shards(&opt, &run);
         if (opt.offsets_path) write_offsets(opt.offsets_path, &run, n);
         if (opt.packets_path) write_alerts(opt.packets_path, &opt, &run, KMPGPU_ALERT_PATTERNS);
         if (opt.alerts_path) write_alerts(opt.alerts_path, &opt, &run, KMPGPU_ALERT_RULES);

@@ -235,6 +235,14 @@ struct kmpgpu_ctx {
     uint64_t            spans_cap = 0;                /* 16-byte units */
     uint64_t            http_stats[4] = {0, 0, 0, 0};
     bool                spans_valid = false;
+    /* kmpgpu_dns_locate: one kmpgpu_dns_span per payload, the separator masks (two 16-byte units per payload as well), the four words
+     * the kernel counts in, and those words on the host.  dns_valid: they describe the arena that is attached now, for the prefix flag
+     * dns_prefix (dropped with the HTTP spans: drop_spans) */
+    uint4              *d_dns = nullptr;
+    uint64_t            dns_cap = 0;                  /* 16-byte units */
+    uint64_t            dns_stats[4] = {0, 0, 0, 0};
+    bool                dns_valid = false;
+    uint32_t            dns_prefix = 0;
     int64_t             flow_slots = 0;               /* KMPGPU_OPT_FLOW_SLOTS */
     /* which build of the flows the context holds: kmpgpu_flows_build and drop_flows start a new generation, and id tells one context from
      * every other the process has made (a seam list names the context and the generation it was built from) */
@@ -513,8 +521,8 @@ void drop_flows(kmpgpu_ctx *c, bool rebuild = false)
     if (!rebuild) c->meta_gen++;                   /* the arena or its metadata change: the thresholds' address orders are none of the next one's */
 }
 
-/* the HTTP spans go with the arena whose payloads they describe; their buffer is kept for the next locate */
-void drop_spans(kmpgpu_ctx *c) { c->spans_valid = false; }
+/* the HTTP spans and the DNS spans go with the arena whose payloads they describe; their buffers are kept for the next locate */
+void drop_spans(kmpgpu_ctx *c) { c->spans_valid = c->dns_valid = false; }
 
 /* the seam list goes with the arena it describes; its buffers are kept for the next build */
 void drop_seams(kmpgpu_ctx *c)
@@ -642,7 +650,7 @@ void release_pass_buffers(kmpgpu_ctx *c)
     free_buffer(&c->d_flow_table, &c->flow_table_cap); free_buffer(&c->d_flow_first, &c->flow_first_cap); free_buffer(&c->d_flow_of, &c->flow_of_cap);
     free_buffer(&c->d_flow_recs, &c->flow_recs_cap); free_buffer(&c->d_flow_fold, &c->flow_fold_cap); free_buffer(&c->d_flow_sel, &c->flow_sel_cap);
     free_buffer(&c->d_dec_changed, &c->dec_changed_cap);
-    free_buffer(&c->d_spans, &c->spans_cap); drop_spans(c);
+    free_buffer(&c->d_spans, &c->spans_cap); free_buffer(&c->d_dns, &c->dns_cap); drop_spans(c);
     drop_flows(c);
     free_buffer(&c->d_seams, &c->seams_cap); free_buffer(&c->d_seam_flow, &c->seam_flow_cap); free_buffer(&c->d_seam_sort, &c->seam_sort_cap);
     drop_seams(c);
@@ -1735,32 +1743,79 @@ int kmpgpu_load_base64(kmpgpu_ctx *dst, kmpgpu_ctx *src, uint32_t min_run, uint3
     return load_recoded(dst, src, how, changed_out, d_changed, stats);
 }
 
-/* The spans of src's arena, made on the stream of `on` (src itself, or the dst of kmpgpu_load_fields, which has waited for src's stream)
- * where they are stale; *launched: the kernel ran.  The caller synchronises the stream before it reads src->http_stats. */
-static int locate_spans(kmpgpu_ctx *src, kmpgpu_ctx *on, const char *who, bool *launched)
+/* Which spans a call means: the HTTP ones, or the DNS ones for a prefix flag (KMPGPU_DNS_TCP_PREFIX or 0). */
+struct SpanKind { bool dns; uint32_t prefix; };
+static bool spans_current(const kmpgpu_ctx *c, SpanKind sk) { return sk.dns ? c->dns_valid && c->dns_prefix == sk.prefix : c->spans_valid; }
+
+/* The spans of src's arena, made on the stream of `on` (src itself, or the dst of kmpgpu_load_fields / kmpgpu_load_dns, which has waited
+ * for src's stream) where they are stale; *launched: the kernel ran.  The caller synchronises the stream before it reads the stats. */
+static int locate_spans(kmpgpu_ctx *src, kmpgpu_ctx *on, SpanKind sk, const char *who, bool *launched)
 {
     *launched = false;
-    if (src->spans_valid) return KMPGPU_OK;
+    if (spans_current(src, sk)) return KMPGPU_OK;
     const uint64_t n = src->n_pkts;
-    memset(src->http_stats, 0, sizeof src->http_stats);
-    if (n == 0) { src->spans_valid = true; return KMPGPU_OK; }
-    const hipError_t e = grow_buffer(&src->d_spans, &src->spans_cap, 2 * n + 2, EIGHTH);       /* 32 bytes per payload, 4 words of totals */
+    uint64_t *h_stats = sk.dns ? src->dns_stats : src->http_stats;
+    memset(h_stats, 0, 4 * sizeof(uint64_t));
+    if (sk.dns) { src->dns_valid = false; src->dns_prefix = sk.prefix; }
+    if (n == 0) { (sk.dns ? src->dns_valid : src->spans_valid) = true; return KMPGPU_OK; }
+    /* 32 bytes per payload, for DNS the separator masks of 32 bytes per payload behind them, 4 words of totals */
+    const uint64_t units = sk.dns ? 4 * n : 2 * n;
+    const hipError_t e = sk.dns ? grow_buffer(&src->d_dns, &src->dns_cap, units + 2, EIGHTH) : grow_buffer(&src->d_spans, &src->spans_cap, units + 2, EIGHTH);
     if (e != hipSuccess) return alloc_fail(e, "%s: the spans (%llu payloads) could not be allocated", who, (unsigned long long)n);
-    unsigned long long *d_stats = reinterpret_cast<unsigned long long *>(src->d_spans + 2 * n);
+    uint4 *d = sk.dns ? src->d_dns : src->d_spans;
+    unsigned long long *d_stats = reinterpret_cast<unsigned long long *>(d + units);
     HIP_TRY(hipMemsetAsync(d_stats, 0, 4 * sizeof(unsigned long long), on->stream));
     hipEvent_t e1;
     HIP_TRY(profile_launch(on, &e1));
-    HIP_TRY(kmp_launch_http_locate(src->d_arena, src->d_off, src->d_len, n, src->d_spans, d_stats, on->stream));
+    if (sk.dns) HIP_TRY(kmp_launch_dns_locate(src->d_arena, src->d_off, src->d_len, n, sk.prefix != 0u, d, d + 2 * n, d_stats, on->stream));
+    else HIP_TRY(kmp_launch_http_locate(src->d_arena, src->d_off, src->d_len, n, d, d_stats, on->stream));
     HIP_TRY(profile_launched(on, e1));
     HIP_TRY(hipMemcpyAsync(on->h_small + 8, d_stats, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, on->stream));         /* (pinned: no staging) */
     *launched = true;
     return KMPGPU_OK;
 }
 /* ... and after that synchronisation */
-static void located_spans(kmpgpu_ctx *src, kmpgpu_ctx *on)
+static void located_spans(kmpgpu_ctx *src, kmpgpu_ctx *on, SpanKind sk)
 {
-    memcpy(src->http_stats, on->h_small + 8, sizeof src->http_stats);
-    src->spans_valid = true;
+    memcpy(sk.dns ? src->dns_stats : src->http_stats, on->h_small + 8, 4 * sizeof(uint64_t));
+    (sk.dns ? src->dns_valid : src->spans_valid) = true;
+}
+
+/* kmpgpu_http_locate and kmpgpu_dns_locate behind their own checks; the stats are then in c->http_stats / c->dns_stats */
+static int locate_call(kmpgpu_ctx *c, SpanKind sk, const char *who)
+{
+    if (c->fr_pending) return fail(KMPGPU_ESTATE, "%s: the context sits between kmpgpu_load_frames_begin and _finish", who);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->last = kmpgpu_timing{};
+    bool launched = false;
+    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+    const int rc = locate_spans(c, c, sk, who, &launched);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    HIP_TRY(hipEventSynchronize(c->ev[3]));
+    if (launched) {
+        located_spans(c, c, sk);
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
+        c->last.kernel_ms = ms; c->last.launches = 1;
+    }
+    return KMPGPU_OK;
+}
+
+/* ... and the two _spans_read: records [first, first + n) of `spans`, 32 bytes each */
+static int spans_read_call(kmpgpu_ctx *c, bool valid, const uint4 *spans, void *out, uint64_t first, uint64_t n, const char *who, const char *locate)
+{
+    if (!valid) return fail(KMPGPU_ESTATE, "%s: no spans (no %s since the arena was set)", who, locate);
+    if (first > c->n_pkts || n > c->n_pkts - first)
+        return fail(KMPGPU_EINVAL, "%s: records [%llu, +%llu) leave the %llu there are", who, (unsigned long long)first, (unsigned long long)n,
+                    (unsigned long long)c->n_pkts);
+    if (n == 0) return KMPGPU_OK;
+    if (!out) return fail(KMPGPU_EINVAL, "%s: out is NULL", who);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(out, spans + 2 * first, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return KMPGPU_OK;
 }
 
 int kmpgpu_http_locate(kmpgpu_ctx *c, kmpgpu_http_stats *stats)
@@ -1768,22 +1823,7 @@ int kmpgpu_http_locate(kmpgpu_ctx *c, kmpgpu_http_stats *stats)
     const char *who = "kmpgpu_http_locate";
     if (stats) *stats = kmpgpu_http_stats{};
     if (!c) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
-    if (c->fr_pending) return fail(KMPGPU_ESTATE, "%s: the context sits between kmpgpu_load_frames_begin and _finish", who);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    c->last = kmpgpu_timing{};
-    bool launched = false;
-    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
-    const int rc = locate_spans(c, c, who, &launched);
-    if (rc) return rc;
-    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
-    HIP_TRY(hipEventSynchronize(c->ev[3]));
-    if (launched) {
-        located_spans(c, c);
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
-        c->last.kernel_ms = ms; c->last.launches = 1;
-    }
+    if (const int rc = locate_call(c, SpanKind{false, 0u}, who)) return rc;
     if (stats) { stats->n_requests = c->http_stats[0]; stats->n_responses = c->http_stats[1]; stats->n_blank = c->http_stats[2]; stats->bytes_scanned = c->http_stats[3]; }
     return KMPGPU_OK;
 }
@@ -1793,32 +1833,45 @@ int kmpgpu_http_spans_read(kmpgpu_ctx *c, kmpgpu_http_span *out, uint64_t first,
     const char *who = "kmpgpu_http_spans_read";
     static_assert(sizeof(kmpgpu_http_span) == 32, "kmpgpu_http_span is two 16-byte units");
     if (!c) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
-    if (!c->spans_valid) return fail(KMPGPU_ESTATE, "%s: no spans (no kmpgpu_http_locate since the arena was set)", who);
-    if (first > c->n_pkts || n > c->n_pkts - first)
-        return fail(KMPGPU_EINVAL, "%s: records [%llu, +%llu) leave the %llu there are", who, (unsigned long long)first, (unsigned long long)n,
-                    (unsigned long long)c->n_pkts);
-    if (n == 0) return KMPGPU_OK;
-    if (!out) return fail(KMPGPU_EINVAL, "%s: out is NULL", who);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpyAsync(out, c->d_spans + 2 * first, (size_t)n * sizeof(kmpgpu_http_span), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    return spans_read_call(c, c->spans_valid, c->d_spans, out, first, n, who, "kmpgpu_http_locate");
+}
+
+int kmpgpu_dns_locate(kmpgpu_ctx *c, uint32_t flags, kmpgpu_dns_stats *stats)
+{
+    const char *who = "kmpgpu_dns_locate";
+    if (stats) *stats = kmpgpu_dns_stats{};
+    if (!c) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
+    if (flags & ~KMPGPU_DNS_TCP_PREFIX) return fail(KMPGPU_EINVAL, "%s: unknown flag bits 0x%x", who, flags);
+    if (const int rc = locate_call(c, SpanKind{true, flags}, who)) return rc;
+    if (stats) { stats->n_queries = c->dns_stats[0]; stats->n_responses = c->dns_stats[1]; stats->n_root = c->dns_stats[2]; stats->name_bytes = c->dns_stats[3]; }
     return KMPGPU_OK;
 }
 
-int kmpgpu_load_fields(kmpgpu_ctx *dst, kmpgpu_ctx *src, int field, uint32_t flags, uint64_t *present_out, const void **d_present,
-                       kmpgpu_fields_stats *stats)
+int kmpgpu_dns_spans_read(kmpgpu_ctx *c, kmpgpu_dns_span *out, uint64_t first, uint64_t n)
 {
-    const char *who = "kmpgpu_load_fields";
-    if (d_present) *d_present = nullptr;
-    if (stats) *stats = kmpgpu_fields_stats{};
-    if (!dst || !src) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
-    if (dst == src) return fail(KMPGPU_EINVAL, "%s: dst and src are the same context (a context holds one arena)", who);
-    if (field < KMPGPU_FIELD_METHOD || field > KMPGPU_FIELD_BODY) return fail(KMPGPU_EINVAL, "%s: field %d is none of KMPGPU_FIELD_*", who, field);
-    if (flags & ~KMPGPU_FIELDS_ONLY_PRESENT) return fail(KMPGPU_EINVAL, "%s: unknown flag bits 0x%x", who, flags);
+    const char *who = "kmpgpu_dns_spans_read";
+    static_assert(sizeof(kmpgpu_dns_span) == 32, "kmpgpu_dns_span is two 16-byte units");
+    if (!c) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
+    return spans_read_call(c, c->dns_valid, c->d_dns, out, first, n, who, "kmpgpu_dns_locate");
+}
+
+/* What kmpgpu_load_fields and kmpgpu_load_dns hand to the span they share */
+struct FieldBuffer { const char *who; SpanKind sk; int field; bool only_present; };
+
+static int field_buffer_refused(const kmpgpu_ctx *dst, const kmpgpu_ctx *src, const char *who)
+{
     if (dst->device != src->device)
         return fail(KMPGPU_EINVAL, "%s: the contexts sit on devices %d and %d (field buffers across devices do not exist)", who, dst->device, src->device);
     if (dst->fr_pending || src->fr_pending) return fail(KMPGPU_ESTATE, "%s: %s sits between kmpgpu_load_frames_begin and _finish", who, dst->fr_pending ? "dst" : "src");
-    const bool only_present = (flags & KMPGPU_FIELDS_ONLY_PRESENT) != 0;
+    return KMPGPU_OK;
+}
+
+/* The span both calls share: the locate where src's spans are stale, lengths, scan, index, gather, through the one arena-install path. */
+static int load_field_buffer(kmpgpu_ctx *dst, kmpgpu_ctx *src, const FieldBuffer &fb, uint64_t *present_out, const void **d_present,
+                             kmpgpu_fields_stats *stats)
+{
+    const char *who = fb.who;
+    const bool only_present = fb.only_present, dns = fb.sk.dns;
     HIP_TRY(hipSetDevice(dst->device));
     HIP_TRY(hipStreamSynchronize(dst->stream));           /* the passes over the arena that is about to be replaced */
     HIP_TRY(hipStreamSynchronize(src->stream));           /* whatever src's stream still does with its arena */
@@ -1837,10 +1890,12 @@ int kmpgpu_load_fields(kmpgpu_ctx *dst, kmpgpu_ctx *src, int field, uint32_t fla
     hipEvent_t e1;
     HIP_TRY(hipEventRecord(c->ev[2], c->stream));
     bool located = false;
-    int rc = locate_spans(src, c, who, &located);         /* (one more launch, where the spans are stale) */
+    int rc = locate_spans(src, c, fb.sk, who, &located);  /* (one more launch, where the spans are stale) */
     if (rc) return rc;
+    const uint4 *spans = dns ? src->d_dns : src->d_spans;
     HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_fields_lengths(src->d_spans, src->d_len, n, field, only_present, c->fr_ws, c->d_dec_changed, d_stats, c->stream));
+    if (dns) HIP_TRY(kmp_launch_dns_lengths(spans, src->d_len, n, only_present, c->fr_ws, c->d_dec_changed, d_stats, c->stream));
+    else HIP_TRY(kmp_launch_fields_lengths(spans, src->d_len, n, fb.field, only_present, c->fr_ws, c->d_dec_changed, d_stats, c->stream));
     HIP_TRY(profile_launched(c, e1));
     HIP_TRY(profile_launch(c, &e1));
     HIP_TRY(kmp_launch_compact_scan(n, c->fr_ws, c->fr_tot, c->stream));
@@ -1849,7 +1904,7 @@ int kmpgpu_load_fields(kmpgpu_ctx *dst, kmpgpu_ctx *src, int field, uint32_t fla
     HIP_TRY(hipMemcpyAsync(c->h_small + 2, d_stats, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     if (present_out) HIP_TRY(hipMemcpyAsync(present_out, c->d_dec_changed, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (located) located_spans(src, c);
+    if (located) located_spans(src, c, fb.sk);
     unsigned long long tot[6] = {0, 0, 0, 0, 0, 0};       /* packed bytes, payloads; source bytes, payloads with the field, field bytes */
     memcpy(tot, c->h_small, sizeof tot);
     const uint64_t n_pkts = tot[1], arena_bytes = tot[0] + 64;
@@ -1880,10 +1935,12 @@ int kmpgpu_load_fields(kmpgpu_ctx *dst, kmpgpu_ctx *src, int field, uint32_t fla
     }
     HIP_TRY(hipMemsetAsync(c->owned_arena + tot[0], 0, 64, c->stream));
     HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_fields_index(src->d_spans, src->d_off, n, field, c->fr_ws, n_pkts, c->owned_off, c->owned_len, c->fr_src, c->stream));
+    if (dns) HIP_TRY(kmp_launch_dns_index(spans, src->d_off, n, c->fr_ws, n_pkts, c->owned_off, c->owned_len, c->fr_src, c->stream));
+    else HIP_TRY(kmp_launch_fields_index(spans, src->d_off, n, fb.field, c->fr_ws, n_pkts, c->owned_off, c->owned_len, c->fr_src, c->stream));
     HIP_TRY(profile_launched(c, e1));
     HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_fields_gather(src->d_arena, c->owned_off, c->fr_src, n_pkts, tot[0], c->owned_arena, c->nontemporal != 0, c->stream));
+    if (dns) HIP_TRY(kmp_launch_dns_gather(src->d_arena, c->owned_off, c->fr_src, spans + 2 * n, n_pkts, tot[0], c->owned_arena, c->nontemporal != 0, c->stream));
+    else HIP_TRY(kmp_launch_fields_gather(src->d_arena, c->owned_off, c->fr_src, n_pkts, tot[0], c->owned_arena, c->nontemporal != 0, c->stream));
     HIP_TRY(profile_launched(c, e1));
     HIP_TRY(hipEventRecord(c->ev[3], c->stream));
     /* src has metadata: the records go with the payloads -- in their new order, or all of them as they are */
@@ -1893,11 +1950,41 @@ int kmpgpu_load_fields(kmpgpu_ctx *dst, kmpgpu_ctx *src, int field, uint32_t fla
     }
     IndexFacts f;
     rc = validate_index(c, who, c->owned_off, c->owned_len, n_pkts, arena_bytes, &f);
-    /* kmp_fields_gather_kernel writes every slot whole: payload, then 0x00 up to the slot's end */
+    /* kmp_fields_gather_kernel and kmp_dns_gather_kernel write every slot whole: payload, then 0x00 up to the slot's end */
     if (!rc) rc = install_arena(c, c->owned_arena, c->owned_off, c->owned_len, arena_bytes, n_pkts, f, /* wrote_padding = */ true);
     if (rc) { release_arena(c, true); return rc; }
     c->has_meta = src->has_meta;
     return done(5);
+}
+
+int kmpgpu_load_fields(kmpgpu_ctx *dst, kmpgpu_ctx *src, int field, uint32_t flags, uint64_t *present_out, const void **d_present,
+                       kmpgpu_fields_stats *stats)
+{
+    const char *who = "kmpgpu_load_fields";
+    if (d_present) *d_present = nullptr;
+    if (stats) *stats = kmpgpu_fields_stats{};
+    if (!dst || !src) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
+    if (dst == src) return fail(KMPGPU_EINVAL, "%s: dst and src are the same context (a context holds one arena)", who);
+    if (field < KMPGPU_FIELD_METHOD || field > KMPGPU_FIELD_BODY) return fail(KMPGPU_EINVAL, "%s: field %d is none of KMPGPU_FIELD_*", who, field);
+    if (flags & ~KMPGPU_FIELDS_ONLY_PRESENT) return fail(KMPGPU_EINVAL, "%s: unknown flag bits 0x%x", who, flags);
+    if (const int rc = field_buffer_refused(dst, src, who)) return rc;
+    const FieldBuffer fb = {who, SpanKind{false, 0u}, field, (flags & KMPGPU_FIELDS_ONLY_PRESENT) != 0};
+    return load_field_buffer(dst, src, fb, present_out, d_present, stats);
+}
+
+int kmpgpu_load_dns(kmpgpu_ctx *dst, kmpgpu_ctx *src, int field, uint32_t flags, uint64_t *present_out, const void **d_present,
+                    kmpgpu_fields_stats *stats)
+{
+    const char *who = "kmpgpu_load_dns";
+    if (d_present) *d_present = nullptr;
+    if (stats) *stats = kmpgpu_fields_stats{};
+    if (!dst || !src) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
+    if (dst == src) return fail(KMPGPU_EINVAL, "%s: dst and src are the same context (a context holds one arena)", who);
+    if (field != KMPGPU_DNS_QNAME) return fail(KMPGPU_EINVAL, "%s: field %d is not KMPGPU_DNS_QNAME", who, field);
+    if (flags & ~(KMPGPU_DNS_ONLY_PRESENT | KMPGPU_DNS_TCP_PREFIX)) return fail(KMPGPU_EINVAL, "%s: unknown flag bits 0x%x", who, flags);
+    if (const int rc = field_buffer_refused(dst, src, who)) return rc;
+    const FieldBuffer fb = {who, SpanKind{true, flags & KMPGPU_DNS_TCP_PREFIX}, field, (flags & KMPGPU_DNS_ONLY_PRESENT) != 0};
+    return load_field_buffer(dst, src, fb, present_out, d_present, stats);
 }
 
 int kmpgpu_load_seams(kmpgpu_ctx *dst, kmpgpu_ctx *src, uint32_t reach, uint64_t *n_seams)

@@ -45,6 +45,15 @@ FIELD_NAMES = {"method": FIELD_METHOD, "raw_uri": FIELD_RAW_URI, "status": FIELD
 HTTP_SPAN_DTYPE = np.dtype([("kind", np.uint8), ("flags", np.uint8), ("method_len", np.uint16), ("tok_off", np.uint32), ("tok_len", np.uint32),
                             ("hdr_off", np.uint32), ("hdr_len", np.uint32), ("body_off", np.uint32), ("body_len", np.uint32),
                             ("reserved", np.uint32)])
+DNS_QNAME = 1                               # KMPGPU_DNS_QNAME: the field of load_dns
+DNS_ONLY_PRESENT, DNS_TCP_PREFIX = 1, 2     # KMPGPU_DNS_*: its flags; DNS_TCP_PREFIX is dns_locate's too
+DNS_NONE, DNS_QUERY, DNS_RESPONSE = 0, 1, 2     # kmpgpu_dns_span.kind
+DNS_FIELD_NAMES = {"qname": DNS_QNAME}
+# kmpgpu_dns_span (include/kmpgpu.h)
+DNS_SPAN_DTYPE = np.dtype([("kind", np.uint8), ("n_labels", np.uint8), ("flags", np.uint16), ("id", np.uint16), ("qtype", np.uint16),
+                           ("qclass", np.uint16), ("qdcount", np.uint16), ("ancount", np.uint16), ("nscount", np.uint16),
+                           ("arcount", np.uint16), ("reserved", np.uint16), ("name_off", np.uint32), ("name_len", np.uint32),
+                           ("q_end", np.uint32)])
 SEAM_DTYPE = np.dtype([("prev", "<u8"), ("next", "<u8"), ("tail_len", "<u4"), ("head_len", "<u4")])      # kmpgpu_seam, 24 bytes
 STREAM_DEPTH_MAX = 1 << 30     # KMPGPU_STREAM_DEPTH_MAX
 STREAM_DTYPE = np.dtype([("first_packet", "<u8"), ("last_packet", "<u8"), ("n_packets", "<u8"), ("bytes", "<u8"), ("flow", "<u4"),
@@ -617,6 +626,49 @@ class GpuMatcher:
         stats = {f: int(getattr(st, f)) for f, _ in _lib.FieldsStats._fields_}
         if stats["n_present"] != int(present.sum()) or stats["n_payloads"] != index.size or self.arena_info()[0] != index.size:
             raise KmpGpuError(f"kmpgpu_load_fields reports {stats['n_payloads']} payloads and {stats['n_present']} present ones, the "
+                              f"bitmap holds {int(present.sum())} of {n_src}")
+        return {"present": present, "index": index, "stats": stats}
+
+    def dns_locate(self, tcp_prefix: bool = False) -> dict:
+        """Locate the first question of the DNS message in every payload of this matcher's arena (kmpgpu_dns_locate; the definition:
+        kmpgpu.h).  tcp_prefix: a 2-byte length stands in front of every message.  The spans stay on the device until the arena
+        changes; with valid spans of the same tcp_prefix nothing is launched.  Returns the stats: {"n_queries", "n_responses",
+        "n_root", "name_bytes"}."""
+        st = _lib.DnsStats()
+        gpu_check(self._g.kmpgpu_dns_locate(self._ctx, DNS_TCP_PREFIX if tcp_prefix else 0, C.byref(st)), "kmpgpu_dns_locate")
+        return {f: int(getattr(st, f)) for f, _ in _lib.DnsStats._fields_}
+
+    def dns_spans(self) -> np.ndarray:
+        """The kmpgpu_dns_span records of the last dns_locate() / load_dns() over this matcher's arena, one per payload, as a
+        structured array (DNS_SPAN_DTYPE)."""
+        n, _ = self.arena_info()
+        out = np.zeros(max(n, 1), dtype=DNS_SPAN_DTYPE)
+        gpu_check(self._g.kmpgpu_dns_spans_read(self._ctx, out.ctypes.data, 0, n), "kmpgpu_dns_spans_read")
+        return out[:n]
+
+    def load_dns(self, src: "GpuMatcher", field: str = "qname", only_present: bool = False, tcp_prefix: bool = False) -> dict:
+        """Make this matcher's arena the dotted name of the first DNS question of every payload of ``src`` (kmpgpu_load_dns; the
+        definition: kmpgpu.h); patterns, rules, windows and options of this matcher stay.  only_present: this matcher holds only
+        the payloads that are DNS messages, compacted in ascending source order.  Returns what load_fields returns:
+        {"present": bool[n_src], "index": int64[n_dst], "stats": {...}}."""
+        if field not in DNS_FIELD_NAMES:
+            raise ValueError(f"field: {field!r} is none of {', '.join(DNS_FIELD_NAMES)}")
+        n_src, _ = src.arena_info()
+        W = (n_src + 63) // 64
+        words = np.zeros(max(W, 1), dtype=np.uint64)
+        st = _lib.FieldsStats()
+        flags = (DNS_ONLY_PRESENT if only_present else 0) | (DNS_TCP_PREFIX if tcp_prefix else 0)
+        gpu_check(self._g.kmpgpu_load_dns(self._ctx, src._ctx, DNS_FIELD_NAMES[field], flags, words.ctypes.data, None, C.byref(st)),
+                  "kmpgpu_load_dns")
+        self._keep = None
+        bits = np.unpackbits(words[:W].view(np.uint8), bitorder="little")
+        if bits[n_src:].any():
+            raise KmpGpuError(f"kmpgpu_load_dns set a bit at or above {n_src} in the present bitmap")
+        present = bits[:n_src].astype(bool)
+        index = np.flatnonzero(present).astype(np.int64) if only_present else np.arange(n_src, dtype=np.int64)
+        stats = {f: int(getattr(st, f)) for f, _ in _lib.FieldsStats._fields_}
+        if stats["n_present"] != int(present.sum()) or stats["n_payloads"] != index.size or self.arena_info()[0] != index.size:
+            raise KmpGpuError(f"kmpgpu_load_dns reports {stats['n_payloads']} payloads and {stats['n_present']} present ones, the "
                               f"bitmap holds {int(present.sum())} of {n_src}")
         return {"present": present, "index": index, "stats": stats}
 
