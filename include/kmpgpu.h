@@ -945,8 +945,8 @@ int  kmpgpu_load_base64(kmpgpu_ctx *dst, kmpgpu_ctx *src, uint32_t min_run, uint
  *   BODY (present iff bl exists): p[b0..L), b0 = bl + 2 or bl + 3 according to which form matched.  It may be empty.
  * A present field of length 0 and an absent field both become an empty payload of dst (one zero slot); the present bitmap tells them
  * apart.  Limits: one message per payload, the one at its start; no chunked or compressed bodies, no header folding, no
- * per-header buffers; methods are 1 to 15 upper-case letters; a rule cannot mix buffers inside one context -- the caller combines rows
- * of contexts that share src's numbering.
+ * per-header buffers; methods are 1 to 15 upper-case letters.  A rule over several buffers takes the other buffers' rows
+ * through links (kmpgpu_link_rows).
  *
  * kmpgpu_http_locate decides all of this for every payload of ctx's arena in one kernel and keeps one kmpgpu_http_span per payload on
  * the device.  Offsets count from the payload's first byte; an absent field has offset and length 0; a NONE payload's record is all
@@ -1454,6 +1454,58 @@ int  kmpgpu_scan_thresholds(kmpgpu_ctx *ctx, const uint64_t *ts, int ts_on_devic
                             uint64_t *any_out /* [W] or NULL */, uint64_t *rule_hits_out /* [n_rules * W] or NULL */,
                             uint32_t *window_counts_out /* [n_thr * n_pkts] or NULL */, uint64_t *counts_out /* [n_pat] or NULL */,
                             kmpgpu_timing *t /* or NULL */);
+
+/* Linked rows: a row that ANOTHER context computed as one more row of this context's hit matrix, and so one more rule term (DESIGN.md
+ * §3.33).  The derived arenas -- kmpgpu_load_decoded, _base64, _fields, _dns, _streams, _selected -- each hold another view of the same
+ * payloads in a context of their own; a link carries a verdict on that view back into the context whose rules want it, translated on the
+ * device into this context's payload numbering.  Everything that starts from the rules' rows (kmpgpu_scan_rules, kmpgpu_scan_alerts,
+ * kmpgpu_scan_flows, kmpgpu_scan_flowbits, kmpgpu_scan_thresholds, kmpgpu_scan_flows_seams) then works on rules over several buffers.
+ *
+ * kmpgpu_set_links reserves n_links rows behind the expressions' rows: link q is row and rule term
+ * n_pat + n_rel + n_chains + n_hdr + n_bt + n_rx + q, with or without KMPGPU_RULE_NOT.  Like every family setter it needs patterns set
+ * (KMPGPU_ESTATE) and drops the rules, and with them the flow bits and thresholds; n_pat + ... + n_links >= 2^31 is KMPGPU_EINVAL, here
+ * and in every family setter called while links are set.
+ * n_links = 0 clears the family; kmpgpu_set_patterns drops the links as it drops the other families.  Every link starts unfilled.
+ *
+ * kmpgpu_link_rows fills links first_link .. first_link + n_rows - 1 of dst from rows first_row .. first_row + n_rows - 1 of src's family
+ * (KMPGPU_ALERT_*: patterns, rules, relations, chains).  It runs src's pass for that family itself -- the marking pass and the family's
+ * kernels, what kmpgpu_scan_<family> with every output NULL runs -- and leaves src as that call leaves it.  Then one kernel translates the
+ * rows into the link buffer dst owns, [n_links][stride]: bit k of a link row is 1 exactly where k < n_dst, map(k) exists and bit map(k) of
+ * src's row is 1; the bits at n_dst and above and the padding word of an odd W are 0.  The map kinds:
+ *   KMPGPU_LINK_SAME    payload k of src is payload k of dst; n_src != n_dst: KMPGPU_EINVAL; map is not read.
+ *   KMPGPU_LINK_BITMAP  map = uint64_t[ceil(n_dst / 64)]: the j-th set bit below n_dst is src's payload j -- the d_changed / d_present
+ *                       pointers and the select bitmap as they are.  Bits at n_dst and above are ignored; a popcount below n_dst that
+ *                       is not n_src: KMPGPU_EINVAL.  On the device the map is 8-byte aligned.
+ *   KMPGPU_LINK_INDEX   map = uint32_t[n_dst]: src's payload for dst's payload k; a value >= n_src (KMPGPU_LINK_NONE): none.  Many
+ *                       payloads may name one: a payload takes the verdict of its stream or of its seam.
+ * map_on_device: 0 a host array, copied; 1 a device array of dst's device, complete before the call.  src without payloads fills zeros.
+ * src's family may be KMPGPU_ALERT_RULES, and its rules may name src's own links: links chain.
+ * Synchronous: it waits for both contexts' streams, as kmpgpu_load_selected does.  t: kernel_ms is the translation alone, by events of
+ * its own on dst's stream -- the rank kernels of a bitmap plus the gather --, launches their number; src's pass is in neither.
+ * KMPGPU_EINVAL: a NULL context; dst == src (rules of rules do not exist); contexts on two devices; a family that is none of
+ * KMPGPU_ALERT_*, a map kind that is none of KMPGPU_LINK_*; a row or a link range out of bounds; KMPGPU_LINK_SAME with unequal payload
+ * counts; a NULL map where one is read; map_on_device not 0 or 1; a misaligned device map.  KMPGPU_ESTATE: either context between
+ * kmpgpu_load_frames_begin and _finish; dst without an arena; what src's own call for the family refuses.  After any error dst's links are
+ * what they were: the filled ones hold their rows, the others read as zeros.
+ * A link stays filled until dst's arena changes (every load, attach and derived-arena loader) or kmpgpu_set_links is called again; src may
+ * change freely afterwards, the caller links again when it wants the new verdict.  A pass over rules that name an unfilled link --
+ * kmpgpu_scan_rules, kmpgpu_scan_alerts and kmpgpu_scan_flows of the rules, kmpgpu_scan_flowbits, kmpgpu_scan_thresholds,
+ * kmpgpu_scan_flows_seams -- is KMPGPU_ESTATE and names the link.  Behind the marking pass the link buffer is copied into the matrix (one
+ * device-to-device copy); no existing kernel changes.
+ *
+ * kmpgpu_scan_links: the family's own scan call, as kmpgpu_scan_regexes: the marking pass, the copy and the reduce of kmpgpu_scan_packets
+ * over the link rows.  An unfilled link reads as zeros.  No links set: KMPGPU_ESTATE.
+ * Not done: links to a context's own rows; rows in flow space (kmpgpu_scan_flows results) as a source; links across devices; automatic
+ * refill when src changes; match offsets. */
+#define KMPGPU_LINK_SAME    0
+#define KMPGPU_LINK_BITMAP  1
+#define KMPGPU_LINK_INDEX   2
+#define KMPGPU_LINK_NONE    0xFFFFFFFFu
+int  kmpgpu_set_links(kmpgpu_ctx *ctx, uint32_t n_links);
+int  kmpgpu_link_rows(kmpgpu_ctx *dst, uint32_t first_link, kmpgpu_ctx *src, int family /* KMPGPU_ALERT_* */, uint32_t first_row,
+                      uint32_t n_rows, int map_kind /* KMPGPU_LINK_* */, const void *map, int map_on_device, kmpgpu_timing *t /* or NULL */);
+int  kmpgpu_scan_links(kmpgpu_ctx *ctx, uint64_t *link_pkt_counts_out /* [n_links] or NULL */, uint64_t *any_out /* [W] or NULL */,
+                       uint64_t *link_hits_out /* [n_links * W] or NULL */, uint64_t *counts_out /* [n_pat] or NULL */, kmpgpu_timing *t);
 
 /* Fill a device arena with the synthetic payloads of kmp_synth.h (benchmark input S1/S2):
  * packet ids first_pkt_id .. first_pkt_id + n_pkts - 1 at the slots of the given device index. */

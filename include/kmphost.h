@@ -135,7 +135,30 @@ int  kmp_rules_parse_bt(const char *path, uint32_t n_patterns, uint32_t n_relati
  * file is opened.  kmp_rules_parse_bt is this with n_regexes = 0, where "x3" is no term at all and every message is what it was. */
 int  kmp_rules_parse_rx(const char *path, uint32_t n_patterns, uint32_t n_relations, uint32_t n_chains, uint32_t n_headers, uint32_t n_bytetests,
                         uint32_t n_regexes, kmp_rules *out, char errbuf[KMP_RULES_ERRBUF]);
+/* The same once more with the links of kmpgpu_set_links behind the expressions: "l<q>" / "!l<q>" is link q, row
+ * n_patterns + ... + n_regexes + q.  Without links (n_links = 0) the token is no term at all, as with the other letters. */
+int  kmp_rules_parse_links(const char *path, uint32_t n_patterns, uint32_t n_relations, uint32_t n_chains, uint32_t n_headers,
+                           uint32_t n_bytetests, uint32_t n_regexes, uint32_t n_links, kmp_rules *out, char errbuf[KMP_RULES_ERRBUF]);
 void kmp_rules_free(kmp_rules *r);
+
+/* ---- links -----------------------------------------------------------------------------------
+ * Not in the reference: the links file of the programs (KMPGPU_LINKS_FILE).  One link per line,
+ *     <buffer> <term>
+ * link q (the q-th such line) is the row <term> -- ONE un-negated token of the rules syntax over the shared tables ("7", "r0", "c1",
+ * "h0", "b0", "x2") -- scanned in the buffer <buffer>, a word of at most KMP_LINK_BUFFER - 1 characters that the caller interprets
+ * ("http:body", "dns:qname,tcp", "decode:percent", "base64:16,url").  Blank lines and lines that start with '#' are skipped.  A negated
+ * term, an l<q> term (a link names no link), a term out of range, a second term, a line without a term or a buffer word that is too
+ * long: KMPHOST_EINVAL with "line N: ..." in errbuf. */
+#define KMP_LINKS_ERRBUF 256
+#define KMP_LINK_BUFFER 64
+typedef struct kmp_links {
+    uint32_t  n;                          /* number of links                                  */
+    char    (*buffer)[KMP_LINK_BUFFER];   /* [n]: the buffer word, NUL-terminated             */
+    uint32_t *term;                       /* [n]: the row the link's single-term rule names   */
+} kmp_links;
+int  kmp_links_parse(const char *path, uint32_t n_patterns, uint32_t n_relations, uint32_t n_chains, uint32_t n_headers, uint32_t n_bytetests,
+                     uint32_t n_regexes, kmp_links *out, char errbuf[KMP_LINKS_ERRBUF]);
+void kmp_links_free(kmp_links *l);
 
 /* ---- relations -------------------------------------------------------------------------------
  * Not in the reference: the relations of kmpgpu_set_relations (include/kmpgpu.h) from a text file.  One relation per line,

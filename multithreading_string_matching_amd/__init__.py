@@ -36,6 +36,10 @@ from .matcher import (  # noqa: F401
     FIELDS_ONLY_PRESENT,
     GpuComm,
     GpuMatcher,
+    LINK_BITMAP,
+    LINK_INDEX,
+    LINK_NONE,
+    LINK_SAME,
     count_matches,
     device_count,
 )

@@ -86,6 +86,14 @@ class Rules(C.Structure):
     _fields_ = [("n", C.c_uint32), ("off", u32p), ("terms", u32p)]
 
 
+KMP_LINK_BUFFER = 64       # KMP_LINK_BUFFER: bytes of a links file's buffer word, the terminator included
+
+
+class Links(C.Structure):
+    """kmp_links (include/kmphost.h)."""
+    _fields_ = [("n", C.c_uint32), ("buffer", C.POINTER(C.c_char * KMP_LINK_BUFFER)), ("term", u32p)]
+
+
 class Relation(C.Structure):
     """kmpgpu_relation (include/kmpgpu.h) = kmp_relation (include/kmphost.h)."""
     _fields_ = [("a", C.c_uint32), ("b", C.c_uint32), ("dmin", C.c_int32), ("dmax", C.c_int32)]
@@ -255,6 +263,10 @@ HOST_API = {
     "kmp_bytetests_parse": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(ByteTests), C.c_char_p]),
     "kmp_bytetests_free": (None, [C.POINTER(ByteTests)]),
     "kmp_rules_parse_rx": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Rules), C.c_char_p]),
+    "kmp_rules_parse_links": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Rules),
+                                        C.c_char_p]),
+    "kmp_links_parse": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Links), C.c_char_p]),
+    "kmp_links_free": (None, [C.POINTER(Links)]),
     "kmp_regexes_parse": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(Regexes), C.c_char_p]),
     "kmp_regexes_free": (None, [C.POINTER(Regexes)]),
     "kmp_chains_parse": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(Chains), C.c_char_p]),
@@ -338,6 +350,10 @@ GPU_API = {
     "kmpgpu_scan_bytetests": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
     "kmpgpu_set_regexes": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), u32p, u32p, u32p, C.c_uint32]),
     "kmpgpu_scan_regexes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
+    "kmpgpu_set_links": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "kmpgpu_link_rows": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_int,
+                                   C.POINTER(Timing)]),
+    "kmpgpu_scan_links": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
     "kmpgpu_scan_alerts": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, u64p, u64p, C.c_void_p, C.c_void_p, C.POINTER(Timing)]),
     "kmpgpu_alerts_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "kmpgpu_load_selected": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, u64p]),

@@ -121,6 +121,16 @@
  * value; the variable together with KMPGPU_DECODE, KMPGPU_HTTP_FIELD, KMPGPU_OFFSETS_FILE, KMPGPU_EXPORT_FILE, KMPGPU_FLOW_SEAMS,
  * KMPGPU_FLOW_STREAMS, KMPGPU_FLOWBITS_FILE or KMPGPU_THRESHOLDS_FILE; the variable with none of the three row outputs.
  *
+ * KMPGPU_LINKS_FILE=<links>, together with KMPGPU_RULES_FILE: one rule over several buffers of the same payloads.  One link per line,
+ * "<buffer> <term>" (kmp_links_parse, kmphost.h; the buffer words: kmp_cli_links.h), and the rules file may then name link q as "l<q>" /
+ * "!l<q>" (kmp_rules_parse_links).  Per shard and distinct buffer a context with the same tables and that buffer of every payload is
+ * built as the variables above build theirs, one single-term rule per link is set on it, and kmpgpu_link_rows carries the rows into the
+ * shard's own context (links_shards); the packets, alerts, flow-alerts, flow-bits and thresholds outputs then come from the shard's own
+ * context, as without the variable.  Refused with a message on stderr and exit 1, before any GPU work: the variable together with
+ * KMPGPU_DECODE, KMPGPU_HTTP_FIELD, KMPGPU_DNS_FIELD, KMPGPU_BASE64 (there the rows come from one buffer), KMPGPU_FLOW_SEAMS or
+ * KMPGPU_FLOW_STREAMS; the variable without KMPGPU_RULES_FILE; a links file that does not parse (a negated or l term, a term out of
+ * range); an unknown buffer; more than KMP_CLI_LINK_BUFFERS_MAX distinct buffers.
+ *
  * KMPGPU_DNS_FIELD=qname[,tcp], together with at least one of KMPGPU_PACKETS_FILE, KMPGPU_ALERTS_FILE and KMPGPU_FLOW_ALERTS_FILE: these row
  * outputs are decided on the dotted name of the first question of the DNS message in every payload (kmpgpu_load_dns; the definition:
  * kmpgpu.h; ,tcp: a 2-byte length stands in front of every message), so that a rule that names `doubleclick.net` meets the queried name.
@@ -184,6 +194,7 @@
 #include "kmp_cli_base64.h"
 #include "kmp_cli_fields.h"
 #include "kmp_cli_dns.h"
+#include "kmp_cli_links.h"
 #include "kmp_cli_streams.h"
 #include "kmp_cli_streams_order.h"
 
@@ -225,6 +236,11 @@ typedef struct cli_options {
     kmp_headers headers;                    /* KMPGPU_HEADERS_FILE (n == 0: none) */
     kmp_bytetests bytetests;                /* KMPGPU_BYTETESTS_FILE (n == 0: none) */
     kmp_regexes regexes;                    /* KMPGPU_REGEX_FILE (n == 0: none) */
+    const char *links_path;                 /* KMPGPU_LINKS_FILE */
+    kmp_links links;                        /* ... its links (n == 0: none): link q is term l<q> of the rules */
+    kmp_cli_link_buffer link_buf[KMP_CLI_LINK_BUFFERS_MAX];        /* ... the distinct buffers they name */
+    int n_link_bufs;
+    int *link_in;                           /* ... and link_in[q]: which of them link q is scanned in */
     kmp_rules rules;                        /* KMPGPU_RULES_FILE, set before the first output that needs them */
     const char *flowbits_path;              /* KMPGPU_FLOWBITS_FILE */
     kmp_flowbits flowbits;                  /* ... and its ops, set behind the rules (n == 0: none) */
@@ -391,7 +407,51 @@ static void load_options(int argc, char *argv[], cli_options *opt)
             exit(1);
         }
     }
-    if (opt->rules_path && kmp_rules_parse_rx(opt->rules_path, n, opt->relations.n, opt->chains.n, opt->headers.n, opt->bytetests.n, opt->regexes.n, &opt->rules, err)) {
+    /* the links: rows of other buffers of the same payloads, which the rules may name as l<q> */
+    opt->links_path = env_path("KMPGPU_LINKS_FILE");
+    if (opt->links_path) {
+        static const char *const not_with[][2] = {
+            {"KMPGPU_DECODE", "there the rows come from one buffer; a line 'decode:percent <term>' links it"},
+            {"KMPGPU_HTTP_FIELD", "there the rows come from one buffer; a line 'http:<field> <term>' links it"},
+            {"KMPGPU_DNS_FIELD", "there the rows come from one buffer; a line 'dns:qname <term>' links it"},
+            {"KMPGPU_BASE64", "there the rows come from one buffer; a line 'base64:<min_run> <term>' links it"},
+            {"KMPGPU_FLOW_SEAMS", "seams are numbered by themselves, links in this program by the capture's payloads"},
+            {"KMPGPU_FLOW_STREAMS", "streams are numbered by themselves, links in this program by the capture's payloads"}};
+        _Static_assert(sizeof err >= KMP_LINKS_ERRBUF, "room for the links parser's message");
+        for (size_t i = 0; i < sizeof not_with / sizeof not_with[0]; i++)
+            if (env_path(not_with[i][0])) {
+                fprintf(stderr, "KMPGPU_LINKS_FILE does not go together with %s: %s\n", not_with[i][0], not_with[i][1]);
+                exit(1);
+            }
+        if (!opt->rules_path) {
+            fprintf(stderr, "KMPGPU_LINKS_FILE goes together with KMPGPU_RULES_FILE: a link is a term l<q> of a rule\n");
+            exit(1);
+        }
+        if (kmp_links_parse(opt->links_path, n, opt->relations.n, opt->chains.n, opt->headers.n, opt->bytetests.n, opt->regexes.n, &opt->links, err)) {
+            fprintf(stderr, "error reading links file %s: %s\n", opt->links_path, err);
+            exit(1);
+        }
+        opt->link_in = (int *)malloc(sizeof(int) * (opt->links.n ? opt->links.n : 1));
+        for (uint32_t q = 0; q < opt->links.n; q++) {
+            kmp_cli_link_buffer b;
+            if (!kmp_cli_parse_link_buffer(opt->links.buffer[q], &b)) {
+                fprintf(stderr, "KMPGPU_LINKS_FILE: link %u: '%s' is no buffer (http:method|raw_uri|uri|status|headers|body, dns:qname[,tcp], decode:percent[+plus], base64:<min_run>[,url])\n",
+                        q, opt->links.buffer[q]);
+                exit(1);
+            }
+            int at = 0;
+            while (at < opt->n_link_bufs && !kmp_cli_link_buffer_same(&opt->link_buf[at], &b)) at++;
+            if (at == opt->n_link_bufs) {
+                if (at == KMP_CLI_LINK_BUFFERS_MAX) {
+                    fprintf(stderr, "KMPGPU_LINKS_FILE: link %u: '%s' is buffer %d: at most %d distinct buffers\n", q, opt->links.buffer[q], at + 1, KMP_CLI_LINK_BUFFERS_MAX);
+                    exit(1);
+                }
+                opt->link_buf[opt->n_link_bufs++] = b;
+            }
+            opt->link_in[q] = at;
+        }
+    }
+    if (opt->rules_path && kmp_rules_parse_links(opt->rules_path, n, opt->relations.n, opt->chains.n, opt->headers.n, opt->bytetests.n, opt->regexes.n, opt->links.n, &opt->rules, err)) {
         fprintf(stderr, "error reading rules file %s: %s\n", opt->rules_path, err);
         exit(1);
     }
@@ -650,6 +710,8 @@ static void free_options(cli_options *opt)
     free(opt->pp);
     kmp_patterns_free(&opt->pats);
     kmp_rules_free(&opt->rules);
+    kmp_links_free(&opt->links);
+    free(opt->link_in);
     kmp_relations_free(&opt->relations);
     kmp_chains_free(&opt->chains);
     kmp_headers_free(&opt->headers);
@@ -875,6 +937,55 @@ static void dns_shards(const cli_options *opt, cli_run *run)
         if (kmpgpu_load_dns(d, run->ctxs[r], opt->dns_field, flags, NULL, NULL, NULL)) die_gpu("kmpgpu_load_dns");
         run->rows[r] = d;
     }
+}
+
+/* KMPGPU_LINKS_FILE: per shard and distinct buffer a context with the same tables that holds that buffer of every payload of the shard,
+ * in the capture's numbering (as decode_shards, base64_shards, field_shards and dns_shards build theirs); on it one single-term rule per
+ * link scanned there, whose row kmpgpu_link_rows carries into the shard's own context.  The row outputs stay the shard's own. */
+static void links_shards(const cli_options *opt, cli_run *run)
+{
+    const uint32_t nl = opt->links.n;
+    uint32_t *off = (uint32_t *)malloc(sizeof(uint32_t) * ((size_t)nl + 1)), *terms = (uint32_t *)malloc(sizeof(uint32_t) * (nl ? nl : 1)),
+             *which = (uint32_t *)malloc(sizeof(uint32_t) * (nl ? nl : 1));
+    if (!off || !terms || !which) die_gpu("out of memory");
+    for (int r = 0; r < run->shards; r++) {
+        if (kmpgpu_set_links(run->ctxs[r], nl)) die_gpu("kmpgpu_set_links");
+        for (int b = 0; b < opt->n_link_bufs; b++) {
+            const kmp_cli_link_buffer *lb = &opt->link_buf[b];
+            kmpgpu_ctx *d = NULL, *raw = NULL;
+            if (kmpgpu_init(&d, run->job[r].device)) die_gpu("kmpgpu_init");
+            const char *failed = upload_tables(d, opt);
+            if (failed) die_gpu(failed);
+            if (lb->kind == KMP_CLI_LINK_HTTP && lb->field == KMP_CLI_FIELD_URI) {
+                if (kmpgpu_init(&raw, run->job[r].device)) die_gpu("kmpgpu_init");
+                if (kmpgpu_load_fields(raw, run->ctxs[r], KMPGPU_FIELD_RAW_URI, 0u, NULL, NULL, NULL)) die_gpu("kmpgpu_load_fields");
+                if (kmpgpu_load_decoded(d, raw, KMPGPU_DECODE_PERCENT, 0u, NULL, NULL, NULL)) die_gpu("kmpgpu_load_decoded");
+                kmpgpu_destroy(raw);
+            } else if (lb->kind == KMP_CLI_LINK_HTTP) {
+                if (kmpgpu_load_fields(d, run->ctxs[r], lb->field, 0u, NULL, NULL, NULL)) die_gpu("kmpgpu_load_fields");
+            } else if (lb->kind == KMP_CLI_LINK_DNS) {
+                if (kmpgpu_load_dns(d, run->ctxs[r], lb->field, lb->flag ? KMPGPU_DNS_TCP_PREFIX : 0u, NULL, NULL, NULL)) die_gpu("kmpgpu_load_dns");
+            } else if (lb->kind == KMP_CLI_LINK_DECODE) {
+                if (kmpgpu_load_decoded(d, run->ctxs[r], KMPGPU_DECODE_PERCENT, lb->field == KMP_CLI_DECODE_PLUS ? KMPGPU_DECODE_PLUS : 0u, NULL, NULL, NULL))
+                    die_gpu("kmpgpu_load_decoded");
+            } else if (kmpgpu_load_base64(d, run->ctxs[r], lb->min_run, lb->flag ? KMPGPU_B64_URLSAFE : 0u, NULL, NULL, NULL)) die_gpu("kmpgpu_load_base64");
+            /* rule j of d: the term of the j-th link scanned in this buffer */
+            uint32_t nr = 0;
+            off[0] = 0;
+            for (uint32_t q = 0; q < nl; q++)
+                if (opt->link_in[q] == b) { terms[nr] = opt->links.term[q]; which[nr] = q; nr++; off[nr] = nr; }
+            if (kmpgpu_set_rules(d, off, terms, nr)) die_gpu("kmpgpu_set_rules");
+            /* consecutive links of one buffer go in one call: src's pass runs once for them */
+            for (uint32_t j = 0; j < nr;) {
+                uint32_t k = j + 1;
+                while (k < nr && which[k] == which[k - 1] + 1) k++;
+                if (kmpgpu_link_rows(run->ctxs[r], which[j], d, KMPGPU_ALERT_RULES, j, k - j, KMPGPU_LINK_SAME, NULL, 0, NULL)) die_gpu("kmpgpu_link_rows");
+                j = k;
+            }
+            kmpgpu_destroy(d);
+        }
+    }
+    free(off); free(terms); free(which);
 }
 
 /* The rules on every context the row outputs come from, once: before the first output that needs them (the alerts file, behind its fopen, or the export). */
@@ -1158,6 +1269,7 @@ int main(int argc, char *argv[])
         if (opt.base64_min_run) base64_shards(&opt, &run);
         if (opt.http_field) field_shards(&opt, &run);
         if (opt.dns_field) dns_shards(&opt, &run);
+        if (opt.links.n) links_shards(&opt, &run);
         if (opt.offsets_path) write_offsets(opt.offsets_path, &run, n);
         if (opt.packets_path) write_alerts(opt.packets_path, &opt, &run, KMPGPU_ALERT_PATTERNS);
         if (opt.alerts_path) write_alerts(opt.alerts_path, &opt, &run, KMPGPU_ALERT_RULES);

@@ -550,7 +550,7 @@ typedef struct rules_ctx {
     uint32_t n_patterns, n_relations, n_chains;
     kmp_rules *out;
     size_t n_off, cap_off, n_terms, cap_terms;
-    uint32_t n_headers, n_bytetests, n_regexes;
+    uint32_t n_headers, n_bytetests, n_regexes, n_links;
 } rules_ctx;
 
 static int rules_line(void *ctx, const char *p, const char *end, size_t lineno, char *errbuf)
@@ -571,18 +571,23 @@ static int rules_line(void *ctx, const char *p, const char *end, size_t lineno, 
         const int is_bt = c->n_bytetests && p < end && *p == 'b';
         /* x<q>: expression q, in the same way */
         const int is_rx = c->n_regexes && p < end && *p == 'x';
-        if (is_rel || is_chain || is_hdr || is_bt || is_rx) p++;
+        /* l<q>: link q, in the same way */
+        const int is_link = c->n_links && p < end && *p == 'l';
+        if (is_rel || is_chain || is_hdr || is_bt || is_rx || is_link) p++;
         const char *digits = p;
         while (p < end && *p >= '0' && *p <= '9') { if (v < (1ull << 40)) v = v * 10 + (uint64_t)(*p - '0'); p++; }
         const char *stop = p;
         while (stop < end && !is_c_space((uint8_t)*stop)) stop++;   /* the whole token, for the message */
-        if (p == digits && neg && stop == p && !is_rel && !is_chain && !is_hdr && !is_bt && !is_rx) return line_error(errbuf, lineno, "'!' without a pattern index");
+        if (p == digits && neg && stop == p && !is_rel && !is_chain && !is_hdr && !is_bt && !is_rx && !is_link) return line_error(errbuf, lineno, "'!' without a pattern index");
         if (p == digits || stop != p)
-            return line_error(errbuf, lineno, "'%.*s' is not a pattern index%s%s%s%s%s", (int)(stop - tok > 64 ? 64 : stop - tok), tok,
+            return line_error(errbuf, lineno, "'%.*s' is not a pattern index%s%s%s%s%s%s", (int)(stop - tok > 64 ? 64 : stop - tok), tok,
                               c->n_relations ? " or r<relation index>" : "", c->n_chains ? " or c<chain index>" : "",
                               c->n_headers ? " or h<header index>" : "", c->n_bytetests ? " or b<byte test index>" : "",
-                              c->n_regexes ? " or x<expression index>" : "");
-        if (is_rx) {
+                              c->n_regexes ? " or x<expression index>" : "", c->n_links ? " or l<link index>" : "");
+        if (is_link) {
+            if (v >= c->n_links) return line_error(errbuf, lineno, "link index %llu, but there are %u links", (unsigned long long)v, c->n_links);
+            row = c->n_patterns + c->n_relations + c->n_chains + c->n_headers + c->n_bytetests + c->n_regexes + (uint32_t)v;
+        } else if (is_rx) {
             if (v >= c->n_regexes) return line_error(errbuf, lineno, "expression index %llu, but there are %u expressions", (unsigned long long)v, c->n_regexes);
             row = c->n_patterns + c->n_relations + c->n_chains + c->n_headers + c->n_bytetests + (uint32_t)v;
         } else if (is_bt) {
@@ -638,12 +643,19 @@ int kmp_rules_parse_bt(const char *path, uint32_t n_patterns, uint32_t n_relatio
 int kmp_rules_parse_rx(const char *path, uint32_t n_patterns, uint32_t n_relations, uint32_t n_chains, uint32_t n_headers, uint32_t n_bytetests,
                        uint32_t n_regexes, kmp_rules *out, char errbuf[KMP_RULES_ERRBUF])
 {
+    return kmp_rules_parse_links(path, n_patterns, n_relations, n_chains, n_headers, n_bytetests, n_regexes, 0, out, errbuf);
+}
+
+int kmp_rules_parse_links(const char *path, uint32_t n_patterns, uint32_t n_relations, uint32_t n_chains, uint32_t n_headers, uint32_t n_bytetests,
+                          uint32_t n_regexes, uint32_t n_links, kmp_rules *out, char errbuf[KMP_RULES_ERRBUF])
+{
     memset(out, 0, sizeof *out);
     if (errbuf) errbuf[0] = 0;
     /* a term is a row below 2^31: bit 31 is KMP_RULE_NOT (kmpgpu_set_relations, _chains, _headers, _bytetests and _regexes refuse such a set too) */
-    if ((uint64_t)n_patterns + n_relations + n_chains + n_headers + n_bytetests + n_regexes >= (1ull << 31)) {
+    if ((uint64_t)n_patterns + n_relations + n_chains + n_headers + n_bytetests + n_regexes + n_links >= (1ull << 31)) {
         if (errbuf) {
-            if (n_regexes) snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations + %u chains + %u header predicates + %u byte tests + %u expressions do not fit the 2^31 rows a term can name", n_patterns, n_relations, n_chains, n_headers, n_bytetests, n_regexes);
+            if (n_links) snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations + %u chains + %u header predicates + %u byte tests + %u expressions + %u links do not fit the 2^31 rows a term can name", n_patterns, n_relations, n_chains, n_headers, n_bytetests, n_regexes, n_links);
+            else if (n_regexes) snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations + %u chains + %u header predicates + %u byte tests + %u expressions do not fit the 2^31 rows a term can name", n_patterns, n_relations, n_chains, n_headers, n_bytetests, n_regexes);
             else if (n_bytetests) snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations + %u chains + %u header predicates + %u byte tests do not fit the 2^31 rows a term can name", n_patterns, n_relations, n_chains, n_headers, n_bytetests);
             else if (n_headers) snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations + %u chains + %u header predicates do not fit the 2^31 rows a term can name", n_patterns, n_relations, n_chains, n_headers);
             else if (n_chains) snprintf(errbuf, KMP_RULES_ERRBUF, "%u patterns + %u relations + %u chains do not fit the 2^31 rows a term can name", n_patterns, n_relations, n_chains);
@@ -651,7 +663,7 @@ int kmp_rules_parse_rx(const char *path, uint32_t n_patterns, uint32_t n_relatio
         }
         return KMPHOST_EINVAL;
     }
-    rules_ctx c = {n_patterns, n_relations, n_chains, out, 0, 0, 0, 0, n_headers, n_bytetests, n_regexes};
+    rules_ctx c = {n_patterns, n_relations, n_chains, out, 0, 0, 0, 0, n_headers, n_bytetests, n_regexes, n_links};
     int rc = rules_push(&out->off, &c.n_off, &c.cap_off, 0) ? out_of_memory(errbuf) : text_lines(path, rules_line, &c, errbuf);
     if (rc) {
         kmp_rules_free(out);
@@ -666,6 +678,77 @@ void kmp_rules_free(kmp_rules *r)
     if (!r) return;
     free(r->off); free(r->terms);
     memset(r, 0, sizeof *r);
+}
+
+/* ============================ links ===================================================== */
+
+typedef struct links_ctx {
+    rules_ctx terms;                      /* the tables a link's term may name: the rules' syntax without links */
+    kmp_links *out;
+    size_t cap;
+} links_ctx;
+
+static int links_line(void *ctx, const char *p, const char *end, size_t lineno, char *errbuf)
+{
+    links_ctx *c = (links_ctx *)ctx;
+    const char *word = p;
+    while (p < end && !is_c_space((uint8_t)*p)) p++;
+    const size_t wl = (size_t)(p - word);
+    if (wl >= KMP_LINK_BUFFER) return line_error(errbuf, lineno, "a buffer word of %zu characters: at most %d", wl, KMP_LINK_BUFFER - 1);
+    while (p < end && is_c_space((uint8_t)*p)) p++;
+    if (p == end) return line_error(errbuf, lineno, "'%.*s' without a term: a line is <buffer> <term>", (int)wl, word);
+    if (*p == '!') return line_error(errbuf, lineno, "a link's term is not negated: the rule that names the link negates it");
+    if (*p == 'l') return line_error(errbuf, lineno, "a link's term names no link");
+    /* the term through the rules' own line parser, into a rule of its own */
+    kmp_rules one;
+    memset(&one, 0, sizeof one);
+    rules_ctx t = c->terms;
+    t.out = &one;
+    const int rc = rules_line(&t, p, end, lineno, errbuf);
+    const uint32_t row = rc || t.n_terms == 0 ? 0u : one.terms[0];
+    const size_t n_terms = t.n_terms;
+    kmp_rules_free(&one);
+    if (rc) return rc;
+    if (n_terms != 1) return line_error(errbuf, lineno, "%zu terms: a link is one term", n_terms);
+    kmp_links *o = c->out;
+    if (o->n == c->cap) {
+        const size_t nc = c->cap ? c->cap * 2 : 16;
+        char (*nb)[KMP_LINK_BUFFER] = (char (*)[KMP_LINK_BUFFER])realloc(o->buffer, nc * sizeof *nb);
+        if (!nb) return KMPHOST_ENOMEM;
+        o->buffer = nb;
+        uint32_t *nt = (uint32_t *)realloc(o->term, nc * sizeof *nt);
+        if (!nt) return KMPHOST_ENOMEM;
+        o->term = nt;
+        c->cap = nc;
+    }
+    if (o->n == 0x7FFFFFFFu) return line_error(errbuf, lineno, "too many links");
+    memcpy(o->buffer[o->n], word, wl);
+    o->buffer[o->n][wl] = 0;
+    o->term[o->n++] = row;
+    return KMPHOST_OK;
+}
+
+int kmp_links_parse(const char *path, uint32_t n_patterns, uint32_t n_relations, uint32_t n_chains, uint32_t n_headers, uint32_t n_bytetests,
+                    uint32_t n_regexes, kmp_links *out, char errbuf[KMP_LINKS_ERRBUF])
+{
+    _Static_assert(KMP_LINKS_ERRBUF == KMP_LINE_ERRBUF, "the links file's error buffer has the size of the others");
+    memset(out, 0, sizeof *out);
+    if (errbuf) errbuf[0] = 0;
+    links_ctx c;
+    memset(&c, 0, sizeof c);
+    c.terms.n_patterns = n_patterns; c.terms.n_relations = n_relations; c.terms.n_chains = n_chains;
+    c.terms.n_headers = n_headers; c.terms.n_bytetests = n_bytetests; c.terms.n_regexes = n_regexes;
+    c.out = out;
+    const int rc = text_lines(path, links_line, &c, errbuf);
+    if (rc) kmp_links_free(out);
+    return rc;
+}
+
+void kmp_links_free(kmp_links *l)
+{
+    if (!l) return;
+    free(l->buffer); free(l->term);
+    memset(l, 0, sizeof *l);
 }
 
 /* ============================ relations ================================================= */

@@ -1,5 +1,5 @@
 /* kmp_launch.h -- launch entry points of kmp_scan_*.hip / kmp_prep.hip / kmp_fold.hip / kmp_marks.hip / kmp_rules.hip / kmp_relations.hip /
- * kmp_chains.hip / kmp_headers.hip / kmp_bytetests.hip / kmp_regex.hip / kmp_select.hip / kmp_decode.hip / kmp_base64.hip / kmp_fields.hip / kmp_dns.hip / kmp_alerts.hip / kmp_flows.hip / kmp_seams.hip / kmp_streams.hip / kmp_streams_seq.hip / kmp_flowbits.hip / kmp_thresholds.hip, used
+ * kmp_chains.hip / kmp_headers.hip / kmp_bytetests.hip / kmp_regex.hip / kmp_links.hip / kmp_select.hip / kmp_decode.hip / kmp_base64.hip / kmp_fields.hip / kmp_dns.hip / kmp_alerts.hip / kmp_flows.hip / kmp_seams.hip / kmp_streams.hip / kmp_streams_seq.hip / kmp_flowbits.hip / kmp_thresholds.hip, used
  * by the C-ABI layer (kmpgpu.hip), which alone decides what is launched; the tables kmp_launch_scan_multi takes come from kmp_tables.h. */
 #ifndef KMP_LAUNCH_H
 #define KMP_LAUNCH_H
@@ -214,6 +214,26 @@ hipError_t kmp_launch_regexes(const unsigned long long *marks, uint64_t stride, 
 hipError_t kmp_launch_regex_groups(const unsigned long long *marks, uint64_t stride, uint64_t n_pkts, const uint4 *tables, uint32_t n_groups,
                                    const uint8_t *arena, const uint64_t *pkt_off, const uint32_t *pkt_len, bool whole,
                                    unsigned long long *rows, unsigned long long *rx_counts, unsigned long long *any, hipStream_t st);
+/* kmp_links.hip (kmpgpu_link_rows): rows of another context's matrix in this one's payload numbering (the definition: kmpgpu.h).
+ * _rank (2 kernels; KMPGPU_LINK_BITMAP only): over bitmap[ceil(n_dst / 64)], bits at n_dst and above not counted, into ws
+ *   (kmp_link_rank_bytes(n_dst) bytes, 8-byte aligned): tile_base[tiles + 1], 64 bits each, one per KMP_LINK_RANK_TILE map words, the last
+ *   one the number of set bits below n_dst (kmp_link_rank_total), then rank[ceil(n_dst / 64)], 32 bits each, inside the word's tile.
+ * _gather (1 kernel): word j < ceil(n_dst / 64) of dst_rows[r][dst_stride] for every r < n_rows: bit k = bit map(k) of src_rows[r][src_stride]
+ *   where k < n_dst, map(k) exists and map(k) < n_src, else 0.  kind KMPGPU_LINK_SAME: map(k) = k, map and rank_ws not read, both strides
+ *   the same even number, the rows 16-byte aligned; _BITMAP: map = the bitmap of _rank and rank_ws its ws; _INDEX: map = uint32_t[n_dst],
+ *   rank_ws not read.  The padding word of an odd destination row is the caller's, except under _SAME, which copies whole 16-byte
+ *   pairs and writes it as 0.  No word of a source row behind that of payload n_src - 1 is read -- under _SAME the padding word of an odd
+ *   source row, which lies inside the row, is loaded with its pair and masked to 0 -- and no map entry at n_dst or behind.  At most KMP_GRID_CAP blocks, grid-stride. */
+#define KMP_LINK_RANK_TILE 1024u
+size_t kmp_link_rank_bytes(uint64_t n_dst);
+static inline const unsigned long long *kmp_link_rank_total(const uint8_t *ws, uint64_t n_dst)
+{
+    return reinterpret_cast<const unsigned long long *>(ws) + ((n_dst + 63u) / 64u + KMP_LINK_RANK_TILE - 1u) / KMP_LINK_RANK_TILE;
+}
+hipError_t kmp_launch_link_rank(const unsigned long long *bitmap, uint64_t n_dst, uint8_t *ws, hipStream_t st);
+hipError_t kmp_launch_link_gather(int kind, const unsigned long long *src_rows, uint64_t src_stride, uint64_t n_src, uint32_t n_rows,
+                                  uint64_t n_dst, const void *map, const uint8_t *rank_ws, unsigned long long *dst_rows,
+                                  uint64_t dst_stride, hipStream_t st);
 /* ... and the metadata itself.  _extract: behind kmp_launch_extract_phase2, with its arguments and its workspace: meta[k] of every accepted
  * frame, k as kmp_scatter_index_kernel numbers the payloads.  _select: behind kmp_launch_select_phase2, with the workspace of the selection
  * over src's n payloads: meta[j] = src_meta[k] for the j-th selected payload k.  One kernel each. */

@@ -45,10 +45,17 @@ int kmp_pack_rules(const uint32_t *rule_off, const uint32_t *terms, uint32_t n_r
 int kmp_pack_rules(const uint32_t *rule_off, const uint32_t *terms, uint32_t n_rules, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains,
                    uint32_t n_hdr, uint32_t n_bt, uint32_t n_rx, std::vector<uint32_t> *heads, std::vector<uint32_t> *quads, std::string *msg)
 {
+    return kmp_pack_rules(rule_off, terms, n_rules, n_pat, n_rel, n_chains, n_hdr, n_bt, n_rx, 0u, heads, quads, msg);
+}
+
+int kmp_pack_rules(const uint32_t *rule_off, const uint32_t *terms, uint32_t n_rules, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains,
+                   uint32_t n_hdr, uint32_t n_bt, uint32_t n_rx, uint32_t n_links, std::vector<uint32_t> *heads, std::vector<uint32_t> *quads,
+                   std::string *msg)
+{
     heads->clear(); quads->clear();
     if (!rule_off || !terms) return refuse(msg, "kmpgpu_set_rules: NULL rule arrays");
     if (rule_off[0] != 0) return refuse(msg, "kmpgpu_set_rules: rule_off[0] is %u, not 0", rule_off[0]);
-    const uint64_t n_rows = (uint64_t)n_pat + n_rel + n_chains + n_hdr + n_bt + n_rx;  /* (< 2^31: kmp_pack_relations, _chains, _headers, _bytetests, _regexes) */
+    const uint64_t n_rows = (uint64_t)n_pat + n_rel + n_chains + n_hdr + n_bt + n_rx + n_links;  /* (< 2^31: the other packers without the links, kmpgpu_set_links and links_fit in every setter with them) */
     std::vector<uint32_t> ord;
     for (uint32_t r = 0; r < n_rules; r++) {
         if (rule_off[r + 1] < rule_off[r]) return refuse(msg, "kmpgpu_set_rules: rule_off decreases at rule %u", r);
@@ -56,6 +63,9 @@ int kmp_pack_rules(const uint32_t *rule_off, const uint32_t *terms, uint32_t n_r
         ord.clear();
         for (int neg = 0; neg < 2; neg++)
             for (uint32_t j = rule_off[r]; j < rule_off[r + 1]; j++) {
+                if ((terms[j] & ~KMPGPU_RULE_NOT) >= n_rows && n_links)
+                    return refuse(msg, "kmpgpu_set_rules: rule %u: term %u names row %u of %u patterns + %u relations + %u chains + %u header predicates + %u byte tests + %u expressions + %u links",
+                                  r, j - rule_off[r], terms[j] & ~KMPGPU_RULE_NOT, n_pat, n_rel, n_chains, n_hdr, n_bt, n_rx, n_links);
                 if ((terms[j] & ~KMPGPU_RULE_NOT) >= n_rows && n_rx)
                     return refuse(msg, "kmpgpu_set_rules: rule %u: term %u names row %u of %u patterns + %u relations + %u chains + %u header predicates + %u byte tests + %u expressions",
                                   r, j - rule_off[r], terms[j] & ~KMPGPU_RULE_NOT, n_pat, n_rel, n_chains, n_hdr, n_bt, n_rx);

@@ -82,6 +82,13 @@ int kmp_pack_bytetests(const kmpgpu_bytetest *bt, uint32_t n_bt, uint32_t n_pat,
                        uint32_t n_rx, const uint8_t *pat_fold, std::vector<uint32_t> *tests, uint32_t *n_relative, uint32_t *reach,
                        std::string *msg);
 
+/* The same once more with the links' rows behind the expressions' (kmpgpu_set_links): terms name rows below
+ * n_pat + n_rel + n_chains + n_hdr + n_bt + n_rx + n_links.  The links have no table of their own, so the other packers do not know them;
+ * kmpgpu_set_links holds the sum below 2^31.  With n_links = 0 every message is what the entries above give. */
+int kmp_pack_rules(const uint32_t *rule_off, const uint32_t *terms, uint32_t n_rules, uint32_t n_pat, uint32_t n_rel, uint32_t n_chains,
+                   uint32_t n_hdr, uint32_t n_bt, uint32_t n_rx, uint32_t n_links, std::vector<uint32_t> *heads, std::vector<uint32_t> *quads,
+                   std::string *msg);
+
 /* (defined in kmp_regex.cpp, beside the compiler it calls: kmp_rowtables.cpp links without it)  The expressions compiled (kmp_regex.h:
  * kmp_regex_compile) and laid out in tiles of KMP_RX_TILE as kmp_regex.h describes the device table;
  * ceil(n_rx / KMP_RX_TILE) * KMP_RX_TILE_WORDS words.  flags NULL: all 0; gate NULL: none gated.  An unknown flag bit, a gate >= n_pat of

@@ -167,7 +167,7 @@ struct kmpgpu_ctx {
     size_t              h_counts_cap = 0;
     unsigned long long *h_small = nullptr;            /* pinned, 16 words: where the loaders read small device results back (a copy to pageable
                                                          memory goes through the runtime's blocking staging path) */
-    unsigned long long *d_marks = nullptr;            /* the marking pass: hit matrix [n_pat + n_rel + n_chains + n_hdr + n_bt + n_rx][stride], then pkt_counts[n_pat], any[stride], counts[n_pat], rel_pkt_counts[n_rel], chain_pkt_counts[n_chains], hdr_pkt_counts[n_hdr], bt_pkt_counts[n_bt], rx_pkt_counts[n_rx] */
+    unsigned long long *d_marks = nullptr;            /* the marking pass: hit matrix [n_pat + n_rel + n_chains + n_hdr + n_bt + n_rx + n_links][stride], then pkt_counts[n_pat], any[stride], counts[n_pat], rel_pkt_counts[n_rel], chain_pkt_counts[n_chains], hdr_pkt_counts[n_hdr], bt_pkt_counts[n_bt], rx_pkt_counts[n_rx], link_pkt_counts[n_links] */
     uint64_t            marks_cap = 0;                /* words */
     /* kmpgpu_set_rules / kmpgpu_scan_rules: the rules as the kernel reads them (kmp_launch.h, kmp_launch_rules) and the results */
     uint32_t            n_rules = 0;
@@ -203,6 +203,18 @@ struct kmpgpu_ctx {
     /* ... and of those the ones under KMPGPU_RX_GROUPS once more, in tiles of KMP_RXG_TILE for their own kernel (kmp_launch_regex_groups) */
     uint32_t            n_rx_groups = 0;
     uint4              *d_regex_groups = nullptr;
+    /* kmpgpu_set_links / kmpgpu_link_rows: the link rows [n_links][links_stride] as kmpgpu_link_rows translated them, copied behind every
+     * marking pass into rows n_pat + n_rel + n_chains + n_hdr + n_bt + n_rx + q of the hit matrix; link q is that term of a rule.
+     * link_filled[q]: the row holds a verdict on the arena that is attached now (release_arena unfills; a filled link implies links_stride
+     * is the stride of the marking pass).  rule_links: the links the rules name, ascending (kmpgpu_set_rules).  d_link_ws: the map a caller
+     * gave on the host and the ranks of a bitmap (kmp_link_rank_bytes) */
+    uint32_t            n_links = 0, n_links_filled = 0;
+    unsigned long long *d_links = nullptr;
+    uint64_t            links_cap = 0, links_stride = 0;          /* words */
+    std::vector<uint8_t>  link_filled;
+    std::vector<uint32_t> rule_links;
+    uint8_t            *d_link_ws = nullptr;
+    uint64_t            link_ws_cap = 0;
     /* the per-payload metadata the predicates are decided from (kmpgpu_pkt_meta, 16 bytes each), in payload order.  It belongs to the arena:
      * has_meta falls with it (release_arena), the buffer is kept for the next one */
     uint4              *d_meta = nullptr;
@@ -469,6 +481,7 @@ void drop_rules(kmpgpu_ctx *c)
     free_buffer(&c->d_rule_heads);
     free_buffer(&c->d_rule_quads);
     c->n_rules = 0;
+    c->rule_links.clear();
     drop_flowbits(c);
     drop_thresholds(c);
 }
@@ -512,6 +525,22 @@ void drop_regexes(kmpgpu_ctx *c)
     c->n_rx = c->n_rx_groups = 0;
 }
 
+/* every link is unfilled again: the arena its verdicts were about goes, or the family is set anew.  The buffer is kept for the next fill */
+void unfill_links(kmpgpu_ctx *c)
+{
+    std::fill(c->link_filled.begin(), c->link_filled.end(), (uint8_t)0);
+    c->n_links_filled = 0;
+}
+
+/* ... and the links */
+void drop_links(kmpgpu_ctx *c)
+{
+    free_buffer(&c->d_links, &c->links_cap);
+    c->link_filled.clear();
+    c->n_links = c->n_links_filled = 0;
+    c->links_stride = 0;
+}
+
 /* the flows go with the arena and its metadata; their buffers are kept for the next build */
 void drop_flows(kmpgpu_ctx *c, bool rebuild = false)
 {
@@ -552,6 +581,7 @@ void release_patterns(kmpgpu_ctx *c)
     drop_headers(c);                               /* ... and the header predicates sit behind all of them */
     drop_bytetests(c);                             /* ... and the byte tests' anchors meant these patterns */
     drop_regexes(c);                               /* ... and so did the expressions' gates */
+    drop_links(c);                                 /* ... and the links sit behind all of them */
     c->pat_fold.clear();
     c->pat_sig.clear();
     c->alerts_valid = false;                       /* the list named their rows */
@@ -597,6 +627,7 @@ void release_arena(kmpgpu_ctx *c, bool keep_buffers = false)
     drop_seams(c);                                    /* ... and the seam list said which of src's payloads they join */
     drop_spans(c);                                    /* ... and the HTTP spans where their fields lie */
     drop_streams(c);                                  /* ... and the stream records which of them each stream is made of */
+    unfill_links(c);                                  /* ... and the links' verdicts were about them */
 }
 
 /* Host ranges pinned through kmpgpu_host_register.  One copy must not straddle two registrations (the runtime refuses it), and a
@@ -649,7 +680,7 @@ void release_pass_buffers(kmpgpu_ctx *c)
     free_buffer(&c->d_meta, &c->meta_cap); c->has_meta = false;
     free_buffer(&c->d_flow_table, &c->flow_table_cap); free_buffer(&c->d_flow_first, &c->flow_first_cap); free_buffer(&c->d_flow_of, &c->flow_of_cap);
     free_buffer(&c->d_flow_recs, &c->flow_recs_cap); free_buffer(&c->d_flow_fold, &c->flow_fold_cap); free_buffer(&c->d_flow_sel, &c->flow_sel_cap);
-    free_buffer(&c->d_dec_changed, &c->dec_changed_cap);
+    free_buffer(&c->d_dec_changed, &c->dec_changed_cap); free_buffer(&c->d_link_ws, &c->link_ws_cap);
     free_buffer(&c->d_spans, &c->spans_cap); free_buffer(&c->d_dns, &c->dns_cap); drop_spans(c);
     drop_flows(c);
     free_buffer(&c->d_seams, &c->seams_cap); free_buffer(&c->d_seam_flow, &c->seam_flow_cap); free_buffer(&c->d_seam_sort, &c->seam_sort_cap);
@@ -2498,7 +2529,7 @@ namespace {
 struct MarkPass {
     bool empty = false;
     uint64_t W = 0, stride = 0, mat = 0;          /* words per row as the caller sees them / on the device (even); words of the matrix */
-    unsigned long long *d_mat = nullptr, *d_cnt = nullptr;       /* [n_pat + n_rel + n_chains + n_hdr + n_bt + n_rx][stride]; the scan's counts [n_pat] */
+    unsigned long long *d_mat = nullptr, *d_cnt = nullptr;       /* [n_pat + n_rel + n_chains + n_hdr + n_bt + n_rx + n_links][stride]; the scan's counts [n_pat] */
     uint32_t launches = 0;
 };
 
@@ -2521,12 +2552,12 @@ int marking_pass(kmpgpu_ctx *c, const char *who, MarkPass *p)
         const int rr = repack_arena(c);
         if (rr) return rr;
     }
-    /* one device buffer, grown like the others: [marks (n_pat + n_rel + n_chains + n_hdr + n_bt + n_rx) x stride][pkt_counts n_pat][any stride]
-     * [counts n_pat][rel_pkt_counts n_rel][chain_pkt_counts n_chains][hdr_pkt_counts n_hdr][bt_pkt_counts n_bt][rx_pkt_counts n_rx]; the scan
-     * kernels mark rows 0 .. n_pat - 1, the relation kernel, the chain kernel, the header kernel, the byte-test kernels and the regex kernel
-     * write the rows behind them (family_rows) */
-    const uint64_t mat = ((uint64_t)np + c->n_rel + c->n_chains + c->n_hdr + c->n_bt + c->n_rx) * stride;
-    const uint64_t words = mat + np + stride + np + c->n_rel + c->n_chains + c->n_hdr + c->n_bt + c->n_rx;
+    /* one device buffer, grown like the others: [marks (n_pat + n_rel + n_chains + n_hdr + n_bt + n_rx + n_links) x stride][pkt_counts n_pat]
+     * [any stride][counts n_pat][rel_pkt_counts n_rel][chain_pkt_counts n_chains][hdr_pkt_counts n_hdr][bt_pkt_counts n_bt][rx_pkt_counts n_rx]
+     * [link_pkt_counts n_links]; the scan kernels mark rows 0 .. n_pat - 1, the relation kernel, the chain kernel, the header kernel, the
+     * byte-test kernels and the regex kernel write the rows behind them, the link rows are copied in behind those (family_rows) */
+    const uint64_t mat = ((uint64_t)np + c->n_rel + c->n_chains + c->n_hdr + c->n_bt + c->n_rx + c->n_links) * stride;
+    const uint64_t words = mat + np + stride + np + c->n_rel + c->n_chains + c->n_hdr + c->n_bt + c->n_rx + c->n_links;
     hipError_t e = grow_buffer(&c->d_marks, &c->marks_cap, words, EIGHTH);
     if (e != hipSuccess) return alloc_fail(e, "%s: the hit matrix (%llu bytes) could not be allocated", who, (unsigned long long)(words * 8u));
     p->stride = stride; p->mat = mat;
@@ -2554,8 +2585,10 @@ constexpr int FAMILY_HEADERS = KMPGPU_ALERT_CHAINS + 1;
 constexpr int FAMILY_BYTETESTS = KMPGPU_ALERT_CHAINS + 2;
 /* ... and the expressions': a family of kmpgpu_scan_regexes and of the rules' terms */
 constexpr int FAMILY_REGEXES = KMPGPU_ALERT_CHAINS + 3;
+/* ... and the links': a family of kmpgpu_scan_links and of the rules' terms */
+constexpr int FAMILY_LINKS = KMPGPU_ALERT_CHAINS + 4;
 
-/* A row family (KMPGPU_ALERT_*, FAMILY_HEADERS, FAMILY_BYTETESTS, FAMILY_REGEXES): patterns, rules, relations, chains, header predicates, byte tests or expressions.  Where its results lie on the device once its kernels are
+/* A row family (KMPGPU_ALERT_*, FAMILY_HEADERS, FAMILY_BYTETESTS, FAMILY_REGEXES, FAMILY_LINKS): patterns, rules, relations, chains, header predicates, byte tests, expressions or links.  Where its results lie on the device once its kernels are
  * enqueued behind a marking pass (enqueue_family). */
 struct FamilyRows {
     unsigned long long *d_rows = nullptr, *d_pc = nullptr, *d_any = nullptr;     /* [n_rows][stride], payloads per row [n_rows], [stride] */
@@ -2566,10 +2599,10 @@ struct FamilyRows {
 uint64_t family_n_rows(const kmpgpu_ctx *c, int family)
 {
     return family == KMPGPU_ALERT_PATTERNS ? c->n_pat : family == KMPGPU_ALERT_RULES ? c->n_rules : family == KMPGPU_ALERT_RELATIONS ? c->n_rel
-         : family == KMPGPU_ALERT_CHAINS ? c->n_chains : family == FAMILY_HEADERS ? c->n_hdr : family == FAMILY_BYTETESTS ? c->n_bt : c->n_rx;
+         : family == KMPGPU_ALERT_CHAINS ? c->n_chains : family == FAMILY_HEADERS ? c->n_hdr : family == FAMILY_BYTETESTS ? c->n_bt : family == FAMILY_REGEXES ? c->n_rx : c->n_links;
 }
 
-/* The one place that knows where the families live: the patterns, relations, chains, header predicates, byte tests and expressions in the marks buffer as marking_pass lays it out
+/* The one place that knows where the families live: the patterns, relations, chains, header predicates, byte tests, expressions and links in the marks buffer as marking_pass lays it out
  * (they share its any[]; one family's kernel writes it per pass), the rules in the context's rule buffer [rule rows n_rules x stride]
  * [rule_pkt_counts n_rules][any stride]. */
 void family_rows(const kmpgpu_ctx *c, const MarkPass &p, int family, FamilyRows *f)
@@ -2583,7 +2616,8 @@ void family_rows(const kmpgpu_ctx *c, const MarkPass &p, int family, FamilyRows 
     const uint64_t np = c->n_pat, first = family == KMPGPU_ALERT_PATTERNS ? 0 : family == KMPGPU_ALERT_RELATIONS ? np
                                         : family == KMPGPU_ALERT_CHAINS ? np + c->n_rel : family == FAMILY_HEADERS ? np + c->n_rel + c->n_chains
                                         : family == FAMILY_BYTETESTS ? np + c->n_rel + c->n_chains + c->n_hdr
-                                        : np + c->n_rel + c->n_chains + c->n_hdr + c->n_bt;
+                                        : family == FAMILY_REGEXES ? np + c->n_rel + c->n_chains + c->n_hdr + c->n_bt
+                                        : np + c->n_rel + c->n_chains + c->n_hdr + c->n_bt + c->n_rx;
     f->d_rows = p.d_mat + first * p.stride;
     f->d_pc = family == KMPGPU_ALERT_PATTERNS ? p.d_mat + p.mat : p.d_cnt + first;      /* (the counts of the rows behind the patterns': behind the scan's counts) */
     f->d_any = p.d_mat + p.mat + np;
@@ -2662,10 +2696,25 @@ int enqueue_regexes(kmpgpu_ctx *c, const MarkPass &p, uint32_t *launches)
     return KMPGPU_OK;
 }
 
+/* The links behind a marking pass: the link buffer as kmpgpu_link_rows left it, copied into the links' rows of the matrix -- one
+ * device-to-device copy, none while no link is filled (the pass has zeroed the rows).  reduce: their popcounts and their OR into any[] as
+ * well, by the reduce of kmpgpu_scan_packets (kmpgpu_scan_links; the rules have no use for either).  *launches: the reduce, where it ran. */
+int enqueue_links(kmpgpu_ctx *c, const MarkPass &p, bool reduce, uint32_t *launches)
+{
+    FamilyRows f;
+    family_rows(c, p, FAMILY_LINKS, &f);
+    if (c->n_links_filled == 0) return KMPGPU_OK;
+    HIP_TRY(hipMemcpyAsync(f.d_rows, c->d_links, (size_t)(f.n_rows * p.stride) * sizeof(unsigned long long), hipMemcpyDeviceToDevice, c->stream));
+    if (!reduce) return KMPGPU_OK;
+    HIP_TRY(kmp_launch_marks_reduce(f.d_rows, (uint32_t)f.n_rows, p.stride, f.d_pc, f.d_any, c->stream));
+    ++*launches;
+    return KMPGPU_OK;
+}
+
 /* The one place that runs a family's kernels behind a marking pass, and says where they leave their results.  Patterns: the marks reduce.
- * Relations, chains, header predicates, byte tests, expressions: their kernels.  Rules: the relation kernel, the chain kernel, the header
- * kernel, the byte-test kernels and the regex kernel where those are set, then the rules kernel, into the context's rule buffer, grown
- * here. */
+ * Relations, chains, header predicates, byte tests, expressions: their kernels.  Links: the copy of their buffer.  Rules: the relation
+ * kernel, the chain kernel, the header kernel, the byte-test kernels, the regex kernel and the links' copy where those are set, then the
+ * rules kernel, into the context's rule buffer, grown here. */
 int enqueue_family(kmpgpu_ctx *c, const char *who, int family, const MarkPass &p, bool profile_reduce, FamilyRows *f)
 {
     hipEvent_t e1 = nullptr;
@@ -2709,6 +2758,10 @@ int enqueue_family(kmpgpu_ctx *c, const char *who, int family, const MarkPass &p
             const int rr = enqueue_regexes(c, p, &f->launches);
             if (rr) return rr;
         }
+        if (c->n_links) {
+            const int rr = enqueue_links(c, p, /* reduce = */ false, &f->launches);
+            if (rr) return rr;
+        }
         HIP_TRY(profile_launch(c, &e1));
         HIP_TRY(kmp_launch_rules(p.d_mat, p.stride, c->n_pkts, c->d_rule_heads, c->d_rule_quads, c->n_rules, f->d_rows, f->d_pc, f->d_any, c->stream));
         HIP_TRY(profile_launched(c, e1));
@@ -2718,6 +2771,7 @@ int enqueue_family(kmpgpu_ctx *c, const char *who, int family, const MarkPass &p
     family_rows(c, p, family, f);
     if (family == FAMILY_BYTETESTS) return enqueue_bytetests(c, p, &f->launches);
     if (family == FAMILY_REGEXES) return enqueue_regexes(c, p, &f->launches);
+    if (family == FAMILY_LINKS) return enqueue_links(c, p, /* reduce = */ true, &f->launches);
     f->launches = 1u;
     return family == FAMILY_HEADERS ? enqueue_headers(c, p) : enqueue_pairing(c, p, family);
 }
@@ -2729,6 +2783,10 @@ int begin_family(kmpgpu_ctx *c, const char *who, int family, uint64_t *row_count
     /* header predicates are decided from the metadata: none on the context is found out before anything is launched */
     if ((family == FAMILY_HEADERS || (family == KMPGPU_ALERT_RULES && c->n_hdr)) && c->n_pkts && !c->has_meta)
         return fail(KMPGPU_ESTATE, "%s: no packet metadata (KMPGPU_OPT_KEEP_META, kmpgpu_set_meta)", who);
+    /* ... and a rule over a link nobody has filled for this arena has no verdict to read */
+    if (family == KMPGPU_ALERT_RULES)
+        for (uint32_t q : c->rule_links)
+            if (!c->link_filled[q]) return fail(KMPGPU_ESTATE, "%s: a rule names link %u, which is not filled (kmpgpu_link_rows)", who, q);
     const int rc = marking_pass(c, who, p);
     if (rc || !p->empty) return rc;
     if (row_counts_out) memset(row_counts_out, 0, (size_t)family_n_rows(c, family) * sizeof(uint64_t));
@@ -2753,7 +2811,7 @@ int finish_marking(kmpgpu_ctx *c, uint32_t launches, kmpgpu_timing *t)
     return KMPGPU_OK;
 }
 
-/* The body of kmpgpu_scan_packets, _rules, _relations, _chains, _headers, _bytetests and _regexes behind their own checks: marking pass, the family's kernels, downloads. */
+/* The body of kmpgpu_scan_packets, _rules, _relations, _chains, _headers, _bytetests, _regexes and _links behind their own checks: marking pass, the family's kernels, downloads. */
 int scan_family(kmpgpu_ctx *c, const char *who, int family, uint64_t *row_counts_out, uint64_t *any_out, uint64_t *hits_out, uint64_t *counts_out,
                 kmpgpu_timing *t)
 {
@@ -2812,6 +2870,15 @@ int setter_state(kmpgpu_ctx *c, const char *who)
     return KMPGPU_OK;
 }
 
+/* The links sit behind every other family and have no table of their own, so no packer counts them: a setter that grows a family in front
+ * of them holds the sum below the 2^31 rows a rule term can name itself.  rows: what the context would hold without the links. */
+int links_fit(const kmpgpu_ctx *c, const char *who, uint64_t rows)
+{
+    if (c->n_links && rows + c->n_links >= (1ull << 31))
+        return fail(KMPGPU_EINVAL, "%s: %llu rows + %u links do not fit the 2^31 rows a rule term can name", who, (unsigned long long)rows, c->n_links);
+    return KMPGPU_OK;
+}
+
 }  // namespace
 
 int kmpgpu_scan_packets(kmpgpu_ctx *c, uint64_t *pkt_counts_out, uint64_t *any_out, uint64_t *hits_out, uint64_t *counts_out, kmpgpu_timing *t)
@@ -2824,16 +2891,23 @@ int kmpgpu_set_rules(kmpgpu_ctx *c, const uint32_t *rule_off, const uint32_t *te
 {
     const int sr = setter_state(c, "kmpgpu_set_rules");
     if (sr) return sr;
-    std::vector<uint32_t> heads, quads;
+    std::vector<uint32_t> heads, quads, named;
     std::string msg;
     if (n_rules) {
-        const int rc = kmp_pack_rules(rule_off, terms, n_rules, c->n_pat, c->n_rel, c->n_chains, c->n_hdr, c->n_bt, c->n_rx, &heads, &quads, &msg);
+        const int rc = kmp_pack_rules(rule_off, terms, n_rules, c->n_pat, c->n_rel, c->n_chains, c->n_hdr, c->n_bt, c->n_rx, c->n_links, &heads, &quads, &msg);
         if (rc) return fail(rc, "%s", msg.c_str());
         if (quads.empty()) quads.assign(4, 0u);         /* rules of one or two terms only: one quad nobody reads, never a NULL table */
+        /* which links the rules name: what every rules pass checks for filled rows before it starts */
+        const uint32_t link0 = c->n_pat + c->n_rel + c->n_chains + c->n_hdr + c->n_bt + c->n_rx;
+        for (uint32_t j = 0; j < rule_off[n_rules] && c->n_links; j++)
+            if ((terms[j] & ~KMPGPU_RULE_NOT) >= link0) named.push_back((terms[j] & ~KMPGPU_RULE_NOT) - link0);
+        std::sort(named.begin(), named.end());
+        named.erase(std::unique(named.begin(), named.end()), named.end());
     }
     const int rc = swap_tables(c, "kmpgpu_set_rules: the rules", {{heads, (void **)&c->d_rule_heads}, {quads, (void **)&c->d_rule_quads}});
     if (rc) return rc;
     c->n_rules = n_rules;
+    c->rule_links.swap(named);
     drop_flowbits(c);                              /* their rule indices meant the rules before */
     drop_thresholds(c);
     return KMPGPU_OK;
@@ -2863,6 +2937,8 @@ int kmpgpu_set_relations(kmpgpu_ctx *c, const kmpgpu_relation *rel, uint32_t n_r
 {
     const int sr = setter_state(c, "kmpgpu_set_relations");
     if (sr) return sr;
+    const int lf = links_fit(c, "kmpgpu_set_relations", (uint64_t)c->n_pat + n_rel + c->n_chains + c->n_hdr + c->n_bt + c->n_rx);
+    if (lf) return lf;
     std::vector<uint32_t> host;
     std::string msg;
     if (n_rel) {
@@ -2888,6 +2964,8 @@ int kmpgpu_set_chains(kmpgpu_ctx *c, const uint32_t *chain_off, const kmpgpu_cha
 {
     const int sr = setter_state(c, "kmpgpu_set_chains");
     if (sr) return sr;
+    const int lf = links_fit(c, "kmpgpu_set_chains", (uint64_t)c->n_pat + c->n_rel + n_chains + c->n_hdr + c->n_bt + c->n_rx);
+    if (lf) return lf;
     std::vector<uint32_t> host;
     std::string msg;
     if (n_chains) {
@@ -2914,6 +2992,8 @@ int kmpgpu_set_headers(kmpgpu_ctx *c, const kmpgpu_header *h, uint32_t n_hdr)
     static_assert(sizeof(kmpgpu_header) == 36, "kmpgpu_header is the 36-byte record of kmpgpu.h");
     const int sr = setter_state(c, "kmpgpu_set_headers");
     if (sr) return sr;
+    const int lf = links_fit(c, "kmpgpu_set_headers", (uint64_t)c->n_pat + c->n_rel + c->n_chains + n_hdr + c->n_bt + c->n_rx);
+    if (lf) return lf;
     std::vector<uint32_t> host;
     std::string msg;
     if (n_hdr) {
@@ -2940,6 +3020,8 @@ int kmpgpu_set_bytetests(kmpgpu_ctx *c, const kmpgpu_bytetest *bt, uint32_t n_bt
     static_assert(sizeof(kmpgpu_bytetest) == 20, "kmpgpu_bytetest is the 20-byte record of kmpgpu.h");
     const int sr = setter_state(c, "kmpgpu_set_bytetests");
     if (sr) return sr;
+    const int lf = links_fit(c, "kmpgpu_set_bytetests", (uint64_t)c->n_pat + c->n_rel + c->n_chains + c->n_hdr + n_bt + c->n_rx);
+    if (lf) return lf;
     std::vector<uint32_t> host;
     std::string msg;
     uint32_t n_relative = 0, reach = 0;
@@ -2966,6 +3048,8 @@ int kmpgpu_set_regexes(kmpgpu_ctx *c, const uint8_t *const *expr, const uint32_t
 {
     const int sr = setter_state(c, "kmpgpu_set_regexes");
     if (sr) return sr;
+    const int lf = links_fit(c, "kmpgpu_set_regexes", (uint64_t)c->n_pat + c->n_rel + c->n_chains + c->n_hdr + c->n_bt + n_rx);
+    if (lf) return lf;
     std::vector<uint32_t> host, host_groups;
     std::string msg;
     uint32_t n_groups = 0;
@@ -2989,6 +3073,140 @@ int kmpgpu_scan_regexes(kmpgpu_ctx *c, uint64_t *rx_pkt_counts_out, uint64_t *an
     if (!c->d_patterns || c->n_pat == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan_regexes: no patterns set");
     if (c->n_rx == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan_regexes: no expressions set");
     return scan_family(c, "kmpgpu_scan_regexes", FAMILY_REGEXES, rx_pkt_counts_out, any_out, rx_hits_out, counts_out, t);
+}
+
+int kmpgpu_set_links(kmpgpu_ctx *c, uint32_t n_links)
+{
+    const int sr = setter_state(c, "kmpgpu_set_links");
+    if (sr) return sr;
+    if ((uint64_t)c->n_pat + c->n_rel + c->n_chains + c->n_hdr + c->n_bt + c->n_rx + n_links >= (1ull << 31))
+        return fail(KMPGPU_EINVAL, "kmpgpu_set_links: %u links behind the %llu rows in front of them do not fit the 2^31 rows a rule term can name", n_links,
+                    (unsigned long long)c->n_pat + c->n_rel + c->n_chains + c->n_hdr + c->n_bt + c->n_rx);
+    HIP_TRY(hipStreamSynchronize(c->stream));      /* no pass may still copy the old rows */
+    drop_rules(c);                                 /* the rows their terms named are no longer the same, whatever was set or cleared */
+    drop_links(c);
+    c->n_links = n_links;
+    c->link_filled.assign(n_links, (uint8_t)0);
+    return KMPGPU_OK;
+}
+
+int kmpgpu_link_rows(kmpgpu_ctx *dst, uint32_t first_link, kmpgpu_ctx *src, int family, uint32_t first_row, uint32_t n_rows, int map_kind,
+                     const void *map, int map_on_device, kmpgpu_timing *t)
+{
+    const char *who = "kmpgpu_link_rows";
+    if (!dst || !src) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
+    if (dst == src) return fail(KMPGPU_EINVAL, "%s: dst and src are the same context (links to a context's own rows do not exist)", who);
+    if (dst->device != src->device)
+        return fail(KMPGPU_EINVAL, "%s: the contexts sit on devices %d and %d (links across devices do not exist)", who, dst->device, src->device);
+    if (family < KMPGPU_ALERT_PATTERNS || family > KMPGPU_ALERT_CHAINS) return fail(KMPGPU_EINVAL, "%s: family %d is none of KMPGPU_ALERT_*", who, family);
+    if (map_kind != KMPGPU_LINK_SAME && map_kind != KMPGPU_LINK_BITMAP && map_kind != KMPGPU_LINK_INDEX)
+        return fail(KMPGPU_EINVAL, "%s: map kind %d is none of KMPGPU_LINK_*", who, map_kind);
+    if (map_on_device != 0 && map_on_device != 1) return fail(KMPGPU_EINVAL, "%s: map_on_device is %d, not 0 or 1", who, map_on_device);
+    const uint64_t src_rows = family_n_rows(src, family);
+    if ((uint64_t)first_row + n_rows > src_rows)
+        return fail(KMPGPU_EINVAL, "%s: rows %u .. %llu of the %llu rows of src's family %d", who, first_row, (unsigned long long)first_row + n_rows, (unsigned long long)src_rows, family);
+    if ((uint64_t)first_link + n_rows > dst->n_links)
+        return fail(KMPGPU_EINVAL, "%s: links %u .. %llu of dst's %u links", who, first_link, (unsigned long long)first_link + n_rows, dst->n_links);
+    const uint64_t n_dst = dst->n_pkts, n_src = src->n_pkts;
+    if (map_kind == KMPGPU_LINK_SAME && n_src != n_dst)
+        return fail(KMPGPU_EINVAL, "%s: KMPGPU_LINK_SAME between %llu payloads of src and %llu of dst", who, (unsigned long long)n_src, (unsigned long long)n_dst);
+    if (map_kind != KMPGPU_LINK_SAME && n_dst && !map) return fail(KMPGPU_EINVAL, "%s: map is NULL", who);
+    if (map_kind != KMPGPU_LINK_SAME && map_on_device && ((uintptr_t)map & (map_kind == KMPGPU_LINK_BITMAP ? 7u : 3u)))
+        return fail(KMPGPU_EINVAL, "%s: the device map is not %d-byte aligned", who, map_kind == KMPGPU_LINK_BITMAP ? 8 : 4);
+    if (dst->fr_pending || src->fr_pending)
+        return fail(KMPGPU_ESTATE, "%s: %s sits between kmpgpu_load_frames_begin and _finish", who, dst->fr_pending ? "dst" : "src");
+    if (dst->n_links == 0) return fail(KMPGPU_ESTATE, "%s: dst: no links set", who);
+    if (!dst->d_off || n_dst == 0) return fail(KMPGPU_ESTATE, "%s: dst has no arena loaded", who);
+    /* what src's own call for the family refuses before it launches anything (the marking pass says the rest) */
+    if (!src->d_patterns || src->n_pat == 0) return fail(KMPGPU_ESTATE, "%s: src: no patterns set", who);
+    if (family != KMPGPU_ALERT_PATTERNS && src_rows == 0)
+        return fail(KMPGPU_ESTATE, "%s: src: no %s set", who, family == KMPGPU_ALERT_RULES ? "rules" : family == KMPGPU_ALERT_RELATIONS ? "relations" : "chains");
+    if (n_dst > 0xFFFFFFFFull && map_kind == KMPGPU_LINK_INDEX) return fail(KMPGPU_EINVAL, "%s: too many payloads for a 32-bit index map", who);
+    HIP_TRY(hipSetDevice(dst->device));
+    HIP_TRY(hipStreamSynchronize(dst->stream));           /* the passes that still copy the link rows */
+    HIP_TRY(hipStreamSynchronize(src->stream));
+    kmpgpu_ctx *c = dst;
+    const uint64_t W = (n_dst + 63u) / 64u, stride = (W + 1u) & ~1ull;
+    uint32_t launches = 0;
+
+    /* the map on the device, and a bitmap's ranks; their total is checked before a word of a link is written */
+    const uint64_t map_bytes = map_kind == KMPGPU_LINK_BITMAP ? W * sizeof(uint64_t) : map_kind == KMPGPU_LINK_INDEX ? n_dst * sizeof(uint32_t) : 0u;
+    const uint64_t up_bytes = map_on_device ? 0u : (map_bytes + 15u) & ~15ull;
+    const uint64_t rank_bytes = map_kind == KMPGPU_LINK_BITMAP ? kmp_link_rank_bytes(n_dst) : 0u;
+    if (up_bytes + rank_bytes) {
+        const hipError_t e = grow_buffer(&c->d_link_ws, &c->link_ws_cap, up_bytes + rank_bytes, EIGHTH);
+        if (e != hipSuccess) return alloc_fail(e, "%s: the map's workspace (%llu bytes) could not be allocated", who, (unsigned long long)(up_bytes + rank_bytes));
+    }
+    const void *d_map = map;
+    if (map_kind != KMPGPU_LINK_SAME && !map_on_device) {
+        HIP_TRY(hipMemcpyAsync(c->d_link_ws, map, (size_t)map_bytes, hipMemcpyHostToDevice, c->stream));
+        d_map = c->d_link_ws;
+    }
+    uint8_t *rank_ws = c->d_link_ws + up_bytes;
+    if (map_kind == KMPGPU_LINK_BITMAP) {
+        HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+        HIP_TRY(kmp_launch_link_rank((const unsigned long long *)d_map, n_dst, rank_ws, c->stream));
+        HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+        launches += 2u;
+        HIP_TRY(hipMemcpyAsync(c->h_small, kmp_link_rank_total(rank_ws, n_dst), sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));     /* (pinned: no staging) */
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        const unsigned long long total = c->h_small[0];
+        if (total != n_src)
+            return fail(KMPGPU_EINVAL, "%s: the bitmap has %llu bits set below dst's %llu payloads, src holds %llu payloads", who, total,
+                        (unsigned long long)n_dst, (unsigned long long)n_src);
+    }
+
+    /* src's pass: the body of scan_family without a download */
+    MarkPass p;
+    FamilyRows f;
+    const int rc = begin_family(src, who, family, nullptr, nullptr, nullptr, &p);
+    if (rc) return rc;
+    if (!p.empty) {
+        const int rr = enqueue_family(src, who, family, p, /* profile_reduce = */ false, &f);
+        if (rr) return rr;
+        HIP_TRY(hipEventRecord(src->ev[1], src->stream));
+        const int fr = finish_marking(src, p.launches + f.launches, nullptr);
+        if (fr) return fr;
+    }
+
+    /* dst's link buffer: taken anew for another stride (no link is filled then), all zero while no link is filled */
+    const uint64_t words = (uint64_t)c->n_links * stride;
+    if (c->n_links_filled == 0) {
+        const hipError_t e = grow_buffer(&c->d_links, &c->links_cap, words, EIGHTH);
+        if (e != hipSuccess) return alloc_fail(e, "%s: the link rows (%llu bytes) could not be allocated", who, (unsigned long long)(words * 8u));
+        c->links_stride = stride;
+        HIP_TRY(hipMemsetAsync(c->d_links, 0, (size_t)words * sizeof(unsigned long long), c->stream));
+    }
+    unsigned long long *d_out = c->d_links + (uint64_t)first_link * stride;
+    HIP_TRY(hipEventRecord(c->ev[0], c->stream));              /* (behind src's pass: the translation's own time) */
+    if (p.empty) {
+        /* src without payloads: no row has a bit */
+        if (n_rows) HIP_TRY(hipMemsetAsync(d_out, 0, (size_t)((uint64_t)n_rows * stride) * sizeof(unsigned long long), c->stream));
+    } else if (n_rows) {
+        HIP_TRY(kmp_launch_link_gather(map_kind, f.d_rows + (uint64_t)first_row * p.stride, p.stride, n_src, n_rows, n_dst, d_map, rank_ws, d_out, stride,
+                                       c->stream));
+        launches += 1u;
+    }
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t q = first_link; q < first_link + n_rows; q++)
+        if (!c->link_filled[q]) { c->link_filled[q] = 1; c->n_links_filled++; }
+    if (t) {
+        float ms = 0, rank_ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+        if (map_kind == KMPGPU_LINK_BITMAP) HIP_TRY(hipEventElapsedTime(&rank_ms, c->ev[2], c->ev[3]));
+        *t = kmpgpu_timing{};
+        t->kernel_ms = ms + rank_ms; t->launches = launches;
+    }
+    return KMPGPU_OK;
+}
+
+int kmpgpu_scan_links(kmpgpu_ctx *c, uint64_t *link_pkt_counts_out, uint64_t *any_out, uint64_t *link_hits_out, uint64_t *counts_out, kmpgpu_timing *t)
+{
+    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_scan_links: ctx is NULL");
+    if (!c->d_patterns || c->n_pat == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan_links: no patterns set");
+    if (c->n_links == 0) return fail(KMPGPU_ESTATE, "kmpgpu_scan_links: no links set");
+    return scan_family(c, "kmpgpu_scan_links", FAMILY_LINKS, link_pkt_counts_out, any_out, link_hits_out, counts_out, t);
 }
 
 int kmpgpu_set_meta(kmpgpu_ctx *c, const void *meta, uint64_t n_pkts, int on_device)
@@ -3257,7 +3475,7 @@ static int scan_flows_body(kmpgpu_ctx *c, const char *who, kmpgpu_ctx *sm, int f
     /* the folded matrix, rows of an even number of words as the reduce and the rules kernel read them: SCOPE_PACKET [family's rows x Sf]
      * [flow_counts rows][any Sf]; SCOPE_FLOW [term rows x Sf][rule rows x Sf][flow_counts rules][any Sf] */
     const uint64_t Wf = (c->n_flows + 63u) / 64u, Sf = (Wf + 1u) & ~1ull;
-    const uint64_t n_terms = (uint64_t)c->n_pat + c->n_rel + c->n_chains + c->n_hdr + c->n_bt + c->n_rx;
+    const uint64_t n_terms = (uint64_t)c->n_pat + c->n_rel + c->n_chains + c->n_hdr + c->n_bt + c->n_rx + c->n_links;
     const uint64_t fold_rows = per_flow ? n_terms : n_rows, out_rows = per_flow ? n_terms + n_rows : n_rows;
     const uint64_t words = out_rows * Sf + n_rows + Sf;
     const hipError_t e = grow_buffer(&c->d_flow_fold, &c->flow_fold_cap, words, EIGHTH);

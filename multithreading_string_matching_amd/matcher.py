@@ -29,6 +29,7 @@ MODE_FILTER, MODE_AUTOMATON = 0, 1
 PAT_NOCASE = 1          # kmpgpu_set_patterns_flags: ASCII letters match either case
 ALERT_PATTERNS, ALERT_RULES, ALERT_RELATIONS, ALERT_CHAINS = 0, 1, 2, 3     # KMPGPU_ALERT_*: the row family of scan_alerts
 ALERT_FAMILIES = {"patterns": ALERT_PATTERNS, "rules": ALERT_RULES, "relations": ALERT_RELATIONS, "chains": ALERT_CHAINS}
+LINK_SAME, LINK_BITMAP, LINK_INDEX, LINK_NONE = 0, 1, 2, 0xFFFFFFFF     # KMPGPU_LINK_*: the map kinds of link_rows
 ALERT_DTYPE = np.dtype([("packet", "<u8"), ("index", "<u4"), ("reserved", "<u4")])     # kmpgpu_alert, 16 bytes
 ALERTS_ALL = 0xFFFFFFFFFFFFFFFF     # max_records: keep the whole list
 FLOW_DIRECTED = 1       # KMPGPU_FLOW_DIRECTED: the two directions of a conversation are two flows
@@ -180,6 +181,7 @@ class GpuMatcher:
         self.headers = np.zeros(0, dtype=HEADER_DTYPE)     # the predicates as set_headers took them
         self.bytetests = np.zeros(0, dtype=BYTETEST_DTYPE)  # the byte tests as set_bytetests took them
         self.regexes: list = []    # (expr, flags, gate) per expression as set_regexes took them, [] = none
+        self.n_links = 0           # the linked rows set_links reserved
         self._keep = None          # objects whose device memory the context borrows
         self._comm = None          # the GpuComm this matcher is a rank of: closed before the context
 
@@ -212,6 +214,7 @@ class GpuMatcher:
         self.headers = np.zeros(0, dtype=HEADER_DTYPE)     # ... and its header predicates
         self.bytetests = np.zeros(0, dtype=BYTETEST_DTYPE)  # ... and its byte tests
         self.regexes = []          # ... and its expressions
+        self.n_links = 0           # ... and its links
 
     def set_rules(self, rules) -> None:
         """Content rules over the current patterns (kmpgpu_set_rules): a sequence of (all_of, none_of) pattern-index sequences;
@@ -220,7 +223,7 @@ class GpuMatcher:
         for a, b in rules:
             for i in a + b:
                 if not 0 <= i < _lib.RULE_NOT:
-                    raise ValueError(f"rule term {i}: not a pattern index (or rel(q), chain(c), hdr(q), btest(q), regex(q))")
+                    raise ValueError(f"rule term {i}: not a pattern index (or rel(q), chain(c), hdr(q), btest(q), regex(q), link(q))")
         off = np.zeros(len(rules) + 1, dtype=np.uint32)
         off[1:] = np.cumsum([len(a) + len(b) for a, b in rules])
         terms = np.array([t for a, b in rules for t in a + [i | _lib.RULE_NOT for i in b]] or [0], dtype=np.uint32)
@@ -420,6 +423,74 @@ class GpuMatcher:
         if not 0 <= q < len(self.regexes):
             raise ValueError(f"regex({q}): {len(self.regexes)} expressions are set")
         return len(self.patterns) + len(self.relations) + len(self.chains) + len(self.headers) + len(self.bytetests) + q
+
+    def set_links(self, n: int) -> None:
+        """Reserve ``n`` linked rows behind the expressions' rows (kmpgpu_set_links): rows another matcher computes over its own view of
+        these payloads, filled by link_rows() and named in set_rules as link(q).  0 clears them.  Every successful call drops the rules,
+        as the library does, and leaves every link unfilled."""
+        gpu_check(self._g.kmpgpu_set_links(self._ctx, int(n)), "kmpgpu_set_links")
+        self.n_links = int(n)
+        self.rules = []            # the library drops its rules with the rows they referred to
+
+    def link(self, q: int) -> int:
+        """The term of link q in set_rules: it is row len(patterns) + len(relations) + len(chains) + len(headers) + len(bytetests) +
+        len(regexes) + q of the hit matrix."""
+        if not 0 <= q < self.n_links:
+            raise ValueError(f"link({q}): {self.n_links} links are set")
+        return len(self.patterns) + len(self.relations) + len(self.chains) + len(self.headers) + len(self.bytetests) + len(self.regexes) + q
+
+    def link_rows(self, first_link: int, src: "GpuMatcher", family: str = "rules", rows=None, map=None) -> Timing:
+        """Fill links first_link, first_link + 1, ... of this matcher from rows of ``src``'s family ("patterns", "rules", "relations",
+        "chains"), translated on the device into this matcher's payload numbering (kmpgpu_link_rows; src's pass for the family runs
+        inside).  rows: None for all rows of the family, a range of consecutive rows, or one row.  map says which payload of src payload k
+        of this matcher is: None -- the same k (the payload counts must be equal); a bool[n] array or uint64 words -- the j-th set bit
+        is src's payload j (the ``changed`` / ``present`` of the derived-arena loaders, the select of load_selected); a uint32[n] array
+        -- src's payload for each of this matcher's, a value >= src's payload count (LINK_NONE) for none (stream_map()["stream"]); or a
+        contiguous torch tensor on the device, of 64-bit words for the bitmap and 32-bit values for the index.  Returns the timing of
+        the translation."""
+        fam = ALERT_FAMILIES
+        if family not in fam:
+            raise ValueError(f"link_rows: family {family!r}; one of {sorted(fam)} is needed")
+        n_fam = {"patterns": len(src.patterns), "rules": len(src.rules), "relations": len(src.relations), "chains": len(src.chains)}[family]
+        if rows is None:
+            first_row, n_rows = 0, n_fam
+        elif isinstance(rows, range):
+            if rows.step != 1:
+                raise ValueError("link_rows: rows must be consecutive")
+            first_row, n_rows = rows.start, len(rows)
+        else:
+            first_row, n_rows = int(rows), 1
+        n_dst, _ = self.arena_info()
+        W = (n_dst + 63) // 64
+        kind, ptr, on_device, keep = LINK_SAME, None, 0, None
+        if map is None:
+            pass
+        elif isinstance(map, np.ndarray):
+            if map.dtype == np.uint32:
+                if map.shape != (n_dst,):
+                    raise ValueError(f"map: uint32{list(map.shape)} for {n_dst} payloads")
+                kind, keep = LINK_INDEX, np.ascontiguousarray(map)
+            else:
+                kind, keep = LINK_BITMAP, select_words(map, n_dst)
+            ptr = keep.ctypes.data if n_dst else None
+        else:                                     # a torch tensor on the device
+            if not map.is_cuda or map.device.index != self.device or not map.is_contiguous() or map.dtype.is_floating_point \
+                    or map.dtype.itemsize not in (4, 8) or map.numel() != (W if map.dtype.itemsize == 8 else n_dst):
+                raise ValueError(f"map: a contiguous tensor of {W} 64-bit words or {n_dst} 32-bit values on the matcher's device is needed")
+            import torch
+            torch.cuda.current_stream(map.device).synchronize()              # complete before the call (kmpgpu.h)
+            kind = LINK_BITMAP if map.dtype.itemsize == 8 else LINK_INDEX
+            ptr, on_device, keep = (map.data_ptr() if n_dst else None), 1, map
+        t = Timing()
+        gpu_check(self._g.kmpgpu_link_rows(self._ctx, int(first_link), src._ctx, fam[family], first_row, n_rows, kind, ptr, on_device,
+                                           C.byref(t)), "kmpgpu_link_rows")
+        del keep
+        return t
+
+    def scan_links(self, hits: bool = False) -> dict:
+        """The linked rows as this matcher holds them (kmpgpu_scan_links): the marking pass of scan_packets and the copy of the link
+        buffer; an unfilled link reads as no payload.  A dict as scan_packets returns, with ``link_pkt_counts`` (uint64[n_links])."""
+        return self._scan_family("kmpgpu_scan_links", self.n_links, "link_pkt_counts", hits)
 
     def set_meta(self, meta) -> None:
         """The per-payload header metadata of the arena at hand (kmpgpu_set_meta): a META_DTYPE array with one record per payload
