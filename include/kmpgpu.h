@@ -1073,6 +1073,79 @@ int  kmpgpu_load_dns(kmpgpu_ctx *dst, kmpgpu_ctx *src, int field, uint32_t flags
                      uint64_t *present_out /* host [ceil(n_src / 64)] or NULL */, const void **d_present /* or NULL */,
                      kmpgpu_fields_stats *stats /* or NULL */);
 
+/* TLS ClientHello buffers: the server name (SNI) and the ALPN protocol list of the ClientHello in every payload, each as a packed arena
+ * that a second context owns -- the tls.sni / tls_sni buffer of signature languages, and the ALPN list as `h2,http/1.1`.  They are the
+ * only text of a TLS connection a signature can name; a pattern over the payload cannot tell the server name from the same bytes
+ * anywhere else, and the ALPN names are length-prefixed on the wire as DNS labels are.
+ * Definition.  Let payload k be the bytes p[0..L), L = pkt_len[k]: the whole payload, whatever KMPGPU_OPT_WHOLE_PAYLOAD says.  No byte at
+ * or behind L takes part: slot padding of a borrowed arena may be dirty.  be16 and be24 are big-endian reads.
+ * The payload is NONE, with every field absent and an all-zero record, unless all of these hold:
+ *   The fixed header.  L >= 11, p[0] == 22 (handshake), p[1] == 3, p[2] <= 4, p[5] == 1 (client_hello), p[9] == 3; with rec = be16(p + 3)
+ *     and hs = be24(p + 6): rec >= hs + 4, the hello lies in one record.  All of this sits in the first aligned 16-byte unit.
+ *   The fixed part.  Let H = 9 + hs and E = min(L, H).  43 < E and sid = p[43] <= 32.  c = 44 + sid needs c + 2 <= E; cs = be16(p + c)
+ *     is even and >= 2.  c += 2 + cs needs c < E; cm = p[c] >= 1.  c += 1 + cm.  c == H: the hello has no extensions, it is valid and
+ *     both fields are absent.  Otherwise c + 2 <= E, X = c + 2 + be16(p + c) == H, and c += 2.  Let Xe = min(X, E): the hello is
+ *     TRUNCATED where Xe < X.
+ *   The extension walk.  While c + 4 <= Xe: t = be16(p + c), n = be16(p + c + 2), b = c + 4.  b + n > X makes the payload NONE.
+ *     b + n > Xe ends the walk (only in a truncated hello).  Otherwise the extension counts, and a 256th makes the payload NONE; the
+ *     first with t == 0 is the server name, the first with t == 16 is ALPN, any other and every later one of these two is stepped over
+ *     unread; c = b + n.  A hello that is not truncated ends the walk with c == X.
+ *   The server name.  n >= 5; ll = be16(p + b) with ll + 2 <= n; p[b + 2] == 0 (host_name); nl = be16(p + b + 3) with 3 + nl <= ll.  Any
+ *     other shape makes the payload NONE.
+ *   ALPN.  n >= 4; ll = be16(p + b) with ll + 2 == n and ll >= 2; any other shape makes the payload NONE.  ll > 256 makes ALPN absent and
+ *     sets ALPN_SKIPPED (the separator mask is 256 bits wide).  Otherwise, from b + 2 on, every name has a length byte 1 .. 255 and the
+ *     names end exactly at b + 2 + ll; any other shape makes the payload NONE.
+ * Fields of a payload that is not NONE:
+ *   SNI is the bytes p[b + 5 .. b + 5 + nl) as they are: the first entry only, no case folding, no IDNA.  nl == 0 is present and empty.
+ *   ALPN is the bytes p[b + 3 .. b + 2 + ll) with every later length byte replaced by ',': h2,http/1.1.
+ *   A truncated hello keeps whatever fields its whole extensions gave it.
+ * Limits: one hello per payload, at its start; no hello split over records, no SSLv2 hello; no DTLS, no QUIC; no
+ * encrypted client hello; no second server_name entry; no JA3 / JA4; no detection by port; no ServerHello, no certificates.  A hello
+ * split over TCP segments is found whole only through a stream context (kmpgpu_load_streams).
+ *
+ * kmpgpu_tls_locate decides all of this for every payload of ctx's arena in one kernel and keeps one kmpgpu_tls_span per payload on the
+ * device.  Offsets count from p[0]; record_version = be16(p + 1), client_version = be16(p + 9), hs_len = hs, sid_len = sid, n_suites =
+ * cs / 2, n_ext the extensions that counted, n_alpn the names walked; an absent field has offset and length 0; a NONE payload's record
+ * is all zero.  flags: 0.  *stats (may be NULL): the hellos, those with a server name, those with an ALPN field, the truncated ones.  The
+ * spans belong to the arena: exactly the calls that drop the HTTP and DNS spans drop them, a scan does not.  With valid spans the call
+ * launches nothing and hands out the stats again.  kmpgpu_tls_spans_read copies records [first, first + n) to the host (KMPGPU_ESTATE
+ * without valid spans, KMPGPU_EINVAL for a range that leaves them).  Both are synchronous on ctx's stream; KMPGPU_ESTATE between
+ * kmpgpu_load_frames_begin and _finish, KMPGPU_EINVAL for an unknown flag bit.  kmpgpu_last_timing: kernel_ms of the locate, launches =
+ * 1 (0 where the spans were valid); kmpgpu_profile_begin .. _end time it as one pair.
+ *
+ * kmpgpu_load_tls makes dst's arena the field `field` (KMPGPU_TLS_SNI or KMPGPU_TLS_ALPN) of every payload of src, running the locate
+ * on src first where src's spans are stale.  flags: KMPGPU_TLS_ONLY_PRESENT (dst holds only the payloads whose field is present, as
+ * kmpgpu_load_fields; without it a payload without the field is an empty payload, in src's numbering).  The result layout, present_out
+ * / *d_present, *stats, the metadata carried along, the state dst's arena is left in, dst without an arena and KMPGPU_OK where no
+ * payload is held or n_src == 0, the workspace and the ordering are those of kmpgpu_load_fields, word for word; src keeps everything
+ * but its span cache, and every output of it is bit-identical before and after.  Errors, all refused before any launch: dst == src, a
+ * NULL context, contexts on different devices, an unknown field, an unknown flag bit: KMPGPU_EINVAL; either context between
+ * kmpgpu_load_frames_begin and _finish: KMPGPU_ESTATE; after each of these dst keeps the arena it had.  kmpgpu_last_timing(dst) and
+ * kmpgpu_profile_begin .. _end: as kmpgpu_load_fields (5 launches; 3 where dst ends up without a payload; one more where the locate ran).
+ * A TLS buffer links like any other context: kmpgpu_link_rows with the identity map, or the present bitmap under ONLY_PRESENT.
+ * Cost: the locate reads the first 16 bytes of every payload and of the hellos the units that hold a length field of
+ * the walk; the load reads the spans twice, for ALPN the separator masks, the field's bytes once, and writes the field once. */
+#define KMPGPU_TLS_NONE          0      /* kmpgpu_tls_span.kind */
+#define KMPGPU_TLS_CLIENT_HELLO  1
+#define KMPGPU_TLS_HAS_SNI       1u     /* kmpgpu_tls_span.flags */
+#define KMPGPU_TLS_HAS_ALPN      2u
+#define KMPGPU_TLS_TRUNCATED     4u
+#define KMPGPU_TLS_ALPN_SKIPPED  8u
+typedef struct kmpgpu_tls_span {
+    uint8_t  kind, flags, n_ext, sid_len;
+    uint16_t record_version, client_version, n_suites, n_alpn;
+    uint32_t hs_len, sni_off, sni_len, alpn_off, alpn_len;
+} kmpgpu_tls_span;
+typedef struct kmpgpu_tls_stats { uint64_t n_hellos, n_sni, n_alpn, n_truncated; } kmpgpu_tls_stats;
+#define KMPGPU_TLS_SNI          1      /* field */
+#define KMPGPU_TLS_ALPN         2
+#define KMPGPU_TLS_ONLY_PRESENT 1u     /* flags of kmpgpu_load_tls: dst holds only the payloads that have the field */
+int  kmpgpu_tls_locate(kmpgpu_ctx *ctx, uint32_t flags /* 0 */, kmpgpu_tls_stats *stats /* or NULL */);
+int  kmpgpu_tls_spans_read(kmpgpu_ctx *ctx, kmpgpu_tls_span *out, uint64_t first, uint64_t n);
+int  kmpgpu_load_tls(kmpgpu_ctx *dst, kmpgpu_ctx *src, int field, uint32_t flags,
+                     uint64_t *present_out /* host [ceil(n_src / 64)] or NULL */, const void **d_present /* or NULL */,
+                     kmpgpu_fields_stats *stats /* or NULL */);
+
 /* Flows: the payloads of the arena grouped by the 5-tuple of their metadata (kmpgpu_pkt_meta, above), on the device -- which payloads
  * belong to one connection, what each connection carried, and the hit rows of every family folded from payload space into flow space.
  * Definitions.  With M = meta[k], the two endpoints of payload k are the 48-bit integers e_src = src_ip << 16 | src_port and

@@ -40,6 +40,9 @@ from .matcher import (  # noqa: F401
     LINK_INDEX,
     LINK_NONE,
     LINK_SAME,
+    TLS_ALPN,
+    TLS_ONLY_PRESENT,
+    TLS_SNI,
     count_matches,
     device_count,
 )

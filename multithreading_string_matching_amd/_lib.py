@@ -191,6 +191,18 @@ class DnsSpan(C.Structure):
                 ("reserved", C.c_uint16), ("name_off", C.c_uint32), ("name_len", C.c_uint32), ("q_end", C.c_uint32)]
 
 
+class TlsStats(C.Structure):
+    """kmpgpu_tls_stats (include/kmpgpu.h)."""
+    _fields_ = [("n_hellos", C.c_uint64), ("n_sni", C.c_uint64), ("n_alpn", C.c_uint64), ("n_truncated", C.c_uint64)]
+
+
+class TlsSpan(C.Structure):
+    """kmpgpu_tls_span (include/kmpgpu.h), 32 bytes."""
+    _fields_ = [("kind", C.c_uint8), ("flags", C.c_uint8), ("n_ext", C.c_uint8), ("sid_len", C.c_uint8), ("record_version", C.c_uint16),
+                ("client_version", C.c_uint16), ("n_suites", C.c_uint16), ("n_alpn", C.c_uint16), ("hs_len", C.c_uint32),
+                ("sni_off", C.c_uint32), ("sni_len", C.c_uint32), ("alpn_off", C.c_uint32), ("alpn_len", C.c_uint32)]
+
+
 class FieldsStats(C.Structure):
     """kmpgpu_fields_stats (include/kmpgpu.h)."""
     _fields_ = [("n_payloads", C.c_uint64), ("n_present", C.c_uint64), ("bytes_in", C.c_uint64), ("bytes_out", C.c_uint64)]
@@ -365,6 +377,9 @@ GPU_API = {
     "kmpgpu_dns_locate": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(DnsStats)]),
     "kmpgpu_dns_spans_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "kmpgpu_load_dns": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(FieldsStats)]),
+    "kmpgpu_tls_locate": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(TlsStats)]),
+    "kmpgpu_tls_spans_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "kmpgpu_load_tls": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(FieldsStats)]),
     "kmpgpu_flows_build": (C.c_int, [C.c_void_p, C.c_uint32, u64p, C.POINTER(Timing)]),
     "kmpgpu_flows_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "kmpgpu_flow_ids_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),

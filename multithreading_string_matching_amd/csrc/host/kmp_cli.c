@@ -140,6 +140,15 @@
  * with KMPGPU_DECODE, KMPGPU_HTTP_FIELD, KMPGPU_BASE64, KMPGPU_OFFSETS_FILE, KMPGPU_EXPORT_FILE, KMPGPU_FLOW_SEAMS, KMPGPU_FLOW_STREAMS,
  * KMPGPU_FLOWBITS_FILE or KMPGPU_THRESHOLDS_FILE; the variable with none of the three row outputs.
  *
+ * KMPGPU_TLS_FIELD=sni|alpn, together with at least one of KMPGPU_PACKETS_FILE, KMPGPU_ALERTS_FILE and KMPGPU_FLOW_ALERTS_FILE: these row
+ * outputs are decided on the server name, or on the ALPN protocol list written as `h2,http/1.1`, of the TLS ClientHello in every payload
+ * (kmpgpu_load_tls; the definition: kmpgpu.h), so that a rule that names `example.com` meets the server name and nothing else of the
+ * connection.  Per shard a second context as KMPGPU_DNS_FIELD builds its own: every payload (no hello, or none with the field: an empty
+ * payload), so the payload numbers are the capture's.  stdout and KMPGPU_FLOWS_FILE are what they are without the variable.  Refused with
+ * a message on stderr and exit 1, before any GPU work and behind every other check: any other value; the variable together with
+ * anything KMPGPU_DNS_FIELD does not go with, with KMPGPU_DNS_FIELD itself or with KMPGPU_LINKS_FILE (the links file has no tls: buffer
+ * word; at the library a TLS buffer links like any other context); the variable with none of the three row outputs.
+ *
  * KMPGPU_FLOW_STREAMS=<depth>, together with KMPGPU_FLOW_ALERTS_FILE: the flow alerts are decided on the reassembled streams.  A second
  * context on the shard's device gets the same tables as the shard's (upload_tables; the windows too: on a stream they mean "offset in the
  * connection's direction") and the payloads of every flow direction concatenated in capture order and cut to <depth> bytes
@@ -194,6 +203,7 @@
 #include "kmp_cli_base64.h"
 #include "kmp_cli_fields.h"
 #include "kmp_cli_dns.h"
+#include "kmp_cli_tls.h"
 #include "kmp_cli_links.h"
 #include "kmp_cli_streams.h"
 #include "kmp_cli_streams_order.h"
@@ -223,6 +233,7 @@ typedef struct cli_options {
     int decode;                             /* KMPGPU_DECODE: KMP_CLI_DECODE_* */
     int http_field;                         /* KMPGPU_HTTP_FIELD: KMP_CLI_FIELD_* */
     int dns_field, dns_tcp;                 /* KMPGPU_DNS_FIELD: KMP_CLI_DNS_*, and ",tcp" */
+    int tls_field;                          /* KMPGPU_TLS_FIELD: KMP_CLI_TLS_* */
     unsigned base64_min_run;                /* KMPGPU_BASE64: min_run, 0 = not set */
     int base64_url;                         /* ... ,url */
     uint32_t flow_streams;                  /* KMPGPU_FLOW_STREAMS: the depth, 0 without the variable */
@@ -280,7 +291,7 @@ typedef struct cli_run {
     int ndev, shards, reduce_rccl, rules_set;
     shard_job *job;
     kmpgpu_ctx **ctxs;                      /* ctxs[r] = job[r].ctx */
-    kmpgpu_ctx **rows;                      /* rows[r]: the context the row outputs of shard r come from -- ctxs[r], or with KMPGPU_DECODE its decoding, with KMPGPU_HTTP_FIELD its field buffer, with KMPGPU_BASE64 its base64 decoding, with KMPGPU_DNS_FIELD its name buffer */
+    kmpgpu_ctx **rows;                      /* rows[r]: the context the row outputs of shard r come from -- ctxs[r], or with KMPGPU_DECODE its decoding, with KMPGPU_HTTP_FIELD its field buffer, with KMPGPU_BASE64 its base64 decoding, with KMPGPU_DNS_FIELD its name buffer, with KMPGPU_TLS_FIELD its server-name or ALPN buffer */
     kmpgpu_comm *comm;
     uint64_t *own, *counts;                 /* own[r * n_patterns + i]: shard r's count of pattern i; counts[i]: the total */
     double kernel_ms;
@@ -697,6 +708,35 @@ static void load_options(int argc, char *argv[], cli_options *opt)
             exit(1);
         }
     }
+    /* the TLS server-name or ALPN buffer: it changes what the row outputs hold and nothing else.  Behind every other check. */
+    const char *tls_env = env_path("KMPGPU_TLS_FIELD");
+    if (tls_env) {
+        static const char *const not_with[][2] = {
+            {"KMPGPU_DECODE", "a field is taken as it is on the wire; at the library, kmpgpu_load_decoded over the TLS context decodes it"},
+            {"KMPGPU_HTTP_FIELD", "one buffer per run"},
+            {"KMPGPU_DNS_FIELD", "one buffer per run"},
+            {"KMPGPU_BASE64", "base64 in a TLS buffer is not wired in this program"},
+            {"KMPGPU_LINKS_FILE", "the links file has no tls: buffer word; at the library, kmpgpu_link_rows links a TLS buffer like any other context"},
+            {"KMPGPU_OFFSETS_FILE", "offsets in a field are not mapped back to the capture's"},
+            {"KMPGPU_EXPORT_FILE", "the export selects and writes the payloads as captured"},
+            {"KMPGPU_FLOW_SEAMS", "seams of TLS fields do not exist"},
+            {"KMPGPU_FLOW_STREAMS", "TLS fields of streams are not wired in this program"},
+            {"KMPGPU_FLOWBITS_FILE", "flow bits over a TLS buffer are not wired in this program"},
+            {"KMPGPU_THRESHOLDS_FILE", "a TLS buffer keeps no timestamps in this program"}};
+        if (!kmp_cli_parse_tls(tls_env, &opt->tls_field)) {
+            fprintf(stderr, "KMPGPU_TLS_FIELD is \"%s\": sni or alpn is needed\n", tls_env);
+            exit(1);
+        }
+        for (size_t i = 0; i < sizeof not_with / sizeof not_with[0]; i++)
+            if (env_path(not_with[i][0])) {
+                fprintf(stderr, "KMPGPU_TLS_FIELD does not go together with %s: %s\n", not_with[i][0], not_with[i][1]);
+                exit(1);
+            }
+        if (!opt->packets_path && !opt->alerts_path && !opt->flow_alerts_path) {
+            fprintf(stderr, "KMPGPU_TLS_FIELD has no effect without KMPGPU_PACKETS_FILE, KMPGPU_ALERTS_FILE or KMPGPU_FLOW_ALERTS_FILE\n");
+            exit(1);
+        }
+    }
     opt->want_meta = opt->headers.n || opt->flows_path || opt->flow_alerts_path || opt->flowbits.n || opt->thresholds_by_flow || opt->thresholds_by_addr;
     /* the export starts as a capture without frames: a path that cannot be written ends the run here */
     if (opt->export_path && kmp_write_udp_pcap_part(opt->export_path, 0, NULL, NULL, NULL, 0, 0)) {
@@ -935,6 +975,21 @@ static void dns_shards(const cli_options *opt, cli_run *run)
         const char *failed = upload_tables(d, opt);
         if (failed) die_gpu(failed);
         if (kmpgpu_load_dns(d, run->ctxs[r], opt->dns_field, flags, NULL, NULL, NULL)) die_gpu("kmpgpu_load_dns");
+        run->rows[r] = d;
+    }
+}
+
+/* KMPGPU_TLS_FIELD: as dns_shards, the server name or the ALPN list of the ClientHello in every payload of the shard (none: an empty
+ * payload). */
+static void tls_shards(const cli_options *opt, cli_run *run)
+{
+    _Static_assert(KMP_CLI_TLS_SNI == KMPGPU_TLS_SNI && KMP_CLI_TLS_ALPN == KMPGPU_TLS_ALPN, "KMP_CLI_TLS_* are the values of KMPGPU_TLS_*");
+    for (int r = 0; r < run->shards; r++) {
+        kmpgpu_ctx *d = NULL;
+        if (kmpgpu_init(&d, run->job[r].device)) die_gpu("kmpgpu_init");
+        const char *failed = upload_tables(d, opt);
+        if (failed) die_gpu(failed);
+        if (kmpgpu_load_tls(d, run->ctxs[r], opt->tls_field, 0u, NULL, NULL, NULL)) die_gpu("kmpgpu_load_tls");
         run->rows[r] = d;
     }
 }
@@ -1269,6 +1324,7 @@ int main(int argc, char *argv[])
         if (opt.base64_min_run) base64_shards(&opt, &run);
         if (opt.http_field) field_shards(&opt, &run);
         if (opt.dns_field) dns_shards(&opt, &run);
+        if (opt.tls_field) tls_shards(&opt, &run);
         if (opt.links.n) links_shards(&opt, &run);
         if (opt.offsets_path) write_offsets(opt.offsets_path, &run, n);
         if (opt.packets_path) write_alerts(opt.packets_path, &opt, &run, KMPGPU_ALERT_PATTERNS);

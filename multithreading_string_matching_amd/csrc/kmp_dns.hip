@@ -32,34 +32,21 @@
 #include "kmp_device.h"
 #include "kmp_launch.h"
 #include "kmp_piece_dev.h"
+#include "kmp_walk_dev.h"
 #include "kmp_compact_dev.h"
 
 namespace {
 
 using namespace kmp_unit;     /* kmp_compact_dev.h: group_tail, index_body, gather_runs; kmp_unit_dev.h: the unit */
 using kmp_piece::fetch_piece;
+using kmp_walk::unit_byte;      /* kmp_walk_dev.h: the held unit of a forward walk, shared with kmp_tls.hip */
+using kmp_walk::walk_byte;
+using kmp_walk::spread4;
 
 /* grid cap of the locate: rounds past 8 192 groups of 64 payloads, as the HTTP locate's */
 constexpr uint32_t DNS_LOCATE_BLOCKS = 2048;
 constexpr uint32_t DNS_NAME_MAX = 255u;          /* wire bytes of a name, its closing 0x00 included */
 constexpr uint32_t DOT4 = 0x2E2E2E2Eu;
-
-/* byte q (0 .. 15) of a unit: two selects and a shift, no register indexing */
-__device__ __forceinline__ uint32_t unit_byte(u32x4 v, uint32_t q)
-{
-    const uint32_t lo = (q & 4u) ? v.y : v.x, hi = (q & 4u) ? v.w : v.z;
-    return (((q & 8u) ? hi : lo) >> (8u * (q & 3u))) & 0xFFu;
-}
-
-/* the byte at `pos` of the payload at p; `held` is the aligned unit `hu` of it.  pos lies in front of the payload's end. */
-__device__ __forceinline__ uint32_t walk_byte(const uint8_t *p, uint32_t pos, u32x4 &held, uint32_t &hu)
-{
-    if ((pos >> 4) != hu) {
-        hu = pos >> 4;
-        held = load_unit<false>(p + 16ull * hu);
-    }
-    return unit_byte(held, pos & 15u);
-}
 
 /* B: the bytes in front of the message (0, or 2 under KMPGPU_DNS_TCP_PREFIX) */
 template <uint32_t B>
@@ -189,9 +176,6 @@ kmp_dns_index_kernel(const uint4 *__restrict__ spans, const uint64_t *__restrict
         return make_uint4((uint32_t)fs, (uint32_t)(fs >> 32), l, (uint32_t)k);
     });
 }
-
-/* 0xFF in every byte of a dword whose bit of the nibble is set */
-__device__ __forceinline__ uint32_t spread4(uint32_t nib) { return (((nib & 15u) * 0x00204081u) & 0x01010101u) * 0xFFu; }
 
 struct DnsRec { uint4 rec, m0, m1; };
 

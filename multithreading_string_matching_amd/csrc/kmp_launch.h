@@ -1,5 +1,5 @@
 /* kmp_launch.h -- launch entry points of kmp_scan_*.hip / kmp_prep.hip / kmp_fold.hip / kmp_marks.hip / kmp_rules.hip / kmp_relations.hip /
- * kmp_chains.hip / kmp_headers.hip / kmp_bytetests.hip / kmp_regex.hip / kmp_links.hip / kmp_select.hip / kmp_decode.hip / kmp_base64.hip / kmp_fields.hip / kmp_dns.hip / kmp_alerts.hip / kmp_flows.hip / kmp_seams.hip / kmp_streams.hip / kmp_streams_seq.hip / kmp_flowbits.hip / kmp_thresholds.hip, used
+ * kmp_chains.hip / kmp_headers.hip / kmp_bytetests.hip / kmp_regex.hip / kmp_links.hip / kmp_select.hip / kmp_decode.hip / kmp_base64.hip / kmp_fields.hip / kmp_dns.hip / kmp_tls.hip / kmp_alerts.hip / kmp_flows.hip / kmp_seams.hip / kmp_streams.hip / kmp_streams_seq.hip / kmp_flowbits.hip / kmp_thresholds.hip, used
  * by the C-ABI layer (kmpgpu.hip), which alone decides what is launched; the tables kmp_launch_scan_multi takes come from kmp_tables.h. */
 #ifndef KMP_LAUNCH_H
 #define KMP_LAUNCH_H
@@ -299,6 +299,19 @@ hipError_t kmp_launch_dns_index(const void *spans, const uint64_t *src_off, uint
                                 uint32_t *pkt_len, void *recs, hipStream_t st);
 hipError_t kmp_launch_dns_gather(const uint8_t *src_arena, const uint64_t *pkt_off, const void *recs, const void *masks, uint64_t n_dst,
                                  uint64_t total_bytes, uint8_t *arena, bool nontemporal, hipStream_t st);
+/* kmp_tls.hip (kmpgpu_tls_locate, kmpgpu_load_tls): the TLS ClientHello buffers (the definition: kmpgpu.h).  _tls_locate (1 kernel) writes
+ * spans[n] (kmpgpu_tls_span, 32 bytes each, 16-byte aligned) and masks[n] (32 bytes each: bit x set where byte x of payload k's ALPN field
+ * is a name's length byte, all zero for a payload without the field) and adds to stats[4] = {hellos, with a server name, with an ALPN
+ * field, truncated}, which the caller zeroes.  The rest as kmp_dns.hip's, with `field` KMPGPU_TLS_SNI or KMPGPU_TLS_ALPN; the gather reads
+ * the masks for KMPGPU_TLS_ALPN only. */
+hipError_t kmp_launch_tls_locate(const uint8_t *src_arena, const uint64_t *src_off, const uint32_t *src_len, uint64_t n, void *spans,
+                                 void *masks, unsigned long long *stats, hipStream_t st);
+hipError_t kmp_launch_tls_lengths(const void *spans, const uint32_t *src_len, uint64_t n, int field, bool only_present, uint8_t *ws,
+                                  unsigned long long *present, unsigned long long *stats, hipStream_t st);
+hipError_t kmp_launch_tls_index(const void *spans, const uint64_t *src_off, uint64_t n, int field, uint8_t *ws, uint64_t n_dst,
+                                uint64_t *pkt_off, uint32_t *pkt_len, void *recs, hipStream_t st);
+hipError_t kmp_launch_tls_gather(const uint8_t *src_arena, const uint64_t *pkt_off, const void *recs, const void *masks, int field,
+                                 uint64_t n_dst, uint64_t total_bytes, uint8_t *arena, bool nontemporal, hipStream_t st);
 /* kmp_alerts.hip (kmpgpu_scan_alerts): the set bits of rows[n_rows][stride] (stride even, 16-byte aligned, every word of a row readable,
  * the bits of index n_pkts and above not looked at; 16 * n_rows <= 0xFFFFFFFE) as 16-byte records {payload (64 bits), row, 0}, sorted by
  * payload, then row.  any[ceil(n_pkts / 64)]: the OR over the rows, complete before the count; a column word whose any word is 0 is not read.

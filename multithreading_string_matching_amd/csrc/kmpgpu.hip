@@ -255,6 +255,11 @@ struct kmpgpu_ctx {
     uint64_t            dns_stats[4] = {0, 0, 0, 0};
     bool                dns_valid = false;
     uint32_t            dns_prefix = 0;
+    /* kmpgpu_tls_locate: as the DNS spans, without a flag -- one kmpgpu_tls_span per payload, the ALPN separator masks, the four words */
+    uint4              *d_tls = nullptr;
+    uint64_t            tls_cap = 0;                  /* 16-byte units */
+    uint64_t            tls_stats[4] = {0, 0, 0, 0};
+    bool                tls_valid = false;
     int64_t             flow_slots = 0;               /* KMPGPU_OPT_FLOW_SLOTS */
     /* which build of the flows the context holds: kmpgpu_flows_build and drop_flows start a new generation, and id tells one context from
      * every other the process has made (a seam list names the context and the generation it was built from) */
@@ -550,8 +555,8 @@ void drop_flows(kmpgpu_ctx *c, bool rebuild = false)
     if (!rebuild) c->meta_gen++;                   /* the arena or its metadata change: the thresholds' address orders are none of the next one's */
 }
 
-/* the HTTP spans and the DNS spans go with the arena whose payloads they describe; their buffers are kept for the next locate */
-void drop_spans(kmpgpu_ctx *c) { c->spans_valid = c->dns_valid = false; }
+/* the HTTP, DNS and TLS spans go with the arena whose payloads they describe; their buffers are kept for the next locate */
+void drop_spans(kmpgpu_ctx *c) { c->spans_valid = c->dns_valid = c->tls_valid = false; }
 
 /* the seam list goes with the arena it describes; its buffers are kept for the next build */
 void drop_seams(kmpgpu_ctx *c)
@@ -681,7 +686,7 @@ void release_pass_buffers(kmpgpu_ctx *c)
     free_buffer(&c->d_flow_table, &c->flow_table_cap); free_buffer(&c->d_flow_first, &c->flow_first_cap); free_buffer(&c->d_flow_of, &c->flow_of_cap);
     free_buffer(&c->d_flow_recs, &c->flow_recs_cap); free_buffer(&c->d_flow_fold, &c->flow_fold_cap); free_buffer(&c->d_flow_sel, &c->flow_sel_cap);
     free_buffer(&c->d_dec_changed, &c->dec_changed_cap); free_buffer(&c->d_link_ws, &c->link_ws_cap);
-    free_buffer(&c->d_spans, &c->spans_cap); free_buffer(&c->d_dns, &c->dns_cap); drop_spans(c);
+    free_buffer(&c->d_spans, &c->spans_cap); free_buffer(&c->d_dns, &c->dns_cap); free_buffer(&c->d_tls, &c->tls_cap); drop_spans(c);
     drop_flows(c);
     free_buffer(&c->d_seams, &c->seams_cap); free_buffer(&c->d_seam_flow, &c->seam_flow_cap); free_buffer(&c->d_seam_sort, &c->seam_sort_cap);
     drop_seams(c);
@@ -1774,31 +1779,43 @@ int kmpgpu_load_base64(kmpgpu_ctx *dst, kmpgpu_ctx *src, uint32_t min_run, uint3
     return load_recoded(dst, src, how, changed_out, d_changed, stats);
 }
 
-/* Which spans a call means: the HTTP ones, or the DNS ones for a prefix flag (KMPGPU_DNS_TCP_PREFIX or 0). */
-struct SpanKind { bool dns; uint32_t prefix; };
-static bool spans_current(const kmpgpu_ctx *c, SpanKind sk) { return sk.dns ? c->dns_valid && c->dns_prefix == sk.prefix : c->spans_valid; }
+/* Which spans a call means: the HTTP ones, the DNS ones for a prefix flag (KMPGPU_DNS_TCP_PREFIX or 0), or the TLS ones. */
+enum SpanProto { SPANS_HTTP, SPANS_DNS, SPANS_TLS };
+struct SpanKind { SpanProto proto; uint32_t prefix; };
+/* ... and where the context keeps them.  masks: 32 bytes of separator mask per payload stand behind the records */
+struct SpanStore { uint4 **d; uint64_t *cap; uint64_t *stats; bool *valid; bool masks; };
+static SpanStore span_store(kmpgpu_ctx *c, SpanKind sk)
+{
+    if (sk.proto == SPANS_DNS) return SpanStore{&c->d_dns, &c->dns_cap, c->dns_stats, &c->dns_valid, true};
+    if (sk.proto == SPANS_TLS) return SpanStore{&c->d_tls, &c->tls_cap, c->tls_stats, &c->tls_valid, true};
+    return SpanStore{&c->d_spans, &c->spans_cap, c->http_stats, &c->spans_valid, false};
+}
+static bool spans_current(kmpgpu_ctx *c, SpanKind sk) { return *span_store(c, sk).valid && (sk.proto != SPANS_DNS || c->dns_prefix == sk.prefix); }
 
-/* The spans of src's arena, made on the stream of `on` (src itself, or the dst of kmpgpu_load_fields / kmpgpu_load_dns, which has waited
- * for src's stream) where they are stale; *launched: the kernel ran.  The caller synchronises the stream before it reads the stats. */
+/* The spans of src's arena, made on the stream of `on` (src itself, or the dst of kmpgpu_load_fields / kmpgpu_load_dns / kmpgpu_load_tls,
+ * which has waited for src's stream) where they are stale; *launched: the kernel ran.  The caller synchronises the stream before it reads
+ * the stats. */
 static int locate_spans(kmpgpu_ctx *src, kmpgpu_ctx *on, SpanKind sk, const char *who, bool *launched)
 {
     *launched = false;
     if (spans_current(src, sk)) return KMPGPU_OK;
     const uint64_t n = src->n_pkts;
-    uint64_t *h_stats = sk.dns ? src->dns_stats : src->http_stats;
-    memset(h_stats, 0, 4 * sizeof(uint64_t));
-    if (sk.dns) { src->dns_valid = false; src->dns_prefix = sk.prefix; }
-    if (n == 0) { (sk.dns ? src->dns_valid : src->spans_valid) = true; return KMPGPU_OK; }
-    /* 32 bytes per payload, for DNS the separator masks of 32 bytes per payload behind them, 4 words of totals */
-    const uint64_t units = sk.dns ? 4 * n : 2 * n;
-    const hipError_t e = sk.dns ? grow_buffer(&src->d_dns, &src->dns_cap, units + 2, EIGHTH) : grow_buffer(&src->d_spans, &src->spans_cap, units + 2, EIGHTH);
+    const SpanStore ss = span_store(src, sk);
+    memset(ss.stats, 0, 4 * sizeof(uint64_t));
+    *ss.valid = false;
+    if (sk.proto == SPANS_DNS) src->dns_prefix = sk.prefix;
+    if (n == 0) { *ss.valid = true; return KMPGPU_OK; }
+    /* 32 bytes per payload, for DNS and TLS the separator masks of 32 bytes per payload behind them, 4 words of totals */
+    const uint64_t units = ss.masks ? 4 * n : 2 * n;
+    const hipError_t e = grow_buffer(ss.d, ss.cap, units + 2, EIGHTH);
     if (e != hipSuccess) return alloc_fail(e, "%s: the spans (%llu payloads) could not be allocated", who, (unsigned long long)n);
-    uint4 *d = sk.dns ? src->d_dns : src->d_spans;
+    uint4 *d = *ss.d;
     unsigned long long *d_stats = reinterpret_cast<unsigned long long *>(d + units);
     HIP_TRY(hipMemsetAsync(d_stats, 0, 4 * sizeof(unsigned long long), on->stream));
     hipEvent_t e1;
     HIP_TRY(profile_launch(on, &e1));
-    if (sk.dns) HIP_TRY(kmp_launch_dns_locate(src->d_arena, src->d_off, src->d_len, n, sk.prefix != 0u, d, d + 2 * n, d_stats, on->stream));
+    if (sk.proto == SPANS_DNS) HIP_TRY(kmp_launch_dns_locate(src->d_arena, src->d_off, src->d_len, n, sk.prefix != 0u, d, d + 2 * n, d_stats, on->stream));
+    else if (sk.proto == SPANS_TLS) HIP_TRY(kmp_launch_tls_locate(src->d_arena, src->d_off, src->d_len, n, d, d + 2 * n, d_stats, on->stream));
     else HIP_TRY(kmp_launch_http_locate(src->d_arena, src->d_off, src->d_len, n, d, d_stats, on->stream));
     HIP_TRY(profile_launched(on, e1));
     HIP_TRY(hipMemcpyAsync(on->h_small + 8, d_stats, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, on->stream));         /* (pinned: no staging) */
@@ -1808,11 +1825,13 @@ static int locate_spans(kmpgpu_ctx *src, kmpgpu_ctx *on, SpanKind sk, const char
 /* ... and after that synchronisation */
 static void located_spans(kmpgpu_ctx *src, kmpgpu_ctx *on, SpanKind sk)
 {
-    memcpy(sk.dns ? src->dns_stats : src->http_stats, on->h_small + 8, 4 * sizeof(uint64_t));
-    (sk.dns ? src->dns_valid : src->spans_valid) = true;
+    const SpanStore ss = span_store(src, sk);
+    memcpy(ss.stats, on->h_small + 8, 4 * sizeof(uint64_t));
+    *ss.valid = true;
 }
 
-/* kmpgpu_http_locate and kmpgpu_dns_locate behind their own checks; the stats are then in c->http_stats / c->dns_stats */
+/* kmpgpu_http_locate, kmpgpu_dns_locate and kmpgpu_tls_locate behind their own checks; the stats are then in c->http_stats / c->dns_stats /
+ * c->tls_stats */
 static int locate_call(kmpgpu_ctx *c, SpanKind sk, const char *who)
 {
     if (c->fr_pending) return fail(KMPGPU_ESTATE, "%s: the context sits between kmpgpu_load_frames_begin and _finish", who);
@@ -1834,7 +1853,7 @@ static int locate_call(kmpgpu_ctx *c, SpanKind sk, const char *who)
     return KMPGPU_OK;
 }
 
-/* ... and the two _spans_read: records [first, first + n) of `spans`, 32 bytes each */
+/* ... and the three _spans_read: records [first, first + n) of `spans`, 32 bytes each */
 static int spans_read_call(kmpgpu_ctx *c, bool valid, const uint4 *spans, void *out, uint64_t first, uint64_t n, const char *who, const char *locate)
 {
     if (!valid) return fail(KMPGPU_ESTATE, "%s: no spans (no %s since the arena was set)", who, locate);
@@ -1854,7 +1873,7 @@ int kmpgpu_http_locate(kmpgpu_ctx *c, kmpgpu_http_stats *stats)
     const char *who = "kmpgpu_http_locate";
     if (stats) *stats = kmpgpu_http_stats{};
     if (!c) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
-    if (const int rc = locate_call(c, SpanKind{false, 0u}, who)) return rc;
+    if (const int rc = locate_call(c, SpanKind{SPANS_HTTP, 0u}, who)) return rc;
     if (stats) { stats->n_requests = c->http_stats[0]; stats->n_responses = c->http_stats[1]; stats->n_blank = c->http_stats[2]; stats->bytes_scanned = c->http_stats[3]; }
     return KMPGPU_OK;
 }
@@ -1873,7 +1892,7 @@ int kmpgpu_dns_locate(kmpgpu_ctx *c, uint32_t flags, kmpgpu_dns_stats *stats)
     if (stats) *stats = kmpgpu_dns_stats{};
     if (!c) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
     if (flags & ~KMPGPU_DNS_TCP_PREFIX) return fail(KMPGPU_EINVAL, "%s: unknown flag bits 0x%x", who, flags);
-    if (const int rc = locate_call(c, SpanKind{true, flags}, who)) return rc;
+    if (const int rc = locate_call(c, SpanKind{SPANS_DNS, flags}, who)) return rc;
     if (stats) { stats->n_queries = c->dns_stats[0]; stats->n_responses = c->dns_stats[1]; stats->n_root = c->dns_stats[2]; stats->name_bytes = c->dns_stats[3]; }
     return KMPGPU_OK;
 }
@@ -1886,7 +1905,26 @@ int kmpgpu_dns_spans_read(kmpgpu_ctx *c, kmpgpu_dns_span *out, uint64_t first, u
     return spans_read_call(c, c->dns_valid, c->d_dns, out, first, n, who, "kmpgpu_dns_locate");
 }
 
-/* What kmpgpu_load_fields and kmpgpu_load_dns hand to the span they share */
+int kmpgpu_tls_locate(kmpgpu_ctx *c, uint32_t flags, kmpgpu_tls_stats *stats)
+{
+    const char *who = "kmpgpu_tls_locate";
+    if (stats) *stats = kmpgpu_tls_stats{};
+    if (!c) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
+    if (flags) return fail(KMPGPU_EINVAL, "%s: unknown flag bits 0x%x", who, flags);
+    if (const int rc = locate_call(c, SpanKind{SPANS_TLS, 0u}, who)) return rc;
+    if (stats) { stats->n_hellos = c->tls_stats[0]; stats->n_sni = c->tls_stats[1]; stats->n_alpn = c->tls_stats[2]; stats->n_truncated = c->tls_stats[3]; }
+    return KMPGPU_OK;
+}
+
+int kmpgpu_tls_spans_read(kmpgpu_ctx *c, kmpgpu_tls_span *out, uint64_t first, uint64_t n)
+{
+    const char *who = "kmpgpu_tls_spans_read";
+    static_assert(sizeof(kmpgpu_tls_span) == 32, "kmpgpu_tls_span is two 16-byte units");
+    if (!c) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
+    return spans_read_call(c, c->tls_valid, c->d_tls, out, first, n, who, "kmpgpu_tls_locate");
+}
+
+/* What kmpgpu_load_fields, kmpgpu_load_dns and kmpgpu_load_tls hand to the span they share */
 struct FieldBuffer { const char *who; SpanKind sk; int field; bool only_present; };
 
 static int field_buffer_refused(const kmpgpu_ctx *dst, const kmpgpu_ctx *src, const char *who)
@@ -1897,12 +1935,12 @@ static int field_buffer_refused(const kmpgpu_ctx *dst, const kmpgpu_ctx *src, co
     return KMPGPU_OK;
 }
 
-/* The span both calls share: the locate where src's spans are stale, lengths, scan, index, gather, through the one arena-install path. */
+/* The span the three calls share: the locate where src's spans are stale, lengths, scan, index, gather, through the one arena-install path. */
 static int load_field_buffer(kmpgpu_ctx *dst, kmpgpu_ctx *src, const FieldBuffer &fb, uint64_t *present_out, const void **d_present,
                              kmpgpu_fields_stats *stats)
 {
     const char *who = fb.who;
-    const bool only_present = fb.only_present, dns = fb.sk.dns;
+    const bool only_present = fb.only_present, dns = fb.sk.proto == SPANS_DNS, tls = fb.sk.proto == SPANS_TLS;
     HIP_TRY(hipSetDevice(dst->device));
     HIP_TRY(hipStreamSynchronize(dst->stream));           /* the passes over the arena that is about to be replaced */
     HIP_TRY(hipStreamSynchronize(src->stream));           /* whatever src's stream still does with its arena */
@@ -1923,9 +1961,10 @@ static int load_field_buffer(kmpgpu_ctx *dst, kmpgpu_ctx *src, const FieldBuffer
     bool located = false;
     int rc = locate_spans(src, c, fb.sk, who, &located);  /* (one more launch, where the spans are stale) */
     if (rc) return rc;
-    const uint4 *spans = dns ? src->d_dns : src->d_spans;
+    const uint4 *spans = *span_store(src, fb.sk).d;
     HIP_TRY(profile_launch(c, &e1));
     if (dns) HIP_TRY(kmp_launch_dns_lengths(spans, src->d_len, n, only_present, c->fr_ws, c->d_dec_changed, d_stats, c->stream));
+    else if (tls) HIP_TRY(kmp_launch_tls_lengths(spans, src->d_len, n, fb.field, only_present, c->fr_ws, c->d_dec_changed, d_stats, c->stream));
     else HIP_TRY(kmp_launch_fields_lengths(spans, src->d_len, n, fb.field, only_present, c->fr_ws, c->d_dec_changed, d_stats, c->stream));
     HIP_TRY(profile_launched(c, e1));
     HIP_TRY(profile_launch(c, &e1));
@@ -1967,10 +2006,12 @@ static int load_field_buffer(kmpgpu_ctx *dst, kmpgpu_ctx *src, const FieldBuffer
     HIP_TRY(hipMemsetAsync(c->owned_arena + tot[0], 0, 64, c->stream));
     HIP_TRY(profile_launch(c, &e1));
     if (dns) HIP_TRY(kmp_launch_dns_index(spans, src->d_off, n, c->fr_ws, n_pkts, c->owned_off, c->owned_len, c->fr_src, c->stream));
+    else if (tls) HIP_TRY(kmp_launch_tls_index(spans, src->d_off, n, fb.field, c->fr_ws, n_pkts, c->owned_off, c->owned_len, c->fr_src, c->stream));
     else HIP_TRY(kmp_launch_fields_index(spans, src->d_off, n, fb.field, c->fr_ws, n_pkts, c->owned_off, c->owned_len, c->fr_src, c->stream));
     HIP_TRY(profile_launched(c, e1));
     HIP_TRY(profile_launch(c, &e1));
     if (dns) HIP_TRY(kmp_launch_dns_gather(src->d_arena, c->owned_off, c->fr_src, spans + 2 * n, n_pkts, tot[0], c->owned_arena, c->nontemporal != 0, c->stream));
+    else if (tls) HIP_TRY(kmp_launch_tls_gather(src->d_arena, c->owned_off, c->fr_src, spans + 2 * n, fb.field, n_pkts, tot[0], c->owned_arena, c->nontemporal != 0, c->stream));
     else HIP_TRY(kmp_launch_fields_gather(src->d_arena, c->owned_off, c->fr_src, n_pkts, tot[0], c->owned_arena, c->nontemporal != 0, c->stream));
     HIP_TRY(profile_launched(c, e1));
     HIP_TRY(hipEventRecord(c->ev[3], c->stream));
@@ -1981,7 +2022,7 @@ static int load_field_buffer(kmpgpu_ctx *dst, kmpgpu_ctx *src, const FieldBuffer
     }
     IndexFacts f;
     rc = validate_index(c, who, c->owned_off, c->owned_len, n_pkts, arena_bytes, &f);
-    /* kmp_fields_gather_kernel and kmp_dns_gather_kernel write every slot whole: payload, then 0x00 up to the slot's end */
+    /* kmp_fields_gather_kernel, kmp_dns_gather_kernel and kmp_tls_gather_kernel write every slot whole: payload, then 0x00 up to the slot's end */
     if (!rc) rc = install_arena(c, c->owned_arena, c->owned_off, c->owned_len, arena_bytes, n_pkts, f, /* wrote_padding = */ true);
     if (rc) { release_arena(c, true); return rc; }
     c->has_meta = src->has_meta;
@@ -1999,7 +2040,7 @@ int kmpgpu_load_fields(kmpgpu_ctx *dst, kmpgpu_ctx *src, int field, uint32_t fla
     if (field < KMPGPU_FIELD_METHOD || field > KMPGPU_FIELD_BODY) return fail(KMPGPU_EINVAL, "%s: field %d is none of KMPGPU_FIELD_*", who, field);
     if (flags & ~KMPGPU_FIELDS_ONLY_PRESENT) return fail(KMPGPU_EINVAL, "%s: unknown flag bits 0x%x", who, flags);
     if (const int rc = field_buffer_refused(dst, src, who)) return rc;
-    const FieldBuffer fb = {who, SpanKind{false, 0u}, field, (flags & KMPGPU_FIELDS_ONLY_PRESENT) != 0};
+    const FieldBuffer fb = {who, SpanKind{SPANS_HTTP, 0u}, field, (flags & KMPGPU_FIELDS_ONLY_PRESENT) != 0};
     return load_field_buffer(dst, src, fb, present_out, d_present, stats);
 }
 
@@ -2014,7 +2055,22 @@ int kmpgpu_load_dns(kmpgpu_ctx *dst, kmpgpu_ctx *src, int field, uint32_t flags,
     if (field != KMPGPU_DNS_QNAME) return fail(KMPGPU_EINVAL, "%s: field %d is not KMPGPU_DNS_QNAME", who, field);
     if (flags & ~(KMPGPU_DNS_ONLY_PRESENT | KMPGPU_DNS_TCP_PREFIX)) return fail(KMPGPU_EINVAL, "%s: unknown flag bits 0x%x", who, flags);
     if (const int rc = field_buffer_refused(dst, src, who)) return rc;
-    const FieldBuffer fb = {who, SpanKind{true, flags & KMPGPU_DNS_TCP_PREFIX}, field, (flags & KMPGPU_DNS_ONLY_PRESENT) != 0};
+    const FieldBuffer fb = {who, SpanKind{SPANS_DNS, flags & KMPGPU_DNS_TCP_PREFIX}, field, (flags & KMPGPU_DNS_ONLY_PRESENT) != 0};
+    return load_field_buffer(dst, src, fb, present_out, d_present, stats);
+}
+
+int kmpgpu_load_tls(kmpgpu_ctx *dst, kmpgpu_ctx *src, int field, uint32_t flags, uint64_t *present_out, const void **d_present,
+                    kmpgpu_fields_stats *stats)
+{
+    const char *who = "kmpgpu_load_tls";
+    if (d_present) *d_present = nullptr;
+    if (stats) *stats = kmpgpu_fields_stats{};
+    if (!dst || !src) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
+    if (dst == src) return fail(KMPGPU_EINVAL, "%s: dst and src are the same context (a context holds one arena)", who);
+    if (field != KMPGPU_TLS_SNI && field != KMPGPU_TLS_ALPN) return fail(KMPGPU_EINVAL, "%s: field %d is neither KMPGPU_TLS_SNI nor KMPGPU_TLS_ALPN", who, field);
+    if (flags & ~KMPGPU_TLS_ONLY_PRESENT) return fail(KMPGPU_EINVAL, "%s: unknown flag bits 0x%x", who, flags);
+    if (const int rc = field_buffer_refused(dst, src, who)) return rc;
+    const FieldBuffer fb = {who, SpanKind{SPANS_TLS, 0u}, field, (flags & KMPGPU_TLS_ONLY_PRESENT) != 0};
     return load_field_buffer(dst, src, fb, present_out, d_present, stats);
 }
 

@@ -55,6 +55,15 @@ DNS_SPAN_DTYPE = np.dtype([("kind", np.uint8), ("n_labels", np.uint8), ("flags",
                            ("qclass", np.uint16), ("qdcount", np.uint16), ("ancount", np.uint16), ("nscount", np.uint16),
                            ("arcount", np.uint16), ("reserved", np.uint16), ("name_off", np.uint32), ("name_len", np.uint32),
                            ("q_end", np.uint32)])
+TLS_SNI, TLS_ALPN = 1, 2                    # KMPGPU_TLS_SNI, KMPGPU_TLS_ALPN: the field of load_tls
+TLS_ONLY_PRESENT = 1                        # KMPGPU_TLS_ONLY_PRESENT: its flag
+TLS_NONE, TLS_CLIENT_HELLO = 0, 1           # kmpgpu_tls_span.kind
+TLS_HAS_SNI, TLS_HAS_ALPN, TLS_TRUNCATED, TLS_ALPN_SKIPPED = 1, 2, 4, 8     # kmpgpu_tls_span.flags
+TLS_FIELD_NAMES = {"sni": TLS_SNI, "alpn": TLS_ALPN}
+# kmpgpu_tls_span (include/kmpgpu.h)
+TLS_SPAN_DTYPE = np.dtype([("kind", np.uint8), ("flags", np.uint8), ("n_ext", np.uint8), ("sid_len", np.uint8), ("record_version", np.uint16),
+                           ("client_version", np.uint16), ("n_suites", np.uint16), ("n_alpn", np.uint16), ("hs_len", np.uint32),
+                           ("sni_off", np.uint32), ("sni_len", np.uint32), ("alpn_off", np.uint32), ("alpn_len", np.uint32)])
 SEAM_DTYPE = np.dtype([("prev", "<u8"), ("next", "<u8"), ("tail_len", "<u4"), ("head_len", "<u4")])      # kmpgpu_seam, 24 bytes
 STREAM_DEPTH_MAX = 1 << 30     # KMPGPU_STREAM_DEPTH_MAX
 STREAM_DTYPE = np.dtype([("first_packet", "<u8"), ("last_packet", "<u8"), ("n_packets", "<u8"), ("bytes", "<u8"), ("flow", "<u4"),
@@ -740,6 +749,47 @@ class GpuMatcher:
         stats = {f: int(getattr(st, f)) for f, _ in _lib.FieldsStats._fields_}
         if stats["n_present"] != int(present.sum()) or stats["n_payloads"] != index.size or self.arena_info()[0] != index.size:
             raise KmpGpuError(f"kmpgpu_load_dns reports {stats['n_payloads']} payloads and {stats['n_present']} present ones, the "
+                              f"bitmap holds {int(present.sum())} of {n_src}")
+        return {"present": present, "index": index, "stats": stats}
+
+    def tls_locate(self) -> dict:
+        """Locate the server name and the ALPN list of the TLS ClientHello in every payload of this matcher's arena (kmpgpu_tls_locate;
+        the definition: kmpgpu.h).  The spans stay on the device until the arena changes; with valid spans nothing is launched.
+        Returns the stats: {"n_hellos", "n_sni", "n_alpn", "n_truncated"}."""
+        st = _lib.TlsStats()
+        gpu_check(self._g.kmpgpu_tls_locate(self._ctx, 0, C.byref(st)), "kmpgpu_tls_locate")
+        return {f: int(getattr(st, f)) for f, _ in _lib.TlsStats._fields_}
+
+    def tls_spans(self) -> np.ndarray:
+        """The kmpgpu_tls_span records of the last tls_locate() / load_tls() over this matcher's arena, one per payload, as a
+        structured array (TLS_SPAN_DTYPE)."""
+        n, _ = self.arena_info()
+        out = np.zeros(max(n, 1), dtype=TLS_SPAN_DTYPE)
+        gpu_check(self._g.kmpgpu_tls_spans_read(self._ctx, out.ctypes.data, 0, n), "kmpgpu_tls_spans_read")
+        return out[:n]
+
+    def load_tls(self, src: "GpuMatcher", field: str = "sni", only_present: bool = False) -> dict:
+        """Make this matcher's arena the server name ("sni") or the ALPN list as ``h2,http/1.1`` ("alpn") of the ClientHello in every
+        payload of ``src`` (kmpgpu_load_tls; the definition: kmpgpu.h); patterns, rules, windows and options of this matcher stay.
+        only_present: this matcher holds only the payloads that have the field, compacted in ascending source order.  Returns what
+        load_fields returns: {"present": bool[n_src], "index": int64[n_dst], "stats": {...}}."""
+        if field not in TLS_FIELD_NAMES:
+            raise ValueError(f"field: {field!r} is none of {', '.join(TLS_FIELD_NAMES)}")
+        n_src, _ = src.arena_info()
+        W = (n_src + 63) // 64
+        words = np.zeros(max(W, 1), dtype=np.uint64)
+        st = _lib.FieldsStats()
+        gpu_check(self._g.kmpgpu_load_tls(self._ctx, src._ctx, TLS_FIELD_NAMES[field], TLS_ONLY_PRESENT if only_present else 0,
+                                          words.ctypes.data, None, C.byref(st)), "kmpgpu_load_tls")
+        self._keep = None
+        bits = np.unpackbits(words[:W].view(np.uint8), bitorder="little")
+        if bits[n_src:].any():
+            raise KmpGpuError(f"kmpgpu_load_tls set a bit at or above {n_src} in the present bitmap")
+        present = bits[:n_src].astype(bool)
+        index = np.flatnonzero(present).astype(np.int64) if only_present else np.arange(n_src, dtype=np.int64)
+        stats = {f: int(getattr(st, f)) for f, _ in _lib.FieldsStats._fields_}
+        if stats["n_present"] != int(present.sum()) or stats["n_payloads"] != index.size or self.arena_info()[0] != index.size:
+            raise KmpGpuError(f"kmpgpu_load_tls reports {stats['n_payloads']} payloads and {stats['n_present']} present ones, the "
                               f"bitmap holds {int(present.sum())} of {n_src}")
         return {"present": present, "index": index, "stats": stats}
 
