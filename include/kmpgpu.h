@@ -805,9 +805,9 @@ int  kmpgpu_alerts_read(kmpgpu_ctx *ctx, kmpgpu_alert *out, uint64_t first, uint
  * Ordering: synchronous.  Waits for dst's stream, as the loaders do, then for src's, as kmpgpu_counts_add does, and works on dst's
  * stream.  dst's owned buffers are reused when the result fits and grown as the loaders grow them otherwise (kmpgpu_reserve sizes
  * them); the workspace is the scratch dst keeps for kmpgpu_load_frames, so a ring of selections does not allocate per call.
- * Errors: dst == src (selection in place does not exist), a NULL context, select NULL with n_src > 0, contexts on different devices
- * (peer copies do not exist): KMPGPU_EINVAL; either context between kmpgpu_load_frames_begin and _finish: KMPGPU_ESTATE; after each
- * of these dst keeps the arena it had.  After an allocation failure (KMPGPU_ENOMEM / KMPGPU_EHIP) dst is without an arena and both
+ * Errors: dst == src (a context holds one arena), a NULL context, select NULL with n_src > 0, contexts on different devices (no
+ * selection across devices): KMPGPU_EINVAL; either context between kmpgpu_load_frames_begin and _finish: KMPGPU_ESTATE; after each of
+ * these dst keeps the arena it had.  After an allocation failure (KMPGPU_ENOMEM / KMPGPU_EHIP) dst is without an arena and both
  * contexts stay usable.
  * kmpgpu_last_timing(dst): h2d_ms / h2d_bytes of the bitmap upload (0 for a device bitmap), kernel_ms from the first selection kernel
  * to the copy's end, launches = the kernels in that span (masked lengths, two scan kernels, index, copy: 5; 3 when nothing is selected).
@@ -859,10 +859,10 @@ int  kmpgpu_load_selected(kmpgpu_ctx *dst, kmpgpu_ctx *src, const void *select /
  * are reused when the result fits and grown as the loaders grow them otherwise (an eighth of headroom; kmpgpu_reserve sizes them); the
  * workspace is the scratch dst keeps for kmpgpu_load_frames, and the bitmap's buffer is kept too, so a ring of calls does not allocate
  * per call.
- * Errors: dst == src (decoding in place does not exist), a NULL context, contexts on different devices, an unknown transform, an
- * unknown flag bit: KMPGPU_EINVAL; either context between kmpgpu_load_frames_begin and _finish: KMPGPU_ESTATE; after each of these dst
- * keeps the arena it had.  After an allocation failure (KMPGPU_ENOMEM / KMPGPU_EHIP) dst is without an arena and both contexts stay
- * usable.
+ * Errors: dst == src (a context holds one arena), a NULL context, contexts on different devices (no decoding across devices), an
+ * unknown transform, an unknown flag bit: KMPGPU_EINVAL; either context between kmpgpu_load_frames_begin and _finish: KMPGPU_ESTATE;
+ * after each of these dst keeps the arena it had.  After an allocation failure (KMPGPU_ENOMEM / KMPGPU_EHIP) dst is without an arena
+ * and both contexts stay usable.
  * kmpgpu_last_timing(dst): kernel_ms from the first decode kernel to the write's end, launches = the kernels in that span (decoded
  * lengths, two scan kernels, index, write: 5; 3 where dst ends up without a payload); the metadata's copy or kernel follows the span.
  * kmpgpu_profile_begin .. _end time the span in four pairs: lengths, scan, index, write.

@@ -871,6 +871,142 @@ hipError_t profile_launched(kmpgpu_ctx *c, hipEvent_t e1)
     c->prof_n++;
     return hipEventRecord(e1, c->stream);
 }
+/* ... and the two around one launch: profiled(c, [&] { return kmp_launch_...(...); }) */
+template <class Launch> hipError_t profiled(kmpgpu_ctx *c, Launch launch)
+{
+    hipEvent_t e1;
+    hipError_t e = profile_launch(c, &e1);
+    if (e == hipSuccess) e = launch();
+    return e == hipSuccess ? profile_launched(c, e1) : e;
+}
+
+/* Records [first, first + n) of a list of `total` on the device, `size` bytes each, to the host: what every _read call does behind its NULL
+ * check.  missing: what the call says while the list is not valid; what / have: "elements" or "records", "there are" or "kept". */
+int read_range(kmpgpu_ctx *c, const char *who, bool valid, const char *missing, void *out, const void *d_list, size_t size, uint64_t first,
+               uint64_t n, uint64_t total, const char *what = "elements", const char *have = "there are")
+{
+    if (!valid) return fail(KMPGPU_ESTATE, "%s: %s", who, missing);
+    if (first > total || n > total - first)
+        return fail(KMPGPU_EINVAL, "%s: %s [%llu, +%llu) leave the %llu %s", who, what, (unsigned long long)first, (unsigned long long)n,
+                    (unsigned long long)total, have);
+    if (n == 0) return KMPGPU_OK;
+    if (!out) return fail(KMPGPU_EINVAL, "%s: out is NULL", who);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(out, (const uint8_t *)d_list + first * size, (size_t)n * size, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return KMPGPU_OK;
+}
+
+/* ------------------------------------------------------------------------------------------------------------------------------------
+ * The derived-arena loaders (kmpgpu_load_selected, _decoded, _base64, _fields, _dns, _tls, _seams, _streams, _streams_ordered): dst's
+ * arena built out of src's on dst's stream.  Every one of them is these steps in this order, with its own launches between them
+ * (DESIGN.md §3.31.1):
+ *   pair_refused, the checks of its own arguments, pair_state_refused, the checks of src's state
+ *   derived_begin; with a src without payloads: release_arena and out
+ *   its scratch; ev[2]; its launches, each through profiled(); read_totals
+ *   release_arena (seams and streams: right behind derived_begin); with nothing to hold: derived_finish(record) and out
+ *   take_arena; its buffers; its index and write launches; ev[3]; install_owned; derived_finish; its state
+ * ------------------------------------------------------------------------------------------------------------------------------------ */
+
+/* The refusals in front of a call's checks of its own arguments ... */
+int pair_refused(const kmpgpu_ctx *dst, const kmpgpu_ctx *src, const char *who)
+{
+    if (!dst || !src) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
+    if (dst == src) return fail(KMPGPU_EINVAL, "%s: dst and src are the same context (a context holds one arena)", who);
+    return KMPGPU_OK;
+}
+/* ... and the ones behind them, in front of its checks of src's state.  what: what the call makes, for the message */
+int pair_state_refused(const kmpgpu_ctx *dst, const kmpgpu_ctx *src, const char *who, const char *what)
+{
+    if (dst->device != src->device)
+        return fail(KMPGPU_EINVAL, "%s: the contexts sit on devices %d and %d (no %s across devices)", who, dst->device, src->device, what);
+    if (dst->fr_pending || src->fr_pending)
+        return fail(KMPGPU_ESTATE, "%s: %s sits between kmpgpu_load_frames_begin and _finish", who, dst->fr_pending ? "dst" : "src");
+    return KMPGPU_OK;
+}
+
+int derived_begin(kmpgpu_ctx *dst, kmpgpu_ctx *src)
+{
+    HIP_TRY(hipSetDevice(dst->device));
+    HIP_TRY(hipStreamSynchronize(dst->stream));           /* the passes over the arena that is about to be replaced */
+    HIP_TRY(hipStreamSynchronize(src->stream));           /* whatever src's stream still does with its arena */
+    dst->last = kmpgpu_timing{};
+    return KMPGPU_OK;
+}
+
+/* What the scan left in fr_tot -- tot[0] the packed bytes, tot[1] the payloads -- through the pinned words (no staging), and with
+ * bitmap_words the changed / present bitmap in d_dec_changed: its four totals behind it to tot[2..6) and its words to bitmap_out (host,
+ * may be NULL).  One synchronisation of the stream. */
+int read_totals(kmpgpu_ctx *c, unsigned long long *tot, uint64_t bitmap_words = 0, void *bitmap_out = nullptr)
+{
+    HIP_TRY(hipMemcpyAsync(c->h_small, c->fr_tot, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    if (bitmap_words)
+        HIP_TRY(hipMemcpyAsync(c->h_small + 2, c->d_dec_changed + bitmap_words, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    if (bitmap_words && bitmap_out)
+        HIP_TRY(hipMemcpyAsync(bitmap_out, c->d_dec_changed, bitmap_words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    memcpy(tot, c->h_small, (bitmap_words ? 6 : 2) * sizeof *tot);
+    return KMPGPU_OK;
+}
+
+/* dst's own buffers for n slots that end at packed_bytes, and the 64 bytes of 0x00 behind them.  On failure dst is empty and usable. */
+int take_arena(kmpgpu_ctx *c, const char *who, uint64_t packed_bytes, uint64_t n, const char *what)
+{
+    const uint64_t arena_bytes = packed_bytes + 64;
+    const hipError_t e = ensure_owned_arena(c, arena_bytes, n, EIGHTH);
+    if (e != hipSuccess)
+        return alloc_fail(e, "%s: an arena of %llu bytes / %llu %s could not be allocated", who, (unsigned long long)(arena_bytes + arena_bytes / 8),
+                          (unsigned long long)(n + n / 8), what);
+    HIP_TRY(hipMemsetAsync(c->owned_arena + packed_bytes, 0, 64, c->stream));
+    return KMPGPU_OK;
+}
+
+/* The arena a loader has written into dst's own buffers becomes dst's; one that fails the check leaves dst empty.  Every write kernel of
+ * these loaders writes its slots whole: payload, then 0x00 up to the slot's end. */
+int install_owned(kmpgpu_ctx *c, const char *who, uint64_t packed_bytes, uint64_t n)
+{
+    IndexFacts f;
+    int rc = validate_index(c, who, c->owned_off, c->owned_len, n, packed_bytes + 64, &f);
+    if (!rc) rc = install_arena(c, c->owned_arena, c->owned_off, c->owned_len, packed_bytes + 64, n, f, /* wrote_padding = */ true);
+    if (rc) release_arena(c, true);
+    return rc;
+}
+
+/* kernel_ms from ev[2] to ev[3], and the launches between them.  record: ev[3] is not on the stream yet (a result without payloads: it is
+ * recorded and waited for here); otherwise the caller recorded it behind its last launch, and install_owned has waited for the stream. */
+int derived_finish(kmpgpu_ctx *c, uint32_t launches, bool record)
+{
+    if (record) {
+        HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+        HIP_TRY(hipEventSynchronize(c->ev[3]));
+    }
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
+    c->last.kernel_ms = ms; c->last.launches = launches;
+    return KMPGPU_OK;
+}
+
+/* The front seams and streams share, in two halves.  Its scratch: the sort sized, fr_ws of ws_bytes, fr_tot and the sort's buffer grown;
+ * nothing goes onto the stream, so a caller takes whatever else it needs and uploads only after that ... */
+int flow_sort_scratch(kmpgpu_ctx *c, const kmpgpu_ctx *src, const char *who, uint64_t ws_bytes)
+{
+    const uint64_t n = src->n_pkts, sort_bytes = kmp_seam_sort_bytes(n, src->n_flows);
+    if (!sort_bytes) return fail(KMPGPU_EHIP, "%s: the sort of %llu payloads could not be sized", who, (unsigned long long)n);
+    hipError_t e = grow_buffer(&c->fr_ws, &c->fr_ws_cap, ws_bytes, EIGHTH);
+    if (e == hipSuccess && !c->fr_tot) e = hipMalloc(&c->fr_tot, 2 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = grow_buffer(&c->d_seam_sort, &c->seam_sort_cap, sort_bytes, EIGHTH);
+    if (e != hipSuccess) return alloc_fail(e, "%s: the sort's buffers (%llu bytes) could not be allocated", who, (unsigned long long)sort_bytes);
+    return KMPGPU_OK;
+}
+/* ... and the work: ev[2], and src's payloads sorted by flow and direction in d_seam_sort. */
+int sort_by_flow(kmpgpu_ctx *c, const kmpgpu_ctx *src)
+{
+    const uint64_t n = src->n_pkts;
+    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+    HIP_TRY(profiled(c, [&] { return kmp_launch_seam_keys(src->d_meta, src->d_flow_of, src->d_flow_recs, n, c->d_seam_sort, c->stream); }));
+    HIP_TRY(profiled(c, [&] { return kmp_launch_seam_sort(n, src->n_flows, c->d_seam_sort, (size_t)c->seam_sort_cap, c->stream); }));
+    return KMPGPU_OK;
+}
 
 /* Enqueue one full pass: scan launches (patterns grouped by "shorter than 4 bytes") + reduce. */
 struct EmitTarget {
@@ -1035,10 +1171,9 @@ int enqueue_set(kmpgpu_ctx *c, const kmpgpu_ctx::PatternSet &s, const uint8_t *a
                 HIP_TRY(hipMemsetAsync(c->d_pool, 0, (size_t)(a.fused_blocks / a.fused_sides) * sizeof(uint32_t), c->stream));
                 f.fused_pool = c->d_pool;
             }
-            hipEvent_t e1;
-            HIP_TRY(profile_launch(c, &e1));
-            HIP_TRY(kmp_launch_scan_multi(f, g.d_tables, g.words, g.n_unique, g.cshift, g.bmask, g.n_ones, g.ones, g.d_uid_first, g.d_uid_ids, c->stream));
-            HIP_TRY(profile_launched(c, e1));
+            HIP_TRY(profiled(c, [&] {
+                return kmp_launch_scan_multi(f, g.d_tables, g.words, g.n_unique, g.cshift, g.bmask, g.n_ones, g.ones, g.d_uid_first, g.d_uid_ids, c->stream);
+            }));
             HIP_TRY(kmp_launch_reduce(c->d_partials, bx, g.d_ids, g.n_ids, d_out, c->stream, g.d_rows, accumulate));
             ++nl;
             max_u = std::max(max_u, g.n_unique);
@@ -1558,21 +1693,16 @@ int kmpgpu_attach_arena(kmpgpu_ctx *c, const void *d_arena, uint64_t arena_bytes
 
 int kmpgpu_load_selected(kmpgpu_ctx *dst, kmpgpu_ctx *src, const void *select, int select_on_device, uint64_t *n_selected)
 {
+    const char *who = "kmpgpu_load_selected";
     if (n_selected) *n_selected = 0;
-    if (!dst || !src) return fail(KMPGPU_EINVAL, "kmpgpu_load_selected: ctx is NULL");
-    if (dst == src) return fail(KMPGPU_EINVAL, "kmpgpu_load_selected: dst and src are the same context (selection in place does not exist)");
-    if (select_on_device != 0 && select_on_device != 1) return fail(KMPGPU_EINVAL, "kmpgpu_load_selected: select_on_device is %d, not 0 or 1", select_on_device);
-    if (dst->device != src->device)
-        return fail(KMPGPU_EINVAL, "kmpgpu_load_selected: the contexts sit on devices %d and %d (selection across devices does not exist)", dst->device, src->device);
-    if (dst->fr_pending || src->fr_pending) return fail(KMPGPU_ESTATE, "kmpgpu_load_selected: %s sits between kmpgpu_load_frames_begin and _finish", dst->fr_pending ? "dst" : "src");
+    if (const int rc = pair_refused(dst, src, who)) return rc;
+    if (select_on_device != 0 && select_on_device != 1) return fail(KMPGPU_EINVAL, "%s: select_on_device is %d, not 0 or 1", who, select_on_device);
+    if (const int rc = pair_state_refused(dst, src, who, "selection")) return rc;
     const uint64_t n = src->n_pkts;
-    if (n && !select) return fail(KMPGPU_EINVAL, "kmpgpu_load_selected: select is NULL");
-    if (n && select_on_device && ((uintptr_t)select & 7u)) return fail(KMPGPU_EINVAL, "kmpgpu_load_selected: the device bitmap is not 8-byte aligned");
-    HIP_TRY(hipSetDevice(dst->device));
-    HIP_TRY(hipStreamSynchronize(dst->stream));           /* the passes over the arena that is about to be replaced */
-    HIP_TRY(hipStreamSynchronize(src->stream));           /* whatever src's stream still does with its arena */
+    if (n && !select) return fail(KMPGPU_EINVAL, "%s: select is NULL", who);
+    if (n && select_on_device && ((uintptr_t)select & 7u)) return fail(KMPGPU_EINVAL, "%s: the device bitmap is not 8-byte aligned", who);
+    if (const int rc = derived_begin(dst, src)) return rc;
     kmpgpu_ctx *c = dst;
-    c->last = kmpgpu_timing{};
     if (n == 0) { release_arena(c, /* keep_buffers = */ true); return KMPGPU_OK; }
 
     /* the scratch of kmpgpu_load_frames: fr_off takes the uploaded bitmap, fr_ws the scan, fr_src the copy's records */
@@ -1589,194 +1719,38 @@ int kmpgpu_load_selected(kmpgpu_ctx *dst, kmpgpu_ctx *src, const void *select, i
     }
     HIP_TRY(hipEventRecord(c->ev[2], c->stream));
     HIP_TRY(kmp_launch_select_phase1(d_select, src->d_len, n, c->fr_ws, c->fr_tot, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->h_small, c->fr_tot, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));         /* (pinned: no staging) */
-    HIP_TRY(hipStreamSynchronize(c->stream));
     unsigned long long tot[2] = {0, 0};
-    memcpy(tot, c->h_small, sizeof tot);
+    if (const int rc = read_totals(c, tot)) return rc;
     if (!select_on_device) {
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
         c->last.h2d_ms = ms; c->last.h2d_bytes = words * sizeof(uint64_t);
     }
-    const uint64_t n_pkts = tot[1], arena_bytes = tot[0] + 64;
+    const uint64_t n_pkts = tot[1];
+    const uint32_t meta_launch = src->has_meta ? 1u : 0u;
     /* from here on dst's earlier arena is gone, whatever happens */
     release_arena(c, /* keep_buffers = */ true);
     if (n_pkts == 0) {
         if (src->has_meta) HIP_TRY(kmp_launch_meta_select(src->d_meta, n, c->fr_ws, c->d_meta, c->stream));       /* (finds no record to move) */
-        HIP_TRY(hipEventRecord(c->ev[3], c->stream));
-        HIP_TRY(hipEventSynchronize(c->ev[3]));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
-        c->last.kernel_ms = ms; c->last.launches = src->has_meta ? 4 : 3;
-        return KMPGPU_OK;
+        return derived_finish(c, 3 + meta_launch, /* record = */ true);
     }
-    hipError_t e = ensure_owned_arena(c, arena_bytes, n_pkts, EIGHTH);       /* (on failure dst is empty and usable) */
-    if (e != hipSuccess)
-        return alloc_fail(e, "kmpgpu_load_selected: an arena of %llu bytes / %llu payloads could not be allocated",
-                          (unsigned long long)(arena_bytes + arena_bytes / 8), (unsigned long long)(n_pkts + n_pkts / 8));
-    e = grow_buffer(&c->fr_src, &c->fr_src_cap, 2 * n_pkts, EIGHTH);      /* 16 bytes per selected payload */
-    if (e != hipSuccess) return alloc_fail(e, "kmpgpu_load_selected: the copy's records (%llu payloads) could not be allocated", (unsigned long long)n_pkts);
+    if (const int rc = take_arena(c, who, tot[0], n_pkts, "payloads")) return rc;
+    hipError_t e = grow_buffer(&c->fr_src, &c->fr_src_cap, 2 * n_pkts, EIGHTH);      /* 16 bytes per selected payload */
+    if (e != hipSuccess) return alloc_fail(e, "%s: the copy's records (%llu payloads) could not be allocated", who, (unsigned long long)n_pkts);
     if (src->has_meta) {
         e = grow_buffer(&c->d_meta, &c->meta_cap, n_pkts, EIGHTH);
-        if (e != hipSuccess) return alloc_fail(e, "kmpgpu_load_selected: the metadata (%llu payloads) could not be allocated", (unsigned long long)n_pkts);
+        if (e != hipSuccess) return alloc_fail(e, "%s: the metadata (%llu payloads) could not be allocated", who, (unsigned long long)n_pkts);
     }
-    HIP_TRY(hipMemsetAsync(c->owned_arena + tot[0], 0, 64, c->stream));
     HIP_TRY(kmp_launch_select_phase2(src->d_arena, src->d_off, n, c->fr_ws, n_pkts, tot[0], c->owned_arena, c->owned_off, c->owned_len, c->fr_src,
                                      c->nontemporal != 0, c->stream));
     /* src has metadata: the selected payloads' records go with them, in their new order */
     if (src->has_meta) HIP_TRY(kmp_launch_meta_select(src->d_meta, n, c->fr_ws, c->d_meta, c->stream));
     HIP_TRY(hipEventRecord(c->ev[3], c->stream));
-    IndexFacts f;
-    int rc = validate_index(c, "kmpgpu_load_selected", c->owned_off, c->owned_len, n_pkts, arena_bytes, &f);
-    /* kmp_select_copy_kernel writes every slot whole: payload, then 0x00 up to the slot's end */
-    if (!rc) rc = install_arena(c, c->owned_arena, c->owned_off, c->owned_len, arena_bytes, n_pkts, f, /* wrote_padding = */ true);
-    if (rc) { release_arena(c, true); return rc; }
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
-    c->last.kernel_ms = ms; c->last.launches = src->has_meta ? 6 : 5;
+    if (const int rc = install_owned(c, who, tot[0], n_pkts)) return rc;
+    if (const int rc = derived_finish(c, 5 + meta_launch, /* record = */ false)) return rc;
     c->has_meta = src->has_meta;
     if (n_selected) *n_selected = n_pkts;
     return KMPGPU_OK;
-}
-
-/* What kmpgpu_load_decoded and kmpgpu_load_base64 differ in: the lengths and the write kernel, and what those take. */
-struct Recoding {
-    const char *who;
-    bool base64;            /* kmp_base64.hip, else kmp_decode.hip */
-    bool plus;              /* KMPGPU_DECODE_PLUS */
-    uint32_t min_run;       /* base64 */
-    bool urlsafe;           /* KMPGPU_B64_URLSAFE */
-    bool only_changed;
-};
-
-/* The checks the two calls share, behind the ones on their own arguments. */
-static int recoding_refused(const kmpgpu_ctx *dst, const kmpgpu_ctx *src, const char *who)
-{
-    if (dst->device != src->device)
-        return fail(KMPGPU_EINVAL, "%s: the contexts sit on devices %d and %d (decoding across devices does not exist)", who, dst->device, src->device);
-    if (dst->fr_pending || src->fr_pending) return fail(KMPGPU_ESTATE, "%s: %s sits between kmpgpu_load_frames_begin and _finish", who, dst->fr_pending ? "dst" : "src");
-    return KMPGPU_OK;
-}
-
-/* The span both calls share: lengths, scan, index, write, through the one arena-install path. */
-static int load_recoded(kmpgpu_ctx *dst, kmpgpu_ctx *src, const Recoding &how, uint64_t *changed_out, const void **d_changed,
-                        kmpgpu_decode_stats *stats)
-{
-    const char *who = how.who;
-    const bool only_changed = how.only_changed;
-    HIP_TRY(hipSetDevice(dst->device));
-    HIP_TRY(hipStreamSynchronize(dst->stream));           /* the passes over the arena that is about to be replaced */
-    HIP_TRY(hipStreamSynchronize(src->stream));           /* whatever src's stream still does with its arena */
-    kmpgpu_ctx *c = dst;
-    c->last = kmpgpu_timing{};
-    const uint64_t n = src->n_pkts;
-    if (n == 0) { release_arena(c, /* keep_buffers = */ true); return KMPGPU_OK; }
-
-    /* the scratch of kmpgpu_load_frames (fr_ws the scan, fr_src the write's records) and the bitmap's own buffer */
-    const uint64_t words = (n + 63) / 64;
-    HIP_TRY(grow_buffer(&c->fr_ws, &c->fr_ws_cap, (uint64_t)kmp_extract_ws_bytes(n), EIGHTH));
-    if (!c->fr_tot) HIP_TRY(hipMalloc(&c->fr_tot, 2 * sizeof(unsigned long long)));
-    HIP_TRY(grow_buffer(&c->d_dec_changed, &c->dec_changed_cap, words + 4, EIGHTH));
-    unsigned long long *d_stats = c->d_dec_changed + words;
-    HIP_TRY(hipMemsetAsync(d_stats, 0, 4 * sizeof(unsigned long long), c->stream));
-    hipEvent_t e1;
-    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
-    HIP_TRY(profile_launch(c, &e1));
-    if (how.base64)
-        HIP_TRY(kmp_launch_base64_lengths(src->d_arena, src->d_off, src->d_len, n, how.min_run, how.urlsafe, only_changed, c->fr_ws, c->d_dec_changed,
-                                          d_stats, c->stream));
-    else
-        HIP_TRY(kmp_launch_decode_lengths(src->d_arena, src->d_off, src->d_len, n, how.plus, only_changed, c->fr_ws, c->d_dec_changed, d_stats, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_compact_scan(n, c->fr_ws, c->fr_tot, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    HIP_TRY(hipMemcpyAsync(c->h_small, c->fr_tot, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));         /* (pinned: no staging) */
-    HIP_TRY(hipMemcpyAsync(c->h_small + 2, d_stats, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    if (changed_out) HIP_TRY(hipMemcpyAsync(changed_out, c->d_dec_changed, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    unsigned long long tot[6] = {0, 0, 0, 0, 0, 0};       /* packed bytes, payloads; source bytes, changed payloads, decoded bytes */
-    memcpy(tot, c->h_small, sizeof tot);
-    const uint64_t n_pkts = tot[1], arena_bytes = tot[0] + 64;
-    auto done = [&](uint32_t launches) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
-        c->last.kernel_ms = ms; c->last.launches = launches;
-        if (d_changed) *d_changed = c->d_dec_changed;
-        if (stats) { stats->n_payloads = n_pkts; stats->n_changed = tot[3]; stats->bytes_in = tot[2]; stats->bytes_out = tot[4]; }
-        return (int)KMPGPU_OK;
-    };
-    /* from here on dst's earlier arena is gone, whatever happens */
-    release_arena(c, /* keep_buffers = */ true);
-    if (n_pkts == 0) {
-        HIP_TRY(hipEventRecord(c->ev[3], c->stream));
-        HIP_TRY(hipEventSynchronize(c->ev[3]));
-        return done(3);
-    }
-    hipError_t e = ensure_owned_arena(c, arena_bytes, n_pkts, EIGHTH);       /* (on failure dst is empty and usable) */
-    if (e != hipSuccess)
-        return alloc_fail(e, "%s: an arena of %llu bytes / %llu payloads could not be allocated", who,
-                          (unsigned long long)(arena_bytes + arena_bytes / 8), (unsigned long long)(n_pkts + n_pkts / 8));
-    e = grow_buffer(&c->fr_src, &c->fr_src_cap, 2 * n_pkts, EIGHTH);      /* 16 bytes per payload of dst */
-    if (e != hipSuccess) return alloc_fail(e, "%s: the write's records (%llu payloads) could not be allocated", who, (unsigned long long)n_pkts);
-    if (src->has_meta) {
-        e = grow_buffer(&c->d_meta, &c->meta_cap, n_pkts, EIGHTH);
-        if (e != hipSuccess) return alloc_fail(e, "%s: the metadata (%llu payloads) could not be allocated", who, (unsigned long long)n_pkts);
-    }
-    HIP_TRY(hipMemsetAsync(c->owned_arena + tot[0], 0, 64, c->stream));
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_decode_index(src->d_off, src->d_len, n, c->fr_ws, n_pkts, c->owned_off, c->owned_len, c->fr_src, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    HIP_TRY(profile_launch(c, &e1));
-    if (how.base64)
-        HIP_TRY(kmp_launch_base64_write(src->d_arena, c->owned_off, c->fr_src, n_pkts, tot[2], tot[0], how.min_run, how.urlsafe, c->owned_arena,
-                                        c->nontemporal != 0, c->stream));
-    else
-        HIP_TRY(kmp_launch_decode_write(src->d_arena, c->owned_off, c->fr_src, n_pkts, tot[2], tot[0], how.plus, c->owned_arena, c->nontemporal != 0, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
-    /* src has metadata: the records go with the payloads -- in their new order, or all of them as they are */
-    if (src->has_meta) {
-        if (only_changed) HIP_TRY(kmp_launch_meta_select(src->d_meta, n, c->fr_ws, c->d_meta, c->stream));
-        else HIP_TRY(hipMemcpyAsync(c->d_meta, src->d_meta, n * sizeof(uint4), hipMemcpyDeviceToDevice, c->stream));
-    }
-    IndexFacts f;
-    int rc = validate_index(c, who, c->owned_off, c->owned_len, n_pkts, arena_bytes, &f);
-    /* kmp_decode_write_kernel and kmp_base64_write_kernel write every slot whole: payload, then 0x00 up to the slot's end */
-    if (!rc) rc = install_arena(c, c->owned_arena, c->owned_off, c->owned_len, arena_bytes, n_pkts, f, /* wrote_padding = */ true);
-    if (rc) { release_arena(c, true); return rc; }
-    c->has_meta = src->has_meta;
-    return done(5);
-}
-
-int kmpgpu_load_decoded(kmpgpu_ctx *dst, kmpgpu_ctx *src, int transform, uint32_t flags, uint64_t *changed_out, const void **d_changed,
-                        kmpgpu_decode_stats *stats)
-{
-    const char *who = "kmpgpu_load_decoded";
-    if (d_changed) *d_changed = nullptr;
-    if (stats) *stats = kmpgpu_decode_stats{};
-    if (!dst || !src) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
-    if (dst == src) return fail(KMPGPU_EINVAL, "%s: dst and src are the same context (decoding in place does not exist)", who);
-    if (transform != KMPGPU_DECODE_PERCENT) return fail(KMPGPU_EINVAL, "%s: transform %d is not KMPGPU_DECODE_PERCENT", who, transform);
-    if (flags & ~(KMPGPU_DECODE_PLUS | KMPGPU_DECODE_ONLY_CHANGED)) return fail(KMPGPU_EINVAL, "%s: unknown flag bits 0x%x", who, flags);
-    if (const int rc = recoding_refused(dst, src, who)) return rc;
-    const Recoding how = {who, false, (flags & KMPGPU_DECODE_PLUS) != 0, 0u, false, (flags & KMPGPU_DECODE_ONLY_CHANGED) != 0};
-    return load_recoded(dst, src, how, changed_out, d_changed, stats);
-}
-
-int kmpgpu_load_base64(kmpgpu_ctx *dst, kmpgpu_ctx *src, uint32_t min_run, uint32_t flags, uint64_t *changed_out, const void **d_changed,
-                       kmpgpu_decode_stats *stats)
-{
-    const char *who = "kmpgpu_load_base64";
-    if (d_changed) *d_changed = nullptr;
-    if (stats) *stats = kmpgpu_decode_stats{};
-    if (!dst || !src) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
-    if (dst == src) return fail(KMPGPU_EINVAL, "%s: dst and src are the same context (decoding in place does not exist)", who);
-    if (min_run < 4u || min_run > 255u) return fail(KMPGPU_EINVAL, "%s: min_run %u is outside 4..255", who, min_run);
-    if (flags & ~(KMPGPU_B64_URLSAFE | KMPGPU_B64_ONLY_CHANGED)) return fail(KMPGPU_EINVAL, "%s: unknown flag bits 0x%x", who, flags);
-    if (const int rc = recoding_refused(dst, src, who)) return rc;
-    const Recoding how = {who, true, false, min_run, (flags & KMPGPU_B64_URLSAFE) != 0, (flags & KMPGPU_B64_ONLY_CHANGED) != 0};
-    return load_recoded(dst, src, how, changed_out, d_changed, stats);
 }
 
 /* Which spans a call means: the HTTP ones, the DNS ones for a prefix flag (KMPGPU_DNS_TCP_PREFIX or 0), or the TLS ones. */
@@ -1812,12 +1786,11 @@ static int locate_spans(kmpgpu_ctx *src, kmpgpu_ctx *on, SpanKind sk, const char
     uint4 *d = *ss.d;
     unsigned long long *d_stats = reinterpret_cast<unsigned long long *>(d + units);
     HIP_TRY(hipMemsetAsync(d_stats, 0, 4 * sizeof(unsigned long long), on->stream));
-    hipEvent_t e1;
-    HIP_TRY(profile_launch(on, &e1));
-    if (sk.proto == SPANS_DNS) HIP_TRY(kmp_launch_dns_locate(src->d_arena, src->d_off, src->d_len, n, sk.prefix != 0u, d, d + 2 * n, d_stats, on->stream));
-    else if (sk.proto == SPANS_TLS) HIP_TRY(kmp_launch_tls_locate(src->d_arena, src->d_off, src->d_len, n, d, d + 2 * n, d_stats, on->stream));
-    else HIP_TRY(kmp_launch_http_locate(src->d_arena, src->d_off, src->d_len, n, d, d_stats, on->stream));
-    HIP_TRY(profile_launched(on, e1));
+    HIP_TRY(profiled(on, [&] {
+        if (sk.proto == SPANS_DNS) return kmp_launch_dns_locate(src->d_arena, src->d_off, src->d_len, n, sk.prefix != 0u, d, d + 2 * n, d_stats, on->stream);
+        if (sk.proto == SPANS_TLS) return kmp_launch_tls_locate(src->d_arena, src->d_off, src->d_len, n, d, d + 2 * n, d_stats, on->stream);
+        return kmp_launch_http_locate(src->d_arena, src->d_off, src->d_len, n, d, d_stats, on->stream);
+    }));
     HIP_TRY(hipMemcpyAsync(on->h_small + 8, d_stats, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, on->stream));         /* (pinned: no staging) */
     *launched = true;
     return KMPGPU_OK;
@@ -1853,21 +1826,6 @@ static int locate_call(kmpgpu_ctx *c, SpanKind sk, const char *who)
     return KMPGPU_OK;
 }
 
-/* ... and the three _spans_read: records [first, first + n) of `spans`, 32 bytes each */
-static int spans_read_call(kmpgpu_ctx *c, bool valid, const uint4 *spans, void *out, uint64_t first, uint64_t n, const char *who, const char *locate)
-{
-    if (!valid) return fail(KMPGPU_ESTATE, "%s: no spans (no %s since the arena was set)", who, locate);
-    if (first > c->n_pkts || n > c->n_pkts - first)
-        return fail(KMPGPU_EINVAL, "%s: records [%llu, +%llu) leave the %llu there are", who, (unsigned long long)first, (unsigned long long)n,
-                    (unsigned long long)c->n_pkts);
-    if (n == 0) return KMPGPU_OK;
-    if (!out) return fail(KMPGPU_EINVAL, "%s: out is NULL", who);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpyAsync(out, spans + 2 * first, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return KMPGPU_OK;
-}
-
 int kmpgpu_http_locate(kmpgpu_ctx *c, kmpgpu_http_stats *stats)
 {
     const char *who = "kmpgpu_http_locate";
@@ -1883,7 +1841,7 @@ int kmpgpu_http_spans_read(kmpgpu_ctx *c, kmpgpu_http_span *out, uint64_t first,
     const char *who = "kmpgpu_http_spans_read";
     static_assert(sizeof(kmpgpu_http_span) == 32, "kmpgpu_http_span is two 16-byte units");
     if (!c) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
-    return spans_read_call(c, c->spans_valid, c->d_spans, out, first, n, who, "kmpgpu_http_locate");
+    return read_range(c, who, c->spans_valid, "no spans (no kmpgpu_http_locate since the arena was set)", out, c->d_spans, 32, first, n, c->n_pkts, "records");
 }
 
 int kmpgpu_dns_locate(kmpgpu_ctx *c, uint32_t flags, kmpgpu_dns_stats *stats)
@@ -1902,7 +1860,7 @@ int kmpgpu_dns_spans_read(kmpgpu_ctx *c, kmpgpu_dns_span *out, uint64_t first, u
     const char *who = "kmpgpu_dns_spans_read";
     static_assert(sizeof(kmpgpu_dns_span) == 32, "kmpgpu_dns_span is two 16-byte units");
     if (!c) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
-    return spans_read_call(c, c->dns_valid, c->d_dns, out, first, n, who, "kmpgpu_dns_locate");
+    return read_range(c, who, c->dns_valid, "no spans (no kmpgpu_dns_locate since the arena was set)", out, c->d_dns, 32, first, n, c->n_pkts, "records");
 }
 
 int kmpgpu_tls_locate(kmpgpu_ctx *c, uint32_t flags, kmpgpu_tls_stats *stats)
@@ -1921,112 +1879,157 @@ int kmpgpu_tls_spans_read(kmpgpu_ctx *c, kmpgpu_tls_span *out, uint64_t first, u
     const char *who = "kmpgpu_tls_spans_read";
     static_assert(sizeof(kmpgpu_tls_span) == 32, "kmpgpu_tls_span is two 16-byte units");
     if (!c) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
-    return spans_read_call(c, c->tls_valid, c->d_tls, out, first, n, who, "kmpgpu_tls_locate");
+    return read_range(c, who, c->tls_valid, "no spans (no kmpgpu_tls_locate since the arena was set)", out, c->d_tls, 32, first, n, c->n_pkts, "records");
 }
 
-/* What kmpgpu_load_fields, kmpgpu_load_dns and kmpgpu_load_tls hand to the span they share */
-struct FieldBuffer { const char *who; SpanKind sk; int field; bool only_present; };
+/* What the five compacting loaders differ in: which lengths, index and write kernels run and what those take, whether src's spans are
+ * located first, and whether dst holds only the payloads the bitmap marks (ONLY_CHANGED / ONLY_PRESENT). */
+enum CompactKind { COMPACT_DECODE, COMPACT_BASE64, COMPACT_FIELDS, COMPACT_DNS, COMPACT_TLS };       /* from COMPACT_FIELDS on: over src's spans */
+struct Compacting {
+    const char *who;
+    CompactKind kind;
+    bool only_marked;
+    bool plus, urlsafe;     /* KMPGPU_DECODE_PLUS; KMPGPU_B64_URLSAFE */
+    uint32_t min_run;       /* base64 */
+    int field;              /* fields, tls */
+    SpanKind sk;            /* fields, dns, tls: the spans the kernels read */
+};
 
-static int field_buffer_refused(const kmpgpu_ctx *dst, const kmpgpu_ctx *src, const char *who)
+/* The span the five calls share: the locate where the kernels read spans and src's are stale, lengths, scan, index, write.  st (zeroed by
+ * the caller): the payloads dst holds, the set bits of the bitmap, the source bytes and the written bytes of the payloads dst holds. */
+static int load_compacted(kmpgpu_ctx *dst, kmpgpu_ctx *src, const Compacting &how, uint64_t *bitmap_out, const void **d_bitmap, uint64_t st[4])
 {
-    if (dst->device != src->device)
-        return fail(KMPGPU_EINVAL, "%s: the contexts sit on devices %d and %d (field buffers across devices do not exist)", who, dst->device, src->device);
-    if (dst->fr_pending || src->fr_pending) return fail(KMPGPU_ESTATE, "%s: %s sits between kmpgpu_load_frames_begin and _finish", who, dst->fr_pending ? "dst" : "src");
-    return KMPGPU_OK;
-}
-
-/* The span the three calls share: the locate where src's spans are stale, lengths, scan, index, gather, through the one arena-install path. */
-static int load_field_buffer(kmpgpu_ctx *dst, kmpgpu_ctx *src, const FieldBuffer &fb, uint64_t *present_out, const void **d_present,
-                             kmpgpu_fields_stats *stats)
-{
-    const char *who = fb.who;
-    const bool only_present = fb.only_present, dns = fb.sk.proto == SPANS_DNS, tls = fb.sk.proto == SPANS_TLS;
-    HIP_TRY(hipSetDevice(dst->device));
-    HIP_TRY(hipStreamSynchronize(dst->stream));           /* the passes over the arena that is about to be replaced */
-    HIP_TRY(hipStreamSynchronize(src->stream));           /* whatever src's stream still does with its arena */
+    const char *who = how.who;
+    const bool spanned = how.kind >= COMPACT_FIELDS, only = how.only_marked;
+    if (const int rc = derived_begin(dst, src)) return rc;
     kmpgpu_ctx *c = dst;
-    c->last = kmpgpu_timing{};
     const uint64_t n = src->n_pkts;
     if (n == 0) { release_arena(c, /* keep_buffers = */ true); return KMPGPU_OK; }
 
-    /* the scratch of kmpgpu_load_frames (fr_ws the scan, fr_src the gather's records) and the bitmap's buffer of kmpgpu_load_decoded */
+    /* the scratch of kmpgpu_load_frames (fr_ws the scan, fr_src the write's records) and the bitmap's own buffer, its four totals behind it */
     const uint64_t words = (n + 63) / 64;
     HIP_TRY(grow_buffer(&c->fr_ws, &c->fr_ws_cap, (uint64_t)kmp_extract_ws_bytes(n), EIGHTH));
     if (!c->fr_tot) HIP_TRY(hipMalloc(&c->fr_tot, 2 * sizeof(unsigned long long)));
     HIP_TRY(grow_buffer(&c->d_dec_changed, &c->dec_changed_cap, words + 4, EIGHTH));
-    unsigned long long *d_stats = c->d_dec_changed + words;
+    unsigned long long *bits = c->d_dec_changed, *d_stats = bits + words;
     HIP_TRY(hipMemsetAsync(d_stats, 0, 4 * sizeof(unsigned long long), c->stream));
-    hipEvent_t e1;
     HIP_TRY(hipEventRecord(c->ev[2], c->stream));
     bool located = false;
-    int rc = locate_spans(src, c, fb.sk, who, &located);  /* (one more launch, where the spans are stale) */
-    if (rc) return rc;
-    const uint4 *spans = *span_store(src, fb.sk).d;
-    HIP_TRY(profile_launch(c, &e1));
-    if (dns) HIP_TRY(kmp_launch_dns_lengths(spans, src->d_len, n, only_present, c->fr_ws, c->d_dec_changed, d_stats, c->stream));
-    else if (tls) HIP_TRY(kmp_launch_tls_lengths(spans, src->d_len, n, fb.field, only_present, c->fr_ws, c->d_dec_changed, d_stats, c->stream));
-    else HIP_TRY(kmp_launch_fields_lengths(spans, src->d_len, n, fb.field, only_present, c->fr_ws, c->d_dec_changed, d_stats, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_compact_scan(n, c->fr_ws, c->fr_tot, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    HIP_TRY(hipMemcpyAsync(c->h_small, c->fr_tot, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));         /* (pinned: no staging) */
-    HIP_TRY(hipMemcpyAsync(c->h_small + 2, d_stats, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    if (present_out) HIP_TRY(hipMemcpyAsync(present_out, c->d_dec_changed, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (located) located_spans(src, c, fb.sk);
-    unsigned long long tot[6] = {0, 0, 0, 0, 0, 0};       /* packed bytes, payloads; source bytes, payloads with the field, field bytes */
-    memcpy(tot, c->h_small, sizeof tot);
-    const uint64_t n_pkts = tot[1], arena_bytes = tot[0] + 64;
-    auto done = [&](uint32_t launches) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
-        c->last.kernel_ms = ms; c->last.launches = launches + (located ? 1u : 0u);
-        if (d_present) *d_present = c->d_dec_changed;
-        if (stats) { stats->n_payloads = n_pkts; stats->n_present = tot[3]; stats->bytes_in = tot[2]; stats->bytes_out = tot[4]; }
+    if (spanned)
+        if (const int rc = locate_spans(src, c, how.sk, who, &located)) return rc;       /* (one more launch, where the spans are stale) */
+    const uint4 *spans = spanned ? *span_store(src, how.sk).d : nullptr;
+    const uint8_t *arena = src->d_arena;
+    const uint64_t *off = src->d_off;
+    const uint32_t *len = src->d_len;
+    const bool nt = c->nontemporal != 0;
+    HIP_TRY(profiled(c, [&] {
+        switch (how.kind) {
+        case COMPACT_DECODE: return kmp_launch_decode_lengths(arena, off, len, n, how.plus, only, c->fr_ws, bits, d_stats, c->stream);
+        case COMPACT_BASE64: return kmp_launch_base64_lengths(arena, off, len, n, how.min_run, how.urlsafe, only, c->fr_ws, bits, d_stats, c->stream);
+        case COMPACT_FIELDS: return kmp_launch_fields_lengths(spans, len, n, how.field, only, c->fr_ws, bits, d_stats, c->stream);
+        case COMPACT_DNS: return kmp_launch_dns_lengths(spans, len, n, only, c->fr_ws, bits, d_stats, c->stream);
+        default: return kmp_launch_tls_lengths(spans, len, n, how.field, only, c->fr_ws, bits, d_stats, c->stream);
+        }
+    }));
+    HIP_TRY(profiled(c, [&] { return kmp_launch_compact_scan(n, c->fr_ws, c->fr_tot, c->stream); }));
+    unsigned long long tot[6] = {0, 0, 0, 0, 0, 0};       /* packed bytes, payloads; source bytes, marked payloads, written bytes */
+    if (const int rc = read_totals(c, tot, words, bitmap_out)) return rc;
+    if (located) located_spans(src, c, how.sk);
+    const uint64_t n_pkts = tot[1];
+    auto done = [&](uint32_t launches, bool record) {
+        if (const int rc = derived_finish(c, launches + (located ? 1u : 0u), record)) return rc;
+        if (d_bitmap) *d_bitmap = bits;
+        st[0] = n_pkts; st[1] = tot[3]; st[2] = tot[2]; st[3] = tot[4];
         return (int)KMPGPU_OK;
     };
     /* from here on dst's earlier arena is gone, whatever happens */
     release_arena(c, /* keep_buffers = */ true);
-    if (n_pkts == 0) {
-        HIP_TRY(hipEventRecord(c->ev[3], c->stream));
-        HIP_TRY(hipEventSynchronize(c->ev[3]));
-        return done(3);
-    }
-    hipError_t e = ensure_owned_arena(c, arena_bytes, n_pkts, EIGHTH);       /* (on failure dst is empty and usable) */
-    if (e != hipSuccess)
-        return alloc_fail(e, "%s: an arena of %llu bytes / %llu payloads could not be allocated", who,
-                          (unsigned long long)(arena_bytes + arena_bytes / 8), (unsigned long long)(n_pkts + n_pkts / 8));
-    e = grow_buffer(&c->fr_src, &c->fr_src_cap, 2 * n_pkts, EIGHTH);      /* 16 bytes per payload of dst */
-    if (e != hipSuccess) return alloc_fail(e, "%s: the gather's records (%llu payloads) could not be allocated", who, (unsigned long long)n_pkts);
+    if (n_pkts == 0) return done(3, /* record = */ true);
+    if (const int rc = take_arena(c, who, tot[0], n_pkts, "payloads")) return rc;
+    hipError_t e = grow_buffer(&c->fr_src, &c->fr_src_cap, 2 * n_pkts, EIGHTH);      /* 16 bytes per payload of dst */
+    if (e != hipSuccess) return alloc_fail(e, "%s: the write's records (%llu payloads) could not be allocated", who, (unsigned long long)n_pkts);
     if (src->has_meta) {
         e = grow_buffer(&c->d_meta, &c->meta_cap, n_pkts, EIGHTH);
         if (e != hipSuccess) return alloc_fail(e, "%s: the metadata (%llu payloads) could not be allocated", who, (unsigned long long)n_pkts);
     }
-    HIP_TRY(hipMemsetAsync(c->owned_arena + tot[0], 0, 64, c->stream));
-    HIP_TRY(profile_launch(c, &e1));
-    if (dns) HIP_TRY(kmp_launch_dns_index(spans, src->d_off, n, c->fr_ws, n_pkts, c->owned_off, c->owned_len, c->fr_src, c->stream));
-    else if (tls) HIP_TRY(kmp_launch_tls_index(spans, src->d_off, n, fb.field, c->fr_ws, n_pkts, c->owned_off, c->owned_len, c->fr_src, c->stream));
-    else HIP_TRY(kmp_launch_fields_index(spans, src->d_off, n, fb.field, c->fr_ws, n_pkts, c->owned_off, c->owned_len, c->fr_src, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    HIP_TRY(profile_launch(c, &e1));
-    if (dns) HIP_TRY(kmp_launch_dns_gather(src->d_arena, c->owned_off, c->fr_src, spans + 2 * n, n_pkts, tot[0], c->owned_arena, c->nontemporal != 0, c->stream));
-    else if (tls) HIP_TRY(kmp_launch_tls_gather(src->d_arena, c->owned_off, c->fr_src, spans + 2 * n, fb.field, n_pkts, tot[0], c->owned_arena, c->nontemporal != 0, c->stream));
-    else HIP_TRY(kmp_launch_fields_gather(src->d_arena, c->owned_off, c->fr_src, n_pkts, tot[0], c->owned_arena, c->nontemporal != 0, c->stream));
-    HIP_TRY(profile_launched(c, e1));
+    uint64_t *o_off = c->owned_off;
+    uint32_t *o_len = c->owned_len;
+    HIP_TRY(profiled(c, [&] {
+        switch (how.kind) {
+        case COMPACT_FIELDS: return kmp_launch_fields_index(spans, off, n, how.field, c->fr_ws, n_pkts, o_off, o_len, c->fr_src, c->stream);
+        case COMPACT_DNS: return kmp_launch_dns_index(spans, off, n, c->fr_ws, n_pkts, o_off, o_len, c->fr_src, c->stream);
+        case COMPACT_TLS: return kmp_launch_tls_index(spans, off, n, how.field, c->fr_ws, n_pkts, o_off, o_len, c->fr_src, c->stream);
+        default: return kmp_launch_decode_index(off, len, n, c->fr_ws, n_pkts, o_off, o_len, c->fr_src, c->stream);
+        }
+    }));
+    HIP_TRY(profiled(c, [&] {
+        switch (how.kind) {
+        case COMPACT_DECODE: return kmp_launch_decode_write(arena, o_off, c->fr_src, n_pkts, tot[2], tot[0], how.plus, c->owned_arena, nt, c->stream);
+        case COMPACT_BASE64:
+            return kmp_launch_base64_write(arena, o_off, c->fr_src, n_pkts, tot[2], tot[0], how.min_run, how.urlsafe, c->owned_arena, nt, c->stream);
+        case COMPACT_FIELDS: return kmp_launch_fields_gather(arena, o_off, c->fr_src, n_pkts, tot[0], c->owned_arena, nt, c->stream);
+        case COMPACT_DNS: return kmp_launch_dns_gather(arena, o_off, c->fr_src, spans + 2 * n, n_pkts, tot[0], c->owned_arena, nt, c->stream);
+        default: return kmp_launch_tls_gather(arena, o_off, c->fr_src, spans + 2 * n, how.field, n_pkts, tot[0], c->owned_arena, nt, c->stream);
+        }
+    }));
     HIP_TRY(hipEventRecord(c->ev[3], c->stream));
     /* src has metadata: the records go with the payloads -- in their new order, or all of them as they are */
     if (src->has_meta) {
-        if (only_present) HIP_TRY(kmp_launch_meta_select(src->d_meta, n, c->fr_ws, c->d_meta, c->stream));
+        if (only) HIP_TRY(kmp_launch_meta_select(src->d_meta, n, c->fr_ws, c->d_meta, c->stream));
         else HIP_TRY(hipMemcpyAsync(c->d_meta, src->d_meta, n * sizeof(uint4), hipMemcpyDeviceToDevice, c->stream));
     }
-    IndexFacts f;
-    rc = validate_index(c, who, c->owned_off, c->owned_len, n_pkts, arena_bytes, &f);
-    /* kmp_fields_gather_kernel, kmp_dns_gather_kernel and kmp_tls_gather_kernel write every slot whole: payload, then 0x00 up to the slot's end */
-    if (!rc) rc = install_arena(c, c->owned_arena, c->owned_off, c->owned_len, arena_bytes, n_pkts, f, /* wrote_padding = */ true);
-    if (rc) { release_arena(c, true); return rc; }
+    if (const int rc = install_owned(c, who, tot[0], n_pkts)) return rc;
     c->has_meta = src->has_meta;
-    return done(5);
+    return done(5, /* record = */ false);
+}
+
+/* kmpgpu_load_decoded and kmpgpu_load_base64 behind the checks of their own arguments */
+static int recoded_call(kmpgpu_ctx *dst, kmpgpu_ctx *src, const Compacting &how, uint64_t *changed_out, const void **d_changed, kmpgpu_decode_stats *stats)
+{
+    if (const int rc = pair_state_refused(dst, src, how.who, "decoding")) return rc;
+    uint64_t st[4] = {0, 0, 0, 0};
+    const int rc = load_compacted(dst, src, how, changed_out, d_changed, st);
+    if (!rc && stats) { stats->n_payloads = st[0]; stats->n_changed = st[1]; stats->bytes_in = st[2]; stats->bytes_out = st[3]; }
+    return rc;
+}
+
+int kmpgpu_load_decoded(kmpgpu_ctx *dst, kmpgpu_ctx *src, int transform, uint32_t flags, uint64_t *changed_out, const void **d_changed,
+                        kmpgpu_decode_stats *stats)
+{
+    const char *who = "kmpgpu_load_decoded";
+    if (d_changed) *d_changed = nullptr;
+    if (stats) *stats = kmpgpu_decode_stats{};
+    if (const int rc = pair_refused(dst, src, who)) return rc;
+    if (transform != KMPGPU_DECODE_PERCENT) return fail(KMPGPU_EINVAL, "%s: transform %d is not KMPGPU_DECODE_PERCENT", who, transform);
+    if (flags & ~(KMPGPU_DECODE_PLUS | KMPGPU_DECODE_ONLY_CHANGED)) return fail(KMPGPU_EINVAL, "%s: unknown flag bits 0x%x", who, flags);
+    Compacting how = {who, COMPACT_DECODE, (flags & KMPGPU_DECODE_ONLY_CHANGED) != 0};
+    how.plus = (flags & KMPGPU_DECODE_PLUS) != 0;
+    return recoded_call(dst, src, how, changed_out, d_changed, stats);
+}
+
+int kmpgpu_load_base64(kmpgpu_ctx *dst, kmpgpu_ctx *src, uint32_t min_run, uint32_t flags, uint64_t *changed_out, const void **d_changed,
+                       kmpgpu_decode_stats *stats)
+{
+    const char *who = "kmpgpu_load_base64";
+    if (d_changed) *d_changed = nullptr;
+    if (stats) *stats = kmpgpu_decode_stats{};
+    if (const int rc = pair_refused(dst, src, who)) return rc;
+    if (min_run < 4u || min_run > 255u) return fail(KMPGPU_EINVAL, "%s: min_run %u is outside 4..255", who, min_run);
+    if (flags & ~(KMPGPU_B64_URLSAFE | KMPGPU_B64_ONLY_CHANGED)) return fail(KMPGPU_EINVAL, "%s: unknown flag bits 0x%x", who, flags);
+    Compacting how = {who, COMPACT_BASE64, (flags & KMPGPU_B64_ONLY_CHANGED) != 0};
+    how.urlsafe = (flags & KMPGPU_B64_URLSAFE) != 0; how.min_run = min_run;
+    return recoded_call(dst, src, how, changed_out, d_changed, stats);
+}
+
+/* kmpgpu_load_fields, kmpgpu_load_dns and kmpgpu_load_tls behind the checks of their own arguments */
+static int field_buffer_call(kmpgpu_ctx *dst, kmpgpu_ctx *src, const Compacting &how, uint64_t *present_out, const void **d_present,
+                             kmpgpu_fields_stats *stats)
+{
+    if (const int rc = pair_state_refused(dst, src, how.who, "field buffers")) return rc;
+    uint64_t st[4] = {0, 0, 0, 0};
+    const int rc = load_compacted(dst, src, how, present_out, d_present, st);
+    if (!rc && stats) { stats->n_payloads = st[0]; stats->n_present = st[1]; stats->bytes_in = st[2]; stats->bytes_out = st[3]; }
+    return rc;
 }
 
 int kmpgpu_load_fields(kmpgpu_ctx *dst, kmpgpu_ctx *src, int field, uint32_t flags, uint64_t *present_out, const void **d_present,
@@ -2035,13 +2038,12 @@ int kmpgpu_load_fields(kmpgpu_ctx *dst, kmpgpu_ctx *src, int field, uint32_t fla
     const char *who = "kmpgpu_load_fields";
     if (d_present) *d_present = nullptr;
     if (stats) *stats = kmpgpu_fields_stats{};
-    if (!dst || !src) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
-    if (dst == src) return fail(KMPGPU_EINVAL, "%s: dst and src are the same context (a context holds one arena)", who);
+    if (const int rc = pair_refused(dst, src, who)) return rc;
     if (field < KMPGPU_FIELD_METHOD || field > KMPGPU_FIELD_BODY) return fail(KMPGPU_EINVAL, "%s: field %d is none of KMPGPU_FIELD_*", who, field);
     if (flags & ~KMPGPU_FIELDS_ONLY_PRESENT) return fail(KMPGPU_EINVAL, "%s: unknown flag bits 0x%x", who, flags);
-    if (const int rc = field_buffer_refused(dst, src, who)) return rc;
-    const FieldBuffer fb = {who, SpanKind{SPANS_HTTP, 0u}, field, (flags & KMPGPU_FIELDS_ONLY_PRESENT) != 0};
-    return load_field_buffer(dst, src, fb, present_out, d_present, stats);
+    Compacting how = {who, COMPACT_FIELDS, (flags & KMPGPU_FIELDS_ONLY_PRESENT) != 0};
+    how.field = field; how.sk = SpanKind{SPANS_HTTP, 0u};
+    return field_buffer_call(dst, src, how, present_out, d_present, stats);
 }
 
 int kmpgpu_load_dns(kmpgpu_ctx *dst, kmpgpu_ctx *src, int field, uint32_t flags, uint64_t *present_out, const void **d_present,
@@ -2050,13 +2052,12 @@ int kmpgpu_load_dns(kmpgpu_ctx *dst, kmpgpu_ctx *src, int field, uint32_t flags,
     const char *who = "kmpgpu_load_dns";
     if (d_present) *d_present = nullptr;
     if (stats) *stats = kmpgpu_fields_stats{};
-    if (!dst || !src) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
-    if (dst == src) return fail(KMPGPU_EINVAL, "%s: dst and src are the same context (a context holds one arena)", who);
+    if (const int rc = pair_refused(dst, src, who)) return rc;
     if (field != KMPGPU_DNS_QNAME) return fail(KMPGPU_EINVAL, "%s: field %d is not KMPGPU_DNS_QNAME", who, field);
     if (flags & ~(KMPGPU_DNS_ONLY_PRESENT | KMPGPU_DNS_TCP_PREFIX)) return fail(KMPGPU_EINVAL, "%s: unknown flag bits 0x%x", who, flags);
-    if (const int rc = field_buffer_refused(dst, src, who)) return rc;
-    const FieldBuffer fb = {who, SpanKind{SPANS_DNS, flags & KMPGPU_DNS_TCP_PREFIX}, field, (flags & KMPGPU_DNS_ONLY_PRESENT) != 0};
-    return load_field_buffer(dst, src, fb, present_out, d_present, stats);
+    Compacting how = {who, COMPACT_DNS, (flags & KMPGPU_DNS_ONLY_PRESENT) != 0};
+    how.field = field; how.sk = SpanKind{SPANS_DNS, flags & KMPGPU_DNS_TCP_PREFIX};
+    return field_buffer_call(dst, src, how, present_out, d_present, stats);
 }
 
 int kmpgpu_load_tls(kmpgpu_ctx *dst, kmpgpu_ctx *src, int field, uint32_t flags, uint64_t *present_out, const void **d_present,
@@ -2065,32 +2066,25 @@ int kmpgpu_load_tls(kmpgpu_ctx *dst, kmpgpu_ctx *src, int field, uint32_t flags,
     const char *who = "kmpgpu_load_tls";
     if (d_present) *d_present = nullptr;
     if (stats) *stats = kmpgpu_fields_stats{};
-    if (!dst || !src) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
-    if (dst == src) return fail(KMPGPU_EINVAL, "%s: dst and src are the same context (a context holds one arena)", who);
+    if (const int rc = pair_refused(dst, src, who)) return rc;
     if (field != KMPGPU_TLS_SNI && field != KMPGPU_TLS_ALPN) return fail(KMPGPU_EINVAL, "%s: field %d is neither KMPGPU_TLS_SNI nor KMPGPU_TLS_ALPN", who, field);
     if (flags & ~KMPGPU_TLS_ONLY_PRESENT) return fail(KMPGPU_EINVAL, "%s: unknown flag bits 0x%x", who, flags);
-    if (const int rc = field_buffer_refused(dst, src, who)) return rc;
-    const FieldBuffer fb = {who, SpanKind{SPANS_TLS, 0u}, field, (flags & KMPGPU_TLS_ONLY_PRESENT) != 0};
-    return load_field_buffer(dst, src, fb, present_out, d_present, stats);
+    Compacting how = {who, COMPACT_TLS, (flags & KMPGPU_TLS_ONLY_PRESENT) != 0};
+    how.field = field; how.sk = SpanKind{SPANS_TLS, 0u};
+    return field_buffer_call(dst, src, how, present_out, d_present, stats);
 }
 
 int kmpgpu_load_seams(kmpgpu_ctx *dst, kmpgpu_ctx *src, uint32_t reach, uint64_t *n_seams)
 {
     const char *who = "kmpgpu_load_seams";
     if (n_seams) *n_seams = 0;
-    if (!dst || !src) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
-    if (dst == src) return fail(KMPGPU_EINVAL, "%s: dst and src are the same context (a context holds one arena)", who);
+    if (const int rc = pair_refused(dst, src, who)) return rc;
     if (reach < 1u || reach > KMPGPU_MAX_PATTERN_LEN - 1u)
         return fail(KMPGPU_EINVAL, "%s: reach %u is not in 1..%u", who, reach, KMPGPU_MAX_PATTERN_LEN - 1u);
-    if (dst->device != src->device)
-        return fail(KMPGPU_EINVAL, "%s: the contexts sit on devices %d and %d (seams across devices do not exist)", who, dst->device, src->device);
-    if (dst->fr_pending || src->fr_pending) return fail(KMPGPU_ESTATE, "%s: %s sits between kmpgpu_load_frames_begin and _finish", who, dst->fr_pending ? "dst" : "src");
+    if (const int rc = pair_state_refused(dst, src, who, "seams")) return rc;
     if (!src->flows_valid) return fail(KMPGPU_ESTATE, "%s: no flows (no kmpgpu_flows_build since the arena or its metadata were set)", who);
-    HIP_TRY(hipSetDevice(dst->device));
-    HIP_TRY(hipStreamSynchronize(dst->stream));           /* the passes over the arena that is about to be replaced */
-    HIP_TRY(hipStreamSynchronize(src->stream));           /* whatever src's stream still does with its arena */
+    if (const int rc = derived_begin(dst, src)) return rc;
     kmpgpu_ctx *c = dst;
-    c->last = kmpgpu_timing{};
     const uint64_t n = src->n_pkts;
     /* from here on dst's earlier arena is gone, whatever happens */
     release_arena(c, /* keep_buffers = */ true);
@@ -2102,62 +2096,32 @@ int kmpgpu_load_seams(kmpgpu_ctx *dst, kmpgpu_ctx *src, uint32_t reach, uint64_t
     if (n == 0) return listed(0);
 
     /* the scratch of kmpgpu_load_frames (fr_ws the scan, fr_src the gather's records) and the sort's own buffer */
-    const uint64_t sort_bytes = kmp_seam_sort_bytes(n, src->n_flows);
-    if (!sort_bytes) return fail(KMPGPU_EHIP, "%s: the sort of %llu payloads could not be sized", who, (unsigned long long)n);
-    hipError_t e = grow_buffer(&c->fr_ws, &c->fr_ws_cap, (uint64_t)kmp_extract_ws_bytes(n), EIGHTH);
-    if (e == hipSuccess && !c->fr_tot) e = hipMalloc(&c->fr_tot, 2 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = grow_buffer(&c->d_seam_sort, &c->seam_sort_cap, sort_bytes, EIGHTH);
-    if (e != hipSuccess) return alloc_fail(e, "%s: the sort's buffers (%llu bytes) could not be allocated", who, (unsigned long long)sort_bytes);
-    hipEvent_t e1;
-    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_seam_keys(src->d_meta, src->d_flow_of, src->d_flow_recs, n, c->d_seam_sort, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_seam_sort(n, src->n_flows, c->d_seam_sort, (size_t)c->seam_sort_cap, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_seam_phase1(src->d_len, n, reach, c->d_seam_sort, c->fr_ws, c->fr_tot, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    HIP_TRY(hipMemcpyAsync(c->h_small, c->fr_tot, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));         /* (pinned: no staging) */
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (const int rc = flow_sort_scratch(c, src, who, (uint64_t)kmp_extract_ws_bytes(n))) return rc;
+    if (const int rc = sort_by_flow(c, src)) return rc;
+    HIP_TRY(profiled(c, [&] { return kmp_launch_seam_phase1(src->d_len, n, reach, c->d_seam_sort, c->fr_ws, c->fr_tot, c->stream); }));
     unsigned long long tot[2] = {0, 0};
-    memcpy(tot, c->h_small, sizeof tot);
-    const uint64_t ns = tot[1], arena_bytes = tot[0] + 64;
+    if (const int rc = read_totals(c, tot)) return rc;
+    const uint64_t ns = tot[1];
     if (ns == 0) {
-        HIP_TRY(hipEventRecord(c->ev[3], c->stream));
-        HIP_TRY(hipEventSynchronize(c->ev[3]));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
-        c->last.kernel_ms = ms; c->last.launches = 5;
+        if (const int rc = derived_finish(c, 5, /* record = */ true)) return rc;
         return listed(0);
     }
-    e = ensure_owned_arena(c, arena_bytes, ns, EIGHTH);                      /* (on failure dst is empty and usable) */
-    if (e != hipSuccess)
-        return alloc_fail(e, "%s: an arena of %llu bytes / %llu seams could not be allocated", who, (unsigned long long)(arena_bytes + arena_bytes / 8),
-                          (unsigned long long)(ns + ns / 8));
-    e = grow_buffer(&c->fr_src, &c->fr_src_cap, 4 * ns, EIGHTH);             /* 32 bytes per seam */
+    if (const int rc = take_arena(c, who, tot[0], ns, "seams")) return rc;
+    hipError_t e = grow_buffer(&c->fr_src, &c->fr_src_cap, 4 * ns, EIGHTH);  /* 32 bytes per seam */
     if (e == hipSuccess) e = grow_buffer(&c->d_meta, &c->meta_cap, ns, EIGHTH);
     if (e == hipSuccess) e = grow_buffer(&c->d_seams, &c->seams_cap, ns, EIGHTH);
     if (e == hipSuccess) e = grow_buffer(&c->d_seam_flow, &c->seam_flow_cap, ns, EIGHTH);
     if (e != hipSuccess) return alloc_fail(e, "%s: the records of %llu seams could not be allocated", who, (unsigned long long)ns);
-    HIP_TRY(hipMemsetAsync(c->owned_arena + tot[0], 0, 64, c->stream));
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_seam_index(src->d_off, src->d_len, src->d_meta, src->d_flow_of, n, reach, c->fr_ws, c->owned_off, c->owned_len, c->d_seams,
-                                  c->d_seam_flow, c->d_meta, c->fr_src, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_seam_gather(src->d_arena, c->owned_off, c->fr_src, ns, tot[0], c->owned_arena, c->nontemporal != 0, c->stream));
-    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(profiled(c, [&] {
+        return kmp_launch_seam_index(src->d_off, src->d_len, src->d_meta, src->d_flow_of, n, reach, c->fr_ws, c->owned_off, c->owned_len, c->d_seams,
+                                     c->d_seam_flow, c->d_meta, c->fr_src, c->stream);
+    }));
+    HIP_TRY(profiled(c, [&] {
+        return kmp_launch_seam_gather(src->d_arena, c->owned_off, c->fr_src, ns, tot[0], c->owned_arena, c->nontemporal != 0, c->stream);
+    }));
     HIP_TRY(hipEventRecord(c->ev[3], c->stream));
-    IndexFacts f;
-    int rc = validate_index(c, who, c->owned_off, c->owned_len, ns, arena_bytes, &f);
-    /* kmp_seam_gather_kernel writes every slot whole: seam, then 0x00 up to the slot's end */
-    if (!rc) rc = install_arena(c, c->owned_arena, c->owned_off, c->owned_len, arena_bytes, ns, f, /* wrote_padding = */ true);
-    if (rc) { release_arena(c, true); return rc; }
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
-    c->last.kernel_ms = ms; c->last.launches = 7;
+    if (const int rc = install_owned(c, who, tot[0], ns)) return rc;
+    if (const int rc = derived_finish(c, 7, /* record = */ false)) return rc;
     c->has_meta = true;
     return listed(ns);
 }
@@ -2167,15 +2131,83 @@ int kmpgpu_seams_read(kmpgpu_ctx *c, kmpgpu_seam *out, uint64_t first, uint64_t 
     static_assert(sizeof(kmpgpu_seam) == 24, "kmpgpu_seam is the 24-byte record of kmpgpu.h");
     const char *who = "kmpgpu_seams_read";
     if (!c) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
-    if (!c->seams_valid) return fail(KMPGPU_ESTATE, "%s: no seams (no kmpgpu_load_seams since the arena was set)", who);
-    if (first > c->n_seams || n > c->n_seams - first)
-        return fail(KMPGPU_EINVAL, "%s: elements [%llu, +%llu) leave the %llu there are", who, (unsigned long long)first, (unsigned long long)n,
-                    (unsigned long long)c->n_seams);
-    if (n == 0) return KMPGPU_OK;
-    if (!out) return fail(KMPGPU_EINVAL, "%s: out is NULL", who);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpyAsync(out, c->d_seams + first, (size_t)n * sizeof(kmpgpu_seam), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    return read_range(c, who, c->seams_valid, "no seams (no kmpgpu_load_seams since the arena was set)", out, c->d_seams, sizeof(kmpgpu_seam), first, n,
+                      c->n_seams);
+}
+
+/* kmpgpu_load_streams and kmpgpu_load_streams_ordered behind their checks: the streams in capture order, or, ordered, with the second
+ * sort, its scans, and the records, index and gather that follow the sequence numbers. */
+static int load_streams_call(kmpgpu_ctx *dst, kmpgpu_ctx *src, const char *who, uint32_t depth, bool ordered, const uint32_t *seq, bool on_device,
+                             uint64_t *n_streams)
+{
+    if (const int rc = derived_begin(dst, src)) return rc;
+    kmpgpu_ctx *c = dst;
+    const uint64_t n = src->n_pkts;
+    /* from here on dst's earlier arena is gone, whatever happens */
+    release_arena(c, /* keep_buffers = */ true);
+    if (n == 0) { c->streams_valid = true; c->stream_order_valid = ordered; return KMPGPU_OK; }       /* (no stream, no map entry) */
+
+    /* the scratch of kmpgpu_load_frames (fr_ws the scans, fr_src the gather's pieces), the sort buffer of kmpgpu_load_seams, and for the
+     * sequence order the second sort's and its scans' workspace and the copy of a host seq: all of it sized and taken before the seq is
+     * uploaded, so that no return for a size or for memory leaves a copy out of the caller's seq under way */
+    const uint64_t seq_bytes = ordered ? kmp_stream_seq_ws_bytes(n, src->n_flows) : 0;
+    if (ordered && !seq_bytes) return fail(KMPGPU_EHIP, "%s: the second sort of %llu payloads could not be sized", who, (unsigned long long)n);
+    if (const int rc = flow_sort_scratch(c, src, who, (uint64_t)kmp_stream_ws_bytes(n))) return rc;
+    hipError_t e = grow_buffer(&c->fr_src, &c->fr_src_cap, 3 * n, EIGHTH);                         /* 24 bytes per source payload */
+    if (e == hipSuccess) e = grow_buffer(&c->d_stream_map, &c->stream_map_cap, n, EIGHTH);
+    if (e == hipSuccess && ordered) e = grow_buffer(&c->d_stream_seq_ws, &c->stream_seq_ws_cap, seq_bytes, EIGHTH);
+    if (e == hipSuccess && ordered) e = grow_buffer(&c->d_stream_segs, &c->stream_segs_cap, n, EIGHTH);
+    if (e == hipSuccess && ordered && !on_device) e = grow_buffer(&c->d_stream_seq, &c->stream_seq_cap, n, EIGHTH);
+    if (e != hipSuccess) return alloc_fail(e, "%s: the scans' buffers (%llu payloads) could not be allocated", who, (unsigned long long)n);
+    const uint32_t *d_seq = seq;
+    if (ordered && !on_device) {
+        HIP_TRY(upload_split(c->d_stream_seq, reinterpret_cast<const uint8_t *>(seq), n * sizeof(uint32_t), c->stream));
+        d_seq = c->d_stream_seq;
+    }
+    if (const int rc = sort_by_flow(c, src)) return rc;
+    HIP_TRY(profiled(c, [&] { return kmp_launch_stream_phase1(src->d_len, n, c->d_seam_sort, c->fr_ws, c->fr_tot, c->stream); }));
+    unsigned long long tot[2] = {0, 0};
+    if (const int rc = read_totals(c, tot)) return rc;
+    const uint64_t total = tot[0], ns = tot[1];                              /* bytes of all members; streams, at least one */
+    e = grow_buffer(&c->d_streams, &c->streams_cap, ns, EIGHTH);
+    if (e == hipSuccess && ordered) e = grow_buffer(&c->d_stream_orders, &c->stream_orders_cap, ns, EIGHTH);
+    if (e == hipSuccess) e = grow_buffer(&c->d_meta, &c->meta_cap, ns, EIGHTH);
+    if (e != hipSuccess) return alloc_fail(e, "%s: the records of %llu streams could not be allocated", who, (unsigned long long)ns);
+    if (ordered) {
+        HIP_TRY(profiled(c, [&] {
+            return kmp_launch_stream_seq_order(src->d_meta, d_seq, n, ns, src->n_flows, c->d_seam_sort, c->fr_ws, c->d_stream_seq_ws,
+                                               (size_t)c->stream_seq_ws_cap, c->stream);
+        }));
+        HIP_TRY(profiled(c, [&] { return kmp_launch_stream_seq_scans(src->d_len, n, c->d_seam_sort, c->fr_ws, c->d_stream_seq_ws, c->stream); }));
+        HIP_TRY(profiled(c, [&] {
+            return kmp_launch_stream_seq_records(src->d_meta, d_seq, n, total, ns, depth, c->d_seam_sort, c->fr_ws, c->d_stream_seq_ws, c->d_streams,
+                                                 c->d_stream_orders, c->d_meta, c->fr_tot, c->stream);
+        }));
+    } else {
+        HIP_TRY(profiled(c, [&] {
+            return kmp_launch_stream_records(src->d_meta, n, total, ns, depth, c->d_seam_sort, c->fr_ws, c->d_streams, c->d_meta, c->fr_tot, c->stream);
+        }));
+    }
+    /* the second read: the arena's size follows from the cut lengths, which follow from the first read's n_streams */
+    if (const int rc = read_totals(c, tot)) return rc;
+    if (const int rc = take_arena(c, who, tot[0], ns, "streams")) return rc;
+    HIP_TRY(profiled(c, [&] {
+        if (ordered)
+            return kmp_launch_stream_seq_index(src->d_off, src->d_len, n, ns, c->d_seam_sort, c->fr_ws, c->d_stream_seq_ws, c->owned_off, c->owned_len,
+                                               c->d_stream_map, c->d_stream_segs, c->fr_src, c->stream);
+        return kmp_launch_stream_index(src->d_off, src->d_len, n, total, ns, c->d_seam_sort, c->fr_ws, c->owned_off, c->owned_len, c->d_stream_map,
+                                       c->fr_src, c->stream);
+    }));
+    HIP_TRY(profiled(c, [&] {
+        if (ordered) return kmp_launch_stream_seq_gather(src->d_arena, c->fr_src, n, tot[0], c->owned_arena, c->nontemporal != 0, c->stream);
+        return kmp_launch_stream_gather(src->d_arena, c->fr_src, n, tot[0], c->owned_arena, c->nontemporal != 0, c->stream);
+    }));
+    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    if (const int rc = install_owned(c, who, tot[0], ns)) return rc;
+    if (const int rc = derived_finish(c, ordered ? 16 : 10, /* record = */ false)) return rc;
+    c->has_meta = true;
+    c->n_streams = ns; c->n_stream_map = n; c->streams_valid = true; c->stream_order_valid = ordered;
+    if (n_streams) *n_streams = ns;
     return KMPGPU_OK;
 }
 
@@ -2183,242 +2215,70 @@ int kmpgpu_load_streams(kmpgpu_ctx *dst, kmpgpu_ctx *src, uint32_t depth, uint64
 {
     const char *who = "kmpgpu_load_streams";
     if (n_streams) *n_streams = 0;
-    if (!dst || !src) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
-    if (dst == src) return fail(KMPGPU_EINVAL, "%s: dst and src are the same context (a context holds one arena)", who);
+    if (const int rc = pair_refused(dst, src, who)) return rc;
     if (depth < 1u || depth > KMPGPU_STREAM_DEPTH_MAX)
         return fail(KMPGPU_EINVAL, "%s: depth %u is not in 1..%u", who, depth, KMPGPU_STREAM_DEPTH_MAX);
-    if (dst->device != src->device)
-        return fail(KMPGPU_EINVAL, "%s: the contexts sit on devices %d and %d (streams across devices do not exist)", who, dst->device, src->device);
-    if (dst->fr_pending || src->fr_pending) return fail(KMPGPU_ESTATE, "%s: %s sits between kmpgpu_load_frames_begin and _finish", who, dst->fr_pending ? "dst" : "src");
+    if (const int rc = pair_state_refused(dst, src, who, "streams")) return rc;
     if (!src->flows_valid) return fail(KMPGPU_ESTATE, "%s: no flows (no kmpgpu_flows_build since the arena or its metadata were set)", who);
-    HIP_TRY(hipSetDevice(dst->device));
-    HIP_TRY(hipStreamSynchronize(dst->stream));           /* the passes over the arena that is about to be replaced */
-    HIP_TRY(hipStreamSynchronize(src->stream));           /* whatever src's stream still does with its arena */
-    kmpgpu_ctx *c = dst;
-    c->last = kmpgpu_timing{};
-    const uint64_t n = src->n_pkts;
-    /* from here on dst's earlier arena is gone, whatever happens */
-    release_arena(c, /* keep_buffers = */ true);
-    if (n == 0) { c->streams_valid = true; return KMPGPU_OK; }       /* (no stream, no map entry) */
-
-    /* the scratch of kmpgpu_load_frames (fr_ws the scans, fr_src the gather's pieces) and the sort buffer of kmpgpu_load_seams */
-    const uint64_t sort_bytes = kmp_seam_sort_bytes(n, src->n_flows);
-    if (!sort_bytes) return fail(KMPGPU_EHIP, "%s: the sort of %llu payloads could not be sized", who, (unsigned long long)n);
-    hipError_t e = grow_buffer(&c->fr_ws, &c->fr_ws_cap, (uint64_t)kmp_stream_ws_bytes(n), EIGHTH);
-    if (e == hipSuccess && !c->fr_tot) e = hipMalloc(&c->fr_tot, 2 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = grow_buffer(&c->d_seam_sort, &c->seam_sort_cap, sort_bytes, EIGHTH);
-    if (e == hipSuccess) e = grow_buffer(&c->fr_src, &c->fr_src_cap, 3 * n, EIGHTH);              /* 24 bytes per source payload */
-    if (e == hipSuccess) e = grow_buffer(&c->d_stream_map, &c->stream_map_cap, n, EIGHTH);
-    if (e != hipSuccess) return alloc_fail(e, "%s: the sort's and the scans' buffers (%llu payloads) could not be allocated", who, (unsigned long long)n);
-    hipEvent_t e1;
-    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_seam_keys(src->d_meta, src->d_flow_of, src->d_flow_recs, n, c->d_seam_sort, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_seam_sort(n, src->n_flows, c->d_seam_sort, (size_t)c->seam_sort_cap, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_stream_phase1(src->d_len, n, c->d_seam_sort, c->fr_ws, c->fr_tot, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    HIP_TRY(hipMemcpyAsync(c->h_small, c->fr_tot, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));         /* (pinned: no staging) */
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    unsigned long long tot[2] = {0, 0};
-    memcpy(tot, c->h_small, sizeof tot);
-    const uint64_t total = tot[0], ns = tot[1];                              /* bytes of all members; streams, at least one */
-    e = grow_buffer(&c->d_streams, &c->streams_cap, ns, EIGHTH);
-    if (e == hipSuccess) e = grow_buffer(&c->d_meta, &c->meta_cap, ns, EIGHTH);
-    if (e != hipSuccess) return alloc_fail(e, "%s: the records of %llu streams could not be allocated", who, (unsigned long long)ns);
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_stream_records(src->d_meta, n, total, ns, depth, c->d_seam_sort, c->fr_ws, c->d_streams, c->d_meta, c->fr_tot, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    /* the second read: the arena's size follows from the cut lengths, which follow from the first read's n_streams */
-    HIP_TRY(hipMemcpyAsync(c->h_small, c->fr_tot, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    memcpy(tot, c->h_small, sizeof tot);
-    const uint64_t arena_bytes = tot[0] + 64;
-    e = ensure_owned_arena(c, arena_bytes, ns, EIGHTH);                      /* (on failure dst is empty and usable) */
-    if (e != hipSuccess)
-        return alloc_fail(e, "%s: an arena of %llu bytes / %llu streams could not be allocated", who, (unsigned long long)(arena_bytes + arena_bytes / 8),
-                          (unsigned long long)(ns + ns / 8));
-    HIP_TRY(hipMemsetAsync(c->owned_arena + tot[0], 0, 64, c->stream));
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_stream_index(src->d_off, src->d_len, n, total, ns, c->d_seam_sort, c->fr_ws, c->owned_off, c->owned_len, c->d_stream_map,
-                                    c->fr_src, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_stream_gather(src->d_arena, c->fr_src, n, tot[0], c->owned_arena, c->nontemporal != 0, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
-    IndexFacts f;
-    int rc = validate_index(c, who, c->owned_off, c->owned_len, ns, arena_bytes, &f);
-    /* kmp_stream_gather_kernel writes every slot whole: stream, then 0x00 up to the slot's end */
-    if (!rc) rc = install_arena(c, c->owned_arena, c->owned_off, c->owned_len, arena_bytes, ns, f, /* wrote_padding = */ true);
-    if (rc) { release_arena(c, true); return rc; }
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
-    c->last.kernel_ms = ms; c->last.launches = 10;
-    c->has_meta = true;
-    c->n_streams = ns; c->n_stream_map = n; c->streams_valid = true;
-    if (n_streams) *n_streams = ns;
-    return KMPGPU_OK;
+    return load_streams_call(dst, src, who, depth, /* ordered = */ false, nullptr, false, n_streams);
 }
 
-namespace {
-
-/* what kmpgpu_streams_read and kmpgpu_stream_map_read share: flows_read_range for the stream state */
-int streams_read_range(kmpgpu_ctx *c, const char *who, void *out, const void *src, size_t size, uint64_t first, uint64_t n, uint64_t total)
+/* what the four reads of the stream state share */
+static int streams_read_range(kmpgpu_ctx *c, const char *who, void *out, const void *list, size_t size, uint64_t first, uint64_t n, uint64_t total)
 {
-    if (!c) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
-    if (!c->streams_valid) return fail(KMPGPU_ESTATE, "%s: no streams (no kmpgpu_load_streams since the arena was set)", who);
-    if (first > total || n > total - first)
-        return fail(KMPGPU_EINVAL, "%s: elements [%llu, +%llu) leave the %llu there are", who, (unsigned long long)first, (unsigned long long)n,
-                    (unsigned long long)total);
-    if (n == 0) return KMPGPU_OK;
-    if (!out) return fail(KMPGPU_EINVAL, "%s: out is NULL", who);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpyAsync(out, (const uint8_t *)src + first * size, (size_t)n * size, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return KMPGPU_OK;
+    return read_range(c, who, c->streams_valid, "no streams (no kmpgpu_load_streams since the arena was set)", out, list, size, first, n, total);
 }
-
-}  // namespace
 
 int kmpgpu_streams_read(kmpgpu_ctx *c, kmpgpu_stream *out, uint64_t first, uint64_t n)
 {
     static_assert(sizeof(kmpgpu_stream) == 48, "kmpgpu_stream is the 48-byte record of kmpgpu.h");
-    return streams_read_range(c, "kmpgpu_streams_read", out, c ? c->d_streams : nullptr, sizeof(kmpgpu_stream), first, n, c ? c->n_streams : 0);
+    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_streams_read: ctx is NULL");
+    return streams_read_range(c, "kmpgpu_streams_read", out, c->d_streams, sizeof(kmpgpu_stream), first, n, c->n_streams);
 }
 
 int kmpgpu_stream_map_read(kmpgpu_ctx *c, kmpgpu_stream_pos *out, uint64_t first, uint64_t n)
 {
     static_assert(sizeof(kmpgpu_stream_pos) == 16, "kmpgpu_stream_pos is the 16-byte record of kmpgpu.h");
-    return streams_read_range(c, "kmpgpu_stream_map_read", out, c ? c->d_stream_map : nullptr, sizeof(kmpgpu_stream_pos), first, n,
-                              c ? c->n_stream_map : 0);
+    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_stream_map_read: ctx is NULL");
+    return streams_read_range(c, "kmpgpu_stream_map_read", out, c->d_stream_map, sizeof(kmpgpu_stream_pos), first, n, c->n_stream_map);
 }
 
 int kmpgpu_load_streams_ordered(kmpgpu_ctx *dst, kmpgpu_ctx *src, uint32_t depth, const uint32_t *seq, int on_device, uint64_t *n_streams)
 {
     const char *who = "kmpgpu_load_streams_ordered";
     if (n_streams) *n_streams = 0;
-    if (!dst || !src) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
-    if (dst == src) return fail(KMPGPU_EINVAL, "%s: dst and src are the same context (a context holds one arena)", who);
+    if (const int rc = pair_refused(dst, src, who)) return rc;
     if (depth < 1u || depth > KMPGPU_STREAM_DEPTH_MAX)
         return fail(KMPGPU_EINVAL, "%s: depth %u is not in 1..%u", who, depth, KMPGPU_STREAM_DEPTH_MAX);
     if (on_device != 0 && on_device != 1) return fail(KMPGPU_EINVAL, "%s: on_device %d is neither 0 nor 1", who, on_device);
-    if (dst->device != src->device)
-        return fail(KMPGPU_EINVAL, "%s: the contexts sit on devices %d and %d (streams across devices do not exist)", who, dst->device, src->device);
-    if (dst->fr_pending || src->fr_pending) return fail(KMPGPU_ESTATE, "%s: %s sits between kmpgpu_load_frames_begin and _finish", who, dst->fr_pending ? "dst" : "src");
+    if (const int rc = pair_state_refused(dst, src, who, "streams")) return rc;
     const uint64_t n = src->n_pkts;
     if (n > (1ull << 30)) return fail(KMPGPU_EINVAL, "%s: %llu payloads are more than 2^30 (the composite sort keys)", who, (unsigned long long)n);
     if (!seq && n > 0) return fail(KMPGPU_EINVAL, "%s: seq is NULL", who);
     if (n > 0 && !src->has_meta) return fail(KMPGPU_ESTATE, "%s: src has no metadata (which stream is TCP is read from it)", who);
     if (!src->flows_valid) return fail(KMPGPU_ESTATE, "%s: no flows (no kmpgpu_flows_build since the arena or its metadata were set)", who);
-    HIP_TRY(hipSetDevice(dst->device));
-    HIP_TRY(hipStreamSynchronize(dst->stream));           /* the passes over the arena that is about to be replaced */
-    HIP_TRY(hipStreamSynchronize(src->stream));           /* whatever src's stream still does with its arena */
-    kmpgpu_ctx *c = dst;
-    c->last = kmpgpu_timing{};
-    /* from here on dst's earlier arena is gone, whatever happens */
-    release_arena(c, /* keep_buffers = */ true);
-    if (n == 0) { c->streams_valid = c->stream_order_valid = true; return KMPGPU_OK; }       /* (no stream, no map entry) */
+    return load_streams_call(dst, src, who, depth, /* ordered = */ true, seq, on_device != 0, n_streams);
+}
 
-    /* the scratch of kmpgpu_load_streams, and this call's own: the second sort's and the scans' workspace, the copy of a host seq */
-    const uint64_t sort_bytes = kmp_seam_sort_bytes(n, src->n_flows), seq_bytes = kmp_stream_seq_ws_bytes(n, src->n_flows);
-    if (!sort_bytes || !seq_bytes) return fail(KMPGPU_EHIP, "%s: the sorts of %llu payloads could not be sized", who, (unsigned long long)n);
-    hipError_t e = grow_buffer(&c->fr_ws, &c->fr_ws_cap, (uint64_t)kmp_stream_ws_bytes(n), EIGHTH);
-    if (e == hipSuccess && !c->fr_tot) e = hipMalloc(&c->fr_tot, 2 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = grow_buffer(&c->d_seam_sort, &c->seam_sort_cap, sort_bytes, EIGHTH);
-    if (e == hipSuccess) e = grow_buffer(&c->d_stream_seq_ws, &c->stream_seq_ws_cap, seq_bytes, EIGHTH);
-    if (e == hipSuccess) e = grow_buffer(&c->fr_src, &c->fr_src_cap, 3 * n, EIGHTH);              /* 24 bytes per source payload */
-    if (e == hipSuccess) e = grow_buffer(&c->d_stream_map, &c->stream_map_cap, n, EIGHTH);
-    if (e == hipSuccess) e = grow_buffer(&c->d_stream_segs, &c->stream_segs_cap, n, EIGHTH);
-    if (e == hipSuccess && !on_device) e = grow_buffer(&c->d_stream_seq, &c->stream_seq_cap, n, EIGHTH);
-    if (e != hipSuccess) return alloc_fail(e, "%s: the sorts' and the scans' buffers (%llu payloads) could not be allocated", who, (unsigned long long)n);
-    const uint32_t *d_seq = seq;
-    if (!on_device) {
-        HIP_TRY(upload_split(c->d_stream_seq, reinterpret_cast<const uint8_t *>(seq), n * sizeof(uint32_t), c->stream));
-        d_seq = c->d_stream_seq;
-    }
-    hipEvent_t e1;
-    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_seam_keys(src->d_meta, src->d_flow_of, src->d_flow_recs, n, c->d_seam_sort, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_seam_sort(n, src->n_flows, c->d_seam_sort, (size_t)c->seam_sort_cap, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_stream_phase1(src->d_len, n, c->d_seam_sort, c->fr_ws, c->fr_tot, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    HIP_TRY(hipMemcpyAsync(c->h_small, c->fr_tot, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));         /* (pinned: no staging) */
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    unsigned long long tot[2] = {0, 0};
-    memcpy(tot, c->h_small, sizeof tot);
-    const uint64_t total = tot[0], ns = tot[1];                              /* bytes of all members; streams, at least one */
-    e = grow_buffer(&c->d_streams, &c->streams_cap, ns, EIGHTH);
-    if (e == hipSuccess) e = grow_buffer(&c->d_stream_orders, &c->stream_orders_cap, ns, EIGHTH);
-    if (e == hipSuccess) e = grow_buffer(&c->d_meta, &c->meta_cap, ns, EIGHTH);
-    if (e != hipSuccess) return alloc_fail(e, "%s: the records of %llu streams could not be allocated", who, (unsigned long long)ns);
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_stream_seq_order(src->d_meta, d_seq, n, ns, src->n_flows, c->d_seam_sort, c->fr_ws, c->d_stream_seq_ws,
-                                        (size_t)c->stream_seq_ws_cap, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_stream_seq_scans(src->d_len, n, c->d_seam_sort, c->fr_ws, c->d_stream_seq_ws, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_stream_seq_records(src->d_meta, d_seq, n, total, ns, depth, c->d_seam_sort, c->fr_ws, c->d_stream_seq_ws, c->d_streams,
-                                          c->d_stream_orders, c->d_meta, c->fr_tot, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    /* the second read: the arena's size follows from the cut lengths, which follow from the first read's n_streams */
-    HIP_TRY(hipMemcpyAsync(c->h_small, c->fr_tot, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    memcpy(tot, c->h_small, sizeof tot);
-    const uint64_t arena_bytes = tot[0] + 64;
-    e = ensure_owned_arena(c, arena_bytes, ns, EIGHTH);                      /* (on failure dst is empty and usable) */
-    if (e != hipSuccess)
-        return alloc_fail(e, "%s: an arena of %llu bytes / %llu streams could not be allocated", who, (unsigned long long)(arena_bytes + arena_bytes / 8),
-                          (unsigned long long)(ns + ns / 8));
-    HIP_TRY(hipMemsetAsync(c->owned_arena + tot[0], 0, 64, c->stream));
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_stream_seq_index(src->d_off, src->d_len, n, ns, c->d_seam_sort, c->fr_ws, c->d_stream_seq_ws, c->owned_off, c->owned_len,
-                                        c->d_stream_map, c->d_stream_segs, c->fr_src, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_stream_seq_gather(src->d_arena, c->fr_src, n, tot[0], c->owned_arena, c->nontemporal != 0, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
-    IndexFacts f;
-    int rc = validate_index(c, who, c->owned_off, c->owned_len, ns, arena_bytes, &f);
-    /* kmp_sseq_gather_kernel writes every slot whole: stream, then 0x00 up to the slot's end */
-    if (!rc) rc = install_arena(c, c->owned_arena, c->owned_off, c->owned_len, arena_bytes, ns, f, /* wrote_padding = */ true);
-    if (rc) { release_arena(c, true); return rc; }
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
-    c->last.kernel_ms = ms; c->last.launches = 16;
-    c->has_meta = true;
-    c->n_streams = ns; c->n_stream_map = n; c->streams_valid = c->stream_order_valid = true;
-    if (n_streams) *n_streams = ns;
-    return KMPGPU_OK;
+/* the two reads that exist for streams in sequence order only */
+static int stream_order_read(kmpgpu_ctx *c, const char *who, void *out, const void *list, size_t size, uint64_t first, uint64_t n, uint64_t total)
+{
+    if (c->streams_valid && !c->stream_order_valid) return fail(KMPGPU_ESTATE, "%s: no sequence order (the streams were built by kmpgpu_load_streams)", who);
+    return streams_read_range(c, who, out, list, size, first, n, total);
 }
 
 int kmpgpu_stream_segs_read(kmpgpu_ctx *c, kmpgpu_stream_seg *out, uint64_t first, uint64_t n)
 {
     static_assert(sizeof(kmpgpu_stream_seg) == 16, "kmpgpu_stream_seg is the 16-byte record of kmpgpu.h");
-    const char *who = "kmpgpu_stream_segs_read";
-    if (c && c->streams_valid && !c->stream_order_valid)
-        return fail(KMPGPU_ESTATE, "%s: no sequence order (the streams were built by kmpgpu_load_streams)", who);
-    return streams_read_range(c, who, out, c ? c->d_stream_segs : nullptr, sizeof(kmpgpu_stream_seg), first, n, c ? c->n_stream_map : 0);
+    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_stream_segs_read: ctx is NULL");
+    return stream_order_read(c, "kmpgpu_stream_segs_read", out, c->d_stream_segs, sizeof(kmpgpu_stream_seg), first, n, c->n_stream_map);
 }
 
 int kmpgpu_stream_orders_read(kmpgpu_ctx *c, kmpgpu_stream_order *out, uint64_t first, uint64_t n)
 {
     static_assert(sizeof(kmpgpu_stream_order) == 32, "kmpgpu_stream_order is the 32-byte record of kmpgpu.h");
-    const char *who = "kmpgpu_stream_orders_read";
-    if (c && c->streams_valid && !c->stream_order_valid)
-        return fail(KMPGPU_ESTATE, "%s: no sequence order (the streams were built by kmpgpu_load_streams)", who);
-    return streams_read_range(c, who, out, c ? c->d_stream_orders : nullptr, sizeof(kmpgpu_stream_order), first, n, c ? c->n_streams : 0);
+    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_stream_orders_read: ctx is NULL");
+    return stream_order_read(c, "kmpgpu_stream_orders_read", out, c->d_stream_orders, sizeof(kmpgpu_stream_order), first, n, c->n_streams);
 }
 
 int kmpgpu_scan_enqueue(kmpgpu_ctx *c, void *d_counts_out)
@@ -2686,13 +2546,12 @@ int enqueue_pairing(kmpgpu_ctx *c, const MarkPass &p, int family)
     const bool rel = family == KMPGPU_ALERT_RELATIONS;
     FamilyRows f;
     family_rows(c, p, family, &f);
-    hipEvent_t e1;
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY((rel ? kmp_launch_relations : kmp_launch_chains)(p.d_mat, p.stride, c->n_pkts, rel ? c->d_relations : c->d_chains, (uint32_t)f.n_rows,
-                                                             c->d_patterns, c->d_arena, c->d_fold, c->d_off, c->d_len, c->d_windows,
-                                                             c->whole_payload != 0, (uint32_t)c->cu_count * 8u, f.d_rows, f.d_pc, f.d_any,
-                                                             c->stream));
-    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(profiled(c, [&] {
+        return (rel ? kmp_launch_relations : kmp_launch_chains)(p.d_mat, p.stride, c->n_pkts, rel ? c->d_relations : c->d_chains, (uint32_t)f.n_rows,
+                                                                c->d_patterns, c->d_arena, c->d_fold, c->d_off, c->d_len, c->d_windows,
+                                                                c->whole_payload != 0, (uint32_t)c->cu_count * 8u, f.d_rows, f.d_pc, f.d_any,
+                                                                c->stream);
+    }));
     return KMPGPU_OK;
 }
 
@@ -2701,10 +2560,9 @@ int enqueue_headers(kmpgpu_ctx *c, const MarkPass &p)
 {
     FamilyRows f;
     family_rows(c, p, FAMILY_HEADERS, &f);
-    hipEvent_t e1;
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_headers(c->d_meta, c->d_len, c->n_pkts, p.stride, c->d_headers, (uint32_t)f.n_rows, f.d_rows, f.d_pc, f.d_any, c->stream));
-    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(profiled(c, [&] {
+        return kmp_launch_headers(c->d_meta, c->d_len, c->n_pkts, p.stride, c->d_headers, (uint32_t)f.n_rows, f.d_rows, f.d_pc, f.d_any, c->stream);
+    }));
     return KMPGPU_OK;
 }
 
@@ -2717,12 +2575,11 @@ int enqueue_bytetests(kmpgpu_ctx *c, const MarkPass &p, uint32_t *launches)
     const uint32_t *rel_idx = reinterpret_cast<const uint32_t *>(c->d_bytetests) + (size_t)c->n_bt * 8u;
     for (int relative = 0; relative < 2; relative++) {
         if (relative ? c->n_bt_rel == 0 : c->n_bt_rel == c->n_bt) continue;
-        hipEvent_t e1;
-        HIP_TRY(profile_launch(c, &e1));
-        HIP_TRY(kmp_launch_bytetests(relative != 0, p.d_mat, p.stride, c->n_pkts, c->d_bytetests, c->n_bt, rel_idx, c->n_bt_rel, c->bt_reach,
-                                     c->d_patterns, c->d_arena, c->d_fold, c->d_off, c->d_len, c->d_windows, c->whole_payload != 0,
-                                     (uint32_t)c->cu_count * 8u, f.d_rows, f.d_pc, f.d_any, c->stream));
-        HIP_TRY(profile_launched(c, e1));
+        HIP_TRY(profiled(c, [&] {
+            return kmp_launch_bytetests(relative != 0, p.d_mat, p.stride, c->n_pkts, c->d_bytetests, c->n_bt, rel_idx, c->n_bt_rel, c->bt_reach,
+                                        c->d_patterns, c->d_arena, c->d_fold, c->d_off, c->d_len, c->d_windows, c->whole_payload != 0,
+                                        (uint32_t)c->cu_count * 8u, f.d_rows, f.d_pc, f.d_any, c->stream);
+        }));
         ++*launches;
     }
     return KMPGPU_OK;
@@ -2734,19 +2591,18 @@ int enqueue_regexes(kmpgpu_ctx *c, const MarkPass &p, uint32_t *launches)
 {
     FamilyRows f;
     family_rows(c, p, FAMILY_REGEXES, &f);
-    hipEvent_t e1;
     if (c->n_rx_groups < c->n_rx) {
-        HIP_TRY(profile_launch(c, &e1));
-        HIP_TRY(kmp_launch_regexes(p.d_mat, p.stride, c->n_pkts, c->d_regexes, c->n_rx, c->d_arena, c->d_off, c->d_len, c->whole_payload != 0,
-                                   f.d_rows, f.d_pc, f.d_any, c->stream));
-        HIP_TRY(profile_launched(c, e1));
+        HIP_TRY(profiled(c, [&] {
+            return kmp_launch_regexes(p.d_mat, p.stride, c->n_pkts, c->d_regexes, c->n_rx, c->d_arena, c->d_off, c->d_len, c->whole_payload != 0,
+                                      f.d_rows, f.d_pc, f.d_any, c->stream);
+        }));
         ++*launches;
     }
     if (c->n_rx_groups) {
-        HIP_TRY(profile_launch(c, &e1));
-        HIP_TRY(kmp_launch_regex_groups(p.d_mat, p.stride, c->n_pkts, c->d_regex_groups, c->n_rx_groups, c->d_arena, c->d_off, c->d_len,
-                                        c->whole_payload != 0, f.d_rows, f.d_pc, f.d_any, c->stream));
-        HIP_TRY(profile_launched(c, e1));
+        HIP_TRY(profiled(c, [&] {
+            return kmp_launch_regex_groups(p.d_mat, p.stride, c->n_pkts, c->d_regex_groups, c->n_rx_groups, c->d_arena, c->d_off, c->d_len,
+                                           c->whole_payload != 0, f.d_rows, f.d_pc, f.d_any, c->stream);
+        }));
         ++*launches;
     }
     return KMPGPU_OK;
@@ -2818,9 +2674,9 @@ int enqueue_family(kmpgpu_ctx *c, const char *who, int family, const MarkPass &p
             const int rr = enqueue_links(c, p, /* reduce = */ false, &f->launches);
             if (rr) return rr;
         }
-        HIP_TRY(profile_launch(c, &e1));
-        HIP_TRY(kmp_launch_rules(p.d_mat, p.stride, c->n_pkts, c->d_rule_heads, c->d_rule_quads, c->n_rules, f->d_rows, f->d_pc, f->d_any, c->stream));
-        HIP_TRY(profile_launched(c, e1));
+        HIP_TRY(profiled(c, [&] {
+            return kmp_launch_rules(p.d_mat, p.stride, c->n_pkts, c->d_rule_heads, c->d_rule_quads, c->n_rules, f->d_rows, f->d_pc, f->d_any, c->stream);
+        }));
         f->launches++;
         return KMPGPU_OK;
     }
@@ -3341,7 +3197,6 @@ int kmpgpu_scan_alerts(kmpgpu_ctx *c, int family, uint64_t max_records, uint64_t
     const int rr = enqueue_family(c, "kmpgpu_scan_alerts", family, p, /* profile_reduce = */ true, &f);
     if (rr) return rr;
     uint32_t launches = p.launches + f.launches;
-    hipEvent_t e1;
     /* the list: count, scan (in the scratch kept for kmpgpu_load_frames, as kmpgpu_load_selected uses it), the totals read once, fill */
     hipError_t e = grow_buffer(&c->fr_ws, &c->fr_ws_cap, (uint64_t)kmp_extract_ws_bytes(c->n_pkts), EIGHTH);
     if (e == hipSuccess && !c->fr_tot) e = hipMalloc(&c->fr_tot, 2 * sizeof(unsigned long long));
@@ -3349,12 +3204,8 @@ int kmpgpu_scan_alerts(kmpgpu_ctx *c, int family, uint64_t max_records, uint64_t
         (void)hipStreamSynchronize(c->stream);      /* the pass is under way on the stream; the context stays usable */
         return alloc_fail(e, "kmpgpu_scan_alerts: the scan workspace (%llu bytes) could not be allocated", (unsigned long long)kmp_extract_ws_bytes(c->n_pkts));
     }
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_alerts_count(f.d_rows, p.stride, (uint32_t)f.n_rows, c->n_pkts, f.d_any, c->fr_ws, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_compact_scan(c->n_pkts, c->fr_ws, c->fr_tot, c->stream));
-    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(profiled(c, [&] { return kmp_launch_alerts_count(f.d_rows, p.stride, (uint32_t)f.n_rows, c->n_pkts, f.d_any, c->fr_ws, c->stream); }));
+    HIP_TRY(profiled(c, [&] { return kmp_launch_compact_scan(c->n_pkts, c->fr_ws, c->fr_tot, c->stream); }));
     HIP_TRY(hipMemcpyAsync(c->h_small, c->fr_tot, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));         /* (pinned: no staging) */
     HIP_TRY(hipStreamSynchronize(c->stream));
     unsigned long long tot[2] = {0, 0};
@@ -3364,9 +3215,7 @@ int kmpgpu_scan_alerts(kmpgpu_ctx *c, int family, uint64_t max_records, uint64_t
     if (kept) {
         e = grow_buffer(&c->d_alerts, &c->alerts_cap, kept, EIGHTH);
         if (e != hipSuccess) return alloc_fail(e, "kmpgpu_scan_alerts: the records (%llu bytes) could not be allocated", (unsigned long long)(kept * 16u));
-        HIP_TRY(profile_launch(c, &e1));
-        HIP_TRY(kmp_launch_alerts_fill(f.d_rows, p.stride, (uint32_t)f.n_rows, c->n_pkts, f.d_any, c->fr_ws, c->d_alerts, kept, c->stream));
-        HIP_TRY(profile_launched(c, e1));
+        HIP_TRY(profiled(c, [&] { return kmp_launch_alerts_fill(f.d_rows, p.stride, (uint32_t)f.n_rows, c->n_pkts, f.d_any, c->fr_ws, c->d_alerts, kept, c->stream); }));
         launches += 1u;
     }
     HIP_TRY(hipEventRecord(c->ev[1], c->stream));
@@ -3383,16 +3232,8 @@ int kmpgpu_scan_alerts(kmpgpu_ctx *c, int family, uint64_t max_records, uint64_t
 int kmpgpu_alerts_read(kmpgpu_ctx *c, kmpgpu_alert *out, uint64_t first, uint64_t n)
 {
     if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_alerts_read: ctx is NULL");
-    if (!c->alerts_valid) return fail(KMPGPU_ESTATE, "kmpgpu_alerts_read: no list (no kmpgpu_scan_alerts since the arena or the patterns were set)");
-    if (first > c->alerts_kept || n > c->alerts_kept - first)
-        return fail(KMPGPU_EINVAL, "kmpgpu_alerts_read: records [%llu, +%llu) leave the %llu kept", (unsigned long long)first, (unsigned long long)n,
-                    (unsigned long long)c->alerts_kept);
-    if (n == 0) return KMPGPU_OK;
-    if (!out) return fail(KMPGPU_EINVAL, "kmpgpu_alerts_read: out is NULL");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpyAsync(out, c->d_alerts + first, (size_t)n * sizeof(kmpgpu_alert), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return KMPGPU_OK;
+    return read_range(c, "kmpgpu_alerts_read", c->alerts_valid, "no list (no kmpgpu_scan_alerts since the arena or the patterns were set)", out,
+                      c->d_alerts, sizeof(kmpgpu_alert), first, n, c->alerts_kept, "records", "kept");
 }
 
 int kmpgpu_flows_build(kmpgpu_ctx *c, uint32_t flags, uint64_t *n_flows, kmpgpu_timing *t)
@@ -3421,19 +3262,14 @@ int kmpgpu_flows_build(kmpgpu_ctx *c, uint32_t flags, uint64_t *n_flows, kmpgpu_
     if (e != hipSuccess)
         return alloc_fail(e, "kmpgpu_flows_build: the table (%llu slots) and the ids (%llu payloads) could not be allocated", (unsigned long long)slots,
                           (unsigned long long)n);
-    hipEvent_t e1;
     HIP_TRY(hipEventRecord(c->ev[0], c->stream));
     HIP_TRY(hipMemsetAsync(c->d_flow_table, 0, (size_t)slots * sizeof(uint32_t), c->stream));
     HIP_TRY(hipMemsetAsync(c->d_flow_first, 0xFF, (size_t)slots * sizeof(uint32_t), c->stream));
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_flows_insert(c->d_meta, n, (flags & KMPGPU_FLOW_DIRECTED) != 0, c->d_flow_table, slots, c->d_flow_first, c->d_flow_of, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_flows_firsts(c->d_flow_first, c->d_flow_of, n, c->fr_ws, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_compact_scan(n, c->fr_ws, c->fr_tot, c->stream));
-    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(profiled(c, [&] {
+        return kmp_launch_flows_insert(c->d_meta, n, (flags & KMPGPU_FLOW_DIRECTED) != 0, c->d_flow_table, slots, c->d_flow_first, c->d_flow_of, c->stream);
+    }));
+    HIP_TRY(profiled(c, [&] { return kmp_launch_flows_firsts(c->d_flow_first, c->d_flow_of, n, c->fr_ws, c->stream); }));
+    HIP_TRY(profiled(c, [&] { return kmp_launch_compact_scan(n, c->fr_ws, c->fr_tot, c->stream); }));
     HIP_TRY(hipMemcpyAsync(c->h_small, c->fr_tot, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));         /* (pinned: no staging) */
     HIP_TRY(hipStreamSynchronize(c->stream));
     unsigned long long tot[2] = {0, 0};
@@ -3442,12 +3278,8 @@ int kmpgpu_flows_build(kmpgpu_ctx *c, uint32_t flags, uint64_t *n_flows, kmpgpu_
     if (nf == 0 || nf > n) return fail(KMPGPU_EHIP, "kmpgpu_flows_build: %llu flows for %llu payloads", (unsigned long long)nf, (unsigned long long)n);
     e = grow_buffer(&c->d_flow_recs, &c->flow_recs_cap, nf, EIGHTH);
     if (e != hipSuccess) return alloc_fail(e, "kmpgpu_flows_build: the records (%llu flows) could not be allocated", (unsigned long long)nf);
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_flows_number(c->d_meta, n, c->fr_ws, c->d_flow_of, c->d_flow_table, c->d_flow_recs, c->stream));
-    HIP_TRY(profile_launched(c, e1));
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_flows_assign(c->d_flow_table, c->d_flow_of, c->d_len, n, c->d_flow_recs, c->stream));
-    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(profiled(c, [&] { return kmp_launch_flows_number(c->d_meta, n, c->fr_ws, c->d_flow_of, c->d_flow_table, c->d_flow_recs, c->stream); }));
+    HIP_TRY(profiled(c, [&] { return kmp_launch_flows_assign(c->d_flow_table, c->d_flow_of, c->d_len, n, c->d_flow_recs, c->stream); }));
     HIP_TRY(hipEventRecord(c->ev[1], c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (t) {
@@ -3460,34 +3292,22 @@ int kmpgpu_flows_build(kmpgpu_ctx *c, uint32_t flags, uint64_t *n_flows, kmpgpu_
     return KMPGPU_OK;
 }
 
-namespace {
-
-/* what kmpgpu_flows_read and kmpgpu_flow_ids_read share: elements [first, first + n) of `total`, `size` bytes each, from src to out */
-int flows_read_range(kmpgpu_ctx *c, const char *who, void *out, const void *src, size_t size, uint64_t first, uint64_t n, uint64_t total)
+/* what kmpgpu_flows_read and kmpgpu_flow_ids_read share */
+static int flows_read_range(kmpgpu_ctx *c, const char *who, void *out, const void *list, size_t size, uint64_t first, uint64_t n, uint64_t total)
 {
-    if (!c) return fail(KMPGPU_EINVAL, "%s: ctx is NULL", who);
-    if (!c->flows_valid) return fail(KMPGPU_ESTATE, "%s: no flows (no kmpgpu_flows_build since the arena or its metadata were set)", who);
-    if (first > total || n > total - first)
-        return fail(KMPGPU_EINVAL, "%s: elements [%llu, +%llu) leave the %llu there are", who, (unsigned long long)first, (unsigned long long)n,
-                    (unsigned long long)total);
-    if (n == 0) return KMPGPU_OK;
-    if (!out) return fail(KMPGPU_EINVAL, "%s: out is NULL", who);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpyAsync(out, (const uint8_t *)src + first * size, (size_t)n * size, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return KMPGPU_OK;
+    return read_range(c, who, c->flows_valid, "no flows (no kmpgpu_flows_build since the arena or its metadata were set)", out, list, size, first, n, total);
 }
-
-}  // namespace
 
 int kmpgpu_flows_read(kmpgpu_ctx *c, kmpgpu_flow *out, uint64_t first, uint64_t n)
 {
-    return flows_read_range(c, "kmpgpu_flows_read", out, c ? c->d_flow_recs : nullptr, sizeof(kmpgpu_flow), first, n, c ? c->n_flows : 0);
+    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_flows_read: ctx is NULL");
+    return flows_read_range(c, "kmpgpu_flows_read", out, c->d_flow_recs, sizeof(kmpgpu_flow), first, n, c->n_flows);
 }
 
 int kmpgpu_flow_ids_read(kmpgpu_ctx *c, uint32_t *out, uint64_t first, uint64_t n)
 {
-    return flows_read_range(c, "kmpgpu_flow_ids_read", out, c ? c->d_flow_of : nullptr, sizeof(uint32_t), first, n, c && c->flows_valid ? c->n_pkts : 0);
+    if (!c) return fail(KMPGPU_EINVAL, "kmpgpu_flow_ids_read: ctx is NULL");
+    return flows_read_range(c, "kmpgpu_flow_ids_read", out, c->d_flow_of, sizeof(uint32_t), first, n, c->n_pkts);
 }
 
 /* The body of kmpgpu_scan_flows, and of kmpgpu_scan_flows_seams where sm is given: the context whose seam list (checked by the caller)
@@ -3550,9 +3370,9 @@ static int scan_flows_body(kmpgpu_ctx *c, const char *who, kmpgpu_ctx *sm, int f
     if (seams) {
         /* the same kernel a second time: its output is an atomic OR into the matrix zeroed above */
         HIP_TRY(hipStreamSynchronize(sm->stream));                  /* the seams' pass has landed in its matrix */
-        HIP_TRY(profile_launch(c, &e1));
-        HIP_TRY(kmp_launch_flows_fold(ps.d_mat, ps.stride, c->n_pat, sm->n_pkts, fs.d_any, sm->d_seam_flow, c->n_flows, c->d_flow_fold, Sf, c->stream));
-        HIP_TRY(profile_launched(c, e1));
+        HIP_TRY(profiled(c, [&] {
+            return kmp_launch_flows_fold(ps.d_mat, ps.stride, c->n_pat, sm->n_pkts, fs.d_any, sm->d_seam_flow, c->n_flows, c->d_flow_fold, Sf, c->stream);
+        }));
     }
     HIP_TRY(profile_launch(c, &e1));
     if (per_flow)
@@ -3645,31 +3465,22 @@ int kmpgpu_scan_flowbits(kmpgpu_ctx *c, uint64_t *rule_pkt_counts_out, uint64_t 
     unsigned long long *d_before = c->d_fb_out, *d_alert = d_before + nb * p.stride, *d_pc = d_alert + nr * p.stride, *d_any = d_pc + nr;
     HIP_TRY(hipMemsetAsync(d_before32, 0, (size_t)(4u * (n + nf)), c->stream));
     HIP_TRY(hipMemsetAsync(c->d_fb_out, 0, (size_t)out_words * sizeof(unsigned long long), c->stream));
-    hipEvent_t e1;
     if (!ordered) {
-        HIP_TRY(profile_launch(c, &e1));
-        HIP_TRY(kmp_launch_flowbits_order(c->d_flow_of, n, nf, c->d_fb_order, (size_t)c->fb_order_cap, c->stream));
-        HIP_TRY(profile_launched(c, e1));
+        HIP_TRY(profiled(c, [&] { return kmp_launch_flowbits_order(c->d_flow_of, n, nf, c->d_fb_order, (size_t)c->fb_order_cap, c->stream); }));
         c->fb_order_valid = true; c->fb_order_gen = c->flows_gen;
         launches += 2u;
     }
     for (size_t l = 0; l < c->fb_level_mask.size(); l++) {
         const uint32_t first = c->fb_level_first[l], n_act = c->fb_level_first[l + 1] - first;
         if (n_act == 0) continue;                   /* bits that are tested only: 0 for ever */
-        HIP_TRY(profile_launch(c, &e1));
-        HIP_TRY(kmp_launch_flowbits_build(f.d_rows, p.stride, n, c->d_fb_acting + 2u * (size_t)first, n_act, d_before32, c->d_fb_order, c->d_fb_ws, c->stream));
-        HIP_TRY(profile_launched(c, e1));
-        HIP_TRY(profile_launch(c, &e1));
-        HIP_TRY(kmp_launch_flowbits_scan(n, c->d_flow_of, c->d_fb_order, c->d_fb_ws, d_before32, d_flow_state, &launches, c->stream));
-        HIP_TRY(profile_launched(c, e1));
-        HIP_TRY(profile_launch(c, &e1));
-        HIP_TRY(kmp_launch_flowbits_rows(d_before32, n, c->fb_level_mask[l], p.stride, d_before, c->stream));
-        HIP_TRY(profile_launched(c, e1));
+        HIP_TRY(profiled(c, [&] {
+            return kmp_launch_flowbits_build(f.d_rows, p.stride, n, c->d_fb_acting + 2u * (size_t)first, n_act, d_before32, c->d_fb_order, c->d_fb_ws, c->stream);
+        }));
+        HIP_TRY(profiled(c, [&] { return kmp_launch_flowbits_scan(n, c->d_flow_of, c->d_fb_order, c->d_fb_ws, d_before32, d_flow_state, &launches, c->stream); }));
+        HIP_TRY(profiled(c, [&] { return kmp_launch_flowbits_rows(d_before32, n, c->fb_level_mask[l], p.stride, d_before, c->stream); }));
         launches += 2u;
     }
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_flowbits_final(f.d_rows, d_before, p.stride, c->d_fb_tests, c->n_rules, d_alert, d_pc, d_any, c->stream));
-    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(profiled(c, [&] { return kmp_launch_flowbits_final(f.d_rows, d_before, p.stride, c->d_fb_tests, c->n_rules, d_alert, d_pc, d_any, c->stream); }));
     launches++;
     HIP_TRY(hipEventRecord(c->ev[1], c->stream));
     if (rule_pkt_counts_out) HIP_TRY(hipMemcpyAsync(rule_pkt_counts_out, d_pc, (size_t)nr * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
@@ -3762,9 +3573,7 @@ int kmpgpu_scan_thresholds(kmpgpu_ctx *c, const uint64_t *ts, int ts_on_device, 
     if (c->thr_windowed) {
         if (ts_on_device) HIP_TRY(hipMemcpyAsync(d_T, ts, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
         else HIP_TRY(upload_split(d_T, reinterpret_cast<const uint8_t *>(ts), n * sizeof(uint64_t), c->stream));
-        HIP_TRY(profile_launch(c, &e1));
-        HIP_TRY(kmp_launch_thresholds_time(d_T, n, d_agg, &launches, c->stream));
-        HIP_TRY(profile_launched(c, e1));
+        HIP_TRY(profiled(c, [&] { return kmp_launch_thresholds_time(d_T, n, d_agg, &launches, c->stream); }));
     }
     for (int x = 0; x < 3; x++) {
         if (!used[x]) continue;
@@ -3781,9 +3590,7 @@ int kmpgpu_scan_thresholds(kmpgpu_ctx *c, const uint64_t *ts, int ts_on_device, 
             launches += 2u;
         }
         if (d_Ts[x]) {
-            HIP_TRY(profile_launch(c, &e1));
-            HIP_TRY(kmp_launch_thresholds_tsort(d_T, *order_buf[x], n, d_Ts[x], c->stream));
-            HIP_TRY(profile_launched(c, e1));
+            HIP_TRY(profiled(c, [&] { return kmp_launch_thresholds_tsort(d_T, *order_buf[x], n, d_Ts[x], c->stream); }));
             launches++;
         }
     }
@@ -3793,19 +3600,15 @@ int kmpgpu_scan_thresholds(kmpgpu_ctx *c, const uint64_t *ts, int ts_on_device, 
         for (const uint32_t q : c->thr_by_track[track]) {
             const kmpgpu_threshold &th = c->thr[q];
             const unsigned long long *row = f.d_rows + (uint64_t)th.rule * p.stride;
-            HIP_TRY(profile_launch(c, &e1));
-            HIP_TRY(kmp_launch_thresholds_count(row, n, ob, d_C, d_agg, &launches, c->stream));
-            HIP_TRY(profile_launched(c, e1));
-            HIP_TRY(profile_launch(c, &e1));
-            HIP_TRY(kmp_launch_thresholds_pass(row, n, ob, Ts, d_C, th.type, th.count, th.window, d_pass + (uint64_t)q * p.stride,
-                                               window_counts_out ? c->d_thr_wc + (uint64_t)q * n : nullptr, c->stream));
-            HIP_TRY(profile_launched(c, e1));
+            HIP_TRY(profiled(c, [&] { return kmp_launch_thresholds_count(row, n, ob, d_C, d_agg, &launches, c->stream); }));
+            HIP_TRY(profiled(c, [&] {
+                return kmp_launch_thresholds_pass(row, n, ob, Ts, d_C, th.type, th.count, th.window, d_pass + (uint64_t)q * p.stride,
+                                                  window_counts_out ? c->d_thr_wc + (uint64_t)q * n : nullptr, c->stream);
+            }));
             launches++;
         }
     }
-    HIP_TRY(profile_launch(c, &e1));
-    HIP_TRY(kmp_launch_thresholds_final(f.d_rows, d_pass, p.stride, c->d_thr_table, c->n_rules, d_alert, d_pc, d_any, c->stream));
-    HIP_TRY(profile_launched(c, e1));
+    HIP_TRY(profiled(c, [&] { return kmp_launch_thresholds_final(f.d_rows, d_pass, p.stride, c->d_thr_table, c->n_rules, d_alert, d_pc, d_any, c->stream); }));
     launches++;
     HIP_TRY(hipEventRecord(c->ev[1], c->stream));
     if (rule_pkt_counts_out) HIP_TRY(hipMemcpyAsync(rule_pkt_counts_out, d_pc, (size_t)nr * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
